@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — batched FFT cross-correlation throughput on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (asx_xcorr_batch_f32_dev: rfft, rfft, conj-multiply, irfft,
 |.|-argmax with exact re-evaluation of near-ties, Pearson) over one batch of synthetic 48 kHz mono
@@ -51,6 +51,7 @@ CONFIG4_BATCH, CONFIG4_N = 8192, 480000
 CONFIG4_SPEEDUP_BASIS = ("config4.value(n_gpus = N) / config4.value(n_gpus = 1) of the same sweep: a fixed batch of %d pairs of "
                          "N = %d block-partitioned over the ranks, result all-gather inside the timed region" % (CONFIG4_BATCH, CONFIG4_N))
 SEED = 20260101
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this much in all
 
 
 # --------------------------------------------------------------------------------------------------
@@ -574,6 +575,16 @@ class Workload:
             info["coef_pairs_compared"] = int(t[1])
         return ok, info
 
+    def outputs(self):
+        """what the last step left for a caller of the path, pair by pair in pair-id order (every rank's pairs, as the gather
+        delivered them): lag, coefficient and ret, widened to float64 (exact for all three) and copied to the host"""
+        if self.multi:
+            counts = [self.sharding.shard_range(self.total, r, self.world)[1] for r in range(self.world)]
+            cols = [self.torch.cat([self.gathered[1][r][j][:counts[r]] for r in range(self.world)]) for j in range(3)]
+        else:
+            cols = [self.d_lag[: self.count], self.d_coef[: self.count], self.d_ret[: self.count]]
+        return {name: t.double().cpu().numpy() for name, t in zip(("lag", "coefficient", "ret"), cols)}
+
     def kernel_medians(self, steps, lead=0):
         """per-kernel HIP-event durations of `steps` CONSECUTIVE steps behind `lead` untimed ones (the profiling ring keeps
         the last `steps` calls): medians.  Called right behind the timed region, so the window is as pre-conditioned as
@@ -631,6 +642,21 @@ def load_baseline_line(path):
         return None
 
 
+def dump_outputs(path, outputs):
+    """--dump-outputs: DIR/<name>.npy per output array (float64) and DIR/pair.npy, the pair ids they hold.  Over
+    DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of pairs."""
+    import numpy as np
+    pairs = len(outputs["lag"])
+    keep = (DUMP_LIMIT_BYTES - 4096) // (8 * (len(outputs) + 1))     # 4096: room for the .npy headers
+    idx = np.arange(pairs)
+    if pairs > keep:
+        idx = np.sort(np.random.default_rng(SEED).choice(pairs, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "pair.npy"), idx.astype(np.float64))
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a[idx])
+
+
 def run_rank(args, cpu=None):
     import torch
     import torch.distributed as dist
@@ -680,6 +706,7 @@ def run_rank(args, cpu=None):
         # Rounds 1 and 2 reported the first form as `value`, round 3 and later the second.
         dt_cold = w.timed(args.steps, args.warmup, 0)
         dt = w.timed(args.steps, args.warmup, pre)
+        outputs = w.outputs() if args.dump_outputs else None
         prof_steps = args.profile_steps or max(20, args.steps)
         med, spread, series = w.kernel_medians(prof_steps, lead=10 if args.profile_steps == 0 else 0)
         dt_local = w.last_dt_local
@@ -833,6 +860,8 @@ def run_rank(args, cpu=None):
     if rank == 0:
         if cpu is not None:
             line["cpu_baseline"] = cpu
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(line), flush=True)
     if multi:
         dist.barrier()
@@ -865,7 +894,13 @@ def main():
     ap.add_argument("--mode", default="batched", choices=["batched", "streaming", "single", "capi"],
                     help="batched = the headline workload (default); streaming = BASELINE config 5 "
                          "(growing window 3..30 s, plan reuse); single = config 2 (one pair, latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline workload computed as DIR/<name>.npy (float64): lag, "
+                         "coefficient and ret of every pair, and pair (their pair ids); the inputs are seeded, so two builds "
+                         "compare output for output")
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode != "batched" or args.dry_run):
+        ap.error("--dump-outputs needs the headline workload (--mode batched, no --dry-run)")
     if args.mode == "capi":      # child of rank 0 (capi_leg_guarded): config4 through asx_comm_create / asx_xcorr_batch_multi_dev
         print(json.dumps(capi_leg(args.gpus, args.steps4)), flush=True)
         return 0

@@ -72,3 +72,33 @@ def test_gpus_8_the_node_size_of_baseline_config_4():
     assert c4["scaling"] == "strong" and c4["n_gpus"] == 8 and c4["pairs_per_gpu"] == 1024 and c4["pairs_total"] == 8192
     assert "n_gpus = 1" in c4["speedup_basis"] and c4["record_bytes_per_rank"] == 1024 * 20
     assert line["scaling"] == "weak"
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_above_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one DIR/<name>.npy per output plus DIR/pair.npy; over the size limit every array holds the same seeded
+    sample of pairs, the same in every run"""
+    import numpy as np
+    import bench
+    outputs = {"lag": np.arange(100, dtype=np.float64) - 50, "coefficient": np.linspace(-1, 1, 100), "ret": np.zeros(100)}
+    bench.dump_outputs(str(tmp_path / "all"), outputs)
+    for name in ("pair", "lag", "coefficient", "ret"):
+        a = np.load(tmp_path / "all" / (name + ".npy"))
+        assert a.dtype == np.float64 and a.shape == (100,)
+    assert np.array_equal(np.load(tmp_path / "all" / "lag.npy"), outputs["lag"])
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 4 * 8 * 10)
+    bench.dump_outputs(str(tmp_path / "a"), outputs)
+    bench.dump_outputs(str(tmp_path / "b"), outputs)
+    pair = np.load(tmp_path / "a" / "pair.npy")
+    assert pair.shape == (10,) and np.all(np.diff(pair) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "lag.npy"), outputs["lag"][pair.astype(int)])
+    assert np.array_equal(np.load(tmp_path / "a" / "coefficient.npy"), outputs["coefficient"][pair.astype(int)])
+    for name in ("pair", "lag", "coefficient", "ret"):
+        assert np.array_equal(np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy")))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_dump_outputs_is_refused_where_there_is_no_timed_path(tmp_path):
+    for extra in (["--dry-run"], ["--mode", "streaming"]):
+        p, line = run_bench("--dump-outputs", str(tmp_path / "out"), *extra)
+        assert p.returncode == 2 and line is None and "--dump-outputs" in p.stderr, p.stderr[-2000:]
+    assert not os.path.exists(tmp_path / "out")

@@ -63,6 +63,33 @@ def test_bench_prints_exactly_one_json_line_on_stdout():
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
 
 
+def test_bench_dump_outputs_hold_what_the_timed_path_computed(tmp_path):
+    """--dump-outputs: after the timed steps, every pair's lag / coefficient / ret of the last one, in pair-id order -- the
+    oracle's answers on the same seeded pairs"""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import oracle
+    import bench
+    n, batch = 144000, 8
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--precondition", "2", "--sample-len", str(n), "--batch", str(batch), "--no-cpu", "--no-config4",
+                        "--no-single", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["results_ok"] and d["steps"] == 3 and d["ms_per_step"] > 0
+    a = {name: np.load(out / (name + ".npy")) for name in ("pair", "lag", "coefficient", "ret")}
+    assert all(v.dtype == np.float64 and v.shape == (batch,) for v in a.values())
+    assert np.array_equal(a["pair"], np.arange(batch))
+    for i in range(batch):
+        src, smp, true_lag = oracle.synth_pair(bench.SEED, i, n, 1)
+        o_ret, o_lag, o_coef = oracle.cross_correlation(src, smp)
+        assert a["ret"][i] == o_ret == 0 and a["lag"][i] == o_lag == true_lag, (i, a["ret"][i], a["lag"][i], o_lag, true_lag)
+        assert abs(a["coefficient"][i] - o_coef) < bench.COEF_TOL, (i, a["coefficient"][i], o_coef)
+
+
 def test_bench_rank_path_with_the_capi_leg_as_a_child_process():
     """the N > 1 form of bench.py on the one GPU there is: a rank under torch.distributed.run (ASX_BENCH_FORCE_DIST=1: process
     group, RCCL gather, the gloo group the idle ranks wait in) whose config4_capi leg runs as a CHILD process with a time limit
