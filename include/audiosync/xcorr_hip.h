@@ -172,6 +172,28 @@ int asx_xcorr_batch_f32_dev(asx_plan *plan, const float *d_source, const float *
                             size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret,
                             void *stream);
 
+/* Strided batches: one track against many.  Pair i (0 <= i < batch) is source = d_source + i*source_stride (2N floats),
+ * sample = d_sample + i*sample_stride (N floats); strides are in floats.  A stride of 0 broadcasts one track to every pair
+ * (one source against many samples, one sample against many sources; both 0 is legal); on real-column plans
+ * (asx_plan_layout() == 1) its forward column transform then runs ONCE per call, into a plan-owned workspace that every launch
+ * group reads, not once per pair or per launch group.  Strides below the track length are allowed (overlapping windows of one
+ * long recording: source_stride = hop, sample_stride = 0): the inputs are only read.
+ *   Results: per pair, bit for bit what asx_xcorr_batch_f32_dev returns on the materialised contiguous pairs on the same plan --
+ * lag, coef and ret, both Pearson forms, exact mode on or off (the second look at overflowed pairs, ret = 1 in the asynchronous
+ * mode), and the overflow, repair and Pearson-mode counters, which count every pair as that call would.  d_lag and d_ret may
+ * be NULL.  Same stream rule as asx_xcorr_batch_f32_dev; this call never tunes placement ("measure" plans).
+ *   Layout rule.  Real-column plans read every row of a pair's inputs with 16-byte float4 loads starting at the pair's first
+ * frame, so both base pointers must be 16-byte aligned and every NONZERO stride a multiple of 4 floats; otherwise the call
+ * returns -1 (asx_last_error() says which) before anything is launched and the outputs are untouched.  Packed plans (every
+ * other length, or $ASX_LAYOUT=packed) take any float-aligned pointer and any stride: their loads fall back to 4-byte loads
+ * where a pair's inputs are not 16-byte aligned; they transform each pair's inputs, a broadcast track included.
+ *   The broadcast workspace ((M1+1)*M2 complex values per operand, plus norm and band partials) is allocated at the first call
+ * with a stride of 0 and kept with the plan.  That first call must not be made while `stream` is being captured into a graph:
+ * it returns -1 instead of allocating. */
+int asx_xcorr_strided_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                              const float *d_sample, size_t sample_stride, size_t batch,
+                              int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream);
+
 /* The batched variant over several GPUs of one node from ONE process (BASELINE.json north_star; no
  * reference equivalent): plans[i] was created on device i (any devices; all the same sample_len); the
  * batch is block-partitioned over the plans, each block runs concurrently on its device, results come

@@ -121,6 +121,14 @@ struct asx_plan {
         double *stats = nullptr;     // {mean of source, sum of sample, their product = the shift of r}
         size_t cap = 0;
     } big;
+    // Broadcast slot of asx_xcorr_strided_f32_dev (real-column plans, lazy, like BigPeak): the forward column pass of a track that
+    // every pair of a call shares (a stride of 0) -- C_x / C_y of ONE pair, its norm partials and band sums in the AsxPeakWs layout
+    // of pair 0 -- written once per call before the launch groups, read by every group's row kernel (k_rows_rb)
+    struct Bcast {
+        float2 *cx = nullptr, *cy = nullptr;
+        float *nrm = nullptr;
+        float2 *band = nullptr;
+    } bslot;
     // pairs whose near-tie list overflowed since the list was last emptied (k_finalize appends, resolve_overflows reads)
     uint32_t *over_list = nullptr, *over_n = nullptr;
     volatile uint32_t *h_over_n = nullptr; // page-locked host mirror of *over_n (device-visible: AsxPeakWs::over_host)
@@ -670,13 +678,16 @@ static int run_group(asx_plan *p, const float *d_src, const float *d_smp, const 
 // It runs on `s` behind everything the call has launched (the lanes have been joined), in the workspace slot 0 of
 // lane 0 and the plan's one set of big lists: nothing else is in flight on this plan (one stream at a time per plan).
 // The pointers are the bases the list's indices count from: pair i of the list is f_src + i * 2N etc.
+// sp / mp: the pair steps of the source and the sample (asx_xcorr_strided_f32_dev; SIZE_MAX = the contiguous 2N and N).
 template <typename TIn>
 static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_src, const TIn *p_smp, int64_t *d_lag,
-                       double *d_coef, int32_t *d_ret, hipStream_t s)
+                       double *d_coef, int32_t *d_ret, hipStream_t s, size_t sp = SIZE_MAX, size_t mp = SIZE_MAX)
 {
     const AsxDev &P = p->dev;
     asx_plan::Lane &W = p->lanes[0];
     const size_t N = p->host.N;
+    if (sp == SIZE_MAX) sp = 2 * N;
+    if (mp == SIZE_MAX) mp = N;
     asx_plan::BigPeak &B = p->big;
     if (!B.cand) {
         // into a local first: a failed allocation must not leave half a set behind for the next call
@@ -700,23 +711,23 @@ static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_s
     HIP_TRY(hipMemsetAsync(B.cand_n, 0, sizeof(uint32_t), s));
     // r = r' + stats[2]
     if (sizeof(TIn) == sizeof(float))
-        asx_launch_dc_remove_f32((const float *)p_src + i * 2 * N, (const float *)p_smp + i * N, P.N, (double)P.F, B.stats, B.src_dc, s);
+        asx_launch_dc_remove_f32((const float *)p_src + i * sp, (const float *)p_smp + i * mp, P.N, (double)P.F, B.stats, B.src_dc, s);
     else
-        asx_launch_dc_remove_f64((const double *)p_src + i * 2 * N, (const double *)p_smp + i * N, P.N, (double)P.F, B.stats, B.src_dc, s);
+        asx_launch_dc_remove_f64((const double *)p_src + i * sp, (const double *)p_smp + i * mp, P.N, (double)P.F, B.stats, B.src_dc, s);
     K.shift = B.stats + 2;
-    asx_launch_fwd_cols(P, B.src_dc, f_smp + i * N, W.zxa, W.zya, K, 1, s);
+    asx_launch_fwd_cols(P, B.src_dc, f_smp + i * mp, W.zxa, W.zya, K, 1, s);
     asx_launch_rows(P, W.zxa, W.zya, W.ga, K, 1, s);
     asx_launch_inv_cols(P, W.ga, K, nullptr, 1, s);
     asx_launch_finalize(P, K, W.seg, 1, s);
     if (sizeof(TIn) == sizeof(float))
-        asx_launch_refine_f32(P, (const float *)p_src + i * 2 * N, (const float *)p_smp + i * N, K, W.seg, 1, s, 2048);
+        asx_launch_refine_f32(P, (const float *)p_src + i * sp, (const float *)p_smp + i * mp, K, W.seg, 1, s, 2048);
     else
-        asx_launch_refine_f64(P, (const double *)p_src + i * 2 * N, (const double *)p_smp + i * N, K, W.seg, 1, s, 2048);
+        asx_launch_refine_f64(P, (const double *)p_src + i * sp, (const double *)p_smp + i * mp, K, W.seg, 1, s, 2048);
     if (sizeof(TIn) == sizeof(float))
-        asx_launch_pearson_f32((const float *)p_src + i * 2 * N, (const float *)p_smp + i * N, 2 * N, N, P.N,
+        asx_launch_pearson_f32((const float *)p_src + i * sp, (const float *)p_smp + i * mp, 2 * N, N, P.N,
                                W.seg, W.psums, d_lag ? d_lag + i : nullptr, d_coef + i, d_ret ? d_ret + i : nullptr, 1, s);
     else
-        asx_launch_pearson_f64((const double *)p_src + i * 2 * N, (const double *)p_smp + i * N, 2 * N, N, P.N,
+        asx_launch_pearson_f64((const double *)p_src + i * sp, (const double *)p_smp + i * mp, 2 * N, N, P.N,
                                W.seg, W.psums, d_lag ? d_lag + i : nullptr, d_coef + i, d_ret ? d_ret + i : nullptr, 1, s);
     HIP_TRY(hipGetLastError());
     p->repaired++;
@@ -728,7 +739,7 @@ static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_s
 // only when a pair overflows -- no device-to-host copy sits between the last kernel and the host.
 template <typename TIn>
 static int resolve_overflows(asx_plan *p, const float *f_smp, const TIn *p_src, const TIn *p_smp, int64_t *d_lag,
-                             double *d_coef, int32_t *d_ret, hipStream_t s)
+                             double *d_coef, int32_t *d_ret, hipStream_t s, size_t sp = SIZE_MAX, size_t mp = SIZE_MAX)
 {
     HIP_TRY(hipStreamSynchronize(s));
     if (p->lanes[0].pk.cap >= 2 * p->host.N) return 0; // the ordinary list already holds every lag
@@ -747,7 +758,7 @@ static int resolve_overflows(asx_plan *p, const float *f_smp, const TIn *p_src, 
     HIP_TRY(hipStreamSynchronize(s));
     *p->h_over_n = 0;
     for (uint32_t k = 0; k < n; k++)
-        if (second_look<TIn>(p, p->h_over[k], f_smp, p_src, p_smp, d_lag, d_coef, d_ret, s)) return -1;
+        if (second_look<TIn>(p, p->h_over[k], f_smp, p_src, p_smp, d_lag, d_coef, d_ret, s, sp, mp)) return -1;
     return (int)n;
 }
 
@@ -876,6 +887,143 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
         if (p->exact &&
             resolve_overflows<float>(p, d_sample + w0 * N, d_source + w0 * 2 * N, d_sample + w0 * N,
                                      d_lag ? d_lag + w0 : nullptr, d_coef + w0, d_ret ? d_ret + w0 : nullptr, s) < 0)
+            return -1;
+    }
+    prof_end_call(p, gi);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// strided batches: one track against many (asx_xcorr_strided_f32_dev)
+// ---------------------------------------------------------------------------
+// One group of a strided call: pair k = source d_src + k*ss, sample d_smp + k*ms.  bc bit 0 / 1: the source / sample is the call's
+// broadcast track, whose forward column pass is already in the plan's slot (real-column plans): only the other operand is
+// transformed here.  Everything behind the transforms is run_group's, with the caller's strides where the inputs are read again.
+static int run_group_strided(asx_plan *p, const float *d_src, size_t ss, const float *d_smp, size_t ms, size_t g, int bc,
+                             int64_t *d_lag, double *d_coef, int32_t *d_ret, hipStream_t s, size_t group_index, int lane,
+                             uint32_t pair_base, bool listed)
+{
+    const AsxDev &P = p->dev;
+    asx_plan::Lane &W = p->lanes[lane];
+    AsxPeakWs fin = W.pk;
+    if (!listed) { fin.over_list = nullptr; fin.over_n = nullptr; fin.over_host = nullptr; fin.over_cap = 0; }
+    const bool spectral = p->spectral && W.pk.band;
+    AsxPeakWs tk = W.pk;
+    if (!spectral) { tk.band = nullptr; tk.tile_peak = nullptr; }
+    const size_t e0 = group_index * 6;
+    if (prof_mark(p, s, e0 + 0)) return -1;
+    if (P.rlayout) {
+        const int op0 = (bc & 1) ? 1 : 0, nops = 2 - (bc & 1) - ((bc >> 1) & 1);
+        if (nops > 0 &&
+            !asx_launch_fwd_cols_r1(P, d_src, ss, d_smp, ms, W.zxa, W.zya, W.pk.nrm_part, tk.band, (int)g, op0, nops, false, s))
+            return fail("internal: no forward column kernel for this plan");
+        for (unsigned which = 0; which < 2; which++)
+            if (bc & (1 << which)) asx_launch_bcast_aux(P, p->bslot.nrm, p->bslot.band, W.pk.nrm_part, tk.band, (int)g, which, s);
+    } else {
+        // packed plans: the contiguous forward kernel once per pair at the pair's own inputs (no broadcast slot: every pair
+        // transforms its own copy of a shared track)
+        for (size_t k = 0; k < g; k++) {
+            AsxPeakWs one = tk;
+            one.nrm_part = W.pk.nrm_part + k * 2 * (size_t)P.ntiles;
+            asx_launch_fwd_cols(P, d_src + k * ss, d_smp + k * ms, W.zxa + k * (size_t)P.M, W.zya + k * (size_t)P.M, one, 1, s);
+        }
+    }
+    if (prof_mark(p, s, e0 + 1)) return -1;
+    if (P.rlayout) {
+        if (!asx_launch_rows_rb(P, (bc & 1) ? p->bslot.cx : W.zxa, (bc & 2) ? p->bslot.cy : W.zya, W.ga, tk, (int)g, bc, s))
+            return fail("internal: no row kernel for this plan");
+    } else {
+        asx_launch_rows(P, W.zxa, W.zya, W.ga, tk, (int)g, s);
+    }
+    if (prof_mark(p, s, e0 + 2)) return -1;
+    asx_launch_inv_cols(P, W.ga, tk, nullptr, (int)g, s);
+    if (prof_mark(p, s, e0 + 3)) return -1;
+    asx_launch_finalize(P, fin, W.seg, (int)g, s, pair_base);
+    const int dot_blocks = (int)std::min<size_t>(ASX_DOT_BLOCKS, std::max<size_t>(8, 16384 / g));
+    asx_launch_refine_f32_strided(P, d_src, ss, d_smp, ms, W.pk, W.seg, (int)g, s, dot_blocks, !spectral);
+    if (prof_mark(p, s, e0 + 4)) return -1;
+    if (spectral)
+        asx_launch_pearson_spectral_f32_strided(P, d_src, ss, d_smp, ms, tk, W.spec, W.seg, W.psums, d_lag, d_coef, d_ret, (int)g, s);
+    else
+        asx_launch_pearson_f32(d_src, d_smp, ss, ms, P.N, W.seg, W.psums, d_lag, d_coef, d_ret, (int)g, s);
+    if (prof_mark(p, s, e0 + 5)) return -1;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                         size_t sample_stride, size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret,
+                                         void *stream)
+{
+    if (!p || !d_source || !d_sample || !d_coef) return fail("asx_xcorr_strided_f32_dev: null argument");
+    std::lock_guard<std::mutex> guard(p->lock);
+    DevGuard dg(p->device);
+    if (!dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+    const AsxDev &P = p->dev;
+    if (P.rlayout) {
+        // k_fwd_cols_r reads every row of a pair's inputs as 16-byte loads from the pair's first frame
+        if (((uintptr_t)d_source & 15u) || ((uintptr_t)d_sample & 15u))
+            return fail("asx_xcorr_strided_f32_dev: real-column plans need 16-byte aligned inputs (source %p, sample %p)",
+                        (const void *)d_source, (const void *)d_sample);
+        if ((source_stride & 3u) || (sample_stride & 3u))
+            return fail("asx_xcorr_strided_f32_dev: real-column plans need strides that are multiples of 4 floats "
+                        "(source_stride %zu, sample_stride %zu)", source_stride, sample_stride);
+    }
+    if (batch == 0) return 0;
+    const int bc = P.rlayout ? (source_stride == 0 ? 1 : 0) | (sample_stride == 0 ? 2 : 0) : 0;
+    if (bc) {
+        asx_plan::Bcast &B = p->bslot;
+        if (!B.cx) {
+            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
+            if (cap != hipStreamCaptureStatusNone)
+                return fail("asx_xcorr_strided_f32_dev: the plan's broadcast workspace does not exist yet and cannot be allocated "
+                            "during a stream capture; make one call with a stride of 0 outside the capture first");
+            asx_plan::Bcast T;
+            const size_t mz = ((size_t)p->host.M1 + 1) * (size_t)p->host.M2;
+            if (dev_alloc(p, &T.cx, mz) || dev_alloc(p, &T.cy, mz) || dev_alloc(p, &T.nrm, 2 * (size_t)P.ntiles) ||
+                (P.nbands && dev_alloc(p, &T.band, 2 * (size_t)P.ntiles * (size_t)P.nbands)))
+                return -1;
+            B = T;
+        }
+        // the shared track's forward column pass: once per call, on the caller's stream, before any lane forks
+        const int op0 = (bc & 1) ? 0 : 1, nops = bc == 3 ? 2 : 1;
+        if (!asx_launch_fwd_cols_r1(P, d_source, 0, d_sample, 0, B.cx, B.cy, B.nrm, B.band, 1, op0, nops, true, s))
+            return fail("internal: no forward column kernel for this plan");
+    }
+    prof_begin_call(p);
+    // chunking, lanes and windows exactly as asx_xcorr_batch_f32_dev
+    const bool overlap = (p->nlanes == 2) && !p->profiling && batch >= 8;
+    size_t chunk = p->group;
+    if (overlap && batch < 2 * chunk) chunk = (batch + 1) / 2;
+    const size_t window = p->exact ? std::max<size_t>(chunk, p->over_cap / chunk * chunk) : batch;
+    size_t gi = 0;
+    for (size_t w0 = 0; w0 < batch; w0 += window) {
+        const size_t wn = std::min(window, batch - w0);
+        if (overlap) {
+            HIP_TRY(hipEventRecord(p->fork, s));
+            for (int l = 0; l < 2; l++) HIP_TRY(hipStreamWaitEvent(p->lanes[l].stream, p->fork, 0));
+        }
+        for (size_t done = w0; done < w0 + wn; done += chunk, gi++) {
+            const size_t g = std::min(chunk, w0 + wn - done);
+            const int lane = overlap ? (int)(gi & 1) : 0;
+            hipStream_t ls = overlap ? p->lanes[lane].stream : s;
+            if (run_group_strided(p, d_source + done * source_stride, source_stride, d_sample + done * sample_stride, sample_stride, g,
+                                  bc, d_lag ? d_lag + done : nullptr, d_coef + done, d_ret ? d_ret + done : nullptr, ls, gi, lane,
+                                  (uint32_t)(done - w0), p->exact))
+                return -1;
+        }
+        if (overlap) {
+            for (int l = 0; l < 2; l++) {
+                HIP_TRY(hipEventRecord(p->lanes[l].done, p->lanes[l].stream));
+                HIP_TRY(hipStreamWaitEvent(s, p->lanes[l].done, 0));
+            }
+        }
+        if (p->exact &&
+            resolve_overflows<float>(p, d_sample + w0 * sample_stride, d_source + w0 * source_stride, d_sample + w0 * sample_stride,
+                                     d_lag ? d_lag + w0 : nullptr, d_coef + w0, d_ret ? d_ret + w0 : nullptr, s, source_stride,
+                                     sample_stride) < 0)
             return -1;
     }
     prof_end_call(p, gi);

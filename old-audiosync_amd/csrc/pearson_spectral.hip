@@ -139,9 +139,11 @@ template <int NTP> __device__ __forceinline__ void block_sum4(double (&v)[4], do
 // four sums; the kernels behind this one add the shares in block order (asx_spec_pick): the same bits whoever adds them, and NB is a
 // constant of the plan (the same pair takes the same tree alone, in a batch, on another shard).  No merged record, hence no fence and no
 // ticket: profiles/r5_experiments/18_* (one block per pair: 25 us for a single pair behind ONE block's loads) and 22_*.
-template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
-                                                                    const float *__restrict__ smp, AsxPeakWs W, AsxSpecWs S,
-                                                                    AsxSeg *__restrict__ seg)
+// (body shared with k_pearson_prep_s: src_pitch / smp_pitch are the pairs' input steps in floats, 0 = one track for every pair)
+template <int NTP, int NB> __device__ __forceinline__ void pearson_prep_body(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
+                                                                            const float *__restrict__ smp, size_t src_pitch,
+                                                                            size_t smp_pitch, AsxPeakWs W, AsxSpecWs S,
+                                                                            AsxSeg *__restrict__ seg)
 {
     __shared__ double red[4][NTP / 64];
     __shared__ double s_exact;
@@ -213,7 +215,7 @@ template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep
         hdr[0] = r; hdr[1] = rb; hdr[2] = direct ? 1.0 : 0.0; hdr[3] = 0.0;
     }
     if (direct) return; // block-uniform, and the same in every block of the pair: nobody reads its shares
-    const float *x = src + pair * (size_t)(2u * N), *y = smp + pair * (size_t)N;
+    const float *x = src + pair * src_pitch, *y = smp + pair * smp_pitch;
     const int ntiles = Pp->ntiles;
     const float2 *bx = W.band + (size_t)pair * 2 * ntiles * nbands, *by = bx + (size_t)ntiles * nbands;
     const Acc2 ax = window_share<(uint32_t)NTP * NB>(x, bx, gs, ntiles, nbands, s.src_off, s.src_off + s.len, gtid);
@@ -224,6 +226,19 @@ template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep
         double *mine = S.part + (pair * NB + blk) * 4;
         mine[0] = v[0]; mine[1] = v[1]; mine[2] = v[2]; mine[3] = v[3];
     }
+}
+
+template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
+                                                                    const float *__restrict__ smp, AsxPeakWs W, AsxSpecWs S,
+                                                                    AsxSeg *__restrict__ seg)
+{
+    pearson_prep_body<NTP, NB>(Pp, src, smp, (size_t)(2u * Pp->N), (size_t)Pp->N, W, S, seg);
+}
+template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep_s(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
+                                                                      const float *__restrict__ smp, size_t src_pitch, size_t smp_pitch,
+                                                                      AsxPeakWs W, AsxSpecWs S, AsxSeg *__restrict__ seg)
+{
+    pearson_prep_body<NTP, NB>(Pp, src, smp, src_pitch, smp_pitch, W, S, seg);
 }
 
 // grid (npairs), one wave per pair: k_pearson_final (xcorr_kernels.hip) with the two spectral modes in front of it.
@@ -279,5 +294,23 @@ void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, const fl
         hipLaunchKernelGGL((k_pearson_prep<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, W, S, seg);
     }
     asx_launch_pearson_partial_spec_f32(src, smp, 2 * (size_t)P.N, P.N, P.N, seg, S, psums, npairs, s);
+    hipLaunchKernelGGL(k_pearson_final_spec, dim3(npairs), dim3(64), 0, s, seg, psums, asx_pearson_blocks(P.N), S, lag, coef, ret);
+}
+
+void asx_launch_pearson_spectral_f32_strided(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
+                                             const AsxPeakWs &W, const AsxSpecWs &S0, AsxSeg *seg, double *psums, int64_t *lag,
+                                             double *coef, int32_t *ret, int npairs, hipStream_t s)
+{
+    AsxSpecWs S = S0;
+    S.N = P.N;
+    if ((size_t)P.band_rows * (size_t)P.M2 >= 16384) {
+        S.nb = ASX_PREP_BLOCKS;
+        hipLaunchKernelGGL((k_pearson_prep_s<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0, s,
+                           P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg);
+    } else {
+        S.nb = 1;
+        hipLaunchKernelGGL((k_pearson_prep_s<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg);
+    }
+    asx_launch_pearson_partial_spec_f32(src, smp, src_pitch, smp_pitch, P.N, seg, S, psums, npairs, s);
     hipLaunchKernelGGL(k_pearson_final_spec, dim3(npairs), dim3(64), 0, s, seg, psums, asx_pearson_blocks(P.N), S, lag, coef, ret);
 }

@@ -32,6 +32,7 @@
 #include "lds_fft.h"
 #include "xcorr_dev.h"
 
+#include <algorithm>
 #include <initializer_list>
 #include <map>
 #include <mutex>
@@ -191,10 +192,13 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 //                longest reference lengths get 600- and 400-row column tiles of sixteen real columns (64-byte input
 //                pieces, whole 128-byte lines of C and Q) instead of 1200 / 800 rows of eight.
 // ---------------------------------------------------------------------------
-template <class S, int NT, bool TWO>
-__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_r(const RArgs P, const float2 *__restrict__ cx,
-                                                                                const float2 *__restrict__ cy, float2 *__restrict__ qo,
-                                                                                int nrows, size_t pair_pitch, AsxPeakWs W)
+// The body is shared with k_rows_rb (broadcast forms, asx_xcorr_strided_f32_dev): pitch_x / pitch_y / pitch_q are the pair steps of
+// C_x, C_y and Q (0 = one C for every pair, the plan's broadcast slot), XNT / YNT whether the C loads are non-temporal (a broadcast C
+// is read by every pair: it must stay in the caches).
+template <class S, int NT, bool TWO, bool XNT, bool YNT>
+__device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restrict__ cx, const float2 *__restrict__ cy,
+                                            float2 *__restrict__ qo, int nrows, size_t pitch_x, size_t pitch_y, size_t pitch_q,
+                                            AsxPeakWs W)
 {
     static_assert(S::nstages == 3, "three-stage row schedules only");
     constexpr int NS = S::n;                 // length of a (sub-)row transform
@@ -222,7 +226,8 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_r(c
 
     const int pair = task / nrows;
     const uint32_t k1 = (uint32_t)(task - pair * nrows);
-    const size_t row = (size_t)RWS_PAIR(pair) * pair_pitch + (size_t)k1 * M2;
+    const size_t row = (size_t)RWS_PAIR(pair) * pitch_q + (size_t)k1 * M2;
+    const size_t rowx = (size_t)RWS_PAIR(pair) * pitch_x + (size_t)k1 * M2, rowy = (size_t)RWS_PAIR(pair) * pitch_y + (size_t)k1 * M2;
     if (k1 == 0 && tid < 64) {
         // Row 0 of a pair also prepares the pair's peak search (k_inv_cols_r runs after this kernel): the float32
         // error bound from the norms k_fwd_cols_r left, the running maximum and the candidate count back to zero.
@@ -271,15 +276,15 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_r(c
     // tw_step / leg threads then started an L2 round trip of their own in front of the block's barrier)
     float4 lx[WSTEPS], ly[WSTEPS], lx2[TWO ? WSTEPS : 1], ly2[TWO ? WSTEPS : 1];
     auto issue_row_loads = [&]() __attribute__((always_inline)) {
-        const float2 *gx = cx + row, *gy = cy + row;
+        const float2 *gx = cx + rowx, *gy = cy + rowy;
         static_for<0, WSTEPS>([&](auto I) __attribute__((always_inline)) {
             const int q = tid + decltype(I)::value * NTB;
             if (((ASX_ROWS_EARLY & 4) && (decltype(I)::value + 1) * NTB <= HALF) || q < HALF) { // (a whole step inside the row: no condition)
-                lx[I] = ld_f4(gx + 2 * q, ASX_RNT & 4);
-                ly[I] = ld_f4(gy + 2 * q, ASX_RNT & 4);
+                lx[I] = ld_f4(gx + 2 * q, XNT && (ASX_RNT & 4));
+                ly[I] = ld_f4(gy + 2 * q, YNT && (ASX_RNT & 4));
                 if constexpr (TWO) {
-                    lx2[I] = ld_f4(gx + NS + 2 * q, ASX_RNT & 4);
-                    ly2[I] = ld_f4(gy + NS + 2 * q, ASX_RNT & 4);
+                    lx2[I] = ld_f4(gx + NS + 2 * q, XNT && (ASX_RNT & 4));
+                    ly2[I] = ld_f4(gy + NS + 2 * q, YNT && (ASX_RNT & 4));
                 }
             }
         });
@@ -455,6 +460,24 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_r(c
 #endif
 }
 
+template <class S, int NT, bool TWO>
+__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_r(const RArgs P, const float2 *__restrict__ cx,
+                                                                                const float2 *__restrict__ cy, float2 *__restrict__ qo,
+                                                                                int nrows, size_t pair_pitch, AsxPeakWs W)
+{
+    rows_r_body<S, NT, TWO, true, true>(P, cx, cy, qo, nrows, pair_pitch, pair_pitch, pair_pitch, W);
+}
+
+// Broadcast forms: BC bit 0 = C_x is the plan's broadcast slot (pitch_x = 0, temporal loads), bit 1 = C_y is.
+template <class S, int NT, bool TWO, int BC>
+__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rb(const RArgs P, const float2 *__restrict__ cx,
+                                                                                 const float2 *__restrict__ cy, float2 *__restrict__ qo,
+                                                                                 int nrows, size_t pitch_x, size_t pitch_y,
+                                                                                 size_t pitch_q, AsxPeakWs W)
+{
+    rows_r_body<S, NT, TWO, (BC & 1) == 0, (BC & 2) == 0>(P, cx, cy, qo, nrows, pitch_x, pitch_y, pitch_q, W);
+}
+
 // ---------------------------------------------------------------------------
 // Column tiles of the real-column kernels: T REAL columns j2 = c0 .. c0+T-1 of the [2 M1][M2] sample matrix, held
 // in LDS as [M1][T/2] float4 slots: slot (m, g) = { x[2m][c0+2g], x[2m+1][c0+2g], x[2m][c0+2g+1], x[2m+1][c0+2g+1] },
@@ -502,22 +525,24 @@ template <int NITEMS, int H, int NT> __device__ __forceinline__ int rcol_item_of
 // sample -- rows j1 >= M1 -- is never loaded, src/cross_correlation.c:159-166): M1-point complex transform of the
 // packed rows, untangling between the slots of u and M1 - u, rows u and M1 - u of C (twice its value: the factor
 // is taken back by k_rows_r) stored in natural row order.
-template <class S1, int TC, int NT>
-__global__ __launch_bounds__(NT, 4) void k_fwd_cols_r(const RArgs P, const float *__restrict__ src,
-                                                       const float *__restrict__ smp, float2 *__restrict__ cx,
-                                                       float2 *__restrict__ cy, float *__restrict__ nrm_part, size_t pair_pitch,
-                                                       float2 *__restrict__ band)
+// The body is shared with k_fwd_cols_r1 (asx_xcorr_strided_f32_dev): `which` = 0 source, 1 sample; src_stride / smp_stride = the
+// pair steps of the inputs in floats (0 = one track for every pair); NTS = non-temporal stores of C (false for the broadcast slot,
+// which every pair's k_rows_rb block reads).
+template <class S1, int TC, int NT, bool NTS>
+__device__ __forceinline__ void fwd_cols_r_body(const RArgs P, const float *__restrict__ src, const float *__restrict__ smp,
+                                                size_t src_stride, size_t smp_stride, float2 *__restrict__ cx,
+                                                float2 *__restrict__ cy, float *__restrict__ nrm_part, size_t pair_pitch,
+                                                float2 *__restrict__ band, unsigned which)
 {
     constexpr int M1 = S1::n, T = TC, logT = asx_ilog2(TC), H = T / 2, logH = logT - 1, Q4 = T / 4, logQ4 = logT - 2;
     static_assert(T >= 4 && (M1 & 1) == 0, "four real columns per 16-byte load, an even number of packed rows");
     __shared__ float nrm_red[NT / 64];
-    const bool is_smp = blockIdx.y != 0;
+    const bool is_smp = which != 0;
     const size_t pair = blockIdx.z;
     const int tile = rcol_tile_of_block(blockIdx.x, logT);
-    const unsigned which = blockIdx.y;
     if (tile >= P.ntiles) return; // grid.x is rounded up
     const int M2 = P.M2, c0 = tile * T;
-    const float *in = is_smp ? smp + pair * (size_t)P.N : src + pair * (size_t)(2u * P.N);
+    const float *in = is_smp ? smp + pair * smp_stride : src + pair * src_stride;
     const int data_m = is_smp ? M1 / 2 : M1; // packed rows that are not zero padding
     float2 *out = (is_smp ? cy : cx) + RWS_PAIR(pair) * pair_pitch;
     float4 *lds4 = reinterpret_cast<float4 *>(asx_lds_r);
@@ -613,7 +638,7 @@ __global__ __launch_bounds__(NT, 4) void k_fwd_cols_r(const RArgs P, const float
         const int cg = 2 * g;
         auto row = [&](int u, Cx2 c, bool conj) __attribute__((always_inline)) {
             st_f4(out + (size_t)u * M2 + c0 + cg, conj ? make_float4(c.re.x, -c.im.x, c.re.y, -c.im.y)
-                                                       : make_float4(c.re.x, c.im.x, c.re.y, c.im.y), ASX_RNT & 2);
+                                                       : make_float4(c.re.x, c.im.x, c.re.y, c.im.y), NTS && (ASX_RNT & 2));
         };
         if (v != 0) {
             const float2 wu = tw_F(P, (uint32_t)ub * (uint32_t)M2); // w_{2 M1}^u_b = w_F^(u_b M2)
@@ -648,6 +673,40 @@ __global__ __launch_bounds__(NT, 4) void k_fwd_cols_r(const RArgs P, const float
             });
         }
     }
+}
+
+template <class S1, int TC, int NT>
+__global__ __launch_bounds__(NT, 4) void k_fwd_cols_r(const RArgs P, const float *__restrict__ src,
+                                                       const float *__restrict__ smp, float2 *__restrict__ cx,
+                                                       float2 *__restrict__ cy, float *__restrict__ nrm_part, size_t pair_pitch,
+                                                       float2 *__restrict__ band)
+{
+    fwd_cols_r_body<S1, TC, NT, true>(P, src, smp, (size_t)(2u * P.N), (size_t)P.N, cx, cy, nrm_part, pair_pitch, band, blockIdx.y);
+}
+
+// grid (tiles, nops, npairs): operand op0 + blockIdx.y of every pair, inputs at the caller's strides.  NTS = false: into the plan's
+// broadcast slot (npairs = 1).
+template <class S1, int TC, int NT, bool NTS>
+__global__ __launch_bounds__(NT, 4) void k_fwd_cols_r1(const RArgs P, const float *__restrict__ src, const float *__restrict__ smp,
+                                                        size_t src_stride, size_t smp_stride, float2 *__restrict__ cx,
+                                                        float2 *__restrict__ cy, float *__restrict__ nrm_part, size_t pair_pitch,
+                                                        float2 *__restrict__ band, unsigned op0)
+{
+    fwd_cols_r_body<S1, TC, NT, NTS>(P, src, smp, src_stride, smp_stride, cx, cy, nrm_part, pair_pitch, band, op0 + blockIdx.y);
+}
+
+// grid (ceil(per / 256), npairs): the broadcast operand's norm partials and band sums (the slot's pair 0, operand `which`) into
+// every pair's place in the group's workspaces, where k_rows_r* and the spectral Pearson form read them.  per = ntiles (norms)
+// + ntiles * nbands (band sums, when band != null).
+__global__ __launch_bounds__(256) void k_bcast_aux(const float *__restrict__ snrm, const float2 *__restrict__ sband,
+                                                    float *__restrict__ nrm, float2 *__restrict__ band, int ntiles, int nbands,
+                                                    unsigned which)
+{
+    const size_t pair = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < ntiles) nrm[(pair * 2 + which) * (size_t)ntiles + i] = snrm[(size_t)which * ntiles + i];
+    const int nb = ntiles * nbands;
+    if (band && i < nb) band[(pair * 2 + which) * (size_t)nb + i] = sband[(size_t)which * nb + i];
 }
 
 // ---------------------------------------------------------------------------
@@ -939,6 +998,34 @@ bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, floa
     return false;
 }
 
+// Broadcast forms of the row kernel (asx_xcorr_strided_f32_dev): bc bit 0 = cx is the broadcast slot, bit 1 = cy is; the other
+// operand and q have the group workspace's pitch.  bc = 0 is k_rows_r itself.
+bool asx_launch_rows_rb(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
+                        hipStream_t s)
+{
+    if (bc == 0) return asx_launch_rows_r(P, cx, cy, q, W, npairs, s);
+    const int nrows = P.M1 + 1;
+    const size_t pitch = (size_t)nrows * (size_t)P.M2;
+    const size_t px = (bc & 1) ? 0 : pitch, py = (bc & 2) ? 0 : pitch;
+    const size_t lds = (size_t)P.M2 * sizeof(float4);
+#define ASX_ROWSRB_LAUNCH(b, nt, two, n, ...)                                                                                   \
+    hipLaunchKernelGGL((k_rows_rb<Sched<n, __VA_ARGS__>, nt, two, b>), dim3((unsigned)nrows * (unsigned)npairs),              \
+                       dim3((two) ? 2 * nt : nt), lds, s, rargs_of(P), cx, cy, q, nrows, px, py, pitch, W);
+#define ASX_ROWSRB_CASE(nt, two, n, ...)                                                                                        \
+    if (P.M2 == ((two) ? 2 * n : n)) {                                                                                          \
+        if (bc == 1) { ASX_ROWSRB_LAUNCH(1, nt, two, n, __VA_ARGS__) }                                                          \
+        else if (bc == 2) { ASX_ROWSRB_LAUNCH(2, nt, two, n, __VA_ARGS__) }                                                     \
+        else { ASX_ROWSRB_LAUNCH(3, nt, two, n, __VA_ARGS__) }                                                                  \
+        return true;                                                                                                            \
+    }
+    ASX_ROWSRB_CASE(128, false, 1200, 12, 10, 10)
+    ASX_ROWSRB_CASE(128, true, 1200, ASX_ROWS2_SCHED)
+    ASX_ROWSRB_CASE(64, false, 480, 10, 8, 6)
+#undef ASX_ROWSRB_CASE
+#undef ASX_ROWSRB_LAUNCH
+    return false;
+}
+
 // Column schedules of the production sample lengths (plan_math.cpp's tuned table):  X(M1, tile width in real columns,
 // block size, radices...).  (1200- and 800-row tiles hold only eight real columns: 32-byte input pieces, measured 25 % slower
 // in k_fwd_cols_r, and a fed first stage of radix 10 needs 20 rows in flight per thread: the two longest lengths use 600 / 400
@@ -988,6 +1075,40 @@ bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, const float *smp, 
     ASX_RCOLS(ASX_TRY)
 #undef ASX_TRY
     return false;
+}
+
+// Forward columns of operands op0 .. op0 + nops - 1 (0 source, 1 sample) of npairs pairs whose inputs are src_stride / smp_stride
+// floats apart, into cx / cy (pair pitch (M1 + 1) M2), nrm (AsxPeakWs::nrm_part layout) and band (AsxPeakWs::band layout, or null).
+// temporal: C stored with ordinary stores (the broadcast slot).
+bool asx_launch_fwd_cols_r1(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
+                            float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s)
+{
+    if (!P.col_pairs) return false;
+    const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, lds = (size_t)P.M1 * P.T * sizeof(float2);
+    const dim3 grid(rcol_grid_x(P.ntiles, P.logT), (unsigned)nops, npairs);
+#define ASX_TRY1(nts, m1, t, nt, ...)                                                                                        \
+    {                                                                                                                       \
+        allow_big_lds_r((const void *)k_fwd_cols_r1<Sched<m1, __VA_ARGS__>, t, nt, nts>, lds);                              \
+        hipLaunchKernelGGL((k_fwd_cols_r1<Sched<m1, __VA_ARGS__>, t, nt, nts>), grid, dim3(nt), lds, s, rargs_of(P), src, smp, \
+                           src_stride, smp_stride, cx, cy, nrm, pitch, band, (unsigned)op0);                                \
+    }
+#define ASX_TRY(m1, t, nt, ...)                                                                                             \
+    if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                                                          \
+        if (temporal) ASX_TRY1(false, m1, t, nt, __VA_ARGS__) else ASX_TRY1(true, m1, t, nt, __VA_ARGS__)                   \
+        return true;                                                                                                        \
+    }
+    ASX_RCOLS(ASX_TRY)
+#undef ASX_TRY
+#undef ASX_TRY1
+    return false;
+}
+
+void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
+                          unsigned which, hipStream_t s)
+{
+    const int per = std::max(P.ntiles, band ? P.ntiles * P.nbands : 0);
+    hipLaunchKernelGGL(k_bcast_aux, dim3((unsigned)(per + 255) / 256, (unsigned)npairs), dim3(256), 0, s, snrm, sband, nrm, band,
+                       P.ntiles, P.nbands, which);
 }
 
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s)

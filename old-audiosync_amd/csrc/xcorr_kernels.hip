@@ -928,17 +928,18 @@ __device__ __forceinline__ dd_t dd_add(dd_t a, dd_t b)
     return r;
 }
 
+// (body shared with k_refine_dots_s: src_pitch / smp_pitch are the pairs' input steps, 0 = one track for every pair)
 template <typename TIn>
-__global__ __launch_bounds__(ASX_THREADS) void k_refine_dots(const AsxDev *__restrict__ Pp, const TIn *__restrict__ src,
-                                                              const TIn *__restrict__ smp, AsxPeakWs W)
+__device__ __forceinline__ void refine_dots_body(const AsxDev *__restrict__ Pp, const TIn *__restrict__ src, const TIn *__restrict__ smp,
+                                                 size_t src_pitch, size_t smp_pitch, AsxPeakWs W)
 {
     __shared__ double red[2][ASX_THREADS / 64];
     const size_t pair = blockIdx.y;
     const uint32_t ncand = W.refine_n[pair];
     if (blockIdx.x >= ncand) return;
     const uint32_t N = Pp->N, L = 2u * N;
-    const TIn *x = src + pair * (size_t)L;
-    const TIn *y = smp + pair * (size_t)N;
+    const TIn *x = src + pair * src_pitch;
+    const TIn *y = smp + pair * smp_pitch;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (uint32_t c = blockIdx.x; c < ncand; c += gridDim.x) {
         const uint32_t k = W.refine_idx[pair * (size_t)W.cap + c];
@@ -978,6 +979,19 @@ __global__ __launch_bounds__(ASX_THREADS) void k_refine_dots(const AsxDev *__res
         }
         __syncthreads();
     }
+}
+
+template <typename TIn>
+__global__ __launch_bounds__(ASX_THREADS) void k_refine_dots(const AsxDev *__restrict__ Pp, const TIn *__restrict__ src,
+                                                              const TIn *__restrict__ smp, AsxPeakWs W)
+{
+    refine_dots_body<TIn>(Pp, src, smp, (size_t)(2u * Pp->N), (size_t)Pp->N, W);
+}
+__global__ __launch_bounds__(ASX_THREADS) void k_refine_dots_s(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
+                                                                const float *__restrict__ smp, size_t src_pitch, size_t smp_pitch,
+                                                                AsxPeakWs W)
+{
+    refine_dots_body<float>(Pp, src, smp, src_pitch, smp_pitch, W);
 }
 
 // grid (npairs): the reference's max_abs_index rule (src/cross_correlation.c:52-67) on the exact values:
@@ -1525,6 +1539,13 @@ void asx_launch_refine_f32(const AsxDev &P, const float *src, const float *smp, 
                            AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick)
 {
     hipLaunchKernelGGL(k_refine_dots<float>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, W);
+    if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg);
+}
+
+void asx_launch_refine_f32_strided(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
+                                   const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick)
+{
+    hipLaunchKernelGGL(k_refine_dots_s, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
     if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg);
 }
 

@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "asx_memcpy_d2h", "asx_stream_sync", "asx_plan_peak_overflows", "asx_plan_peak_repairs", "asx_plan_set_exact", "asx_plan_peak_capacity",
     "asx_current_device", "asx_plan_timings_ms", "asx_xcorr_batch_multi", "asx_plan_layout", "asx_plan_narrowed_calls",
     "asx_plan_set_pearson", "asx_plan_pearson_modes", "asx_plan_placement", "asx_host_malloc", "asx_host_free", "asx_shard_range", "asx_result_bytes", "asx_comm_create", "asx_comm_destroy", "asx_xcorr_batch_multi_dev",
+    "asx_xcorr_strided_f32_dev",
 ]
 
 
@@ -99,6 +100,8 @@ def lib():
     L.asx_xcorr_batch_multi.argtypes = [ctypes.POINTER(vp), ctypes.c_int, c_f32p, c_f32p, ctypes.c_size_t, c_i64p, c_f64p, c_i32p]
     L.asx_xcorr_batch_f32_dev.restype = ctypes.c_int
     L.asx_xcorr_batch_f32_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, vp, vp, vp]
+    L.asx_xcorr_strided_f32_dev.restype = ctypes.c_int
+    L.asx_xcorr_strided_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, vp]
     L.asx_shard_range.restype = ctypes.c_int
     L.asx_shard_range.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t),
                                   ctypes.POINTER(ctypes.c_size_t)]
@@ -382,6 +385,7 @@ class Plan:
             raise AsxError(_err())
         self._destroy = lib().asx_plan_destroy  # bound now: module globals may be gone at interpreter exit
         self.sample_len = int(sample_len)
+        self.device = int(device)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -511,6 +515,78 @@ class Plan:
                                            d_ret or None, stream or None)
         if rc != 0:
             raise AsxError(_err())
+
+    def xcorr_strided_dev(self, d_src, src_stride, d_smp, smp_stride, batch, d_lag, d_coef, d_ret, stream=0):
+        """raw device pointers (ints), strides in floats (0 = one track for every pair; see asx_xcorr_strided_f32_dev);
+        asynchronous on `stream` (0 = the plan's own)"""
+        rc = lib().asx_xcorr_strided_f32_dev(self._h, d_src, int(src_stride), d_smp, int(smp_stride), int(batch), d_lag or None,
+                                             d_coef, d_ret or None, stream or None)
+        if rc != 0:
+            raise AsxError(_err())
+
+    def _strided_host(self, src, src_stride, smp, smp_stride, batch):
+        """host float32 buffers -> device copies -> asx_xcorr_strided_f32_dev -> (lag, coef, ret)"""
+        L = lib()
+        bufs = []
+        try:
+            def dev(nbytes):
+                ptr = L.asx_device_malloc(max(int(nbytes), 16), self.device)
+                if not ptr:
+                    raise AsxError(_err())
+                bufs.append(ptr)
+                return ptr
+            d_src, d_smp = dev(src.nbytes), dev(smp.nbytes)
+            d_lag, d_coef, d_ret = dev(8 * batch), dev(8 * batch), dev(4 * batch)
+            for d, h in ((d_src, src), (d_smp, smp)):
+                if L.asx_memcpy_h2d(d, h.ctypes.data, h.nbytes) != 0:
+                    raise AsxError(_err())
+            self.xcorr_strided_dev(d_src, src_stride, d_smp, smp_stride, batch, d_lag, d_coef, d_ret)
+            self.sync()
+            lag = np.zeros(batch, dtype=np.int64)
+            coef = np.zeros(batch, dtype=np.float64)
+            ret = np.zeros(batch, dtype=np.int32)
+            for h, d in ((lag, d_lag), (coef, d_coef), (ret, d_ret)):
+                if L.asx_memcpy_d2h(h.ctypes.data, d, h.nbytes) != 0:
+                    raise AsxError(_err())
+            return lag, coef, ret
+        finally:
+            for ptr in bufs:
+                L.asx_device_free(ptr)
+
+    def xcorr_broadcast_f32(self, source, sample):
+        """One track against many.  source: float32 [2N] (one source for every pair) or [B, 2N]; sample: [N] (one sample for every
+        pair) or [B, N].  At least one may be 1-D; with both 1-D there is one pair.  The 1-D track is transformed once per call
+        (real-column plans).  Returns (lag int64[B], coef float64[B], ret int32[B]) like xcorr_batch_f32."""
+        n = self.sample_len
+        s = np.ascontiguousarray(source, dtype=np.float32)
+        t = np.ascontiguousarray(sample, dtype=np.float32)
+        if s.ndim not in (1, 2) or t.ndim not in (1, 2) or s.shape[-1] != 2 * n or t.shape[-1] != n:
+            raise ValueError("source must be [2N] or [B, 2N] and sample [N] or [B, N] with N = %d" % n)
+        bs = s.shape[0] if s.ndim == 2 else None
+        bt = t.shape[0] if t.ndim == 2 else None
+        if bs is not None and bt is not None and bs != bt:
+            raise ValueError("source and sample have different batch sizes (%d, %d)" % (bs, bt))
+        batch = bs if bs is not None else bt if bt is not None else 1
+        return self._strided_host(s, 2 * n if s.ndim == 2 else 0, t, n if t.ndim == 2 else 0, batch)
+
+    def xcorr_windows_f32(self, recording, sample, hop):
+        """Windows recording[k*hop : k*hop + 2N] (k = 0 .. (len - 2N) // hop) of one long float32 recording, each correlated with
+        the one float32 sample [N]: one (lag, coef, ret) per window, arrays like xcorr_batch_f32's.  The recording and the sample
+        are uploaded once and the sample is transformed once.  Which window holds the sample is the caller's decision (for
+        instance the largest |coef| with ret == 0); a clip that straddles two windows shows in both with lower coefficients, so a
+        hop of at most N keeps every clip of length N whole in some window.  On real-column plans hop must be a multiple of 4."""
+        n = self.sample_len
+        r = np.ascontiguousarray(recording, dtype=np.float32).ravel()
+        t = np.ascontiguousarray(sample, dtype=np.float32).ravel()
+        hop = int(hop)
+        if t.size != n:
+            raise ValueError("sample must have N = %d frames" % n)
+        if hop < 1:
+            raise ValueError("hop must be >= 1")
+        if r.size < 2 * n:
+            raise ValueError("recording shorter than one window of 2N = %d frames" % (2 * n))
+        batch = (r.size - 2 * n) // hop + 1
+        return self._strided_host(r, hop, t, 0, batch)
 
     def debug_r_dev(self, d_src, d_smp, d_r, d_lag, d_coef, d_ret, stream=0):
         rc = lib().asx_xcorr_debug_r_dev(self._h, d_src, d_smp, d_r, d_lag, d_coef, d_ret, stream or None)
