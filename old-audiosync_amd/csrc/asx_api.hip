@@ -123,7 +123,7 @@ struct asx_plan {
     } big;
     // Broadcast slot of asx_xcorr_strided_f32_dev (real-column plans, lazy, like BigPeak): the forward column pass of a track that
     // every pair of a call shares (a stride of 0) -- C_x / C_y of ONE pair, its norm partials and band sums in the AsxPeakWs layout
-    // of pair 0 -- written once per call before the launch groups, read by every group's row kernel (k_rows_rb)
+    // of pair 0 -- written once per call before the launch groups, read by every group's row kernel (k_rows_r, BC != 0)
     struct Bcast {
         float2 *cx = nullptr, *cy = nullptr;
         float *nrm = nullptr;
@@ -608,12 +608,14 @@ static int prof_mark(asx_plan *p, hipStream_t s, size_t slot)
     return 0;
 }
 
-// one group: g <= plan->group pairs, inputs device resident.  TIn selects the Pearson input type.
+// One group: g <= plan->group pairs, inputs device resident.  Pair k is source d_src + k * src_step and sample d_smp + k * smp_step
+// (floats); the exact passes read it from p_src / p_smp at the same steps, TIn selecting the Pearson input type.  bc bit 0 / 1: the
+// source / sample is the call's broadcast track (asx_xcorr_strided_f32_dev, real-column plans), whose forward column pass is already
+// in the plan's slot: only the other operand is transformed here.
 template <typename TIn>
-static int run_group(asx_plan *p, const float *d_src, const float *d_smp, const TIn *p_src,
-                     const TIn *p_smp, size_t g, int64_t *d_lag, double *d_coef, int32_t *d_ret,
-                     float *d_r, hipStream_t s, size_t group_index, int lane = 0, uint32_t pair_base = 0, bool listed = true,
-                     bool float32_call = true)
+static int run_group(asx_plan *p, const float *d_src, size_t src_step, const float *d_smp, size_t smp_step, const TIn *p_src,
+                     const TIn *p_smp, int bc, size_t g, int64_t *d_lag, double *d_coef, int32_t *d_ret, float *d_r, hipStream_t s,
+                     size_t group_index, int lane = 0, uint32_t pair_base = 0, bool listed = true, bool float32_call = true)
 {
     const AsxDev &P = p->dev;
     asx_plan::Lane &W = p->lanes[lane];
@@ -630,10 +632,32 @@ static int run_group(asx_plan *p, const float *d_src, const float *d_smp, const 
     if (!spectral) { tk.band = nullptr; tk.tile_peak = nullptr; }
     const size_t e0 = group_index * 6;
     if (prof_mark(p, s, e0 + 0)) return -1;
-    asx_launch_fwd_cols(P, d_src, d_smp, W.zxa, W.zya, tk, (int)g, s);
+    if (P.rlayout) {
+        const int op0 = bc & 1, nops = 2 - (bc & 1) - ((bc >> 1) & 1);
+        if (nops > 0 &&
+            !asx_launch_fwd_cols_r(P, d_src, src_step, d_smp, smp_step, W.zxa, W.zya, W.pk.nrm_part, tk.band, (int)g, op0, nops, false, s))
+            return fail("internal: no forward column kernel for this plan");
+        for (unsigned which = 0; which < 2; which++)
+            if (bc & (1 << which)) asx_launch_bcast_aux(P, p->bslot.nrm, p->bslot.band, W.pk.nrm_part, tk.band, (int)g, which, s);
+    } else if (src_step == 2 * (size_t)P.N && smp_step == P.N) {
+        asx_launch_fwd_cols(P, d_src, d_smp, W.zxa, W.zya, tk, (int)g, s);
+    } else {
+        // packed plans have no strided forward kernel: the contiguous one once per pair at the pair's own inputs (no broadcast
+        // slot: every pair transforms its own copy of a shared track)
+        for (size_t k = 0; k < g; k++) {
+            AsxPeakWs one = tk;
+            one.nrm_part = W.pk.nrm_part + k * 2 * (size_t)P.ntiles;
+            asx_launch_fwd_cols(P, d_src + k * src_step, d_smp + k * smp_step, W.zxa + k * (size_t)P.M, W.zya + k * (size_t)P.M, one, 1, s);
+        }
+    }
     if (prof_mark(p, s, e0 + 1)) return -1;
     float2 *q = W.ga;
-    asx_launch_rows(P, W.zxa, W.zya, q, tk, (int)g, s);
+    if (P.rlayout) {
+        if (!asx_launch_rows_r(P, (bc & 1) ? p->bslot.cx : W.zxa, (bc & 2) ? p->bslot.cy : W.zya, q, tk, (int)g, bc, s))
+            return fail("internal: no row kernel for this plan");
+    } else {
+        asx_launch_rows(P, W.zxa, W.zya, q, tk, (int)g, s);
+    }
     if (prof_mark(p, s, e0 + 2)) return -1;
     asx_launch_inv_cols(P, q, tk, d_r, (int)g, s);
     if (prof_mark(p, s, e0 + 3)) return -1;
@@ -643,18 +667,19 @@ static int run_group(asx_plan *p, const float *d_src, const float *d_smp, const 
     // pairs, 128 blocks each were 131 072 empty blocks, 25 us of a 2 ms step.
     const int dot_blocks = (int)std::min<size_t>(ASX_DOT_BLOCKS, std::max<size_t>(8, 16384 / g));
     if (sizeof(TIn) == sizeof(float)) // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
-        asx_launch_refine_f32(P, (const float *)p_src, (const float *)p_smp, W.pk, W.seg, (int)g, s, dot_blocks, !spectral);
+        asx_launch_refine_f32(P, (const float *)p_src, src_step, (const float *)p_smp, smp_step, W.pk, W.seg, (int)g, s, dot_blocks,
+                              !spectral);
     else
-        asx_launch_refine_f64(P, (const double *)p_src, (const double *)p_smp, W.pk, W.seg, (int)g, s, dot_blocks);
+        asx_launch_refine_f64(P, (const double *)p_src, src_step, (const double *)p_smp, smp_step, W.pk, W.seg, (int)g, s, dot_blocks);
     if (prof_mark(p, s, e0 + 4)) return -1;
     if (spectral)
-        asx_launch_pearson_spectral_f32(P, (const float *)p_src, (const float *)p_smp, tk, W.spec, W.seg, W.psums, d_lag, d_coef,
-                                        d_ret, (int)g, s);
+        asx_launch_pearson_spectral_f32(P, (const float *)p_src, src_step, (const float *)p_smp, smp_step, tk, W.spec, W.seg, W.psums,
+                                        d_lag, d_coef, d_ret, (int)g, s);
     else if (sizeof(TIn) == sizeof(float))
-        asx_launch_pearson_f32((const float *)p_src, (const float *)p_smp, 2 * (size_t)P.N, P.N, P.N,
+        asx_launch_pearson_f32((const float *)p_src, (const float *)p_smp, src_step, smp_step, P.N,
                                W.seg, W.psums, d_lag, d_coef, d_ret, (int)g, s);
     else
-        asx_launch_pearson_f64((const double *)p_src, (const double *)p_smp, 2 * (size_t)P.N, P.N, P.N,
+        asx_launch_pearson_f64((const double *)p_src, (const double *)p_smp, src_step, smp_step, P.N,
                                W.seg, W.psums, d_lag, d_coef, d_ret, (int)g, s);
     if (prof_mark(p, s, e0 + 5)) return -1;
     HIP_TRY(hipGetLastError());
@@ -677,17 +702,15 @@ static int run_group(asx_plan *p, const float *d_src, const float *d_smp, const 
 //        lag that wins.
 // It runs on `s` behind everything the call has launched (the lanes have been joined), in the workspace slot 0 of
 // lane 0 and the plan's one set of big lists: nothing else is in flight on this plan (one stream at a time per plan).
-// The pointers are the bases the list's indices count from: pair i of the list is f_src + i * 2N etc.
-// sp / mp: the pair steps of the source and the sample (asx_xcorr_strided_f32_dev; SIZE_MAX = the contiguous 2N and N).
+// The pointers are the bases the list's indices count from: pair i of the list is p_src + i * sp, f_smp and p_smp + i * mp
+// (sp / mp: the pair steps of the source and the sample).
 template <typename TIn>
-static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_src, const TIn *p_smp, int64_t *d_lag,
-                       double *d_coef, int32_t *d_ret, hipStream_t s, size_t sp = SIZE_MAX, size_t mp = SIZE_MAX)
+static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_src, const TIn *p_smp, size_t sp, size_t mp,
+                       int64_t *d_lag, double *d_coef, int32_t *d_ret, hipStream_t s)
 {
     const AsxDev &P = p->dev;
     asx_plan::Lane &W = p->lanes[0];
     const size_t N = p->host.N;
-    if (sp == SIZE_MAX) sp = 2 * N;
-    if (mp == SIZE_MAX) mp = N;
     asx_plan::BigPeak &B = p->big;
     if (!B.cand) {
         // into a local first: a failed allocation must not leave half a set behind for the next call
@@ -720,9 +743,9 @@ static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_s
     asx_launch_inv_cols(P, W.ga, K, nullptr, 1, s);
     asx_launch_finalize(P, K, W.seg, 1, s);
     if (sizeof(TIn) == sizeof(float))
-        asx_launch_refine_f32(P, (const float *)p_src + i * sp, (const float *)p_smp + i * mp, K, W.seg, 1, s, 2048);
+        asx_launch_refine_f32(P, (const float *)p_src + i * sp, 2 * N, (const float *)p_smp + i * mp, N, K, W.seg, 1, s, 2048);
     else
-        asx_launch_refine_f64(P, (const double *)p_src + i * sp, (const double *)p_smp + i * mp, K, W.seg, 1, s, 2048);
+        asx_launch_refine_f64(P, (const double *)p_src + i * sp, 2 * N, (const double *)p_smp + i * mp, N, K, W.seg, 1, s, 2048);
     if (sizeof(TIn) == sizeof(float))
         asx_launch_pearson_f32((const float *)p_src + i * sp, (const float *)p_smp + i * mp, 2 * N, N, P.N,
                                W.seg, W.psums, d_lag ? d_lag + i : nullptr, d_coef + i, d_ret ? d_ret + i : nullptr, 1, s);
@@ -738,8 +761,8 @@ static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_s
 // on `s` (its result copies included): ONE synchronisation; the count is read from the page-locked mirror k_finalize adds to
 // only when a pair overflows -- no device-to-host copy sits between the last kernel and the host.
 template <typename TIn>
-static int resolve_overflows(asx_plan *p, const float *f_smp, const TIn *p_src, const TIn *p_smp, int64_t *d_lag,
-                             double *d_coef, int32_t *d_ret, hipStream_t s, size_t sp = SIZE_MAX, size_t mp = SIZE_MAX)
+static int resolve_overflows(asx_plan *p, const float *f_smp, const TIn *p_src, const TIn *p_smp, size_t sp, size_t mp,
+                             int64_t *d_lag, double *d_coef, int32_t *d_ret, hipStream_t s)
 {
     HIP_TRY(hipStreamSynchronize(s));
     if (p->lanes[0].pk.cap >= 2 * p->host.N) return 0; // the ordinary list already holds every lag
@@ -758,8 +781,27 @@ static int resolve_overflows(asx_plan *p, const float *f_smp, const TIn *p_src, 
     HIP_TRY(hipStreamSynchronize(s));
     *p->h_over_n = 0;
     for (uint32_t k = 0; k < n; k++)
-        if (second_look<TIn>(p, p->h_over[k], f_smp, p_src, p_smp, d_lag, d_coef, d_ret, s, sp, mp)) return -1;
+        if (second_look<TIn>(p, p->h_over[k], f_smp, p_src, p_smp, sp, mp, d_lag, d_coef, d_ret, s)) return -1;
     return (int)n;
+}
+
+// Copies the results of g contiguous pairs (one group of a host-side entry point) back to the host.  The copies go out with the one
+// synchronisation that reads the overflow list, and once more behind the second look if any pair took it.
+template <typename TIn>
+static int fetch_results(asx_plan *p, const float *f_smp, const TIn *p_src, const TIn *p_smp, size_t g, int64_t *d_lag, double *d_coef,
+                         int32_t *d_ret, int64_t *lag, double *coef, int32_t *ret, hipStream_t s)
+{
+    const size_t N = p->host.N;
+    for (int pass = 0; pass < 2; pass++) {
+        HIP_TRY(hipMemcpyAsync(lag, d_lag, g * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(coef, d_coef, g * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ret, d_ret, g * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (pass == 1) { HIP_TRY(hipStreamSynchronize(s)); break; }
+        const int looked = resolve_overflows<TIn>(p, f_smp, p_src, p_smp, 2 * N, N, d_lag, d_coef, d_ret, s);
+        if (looked < 0) return -1;
+        if (looked == 0) break;
+    }
+    return 0;
 }
 
 // The forward column kernel runs 2-5 % faster or slower with the PHYSICAL placement of the buffers it streams together (the
@@ -839,19 +881,11 @@ extern "C" int asx_plan_placement(asx_plan *p, double ms[2], int *kept)
     return 0;
 }
 
-extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const float *d_sample,
-                                       size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret,
-                                       void *stream)
+// A device-resident batch, after the entry point's own checks: pair k is source d_source + k * src_step and sample
+// d_sample + k * smp_step (floats), bc as in run_group.
+static int run_batch(asx_plan *p, const float *d_source, size_t src_step, const float *d_sample, size_t smp_step, int bc, size_t batch,
+                     int64_t *d_lag, double *d_coef, int32_t *d_ret, hipStream_t s)
 {
-    if (!p || !d_source || !d_sample || !d_coef) return fail("asx_xcorr_batch_f32_dev: null argument");
-    std::lock_guard<std::mutex> guard(p->lock);
-    DevGuard dg(p->device);
-    if (!dg.ok) return fail("cannot select device %d", p->device);
-    hipStream_t s = stream ? (hipStream_t)stream : p->stream;
-    const size_t N = p->host.N;
-    if (p->tune_placement && !p->placement_done && batch >= std::min<size_t>(p->group, 8) && // (lane 0's workspaces; a second lane keeps its own)
-        tune_placement(p, d_source, d_sample, std::min(batch, p->group), s))
-        return -1;
     prof_begin_call(p);
     // chunking: groups of at most `group` pairs; with two lanes a batch is cut into at least two
     // chunks (when it is big enough to fill the chip twice) that alternate between the lanes
@@ -872,8 +906,8 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
             const size_t g = std::min(chunk, w0 + wn - done);
             const int lane = overlap ? (int)(gi & 1) : 0;
             hipStream_t ls = overlap ? p->lanes[lane].stream : s;
-            if (run_group<float>(p, d_source + done * 2 * N, d_sample + done * N, d_source + done * 2 * N,
-                                 d_sample + done * N, g, d_lag ? d_lag + done : nullptr, d_coef + done,
+            const float *src = d_source + done * src_step, *smp = d_sample + done * smp_step;
+            if (run_group<float>(p, src, src_step, smp, smp_step, src, smp, bc, g, d_lag ? d_lag + done : nullptr, d_coef + done,
                                  d_ret ? d_ret + done : nullptr, nullptr, ls, gi, lane, (uint32_t)(done - w0), p->exact))
                 return -1;
         }
@@ -884,73 +918,35 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
             }
         }
         // the second look, behind the window's last group (one host synchronisation per window)
+        const float *src = d_source + w0 * src_step, *smp = d_sample + w0 * smp_step;
         if (p->exact &&
-            resolve_overflows<float>(p, d_sample + w0 * N, d_source + w0 * 2 * N, d_sample + w0 * N,
-                                     d_lag ? d_lag + w0 : nullptr, d_coef + w0, d_ret ? d_ret + w0 : nullptr, s) < 0)
+            resolve_overflows<float>(p, smp, src, smp, src_step, smp_step, d_lag ? d_lag + w0 : nullptr, d_coef + w0,
+                                     d_ret ? d_ret + w0 : nullptr, s) < 0)
             return -1;
     }
     prof_end_call(p, gi);
     return 0;
 }
 
+extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const float *d_sample,
+                                       size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret,
+                                       void *stream)
+{
+    if (!p || !d_source || !d_sample || !d_coef) return fail("asx_xcorr_batch_f32_dev: null argument");
+    std::lock_guard<std::mutex> guard(p->lock);
+    DevGuard dg(p->device);
+    if (!dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+    const size_t N = p->host.N;
+    if (p->tune_placement && !p->placement_done && batch >= std::min<size_t>(p->group, 8) && // (lane 0's workspaces; a second lane keeps its own)
+        tune_placement(p, d_source, d_sample, std::min(batch, p->group), s))
+        return -1;
+    return run_batch(p, d_source, 2 * N, d_sample, N, 0, batch, d_lag, d_coef, d_ret, s);
+}
+
 // ---------------------------------------------------------------------------
 // strided batches: one track against many (asx_xcorr_strided_f32_dev)
 // ---------------------------------------------------------------------------
-// One group of a strided call: pair k = source d_src + k*ss, sample d_smp + k*ms.  bc bit 0 / 1: the source / sample is the call's
-// broadcast track, whose forward column pass is already in the plan's slot (real-column plans): only the other operand is
-// transformed here.  Everything behind the transforms is run_group's, with the caller's strides where the inputs are read again.
-static int run_group_strided(asx_plan *p, const float *d_src, size_t ss, const float *d_smp, size_t ms, size_t g, int bc,
-                             int64_t *d_lag, double *d_coef, int32_t *d_ret, hipStream_t s, size_t group_index, int lane,
-                             uint32_t pair_base, bool listed)
-{
-    const AsxDev &P = p->dev;
-    asx_plan::Lane &W = p->lanes[lane];
-    AsxPeakWs fin = W.pk;
-    if (!listed) { fin.over_list = nullptr; fin.over_n = nullptr; fin.over_host = nullptr; fin.over_cap = 0; }
-    const bool spectral = p->spectral && W.pk.band;
-    AsxPeakWs tk = W.pk;
-    if (!spectral) { tk.band = nullptr; tk.tile_peak = nullptr; }
-    const size_t e0 = group_index * 6;
-    if (prof_mark(p, s, e0 + 0)) return -1;
-    if (P.rlayout) {
-        const int op0 = (bc & 1) ? 1 : 0, nops = 2 - (bc & 1) - ((bc >> 1) & 1);
-        if (nops > 0 &&
-            !asx_launch_fwd_cols_r1(P, d_src, ss, d_smp, ms, W.zxa, W.zya, W.pk.nrm_part, tk.band, (int)g, op0, nops, false, s))
-            return fail("internal: no forward column kernel for this plan");
-        for (unsigned which = 0; which < 2; which++)
-            if (bc & (1 << which)) asx_launch_bcast_aux(P, p->bslot.nrm, p->bslot.band, W.pk.nrm_part, tk.band, (int)g, which, s);
-    } else {
-        // packed plans: the contiguous forward kernel once per pair at the pair's own inputs (no broadcast slot: every pair
-        // transforms its own copy of a shared track)
-        for (size_t k = 0; k < g; k++) {
-            AsxPeakWs one = tk;
-            one.nrm_part = W.pk.nrm_part + k * 2 * (size_t)P.ntiles;
-            asx_launch_fwd_cols(P, d_src + k * ss, d_smp + k * ms, W.zxa + k * (size_t)P.M, W.zya + k * (size_t)P.M, one, 1, s);
-        }
-    }
-    if (prof_mark(p, s, e0 + 1)) return -1;
-    if (P.rlayout) {
-        if (!asx_launch_rows_rb(P, (bc & 1) ? p->bslot.cx : W.zxa, (bc & 2) ? p->bslot.cy : W.zya, W.ga, tk, (int)g, bc, s))
-            return fail("internal: no row kernel for this plan");
-    } else {
-        asx_launch_rows(P, W.zxa, W.zya, W.ga, tk, (int)g, s);
-    }
-    if (prof_mark(p, s, e0 + 2)) return -1;
-    asx_launch_inv_cols(P, W.ga, tk, nullptr, (int)g, s);
-    if (prof_mark(p, s, e0 + 3)) return -1;
-    asx_launch_finalize(P, fin, W.seg, (int)g, s, pair_base);
-    const int dot_blocks = (int)std::min<size_t>(ASX_DOT_BLOCKS, std::max<size_t>(8, 16384 / g));
-    asx_launch_refine_f32_strided(P, d_src, ss, d_smp, ms, W.pk, W.seg, (int)g, s, dot_blocks, !spectral);
-    if (prof_mark(p, s, e0 + 4)) return -1;
-    if (spectral)
-        asx_launch_pearson_spectral_f32_strided(P, d_src, ss, d_smp, ms, tk, W.spec, W.seg, W.psums, d_lag, d_coef, d_ret, (int)g, s);
-    else
-        asx_launch_pearson_f32(d_src, d_smp, ss, ms, P.N, W.seg, W.psums, d_lag, d_coef, d_ret, (int)g, s);
-    if (prof_mark(p, s, e0 + 5)) return -1;
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
                                          size_t sample_stride, size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret,
                                          void *stream)
@@ -989,45 +985,10 @@ extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, siz
         }
         // the shared track's forward column pass: once per call, on the caller's stream, before any lane forks
         const int op0 = (bc & 1) ? 0 : 1, nops = bc == 3 ? 2 : 1;
-        if (!asx_launch_fwd_cols_r1(P, d_source, 0, d_sample, 0, B.cx, B.cy, B.nrm, B.band, 1, op0, nops, true, s))
+        if (!asx_launch_fwd_cols_r(P, d_source, 0, d_sample, 0, B.cx, B.cy, B.nrm, B.band, 1, op0, nops, true, s))
             return fail("internal: no forward column kernel for this plan");
     }
-    prof_begin_call(p);
-    // chunking, lanes and windows exactly as asx_xcorr_batch_f32_dev
-    const bool overlap = (p->nlanes == 2) && !p->profiling && batch >= 8;
-    size_t chunk = p->group;
-    if (overlap && batch < 2 * chunk) chunk = (batch + 1) / 2;
-    const size_t window = p->exact ? std::max<size_t>(chunk, p->over_cap / chunk * chunk) : batch;
-    size_t gi = 0;
-    for (size_t w0 = 0; w0 < batch; w0 += window) {
-        const size_t wn = std::min(window, batch - w0);
-        if (overlap) {
-            HIP_TRY(hipEventRecord(p->fork, s));
-            for (int l = 0; l < 2; l++) HIP_TRY(hipStreamWaitEvent(p->lanes[l].stream, p->fork, 0));
-        }
-        for (size_t done = w0; done < w0 + wn; done += chunk, gi++) {
-            const size_t g = std::min(chunk, w0 + wn - done);
-            const int lane = overlap ? (int)(gi & 1) : 0;
-            hipStream_t ls = overlap ? p->lanes[lane].stream : s;
-            if (run_group_strided(p, d_source + done * source_stride, source_stride, d_sample + done * sample_stride, sample_stride, g,
-                                  bc, d_lag ? d_lag + done : nullptr, d_coef + done, d_ret ? d_ret + done : nullptr, ls, gi, lane,
-                                  (uint32_t)(done - w0), p->exact))
-                return -1;
-        }
-        if (overlap) {
-            for (int l = 0; l < 2; l++) {
-                HIP_TRY(hipEventRecord(p->lanes[l].done, p->lanes[l].stream));
-                HIP_TRY(hipStreamWaitEvent(s, p->lanes[l].done, 0));
-            }
-        }
-        if (p->exact &&
-            resolve_overflows<float>(p, d_sample + w0 * sample_stride, d_source + w0 * source_stride, d_sample + w0 * sample_stride,
-                                     d_lag ? d_lag + w0 : nullptr, d_coef + w0, d_ret ? d_ret + w0 : nullptr, s, source_stride,
-                                     sample_stride) < 0)
-            return -1;
-    }
-    prof_end_call(p, gi);
-    return 0;
+    return run_batch(p, d_source, source_stride, d_sample, sample_stride, bc, batch, d_lag, d_coef, d_ret, s);
 }
 
 extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const float *d_sample,
@@ -1042,9 +1003,11 @@ extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const f
     prof_begin_call(p);
     // like every other entry point: listed and looked at again in the exact mode, only marked (ret = 1) otherwise
     // (the direct Pearson form: this entry point exists to compare decompositions and to dump r)
-    int rc = run_group<float>(p, d_source, d_sample, d_source, d_sample, 1, d_lag, d_coef, d_ret, d_r, s, 0, 0, 0, p->exact, false);
+    const size_t N = p->host.N;
+    int rc = run_group<float>(p, d_source, 2 * N, d_sample, N, d_source, d_sample, 0, 1, d_lag, d_coef, d_ret, d_r, s, 0, 0, 0, p->exact,
+                              false);
     prof_end_call(p, 1);
-    if (rc == 0 && p->exact && resolve_overflows<float>(p, d_sample, d_source, d_sample, d_lag, d_coef, d_ret, s) < 0) rc = -1;
+    if (rc == 0 && p->exact && resolve_overflows<float>(p, d_sample, d_source, d_sample, 2 * N, N, d_lag, d_coef, d_ret, s) < 0) rc = -1;
     return rc;
 }
 
@@ -1073,19 +1036,11 @@ extern "C" int asx_xcorr_batch_f32(asx_plan *p, const float *source, const float
         const size_t g = std::min(p->group, batch - done);
         HIP_TRY(hipMemcpyAsync(p->st_src, source + done * 2 * N, g * 2 * N * sizeof(float), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(p->st_smp, sample + done * N, g * N * sizeof(float), hipMemcpyHostToDevice, s));
-        if (run_group<float>(p, p->st_src, p->st_smp, p->st_src, p->st_smp, g, p->st_lag, p->st_coef,
-                             p->st_ret, nullptr, s, 0))
+        if (run_group<float>(p, p->st_src, 2 * N, p->st_smp, N, p->st_src, p->st_smp, 0, g, p->st_lag, p->st_coef, p->st_ret, nullptr,
+                             s, 0) ||
+            fetch_results<float>(p, p->st_smp, p->st_src, p->st_smp, g, p->st_lag, p->st_coef, p->st_ret, lag + done, coef + done,
+                                 ret + done, s))
             return -1;
-        // the results come back with the same synchronisation that looks at the overflow list; again behind a second look
-        for (int pass = 0; pass < 2; pass++) {
-            HIP_TRY(hipMemcpyAsync(lag + done, p->st_lag, g * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(coef + done, p->st_coef, g * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(ret + done, p->st_ret, g * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            if (pass == 1) { HIP_TRY(hipStreamSynchronize(s)); break; }
-            const int looked = resolve_overflows<float>(p, p->st_smp, p->st_src, p->st_smp, p->st_lag, p->st_coef, p->st_ret, s);
-            if (looked < 0) return -1;
-            if (looked == 0) break;
-        }
     }
     return 0;
 }
@@ -1358,32 +1313,26 @@ extern "C" int asx_xcorr_f64(asx_plan *p, const double *source, const double *sa
     }
     if (narrow == 1) {
         p->narrowed++;
-        if (run_group<float>(p, p->st_src, p->st_smp, p->st_src, p->st_smp, 1, p->st_lag, p->st_coef, p->st_ret, nullptr, s, 0, 0, 0,
-                             true, false))
+        if (run_group<float>(p, p->st_src, 2 * N, p->st_smp, N, p->st_src, p->st_smp, 0, 1, p->st_lag, p->st_coef, p->st_ret, nullptr, s,
+                             0, 0, 0, true, false))
             return -1;
     } else {
     HIP_TRY(hipMemcpyAsync(p->st_src64, source, 2 * N * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(p->st_smp64, sample, N * sizeof(double), hipMemcpyHostToDevice, s));
     asx_launch_cvt_f64_f32(p->st_src64, p->st_src, 2 * N, s);
     asx_launch_cvt_f64_f32(p->st_smp64, p->st_smp, N, s);
-    if (run_group<double>(p, p->st_src, p->st_smp, p->st_src64, p->st_smp64, 1, p->st_lag, p->st_coef,
-                          p->st_ret, nullptr, s, 0))
+    if (run_group<double>(p, p->st_src, 2 * N, p->st_smp, N, p->st_src64, p->st_smp64, 0, 1, p->st_lag, p->st_coef, p->st_ret, nullptr,
+                          s, 0))
         return -1;
     }
     int64_t h_lag = 0;
     double h_coef = 0;
     int32_t h_ret = -1;
-    // the result comes back with the same synchronisation that looks at the overflow list; again behind a second look
-    for (int pass = 0; pass < 2; pass++) {
-        HIP_TRY(hipMemcpyAsync(&h_lag, p->st_lag, sizeof(h_lag), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&h_coef, p->st_coef, sizeof(h_coef), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&h_ret, p->st_ret, sizeof(h_ret), hipMemcpyDeviceToHost, s));
-        if (pass == 1) { HIP_TRY(hipStreamSynchronize(s)); break; }
-        const int looked = narrow == 1 ? resolve_overflows<float>(p, p->st_smp, p->st_src, p->st_smp, p->st_lag, p->st_coef, p->st_ret, s)
-                                       : resolve_overflows<double>(p, p->st_smp, p->st_src64, p->st_smp64, p->st_lag, p->st_coef, p->st_ret, s);
-        if (looked < 0) return -1;
-        if (looked == 0) break;
-    }
+    if (narrow == 1 ? fetch_results<float>(p, p->st_smp, p->st_src, p->st_smp, 1, p->st_lag, p->st_coef, p->st_ret, &h_lag, &h_coef,
+                                           &h_ret, s)
+                    : fetch_results<double>(p, p->st_smp, p->st_src64, p->st_smp64, 1, p->st_lag, p->st_coef, p->st_ret, &h_lag, &h_coef,
+                                            &h_ret, s))
+        return -1;
     *lag = (long)h_lag;
     *coefficient = h_coef;
     return h_ret;
@@ -1597,21 +1546,13 @@ extern "C" int asx_stream_xcorr(asx_stream *st, size_t sample_len, long *lag, do
     if (!dg.ok) return fail("cannot select device %d", st->device);
     hipStream_t s = p->stream;
     prof_begin_call(p);
-    if (run_group<double>(p, st->src32, st->smp32, st->src64, st->smp64, 1, st->d_lag, st->d_coef, st->d_ret,
-                          nullptr, s, 0))
-        return -1;
     int64_t h_lag = 0;
     double h_coef = 0;
     int32_t h_ret = -1;
-    for (int pass = 0; pass < 2; pass++) { // as in asx_xcorr_f64
-        HIP_TRY(hipMemcpyAsync(&h_lag, st->d_lag, sizeof(h_lag), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&h_coef, st->d_coef, sizeof(h_coef), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&h_ret, st->d_ret, sizeof(h_ret), hipMemcpyDeviceToHost, s));
-        if (pass == 1) { HIP_TRY(hipStreamSynchronize(s)); break; }
-        const int looked = resolve_overflows<double>(p, st->smp32, st->src64, st->smp64, st->d_lag, st->d_coef, st->d_ret, s);
-        if (looked < 0) return -1;
-        if (looked == 0) break;
-    }
+    if (run_group<double>(p, st->src32, 2 * sample_len, st->smp32, sample_len, st->src64, st->smp64, 0, 1, st->d_lag, st->d_coef,
+                          st->d_ret, nullptr, s, 0) ||
+        fetch_results<double>(p, st->smp32, st->src64, st->smp64, 1, st->d_lag, st->d_coef, st->d_ret, &h_lag, &h_coef, &h_ret, s))
+        return -1;
     *lag = (long)h_lag;
     *coefficient = h_coef;
     return h_ret;

@@ -159,30 +159,24 @@ void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, floa
                      const AsxPeakWs &W, int npairs, hipStream_t s);
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out,
                          int npairs, hipStream_t s);
-// rlayout.hip: the real-column decomposition (production lengths); false = no kernel compiled in for this plan
-bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs,
+// rlayout.hip: the real-column decomposition (production lengths); false = no kernel compiled in for this plan.
+// bc (the broadcast forms of asx_xcorr_strided_f32_dev): bit 0 = cx is the plan's broadcast slot (one C for every pair), bit 1 = cy is
+bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
                        hipStream_t s);
-bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, const float *smp, float2 *cx, float2 *cy, const AsxPeakWs &W,
-                           int npairs, hipStream_t s);
+bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
+                           float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s);
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s);
-// broadcast / strided forms (asx_xcorr_strided_f32_dev): bc bit 0 = cx is the plan's broadcast slot (one C for every pair), bit 1 = cy is
-bool asx_launch_rows_rb(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
-                        hipStream_t s);
-bool asx_launch_fwd_cols_r1(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
-                            float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 bool asx_rlayout_available(const AsxDev &P); // all three kernels compiled in for this plan's schedules
 int asx_rlayout_band_rows(const AsxDev &P);
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base = 0);
-void asx_launch_refine_f32(const AsxDev &P, const float *src, const float *smp, const AsxPeakWs &W,
+// the pairs' inputs are src_pitch / smp_pitch elements apart (0 = one track for every pair)
+void asx_launch_refine_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch, const AsxPeakWs &W,
                            AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks = ASX_DOT_BLOCKS, bool pick = true);
                            // pick = false: the exact values only; the caller's next kernel applies the rule (k_pearson_prep)
-// the same with the pairs' inputs src_pitch / smp_pitch floats apart (0 = one track for every pair)
-void asx_launch_refine_f32_strided(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
-                                   const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick);
-void asx_launch_refine_f64(const AsxDev &P, const double *src, const double *smp, const AsxPeakWs &W,
-                           AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks = ASX_DOT_BLOCKS);
+void asx_launch_refine_f64(const AsxDev &P, const double *src, size_t src_pitch, const double *smp, size_t smp_pitch,
+                           const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks = ASX_DOT_BLOCKS);
 void asx_launch_pearson_f32(const float *src, const float *smp, size_t src_pitch, size_t smp_pitch,
                             uint32_t basis_len, const AsxSeg *seg, double *psums, int64_t *lag,
                             double *coef, int32_t *ret, int npairs, hipStream_t s);
@@ -192,14 +186,11 @@ void asx_launch_pearson_f64(const double *src, const double *smp, size_t src_pit
 // the partial-sum kernel alone (the spectral form runs it on its own segment list, pearson_spectral.hip)
 void asx_launch_pearson_partial_spec_f32(const float *src, const float *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len,
                                          const AsxSeg *seg, const AsxSpecWs &S, double *psums, int npairs, hipStream_t s);
-// pearson_spectral.hip: float32 inputs, real-column plans (W.band and W.tile_peak filled by this group's transform kernels)
-void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, const float *smp, const AsxPeakWs &W, const AsxSpecWs &S,
-                                     AsxSeg *seg, double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs,
-                                     hipStream_t s);
-// the same with the pairs' inputs src_pitch / smp_pitch floats apart (0 = one track for every pair)
-void asx_launch_pearson_spectral_f32_strided(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
-                                             const AsxPeakWs &W, const AsxSpecWs &S, AsxSeg *seg, double *psums, int64_t *lag,
-                                             double *coef, int32_t *ret, int npairs, hipStream_t s);
+// pearson_spectral.hip: float32 inputs src_pitch / smp_pitch floats apart, real-column plans (W.band and W.tile_peak filled by this
+// group's transform kernels)
+void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
+                                     const AsxPeakWs &W, const AsxSpecWs &S, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
+                                     int32_t *ret, int npairs, hipStream_t s);
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
                               double min_confidence, double sample_rate, int64_t *lag_ms, int32_t *accept,
                               hipStream_t s);

@@ -139,11 +139,10 @@ template <int NTP> __device__ __forceinline__ void block_sum4(double (&v)[4], do
 // four sums; the kernels behind this one add the shares in block order (asx_spec_pick): the same bits whoever adds them, and NB is a
 // constant of the plan (the same pair takes the same tree alone, in a batch, on another shard).  No merged record, hence no fence and no
 // ticket: profiles/r5_experiments/18_* (one block per pair: 25 us for a single pair behind ONE block's loads) and 22_*.
-// (body shared with k_pearson_prep_s: src_pitch / smp_pitch are the pairs' input steps in floats, 0 = one track for every pair)
-template <int NTP, int NB> __device__ __forceinline__ void pearson_prep_body(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
-                                                                            const float *__restrict__ smp, size_t src_pitch,
-                                                                            size_t smp_pitch, AsxPeakWs W, AsxSpecWs S,
-                                                                            AsxSeg *__restrict__ seg)
+// src_pitch / smp_pitch: the pairs' input steps in floats (0 = one track for every pair).
+template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
+                                                                    const float *__restrict__ smp, size_t src_pitch, size_t smp_pitch,
+                                                                    AsxPeakWs W, AsxSpecWs S, AsxSeg *__restrict__ seg)
 {
     __shared__ double red[4][NTP / 64];
     __shared__ double s_exact;
@@ -228,19 +227,6 @@ template <int NTP, int NB> __device__ __forceinline__ void pearson_prep_body(con
     }
 }
 
-template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
-                                                                    const float *__restrict__ smp, AsxPeakWs W, AsxSpecWs S,
-                                                                    AsxSeg *__restrict__ seg)
-{
-    pearson_prep_body<NTP, NB>(Pp, src, smp, (size_t)(2u * Pp->N), (size_t)Pp->N, W, S, seg);
-}
-template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep_s(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
-                                                                      const float *__restrict__ smp, size_t src_pitch, size_t smp_pitch,
-                                                                      AsxPeakWs W, AsxSpecWs S, AsxSeg *__restrict__ seg)
-{
-    pearson_prep_body<NTP, NB>(Pp, src, smp, src_pitch, smp_pitch, W, S, seg);
-}
-
 // grid (npairs), one wave per pair: k_pearson_final (xcorr_kernels.hip) with the two spectral modes in front of it.
 __global__ __launch_bounds__(64) void k_pearson_final_spec(const AsxSeg *__restrict__ seg, const double *__restrict__ psums, uint32_t nb,
                                                             AsxSpecWs S, int64_t *__restrict__ lag,
@@ -280,36 +266,19 @@ __global__ __launch_bounds__(64) void k_pearson_final_spec(const AsxSeg *__restr
     }
 }
 
-void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, const float *smp, const AsxPeakWs &W, const AsxSpecWs &S0,
-                                     AsxSeg *seg, double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs,
-                                     hipStream_t s)
+void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
+                                     const AsxPeakWs &W, const AsxSpecWs &S0, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
+                                     int32_t *ret, int npairs, hipStream_t s)
 {
     AsxSpecWs S = S0;
     S.N = P.N;
     if ((size_t)P.band_rows * (size_t)P.M2 >= 16384) {
         S.nb = ASX_PREP_BLOCKS;
-        hipLaunchKernelGGL((k_pearson_prep<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0, s, P.self_dev, src, smp, W, S, seg);
-    } else {
-        S.nb = 1;
-        hipLaunchKernelGGL((k_pearson_prep<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, W, S, seg);
-    }
-    asx_launch_pearson_partial_spec_f32(src, smp, 2 * (size_t)P.N, P.N, P.N, seg, S, psums, npairs, s);
-    hipLaunchKernelGGL(k_pearson_final_spec, dim3(npairs), dim3(64), 0, s, seg, psums, asx_pearson_blocks(P.N), S, lag, coef, ret);
-}
-
-void asx_launch_pearson_spectral_f32_strided(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
-                                             const AsxPeakWs &W, const AsxSpecWs &S0, AsxSeg *seg, double *psums, int64_t *lag,
-                                             double *coef, int32_t *ret, int npairs, hipStream_t s)
-{
-    AsxSpecWs S = S0;
-    S.N = P.N;
-    if ((size_t)P.band_rows * (size_t)P.M2 >= 16384) {
-        S.nb = ASX_PREP_BLOCKS;
-        hipLaunchKernelGGL((k_pearson_prep_s<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0, s,
+        hipLaunchKernelGGL((k_pearson_prep<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0, s,
                            P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg);
     } else {
         S.nb = 1;
-        hipLaunchKernelGGL((k_pearson_prep_s<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg);
+        hipLaunchKernelGGL((k_pearson_prep<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg);
     }
     asx_launch_pearson_partial_spec_f32(src, smp, src_pitch, smp_pitch, P.N, seg, S, psums, npairs, s);
     hipLaunchKernelGGL(k_pearson_final_spec, dim3(npairs), dim3(64), 0, s, seg, psums, asx_pearson_blocks(P.N), S, lag, coef, ret);

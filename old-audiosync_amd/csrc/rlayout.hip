@@ -191,11 +191,13 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 //                store phase, Q[j] = A[j] + conj(w_M2^j) B[j], Q[j+n] = A[j] - conj(w_M2^j) B[j].  This is how the two
 //                longest reference lengths get 600- and 400-row column tiles of sixteen real columns (64-byte input
 //                pieces, whole 128-byte lines of C and Q) instead of 1200 / 800 rows of eight.
+//   BC: broadcast forms (asx_xcorr_strided_f32_dev).  Bit 0 = C_x is the plan's broadcast slot, one C for every pair (pair step
+//   0, temporal loads: every pair reads it, it must stay in the caches), bit 1 = C_y is.  BC = 0: both have Q's pair step.
 // ---------------------------------------------------------------------------
-// The body is shared with k_rows_rb (broadcast forms, asx_xcorr_strided_f32_dev): pitch_x / pitch_y / pitch_q are the pair steps of
-// C_x, C_y and Q (0 = one C for every pair, the plan's broadcast slot), XNT / YNT whether the C loads are non-temporal (a broadcast C
-// is read by every pair: it must stay in the caches).
-template <class S, int NT, bool TWO, bool XNT, bool YNT>
+// The body takes P and W by value: that call boundary loads their fields at the top of the kernel.  Written inside the __global__
+// itself the instruction stream changes, and with it the float32 rounding of r (11 of the headline's 124 coefficients moved by
+// about 1e-7).
+template <class S, int NT, bool TWO, int BC>
 __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restrict__ cx, const float2 *__restrict__ cy,
                                             float2 *__restrict__ qo, int nrows, size_t pitch_x, size_t pitch_y, size_t pitch_q,
                                             AsxPeakWs W)
@@ -214,6 +216,7 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
     constexpr int HALF = NS / 2, WSTEPS = (HALF + NTB - 1) / NTB;
     constexpr int LPU = R1 > R2 ? R1 : R2, UPW = 64 / LPU, NW = NT / 64;
     static_assert(NT % 64 == 0 && UPW >= 1, "whole waves");
+    constexpr bool XNT = (BC & 1) == 0, YNT = (BC & 2) == 0;
 
 #ifdef ASX_STAMPS
     const long long t_entry = clock64(), w_entry = wall_clock64();
@@ -460,22 +463,12 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
 #endif
 }
 
-template <class S, int NT, bool TWO>
+template <class S, int NT, bool TWO, int BC>
 __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_r(const RArgs P, const float2 *__restrict__ cx,
                                                                                 const float2 *__restrict__ cy, float2 *__restrict__ qo,
                                                                                 int nrows, size_t pair_pitch, AsxPeakWs W)
 {
-    rows_r_body<S, NT, TWO, true, true>(P, cx, cy, qo, nrows, pair_pitch, pair_pitch, pair_pitch, W);
-}
-
-// Broadcast forms: BC bit 0 = C_x is the plan's broadcast slot (pitch_x = 0, temporal loads), bit 1 = C_y is.
-template <class S, int NT, bool TWO, int BC>
-__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rb(const RArgs P, const float2 *__restrict__ cx,
-                                                                                 const float2 *__restrict__ cy, float2 *__restrict__ qo,
-                                                                                 int nrows, size_t pitch_x, size_t pitch_y,
-                                                                                 size_t pitch_q, AsxPeakWs W)
-{
-    rows_r_body<S, NT, TWO, (BC & 1) == 0, (BC & 2) == 0>(P, cx, cy, qo, nrows, pitch_x, pitch_y, pitch_q, W);
+    rows_r_body<S, NT, TWO, BC>(P, cx, cy, qo, nrows, (BC & 1) ? 0 : pair_pitch, (BC & 2) ? 0 : pair_pitch, pair_pitch, W);
 }
 
 // ---------------------------------------------------------------------------
@@ -521,22 +514,23 @@ template <int NITEMS, int H, int NT> __device__ __forceinline__ int rcol_item_of
 #define ASX_RCOL_LOADS 5 // row-pair pieces (two 16-byte loads each) a thread keeps in flight
 #endif
 
-// k_fwd_cols_r: grid (tiles, {source, sample}, npairs).  r2c column transforms of length 2 M1 (the zero half of the
+// k_fwd_cols_r: grid (tiles, nops, npairs).  r2c column transforms of length 2 M1 (the zero half of the
 // sample -- rows j1 >= M1 -- is never loaded, src/cross_correlation.c:159-166): M1-point complex transform of the
 // packed rows, untangling between the slots of u and M1 - u, rows u and M1 - u of C (twice its value: the factor
 // is taken back by k_rows_r) stored in natural row order.
-// The body is shared with k_fwd_cols_r1 (asx_xcorr_strided_f32_dev): `which` = 0 source, 1 sample; src_stride / smp_stride = the
-// pair steps of the inputs in floats (0 = one track for every pair); NTS = non-temporal stores of C (false for the broadcast slot,
-// which every pair's k_rows_rb block reads).
+// A block transforms operand op0 + blockIdx.y (0 source, 1 sample) of pair blockIdx.z, whose inputs are src_stride / smp_stride
+// floats apart (0 = one track for every pair).  NTS = non-temporal stores of C (false for the plan's broadcast slot, which every
+// pair's k_rows_r block reads).
 template <class S1, int TC, int NT, bool NTS>
-__device__ __forceinline__ void fwd_cols_r_body(const RArgs P, const float *__restrict__ src, const float *__restrict__ smp,
-                                                size_t src_stride, size_t smp_stride, float2 *__restrict__ cx,
-                                                float2 *__restrict__ cy, float *__restrict__ nrm_part, size_t pair_pitch,
-                                                float2 *__restrict__ band, unsigned which)
+__global__ __launch_bounds__(NT, 4) void k_fwd_cols_r(const RArgs P, const float *__restrict__ src, const float *__restrict__ smp,
+                                                       size_t src_stride, size_t smp_stride, float2 *__restrict__ cx,
+                                                       float2 *__restrict__ cy, float *__restrict__ nrm_part, size_t pair_pitch,
+                                                       float2 *__restrict__ band, unsigned op0)
 {
     constexpr int M1 = S1::n, T = TC, logT = asx_ilog2(TC), H = T / 2, logH = logT - 1, Q4 = T / 4, logQ4 = logT - 2;
     static_assert(T >= 4 && (M1 & 1) == 0, "four real columns per 16-byte load, an even number of packed rows");
     __shared__ float nrm_red[NT / 64];
+    const unsigned which = op0 + blockIdx.y;
     const bool is_smp = which != 0;
     const size_t pair = blockIdx.z;
     const int tile = rcol_tile_of_block(blockIdx.x, logT);
@@ -675,28 +669,8 @@ __device__ __forceinline__ void fwd_cols_r_body(const RArgs P, const float *__re
     }
 }
 
-template <class S1, int TC, int NT>
-__global__ __launch_bounds__(NT, 4) void k_fwd_cols_r(const RArgs P, const float *__restrict__ src,
-                                                       const float *__restrict__ smp, float2 *__restrict__ cx,
-                                                       float2 *__restrict__ cy, float *__restrict__ nrm_part, size_t pair_pitch,
-                                                       float2 *__restrict__ band)
-{
-    fwd_cols_r_body<S1, TC, NT, true>(P, src, smp, (size_t)(2u * P.N), (size_t)P.N, cx, cy, nrm_part, pair_pitch, band, blockIdx.y);
-}
-
-// grid (tiles, nops, npairs): operand op0 + blockIdx.y of every pair, inputs at the caller's strides.  NTS = false: into the plan's
-// broadcast slot (npairs = 1).
-template <class S1, int TC, int NT, bool NTS>
-__global__ __launch_bounds__(NT, 4) void k_fwd_cols_r1(const RArgs P, const float *__restrict__ src, const float *__restrict__ smp,
-                                                        size_t src_stride, size_t smp_stride, float2 *__restrict__ cx,
-                                                        float2 *__restrict__ cy, float *__restrict__ nrm_part, size_t pair_pitch,
-                                                        float2 *__restrict__ band, unsigned op0)
-{
-    fwd_cols_r_body<S1, TC, NT, NTS>(P, src, smp, src_stride, smp_stride, cx, cy, nrm_part, pair_pitch, band, op0 + blockIdx.y);
-}
-
 // grid (ceil(per / 256), npairs): the broadcast operand's norm partials and band sums (the slot's pair 0, operand `which`) into
-// every pair's place in the group's workspaces, where k_rows_r* and the spectral Pearson form read them.  per = ntiles (norms)
+// every pair's place in the group's workspaces, where k_rows_r and the spectral Pearson form read them.  per = ntiles (norms)
 // + ntiles * nbands (band sums, when band != null).
 __global__ __launch_bounds__(256) void k_bcast_aux(const float *__restrict__ snrm, const float2 *__restrict__ sband,
                                                     float *__restrict__ nrm, float2 *__restrict__ band, int ntiles, int nbands,
@@ -975,17 +949,25 @@ static bool schedule_is_r(const AsxStages &st, int n, std::initializer_list<int>
     return true;
 }
 
-bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs,
+// bc: the broadcast form (k_rows_r's BC); the operands that are not broadcast and q have the group workspace's pair pitch
+bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
                        hipStream_t s)
 {
     const int nrows = P.M1 + 1;
     const size_t pitch = (size_t)nrows * (size_t)P.M2;
     const size_t lds = (size_t)P.M2 * sizeof(float4);
     // chosen by the row length alone: these kernels carry their own schedule and only read the plan's w_M2 table
+#define ASX_ROWSR_LAUNCH(b, nt, two, n, ...)                                                                                    \
+    hipLaunchKernelGGL((k_rows_r<Sched<n, __VA_ARGS__>, nt, two, b>), dim3((unsigned)nrows * (unsigned)npairs),                 \
+                       dim3((two) ? 2 * nt : nt), lds, s, rargs_of(P), cx, cy, q, nrows, pitch, W);
 #define ASX_ROWSR_CASE(nt, two, n, ...)                                                                                         \
     if (P.M2 == ((two) ? 2 * n : n)) {                                                                                          \
-        hipLaunchKernelGGL((k_rows_r<Sched<n, __VA_ARGS__>, nt, two>), dim3((unsigned)nrows * (unsigned)npairs),                \
-                           dim3((two) ? 2 * nt : nt), lds, s, rargs_of(P), cx, cy, q, nrows, pitch, W);                          \
+        switch (bc) {                                                                                                           \
+        case 0: ASX_ROWSR_LAUNCH(0, nt, two, n, __VA_ARGS__) break;                                                             \
+        case 1: ASX_ROWSR_LAUNCH(1, nt, two, n, __VA_ARGS__) break;                                                             \
+        case 2: ASX_ROWSR_LAUNCH(2, nt, two, n, __VA_ARGS__) break;                                                             \
+        default: ASX_ROWSR_LAUNCH(3, nt, two, n, __VA_ARGS__) break;                                                            \
+        }                                                                                                                       \
         return true;                                                                                                            \
     }
     ASX_ROWSR_CASE(128, false, 1200, 12, 10, 10)
@@ -995,34 +977,7 @@ bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, floa
     // pairs of N = 144 000, same box)
     ASX_ROWSR_CASE(64, false, 480, 10, 8, 6)
 #undef ASX_ROWSR_CASE
-    return false;
-}
-
-// Broadcast forms of the row kernel (asx_xcorr_strided_f32_dev): bc bit 0 = cx is the broadcast slot, bit 1 = cy is; the other
-// operand and q have the group workspace's pitch.  bc = 0 is k_rows_r itself.
-bool asx_launch_rows_rb(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
-                        hipStream_t s)
-{
-    if (bc == 0) return asx_launch_rows_r(P, cx, cy, q, W, npairs, s);
-    const int nrows = P.M1 + 1;
-    const size_t pitch = (size_t)nrows * (size_t)P.M2;
-    const size_t px = (bc & 1) ? 0 : pitch, py = (bc & 2) ? 0 : pitch;
-    const size_t lds = (size_t)P.M2 * sizeof(float4);
-#define ASX_ROWSRB_LAUNCH(b, nt, two, n, ...)                                                                                   \
-    hipLaunchKernelGGL((k_rows_rb<Sched<n, __VA_ARGS__>, nt, two, b>), dim3((unsigned)nrows * (unsigned)npairs),              \
-                       dim3((two) ? 2 * nt : nt), lds, s, rargs_of(P), cx, cy, q, nrows, px, py, pitch, W);
-#define ASX_ROWSRB_CASE(nt, two, n, ...)                                                                                        \
-    if (P.M2 == ((two) ? 2 * n : n)) {                                                                                          \
-        if (bc == 1) { ASX_ROWSRB_LAUNCH(1, nt, two, n, __VA_ARGS__) }                                                          \
-        else if (bc == 2) { ASX_ROWSRB_LAUNCH(2, nt, two, n, __VA_ARGS__) }                                                     \
-        else { ASX_ROWSRB_LAUNCH(3, nt, two, n, __VA_ARGS__) }                                                                  \
-        return true;                                                                                                            \
-    }
-    ASX_ROWSRB_CASE(128, false, 1200, 12, 10, 10)
-    ASX_ROWSRB_CASE(128, true, 1200, ASX_ROWS2_SCHED)
-    ASX_ROWSRB_CASE(64, false, 480, 10, 8, 6)
-#undef ASX_ROWSRB_CASE
-#undef ASX_ROWSRB_LAUNCH
+#undef ASX_ROWSR_LAUNCH
     return false;
 }
 
@@ -1059,37 +1014,19 @@ static unsigned resident_blocks(const void *fn, int nthreads, size_t lds)
     return n;
 }
 
-bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, const float *smp, float2 *cx, float2 *cy, const AsxPeakWs &W,
-                           int npairs, hipStream_t s)
-{
-    if (!P.col_pairs) return false;
-    const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, lds = (size_t)P.M1 * P.T * sizeof(float2);
-    const dim3 grid(rcol_grid_x(P.ntiles, P.logT), 2, npairs);
-#define ASX_TRY(m1, t, nt, ...)                                                                                             \
-    if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                                    \
-        allow_big_lds_r((const void *)k_fwd_cols_r<Sched<m1, __VA_ARGS__>, t, nt>, lds);                                    \
-        hipLaunchKernelGGL((k_fwd_cols_r<Sched<m1, __VA_ARGS__>, t, nt>), grid, dim3(nt), lds, s, rargs_of(P), src, smp, cx, cy, \
-                           W.nrm_part, pitch, W.band);                                                                      \
-        return true;                                                                                                        \
-    }
-    ASX_RCOLS(ASX_TRY)
-#undef ASX_TRY
-    return false;
-}
-
 // Forward columns of operands op0 .. op0 + nops - 1 (0 source, 1 sample) of npairs pairs whose inputs are src_stride / smp_stride
 // floats apart, into cx / cy (pair pitch (M1 + 1) M2), nrm (AsxPeakWs::nrm_part layout) and band (AsxPeakWs::band layout, or null).
 // temporal: C stored with ordinary stores (the broadcast slot).
-bool asx_launch_fwd_cols_r1(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
-                            float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s)
+bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
+                           float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s)
 {
     if (!P.col_pairs) return false;
     const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, lds = (size_t)P.M1 * P.T * sizeof(float2);
     const dim3 grid(rcol_grid_x(P.ntiles, P.logT), (unsigned)nops, npairs);
 #define ASX_TRY1(nts, m1, t, nt, ...)                                                                                        \
     {                                                                                                                       \
-        allow_big_lds_r((const void *)k_fwd_cols_r1<Sched<m1, __VA_ARGS__>, t, nt, nts>, lds);                              \
-        hipLaunchKernelGGL((k_fwd_cols_r1<Sched<m1, __VA_ARGS__>, t, nt, nts>), grid, dim3(nt), lds, s, rargs_of(P), src, smp, \
+        allow_big_lds_r((const void *)k_fwd_cols_r<Sched<m1, __VA_ARGS__>, t, nt, nts>, lds);                               \
+        hipLaunchKernelGGL((k_fwd_cols_r<Sched<m1, __VA_ARGS__>, t, nt, nts>), grid, dim3(nt), lds, s, rargs_of(P), src, smp,  \
                            src_stride, smp_stride, cx, cy, nrm, pitch, band, (unsigned)op0);                                \
     }
 #define ASX_TRY(m1, t, nt, ...)                                                                                             \

@@ -928,10 +928,10 @@ __device__ __forceinline__ dd_t dd_add(dd_t a, dd_t b)
     return r;
 }
 
-// (body shared with k_refine_dots_s: src_pitch / smp_pitch are the pairs' input steps, 0 = one track for every pair)
+// src_pitch / smp_pitch: the pairs' input steps in elements (0 = one track for every pair)
 template <typename TIn>
-__device__ __forceinline__ void refine_dots_body(const AsxDev *__restrict__ Pp, const TIn *__restrict__ src, const TIn *__restrict__ smp,
-                                                 size_t src_pitch, size_t smp_pitch, AsxPeakWs W)
+__global__ __launch_bounds__(ASX_THREADS) void k_refine_dots(const AsxDev *__restrict__ Pp, const TIn *__restrict__ src,
+                                                              const TIn *__restrict__ smp, size_t src_pitch, size_t smp_pitch, AsxPeakWs W)
 {
     __shared__ double red[2][ASX_THREADS / 64];
     const size_t pair = blockIdx.y;
@@ -979,19 +979,6 @@ __device__ __forceinline__ void refine_dots_body(const AsxDev *__restrict__ Pp, 
         }
         __syncthreads();
     }
-}
-
-template <typename TIn>
-__global__ __launch_bounds__(ASX_THREADS) void k_refine_dots(const AsxDev *__restrict__ Pp, const TIn *__restrict__ src,
-                                                              const TIn *__restrict__ smp, AsxPeakWs W)
-{
-    refine_dots_body<TIn>(Pp, src, smp, (size_t)(2u * Pp->N), (size_t)Pp->N, W);
-}
-__global__ __launch_bounds__(ASX_THREADS) void k_refine_dots_s(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
-                                                                const float *__restrict__ smp, size_t src_pitch, size_t smp_pitch,
-                                                                AsxPeakWs W)
-{
-    refine_dots_body<float>(Pp, src, smp, src_pitch, smp_pitch, W);
 }
 
 // grid (npairs): the reference's max_abs_index rule (src/cross_correlation.c:52-67) on the exact values:
@@ -1509,7 +1496,8 @@ static bool generic_only()
 void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, float2 *zxa,
                          float2 *zya, const AsxPeakWs &W, int npairs, hipStream_t s)
 {
-    if (P.rlayout && asx_launch_fwd_cols_r(P, src, smp, zxa, zya, W, npairs, s)) return;
+    if (P.rlayout && asx_launch_fwd_cols_r(P, src, 2 * (size_t)P.N, smp, P.N, zxa, zya, W.nrm_part, W.band, npairs, 0, 2, false, s))
+        return;
     if (generic_only() || !asx_launch_fwd_cols_static(P, src, smp, zxa, zya, W, npairs, s))
         asx_launch_fwd_cols_generic(P, src, smp, zxa, zya, W, npairs, s);
 }
@@ -1517,7 +1505,7 @@ void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, fl
 void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga,
                      const AsxPeakWs &W, int npairs, hipStream_t s)
 {
-    if (P.rlayout && asx_launch_rows_r(P, zxa, zya, ga, W, npairs, s)) return;
+    if (P.rlayout && asx_launch_rows_r(P, zxa, zya, ga, W, npairs, 0, s)) return;
     if (generic_only() || !asx_launch_rows_static(P, zxa, zya, ga, W, npairs, s))
         asx_launch_rows_generic(P, zxa, zya, ga, W, npairs, s);
 }
@@ -1535,24 +1523,17 @@ void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int n
     hipLaunchKernelGGL(k_finalize, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base);
 }
 
-void asx_launch_refine_f32(const AsxDev &P, const float *src, const float *smp, const AsxPeakWs &W,
+void asx_launch_refine_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch, const AsxPeakWs &W,
                            AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick)
 {
-    hipLaunchKernelGGL(k_refine_dots<float>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, W);
+    hipLaunchKernelGGL(k_refine_dots<float>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
     if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg);
 }
 
-void asx_launch_refine_f32_strided(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
-                                   const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick)
+void asx_launch_refine_f64(const AsxDev &P, const double *src, size_t src_pitch, const double *smp, size_t smp_pitch,
+                           const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks)
 {
-    hipLaunchKernelGGL(k_refine_dots_s, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
-    if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg);
-}
-
-void asx_launch_refine_f64(const AsxDev &P, const double *src, const double *smp, const AsxPeakWs &W,
-                           AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks)
-{
-    hipLaunchKernelGGL(k_refine_dots<double>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, W);
+    hipLaunchKernelGGL(k_refine_dots<double>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
     hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg);
 }
 

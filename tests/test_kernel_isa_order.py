@@ -90,7 +90,7 @@ def positions(ins, pred):
 def test_two_half_row_kernel_issues_no_load_behind_a_barrier(isa):
     """k_rows_r, two-half form (N = 1 440 000, 960 000): every table look-up -- the load steps' w_M2 values, the stage seeds, the store
     phase's twiddles -- is issued in front of the first barrier; behind it the kernel only computes, exchanges through LDS and stores"""
-    ins = one(isa, "void k_rows_r<Sched<1200, 12, 10, 10>, 128, true>")
+    ins = one(isa, "void k_rows_r<Sched<1200, 12, 10, 10>, 128, true, 0>")
     barriers = positions(ins, lambda s: s.startswith("s_barrier"))
     loads = positions(ins, lambda s: s.startswith("global_load"))
     assert len(barriers) >= 4 and loads, (len(barriers), len(loads))
@@ -104,7 +104,7 @@ def test_two_half_row_kernel_issues_no_load_behind_a_barrier(isa):
 
 def test_one_wave_row_kernel_issues_every_look_up_in_front_of_its_rows(isa):
     """k_rows_r, 480-point rows (N = 144 000, 288 000, 480 000): twelve look-ups, then the rows, then waits that count down"""
-    ins = one(isa, "void k_rows_r<Sched<480, 10, 8, 6>, 64, false>")
+    ins = one(isa, "void k_rows_r<Sched<480, 10, 8, 6>, 64, false, 0>")
     rows = positions(ins, lambda s: s.startswith("global_load_dwordx4") and s.endswith(" nt"))
     k1_block = positions(ins, lambda s: s.startswith("global_load_dword ") )          # the k1 == 0 block's norm loads (4-byte), in front of everything
     tables = positions(ins, lambda s: s.startswith("global_load_dwordx2"))

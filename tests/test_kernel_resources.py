@@ -84,20 +84,36 @@ def test_real_column_kernels_keep_their_occupancy_budgets(kernels):
     """csrc/rlayout.hip (the production path): k_rows_r eight 128-thread blocks per CU in its one-row form (19.2 KB of
     dynamic LDS each) and four 256-thread blocks in its two-half form (38.4 KB), both at <= 128 VGPRs = four waves per
     SIMD; the column kernels two or three blocks per CU by their tile (76.8 KB for 600 x 16, 51.2 KB for 400 x 16,
-    38.4 KB for 300 x 16); nothing spills."""
+    38.4 KB for 300 x 16); nothing spills.  Every instantiation counts, the broadcast forms (BC = 1..3, NTS = false) of
+    asx_xcorr_strided_f32_dev included: 3 row schedules x BC 0..3, 3 column schedules x NTS."""
     names = {demangled(k): v for k, v in kernels.items()}
     rows = [(n, r) for n, r in names.items() if n.startswith("void k_rows_r<")]
-    assert len(rows) >= 3, sorted(names)[:8]
+    assert len(rows) == 12, sorted(n for n, _ in rows)
     for n, r in rows:
         assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (n, r)
-        two = n.rstrip(">( ").endswith("true") or ", true>" in n
+        two = re.match(r"void k_rows_r<Sched<[^>]*>, \d+, (true|false), \d>", n).group(1) == "true"
         m2 = int(re.search(r"Sched<(\d+)", n).group(1)) * (2 if two else 1)
         blocks = 4 if two else 8
         if m2 <= 1200 or two:
             assert blocks * (m2 * 16 + r["group_segment_fixed_size"]) <= 160 * 1024, (n, r)
+    fwd = [n for n in names if n.startswith("void k_fwd_cols_r<")]
+    assert len(fwd) == 6, sorted(fwd)
     cols = [(n, r) for n, r in names.items() if n.startswith("void k_fwd_cols_r<") or n.startswith("void k_inv_cols_r<")]
-    assert len(cols) >= 6
+    assert len(cols) >= 9
     for n, r in cols:
         assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (n, r)
         m1 = int(re.search(r"Sched<(\d+)", n).group(1))
         assert 2 * (m1 * 16 * 8 + r["group_segment_fixed_size"]) <= 160 * 1024, (n, r)
+
+
+def test_pair_step_kernels_meet_the_resource_budgets(kernels):
+    """the kernels that read the inputs at the caller's pair steps, and the broadcast operand's copy: <= 128 VGPRs, no scratch"""
+    names = {demangled(k): v for k, v in kernels.items()}
+    found = {}
+    for n, r in names.items():
+        m = re.match(r"(?:void )?(k_refine_dots|k_pearson_prep|k_bcast_aux)\b", n)
+        if m:
+            found.setdefault(m.group(1), []).append((n, r))
+    assert {k: len(v) for k, v in found.items()} == {"k_refine_dots": 2, "k_pearson_prep": 2, "k_bcast_aux": 1}, found
+    for n, r in sum(found.values(), []):
+        assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (n, r)
