@@ -17,6 +17,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 // ---------------------------------------------------------------------------
@@ -608,80 +609,104 @@ static int prof_mark(asx_plan *p, hipStream_t s, size_t slot)
     return 0;
 }
 
-// One group: g <= plan->group pairs, inputs device resident.  Pair k is source d_src + k * src_step and sample d_smp + k * smp_step
-// (floats); the exact passes read it from p_src / p_smp at the same steps, TIn selecting the Pearson input type.  bc bit 0 / 1: the
-// source / sample is the call's broadcast track (asx_xcorr_strided_f32_dev, real-column plans), whose forward column pass is already
-// in the plan's slot: only the other operand is transformed here.
+// The pairs of a call, device resident: pair k is source src + k * src_step and sample smp + k * smp_step (elements).  The
+// transforms read the float32 views, the exact passes (refine dots, Pearson, DC removal) the TIn views at the same steps: the
+// caller's values when they are not float32, else the same buffers.  bc bit 0 / 1: the source / sample is the call's broadcast
+// track (asx_xcorr_strided_f32_dev, real-column plans), whose forward column pass is already in the plan's slot.
+template <typename TIn> struct Pairs {
+    const float *src, *smp;
+    const TIn *tsrc, *tsmp;
+    size_t src_step, smp_step;
+    int bc;
+    Pairs at(size_t k) const
+    {
+        return { src + k * src_step, smp + k * smp_step, tsrc + k * src_step, tsmp + k * smp_step, src_step, smp_step, bc };
+    }
+};
+
+// Where pair k's results go (lag and ret may be null).
+struct Results {
+    int64_t *lag;
+    double *coef;
+    int32_t *ret;
+    Results at(size_t k) const { return { lag ? lag + k : nullptr, coef + k, ret ? ret + k : nullptr }; }
+};
+
+struct GroupOpts {
+    static constexpr size_t no_marks = SIZE_MAX;
+    size_t prof_group = 0;       // which group of the call the profiling events time (no_marks: none)
+    int lane = 0;
+    uint32_t pair_base = 0;      // the group's first pair in the caller's overflow window (what the overflow list records)
+    // The caller reads the plan's overflow list behind this group (resolve_overflows).  A caller that does not (the asynchronous
+    // mode) must not leave entries on it either: their indices count from ITS buffers, and the next synchronous call would take
+    // a second look at its own staging buffers with them.  Marked and counted (ASX_SEG_INEXACT -> ret = 1,
+    // asx_plan_peak_overflows) they still are.
+    bool listed = true;
+    // The spectral Pearson form (pearson_spectral.hip) may run: float32 inputs of a float32 ENTRY POINT on a real-column plan.
+    // The double ABI keeps the float64 reduction over the caller's values even when its frames crossed PCIe as float32.
+    bool spectral = true;
+    float *r_out = nullptr;      // r of every lag (asx_xcorr_debug_r_dev)
+    int dot_blocks = 0;          // blocks per pair of the exact re-evaluation; 0: by the group size
+    const AsxPeakWs *pk = nullptr; // the peak workspace instead of the lane's (the second look's lists for every lag)
+};
+
+// One group: g <= plan->group pairs, the first g of x, results to the first g of y.
 template <typename TIn>
-static int run_group(asx_plan *p, const float *d_src, size_t src_step, const float *d_smp, size_t smp_step, const TIn *p_src,
-                     const TIn *p_smp, int bc, size_t g, int64_t *d_lag, double *d_coef, int32_t *d_ret, float *d_r, hipStream_t s,
-                     size_t group_index, int lane = 0, uint32_t pair_base = 0, bool listed = true, bool float32_call = true)
+static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &y, hipStream_t s, const GroupOpts &o = {})
 {
     const AsxDev &P = p->dev;
-    asx_plan::Lane &W = p->lanes[lane];
-    // `listed`: the caller reads the plan's overflow list behind this group (resolve_overflows).  A caller that does not
-    // (the asynchronous mode) must not leave entries on it either: their indices count from ITS buffers, and the next
-    // synchronous call would take a second look at its own staging buffers with them.  Marked and counted
-    // (ASX_SEG_INEXACT -> ret = 1, asx_plan_peak_overflows) they still are.
-    AsxPeakWs fin = W.pk;
-    if (!listed) { fin.over_list = nullptr; fin.over_n = nullptr; fin.over_host = nullptr; fin.over_cap = 0; }
-    // The spectral Pearson form (pearson_spectral.hip): groups of float32 inputs of a float32 ENTRY POINT on a real-column plan.
-    // The double ABI keeps the float64 reduction over the caller's values even when its frames crossed PCIe as float32.
-    const bool spectral = p->spectral && sizeof(TIn) == sizeof(float) && float32_call && W.pk.band;
-    AsxPeakWs tk = W.pk; // what the transform kernels see
+    asx_plan::Lane &W = p->lanes[o.lane];
+    const AsxPeakWs &pk = o.pk ? *o.pk : W.pk;
+    auto mark = [&](size_t k) { return o.prof_group != GroupOpts::no_marks && prof_mark(p, s, o.prof_group * 6 + k); };
+    AsxPeakWs fin = pk;
+    if (!o.listed) { fin.over_list = nullptr; fin.over_n = nullptr; fin.over_host = nullptr; fin.over_cap = 0; }
+    const bool spectral = std::is_same<TIn, float>::value && p->spectral && o.spectral && pk.band;
+    AsxPeakWs tk = pk; // what the transform kernels see
     if (!spectral) { tk.band = nullptr; tk.tile_peak = nullptr; }
-    const size_t e0 = group_index * 6;
-    if (prof_mark(p, s, e0 + 0)) return -1;
+    if (mark(0)) return -1;
     if (P.rlayout) {
-        const int op0 = bc & 1, nops = 2 - (bc & 1) - ((bc >> 1) & 1);
-        if (nops > 0 &&
-            !asx_launch_fwd_cols_r(P, d_src, src_step, d_smp, smp_step, W.zxa, W.zya, W.pk.nrm_part, tk.band, (int)g, op0, nops, false, s))
+        const int op0 = x.bc & 1, nops = 2 - (x.bc & 1) - ((x.bc >> 1) & 1);
+        if (nops > 0 && !asx_launch_fwd_cols_r(P, x.src, x.src_step, x.smp, x.smp_step, W.zxa, W.zya, pk.nrm_part, tk.band, (int)g, op0,
+                                               nops, false, s))
             return fail("internal: no forward column kernel for this plan");
         for (unsigned which = 0; which < 2; which++)
-            if (bc & (1 << which)) asx_launch_bcast_aux(P, p->bslot.nrm, p->bslot.band, W.pk.nrm_part, tk.band, (int)g, which, s);
-    } else if (src_step == 2 * (size_t)P.N && smp_step == P.N) {
-        asx_launch_fwd_cols(P, d_src, d_smp, W.zxa, W.zya, tk, (int)g, s);
+            if (x.bc & (1 << which)) asx_launch_bcast_aux(P, p->bslot.nrm, p->bslot.band, pk.nrm_part, tk.band, (int)g, which, s);
+    } else if (x.src_step == 2 * (size_t)P.N && x.smp_step == P.N) {
+        asx_launch_fwd_cols(P, x.src, x.smp, W.zxa, W.zya, tk, (int)g, s);
     } else {
         // packed plans have no strided forward kernel: the contiguous one once per pair at the pair's own inputs (no broadcast
         // slot: every pair transforms its own copy of a shared track)
         for (size_t k = 0; k < g; k++) {
             AsxPeakWs one = tk;
-            one.nrm_part = W.pk.nrm_part + k * 2 * (size_t)P.ntiles;
-            asx_launch_fwd_cols(P, d_src + k * src_step, d_smp + k * smp_step, W.zxa + k * (size_t)P.M, W.zya + k * (size_t)P.M, one, 1, s);
+            one.nrm_part = pk.nrm_part + k * 2 * (size_t)P.ntiles;
+            asx_launch_fwd_cols(P, x.at(k).src, x.at(k).smp, W.zxa + k * (size_t)P.M, W.zya + k * (size_t)P.M, one, 1, s);
         }
     }
-    if (prof_mark(p, s, e0 + 1)) return -1;
+    if (mark(1)) return -1;
     float2 *q = W.ga;
     if (P.rlayout) {
-        if (!asx_launch_rows_r(P, (bc & 1) ? p->bslot.cx : W.zxa, (bc & 2) ? p->bslot.cy : W.zya, q, tk, (int)g, bc, s))
+        if (!asx_launch_rows_r(P, (x.bc & 1) ? p->bslot.cx : W.zxa, (x.bc & 2) ? p->bslot.cy : W.zya, q, tk, (int)g, x.bc, s))
             return fail("internal: no row kernel for this plan");
     } else {
         asx_launch_rows(P, W.zxa, W.zya, q, tk, (int)g, s);
     }
-    if (prof_mark(p, s, e0 + 2)) return -1;
-    asx_launch_inv_cols(P, q, tk, d_r, (int)g, s);
-    if (prof_mark(p, s, e0 + 3)) return -1;
-    asx_launch_finalize(P, fin, W.seg, (int)g, s, pair_base);
+    if (mark(2)) return -1;
+    asx_launch_inv_cols(P, q, tk, o.r_out, (int)g, s);
+    if (mark(3)) return -1;
+    asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base);
     // Blocks per pair of the exact re-evaluation: a candidate is one whole block's work whatever the grid, so the count only
     // sets how many candidates of a pair are in flight.  Nearly every block of a batch finds no candidate and exits: with 1024
     // pairs, 128 blocks each were 131 072 empty blocks, 25 us of a 2 ms step.
-    const int dot_blocks = (int)std::min<size_t>(ASX_DOT_BLOCKS, std::max<size_t>(8, 16384 / g));
-    if (sizeof(TIn) == sizeof(float)) // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
-        asx_launch_refine_f32(P, (const float *)p_src, src_step, (const float *)p_smp, smp_step, W.pk, W.seg, (int)g, s, dot_blocks,
-                              !spectral);
-    else
-        asx_launch_refine_f64(P, (const double *)p_src, src_step, (const double *)p_smp, smp_step, W.pk, W.seg, (int)g, s, dot_blocks);
-    if (prof_mark(p, s, e0 + 4)) return -1;
-    if (spectral)
-        asx_launch_pearson_spectral_f32(P, (const float *)p_src, src_step, (const float *)p_smp, smp_step, tk, W.spec, W.seg, W.psums,
-                                        d_lag, d_coef, d_ret, (int)g, s);
-    else if (sizeof(TIn) == sizeof(float))
-        asx_launch_pearson_f32((const float *)p_src, (const float *)p_smp, src_step, smp_step, P.N,
-                               W.seg, W.psums, d_lag, d_coef, d_ret, (int)g, s);
-    else
-        asx_launch_pearson_f64((const double *)p_src, (const double *)p_smp, src_step, smp_step, P.N,
-                               W.seg, W.psums, d_lag, d_coef, d_ret, (int)g, s);
-    if (prof_mark(p, s, e0 + 5)) return -1;
+    const int dot_blocks = o.dot_blocks ? o.dot_blocks : (int)std::min<size_t>(ASX_DOT_BLOCKS, std::max<size_t>(8, 16384 / g));
+    // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
+    asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral);
+    if (mark(4)) return -1;
+    if (!spectral)
+        asx_launch_pearson(x.tsrc, x.tsmp, x.src_step, x.smp_step, P.N, W.seg, W.psums, y.lag, y.coef, y.ret, (int)g, s);
+    else if constexpr (std::is_same<TIn, float>::value)
+        asx_launch_pearson_spectral_f32(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, tk, W.spec, W.seg, W.psums, y.lag, y.coef, y.ret,
+                                        (int)g, s);
+    if (mark(5)) return -1;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -692,24 +717,21 @@ static int run_group(asx_plan *p, const float *d_src, size_t src_step, const flo
 // indices on the plan's list; every entry point reads it -- ONE host synchronisation per call (per window of
 // `over_cap` pairs in a long device-resident batch), the price of a lag that is the reference's float64 argmax by
 // construction (src/cross_correlation.c:52-67 has no candidate limit) -- and, only when the list is not empty, runs
-// each listed pair again:
+// each listed pair again through run_group, as a group of one:
 //   (i)  its transforms on (source - mean of source): the float32 error bound scales with both norms, and
 //        r[k] = r'[k] + mean * sum(sample) exactly, a constant that k_inv_cols adds back when it forms the keys
 //        (AsxPeakWs::shift, peak_key_shifted): with the offset gone from the source's norm the window shrinks by the
 //        ratio offset / deviation;
 //   (ii) into lists that hold all 2N lags; every listed lag is re-evaluated exactly (candidates x N double-double
-//        multiply-adds: about 0.2 s for 400 000 candidates at N = 1 440 000) and the Pearson pass is redone for the
-//        lag that wins.
+//        multiply-adds: about 0.2 s for 400 000 candidates at N = 1 440 000, hence 2048 blocks) and the direct Pearson
+//        pass is redone on the caller's values for the lag that wins.
 // It runs on `s` behind everything the call has launched (the lanes have been joined), in the workspace slot 0 of
 // lane 0 and the plan's one set of big lists: nothing else is in flight on this plan (one stream at a time per plan).
-// The pointers are the bases the list's indices count from: pair i of the list is p_src + i * sp, f_smp and p_smp + i * mp
-// (sp / mp: the pair steps of the source and the sample).
+// x and y are the window the list's indices count from: the listed pair i is x.at(i), its results y.at(i).
 template <typename TIn>
-static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_src, const TIn *p_smp, size_t sp, size_t mp,
-                       int64_t *d_lag, double *d_coef, int32_t *d_ret, hipStream_t s)
+static int second_look(asx_plan *p, const Pairs<TIn> &x, const Results &y, size_t i, hipStream_t s)
 {
     const AsxDev &P = p->dev;
-    asx_plan::Lane &W = p->lanes[0];
     const size_t N = p->host.N;
     asx_plan::BigPeak &B = p->big;
     if (!B.cand) {
@@ -724,7 +746,7 @@ static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_s
         HIP_TRY(hipMemsetAsync(T.overflows, 0, sizeof(unsigned long long), s));
         B = T;
     }
-    AsxPeakWs K = W.pk;                   // slot 0's norms, bound and running maximum (k_rows recomputes all three) ...
+    AsxPeakWs K = p->lanes[0].pk;         // slot 0's norms, bound and running maximum (k_rows recomputes all three) ...
     K.cand_n = B.cand_n; K.cand = B.cand; // ... with lists for all 2N lags: this look cannot overflow
     K.refine_n = B.refine_n; K.refine_idx = B.refine_idx; K.refine_val = B.refine_val;
     K.overflows = B.overflows;
@@ -733,26 +755,12 @@ static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_s
     K.cap = (uint32_t)B.cap;
     HIP_TRY(hipMemsetAsync(B.cand_n, 0, sizeof(uint32_t), s));
     // r = r' + stats[2]
-    if (sizeof(TIn) == sizeof(float))
-        asx_launch_dc_remove_f32((const float *)p_src + i * sp, (const float *)p_smp + i * mp, P.N, (double)P.F, B.stats, B.src_dc, s);
-    else
-        asx_launch_dc_remove_f64((const double *)p_src + i * sp, (const double *)p_smp + i * mp, P.N, (double)P.F, B.stats, B.src_dc, s);
+    const Pairs<TIn> xi = x.at(i);
+    asx_launch_dc_remove(xi.tsrc, xi.tsmp, P.N, (double)P.F, B.stats, B.src_dc, s);
     K.shift = B.stats + 2;
-    asx_launch_fwd_cols(P, B.src_dc, f_smp + i * mp, W.zxa, W.zya, K, 1, s);
-    asx_launch_rows(P, W.zxa, W.zya, W.ga, K, 1, s);
-    asx_launch_inv_cols(P, W.ga, K, nullptr, 1, s);
-    asx_launch_finalize(P, K, W.seg, 1, s);
-    if (sizeof(TIn) == sizeof(float))
-        asx_launch_refine_f32(P, (const float *)p_src + i * sp, 2 * N, (const float *)p_smp + i * mp, N, K, W.seg, 1, s, 2048);
-    else
-        asx_launch_refine_f64(P, (const double *)p_src + i * sp, 2 * N, (const double *)p_smp + i * mp, N, K, W.seg, 1, s, 2048);
-    if (sizeof(TIn) == sizeof(float))
-        asx_launch_pearson_f32((const float *)p_src + i * sp, (const float *)p_smp + i * mp, 2 * N, N, P.N,
-                               W.seg, W.psums, d_lag ? d_lag + i : nullptr, d_coef + i, d_ret ? d_ret + i : nullptr, 1, s);
-    else
-        asx_launch_pearson_f64((const double *)p_src + i * sp, (const double *)p_smp + i * mp, 2 * N, N, P.N,
-                               W.seg, W.psums, d_lag ? d_lag + i : nullptr, d_coef + i, d_ret ? d_ret + i : nullptr, 1, s);
-    HIP_TRY(hipGetLastError());
+    if (run_group(p, Pairs<TIn>{ B.src_dc, xi.smp, xi.tsrc, xi.tsmp, 2 * N, N, 0 }, 1, y.at(i), s,
+                  { .prof_group = GroupOpts::no_marks, .listed = false, .spectral = false, .dot_blocks = 2048, .pk = &K }))
+        return -1;
     p->repaired++;
     return 0;
 }
@@ -761,8 +769,7 @@ static int second_look(asx_plan *p, size_t i, const float *f_smp, const TIn *p_s
 // on `s` (its result copies included): ONE synchronisation; the count is read from the page-locked mirror k_finalize adds to
 // only when a pair overflows -- no device-to-host copy sits between the last kernel and the host.
 template <typename TIn>
-static int resolve_overflows(asx_plan *p, const float *f_smp, const TIn *p_src, const TIn *p_smp, size_t sp, size_t mp,
-                             int64_t *d_lag, double *d_coef, int32_t *d_ret, hipStream_t s)
+static int resolve_overflows(asx_plan *p, const Pairs<TIn> &x, const Results &y, hipStream_t s)
 {
     HIP_TRY(hipStreamSynchronize(s));
     if (p->lanes[0].pk.cap >= 2 * p->host.N) return 0; // the ordinary list already holds every lag
@@ -781,23 +788,21 @@ static int resolve_overflows(asx_plan *p, const float *f_smp, const TIn *p_src, 
     HIP_TRY(hipStreamSynchronize(s));
     *p->h_over_n = 0;
     for (uint32_t k = 0; k < n; k++)
-        if (second_look<TIn>(p, p->h_over[k], f_smp, p_src, p_smp, sp, mp, d_lag, d_coef, d_ret, s)) return -1;
+        if (second_look(p, x, y, p->h_over[k], s)) return -1;
     return (int)n;
 }
 
-// Copies the results of g contiguous pairs (one group of a host-side entry point) back to the host.  The copies go out with the one
-// synchronisation that reads the overflow list, and once more behind the second look if any pair took it.
+// Copies the results of the g pairs of one group of a host-side entry point (device d, host h) back to the host.  The copies go
+// out with the one synchronisation that reads the overflow list, and once more behind the second look if any pair took it.
 template <typename TIn>
-static int fetch_results(asx_plan *p, const float *f_smp, const TIn *p_src, const TIn *p_smp, size_t g, int64_t *d_lag, double *d_coef,
-                         int32_t *d_ret, int64_t *lag, double *coef, int32_t *ret, hipStream_t s)
+static int fetch_results(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &d, const Results &h, hipStream_t s)
 {
-    const size_t N = p->host.N;
     for (int pass = 0; pass < 2; pass++) {
-        HIP_TRY(hipMemcpyAsync(lag, d_lag, g * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(coef, d_coef, g * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(ret, d_ret, g * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h.lag, d.lag, g * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h.coef, d.coef, g * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h.ret, d.ret, g * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (pass == 1) { HIP_TRY(hipStreamSynchronize(s)); break; }
-        const int looked = resolve_overflows<TIn>(p, f_smp, p_src, p_smp, 2 * N, N, d_lag, d_coef, d_ret, s);
+        const int looked = resolve_overflows(p, x, d, s);
         if (looked < 0) return -1;
         if (looked == 0) break;
     }
@@ -881,10 +886,8 @@ extern "C" int asx_plan_placement(asx_plan *p, double ms[2], int *kept)
     return 0;
 }
 
-// A device-resident batch, after the entry point's own checks: pair k is source d_source + k * src_step and sample
-// d_sample + k * smp_step (floats), bc as in run_group.
-static int run_batch(asx_plan *p, const float *d_source, size_t src_step, const float *d_sample, size_t smp_step, int bc, size_t batch,
-                     int64_t *d_lag, double *d_coef, int32_t *d_ret, hipStream_t s)
+// A device-resident batch of float32 pairs, after the entry point's own checks.
+static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Results &y, hipStream_t s)
 {
     prof_begin_call(p);
     // chunking: groups of at most `group` pairs; with two lanes a batch is cut into at least two
@@ -906,9 +909,8 @@ static int run_batch(asx_plan *p, const float *d_source, size_t src_step, const 
             const size_t g = std::min(chunk, w0 + wn - done);
             const int lane = overlap ? (int)(gi & 1) : 0;
             hipStream_t ls = overlap ? p->lanes[lane].stream : s;
-            const float *src = d_source + done * src_step, *smp = d_sample + done * smp_step;
-            if (run_group<float>(p, src, src_step, smp, smp_step, src, smp, bc, g, d_lag ? d_lag + done : nullptr, d_coef + done,
-                                 d_ret ? d_ret + done : nullptr, nullptr, ls, gi, lane, (uint32_t)(done - w0), p->exact))
+            if (run_group(p, x.at(done), g, y.at(done), ls,
+                          { .prof_group = gi, .lane = lane, .pair_base = (uint32_t)(done - w0), .listed = p->exact }))
                 return -1;
         }
         if (overlap) {
@@ -918,11 +920,7 @@ static int run_batch(asx_plan *p, const float *d_source, size_t src_step, const 
             }
         }
         // the second look, behind the window's last group (one host synchronisation per window)
-        const float *src = d_source + w0 * src_step, *smp = d_sample + w0 * smp_step;
-        if (p->exact &&
-            resolve_overflows<float>(p, smp, src, smp, src_step, smp_step, d_lag ? d_lag + w0 : nullptr, d_coef + w0,
-                                     d_ret ? d_ret + w0 : nullptr, s) < 0)
-            return -1;
+        if (p->exact && resolve_overflows(p, x.at(w0), y.at(w0), s) < 0) return -1;
     }
     prof_end_call(p, gi);
     return 0;
@@ -941,7 +939,7 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
     if (p->tune_placement && !p->placement_done && batch >= std::min<size_t>(p->group, 8) && // (lane 0's workspaces; a second lane keeps its own)
         tune_placement(p, d_source, d_sample, std::min(batch, p->group), s))
         return -1;
-    return run_batch(p, d_source, 2 * N, d_sample, N, 0, batch, d_lag, d_coef, d_ret, s);
+    return run_batch(p, { d_source, d_sample, d_source, d_sample, 2 * N, N, 0 }, batch, { d_lag, d_coef, d_ret }, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -988,7 +986,7 @@ extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, siz
         if (!asx_launch_fwd_cols_r(P, d_source, 0, d_sample, 0, B.cx, B.cy, B.nrm, B.band, 1, op0, nops, true, s))
             return fail("internal: no forward column kernel for this plan");
     }
-    return run_batch(p, d_source, source_stride, d_sample, sample_stride, bc, batch, d_lag, d_coef, d_ret, s);
+    return run_batch(p, { d_source, d_sample, d_source, d_sample, source_stride, sample_stride, bc }, batch, { d_lag, d_coef, d_ret }, s);
 }
 
 extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const float *d_sample,
@@ -1004,10 +1002,11 @@ extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const f
     // like every other entry point: listed and looked at again in the exact mode, only marked (ret = 1) otherwise
     // (the direct Pearson form: this entry point exists to compare decompositions and to dump r)
     const size_t N = p->host.N;
-    int rc = run_group<float>(p, d_source, 2 * N, d_sample, N, d_source, d_sample, 0, 1, d_lag, d_coef, d_ret, d_r, s, 0, 0, 0, p->exact,
-                              false);
+    const Pairs<float> x{ d_source, d_sample, d_source, d_sample, 2 * N, N, 0 };
+    const Results y{ d_lag, d_coef, d_ret };
+    int rc = run_group(p, x, 1, y, s, { .listed = p->exact, .spectral = false, .r_out = d_r });
     prof_end_call(p, 1);
-    if (rc == 0 && p->exact && resolve_overflows<float>(p, d_sample, d_source, d_sample, 2 * N, N, d_lag, d_coef, d_ret, s) < 0) rc = -1;
+    if (rc == 0 && p->exact && resolve_overflows(p, x, y, s) < 0) rc = -1;
     return rc;
 }
 
@@ -1031,16 +1030,14 @@ extern "C" int asx_xcorr_batch_f32(asx_plan *p, const float *source, const float
     if (ensure_staging(p)) return -1;
     const size_t N = p->host.N;
     hipStream_t s = p->stream;
+    const Pairs<float> x{ p->st_src, p->st_smp, p->st_src, p->st_smp, 2 * N, N, 0 };
+    const Results d{ p->st_lag, p->st_coef, p->st_ret };
     prof_begin_call(p);
     for (size_t done = 0; done < batch; done += p->group) {
         const size_t g = std::min(p->group, batch - done);
         HIP_TRY(hipMemcpyAsync(p->st_src, source + done * 2 * N, g * 2 * N * sizeof(float), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(p->st_smp, sample + done * N, g * N * sizeof(float), hipMemcpyHostToDevice, s));
-        if (run_group<float>(p, p->st_src, 2 * N, p->st_smp, N, p->st_src, p->st_smp, 0, g, p->st_lag, p->st_coef, p->st_ret, nullptr,
-                             s, 0) ||
-            fetch_results<float>(p, p->st_smp, p->st_src, p->st_smp, g, p->st_lag, p->st_coef, p->st_ret, lag + done, coef + done,
-                                 ret + done, s))
-            return -1;
+        if (run_group(p, x, g, d, s) || fetch_results(p, x, g, d, { lag + done, coef + done, ret + done }, s)) return -1;
     }
     return 0;
 }
@@ -1281,6 +1278,17 @@ int upload_narrowed(hipStream_t s, const double *host, size_t n, float *pin, flo
 }
 } // namespace
 
+// One pair of asx_xcorr_f64 in the plan's staging buffers: the transforms read the float32 copy, the exact passes tsrc / tsmp
+// (the float32 copy itself when the frames were narrowed); the direct Pearson form, see GroupOpts::spectral.
+template <typename TIn>
+static int staged_pair(asx_plan *p, const TIn *tsrc, const TIn *tsmp, const Results &h, hipStream_t s)
+{
+    const size_t N = p->host.N;
+    const Pairs<TIn> x{ p->st_src, p->st_smp, tsrc, tsmp, 2 * N, N, 0 };
+    const Results d{ p->st_lag, p->st_coef, p->st_ret };
+    return run_group(p, x, 1, d, s, { .spectral = false }) || fetch_results(p, x, 1, d, h, s) ? -1 : 0;
+}
+
 extern "C" int asx_xcorr_f64(asx_plan *p, const double *source, const double *sample, long *lag,
                              double *coefficient)
 {
@@ -1311,28 +1319,20 @@ extern "C" int asx_xcorr_f64(asx_plan *p, const double *source, const double *sa
             if (narrow < 0) return -1;
         }
     }
-    if (narrow == 1) {
-        p->narrowed++;
-        if (run_group<float>(p, p->st_src, 2 * N, p->st_smp, N, p->st_src, p->st_smp, 0, 1, p->st_lag, p->st_coef, p->st_ret, nullptr, s,
-                             0, 0, 0, true, false))
-            return -1;
-    } else {
-    HIP_TRY(hipMemcpyAsync(p->st_src64, source, 2 * N * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(p->st_smp64, sample, N * sizeof(double), hipMemcpyHostToDevice, s));
-    asx_launch_cvt_f64_f32(p->st_src64, p->st_src, 2 * N, s);
-    asx_launch_cvt_f64_f32(p->st_smp64, p->st_smp, N, s);
-    if (run_group<double>(p, p->st_src, 2 * N, p->st_smp, N, p->st_src64, p->st_smp64, 0, 1, p->st_lag, p->st_coef, p->st_ret, nullptr,
-                          s, 0))
-        return -1;
-    }
     int64_t h_lag = 0;
     double h_coef = 0;
     int32_t h_ret = -1;
-    if (narrow == 1 ? fetch_results<float>(p, p->st_smp, p->st_src, p->st_smp, 1, p->st_lag, p->st_coef, p->st_ret, &h_lag, &h_coef,
-                                           &h_ret, s)
-                    : fetch_results<double>(p, p->st_smp, p->st_src64, p->st_smp64, 1, p->st_lag, p->st_coef, p->st_ret, &h_lag, &h_coef,
-                                            &h_ret, s))
-        return -1;
+    const Results h{ &h_lag, &h_coef, &h_ret };
+    if (narrow == 1) {
+        p->narrowed++;
+        if (staged_pair(p, p->st_src, p->st_smp, h, s)) return -1;
+    } else {
+        HIP_TRY(hipMemcpyAsync(p->st_src64, source, 2 * N * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->st_smp64, sample, N * sizeof(double), hipMemcpyHostToDevice, s));
+        asx_launch_cvt_f64_f32(p->st_src64, p->st_src, 2 * N, s);
+        asx_launch_cvt_f64_f32(p->st_smp64, p->st_smp, N, s);
+        if (staged_pair(p, p->st_src64, p->st_smp64, h, s)) return -1;
+    }
     *lag = (long)h_lag;
     *coefficient = h_coef;
     return h_ret;
@@ -1401,7 +1401,7 @@ extern "C" int asx_pearson_f64(const double *a, const double *b, size_t n, int d
     HIP_TRY(hipMemcpyAsync(S.a, a, n * sizeof(double), hipMemcpyHostToDevice, S.stream));
     HIP_TRY(hipMemcpyAsync(S.b, b, n * sizeof(double), hipMemcpyHostToDevice, S.stream));
     HIP_TRY(hipMemcpyAsync(S.seg, &seg, sizeof(seg), hipMemcpyHostToDevice, S.stream));
-    asx_launch_pearson_f64(S.a, S.b, 0, 0, (uint32_t)n, S.seg, S.ps, nullptr, S.c, nullptr, 1, S.stream);
+    asx_launch_pearson(S.a, S.b, 0, 0, (uint32_t)n, S.seg, S.ps, nullptr, S.c, nullptr, 1, S.stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, S.c, sizeof(double), hipMemcpyDeviceToHost, S.stream));
     HIP_TRY(hipStreamSynchronize(S.stream));
@@ -1549,10 +1549,9 @@ extern "C" int asx_stream_xcorr(asx_stream *st, size_t sample_len, long *lag, do
     int64_t h_lag = 0;
     double h_coef = 0;
     int32_t h_ret = -1;
-    if (run_group<double>(p, st->src32, 2 * sample_len, st->smp32, sample_len, st->src64, st->smp64, 0, 1, st->d_lag, st->d_coef,
-                          st->d_ret, nullptr, s, 0) ||
-        fetch_results<double>(p, st->smp32, st->src64, st->smp64, 1, st->d_lag, st->d_coef, st->d_ret, &h_lag, &h_coef, &h_ret, s))
-        return -1;
+    const Pairs<double> x{ st->src32, st->smp32, st->src64, st->smp64, 2 * sample_len, sample_len, 0 };
+    const Results d{ st->d_lag, st->d_coef, st->d_ret };
+    if (run_group(p, x, 1, d, s) || fetch_results(p, x, 1, d, { &h_lag, &h_coef, &h_ret }, s)) return -1;
     *lag = (long)h_lag;
     *coefficient = h_coef;
     return h_ret;

@@ -171,18 +171,15 @@ void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sban
 bool asx_rlayout_available(const AsxDev &P); // all three kernels compiled in for this plan's schedules
 int asx_rlayout_band_rows(const AsxDev &P);
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base = 0);
-// the pairs' inputs are src_pitch / smp_pitch elements apart (0 = one track for every pair)
-void asx_launch_refine_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch, const AsxPeakWs &W,
-                           AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks = ASX_DOT_BLOCKS, bool pick = true);
-                           // pick = false: the exact values only; the caller's next kernel applies the rule (k_pearson_prep)
-void asx_launch_refine_f64(const AsxDev &P, const double *src, size_t src_pitch, const double *smp, size_t smp_pitch,
-                           const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks = ASX_DOT_BLOCKS);
-void asx_launch_pearson_f32(const float *src, const float *smp, size_t src_pitch, size_t smp_pitch,
-                            uint32_t basis_len, const AsxSeg *seg, double *psums, int64_t *lag,
-                            double *coef, int32_t *ret, int npairs, hipStream_t s);
-void asx_launch_pearson_f64(const double *src, const double *smp, size_t src_pitch, size_t smp_pitch,
-                            uint32_t basis_len, const AsxSeg *seg, double *psums, int64_t *lag,
-                            double *coef, int32_t *ret, int npairs, hipStream_t s);
+// The exact passes over float or double inputs (instances for both next to the kernels, xcorr_kernels.hip).  The pairs' inputs
+// are src_pitch / smp_pitch elements apart (0 = one track for every pair).
+// refine: pick = false: the exact values only; the caller's next kernel applies the rule (k_pearson_prep)
+template <typename TIn>
+void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
+                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick);
+template <typename TIn>
+void asx_launch_pearson(const TIn *src, const TIn *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len, const AsxSeg *seg,
+                        double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 // the partial-sum kernel alone (the spectral form runs it on its own segment list, pearson_spectral.hip)
 void asx_launch_pearson_partial_spec_f32(const float *src, const float *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len,
                                          const AsxSeg *seg, const AsxSpecWs &S, double *psums, int npairs, hipStream_t s);
@@ -199,8 +196,8 @@ unsigned asx_pearson_blocks(uint32_t basis_len); // partial blocks per pair: psu
 // second look, DC removal: stats[0] = mean of source[0..2N), stats[1] = sum of sample[0..N), stats[2] = scale * stats[0] * stats[1]
 // (scale = F: the device's r is F times the plain sum of products); out[i] = (float)(source[i] - stats[0]); stats holds
 // ASX_DC_STATS_DOUBLES doubles
-void asx_launch_dc_remove_f32(const float *src, const float *smp, uint32_t N, double scale, double *stats, float *out, hipStream_t s);
-void asx_launch_dc_remove_f64(const double *src, const double *smp, uint32_t N, double scale, double *stats, float *out, hipStream_t s);
+template <typename TIn>
+void asx_launch_dc_remove(const TIn *src, const TIn *smp, uint32_t N, double scale, double *stats, float *out, hipStream_t s);
 void asx_launch_synth(uint64_t seed, uint64_t first_pair, size_t count, uint32_t N,
                       int noise_shift, float *src, float *smp, int64_t *true_lag, hipStream_t s);
 int asx_pick_threads(const AsxStages &st, int groups, int min_threads, size_t lds_bytes);

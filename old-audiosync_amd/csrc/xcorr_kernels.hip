@@ -1523,18 +1523,12 @@ void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int n
     hipLaunchKernelGGL(k_finalize, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base);
 }
 
-void asx_launch_refine_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch, const AsxPeakWs &W,
-                           AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick)
+template <typename TIn>
+void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
+                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick)
 {
-    hipLaunchKernelGGL(k_refine_dots<float>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
+    hipLaunchKernelGGL(k_refine_dots<TIn>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
     if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg);
-}
-
-void asx_launch_refine_f64(const AsxDev &P, const double *src, size_t src_pitch, const double *smp, size_t smp_pitch,
-                           const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks)
-{
-    hipLaunchKernelGGL(k_refine_dots<double>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
-    hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg);
 }
 
 // Partial blocks per pair: a function of the segment's BASIS LENGTH ONLY -- one block per 16 sweeps of 256 threads x 4
@@ -1552,12 +1546,12 @@ unsigned asx_pearson_blocks(uint32_t basis_len)
     return nb;
 }
 
-void asx_launch_pearson_f32(const float *src, const float *smp, size_t src_pitch, size_t smp_pitch,
-                            uint32_t basis_len, const AsxSeg *seg, double *psums, int64_t *lag,
-                            double *coef, int32_t *ret, int npairs, hipStream_t s)
+template <typename TIn>
+void asx_launch_pearson(const TIn *src, const TIn *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len, const AsxSeg *seg,
+                        double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
 {
     const unsigned nb = asx_pearson_blocks(basis_len);
-    hipLaunchKernelGGL((k_pearson_partial<float, false>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
+    hipLaunchKernelGGL((k_pearson_partial<TIn, false>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
                        src, smp, src_pitch, smp_pitch, basis_len, seg, psums, AsxSpecWs{});
     hipLaunchKernelGGL(k_pearson_final, dim3(npairs), dim3(64), 0, s, seg, psums, nb, lag, coef, ret);
 }
@@ -1568,16 +1562,6 @@ void asx_launch_pearson_partial_spec_f32(const float *src, const float *smp, siz
     const unsigned nb = asx_pearson_blocks(basis_len);
     hipLaunchKernelGGL((k_pearson_partial<float, true>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
                        src, smp, src_pitch, smp_pitch, basis_len, seg, psums, S);
-}
-
-void asx_launch_pearson_f64(const double *src, const double *smp, size_t src_pitch, size_t smp_pitch,
-                            uint32_t basis_len, const AsxSeg *seg, double *psums, int64_t *lag,
-                            double *coef, int32_t *ret, int npairs, hipStream_t s)
-{
-    const unsigned nb = asx_pearson_blocks(basis_len);
-    hipLaunchKernelGGL((k_pearson_partial<double, false>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
-                       src, smp, src_pitch, smp_pitch, basis_len, seg, psums, AsxSpecWs{});
-    hipLaunchKernelGGL(k_pearson_final, dim3(npairs), dim3(64), 0, s, seg, psums, nb, lag, coef, ret);
 }
 
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
@@ -1598,18 +1582,24 @@ void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t 
     hipLaunchKernelGGL(k_cvt_f64_f32, dim3((unsigned)blocks), dim3(ASX_THREADS), 0, s, in, out, n);
 }
 
-void asx_launch_dc_remove_f32(const float *src, const float *smp, uint32_t N, double scale, double *stats, float *out, hipStream_t s)
+template <typename TIn>
+void asx_launch_dc_remove(const TIn *src, const TIn *smp, uint32_t N, double scale, double *stats, float *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_dc_partial<float>, dim3(ASX_DC_BLOCKS), dim3(ASX_THREADS), 0, s, src, smp, N, stats + 4);
+    hipLaunchKernelGGL(k_dc_partial<TIn>, dim3(ASX_DC_BLOCKS), dim3(ASX_THREADS), 0, s, src, smp, N, stats + 4);
     hipLaunchKernelGGL(k_dc_final, dim3(1), dim3(64), 0, s, stats + 4, N, scale, stats);
-    hipLaunchKernelGGL(k_dc_apply<float>, dim3(512), dim3(ASX_THREADS), 0, s, src, N, stats, out);
+    hipLaunchKernelGGL(k_dc_apply<TIn>, dim3(512), dim3(ASX_THREADS), 0, s, src, N, stats, out);
 }
-void asx_launch_dc_remove_f64(const double *src, const double *smp, uint32_t N, double scale, double *stats, float *out, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_dc_partial<double>, dim3(ASX_DC_BLOCKS), dim3(ASX_THREADS), 0, s, src, smp, N, stats + 4);
-    hipLaunchKernelGGL(k_dc_final, dim3(1), dim3(64), 0, s, stats + 4, N, scale, stats);
-    hipLaunchKernelGGL(k_dc_apply<double>, dim3(512), dim3(ASX_THREADS), 0, s, src, N, stats, out);
-}
+
+// the exact passes' instances (asx_internal.h): float32 and float64 inputs
+#define ASX_EXACT_PASSES(T)                                                                                                             \
+    template void asx_launch_refine<T>(const AsxDev &, const T *, size_t, const T *, size_t, const AsxPeakWs &, AsxSeg *, int,           \
+                                       hipStream_t, int, bool);                                                                         \
+    template void asx_launch_pearson<T>(const T *, const T *, size_t, size_t, uint32_t, const AsxSeg *, double *, int64_t *, double *,   \
+                                        int32_t *, int, hipStream_t);                                                                   \
+    template void asx_launch_dc_remove<T>(const T *, const T *, uint32_t, double, double *, float *, hipStream_t);
+ASX_EXACT_PASSES(float)
+ASX_EXACT_PASSES(double)
+#undef ASX_EXACT_PASSES
 
 void asx_launch_synth(uint64_t seed, uint64_t first_pair, size_t count, uint32_t N, int noise_shift,
                       float *src, float *smp, int64_t *true_lag, hipStream_t s)
