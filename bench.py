@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — batched FFT cross-correlation throughput on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (asx_xcorr_batch_f32_dev: rfft, rfft, conj-multiply, irfft,
 |.|-argmax with exact re-evaluation of near-ties, Pearson) over one batch of synthetic 48 kHz mono
 float32 pairs already resident in HBM.
+
+A plain run does what the headline figure needs and nothing else: it sets up the headline workload, warms up,
+times the K steps, writes --dump-outputs and prints the line (metric, value, unit, ms_per_step, config, ...).
+`--full` adds everything else the benchmark measures or checks, as described below: the CPU baseline and the
+oracle's answer for pair 0, the per-kernel HIP-event window and the roofline, the result and coefficient checks
+(`results_ok`, `coef_check`), the config4 and config4_capi legs, the single-pair latency and, with N > 1 ranks,
+`per_rank`.  The --no-cpu / --no-config4 / --no-single / --no-capi switches thin out a --full run.
 
 Workloads
   headline  (the JSON line's `value`)  BASELINE.json's metric: N = 1 440 000 frames per sample, one
@@ -24,8 +31,8 @@ as a CHILD process before anything touches the GPU, and exits with the child's c
 (WORLD_SIZE set) it is a rank.  `--dry-run` walks the same rank / shard / gather code with the gloo
 backend and fabricated results (no GPU): the CPU test of the N>1 path.
 
-Rank 0 prints ONE JSON line carrying `roofline` (algorithmic bytes 52*N per pair, SURVEY.md 8d, over
-the live HIP-event duration of the dominant kernel) and `cpu_baseline` (the reference's cost model on
+Rank 0 prints ONE JSON line; with --full it carries `roofline` (algorithmic bytes 52*N per pair, SURVEY.md 8d,
+over the live HIP-event duration of the dominant kernel) and `cpu_baseline` (the reference's cost model on
 the host cores: FFTW3 if the node has it, else the oracle's own DFT -- labelled).
 """
 import argparse
@@ -685,7 +692,7 @@ def run_rank(args, cpu=None):
             torch.cuda.synchronize()
             # a CPU-side group for waits that must not occupy the GPUs (the ranks idle while rank 0 runs the config4_capi leg:
             # inside an RCCL barrier they would spin in a kernel on the very devices that leg uses)
-            cpu_group = dist.new_group(backend="gloo")
+            cpu_group = dist.new_group(backend="gloo") if args.full else None
         finally:
             sys.stdout.flush()
             os.dup2(saved_stdout, 1)
@@ -707,10 +714,11 @@ def run_rank(args, cpu=None):
         dt_cold = w.timed(args.steps, args.warmup, 0)
         dt = w.timed(args.steps, args.warmup, pre)
         outputs = w.outputs() if args.dump_outputs else None
-        prof_steps = args.profile_steps or max(20, args.steps)
-        med, spread, series = w.kernel_medians(prof_steps, lead=10 if args.profile_steps == 0 else 0)
         dt_local = w.last_dt_local
-        ok, coef_check = w.verify(cpu.get("oracle_pair0") if cpu else None)
+        if args.full:
+            prof_steps = args.profile_steps or max(20, args.steps)
+            med, spread, series = w.kernel_medians(prof_steps, lead=10 if args.profile_steps == 0 else 0)
+            ok, coef_check = w.verify(cpu.get("oracle_pair0") if cpu else None)
         plan_group, plan_split, plan_threads, plan_layout = w.plan.group, w.plan.split, w.plan.threads, w.plan.layout
         overflows, w_count = w.plan.peak_overflows(), w.count
         spectral_modes = list(w.plan.pearson_modes()) if plan_layout == "real-column" and os.environ.get("ASX_PEARSON") != "direct" else None
@@ -718,7 +726,7 @@ def run_rank(args, cpu=None):
         torch.cuda.empty_cache()
 
         cfg4 = None
-        if not args.no_config4:
+        if args.full and not args.no_config4:
             w4 = Workload(asx, sharding, torch, dist, dev, stream, CONFIG4_N, CONFIG4_BATCH, world, rank, multi, 0, None)
             dt4 = w4.timed(args.steps4, 1)
             dt4_local = w4.last_dt_local
@@ -739,7 +747,7 @@ def run_rank(args, cpu=None):
         # more than one GPU fall short of >= 3.5x / >= 7x, the one JSON line says where -- a slow rank (its kernels), the result
         # gather (ms_per_step far above kernel_ms_sum on every rank) or the host thread (one rank's ms_per_step alone).
         per_rank = None
-        if multi:
+        if args.full and multi:
             mine = {"rank": rank, "device": torch.cuda.current_device(), "pairs": w_count,
                     "ms_per_step": dt_local / args.steps * 1e3,
                     "kernel_ms_per_step": {k: round(v, 4) for k, v in med.items()},
@@ -749,7 +757,7 @@ def run_rank(args, cpu=None):
             dist.all_gather_object(per_rank, mine, group=cpu_group)
 
         cfg4c = None
-        if not args.no_config4 and not args.no_capi:
+        if args.full and not args.no_config4 and not args.no_capi:
             if multi:
                 torch.cuda.synchronize()
                 dist.barrier(group=cpu_group)        # every rank has released its config4 buffers and its GPU is idle
@@ -759,7 +767,7 @@ def run_rank(args, cpu=None):
                 dist.barrier(group=cpu_group)        # the others wait on the CPU, not in a kernel on the devices the leg uses
 
         single = None
-        if world == 1 and not args.no_single:
+        if args.full and world == 1 and not args.no_single:
             import numpy as np
             s32 = torch.empty(2 * n, dtype=torch.float32, device=dev); t32 = torch.empty(n, dtype=torch.float32, device=dev)
             asx.synth_pairs_dev(SEED, 0, 1, n, 1, s32.data_ptr(), t32.data_ptr(), 0, stream.cuda_stream)
@@ -768,54 +776,55 @@ def run_rank(args, cpu=None):
 
         if rank == 0:
             value = batch * world * args.steps / dt
-            groups = (batch + plan_group - 1) // plan_group
-            per_launch_pairs = min(batch, plan_group)
-            # the dominant kernel = the longest one; the forward column kernel and the row kernel are within a few percent of
-            # each other (which is ahead changes with the physical placement of a process's buffers), so among kernels within
-            # 10 % of the longest the one with the LOWER roofline fraction is reported: the conservative reading
-            longest = max(med[k] for k in ("fwd_cols", "rows", "inv_cols", "pearson"))
-            shared = [k for k in ("fwd_cols", "rows", "inv_cols", "pearson") if ALGO_SHARE[k] > 0]
-            near = [k for k in shared if med[k] >= 0.9 * longest]
-            # (k_inv_cols has no algorithmic share -- Q is the intermediate; should it ever be the longest kernel with nothing
-            # near it, the longest kernel that has a share is reported)
-            dom = min(near, key=lambda k: ALGO_SHARE[k] / med[k]) if near else max(shared, key=lambda k: med[k])
-            dom_launch_ms = med[dom] / groups
-            dom_bytes = ALGO_SHARE[dom] * n * per_launch_pairs
-            achieved = dom_bytes / (dom_launch_ms * 1e-3) / 1e9
-            path_gbs = BYTES_PER_FRAME * n * value / world / 1e9   # per GPU, from the timed steps
             split = "%dx%dx%d" % plan_split
-            traffic, traffic_src = traffic_from_profiles(n, split, plan_group, dom)
-            ksum = sum(med[k] for k in ("fwd_cols", "rows", "inv_cols", "finalize", "pearson"))
-            suffix = "_r" if plan_layout == "real-column" else ""
-            per_kernel = {}
-            for k in ("fwd_cols", "rows", "inv_cols", "pearson"):
-                kb = ALGO_SHARE[k] * n * per_launch_pairs
-                ka = kb / (med[k] / groups * 1e-3) / 1e9
-                e = {"algorithmic_bytes_per_launch": kb, "avg_launch_ms": med[k] / groups, "achieved": ka, "frac": ka / HBM_PEAK_GBS}
-                if k == "pearson" and spectral_modes is not None:
-                    # the spectral form does not MOVE the 8 N bytes of the reference's reduction (it takes r[peak] and band sums the
-                    # forward pass kept): their quotient by the family's time is work per second, not a bandwidth
-                    e["frac"] = None
-                    e["note"] = ("spectral Pearson form: pairs by form (spectral, + wrap-around correction, direct) = %s; "
-                                 "`achieved` is algorithmic bytes per second, not bytes moved" % (spectral_modes,))
-                per_kernel["k_" + k + (suffix if k != "pearson" else "_partial")] = e
-            roofline = {
-                "bound": "hbm", "kernel": "k_" + dom + (suffix if dom != "pearson" else "_partial"), "achieved": achieved,
-                "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_ms": dom_launch_ms,
-                "launches_per_step": groups, "pairs_per_launch": per_launch_pairs,
-                "path": {"algorithmic_bytes_per_pair": BYTES_PER_FRAME * n, "achieved": path_gbs,
-                         "frac": path_gbs / HBM_PEAK_GBS,
-                         "basis": "52*N bytes per pair x pairs/s per GPU over the timed steps"},
-                "kernels": per_kernel,
-                "kernel_ms_per_step": med, "kernel_ms_min_max": spread, "kernel_ms_sum": ksum,
-                "kernel_ms_series": {k: v[:40] for k, v in series.items()},
-                "kernel_ms_basis": "HIP events on the launch stream, median over %d consecutive steps right behind the timed "
-                                   "region and 10 more untimed steps (the same pre-conditioned window; the only host "
-                                   "synchronisation inside it is the library's own look at its overflow list, once per step)"
-                                   % prof_steps,
-            }
+            if args.full:
+                groups = (batch + plan_group - 1) // plan_group
+                per_launch_pairs = min(batch, plan_group)
+                # the dominant kernel = the longest one; the forward column kernel and the row kernel are within a few percent of
+                # each other (which is ahead changes with the physical placement of a process's buffers), so among kernels within
+                # 10 % of the longest the one with the LOWER roofline fraction is reported: the conservative reading
+                longest = max(med[k] for k in ("fwd_cols", "rows", "inv_cols", "pearson"))
+                shared = [k for k in ("fwd_cols", "rows", "inv_cols", "pearson") if ALGO_SHARE[k] > 0]
+                near = [k for k in shared if med[k] >= 0.9 * longest]
+                # (k_inv_cols has no algorithmic share -- Q is the intermediate; should it ever be the longest kernel with nothing
+                # near it, the longest kernel that has a share is reported)
+                dom = min(near, key=lambda k: ALGO_SHARE[k] / med[k]) if near else max(shared, key=lambda k: med[k])
+                dom_launch_ms = med[dom] / groups
+                dom_bytes = ALGO_SHARE[dom] * n * per_launch_pairs
+                achieved = dom_bytes / (dom_launch_ms * 1e-3) / 1e9
+                path_gbs = BYTES_PER_FRAME * n * value / world / 1e9   # per GPU, from the timed steps
+                traffic, traffic_src = traffic_from_profiles(n, split, plan_group, dom)
+                ksum = sum(med[k] for k in ("fwd_cols", "rows", "inv_cols", "finalize", "pearson"))
+                suffix = "_r" if plan_layout == "real-column" else ""
+                per_kernel = {}
+                for k in ("fwd_cols", "rows", "inv_cols", "pearson"):
+                    kb = ALGO_SHARE[k] * n * per_launch_pairs
+                    ka = kb / (med[k] / groups * 1e-3) / 1e9
+                    e = {"algorithmic_bytes_per_launch": kb, "avg_launch_ms": med[k] / groups, "achieved": ka, "frac": ka / HBM_PEAK_GBS}
+                    if k == "pearson" and spectral_modes is not None:
+                        # the spectral form does not MOVE the 8 N bytes of the reference's reduction (it takes r[peak] and band sums the
+                        # forward pass kept): their quotient by the family's time is work per second, not a bandwidth
+                        e["frac"] = None
+                        e["note"] = ("spectral Pearson form: pairs by form (spectral, + wrap-around correction, direct) = %s; "
+                                     "`achieved` is algorithmic bytes per second, not bytes moved" % (spectral_modes,))
+                    per_kernel["k_" + k + (suffix if k != "pearson" else "_partial")] = e
+                roofline = {
+                    "bound": "hbm", "kernel": "k_" + dom + (suffix if dom != "pearson" else "_partial"), "achieved": achieved,
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                    "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_ms": dom_launch_ms,
+                    "launches_per_step": groups, "pairs_per_launch": per_launch_pairs,
+                    "path": {"algorithmic_bytes_per_pair": BYTES_PER_FRAME * n, "achieved": path_gbs,
+                             "frac": path_gbs / HBM_PEAK_GBS,
+                             "basis": "52*N bytes per pair x pairs/s per GPU over the timed steps"},
+                    "kernels": per_kernel,
+                    "kernel_ms_per_step": med, "kernel_ms_min_max": spread, "kernel_ms_sum": ksum,
+                    "kernel_ms_series": {k: v[:40] for k, v in series.items()},
+                    "kernel_ms_basis": "HIP events on the launch stream, median over %d consecutive steps right behind the timed "
+                                       "region and 10 more untimed steps (the same pre-conditioned window; the only host "
+                                       "synchronisation inside it is the library's own look at its overflow list, once per step)"
+                                       % prof_steps,
+                }
             line = {
                 "metric": "cross-correlations/sec (N=%d float32 pairs)" % n,
                 "value": value, "unit": "cross-correlations/s", "n_gpus": world, "steps": args.steps,
@@ -840,9 +849,10 @@ def run_rank(args, cpu=None):
                                     "the timed region)",
                            "parallelism": "pairs sharded over %d GPU(s), one process per GPU, RCCL all_gather of results" % world},
                 "world_size_seen": dist.get_world_size() if multi else 1,
-                "results_ok": ok, "coef_check": coef_check, "pearson_modes": spectral_modes, "peak_overflows": overflows,
-                "roofline": roofline,
+                "pearson_modes": spectral_modes, "peak_overflows": overflows,
             }
+            if args.full:
+                line.update({"results_ok": ok, "coef_check": coef_check, "roofline": roofline})
             if per_rank is not None:
                 line["per_rank"] = per_rank
             base = load_baseline_line(args.baseline_json)
@@ -879,14 +889,17 @@ def main():
     ap.add_argument("--sample-len", type=int, default=1440000)
     ap.add_argument("--batch", type=int, default=0, help="pairs per GPU per step (0 = auto)")
     ap.add_argument("--noise-shift", type=int, default=1)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-config4", action="store_true", help="skip the fixed-batch 8192 x 480000 leg")
-    ap.add_argument("--no-single", action="store_true", help="skip the single-pair latency leg")
-    ap.add_argument("--no-capi", action="store_true", help="skip the C-ABI multi-device form of the config4 leg")
-    ap.add_argument("--steps4", type=int, default=3, help="timed steps of the config4 leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other leg and check: CPU baseline, per-kernel window and roofline, "
+                         "results_ok / coef_check, config4, config4_capi, single-pair latency, per_rank (off: the headline only)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-config4", action="store_true", help="--full without the fixed-batch 8192 x 480000 leg")
+    ap.add_argument("--no-single", action="store_true", help="--full without the single-pair latency leg")
+    ap.add_argument("--no-capi", action="store_true", help="--full without the C-ABI multi-device form of the config4 leg")
+    ap.add_argument("--steps4", type=int, default=3, help="timed steps of the config4 leg (--full)")
     ap.add_argument("--profile-steps", type=int, default=0,
-                    help="steps of the per-kernel HIP-event window (0 = max(20, steps) behind 10 lead steps); counter-collection "
-                         "runs (tools/traffic.sh, tools/pmc.sh), where every launch is serialised, pass a small number")
+                    help="steps of the per-kernel HIP-event window of --full (0 = max(20, steps) behind 10 lead steps); "
+                         "counter-collection runs (tools/traffic.sh, tools/pmc.sh), where every launch is serialised, pass a small number")
     ap.add_argument("--split", default=None)
     ap.add_argument("--dry-run", action="store_true", help="rank/shard/gather path on CPU with gloo, no GPU")
     ap.add_argument("--baseline-json", default=None,
@@ -911,7 +924,7 @@ def main():
     if args.dry_run:
         return dry_run(args)
     cpu = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu:
         # rank 0 at N = 1 only, and FIRST: forked worker processes and a clean machine, before any GPU call
         cpu = cpu_baseline(args.sample_len)
         # the same leg also leaves the checker's answer for pair 0 of the bench workload (the oracle on the inputs k_synth

@@ -9,7 +9,7 @@ for r in $(seq $rounds); do
   for v in "${vars[@]}"; do
     lib=${v%%:*}; envs=""; [[ "$v" == *:* ]] && envs=${v#*:}
     if [ "$lib" == "main" ]; then cp /tmp/asx_keep.so $R/old-audiosync_amd/libaudiosync_hip.so; else cp $R/ab/$lib.so $R/old-audiosync_amd/libaudiosync_hip.so; fi
-    echo -n "$v: "; env ${envs//,/ } python3 $R/bench.py --no-cpu --no-config4 --no-single "$@" 2>/dev/null | python3 $R/tools/brief.py
+    echo -n "$v: "; env ${envs//,/ } python3 $R/bench.py --full --no-cpu --no-config4 --no-single "$@" 2>/dev/null | python3 $R/tools/brief.py
   done
 done
 cp /tmp/asx_keep.so $R/old-audiosync_amd/libaudiosync_hip.so

@@ -21,11 +21,11 @@ echo "== traffic + kernel trace, N=480000 x 1024"; $R/tools/traffic.sh r${RD}c/t
 echo "== traffic + kernel trace, N=720000 x 512"; $R/tools/traffic.sh r${RD}c/traffic_N720000 --sample-len 720000 --batch 512 > $O/traffic_N720000.txt 2>&1
 # the bench lines below quote the PMC traffic of THIS collection (bench.py reads profiles/r<round>_traffic*.json)
 cp $O/traffic_N1440000/traffic.json $R/profiles/r${RD}_traffic.json; cp $O/traffic_N288000/traffic.json $R/profiles/r${RD}_traffic_N288000.json; cp $O/traffic_N480000/traffic.json $R/profiles/r${RD}_traffic_N480000.json; cp $O/traffic_N720000/traffic.json $R/profiles/r${RD}_traffic_N720000.json
-echo "== bench (headline, cpu baseline, config4, single pair)"; python3 $R/bench.py > $O/bench.json 2> $O/bench.err; stamp $O/bench.json
+echo "== bench (headline, cpu baseline, config4, single pair)"; python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err; stamp $O/bench.json
 for n in 144000 288000 480000 720000 960000; do
-  echo "== bench N=$n x 1024"; python3 $R/bench.py --sample-len $n --batch 1024 --steps 20 --no-cpu --no-config4 --no-single > $O/bench_N$n.json 2>> $O/bench.err; stamp $O/bench_N$n.json
+  echo "== bench N=$n x 1024"; python3 $R/bench.py --sample-len $n --batch 1024 --steps 20 --full --no-cpu --no-config4 --no-single > $O/bench_N$n.json 2>> $O/bench.err; stamp $O/bench_N$n.json
 done
-echo "== packed layout, same box (A/B reference)"; ASX_LAYOUT=packed python3 $R/bench.py --no-cpu --no-config4 --no-single > $O/bench_packed.json 2>> $O/bench.err; stamp $O/bench_packed.json
+echo "== packed layout, same box (A/B reference)"; ASX_LAYOUT=packed python3 $R/bench.py --full --no-cpu --no-config4 --no-single > $O/bench_packed.json 2>> $O/bench.err; stamp $O/bench_packed.json
 echo "== streaming / single"; python3 $R/bench.py --mode streaming --steps 5 > $O/bench_streaming.json 2>> $O/bench.err; stamp $O/bench_streaming.json
 python3 $R/bench.py --mode single --steps 20 > $O/bench_single.json 2>> $O/bench.err; stamp $O/bench_single.json
 echo "== SQ counters"; $R/tools/pmc.sh r${RD}c/pmc --precondition 0 --profile-steps 2 > $O/pmc_summary.txt 2>&1

@@ -5,8 +5,8 @@ cp $R/old-audiosync_amd/libaudiosync_hip.so /tmp/asx_keep.so
 for r in $(seq $rounds); do
   for l in "$@"; do
     cp $R/ab/$l.so $R/old-audiosync_amd/libaudiosync_hip.so
-    echo -n "$l 1.44M: "; python3 $R/bench.py --no-cpu --no-config4 --no-single --steps 30 | python3 $R/tools/brief.py
-    echo -n "$l 720k : "; python3 $R/bench.py --no-cpu --no-config4 --no-single --steps 8 --sample-len 720000 --batch 1024 | python3 $R/tools/brief.py
+    echo -n "$l 1.44M: "; python3 $R/bench.py --full --no-cpu --no-config4 --no-single --steps 30 | python3 $R/tools/brief.py
+    echo -n "$l 720k : "; python3 $R/bench.py --full --no-cpu --no-config4 --no-single --steps 8 --sample-len 720000 --batch 1024 | python3 $R/tools/brief.py
   done
 done
 cp /tmp/asx_keep.so $R/old-audiosync_amd/libaudiosync_hip.so

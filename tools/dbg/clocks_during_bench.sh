@@ -7,5 +7,5 @@ try:
 except Exception as e: print('err',e)
 "; sleep 0.25; done ) > $R/gpurun_out/clk.log 2>&1 &
 sleep 1
-python3 $R/bench.py --no-cpu --no-config4 --no-single --steps 2500 | python3 $R/tools/brief.py
+python3 $R/bench.py --full --no-cpu --no-config4 --no-single --steps 2500 | python3 $R/tools/brief.py
 wait

@@ -5,7 +5,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r5a; mkdir -p $O
 cd $R
 python3 -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.txt; tail -3 $O/pytest.txt
-B="python3 $R/bench.py --no-cpu --no-config4 --no-single"
+B="python3 $R/bench.py --full --no-cpu --no-config4 --no-single"
 run() { echo -n "$1: "; shift; env "$@" $B 2>/dev/null | python3 $R/tools/brief.py; }
 {
 echo "== schedules / inverse order (2 rounds, alternating)"

@@ -5,6 +5,6 @@ R=$1; N=$2; shift 2
 for r in $(seq $R); do
   for c in "$@"; do
     lay=${c%%:*}; sp=${c##*:}
-    echo -n "$c : "; ASX_LAYOUT=$lay python3 bench.py --no-cpu --no-config4 --no-single --steps 40 --sample-len $N --split $sp | python3 tools/brief.py
+    echo -n "$c : "; ASX_LAYOUT=$lay python3 bench.py --full --no-cpu --no-config4 --no-single --steps 40 --sample-len $N --split $sp | python3 tools/brief.py
   done
 done

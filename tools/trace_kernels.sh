@@ -3,7 +3,7 @@
 # rocprofv3 --kernel-trace of one bench.py run: median / minimum duration of EVERY kernel of the library (the small tail kernels --
 # finalize, refine, Pearson prep / partial / final -- that bench.py's HIP events lump into two families)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; shift; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 10 --warmup 5 --precondition 30 --no-cpu --no-config4 --no-single "$@" > $O/trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 10 --warmup 5 --precondition 30 --full --no-cpu --no-config4 --no-single "$@" > $O/trace.log 2>&1
 python3 - $O <<'PY'
 import csv, glob, sys, collections
 calls = collections.defaultdict(list)

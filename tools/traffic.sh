@@ -9,9 +9,9 @@
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/$1; shift
 mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 TR_STEPS=10; TR_WARMUP=5; TR_PRE=30
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 $R/bench.py --steps 2 --warmup 1 --precondition 0 --profile-steps 2 --no-cpu --no-config4 --no-single "$@" > $OUT/fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 $R/bench.py --steps 2 --warmup 1 --precondition 0 --profile-steps 2 --no-cpu --no-config4 --no-single "$@" > $OUT/write.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps $TR_STEPS --warmup $TR_WARMUP --precondition $TR_PRE --no-cpu --no-config4 --no-single "$@" > $OUT/trace.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 $R/bench.py --steps 2 --warmup 1 --precondition 0 --profile-steps 2 --full --no-cpu --no-config4 --no-single "$@" > $OUT/fetch.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 $R/bench.py --steps 2 --warmup 1 --precondition 0 --profile-steps 2 --full --no-cpu --no-config4 --no-single "$@" > $OUT/write.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps $TR_STEPS --warmup $TR_WARMUP --precondition $TR_PRE --full --no-cpu --no-config4 --no-single "$@" > $OUT/trace.log 2>&1
 export TR_STEPS TR_WARMUP TR_PRE
 python3 - $OUT <<'PY'
 import csv, collections, glob, json, sys
