@@ -112,6 +112,13 @@ extern int audiosync_set_feed(const double *source, size_t source_len,
  * the run.  Returns 0, or -1 for a NULL path or while a run is in progress. */
 extern int audiosync_set_feed_files(const char *source_path, const char *sample_path);
 
+/* Bound on |lag| for the peak search of audiosync_run(): the stream it correlates searches only the lags
+ * -round(ms * SAMPLE_RATE / 1000) .. +round(ms * SAMPLE_RATE / 1000) (asx_stream_set_lag_window).  0 = unbounded, the
+ * default; a negative value counts as its magnitude.  Guarded by `mutex` like audiosync_set_debug(); takes effect at the next
+ * audiosync_run(). */
+extern void audiosync_set_max_lag_ms(long ms);
+extern long audiosync_get_max_lag_ms(void);
+
 /* Debug aid replacing the reference's compile-time PLOT/gnuplot dumps
  * (src/cross_correlation.c:168-184,280-296): writes the two segments that
  * pearson_coefficient() compares for `lag` (src/cross_correlation.c:256-271) as

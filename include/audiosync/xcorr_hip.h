@@ -102,6 +102,26 @@ int asx_plan_peak_repairs(asx_plan *plan, uint64_t *count);
 int asx_plan_set_exact(asx_plan *plan, int on);
 size_t asx_plan_peak_capacity(const asx_plan *plan);
 
+/* Lag window of the peak search ("maxlag" of MATLAB's xcorr, max_tau of GCC-PHAT tools): only the lags lag_min..lag_max,
+ * -N <= lag_min <= lag_max <= N-1, compete for the peak; the default [-N, N-1] is every lag.  Lag l >= 0 is index l of the
+ * reference's results[], lag l < 0 index 2N + l (the inverse of the wrap at src/cross_correlation.c:256-263), so the window
+ * is one or two ranges of [0, 2N).  The windowed peak is max_abs_index() (src/cross_correlation.c:52-67) run over the
+ * in-window elements in ascending index order: the first of them (the smallest in-window index, the "seed") starts the
+ * running maximum with its SIGNED value, as arr[0] does at :56, every later one competes with fabs and the strict '>' of :60.
+ * So the smallest index wins ties; a digitally silent pair returns the seed's lag; a negative r at the seed loses to any
+ * larger |r| in the window, as a negative r[0] does without one.  Everything after the peak is unchanged: the lag wrap and
+ * segments (:256-271), the Pearson coefficient in both forms, ret = -1 for a NaN, ret = 1 in the asynchronous mode, the
+ * near-tie lists and the second look (which runs with the window of the call that listed the pair).  When the windowed peak
+ * is the unwindowed one, every output is bit for bit the unwindowed call's.  The full window runs exactly the kernels of a
+ * plan that never had one; any other window runs the inverse column pass in its windowed form (csrc/rlayout.hip
+ * k_inv_cols_rw, csrc/xcorr_kernels.hip k_inv_cols_w).  The window does not prune work: the call costs what it costs.
+ * Every entry point on the plan honours it (asx_xcorr_debug_r_dev still returns the whole of r; asx_xcorr_batch_multi /
+ * _multi_dev: set it on each plan).  Setting it neither allocates nor synchronises: it is safe between captured calls.
+ * asx_plan_set_lag_window returns -1 and leaves the window unchanged when lag_min < -N, lag_max > N-1 or
+ * lag_min > lag_max. */
+int asx_plan_set_lag_window(asx_plan *plan, int64_t lag_min, int64_t lag_max);
+int asx_plan_lag_window(const asx_plan *plan, int64_t *lag_min, int64_t *lag_max);
+
 /* The Pearson coefficient of src/cross_correlation.c:74-116 (pearson_coefficient(), :272) in the batched float32 entry
  * points.  Two forms, the same formula:
  *   direct    the reference's reduction over both segments (one streaming pass with the accuracy of its two);
@@ -278,6 +298,9 @@ int asx_stream_reset(asx_stream *stream);
  * already resident.  Same return convention as asx_xcorr_f64.  -1 (outputs untouched) if
  * fewer frames than that have been appended. */
 int asx_stream_xcorr(asx_stream *stream, size_t sample_len, long *lag, double *coefficient);
+/* The lag window (asx_plan_set_lag_window) of every later asx_stream_xcorr, in frames: clamped to [-n, n-1] for each
+ * prefix length n it correlates.  Default: unbounded.  -1 when lag_min > lag_max. */
+int asx_stream_set_lag_window(asx_stream *stream, int64_t lag_min, int64_t lag_max);
 
 /* ---- synthetic inputs and timing -------------------------------------- */
 

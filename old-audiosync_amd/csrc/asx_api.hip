@@ -137,6 +137,7 @@ struct asx_plan {
     std::vector<uint32_t> h_over;
     unsigned long long repaired = 0;   // pairs that took the second look
     bool exact = true;                 // asx_plan_set_exact: every entry point takes the second look (default)
+    int64_t win_lo = 0, win_hi = 0;    // asx_plan_set_lag_window: the lags whose peak is searched, [-N, N-1] (set at creation) = all
     bool spectral = false;             // float32 groups take the spectral Pearson form (asx_plan_set_pearson; real-column plans)
     unsigned long long *mode_count = nullptr; // [ASX_PM_NMODES], cumulative over the plan's life
     // "measure" plans only: at the first device-resident batch the forward column kernel is timed against the caller's buffers
@@ -296,6 +297,8 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
     p->spectral = d.rlayout != 0;
     if (const char *e = getenv("ASX_PEARSON")) p->spectral = p->spectral && strcmp(e, "direct") != 0; // A/B of the two forms
     if (const char *e = getenv("ASX_EXACT")) p->exact = atoi(e) != 0; // initial value of asx_plan_set_exact (A/B of its cost)
+    p->win_lo = -(int64_t)p->host.N; // the full lag window
+    p->win_hi = (int64_t)p->host.N - 1;
     HIP_TRY(hipEventCreateWithFlags(&p->fork, hipEventDisableTiming));
     d.stamps = nullptr;
     d.stamp_kernel = 0;
@@ -548,6 +551,29 @@ extern "C" int asx_plan_debug_peak(asx_plan *p, size_t pair, float *bound2, uint
 
 extern "C" size_t asx_plan_peak_capacity(const asx_plan *p) { return p ? p->lanes[0].pk.cap : 0; }
 
+// The window is plain host state under the plan's lock, read by run_group when it launches: no allocation, no synchronisation.
+extern "C" int asx_plan_set_lag_window(asx_plan *p, int64_t lag_min, int64_t lag_max)
+{
+    if (!p) return fail("asx_plan_set_lag_window: null plan");
+    const int64_t N = (int64_t)p->host.N;
+    if (lag_min < -N || lag_max > N - 1 || lag_min > lag_max)
+        return fail("asx_plan_set_lag_window: [%lld, %lld] is not a window inside [%lld, %lld] with lag_min <= lag_max",
+                    (long long)lag_min, (long long)lag_max, (long long)-N, (long long)(N - 1));
+    std::lock_guard<std::mutex> guard(p->lock);
+    p->win_lo = lag_min;
+    p->win_hi = lag_max;
+    return 0;
+}
+
+extern "C" int asx_plan_lag_window(const asx_plan *p, int64_t *lag_min, int64_t *lag_max)
+{
+    if (!p || !lag_min || !lag_max) return fail("asx_plan_lag_window: null argument");
+    std::lock_guard<std::mutex> guard(const_cast<asx_plan *>(p)->lock);
+    *lag_min = p->win_lo;
+    *lag_max = p->win_hi;
+    return 0;
+}
+
 extern "C" int asx_plan_threads(const asx_plan *p, int *cols, int *rows)
 {
     if (!p) return -1;
@@ -691,21 +717,26 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
         asx_launch_rows(P, W.zxa, W.zya, q, tk, (int)g, s);
     }
     if (mark(2)) return -1;
-    asx_launch_inv_cols(P, q, tk, o.r_out, (int)g, s);
+    // The lag window (asx_plan_set_lag_window), by value: the full one launches the same kernels as a plan that never had one.
+    // The second look at a pair runs through here too, with the window of the call that listed it.
+    const bool windowed = p->win_lo != -(int64_t)P.N || p->win_hi != (int64_t)P.N - 1;
+    const AsxWin win = asx_win_of(p->win_lo, p->win_hi, P.N);
+    const uint32_t seed = windowed ? win.seed : 0u;
+    asx_launch_inv_cols(P, q, tk, o.r_out, (int)g, s, windowed ? &win : nullptr);
     if (mark(3)) return -1;
-    asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base);
+    asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, seed);
     // Blocks per pair of the exact re-evaluation: a candidate is one whole block's work whatever the grid, so the count only
     // sets how many candidates of a pair are in flight.  Nearly every block of a batch finds no candidate and exits: with 1024
     // pairs, 128 blocks each were 131 072 empty blocks, 25 us of a 2 ms step.
     const int dot_blocks = o.dot_blocks ? o.dot_blocks : (int)std::min<size_t>(ASX_DOT_BLOCKS, std::max<size_t>(8, 16384 / g));
     // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
-    asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral);
+    asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral, seed);
     if (mark(4)) return -1;
     if (!spectral)
         asx_launch_pearson(x.tsrc, x.tsmp, x.src_step, x.smp_step, P.N, W.seg, W.psums, y.lag, y.coef, y.ret, (int)g, s);
     else if constexpr (std::is_same<TIn, float>::value)
         asx_launch_pearson_spectral_f32(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, tk, W.spec, W.seg, W.psums, y.lag, y.coef, y.ret,
-                                        (int)g, s);
+                                        (int)g, s, seed);
     if (mark(5)) return -1;
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1436,6 +1467,7 @@ struct asx_stream {
     double *d_coef = nullptr;
     int32_t *d_ret = nullptr;
     std::vector<asx_plan *> plans;  // one per prefix length seen
+    int64_t win_lo = INT64_MIN, win_hi = INT64_MAX; // asx_stream_set_lag_window, in frames: clamped to [-n, n-1] per prefix length n
     hipStream_t s = nullptr;        // uploads and conversions of new frames
     std::mutex lock;
 };
@@ -1526,6 +1558,16 @@ extern "C" int asx_stream_append_f64(asx_stream *st, const double *source_frames
     return 0;
 }
 
+extern "C" int asx_stream_set_lag_window(asx_stream *st, int64_t lag_min, int64_t lag_max)
+{
+    if (!st) return fail("asx_stream_set_lag_window: null stream");
+    if (lag_min > lag_max) return fail("asx_stream_set_lag_window: lag_min %lld > lag_max %lld", (long long)lag_min, (long long)lag_max);
+    std::lock_guard<std::mutex> guard(st->lock);
+    st->win_lo = lag_min;
+    st->win_hi = lag_max;
+    return 0;
+}
+
 extern "C" int asx_stream_xcorr(asx_stream *st, size_t sample_len, long *lag, double *coefficient)
 {
     if (!st || !lag || !coefficient || sample_len == 0) return fail("asx_stream_xcorr: bad argument");
@@ -1545,6 +1587,10 @@ extern "C" int asx_stream_xcorr(asx_stream *st, size_t sample_len, long *lag, do
     DevGuard dg(st->device);
     if (!dg.ok) return fail("cannot select device %d", st->device);
     hipStream_t s = p->stream;
+    // the stream's window on this prefix length (both ends clamped to [-n, n-1]: lo <= hi stays true)
+    const int64_t n = (int64_t)sample_len;
+    p->win_lo = std::min(std::max(st->win_lo, -n), n - 1);
+    p->win_hi = std::min(std::max(st->win_hi, -n), n - 1);
     prof_begin_call(p);
     int64_t h_lag = 0;
     double h_coef = 0;

@@ -97,6 +97,31 @@ struct AsxSeg {           // per pair, produced by k_finalize
 };
 #define ASX_SEG_INEXACT 1u
 
+// Lag window of the peak search (asx_plan_set_lag_window).  Lags lo..hi are the indices a, a+1, ..., a+w of r modulo n = 2N
+// (lag l >= 0 is index l, lag l < 0 index 2N + l: the inverse of the wrap at src/cross_correlation.c:256-263) -- one range, or two
+// when the window holds lag 0 and a negative lag.  seed = the smallest in-window index: the element that starts the reference's
+// running maximum with its SIGNED value (arr[0], :56), 0 for every window that holds lag 0.  The full window (a = N, w = 2N - 1,
+// seed = 0) runs the kernels without a window; the others run k_inv_cols_rw / k_inv_cols_w, which mask every key they form with
+// asx_win_has.  Travels by value as a kernel argument.
+struct AsxWin {
+    uint32_t a, w, seed, n;
+};
+__host__ __device__ inline bool asx_win_has(const AsxWin &z, uint32_t idx)
+{
+    if (idx >= z.n) return false; // (packed plans: the embedding's lags past 2N)
+    const uint32_t d = idx >= z.a ? idx - z.a : idx + (z.n - z.a);
+    return d <= z.w;
+}
+inline AsxWin asx_win_of(int64_t lo, int64_t hi, uint32_t N)
+{
+    AsxWin z;
+    z.n = 2u * N;
+    z.a = (uint32_t)(lo >= 0 ? lo : (int64_t)z.n + lo);
+    z.w = (uint32_t)(hi - lo);
+    z.seed = (lo < 0 && hi >= 0) ? 0u : z.a;
+    return z;
+}
+
 // kernel launchers (defined in xcorr_kernels.hip, called from asx_api.hip)
 struct AsxCand {          // one near-maximum lag found by a column tile
     uint32_t idx;
@@ -158,25 +183,29 @@ void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, fl
 void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga,
                      const AsxPeakWs &W, int npairs, hipStream_t s);
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out,
-                         int npairs, hipStream_t s);
+                         int npairs, hipStream_t s, const AsxWin *win = nullptr);
 // rlayout.hip: the real-column decomposition (production lengths); false = no kernel compiled in for this plan.
 // bc (the broadcast forms of asx_xcorr_strided_f32_dev): bit 0 = cx is the plan's broadcast slot (one C for every pair), bit 1 = cy is
 bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
                        hipStream_t s);
 bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
                            float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s);
-bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s);
+// win: null = every lag competes (k_inv_cols_r); else the lag-window form (k_inv_cols_rw)
+bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
+                           const AsxWin *win = nullptr);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 bool asx_rlayout_available(const AsxDev &P); // all three kernels compiled in for this plan's schedules
 int asx_rlayout_band_rows(const AsxDev &P);
-void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base = 0);
+// seed (the lag window's, AsxWin): the index an empty running maximum stands for, and the one whose exact value competes signed
+void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base = 0,
+                         uint32_t seed = 0);
 // The exact passes over float or double inputs (instances for both next to the kernels, xcorr_kernels.hip).  The pairs' inputs
 // are src_pitch / smp_pitch elements apart (0 = one track for every pair).
 // refine: pick = false: the exact values only; the caller's next kernel applies the rule (k_pearson_prep)
 template <typename TIn>
 void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
-                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick);
+                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed = 0);
 template <typename TIn>
 void asx_launch_pearson(const TIn *src, const TIn *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len, const AsxSeg *seg,
                         double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
@@ -187,7 +216,7 @@ void asx_launch_pearson_partial_spec_f32(const float *src, const float *smp, siz
 // group's transform kernels)
 void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
                                      const AsxPeakWs &W, const AsxSpecWs &S, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
-                                     int32_t *ret, int npairs, hipStream_t s);
+                                     int32_t *ret, int npairs, hipStream_t s, uint32_t seed = 0);
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
                               double min_confidence, double sample_rate, int64_t *lag_ms, int32_t *accept,
                               hipStream_t s);

@@ -142,7 +142,7 @@ template <int NTP> __device__ __forceinline__ void block_sum4(double (&v)[4], do
 // src_pitch / smp_pitch: the pairs' input steps in floats (0 = one track for every pair).
 template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
                                                                     const float *__restrict__ smp, size_t src_pitch, size_t smp_pitch,
-                                                                    AsxPeakWs W, AsxSpecWs S, AsxSeg *__restrict__ seg)
+                                                                    AsxPeakWs W, AsxSpecWs S, AsxSeg *__restrict__ seg, uint32_t seed)
 {
     __shared__ double red[4][NTP / 64];
     __shared__ double s_exact;
@@ -158,7 +158,8 @@ template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep
     const asx_peak_t best = W.pairmax[pair];
     // ---- k_refine_pick's part (xcorr_kernels.hip; this kernel stands in for it in the spectral form: one launch less): the
     // reference's max_abs_index rule (src/cross_correlation.c:52-67) on the exact values of the re-evaluated near-ties --
-    // key(0) = r[0] signed, key(i) = |r[i]|, largest key, smallest lag among equal keys, a NaN never wins unless at lag 0 --
+    // key(seed) = r[seed] signed (seed = 0, or a lag window's first index), key(i) = |r[i]|, largest key, smallest lag among equal
+    // keys, a NaN never wins unless at the seed --
     // and, kept here, the winner's exact SIGNED value: the cross term of the coefficient
     const uint32_t nref = W.refine_n[pair];
     if (nref >= 2u) { // block-uniform
@@ -168,7 +169,7 @@ template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep
             const uint32_t idx = W.refine_idx[pair * (size_t)W.cap + i];
             const double v = W.refine_val[pair * (size_t)W.cap + i];
             double key;
-            if (idx == 0u) key = (v != v) ? (double)INFINITY : v + 0.0;
+            if (idx == seed) key = (v != v) ? (double)INFINITY : v + 0.0;
             else { key = fabs(v); if (key != key) key = -(double)INFINITY; }
             if (key > bk || (key == bk && idx < bi)) { bk = key; bi = idx; bv = v; }
         }
@@ -268,17 +269,17 @@ __global__ __launch_bounds__(64) void k_pearson_final_spec(const AsxSeg *__restr
 
 void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
                                      const AsxPeakWs &W, const AsxSpecWs &S0, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
-                                     int32_t *ret, int npairs, hipStream_t s)
+                                     int32_t *ret, int npairs, hipStream_t s, uint32_t seed)
 {
     AsxSpecWs S = S0;
     S.N = P.N;
     if ((size_t)P.band_rows * (size_t)P.M2 >= 16384) {
         S.nb = ASX_PREP_BLOCKS;
         hipLaunchKernelGGL((k_pearson_prep<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0, s,
-                           P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg);
+                           P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg, seed);
     } else {
         S.nb = 1;
-        hipLaunchKernelGGL((k_pearson_prep<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg);
+        hipLaunchKernelGGL((k_pearson_prep<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg, seed);
     }
     asx_launch_pearson_partial_spec_f32(src, smp, src_pitch, smp_pitch, P.N, seg, S, psums, npairs, s);
     hipLaunchKernelGGL(k_pearson_final_spec, dim3(npairs), dim3(64), 0, s, seg, psums, asx_pearson_blocks(P.N), S, lag, coef, ret);

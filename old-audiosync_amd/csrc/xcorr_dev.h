@@ -106,21 +106,22 @@ constexpr int asx_ilog2(int v) { return v <= 1 ? 0 : 1 + asx_ilog2(v >> 1); }
 // ---------------------------------------------------------------------------
 // key(0) = arr[0] SIGNED (:56), key(i) = fabs(arr[i]) (:59).  A NaN key never wins the strict
 // '>' of :60 (so it needs no mapping in a running maximum); a NaN at index 0 is never beaten.
-__device__ __forceinline__ float peak_key_of(float value, uint32_t idx)
+// seed: the index that competes signed -- 0, or the first in-window index of a lag window (AsxWin)
+__device__ __forceinline__ float peak_key_of(float value, uint32_t idx, uint32_t seed = 0u)
 {
     const float a = fabsf(value);
     const float z = (value != value) ? INFINITY : (value + 0.0f); // -0.0 -> +0.0 so it ties with |0|
-    return idx == 0u ? z : a;
+    return idx == seed ? z : a;
 }
 // The same when the transforms ran on (source - mean) (second look at a pair with a large offset in both tracks,
 // second_look, asx_api.hip): r[k] = value + c with c = mean * sum(sample), the same for every k.  Keys are taken RELATIVE to
 // |c| -- key' = |r| - |c|, lag 0: r - |c| -- so that float32 keeps the differences between lags when |c| >> |value|;
 // a common shift changes neither the order of the keys nor the width of the near-maximum window.
-__device__ __forceinline__ float peak_key_shifted(float value, uint32_t idx, double c)
+__device__ __forceinline__ float peak_key_shifted(float value, uint32_t idx, double c, uint32_t seed = 0u)
 {
-    if (value != value) return idx == 0u ? INFINITY : value;
+    if (value != value) return idx == seed ? INFINITY : value;
     const double r = (double)value + c;
-    return (float)((idx == 0u ? r : fabs(r)) - fabs(c)) + 0.0f;
+    return (float)((idx == seed ? r : fabs(r)) - fabs(c)) + 0.0f;
 }
 __device__ __forceinline__ asx_peak_t peak_pack_key(float key, uint32_t idx)
 {

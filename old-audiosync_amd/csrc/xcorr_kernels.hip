@@ -542,330 +542,27 @@ template <int MAXR, class S1 = void, int TC = 0, int NT = 0>
 __global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols(const AsxDev *__restrict__ Pp, const float2 *__restrict__ ga,
                                                                    AsxPeakWs W, float *__restrict__ r_out)
 {
-    const AsxDev &PD = *Pp; // the plan lives in device memory: uniform scalar loads, taken once
-    const AsxKP P = asx_kp(PD);
-    __shared__ asx_peak_t red[ASX_FFT_THREADS_MAX / 64];
-    const size_t pair = blockIdx.y;
-    constexpr bool STATIC = !std::is_void<S1>::value;
-    int T = P.T, logT = P.logT, M1 = P.M1;
-    int nthreads = blockDim.x;
-    if constexpr (STATIC) { T = TC; logT = asx_ilog2(TC); M1 = S1::n; nthreads = NT; }
-    const int tile = col_tile_of_block(blockIdx.x, logT);
-    if (tile >= P.ntiles) return; // grid.x is rounded up (col_grid_x)
-    // A digitally silent track (a zero norm, e.g. the zero-filled tail of a short capture): r is exactly zero
-    // everywhere, the reference's scan returns index 0 (src/cross_correlation.c:52-67), which is what a running
-    // maximum left at zero means to k_finalize.  Without this every one of the 2N lags would be a near-tie of the
-    // maximum 0 inside a window of width 0, the lists would overflow and the synchronous entry points would
-    // re-evaluate all of them exactly (seconds at N = 1 440 000).  Block-uniform; r_out (tests) still wants zeros.
-    if (W.bound2[pair] == 0.f && r_out == nullptr) return;
-    const double shift = W.shift ? W.shift[pair] : 0.0; // block-uniform; non-zero only in the second look (second_look, asx_api.hip)
-    const int logH = logT - 1, H = T >> 1, M2 = P.M2;
-    const int c0 = tile * T;
-    const float2 *in = ga + pair * (size_t)P.M;
-    const bool even = (M2 & 1) == 0;
-    float4 *lds4 = reinterpret_cast<float4 *>(asx_lds);
+    constexpr bool WIN = false;
+    const AsxWin Z{};
+#include "inv_cols_body.h"
+}
 
-    const int nelem4 = M1 << logH;
-    const LdsLayout Lc = col_layout(T, logT, nthreads);
-    const size_t stamp_block = pair * P.ntiles + tile;
-    (void)stamp_block;
-    ASX_STAMP_AT(2, stamp_block, 0);
-    // The pair's running maximum so far (other tiles publish theirs with atomicMax below) and the width
-    // of the near-maximum window are consumed after the first pass of the scan, at the very end.  Loaded where
-    // they are used, the block waits 2 700 cycles for an L2 round trip there (phase stamps).  Thread 0 fetches
-    // them now and parks them in LDS: its wave waits for them together with its tile loads, and everybody reads
-    // them behind the barriers of the transform.
-    __shared__ asx_peak_t s_run0;
-    __shared__ float s_b2;
-    if (threadIdx.x == 0) {
-        s_run0 = W.pairmax[pair];
-        s_b2 = W.bound2[pair];
-    }
-    TwPre pre;
-    if constexpr (STATIC) pre = tw_prefetch_first<S1, true, true, true>(Lc, P.tw1);
-    else pre = tw_prefetch<true>(PD.st1, PD.st1.nstages - 1, Lc, P.tw1);
-#ifndef ASX_INV_FED
-#define ASX_INV_FED 1 // first inverse stage fed straight from HBM (compile-time schedules, full tiles)
-#endif
-    TwPre pre_last;
-    bool filled = false;
-    if constexpr (STATIC && ASX_INV_FED) {
-        if (even && (c0 + T <= M2)) { // block-uniform: full tile
-            // No fill phase: the first stage to run (innermost, 10 consecutive rows per butterfly) takes its
-            // inputs from HBM -- the thread's loads are all in flight together, as in the fill loop -- and writes
-            // its outputs to LDS: one LDS write + read pass and one barrier less per tile.
-            ASX_STAMP_AT(2, stamp_block, 1);
-            pre_last = lds_fft_static_head_fed<S1, true, true>(lds4, Lc, P.tw1, pre,
-                [&](auto RC, auto &v, int g, int pos0, int q) __attribute__((always_inline)) {
-                    const float2 *col = in + (size_t)pos0 * M2 + c0 + 2 * g;
-                    static_for<0, decltype(RC)::value>([&](auto TT) __attribute__((always_inline)) {
-                        constexpr int t = decltype(TT)::value;
-                        const float4 x = asx_ld16(col + (size_t)(t * q) * M2, ASX_NT & 16);
-                        v[t] = Cx2{ v2f{ x.x, x.z }, v2f{ x.y, x.w } };
-                    });
-                });
-            filled = true;
-        }
-    }
-    if (!filled) {
-    for (int e0 = threadIdx.x; e0 < nelem4; e0 += ASX_COL_LOADS * nthreads) {
-        float4 v[ASX_COL_LOADS];
-        static_for<0, ASX_COL_LOADS>([&](auto I) __attribute__((always_inline)) {
-            const int e = e0 + decltype(I)::value * nthreads;
-            const int cg = e & (H - 1), p1 = e >> logH;
-            const int j2 = c0 + 2 * cg;
-            v[I] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (even && (c0 + T <= M2)) { // block-uniform: full tile
-                if (e < nelem4) v[I] = *reinterpret_cast<const float4 *>(in + (size_t)p1 * M2 + j2);
-            } else if (e < nelem4 && j2 < M2) {
-                const float2 *g = in + (size_t)p1 * M2 + j2;
-                if (even) {
-                    v[I] = *reinterpret_cast<const float4 *>(g);
-                } else {
-                    const float2 a = g[0];
-                    const float2 b = (j2 + 1 < M2) ? g[1] : make_float2(0.f, 0.f);
-                    v[I] = make_float4(a.x, a.y, b.x, b.y);
-                }
-            }
-        });
-        static_for<0, ASX_COL_LOADS>([&](auto I) __attribute__((always_inline)) {
-            const int e = e0 + decltype(I)::value * nthreads;
-            if (e < nelem4) lds4[e] = v[I];
-        });
-    }
-    __syncthreads();
-    ASX_STAMP_AT(2, stamp_block, 1);
-    // every inverse stage but the last: the last one's outputs are consumed from registers below
-    // (r reaches neither HBM nor LDS; LDS keeps that stage's input, so the stage can be run again)
-    if constexpr (STATIC) pre_last = lds_fft_static_head<S1, true, true>(lds4, Lc, P.tw1, pre);
-    else lds_fft<MAXR, true, true>(lds4, PD.st1, Lc, P.tw1, pre); // run-time schedule: the whole transform, r into LDS
-    }
-    ASX_STAMP_AT(2, stamp_block, 2);
-
-    // ANY earlier value of the running maximum is a lower bound of the final one, so a stale read merely admits
-    // more candidates (k_finalize filters them against the final maximum).
-    const asx_peak_t run0 = s_run0;
-    const float b2 = s_b2;
-    if constexpr (!STATIC) {
-        // Run-time schedules (lengths outside the reference's six): r lies in LDS and is scanned there.  The
-        // scan from the last stage's registers below, instantiated inside the switch over eleven radix bodies,
-        // pushed these kernels into scratch (k_inv_cols 0.77 ms against 0.43 ms for the compiled-in schedule).
-        const bool fastg = even && (c0 + T <= M2) && (P.nout == P.F) && (tile != 0) && (r_out == nullptr) && shift == 0.0;
-        auto examine_slot = [&](int e, float4 g, float thr) {
-            const int cg = e & (H - 1), j1 = e >> logH;
-            const int j2 = c0 + 2 * cg;
-            if (j2 >= M2) return;
-            const uint32_t i0 = 2u * ((uint32_t)j1 * (uint32_t)M2 + (uint32_t)j2);
-            const float val[4] = { g.x, g.y, g.z, g.w }; // slot = {re0, im0, re1, im1}: four consecutive lags
-#pragma unroll
-            for (int h = 0; h < 4; h++) {
-                const uint32_t idx = i0 + h;
-                if (idx < P.nout && j2 + (h >> 1) < M2) {
-                    const float key = shift == 0.0 ? peak_key_of(val[h], idx) : peak_key_shifted(val[h], idx, shift);
-                    if (key >= thr) cand_append(W, pair, idx, key);
-                }
-            }
-        };
-        if (fastg) {
-            // pass 1: per thread the largest and second largest slot maximum; a thread meets its slots in
-            // increasing lag order, so a strict '>' keeps the earliest of equal maxima
-            float best_m = -INFINITY, second_m = -INFINITY;
-            int best_e = threadIdx.x;
-            for (int e = threadIdx.x; e < nelem4; e += nthreads) {
-                const float4 g = lds4[e];
-                const float m = fmaxf(fmaxf(fabsf(g.x), fabsf(g.y)), fmaxf(fabsf(g.z), fabsf(g.w))); // NaNs drop out
-                if (m > best_m) { second_m = best_m; best_m = m; best_e = e; }
-                else if (m > second_m) second_m = m;
-            }
-            const float4 gb = lds4[best_e];
-            uint32_t my_idx;
-            {
-                const int cg = best_e & (H - 1), j1 = best_e >> logH;
-                const uint32_t i0 = 2u * ((uint32_t)j1 * (uint32_t)M2 + (uint32_t)(c0 + 2 * cg));
-                const uint32_t h = fabsf(gb.x) == best_m ? 0u : fabsf(gb.y) == best_m ? 1u : fabsf(gb.z) == best_m ? 2u : 3u;
-                my_idx = i0 + h;
-            }
-            const float wmax = wave_max_nonneg(fmaxf(best_m, 0.f));
-            unsigned long long holders = __ballot(best_m == wmax);
-            uint32_t widx = 0xFFFFFFFFu;
-            while (holders) {
-                const int l = __ffsll((long long)holders) - 1;
-                const uint32_t li = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, l);
-                widx = li < widx ? li : widx;
-                holders &= holders - 1;
-            }
-            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = widx == 0xFFFFFFFFu ? 0 : peak_pack_key(wmax, widx);
-            __syncthreads();
-            asx_peak_t tb = red[0];
-            for (int w = 1; w < (int)((nthreads + 63) >> 6); w++) tb = peak_max(tb, red[w]);
-            if (threadIdx.x == 0) atomicMax(&W.pairmax[pair], tb);
-            const float thr = near_max_threshold(peak_key(peak_max(tb, run0)), b2);
-            if (best_m >= thr) {
-                if (second_m >= thr) {
-                    for (int e = threadIdx.x; e < nelem4; e += nthreads) {
-                        const float4 g = lds4[e];
-                        const float m = fmaxf(fmaxf(fabsf(g.x), fabsf(g.y)), fmaxf(fabsf(g.z), fabsf(g.w)));
-                        if (m >= thr) examine_slot(e, g, thr);
-                    }
-                } else {
-                    examine_slot(best_e, gb, thr);
-                }
-            }
-        } else {
-            float best_key = -INFINITY;
-            uint32_t best_idx = 0xFFFFFFFFu;
-            for (int e = threadIdx.x; e < nelem4; e += nthreads) {
-                const int cg = e & (H - 1), j1 = e >> logH;
-                const int j2 = c0 + 2 * cg;
-                if (j2 < M2) {
-                    const uint32_t i0 = 2u * ((uint32_t)j1 * (uint32_t)M2 + (uint32_t)j2);
-                    const float4 g = lds4[e];
-                    const float val[4] = { g.x, g.y, g.z, g.w };
-#pragma unroll
-                    for (int h = 0; h < 4; h++) {
-                        const uint32_t idx = i0 + h;
-                        if (idx < P.nout && j2 + (h >> 1) < M2) {
-                            const float key = shift == 0.0 ? peak_key_of(val[h], idx) : peak_key_shifted(val[h], idx, shift);
-                            if (key > best_key || (key == best_key && idx < best_idx) || best_idx == 0xFFFFFFFFu) { best_key = key; best_idx = idx; }
-                            if (r_out) r_out[pair * (size_t)P.nout + idx] = val[h];
-                        }
-                    }
-                }
-            }
-            asx_peak_t best = best_idx == 0xFFFFFFFFu ? 0 : peak_pack_key(best_key, best_idx);
-            best = block_peak_max(best, red);
-            if (threadIdx.x == 0) { atomicMax(&W.pairmax[pair], best); red[0] = best; }
-            __syncthreads();
-            const float thr = near_max_threshold(peak_key(peak_max(red[0], run0)), b2);
-            for (int e = threadIdx.x; e < nelem4; e += nthreads) examine_slot(e, lds4[e], thr);
-        }
-        ASX_STAMP_AT(2, stamp_block, 3);
-    } else {
-    auto last_stage = [&](auto &&sink) __attribute__((always_inline)) {
-        lds_last_stage_static<S1, true, true>(lds4, Lc, P.tw1, pre_last, sink);
-    };
-
-    // Output T of a butterfly is row j1 = pos0 + T*q of column pair g: four consecutive lags
-    // {re0, im0, re1, im1} from i0 = 2*(j1*M2 + c0 + 2g).
-    // Peak search (src/cross_correlation.c:52-67): largest key, smallest lag among equal keys.
-    // Fast path (block-uniform): the tile is full, every lag counts, lag 0 (the signed one) is
-    // not in it and r is not being dumped -> one packed maximum per slot, indices resolved at the end.
-    const bool fast = even && (c0 + T <= M2) && (P.nout == P.F) && (tile != 0) && (r_out == nullptr) && shift == 0.0;
-    // second look (rare, one instantiation for both paths): the thread runs its last stage again and
-    // appends every valid lag whose key is inside the window
-    auto examine_again = [&](float thr) __attribute__((always_inline)) {
-        last_stage([&](auto RC, auto &v, int g, int pos0, int q) __attribute__((always_inline)) {
-            const int j2 = c0 + 2 * g;
-            if (j2 >= M2) return;
-            static_for<0, decltype(RC)::value>([&](auto TT) __attribute__((always_inline)) {
-                constexpr int t = decltype(TT)::value;
-                const float val[4] = { v[t].re.x, v[t].im.x, v[t].re.y, v[t].im.y };
-                const uint32_t i0 = 2u * ((uint32_t)(pos0 + t * q) * (uint32_t)M2 + (uint32_t)j2);
-#pragma unroll
-                for (int h = 0; h < 4; h++) {
-                    const uint32_t idx = i0 + h;
-                    if (idx < P.nout && j2 + (h >> 1) < M2) {
-                        const float key = shift == 0.0 ? peak_key_of(val[h], idx) : peak_key_shifted(val[h], idx, shift);
-                        if (key >= thr) cand_append(W, pair, idx, key);
-                    }
-                }
-            });
-        });
-    };
-    float thr_again = 0.f;
-    bool again = false;
-    if (fast) {
-        // pass 1: per thread the largest and second largest slot maximum
-        float best_m = -INFINITY, second_m = -INFINITY;
-        uint32_t best_i0 = 0xFFFFFFFFu;
-        float4 gb = make_float4(0.f, 0.f, 0.f, 0.f);
-        last_stage([&](auto RC, auto &v, int g, int pos0, int q) __attribute__((always_inline)) {
-            static_for<0, decltype(RC)::value>([&](auto TT) __attribute__((always_inline)) {
-                constexpr int t = decltype(TT)::value;
-                const float4 s4 = make_float4(v[t].re.x, v[t].im.x, v[t].re.y, v[t].im.y);
-                const float m = fmaxf(fmaxf(fabsf(s4.x), fabsf(s4.y)), fmaxf(fabsf(s4.z), fabsf(s4.w))); // NaNs drop out
-                const uint32_t i0 = 2u * ((uint32_t)(pos0 + t * q) * (uint32_t)M2 + (uint32_t)(c0 + 2 * g));
-                if (m > best_m || (m == best_m && i0 < best_i0)) { second_m = best_m; best_m = m; gb = s4; best_i0 = i0; }
-                else if (m > second_m) second_m = m;
-            });
-        });
-        // lag order inside a slot = its memory order {re0, im0, re1, im1}
-        const uint32_t hh = fabsf(gb.x) == best_m ? 0u : fabsf(gb.y) == best_m ? 1u : fabsf(gb.z) == best_m ? 2u : 3u;
-        const uint32_t my_idx = best_i0 + hh;
-        // wave maximum in registers, smallest lag among the lanes that hold it, one entry per wave
-        ASX_STAMP_AT(2, stamp_block, 4);
-        const float wmax = wave_max_nonneg(fmaxf(best_m, 0.f));
-        unsigned long long holders = __ballot(best_m == wmax);
-        uint32_t widx = 0xFFFFFFFFu;
-        while (holders) {
-            const int l = __ffsll((long long)holders) - 1;
-            const uint32_t li = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, l);
-            widx = li < widx ? li : widx;
-            holders &= holders - 1;
-        }
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = widx == 0xFFFFFFFFu ? 0 : peak_pack_key(wmax, widx);
-        __syncthreads();
-        // every thread folds the wave entries itself: no second barrier to broadcast the result
-        asx_peak_t tb = red[0];
-        for (int w = 1; w < (int)((nthreads + 63) >> 6); w++) tb = peak_max(tb, red[w]);
-        if (threadIdx.x == 0) atomicMax(&W.pairmax[pair], tb);
-        // Second look: lags within the float32 error window of the largest key known so far.  Almost every
-        // thread is below the threshold; the one that holds the maximum usually has no second slot near
-        // it and examines just that slot; a thread with more runs its last stage again.
-        ASX_STAMP_AT(2, stamp_block, 5);
-        const float thr = near_max_threshold(peak_key(peak_max(tb, run0)), b2);
-        thr_again = thr;
-        if (best_m >= thr) {
-            if (second_m >= thr) {
-                again = true;
-            } else {
-                const float val[4] = { gb.x, gb.y, gb.z, gb.w };
-#pragma unroll
-                for (int h = 0; h < 4; h++)
-                    if (fabsf(val[h]) >= thr) cand_append(W, pair, best_i0 + h, fabsf(val[h]));
-            }
-        }
-    } else {
-        // general form: first tile (lag 0 competes signed), ragged or embedded tiles, r dumped for tests
-        float best_key = -INFINITY;
-        uint32_t best_idx = 0xFFFFFFFFu;
-        last_stage([&](auto RC, auto &v, int g, int pos0, int q) __attribute__((always_inline)) {
-            const int j2 = c0 + 2 * g;
-            if (j2 >= M2) return;
-            static_for<0, decltype(RC)::value>([&](auto TT) __attribute__((always_inline)) {
-                constexpr int t = decltype(TT)::value;
-                const float val[4] = { v[t].re.x, v[t].im.x, v[t].re.y, v[t].im.y };
-                const uint32_t i0 = 2u * ((uint32_t)(pos0 + t * q) * (uint32_t)M2 + (uint32_t)j2);
-#pragma unroll
-                for (int h = 0; h < 4; h++) {
-                    const uint32_t idx = i0 + h;
-                    if (idx < P.nout && j2 + (h >> 1) < M2) {
-                        const float key = shift == 0.0 ? peak_key_of(val[h], idx) : peak_key_shifted(val[h], idx, shift);
-                        if (key > best_key || (key == best_key && idx < best_idx) || best_idx == 0xFFFFFFFFu) { best_key = key; best_idx = idx; }
-                        if (r_out) r_out[pair * (size_t)P.nout + idx] = val[h];
-                    }
-                }
-            });
-        });
-        asx_peak_t best = best_idx == 0xFFFFFFFFu ? 0 : peak_pack_key(best_key, best_idx);
-        best = block_peak_max(best, red);
-        if (threadIdx.x == 0) { atomicMax(&W.pairmax[pair], best); red[0] = best; }
-        __syncthreads();
-        const float thr = near_max_threshold(peak_key(peak_max(red[0], run0)), b2);
-        again = best_key >= thr;
-        thr_again = thr;
-    }
-    if (again) examine_again(thr_again);
-    ASX_STAMP_AT(2, stamp_block, 3);
-    } // compiled-in schedules
+// the lag-window form (asx_plan_set_lag_window): a kernel of its own, so that the full window runs k_inv_cols untouched
+template <int MAXR, class S1 = void, int TC = 0, int NT = 0>
+__global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols_w(const AsxDev *__restrict__ Pp, const float2 *__restrict__ ga,
+                                                                     AsxPeakWs W, float *__restrict__ r_out, AsxWin Z)
+{
+    constexpr bool WIN = true;
+#include "inv_cols_body.h"
 }
 
 #if ASX_HAS_PART(64)
 // ---------------------------------------------------------------------------
 // k_finalize: grid (npairs).  Reduce tile partials, wrap the lag, pick segments.
 // ---------------------------------------------------------------------------
+// seed: the lag window's first index (AsxWin; 0 without a window) -- what a running maximum that nothing reached stands for
 __global__ __launch_bounds__(ASX_THREADS) void k_finalize(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
-                                                           uint32_t pair_base)
+                                                           uint32_t pair_base, uint32_t seed)
 {
     const uint32_t N = Pp->N;
     __shared__ uint32_t nsel;
@@ -885,7 +582,7 @@ __global__ __launch_bounds__(ASX_THREADS) void k_finalize(const AsxDev *__restri
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        AsxSeg sg = make_seg(best ? peak_index(best) : 0u, N);
+        AsxSeg sg = make_seg(best ? peak_index(best) : seed, N);
         // One candidate: the float32 argmax is unambiguous.  More than the list holds (a signal periodic in
         // more than `cap` lags, an offset of hundreds of deviations in both tracks): the float32 argmax is only a
         // placeholder.  The pair is MARKED (its ret becomes ASX_RET_INEXACT in k_pearson_final), counted
@@ -982,9 +679,10 @@ __global__ __launch_bounds__(ASX_THREADS) void k_refine_dots(const AsxDev *__res
 }
 
 // grid (npairs): the reference's max_abs_index rule (src/cross_correlation.c:52-67) on the exact values:
-// key(0) = r[0] signed, key(i) = |r[i]|, largest key, smallest lag among equal keys; a NaN key never
-// wins unless it sits at lag 0.
-__global__ __launch_bounds__(ASX_THREADS) void k_refine_pick(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg)
+// key(seed) = r[seed] signed, key(i) = |r[i]|, largest key, smallest lag among equal keys; a NaN key never
+// wins unless it sits at the seed (index 0, or the first index of a lag window: AsxWin).
+__global__ __launch_bounds__(ASX_THREADS) void k_refine_pick(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
+                                                              uint32_t seed)
 {
     __shared__ double rkey[ASX_THREADS / 64];
     __shared__ uint32_t ridx[ASX_THREADS / 64];
@@ -997,7 +695,7 @@ __global__ __launch_bounds__(ASX_THREADS) void k_refine_pick(const AsxDev *__res
         const uint32_t idx = W.refine_idx[pair * (size_t)W.cap + i];
         const double v = W.refine_val[pair * (size_t)W.cap + i];
         double key;
-        if (idx == 0u) key = (v != v) ? (double)INFINITY : v + 0.0;
+        if (idx == seed) key = (v != v) ? (double)INFINITY : v + 0.0;
         else { key = fabs(v); if (key != key) key = -(double)INFINITY; }
         if (key > bk || (key == bk && idx < bi)) { bk = key; bi = idx; }
     }
@@ -1366,9 +1064,9 @@ bool asx_launch_rows_static(const AsxDev &P, const float2 *zxa, const float2 *zy
 void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga, const AsxPeakWs &W,
                              int npairs, hipStream_t s);
 bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                hipStream_t s);
+                                hipStream_t s, const AsxWin *win);
 void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                 hipStream_t s);
+                                 hipStream_t s, const AsxWin *win);
 
 #define ASX_FWD_LAUNCH(...) \
     do { allow_big_lds((const void *)k_fwd_cols<__VA_ARGS__>, lds_bytes_cols(P)); \
@@ -1431,11 +1129,14 @@ void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *z
 #undef ASX_ROWS_LAUNCH
 
 #define ASX_INV_LAUNCH(...) \
-    do { allow_big_lds((const void *)k_inv_cols<__VA_ARGS__>, lds_bytes_cols(P)); \
+    do { if (win) { allow_big_lds((const void *)k_inv_cols_w<__VA_ARGS__>, lds_bytes_cols(P)); \
+                    hipLaunchKernelGGL((k_inv_cols_w<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, *win); \
+                    break; } \
+         allow_big_lds((const void *)k_inv_cols<__VA_ARGS__>, lds_bytes_cols(P)); \
          hipLaunchKernelGGL((k_inv_cols<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out); } while (0)
 #if ASX_HAS_PART(16)
 bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                hipStream_t s)
+                                hipStream_t s, const AsxWin *win)
 {
     dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
 #define ASX_TRY_STATIC(m1, t, nt, maxr, ...) \
@@ -1447,7 +1148,7 @@ bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeak
 #endif
 #if ASX_HAS_PART(32)
 void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                 hipStream_t s)
+                                 hipStream_t s, const AsxWin *win)
 {
     dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
     const int mr = max_radix(P.st1);
@@ -1511,24 +1212,25 @@ void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, floa
 }
 
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                         hipStream_t s)
+                         hipStream_t s, const AsxWin *win)
 {
-    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s)) return;
-    if (generic_only() || !asx_launch_inv_cols_static(P, ga, W, r_out, npairs, s))
-        asx_launch_inv_cols_generic(P, ga, W, r_out, npairs, s);
+    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s, win)) return;
+    if (generic_only() || !asx_launch_inv_cols_static(P, ga, W, r_out, npairs, s, win))
+        asx_launch_inv_cols_generic(P, ga, W, r_out, npairs, s, win);
 }
 
-void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base)
+void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,
+                         uint32_t seed)
 {
-    hipLaunchKernelGGL(k_finalize, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base);
+    hipLaunchKernelGGL(k_finalize, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, seed);
 }
 
 template <typename TIn>
 void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
-                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick)
+                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed)
 {
     hipLaunchKernelGGL(k_refine_dots<TIn>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
-    if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg);
+    if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, seed);
 }
 
 // Partial blocks per pair: a function of the segment's BASIS LENGTH ONLY -- one block per 16 sweeps of 256 threads x 4
@@ -1593,7 +1295,7 @@ void asx_launch_dc_remove(const TIn *src, const TIn *smp, uint32_t N, double sca
 // the exact passes' instances (asx_internal.h): float32 and float64 inputs
 #define ASX_EXACT_PASSES(T)                                                                                                             \
     template void asx_launch_refine<T>(const AsxDev &, const T *, size_t, const T *, size_t, const AsxPeakWs &, AsxSeg *, int,           \
-                                       hipStream_t, int, bool);                                                                         \
+                                       hipStream_t, int, bool, uint32_t);                                                               \
     template void asx_launch_pearson<T>(const T *, const T *, size_t, size_t, uint32_t, const AsxSeg *, double *, int64_t *, double *,   \
                                         int32_t *, int, hipStream_t);                                                                   \
     template void asx_launch_dc_remove<T>(const T *, const T *, uint32_t, double, double *, float *, hipStream_t);

@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "asx_memcpy_d2h", "asx_stream_sync", "asx_plan_peak_overflows", "asx_plan_peak_repairs", "asx_plan_set_exact", "asx_plan_peak_capacity",
     "asx_current_device", "asx_plan_timings_ms", "asx_xcorr_batch_multi", "asx_plan_layout", "asx_plan_narrowed_calls",
     "asx_plan_set_pearson", "asx_plan_pearson_modes", "asx_plan_placement", "asx_host_malloc", "asx_host_free", "asx_shard_range", "asx_result_bytes", "asx_comm_create", "asx_comm_destroy", "asx_xcorr_batch_multi_dev",
-    "asx_xcorr_strided_f32_dev",
+    "asx_xcorr_strided_f32_dev", "asx_plan_set_lag_window", "asx_plan_lag_window", "asx_stream_set_lag_window",
 ]
 
 
@@ -72,6 +72,12 @@ def lib():
     L.asx_plan_peak_overflows.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.asx_plan_set_exact.restype = ctypes.c_int
     L.asx_plan_set_exact.argtypes = [vp, ctypes.c_int]
+    L.asx_plan_set_lag_window.restype = ctypes.c_int
+    L.asx_plan_set_lag_window.argtypes = [vp, ctypes.c_int64, ctypes.c_int64]
+    L.asx_plan_lag_window.restype = ctypes.c_int
+    L.asx_plan_lag_window.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    L.asx_stream_set_lag_window.restype = ctypes.c_int
+    L.asx_stream_set_lag_window.argtypes = [vp, ctypes.c_int64, ctypes.c_int64]
     L.asx_plan_placement.restype = ctypes.c_int
     L.asx_plan_placement.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
     L.asx_plan_set_pearson.restype = ctypes.c_int
@@ -368,6 +374,11 @@ class Stream:
     def reset(self):
         lib().asx_stream_reset(self._h)
 
+    def set_lag_window(self, lo, hi):
+        """search the peak only at lags lo..hi (frames), clamped to [-n, n-1] for each prefix length n that xcorr correlates"""
+        if lib().asx_stream_set_lag_window(self._h, int(lo), int(hi)) != 0:
+            raise AsxError(_err())
+
     def xcorr(self, sample_len):
         lag = ctypes.c_long(0)
         coef = ctypes.c_double(0.0)
@@ -418,6 +429,18 @@ class Plan:
         if lib().asx_plan_peak_overflows(self._h, ctypes.byref(c)) != 0:
             raise AsxError(_err())
         return c.value
+
+    def set_lag_window(self, lo, hi):
+        """search the peak only at lags lo..hi, -N <= lo <= hi <= N-1 (asx_plan_set_lag_window); (-N, N-1) = every lag, the default"""
+        if lib().asx_plan_set_lag_window(self._h, int(lo), int(hi)) != 0:
+            raise AsxError(_err())
+
+    @property
+    def lag_window(self):
+        lo, hi = ctypes.c_int64(0), ctypes.c_int64(0)
+        if lib().asx_plan_lag_window(self._h, ctypes.byref(lo), ctypes.byref(hi)) != 0:
+            raise AsxError(_err())
+        return lo.value, hi.value
 
     def set_exact(self, on=True):
         """on (the default): every entry point takes the second look at overflowing pairs (the device-resident batch waits

@@ -100,6 +100,26 @@ void audiosync_set_debug(int do_debug)
     pthread_mutex_unlock(&mutex);
 }
 
+static long max_lag_ms = 0; /* audiosync_set_max_lag_ms: 0 = every lag; guarded by mutex */
+/* weak: the CPU-only test builds of this file (tests/c, under the sanitizers) link a stand-in of the HIP layer that has no lag
+ * window; with the default bound of 0 the run never calls it */
+#pragma weak asx_stream_set_lag_window
+
+void audiosync_set_max_lag_ms(long ms)
+{
+    pthread_mutex_lock(&mutex);
+    max_lag_ms = ms < 0 ? -ms : ms;
+    pthread_mutex_unlock(&mutex);
+}
+
+long audiosync_get_max_lag_ms(void)
+{
+    pthread_mutex_lock(&mutex);
+    long now = max_lag_ms;
+    pthread_mutex_unlock(&mutex);
+    return now;
+}
+
 char *status_to_string(global_status_t status)
 {
     switch (status) {
@@ -362,6 +382,16 @@ int audiosync_run(const char *yt_title, long *lag)
     if (stream == NULL) {
         fprintf(stderr, "audiosync: no GPU stream: %s\n", asx_last_error());
         goto finish;
+    }
+    {
+        const long ms = audiosync_get_max_lag_ms();
+        if (ms > 0) {
+            const int64_t frames = (int64_t)llround((double)ms * SAMPLE_RATE / 1000.0);
+            if (!asx_stream_set_lag_window || asx_stream_set_lag_window(stream, -frames, frames) < 0) {
+                fprintf(stderr, "audiosync: lag window: %s\n", asx_stream_set_lag_window ? asx_last_error() : "not available");
+                goto finish;
+            }
+        }
     }
 
     LOG("starting interval loop");

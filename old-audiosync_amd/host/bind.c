@@ -108,6 +108,21 @@ static PyObject *mod_set_debug(PyObject *self, PyObject *args)
     Py_RETURN_NONE;
 }
 
+static PyObject *mod_get_max_lag(PyObject *self, PyObject *noargs)
+{
+    UNUSED(self); UNUSED(noargs);
+    return PyLong_FromLong(audiosync_get_max_lag_ms());
+}
+
+static PyObject *mod_set_max_lag(PyObject *self, PyObject *args)
+{
+    UNUSED(self);
+    long ms;
+    if (!PyArg_ParseTuple(args, "l", &ms)) return NULL;
+    audiosync_set_max_lag_ms(ms);
+    Py_RETURN_NONE;
+}
+
 static int as_doubles(PyObject *obj, Py_buffer *view, const char *what)
 {
     if (PyObject_GetBuffer(obj, view, PyBUF_FORMAT | PyBUF_C_CONTIGUOUS) != 0) return -1;
@@ -342,6 +357,8 @@ static PyMethodDef methods[] = {
     { "setup", mod_setup, METH_VARARGS, "setup(stream_name) -> bool. Always False here (no PulseAudio)." },
     { "get_debug", mod_get_debug, METH_NOARGS, "Debug logging on? Thread-safe." },
     { "set_debug", mod_set_debug, METH_VARARGS, "set_debug(flag). Thread-safe." },
+    { "get_max_lag", mod_get_max_lag, METH_NOARGS, "Bound on |lag| in ms of the next run (0 = unbounded). Thread-safe." },
+    { "set_max_lag", mod_set_max_lag, METH_VARARGS, "set_max_lag(ms): search only lags within +-ms at the next run; 0 = unbounded. Thread-safe." },
     { "cross_correlation", mod_cross_correlation, METH_VARARGS,
       "cross_correlation(source, sample) -> (ret, lag, coefficient) on the GPU; float64 or float32 buffers." },
     { "cross_correlation_batch", mod_cross_correlation_batch, METH_VARARGS,
