@@ -28,6 +28,8 @@
  * Per-pair result convention (the reference's, src/cross_correlation.c:140,276,298):
  *   ret[i] = 0 on success, -1 when the Pearson coefficient is NaN (lag[i] and
  *   coef[i] are still written, exactly as the reference leaves them).
+ *   ret[i] = -2 (asx_xcorr_windowed_f32_dev only): pair i's lag window was not a window
+ *   inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.
  */
 #ifndef AUDIOSYNC_XCORR_HIP_H
 #define AUDIOSYNC_XCORR_HIP_H
@@ -213,6 +215,27 @@ int asx_xcorr_batch_f32_dev(asx_plan *plan, const float *d_source, const float *
 int asx_xcorr_strided_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
                               const float *d_sample, size_t sample_stride, size_t batch,
                               int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream);
+
+/* Strided batches with a lag window per pair (asx_plan_set_lag_window's rule, one window per pair instead of one per plan).
+ * Pair i's inputs are exactly those of asx_xcorr_strided_f32_dev (strides, broadcast, layout rule, stream rule).  Its window is
+ * d_windows[2*i*window_stride] (lag_min) and d_windows[2*i*window_stride + 1] (lag_max), int64 in DEVICE memory, read when the
+ * kernels run: window_stride counts rows of two int64s (1 = one row per pair, 0 = one row for every pair).  So a call captured
+ * into a graph (asx_plan_set_exact(plan, 0), as any capture) follows rows that change between replays.
+ *   A valid row (-N <= lag_min <= lag_max <= N-1) follows asx_plan_set_lag_window's rule in full, the second look included (it
+ * runs with that pair's row): per pair, the results are bit for bit what asx_xcorr_strided_f32_dev returns for that pair alone
+ * on the same plan with asx_plan_set_lag_window(plan, lag_min, lag_max).  A full row [-N, N-1] gives the unwindowed bits.
+ *   Any other row (an empty one, lag_min > lag_max, included) cannot be refused before launch without a host copy: that pair
+ * returns lag = 0, coef = NaN, ret = -2, and is never listed for the second look, so the overflow and repair counters never
+ * count it; the Pearson-mode counter (asx_plan_pearson_modes) counts it once as a direct reduction.  The other pairs of the call
+ * are unaffected, bit for bit.  Every valid pair counts as the strided call would count it.
+ *   d_windows, d_coef and d_ret must not be NULL (d_lag may be); otherwise, or when the layout rule fails, the call returns -1
+ * before anything is launched and the outputs are untouched.  The plan's own window is ignored by this call and left as it is.
+ * Costs what the strided call costs: the window does not prune work. */
+int asx_xcorr_windowed_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                               const float *d_sample, size_t sample_stride,
+                               const int64_t *d_windows, size_t window_stride,
+                               size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret,
+                               void *stream);
 
 /* The batched variant over several GPUs of one node from ONE process (BASELINE.json north_star; no
  * reference equivalent): plans[i] was created on device i (any devices; all the same sample_len); the

@@ -638,15 +638,20 @@ static int prof_mark(asx_plan *p, hipStream_t s, size_t slot)
 // The pairs of a call, device resident: pair k is source src + k * src_step and sample smp + k * smp_step (elements).  The
 // transforms read the float32 views, the exact passes (refine dots, Pearson, DC removal) the TIn views at the same steps: the
 // caller's values when they are not float32, else the same buffers.  bc bit 0 / 1: the source / sample is the call's broadcast
-// track (asx_xcorr_strided_f32_dev, real-column plans), whose forward column pass is already in the plan's slot.
+// track (asx_xcorr_strided_f32_dev, real-column plans), whose forward column pass is already in the plan's slot.  win: null, or the
+// per-pair lag windows of asx_xcorr_windowed_f32_dev -- pair k's row {lag_min, lag_max} is win + 2 k win_step (device memory) --
+// which then replace the plan's window for these pairs.
 template <typename TIn> struct Pairs {
     const float *src, *smp;
     const TIn *tsrc, *tsmp;
     size_t src_step, smp_step;
     int bc;
+    const int64_t *win = nullptr;
+    size_t win_step = 0;
     Pairs at(size_t k) const
     {
-        return { src + k * src_step, smp + k * smp_step, tsrc + k * src_step, tsmp + k * smp_step, src_step, smp_step, bc };
+        return { src + k * src_step, smp + k * smp_step, tsrc + k * src_step, tsmp + k * smp_step, src_step, smp_step, bc,
+                 win ? win + 2 * k * win_step : nullptr, win_step };
     }
 };
 
@@ -718,25 +723,30 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     }
     if (mark(2)) return -1;
     // The lag window (asx_plan_set_lag_window), by value: the full one launches the same kernels as a plan that never had one.
-    // The second look at a pair runs through here too, with the window of the call that listed it.
-    const bool windowed = p->win_lo != -(int64_t)P.N || p->win_hi != (int64_t)P.N - 1;
+    // The second look at a pair runs through here too, with the window of the call that listed it.  Per-pair windows
+    // (asx_xcorr_windowed_f32_dev) replace it: the per-pair kernels read each pair's row from device memory.
+    const AsxWinRows rows{ x.win, x.win_step };
+    const AsxWinRows *pr = x.win ? &rows : nullptr;
+    const bool windowed = !pr && (p->win_lo != -(int64_t)P.N || p->win_hi != (int64_t)P.N - 1);
     const AsxWin win = asx_win_of(p->win_lo, p->win_hi, P.N);
     const uint32_t seed = windowed ? win.seed : 0u;
-    asx_launch_inv_cols(P, q, tk, o.r_out, (int)g, s, windowed ? &win : nullptr);
+    asx_launch_inv_cols(P, q, tk, o.r_out, (int)g, s, windowed ? &win : nullptr, pr);
     if (mark(3)) return -1;
-    asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, seed);
+    asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, seed, pr);
     // Blocks per pair of the exact re-evaluation: a candidate is one whole block's work whatever the grid, so the count only
     // sets how many candidates of a pair are in flight.  Nearly every block of a batch finds no candidate and exits: with 1024
     // pairs, 128 blocks each were 131 072 empty blocks, 25 us of a 2 ms step.
     const int dot_blocks = o.dot_blocks ? o.dot_blocks : (int)std::min<size_t>(ASX_DOT_BLOCKS, std::max<size_t>(8, 16384 / g));
     // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
-    asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral, seed);
+    asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral, seed, pr);
     if (mark(4)) return -1;
     if (!spectral)
         asx_launch_pearson(x.tsrc, x.tsmp, x.src_step, x.smp_step, P.N, W.seg, W.psums, y.lag, y.coef, y.ret, (int)g, s);
     else if constexpr (std::is_same<TIn, float>::value)
         asx_launch_pearson_spectral_f32(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, tk, W.spec, W.seg, W.psums, y.lag, y.coef, y.ret,
-                                        (int)g, s, seed);
+                                        (int)g, s, seed, pr);
+    // a pair whose row is not a window: (0, NaN, -2), the others untouched
+    if (pr) asx_launch_invalid_rows(rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
     if (mark(5)) return -1;
     HIP_TRY(hipGetLastError());
     return 0;
@@ -789,7 +799,7 @@ static int second_look(asx_plan *p, const Pairs<TIn> &x, const Results &y, size_
     const Pairs<TIn> xi = x.at(i);
     asx_launch_dc_remove(xi.tsrc, xi.tsmp, P.N, (double)P.F, B.stats, B.src_dc, s);
     K.shift = B.stats + 2;
-    if (run_group(p, Pairs<TIn>{ B.src_dc, xi.smp, xi.tsrc, xi.tsmp, 2 * N, N, 0 }, 1, y.at(i), s,
+    if (run_group(p, Pairs<TIn>{ B.src_dc, xi.smp, xi.tsrc, xi.tsmp, 2 * N, N, 0, xi.win, xi.win_step }, 1, y.at(i), s,
                   { .prof_group = GroupOpts::no_marks, .listed = false, .spectral = false, .dot_blocks = 2048, .pk = &K }))
         return -1;
     p->repaired++;
@@ -976,11 +986,11 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
 // ---------------------------------------------------------------------------
 // strided batches: one track against many (asx_xcorr_strided_f32_dev)
 // ---------------------------------------------------------------------------
-extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
-                                         size_t sample_stride, size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret,
-                                         void *stream)
+// asx_xcorr_strided_f32_dev and asx_xcorr_windowed_f32_dev (fn: the entry point's name for the messages), after their own null checks.
+// d_windows: null, or the per-pair windows (Pairs::win), window_stride rows apart.
+static int strided_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
+                         size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, const Results &y, void *stream)
 {
-    if (!p || !d_source || !d_sample || !d_coef) return fail("asx_xcorr_strided_f32_dev: null argument");
     std::lock_guard<std::mutex> guard(p->lock);
     DevGuard dg(p->device);
     if (!dg.ok) return fail("cannot select device %d", p->device);
@@ -989,11 +999,11 @@ extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, siz
     if (P.rlayout) {
         // k_fwd_cols_r reads every row of a pair's inputs as 16-byte loads from the pair's first frame
         if (((uintptr_t)d_source & 15u) || ((uintptr_t)d_sample & 15u))
-            return fail("asx_xcorr_strided_f32_dev: real-column plans need 16-byte aligned inputs (source %p, sample %p)",
-                        (const void *)d_source, (const void *)d_sample);
+            return fail("%s: real-column plans need 16-byte aligned inputs (source %p, sample %p)",
+                        fn, (const void *)d_source, (const void *)d_sample);
         if ((source_stride & 3u) || (sample_stride & 3u))
-            return fail("asx_xcorr_strided_f32_dev: real-column plans need strides that are multiples of 4 floats "
-                        "(source_stride %zu, sample_stride %zu)", source_stride, sample_stride);
+            return fail("%s: real-column plans need strides that are multiples of 4 floats "
+                        "(source_stride %zu, sample_stride %zu)", fn, source_stride, sample_stride);
     }
     if (batch == 0) return 0;
     const int bc = P.rlayout ? (source_stride == 0 ? 1 : 0) | (sample_stride == 0 ? 2 : 0) : 0;
@@ -1003,8 +1013,8 @@ extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, siz
             hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
             if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
             if (cap != hipStreamCaptureStatusNone)
-                return fail("asx_xcorr_strided_f32_dev: the plan's broadcast workspace does not exist yet and cannot be allocated "
-                            "during a stream capture; make one call with a stride of 0 outside the capture first");
+                return fail("%s: the plan's broadcast workspace does not exist yet and cannot be allocated "
+                            "during a stream capture; make one call with a stride of 0 outside the capture first", fn);
             asx_plan::Bcast T;
             const size_t mz = ((size_t)p->host.M1 + 1) * (size_t)p->host.M2;
             if (dev_alloc(p, &T.cx, mz) || dev_alloc(p, &T.cy, mz) || dev_alloc(p, &T.nrm, 2 * (size_t)P.ntiles) ||
@@ -1017,7 +1027,27 @@ extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, siz
         if (!asx_launch_fwd_cols_r(P, d_source, 0, d_sample, 0, B.cx, B.cy, B.nrm, B.band, 1, op0, nops, true, s))
             return fail("internal: no forward column kernel for this plan");
     }
-    return run_batch(p, { d_source, d_sample, d_source, d_sample, source_stride, sample_stride, bc }, batch, { d_lag, d_coef, d_ret }, s);
+    return run_batch(p, { d_source, d_sample, d_source, d_sample, source_stride, sample_stride, bc, d_windows, window_stride }, batch, y, s);
+}
+
+extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                         size_t sample_stride, size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret,
+                                         void *stream)
+{
+    if (!p || !d_source || !d_sample || !d_coef) return fail("asx_xcorr_strided_f32_dev: null argument");
+    return strided_batch(p, "asx_xcorr_strided_f32_dev", d_source, source_stride, d_sample, sample_stride, nullptr, 0, batch,
+                         { d_lag, d_coef, d_ret }, stream);
+}
+
+// Per-pair lag windows: the strided batch with each pair's row read on the device (run_group's per-pair kernels).  The plan's own
+// window is neither used nor changed.
+extern "C" int asx_xcorr_windowed_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                          size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                          int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream)
+{
+    if (!p || !d_source || !d_sample || !d_windows || !d_coef || !d_ret) return fail("asx_xcorr_windowed_f32_dev: null argument");
+    return strided_batch(p, "asx_xcorr_windowed_f32_dev", d_source, source_stride, d_sample, sample_stride, d_windows, window_stride,
+                         batch, { d_lag, d_coef, d_ret }, stream);
 }
 
 extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const float *d_sample,

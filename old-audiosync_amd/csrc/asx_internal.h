@@ -112,7 +112,7 @@ __host__ __device__ inline bool asx_win_has(const AsxWin &z, uint32_t idx)
     const uint32_t d = idx >= z.a ? idx - z.a : idx + (z.n - z.a);
     return d <= z.w;
 }
-inline AsxWin asx_win_of(int64_t lo, int64_t hi, uint32_t N)
+__host__ __device__ inline AsxWin asx_win_of(int64_t lo, int64_t hi, uint32_t N)
 {
     AsxWin z;
     z.n = 2u * N;
@@ -120,6 +120,27 @@ inline AsxWin asx_win_of(int64_t lo, int64_t hi, uint32_t N)
     z.w = (uint32_t)(hi - lo);
     z.seed = (lo < 0 && hi >= 0) ? 0u : z.a;
     return z;
+}
+
+// Per-pair lag windows (asx_xcorr_windowed_f32_dev): pair k of a group reads its row {lag_min, lag_max} at rows + 2 k step, in device
+// memory, when its kernels run (step 0: one row for every pair).  The group's pointer is already offset to its first pair
+// (Pairs::at, asx_api.hip).  The per-pair kernels (k_inv_cols_rp, k_inv_cols_wp, k_finalize_p, k_refine_pick_p, k_pearson_prep_p)
+// form their AsxWin from it with asx_win_row instead of taking one by value.
+struct AsxWinRows {
+    const int64_t *rows;
+    size_t step;
+};
+// A valid row (-N <= lag_min <= lag_max <= N-1) gives asx_win_of's window.  Any other row gives n = 0, a window that holds no index:
+// nothing competes, nothing is listed, the running maximum stays empty (seed 0), and k_invalid_rows writes (0, NaN, -2) behind the
+// Pearson kernels.
+__device__ inline bool asx_win_row(const AsxWinRows &R, size_t pair, uint32_t N, AsxWin &z)
+{
+    const int64_t *row = R.rows + 2 * pair * R.step;
+    const int64_t lo = row[0], hi = row[1], n = (int64_t)N;
+    const bool ok = -n <= lo && lo <= hi && hi <= n - 1;
+    if (ok) z = asx_win_of(lo, hi, N);
+    else z.a = z.w = z.seed = z.n = 0u;
+    return ok;
 }
 
 // kernel launchers (defined in xcorr_kernels.hip, called from asx_api.hip)
@@ -182,30 +203,35 @@ void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, fl
                          float2 *zya, const AsxPeakWs &W, int npairs, hipStream_t s);
 void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga,
                      const AsxPeakWs &W, int npairs, hipStream_t s);
+// rows (per-pair windows) takes precedence over win (the plan's)
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out,
-                         int npairs, hipStream_t s, const AsxWin *win = nullptr);
+                         int npairs, hipStream_t s, const AsxWin *win = nullptr, const AsxWinRows *rows = nullptr);
 // rlayout.hip: the real-column decomposition (production lengths); false = no kernel compiled in for this plan.
 // bc (the broadcast forms of asx_xcorr_strided_f32_dev): bit 0 = cx is the plan's broadcast slot (one C for every pair), bit 1 = cy is
 bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
                        hipStream_t s);
 bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
                            float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s);
-// win: null = every lag competes (k_inv_cols_r); else the lag-window form (k_inv_cols_rw)
+// win: null = every lag competes (k_inv_cols_r); else the lag-window form (k_inv_cols_rw); rows: the per-pair form (k_inv_cols_rp)
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
-                           const AsxWin *win = nullptr);
+                           const AsxWin *win = nullptr, const AsxWinRows *rows = nullptr);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 bool asx_rlayout_available(const AsxDev &P); // all three kernels compiled in for this plan's schedules
 int asx_rlayout_band_rows(const AsxDev &P);
-// seed (the lag window's, AsxWin): the index an empty running maximum stands for, and the one whose exact value competes signed
+// seed (the lag window's, AsxWin): the index an empty running maximum stands for, and the one whose exact value competes signed;
+// rows (per-pair windows): each pair's own seed, from its row (k_finalize_p, k_refine_pick_p, k_pearson_prep_p)
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base = 0,
-                         uint32_t seed = 0);
+                         uint32_t seed = 0, const AsxWinRows *rows = nullptr);
+// behind the Pearson kernels of a group with per-pair windows: (lag, coef, ret) = (0, NaN, -2) for every pair whose row is invalid
+void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 // The exact passes over float or double inputs (instances for both next to the kernels, xcorr_kernels.hip).  The pairs' inputs
 // are src_pitch / smp_pitch elements apart (0 = one track for every pair).
 // refine: pick = false: the exact values only; the caller's next kernel applies the rule (k_pearson_prep)
 template <typename TIn>
 void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
-                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed = 0);
+                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed = 0,
+                       const AsxWinRows *rows = nullptr);
 template <typename TIn>
 void asx_launch_pearson(const TIn *src, const TIn *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len, const AsxSeg *seg,
                         double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
@@ -216,7 +242,7 @@ void asx_launch_pearson_partial_spec_f32(const float *src, const float *smp, siz
 // group's transform kernels)
 void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
                                      const AsxPeakWs &W, const AsxSpecWs &S, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
-                                     int32_t *ret, int npairs, hipStream_t s, uint32_t seed = 0);
+                                     int32_t *ret, int npairs, hipStream_t s, uint32_t seed = 0, const AsxWinRows *rows = nullptr);
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
                               double min_confidence, double sample_rate, int64_t *lag_ms, int32_t *accept,
                               hipStream_t s);

@@ -709,6 +709,18 @@ __global__ __launch_bounds__(NT, 4) void k_inv_cols_rw(const RArgs P, const floa
 #include "inv_cols_r_body.h"
 }
 
+// the per-pair form (asx_xcorr_windowed_f32_dev): the window is the pair's row in device memory, read once per block in front of
+// the tile loads; an invalid row holds no lag (asx_win_row)
+template <class S1, int TC, int NT>
+__global__ __launch_bounds__(NT, 4) void k_inv_cols_rp(const RArgs P, const float2 *__restrict__ qi, size_t pair_pitch,
+                                                        AsxPeakWs W, float *__restrict__ r_out, unsigned first_gen, AsxWinRows R)
+{
+    constexpr bool WIN = true;
+    AsxWin Z;
+    (void)asx_win_row(R, blockIdx.x, P.N, Z);
+#include "inv_cols_r_body.h"
+}
+
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
@@ -821,7 +833,7 @@ void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sban
 }
 
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
-                           const AsxWin *win)
+                           const AsxWin *win, const AsxWinRows *rows)
 {
     if (!P.col_pairs) return false;
     const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2;
@@ -829,6 +841,13 @@ bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W,
     if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                               \
         const size_t lds = (size_t)(m1) * (t) * sizeof(float2);                                                             \
         const dim3 grid(npairs, rcol_grid_x(P.M2 / (t), asx_ilog2(t)));                                                     \
+        if (rows) {                                                                                                         \
+            const void *fp = (const void *)k_inv_cols_rp<Sched<m1, __VA_ARGS__>, t, nt>;                                    \
+            allow_big_lds_r(fp, lds);                                                                                       \
+            hipLaunchKernelGGL((k_inv_cols_rp<Sched<m1, __VA_ARGS__>, t, nt>), grid, dim3(nt), lds, s, rargs_of(P), q, pitch, W, \
+                               r_out, resident_blocks(fp, nt, lds), *rows);                                                 \
+            return true;                                                                                                    \
+        }                                                                                                                   \
         if (win) {                                                                                                          \
             const void *fw = (const void *)k_inv_cols_rw<Sched<m1, __VA_ARGS__>, t, nt>;                                    \
             allow_big_lds_r(fw, lds);                                                                                       \

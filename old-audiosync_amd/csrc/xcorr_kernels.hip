@@ -556,6 +556,18 @@ __global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols_w(const Asx
 #include "inv_cols_body.h"
 }
 
+// the per-pair form (asx_xcorr_windowed_f32_dev): the window is the pair's row in device memory, read once per block in front of
+// the tile loads; an invalid row holds no lag (asx_win_row)
+template <int MAXR, class S1 = void, int TC = 0, int NT = 0>
+__global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols_wp(const AsxDev *__restrict__ Pp, const float2 *__restrict__ ga,
+                                                                      AsxPeakWs W, float *__restrict__ r_out, AsxWinRows R)
+{
+    constexpr bool WIN = true;
+    AsxWin Z;
+    (void)asx_win_row(R, blockIdx.y, Pp->N, Z);
+#include "inv_cols_body.h"
+}
+
 #if ASX_HAS_PART(64)
 // ---------------------------------------------------------------------------
 // k_finalize: grid (npairs).  Reduce tile partials, wrap the lag, pick segments.
@@ -564,43 +576,32 @@ __global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols_w(const Asx
 __global__ __launch_bounds__(ASX_THREADS) void k_finalize(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
                                                            uint32_t pair_base, uint32_t seed)
 {
-    const uint32_t N = Pp->N;
-    __shared__ uint32_t nsel;
-    const size_t pair = blockIdx.x;
-    const asx_peak_t best = W.pairmax[pair];        // float32 maximum, smallest lag among equal keys
-    const uint32_t ntot = W.cand_n[pair];
-    const uint32_t n = ntot < W.cap ? ntot : W.cap;
-    // the tiles collected against the running maximum; keep what is near the FINAL maximum
-    const float thr = near_max_threshold(peak_key(best), W.bound2[pair]);
-    if (threadIdx.x == 0) nsel = 0;
-    __syncthreads();
-    const AsxCand *c = W.cand + pair * (size_t)W.cap;
-    uint32_t *out = W.refine_idx + pair * (size_t)W.cap;
-    for (uint32_t i = threadIdx.x; i < n; i += ASX_THREADS) {
-        const AsxCand e = c[i];
-        if (e.key >= thr) out[atomicAdd(&nsel, 1u)] = e.idx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        AsxSeg sg = make_seg(best ? peak_index(best) : seed, N);
-        // One candidate: the float32 argmax is unambiguous.  More than the list holds (a signal periodic in
-        // more than `cap` lags, an offset of hundreds of deviations in both tracks): the float32 argmax is only a
-        // placeholder.  The pair is MARKED (its ret becomes ASX_RET_INEXACT in k_pearson_final), counted
-        // (asx_plan_peak_overflows) and put on the list the entry points read to take the second look
-        // (asx_api.hip: resolve_overflows): the reference's scan has no candidate limit (src/cross_correlation.c:52-67).
-        const bool over = ntot > W.cap;
-        if (over) sg.flags = ASX_SEG_INEXACT;
-        seg[pair] = sg;
-        W.refine_n[pair] = (!over && nsel >= 2u) ? nsel : 0u;
-        if (over) {
-            atomicAdd(W.overflows, 1ull);
-            if (W.over_list) {
-                const uint32_t slot = atomicAdd(W.over_n, 1u);
-                if (slot < W.over_cap) W.over_list[slot] = pair_base + (uint32_t)pair;
-                if (W.over_host) (void)__hip_atomic_fetch_add(W.over_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
+#include "finalize_body.h"
+}
+
+// the per-pair form (asx_xcorr_windowed_f32_dev): the seed is the pair's own, from its row (0 for an invalid row, which lists nothing:
+// it never overflows, and k_invalid_rows overwrites its results)
+__global__ __launch_bounds__(ASX_THREADS) void k_finalize_p(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
+                                                             uint32_t pair_base, AsxWinRows R)
+{
+    AsxWin Z;
+    (void)asx_win_row(R, blockIdx.x, Pp->N, Z);
+    const uint32_t seed = Z.seed;
+#include "finalize_body.h"
+}
+
+// grid (npairs / ASX_THREADS): behind k_pearson_final / k_pearson_final_spec of a group with per-pair windows, the pairs whose row is
+// invalid (asx_win_row) get lag 0, a NaN coefficient and ret -2; the others are not touched
+__global__ __launch_bounds__(ASX_THREADS) void k_invalid_rows(AsxWinRows R, uint32_t N, int npairs, int64_t *__restrict__ lag,
+                                                               double *__restrict__ coef, int32_t *__restrict__ ret)
+{
+    const int pair = blockIdx.x * ASX_THREADS + threadIdx.x;
+    if (pair >= npairs) return;
+    AsxWin Z;
+    if (asx_win_row(R, (size_t)pair, N, Z)) return;
+    if (lag) lag[pair] = 0;
+    coef[pair] = (double)NAN;
+    ret[pair] = -2;
 }
 
 // ---------------------------------------------------------------------------
@@ -684,35 +685,17 @@ __global__ __launch_bounds__(ASX_THREADS) void k_refine_dots(const AsxDev *__res
 __global__ __launch_bounds__(ASX_THREADS) void k_refine_pick(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
                                                               uint32_t seed)
 {
-    __shared__ double rkey[ASX_THREADS / 64];
-    __shared__ uint32_t ridx[ASX_THREADS / 64];
-    const size_t pair = blockIdx.x;
-    const uint32_t n = W.refine_n[pair];
-    if (n < 2u) return;
-    double bk = -INFINITY;
-    uint32_t bi = 0xFFFFFFFFu;
-    for (uint32_t i = threadIdx.x; i < n; i += ASX_THREADS) {
-        const uint32_t idx = W.refine_idx[pair * (size_t)W.cap + i];
-        const double v = W.refine_val[pair * (size_t)W.cap + i];
-        double key;
-        if (idx == seed) key = (v != v) ? (double)INFINITY : v + 0.0;
-        else { key = fabs(v); if (key != key) key = -(double)INFINITY; }
-        if (key > bk || (key == bk && idx < bi)) { bk = key; bi = idx; }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ok = __shfl_xor(bk, off, 64);
-        const uint32_t oi = (uint32_t)__shfl_xor((int)bi, off, 64);
-        if (ok > bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { rkey[wave] = bk; ridx[wave] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < ASX_THREADS / 64; w++)
-            if (rkey[w] > bk || (rkey[w] == bk && ridx[w] < bi)) { bk = rkey[w]; bi = ridx[w]; }
-        if (bi != 0xFFFFFFFFu) seg[pair] = make_seg(bi, Pp->N);
-    }
+#include "refine_pick_body.h"
+}
+
+// the per-pair form (asx_xcorr_windowed_f32_dev): the seed is the pair's own, from its row
+__global__ __launch_bounds__(ASX_THREADS) void k_refine_pick_p(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
+                                                                AsxWinRows R)
+{
+    AsxWin Z;
+    (void)asx_win_row(R, blockIdx.x, Pp->N, Z);
+    const uint32_t seed = Z.seed;
+#include "refine_pick_body.h"
 }
 
 // ---------------------------------------------------------------------------
@@ -1064,9 +1047,9 @@ bool asx_launch_rows_static(const AsxDev &P, const float2 *zxa, const float2 *zy
 void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga, const AsxPeakWs &W,
                              int npairs, hipStream_t s);
 bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                hipStream_t s, const AsxWin *win);
+                                hipStream_t s, const AsxWin *win, const AsxWinRows *rows);
 void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                 hipStream_t s, const AsxWin *win);
+                                 hipStream_t s, const AsxWin *win, const AsxWinRows *rows);
 
 #define ASX_FWD_LAUNCH(...) \
     do { allow_big_lds((const void *)k_fwd_cols<__VA_ARGS__>, lds_bytes_cols(P)); \
@@ -1129,14 +1112,17 @@ void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *z
 #undef ASX_ROWS_LAUNCH
 
 #define ASX_INV_LAUNCH(...) \
-    do { if (win) { allow_big_lds((const void *)k_inv_cols_w<__VA_ARGS__>, lds_bytes_cols(P)); \
+    do { if (rows) { allow_big_lds((const void *)k_inv_cols_wp<__VA_ARGS__>, lds_bytes_cols(P)); \
+                     hipLaunchKernelGGL((k_inv_cols_wp<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, *rows); \
+                     break; } \
+         if (win) { allow_big_lds((const void *)k_inv_cols_w<__VA_ARGS__>, lds_bytes_cols(P)); \
                     hipLaunchKernelGGL((k_inv_cols_w<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, *win); \
                     break; } \
          allow_big_lds((const void *)k_inv_cols<__VA_ARGS__>, lds_bytes_cols(P)); \
          hipLaunchKernelGGL((k_inv_cols<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out); } while (0)
 #if ASX_HAS_PART(16)
 bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                hipStream_t s, const AsxWin *win)
+                                hipStream_t s, const AsxWin *win, const AsxWinRows *rows)
 {
     dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
 #define ASX_TRY_STATIC(m1, t, nt, maxr, ...) \
@@ -1148,7 +1134,7 @@ bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeak
 #endif
 #if ASX_HAS_PART(32)
 void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                 hipStream_t s, const AsxWin *win)
+                                 hipStream_t s, const AsxWin *win, const AsxWinRows *rows)
 {
     dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
     const int mr = max_radix(P.st1);
@@ -1212,25 +1198,33 @@ void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, floa
 }
 
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                         hipStream_t s, const AsxWin *win)
+                         hipStream_t s, const AsxWin *win, const AsxWinRows *rows)
 {
-    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s, win)) return;
-    if (generic_only() || !asx_launch_inv_cols_static(P, ga, W, r_out, npairs, s, win))
-        asx_launch_inv_cols_generic(P, ga, W, r_out, npairs, s, win);
+    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s, win, rows)) return;
+    if (generic_only() || !asx_launch_inv_cols_static(P, ga, W, r_out, npairs, s, win, rows))
+        asx_launch_inv_cols_generic(P, ga, W, r_out, npairs, s, win, rows);
 }
 
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,
-                         uint32_t seed)
+                         uint32_t seed, const AsxWinRows *rows)
 {
-    hipLaunchKernelGGL(k_finalize, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, seed);
+    if (rows) hipLaunchKernelGGL(k_finalize_p, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, *rows);
+    else hipLaunchKernelGGL(k_finalize, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, seed);
+}
+
+void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_invalid_rows, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, rows, N, npairs, lag,
+                       coef, ret);
 }
 
 template <typename TIn>
 void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
-                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed)
+                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed, const AsxWinRows *rows)
 {
     hipLaunchKernelGGL(k_refine_dots<TIn>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
-    if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, seed);
+    if (pick && rows) hipLaunchKernelGGL(k_refine_pick_p, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, *rows);
+    else if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, seed);
 }
 
 // Partial blocks per pair: a function of the segment's BASIS LENGTH ONLY -- one block per 16 sweeps of 256 threads x 4
@@ -1295,7 +1289,7 @@ void asx_launch_dc_remove(const TIn *src, const TIn *smp, uint32_t N, double sca
 // the exact passes' instances (asx_internal.h): float32 and float64 inputs
 #define ASX_EXACT_PASSES(T)                                                                                                             \
     template void asx_launch_refine<T>(const AsxDev &, const T *, size_t, const T *, size_t, const AsxPeakWs &, AsxSeg *, int,           \
-                                       hipStream_t, int, bool, uint32_t);                                                               \
+                                       hipStream_t, int, bool, uint32_t, const AsxWinRows *);                                           \
     template void asx_launch_pearson<T>(const T *, const T *, size_t, size_t, uint32_t, const AsxSeg *, double *, int64_t *, double *,   \
                                         int32_t *, int, hipStream_t);                                                                   \
     template void asx_launch_dc_remove<T>(const T *, const T *, uint32_t, double, double *, float *, hipStream_t);

@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "asx_current_device", "asx_plan_timings_ms", "asx_xcorr_batch_multi", "asx_plan_layout", "asx_plan_narrowed_calls",
     "asx_plan_set_pearson", "asx_plan_pearson_modes", "asx_plan_placement", "asx_host_malloc", "asx_host_free", "asx_shard_range", "asx_result_bytes", "asx_comm_create", "asx_comm_destroy", "asx_xcorr_batch_multi_dev",
     "asx_xcorr_strided_f32_dev", "asx_plan_set_lag_window", "asx_plan_lag_window", "asx_stream_set_lag_window",
+    "asx_xcorr_windowed_f32_dev",
 ]
 
 
@@ -108,6 +109,9 @@ def lib():
     L.asx_xcorr_batch_f32_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, vp, vp, vp]
     L.asx_xcorr_strided_f32_dev.restype = ctypes.c_int
     L.asx_xcorr_strided_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, vp]
+    L.asx_xcorr_windowed_f32_dev.restype = ctypes.c_int
+    L.asx_xcorr_windowed_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
+                                             vp, vp, vp, vp]
     L.asx_shard_range.restype = ctypes.c_int
     L.asx_shard_range.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t),
                                   ctypes.POINTER(ctypes.c_size_t)]
@@ -278,6 +282,48 @@ def xcorr_batch_multi(plans, source, sample):
     if rc != 0:
         raise AsxError(_err())
     return lag, coef, ret
+
+
+def windowed_args(n, source, sample, windows):
+    """Host checks of Plan.xcorr_windowed_f32 for a plan of sample length n: source [2N] or [B, 2N], sample [N] or [B, N], windows
+    [2] or [B, 2] integers (a 1-D operand serves every pair).  -> (source, sample, windows, batch, source_stride, sample_stride,
+    window_stride) as contiguous float32 / int64 arrays and strides in elements / rows.  ValueError on anything else.  The rows'
+    values are not checked: a row that is not a window comes back as (0, NaN, -2)."""
+    s = np.ascontiguousarray(source, dtype=np.float32)
+    t = np.ascontiguousarray(sample, dtype=np.float32)
+    w = np.asarray(windows)
+    if w.dtype.kind not in "iu":
+        raise ValueError("windows must hold integers (lag_min, lag_max), not %s" % w.dtype)
+    w = np.ascontiguousarray(w, dtype=np.int64)
+    if s.ndim not in (1, 2) or t.ndim not in (1, 2) or s.shape[-1] != 2 * n or t.shape[-1] != n:
+        raise ValueError("source must be [2N] or [B, 2N] and sample [N] or [B, N] with N = %d" % n)
+    if w.ndim not in (1, 2) or w.shape[-1] != 2:
+        raise ValueError("windows must be [2] or [B, 2]")
+    sizes = {a.shape[0] for a in (s, t, w) if a.ndim == 2}
+    if len(sizes) > 1:
+        raise ValueError("source, sample and windows have different batch sizes %s" % sorted(sizes))
+    batch = sizes.pop() if sizes else 1
+    if batch < 1:
+        raise ValueError("empty batch")
+    return s, t, w, batch, 2 * n if s.ndim == 2 else 0, n if t.ndim == 2 else 0, 1 if w.ndim == 2 else 0
+
+
+def position_rows(n, hop, batch, p_lo, p_hi):
+    """Lag windows of Plan.xcorr_windows_f32(..., positions=(p_lo, p_hi)): window k (source frames k*hop .. k*hop + 2N - 1 of the
+    recording, 0 <= k < batch) holds a sample that starts at recording frame k*hop + lag, so its rows are
+    [p_lo - k*hop, p_hi - k*hop] clipped to [-N, N-1].  The windows whose clipped row is not empty are k0 <= k < k1, a contiguous
+    range.  -> (k0, k1, rows int64 [k1 - k0, 2]); k0 == k1 when no window can hold such a start."""
+    n, hop, batch, p_lo, p_hi = int(n), int(hop), int(batch), int(p_lo), int(p_hi)
+    if hop < 1 or p_lo > p_hi:
+        raise ValueError("need hop >= 1 and p_lo <= p_hi")
+    # non-empty: p_lo - k hop <= N - 1 and p_hi - k hop >= -N
+    k0 = max(0, -((n - 1 - p_lo) // hop))       # ceil((p_lo - N + 1) / hop)
+    k1 = min(batch, (p_hi + n) // hop + 1)      # floor((p_hi + N) / hop) + 1
+    if k1 <= k0:
+        return 0, 0, np.zeros((0, 2), dtype=np.int64)
+    k = np.arange(k0, k1, dtype=np.int64) * hop
+    rows = np.stack([np.maximum(p_lo - k, -n), np.minimum(p_hi - k, n - 1)], axis=1)
+    return k0, k1, np.ascontiguousarray(rows, dtype=np.int64)
 
 
 class PinnedArray:
@@ -547,8 +593,18 @@ class Plan:
         if rc != 0:
             raise AsxError(_err())
 
-    def _strided_host(self, src, src_stride, smp, smp_stride, batch):
-        """host float32 buffers -> device copies -> asx_xcorr_strided_f32_dev -> (lag, coef, ret)"""
+    def xcorr_windowed_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, d_lag, d_coef, d_ret,
+                           stream=0):
+        """raw device pointers (ints): asx_xcorr_windowed_f32_dev -- the strided batch with pair i's lag window at
+        d_windows[2 i window_stride], d_windows[2 i window_stride + 1] (int64, device memory); asynchronous on `stream`"""
+        rc = lib().asx_xcorr_windowed_f32_dev(self._h, d_src, int(src_stride), d_smp, int(smp_stride), d_windows, int(window_stride),
+                                              int(batch), d_lag or None, d_coef, d_ret, stream or None)
+        if rc != 0:
+            raise AsxError(_err())
+
+    def _strided_host(self, src, src_stride, smp, smp_stride, batch, windows=None, window_stride=0):
+        """host float32 buffers (and int64 windows) -> device copies -> asx_xcorr_strided_f32_dev (asx_xcorr_windowed_f32_dev)
+        -> (lag, coef, ret)"""
         L = lib()
         bufs = []
         try:
@@ -560,10 +616,16 @@ class Plan:
                 return ptr
             d_src, d_smp = dev(src.nbytes), dev(smp.nbytes)
             d_lag, d_coef, d_ret = dev(8 * batch), dev(8 * batch), dev(4 * batch)
-            for d, h in ((d_src, src), (d_smp, smp)):
+            ups = [(d_src, src), (d_smp, smp)]
+            if windows is not None:
+                ups.append((dev(windows.nbytes), windows))
+            for d, h in ups:
                 if L.asx_memcpy_h2d(d, h.ctypes.data, h.nbytes) != 0:
                     raise AsxError(_err())
-            self.xcorr_strided_dev(d_src, src_stride, d_smp, smp_stride, batch, d_lag, d_coef, d_ret)
+            if windows is None:
+                self.xcorr_strided_dev(d_src, src_stride, d_smp, smp_stride, batch, d_lag, d_coef, d_ret)
+            else:
+                self.xcorr_windowed_dev(d_src, src_stride, d_smp, smp_stride, ups[2][0], window_stride, batch, d_lag, d_coef, d_ret)
             self.sync()
             lag = np.zeros(batch, dtype=np.int64)
             coef = np.zeros(batch, dtype=np.float64)
@@ -592,12 +654,25 @@ class Plan:
         batch = bs if bs is not None else bt if bt is not None else 1
         return self._strided_host(s, 2 * n if s.ndim == 2 else 0, t, n if t.ndim == 2 else 0, batch)
 
-    def xcorr_windows_f32(self, recording, sample, hop):
+    def xcorr_windowed_f32(self, source, sample, windows):
+        """Pairs with a lag window each (asx_xcorr_windowed_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N];
+        windows: integers [2] (one window for every pair) or [B, 2], rows (lag_min, lag_max).  A 1-D operand serves every pair; all
+        1-D is one pair.  Shapes are checked on the host (ValueError) before anything is uploaded; a row that is not a window
+        inside [-N, N-1] gives that pair (0, NaN, -2).  The plan's own window is not used.  Returns (lag, coef, ret) like
+        xcorr_batch_f32."""
+        s, t, w, batch, ss, ts, ws = windowed_args(self.sample_len, source, sample, windows)
+        return self._strided_host(s, ss, t, ts, batch, w, ws)
+
+    def xcorr_windows_f32(self, recording, sample, hop, positions=None):
         """Windows recording[k*hop : k*hop + 2N] (k = 0 .. (len - 2N) // hop) of one long float32 recording, each correlated with
         the one float32 sample [N]: one (lag, coef, ret) per window, arrays like xcorr_batch_f32's.  The recording and the sample
         are uploaded once and the sample is transformed once.  Which window holds the sample is the caller's decision (for
         instance the largest |coef| with ret == 0); a clip that straddles two windows shows in both with lower coefficients, so a
-        hop of at most N keeps every clip of length N whole in some window.  On real-column plans hop must be a multiple of 4."""
+        hop of at most N keeps every clip of length N whole in some window.  On real-column plans hop must be a multiple of 4.
+        positions=(p_lo, p_hi): the sample is known to start between recording frames p_lo and p_hi.  Window k then searches only
+        lags [p_lo - k*hop, p_hi - k*hop] clipped to [-N, N-1] (position_rows), in one asx_xcorr_windowed_f32_dev call over the
+        windows where that is not empty; the others are not correlated and come back (0, NaN, -2).  A window's lag l is the start
+        frame k*hop + l.  positions=None: every lag of every window, the plan's own window applies."""
         n = self.sample_len
         r = np.ascontiguousarray(recording, dtype=np.float32).ravel()
         t = np.ascontiguousarray(sample, dtype=np.float32).ravel()
@@ -609,7 +684,18 @@ class Plan:
         if r.size < 2 * n:
             raise ValueError("recording shorter than one window of 2N = %d frames" % (2 * n))
         batch = (r.size - 2 * n) // hop + 1
-        return self._strided_host(r, hop, t, 0, batch)
+        if positions is None:
+            return self._strided_host(r, hop, t, 0, batch)
+        p_lo, p_hi = (int(v) for v in positions)
+        k0, k1, rows = position_rows(n, hop, batch, p_lo, p_hi)
+        lag = np.zeros(batch, dtype=np.int64)
+        coef = np.full(batch, np.nan, dtype=np.float64)
+        ret = np.full(batch, -2, dtype=np.int32)
+        if k1 > k0:
+            part = self._strided_host(np.ascontiguousarray(r[k0 * hop:(k1 - 1) * hop + 2 * n]), hop, t, 0, k1 - k0, rows, 1)
+            for whole, got in zip((lag, coef, ret), part):
+                whole[k0:k1] = got
+        return lag, coef, ret
 
     def debug_r_dev(self, d_src, d_smp, d_r, d_lag, d_coef, d_ret, stream=0):
         rc = lib().asx_xcorr_debug_r_dev(self._h, d_src, d_smp, d_r, d_lag, d_coef, d_ret, stream or None)
