@@ -30,6 +30,8 @@
  *   coef[i] are still written, exactly as the reference leaves them).
  *   ret[i] = -2 (asx_xcorr_windowed_f32_dev only): pair i's lag window was not a window
  *   inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.
+ *   ret = -3 (asx_xcorr_topk_f32_dev only): no lag is left for this entry of the pair (its
+ *   window minus the zones around the earlier entries is empty); lag = 0 and coef = NaN.
  */
 #ifndef AUDIOSYNC_XCORR_HIP_H
 #define AUDIOSYNC_XCORR_HIP_H
@@ -236,6 +238,46 @@ int asx_xcorr_windowed_f32_dev(asx_plan *plan, const float *d_source, size_t sou
                                const int64_t *d_windows, size_t window_stride,
                                size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret,
                                void *stream);
+
+/* The K strongest separated lags per pair, each with its own Pearson coefficient.  The peak of r is not normalised: its argmax
+ * favours lags with a long overlap, and repeated bars, choruses, echoes and reverb give several near-equal peaks, so the true
+ * offset can be the runner-up -- with the higher coefficient.  This call returns the runner-ups too, and how close they are.
+ *   Inputs.  Strides, broadcast (stride 0), the layout rule of real-column plans and the stream rule are exactly those of
+ * asx_xcorr_strided_f32_dev.  d_windows == NULL: the plan's window (asx_plan_set_lag_window) applies to every pair.  Otherwise
+ * d_windows holds per-pair rows with the rule of asx_xcorr_windowed_f32_dev, and the plan's window is ignored and left as it is.
+ * 1 <= k <= ASX_TOPK_MAX (8) and min_separation >= 0; otherwise, or when d_coef or d_ret is NULL or the layout rule fails, the
+ * call returns -1 before anything is launched and the outputs are untouched.  d_lag may be NULL.
+ *   Outputs.  Entry j (0-based) of pair i is at index i*k + j of d_lag, d_coef and d_ret.
+ *   The rule (float64 semantics, exact by construction like every entry point).  A_1 is the pair's window.  A_j is A_1 minus every
+ * lag l with |l - lag_i| <= min_separation for an earlier entry i < j -- linear lag distance, so lags -N and N-1 are far apart.
+ * Entry j is max_abs_index() (src/cross_correlation.c:52-67) over the elements of A_j in ascending index order (lag l >= 0 is
+ * index l, lag l < 0 index 2N + l, as in the window rule): the smallest index of A_j is the seed and competes with its SIGNED
+ * value, every other element with fabs and the strict '>'.  A window with no zone is exactly the window rule.  After the peak,
+ * the lag wrap, the segments and the Pearson coefficient follow cross_correlation() (:256-272), as for entry 0.
+ *   If A_j is empty, entry j and every later entry of the pair are (0, NaN, -3).  An invalid row gives (0, NaN, -2) for all k
+ * entries of its pair.  The other pairs are untouched, bit for bit.
+ *   Entry 0 of every pair that did not take the second look is bit for bit the (lag, coef, ret) of asx_xcorr_strided_f32_dev
+ * (d_windows == NULL) or asx_xcorr_windowed_f32_dev (with d_windows) on the same plan; k = 1 launches exactly that call, so it is
+ * bit for bit that call for every pair, the second look and the counters included.  Entries j >= 1 take either Pearson form
+ * within the 1e-5 contract; with asx_plan_set_pearson(plan, 0) entry j's coefficient is bit for bit the direct reduction at its
+ * lag (what the windowed call returns for the row [lag_j, lag_j]).
+ *   Exact mode (the default).  A pair whose near-tie list overflows in any of its passes is listed once; the second look then
+ * recomputes all k entries of that pair with lists that hold every lag and the direct Pearson form.  asx_plan_peak_overflows and
+ * asx_plan_peak_repairs count such a pair once per call.  Under the spectral setting, asx_plan_pearson_modes counts every entry of
+ * every pair once, in the mode its pass took (an entry with no lag left, and every entry of an invalid row, as a direct reduction;
+ * the second look's recomputation is not counted again); under the direct setting it counts nothing, as for every entry point.
+ *   Asynchronous mode (asx_plan_set_exact(plan, 0)): the overflowing entry and every later entry of that pair get ret = 1 (their
+ * zones came from a float32 argmax), whatever they hold; earlier entries keep their values; nothing is left on the overflow list.
+ * The call is then asynchronous and capturable.  Its per-group state lives in workspaces the plan allocates when it is created.
+ *   Cost: the transforms run once per call; every further entry is one more inverse column pass over the resident product
+ * spectrum plus the tail (finalize, exact re-evaluation, Pearson).  A runner-up at the noise floor has many near-ties in |r|,
+ * and their exact re-evaluation makes its pass cost more. */
+#define ASX_TOPK_MAX 8
+int asx_xcorr_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                           const float *d_sample, size_t sample_stride,
+                           const int64_t *d_windows, size_t window_stride,
+                           size_t batch, int k, int64_t min_separation,
+                           int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream);
 
 /* The batched variant over several GPUs of one node from ONE process (BASELINE.json north_star; no
  * reference equivalent): plans[i] was created on device i (any devices; all the same sample_len); the

@@ -108,6 +108,7 @@ struct asx_plan {
         AsxSeg *seg = nullptr;
         double *psums = nullptr;
         AsxSpecWs spec{};      // spectral Pearson (pearson_spectral.hip): work list, window sums, mode counters
+        AsxTopkWs tk{};        // top-k passes (asx_xcorr_topk_f32_dev): per-pair records and one pass's results
     } lanes[2];
     int nlanes = 1;   // ASX_LANES=2 enables the second lane (measured: +0..4 %)
     hipEvent_t fork = nullptr;
@@ -253,7 +254,9 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
             dev_alloc(p, &ln.pk.cand, g * cap) || dev_alloc(p, &ln.pk.refine_n, g) ||
             dev_alloc(p, &ln.pk.refine_idx, g * cap) || dev_alloc(p, &ln.pk.refine_val, g * cap) ||
             dev_alloc(p, &ln.pk.overflows, 1) ||
-            dev_alloc(p, &ln.seg, g) || dev_alloc(p, &ln.psums, g * (size_t)asx_pearson_blocks((uint32_t)N) * 6))
+            dev_alloc(p, &ln.seg, g) || dev_alloc(p, &ln.psums, g * (size_t)asx_pearson_blocks((uint32_t)N) * 6) ||
+            dev_alloc(p, &ln.tk.pairs, g) || dev_alloc(p, &ln.tk.lag, g) || dev_alloc(p, &ln.tk.coef, g) || dev_alloc(p, &ln.tk.ret, g) ||
+            dev_alloc(p, &ln.tk.sink, 1))
             return -1;
         HIP_TRY(hipMemset(ln.pk.overflows, 0, sizeof(unsigned long long)));
         ln.pk.band = nullptr; ln.pk.tile_peak = nullptr;
@@ -549,6 +552,18 @@ extern "C" int asx_plan_debug_peak(asx_plan *p, size_t pair, float *bound2, uint
     return 0;
 }
 
+// diagnostic (not in the public header): the plan's list of overflowed pairs as it stands -- the device's count and its host mirror --
+// without emptying it (synchronises the device; asx_plan_set_exact would empty it)
+extern "C" int asx_plan_debug_over_list(asx_plan *p, uint32_t *dev_n, uint32_t *host_n)
+{
+    if (!p || !dev_n || !host_n) return -1;
+    DevGuard dg(p->device);
+    if (!dg.ok || hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpy(dev_n, p->over_n, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    *host_n = *p->h_over_n;
+    return 0;
+}
+
 extern "C" size_t asx_plan_peak_capacity(const asx_plan *p) { return p ? p->lanes[0].pk.cap : 0; }
 
 // The window is plain host state under the plan's lock, read by run_group when it launches: no allocation, no synchronisation.
@@ -655,12 +670,24 @@ template <typename TIn> struct Pairs {
     }
 };
 
-// Where pair k's results go (lag and ret may be null).
+// Where pair k's results go (lag and ret may be null): entries step apart (asx_xcorr_topk_f32_dev: step = k, entry j of pair i at
+// i * k + j; every other entry point: 1).
 struct Results {
     int64_t *lag;
     double *coef;
     int32_t *ret;
-    Results at(size_t k) const { return { lag ? lag + k : nullptr, coef + k, ret ? ret + k : nullptr }; }
+    size_t step = 1;
+    Results at(size_t k) const
+    {
+        return { lag ? lag + k * step : nullptr, coef + k * step, ret ? ret + k * step : nullptr, step };
+    }
+};
+
+// The top-k option of a call (asx_xcorr_topk_f32_dev): k passes over each group's Q, min_separation between the entries' lags.
+// k = 1 is the strided / windowed call itself.
+struct Topk {
+    int k = 1;
+    int64_t sep = 0;
 };
 
 struct GroupOpts {
@@ -679,6 +706,7 @@ struct GroupOpts {
     float *r_out = nullptr;      // r of every lag (asx_xcorr_debug_r_dev)
     int dot_blocks = 0;          // blocks per pair of the exact re-evaluation; 0: by the group size
     const AsxPeakWs *pk = nullptr; // the peak workspace instead of the lane's (the second look's lists for every lag)
+    Topk topk{};                 // k > 1: passes 2..k over the group's Q (y's entry stride is k)
 };
 
 // One group: g <= plan->group pairs, the first g of x, results to the first g of y.
@@ -730,6 +758,9 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     const bool windowed = !pr && (p->win_lo != -(int64_t)P.N || p->win_hi != (int64_t)P.N - 1);
     const AsxWin win = asx_win_of(p->win_lo, p->win_hi, P.N);
     const uint32_t seed = windowed ? win.seed : 0u;
+    // Top-k (o.topk.k > 1): every pass's results go to the lane's temporaries, and k_topk_step moves them to entry j of y
+    const int K = o.topk.k;
+    const Results out = K > 1 ? Results{ W.tk.lag, W.tk.coef, W.tk.ret } : y;
     asx_launch_inv_cols(P, q, tk, o.r_out, (int)g, s, windowed ? &win : nullptr, pr);
     if (mark(3)) return -1;
     asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, seed, pr);
@@ -741,12 +772,28 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral, seed, pr);
     if (mark(4)) return -1;
     if (!spectral)
-        asx_launch_pearson(x.tsrc, x.tsmp, x.src_step, x.smp_step, P.N, W.seg, W.psums, y.lag, y.coef, y.ret, (int)g, s);
+        asx_launch_pearson(x.tsrc, x.tsmp, x.src_step, x.smp_step, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
     else if constexpr (std::is_same<TIn, float>::value)
-        asx_launch_pearson_spectral_f32(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, tk, W.spec, W.seg, W.psums, y.lag, y.coef, y.ret,
-                                        (int)g, s, seed, pr);
-    // a pair whose row is not a window: (0, NaN, -2), the others untouched
-    if (pr) asx_launch_invalid_rows(rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
+        asx_launch_pearson_spectral_f32(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, tk, W.spec, W.seg, W.psums, out.lag, out.coef,
+                                        out.ret, (int)g, s, seed, pr);
+    // a pair whose row is not a window: (0, NaN, -2), the others untouched (top-k: k_topk_step writes it for every entry)
+    if (pr && K == 1) asx_launch_invalid_rows(rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
+    // Passes 2..k over the same Q: the inverse columns, finalize, exact re-evaluation and Pearson again, each pair's window minus the
+    // zones around its earlier entries (the records k_topk_step keeps); the transforms are not run again.
+    for (int j = 0; K > 1 && j < K; j++) {
+        if (j > 0) {
+            asx_launch_inv_cols(P, q, tk, nullptr, (int)g, s, nullptr, nullptr, W.tk.pairs, j); // (pass j + 1: at most j zones)
+            asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, 0, nullptr, W.tk.pairs, W.tk.sink);
+            asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral, 0, nullptr,
+                              W.tk.pairs);
+            if (!spectral)
+                asx_launch_pearson(x.tsrc, x.tsmp, x.src_step, x.smp_step, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
+            else if constexpr (std::is_same<TIn, float>::value)
+                asx_launch_pearson_spectral_f32(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, tk, W.spec, W.seg, W.psums, out.lag,
+                                                out.coef, out.ret, (int)g, s, 0, nullptr, W.tk.pairs);
+        }
+        asx_launch_topk_step(W.tk, W.seg, pk, p->win_lo, p->win_hi, pr, P.N, (int)g, j, K, o.topk.sep, y.lag, y.coef, y.ret, s);
+    }
     if (mark(5)) return -1;
     HIP_TRY(hipGetLastError());
     return 0;
@@ -770,7 +817,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
 // lane 0 and the plan's one set of big lists: nothing else is in flight on this plan (one stream at a time per plan).
 // x and y are the window the list's indices count from: the listed pair i is x.at(i), its results y.at(i).
 template <typename TIn>
-static int second_look(asx_plan *p, const Pairs<TIn> &x, const Results &y, size_t i, hipStream_t s)
+static int second_look(asx_plan *p, const Pairs<TIn> &x, const Results &y, size_t i, hipStream_t s, const Topk &topk)
 {
     const AsxDev &P = p->dev;
     const size_t N = p->host.N;
@@ -800,7 +847,7 @@ static int second_look(asx_plan *p, const Pairs<TIn> &x, const Results &y, size_
     asx_launch_dc_remove(xi.tsrc, xi.tsmp, P.N, (double)P.F, B.stats, B.src_dc, s);
     K.shift = B.stats + 2;
     if (run_group(p, Pairs<TIn>{ B.src_dc, xi.smp, xi.tsrc, xi.tsmp, 2 * N, N, 0, xi.win, xi.win_step }, 1, y.at(i), s,
-                  { .prof_group = GroupOpts::no_marks, .listed = false, .spectral = false, .dot_blocks = 2048, .pk = &K }))
+                  { .prof_group = GroupOpts::no_marks, .listed = false, .spectral = false, .dot_blocks = 2048, .pk = &K, .topk = topk }))
         return -1;
     p->repaired++;
     return 0;
@@ -810,7 +857,7 @@ static int second_look(asx_plan *p, const Pairs<TIn> &x, const Results &y, size_
 // on `s` (its result copies included): ONE synchronisation; the count is read from the page-locked mirror k_finalize adds to
 // only when a pair overflows -- no device-to-host copy sits between the last kernel and the host.
 template <typename TIn>
-static int resolve_overflows(asx_plan *p, const Pairs<TIn> &x, const Results &y, hipStream_t s)
+static int resolve_overflows(asx_plan *p, const Pairs<TIn> &x, const Results &y, hipStream_t s, const Topk &topk = {})
 {
     HIP_TRY(hipStreamSynchronize(s));
     if (p->lanes[0].pk.cap >= 2 * p->host.N) return 0; // the ordinary list already holds every lag
@@ -829,7 +876,7 @@ static int resolve_overflows(asx_plan *p, const Pairs<TIn> &x, const Results &y,
     HIP_TRY(hipStreamSynchronize(s));
     *p->h_over_n = 0;
     for (uint32_t k = 0; k < n; k++)
-        if (second_look(p, x, y, p->h_over[k], s)) return -1;
+        if (second_look(p, x, y, p->h_over[k], s, topk)) return -1;
     return (int)n;
 }
 
@@ -928,7 +975,7 @@ extern "C" int asx_plan_placement(asx_plan *p, double ms[2], int *kept)
 }
 
 // A device-resident batch of float32 pairs, after the entry point's own checks.
-static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Results &y, hipStream_t s)
+static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Results &y, hipStream_t s, const Topk &topk = {})
 {
     prof_begin_call(p);
     // chunking: groups of at most `group` pairs; with two lanes a batch is cut into at least two
@@ -951,7 +998,7 @@ static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Res
             const int lane = overlap ? (int)(gi & 1) : 0;
             hipStream_t ls = overlap ? p->lanes[lane].stream : s;
             if (run_group(p, x.at(done), g, y.at(done), ls,
-                          { .prof_group = gi, .lane = lane, .pair_base = (uint32_t)(done - w0), .listed = p->exact }))
+                          { .prof_group = gi, .lane = lane, .pair_base = (uint32_t)(done - w0), .listed = p->exact, .topk = topk }))
                 return -1;
         }
         if (overlap) {
@@ -961,7 +1008,7 @@ static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Res
             }
         }
         // the second look, behind the window's last group (one host synchronisation per window)
-        if (p->exact && resolve_overflows(p, x.at(w0), y.at(w0), s) < 0) return -1;
+        if (p->exact && resolve_overflows(p, x.at(w0), y.at(w0), s, topk) < 0) return -1;
     }
     prof_end_call(p, gi);
     return 0;
@@ -989,7 +1036,8 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
 // asx_xcorr_strided_f32_dev and asx_xcorr_windowed_f32_dev (fn: the entry point's name for the messages), after their own null checks.
 // d_windows: null, or the per-pair windows (Pairs::win), window_stride rows apart.
 static int strided_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
-                         size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, const Results &y, void *stream)
+                         size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, const Results &y, void *stream,
+                         const Topk &topk = {})
 {
     std::lock_guard<std::mutex> guard(p->lock);
     DevGuard dg(p->device);
@@ -1027,7 +1075,8 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
         if (!asx_launch_fwd_cols_r(P, d_source, 0, d_sample, 0, B.cx, B.cy, B.nrm, B.band, 1, op0, nops, true, s))
             return fail("internal: no forward column kernel for this plan");
     }
-    return run_batch(p, { d_source, d_sample, d_source, d_sample, source_stride, sample_stride, bc, d_windows, window_stride }, batch, y, s);
+    return run_batch(p, { d_source, d_sample, d_source, d_sample, source_stride, sample_stride, bc, d_windows, window_stride }, batch, y, s,
+                     topk);
 }
 
 extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
@@ -1048,6 +1097,19 @@ extern "C" int asx_xcorr_windowed_f32_dev(asx_plan *p, const float *d_source, si
     if (!p || !d_source || !d_sample || !d_windows || !d_coef || !d_ret) return fail("asx_xcorr_windowed_f32_dev: null argument");
     return strided_batch(p, "asx_xcorr_windowed_f32_dev", d_source, source_stride, d_sample, sample_stride, d_windows, window_stride,
                          batch, { d_lag, d_coef, d_ret }, stream);
+}
+
+// The K strongest separated lags per pair: the strided / windowed batch with passes 2..k over each group's Q (run_group).  k = 1
+// launches exactly what that call launches.
+extern "C" int asx_xcorr_topk_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                      size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, int k,
+                                      int64_t min_separation, int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream)
+{
+    if (!p || !d_source || !d_sample || !d_coef || !d_ret) return fail("asx_xcorr_topk_f32_dev: null argument");
+    if (k < 1 || k > ASX_TOPK_MAX) return fail("asx_xcorr_topk_f32_dev: k = %d is not in [1, %d]", k, ASX_TOPK_MAX);
+    if (min_separation < 0) return fail("asx_xcorr_topk_f32_dev: min_separation = %lld is negative", (long long)min_separation);
+    return strided_batch(p, "asx_xcorr_topk_f32_dev", d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch,
+                         { d_lag, d_coef, d_ret, (size_t)k }, stream, Topk{ k, min_separation });
 }
 
 extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const float *d_sample,

@@ -143,6 +143,66 @@ __device__ inline bool asx_win_row(const AsxWinRows &R, size_t pair, uint32_t N,
     return ok;
 }
 
+// Top-k peaks (asx_xcorr_topk_f32_dev): pass 1 is the strided / windowed call's peak search; pass j >= 2 searches the same Q again
+// with A_j = the call's window minus the zones |lag - lag_i| <= min_separation around the entries i < j (lags, not indices: -N and
+// N-1 are far apart).  k_topk_step (xcorr_kernels.hip) writes entry j and prepares pass j + 1 in the group's AsxTopkPair records; the
+// pass kernels (k_inv_cols_rx, k_inv_cols_wx, k_finalize_x, k_refine_pick_x, k_pearson_prep_x) read them.
+#define ASX_TOPK_MAX 8
+#define ASX_TK_EMPTY 1u   // A_j is empty: this entry and every later one are (0, NaN, -3)
+#define ASX_TK_INVALID 2u // the pair's row is not a window: every entry is (0, NaN, -2)
+#define ASX_TK_INEXACT 4u // a pass of this call overflowed its near-tie list: counted and listed once; ret = 1 from that entry on
+struct AsxTopkPair {
+    AsxWin z;                     // the next pass's window: the call's, with seed = the smallest index of A_j (n = 0: nothing competes)
+    int32_t lo[ASX_TOPK_MAX - 1]; // zone i: lags lo[i] .. lo[i] + wd[i] (an earlier entry +- min_separation, clipped to [-N, N-1])
+    uint32_t wd[ASX_TOPK_MAX - 1];
+    uint32_t nz;                  // zones so far
+    uint32_t flags;               // ASX_TK_*
+    int32_t wlo, whi;             // the call's window in lags
+};
+// What the top-k inverse kernels hand their body as Z: an AsxWin whose asx_win_has also leaves out the zones.  The bodies only ask
+// Z.seed and asx_win_has(Z, idx), so they compile unchanged against it.  An in-window index at distance d from a is the lag
+// wlo + d, so zone i is the distances zo[i] .. zo[i] + wd[i] (zo[i] = lo[i] - wlo, wrapping): two operations per zone and index,
+// for ZC zones -- the kernel's capacity, chosen per pass by the launcher (1, 3 or 7); the unused ones are (~0, 0), which hold
+// no distance (d - ~0 = d + 1 > 0).  (Testing only the first nz zones under a run-time guard kept the lane masks in VGPRs and
+// spilled k_inv_cols_rx to scratch.)
+template <int ZC> struct AsxWinX {
+    uint32_t a, w, seed, n;
+    uint32_t zo[ZC];
+    uint32_t wd[ZC];
+};
+template <int ZC> __host__ __device__ inline bool asx_win_has(const AsxWinX<ZC> &z, uint32_t idx)
+{
+    if (idx >= z.n) return false;
+    const uint32_t d = idx >= z.a ? idx - z.a : idx + (z.n - z.a);
+    bool in = d <= z.w;
+#pragma unroll
+    for (int i = 0; i < ZC; i++) in = in && d - z.zo[i] > z.wd[i];
+    return in;
+}
+template <int ZC> __host__ __device__ inline AsxWinX<ZC> asx_win_x(const AsxTopkPair *X, size_t pair)
+{
+    const AsxTopkPair &t = X[pair];
+    AsxWinX<ZC> z;
+    z.a = t.z.a; z.w = t.z.w; z.seed = t.z.seed; z.n = t.z.n;
+#pragma unroll
+    for (int i = 0; i < ZC; i++) {
+        const bool used = (uint32_t)i < t.nz;
+        z.zo[i] = used ? (uint32_t)(t.lo[i] - t.wlo) : ~0u;
+        z.wd[i] = used ? t.wd[i] : 0u;
+    }
+    return z;
+}
+// the zone capacity of the inverse kernel of a pass with nz zones
+inline int asx_tk_zone_cap(int nz) { return nz <= 1 ? 1 : nz <= 3 ? 3 : ASX_TOPK_MAX - 1; }
+// per-lane top-k workspace: the records and pass j's results, which k_topk_step moves to entry j of the caller's arrays
+struct AsxTopkWs {
+    AsxTopkPair *pairs;          // [pairs]
+    int64_t *lag;                // [pairs]
+    double *coef;                // [pairs]
+    int32_t *ret;                // [pairs]
+    unsigned long long *sink;    // [1] where k_finalize_x counts the later overflows of a pair already counted in this call
+};
+
 // kernel launchers (defined in xcorr_kernels.hip, called from asx_api.hip)
 struct AsxCand {          // one near-maximum lag found by a column tile
     uint32_t idx;
@@ -203,9 +263,11 @@ void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, fl
                          float2 *zya, const AsxPeakWs &W, int npairs, hipStream_t s);
 void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga,
                      const AsxPeakWs &W, int npairs, hipStream_t s);
-// rows (per-pair windows) takes precedence over win (the plan's)
+// tk (a top-k pass >= 2: each pair's window and zones from its record) takes precedence over rows (per-pair windows), rows over
+// win (the plan's)
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out,
-                         int npairs, hipStream_t s, const AsxWin *win = nullptr, const AsxWinRows *rows = nullptr);
+                         int npairs, hipStream_t s, const AsxWin *win = nullptr, const AsxWinRows *rows = nullptr,
+                         const AsxTopkPair *tk = nullptr, int tk_zones = 0);
 // rlayout.hip: the real-column decomposition (production lengths); false = no kernel compiled in for this plan.
 // bc (the broadcast forms of asx_xcorr_strided_f32_dev): bit 0 = cx is the plan's broadcast slot (one C for every pair), bit 1 = cy is
 bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
@@ -213,16 +275,24 @@ bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, floa
 bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
                            float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s);
 // win: null = every lag competes (k_inv_cols_r); else the lag-window form (k_inv_cols_rw); rows: the per-pair form (k_inv_cols_rp)
+// tk: the top-k form (k_inv_cols_rx), for a pass whose records hold at most tk_zones zones
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
-                           const AsxWin *win = nullptr, const AsxWinRows *rows = nullptr);
+                           const AsxWin *win = nullptr, const AsxWinRows *rows = nullptr, const AsxTopkPair *tk = nullptr,
+                           int tk_zones = 0);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 bool asx_rlayout_available(const AsxDev &P); // all three kernels compiled in for this plan's schedules
 int asx_rlayout_band_rows(const AsxDev &P);
 // seed (the lag window's, AsxWin): the index an empty running maximum stands for, and the one whose exact value competes signed;
 // rows (per-pair windows): each pair's own seed, from its row (k_finalize_p, k_refine_pick_p, k_pearson_prep_p)
+// tk (a top-k pass >= 2): each pair's seed from its record (k_finalize_x, k_refine_pick_x, k_pearson_prep_x); tk_sink: see AsxTopkWs
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base = 0,
-                         uint32_t seed = 0, const AsxWinRows *rows = nullptr);
+                         uint32_t seed = 0, const AsxWinRows *rows = nullptr, const AsxTopkPair *tk = nullptr,
+                         unsigned long long *tk_sink = nullptr);
+// behind the Pearson kernels of pass j of a top-k group: entry j of the caller's arrays (entry stride k) from the pass's results,
+// then pass j + 1's records (win_lo / win_hi: the plan's window, used when rows is null)
+void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, int64_t win_lo, int64_t win_hi, const AsxWinRows *rows,
+                          uint32_t N, int npairs, int j, int k, int64_t sep, int64_t *lag, double *coef, int32_t *ret, hipStream_t s);
 // behind the Pearson kernels of a group with per-pair windows: (lag, coef, ret) = (0, NaN, -2) for every pair whose row is invalid
 void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 // The exact passes over float or double inputs (instances for both next to the kernels, xcorr_kernels.hip).  The pairs' inputs
@@ -231,7 +301,7 @@ void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, d
 template <typename TIn>
 void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
                        AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed = 0,
-                       const AsxWinRows *rows = nullptr);
+                       const AsxWinRows *rows = nullptr, const AsxTopkPair *tk = nullptr);
 template <typename TIn>
 void asx_launch_pearson(const TIn *src, const TIn *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len, const AsxSeg *seg,
                         double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
@@ -242,7 +312,8 @@ void asx_launch_pearson_partial_spec_f32(const float *src, const float *smp, siz
 // group's transform kernels)
 void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
                                      const AsxPeakWs &W, const AsxSpecWs &S, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
-                                     int32_t *ret, int npairs, hipStream_t s, uint32_t seed = 0, const AsxWinRows *rows = nullptr);
+                                     int32_t *ret, int npairs, hipStream_t s, uint32_t seed = 0, const AsxWinRows *rows = nullptr,
+                                     const AsxTopkPair *tk = nullptr);
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
                               double min_confidence, double sample_rate, int64_t *lag_ms, int32_t *accept,
                               hipStream_t s);

@@ -159,6 +159,17 @@ template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep
 #include "pearson_prep_body.h"
 }
 
+// the top-k form (asx_xcorr_topk_f32_dev, passes 2..k): the seed is the pass's, from the pair's record.  An empty A_j has no maximum,
+// so the pair takes the direct reduction (counted as ASX_PM_DIRECT) before k_topk_step writes (0, NaN, -3) for it.
+template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep_x(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
+                                                                      const float *__restrict__ smp, size_t src_pitch, size_t smp_pitch,
+                                                                      AsxPeakWs W, AsxSpecWs S, AsxSeg *__restrict__ seg,
+                                                                      const AsxTopkPair *__restrict__ X)
+{
+    const uint32_t seed = X[blockIdx.y].z.seed;
+#include "pearson_prep_body.h"
+}
+
 // grid (npairs), one wave per pair: k_pearson_final (xcorr_kernels.hip) with the two spectral modes in front of it.
 __global__ __launch_bounds__(64) void k_pearson_final_spec(const AsxSeg *__restrict__ seg, const double *__restrict__ psums, uint32_t nb,
                                                             AsxSpecWs S, int64_t *__restrict__ lag,
@@ -200,11 +211,20 @@ __global__ __launch_bounds__(64) void k_pearson_final_spec(const AsxSeg *__restr
 
 void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
                                      const AsxPeakWs &W, const AsxSpecWs &S0, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
-                                     int32_t *ret, int npairs, hipStream_t s, uint32_t seed, const AsxWinRows *rows)
+                                     int32_t *ret, int npairs, hipStream_t s, uint32_t seed, const AsxWinRows *rows,
+                                     const AsxTopkPair *tk)
 {
     AsxSpecWs S = S0;
     S.N = P.N;
-    if (rows) {
+    if (tk) {
+        S.nb = (size_t)P.band_rows * (size_t)P.M2 >= 16384 ? ASX_PREP_BLOCKS : 1;
+        if (S.nb > 1)
+            hipLaunchKernelGGL((k_pearson_prep_x<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0,
+                               s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg, tk);
+        else
+            hipLaunchKernelGGL((k_pearson_prep_x<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S,
+                               seg, tk);
+    } else if (rows) {
         S.nb = (size_t)P.band_rows * (size_t)P.M2 >= 16384 ? ASX_PREP_BLOCKS : 1;
         if (S.nb > 1)
             hipLaunchKernelGGL((k_pearson_prep_p<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0,

@@ -721,6 +721,20 @@ __global__ __launch_bounds__(NT, 4) void k_inv_cols_rp(const RArgs P, const floa
 #include "inv_cols_r_body.h"
 }
 
+// the top-k form (asx_xcorr_topk_f32_dev, passes 2..k): the pass's window, seed and the zones around the pair's earlier entries, from
+// its record (AsxTopkPair, written by k_topk_step); asx_win_has(AsxWinX) leaves the zones out of every scan, candidate list and tile
+// peak of the pass
+// ZC: the zones the kernel tests (asx_tk_zone_cap)
+template <class S1, int TC, int NT, int ZC>
+__global__ __launch_bounds__(NT, 4) void k_inv_cols_rx(const RArgs P, const float2 *__restrict__ qi, size_t pair_pitch,
+                                                        AsxPeakWs W, float *__restrict__ r_out, unsigned first_gen,
+                                                        const AsxTopkPair *__restrict__ X)
+{
+    constexpr bool WIN = true;
+    const AsxWinX<ZC> Z = asx_win_x<ZC>(X, blockIdx.x);
+#include "inv_cols_r_body.h"
+}
+
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
@@ -833,14 +847,29 @@ void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sban
 }
 
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
-                           const AsxWin *win, const AsxWinRows *rows)
+                           const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk, int tk_zones)
 {
     if (!P.col_pairs) return false;
     const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2;
+#define ASX_RX(zc, m1, t, nt, ...)                                                                                          \
+    {                                                                                                                       \
+        const void *fx = (const void *)k_inv_cols_rx<Sched<m1, __VA_ARGS__>, t, nt, zc>;                                    \
+        allow_big_lds_r(fx, lds);                                                                                           \
+        hipLaunchKernelGGL((k_inv_cols_rx<Sched<m1, __VA_ARGS__>, t, nt, zc>), grid, dim3(nt), lds, s, rargs_of(P), q, pitch, W, \
+                           r_out, resident_blocks(fx, nt, lds), tk);                                                        \
+    }
 #define ASX_TRY(m1, t, nt, ...)                                                                                             \
     if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                               \
         const size_t lds = (size_t)(m1) * (t) * sizeof(float2);                                                             \
         const dim3 grid(npairs, rcol_grid_x(P.M2 / (t), asx_ilog2(t)));                                                     \
+        if (tk) {                                                                                                           \
+            switch (asx_tk_zone_cap(tk_zones)) {                                                                            \
+            case 1: ASX_RX(1, m1, t, nt, __VA_ARGS__) break;                                                                \
+            case 3: ASX_RX(3, m1, t, nt, __VA_ARGS__) break;                                                                \
+            default: ASX_RX(ASX_TOPK_MAX - 1, m1, t, nt, __VA_ARGS__) break;                                                \
+            }                                                                                                               \
+            return true;                                                                                                    \
+        }                                                                                                                   \
         if (rows) {                                                                                                         \
             const void *fp = (const void *)k_inv_cols_rp<Sched<m1, __VA_ARGS__>, t, nt>;                                    \
             allow_big_lds_r(fp, lds);                                                                                       \
@@ -863,6 +892,7 @@ bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W,
     }
     ASX_RCOLS(ASX_TRY)
 #undef ASX_TRY
+#undef ASX_RX
     return false;
 }
 

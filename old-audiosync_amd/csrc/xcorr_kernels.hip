@@ -568,6 +568,18 @@ __global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols_wp(const As
 #include "inv_cols_body.h"
 }
 
+// the top-k form (asx_xcorr_topk_f32_dev, passes 2..k): the pass's window, seed and the zones around the pair's earlier entries, from
+// its record (AsxTopkPair, written by k_topk_step); asx_win_has(AsxWinX) leaves the zones out
+template <int MAXR, class S1 = void, int TC = 0, int NT = 0>
+__global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols_wx(const AsxDev *__restrict__ Pp, const float2 *__restrict__ ga,
+                                                                      AsxPeakWs W, float *__restrict__ r_out,
+                                                                      const AsxTopkPair *__restrict__ X)
+{
+    constexpr bool WIN = true;
+    const AsxWinX<ASX_TOPK_MAX - 1> Z = asx_win_x<ASX_TOPK_MAX - 1>(X, blockIdx.y); // (one zone capacity: the packed kernels are off the hot path)
+#include "inv_cols_body.h"
+}
+
 #if ASX_HAS_PART(64)
 // ---------------------------------------------------------------------------
 // k_finalize: grid (npairs).  Reduce tile partials, wrap the lag, pick segments.
@@ -588,6 +600,115 @@ __global__ __launch_bounds__(ASX_THREADS) void k_finalize_p(const AsxDev *__rest
     (void)asx_win_row(R, blockIdx.x, Pp->N, Z);
     const uint32_t seed = Z.seed;
 #include "finalize_body.h"
+}
+
+// the top-k form (passes 2..k): the seed is the pass's, from the pair's record.  A pair that already overflowed in an earlier pass of
+// the call was counted and listed then: its later overflows go to a sink (asx_plan_peak_overflows counts a pair once per call)
+__global__ __launch_bounds__(ASX_THREADS) void k_finalize_x(const AsxDev *__restrict__ Pp, AsxPeakWs W0, AsxSeg *__restrict__ seg,
+                                                             uint32_t pair_base, const AsxTopkPair *__restrict__ X,
+                                                             unsigned long long *__restrict__ sink)
+{
+    const uint32_t seed = X[blockIdx.x].z.seed;
+    AsxPeakWs W = W0;
+    if (X[blockIdx.x].flags & ASX_TK_INEXACT) {
+        W.overflows = sink;
+        W.over_list = nullptr;
+    }
+#include "finalize_body.h"
+}
+
+// grid (npairs / ASX_THREADS): behind the Pearson kernels of pass j of a top-k group (asx_xcorr_topk_f32_dev).  Pass j's result of
+// each pair (in the group's temporaries) becomes entry j of the caller's arrays (index pair * k + j): (0, NaN, -2) for an invalid
+// row, (0, NaN, -3) once A_j is empty, ret = 1 from an overflowed pass on.  Then, unless j is the last pass, the zone around the
+// entry's lag joins the pair's record, the next pass's seed is the smallest index left in the window (none: the record is marked
+// empty and its window holds nothing), and the per-pair state of the peak search that k_rows zeroes is zeroed again.  j = 0 starts
+// the record from the call's window: the plan's (win_lo, win_hi) or the pair's row.
+__device__ inline int64_t tk_first_free(const AsxTopkPair *__restrict__ t, uint32_t nz, int64_t l, int64_t end)
+{
+    // the smallest lag >= l and <= end outside the record's first nz zones (end + 1: none); a zone once passed is never met again
+    for (int it = 0; it < ASX_TOPK_MAX; it++) {
+        bool moved = false;
+        for (uint32_t i = 0; i < nz; i++) {
+            const int64_t lo = t->lo[i], hi = lo + (int64_t)t->wd[i];
+            if (lo <= l && l <= hi) { l = hi + 1; moved = true; }
+        }
+        if (!moved || l > end) break;
+    }
+    return l <= end ? l : end + 1;
+}
+
+__global__ __launch_bounds__(ASX_THREADS) void k_topk_step(AsxTopkWs T, const AsxSeg *__restrict__ seg, AsxPeakWs W, int64_t win_lo,
+                                                            int64_t win_hi, AsxWinRows R, uint32_t N, int npairs, int j, int k,
+                                                            int64_t sep, int64_t *__restrict__ lag, double *__restrict__ coef,
+                                                            int32_t *__restrict__ ret)
+{
+    const int pair = blockIdx.x * ASX_THREADS + threadIdx.x;
+    if (pair >= npairs) return;
+    const int64_t n = (int64_t)N;
+    AsxTopkPair *t = T.pairs + pair; // (fields one by one: a whole record in registers, indexed by nz, went to scratch)
+    uint32_t flags, nz;
+    if (j == 0) {
+        int64_t lo = win_lo, hi = win_hi;
+        AsxWin z;
+        flags = 0;
+        if (R.rows) {
+            const int64_t *row = R.rows + 2 * (size_t)pair * R.step;
+            lo = row[0];
+            hi = row[1];
+            if (!asx_win_row(R, (size_t)pair, N, z)) flags = ASX_TK_INVALID;
+        } else {
+            z = asx_win_of(lo, hi, N);
+        }
+        t->z = z;
+        t->wlo = (int32_t)lo;
+        t->whi = (int32_t)hi;
+        nz = 0;
+    } else {
+        flags = t->flags;
+        nz = t->nz;
+    }
+    const AsxSeg sg = seg[pair];
+    if (sg.flags & ASX_SEG_INEXACT) flags |= ASX_TK_INEXACT;
+    int64_t l = T.lag[pair];
+    double c = T.coef[pair];
+    int32_t r = T.ret[pair];
+    if (flags & ASX_TK_INVALID) { l = 0; c = (double)NAN; r = -2; }
+    else if (flags & ASX_TK_EMPTY) { l = 0; c = (double)NAN; r = -3; }
+    if ((flags & ASX_TK_INEXACT) && !(flags & ASX_TK_INVALID)) r = 1; // (the zones of the entries from here on came from a float32 argmax)
+    const size_t e = (size_t)pair * (size_t)k + (size_t)j;
+    if (lag) lag[e] = l;
+    coef[e] = c;
+    ret[e] = r;
+    if (j + 1 >= k) return;
+    if (!(flags & (ASX_TK_INVALID | ASX_TK_EMPTY))) {
+        const int64_t d = sep < 2 * n ? sep : 2 * n;
+        const int64_t zlo = sg.lag - d < -n ? -n : sg.lag - d, zhi = sg.lag + d > n - 1 ? n - 1 : sg.lag + d;
+        t->lo[nz] = (int32_t)zlo;
+        t->wd[nz] = (uint32_t)(zhi - zlo);
+        nz++;
+        // ascending index order: the lags max(lo, 0) .. hi, then lo .. min(hi, -1)
+        const int64_t lo = t->wlo, hi = t->whi;
+        int64_t seed = -1;
+        if (hi >= 0) {
+            const int64_t f = tk_first_free(t, nz, lo > 0 ? lo : 0, hi);
+            if (f <= hi) seed = f;
+        }
+        if (seed < 0 && lo < 0) {
+            const int64_t e1 = hi < -1 ? hi : -1, f = tk_first_free(t, nz, lo, e1);
+            if (f <= e1) seed = 2 * n + f;
+        }
+        if (seed < 0) {
+            flags |= ASX_TK_EMPTY;
+            t->z.n = 0; // nothing competes: the running maximum stays empty and stands for index 0
+            t->z.seed = 0;
+        } else {
+            t->z.seed = (uint32_t)seed;
+        }
+    }
+    t->nz = nz;
+    t->flags = flags;
+    W.pairmax[pair] = 0;
+    W.cand_n[pair] = 0;
 }
 
 // grid (npairs / ASX_THREADS): behind k_pearson_final / k_pearson_final_spec of a group with per-pair windows, the pairs whose row is
@@ -695,6 +816,14 @@ __global__ __launch_bounds__(ASX_THREADS) void k_refine_pick_p(const AsxDev *__r
     AsxWin Z;
     (void)asx_win_row(R, blockIdx.x, Pp->N, Z);
     const uint32_t seed = Z.seed;
+#include "refine_pick_body.h"
+}
+
+// the top-k form (passes 2..k): the seed is the pass's, from the pair's record
+__global__ __launch_bounds__(ASX_THREADS) void k_refine_pick_x(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
+                                                                const AsxTopkPair *__restrict__ X)
+{
+    const uint32_t seed = X[blockIdx.x].z.seed;
 #include "refine_pick_body.h"
 }
 
@@ -1047,9 +1176,9 @@ bool asx_launch_rows_static(const AsxDev &P, const float2 *zxa, const float2 *zy
 void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga, const AsxPeakWs &W,
                              int npairs, hipStream_t s);
 bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                hipStream_t s, const AsxWin *win, const AsxWinRows *rows);
+                                hipStream_t s, const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk);
 void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                 hipStream_t s, const AsxWin *win, const AsxWinRows *rows);
+                                 hipStream_t s, const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk);
 
 #define ASX_FWD_LAUNCH(...) \
     do { allow_big_lds((const void *)k_fwd_cols<__VA_ARGS__>, lds_bytes_cols(P)); \
@@ -1112,7 +1241,10 @@ void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *z
 #undef ASX_ROWS_LAUNCH
 
 #define ASX_INV_LAUNCH(...) \
-    do { if (rows) { allow_big_lds((const void *)k_inv_cols_wp<__VA_ARGS__>, lds_bytes_cols(P)); \
+    do { if (tk) { allow_big_lds((const void *)k_inv_cols_wx<__VA_ARGS__>, lds_bytes_cols(P)); \
+                   hipLaunchKernelGGL((k_inv_cols_wx<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, tk); \
+                   break; } \
+         if (rows) { allow_big_lds((const void *)k_inv_cols_wp<__VA_ARGS__>, lds_bytes_cols(P)); \
                      hipLaunchKernelGGL((k_inv_cols_wp<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, *rows); \
                      break; } \
          if (win) { allow_big_lds((const void *)k_inv_cols_w<__VA_ARGS__>, lds_bytes_cols(P)); \
@@ -1122,7 +1254,7 @@ void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *z
          hipLaunchKernelGGL((k_inv_cols<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out); } while (0)
 #if ASX_HAS_PART(16)
 bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                hipStream_t s, const AsxWin *win, const AsxWinRows *rows)
+                                hipStream_t s, const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk)
 {
     dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
 #define ASX_TRY_STATIC(m1, t, nt, maxr, ...) \
@@ -1134,7 +1266,7 @@ bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeak
 #endif
 #if ASX_HAS_PART(32)
 void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                 hipStream_t s, const AsxWin *win, const AsxWinRows *rows)
+                                 hipStream_t s, const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk)
 {
     dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
     const int mr = max_radix(P.st1);
@@ -1198,18 +1330,26 @@ void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, floa
 }
 
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                         hipStream_t s, const AsxWin *win, const AsxWinRows *rows)
+                         hipStream_t s, const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk, int tk_zones)
 {
-    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s, win, rows)) return;
-    if (generic_only() || !asx_launch_inv_cols_static(P, ga, W, r_out, npairs, s, win, rows))
-        asx_launch_inv_cols_generic(P, ga, W, r_out, npairs, s, win, rows);
+    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s, win, rows, tk, tk_zones)) return;
+    if (generic_only() || !asx_launch_inv_cols_static(P, ga, W, r_out, npairs, s, win, rows, tk))
+        asx_launch_inv_cols_generic(P, ga, W, r_out, npairs, s, win, rows, tk);
 }
 
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,
-                         uint32_t seed, const AsxWinRows *rows)
+                         uint32_t seed, const AsxWinRows *rows, const AsxTopkPair *tk, unsigned long long *tk_sink)
 {
-    if (rows) hipLaunchKernelGGL(k_finalize_p, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, *rows);
+    if (tk) hipLaunchKernelGGL(k_finalize_x, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, tk, tk_sink);
+    else if (rows) hipLaunchKernelGGL(k_finalize_p, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, *rows);
     else hipLaunchKernelGGL(k_finalize, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, seed);
+}
+
+void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, int64_t win_lo, int64_t win_hi, const AsxWinRows *rows,
+                          uint32_t N, int npairs, int j, int k, int64_t sep, int64_t *lag, double *coef, int32_t *ret, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_topk_step, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, T, seg, W, win_lo, win_hi,
+                       rows ? *rows : AsxWinRows{ nullptr, 0 }, N, npairs, j, k, sep, lag, coef, ret);
 }
 
 void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
@@ -1220,10 +1360,12 @@ void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, d
 
 template <typename TIn>
 void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
-                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed, const AsxWinRows *rows)
+                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed, const AsxWinRows *rows,
+                       const AsxTopkPair *tk)
 {
     hipLaunchKernelGGL(k_refine_dots<TIn>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
-    if (pick && rows) hipLaunchKernelGGL(k_refine_pick_p, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, *rows);
+    if (pick && tk) hipLaunchKernelGGL(k_refine_pick_x, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, tk);
+    else if (pick && rows) hipLaunchKernelGGL(k_refine_pick_p, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, *rows);
     else if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, seed);
 }
 
@@ -1289,7 +1431,7 @@ void asx_launch_dc_remove(const TIn *src, const TIn *smp, uint32_t N, double sca
 // the exact passes' instances (asx_internal.h): float32 and float64 inputs
 #define ASX_EXACT_PASSES(T)                                                                                                             \
     template void asx_launch_refine<T>(const AsxDev &, const T *, size_t, const T *, size_t, const AsxPeakWs &, AsxSeg *, int,           \
-                                       hipStream_t, int, bool, uint32_t, const AsxWinRows *);                                           \
+                                       hipStream_t, int, bool, uint32_t, const AsxWinRows *, const AsxTopkPair *);                      \
     template void asx_launch_pearson<T>(const T *, const T *, size_t, size_t, uint32_t, const AsxSeg *, double *, int64_t *, double *,   \
                                         int32_t *, int, hipStream_t);                                                                   \
     template void asx_launch_dc_remove<T>(const T *, const T *, uint32_t, double, double *, float *, hipStream_t);

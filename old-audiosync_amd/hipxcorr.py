@@ -27,8 +27,10 @@ ABI_SYMBOLS = [
     "asx_current_device", "asx_plan_timings_ms", "asx_xcorr_batch_multi", "asx_plan_layout", "asx_plan_narrowed_calls",
     "asx_plan_set_pearson", "asx_plan_pearson_modes", "asx_plan_placement", "asx_host_malloc", "asx_host_free", "asx_shard_range", "asx_result_bytes", "asx_comm_create", "asx_comm_destroy", "asx_xcorr_batch_multi_dev",
     "asx_xcorr_strided_f32_dev", "asx_plan_set_lag_window", "asx_plan_lag_window", "asx_stream_set_lag_window",
-    "asx_xcorr_windowed_f32_dev",
+    "asx_xcorr_windowed_f32_dev", "asx_xcorr_topk_f32_dev",
 ]
+
+TOPK_MAX = 8  # ASX_TOPK_MAX, include/audiosync/xcorr_hip.h
 
 
 class AsxError(RuntimeError):
@@ -112,6 +114,9 @@ def lib():
     L.asx_xcorr_windowed_f32_dev.restype = ctypes.c_int
     L.asx_xcorr_windowed_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
                                              vp, vp, vp, vp]
+    L.asx_xcorr_topk_f32_dev.restype = ctypes.c_int
+    L.asx_xcorr_topk_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
+                                         ctypes.c_int, ctypes.c_int64, vp, vp, vp, vp]
     L.asx_shard_range.restype = ctypes.c_int
     L.asx_shard_range.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t),
                                   ctypes.POINTER(ctypes.c_size_t)]
@@ -306,6 +311,21 @@ def windowed_args(n, source, sample, windows):
     if batch < 1:
         raise ValueError("empty batch")
     return s, t, w, batch, 2 * n if s.ndim == 2 else 0, n if t.ndim == 2 else 0, 1 if w.ndim == 2 else 0
+
+
+def topk_args(n, source, sample, k, min_separation, windows=None):
+    """Host checks of Plan.xcorr_topk_f32: the shapes of windowed_args (windows=None: the plan's window, no rows), 1 <= k <= TOPK_MAX
+    and min_separation >= 0, integers.  -> (source, sample, windows or None, batch, source_stride, sample_stride, window_stride, k,
+    min_separation).  ValueError on anything else."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= TOPK_MAX:
+        raise ValueError("k must be an integer in [1, %d], not %r" % (TOPK_MAX, k))
+    if isinstance(min_separation, bool) or not isinstance(min_separation, (int, np.integer)) or int(min_separation) < 0:
+        raise ValueError("min_separation must be an integer >= 0, not %r" % (min_separation,))
+    if windows is None:
+        s, t, _, batch, ss, ts, _ = windowed_args(n, source, sample, np.zeros(2, dtype=np.int64))
+        return s, t, None, batch, ss, ts, 0, int(k), int(min_separation)
+    s, t, w, batch, ss, ts, ws = windowed_args(n, source, sample, windows)
+    return s, t, w, batch, ss, ts, ws, int(k), int(min_separation)
 
 
 def position_rows(n, hop, batch, p_lo, p_hi):
@@ -602,9 +622,27 @@ class Plan:
         if rc != 0:
             raise AsxError(_err())
 
-    def _strided_host(self, src, src_stride, smp, smp_stride, batch, windows=None, window_stride=0):
-        """host float32 buffers (and int64 windows) -> device copies -> asx_xcorr_strided_f32_dev (asx_xcorr_windowed_f32_dev)
-        -> (lag, coef, ret)"""
+    def xcorr_topk_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, k, min_separation, d_lag, d_coef,
+                       d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_topk_f32_dev -- the k strongest lags of pair i at least min_separation apart, entry j
+        at index i*k + j of d_lag / d_coef / d_ret; d_windows = 0: the plan's window applies; asynchronous on `stream`"""
+        rc = lib().asx_xcorr_topk_f32_dev(self._h, d_src, int(src_stride), d_smp, int(smp_stride), d_windows or None,
+                                          int(window_stride), int(batch), int(k), int(min_separation), d_lag or None, d_coef,
+                                          d_ret or None, stream or None)
+        if rc != 0:
+            raise AsxError(_err())
+
+    def xcorr_topk_f32(self, source, sample, k, min_separation, windows=None):
+        """The k strongest separated lags per pair (asx_xcorr_topk_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N];
+        windows: None (the plan's window), or integers [2] / [B, 2] as in xcorr_windowed_f32.  Entry j is the largest |r| among the
+        window's lags farther than min_separation from entries 0..j-1.  Arguments are checked on the host (ValueError) before
+        anything is uploaded.  Returns (lag int64 [B, k], coef float64 [B, k], ret int32 [B, k]); ret = -3 where no lag was left."""
+        s, t, w, batch, ss, ts, ws, k, sep = topk_args(self.sample_len, source, sample, k, min_separation, windows)
+        return self._strided_host(s, ss, t, ts, batch, w, ws, topk=(k, sep))
+
+    def _strided_host(self, src, src_stride, smp, smp_stride, batch, windows=None, window_stride=0, topk=None):
+        """host float32 buffers (and int64 windows) -> device copies -> asx_xcorr_strided_f32_dev (asx_xcorr_windowed_f32_dev;
+        topk = (k, min_separation): asx_xcorr_topk_f32_dev, results [batch, k]) -> (lag, coef, ret)"""
         L = lib()
         bufs = []
         try:
@@ -615,21 +653,26 @@ class Plan:
                 bufs.append(ptr)
                 return ptr
             d_src, d_smp = dev(src.nbytes), dev(smp.nbytes)
-            d_lag, d_coef, d_ret = dev(8 * batch), dev(8 * batch), dev(4 * batch)
+            shape = (batch,) if topk is None else (batch, topk[0])
+            entries = batch if topk is None else batch * topk[0]
+            d_lag, d_coef, d_ret = dev(8 * entries), dev(8 * entries), dev(4 * entries)
             ups = [(d_src, src), (d_smp, smp)]
             if windows is not None:
                 ups.append((dev(windows.nbytes), windows))
             for d, h in ups:
                 if L.asx_memcpy_h2d(d, h.ctypes.data, h.nbytes) != 0:
                     raise AsxError(_err())
-            if windows is None:
+            if topk is not None:
+                self.xcorr_topk_dev(d_src, src_stride, d_smp, smp_stride, ups[2][0] if windows is not None else 0, window_stride, batch,
+                                    topk[0], topk[1], d_lag, d_coef, d_ret)
+            elif windows is None:
                 self.xcorr_strided_dev(d_src, src_stride, d_smp, smp_stride, batch, d_lag, d_coef, d_ret)
             else:
                 self.xcorr_windowed_dev(d_src, src_stride, d_smp, smp_stride, ups[2][0], window_stride, batch, d_lag, d_coef, d_ret)
             self.sync()
-            lag = np.zeros(batch, dtype=np.int64)
-            coef = np.zeros(batch, dtype=np.float64)
-            ret = np.zeros(batch, dtype=np.int32)
+            lag = np.zeros(shape, dtype=np.int64)
+            coef = np.zeros(shape, dtype=np.float64)
+            ret = np.zeros(shape, dtype=np.int32)
             for h, d in ((lag, d_lag), (coef, d_coef), (ret, d_ret)):
                 if L.asx_memcpy_d2h(h.ctypes.data, d, h.nbytes) != 0:
                     raise AsxError(_err())
