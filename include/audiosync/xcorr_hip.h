@@ -32,6 +32,8 @@
  *   inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.
  *   ret = -3 (asx_xcorr_topk_f32_dev only): no lag is left for this entry of the pair (its
  *   window minus the zones around the earlier entries is empty); lag = 0 and coef = NaN.
+ *   ret = -4 (asx_xcorr_pool_f32_dev only): a pair's source or sample index is outside its
+ *   pool; lag = 0 and coef = NaN.  It takes precedence over -2.
  */
 #ifndef AUDIOSYNC_XCORR_HIP_H
 #define AUDIOSYNC_XCORR_HIP_H
@@ -278,6 +280,35 @@ int asx_xcorr_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_
                            const int64_t *d_windows, size_t window_stride,
                            size_t batch, int k, int64_t min_separation,
                            int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream);
+
+/* Many tracks against many: listed pairs of two track pools, every track transformed once per call.
+ * Source track a is d_sources + a*source_stride (2N floats), sample track b is d_samples + b*sample_stride
+ * (N floats); strides in floats.  The pools may overlap or alias (one pool of clips as both, for all-pairs),
+ * and a stride may be below the track length (windows of one recording).  Row i of d_pairs (int32, device
+ * memory, read when the kernels run) is pair i = {a_i, b_i}.  d_pairs == NULL: every combination,
+ * source-major -- pair i = (i / nsamples, i % nsamples) -- and batch must be nsources * nsamples.
+ * d_windows / window_stride: NULL (the plan's window), or per-pair rows exactly as asx_xcorr_windowed_f32_dev.
+ * Pair i's (lag, coef, ret) are bit for bit what asx_xcorr_strided_f32_dev returns for that pair alone on the
+ * same plan (with a row: asx_xcorr_windowed_f32_dev with that row), in both Pearson forms, exact and
+ * asynchronous (ret = 1) mode alike; the overflow and repair counters count each valid pair as that call
+ * would.  A row with an index outside its pool gives that pair (0, NaN, -4) and reads nothing outside the
+ * pools; the other pairs are untouched.
+ * Returns -1 with the outputs untouched when a pointer is NULL (the pools, d_coef, d_ret), a pool is empty
+ * while batch > 0, the plan is not a real-column plan (asx_plan_layout() != 1), the pools are not 16-byte
+ * aligned or a stride is not a multiple of 4 floats, or the bank cannot be allocated.  batch == 0 returns 0.
+ * One stream at a time per plan, as for the strided call.
+ * The bank: the plan keeps the forward column pass of every track of a call, (M1+1)*M2 complex floats per
+ * track plus its norm partials and band sums -- about 11.5 MB per track at N = 1 440 000, 1.15 MB at 144 000
+ * (8 bytes per frame of 2N, roughly).  It is allocated at the first pool call, grown (behind a device
+ * synchronisation) when a call names more tracks, and freed with the plan; it is not counted in
+ * asx_plan_workspace_bytes.  Growing it during a stream capture fails (-1): make a call with pools at least
+ * as large outside the capture first.  Top-k over pools is not offered. */
+int asx_xcorr_pool_f32_dev(asx_plan *plan,
+                           const float *d_sources, size_t source_stride, size_t nsources,
+                           const float *d_samples, size_t sample_stride, size_t nsamples,
+                           const int32_t *d_pairs,
+                           const int64_t *d_windows, size_t window_stride,
+                           size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream);
 
 /* The batched variant over several GPUs of one node from ONE process (BASELINE.json north_star; no
  * reference equivalent): plans[i] was created on device i (any devices; all the same sample_len); the

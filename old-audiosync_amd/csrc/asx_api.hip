@@ -109,6 +109,7 @@ struct asx_plan {
         double *psums = nullptr;
         AsxSpecWs spec{};      // spectral Pearson (pearson_spectral.hip): work list, window sums, mode counters
         AsxTopkWs tk{};        // top-k passes (asx_xcorr_topk_f32_dev): per-pair records and one pass's results
+        AsxPoolPair *pool = nullptr; // pool calls (asx_xcorr_pool_f32_dev): the group's pairs as slots and input offsets (k_pool_resolve)
     } lanes[2];
     int nlanes = 1;   // ASX_LANES=2 enables the second lane (measured: +0..4 %)
     hipEvent_t fork = nullptr;
@@ -131,6 +132,17 @@ struct asx_plan {
         float *nrm = nullptr;
         float2 *band = nullptr;
     } bslot;
+    // Bank of asx_xcorr_pool_f32_dev (real-column plans; allocated at the first pool call, grown when a call names more tracks): the
+    // forward column pass of every track of a call's two pools -- source a at row a of cx, sample b at row b of cy, their norm partials
+    // and band sums in the AsxPeakWs layout of "pair" a, operand 0, and "pair" b, operand 1 -- written once per call before the launch
+    // groups, read by slot (k_pool_resolve, k_rows_rl).  Its own allocations: not part of asx_plan_workspace_bytes.
+    struct Bank {
+        float2 *cx = nullptr, *cy = nullptr;
+        float *nrm = nullptr;
+        float2 *band = nullptr;
+        size_t nsrc = 0, nsmp = 0;      // capacity in tracks
+        unsigned long long fills = 0;   // pool calls that filled it (diagnostic: asx_plan_debug_bank)
+    } bank;
     // pairs whose near-tie list overflowed since the list was last emptied (k_finalize appends, resolve_overflows reads)
     uint32_t *over_list = nullptr, *over_n = nullptr;
     volatile uint32_t *h_over_n = nullptr; // page-locked host mirror of *over_n (device-visible: AsxPeakWs::over_host)
@@ -256,7 +268,7 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
             dev_alloc(p, &ln.pk.overflows, 1) ||
             dev_alloc(p, &ln.seg, g) || dev_alloc(p, &ln.psums, g * (size_t)asx_pearson_blocks((uint32_t)N) * 6) ||
             dev_alloc(p, &ln.tk.pairs, g) || dev_alloc(p, &ln.tk.lag, g) || dev_alloc(p, &ln.tk.coef, g) || dev_alloc(p, &ln.tk.ret, g) ||
-            dev_alloc(p, &ln.tk.sink, 1))
+            dev_alloc(p, &ln.tk.sink, 1) || dev_alloc(p, &ln.pool, g))
             return -1;
         HIP_TRY(hipMemset(ln.pk.overflows, 0, sizeof(unsigned long long)));
         ln.pk.band = nullptr; ln.pk.tile_peak = nullptr;
@@ -446,6 +458,8 @@ extern "C" void asx_plan_destroy(asx_plan *p)
     for (auto &ring : p->evr)
         for (hipEvent_t ev : ring) (void)hipEventDestroy(ev);
     for (void *a : p->allocs) (void)hipFree(a);
+    for (void *a : { (void *)p->bank.cx, (void *)p->bank.cy, (void *)p->bank.nrm, (void *)p->bank.band })
+        if (a) (void)hipFree(a);
     if (p->pin32) (void)hipHostFree(p->pin32);
     if (p->h_over_n) (void)hipHostFree((void *)p->h_over_n);
     (void)hipSetDevice(prev);
@@ -655,7 +669,13 @@ static int prof_mark(asx_plan *p, hipStream_t s, size_t slot)
 // caller's values when they are not float32, else the same buffers.  bc bit 0 / 1: the source / sample is the call's broadcast
 // track (asx_xcorr_strided_f32_dev, real-column plans), whose forward column pass is already in the plan's slot.  win: null, or the
 // per-pair lag windows of asx_xcorr_windowed_f32_dev -- pair k's row {lag_min, lag_max} is win + 2 k win_step (device memory) --
-// which then replace the plan's window for these pairs.
+// which then replace the plan's window for these pairs.  pool: a pool call (asx_xcorr_pool_f32_dev) -- src / smp are the two pools,
+// the steps their strides, and pair k is the call's pair first + k: {source a, sample b} from the caller's rows (or the implicit
+// product), resolved on the device per group (k_pool_resolve); at() moves first and the window rows, not the pools.
+struct PoolCall {
+    const int32_t *rows;   // [batch][2] {a, b}, device memory; null: pair i = (i / nsmp, i % nsmp)
+    size_t nsrc, nsmp;
+};
 template <typename TIn> struct Pairs {
     const float *src, *smp;
     const TIn *tsrc, *tsmp;
@@ -663,8 +683,11 @@ template <typename TIn> struct Pairs {
     int bc;
     const int64_t *win = nullptr;
     size_t win_step = 0;
+    const PoolCall *pool = nullptr;
+    size_t first = 0;
     Pairs at(size_t k) const
     {
+        if (pool) return { src, smp, tsrc, tsmp, src_step, smp_step, bc, win ? win + 2 * k * win_step : nullptr, win_step, pool, first + k };
         return { src + k * src_step, smp + k * smp_step, tsrc + k * src_step, tsmp + k * smp_step, src_step, smp_step, bc,
                  win ? win + 2 * k * win_step : nullptr, win_step };
     }
@@ -723,7 +746,13 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     AsxPeakWs tk = pk; // what the transform kernels see
     if (!spectral) { tk.band = nullptr; tk.tile_peak = nullptr; }
     if (mark(0)) return -1;
-    if (P.rlayout) {
+    // pool calls: the bank holds every track's forward column pass; this group only resolves its pairs into slots and offsets
+    const AsxPoolPair *pl = x.pool ? W.pool : nullptr;
+    if (x.pool) {
+        const AsxPoolArgs A{ x.pool->rows, (uint64_t)x.first, (uint64_t)x.pool->nsrc, (uint64_t)x.pool->nsmp, (uint64_t)x.src_step,
+                             (uint64_t)x.smp_step, p->bank.nrm, p->bank.band };
+        asx_launch_pool_resolve(P, A, W.pool, pk.nrm_part, tk.band, (int)g, s);
+    } else if (P.rlayout) {
         const int op0 = x.bc & 1, nops = 2 - (x.bc & 1) - ((x.bc >> 1) & 1);
         if (nops > 0 && !asx_launch_fwd_cols_r(P, x.src, x.src_step, x.smp, x.smp_step, W.zxa, W.zya, pk.nrm_part, tk.band, (int)g, op0,
                                                nops, false, s))
@@ -743,7 +772,9 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     }
     if (mark(1)) return -1;
     float2 *q = W.ga;
-    if (P.rlayout) {
+    if (x.pool) {
+        if (!asx_launch_rows_rl(P, p->bank.cx, p->bank.cy, q, tk, pl, (int)g, s)) return fail("internal: no row kernel for this plan");
+    } else if (P.rlayout) {
         if (!asx_launch_rows_r(P, (x.bc & 1) ? p->bslot.cx : W.zxa, (x.bc & 2) ? p->bslot.cy : W.zya, q, tk, (int)g, x.bc, s))
             return fail("internal: no row kernel for this plan");
     } else {
@@ -769,15 +800,17 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // pairs, 128 blocks each were 131 072 empty blocks, 25 us of a 2 ms step.
     const int dot_blocks = o.dot_blocks ? o.dot_blocks : (int)std::min<size_t>(ASX_DOT_BLOCKS, std::max<size_t>(8, 16384 / g));
     // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
-    asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral, seed, pr);
+    asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral, seed, pr, nullptr, pl);
     if (mark(4)) return -1;
     if (!spectral)
-        asx_launch_pearson(x.tsrc, x.tsmp, x.src_step, x.smp_step, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
+        asx_launch_pearson(x.tsrc, x.tsmp, x.src_step, x.smp_step, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s, pl);
     else if constexpr (std::is_same<TIn, float>::value)
         asx_launch_pearson_spectral_f32(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, tk, W.spec, W.seg, W.psums, out.lag, out.coef,
-                                        out.ret, (int)g, s, seed, pr);
+                                        out.ret, (int)g, s, seed, pr, nullptr, pl);
     // a pair whose row is not a window: (0, NaN, -2), the others untouched (top-k: k_topk_step writes it for every entry)
     if (pr && K == 1) asx_launch_invalid_rows(rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
+    // a pool pair with an index outside its pool: (0, NaN, -4), which takes precedence over -2
+    if (pl) asx_launch_invalid_pairs(pl, y.lag, y.coef, y.ret, (int)g, s);
     // Passes 2..k over the same Q: the inverse columns, finalize, exact re-evaluation and Pearson again, each pair's window minus the
     // zones around its earlier entries (the records k_topk_step keeps); the transforms are not run again.
     for (int j = 0; K > 1 && j < K; j++) {
@@ -815,9 +848,9 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
 //        pass is redone on the caller's values for the lag that wins.
 // It runs on `s` behind everything the call has launched (the lanes have been joined), in the workspace slot 0 of
 // lane 0 and the plan's one set of big lists: nothing else is in flight on this plan (one stream at a time per plan).
-// x and y are the window the list's indices count from: the listed pair i is x.at(i), its results y.at(i).
+// xi is the listed pair itself (explicit pointers, no broadcast slot, no pool), yi its results.
 template <typename TIn>
-static int second_look(asx_plan *p, const Pairs<TIn> &x, const Results &y, size_t i, hipStream_t s, const Topk &topk)
+static int second_look(asx_plan *p, const Pairs<TIn> &xi, const Results &yi, hipStream_t s, const Topk &topk)
 {
     const AsxDev &P = p->dev;
     const size_t N = p->host.N;
@@ -843,10 +876,9 @@ static int second_look(asx_plan *p, const Pairs<TIn> &x, const Results &y, size_
     K.cap = (uint32_t)B.cap;
     HIP_TRY(hipMemsetAsync(B.cand_n, 0, sizeof(uint32_t), s));
     // r = r' + stats[2]
-    const Pairs<TIn> xi = x.at(i);
     asx_launch_dc_remove(xi.tsrc, xi.tsmp, P.N, (double)P.F, B.stats, B.src_dc, s);
     K.shift = B.stats + 2;
-    if (run_group(p, Pairs<TIn>{ B.src_dc, xi.smp, xi.tsrc, xi.tsmp, 2 * N, N, 0, xi.win, xi.win_step }, 1, y.at(i), s,
+    if (run_group(p, Pairs<TIn>{ B.src_dc, xi.smp, xi.tsrc, xi.tsmp, 2 * N, N, 0, xi.win, xi.win_step }, 1, yi, s,
                   { .prof_group = GroupOpts::no_marks, .listed = false, .spectral = false, .dot_blocks = 2048, .pk = &K, .topk = topk }))
         return -1;
     p->repaired++;
@@ -873,10 +905,32 @@ static int resolve_overflows(asx_plan *p, const Pairs<TIn> &x, const Results &y,
     p->h_over.resize(n);
     HIP_TRY(hipMemcpyAsync(p->h_over.data(), p->over_list, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemsetAsync(p->over_n, 0, sizeof(uint32_t), s));
+    // pool calls: the listed pairs' rows {a, b} (a small copy of those rows only), so that each pair's second look runs on explicit
+    // pointers -- as the strided call's does
+    std::vector<int32_t> ab;
+    if (x.pool) {
+        ab.resize(2 * (size_t)n);
+        for (uint32_t k = 0; k < n; k++) {
+            const size_t pi = x.first + p->h_over[k];
+            if (x.pool->rows)
+                HIP_TRY(hipMemcpyAsync(&ab[2 * k], x.pool->rows + 2 * pi, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            else { ab[2 * k] = (int32_t)(pi / x.pool->nsmp); ab[2 * k + 1] = (int32_t)(pi % x.pool->nsmp); }
+        }
+    }
     HIP_TRY(hipStreamSynchronize(s));
     *p->h_over_n = 0;
-    for (uint32_t k = 0; k < n; k++)
-        if (second_look(p, x, y, p->h_over[k], s, topk)) return -1;
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t i = p->h_over[k];
+        Pairs<TIn> xi = x.at(i);
+        if (x.pool) {
+            const int64_t a = ab[2 * k], b = ab[2 * k + 1];
+            if (a < 0 || (size_t)a >= x.pool->nsrc || b < 0 || (size_t)b >= x.pool->nsmp) continue; // (k_rows_rl never lets one overflow)
+            const size_t N = p->host.N;
+            xi = Pairs<TIn>{ x.src + (size_t)a * x.src_step, x.smp + (size_t)b * x.smp_step, x.tsrc + (size_t)a * x.src_step,
+                             x.tsmp + (size_t)b * x.smp_step, 2 * N, N, 0, xi.win, xi.win_step };
+        }
+        if (second_look(p, xi, y.at(i), s, topk)) return -1;
+    }
     return (int)n;
 }
 
@@ -1110,6 +1164,102 @@ extern "C" int asx_xcorr_topk_f32_dev(asx_plan *p, const float *d_source, size_t
     if (min_separation < 0) return fail("asx_xcorr_topk_f32_dev: min_separation = %lld is negative", (long long)min_separation);
     return strided_batch(p, "asx_xcorr_topk_f32_dev", d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch,
                          { d_lag, d_coef, d_ret, (size_t)k }, stream, Topk{ k, min_separation });
+}
+
+// ---------------------------------------------------------------------------
+// pool calls: listed pairs of two track pools (asx_xcorr_pool_f32_dev)
+// ---------------------------------------------------------------------------
+// The bank holds at least nsrc source and nsmp sample tracks.  Grown (everything reallocated, behind a device synchronisation: earlier
+// calls may still read the old one) when a call names more; never inside a stream capture.
+static int ensure_bank(asx_plan *p, const char *fn, size_t nsrc, size_t nsmp, hipStream_t s)
+{
+    asx_plan::Bank &B = p->bank;
+    if (nsrc <= B.nsrc && nsmp <= B.nsmp) return 0;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
+    if (cap != hipStreamCaptureStatusNone)
+        return fail("%s: the plan's bank holds %zu x %zu tracks and cannot grow to %zu x %zu during a stream capture; make a call "
+                    "with pools at least this large outside the capture first", fn, B.nsrc, B.nsmp, nsrc, nsmp);
+    const AsxDev &P = p->dev;
+    const size_t ns = std::max(nsrc, B.nsrc), nm = std::max(nsmp, B.nsmp), na = std::max(ns, nm);
+    const size_t pitch = ((size_t)p->host.M1 + 1) * (size_t)p->host.M2, nb = (size_t)P.ntiles * (size_t)P.nbands;
+    HIP_TRY(hipDeviceSynchronize());
+    for (void *a : { (void *)B.cx, (void *)B.cy, (void *)B.nrm, (void *)B.band })
+        if (a) (void)hipFree(a);
+    B = asx_plan::Bank{ nullptr, nullptr, nullptr, nullptr, 0, 0, B.fills };
+    asx_plan::Bank T = B;
+    if (hipMalloc((void **)&T.cx, ns * pitch * sizeof(float2)) != hipSuccess ||
+        hipMalloc((void **)&T.cy, nm * pitch * sizeof(float2)) != hipSuccess ||
+        hipMalloc((void **)&T.nrm, na * 2 * (size_t)P.ntiles * sizeof(float)) != hipSuccess ||
+        (nb && hipMalloc((void **)&T.band, na * 2 * nb * sizeof(float2)) != hipSuccess)) {
+        (void)hipGetLastError();
+        for (void *a : { (void *)T.cx, (void *)T.cy, (void *)T.nrm, (void *)T.band })
+            if (a) (void)hipFree(a);
+        return fail("%s: cannot allocate the plan's bank for %zu source and %zu sample tracks (%zu bytes per track)", fn, ns, nm,
+                    pitch * sizeof(float2));
+    }
+    T.nsrc = ns;
+    T.nsmp = nm;
+    B = T;
+    return 0;
+}
+
+extern "C" int asx_xcorr_pool_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                      const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                      const int64_t *d_windows, size_t window_stride, size_t batch, int64_t *d_lag, double *d_coef,
+                                      int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_pool_f32_dev";
+    if (!p || !d_sources || !d_samples || !d_coef || !d_ret) return fail("%s: null argument", fn);
+    std::lock_guard<std::mutex> guard(p->lock);
+    DevGuard dg(p->device);
+    if (!dg.ok) return fail("cannot select device %d", p->device);
+    const AsxDev &P = p->dev;
+    if (P.rlayout != 1) return fail("%s: pool calls need a real-column plan (asx_plan_layout() == 1)", fn);
+    if (((uintptr_t)d_sources & 15u) || ((uintptr_t)d_samples & 15u))
+        return fail("%s: the pools must be 16-byte aligned (sources %p, samples %p)", fn, (const void *)d_sources, (const void *)d_samples);
+    if ((source_stride & 3u) || (sample_stride & 3u))
+        return fail("%s: strides must be multiples of 4 floats (source_stride %zu, sample_stride %zu)", fn, source_stride, sample_stride);
+    if (nsources > INT32_MAX || nsamples > INT32_MAX) return fail("%s: a pool of more than 2^31 - 1 tracks", fn);
+    if (!d_pairs && batch != nsources * nsamples)
+        return fail("%s: without pairs the batch is every combination, %zu x %zu, not %zu", fn, nsources, nsamples, batch);
+    if (batch == 0) return 0;
+    if (nsources == 0 || nsamples == 0) return fail("%s: an empty pool (%zu sources, %zu samples) for %zu pairs", fn, nsources, nsamples, batch);
+    hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+    if (ensure_bank(p, fn, nsources, nsamples, s)) return -1;
+    // the bank fill: every track's forward column pass, once per call, on the caller's stream before any lane forks (grid.z: at most
+    // 65535 tracks per launch)
+    asx_plan::Bank &B = p->bank;
+    const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, nt = (size_t)P.ntiles, nb = nt * (size_t)P.nbands;
+    for (int op = 0; op < 2; op++) {
+        const size_t n = op ? nsamples : nsources;
+        for (size_t c0 = 0; c0 < n; c0 += 65535) {
+            const size_t c = std::min<size_t>(65535, n - c0);
+            const bool ok = op == 0 ? asx_launch_fwd_cols_r(P, d_sources + c0 * source_stride, source_stride, d_samples, 0, B.cx + c0 * pitch,
+                                                            B.cy, B.nrm + c0 * 2 * nt, B.band ? B.band + c0 * 2 * nb : nullptr, (int)c, 0, 1,
+                                                            true, s)
+                                    : asx_launch_fwd_cols_r(P, d_sources, 0, d_samples + c0 * sample_stride, sample_stride, B.cx,
+                                                            B.cy + c0 * pitch, B.nrm + c0 * 2 * nt, B.band ? B.band + c0 * 2 * nb : nullptr,
+                                                            (int)c, 1, 1, true, s);
+            if (!ok) return fail("internal: no forward column kernel for this plan");
+        }
+    }
+    B.fills++;
+    const PoolCall pool{ d_pairs, nsources, nsamples };
+    Pairs<float> x{ d_sources, d_samples, d_sources, d_samples, source_stride, sample_stride, 0, d_windows, window_stride };
+    x.pool = &pool;
+    return run_batch(p, x, batch, { d_lag, d_coef, d_ret }, s);
+}
+
+// diagnostic (not in the public header): the bank's capacity in tracks and how many pool calls have filled it
+extern "C" int asx_plan_debug_bank(asx_plan *p, uint64_t *nsrc, uint64_t *nsmp, uint64_t *fills)
+{
+    if (!p || !nsrc || !nsmp || !fills) return -1;
+    std::lock_guard<std::mutex> guard(p->lock);
+    *nsrc = p->bank.nsrc;
+    *nsmp = p->bank.nsmp;
+    *fills = p->bank.fills;
+    return 0;
 }
 
 extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const float *d_sample,

@@ -203,6 +203,29 @@ struct AsxTopkWs {
     unsigned long long *sink;    // [1] where k_finalize_x counts the later overflows of a pair already counted in this call
 };
 
+// Pool calls (asx_xcorr_pool_f32_dev): pair i of a call is source a_i of one pool against sample b_i of another.  Every track of both
+// pools has its forward column pass in the plan's bank (written once per call); k_pool_resolve (rlayout.hip) turns each pair of a launch
+// group into one of these records in the lane's workspace, and the listed kernels (k_rows_rl, k_refine_dots_l, k_pearson_partial_l,
+// k_pearson_prep_l, k_pearson_prep_pl) read pair i's slots and inputs from it instead of from i * pitch.  An index outside its pool
+// gives slot 0 and ASX_POOL_INVALID: k_rows_rl writes a NaN Q for it (one candidate, the seed: it can never overflow) and
+// k_invalid_pairs writes (0, NaN, -4) behind the Pearson kernels.
+#define ASX_POOL_INVALID 1u
+struct AsxPoolPair {
+    uint32_t sx, sy;        // bank slots: source a, sample b (0 for an invalid pair)
+    uint32_t flags, pad;    // ASX_POOL_INVALID
+    uint64_t src_off;       // a * source_stride: the source's first float in the source pool
+    uint64_t smp_off;       // b * sample_stride
+};
+// what k_pool_resolve reads: the caller's rows (null: every combination, source-major), the pools' sizes and strides, and the
+// bank's norm partials and band sums (AsxPeakWs layout: source slot a at operand 0 of "pair" a, sample slot b at operand 1 of b)
+struct AsxPoolArgs {
+    const int32_t *rows;
+    uint64_t first;         // the group's first pair in the call
+    uint64_t nsrc, nsmp, src_stride, smp_stride;
+    const float *nrm;
+    const float2 *band;
+};
+
 // kernel launchers (defined in xcorr_kernels.hip, called from asx_api.hip)
 struct AsxCand {          // one near-maximum lag found by a column tile
     uint32_t idx;
@@ -281,6 +304,14 @@ bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W,
                            int tk_zones = 0);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
+// pool calls: each pair's record (out) and its two slots' norm partials and band sums (band may be null) into the group's places
+void asx_launch_pool_resolve(const AsxDev &P, const AsxPoolArgs &A, AsxPoolPair *out, float *nrm, float2 *band, int npairs,
+                             hipStream_t s);
+// k_rows_rl: k_rows_r with C_x / C_y at the pairs' bank slots (cx, cy: the bank's source and sample spectra)
+bool asx_launch_rows_rl(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, const AsxPoolPair *pl,
+                        int npairs, hipStream_t s);
+// behind the Pearson kernels of a pool group: (0, NaN, -4) for every pair flagged ASX_POOL_INVALID
+void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 bool asx_rlayout_available(const AsxDev &P); // all three kernels compiled in for this plan's schedules
 int asx_rlayout_band_rows(const AsxDev &P);
 // seed (the lag window's, AsxWin): the index an empty running maximum stands for, and the one whose exact value competes signed;
@@ -296,24 +327,27 @@ void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, in
 // behind the Pearson kernels of a group with per-pair windows: (lag, coef, ret) = (0, NaN, -2) for every pair whose row is invalid
 void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 // The exact passes over float or double inputs (instances for both next to the kernels, xcorr_kernels.hip).  The pairs' inputs
-// are src_pitch / smp_pitch elements apart (0 = one track for every pair).
+// are src_pitch / smp_pitch elements apart (0 = one track for every pair); pl (pool calls, float inputs only): pair i's inputs are
+// src + pl[i].src_off and smp + pl[i].smp_off instead (the listed kernels).
 // refine: pick = false: the exact values only; the caller's next kernel applies the rule (k_pearson_prep)
 template <typename TIn>
 void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
                        AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed = 0,
-                       const AsxWinRows *rows = nullptr, const AsxTopkPair *tk = nullptr);
+                       const AsxWinRows *rows = nullptr, const AsxTopkPair *tk = nullptr, const AsxPoolPair *pl = nullptr);
 template <typename TIn>
 void asx_launch_pearson(const TIn *src, const TIn *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len, const AsxSeg *seg,
-                        double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
+                        double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s,
+                        const AsxPoolPair *pl = nullptr);
 // the partial-sum kernel alone (the spectral form runs it on its own segment list, pearson_spectral.hip)
 void asx_launch_pearson_partial_spec_f32(const float *src, const float *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len,
-                                         const AsxSeg *seg, const AsxSpecWs &S, double *psums, int npairs, hipStream_t s);
+                                         const AsxSeg *seg, const AsxSpecWs &S, double *psums, int npairs, hipStream_t s,
+                                         const AsxPoolPair *pl = nullptr);
 // pearson_spectral.hip: float32 inputs src_pitch / smp_pitch floats apart, real-column plans (W.band and W.tile_peak filled by this
 // group's transform kernels)
 void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
                                      const AsxPeakWs &W, const AsxSpecWs &S, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
                                      int32_t *ret, int npairs, hipStream_t s, uint32_t seed = 0, const AsxWinRows *rows = nullptr,
-                                     const AsxTopkPair *tk = nullptr);
+                                     const AsxTopkPair *tk = nullptr, const AsxPoolPair *pl = nullptr);
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
                               double min_confidence, double sample_rate, int64_t *lag_ms, int32_t *accept,
                               hipStream_t s);

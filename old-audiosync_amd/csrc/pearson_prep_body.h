@@ -1,6 +1,11 @@
 // csrc/pearson_prep_body.h -- the body of k_pearson_prep and of its per-pair form k_pearson_prep_p (pearson_spectral.hip), included
 // INSIDE both kernels (k_pearson_prep has to stay the kernel it was).  The including kernel defines seed (uint32_t): the index whose
-// exact value competes signed.
+// exact value competes signed.  ASX_SRC_OF(pair) / ASX_SMP_OF(pair): where pair's inputs start in floats from src / smp (by default
+// pair * src_pitch / pair * smp_pitch; the listed forms k_pearson_prep_l / _pl define their own before the include).
+#ifndef ASX_SRC_OF
+#define ASX_SRC_OF(pair) pair * src_pitch
+#define ASX_SMP_OF(pair) pair * smp_pitch
+#endif
     __shared__ double red[4][NTP / 64];
     __shared__ double s_exact;
     __shared__ int s_have_exact;
@@ -72,7 +77,7 @@
         hdr[0] = r; hdr[1] = rb; hdr[2] = direct ? 1.0 : 0.0; hdr[3] = 0.0;
     }
     if (direct) return; // block-uniform, and the same in every block of the pair: nobody reads its shares
-    const float *x = src + pair * src_pitch, *y = smp + pair * smp_pitch;
+    const float *x = src + ASX_SRC_OF(pair), *y = smp + ASX_SMP_OF(pair);
     const int ntiles = Pp->ntiles;
     const float2 *bx = W.band + (size_t)pair * 2 * ntiles * nbands, *by = bx + (size_t)ntiles * nbands;
     const Acc2 ax = window_share<(uint32_t)NTP * NB>(x, bx, gs, ntiles, nbands, s.src_off, s.src_off + s.len, gtid);
@@ -83,3 +88,5 @@
         double *mine = S.part + (pair * NB + blk) * 4;
         mine[0] = v[0]; mine[1] = v[1]; mine[2] = v[2]; mine[3] = v[3];
     }
+#undef ASX_SRC_OF
+#undef ASX_SMP_OF

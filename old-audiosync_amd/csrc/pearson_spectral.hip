@@ -170,6 +170,29 @@ template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep
 #include "pearson_prep_body.h"
 }
 
+// the listed forms (asx_xcorr_pool_f32_dev): pair i's inputs at src + PL[i].src_off, smp + PL[i].smp_off; the plan's seed, or (_pl) the
+// pair's own from its row
+template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep_l(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
+                                                                      const float *__restrict__ smp, const AsxPoolPair *__restrict__ PL,
+                                                                      AsxPeakWs W, AsxSpecWs S, AsxSeg *__restrict__ seg, uint32_t seed)
+{
+#define ASX_SRC_OF(pair) PL[pair].src_off
+#define ASX_SMP_OF(pair) PL[pair].smp_off
+#include "pearson_prep_body.h"
+}
+
+template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep_pl(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
+                                                                       const float *__restrict__ smp, const AsxPoolPair *__restrict__ PL,
+                                                                       AsxPeakWs W, AsxSpecWs S, AsxSeg *__restrict__ seg, AsxWinRows R)
+{
+    AsxWin Z;
+    (void)asx_win_row(R, blockIdx.y, Pp->N, Z);
+    const uint32_t seed = Z.seed;
+#define ASX_SRC_OF(pair) PL[pair].src_off
+#define ASX_SMP_OF(pair) PL[pair].smp_off
+#include "pearson_prep_body.h"
+}
+
 // grid (npairs), one wave per pair: k_pearson_final (xcorr_kernels.hip) with the two spectral modes in front of it.
 __global__ __launch_bounds__(64) void k_pearson_final_spec(const AsxSeg *__restrict__ seg, const double *__restrict__ psums, uint32_t nb,
                                                             AsxSpecWs S, int64_t *__restrict__ lag,
@@ -212,11 +235,24 @@ __global__ __launch_bounds__(64) void k_pearson_final_spec(const AsxSeg *__restr
 void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
                                      const AsxPeakWs &W, const AsxSpecWs &S0, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
                                      int32_t *ret, int npairs, hipStream_t s, uint32_t seed, const AsxWinRows *rows,
-                                     const AsxTopkPair *tk)
+                                     const AsxTopkPair *tk, const AsxPoolPair *pl)
 {
     AsxSpecWs S = S0;
     S.N = P.N;
-    if (tk) {
+    if (pl) {
+        // (pool calls: no top-k; per-pair windows or the plan's seed)
+        S.nb = (size_t)P.band_rows * (size_t)P.M2 >= 16384 ? ASX_PREP_BLOCKS : 1;
+        if (rows && S.nb > 1)
+            hipLaunchKernelGGL((k_pearson_prep_pl<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS),
+                               0, s, P.self_dev, src, smp, pl, W, S, seg, *rows);
+        else if (rows)
+            hipLaunchKernelGGL((k_pearson_prep_pl<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, pl, W, S, seg, *rows);
+        else if (S.nb > 1)
+            hipLaunchKernelGGL((k_pearson_prep_l<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS),
+                               0, s, P.self_dev, src, smp, pl, W, S, seg, seed);
+        else
+            hipLaunchKernelGGL((k_pearson_prep_l<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, pl, W, S, seg, seed);
+    } else if (tk) {
         S.nb = (size_t)P.band_rows * (size_t)P.M2 >= 16384 ? ASX_PREP_BLOCKS : 1;
         if (S.nb > 1)
             hipLaunchKernelGGL((k_pearson_prep_x<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0,
@@ -240,6 +276,6 @@ void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t s
         S.nb = 1;
         hipLaunchKernelGGL((k_pearson_prep<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg, seed);
     }
-    asx_launch_pearson_partial_spec_f32(src, smp, src_pitch, smp_pitch, P.N, seg, S, psums, npairs, s);
+    asx_launch_pearson_partial_spec_f32(src, smp, src_pitch, smp_pitch, P.N, seg, S, psums, npairs, s, pl);
     hipLaunchKernelGGL(k_pearson_final_spec, dim3(npairs), dim3(64), 0, s, seg, psums, asx_pearson_blocks(P.N), S, lag, coef, ret);
 }

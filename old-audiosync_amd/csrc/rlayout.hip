@@ -193,6 +193,7 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 //                pieces, whole 128-byte lines of C and Q) instead of 1200 / 800 rows of eight.
 //   BC: broadcast forms (asx_xcorr_strided_f32_dev).  Bit 0 = C_x is the plan's broadcast slot, one C for every pair (pair step
 //   0, temporal loads: every pair reads it, it must stay in the caches), bit 1 = C_y is.  BC = 0: both have Q's pair step.
+//   Bit 2 (k_rows_rl, pool calls): C_x / C_y are rows sx / sy of the plan's bank (L[pair], AsxPoolPair), temporal like the slot.
 // ---------------------------------------------------------------------------
 // The body takes P and W by value: that call boundary loads their fields at the top of the kernel.  Written inside the __global__
 // itself the instruction stream changes, and with it the float32 rounding of r (11 of the headline's 124 coefficients moved by
@@ -200,7 +201,7 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 template <class S, int NT, bool TWO, int BC>
 __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restrict__ cx, const float2 *__restrict__ cy,
                                             float2 *__restrict__ qo, int nrows, size_t pitch_x, size_t pitch_y, size_t pitch_q,
-                                            AsxPeakWs W)
+                                            AsxPeakWs W, const AsxPoolPair *__restrict__ L = nullptr)
 {
     static_assert(S::nstages == 3, "three-stage row schedules only");
     constexpr int NS = S::n;                 // length of a (sub-)row transform
@@ -230,7 +231,14 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
     const int pair = task / nrows;
     const uint32_t k1 = (uint32_t)(task - pair * nrows);
     const size_t row = (size_t)RWS_PAIR(pair) * pitch_q + (size_t)k1 * M2;
-    const size_t rowx = (size_t)RWS_PAIR(pair) * pitch_x + (size_t)k1 * M2, rowy = (size_t)RWS_PAIR(pair) * pitch_y + (size_t)k1 * M2;
+    size_t rowx, rowy;
+    if constexpr ((BC & 4) != 0) {
+        rowx = (size_t)L[pair].sx * pitch_x + (size_t)k1 * M2;
+        rowy = (size_t)L[pair].sy * pitch_y + (size_t)k1 * M2;
+    } else {
+        rowx = (size_t)RWS_PAIR(pair) * pitch_x + (size_t)k1 * M2;
+        rowy = (size_t)RWS_PAIR(pair) * pitch_y + (size_t)k1 * M2;
+    }
     if (k1 == 0 && tid < 64) {
         // Row 0 of a pair also prepares the pair's peak search (k_inv_cols_r runs after this kernel): the float32
         // error bound from the norms k_fwd_cols_r left, the running maximum and the candidate count back to zero.
@@ -471,6 +479,33 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_r(c
     rows_r_body<S, NT, TWO, BC>(P, cx, cy, qo, nrows, (BC & 1) ? 0 : pair_pitch, (BC & 2) ? 0 : pair_pitch, pair_pitch, W);
 }
 
+// The listed form (asx_xcorr_pool_f32_dev): pair p's C_x / C_y are rows L[p].sx / L[p].sy of the bank (cx, cy: its source and sample
+// spectra, pair_pitch apart), both loaded temporal -- consecutive pairs may share a slot.  The same body: the same float32 Q, bit for
+// bit, as k_rows_r on the same C rows.  A pair flagged ASX_POOL_INVALID (an index outside its pool) gets a NaN Q instead: its peak
+// search sees a NaN r, in which only the seed has a key (+inf, asx_win_has permitting) -- one candidate at most whatever its window, so
+// it is never counted, listed or re-evaluated -- and k_invalid_pairs overwrites its results.
+template <class S, int NT, bool TWO>
+__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rl(const RArgs P, const float2 *__restrict__ cx,
+                                                                                 const float2 *__restrict__ cy, float2 *__restrict__ qo,
+                                                                                 int nrows, size_t pair_pitch, AsxPeakWs W,
+                                                                                 const AsxPoolPair *__restrict__ L)
+{
+    const int pair = blockIdx.x / nrows;
+    if (L[pair].flags & ASX_POOL_INVALID) { // block-uniform
+        constexpr int M2 = TWO ? 2 * S::n : S::n, NTB = TWO ? 2 * NT : NT;
+        const int k1 = blockIdx.x - pair * nrows;
+        float2 *go = qo + (size_t)pair * pair_pitch + (size_t)k1 * M2;
+        for (int j = threadIdx.x; j < M2; j += NTB) go[j] = make_float2(NAN, NAN);
+        if (k1 == 0 && threadIdx.x == 0) {
+            W.bound2[pair] = 0.f;
+            W.pairmax[pair] = 0;
+            W.cand_n[pair] = 0;
+        }
+        return;
+    }
+    rows_r_body<S, NT, TWO, 7>(P, cx, cy, qo, nrows, pair_pitch, pair_pitch, pair_pitch, W, L);
+}
+
 // ---------------------------------------------------------------------------
 // Column tiles of the real-column kernels: T REAL columns j2 = c0 .. c0+T-1 of the [2 M1][M2] sample matrix, held
 // in LDS as [M1][T/2] float4 slots: slot (m, g) = { x[2m][c0+2g], x[2m+1][c0+2g], x[2m][c0+2g+1], x[2m+1][c0+2g+1] },
@@ -669,6 +704,40 @@ __global__ __launch_bounds__(NT, 4) void k_fwd_cols_r(const RArgs P, const float
     }
 }
 
+// grid (ceil(per / 256), npairs): pool calls.  Pair i of the group (the call's pair A.first + i) as {source a, sample b}: from the caller's
+// row, or a = (first + i) / nsmp, b = (first + i) % nsmp.  An index outside its pool gives slot 0 and ASX_POOL_INVALID, so that no
+// kernel reads outside the pools.  Block x = 0 writes the record; every block copies its share of the two slots' norm partials and
+// band sums into pair i's places (k_bcast_aux's copy with a slot per pair).  per = ntiles, or ntiles * nbands with band sums.
+__global__ __launch_bounds__(256) void k_pool_resolve(AsxPoolArgs A, AsxPoolPair *__restrict__ out, float *__restrict__ nrm,
+                                                       float2 *__restrict__ band, int ntiles, int nbands)
+{
+    const size_t pair = blockIdx.y;
+    const uint64_t k = A.first + pair;
+    int64_t a, b;
+    if (A.rows) { a = A.rows[2 * k]; b = A.rows[2 * k + 1]; }
+    else { a = (int64_t)(k / A.nsmp); b = (int64_t)(k - (uint64_t)a * A.nsmp); }
+    const bool ok = a >= 0 && (uint64_t)a < A.nsrc && b >= 0 && (uint64_t)b < A.nsmp;
+    if (!ok) a = b = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        AsxPoolPair r;
+        r.sx = (uint32_t)a; r.sy = (uint32_t)b;
+        r.flags = ok ? 0u : ASX_POOL_INVALID; r.pad = 0u;
+        r.src_off = (uint64_t)a * A.src_stride;
+        r.smp_off = (uint64_t)b * A.smp_stride;
+        out[pair] = r;
+    }
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < ntiles) {
+        nrm[(pair * 2 + 0) * (size_t)ntiles + i] = A.nrm[((size_t)a * 2 + 0) * ntiles + i];
+        nrm[(pair * 2 + 1) * (size_t)ntiles + i] = A.nrm[((size_t)b * 2 + 1) * ntiles + i];
+    }
+    const int nb = ntiles * nbands;
+    if (band && i < nb) {
+        band[(pair * 2 + 0) * (size_t)nb + i] = A.band[((size_t)a * 2 + 0) * nb + i];
+        band[(pair * 2 + 1) * (size_t)nb + i] = A.band[((size_t)b * 2 + 1) * nb + i];
+    }
+}
+
 // grid (ceil(per / 256), npairs): the broadcast operand's norm partials and band sums (the slot's pair 0, operand `which`) into
 // every pair's place in the group's workspaces, where k_rows_r and the spectral Pearson form read them.  per = ntiles (norms)
 // + ntiles * nbands (band sums, when band != null).
@@ -836,6 +905,33 @@ bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride,
 #undef ASX_TRY
 #undef ASX_TRY1
     return false;
+}
+
+bool asx_launch_rows_rl(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, const AsxPoolPair *pl,
+                        int npairs, hipStream_t s)
+{
+    const int nrows = P.M1 + 1;
+    const size_t pitch = (size_t)nrows * (size_t)P.M2;
+    const size_t lds = (size_t)P.M2 * sizeof(float4);
+#define ASX_ROWSRL_CASE(nt, two, n, ...)                                                                                        \
+    if (P.M2 == ((two) ? 2 * n : n)) {                                                                                          \
+        hipLaunchKernelGGL((k_rows_rl<Sched<n, __VA_ARGS__>, nt, two>), dim3((unsigned)nrows * (unsigned)npairs),               \
+                           dim3((two) ? 2 * nt : nt), lds, s, rargs_of(P), cx, cy, q, nrows, pitch, W, pl);                      \
+        return true;                                                                                                            \
+    }
+    ASX_ROWSRL_CASE(128, false, 1200, 12, 10, 10)
+    ASX_ROWSRL_CASE(128, true, 1200, ASX_ROWS2_SCHED)
+    ASX_ROWSRL_CASE(64, false, 480, 10, 8, 6)
+#undef ASX_ROWSRL_CASE
+    return false;
+}
+
+void asx_launch_pool_resolve(const AsxDev &P, const AsxPoolArgs &A, AsxPoolPair *out, float *nrm, float2 *band, int npairs,
+                             hipStream_t s)
+{
+    const int per = std::max(P.ntiles, band ? P.ntiles * P.nbands : 0);
+    hipLaunchKernelGGL(k_pool_resolve, dim3((unsigned)(per + 255) / 256, (unsigned)npairs), dim3(256), 0, s, A, out, nrm, band, P.ntiles,
+                       P.nbands);
 }
 
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,

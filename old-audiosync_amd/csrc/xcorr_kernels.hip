@@ -725,6 +725,18 @@ __global__ __launch_bounds__(ASX_THREADS) void k_invalid_rows(AsxWinRows R, uint
     ret[pair] = -2;
 }
 
+// grid (npairs / ASX_THREADS): behind the Pearson kernels (and k_invalid_rows) of a pool group, the pairs with an index outside its pool
+// (ASX_POOL_INVALID) get lag 0, a NaN coefficient and ret -4; the others are not touched
+__global__ __launch_bounds__(ASX_THREADS) void k_invalid_pairs(const AsxPoolPair *__restrict__ PL, int npairs, int64_t *__restrict__ lag,
+                                                                double *__restrict__ coef, int32_t *__restrict__ ret)
+{
+    const int pair = blockIdx.x * ASX_THREADS + threadIdx.x;
+    if (pair >= npairs || !(PL[pair].flags & ASX_POOL_INVALID)) return;
+    if (lag) lag[pair] = 0;
+    coef[pair] = (double)NAN;
+    ret[pair] = -4;
+}
+
 // ---------------------------------------------------------------------------
 // Exact re-evaluation of near-tied lags: r[k] = sum_{n<N} source[(n+k) mod 2N] * sample[n]
 // (the identity behind src/cross_correlation.c:232-239), accumulated as an
@@ -752,52 +764,18 @@ template <typename TIn>
 __global__ __launch_bounds__(ASX_THREADS) void k_refine_dots(const AsxDev *__restrict__ Pp, const TIn *__restrict__ src,
                                                               const TIn *__restrict__ smp, size_t src_pitch, size_t smp_pitch, AsxPeakWs W)
 {
-    __shared__ double red[2][ASX_THREADS / 64];
-    const size_t pair = blockIdx.y;
-    const uint32_t ncand = W.refine_n[pair];
-    if (blockIdx.x >= ncand) return;
-    const uint32_t N = Pp->N, L = 2u * N;
-    const TIn *x = src + pair * src_pitch;
-    const TIn *y = smp + pair * smp_pitch;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (uint32_t c = blockIdx.x; c < ncand; c += gridDim.x) {
-        const uint32_t k = W.refine_idx[pair * (size_t)W.cap + c];
-        double hi = 0.0, lo = 0.0;
-        for (uint32_t n = threadIdx.x; n < N; n += ASX_THREADS) {
-            uint32_t i = n + k;
-            if (i >= L) i -= L;
-            const double a = (double)x[i], b = (double)y[n];
-            const double p = a * b;
-            double pe = 0.0;
-            if (sizeof(TIn) == sizeof(double)) pe = fma(a, b, -p);
-            const double s = hi + p;
-            const double bb = s - hi;
-            lo += ((hi - (s - bb)) + (p - bb)) + pe;
-            hi = s;
-        }
-        dd_t acc;
-        acc.hi = hi; acc.lo = lo;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            dd_t o;
-            o.hi = __shfl_xor(acc.hi, off, 64);
-            o.lo = __shfl_xor(acc.lo, off, 64);
-            acc = dd_add(acc, o);
-        }
-        if (lane == 0) { red[0][wave] = acc.hi; red[1][wave] = acc.lo; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            dd_t t;
-            t.hi = red[0][0]; t.lo = red[1][0];
-            for (int w = 1; w < ASX_THREADS / 64; w++) {
-                dd_t o;
-                o.hi = red[0][w]; o.lo = red[1][w];
-                t = dd_add(t, o);
-            }
-            W.refine_val[pair * (size_t)W.cap + c] = t.hi + t.lo;
-        }
-        __syncthreads();
-    }
+#include "refine_dots_body.h"
+}
+
+// the listed form (asx_xcorr_pool_f32_dev): pair i's inputs at src + PL[i].src_off, smp + PL[i].smp_off
+__global__ __launch_bounds__(ASX_THREADS) void k_refine_dots_l(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
+                                                                const float *__restrict__ smp, const AsxPoolPair *__restrict__ PL,
+                                                                AsxPeakWs W)
+{
+    typedef float TIn;
+#define ASX_SRC_OF(pair) PL[pair].src_off
+#define ASX_SMP_OF(pair) PL[pair].smp_off
+#include "refine_dots_body.h"
 }
 
 // grid (npairs): the reference's max_abs_index rule (src/cross_correlation.c:52-67) on the exact values:
@@ -850,117 +828,20 @@ __global__ __launch_bounds__(ASX_THREADS) void k_pearson_partial(const TIn *__re
                                                                   const AsxSeg *__restrict__ seg,
                                                                   double *__restrict__ psums, AsxSpecWs V)
 {
-    __shared__ double red[6][ASX_THREADS / 64];
-    const size_t pair = blockIdx.y;
-    AsxSeg s = seg[pair];
-    // SPEC (the spectral Pearson form): what this pair still needs read -- nothing, its wrap-around part, or its segment -- follows from
-    // the sums k_pearson_prep left; every block works that out for itself (pair-uniform: scalar loads and arithmetic)
-    // Block 0 also RECORDS the mode (the spare header slot): k_pearson_final_spec, in another translation unit, reads it instead of
-    // deciding again -- with -ffp-contract=fast two inlining contexts may round `bound <= tol` differently at the threshold, and a final
-    // kernel that disagreed with the work list would read partial sums written for another mode.  One writer, a later
-    // kernel reads: no fence.
-    if constexpr (SPEC) {
-        const AsxSpecPick d = asx_spec_pick(s, V.part + pair * (size_t)(V.nb * 4), V.nb, V.hdr + pair * ASX_SPEC_HDR, V.tol, V.N);
-        s = d.work;
-        if (blockIdx.x == 0 && threadIdx.x == 0) V.hdr[pair * ASX_SPEC_HDR + 3] = (double)d.mode;
-    }
-    // gridDim.x partial blocks per pair (asx_pearson_blocks: by the basis length alone); the final kernel merges
-    // exactly gridDim.x entries
-    const uint32_t chunk = (basis_len + gridDim.x - 1) / gridDim.x;
-    const uint64_t lo = (uint64_t)blockIdx.x * chunk;
-    uint64_t hi = lo + chunk;
-    if (hi > s.len) hi = s.len;
-    if (lo >= s.len) {
-        // nothing of the segment falls to this block (block-uniform): an empty record (pstat_merge skips n == 0) -- the whole
-        // launch for a pair the spectral form has settled (pearson_spectral.hip), the tail of a short segment otherwise
-        if (threadIdx.x == 0) psums[(pair * gridDim.x + blockIdx.x) * 6] = 0.0;
-        return;
-    }
-    const TIn *x = src + pair * src_pitch + s.src_off;
-    const TIn *y = smp + pair * smp_pitch + s.smp_off;
-    uint64_t i = lo + 4u * threadIdx.x;
-    double px = 0, py = 0; // pivots: the first element this thread meets
-#if ASX_PEARSON_DEEP
-    // (taken from the first 16-byte load below when the thread has one: a scalar load and the wait for it in front of the loop otherwise)
-    if (i < hi && !(i + 3 < hi)) { px = (double)x[i]; py = (double)y[i]; }
-#else
-    if (i < hi) { px = (double)x[i]; py = (double)y[i]; }
-#endif
-    double sx = 0, sy = 0, sxy = 0, sxx = 0, syy = 0;
-    uint32_t cnt = 0;
-    auto add = [&](double a, double b) {
-        const double da = a - px, db = b - py;
-        sx += da;
-        sy += db;
-        sxy += da * db;
-        sxx += da * da;
-        syy += db * db;
-        cnt++;
-    };
-    // four consecutive elements per lane and step: 16-byte loads (the segments start at any element,
-    // so the vector type only promises element alignment), then the few elements that are left
-    typedef TIn vec4u __attribute__((ext_vector_type(4), aligned(sizeof(TIn))));
-    auto ld4 = [&](const TIn *p) __attribute__((always_inline)) {
-        return (ASX_NT & 4) ? __builtin_nontemporal_load(reinterpret_cast<const vec4u *>(p)) : *reinterpret_cast<const vec4u *>(p);
-    };
-#if ASX_PEARSON_DEEP
-    // ASX_PEARSON_DEEP steps at a time: their 2 * ASX_PEARSON_DEEP loads in flight together, then the same additions in the same order (the
-    // loop used to wait for each step's two loads before it issued the next step's: 16 memory round trips per block, one after the other)
-    {
-        bool first = i + 3 < hi;
-        constexpr uint32_t STEP = 4u * ASX_THREADS;
-        for (; i + 3 + (uint64_t)(ASX_PEARSON_DEEP - 1) * STEP < hi; i += (uint64_t)ASX_PEARSON_DEEP * STEP) {
-            vec4u a[ASX_PEARSON_DEEP], b[ASX_PEARSON_DEEP];
-#pragma unroll
-            for (int u = 0; u < ASX_PEARSON_DEEP; u++) { a[u] = ld4(x + i + (uint64_t)u * STEP); b[u] = ld4(y + i + (uint64_t)u * STEP); }
-            if (first) { px = (double)a[0].x; py = (double)b[0].x; first = false; }
-#pragma unroll
-            for (int u = 0; u < ASX_PEARSON_DEEP; u++) {
-                add((double)a[u].x, (double)b[u].x);
-                add((double)a[u].y, (double)b[u].y);
-                add((double)a[u].z, (double)b[u].z);
-                add((double)a[u].w, (double)b[u].w);
-            }
-        }
-        if (first) { px = (double)x[i]; py = (double)y[i]; } // fewer than ASX_PEARSON_DEEP whole steps: the step loop below meets it first
-    }
-#endif
-    for (; i + 3 < hi; i += 4u * ASX_THREADS) {
-        const vec4u a = (ASX_NT & 4) ? __builtin_nontemporal_load(reinterpret_cast<const vec4u *>(x + i)) : *reinterpret_cast<const vec4u *>(x + i);
-        const vec4u b = (ASX_NT & 4) ? __builtin_nontemporal_load(reinterpret_cast<const vec4u *>(y + i)) : *reinterpret_cast<const vec4u *>(y + i);
-        add((double)a.x, (double)b.x);
-        add((double)a.y, (double)b.y);
-        add((double)a.z, (double)b.z);
-        add((double)a.w, (double)b.w);
-    }
-    for (; i < hi; i++) add((double)x[i], (double)y[i]); // only the lane that holds the ragged end
-    PStat v;
-    v.n = (double)cnt;
-    v.mx = v.my = v.mxx = v.myy = v.cxy = 0.0;
-    if (cnt) {
-        v.mx = px + sx / v.n;
-        v.my = py + sy / v.n;
-        v.mxx = sxx - sx * sx / v.n;
-        v.myy = syy - sy * sy / v.n;
-        v.cxy = sxy - sx * sy / v.n;
-    }
-    v = pstat_wave_merge(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = v.n; red[1][wave] = v.mx; red[2][wave] = v.my;
-        red[3][wave] = v.mxx; red[4][wave] = v.myy; red[5][wave] = v.cxy;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < ASX_THREADS / 64; w++) {
-            PStat o;
-            o.n = red[0][w]; o.mx = red[1][w]; o.my = red[2][w];
-            o.mxx = red[3][w]; o.myy = red[4][w]; o.cxy = red[5][w];
-            v = pstat_merge(v, o);
-        }
-        double *out = psums + (pair * gridDim.x + blockIdx.x) * 6;
-        out[0] = v.n; out[1] = v.mx; out[2] = v.my; out[3] = v.mxx; out[4] = v.myy; out[5] = v.cxy;
-    }
+#include "pearson_partial_body.h"
+}
+
+// the listed form (asx_xcorr_pool_f32_dev): pair i's inputs at src + PL[i].src_off, smp + PL[i].smp_off
+template <bool SPEC>
+__global__ __launch_bounds__(ASX_THREADS) void k_pearson_partial_l(const float *__restrict__ src, const float *__restrict__ smp,
+                                                                    const AsxPoolPair *__restrict__ PL, uint32_t basis_len,
+                                                                    const AsxSeg *__restrict__ seg, double *__restrict__ psums,
+                                                                    AsxSpecWs V)
+{
+    typedef float TIn;
+#define ASX_SRC_OF(pair) PL[pair].src_off
+#define ASX_SMP_OF(pair) PL[pair].smp_off
+#include "pearson_partial_body.h"
 }
 
 // grid (npairs), one wave per pair: lane b owns the partial blocks b, b + 64, ... (merged in that order: a fixed tree for a
@@ -1352,6 +1233,11 @@ void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, in
                        rows ? *rows : AsxWinRows{ nullptr, 0 }, N, npairs, j, k, sep, lag, coef, ret);
 }
 
+void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_invalid_pairs, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, pl, npairs, lag, coef, ret);
+}
+
 void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
 {
     hipLaunchKernelGGL(k_invalid_rows, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, rows, N, npairs, lag,
@@ -1361,9 +1247,17 @@ void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, d
 template <typename TIn>
 void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
                        AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed, const AsxWinRows *rows,
-                       const AsxTopkPair *tk)
+                       const AsxTopkPair *tk, const AsxPoolPair *pl)
 {
-    hipLaunchKernelGGL(k_refine_dots<TIn>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
+    if constexpr (std::is_same<TIn, float>::value) {
+        if (pl)
+            hipLaunchKernelGGL(k_refine_dots_l, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, pl, W);
+        else
+            hipLaunchKernelGGL(k_refine_dots<TIn>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch,
+                               smp_pitch, W);
+    } else {
+        hipLaunchKernelGGL(k_refine_dots<TIn>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
+    }
     if (pick && tk) hipLaunchKernelGGL(k_refine_pick_x, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, tk);
     else if (pick && rows) hipLaunchKernelGGL(k_refine_pick_p, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, *rows);
     else if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, seed);
@@ -1386,20 +1280,33 @@ unsigned asx_pearson_blocks(uint32_t basis_len)
 
 template <typename TIn>
 void asx_launch_pearson(const TIn *src, const TIn *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len, const AsxSeg *seg,
-                        double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
+                        double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s, const AsxPoolPair *pl)
 {
     const unsigned nb = asx_pearson_blocks(basis_len);
-    hipLaunchKernelGGL((k_pearson_partial<TIn, false>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
-                       src, smp, src_pitch, smp_pitch, basis_len, seg, psums, AsxSpecWs{});
+    if constexpr (std::is_same<TIn, float>::value) {
+        if (pl)
+            hipLaunchKernelGGL((k_pearson_partial_l<false>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s, src, smp, pl, basis_len, seg, psums,
+                               AsxSpecWs{});
+        else
+            hipLaunchKernelGGL((k_pearson_partial<TIn, false>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
+                               src, smp, src_pitch, smp_pitch, basis_len, seg, psums, AsxSpecWs{});
+    } else {
+        hipLaunchKernelGGL((k_pearson_partial<TIn, false>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
+                           src, smp, src_pitch, smp_pitch, basis_len, seg, psums, AsxSpecWs{});
+    }
     hipLaunchKernelGGL(k_pearson_final, dim3(npairs), dim3(64), 0, s, seg, psums, nb, lag, coef, ret);
 }
 
 void asx_launch_pearson_partial_spec_f32(const float *src, const float *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len,
-                                         const AsxSeg *seg, const AsxSpecWs &S, double *psums, int npairs, hipStream_t s)
+                                         const AsxSeg *seg, const AsxSpecWs &S, double *psums, int npairs, hipStream_t s,
+                                         const AsxPoolPair *pl)
 {
     const unsigned nb = asx_pearson_blocks(basis_len);
-    hipLaunchKernelGGL((k_pearson_partial<float, true>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
-                       src, smp, src_pitch, smp_pitch, basis_len, seg, psums, S);
+    if (pl)
+        hipLaunchKernelGGL((k_pearson_partial_l<true>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s, src, smp, pl, basis_len, seg, psums, S);
+    else
+        hipLaunchKernelGGL((k_pearson_partial<float, true>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
+                           src, smp, src_pitch, smp_pitch, basis_len, seg, psums, S);
 }
 
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
@@ -1431,9 +1338,9 @@ void asx_launch_dc_remove(const TIn *src, const TIn *smp, uint32_t N, double sca
 // the exact passes' instances (asx_internal.h): float32 and float64 inputs
 #define ASX_EXACT_PASSES(T)                                                                                                             \
     template void asx_launch_refine<T>(const AsxDev &, const T *, size_t, const T *, size_t, const AsxPeakWs &, AsxSeg *, int,           \
-                                       hipStream_t, int, bool, uint32_t, const AsxWinRows *, const AsxTopkPair *);                      \
+                                       hipStream_t, int, bool, uint32_t, const AsxWinRows *, const AsxTopkPair *, const AsxPoolPair *); \
     template void asx_launch_pearson<T>(const T *, const T *, size_t, size_t, uint32_t, const AsxSeg *, double *, int64_t *, double *,   \
-                                        int32_t *, int, hipStream_t);                                                                   \
+                                        int32_t *, int, hipStream_t, const AsxPoolPair *);                                              \
     template void asx_launch_dc_remove<T>(const T *, const T *, uint32_t, double, double *, float *, hipStream_t);
 ASX_EXACT_PASSES(float)
 ASX_EXACT_PASSES(double)

@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "asx_current_device", "asx_plan_timings_ms", "asx_xcorr_batch_multi", "asx_plan_layout", "asx_plan_narrowed_calls",
     "asx_plan_set_pearson", "asx_plan_pearson_modes", "asx_plan_placement", "asx_host_malloc", "asx_host_free", "asx_shard_range", "asx_result_bytes", "asx_comm_create", "asx_comm_destroy", "asx_xcorr_batch_multi_dev",
     "asx_xcorr_strided_f32_dev", "asx_plan_set_lag_window", "asx_plan_lag_window", "asx_stream_set_lag_window",
-    "asx_xcorr_windowed_f32_dev", "asx_xcorr_topk_f32_dev",
+    "asx_xcorr_windowed_f32_dev", "asx_xcorr_topk_f32_dev", "asx_xcorr_pool_f32_dev",
 ]
 
 TOPK_MAX = 8  # ASX_TOPK_MAX, include/audiosync/xcorr_hip.h
@@ -117,6 +117,12 @@ def lib():
     L.asx_xcorr_topk_f32_dev.restype = ctypes.c_int
     L.asx_xcorr_topk_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
                                          ctypes.c_int, ctypes.c_int64, vp, vp, vp, vp]
+    L.asx_xcorr_pool_f32_dev.restype = ctypes.c_int
+    L.asx_xcorr_pool_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp,
+                                         ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, vp]
+    L.asx_plan_debug_bank.restype = ctypes.c_int
+    L.asx_plan_debug_bank.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                      ctypes.POINTER(ctypes.c_uint64)]
     L.asx_shard_range.restype = ctypes.c_int
     L.asx_shard_range.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t),
                                   ctypes.POINTER(ctypes.c_size_t)]
@@ -326,6 +332,45 @@ def topk_args(n, source, sample, k, min_separation, windows=None):
         return s, t, None, batch, ss, ts, 0, int(k), int(min_separation)
     s, t, w, batch, ss, ts, ws = windowed_args(n, source, sample, windows)
     return s, t, w, batch, ss, ts, ws, int(k), int(min_separation)
+
+
+def pool_args(n, sources, samples, pairs=None, windows=None):
+    """Host checks of Plan.xcorr_pool_f32 for a plan of sample length n: sources [S, 2N] and samples [R, N] float arrays (S, R >= 1),
+    pairs None (every combination, source-major) or integers [B, 2] rows (source index, sample index), windows None or integers [2] /
+    [B, 2] rows (lag_min, lag_max) as in xcorr_windowed_f32.  -> (sources, samples, pairs or None, windows or None, batch,
+    window_stride) as contiguous float32 / int32 / int64 arrays.  ValueError on anything else.  The indices and the rows' values are
+    not checked: an index outside its pool comes back as (0, NaN, -4), a row that is not a window as (0, NaN, -2)."""
+    s = np.ascontiguousarray(sources, dtype=np.float32)
+    t = np.ascontiguousarray(samples, dtype=np.float32)
+    if s.ndim != 2 or t.ndim != 2 or s.shape[1] != 2 * n or t.shape[1] != n:
+        raise ValueError("sources must be [S, 2N] and samples [R, N] with N = %d" % n)
+    if s.shape[0] < 1 or t.shape[0] < 1:
+        raise ValueError("empty pool (%d sources, %d samples)" % (s.shape[0], t.shape[0]))
+    if s.shape[0] > 2 ** 31 - 1 or t.shape[0] > 2 ** 31 - 1:
+        raise ValueError("a pool of more than 2^31 - 1 tracks")
+    if pairs is None:
+        pr = None
+        batch = s.shape[0] * t.shape[0]
+    else:
+        pr = np.asarray(pairs)
+        if pr.dtype.kind not in "iu":
+            raise ValueError("pairs must hold integers (source index, sample index), not %s" % pr.dtype)
+        if pr.ndim != 2 or pr.shape[1] != 2 or pr.shape[0] < 1:
+            raise ValueError("pairs must be [B, 2] with B >= 1")
+        if pr.size and (pr.min() < -2 ** 31 or pr.max() > 2 ** 31 - 1):
+            raise ValueError("pair indices must fit int32")
+        pr = np.ascontiguousarray(pr, dtype=np.int32)
+        batch = pr.shape[0]
+    w, ws = None, 0
+    if windows is not None:
+        w = np.asarray(windows)
+        if w.dtype.kind not in "iu":
+            raise ValueError("windows must hold integers (lag_min, lag_max), not %s" % w.dtype)
+        w = np.ascontiguousarray(w, dtype=np.int64)
+        if w.ndim not in (1, 2) or w.shape[-1] != 2 or (w.ndim == 2 and w.shape[0] != batch):
+            raise ValueError("windows must be [2] or [B, 2] with B = %d pairs" % batch)
+        ws = 1 if w.ndim == 2 else 0
+    return s, t, pr, w, batch, ws
 
 
 def position_rows(n, hop, batch, p_lo, p_hi):
@@ -631,6 +676,66 @@ class Plan:
                                           d_ret or None, stream or None)
         if rc != 0:
             raise AsxError(_err())
+
+    def xcorr_pool_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows, window_stride,
+                       batch, d_lag, d_coef, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_f32_dev -- pair i is source d_pairs[2 i] of the source pool against sample
+        d_pairs[2 i + 1] of the sample pool (int32, device memory); d_pairs = 0: every combination, source-major, batch =
+        nsources * nsamples; d_windows = 0: the plan's window; asynchronous on `stream`"""
+        rc = lib().asx_xcorr_pool_f32_dev(self._h, d_sources, int(source_stride), int(nsources), d_samples, int(sample_stride),
+                                          int(nsamples), d_pairs or None, d_windows or None, int(window_stride), int(batch),
+                                          d_lag or None, d_coef, d_ret, stream or None)
+        if rc != 0:
+            raise AsxError(_err())
+
+    def debug_bank(self):
+        """(source tracks, sample tracks) the plan's pool bank holds, and how many pool calls have filled it"""
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        if lib().asx_plan_debug_bank(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)) != 0:
+            raise AsxError("asx_plan_debug_bank failed")
+        return a.value, b.value, c.value
+
+    def xcorr_pool_f32(self, sources, samples, pairs=None, windows=None):
+        """Many tracks against many (asx_xcorr_pool_f32_dev): sources float32 [S, 2N], samples [R, N]; pairs None (every combination)
+        or integers [B, 2] rows (source index, sample index); windows None (the plan's window) or integers [2] / [B, 2] as in
+        xcorr_windowed_f32.  Every track is transformed once per call.  Shapes are checked on the host (ValueError) before anything is
+        uploaded; an index outside its pool gives that pair (0, NaN, -4).  Returns (lag int64, coef float64, ret int32) of shape [B],
+        or [S, R] when pairs is None."""
+        s, t, pr, w, batch, ws = pool_args(self.sample_len, sources, samples, pairs, windows)
+        L = lib()
+        bufs = []
+        try:
+            def dev(nbytes):
+                ptr = L.asx_device_malloc(max(int(nbytes), 16), self.device)
+                if not ptr:
+                    raise AsxError(_err())
+                bufs.append(ptr)
+                return ptr
+            ups = [(dev(s.nbytes), s), (dev(t.nbytes), t)]
+            d_pairs = dev(pr.nbytes) if pr is not None else 0
+            d_win = dev(w.nbytes) if w is not None else 0
+            if pr is not None:
+                ups.append((d_pairs, pr))
+            if w is not None:
+                ups.append((d_win, w))
+            d_lag, d_coef, d_ret = dev(8 * batch), dev(8 * batch), dev(4 * batch)
+            for d, h in ups:
+                if L.asx_memcpy_h2d(d, h.ctypes.data, h.nbytes) != 0:
+                    raise AsxError(_err())
+            n = self.sample_len
+            self.xcorr_pool_dev(ups[0][0], 2 * n, s.shape[0], ups[1][0], n, t.shape[0], d_pairs, d_win, ws, batch, d_lag, d_coef, d_ret)
+            self.sync()
+            shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
+            lag = np.zeros(shape, dtype=np.int64)
+            coef = np.zeros(shape, dtype=np.float64)
+            ret = np.zeros(shape, dtype=np.int32)
+            for h, d in ((lag, d_lag), (coef, d_coef), (ret, d_ret)):
+                if L.asx_memcpy_d2h(h.ctypes.data, d, h.nbytes) != 0:
+                    raise AsxError(_err())
+            return lag, coef, ret
+        finally:
+            for ptr in bufs:
+                L.asx_device_free(ptr)
 
     def xcorr_topk_f32(self, source, sample, k, min_separation, windows=None):
         """The k strongest separated lags per pair (asx_xcorr_topk_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N];
