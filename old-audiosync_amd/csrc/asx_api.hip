@@ -9,6 +9,7 @@
 #include "host_narrow.h"
 
 #include <algorithm>
+#include <cassert>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -73,6 +74,14 @@ struct DevGuard {
     }
     ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+
+// whether s is capturing; a stream that cannot be asked counts as not capturing (the error is cleared)
+static bool stream_capturing(hipStream_t s)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
+    return cap != hipStreamCaptureStatusNone;
+}
 
 extern "C" int asx_current_device(void)
 {
@@ -175,6 +184,17 @@ struct asx_plan {
     std::vector<std::vector<hipEvent_t>> evr; // ring slot -> 6 events per launch group of that call, grown as needed
     std::vector<size_t> prof_groups; // groups recorded by the call in ring slot i
     size_t ev_groups = 0;            // groups recorded by the call in progress / the latest call
+};
+
+// What an entry point on a plan starts with: the plan's lock (the diagnostics take none), the plan's device selected until the
+// call returns, and the stream the call works on: the caller's, or the plan's own.
+struct PlanCall {
+    std::unique_lock<std::mutex> guard;
+    DevGuard dg;
+    hipStream_t s;
+    explicit PlanCall(asx_plan *p, void *stream = nullptr, bool lock = true)
+        : guard(lock ? std::unique_lock<std::mutex>(p->lock) : std::unique_lock<std::mutex>()), dg(p->device),
+          s(stream ? (hipStream_t)stream : p->stream) {}
 };
 
 template <typename T> static int dev_alloc(asx_plan *p, T **out, size_t count)
@@ -483,9 +503,8 @@ extern "C" long asx_plan_debug_stamps(asx_plan *p, unsigned long long *out, size
 extern "C" int asx_plan_peak_overflows(asx_plan *p, uint64_t *count)
 {
     if (!p || !count) return fail("asx_plan_peak_overflows: null argument");
-    std::lock_guard<std::mutex> guard(p->lock);
-    DevGuard dg(p->device);
-    if (!dg.ok) return fail("cannot select device %d", p->device);
+    PlanCall c(p);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
     unsigned long long total = 0;
     for (int l = 0; l < p->nlanes; l++) {
         unsigned long long v = 0;
@@ -501,9 +520,8 @@ extern "C" int asx_plan_peak_overflows(asx_plan *p, uint64_t *count)
 extern "C" int asx_plan_set_exact(asx_plan *p, int on)
 {
     if (!p) return fail("asx_plan_set_exact: null argument");
-    std::lock_guard<std::mutex> guard(p->lock);
-    DevGuard dg(p->device);
-    if (!dg.ok) return fail("cannot select device %d", p->device);
+    PlanCall c(p);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
     // whatever the asynchronous mode left on the list belongs to calls that have returned: start empty.  The whole
     // device is drained, not only the plan's own streams: an asynchronous batch may still be in flight on a stream the
     // CALLER supplied (asx_xcorr_batch_f32_dev's `stream`), and its k_finalize adds to the count this resets.
@@ -526,9 +544,8 @@ extern "C" int asx_plan_set_pearson(asx_plan *p, int spectral)
 extern "C" int asx_plan_pearson_modes(asx_plan *p, uint64_t counts[3])
 {
     if (!p || !counts) return fail("asx_plan_pearson_modes: null argument");
-    std::lock_guard<std::mutex> guard(p->lock);
-    DevGuard dg(p->device);
-    if (!dg.ok) return fail("cannot select device %d", p->device);
+    PlanCall c(p);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
     counts[0] = counts[1] = counts[2] = 0;
     if (!p->mode_count) return 0;
     // the whole device, as asx_plan_set_exact does: a batch on a caller-supplied stream (asx_xcorr_batch_f32_dev) is on none of the
@@ -553,7 +570,7 @@ extern "C" int asx_plan_debug_peak(asx_plan *p, size_t pair, float *bound2, uint
                                    unsigned long long *pairmax, double *vals, uint32_t *idxs, size_t cap)
 {
     if (!p || pair >= p->group) return -1;
-    DevGuard dg(p->device);
+    PlanCall c(p, nullptr, false);
     const AsxPeakWs &W = p->lanes[0].pk;
     (void)hipDeviceSynchronize();
     if (hipMemcpy(bound2, W.bound2 + pair, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
@@ -571,8 +588,8 @@ extern "C" int asx_plan_debug_peak(asx_plan *p, size_t pair, float *bound2, uint
 extern "C" int asx_plan_debug_over_list(asx_plan *p, uint32_t *dev_n, uint32_t *host_n)
 {
     if (!p || !dev_n || !host_n) return -1;
-    DevGuard dg(p->device);
-    if (!dg.ok || hipDeviceSynchronize() != hipSuccess) return -1;
+    PlanCall c(p, nullptr, false);
+    if (!c.dg.ok || hipDeviceSynchronize() != hipSuccess) return -1;
     if (hipMemcpy(dev_n, p->over_n, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     *host_n = *p->h_over_n;
     return 0;
@@ -691,6 +708,8 @@ template <typename TIn> struct Pairs {
         return { src + k * src_step, smp + k * smp_step, tsrc + k * src_step, tsmp + k * smp_step, src_step, smp_step, bc,
                  win ? win + 2 * k * win_step : nullptr, win_step };
     }
+    // what the exact passes read (pl: the group's resolved records in a pool call, else null)
+    AsxInputs<TIn> inputs(const AsxPoolPair *pl) const { return { tsrc, tsmp, src_step, smp_step, pl }; }
 };
 
 // Where pair k's results go (lag and ret may be null): entries step apart (asx_xcorr_topk_f32_dev: step = k, entry j of pair i at
@@ -781,51 +800,45 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
         asx_launch_rows(P, W.zxa, W.zya, q, tk, (int)g, s);
     }
     if (mark(2)) return -1;
-    // The lag window (asx_plan_set_lag_window), by value: the full one launches the same kernels as a plan that never had one.
-    // The second look at a pair runs through here too, with the window of the call that listed it.  Per-pair windows
-    // (asx_xcorr_windowed_f32_dev) replace it: the per-pair kernels read each pair's row from device memory.
-    const AsxWinRows rows{ x.win, x.win_step };
-    const AsxWinRows *pr = x.win ? &rows : nullptr;
-    const bool windowed = !pr && (p->win_lo != -(int64_t)P.N || p->win_hi != (int64_t)P.N - 1);
-    const AsxWin win = asx_win_of(p->win_lo, p->win_hi, P.N);
-    const uint32_t seed = windowed ? win.seed : 0u;
     // Top-k (o.topk.k > 1): every pass's results go to the lane's temporaries, and k_topk_step moves them to entry j of y
     const int K = o.topk.k;
     const Results out = K > 1 ? Results{ W.tk.lag, W.tk.coef, W.tk.ret } : y;
-    asx_launch_inv_cols(P, q, tk, o.r_out, (int)g, s, windowed ? &win : nullptr, pr);
-    if (mark(3)) return -1;
-    asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, seed, pr);
+    const AsxInputs<TIn> in = x.inputs(pl);
     // Blocks per pair of the exact re-evaluation: a candidate is one whole block's work whatever the grid, so the count only
     // sets how many candidates of a pair are in flight.  Nearly every block of a batch finds no candidate and exits: with 1024
     // pairs, 128 blocks each were 131 072 empty blocks, 25 us of a 2 ms step.
     const int dot_blocks = o.dot_blocks ? o.dot_blocks : (int)std::min<size_t>(ASX_DOT_BLOCKS, std::max<size_t>(8, 16384 / g));
-    // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
-    asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral, seed, pr, nullptr, pl);
-    if (mark(4)) return -1;
-    if (!spectral)
-        asx_launch_pearson(x.tsrc, x.tsmp, x.src_step, x.smp_step, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s, pl);
-    else if constexpr (std::is_same<TIn, float>::value)
-        asx_launch_pearson_spectral_f32(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, tk, W.spec, W.seg, W.psums, out.lag, out.coef,
-                                        out.ret, (int)g, s, seed, pr, nullptr, pl);
+    // The search of pass j + 1 (AsxSearch).  Pass 1: the plan's lag window (asx_plan_set_lag_window) -- the second look at a pair runs
+    // through here too, with the window of the call that listed it -- or the per-pair windows (asx_xcorr_windowed_f32_dev), which
+    // replace it.  Later passes of a top-k call: each pair's window minus the zones around its earlier entries (the records
+    // k_topk_step keeps).
+    auto search = [&](int j) { return AsxSearch::of(p->win_lo, p->win_hi, P.N, x.win, x.win_step, W.tk, j); };
+    // One pass over the group's Q: the inverse columns, finalize, the exact re-evaluation and Pearson, the lags of `find` competing.
+    // first: pass 1, which the profiling marks time and whose r goes to o.r_out.
+    auto pass = [&](const AsxSearch &find, bool first) -> int {
+        assert(!(pl && find.kind == AsxSearch::TOPK)); // pool + top-k: there are no listed top-k kernels, and no entry point asks for them
+        asx_launch_inv_cols(P, q, tk, first ? o.r_out : nullptr, (int)g, s, find);
+        if (first && mark(3)) return -1;
+        asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, find);
+        // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
+        asx_launch_refine(P, in, pk, W.seg, (int)g, s, dot_blocks, !spectral, find);
+        if (first && mark(4)) return -1;
+        if (!spectral)
+            asx_launch_pearson(in, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
+        else if constexpr (std::is_same<TIn, float>::value)
+            asx_launch_pearson_spectral_f32(P, in, find, tk, W.spec, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
+        return 0;
+    };
+    const AsxSearch call = search(0);
+    if (pass(call, true)) return -1;
     // a pair whose row is not a window: (0, NaN, -2), the others untouched (top-k: k_topk_step writes it for every entry)
-    if (pr && K == 1) asx_launch_invalid_rows(rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
+    if (call.kind == AsxSearch::ROWS && K == 1) asx_launch_invalid_rows(call.rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
     // a pool pair with an index outside its pool: (0, NaN, -4), which takes precedence over -2
     if (pl) asx_launch_invalid_pairs(pl, y.lag, y.coef, y.ret, (int)g, s);
-    // Passes 2..k over the same Q: the inverse columns, finalize, exact re-evaluation and Pearson again, each pair's window minus the
-    // zones around its earlier entries (the records k_topk_step keeps); the transforms are not run again.
+    // Passes 2..k over the same Q; the transforms are not run again.
     for (int j = 0; K > 1 && j < K; j++) {
-        if (j > 0) {
-            asx_launch_inv_cols(P, q, tk, nullptr, (int)g, s, nullptr, nullptr, W.tk.pairs, j); // (pass j + 1: at most j zones)
-            asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, 0, nullptr, W.tk.pairs, W.tk.sink);
-            asx_launch_refine(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, pk, W.seg, (int)g, s, dot_blocks, !spectral, 0, nullptr,
-                              W.tk.pairs);
-            if (!spectral)
-                asx_launch_pearson(x.tsrc, x.tsmp, x.src_step, x.smp_step, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
-            else if constexpr (std::is_same<TIn, float>::value)
-                asx_launch_pearson_spectral_f32(P, x.tsrc, x.src_step, x.tsmp, x.smp_step, tk, W.spec, W.seg, W.psums, out.lag,
-                                                out.coef, out.ret, (int)g, s, 0, nullptr, W.tk.pairs);
-        }
-        asx_launch_topk_step(W.tk, W.seg, pk, p->win_lo, p->win_hi, pr, P.N, (int)g, j, K, o.topk.sep, y.lag, y.coef, y.ret, s);
+        if (j > 0 && pass(search(j), false)) return -1;
+        asx_launch_topk_step(W.tk, W.seg, pk, call, P.N, (int)g, j, K, o.topk.sep, y.lag, y.coef, y.ret, s);
     }
     if (mark(5)) return -1;
     HIP_TRY(hipGetLastError());
@@ -961,9 +974,7 @@ static int tune_placement(asx_plan *p, const float *d_src, const float *d_smp, s
 {
     // (It allocates, synchronises and frees: never inside a stream capture -- a capturing caller keeps the first set, and the next
     // un-captured batch of >= min(group, 8) pairs tunes.)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
-    if (cap != hipStreamCaptureStatusNone) return 0;
+    if (stream_capturing(s)) return 0;
     p->placement_done = true;
     const AsxDev &P = p->dev;
     asx_plan::Lane &W = p->lanes[0];
@@ -1073,15 +1084,13 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
                                        void *stream)
 {
     if (!p || !d_source || !d_sample || !d_coef) return fail("asx_xcorr_batch_f32_dev: null argument");
-    std::lock_guard<std::mutex> guard(p->lock);
-    DevGuard dg(p->device);
-    if (!dg.ok) return fail("cannot select device %d", p->device);
-    hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
     const size_t N = p->host.N;
     if (p->tune_placement && !p->placement_done && batch >= std::min<size_t>(p->group, 8) && // (lane 0's workspaces; a second lane keeps its own)
-        tune_placement(p, d_source, d_sample, std::min(batch, p->group), s))
+        tune_placement(p, d_source, d_sample, std::min(batch, p->group), c.s))
         return -1;
-    return run_batch(p, { d_source, d_sample, d_source, d_sample, 2 * N, N, 0 }, batch, { d_lag, d_coef, d_ret }, s);
+    return run_batch(p, { d_source, d_sample, d_source, d_sample, 2 * N, N, 0 }, batch, { d_lag, d_coef, d_ret }, c.s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1093,10 +1102,9 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
                          size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, const Results &y, void *stream,
                          const Topk &topk = {})
 {
-    std::lock_guard<std::mutex> guard(p->lock);
-    DevGuard dg(p->device);
-    if (!dg.ok) return fail("cannot select device %d", p->device);
-    hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
     const AsxDev &P = p->dev;
     if (P.rlayout) {
         // k_fwd_cols_r reads every row of a pair's inputs as 16-byte loads from the pair's first frame
@@ -1112,9 +1120,7 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
     if (bc) {
         asx_plan::Bcast &B = p->bslot;
         if (!B.cx) {
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
-            if (cap != hipStreamCaptureStatusNone)
+            if (stream_capturing(s))
                 return fail("%s: the plan's broadcast workspace does not exist yet and cannot be allocated "
                             "during a stream capture; make one call with a stride of 0 outside the capture first", fn);
             asx_plan::Bcast T;
@@ -1175,9 +1181,7 @@ static int ensure_bank(asx_plan *p, const char *fn, size_t nsrc, size_t nsmp, hi
 {
     asx_plan::Bank &B = p->bank;
     if (nsrc <= B.nsrc && nsmp <= B.nsmp) return 0;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
-    if (cap != hipStreamCaptureStatusNone)
+    if (stream_capturing(s))
         return fail("%s: the plan's bank holds %zu x %zu tracks and cannot grow to %zu x %zu during a stream capture; make a call "
                     "with pools at least this large outside the capture first", fn, B.nsrc, B.nsmp, nsrc, nsmp);
     const AsxDev &P = p->dev;
@@ -1211,9 +1215,9 @@ extern "C" int asx_xcorr_pool_f32_dev(asx_plan *p, const float *d_sources, size_
 {
     static const char *fn = "asx_xcorr_pool_f32_dev";
     if (!p || !d_sources || !d_samples || !d_coef || !d_ret) return fail("%s: null argument", fn);
-    std::lock_guard<std::mutex> guard(p->lock);
-    DevGuard dg(p->device);
-    if (!dg.ok) return fail("cannot select device %d", p->device);
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
     const AsxDev &P = p->dev;
     if (P.rlayout != 1) return fail("%s: pool calls need a real-column plan (asx_plan_layout() == 1)", fn);
     if (((uintptr_t)d_sources & 15u) || ((uintptr_t)d_samples & 15u))
@@ -1225,7 +1229,6 @@ extern "C" int asx_xcorr_pool_f32_dev(asx_plan *p, const float *d_sources, size_
         return fail("%s: without pairs the batch is every combination, %zu x %zu, not %zu", fn, nsources, nsamples, batch);
     if (batch == 0) return 0;
     if (nsources == 0 || nsamples == 0) return fail("%s: an empty pool (%zu sources, %zu samples) for %zu pairs", fn, nsources, nsamples, batch);
-    hipStream_t s = stream ? (hipStream_t)stream : p->stream;
     if (ensure_bank(p, fn, nsources, nsamples, s)) return -1;
     // the bank fill: every track's forward column pass, once per call, on the caller's stream before any lane forks (grid.z: at most
     // 65535 tracks per launch)
@@ -1267,19 +1270,17 @@ extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const f
                                      void *stream)
 {
     if (!p || !d_source || !d_sample || !d_coef || !d_r) return fail("asx_xcorr_debug_r_dev: null argument");
-    std::lock_guard<std::mutex> guard(p->lock);
-    DevGuard dg(p->device);
-    if (!dg.ok) return fail("cannot select device %d", p->device);
-    hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
     prof_begin_call(p);
     // like every other entry point: listed and looked at again in the exact mode, only marked (ret = 1) otherwise
     // (the direct Pearson form: this entry point exists to compare decompositions and to dump r)
     const size_t N = p->host.N;
     const Pairs<float> x{ d_source, d_sample, d_source, d_sample, 2 * N, N, 0 };
     const Results y{ d_lag, d_coef, d_ret };
-    int rc = run_group(p, x, 1, y, s, { .listed = p->exact, .spectral = false, .r_out = d_r });
+    int rc = run_group(p, x, 1, y, c.s, { .listed = p->exact, .spectral = false, .r_out = d_r });
     prof_end_call(p, 1);
-    if (rc == 0 && p->exact && resolve_overflows(p, x, y, s) < 0) rc = -1;
+    if (rc == 0 && p->exact && resolve_overflows(p, x, y, c.s) < 0) rc = -1;
     return rc;
 }
 
@@ -1297,12 +1298,11 @@ extern "C" int asx_xcorr_batch_f32(asx_plan *p, const float *source, const float
                                    int64_t *lag, double *coef, int32_t *ret)
 {
     if (!p || !source || !sample || !lag || !coef || !ret) return fail("asx_xcorr_batch_f32: null argument");
-    std::lock_guard<std::mutex> guard(p->lock);
-    DevGuard dg(p->device);
-    if (!dg.ok) return fail("cannot select device %d", p->device);
+    PlanCall c(p);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
     if (ensure_staging(p)) return -1;
     const size_t N = p->host.N;
-    hipStream_t s = p->stream;
+    hipStream_t s = c.s;
     const Pairs<float> x{ p->st_src, p->st_smp, p->st_src, p->st_smp, 2 * N, N, 0 };
     const Results d{ p->st_lag, p->st_coef, p->st_ret };
     prof_begin_call(p);
@@ -1566,15 +1566,14 @@ extern "C" int asx_xcorr_f64(asx_plan *p, const double *source, const double *sa
                              double *coefficient)
 {
     if (!p || !source || !sample || !lag || !coefficient) return fail("asx_xcorr_f64: null argument");
-    std::lock_guard<std::mutex> guard(p->lock);
-    DevGuard dg(p->device);
-    if (!dg.ok) return fail("cannot select device %d", p->device);
+    PlanCall c(p);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
     if (ensure_staging(p)) return -1;
     const size_t N = p->host.N;
     if (!p->st_src64) {
         if (dev_alloc(p, &p->st_src64, 2 * N) || dev_alloc(p, &p->st_smp64, N)) return -1;
     }
-    hipStream_t s = p->stream;
+    hipStream_t s = c.s;
     prof_begin_call(p);
     // What ffmpeg decodes from 16-bit or float audio is exactly representable in float32 (src/capture/linux_capture.c:370
     // asks for f64le all the same): then 4 bytes per frame cross PCIe, and the float64 passes (exact re-evaluation, Pearson)
@@ -1674,7 +1673,7 @@ extern "C" int asx_pearson_f64(const double *a, const double *b, size_t n, int d
     HIP_TRY(hipMemcpyAsync(S.a, a, n * sizeof(double), hipMemcpyHostToDevice, S.stream));
     HIP_TRY(hipMemcpyAsync(S.b, b, n * sizeof(double), hipMemcpyHostToDevice, S.stream));
     HIP_TRY(hipMemcpyAsync(S.seg, &seg, sizeof(seg), hipMemcpyHostToDevice, S.stream));
-    asx_launch_pearson(S.a, S.b, 0, 0, (uint32_t)n, S.seg, S.ps, nullptr, S.c, nullptr, 1, S.stream);
+    asx_launch_pearson(AsxInputs<double>{ S.a, S.b, 0, 0, nullptr }, (uint32_t)n, S.seg, S.ps, nullptr, S.c, nullptr, 1, S.stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, S.c, sizeof(double), hipMemcpyDeviceToHost, S.stream));
     HIP_TRY(hipStreamSynchronize(S.stream));
@@ -1825,10 +1824,8 @@ extern "C" int asx_stream_xcorr(asx_stream *st, size_t sample_len, long *lag, do
         if (!p) return -1;
         st->plans.push_back(p);
     }
-    std::lock_guard<std::mutex> pguard(p->lock);
-    DevGuard dg(st->device);
-    if (!dg.ok) return fail("cannot select device %d", st->device);
-    hipStream_t s = p->stream;
+    PlanCall c(p); // (the plan was made on the stream's device)
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
     // the stream's window on this prefix length (both ends clamped to [-n, n-1]: lo <= hi stays true)
     const int64_t n = (int64_t)sample_len;
     p->win_lo = std::min(std::max(st->win_lo, -n), n - 1);
@@ -1839,7 +1836,7 @@ extern "C" int asx_stream_xcorr(asx_stream *st, size_t sample_len, long *lag, do
     int32_t h_ret = -1;
     const Pairs<double> x{ st->src32, st->smp32, st->src64, st->smp64, 2 * sample_len, sample_len, 0 };
     const Results d{ st->d_lag, st->d_coef, st->d_ret };
-    if (run_group(p, x, 1, d, s) || fetch_results(p, x, 1, d, { &h_lag, &h_coef, &h_ret }, s)) return -1;
+    if (run_group(p, x, 1, d, c.s) || fetch_results(p, x, 1, d, { &h_lag, &h_coef, &h_ret }, c.s)) return -1;
     *lag = (long)h_lag;
     *coefficient = h_coef;
     return h_ret;
@@ -1961,13 +1958,12 @@ extern "C" int asx_memcpy_d2h(void *dst, const void *src, size_t bytes)
 
 extern "C" int asx_stream_sync(asx_plan *p, void *stream)
 {
-    hipStream_t s = stream ? (hipStream_t)stream : (p ? p->stream : nullptr);
-    if (p) {
-        DevGuard dg(p->device);
-        HIP_TRY(hipStreamSynchronize(s));
+    if (!p) {
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
         return 0;
     }
-    HIP_TRY(hipStreamSynchronize(s));
+    PlanCall c(p, stream, false);
+    HIP_TRY(hipStreamSynchronize(c.s));
     return 0;
 }
 

@@ -203,6 +203,37 @@ struct AsxTopkWs {
     unsigned long long *sink;    // [1] where k_finalize_x counts the later overflows of a pair already counted in this call
 };
 
+// Which lags compete for pair i of a group, and what seeds its running maximum: the host's one statement of that choice.  Host only,
+// never a kernel argument: the launcher of each kernel family switches on `kind` and hands its flavour what that flavour takes.
+//   ALL     every lag, seed 0 (k_inv_cols_r, k_finalize, ...).  The plan's full window is this: it launches exactly the kernels of
+//           a plan that never had one.
+//   WINDOW  the plan's window (asx_plan_set_lag_window), by value, the seed inside it (k_inv_cols_rw / k_inv_cols_w; k_finalize,
+//           k_refine_pick and k_pearson_prep take the seed)
+//   ROWS    per-pair windows, which replace the plan's: each pair's row and seed from device memory (the _p kernels)
+//   TOPK    a top-k pass >= 2, which replaces both: each pair's window, seed and zones from its record (the _x kernels)
+struct AsxSearch {
+    enum Kind { ALL, WINDOW, ROWS, TOPK } kind;
+    int64_t lo, hi;              // the plan's window in lags ...
+    AsxWin win;                  // ... and as indices
+    AsxWinRows rows;             // the call's per-pair windows (rows.rows null: none)
+    const AsxTopkPair *tk;       // TOPK: the group's records,
+    int tk_zones;                //   the most zones one of them holds in this pass (asx_tk_zone_cap picks the inverse kernel by it)
+    unsigned long long *tk_sink; //   and AsxTopkWs::sink
+    // the index an empty running maximum stands for, and the one whose exact value competes signed -- where a kernel takes it by
+    // value (the ROWS and TOPK kernels read each pair's own)
+    uint32_t seed() const { return kind == WINDOW ? win.seed : 0u; }
+    // pass 0: the call's own search (the strided / windowed call's; what k_topk_step starts the records from); pass j >= 1 of a
+    // top-k call: the records of lane workspace T, which by then hold at most j zones
+    static AsxSearch of(int64_t lo, int64_t hi, uint32_t N, const int64_t *rows, size_t rows_step, const AsxTopkWs &T, int pass)
+    {
+        AsxSearch q{ ALL, lo, hi, asx_win_of(lo, hi, N), { rows, rows_step }, nullptr, 0, nullptr };
+        if (pass > 0) { q.kind = TOPK; q.tk = T.pairs; q.tk_zones = pass; q.tk_sink = T.sink; }
+        else if (rows) q.kind = ROWS;
+        else if (lo != -(int64_t)N || hi != (int64_t)N - 1) q.kind = WINDOW;
+        return q;
+    }
+};
+
 // Pool calls (asx_xcorr_pool_f32_dev): pair i of a call is source a_i of one pool against sample b_i of another.  Every track of both
 // pools has its forward column pass in the plan's bank (written once per call); k_pool_resolve (rlayout.hip) turns each pair of a launch
 // group into one of these records in the lane's workspace, and the listed kernels (k_rows_rl, k_refine_dots_l, k_pearson_partial_l,
@@ -224,6 +255,15 @@ struct AsxPoolArgs {
     uint64_t nsrc, nsmp, src_stride, smp_stride;
     const float *nrm;
     const float2 *band;
+};
+
+// Where pair i's inputs are, for the exact passes over float or double inputs: src + i * src_pitch and smp + i * smp_pitch (elements;
+// 0 = one track for every pair), or, in a pool call (pl not null, float inputs only), src + pl[i].src_off and smp + pl[i].smp_off
+// (the listed kernels).  Host only: the launchers unpack it.
+template <typename TIn> struct AsxInputs {
+    const TIn *src, *smp;
+    size_t src_pitch, smp_pitch;
+    const AsxPoolPair *pl;
 };
 
 // kernel launchers (defined in xcorr_kernels.hip, called from asx_api.hip)
@@ -286,22 +326,17 @@ void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, fl
                          float2 *zya, const AsxPeakWs &W, int npairs, hipStream_t s);
 void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga,
                      const AsxPeakWs &W, int npairs, hipStream_t s);
-// tk (a top-k pass >= 2: each pair's window and zones from its record) takes precedence over rows (per-pair windows), rows over
-// win (the plan's)
-void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out,
-                         int npairs, hipStream_t s, const AsxWin *win = nullptr, const AsxWinRows *rows = nullptr,
-                         const AsxTopkPair *tk = nullptr, int tk_zones = 0);
+// q: which flavour of the inverse column kernel runs (AsxSearch)
+void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
+                         const AsxSearch &q);
 // rlayout.hip: the real-column decomposition (production lengths); false = no kernel compiled in for this plan.
 // bc (the broadcast forms of asx_xcorr_strided_f32_dev): bit 0 = cx is the plan's broadcast slot (one C for every pair), bit 1 = cy is
 bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
                        hipStream_t s);
 bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
                            float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s);
-// win: null = every lag competes (k_inv_cols_r); else the lag-window form (k_inv_cols_rw); rows: the per-pair form (k_inv_cols_rp)
-// tk: the top-k form (k_inv_cols_rx), for a pass whose records hold at most tk_zones zones
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
-                           const AsxWin *win = nullptr, const AsxWinRows *rows = nullptr, const AsxTopkPair *tk = nullptr,
-                           int tk_zones = 0);
+                           const AsxSearch &search);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 // pool calls: each pair's record (out) and its two slots' norm partials and band sums (band may be null) into the group's places
@@ -314,40 +349,29 @@ bool asx_launch_rows_rl(const AsxDev &P, const float2 *cx, const float2 *cy, flo
 void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 bool asx_rlayout_available(const AsxDev &P); // all three kernels compiled in for this plan's schedules
 int asx_rlayout_band_rows(const AsxDev &P);
-// seed (the lag window's, AsxWin): the index an empty running maximum stands for, and the one whose exact value competes signed;
-// rows (per-pair windows): each pair's own seed, from its row (k_finalize_p, k_refine_pick_p, k_pearson_prep_p)
-// tk (a top-k pass >= 2): each pair's seed from its record (k_finalize_x, k_refine_pick_x, k_pearson_prep_x); tk_sink: see AsxTopkWs
-void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base = 0,
-                         uint32_t seed = 0, const AsxWinRows *rows = nullptr, const AsxTopkPair *tk = nullptr,
-                         unsigned long long *tk_sink = nullptr);
+void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,
+                         const AsxSearch &q);
 // behind the Pearson kernels of pass j of a top-k group: entry j of the caller's arrays (entry stride k) from the pass's results,
-// then pass j + 1's records (win_lo / win_hi: the plan's window, used when rows is null)
-void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, int64_t win_lo, int64_t win_hi, const AsxWinRows *rows,
-                          uint32_t N, int npairs, int j, int k, int64_t sep, int64_t *lag, double *coef, int32_t *ret, hipStream_t s);
+// then pass j + 1's records (call: the call's own search, pass 0's -- the plan's window, used when it has no rows)
+void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, const AsxSearch &call, uint32_t N, int npairs, int j,
+                          int k, int64_t sep, int64_t *lag, double *coef, int32_t *ret, hipStream_t s);
 // behind the Pearson kernels of a group with per-pair windows: (lag, coef, ret) = (0, NaN, -2) for every pair whose row is invalid
 void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
-// The exact passes over float or double inputs (instances for both next to the kernels, xcorr_kernels.hip).  The pairs' inputs
-// are src_pitch / smp_pitch elements apart (0 = one track for every pair); pl (pool calls, float inputs only): pair i's inputs are
-// src + pl[i].src_off and smp + pl[i].smp_off instead (the listed kernels).
+// The exact passes over float or double inputs (instances for both next to the kernels, xcorr_kernels.hip).
 // refine: pick = false: the exact values only; the caller's next kernel applies the rule (k_pearson_prep)
 template <typename TIn>
-void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
-                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed = 0,
-                       const AsxWinRows *rows = nullptr, const AsxTopkPair *tk = nullptr, const AsxPoolPair *pl = nullptr);
+void asx_launch_refine(const AsxDev &P, const AsxInputs<TIn> &in, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s,
+                       int dot_blocks, bool pick, const AsxSearch &q);
 template <typename TIn>
-void asx_launch_pearson(const TIn *src, const TIn *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len, const AsxSeg *seg,
-                        double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s,
-                        const AsxPoolPair *pl = nullptr);
+void asx_launch_pearson(const AsxInputs<TIn> &in, uint32_t basis_len, const AsxSeg *seg, double *psums, int64_t *lag, double *coef,
+                        int32_t *ret, int npairs, hipStream_t s);
 // the partial-sum kernel alone (the spectral form runs it on its own segment list, pearson_spectral.hip)
-void asx_launch_pearson_partial_spec_f32(const float *src, const float *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len,
-                                         const AsxSeg *seg, const AsxSpecWs &S, double *psums, int npairs, hipStream_t s,
-                                         const AsxPoolPair *pl = nullptr);
-// pearson_spectral.hip: float32 inputs src_pitch / smp_pitch floats apart, real-column plans (W.band and W.tile_peak filled by this
-// group's transform kernels)
-void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
-                                     const AsxPeakWs &W, const AsxSpecWs &S, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
-                                     int32_t *ret, int npairs, hipStream_t s, uint32_t seed = 0, const AsxWinRows *rows = nullptr,
-                                     const AsxTopkPair *tk = nullptr, const AsxPoolPair *pl = nullptr);
+void asx_launch_pearson_partial_spec_f32(const AsxInputs<float> &in, uint32_t basis_len, const AsxSeg *seg, const AsxSpecWs &S,
+                                         double *psums, int npairs, hipStream_t s);
+// pearson_spectral.hip: float32 inputs, real-column plans (W.band and W.tile_peak filled by this group's transform kernels)
+void asx_launch_pearson_spectral_f32(const AsxDev &P, const AsxInputs<float> &in, const AsxSearch &q, const AsxPeakWs &W,
+                                     const AsxSpecWs &S, AsxSeg *seg, double *psums, int64_t *lag, double *coef, int32_t *ret,
+                                     int npairs, hipStream_t s);
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
                               double min_confidence, double sample_rate, int64_t *lag_ms, int32_t *accept,
                               hipStream_t s);

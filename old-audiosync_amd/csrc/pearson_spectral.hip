@@ -232,50 +232,37 @@ __global__ __launch_bounds__(64) void k_pearson_final_spec(const AsxSeg *__restr
     }
 }
 
-void asx_launch_pearson_spectral_f32(const AsxDev &P, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
-                                     const AsxPeakWs &W, const AsxSpecWs &S0, AsxSeg *seg, double *psums, int64_t *lag, double *coef,
-                                     int32_t *ret, int npairs, hipStream_t s, uint32_t seed, const AsxWinRows *rows,
-                                     const AsxTopkPair *tk, const AsxPoolPair *pl)
+// the prep kernel of the group's inputs (listed: the plan's seed or the pairs' rows) and search, NB blocks of NTP threads per pair
+template <int NTP, int NB>
+static void launch_prep(const AsxDev &P, const AsxInputs<float> &in, const AsxSearch &q, const AsxPeakWs &W, const AsxSpecWs &S,
+                        AsxSeg *seg, int npairs, hipStream_t s)
+{
+    const dim3 grid(NB, npairs), block(NTP);
+    if (in.pl && q.kind == AsxSearch::ROWS)
+        hipLaunchKernelGGL((k_pearson_prep_pl<NTP, NB>), grid, block, 0, s, P.self_dev, in.src, in.smp, in.pl, W, S, seg, q.rows);
+    else if (in.pl)
+        hipLaunchKernelGGL((k_pearson_prep_l<NTP, NB>), grid, block, 0, s, P.self_dev, in.src, in.smp, in.pl, W, S, seg, q.seed());
+    else if (q.kind == AsxSearch::TOPK)
+        hipLaunchKernelGGL((k_pearson_prep_x<NTP, NB>), grid, block, 0, s, P.self_dev, in.src, in.smp, in.src_pitch, in.smp_pitch, W, S,
+                           seg, q.tk);
+    else if (q.kind == AsxSearch::ROWS)
+        hipLaunchKernelGGL((k_pearson_prep_p<NTP, NB>), grid, block, 0, s, P.self_dev, in.src, in.smp, in.src_pitch, in.smp_pitch, W, S,
+                           seg, q.rows);
+    else
+        hipLaunchKernelGGL((k_pearson_prep<NTP, NB>), grid, block, 0, s, P.self_dev, in.src, in.smp, in.src_pitch, in.smp_pitch, W, S,
+                           seg, q.seed());
+}
+
+void asx_launch_pearson_spectral_f32(const AsxDev &P, const AsxInputs<float> &in, const AsxSearch &q, const AsxPeakWs &W,
+                                     const AsxSpecWs &S0, AsxSeg *seg, double *psums, int64_t *lag, double *coef, int32_t *ret,
+                                     int npairs, hipStream_t s)
 {
     AsxSpecWs S = S0;
     S.N = P.N;
-    if (pl) {
-        // (pool calls: no top-k; per-pair windows or the plan's seed)
-        S.nb = (size_t)P.band_rows * (size_t)P.M2 >= 16384 ? ASX_PREP_BLOCKS : 1;
-        if (rows && S.nb > 1)
-            hipLaunchKernelGGL((k_pearson_prep_pl<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS),
-                               0, s, P.self_dev, src, smp, pl, W, S, seg, *rows);
-        else if (rows)
-            hipLaunchKernelGGL((k_pearson_prep_pl<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, pl, W, S, seg, *rows);
-        else if (S.nb > 1)
-            hipLaunchKernelGGL((k_pearson_prep_l<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS),
-                               0, s, P.self_dev, src, smp, pl, W, S, seg, seed);
-        else
-            hipLaunchKernelGGL((k_pearson_prep_l<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, pl, W, S, seg, seed);
-    } else if (tk) {
-        S.nb = (size_t)P.band_rows * (size_t)P.M2 >= 16384 ? ASX_PREP_BLOCKS : 1;
-        if (S.nb > 1)
-            hipLaunchKernelGGL((k_pearson_prep_x<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0,
-                               s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg, tk);
-        else
-            hipLaunchKernelGGL((k_pearson_prep_x<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S,
-                               seg, tk);
-    } else if (rows) {
-        S.nb = (size_t)P.band_rows * (size_t)P.M2 >= 16384 ? ASX_PREP_BLOCKS : 1;
-        if (S.nb > 1)
-            hipLaunchKernelGGL((k_pearson_prep_p<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0,
-                               s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg, *rows);
-        else
-            hipLaunchKernelGGL((k_pearson_prep_p<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S,
-                               seg, *rows);
-    } else if ((size_t)P.band_rows * (size_t)P.M2 >= 16384) {
-        S.nb = ASX_PREP_BLOCKS;
-        hipLaunchKernelGGL((k_pearson_prep<ASX_PREP_THREADS, ASX_PREP_BLOCKS>), dim3(ASX_PREP_BLOCKS, npairs), dim3(ASX_PREP_THREADS), 0, s,
-                           P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg, seed);
-    } else {
-        S.nb = 1;
-        hipLaunchKernelGGL((k_pearson_prep<256, 1>), dim3(1, npairs), dim3(256), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W, S, seg, seed);
-    }
-    asx_launch_pearson_partial_spec_f32(src, smp, src_pitch, smp_pitch, P.N, seg, S, psums, npairs, s, pl);
+    const bool long_tracks = (size_t)P.band_rows * (size_t)P.M2 >= 16384;
+    S.nb = long_tracks ? ASX_PREP_BLOCKS : 1;
+    if (long_tracks) launch_prep<ASX_PREP_THREADS, ASX_PREP_BLOCKS>(P, in, q, W, S, seg, npairs, s);
+    else launch_prep<256, 1>(P, in, q, W, S, seg, npairs, s);
+    asx_launch_pearson_partial_spec_f32(in, P.N, seg, S, psums, npairs, s);
     hipLaunchKernelGGL(k_pearson_final_spec, dim3(npairs), dim3(64), 0, s, seg, psums, asx_pearson_blocks(P.N), S, lag, coef, ret);
 }

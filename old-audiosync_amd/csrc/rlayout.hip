@@ -942,48 +942,39 @@ void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sban
                        P.ntiles, P.nbands, which);
 }
 
+// one flavour of k_inv_cols_r, with the flavour's extra argument (none: every lag competes)
+template <class K, class... X>
+static void launch_inv_r(K kernel, const AsxDev &P, dim3 grid, int nt, size_t lds, hipStream_t s, const float2 *q, const AsxPeakWs &W,
+                         float *r_out, X... extra)
+{
+    const void *fn = (const void *)kernel;
+    allow_big_lds_r(fn, lds);
+    hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, s, rargs_of(P), q, ((size_t)P.M1 + 1) * (size_t)P.M2, W, r_out,
+                       resident_blocks(fn, nt, lds), extra...);
+}
+
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
-                           const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk, int tk_zones)
+                           const AsxSearch &search)
 {
     if (!P.col_pairs) return false;
-    const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2;
-#define ASX_RX(zc, m1, t, nt, ...)                                                                                          \
-    {                                                                                                                       \
-        const void *fx = (const void *)k_inv_cols_rx<Sched<m1, __VA_ARGS__>, t, nt, zc>;                                    \
-        allow_big_lds_r(fx, lds);                                                                                           \
-        hipLaunchKernelGGL((k_inv_cols_rx<Sched<m1, __VA_ARGS__>, t, nt, zc>), grid, dim3(nt), lds, s, rargs_of(P), q, pitch, W, \
-                           r_out, resident_blocks(fx, nt, lds), tk);                                                        \
-    }
+#define ASX_RX(zc, m1, t, nt, ...) \
+    launch_inv_r(k_inv_cols_rx<Sched<m1, __VA_ARGS__>, t, nt, zc>, P, grid, nt, lds, s, q, W, r_out, search.tk)
 #define ASX_TRY(m1, t, nt, ...)                                                                                             \
-    if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                               \
+    if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                                                          \
         const size_t lds = (size_t)(m1) * (t) * sizeof(float2);                                                             \
         const dim3 grid(npairs, rcol_grid_x(P.M2 / (t), asx_ilog2(t)));                                                     \
-        if (tk) {                                                                                                           \
-            switch (asx_tk_zone_cap(tk_zones)) {                                                                            \
-            case 1: ASX_RX(1, m1, t, nt, __VA_ARGS__) break;                                                                \
-            case 3: ASX_RX(3, m1, t, nt, __VA_ARGS__) break;                                                                \
-            default: ASX_RX(ASX_TOPK_MAX - 1, m1, t, nt, __VA_ARGS__) break;                                                \
+        if (search.kind == AsxSearch::TOPK)                                                                                 \
+            switch (asx_tk_zone_cap(search.tk_zones)) {                                                                     \
+            case 1: ASX_RX(1, m1, t, nt, __VA_ARGS__); break;                                                               \
+            case 3: ASX_RX(3, m1, t, nt, __VA_ARGS__); break;                                                               \
+            default: ASX_RX(ASX_TOPK_MAX - 1, m1, t, nt, __VA_ARGS__);                                                      \
             }                                                                                                               \
-            return true;                                                                                                    \
-        }                                                                                                                   \
-        if (rows) {                                                                                                         \
-            const void *fp = (const void *)k_inv_cols_rp<Sched<m1, __VA_ARGS__>, t, nt>;                                    \
-            allow_big_lds_r(fp, lds);                                                                                       \
-            hipLaunchKernelGGL((k_inv_cols_rp<Sched<m1, __VA_ARGS__>, t, nt>), grid, dim3(nt), lds, s, rargs_of(P), q, pitch, W, \
-                               r_out, resident_blocks(fp, nt, lds), *rows);                                                 \
-            return true;                                                                                                    \
-        }                                                                                                                   \
-        if (win) {                                                                                                          \
-            const void *fw = (const void *)k_inv_cols_rw<Sched<m1, __VA_ARGS__>, t, nt>;                                    \
-            allow_big_lds_r(fw, lds);                                                                                       \
-            hipLaunchKernelGGL((k_inv_cols_rw<Sched<m1, __VA_ARGS__>, t, nt>), grid, dim3(nt), lds, s, rargs_of(P), q, pitch, W, \
-                               r_out, resident_blocks(fw, nt, lds), *win);                                                  \
-            return true;                                                                                                    \
-        }                                                                                                                   \
-        const void *fn = (const void *)k_inv_cols_r<Sched<m1, __VA_ARGS__>, t, nt>;                                         \
-        allow_big_lds_r(fn, lds);                                                                                           \
-        hipLaunchKernelGGL((k_inv_cols_r<Sched<m1, __VA_ARGS__>, t, nt>), grid, dim3(nt), lds, s, rargs_of(P), q, pitch, W, r_out, \
-                           resident_blocks(fn, nt, lds));                                                                   \
+        else if (search.kind == AsxSearch::ROWS)                                                                            \
+            launch_inv_r(k_inv_cols_rp<Sched<m1, __VA_ARGS__>, t, nt>, P, grid, nt, lds, s, q, W, r_out, search.rows);      \
+        else if (search.kind == AsxSearch::WINDOW)                                                                          \
+            launch_inv_r(k_inv_cols_rw<Sched<m1, __VA_ARGS__>, t, nt>, P, grid, nt, lds, s, q, W, r_out, search.win);       \
+        else                                                                                                                \
+            launch_inv_r(k_inv_cols_r<Sched<m1, __VA_ARGS__>, t, nt>, P, grid, nt, lds, s, q, W, r_out);                    \
         return true;                                                                                                        \
     }
     ASX_RCOLS(ASX_TRY)

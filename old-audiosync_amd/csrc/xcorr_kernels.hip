@@ -1057,9 +1057,9 @@ bool asx_launch_rows_static(const AsxDev &P, const float2 *zxa, const float2 *zy
 void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga, const AsxPeakWs &W,
                              int npairs, hipStream_t s);
 bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                hipStream_t s, const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk);
+                                hipStream_t s, const AsxSearch &q);
 void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                 hipStream_t s, const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk);
+                                 hipStream_t s, const AsxSearch &q);
 
 #define ASX_FWD_LAUNCH(...) \
     do { allow_big_lds((const void *)k_fwd_cols<__VA_ARGS__>, lds_bytes_cols(P)); \
@@ -1121,21 +1121,22 @@ void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *z
 #endif
 #undef ASX_ROWS_LAUNCH
 
+// one flavour of the inverse column kernel, with the flavour's extra argument (none: every lag competes)
+template <class K, class... X>
+static void launch_inv(K kernel, const AsxDev &P, dim3 grid, hipStream_t s, const float2 *ga, const AsxPeakWs &W, float *r_out, X... extra)
+{
+    allow_big_lds((const void *)kernel, lds_bytes_cols(P));
+    hipLaunchKernelGGL(kernel, grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, extra...);
+}
+// (one zone capacity in k_inv_cols_wx: q.tk_zones is not asked)
 #define ASX_INV_LAUNCH(...) \
-    do { if (tk) { allow_big_lds((const void *)k_inv_cols_wx<__VA_ARGS__>, lds_bytes_cols(P)); \
-                   hipLaunchKernelGGL((k_inv_cols_wx<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, tk); \
-                   break; } \
-         if (rows) { allow_big_lds((const void *)k_inv_cols_wp<__VA_ARGS__>, lds_bytes_cols(P)); \
-                     hipLaunchKernelGGL((k_inv_cols_wp<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, *rows); \
-                     break; } \
-         if (win) { allow_big_lds((const void *)k_inv_cols_w<__VA_ARGS__>, lds_bytes_cols(P)); \
-                    hipLaunchKernelGGL((k_inv_cols_w<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, *win); \
-                    break; } \
-         allow_big_lds((const void *)k_inv_cols<__VA_ARGS__>, lds_bytes_cols(P)); \
-         hipLaunchKernelGGL((k_inv_cols<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out); } while (0)
+    do { if (q.kind == AsxSearch::TOPK) launch_inv(k_inv_cols_wx<__VA_ARGS__>, P, grid, s, ga, W, r_out, q.tk); \
+         else if (q.kind == AsxSearch::ROWS) launch_inv(k_inv_cols_wp<__VA_ARGS__>, P, grid, s, ga, W, r_out, q.rows); \
+         else if (q.kind == AsxSearch::WINDOW) launch_inv(k_inv_cols_w<__VA_ARGS__>, P, grid, s, ga, W, r_out, q.win); \
+         else launch_inv(k_inv_cols<__VA_ARGS__>, P, grid, s, ga, W, r_out); } while (0)
 #if ASX_HAS_PART(16)
 bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                hipStream_t s, const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk)
+                                hipStream_t s, const AsxSearch &q)
 {
     dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
 #define ASX_TRY_STATIC(m1, t, nt, maxr, ...) \
@@ -1147,7 +1148,7 @@ bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeak
 #endif
 #if ASX_HAS_PART(32)
 void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                 hipStream_t s, const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk)
+                                 hipStream_t s, const AsxSearch &q)
 {
     dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
     const int mr = max_radix(P.st1);
@@ -1210,27 +1211,28 @@ void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, floa
         asx_launch_rows_generic(P, zxa, zya, ga, W, npairs, s);
 }
 
-void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                         hipStream_t s, const AsxWin *win, const AsxWinRows *rows, const AsxTopkPair *tk, int tk_zones)
+void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
+                         const AsxSearch &q)
 {
-    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s, win, rows, tk, tk_zones)) return;
-    if (generic_only() || !asx_launch_inv_cols_static(P, ga, W, r_out, npairs, s, win, rows, tk))
-        asx_launch_inv_cols_generic(P, ga, W, r_out, npairs, s, win, rows, tk);
+    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s, q)) return;
+    if (generic_only() || !asx_launch_inv_cols_static(P, ga, W, r_out, npairs, s, q))
+        asx_launch_inv_cols_generic(P, ga, W, r_out, npairs, s, q);
 }
 
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,
-                         uint32_t seed, const AsxWinRows *rows, const AsxTopkPair *tk, unsigned long long *tk_sink)
+                         const AsxSearch &q)
 {
-    if (tk) hipLaunchKernelGGL(k_finalize_x, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, tk, tk_sink);
-    else if (rows) hipLaunchKernelGGL(k_finalize_p, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, *rows);
-    else hipLaunchKernelGGL(k_finalize, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, pair_base, seed);
+    const dim3 grid(npairs), block(ASX_THREADS);
+    if (q.kind == AsxSearch::TOPK) hipLaunchKernelGGL(k_finalize_x, grid, block, 0, s, P.self_dev, W, seg, pair_base, q.tk, q.tk_sink);
+    else if (q.kind == AsxSearch::ROWS) hipLaunchKernelGGL(k_finalize_p, grid, block, 0, s, P.self_dev, W, seg, pair_base, q.rows);
+    else hipLaunchKernelGGL(k_finalize, grid, block, 0, s, P.self_dev, W, seg, pair_base, q.seed());
 }
 
-void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, int64_t win_lo, int64_t win_hi, const AsxWinRows *rows,
-                          uint32_t N, int npairs, int j, int k, int64_t sep, int64_t *lag, double *coef, int32_t *ret, hipStream_t s)
+void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, const AsxSearch &call, uint32_t N, int npairs, int j,
+                          int k, int64_t sep, int64_t *lag, double *coef, int32_t *ret, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_topk_step, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, T, seg, W, win_lo, win_hi,
-                       rows ? *rows : AsxWinRows{ nullptr, 0 }, N, npairs, j, k, sep, lag, coef, ret);
+    hipLaunchKernelGGL(k_topk_step, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, T, seg, W, call.lo, call.hi,
+                       call.rows, N, npairs, j, k, sep, lag, coef, ret);
 }
 
 void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
@@ -1244,23 +1246,28 @@ void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, d
                        coef, ret);
 }
 
-template <typename TIn>
-void asx_launch_refine(const AsxDev &P, const TIn *src, size_t src_pitch, const TIn *smp, size_t smp_pitch, const AsxPeakWs &W,
-                       AsxSeg *seg, int npairs, hipStream_t s, int dot_blocks, bool pick, uint32_t seed, const AsxWinRows *rows,
-                       const AsxTopkPair *tk, const AsxPoolPair *pl)
+// The strided / listed choice of the exact passes: go(kernel, where pair i's inputs are...) with the strided kernel and the two
+// pitches, or (pool calls, float inputs only) the listed kernel and the pairs' records.
+template <typename TIn, class KS, class KL, class F> static void launch_by_inputs(const AsxInputs<TIn> &in, KS strided, KL listed, F go)
 {
     if constexpr (std::is_same<TIn, float>::value) {
-        if (pl)
-            hipLaunchKernelGGL(k_refine_dots_l, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, pl, W);
-        else
-            hipLaunchKernelGGL(k_refine_dots<TIn>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch,
-                               smp_pitch, W);
-    } else {
-        hipLaunchKernelGGL(k_refine_dots<TIn>, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, src, smp, src_pitch, smp_pitch, W);
+        if (in.pl) return go(listed, in.pl);
     }
-    if (pick && tk) hipLaunchKernelGGL(k_refine_pick_x, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, tk);
-    else if (pick && rows) hipLaunchKernelGGL(k_refine_pick_p, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, *rows);
-    else if (pick) hipLaunchKernelGGL(k_refine_pick, dim3(npairs), dim3(ASX_THREADS), 0, s, P.self_dev, W, seg, seed);
+    go(strided, in.src_pitch, in.smp_pitch);
+}
+
+template <typename TIn>
+void asx_launch_refine(const AsxDev &P, const AsxInputs<TIn> &in, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s,
+                       int dot_blocks, bool pick, const AsxSearch &q)
+{
+    launch_by_inputs(in, k_refine_dots<TIn>, k_refine_dots_l, [&](auto kernel, auto... where) {
+        hipLaunchKernelGGL(kernel, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, in.src, in.smp, where..., W);
+    });
+    if (!pick) return;
+    const dim3 grid(npairs), block(ASX_THREADS);
+    if (q.kind == AsxSearch::TOPK) hipLaunchKernelGGL(k_refine_pick_x, grid, block, 0, s, P.self_dev, W, seg, q.tk);
+    else if (q.kind == AsxSearch::ROWS) hipLaunchKernelGGL(k_refine_pick_p, grid, block, 0, s, P.self_dev, W, seg, q.rows);
+    else hipLaunchKernelGGL(k_refine_pick, grid, block, 0, s, P.self_dev, W, seg, q.seed());
 }
 
 // Partial blocks per pair: a function of the segment's BASIS LENGTH ONLY -- one block per 16 sweeps of 256 threads x 4
@@ -1278,35 +1285,29 @@ unsigned asx_pearson_blocks(uint32_t basis_len)
     return nb;
 }
 
-template <typename TIn>
-void asx_launch_pearson(const TIn *src, const TIn *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len, const AsxSeg *seg,
-                        double *psums, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s, const AsxPoolPair *pl)
+// k_pearson_partial / k_pearson_partial_l: SPEC = false with an empty S (the direct form), true with the spectral form's
+template <typename TIn, bool SPEC>
+static void launch_pearson_partial(const AsxInputs<TIn> &in, uint32_t basis_len, const AsxSeg *seg, const AsxSpecWs &S, double *psums,
+                                   int npairs, hipStream_t s)
 {
-    const unsigned nb = asx_pearson_blocks(basis_len);
-    if constexpr (std::is_same<TIn, float>::value) {
-        if (pl)
-            hipLaunchKernelGGL((k_pearson_partial_l<false>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s, src, smp, pl, basis_len, seg, psums,
-                               AsxSpecWs{});
-        else
-            hipLaunchKernelGGL((k_pearson_partial<TIn, false>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
-                               src, smp, src_pitch, smp_pitch, basis_len, seg, psums, AsxSpecWs{});
-    } else {
-        hipLaunchKernelGGL((k_pearson_partial<TIn, false>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
-                           src, smp, src_pitch, smp_pitch, basis_len, seg, psums, AsxSpecWs{});
-    }
-    hipLaunchKernelGGL(k_pearson_final, dim3(npairs), dim3(64), 0, s, seg, psums, nb, lag, coef, ret);
+    launch_by_inputs(in, k_pearson_partial<TIn, SPEC>, k_pearson_partial_l<SPEC>, [&](auto kernel, auto... where) {
+        hipLaunchKernelGGL(kernel, dim3(asx_pearson_blocks(basis_len), npairs), dim3(ASX_THREADS), 0, s, in.src, in.smp, where...,
+                           basis_len, seg, psums, S);
+    });
 }
 
-void asx_launch_pearson_partial_spec_f32(const float *src, const float *smp, size_t src_pitch, size_t smp_pitch, uint32_t basis_len,
-                                         const AsxSeg *seg, const AsxSpecWs &S, double *psums, int npairs, hipStream_t s,
-                                         const AsxPoolPair *pl)
+template <typename TIn>
+void asx_launch_pearson(const AsxInputs<TIn> &in, uint32_t basis_len, const AsxSeg *seg, double *psums, int64_t *lag, double *coef,
+                        int32_t *ret, int npairs, hipStream_t s)
 {
-    const unsigned nb = asx_pearson_blocks(basis_len);
-    if (pl)
-        hipLaunchKernelGGL((k_pearson_partial_l<true>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s, src, smp, pl, basis_len, seg, psums, S);
-    else
-        hipLaunchKernelGGL((k_pearson_partial<float, true>), dim3(nb, npairs), dim3(ASX_THREADS), 0, s,
-                           src, smp, src_pitch, smp_pitch, basis_len, seg, psums, S);
+    launch_pearson_partial<TIn, false>(in, basis_len, seg, AsxSpecWs{}, psums, npairs, s);
+    hipLaunchKernelGGL(k_pearson_final, dim3(npairs), dim3(64), 0, s, seg, psums, asx_pearson_blocks(basis_len), lag, coef, ret);
+}
+
+void asx_launch_pearson_partial_spec_f32(const AsxInputs<float> &in, uint32_t basis_len, const AsxSeg *seg, const AsxSpecWs &S,
+                                         double *psums, int npairs, hipStream_t s)
+{
+    launch_pearson_partial<float, true>(in, basis_len, seg, S, psums, npairs, s);
 }
 
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
@@ -1337,10 +1338,10 @@ void asx_launch_dc_remove(const TIn *src, const TIn *smp, uint32_t N, double sca
 
 // the exact passes' instances (asx_internal.h): float32 and float64 inputs
 #define ASX_EXACT_PASSES(T)                                                                                                             \
-    template void asx_launch_refine<T>(const AsxDev &, const T *, size_t, const T *, size_t, const AsxPeakWs &, AsxSeg *, int,           \
-                                       hipStream_t, int, bool, uint32_t, const AsxWinRows *, const AsxTopkPair *, const AsxPoolPair *); \
-    template void asx_launch_pearson<T>(const T *, const T *, size_t, size_t, uint32_t, const AsxSeg *, double *, int64_t *, double *,   \
-                                        int32_t *, int, hipStream_t, const AsxPoolPair *);                                              \
+    template void asx_launch_refine<T>(const AsxDev &, const AsxInputs<T> &, const AsxPeakWs &, AsxSeg *, int, hipStream_t, int, bool,    \
+                                       const AsxSearch &);                                                                              \
+    template void asx_launch_pearson<T>(const AsxInputs<T> &, uint32_t, const AsxSeg *, double *, int64_t *, double *, int32_t *, int,    \
+                                        hipStream_t);                                                                                   \
     template void asx_launch_dc_remove<T>(const T *, const T *, uint32_t, double, double *, float *, hipStream_t);
 ASX_EXACT_PASSES(float)
 ASX_EXACT_PASSES(double)
