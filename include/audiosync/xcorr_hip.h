@@ -30,10 +30,12 @@
  *   coef[i] are still written, exactly as the reference leaves them).
  *   ret[i] = -2 (asx_xcorr_windowed_f32_dev only): pair i's lag window was not a window
  *   inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.
- *   ret = -3 (asx_xcorr_topk_f32_dev only): no lag is left for this entry of the pair (its
- *   window minus the zones around the earlier entries is empty); lag = 0 and coef = NaN.
- *   ret = -4 (asx_xcorr_pool_f32_dev only): a pair's source or sample index is outside its
- *   pool; lag = 0 and coef = NaN.  It takes precedence over -2.
+ *   ret = -3 (asx_xcorr_topk_f32_dev and asx_xcorr_pool_topk_f32_dev only): no lag is left for
+ *   this entry of the pair (its window minus the zones around the earlier entries is empty);
+ *   lag = 0 and coef = NaN.
+ *   ret = -4 (asx_xcorr_pool_f32_dev and asx_xcorr_pool_topk_f32_dev only): a pair's source or
+ *   sample index is outside its pool; lag = 0 and coef = NaN (the top-k form: in all k entries
+ *   of the pair).  It takes precedence over -2 and -3.
  */
 #ifndef AUDIOSYNC_XCORR_HIP_H
 #define AUDIOSYNC_XCORR_HIP_H
@@ -302,13 +304,48 @@ int asx_xcorr_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_
  * (8 bytes per frame of 2N, roughly).  It is allocated at the first pool call, grown (behind a device
  * synchronisation) when a call names more tracks, and freed with the plan; it is not counted in
  * asx_plan_workspace_bytes.  Growing it during a stream capture fails (-1): make a call with pools at least
- * as large outside the capture first.  Top-k over pools is not offered. */
+ * as large outside the capture first.  asx_xcorr_pool_topk_f32_dev returns the K strongest lags of every pair. */
 int asx_xcorr_pool_f32_dev(asx_plan *plan,
                            const float *d_sources, size_t source_stride, size_t nsources,
                            const float *d_samples, size_t sample_stride, size_t nsamples,
                            const int32_t *d_pairs,
                            const int64_t *d_windows, size_t window_stride,
                            size_t batch, int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream);
+
+/* The K strongest separated lags per pair of two track pools: asx_xcorr_pool_f32_dev's pairs with asx_xcorr_topk_f32_dev's entries.
+ * All-pairs over a pool of clips of one event is where runner-ups matter: choruses and bars repeat in every clip, and the candidates
+ * of each pair let a caller test triangle closure (lag_ab + lag_bc = lag_ac) over more than two clips.
+ *   Everything before `batch` means what it means in asx_xcorr_pool_f32_dev: the pools, strides and aliasing, d_pairs == NULL =
+ * every combination source-major (batch = nsources * nsamples), per-pair window rows or the plan's window (d_windows == NULL), the
+ * layout rule, the stream rule and the bank -- which is filled ONCE per call, whatever k is.  k and min_separation mean what they
+ * mean in asx_xcorr_topk_f32_dev.  Entry j of pair i is at index i*k + j of d_lag, d_coef and d_ret; d_lag may be NULL.
+ *   Per pair it is the top-k call: for a pair whose indices are inside their pools, all k entries (lag, coef, ret) are bit for bit
+ * what asx_xcorr_topk_f32_dev returns for that pair alone on the same plan with the same k, min_separation and window (the pair's
+ * row, or the plan's window) -- in both Pearson settings, in exact and in asynchronous mode (ret = 1 from the overflowing entry on),
+ * -3 once no lag is left and -2 in all k entries for a row that is not a window.  k = 1 launches exactly asx_xcorr_pool_f32_dev:
+ * the same kernels and the same results, counters and second look included.
+ *   A row of d_pairs with an index outside its pool gives (0, NaN, -4) in all k entries of that pair (over -2 and -3), reads nothing
+ * outside the pools and leaves the other pairs untouched; such a pair never overflows and is never listed, counted or repaired.
+ *   Counters: asx_plan_peak_overflows / asx_plan_peak_repairs count a valid pair once per call if any of its passes overflows.
+ * Under the spectral setting asx_plan_pearson_modes grows by batch * k per call (every entry once, in the mode its pass took; the
+ * second look's recomputation is not counted again); under the direct setting it counts nothing.
+ *   Exact mode: a listed pair's row {a, b} is copied back and the pair is redone alone on explicit pointers -- all k entries, lists
+ * that hold every lag, the direct Pearson form -- as the top-k call's second look does.  Asynchronous mode
+ * (asx_plan_set_exact(plan, 0)): with a bank already large enough the call makes no host synchronisation and allocates nothing;
+ * its per-group state lives in workspaces the plan allocated when it was created.
+ *   Returns -1 with the outputs untouched and nothing launched on every refusal of asx_xcorr_pool_f32_dev (a NULL pool, d_coef or
+ * d_ret; an empty pool while batch > 0; not a real-column plan; alignment; strides that are not multiples of 4 floats; d_pairs ==
+ * NULL with batch != nsources * nsamples; a bank that cannot be allocated, or would have to grow during a stream capture) and of
+ * asx_xcorr_topk_f32_dev (k outside 1..ASX_TOPK_MAX, min_separation < 0).  batch == 0 returns 0.
+ *   Cost: the bank fill and each group's row pass once per call; every further entry is one more inverse column pass over the
+ * resident product spectrum plus the tail, as in asx_xcorr_topk_f32_dev. */
+int asx_xcorr_pool_topk_f32_dev(asx_plan *plan,
+                                const float *d_sources, size_t source_stride, size_t nsources,
+                                const float *d_samples, size_t sample_stride, size_t nsamples,
+                                const int32_t *d_pairs,
+                                const int64_t *d_windows, size_t window_stride,
+                                size_t batch, int k, int64_t min_separation,
+                                int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream);
 
 /* The batched variant over several GPUs of one node from ONE process (BASELINE.json north_star; no
  * reference equivalent): plans[i] was created on device i (any devices; all the same sample_len); the
@@ -369,6 +406,19 @@ int asx_pearson_f64(const double *source_seg, const double *sample_seg, size_t n
 int asx_results_to_ms_dev(const int64_t *d_lag, const double *d_coef, const int32_t *d_ret,
                           size_t batch, double min_confidence, double sample_rate,
                           int64_t *d_lag_ms, int32_t *d_accept, void *stream);
+
+/* The entry to keep of each pair of a top-k call (asx_xcorr_topk_f32_dev, asx_xcorr_pool_topk_f32_dev), on the device: runner-ups are
+ * asked for to pick by coefficient.  Per pair i over its entries j = 0..k-1 at index i*k + j: among the entries with ret == 0 the one
+ * with the largest SIGNED coefficient wins (the acceptance above is signed: coef >= min_confidence), the smallest j among equal
+ * coefficients; its (lag, coef, 0) go to index i of d_best_lag / d_best_coef / d_best_ret and j to d_best_entry[i].  When no entry of
+ * the pair has ret == 0 (NaN coefficients, inexact, no lag left, an invalid row or pair), entry 0 is copied as it is and
+ * d_best_entry[i] = 0.  The outputs have the layout asx_results_to_ms_dev takes.
+ * All pointers are device pointers; d_best_lag and d_best_entry may be NULL, the others may not; k outside 1..ASX_TOPK_MAX or a NULL
+ * pointer returns -1 before anything is launched.  Asynchronous on `stream`; allocates nothing. */
+int asx_topk_best_dev(const int64_t *d_lag, const double *d_coef, const int32_t *d_ret,
+                      size_t batch, int k,
+                      int64_t *d_best_lag, double *d_best_coef, int32_t *d_best_ret, int32_t *d_best_entry,
+                      void *stream);
 
 /* ---- growing-window (streaming) mode ------------------------------------ */
 

@@ -712,7 +712,7 @@ template <typename TIn> struct Pairs {
     AsxInputs<TIn> inputs(const AsxPoolPair *pl) const { return { tsrc, tsmp, src_step, smp_step, pl }; }
 };
 
-// Where pair k's results go (lag and ret may be null): entries step apart (asx_xcorr_topk_f32_dev: step = k, entry j of pair i at
+// Where pair k's results go (lag and ret may be null): entries step apart (the top-k calls: step = k, entry j of pair i at
 // i * k + j; every other entry point: 1).
 struct Results {
     int64_t *lag;
@@ -725,7 +725,7 @@ struct Results {
     }
 };
 
-// The top-k option of a call (asx_xcorr_topk_f32_dev): k passes over each group's Q, min_separation between the entries' lags.
+// The top-k option of a call (asx_xcorr_topk_f32_dev, asx_xcorr_pool_topk_f32_dev): k passes over each group's Q, min_separation between the entries' lags.
 // k = 1 is the strided / windowed call itself.
 struct Topk {
     int k = 1;
@@ -816,7 +816,6 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // One pass over the group's Q: the inverse columns, finalize, the exact re-evaluation and Pearson, the lags of `find` competing.
     // first: pass 1, which the profiling marks time and whose r goes to o.r_out.
     auto pass = [&](const AsxSearch &find, bool first) -> int {
-        assert(!(pl && find.kind == AsxSearch::TOPK)); // pool + top-k: there are no listed top-k kernels, and no entry point asks for them
         asx_launch_inv_cols(P, q, tk, first ? o.r_out : nullptr, (int)g, s, find);
         if (first && mark(3)) return -1;
         asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, find);
@@ -834,12 +833,15 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // a pair whose row is not a window: (0, NaN, -2), the others untouched (top-k: k_topk_step writes it for every entry)
     if (call.kind == AsxSearch::ROWS && K == 1) asx_launch_invalid_rows(call.rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
     // a pool pair with an index outside its pool: (0, NaN, -4), which takes precedence over -2
-    if (pl) asx_launch_invalid_pairs(pl, y.lag, y.coef, y.ret, (int)g, s);
-    // Passes 2..k over the same Q; the transforms are not run again.
+    if (pl && K == 1) asx_launch_invalid_pairs(pl, y.lag, y.coef, y.ret, (int)g, s);
+    // Passes 2..k over the same Q; the transforms are not run again.  In a pool group the passes read the pairs' inputs through the
+    // group's records (the listed kernels), and an invalid pair -- whose Q is NaN and whose bound is zero, so that no pass finds or
+    // lists anything for it -- gets (0, NaN, -4) in all k entries behind the last step, over the steps' -2 and -3.
     for (int j = 0; K > 1 && j < K; j++) {
         if (j > 0 && pass(search(j), false)) return -1;
         asx_launch_topk_step(W.tk, W.seg, pk, call, P.N, (int)g, j, K, o.topk.sep, y.lag, y.coef, y.ret, s);
     }
+    if (pl && K > 1) asx_launch_invalid_pairs_k(pl, K, y.lag, y.coef, y.ret, (int)g, s);
     if (mark(5)) return -1;
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1208,13 +1210,13 @@ static int ensure_bank(asx_plan *p, const char *fn, size_t nsrc, size_t nsmp, hi
     return 0;
 }
 
-extern "C" int asx_xcorr_pool_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
-                                      const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
-                                      const int64_t *d_windows, size_t window_stride, size_t batch, int64_t *d_lag, double *d_coef,
-                                      int32_t *d_ret, void *stream)
+// asx_xcorr_pool_f32_dev and asx_xcorr_pool_topk_f32_dev (fn: the entry point's name for the messages; y and topk: the latter's entry
+// stride and option, after its own checks of k and min_separation)
+static int pool_batch(asx_plan *p, const char *fn, const float *d_sources, size_t source_stride, size_t nsources, const float *d_samples,
+                      size_t sample_stride, size_t nsamples, const int32_t *d_pairs, const int64_t *d_windows, size_t window_stride,
+                      size_t batch, const Results &y, void *stream, const Topk &topk = {})
 {
-    static const char *fn = "asx_xcorr_pool_f32_dev";
-    if (!p || !d_sources || !d_samples || !d_coef || !d_ret) return fail("%s: null argument", fn);
+    if (!p || !d_sources || !d_samples || !y.coef || !y.ret) return fail("%s: null argument", fn);
     PlanCall c(p, stream);
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
     hipStream_t s = c.s;
@@ -1251,7 +1253,30 @@ extern "C" int asx_xcorr_pool_f32_dev(asx_plan *p, const float *d_sources, size_
     const PoolCall pool{ d_pairs, nsources, nsamples };
     Pairs<float> x{ d_sources, d_samples, d_sources, d_samples, source_stride, sample_stride, 0, d_windows, window_stride };
     x.pool = &pool;
-    return run_batch(p, x, batch, { d_lag, d_coef, d_ret }, s);
+    return run_batch(p, x, batch, y, s, topk);
+}
+
+extern "C" int asx_xcorr_pool_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                      const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                      const int64_t *d_windows, size_t window_stride, size_t batch, int64_t *d_lag, double *d_coef,
+                                      int32_t *d_ret, void *stream)
+{
+    return pool_batch(p, "asx_xcorr_pool_f32_dev", d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs,
+                      d_windows, window_stride, batch, { d_lag, d_coef, d_ret }, stream);
+}
+
+// The K strongest separated lags per pair of two pools: the pool call with passes 2..k over each group's Q (run_group); the bank is
+// filled once per call whatever k is.  k = 1 launches exactly the pool call.
+extern "C" int asx_xcorr_pool_topk_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                           const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                           const int64_t *d_windows, size_t window_stride, size_t batch, int k, int64_t min_separation,
+                                           int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_pool_topk_f32_dev";
+    if (k < 1 || k > ASX_TOPK_MAX) return fail("%s: k = %d is not in [1, %d]", fn, k, ASX_TOPK_MAX);
+    if (min_separation < 0) return fail("%s: min_separation = %lld is negative", fn, (long long)min_separation);
+    return pool_batch(p, fn, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows, window_stride,
+                      batch, { d_lag, d_coef, d_ret, (size_t)k }, stream, Topk{ k, min_separation });
 }
 
 // diagnostic (not in the public header): the bank's capacity in tracks and how many pool calls have filled it
@@ -1691,6 +1716,17 @@ extern "C" int asx_results_to_ms_dev(const int64_t *d_lag, const double *d_coef,
     if (!(sample_rate > 0.0)) return fail("asx_results_to_ms_dev: bad sample rate");
     asx_launch_results_to_ms(d_lag, d_coef, d_ret, batch, min_confidence, sample_rate, d_lag_ms, d_accept,
                              (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The entry of each pair a caller of the top-k calls keeps (k_topk_best): one launch on `stream`, nothing allocated.
+extern "C" int asx_topk_best_dev(const int64_t *d_lag, const double *d_coef, const int32_t *d_ret, size_t batch, int k,
+                                 int64_t *d_best_lag, double *d_best_coef, int32_t *d_best_ret, int32_t *d_best_entry, void *stream)
+{
+    if (!d_lag || !d_coef || !d_ret || !d_best_coef || !d_best_ret) return fail("asx_topk_best_dev: null argument");
+    if (k < 1 || k > ASX_TOPK_MAX) return fail("asx_topk_best_dev: k = %d is not in [1, %d]", k, ASX_TOPK_MAX);
+    asx_launch_topk_best(d_lag, d_coef, d_ret, batch, k, d_best_lag, d_best_coef, d_best_ret, d_best_entry, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }

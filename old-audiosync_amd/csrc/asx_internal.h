@@ -146,7 +146,7 @@ __device__ inline bool asx_win_row(const AsxWinRows &R, size_t pair, uint32_t N,
 // Top-k peaks (asx_xcorr_topk_f32_dev): pass 1 is the strided / windowed call's peak search; pass j >= 2 searches the same Q again
 // with A_j = the call's window minus the zones |lag - lag_i| <= min_separation around the entries i < j (lags, not indices: -N and
 // N-1 are far apart).  k_topk_step (xcorr_kernels.hip) writes entry j and prepares pass j + 1 in the group's AsxTopkPair records; the
-// pass kernels (k_inv_cols_rx, k_inv_cols_wx, k_finalize_x, k_refine_pick_x, k_pearson_prep_x) read them.
+// pass kernels (k_inv_cols_rx, k_inv_cols_wx, k_finalize_x, k_refine_pick_x, k_pearson_prep_x; k_pearson_prep_xl in a pool call) read them.
 #define ASX_TOPK_MAX 8
 #define ASX_TK_EMPTY 1u   // A_j is empty: this entry and every later one are (0, NaN, -3)
 #define ASX_TK_INVALID 2u // the pair's row is not a window: every entry is (0, NaN, -2)
@@ -234,12 +234,13 @@ struct AsxSearch {
     }
 };
 
-// Pool calls (asx_xcorr_pool_f32_dev): pair i of a call is source a_i of one pool against sample b_i of another.  Every track of both
+// Pool calls (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev): pair i of a call is source a_i of one pool against sample b_i of another.  Every track of both
 // pools has its forward column pass in the plan's bank (written once per call); k_pool_resolve (rlayout.hip) turns each pair of a launch
 // group into one of these records in the lane's workspace, and the listed kernels (k_rows_rl, k_refine_dots_l, k_pearson_partial_l,
-// k_pearson_prep_l, k_pearson_prep_pl) read pair i's slots and inputs from it instead of from i * pitch.  An index outside its pool
-// gives slot 0 and ASX_POOL_INVALID: k_rows_rl writes a NaN Q for it (one candidate, the seed: it can never overflow) and
-// k_invalid_pairs writes (0, NaN, -4) behind the Pearson kernels.
+// k_pearson_prep_l, k_pearson_prep_pl, k_pearson_prep_xl) read pair i's slots and inputs from it instead of from i * pitch.  An index
+// outside its pool gives slot 0 and ASX_POOL_INVALID: k_rows_rl writes a NaN Q and a zero bound for it -- every inverse tile of every
+// pass leaves at once, whatever the pair's window, zones or seed, so its running maximum stays empty and it can never overflow -- and
+// k_invalid_pairs writes (0, NaN, -4) behind the Pearson kernels (top-k: k_invalid_pairs_k, all k entries, behind the last step).
 #define ASX_POOL_INVALID 1u
 struct AsxPoolPair {
     uint32_t sx, sy;        // bank slots: source a, sample b (0 for an invalid pair)
@@ -347,6 +348,8 @@ bool asx_launch_rows_rl(const AsxDev &P, const float2 *cx, const float2 *cy, flo
                         int npairs, hipStream_t s);
 // behind the Pearson kernels of a pool group: (0, NaN, -4) for every pair flagged ASX_POOL_INVALID
 void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
+// the same behind the last k_topk_step of a pool group with top-k: all k entries of such a pair (entry stride k)
+void asx_launch_invalid_pairs_k(const AsxPoolPair *pl, int k, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 bool asx_rlayout_available(const AsxDev &P); // all three kernels compiled in for this plan's schedules
 int asx_rlayout_band_rows(const AsxDev &P);
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,
@@ -375,6 +378,9 @@ void asx_launch_pearson_spectral_f32(const AsxDev &P, const AsxInputs<float> &in
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
                               double min_confidence, double sample_rate, int64_t *lag_ms, int32_t *accept,
                               hipStream_t s);
+// asx_topk_best_dev: per pair the entry with ret == 0 and the largest signed coefficient (none: entry 0), to index pair
+void asx_launch_topk_best(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch, int k, int64_t *best_lag,
+                          double *best_coef, int32_t *best_ret, int32_t *best_entry, hipStream_t s);
 void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t s);
 unsigned asx_pearson_blocks(uint32_t basis_len); // partial blocks per pair: psums holds 6 doubles per block and pair
 // second look, DC removal: stats[0] = mean of source[0..2N), stats[1] = sum of sample[0..N), stats[2] = scale * stats[0] * stats[1]

@@ -193,6 +193,19 @@ template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep
 #include "pearson_prep_body.h"
 }
 
+// the listed top-k form (asx_xcorr_pool_topk_f32_dev, passes 2..k): the seed from the pair's record as k_pearson_prep_x, the inputs
+// from the pair's pool record as k_pearson_prep_l
+template <int NTP, int NB> __global__ __launch_bounds__(NTP) void k_pearson_prep_xl(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
+                                                                       const float *__restrict__ smp, const AsxPoolPair *__restrict__ PL,
+                                                                       AsxPeakWs W, AsxSpecWs S, AsxSeg *__restrict__ seg,
+                                                                       const AsxTopkPair *__restrict__ X)
+{
+    const uint32_t seed = X[blockIdx.y].z.seed;
+#define ASX_SRC_OF(pair) PL[pair].src_off
+#define ASX_SMP_OF(pair) PL[pair].smp_off
+#include "pearson_prep_body.h"
+}
+
 // grid (npairs), one wave per pair: k_pearson_final (xcorr_kernels.hip) with the two spectral modes in front of it.
 __global__ __launch_bounds__(64) void k_pearson_final_spec(const AsxSeg *__restrict__ seg, const double *__restrict__ psums, uint32_t nb,
                                                             AsxSpecWs S, int64_t *__restrict__ lag,
@@ -232,13 +245,15 @@ __global__ __launch_bounds__(64) void k_pearson_final_spec(const AsxSeg *__restr
     }
 }
 
-// the prep kernel of the group's inputs (listed: the plan's seed or the pairs' rows) and search, NB blocks of NTP threads per pair
+// the prep kernel of the group's inputs (listed: the plan's seed, the pairs' rows or their top-k records) and search, NB blocks of NTP threads per pair
 template <int NTP, int NB>
 static void launch_prep(const AsxDev &P, const AsxInputs<float> &in, const AsxSearch &q, const AsxPeakWs &W, const AsxSpecWs &S,
                         AsxSeg *seg, int npairs, hipStream_t s)
 {
     const dim3 grid(NB, npairs), block(NTP);
-    if (in.pl && q.kind == AsxSearch::ROWS)
+    if (in.pl && q.kind == AsxSearch::TOPK)
+        hipLaunchKernelGGL((k_pearson_prep_xl<NTP, NB>), grid, block, 0, s, P.self_dev, in.src, in.smp, in.pl, W, S, seg, q.tk);
+    else if (in.pl && q.kind == AsxSearch::ROWS)
         hipLaunchKernelGGL((k_pearson_prep_pl<NTP, NB>), grid, block, 0, s, P.self_dev, in.src, in.smp, in.pl, W, S, seg, q.rows);
     else if (in.pl)
         hipLaunchKernelGGL((k_pearson_prep_l<NTP, NB>), grid, block, 0, s, P.self_dev, in.src, in.smp, in.pl, W, S, seg, q.seed());

@@ -481,9 +481,10 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_r(c
 
 // The listed form (asx_xcorr_pool_f32_dev): pair p's C_x / C_y are rows L[p].sx / L[p].sy of the bank (cx, cy: its source and sample
 // spectra, pair_pitch apart), both loaded temporal -- consecutive pairs may share a slot.  The same body: the same float32 Q, bit for
-// bit, as k_rows_r on the same C rows.  A pair flagged ASX_POOL_INVALID (an index outside its pool) gets a NaN Q instead: its peak
-// search sees a NaN r, in which only the seed has a key (+inf, asx_win_has permitting) -- one candidate at most whatever its window, so
-// it is never counted, listed or re-evaluated -- and k_invalid_pairs overwrites its results.
+// bit, as k_rows_r on the same C rows.  A pair flagged ASX_POOL_INVALID (an index outside its pool) gets a NaN Q and a zero bound instead: every
+// inverse tile of every pass leaves at the zero bound before it scans anything (inv_cols_r_body.h), whatever the pair's window, zones
+// or seed, so its running maximum stays empty and it is never counted, listed or re-evaluated -- and k_invalid_pairs (top-k:
+// k_invalid_pairs_k) overwrites its results.
 template <class S, int NT, bool TWO>
 __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rl(const RArgs P, const float2 *__restrict__ cx,
                                                                                  const float2 *__restrict__ cy, float2 *__restrict__ qo,

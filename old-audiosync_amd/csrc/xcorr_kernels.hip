@@ -737,6 +737,22 @@ __global__ __launch_bounds__(ASX_THREADS) void k_invalid_pairs(const AsxPoolPair
     ret[pair] = -4;
 }
 
+// the k-entry form (asx_xcorr_pool_topk_f32_dev): behind the LAST k_topk_step of a pool group, all k entries (index pair * k + j) of
+// such a pair, over whatever the steps wrote there (-2 and -3 included)
+__global__ __launch_bounds__(ASX_THREADS) void k_invalid_pairs_k(const AsxPoolPair *__restrict__ PL, int npairs, int k,
+                                                                  int64_t *__restrict__ lag, double *__restrict__ coef,
+                                                                  int32_t *__restrict__ ret)
+{
+    const int pair = blockIdx.x * ASX_THREADS + threadIdx.x;
+    if (pair >= npairs || !(PL[pair].flags & ASX_POOL_INVALID)) return;
+    for (int j = 0; j < k; j++) {
+        const size_t e = (size_t)pair * (size_t)k + (size_t)j;
+        if (lag) lag[e] = 0;
+        coef[e] = (double)NAN;
+        ret[e] = -4;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Exact re-evaluation of near-tied lags: r[k] = sum_{n<N} source[(n+k) mod 2N] * sample[n]
 // (the identity behind src/cross_correlation.c:232-239), accumulated as an
@@ -893,6 +909,31 @@ __global__ __launch_bounds__(ASX_THREADS) void k_results_to_ms(const int64_t *__
     if (i >= batch) return;
     lag_ms[i] = (int64_t)round((double)lag[i] * ms_per_frame);
     if (accept) accept[i] = (ret[i] == 0 && coef[i] >= min_confidence) ? 1 : 0;
+}
+
+// The entry a caller of the top-k calls keeps, one thread per pair: among the pair's k entries (index pair * k + j) with ret == 0 the
+// largest SIGNED coefficient (the acceptance above is signed too), the smallest j among equals; none with ret == 0: entry 0 as it is.
+// Its (lag, coef, ret) go to index pair -- the layout k_results_to_ms takes -- and j to best_entry.
+__global__ __launch_bounds__(ASX_THREADS) void k_topk_best(const int64_t *__restrict__ lag, const double *__restrict__ coef,
+                                                            const int32_t *__restrict__ ret, size_t batch, int k,
+                                                            int64_t *__restrict__ best_lag, double *__restrict__ best_coef,
+                                                            int32_t *__restrict__ best_ret, int32_t *__restrict__ best_entry)
+{
+    const size_t i = (size_t)blockIdx.x * ASX_THREADS + threadIdx.x;
+    if (i >= batch) return;
+    const size_t e0 = i * (size_t)k;
+    int bj = -1;
+    double bc = 0.0;
+    for (int j = 0; j < k; j++) {
+        if (ret[e0 + j] != 0) continue;
+        const double c = coef[e0 + j];
+        if (bj < 0 || c > bc) { bj = j; bc = c; }
+    }
+    const int j = bj < 0 ? 0 : bj;
+    if (best_lag) best_lag[i] = lag[e0 + j];
+    best_coef[i] = coef[e0 + j];
+    best_ret[i] = ret[e0 + j];
+    if (best_entry) best_entry[i] = j;
 }
 
 // ---------------------------------------------------------------------------
@@ -1240,6 +1281,12 @@ void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef,
     hipLaunchKernelGGL(k_invalid_pairs, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, pl, npairs, lag, coef, ret);
 }
 
+void asx_launch_invalid_pairs_k(const AsxPoolPair *pl, int k, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_invalid_pairs_k, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, pl, npairs, k, lag, coef,
+                       ret);
+}
+
 void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
 {
     hipLaunchKernelGGL(k_invalid_rows, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, rows, N, npairs, lag,
@@ -1318,6 +1365,15 @@ void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int3
     const unsigned blocks = (unsigned)((batch + ASX_THREADS - 1) / ASX_THREADS);
     hipLaunchKernelGGL(k_results_to_ms, dim3(blocks), dim3(ASX_THREADS), 0, s, lag, coef, ret, batch, min_confidence,
                        1000.0 / sample_rate, lag_ms, accept);
+}
+
+void asx_launch_topk_best(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch, int k, int64_t *best_lag,
+                          double *best_coef, int32_t *best_ret, int32_t *best_entry, hipStream_t s)
+{
+    if (batch == 0) return;
+    const unsigned blocks = (unsigned)((batch + ASX_THREADS - 1) / ASX_THREADS);
+    hipLaunchKernelGGL(k_topk_best, dim3(blocks), dim3(ASX_THREADS), 0, s, lag, coef, ret, batch, k, best_lag, best_coef, best_ret,
+                       best_entry);
 }
 
 void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t s)

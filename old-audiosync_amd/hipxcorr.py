@@ -27,7 +27,8 @@ ABI_SYMBOLS = [
     "asx_current_device", "asx_plan_timings_ms", "asx_xcorr_batch_multi", "asx_plan_layout", "asx_plan_narrowed_calls",
     "asx_plan_set_pearson", "asx_plan_pearson_modes", "asx_plan_placement", "asx_host_malloc", "asx_host_free", "asx_shard_range", "asx_result_bytes", "asx_comm_create", "asx_comm_destroy", "asx_xcorr_batch_multi_dev",
     "asx_xcorr_strided_f32_dev", "asx_plan_set_lag_window", "asx_plan_lag_window", "asx_stream_set_lag_window",
-    "asx_xcorr_windowed_f32_dev", "asx_xcorr_topk_f32_dev", "asx_xcorr_pool_f32_dev",
+    "asx_xcorr_windowed_f32_dev", "asx_xcorr_topk_f32_dev", "asx_xcorr_pool_f32_dev", "asx_xcorr_pool_topk_f32_dev",
+    "asx_topk_best_dev",
 ]
 
 TOPK_MAX = 8  # ASX_TOPK_MAX, include/audiosync/xcorr_hip.h
@@ -120,6 +121,9 @@ def lib():
     L.asx_xcorr_pool_f32_dev.restype = ctypes.c_int
     L.asx_xcorr_pool_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp,
                                          ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, vp]
+    L.asx_xcorr_pool_topk_f32_dev.restype = ctypes.c_int
+    L.asx_xcorr_pool_topk_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp,
+                                              ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, vp, vp, vp, vp]
     L.asx_plan_debug_bank.restype = ctypes.c_int
     L.asx_plan_debug_bank.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                       ctypes.POINTER(ctypes.c_uint64)]
@@ -141,6 +145,8 @@ def lib():
     L.asx_pearson_f64.argtypes = [c_f64p, c_f64p, ctypes.c_size_t, ctypes.c_int, c_f64p]
     L.asx_results_to_ms_dev.restype = ctypes.c_int
     L.asx_results_to_ms_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, vp, vp, vp]
+    L.asx_topk_best_dev.restype = ctypes.c_int
+    L.asx_topk_best_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.c_int, vp, vp, vp, vp, vp]
     L.asx_stream_create.restype = vp
     L.asx_stream_create.argtypes = [ctypes.c_size_t, ctypes.c_int]
     L.asx_stream_destroy.restype = None
@@ -270,6 +276,15 @@ def results_to_ms_dev(d_lag, d_coef, d_ret, batch, d_lag_ms, d_accept=0, min_con
         raise AsxError(_err())
 
 
+def topk_best_dev(d_lag, d_coef, d_ret, batch, k, d_best_coef, d_best_ret, d_best_lag=0, d_best_entry=0, stream=0):
+    """raw device pointers (ints): asx_topk_best_dev -- per pair, of its k entries at i*k + j, the one with ret == 0 and the largest
+    signed coefficient (none: entry 0) to index i of the best arrays, which results_to_ms_dev takes; asynchronous on `stream`"""
+    rc = lib().asx_topk_best_dev(d_lag, d_coef, d_ret, int(batch), int(k), d_best_lag or None, d_best_coef, d_best_ret,
+                                 d_best_entry or None, stream or None)
+    if rc != 0:
+        raise AsxError(_err())
+
+
 def synth_pairs_dev(seed, first_pair, count, sample_len, noise_shift, d_src, d_smp, d_lag=0, stream=0):
     rc = lib().asx_synth_pairs_dev(seed, first_pair, count, sample_len, noise_shift, d_src, d_smp,
                                    d_lag or None, stream or None)
@@ -371,6 +386,13 @@ def pool_args(n, sources, samples, pairs=None, windows=None):
             raise ValueError("windows must be [2] or [B, 2] with B = %d pairs" % batch)
         ws = 1 if w.ndim == 2 else 0
     return s, t, pr, w, batch, ws
+
+
+def pool_topk_args(n, sources, samples, k, min_separation, pairs=None, windows=None):
+    """Host checks of Plan.xcorr_pool_topk_f32: k and min_separation as topk_args checks them, the rest as pool_args.  -> pool_args'
+    tuple + (k, min_separation).  ValueError on anything else."""
+    k, sep = topk_args(1, np.zeros(2, np.float32), np.zeros(1, np.float32), k, min_separation)[-2:]
+    return pool_args(n, sources, samples, pairs, windows) + (k, sep)
 
 
 def position_rows(n, hop, batch, p_lo, p_hi):
@@ -688,6 +710,16 @@ class Plan:
         if rc != 0:
             raise AsxError(_err())
 
+    def xcorr_pool_topk_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows,
+                            window_stride, batch, k, min_separation, d_lag, d_coef, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_topk_f32_dev -- xcorr_pool_dev's pairs with the k strongest lags of pair i at
+        least min_separation apart, entry j at index i*k + j of d_lag / d_coef / d_ret; asynchronous on `stream`"""
+        rc = lib().asx_xcorr_pool_topk_f32_dev(self._h, d_sources, int(source_stride), int(nsources), d_samples, int(sample_stride),
+                                               int(nsamples), d_pairs or None, d_windows or None, int(window_stride), int(batch),
+                                               int(k), int(min_separation), d_lag or None, d_coef, d_ret, stream or None)
+        if rc != 0:
+            raise AsxError(_err())
+
     def debug_bank(self):
         """(source tracks, sample tracks) the plan's pool bank holds, and how many pool calls have filled it"""
         a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
@@ -701,7 +733,20 @@ class Plan:
         xcorr_windowed_f32.  Every track is transformed once per call.  Shapes are checked on the host (ValueError) before anything is
         uploaded; an index outside its pool gives that pair (0, NaN, -4).  Returns (lag int64, coef float64, ret int32) of shape [B],
         or [S, R] when pairs is None."""
-        s, t, pr, w, batch, ws = pool_args(self.sample_len, sources, samples, pairs, windows)
+        return Plan._pool_host(self, *pool_args(self.sample_len, sources, samples, pairs, windows))
+
+    def xcorr_pool_topk_f32(self, sources, samples, k, min_separation, pairs=None, windows=None):
+        """The k strongest separated lags per pair of two pools (asx_xcorr_pool_topk_f32_dev): the pools, pairs and windows of
+        xcorr_pool_f32, k and min_separation of xcorr_topk_f32.  Every track is transformed once per call, whatever k is.  Arguments
+        are checked on the host (ValueError) before anything is uploaded.  Returns (lag int64, coef float64, ret int32) of shape
+        [B, k], or [S, R, k] when pairs is None; ret = -3 where no lag was left, -4 in all k entries of a pair with an index outside
+        its pool."""
+        a = pool_topk_args(self.sample_len, sources, samples, k, min_separation, pairs, windows)
+        return Plan._pool_host(self, *a[:6], topk=a[6:])
+
+    def _pool_host(self, s, t, pr, w, batch, ws, topk=None):
+        """checked host arrays (pool_args) -> device copies -> asx_xcorr_pool_f32_dev (topk = (k, min_separation):
+        asx_xcorr_pool_topk_f32_dev, a last axis of k entries) -> (lag, coef, ret)"""
         L = lib()
         bufs = []
         try:
@@ -718,14 +763,22 @@ class Plan:
                 ups.append((d_pairs, pr))
             if w is not None:
                 ups.append((d_win, w))
-            d_lag, d_coef, d_ret = dev(8 * batch), dev(8 * batch), dev(4 * batch)
+            entries = batch if topk is None else batch * topk[0]
+            d_lag, d_coef, d_ret = dev(8 * entries), dev(8 * entries), dev(4 * entries)
             for d, h in ups:
                 if L.asx_memcpy_h2d(d, h.ctypes.data, h.nbytes) != 0:
                     raise AsxError(_err())
             n = self.sample_len
-            self.xcorr_pool_dev(ups[0][0], 2 * n, s.shape[0], ups[1][0], n, t.shape[0], d_pairs, d_win, ws, batch, d_lag, d_coef, d_ret)
+            if topk is None:
+                self.xcorr_pool_dev(ups[0][0], 2 * n, s.shape[0], ups[1][0], n, t.shape[0], d_pairs, d_win, ws, batch, d_lag, d_coef,
+                                    d_ret)
+            else:
+                self.xcorr_pool_topk_dev(ups[0][0], 2 * n, s.shape[0], ups[1][0], n, t.shape[0], d_pairs, d_win, ws, batch, topk[0],
+                                         topk[1], d_lag, d_coef, d_ret)
             self.sync()
             shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
+            if topk is not None:
+                shape += (topk[0],)
             lag = np.zeros(shape, dtype=np.int64)
             coef = np.zeros(shape, dtype=np.float64)
             ret = np.zeros(shape, dtype=np.int32)
