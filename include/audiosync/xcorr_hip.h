@@ -152,6 +152,21 @@ int asx_plan_lag_window(const asx_plan *plan, int64_t *lag_min, int64_t *lag_max
 int asx_plan_set_pearson(asx_plan *plan, int spectral);
 int asx_plan_pearson_modes(asx_plan *plan, uint64_t counts[3]);
 
+/* The pruned inverse pass (real-column plans; on by default there, $ASX_PRUNE=0 = the initial value off).  The row pass of a group
+ * also leaves the energy of every row of Q per column tile; by Parseval no |r| of a tile exceeds sqrt(4 M1 x the tile's energy), and
+ * a tile whose bound lies under the near-maximum window of the pair's running maximum is not transformed: it can hold neither the
+ * peak nor a lag the exact re-evaluation would look at.  The tile with the largest bound and the tile of lag 0 go first, the others
+ * only if their bound allows; a tile too quiet for its float32 energies to be trusted (underflow) has no bound and is transformed.
+ * Lag, ret and coefficient are what the unpruned pass returns, bit for bit; only
+ * asx_plan_peak_overflows may come out smaller (fewer stale near-tie entries).  Taken by the float32 batch and strided calls without
+ * a broadcast track when every lag competes (the plan's full window, no per-pair windows, k = 1, no pools); every other call, the
+ * second look and asx_xcorr_debug_r_dev run the unpruned kernels whatever the setting.  asx_plan_set_prune(plan, 1) fails on a
+ * packed-sample plan.
+ * asx_plan_prune_stats: column tiles the pruned groups transformed, and the tiles those groups had in all, over the plan's life
+ * (synchronises the DEVICE, as asx_plan_pearson_modes does). */
+int asx_plan_set_prune(asx_plan *plan, int on);
+int asx_plan_prune_stats(asx_plan *plan, uint64_t *tiles_transformed, uint64_t *tiles_total);
+
 /* Introspection (used by tests, bench and DESIGN.md's numbers). */
 size_t asx_plan_sample_len(const asx_plan *plan);
 size_t asx_plan_fft_len(const asx_plan *plan);        /* F, real transform length */

@@ -118,6 +118,7 @@ struct asx_plan {
         double *psums = nullptr;
         AsxSpecWs spec{};      // spectral Pearson (pearson_spectral.hip): work list, window sums, mode counters
         AsxTopkWs tk{};        // top-k passes (asx_xcorr_topk_f32_dev): per-pair records and one pass's results
+        AsxPrune prune{};      // pruned inverse pass (asx_plan_set_prune): tile energies of Q, bounds, flags
         AsxPoolPair *pool = nullptr; // pool calls (asx_xcorr_pool_f32_dev): the group's pairs as slots and input offsets (k_pool_resolve)
     } lanes[2];
     int nlanes = 1;   // ASX_LANES=2 enables the second lane (measured: +0..4 %)
@@ -162,6 +163,8 @@ struct asx_plan {
     int64_t win_lo = 0, win_hi = 0;    // asx_plan_set_lag_window: the lags whose peak is searched, [-N, N-1] (set at creation) = all
     bool spectral = false;             // float32 groups take the spectral Pearson form (asx_plan_set_pearson; real-column plans)
     unsigned long long *mode_count = nullptr; // [ASX_PM_NMODES], cumulative over the plan's life
+    bool prune = false;                // asx_plan_set_prune: in-scope groups skip the inverse column tiles a bound rules out
+    unsigned long long *prune_stats = nullptr; // [2] tiles transformed, tiles in all, by the pruned groups; cumulative
     // "measure" plans only: at the first device-resident batch the forward column kernel is timed against the caller's buffers
     // on TWO allocations of its output workspaces and the faster set is kept (tune_placement)
     bool tune_placement = false, placement_done = false;
@@ -305,6 +308,15 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
                 return -1;
             ln.spec.mode_count = p->mode_count;
             ln.spec.tol = 1e-5;
+            // pruned inverse pass: 4 (M1 + 1) ntiles bytes per pair, about 1 % of Q; the group size does not depend on it
+            if (!p->prune_stats) {
+                if (dev_alloc(p, &p->prune_stats, 2)) return -1;
+                HIP_TRY(hipMemset(p->prune_stats, 0, 2 * sizeof(unsigned long long)));
+            }
+            if (dev_alloc(p, &ln.prune.eng, g * ((size_t)h.M1 + 1) * (size_t)h.ntiles) || dev_alloc(p, &ln.prune.ub, g * (size_t)h.ntiles) ||
+                dev_alloc(p, &ln.prune.best, g) || dev_alloc(p, &ln.prune.skip, g * (size_t)h.ntiles))
+                return -1;
+            ln.prune.stats = p->prune_stats;
         }
         HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
@@ -331,6 +343,8 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
     }
     p->spectral = d.rlayout != 0;
     if (const char *e = getenv("ASX_PEARSON")) p->spectral = p->spectral && strcmp(e, "direct") != 0; // A/B of the two forms
+    p->prune = d.rlayout != 0 && d.T == ASX_PRUNE_T && h.M2 % ASX_PRUNE_T == 0;
+    if (const char *e = getenv("ASX_PRUNE")) p->prune = p->prune && atoi(e) != 0; // A/B of the pruned inverse pass
     if (const char *e = getenv("ASX_EXACT")) p->exact = atoi(e) != 0; // initial value of asx_plan_set_exact (A/B of its cost)
     p->win_lo = -(int64_t)p->host.N; // the full lag window
     p->win_hi = (int64_t)p->host.N - 1;
@@ -557,6 +571,31 @@ extern "C" int asx_plan_pearson_modes(asx_plan *p, uint64_t counts[3])
     return 0;
 }
 
+extern "C" int asx_plan_set_prune(asx_plan *p, int on)
+{
+    if (!p) return fail("asx_plan_set_prune: null argument");
+    std::lock_guard<std::mutex> guard(p->lock);
+    if (on && !(p->dev.rlayout && p->dev.T == ASX_PRUNE_T && p->lanes[0].prune.eng))
+        return fail("asx_plan_set_prune: the pruned inverse pass needs a real-column plan (the reference's six lengths)");
+    p->prune = on != 0;
+    return 0;
+}
+
+extern "C" int asx_plan_prune_stats(asx_plan *p, uint64_t *tiles_transformed, uint64_t *tiles_total)
+{
+    if (!p || !tiles_transformed || !tiles_total) return fail("asx_plan_prune_stats: null argument");
+    PlanCall c(p);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    *tiles_transformed = *tiles_total = 0;
+    if (!p->prune_stats) return 0;
+    HIP_TRY(hipDeviceSynchronize()); // the whole device, as asx_plan_pearson_modes does
+    unsigned long long v[2];
+    HIP_TRY(hipMemcpy(v, p->prune_stats, sizeof v, hipMemcpyDeviceToHost));
+    *tiles_transformed = v[0];
+    *tiles_total = v[1];
+    return 0;
+}
+
 extern "C" int asx_plan_peak_repairs(asx_plan *p, uint64_t *count)
 {
     if (!p || !count) return fail("asx_plan_peak_repairs: null argument");
@@ -580,6 +619,19 @@ extern "C" int asx_plan_debug_peak(asx_plan *p, size_t pair, float *bound2, uint
     size_t n = std::min<size_t>(cap, W.cap);
     if (vals && hipMemcpy(vals, W.refine_val + pair * (size_t)W.cap, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     if (idxs && hipMemcpy(idxs, W.refine_idx + pair * (size_t)W.cap, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return 0;
+}
+
+// diagnostic (not in the public header): the pruned pass's bounds ub[0 .. n) and largest-bound tile of pair `pair` of the last pruned
+// group on lane 0 (n <= the plan's tile count)
+extern "C" int asx_plan_debug_prune(asx_plan *p, size_t pair, float *ub, int *best, size_t n)
+{
+    if (!p || pair >= p->group || !p->lanes[0].prune.ub || n > (size_t)p->host.ntiles) return -1;
+    PlanCall c(p, nullptr, false);
+    if (!c.dg.ok || hipDeviceSynchronize() != hipSuccess) return -1;
+    const AsxPrune &U = p->lanes[0].prune;
+    if (ub && hipMemcpy(ub, U.ub + pair * (size_t)p->host.ntiles, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (best && hipMemcpy(best, U.best + pair, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return 0;
 }
 
@@ -791,7 +843,18 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     }
     if (mark(1)) return -1;
     float2 *q = W.ga;
-    if (x.pool) {
+    // The pruned pair of passes (rlayout.hip: k_rows_re, asx_launch_inv_cols_rq) in place of the row pass and the inverse column pass:
+    // a float32 entry point's group on a real-column plan, every lag competing, no broadcast operand and no pool, one pass, r not asked
+    // for, the lane's own lists (not the second look).  Everything else launches what it always did.
+    // (GroupOpts::spectral is how an entry point says "float32 ABI": the double ABI clears it even when its frames were narrowed.
+    // Whether the plan's Pearson form IS spectral -- p->spectral -- plays no part here.)
+    const bool f32_entry = std::is_same<TIn, float>::value && o.spectral;
+    const AsxSearch call = AsxSearch::of(p->win_lo, p->win_hi, P.N, x.win, x.win_step, W.tk, 0); // pass 1's search
+    const bool prune = p->prune && P.rlayout && f32_entry && !x.pool && x.bc == 0 && !o.r_out && !o.pk && o.topk.k == 1 &&
+                       call.kind == AsxSearch::ALL;
+    if (prune) {
+        if (!asx_launch_rows_re(P, W.zxa, W.zya, q, tk, W.prune, (int)g, s)) return fail("internal: no row kernel for this plan");
+    } else if (x.pool) {
         if (!asx_launch_rows_rl(P, p->bank.cx, p->bank.cy, q, tk, pl, (int)g, s)) return fail("internal: no row kernel for this plan");
     } else if (P.rlayout) {
         if (!asx_launch_rows_r(P, (x.bc & 1) ? p->bslot.cx : W.zxa, (x.bc & 2) ? p->bslot.cy : W.zya, q, tk, (int)g, x.bc, s))
@@ -816,7 +879,11 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // One pass over the group's Q: the inverse columns, finalize, the exact re-evaluation and Pearson, the lags of `find` competing.
     // first: pass 1, which the profiling marks time and whose r goes to o.r_out.
     auto pass = [&](const AsxSearch &find, bool first) -> int {
-        asx_launch_inv_cols(P, q, tk, first ? o.r_out : nullptr, (int)g, s, find);
+        if (prune) {
+            if (!asx_launch_inv_cols_rq(P, q, tk, W.prune, (int)g, s)) return fail("internal: no inverse column kernel for this plan");
+        } else {
+            asx_launch_inv_cols(P, q, tk, first ? o.r_out : nullptr, (int)g, s, find);
+        }
         if (first && mark(3)) return -1;
         asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, find);
         // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
@@ -828,7 +895,6 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
             asx_launch_pearson_spectral_f32(P, in, find, tk, W.spec, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
         return 0;
     };
-    const AsxSearch call = search(0);
     if (pass(call, true)) return -1;
     // a pair whose row is not a window: (0, NaN, -2), the others untouched (top-k: k_topk_step writes it for every entry)
     if (call.kind == AsxSearch::ROWS && K == 1) asx_launch_invalid_rows(call.rows, P.N, y.lag, y.coef, y.ret, (int)g, s);

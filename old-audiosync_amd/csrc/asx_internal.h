@@ -30,6 +30,25 @@
 // values -- for any number of such lags up to the per-pair capacity below (pure tones at N = 1 440 000
 // have ~5 000).  The norms come for free from k_fwd_cols (it reads every input sample anyway).
 #define ASX_BOUND_C 4.0f
+// Pruned inverse pass (rlayout.hip: k_tile_bounds): a column tile of r whose bound ub = sqrt(4 M1 E) (1 + ASX_PRUNE_DELTA) lies under the
+// near-maximum window is not transformed.  What the factor has to cover, in units of eps32 = 2^-23, derived as ASX_BOUND_C is:
+//   the computed E against the exact energy of the float32 Q: |Q|^2 two roundings, four levels of additions of non-negative terms
+//     (a balanced tree over the tile's sixteen columns), the float64 sum over the rows and the square root nothing: 6 u = 3 eps on E, 1.5 eps on its root;
+//   the computed tile r^ against the exact transform r of that Q: no element of r^ exceeds its column's 2-norm, and the float32
+//     c2r transform of length 2 M1 <= 1200 delivers a column whose 2-norm is off by at most C eps log2(2 M1) of it -- the worst-case
+//     constant of one transform is ~1 (a third of the three transforms' ~3 in ASX_BOUND_C's note), taken as ASX_BOUND_C = 4 here as
+//     there: 4 * 10.3 = 41 eps, the tangling's few roundings included.
+// 43 eps = 5.1e-6 = 2^-17.6.  The bound has a factor 1.8 to spare on the generator's pairs (the second-largest bound is <= 0.56 of the
+// peak), so the factor is rounded up generously: 2^-14, twelve times what the derivation asks for.
+// All of the above are RELATIVE roundings.  |Q|^2 = re * re + im * im can also underflow: each of the two products loses up to
+// FLT_MIN absolutely when it is flushed or denormal (r itself, a sum of 2 M1 such Q, is then still an ordinary float32: tracks of
+// amplitude 1e-16 give |r| ~ 5e-23 and every |Q|^2 = 0).  A tile's energy is a sum of n = 16 (M1 + 1) terms, so its absolute error
+// from underflow is at most 2 n FLT_MIN; with E >= 2^25 n FLT_MIN that is 2^-24 E = eps / 2 more on E, inside the factor.  Below
+// that floor (ASX_PRUNE_FLOOR_PER_TERM per term: 2^25 * 2^-126 = 2^-101) k_tile_bounds states no bound: ub = +infinity, the tile is
+// transformed.  (The floor in r: sqrt(4 M1 n 2^-101) = 3e-12 at M1 = 600 -- pairs that quiet lose the pruning, nothing else.)
+#define ASX_PRUNE_DELTA 6.103515625e-5f
+#define ASX_PRUNE_FLOOR_PER_TERM 3.944304526105059e-31
+#define ASX_PRUNE_T 16                      // the tile width the row pass sums energies for (every real-column schedule's)
 #define ASX_CAND_MAX 16384                  // upper limit of a plan's per-pair candidate capacity
 #define ASX_CAND_MIN 2048
 #define ASX_DOT_BLOCKS 128                  // blocks per pair that walk the pair's candidate list
@@ -298,6 +317,15 @@ struct AsxPeakWs {
     float *tile_peak;      // [pairs][M2 / T] SIGNED float32 r (times F) at the best lag of each k_inv_cols_r tile
 };
 
+// Per-lane workspace of the pruned inverse pass (rlayout.hip: k_rows_re, k_tile_bounds, k_prune_select, k_inv_cols_rq)
+struct AsxPrune {
+    float *eng;            // [pairs][M1 + 1][ntiles] sum of |Q[k1][j2]|^2 over the tile's columns (k_rows_re)
+    float *ub;             // [pairs][ntiles] upper bound of |r^| over the tile
+    int *best;             // [pairs] the tile with the largest bound
+    unsigned char *skip;   // [pairs][ntiles] 1 = the second launch leaves the tile out
+    unsigned long long *stats; // [2] tiles transformed, tiles in all: cumulative over the plan's life (asx_plan_prune_stats)
+};
+
 // Spectral Pearson: the coefficient from r[peak] and window sums instead of a second pass over the inputs.
 // Modes a pair can take (k_pearson_prep decides, k_pearson_partial / k_pearson_final_spec act on it):
 #define ASX_PM_FAST 0    // lag >= 0: cross term = r[peak], window sums from the band sums + two band edges; nothing else is read
@@ -338,6 +366,11 @@ bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride,
                            float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s);
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                            const AsxSearch &search);
+// The pruned pair (every lag competes, no broadcast operand, no r_out): the row pass that also leaves U.eng, and the inverse pass
+// that reads it -- bounds, two tiles per pair, flags, the tiles that are left.  false = no kernel for this plan.
+bool asx_launch_rows_re(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, const AsxPrune &U,
+                        int npairs, hipStream_t s);
+bool asx_launch_inv_cols_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, const AsxPrune &U, int npairs, hipStream_t s);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 // pool calls: each pair's record (out) and its two slots' norm partials and band sums (band may be null) into the group's places

@@ -13,7 +13,11 @@
     // pair resident together, run0 == 0 for all of them): 0.405 against 0.367 ms at 600 rows, 0.423 against 0.299 ms per 1024 pairs
     // at 300 rows (profiles/r5_experiments/02_*).
     const size_t pair = blockIdx.x;
+#ifdef ASX_INV_BODY_TILE // k_inv_cols_rq: the tile its prologue chose; every other kernel: the tile of its place in the grid, as before
+    const int tile = ASX_INV_BODY_TILE;
+#else
     const int tile = rcol_tile_of_block(blockIdx.y, logT);
+#endif
     if (tile * T >= P.M2) return; // the tile count is rounded up; the tile width is this kernel's own (it reads only)
     {
         // Stagger: the blocks that share a CU run the same program -- a load phase (the tile's rows), then compute phases of about

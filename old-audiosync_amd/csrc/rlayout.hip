@@ -194,14 +194,22 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 //   BC: broadcast forms (asx_xcorr_strided_f32_dev).  Bit 0 = C_x is the plan's broadcast slot, one C for every pair (pair step
 //   0, temporal loads: every pair reads it, it must stay in the caches), bit 1 = C_y is.  BC = 0: both have Q's pair step.
 //   Bit 2 (k_rows_rl, pool calls): C_x / C_y are rows sx / sy of the plan's bank (L[pair], AsxPoolPair), temporal like the slot.
+//   ENG (k_rows_re, the pruned inverse pass): the block also leaves the energy of its row of Q per column tile of sixteen,
+//   eng[pair][k1][tile] = sum of |Q[k1][j2]|^2 over the tile's columns, in float32, one contiguous run per block.  The store phase
+//   holds every Q value in a register: its |Q|^2 goes to LDS, into the upper halves of the slots, which are free by then (the
+//   single-member values of the inverse stages live in the first 8 bytes of a slot) -- value p = 17 * tile + column-in-tile at float
+//   2 + (p & 1) of slot p / 2, a tile's sixteen values 17 apart from the next tile's, so that neither the writers (consecutive
+//   columns) nor the readers (consecutive tiles) meet in a bank more than two at a time -- and behind a barrier one thread per tile
+//   adds its sixteen as a balanced tree.  No atomics, no cross-lane step: the same Q gives the same bits.  Nothing is loaded for it.
+//   (Quad sums by DPP in front of the LDS write, four values per tile to add: the same time, profiles/r7_prune/ab_rows_variants.txt.)
 // ---------------------------------------------------------------------------
 // The body takes P and W by value: that call boundary loads their fields at the top of the kernel.  Written inside the __global__
 // itself the instruction stream changes, and with it the float32 rounding of r (11 of the headline's 124 coefficients moved by
 // about 1e-7).
-template <class S, int NT, bool TWO, int BC>
+template <class S, int NT, bool TWO, int BC, bool ENG = false>
 __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restrict__ cx, const float2 *__restrict__ cy,
                                             float2 *__restrict__ qo, int nrows, size_t pitch_x, size_t pitch_y, size_t pitch_q,
-                                            AsxPeakWs W, const AsxPoolPair *__restrict__ L = nullptr)
+                                            AsxPeakWs W, const AsxPoolPair *__restrict__ L = nullptr, float *__restrict__ eng = nullptr)
 {
     static_assert(S::nstages == 3, "three-stage row schedules only");
     constexpr int NS = S::n;                 // length of a (sub-)row transform
@@ -413,6 +421,13 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
 
     // ---- inverse stage 0 from LDS, the outputs leave from registers -------------------------------------------------
     float2 *go = qo + row;
+    // ENG: |Q|^2 of column c into the free upper half of an LDS slot (see above); 17 * M2 / 16 values fit the M2 slots' upper halves
+    static_assert(!ENG || (ASX_PRUNE_T == 16 && M2 % ASX_PRUNE_T == 0 && M2 / ASX_PRUNE_T <= NTB),
+                  "tile energies: tiles of sixteen columns, one thread per tile");
+    auto eng_slot = [](int p) __attribute__((always_inline)) { return 4 * (p >> 1) + 2 + (p & 1); };
+    auto eng_put = [&](int c, Cx1 y) __attribute__((always_inline)) {
+        reinterpret_cast<float *>(asx_lds_r)[eng_slot(17 * (c >> 4) + (c & 15))] = fmaf(y.re, y.re, y.im * y.im);
+    };
     if constexpr (!TWO) {
         for (int j = lt; j < Q0; j += NT) {
             const float4 *p = A4 + j;
@@ -429,6 +444,7 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
                 constexpr int t = decltype(T)::value;
                 const Cx1 y = mulwc(v[t], t == 0 ? fb : cmul(fb, leg[t]));
                 st_f2(go + j + t * Q0, make_float2(y.re, y.im), ASX_RNT & 8);
+                if constexpr (ENG) eng_put(j + t * Q0, y);
             });
         }
     } else {
@@ -462,7 +478,19 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
                 const Cx1 z = mulwc(A - Bw, t == 0 ? fbh : cmul(fbh, lg));
                 st_f2(go + j + t * Q0, make_float2(y.re, y.im), ASX_RNT & 8);
                 st_f2(go + NS + j + t * Q0, make_float2(z.re, z.im), ASX_RNT & 8);
+                if constexpr (ENG) { eng_put(j + t * Q0, y); eng_put(NS + j + t * Q0, z); }
             });
+        }
+    }
+    if constexpr (ENG) {
+        __syncthreads();
+        constexpr int NTILE = M2 / ASX_PRUNE_T;
+        if (tid < NTILE) {
+            float v[16];
+            static_for<0, 16>([&](auto I) __attribute__((always_inline)) {
+                v[I] = reinterpret_cast<const float *>(asx_lds_r)[eng_slot(17 * tid + decltype(I)::value)];
+            });
+            eng[((size_t)pair * nrows + k1) * NTILE + tid] = tree_sum<16>(v);
         }
     }
     RSTAMP(0, task, 4);
@@ -477,6 +505,17 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_r(c
                                                                                 int nrows, size_t pair_pitch, AsxPeakWs W)
 {
     rows_r_body<S, NT, TWO, BC>(P, cx, cy, qo, nrows, (BC & 1) ? 0 : pair_pitch, (BC & 2) ? 0 : pair_pitch, pair_pitch, W);
+}
+
+// The row pass of the pruned inverse pass (asx_launch_rows_re): k_rows_r<S, NT, TWO, 0> that also leaves the tile energies of Q (ENG
+// above).  A kernel name of its own: the twelve k_rows_r instances stay the kernels they were.
+template <class S, int NT, bool TWO>
+__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_re(const RArgs P, const float2 *__restrict__ cx,
+                                                                                 const float2 *__restrict__ cy, float2 *__restrict__ qo,
+                                                                                 int nrows, size_t pair_pitch, AsxPeakWs W,
+                                                                                 float *__restrict__ eng)
+{
+    rows_r_body<S, NT, TWO, 0, true>(P, cx, cy, qo, nrows, pair_pitch, pair_pitch, pair_pitch, W, nullptr, eng);
 }
 
 // The listed form (asx_xcorr_pool_f32_dev): pair p's C_x / C_y are rows L[p].sx / L[p].sy of the bank (cx, cy: its source and sample
@@ -806,6 +845,115 @@ __global__ __launch_bounds__(NT, 4) void k_inv_cols_rx(const RArgs P, const floa
 }
 
 // ---------------------------------------------------------------------------
+// The pruned inverse pass (asx_launch_inv_cols_rq; every lag competes, no r_out, no second look): k_tile_bounds, k_inv_cols_rq
+// <FIRST = true> on two tiles per pair, k_prune_select, k_inv_cols_rq<FIRST = false> on the tiles that are left.
+//
+// The bound.  Column j2 of r is the c2r transform of column j2 of Q: with the tangling Z'[u] = S + i conj(w) D, S = Q[u] + conj Q[M1-u],
+// D = Q[u] - conj Q[M1-u], |Z'[u]|^2 + |Z'[M1-u]|^2 = 2 |S|^2 + 2 |D|^2 = 4 (|Q[u]|^2 + |Q[M1-u]|^2) (u = M1/2: |Z'|^2 = 4 |Q|^2), and
+// for u = 0, with Q[0] = a + ib and Q[M1] = c + id, |Z'[0]|^2 = 2 (a - d)^2 + 2 (c - b)^2 <= 4 (|Q[0]|^2 + |Q[M1]|^2).  The M1-point
+// inverse transform is unnormalised, sum_m |z[m]|^2 = M1 sum_u |Z'[u]|^2, and r[2m] + i r[2m+1] = z[m], so for ANY complex rows
+//     sum_j1 r[j1][j2]^2 <= 4 M1 sum_{k1 = 0 .. M1} |Q[k1][j2]|^2
+// with equality but for rows 0 and M1, which count twice here: in exact arithmetic they are real and Parseval gives them the weight
+// 1 (h(0) = h(M1) = 1, h = 2 elsewhere), but the float32 rows carry an imaginary residue that the tangling mixes in (a - d, c - b),
+// and the weight 2 covers every value of it -- two rows of M1 + 1, a bound larger by 1 / M1 at most.  No element of a tile exceeds
+// the tile's Frobenius norm:
+//     |r[j1][j2]| <= sqrt(4 M1 E),  E = sum over the tile's sixteen columns and all rows of |Q|^2 = the sum over k1 of eng.
+// delta (ASX_PRUNE_DELTA, asx_internal.h) covers the float32 roundings on both sides of that; a tile whose energy sum lies under
+// ASX_PRUNE_FLOOR_PER_TERM times its number of terms gets the bound +infinity (the squares of a very quiet pair underflow in
+// float32 although r itself does not): it is never skipped.
+// ---------------------------------------------------------------------------
+// grid (npairs), 1024 threads: ub[pair][tile] and the pair's largest-bound tile from eng[pair][k1][tile].  The rows are dealt to
+// 1024 / (tiles rounded up to 32) slices, summed in float64 per slice and then over the slices in slice order: the same eng gives
+// the same bits.
+__global__ __launch_bounds__(1024) void k_tile_bounds(const float *__restrict__ eng, float *__restrict__ ub, int *__restrict__ best,
+                                                       int nrows, int ntiles, double scale, double floor)
+{
+    __shared__ double part[1024];
+    const size_t pair = blockIdx.x;
+    const int tid = threadIdx.x, tp = (ntiles + 31) & ~31, nsl = 1024 / tp;
+    const int tile = tid % tp, sl = tid / tp;
+    const float *e = eng + pair * (size_t)nrows * ntiles;
+    double sum = 0.0;
+    if (tile < ntiles && sl < nsl)
+        for (int k1 = sl; k1 < nrows; k1 += nsl) sum += (double)e[(size_t)k1 * ntiles + tile];
+    part[tid] = sum;
+    __syncthreads();
+    if (tid >= 64) return;
+    // bounds are >= 0 or NaN: their bits order them; a NaN bound (NaN in Q) is never the largest, and never below a threshold either
+    unsigned long long top = 0;
+    for (int t = tid; t < ntiles; t += 64) {
+        double s = 0.0;
+        for (int i = 0; i < nsl; i++) s += part[i * tp + t];
+        // under the floor the float32 squares may have underflowed (asx_internal.h): no bound, the tile is transformed
+        const float b = s < floor ? INFINITY : __double2float_ru(sqrt(scale * s) * (1.0 + (double)ASX_PRUNE_DELTA));
+        ub[pair * ntiles + t] = b;
+        const unsigned long long key = b == b ? ((unsigned long long)__float_as_uint(b) << 32) | (0xFFFFFFFFu - (unsigned)t) : 0ull;
+        top = key > top ? key : top;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned hi = __shfl_xor((unsigned)(top >> 32), off, 64), lo = __shfl_xor((unsigned)top, off, 64);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        top = o > top ? o : top;
+    }
+    if (tid == 0) best[pair] = top ? (int)(0xFFFFFFFFu - (unsigned)top) : 0; // (ties: the smallest tile; every bound NaN: tile 0)
+}
+
+// grid (npairs), 256 threads, behind the first launch: skip[pair][tile] = 1 for the tiles the second launch leaves out -- the two the
+// first launch took, and every tile whose bound lies under the window of the pair's running maximum: |r^| <= ub < key(max so far) - b2
+// <= final maximum - b2, the exit inv_cols_r_body.h takes behind its scan, taken before the tile is loaded.  An empty running maximum
+// (a silent pair: the blocks left at the zero bound) and a NaN bound make the comparison false: nothing but the two is skipped.
+__global__ __launch_bounds__(256) void k_prune_select(const float *__restrict__ ub, const int *__restrict__ best,
+                                                       unsigned char *__restrict__ skip, AsxPeakWs W, int ntiles,
+                                                       unsigned long long *__restrict__ stats)
+{
+    __shared__ unsigned kept;
+    const size_t pair = blockIdx.x;
+    if (threadIdx.x == 0) kept = 0;
+    __syncthreads();
+    const asx_peak_t pm = W.pairmax[pair];
+    const float thr = near_max_threshold(peak_key(pm), W.bound2[pair]); // NaN when pm == 0
+    const int bt = best[pair];
+    unsigned n = 0;
+    for (int t = threadIdx.x; t < ntiles; t += 256) {
+        const bool sk = t == bt || t == 0 || (pm != 0 && ub[pair * ntiles + t] < thr);
+        skip[pair * ntiles + t] = sk ? 1 : 0;
+        n += sk ? 0u : 1u;
+    }
+    if (n) atomicAdd(&kept, n);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&stats[0], (unsigned long long)(kept + (bt == 0 ? 1u : 2u)));
+        atomicAdd(&stats[1], (unsigned long long)ntiles);
+    }
+}
+
+// k_inv_cols_r on the tile its prologue names.  FIRST: grid (npairs, 2) -- y = 0 the pair's largest-bound tile, which holds the peak
+// on all but contrived inputs, y = 1 the seed's tile (tile 0: lag 0 competes signed), gone when that is the same tile.  !FIRST: the
+// grid of k_inv_cols_r; a block whose flag is set returns before it asks for anything else.
+template <class S1, int TC, int NT, bool FIRST>
+__global__ __launch_bounds__(NT, 4) void k_inv_cols_rq(const RArgs P, const float2 *__restrict__ qi, size_t pair_pitch, AsxPeakWs W,
+                                                        unsigned first_gen, const int *__restrict__ best,
+                                                        const unsigned char *__restrict__ skip)
+{
+    int q_tile;
+    if constexpr (FIRST) {
+        const int bt = best[blockIdx.x];
+        if (blockIdx.y != 0 && bt == 0) return;
+        q_tile = blockIdx.y == 0 ? bt : 0;
+    } else {
+        q_tile = rcol_tile_of_block(blockIdx.y, asx_ilog2(TC));
+        if (q_tile * TC >= P.M2 || skip[(size_t)blockIdx.x * (size_t)(P.M2 / TC) + q_tile]) return; // (the tile count is rounded up)
+    }
+    constexpr bool WIN = false;
+    const AsxWin Z{};
+    float *const r_out = nullptr;
+#define ASX_INV_BODY_TILE q_tile
+#include "inv_cols_r_body.h"
+#undef ASX_INV_BODY_TILE
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 static bool schedule_is_r(const AsxStages &st, int n, std::initializer_list<int> radices)
@@ -846,6 +994,27 @@ bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, floa
     ASX_ROWSR_CASE(64, false, 480, 10, 8, 6)
 #undef ASX_ROWSR_CASE
 #undef ASX_ROWSR_LAUNCH
+    return false;
+}
+
+// the row pass of the pruned inverse pass: k_rows_r<..., 0> plus the tile energies U.eng
+bool asx_launch_rows_re(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, const AsxPrune &U,
+                        int npairs, hipStream_t s)
+{
+    if (P.T != ASX_PRUNE_T) return false;
+    const int nrows = P.M1 + 1;
+    const size_t pitch = (size_t)nrows * (size_t)P.M2;
+    const size_t lds = (size_t)P.M2 * sizeof(float4);
+#define ASX_ROWSRE_CASE(nt, two, n, ...)                                                                                        \
+    if (P.M2 == ((two) ? 2 * n : n)) {                                                                                          \
+        hipLaunchKernelGGL((k_rows_re<Sched<n, __VA_ARGS__>, nt, two>), dim3((unsigned)nrows * (unsigned)npairs),               \
+                           dim3((two) ? 2 * nt : nt), lds, s, rargs_of(P), cx, cy, q, nrows, pitch, W, U.eng);                   \
+        return true;                                                                                                            \
+    }
+    ASX_ROWSRE_CASE(128, false, 1200, 12, 10, 10)
+    ASX_ROWSRE_CASE(128, true, 1200, ASX_ROWS2_SCHED)
+    ASX_ROWSRE_CASE(64, false, 480, 10, 8, 6)
+#undef ASX_ROWSRE_CASE
     return false;
 }
 
@@ -981,6 +1150,32 @@ bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W,
     ASX_RCOLS(ASX_TRY)
 #undef ASX_TRY
 #undef ASX_RX
+    return false;
+}
+
+// The pruned inverse pass over the Q and the tile energies asx_launch_rows_re left: bounds, the two likely tiles, the flags, the rest.
+bool asx_launch_inv_cols_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, const AsxPrune &U, int npairs, hipStream_t s)
+{
+    if (!P.col_pairs || P.T != ASX_PRUNE_T || P.M2 % ASX_PRUNE_T != 0 || P.ntiles > 1024) return false;
+    const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2;
+#define ASX_TRY(m1, t, nt, ...)                                                                                             \
+    if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                                                          \
+        const size_t lds = (size_t)(m1) * (t) * sizeof(float2);                                                             \
+        auto k1 = k_inv_cols_rq<Sched<m1, __VA_ARGS__>, t, nt, true>;                                                       \
+        auto k2 = k_inv_cols_rq<Sched<m1, __VA_ARGS__>, t, nt, false>;                                                      \
+        allow_big_lds_r((const void *)k1, lds);                                                                             \
+        allow_big_lds_r((const void *)k2, lds);                                                                             \
+        hipLaunchKernelGGL(k_tile_bounds, dim3(npairs), dim3(1024), 0, s, U.eng, U.ub, U.best, P.M1 + 1, P.ntiles,          \
+                           4.0 * (double)P.M1, ASX_PRUNE_FLOOR_PER_TERM * (double)ASX_PRUNE_T * (double)(P.M1 + 1));        \
+        hipLaunchKernelGGL(k1, dim3(npairs, 2), dim3(nt), lds, s, rargs_of(P), q, pitch, W,                                 \
+                           resident_blocks((const void *)k1, nt, lds), U.best, U.skip);                                     \
+        hipLaunchKernelGGL(k_prune_select, dim3(npairs), dim3(256), 0, s, U.ub, U.best, U.skip, W, P.ntiles, U.stats);      \
+        hipLaunchKernelGGL(k2, dim3(npairs, rcol_grid_x(P.ntiles, asx_ilog2(t))), dim3(nt), lds, s, rargs_of(P), q, pitch, W, \
+                           resident_blocks((const void *)k2, nt, lds), U.best, U.skip);                                     \
+        return true;                                                                                                        \
+    }
+    ASX_RCOLS(ASX_TRY)
+#undef ASX_TRY
     return false;
 }
 

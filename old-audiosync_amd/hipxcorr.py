@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "asx_plan_set_pearson", "asx_plan_pearson_modes", "asx_plan_placement", "asx_host_malloc", "asx_host_free", "asx_shard_range", "asx_result_bytes", "asx_comm_create", "asx_comm_destroy", "asx_xcorr_batch_multi_dev",
     "asx_xcorr_strided_f32_dev", "asx_plan_set_lag_window", "asx_plan_lag_window", "asx_stream_set_lag_window",
     "asx_xcorr_windowed_f32_dev", "asx_xcorr_topk_f32_dev", "asx_xcorr_pool_f32_dev", "asx_xcorr_pool_topk_f32_dev",
-    "asx_topk_best_dev",
+    "asx_topk_best_dev", "asx_plan_set_prune", "asx_plan_prune_stats",
 ]
 
 TOPK_MAX = 8  # ASX_TOPK_MAX, include/audiosync/xcorr_hip.h
@@ -88,6 +88,10 @@ def lib():
     L.asx_plan_set_pearson.argtypes = [vp, ctypes.c_int]
     L.asx_plan_pearson_modes.restype = ctypes.c_int
     L.asx_plan_pearson_modes.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.asx_plan_set_prune.restype = ctypes.c_int
+    L.asx_plan_set_prune.argtypes = [vp, ctypes.c_int]
+    L.asx_plan_prune_stats.restype = ctypes.c_int
+    L.asx_plan_prune_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.asx_plan_peak_repairs.restype = ctypes.c_int
     L.asx_plan_peak_repairs.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.asx_plan_narrowed_calls.restype = ctypes.c_int
@@ -602,6 +606,19 @@ class Plan:
             raise AsxError(_err())
         return tuple(int(v) for v in c)
 
+    def set_prune(self, on=True):
+        """on (the default on real-column plans): in-scope groups skip the inverse column tiles whose energy bound rules out the
+        peak and its near-ties; same lag, ret and coefficient bits either way (include/audiosync/xcorr_hip.h)"""
+        if lib().asx_plan_set_prune(self._h, 1 if on else 0) != 0:
+            raise AsxError(_err())
+
+    def prune_stats(self):
+        """(column tiles the pruned groups transformed, tiles those groups had in all) over the plan's life"""
+        a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if lib().asx_plan_prune_stats(self._h, ctypes.byref(a), ctypes.byref(b)) != 0:
+            raise AsxError(_err())
+        return int(a.value), int(b.value)
+
     def narrowed_calls(self):
         """xcorr_f64 calls whose frames were all exactly float32 and crossed PCIe as 4 bytes each"""
         c = ctypes.c_uint64(0)
@@ -719,6 +736,18 @@ class Plan:
                                                int(k), int(min_separation), d_lag or None, d_coef, d_ret, stream or None)
         if rc != 0:
             raise AsxError(_err())
+
+    def debug_prune(self, pair=0):
+        """diagnostic: (upper bounds of |r| per column tile, the largest-bound tile) of `pair` of the last pruned group"""
+        n = (self.split[1] + self.split[2] - 1) // self.split[2]
+        ub = (ctypes.c_float * n)()
+        best = ctypes.c_int(-1)
+        f = lib().asx_plan_debug_prune
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), ctypes.c_size_t]
+        if f(self._h, int(pair), ub, ctypes.byref(best), n) != 0:
+            raise AsxError("asx_plan_debug_prune failed")
+        return np.frombuffer(ub, dtype=np.float32).copy(), int(best.value)
 
     def debug_bank(self):
         """(source tracks, sample tracks) the plan's pool bank holds, and how many pool calls have filled it"""

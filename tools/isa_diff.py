@@ -50,6 +50,11 @@ def kernels(path):
                 elif cur is not None and line.strip():
                     ins = re.sub(r"\s*//.*$", "", line.strip())
                     found[cur].append(re.sub(r"<\S+>", "<L>", ins))
+    # what follows a kernel's last instruction up to the next symbol is alignment padding (s_nop / s_code_end runs, "..."): its
+    # length depends on what the linker placed next, not on the kernel
+    for v in found.values():
+        while v and (v[-1].startswith("s_nop") or v[-1].startswith("s_code_end") or v[-1] == "..."):
+            v.pop()
     return {k: v for k, v in found.items() if k.startswith("_Z")}
 
 
