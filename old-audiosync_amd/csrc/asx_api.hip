@@ -137,19 +137,13 @@ struct asx_plan {
     // Broadcast slot of asx_xcorr_strided_f32_dev (real-column plans, lazy, like BigPeak): the forward column pass of a track that
     // every pair of a call shares (a stride of 0) -- C_x / C_y of ONE pair, its norm partials and band sums in the AsxPeakWs layout
     // of pair 0 -- written once per call before the launch groups, read by every group's row kernel (k_rows_r, BC != 0)
-    struct Bcast {
-        float2 *cx = nullptr, *cy = nullptr;
-        float *nrm = nullptr;
-        float2 *band = nullptr;
-    } bslot;
+    AsxSpectra bslot{};
     // Bank of asx_xcorr_pool_f32_dev (real-column plans; allocated at the first pool call, grown when a call names more tracks): the
     // forward column pass of every track of a call's two pools -- source a at row a of cx, sample b at row b of cy, their norm partials
     // and band sums in the AsxPeakWs layout of "pair" a, operand 0, and "pair" b, operand 1 -- written once per call before the launch
     // groups, read by slot (k_pool_resolve, k_rows_rl).  Its own allocations: not part of asx_plan_workspace_bytes.
     struct Bank {
-        float2 *cx = nullptr, *cy = nullptr;
-        float *nrm = nullptr;
-        float2 *band = nullptr;
+        AsxSpectra c{};
         size_t nsrc = 0, nsmp = 0;      // capacity in tracks
         unsigned long long fills = 0;   // pool calls that filled it (diagnostic: asx_plan_debug_bank)
     } bank;
@@ -163,6 +157,7 @@ struct asx_plan {
     int64_t win_lo = 0, win_hi = 0;    // asx_plan_set_lag_window: the lags whose peak is searched, [-N, N-1] (set at creation) = all
     bool spectral = false;             // float32 groups take the spectral Pearson form (asx_plan_set_pearson; real-column plans)
     unsigned long long *mode_count = nullptr; // [ASX_PM_NMODES], cumulative over the plan's life
+    bool prunable = false;             // asx_rlayout_prunable, asked once (plan_init): the lanes have their AsxPrune workspaces
     bool prune = false;                // asx_plan_set_prune: in-scope groups skip the inverse column tiles a bound rules out
     unsigned long long *prune_stats = nullptr; // [2] tiles transformed, tiles in all, by the pruned groups; cumulative
     // "measure" plans only: at the first device-resident batch the forward column kernel is timed against the caller's buffers
@@ -260,6 +255,7 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
             d.rlayout = asx_rlayout_available(d) ? 1 : 0;
             d.band_rows = d.rlayout ? asx_rlayout_band_rows(d) : 0;
             d.nbands = d.band_rows ? 2 * h.M1 / d.band_rows : 0;
+            p->prunable = asx_rlayout_prunable(d);
         }
     }
     // group size: keep the three inter-kernel intermediates (24*M bytes per pair) of one
@@ -308,6 +304,8 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
                 return -1;
             ln.spec.mode_count = p->mode_count;
             ln.spec.tol = 1e-5;
+        }
+        if (p->prunable) {
             // pruned inverse pass: 4 (M1 + 1) ntiles bytes per pair, about 1 % of Q; the group size does not depend on it
             if (!p->prune_stats) {
                 if (dev_alloc(p, &p->prune_stats, 2)) return -1;
@@ -343,7 +341,7 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
     }
     p->spectral = d.rlayout != 0;
     if (const char *e = getenv("ASX_PEARSON")) p->spectral = p->spectral && strcmp(e, "direct") != 0; // A/B of the two forms
-    p->prune = d.rlayout != 0 && d.T == ASX_PRUNE_T && h.M2 % ASX_PRUNE_T == 0;
+    p->prune = p->prunable;
     if (const char *e = getenv("ASX_PRUNE")) p->prune = p->prune && atoi(e) != 0; // A/B of the pruned inverse pass
     if (const char *e = getenv("ASX_EXACT")) p->exact = atoi(e) != 0; // initial value of asx_plan_set_exact (A/B of its cost)
     p->win_lo = -(int64_t)p->host.N; // the full lag window
@@ -492,7 +490,7 @@ extern "C" void asx_plan_destroy(asx_plan *p)
     for (auto &ring : p->evr)
         for (hipEvent_t ev : ring) (void)hipEventDestroy(ev);
     for (void *a : p->allocs) (void)hipFree(a);
-    for (void *a : { (void *)p->bank.cx, (void *)p->bank.cy, (void *)p->bank.nrm, (void *)p->bank.band })
+    for (void *a : { (void *)p->bank.c.cx, (void *)p->bank.c.cy, (void *)p->bank.c.nrm, (void *)p->bank.c.band })
         if (a) (void)hipFree(a);
     if (p->pin32) (void)hipHostFree(p->pin32);
     if (p->h_over_n) (void)hipHostFree((void *)p->h_over_n);
@@ -575,7 +573,7 @@ extern "C" int asx_plan_set_prune(asx_plan *p, int on)
 {
     if (!p) return fail("asx_plan_set_prune: null argument");
     std::lock_guard<std::mutex> guard(p->lock);
-    if (on && !(p->dev.rlayout && p->dev.T == ASX_PRUNE_T && p->lanes[0].prune.eng))
+    if (on && !p->prunable)
         return fail("asx_plan_set_prune: the pruned inverse pass needs a real-column plan (the reference's six lengths)");
     p->prune = on != 0;
     return 0;
@@ -754,11 +752,40 @@ template <typename TIn> struct Pairs {
     size_t win_step = 0;
     const PoolCall *pool = nullptr;
     size_t first = 0;
+    // The shapes the entry points use.  staged: pair k at [k][2N] / [k][N], the transforms' float32 views apart from what the exact
+    // passes read (the double ABI, the second look's source minus its mean); win: one pair's window row, or null.
+    static Pairs staged(const float *src, const float *smp, const TIn *tsrc, const TIn *tsmp, size_t N, const int64_t *win = nullptr,
+                        size_t win_step = 0)
+    {
+        return { .src = src, .smp = smp, .tsrc = tsrc, .tsmp = tsmp, .src_step = 2 * N, .smp_step = N, .bc = 0, .win = win, .win_step = win_step };
+    }
+    // contiguous float32 pairs, [batch][2N] and [batch][N]
+    static Pairs contiguous(const float *src, const float *smp, size_t N) { return staged(src, smp, src, smp, N); }
+    // float32 pairs src_step / smp_step apart (0: the call's broadcast track, whose bit of bc a real-column plan sets), per-pair windows or null
+    static Pairs strided(const float *src, size_t src_step, const float *smp, size_t smp_step, int bc, const int64_t *win, size_t win_step)
+    {
+        return { .src = src, .smp = smp, .tsrc = src, .tsmp = smp, .src_step = src_step, .smp_step = smp_step, .bc = bc, .win = win, .win_step = win_step };
+    }
+    // the pairs of a pool call: the two pools and their strides, pair k = the call's pair k
+    static Pairs pooled(const PoolCall *pool, const float *srcs, size_t src_stride, const float *smps, size_t smp_stride, const int64_t *win,
+                        size_t win_step)
+    {
+        Pairs x = strided(srcs, src_stride, smps, smp_stride, 0, win, win_step);
+        x.pool = pool;
+        return x;
+    }
+    // one pair of a pool call on explicit pointers (the second look): source a against sample b, with this pair's window row
+    Pairs pool_pair(size_t a, size_t b, size_t N) const
+    {
+        return staged(src + a * src_step, smp + b * smp_step, tsrc + a * src_step, tsmp + b * smp_step, N, win, win_step);
+    }
     Pairs at(size_t k) const
     {
-        if (pool) return { src, smp, tsrc, tsmp, src_step, smp_step, bc, win ? win + 2 * k * win_step : nullptr, win_step, pool, first + k };
-        return { src + k * src_step, smp + k * smp_step, tsrc + k * src_step, tsmp + k * smp_step, src_step, smp_step, bc,
-                 win ? win + 2 * k * win_step : nullptr, win_step };
+        Pairs x = *this;
+        if (win) x.win += 2 * k * win_step;
+        if (pool) { x.first += k; return x; }
+        x.src += k * src_step; x.smp += k * smp_step; x.tsrc += k * src_step; x.tsmp += k * smp_step;
+        return x;
     }
     // what the exact passes read (pl: the group's resolved records in a pool call, else null)
     AsxInputs<TIn> inputs(const AsxPoolPair *pl) const { return { tsrc, tsmp, src_step, smp_step, pl }; }
@@ -816,20 +843,34 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     const bool spectral = std::is_same<TIn, float>::value && p->spectral && o.spectral && pk.band;
     AsxPeakWs tk = pk; // what the transform kernels see
     if (!spectral) { tk.band = nullptr; tk.tile_peak = nullptr; }
-    if (mark(0)) return -1;
-    // pool calls: the bank holds every track's forward column pass; this group only resolves its pairs into slots and offsets
+    // The pruned pair of passes (rlayout.hip: k_rows_re, and k_tile_bounds and k_inv_cols_rq around k_prune_select) in place of the row pass
+    // and the inverse column pass:
+    // a float32 entry point's group on a real-column plan, every lag competing, no broadcast operand and no pool, one pass, r not asked
+    // for, the lane's own lists (not the second look).  Everything else launches what it always did.
+    // (GroupOpts::spectral is how an entry point says "float32 ABI": the double ABI clears it even when its frames were narrowed.
+    // Whether the plan's Pearson form IS spectral -- p->spectral -- plays no part here.  p->prune is only ever set on a plan the
+    // pruned pass can run on: asx_rlayout_prunable.)
+    const bool f32_entry = std::is_same<TIn, float>::value && o.spectral;
+    const AsxSearch call = AsxSearch::of(p->win_lo, p->win_hi, P.N, x.win, x.win_step, W.tk, 0); // pass 1's search
+    const bool prune = p->prune && f32_entry && !x.pool && x.bc == 0 && !o.r_out && !o.pk && o.topk.k == 1 && call.kind == AsxSearch::ALL;
+    // The group's spectra (AsxSpectra): the lane's own forward passes -- but a broadcast operand's rows are in the plan's slot, and a
+    // pool group's in the bank, found through its resolved records -- with the norm partials and band sums always in the lane's places.
     const AsxPoolPair *pl = x.pool ? W.pool : nullptr;
-    if (x.pool) {
+    const AsxSpectra &from = pl ? p->bank.c : p->bslot;
+    const AsxSpectra C{ (pl || (x.bc & 1)) ? from.cx : W.zxa, (pl || (x.bc & 2)) ? from.cy : W.zya, pk.nrm_part, tk.band, x.bc, pl,
+                        prune ? &W.prune : nullptr };
+    if (mark(0)) return -1;
+    if (pl) {
+        // pool calls: the bank holds every track's forward column pass; this group only resolves its pairs into slots and offsets
         const AsxPoolArgs A{ x.pool->rows, (uint64_t)x.first, (uint64_t)x.pool->nsrc, (uint64_t)x.pool->nsmp, (uint64_t)x.src_step,
-                             (uint64_t)x.smp_step, p->bank.nrm, p->bank.band };
-        asx_launch_pool_resolve(P, A, W.pool, pk.nrm_part, tk.band, (int)g, s);
+                             (uint64_t)x.smp_step, from.nrm, from.band };
+        asx_launch_pool_resolve(P, A, W.pool, C.nrm, C.band, (int)g, s);
     } else if (P.rlayout) {
-        const int op0 = x.bc & 1, nops = 2 - (x.bc & 1) - ((x.bc >> 1) & 1);
-        if (nops > 0 && !asx_launch_fwd_cols_r(P, x.src, x.src_step, x.smp, x.smp_step, W.zxa, W.zya, pk.nrm_part, tk.band, (int)g, op0,
-                                               nops, false, s))
+        // the operands that are not the call's broadcast track, whose pass is in the slot: only its norm partials and band sums are copied
+        if (!asx_launch_fwd_cols_r(P, (x.bc & 1) ? nullptr : x.src, x.src_step, (x.bc & 2) ? nullptr : x.smp, x.smp_step, 0, (int)g, C, false, s))
             return fail("internal: no forward column kernel for this plan");
         for (unsigned which = 0; which < 2; which++)
-            if (x.bc & (1 << which)) asx_launch_bcast_aux(P, p->bslot.nrm, p->bslot.band, pk.nrm_part, tk.band, (int)g, which, s);
+            if (x.bc & (1 << which)) asx_launch_bcast_aux(P, from.nrm, from.band, C.nrm, C.band, (int)g, which, s);
     } else if (x.src_step == 2 * (size_t)P.N && x.smp_step == P.N) {
         asx_launch_fwd_cols(P, x.src, x.smp, W.zxa, W.zya, tk, (int)g, s);
     } else {
@@ -843,25 +884,8 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     }
     if (mark(1)) return -1;
     float2 *q = W.ga;
-    // The pruned pair of passes (rlayout.hip: k_rows_re, asx_launch_inv_cols_rq) in place of the row pass and the inverse column pass:
-    // a float32 entry point's group on a real-column plan, every lag competing, no broadcast operand and no pool, one pass, r not asked
-    // for, the lane's own lists (not the second look).  Everything else launches what it always did.
-    // (GroupOpts::spectral is how an entry point says "float32 ABI": the double ABI clears it even when its frames were narrowed.
-    // Whether the plan's Pearson form IS spectral -- p->spectral -- plays no part here.)
-    const bool f32_entry = std::is_same<TIn, float>::value && o.spectral;
-    const AsxSearch call = AsxSearch::of(p->win_lo, p->win_hi, P.N, x.win, x.win_step, W.tk, 0); // pass 1's search
-    const bool prune = p->prune && P.rlayout && f32_entry && !x.pool && x.bc == 0 && !o.r_out && !o.pk && o.topk.k == 1 &&
-                       call.kind == AsxSearch::ALL;
-    if (prune) {
-        if (!asx_launch_rows_re(P, W.zxa, W.zya, q, tk, W.prune, (int)g, s)) return fail("internal: no row kernel for this plan");
-    } else if (x.pool) {
-        if (!asx_launch_rows_rl(P, p->bank.cx, p->bank.cy, q, tk, pl, (int)g, s)) return fail("internal: no row kernel for this plan");
-    } else if (P.rlayout) {
-        if (!asx_launch_rows_r(P, (x.bc & 1) ? p->bslot.cx : W.zxa, (x.bc & 2) ? p->bslot.cy : W.zya, q, tk, (int)g, x.bc, s))
-            return fail("internal: no row kernel for this plan");
-    } else {
-        asx_launch_rows(P, W.zxa, W.zya, q, tk, (int)g, s);
-    }
+    if (!P.rlayout) asx_launch_rows(P, W.zxa, W.zya, q, tk, (int)g, s);
+    else if (!asx_launch_rows_r(P, C, q, tk, (int)g, s)) return fail("internal: no row kernel for this plan");
     if (mark(2)) return -1;
     // Top-k (o.topk.k > 1): every pass's results go to the lane's temporaries, and k_topk_step moves them to entry j of y
     const int K = o.topk.k;
@@ -879,11 +903,9 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // One pass over the group's Q: the inverse columns, finalize, the exact re-evaluation and Pearson, the lags of `find` competing.
     // first: pass 1, which the profiling marks time and whose r goes to o.r_out.
     auto pass = [&](const AsxSearch &find, bool first) -> int {
-        if (prune) {
-            if (!asx_launch_inv_cols_rq(P, q, tk, W.prune, (int)g, s)) return fail("internal: no inverse column kernel for this plan");
-        } else {
-            asx_launch_inv_cols(P, q, tk, first ? o.r_out : nullptr, (int)g, s, find);
-        }
+        float *const r_out = first ? o.r_out : nullptr;
+        if (!P.rlayout) asx_launch_inv_cols(P, q, tk, r_out, (int)g, s, find);
+        else if (!asx_launch_inv_cols_r(P, q, tk, r_out, (int)g, s, find, C.prune)) return fail("internal: no inverse column kernel for this plan");
         if (first && mark(3)) return -1;
         asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, find);
         // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
@@ -959,7 +981,7 @@ static int second_look(asx_plan *p, const Pairs<TIn> &xi, const Results &yi, hip
     // r = r' + stats[2]
     asx_launch_dc_remove(xi.tsrc, xi.tsmp, P.N, (double)P.F, B.stats, B.src_dc, s);
     K.shift = B.stats + 2;
-    if (run_group(p, Pairs<TIn>{ B.src_dc, xi.smp, xi.tsrc, xi.tsmp, 2 * N, N, 0, xi.win, xi.win_step }, 1, yi, s,
+    if (run_group(p, Pairs<TIn>::staged(B.src_dc, xi.smp, xi.tsrc, xi.tsmp, N, xi.win, xi.win_step), 1, yi, s,
                   { .prof_group = GroupOpts::no_marks, .listed = false, .spectral = false, .dot_blocks = 2048, .pk = &K, .topk = topk }))
         return -1;
     p->repaired++;
@@ -1006,9 +1028,7 @@ static int resolve_overflows(asx_plan *p, const Pairs<TIn> &x, const Results &y,
         if (x.pool) {
             const int64_t a = ab[2 * k], b = ab[2 * k + 1];
             if (a < 0 || (size_t)a >= x.pool->nsrc || b < 0 || (size_t)b >= x.pool->nsmp) continue; // (k_rows_rl never lets one overflow)
-            const size_t N = p->host.N;
-            xi = Pairs<TIn>{ x.src + (size_t)a * x.src_step, x.smp + (size_t)b * x.smp_step, x.tsrc + (size_t)a * x.src_step,
-                             x.tsmp + (size_t)b * x.smp_step, 2 * N, N, 0, xi.win, xi.win_step };
+            xi = xi.pool_pair((size_t)a, (size_t)b, p->host.N);
         }
         if (second_look(p, xi, y.at(i), s, topk)) return -1;
     }
@@ -1158,7 +1178,7 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
     if (p->tune_placement && !p->placement_done && batch >= std::min<size_t>(p->group, 8) && // (lane 0's workspaces; a second lane keeps its own)
         tune_placement(p, d_source, d_sample, std::min(batch, p->group), c.s))
         return -1;
-    return run_batch(p, { d_source, d_sample, d_source, d_sample, 2 * N, N, 0 }, batch, { d_lag, d_coef, d_ret }, c.s);
+    return run_batch(p, Pairs<float>::contiguous(d_source, d_sample, N), batch, { d_lag, d_coef, d_ret }, c.s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1186,12 +1206,12 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
     if (batch == 0) return 0;
     const int bc = P.rlayout ? (source_stride == 0 ? 1 : 0) | (sample_stride == 0 ? 2 : 0) : 0;
     if (bc) {
-        asx_plan::Bcast &B = p->bslot;
+        AsxSpectra &B = p->bslot;
         if (!B.cx) {
             if (stream_capturing(s))
                 return fail("%s: the plan's broadcast workspace does not exist yet and cannot be allocated "
                             "during a stream capture; make one call with a stride of 0 outside the capture first", fn);
-            asx_plan::Bcast T;
+            AsxSpectra T{};
             const size_t mz = ((size_t)p->host.M1 + 1) * (size_t)p->host.M2;
             if (dev_alloc(p, &T.cx, mz) || dev_alloc(p, &T.cy, mz) || dev_alloc(p, &T.nrm, 2 * (size_t)P.ntiles) ||
                 (P.nbands && dev_alloc(p, &T.band, 2 * (size_t)P.ntiles * (size_t)P.nbands)))
@@ -1199,11 +1219,10 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
             B = T;
         }
         // the shared track's forward column pass: once per call, on the caller's stream, before any lane forks
-        const int op0 = (bc & 1) ? 0 : 1, nops = bc == 3 ? 2 : 1;
-        if (!asx_launch_fwd_cols_r(P, d_source, 0, d_sample, 0, B.cx, B.cy, B.nrm, B.band, 1, op0, nops, true, s))
+        if (!asx_launch_fwd_cols_r(P, (bc & 1) ? d_source : nullptr, 0, (bc & 2) ? d_sample : nullptr, 0, 0, 1, B, true, s))
             return fail("internal: no forward column kernel for this plan");
     }
-    return run_batch(p, { d_source, d_sample, d_source, d_sample, source_stride, sample_stride, bc, d_windows, window_stride }, batch, y, s,
+    return run_batch(p, Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, bc, d_windows, window_stride), batch, y, s,
                      topk);
 }
 
@@ -1256,16 +1275,16 @@ static int ensure_bank(asx_plan *p, const char *fn, size_t nsrc, size_t nsmp, hi
     const size_t ns = std::max(nsrc, B.nsrc), nm = std::max(nsmp, B.nsmp), na = std::max(ns, nm);
     const size_t pitch = ((size_t)p->host.M1 + 1) * (size_t)p->host.M2, nb = (size_t)P.ntiles * (size_t)P.nbands;
     HIP_TRY(hipDeviceSynchronize());
-    for (void *a : { (void *)B.cx, (void *)B.cy, (void *)B.nrm, (void *)B.band })
+    for (void *a : { (void *)B.c.cx, (void *)B.c.cy, (void *)B.c.nrm, (void *)B.c.band })
         if (a) (void)hipFree(a);
-    B = asx_plan::Bank{ nullptr, nullptr, nullptr, nullptr, 0, 0, B.fills };
+    B = asx_plan::Bank{ {}, 0, 0, B.fills };
     asx_plan::Bank T = B;
-    if (hipMalloc((void **)&T.cx, ns * pitch * sizeof(float2)) != hipSuccess ||
-        hipMalloc((void **)&T.cy, nm * pitch * sizeof(float2)) != hipSuccess ||
-        hipMalloc((void **)&T.nrm, na * 2 * (size_t)P.ntiles * sizeof(float)) != hipSuccess ||
-        (nb && hipMalloc((void **)&T.band, na * 2 * nb * sizeof(float2)) != hipSuccess)) {
+    if (hipMalloc((void **)&T.c.cx, ns * pitch * sizeof(float2)) != hipSuccess ||
+        hipMalloc((void **)&T.c.cy, nm * pitch * sizeof(float2)) != hipSuccess ||
+        hipMalloc((void **)&T.c.nrm, na * 2 * (size_t)P.ntiles * sizeof(float)) != hipSuccess ||
+        (nb && hipMalloc((void **)&T.c.band, na * 2 * nb * sizeof(float2)) != hipSuccess)) {
         (void)hipGetLastError();
-        for (void *a : { (void *)T.cx, (void *)T.cy, (void *)T.nrm, (void *)T.band })
+        for (void *a : { (void *)T.c.cx, (void *)T.c.cy, (void *)T.c.nrm, (void *)T.c.band })
             if (a) (void)hipFree(a);
         return fail("%s: cannot allocate the plan's bank for %zu source and %zu sample tracks (%zu bytes per track)", fn, ns, nm,
                     pitch * sizeof(float2));
@@ -1300,26 +1319,17 @@ static int pool_batch(asx_plan *p, const char *fn, const float *d_sources, size_
     if (ensure_bank(p, fn, nsources, nsamples, s)) return -1;
     // the bank fill: every track's forward column pass, once per call, on the caller's stream before any lane forks (grid.z: at most
     // 65535 tracks per launch)
-    asx_plan::Bank &B = p->bank;
-    const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, nt = (size_t)P.ntiles, nb = nt * (size_t)P.nbands;
     for (int op = 0; op < 2; op++) {
         const size_t n = op ? nsamples : nsources;
-        for (size_t c0 = 0; c0 < n; c0 += 65535) {
-            const size_t c = std::min<size_t>(65535, n - c0);
-            const bool ok = op == 0 ? asx_launch_fwd_cols_r(P, d_sources + c0 * source_stride, source_stride, d_samples, 0, B.cx + c0 * pitch,
-                                                            B.cy, B.nrm + c0 * 2 * nt, B.band ? B.band + c0 * 2 * nb : nullptr, (int)c, 0, 1,
-                                                            true, s)
-                                    : asx_launch_fwd_cols_r(P, d_sources, 0, d_samples + c0 * sample_stride, sample_stride, B.cx,
-                                                            B.cy + c0 * pitch, B.nrm + c0 * 2 * nt, B.band ? B.band + c0 * 2 * nb : nullptr,
-                                                            (int)c, 1, 1, true, s);
-            if (!ok) return fail("internal: no forward column kernel for this plan");
-        }
+        for (size_t c0 = 0; c0 < n; c0 += 65535)
+            if (!asx_launch_fwd_cols_r(P, op ? nullptr : d_sources, source_stride, op ? d_samples : nullptr, sample_stride, c0,
+                                       (int)std::min<size_t>(65535, n - c0), p->bank.c, true, s))
+                return fail("internal: no forward column kernel for this plan");
     }
-    B.fills++;
+    p->bank.fills++;
     const PoolCall pool{ d_pairs, nsources, nsamples };
-    Pairs<float> x{ d_sources, d_samples, d_sources, d_samples, source_stride, sample_stride, 0, d_windows, window_stride };
-    x.pool = &pool;
-    return run_batch(p, x, batch, y, s, topk);
+    return run_batch(p, Pairs<float>::pooled(&pool, d_sources, source_stride, d_samples, sample_stride, d_windows, window_stride), batch, y,
+                     s, topk);
 }
 
 extern "C" int asx_xcorr_pool_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
@@ -1367,7 +1377,7 @@ extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const f
     // like every other entry point: listed and looked at again in the exact mode, only marked (ret = 1) otherwise
     // (the direct Pearson form: this entry point exists to compare decompositions and to dump r)
     const size_t N = p->host.N;
-    const Pairs<float> x{ d_source, d_sample, d_source, d_sample, 2 * N, N, 0 };
+    const Pairs<float> x = Pairs<float>::contiguous(d_source, d_sample, N);
     const Results y{ d_lag, d_coef, d_ret };
     int rc = run_group(p, x, 1, y, c.s, { .listed = p->exact, .spectral = false, .r_out = d_r });
     prof_end_call(p, 1);
@@ -1394,7 +1404,7 @@ extern "C" int asx_xcorr_batch_f32(asx_plan *p, const float *source, const float
     if (ensure_staging(p)) return -1;
     const size_t N = p->host.N;
     hipStream_t s = c.s;
-    const Pairs<float> x{ p->st_src, p->st_smp, p->st_src, p->st_smp, 2 * N, N, 0 };
+    const Pairs<float> x = Pairs<float>::contiguous(p->st_src, p->st_smp, N);
     const Results d{ p->st_lag, p->st_coef, p->st_ret };
     prof_begin_call(p);
     for (size_t done = 0; done < batch; done += p->group) {
@@ -1648,7 +1658,7 @@ template <typename TIn>
 static int staged_pair(asx_plan *p, const TIn *tsrc, const TIn *tsmp, const Results &h, hipStream_t s)
 {
     const size_t N = p->host.N;
-    const Pairs<TIn> x{ p->st_src, p->st_smp, tsrc, tsmp, 2 * N, N, 0 };
+    const Pairs<TIn> x = Pairs<TIn>::staged(p->st_src, p->st_smp, tsrc, tsmp, N);
     const Results d{ p->st_lag, p->st_coef, p->st_ret };
     return run_group(p, x, 1, d, s, { .spectral = false }) || fetch_results(p, x, 1, d, h, s) ? -1 : 0;
 }
@@ -1936,7 +1946,7 @@ extern "C" int asx_stream_xcorr(asx_stream *st, size_t sample_len, long *lag, do
     int64_t h_lag = 0;
     double h_coef = 0;
     int32_t h_ret = -1;
-    const Pairs<double> x{ st->src32, st->smp32, st->src64, st->smp64, 2 * sample_len, sample_len, 0 };
+    const Pairs<double> x = Pairs<double>::staged(st->src32, st->smp32, st->src64, st->smp64, sample_len);
     const Results d{ st->d_lag, st->d_coef, st->d_ret };
     if (run_group(p, x, 1, d, c.s) || fetch_results(p, x, 1, d, { &h_lag, &h_coef, &h_ret }, c.s)) return -1;
     *lag = (long)h_lag;

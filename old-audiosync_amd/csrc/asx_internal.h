@@ -326,6 +326,25 @@ struct AsxPrune {
     unsigned long long *stats; // [2] tiles transformed, tiles in all: cumulative over the plan's life (asx_plan_prune_stats)
 };
 
+// Where forward column passes are (real-column plans), and how the pairs of a launch group find theirs: the host's one statement of
+// that.  Host only, never a kernel argument: the launchers of rlayout.hip unpack it.
+//   As a set of passes -- the lane's workspace, the plan's broadcast slot, the plan's bank -- track t has C_x / C_y at cx / cy +
+//   t (M1 + 1) M2 and its norm partials and band sums at slot t of the AsxPeakWs layouts (source: operand 0, sample: operand 1).
+//   asx_launch_fwd_cols_r fills tracks of one.
+//   As a group's spectra it adds where pair i's rows are: cx + i pitch and cy + i pitch (the lane's workspace); one track for every
+//   pair for the operands of `bc` (bit 0: cx, bit 1: cy -- the broadcast slot's, pitch 0); or rows pl[i].sx of cx and pl[i].sy of cy
+//   (a pool group: cx / cy are the bank's).  nrm and band are then the group's own places (the lane's), whatever cx / cy are: a
+//   broadcast or listed operand's are copied there (k_bcast_aux, k_pool_resolve).  asx_launch_rows_r picks its kernel by it.
+//   prune: the lane's workspace of the pruned inverse pass when the group is in scope for it (run_group decides), else null.
+struct AsxSpectra {
+    float2 *cx, *cy;
+    float *nrm;
+    float2 *band;                 // may be null: no band sums
+    int bc = 0;
+    const AsxPoolPair *pl = nullptr;
+    const AsxPrune *prune = nullptr;
+};
+
 // Spectral Pearson: the coefficient from r[peak] and window sums instead of a second pass over the inputs.
 // Modes a pair can take (k_pearson_prep decides, k_pearson_partial / k_pearson_final_spec act on it):
 #define ASX_PM_FAST 0    // lag >= 0: cross term = r[peak], window sums from the band sums + two band edges; nothing else is read
@@ -353,37 +372,31 @@ struct AsxSpecWs {
 
 void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, float2 *zxa,
                          float2 *zya, const AsxPeakWs &W, int npairs, hipStream_t s);
-void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga,
+void asx_launch_rows(const AsxDev &P, float2 *zxa, float2 *zya, float2 *ga,
                      const AsxPeakWs &W, int npairs, hipStream_t s);
 // q: which flavour of the inverse column kernel runs (AsxSearch)
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                          const AsxSearch &q);
-// rlayout.hip: the real-column decomposition (production lengths); false = no kernel compiled in for this plan.
-// bc (the broadcast forms of asx_xcorr_strided_f32_dev): bit 0 = cx is the plan's broadcast slot (one C for every pair), bit 1 = cy is
-bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
-                       hipStream_t s);
-bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
-                           float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s);
+// rlayout.hip: the real-column decomposition (production lengths); false = no kernel compiled in for this plan.  Which flavour of a
+// kernel runs is the launcher's decision: the row launcher reads it from the group's AsxSpectra, the inverse launcher from the search
+// and from U (the AsxPrune of a group in scope for pruning, else null), the forward launcher from the operands it is given (null: not
+// that operand) -- tracks first .. first + count - 1 of each, into the same tracks of dst.
+bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, size_t first,
+                           int count, const AsxSpectra &dst, bool temporal, hipStream_t s);
+bool asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s);
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
-                           const AsxSearch &search);
-// The pruned pair (every lag competes, no broadcast operand, no r_out): the row pass that also leaves U.eng, and the inverse pass
-// that reads it -- bounds, two tiles per pair, flags, the tiles that are left.  false = no kernel for this plan.
-bool asx_launch_rows_re(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, const AsxPrune &U,
-                        int npairs, hipStream_t s);
-bool asx_launch_inv_cols_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, const AsxPrune &U, int npairs, hipStream_t s);
+                           const AsxSearch &search, const AsxPrune *U);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 // pool calls: each pair's record (out) and its two slots' norm partials and band sums (band may be null) into the group's places
 void asx_launch_pool_resolve(const AsxDev &P, const AsxPoolArgs &A, AsxPoolPair *out, float *nrm, float2 *band, int npairs,
                              hipStream_t s);
-// k_rows_rl: k_rows_r with C_x / C_y at the pairs' bank slots (cx, cy: the bank's source and sample spectra)
-bool asx_launch_rows_rl(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, const AsxPoolPair *pl,
-                        int npairs, hipStream_t s);
 // behind the Pearson kernels of a pool group: (0, NaN, -4) for every pair flagged ASX_POOL_INVALID
 void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 // the same behind the last k_topk_step of a pool group with top-k: all k entries of such a pair (entry stride k)
 void asx_launch_invalid_pairs_k(const AsxPoolPair *pl, int k, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 bool asx_rlayout_available(const AsxDev &P); // all three kernels compiled in for this plan's schedules
+bool asx_rlayout_prunable(const AsxDev &P);  // ... and the pruned inverse pass can run on it (asked once, by plan_init)
 int asx_rlayout_band_rows(const AsxDev &P);
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,
                          const AsxSearch &q);

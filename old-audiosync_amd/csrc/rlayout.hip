@@ -507,7 +507,7 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_r(c
     rows_r_body<S, NT, TWO, BC>(P, cx, cy, qo, nrows, (BC & 1) ? 0 : pair_pitch, (BC & 2) ? 0 : pair_pitch, pair_pitch, W);
 }
 
-// The row pass of the pruned inverse pass (asx_launch_rows_re): k_rows_r<S, NT, TWO, 0> that also leaves the tile energies of Q (ENG
+// The row pass of the pruned inverse pass (asx_launch_rows_r, a group whose AsxSpectra carries the lane's AsxPrune): k_rows_r<S, NT, TWO, 0> that also leaves the tile energies of Q (ENG
 // above).  A kernel name of its own: the twelve k_rows_r instances stay the kernels they were.
 template <class S, int NT, bool TWO>
 __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_re(const RArgs P, const float2 *__restrict__ cx,
@@ -845,7 +845,7 @@ __global__ __launch_bounds__(NT, 4) void k_inv_cols_rx(const RArgs P, const floa
 }
 
 // ---------------------------------------------------------------------------
-// The pruned inverse pass (asx_launch_inv_cols_rq; every lag competes, no r_out, no second look): k_tile_bounds, k_inv_cols_rq
+// The pruned inverse pass (asx_launch_inv_cols_r with an AsxPrune; every lag competes, no r_out, no second look): k_tile_bounds, k_inv_cols_rq
 // <FIRST = true> on two tiles per pair, k_prune_select, k_inv_cols_rq<FIRST = false> on the tiles that are left.
 //
 // The bound.  Column j2 of r is the c2r transform of column j2 of Q: with the tangling Z'[u] = S + i conj(w) D, S = Q[u] + conj Q[M1-u],
@@ -965,56 +965,49 @@ static bool schedule_is_r(const AsxStages &st, int n, std::initializer_list<int>
     return true;
 }
 
-// bc: the broadcast form (k_rows_r's BC); the operands that are not broadcast and q have the group workspace's pair pitch
-bool asx_launch_rows_r(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, int npairs, int bc,
-                       hipStream_t s)
+// Row schedules of the real-column kernels: X(block size of a (sub-)row, two-half form, (sub-)row length, radices...); the plan's row
+// length M2 is the sub-row's, twice in the two-half form.  Chosen by the row length alone: these kernels carry their own schedule and
+// only read the plan's w_M2 table.
+// 480-point rows: ONE wave per block -- a block is 11.5 KB of traffic and a chain of five short phases, so what counts is
+// how many are in flight: sixteen single-wave blocks per CU against eight of two waves (rows 0.93 -> 0.83 ms per 1024
+// pairs of N = 144 000, same box)
+#define ASX_RROWS(X) \
+    X(128, false, 1200, 12, 10, 10) X(128, true, 1200, ASX_ROWS2_SCHED) X(64, false, 480, 10, 8, 6)
+
+// one flavour of k_rows_r, with the flavour's extra argument (none: k_rows_r itself)
+template <class K, class... X>
+static void launch_rows_r(K kernel, const AsxDev &P, int nt, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs,
+                          hipStream_t s, X... extra)
 {
     const int nrows = P.M1 + 1;
-    const size_t pitch = (size_t)nrows * (size_t)P.M2;
-    const size_t lds = (size_t)P.M2 * sizeof(float4);
-    // chosen by the row length alone: these kernels carry their own schedule and only read the plan's w_M2 table
-#define ASX_ROWSR_LAUNCH(b, nt, two, n, ...)                                                                                    \
-    hipLaunchKernelGGL((k_rows_r<Sched<n, __VA_ARGS__>, nt, two, b>), dim3((unsigned)nrows * (unsigned)npairs),                 \
-                       dim3((two) ? 2 * nt : nt), lds, s, rargs_of(P), cx, cy, q, nrows, pitch, W);
-#define ASX_ROWSR_CASE(nt, two, n, ...)                                                                                         \
-    if (P.M2 == ((two) ? 2 * n : n)) {                                                                                          \
-        switch (bc) {                                                                                                           \
-        case 0: ASX_ROWSR_LAUNCH(0, nt, two, n, __VA_ARGS__) break;                                                             \
-        case 1: ASX_ROWSR_LAUNCH(1, nt, two, n, __VA_ARGS__) break;                                                             \
-        case 2: ASX_ROWSR_LAUNCH(2, nt, two, n, __VA_ARGS__) break;                                                             \
-        default: ASX_ROWSR_LAUNCH(3, nt, two, n, __VA_ARGS__) break;                                                            \
-        }                                                                                                                       \
-        return true;                                                                                                            \
-    }
-    ASX_ROWSR_CASE(128, false, 1200, 12, 10, 10)
-    ASX_ROWSR_CASE(128, true, 1200, ASX_ROWS2_SCHED)
-    // 480-point rows: ONE wave per block -- a block is 11.5 KB of traffic and a chain of five short phases, so what counts is
-    // how many are in flight: sixteen single-wave blocks per CU against eight of two waves (rows 0.93 -> 0.83 ms per 1024
-    // pairs of N = 144 000, same box)
-    ASX_ROWSR_CASE(64, false, 480, 10, 8, 6)
-#undef ASX_ROWSR_CASE
-#undef ASX_ROWSR_LAUNCH
-    return false;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nrows * (unsigned)npairs), dim3(nt), (size_t)P.M2 * sizeof(float4), s, rargs_of(P),
+                       (const float2 *)C.cx, (const float2 *)C.cy, q, nrows, (size_t)nrows * (size_t)P.M2, W, extra...);
 }
 
-// the row pass of the pruned inverse pass: k_rows_r<..., 0> plus the tile energies U.eng
-bool asx_launch_rows_re(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, const AsxPrune &U,
-                        int npairs, hipStream_t s)
+// The row pass of a group whose spectra are C, which decides the flavour: k_rows_re (plus the tile energies C.prune->eng) when the
+// group is in scope for pruning, k_rows_rl (C_x / C_y at the pairs' bank slots) in a pool group, else k_rows_r in the broadcast form
+// C.bc.  The operands that are not broadcast and q have the group workspace's pair pitch.
+bool asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s)
 {
-    if (P.T != ASX_PRUNE_T) return false;
-    const int nrows = P.M1 + 1;
-    const size_t pitch = (size_t)nrows * (size_t)P.M2;
-    const size_t lds = (size_t)P.M2 * sizeof(float4);
-#define ASX_ROWSRE_CASE(nt, two, n, ...)                                                                                        \
+#define ASX_BC(b, nt, two, n, ...) launch_rows_r(k_rows_r<Sched<n, __VA_ARGS__>, nt, two, b>, P, (two) ? 2 * nt : nt, C, q, W, npairs, s)
+#define ASX_TRY(nt, two, n, ...)                                                                                                \
     if (P.M2 == ((two) ? 2 * n : n)) {                                                                                          \
-        hipLaunchKernelGGL((k_rows_re<Sched<n, __VA_ARGS__>, nt, two>), dim3((unsigned)nrows * (unsigned)npairs),               \
-                           dim3((two) ? 2 * nt : nt), lds, s, rargs_of(P), cx, cy, q, nrows, pitch, W, U.eng);                   \
+        if (C.prune)                                                                                                            \
+            launch_rows_r(k_rows_re<Sched<n, __VA_ARGS__>, nt, two>, P, (two) ? 2 * nt : nt, C, q, W, npairs, s, C.prune->eng); \
+        else if (C.pl)                                                                                                          \
+            launch_rows_r(k_rows_rl<Sched<n, __VA_ARGS__>, nt, two>, P, (two) ? 2 * nt : nt, C, q, W, npairs, s, C.pl);         \
+        else                                                                                                                    \
+            switch (C.bc) {                                                                                                     \
+            case 0: ASX_BC(0, nt, two, n, __VA_ARGS__); break;                                                                  \
+            case 1: ASX_BC(1, nt, two, n, __VA_ARGS__); break;                                                                  \
+            case 2: ASX_BC(2, nt, two, n, __VA_ARGS__); break;                                                                  \
+            default: ASX_BC(3, nt, two, n, __VA_ARGS__); break;                                                                 \
+            }                                                                                                                   \
         return true;                                                                                                            \
     }
-    ASX_ROWSRE_CASE(128, false, 1200, 12, 10, 10)
-    ASX_ROWSRE_CASE(128, true, 1200, ASX_ROWS2_SCHED)
-    ASX_ROWSRE_CASE(64, false, 480, 10, 8, 6)
-#undef ASX_ROWSRE_CASE
+    ASX_RROWS(ASX_TRY)
+#undef ASX_TRY
+#undef ASX_BC
     return false;
 }
 
@@ -1051,20 +1044,29 @@ static unsigned resident_blocks(const void *fn, int nthreads, size_t lds)
     return n;
 }
 
-// Forward columns of operands op0 .. op0 + nops - 1 (0 source, 1 sample) of npairs pairs whose inputs are src_stride / smp_stride
-// floats apart, into cx / cy (pair pitch (M1 + 1) M2), nrm (AsxPeakWs::nrm_part layout) and band (AsxPeakWs::band layout, or null).
-// temporal: C stored with ordinary stores (the broadcast slot).
-bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, float2 *cx,
-                           float2 *cy, float *nrm, float2 *band, int npairs, int op0, int nops, bool temporal, hipStream_t s)
+// Forward columns of tracks first .. first + count - 1 of src and / or smp (null: not that operand), src_stride / smp_stride floats
+// apart (0 = one track), into the same tracks of dst: C at pitch (M1 + 1) M2, norm partials and band sums in the AsxPeakWs layouts.
+// temporal: C stored with ordinary stores (the broadcast slot, the bank).  The kernel reads and writes only the operands it is
+// launched for (op0 + blockIdx.y), so an absent operand's pointers are never used.
+bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, size_t first,
+                           int count, const AsxSpectra &dst, bool temporal, hipStream_t s)
 {
     if (!P.col_pairs) return false;
+    const unsigned op0 = src ? 0 : 1, nops = (src ? 1 : 0) + (smp ? 1 : 0);
+    if (nops == 0) return true;
     const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, lds = (size_t)P.M1 * P.T * sizeof(float2);
-    const dim3 grid(rcol_grid_x(P.ntiles, P.logT), (unsigned)nops, npairs);
+    const size_t per = 2 * (size_t)P.ntiles; // norm partials per track slot; band sums: nbands times as many
+    if (src) src += first * src_stride;
+    if (smp) smp += first * smp_stride;
+    float2 *cx = dst.cx + first * pitch, *cy = dst.cy + first * pitch;
+    float2 *band = dst.band ? dst.band + first * per * (size_t)P.nbands : nullptr;
+    float *nrm = dst.nrm + first * per;
+    const dim3 grid(rcol_grid_x(P.ntiles, P.logT), nops, count);
 #define ASX_TRY1(nts, m1, t, nt, ...)                                                                                        \
     {                                                                                                                       \
         allow_big_lds_r((const void *)k_fwd_cols_r<Sched<m1, __VA_ARGS__>, t, nt, nts>, lds);                               \
         hipLaunchKernelGGL((k_fwd_cols_r<Sched<m1, __VA_ARGS__>, t, nt, nts>), grid, dim3(nt), lds, s, rargs_of(P), src, smp,  \
-                           src_stride, smp_stride, cx, cy, nrm, pitch, band, (unsigned)op0);                                \
+                           src_stride, smp_stride, cx, cy, nrm, pitch, band, op0);                                          \
     }
 #define ASX_TRY(m1, t, nt, ...)                                                                                             \
     if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                                                          \
@@ -1074,25 +1076,6 @@ bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride,
     ASX_RCOLS(ASX_TRY)
 #undef ASX_TRY
 #undef ASX_TRY1
-    return false;
-}
-
-bool asx_launch_rows_rl(const AsxDev &P, const float2 *cx, const float2 *cy, float2 *q, const AsxPeakWs &W, const AsxPoolPair *pl,
-                        int npairs, hipStream_t s)
-{
-    const int nrows = P.M1 + 1;
-    const size_t pitch = (size_t)nrows * (size_t)P.M2;
-    const size_t lds = (size_t)P.M2 * sizeof(float4);
-#define ASX_ROWSRL_CASE(nt, two, n, ...)                                                                                        \
-    if (P.M2 == ((two) ? 2 * n : n)) {                                                                                          \
-        hipLaunchKernelGGL((k_rows_rl<Sched<n, __VA_ARGS__>, nt, two>), dim3((unsigned)nrows * (unsigned)npairs),               \
-                           dim3((two) ? 2 * nt : nt), lds, s, rargs_of(P), cx, cy, q, nrows, pitch, W, pl);                      \
-        return true;                                                                                                            \
-    }
-    ASX_ROWSRL_CASE(128, false, 1200, 12, 10, 10)
-    ASX_ROWSRL_CASE(128, true, 1200, ASX_ROWS2_SCHED)
-    ASX_ROWSRL_CASE(64, false, 480, 10, 8, 6)
-#undef ASX_ROWSRL_CASE
     return false;
 }
 
@@ -1123,8 +1106,28 @@ static void launch_inv_r(K kernel, const AsxDev &P, dim3 grid, int nt, size_t ld
                        resident_blocks(fn, nt, lds), extra...);
 }
 
+// The pruned inverse pass over the Q and the tile energies k_rows_re left: bounds, the two likely tiles, the flags, the rest.
+template <class S1, int TC, int NT>
+static void launch_inv_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, const AsxPrune &U, int npairs, hipStream_t s)
+{
+    const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, lds = (size_t)S1::n * TC * sizeof(float2);
+    auto k1 = k_inv_cols_rq<S1, TC, NT, true>;
+    auto k2 = k_inv_cols_rq<S1, TC, NT, false>;
+    allow_big_lds_r((const void *)k1, lds);
+    allow_big_lds_r((const void *)k2, lds);
+    hipLaunchKernelGGL(k_tile_bounds, dim3(npairs), dim3(1024), 0, s, U.eng, U.ub, U.best, P.M1 + 1, P.ntiles, 4.0 * (double)P.M1,
+                       ASX_PRUNE_FLOOR_PER_TERM * (double)ASX_PRUNE_T * (double)(P.M1 + 1));
+    hipLaunchKernelGGL(k1, dim3(npairs, 2), dim3(NT), lds, s, rargs_of(P), q, pitch, W, resident_blocks((const void *)k1, NT, lds),
+                       U.best, U.skip);
+    hipLaunchKernelGGL(k_prune_select, dim3(npairs), dim3(256), 0, s, U.ub, U.best, U.skip, W, P.ntiles, U.stats);
+    hipLaunchKernelGGL(k2, dim3(npairs, rcol_grid_x(P.ntiles, asx_ilog2(TC))), dim3(NT), lds, s, rargs_of(P), q, pitch, W,
+                       resident_blocks((const void *)k2, NT, lds), U.best, U.skip);
+}
+
+// The inverse column pass of a group: U null, the flavour the search asks for; U the lane's prune workspace (a group in scope for
+// pruning: every lag competes, no r_out, and k_rows_re has left U->eng), the pruned pass.
 bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
-                           const AsxSearch &search)
+                           const AsxSearch &search, const AsxPrune *U)
 {
     if (!P.col_pairs) return false;
 #define ASX_RX(zc, m1, t, nt, ...) \
@@ -1133,7 +1136,9 @@ bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W,
     if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                                                          \
         const size_t lds = (size_t)(m1) * (t) * sizeof(float2);                                                             \
         const dim3 grid(npairs, rcol_grid_x(P.M2 / (t), asx_ilog2(t)));                                                     \
-        if (search.kind == AsxSearch::TOPK)                                                                                 \
+        if (U)                                                                                                              \
+            launch_inv_rq<Sched<m1, __VA_ARGS__>, t, nt>(P, q, W, *U, npairs, s);                                           \
+        else if (search.kind == AsxSearch::TOPK)                                                                            \
             switch (asx_tk_zone_cap(search.tk_zones)) {                                                                     \
             case 1: ASX_RX(1, m1, t, nt, __VA_ARGS__); break;                                                               \
             case 3: ASX_RX(3, m1, t, nt, __VA_ARGS__); break;                                                               \
@@ -1153,32 +1158,6 @@ bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W,
     return false;
 }
 
-// The pruned inverse pass over the Q and the tile energies asx_launch_rows_re left: bounds, the two likely tiles, the flags, the rest.
-bool asx_launch_inv_cols_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, const AsxPrune &U, int npairs, hipStream_t s)
-{
-    if (!P.col_pairs || P.T != ASX_PRUNE_T || P.M2 % ASX_PRUNE_T != 0 || P.ntiles > 1024) return false;
-    const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2;
-#define ASX_TRY(m1, t, nt, ...)                                                                                             \
-    if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                                                          \
-        const size_t lds = (size_t)(m1) * (t) * sizeof(float2);                                                             \
-        auto k1 = k_inv_cols_rq<Sched<m1, __VA_ARGS__>, t, nt, true>;                                                       \
-        auto k2 = k_inv_cols_rq<Sched<m1, __VA_ARGS__>, t, nt, false>;                                                      \
-        allow_big_lds_r((const void *)k1, lds);                                                                             \
-        allow_big_lds_r((const void *)k2, lds);                                                                             \
-        hipLaunchKernelGGL(k_tile_bounds, dim3(npairs), dim3(1024), 0, s, U.eng, U.ub, U.best, P.M1 + 1, P.ntiles,          \
-                           4.0 * (double)P.M1, ASX_PRUNE_FLOOR_PER_TERM * (double)ASX_PRUNE_T * (double)(P.M1 + 1));        \
-        hipLaunchKernelGGL(k1, dim3(npairs, 2), dim3(nt), lds, s, rargs_of(P), q, pitch, W,                                 \
-                           resident_blocks((const void *)k1, nt, lds), U.best, U.skip);                                     \
-        hipLaunchKernelGGL(k_prune_select, dim3(npairs), dim3(256), 0, s, U.ub, U.best, U.skip, W, P.ntiles, U.stats);      \
-        hipLaunchKernelGGL(k2, dim3(npairs, rcol_grid_x(P.ntiles, asx_ilog2(t))), dim3(nt), lds, s, rargs_of(P), q, pitch, W, \
-                           resident_blocks((const void *)k2, nt, lds), U.best, U.skip);                                     \
-        return true;                                                                                                        \
-    }
-    ASX_RCOLS(ASX_TRY)
-#undef ASX_TRY
-    return false;
-}
-
 // rows of the sample matrix per band of the spectral Pearson form = what one lane group of this plan's k_fwd_cols_r loads; 0 = no kernel
 int asx_rlayout_band_rows(const AsxDev &P)
 {
@@ -1195,6 +1174,16 @@ bool asx_rlayout_available(const AsxDev &P)
 #define ASX_TRY(m1, t, nt, ...) if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) cols = true;
     ASX_RCOLS(ASX_TRY)
 #undef ASX_TRY
-    rows = P.M2 == 1200 || P.M2 == 480 || P.M2 == 2400;
+#define ASX_TRY(nt, two, n, ...) if (P.M2 == ((two) ? 2 * n : n)) rows = true;
+    ASX_RROWS(ASX_TRY)
+#undef ASX_TRY
     return cols && rows;
+}
+
+// Whether the pruned inverse pass can run on this plan, the one statement of it (plan_init asks once; the launchers do not ask
+// again): the real-column kernels, the tile width k_rows_re sums energies for, whole tiles only (k_inv_cols_rq indexes its flags by
+// M2 / T), and a tile per thread of k_tile_bounds' 1024.
+bool asx_rlayout_prunable(const AsxDev &P)
+{
+    return asx_rlayout_available(P) && P.T == ASX_PRUNE_T && P.M2 % ASX_PRUNE_T == 0 && P.ntiles <= 1024;
 }

@@ -1238,16 +1238,16 @@ static bool generic_only()
 void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, float2 *zxa,
                          float2 *zya, const AsxPeakWs &W, int npairs, hipStream_t s)
 {
-    if (P.rlayout && asx_launch_fwd_cols_r(P, src, 2 * (size_t)P.N, smp, P.N, zxa, zya, W.nrm_part, W.band, npairs, 0, 2, false, s))
+    if (P.rlayout && asx_launch_fwd_cols_r(P, src, 2 * (size_t)P.N, smp, P.N, 0, npairs, { zxa, zya, W.nrm_part, W.band }, false, s))
         return;
     if (generic_only() || !asx_launch_fwd_cols_static(P, src, smp, zxa, zya, W, npairs, s))
         asx_launch_fwd_cols_generic(P, src, smp, zxa, zya, W, npairs, s);
 }
 
-void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga,
+void asx_launch_rows(const AsxDev &P, float2 *zxa, float2 *zya, float2 *ga,
                      const AsxPeakWs &W, int npairs, hipStream_t s)
 {
-    if (P.rlayout && asx_launch_rows_r(P, zxa, zya, ga, W, npairs, 0, s)) return;
+    if (P.rlayout && asx_launch_rows_r(P, { zxa, zya, W.nrm_part, W.band }, ga, W, npairs, s)) return;
     if (generic_only() || !asx_launch_rows_static(P, zxa, zya, ga, W, npairs, s))
         asx_launch_rows_generic(P, zxa, zya, ga, W, npairs, s);
 }
@@ -1255,7 +1255,7 @@ void asx_launch_rows(const AsxDev &P, const float2 *zxa, const float2 *zya, floa
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                          const AsxSearch &q)
 {
-    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s, q)) return;
+    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s, q, nullptr)) return;
     if (generic_only() || !asx_launch_inv_cols_static(P, ga, W, r_out, npairs, s, q))
         asx_launch_inv_cols_generic(P, ga, W, r_out, npairs, s, q);
 }
