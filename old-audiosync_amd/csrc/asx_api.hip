@@ -312,8 +312,14 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
                 HIP_TRY(hipMemset(p->prune_stats, 0, 2 * sizeof(unsigned long long)));
             }
             if (dev_alloc(p, &ln.prune.eng, g * ((size_t)h.M1 + 1) * (size_t)h.ntiles) || dev_alloc(p, &ln.prune.ub, g * (size_t)h.ntiles) ||
-                dev_alloc(p, &ln.prune.best, g) || dev_alloc(p, &ln.prune.skip, g * (size_t)h.ntiles))
+                dev_alloc(p, &ln.prune.best, g) || dev_alloc(p, &ln.prune.skip, g * (size_t)h.ntiles) ||
+                dev_alloc(p, &ln.prune.part, g * 1024) || dev_alloc(p, &ln.prune.ticket, g))
                 return -1;
+            // part: [slices][tiles rounded up to 32] of 1024 doubles per pair whatever the length; every slot a launch reads it has
+            // written itself, the zeroing is for a defined first state only.  The tickets must be zero: k_tile_bounds counts on it
+            // and leaves them zero behind every launch
+            HIP_TRY(hipMemset(ln.prune.part, 0, g * 1024 * sizeof(double)));
+            HIP_TRY(hipMemset(ln.prune.ticket, 0, g * sizeof(unsigned)));
             ln.prune.stats = p->prune_stats;
         }
         HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));

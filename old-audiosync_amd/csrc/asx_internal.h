@@ -33,7 +33,9 @@
 // Pruned inverse pass (rlayout.hip: k_tile_bounds): a column tile of r whose bound ub = sqrt(4 M1 E) (1 + ASX_PRUNE_DELTA) lies under the
 // near-maximum window is not transformed.  What the factor has to cover, in units of eps32 = 2^-23, derived as ASX_BOUND_C is:
 //   the computed E against the exact energy of the float32 Q: |Q|^2 two roundings, four levels of additions of non-negative terms
-//     (a balanced tree over the tile's sixteen columns), the float64 sum over the rows and the square root nothing: 6 u = 3 eps on E, 1.5 eps on its root;
+//     (a balanced tree over the tile's sixteen columns: k_rows_re's four DPP steps inside a row of sixteen lanes pair the columns as
+//     tree_sum<16> does, so this stands for them as written), the float64 sum over the rows and the square root nothing: 6 u = 3 eps
+//     on E, 1.5 eps on its root;
 //   the computed tile r^ against the exact transform r of that Q: no element of r^ exceeds its column's 2-norm, and the float32
 //     c2r transform of length 2 M1 <= 1200 delivers a column whose 2-norm is off by at most C eps log2(2 M1) of it -- the worst-case
 //     constant of one transform is ~1 (a third of the three transforms' ~3 in ASX_BOUND_C's note), taken as ASX_BOUND_C = 4 here as
@@ -322,6 +324,8 @@ struct AsxPrune {
     float *eng;            // [pairs][M1 + 1][ntiles] sum of |Q[k1][j2]|^2 over the tile's columns (k_rows_re)
     float *ub;             // [pairs][ntiles] upper bound of |r^| over the tile
     int *best;             // [pairs] the tile with the largest bound
+    double *part;          // [pairs][1024] = [slices][tiles rounded up to 32]: a slice's float64 sum over its rows (k_tile_bounds)
+    unsigned *ticket;      // [pairs] slices of the pair that have left their sums; zero between launches
     unsigned char *skip;   // [pairs][ntiles] 1 = the second launch leaves the tile out
     unsigned long long *stats; // [2] tiles transformed, tiles in all: cumulative over the plan's life (asx_plan_prune_stats)
 };

@@ -113,6 +113,14 @@ __device__ __forceinline__ float quad_sum(float v)
     v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true)); // quad_perm [2,3,0,1]
     return v;
 }
+// sum over a DPP row of sixteen lanes (every lane gets it): the balanced tree tree_sum<16> is, ((0+1)+(2+3))+((4+5)+(6+7)) + the same of 8..15
+__device__ __forceinline__ float row16_sum(float v)
+{
+    v = quad_sum(v);
+    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xF, 0xF, true)); // row_half_mirror: the other quad of the eight
+    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xF, 0xF, true)); // row_mirror: the other eight
+    return v;
+}
 // p[0] + ... + p[N-1] as a balanced tree: ceil(log2 N) roundings on every path
 template <int N> __device__ __forceinline__ float tree_sum(const float (&p)[N])
 {
@@ -197,11 +205,14 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 //   ENG (k_rows_re, the pruned inverse pass): the block also leaves the energy of its row of Q per column tile of sixteen,
 //   eng[pair][k1][tile] = sum of |Q[k1][j2]|^2 over the tile's columns, in float32, one contiguous run per block.  The store phase
 //   holds every Q value in a register: its |Q|^2 goes to LDS, into the upper halves of the slots, which are free by then (the
-//   single-member values of the inverse stages live in the first 8 bytes of a slot) -- value p = 17 * tile + column-in-tile at float
-//   2 + (p & 1) of slot p / 2, a tile's sixteen values 17 apart from the next tile's, so that neither the writers (consecutive
-//   columns) nor the readers (consecutive tiles) meet in a bank more than two at a time -- and behind a barrier one thread per tile
-//   adds its sixteen as a balanced tree.  No atomics, no cross-lane step: the same Q gives the same bits.  Nothing is loaded for it.
-//   (Quad sums by DPP in front of the LDS write, four values per tile to add: the same time, profiles/r7_prune/ab_rows_variants.txt.)
+//   single-member values of the inverse stages live in the first 8 bytes of a slot) -- column c at the third float of slot c itself,
+//   so a thread's stores share one address and differ in the instruction's offset field: a value costs its two multiplications and
+//   the store, no index arithmetic (round 7's layout, 17 * tile + column, took eight integer instructions per value; dropping them
+//   took back about a fifth of what the energies cost the row pass, which is now the fifth barrier and the phase behind it,
+//   EXPERIMENTS.md round 8) -- and behind a barrier ALL threads of the block read column tid + NTB i: sixteen consecutive lanes
+//   hold a tile and add it in four DPP steps inside their row, the balanced tree ((0+1)+(2+3))+... that tree_sum<16> is; one lane
+//   of the sixteen stores.  No atomics: the same Q gives the same bits.  Nothing is loaded for it.  (Lanes are four dwords apart:
+//   a four-way bank conflict on these stores and loads, a few hundred LDS cycles per block.)
 // ---------------------------------------------------------------------------
 // The body takes P and W by value: that call boundary loads their fields at the top of the kernel.  Written inside the __global__
 // itself the instruction stream changes, and with it the float32 rounding of r (11 of the headline's 124 coefficients moved by
@@ -421,15 +432,15 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
 
     // ---- inverse stage 0 from LDS, the outputs leave from registers -------------------------------------------------
     float2 *go = qo + row;
-    // ENG: |Q|^2 of column c into the free upper half of an LDS slot (see above); 17 * M2 / 16 values fit the M2 slots' upper halves
-    static_assert(!ENG || (ASX_PRUNE_T == 16 && M2 % ASX_PRUNE_T == 0 && M2 / ASX_PRUNE_T <= NTB),
-                  "tile energies: tiles of sixteen columns, one thread per tile");
-    auto eng_slot = [](int p) __attribute__((always_inline)) { return 4 * (p >> 1) + 2 + (p & 1); };
-    auto eng_put = [&](int c, Cx1 y) __attribute__((always_inline)) {
-        reinterpret_cast<float *>(asx_lds_r)[eng_slot(17 * (c >> 4) + (c & 15))] = fmaf(y.re, y.re, y.im * y.im);
-    };
+    // ENG: |Q|^2 of column c into the third float of LDS slot c (see above).  eng_put(ej, c0, y) is column j + c0, c0 a compile-time
+    // constant at every call: one address per thread, the rest is the instruction's offset field (16 * (M2 - 1) + 8 < 2^16)
+    static_assert(!ENG || (ASX_PRUNE_T == 16 && M2 % ASX_PRUNE_T == 0 && NTB % ASX_PRUNE_T == 0 && 16 * M2 < 65536),
+                  "tile energies: tiles of sixteen columns, a tile per row of sixteen lanes");
+    auto eng_base = [](int j) __attribute__((always_inline)) { return reinterpret_cast<float *>(asx_lds_r) + 4 * j + 2; };
+    auto eng_put = [](float *ej, int c0, Cx1 y) __attribute__((always_inline)) { ej[4 * c0] = fmaf(y.re, y.re, y.im * y.im); };
     if constexpr (!TWO) {
         for (int j = lt; j < Q0; j += NT) {
+            [[maybe_unused]] float *const ej = eng_base(j);
             const float4 *p = A4 + j;
             Cx1 v[R0];
             static_for<0, R0>([&](auto T) __attribute__((always_inline)) { v[T] = lds_get1(p + decltype(T)::value * Q0); });
@@ -444,7 +455,7 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
                 constexpr int t = decltype(T)::value;
                 const Cx1 y = mulwc(v[t], t == 0 ? fb : cmul(fb, leg[t]));
                 st_f2(go + j + t * Q0, make_float2(y.re, y.im), ASX_RNT & 8);
-                if constexpr (ENG) eng_put(j + t * Q0, y);
+                if constexpr (ENG) eng_put(ej, t * Q0, y);
             });
         }
     } else {
@@ -456,6 +467,7 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
         const float4 *base = reinterpret_cast<const float4 *>(asx_lds_r);
         static_assert(Q0 <= NT, "one butterfly per thread of the first half");
         for (int j = tid; j < Q0; j += NTB) {
+            [[maybe_unused]] float *const ej = eng_base(j);
             Cx2 v[R0];
             static_for<0, R0>([&](auto T) __attribute__((always_inline)) {
                 const Cx1 a = lds_get1(base + j + decltype(T)::value * Q0), b = lds_get1(base + NS + j + decltype(T)::value * Q0);
@@ -478,20 +490,27 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
                 const Cx1 z = mulwc(A - Bw, t == 0 ? fbh : cmul(fbh, lg));
                 st_f2(go + j + t * Q0, make_float2(y.re, y.im), ASX_RNT & 8);
                 st_f2(go + NS + j + t * Q0, make_float2(z.re, z.im), ASX_RNT & 8);
-                if constexpr (ENG) { eng_put(j + t * Q0, y); eng_put(NS + j + t * Q0, z); }
+                if constexpr (ENG) { eng_put(ej, t * Q0, y); eng_put(ej, NS + t * Q0, z); }
             });
         }
     }
     if constexpr (ENG) {
+        // every thread of the block: column tid + NTB i of step i, sixteen consecutive lanes = one tile, added inside their DPP row
         __syncthreads();
-        constexpr int NTILE = M2 / ASX_PRUNE_T;
-        if (tid < NTILE) {
-            float v[16];
-            static_for<0, 16>([&](auto I) __attribute__((always_inline)) {
-                v[I] = reinterpret_cast<const float *>(asx_lds_r)[eng_slot(17 * tid + decltype(I)::value)];
+        constexpr int NTILE = M2 / ASX_PRUNE_T, ESTEPS = (M2 + NTB - 1) / NTB;
+        const float *er = eng_base(tid);
+        float *eo = eng + ((size_t)pair * nrows + k1) * NTILE + (tid >> 4);
+        float v[ESTEPS];
+        static_for<0, ESTEPS>([&](auto I) __attribute__((always_inline)) {
+            constexpr int i = decltype(I)::value;
+            v[I] = ((i + 1) * NTB <= M2 || tid + i * NTB < M2) ? er[4 * NTB * i] : 0.f; // (whole rows of sixteen lanes are in or out)
+        });
+        static_for<0, ESTEPS>([&](auto I) __attribute__((always_inline)) { v[I] = row16_sum(v[I]); });
+        if ((tid & 15) == 0)
+            static_for<0, ESTEPS>([&](auto I) __attribute__((always_inline)) {
+                constexpr int i = decltype(I)::value;
+                if ((i + 1) * NTB <= M2 || tid + i * NTB < M2) eo[(NTB / 16) * i] = v[I];
             });
-            eng[((size_t)pair * nrows + k1) * NTILE + tid] = tree_sum<16>(v);
-        }
     }
     RSTAMP(0, task, 4);
 #ifdef ASX_STAMPS
@@ -862,33 +881,89 @@ __global__ __launch_bounds__(NT, 4) void k_inv_cols_rx(const RArgs P, const floa
 // ASX_PRUNE_FLOOR_PER_TERM times its number of terms gets the bound +infinity (the squares of a very quiet pair underflow in
 // float32 although r itself does not): it is never skipped.
 // ---------------------------------------------------------------------------
-// grid (npairs), 1024 threads: ub[pair][tile] and the pair's largest-bound tile from eng[pair][k1][tile].  The rows are dealt to
-// 1024 / (tiles rounded up to 32) slices, summed in float64 per slice and then over the slices in slice order: the same eng gives
-// the same bits.
-__global__ __launch_bounds__(1024) void k_tile_bounds(const float *__restrict__ eng, float *__restrict__ ub, int *__restrict__ best,
-                                                       int nrows, int ntiles, double scale, double floor)
+// grid (npairs, nsl), tp threads in whole waves, tp = the tiles rounded up to 32 and nsl = 1024 / tp: ub[pair][tile] and the pair's largest-bound tile
+// from eng[pair][k1][tile].  The rows are dealt to the nsl slices, k1 = s mod nsl to block (pair, s), which sums its rows in float64 in
+// increasing k1, a tile per thread, and leaves part[pair][s][tile].  The block of a pair that draws the pair's last ticket adds the
+// slices in slice order and states the bounds: the same eng gives the same bits, whichever block that is.  It puts the ticket back
+// to zero for the next launch on this stream (U.ticket is zeroed once, when the plan is made).
+//
+// The hand-over inside the launch RESTS ON THE CODE GENERATED FOR THE gfx942 FAMILY (gfx950 included), NOT ON THE LANGUAGE'S MEMORY
+// MODEL.  The model asks for a release in front of the ticket; at agent scope that is a write-back of the XCD's whole L2
+// (buffer_wbl2 sc1), 744 of them per launch, and the kernel takes 25 us with it instead of 16 (EXPERIMENTS.md round 8).  What stands
+// here instead, every access to part an atomic one so that none of it is a data race:
+//   - a slice's sums leave as relaxed agent-scope atomic stores: global_store_dwordx2 ... sc1, written through to memory;
+//   - every wave waits for its stores' acknowledgement (s_waitcnt vmcnt(0)) in front of the barrier, so all of the block's sums are in
+//     memory before its one lane draws the ticket, an agent-scope atomic add (relaxed: NO release);
+//   - the last arriver's agent-scope acquire fence (buffer_inv sc1) stands behind its ticket and in front of the barrier behind which
+//     its threads load the sums, as relaxed agent-scope atomic loads (sc1).
+// Relaxed atomics alone order nothing between the stores and the ticket; the explicit wait does, on this hardware.
+// tests/test_rows_energy_isa.py pins each instruction of that sequence in the built library: a compiler that lowers any of it
+// differently fails there.  That test knows one compiler (ROCm 7.2, tests/test_kernel_isa_order.py: PINNED_ROCM) and skips elsewhere,
+// so any other compiler gets the release the model asks for on the ticket, and with it the slower, portable kernel, until the
+// sequence has been read and stated for that compiler too.
+#if defined(HIP_VERSION_MAJOR) && HIP_VERSION_MAJOR == 7 && HIP_VERSION_MINOR == 2
+constexpr int BOUNDS_TICKET_ORDER = __ATOMIC_RELAXED;
+#else
+constexpr int BOUNDS_TICKET_ORDER = __ATOMIC_RELEASE;
+#endif
+constexpr int BOUNDS_ROWS_IN_FLIGHT = 16, BOUNDS_SLICES_IN_FLIGHT = 8;
+
+// load(i), i = 0 .. n-1, added in float64 in increasing i with DEPTH loads in flight; past the last term a thread loads that term
+// again and adds +0.0 in its place, which leaves a sum of non-negative terms (or a NaN) as it is
+template <int DEPTH, class Load>
+__device__ __forceinline__ double sum_in_order(int n, Load load)
 {
-    __shared__ double part[1024];
-    const size_t pair = blockIdx.x;
-    const int tid = threadIdx.x, tp = (ntiles + 31) & ~31, nsl = 1024 / tp;
-    const int tile = tid % tp, sl = tid / tp;
-    const float *e = eng + pair * (size_t)nrows * ntiles;
     double sum = 0.0;
-    if (tile < ntiles && sl < nsl)
-        for (int k1 = sl; k1 < nrows; k1 += nsl) sum += (double)e[(size_t)k1 * ntiles + tile];
-    part[tid] = sum;
+    for (int i0 = 0; i0 < n; i0 += DEPTH) {
+        double v[DEPTH];
+#pragma unroll
+        for (int i = 0; i < DEPTH; i++) v[i] = load(i0 + i < n ? i0 + i : n - 1);
+#pragma unroll
+        for (int i = 0; i < DEPTH; i++) sum += i0 + i < n ? v[i] : 0.0;
+    }
+    return sum;
+}
+
+__global__ __launch_bounds__(1024) void k_tile_bounds(const float *__restrict__ eng, float *__restrict__ ub, int *__restrict__ best,
+                                                       double *part, unsigned *__restrict__ ticket, int nrows, int ntiles,
+                                                       double scale, double floor)
+{
+    __shared__ unsigned long long tops[16];
+    __shared__ int last;
+    const size_t pair = blockIdx.x;
+    const int tile = threadIdx.x, tp = (ntiles + 31) & ~31, sl = blockIdx.y, nsl = gridDim.y; // (whole waves: blockDim.x may exceed tp)
+    unsigned long long *pp = reinterpret_cast<unsigned long long *>(part + pair * 1024);
+    if (tile < ntiles) {
+        const float *e = eng + pair * (size_t)nrows * ntiles + (size_t)sl * ntiles + tile;
+        const size_t step = (size_t)nsl * ntiles;
+        const double sum = sum_in_order<BOUNDS_ROWS_IN_FLIGHT>((nrows - sl + nsl - 1) / nsl, // rows of the slice
+                                                               [=](int i) { return (double)e[(size_t)i * step]; });
+        __hip_atomic_store(pp + sl * tp + tile, (unsigned long long)__double_as_longlong(sum), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid >= 64) return;
+    if (threadIdx.x == 0) {
+        const unsigned drawn = __hip_atomic_fetch_add(ticket + pair, 1u, BOUNDS_TICKET_ORDER, __HIP_MEMORY_SCOPE_AGENT);
+        last = drawn == (unsigned)nsl - 1u;
+        if (last) {
+            __hip_atomic_store(ticket + pair, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    }
+    __syncthreads();
+    if (!last) return;
     // bounds are >= 0 or NaN: their bits order them; a NaN bound (NaN in Q) is never the largest, and never below a threshold either
     unsigned long long top = 0;
-    for (int t = tid; t < ntiles; t += 64) {
-        double s = 0.0;
-        for (int i = 0; i < nsl; i++) s += part[i * tp + t];
+    if (tile < ntiles) {
+        const double s = sum_in_order<BOUNDS_SLICES_IN_FLIGHT>(nsl, [=](int i) { // in slice order
+            return __longlong_as_double((long long)__hip_atomic_load(pp + i * tp + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        });
         // under the floor the float32 squares may have underflowed (asx_internal.h): no bound, the tile is transformed
         const float b = s < floor ? INFINITY : __double2float_ru(sqrt(scale * s) * (1.0 + (double)ASX_PRUNE_DELTA));
-        ub[pair * ntiles + t] = b;
-        const unsigned long long key = b == b ? ((unsigned long long)__float_as_uint(b) << 32) | (0xFFFFFFFFu - (unsigned)t) : 0ull;
-        top = key > top ? key : top;
+        ub[pair * ntiles + tile] = b;
+        top = b == b ? ((unsigned long long)__float_as_uint(b) << 32) | (0xFFFFFFFFu - (unsigned)tile) : 0ull;
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -896,7 +971,11 @@ __global__ __launch_bounds__(1024) void k_tile_bounds(const float *__restrict__ 
         const unsigned long long o = ((unsigned long long)hi << 32) | lo;
         top = o > top ? o : top;
     }
-    if (tid == 0) best[pair] = top ? (int)(0xFFFFFFFFu - (unsigned)top) : 0; // (ties: the smallest tile; every bound NaN: tile 0)
+    if ((threadIdx.x & 63) == 0) tops[threadIdx.x >> 6] = top;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < (int)blockDim.x / 64; w++) top = tops[w] > top ? tops[w] : top;
+    best[pair] = top ? (int)(0xFFFFFFFFu - (unsigned)top) : 0; // (ties: the smallest tile; every bound NaN: tile 0)
 }
 
 // grid (npairs), 256 threads, behind the first launch: skip[pair][tile] = 1 for the tiles the second launch leaves out -- the two the
@@ -1115,8 +1194,9 @@ static void launch_inv_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, 
     auto k2 = k_inv_cols_rq<S1, TC, NT, false>;
     allow_big_lds_r((const void *)k1, lds);
     allow_big_lds_r((const void *)k2, lds);
-    hipLaunchKernelGGL(k_tile_bounds, dim3(npairs), dim3(1024), 0, s, U.eng, U.ub, U.best, P.M1 + 1, P.ntiles, 4.0 * (double)P.M1,
-                       ASX_PRUNE_FLOOR_PER_TERM * (double)ASX_PRUNE_T * (double)(P.M1 + 1));
+    const int tp = (P.ntiles + 31) & ~31; // asx_rlayout_prunable: at most 1024
+    hipLaunchKernelGGL(k_tile_bounds, dim3(npairs, 1024 / tp), dim3((tp + 63) & ~63), 0, s, U.eng, U.ub, U.best, U.part, U.ticket, P.M1 + 1, P.ntiles,
+                       4.0 * (double)P.M1, ASX_PRUNE_FLOOR_PER_TERM * (double)ASX_PRUNE_T * (double)(P.M1 + 1));
     hipLaunchKernelGGL(k1, dim3(npairs, 2), dim3(NT), lds, s, rargs_of(P), q, pitch, W, resident_blocks((const void *)k1, NT, lds),
                        U.best, U.skip);
     hipLaunchKernelGGL(k_prune_select, dim3(npairs), dim3(256), 0, s, U.ub, U.best, U.skip, W, P.ntiles, U.stats);
@@ -1182,7 +1262,7 @@ bool asx_rlayout_available(const AsxDev &P)
 
 // Whether the pruned inverse pass can run on this plan, the one statement of it (plan_init asks once; the launchers do not ask
 // again): the real-column kernels, the tile width k_rows_re sums energies for, whole tiles only (k_inv_cols_rq indexes its flags by
-// M2 / T), and a tile per thread of k_tile_bounds' 1024.
+// M2 / T), and a tile per thread of a k_tile_bounds block.
 bool asx_rlayout_prunable(const AsxDev &P)
 {
     return asx_rlayout_available(P) && P.T == ASX_PRUNE_T && P.M2 % ASX_PRUNE_T == 0 && P.ntiles <= 1024;
