@@ -849,7 +849,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     const bool spectral = std::is_same<TIn, float>::value && p->spectral && o.spectral && pk.band;
     AsxPeakWs tk = pk; // what the transform kernels see
     if (!spectral) { tk.band = nullptr; tk.tile_peak = nullptr; }
-    // The pruned pair of passes (rlayout.hip: k_rows_re, and k_tile_bounds and k_inv_cols_rq around k_prune_select) in place of the row pass
+    // The pruned pair of passes (rlayout.hip: k_rows_re, and k_tile_bounds and k_inv_cols_r<..., AsxSelPrune> around k_prune_select) in place of the row pass
     // and the inverse column pass:
     // a float32 entry point's group on a real-column plan, every lag competing, no broadcast operand and no pool, one pass, r not asked
     // for, the lane's own lists (not the second look).  Everything else launches what it always did.

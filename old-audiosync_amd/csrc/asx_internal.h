@@ -12,6 +12,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define ASX_MAX_STAGES 12
 #define ASX_TW_LOG 11                       // two-level twiddle: low table has 2^11 entries
@@ -122,10 +123,12 @@ struct AsxSeg {           // per pair, produced by k_finalize
 // (lag l >= 0 is index l, lag l < 0 index 2N + l: the inverse of the wrap at src/cross_correlation.c:256-263) -- one range, or two
 // when the window holds lag 0 and a negative lag.  seed = the smallest in-window index: the element that starts the reference's
 // running maximum with its SIGNED value (arr[0], :56), 0 for every window that holds lag 0.  The full window (a = N, w = 2N - 1,
-// seed = 0) runs the kernels without a window; the others run k_inv_cols_rw / k_inv_cols_w, which mask every key they form with
-// asx_win_has.  Travels by value as a kernel argument.
+// seed = 0) runs the kernels without a window; the others run k_inv_cols_r<..., AsxWin> / k_inv_cols_w, which mask every key they
+// form with asx_win_has.  Travels by value as a kernel argument: it is its own selection (see "Selections" below).
 struct AsxWin {
     uint32_t a, w, seed, n;
+    static constexpr bool masks = true;
+    __device__ __forceinline__ AsxWin window_of(size_t, uint32_t) const { return *this; }
 };
 __host__ __device__ inline bool asx_win_has(const AsxWin &z, uint32_t idx)
 {
@@ -145,11 +148,21 @@ __host__ __device__ inline AsxWin asx_win_of(int64_t lo, int64_t hi, uint32_t N)
 
 // Per-pair lag windows (asx_xcorr_windowed_f32_dev): pair k of a group reads its row {lag_min, lag_max} at rows + 2 k step, in device
 // memory, when its kernels run (step 0: one row for every pair).  The group's pointer is already offset to its first pair
-// (Pairs::at, asx_api.hip).  The per-pair kernels (k_inv_cols_rp, k_inv_cols_wp, k_finalize_p, k_refine_pick_p, k_pearson_prep_p)
-// form their AsxWin from it with asx_win_row instead of taking one by value.
+// (Pairs::at, asx_api.hip).  The per-pair kernels (k_inv_cols_r<..., AsxWinRows>, k_refine_pick<AsxWinRows>, k_inv_cols_wp,
+// k_finalize_p, k_pearson_prep_p) form their AsxWin from it with asx_win_row instead of taking one by value: it is a selection too.
+struct AsxWinRows;
+__device__ inline bool asx_win_row(const AsxWinRows &R, size_t pair, uint32_t N, AsxWin &z);
 struct AsxWinRows {
     const int64_t *rows;
     size_t step;
+    static constexpr bool masks = true;
+    __device__ __forceinline__ AsxWin window_of(size_t pair, uint32_t N) const
+    {
+        AsxWin z;
+        (void)asx_win_row(*this, pair, N, z);
+        return z;
+    }
+    __device__ __forceinline__ uint32_t seed_of(size_t pair, uint32_t N) const { return window_of(pair, N).seed; }
 };
 // A valid row (-N <= lag_min <= lag_max <= N-1) gives asx_win_of's window.  Any other row gives n = 0, a window that holds no index:
 // nothing competes, nothing is listed, the running maximum stays empty (seed 0), and k_invalid_rows writes (0, NaN, -2) behind the
@@ -167,7 +180,8 @@ __device__ inline bool asx_win_row(const AsxWinRows &R, size_t pair, uint32_t N,
 // Top-k peaks (asx_xcorr_topk_f32_dev): pass 1 is the strided / windowed call's peak search; pass j >= 2 searches the same Q again
 // with A_j = the call's window minus the zones |lag - lag_i| <= min_separation around the entries i < j (lags, not indices: -N and
 // N-1 are far apart).  k_topk_step (xcorr_kernels.hip) writes entry j and prepares pass j + 1 in the group's AsxTopkPair records; the
-// pass kernels (k_inv_cols_rx, k_inv_cols_wx, k_finalize_x, k_refine_pick_x, k_pearson_prep_x; k_pearson_prep_xl in a pool call) read them.
+// pass kernels (k_inv_cols_r<..., AsxSelTopk<ZC>>, k_refine_pick<AsxSelTopkSeed>, k_inv_cols_wx, k_finalize_x, k_pearson_prep_x;
+// k_pearson_prep_xl in a pool call) read them.
 #define ASX_TOPK_MAX 8
 #define ASX_TK_EMPTY 1u   // A_j is empty: this entry and every later one are (0, NaN, -3)
 #define ASX_TK_INVALID 2u // the pair's row is not a window: every entry is (0, NaN, -2)
@@ -185,7 +199,7 @@ struct AsxTopkPair {
 // wlo + d, so zone i is the distances zo[i] .. zo[i] + wd[i] (zo[i] = lo[i] - wlo, wrapping): two operations per zone and index,
 // for ZC zones -- the kernel's capacity, chosen per pass by the launcher (1, 3 or 7); the unused ones are (~0, 0), which hold
 // no distance (d - ~0 = d + 1 > 0).  (Testing only the first nz zones under a run-time guard kept the lane masks in VGPRs and
-// spilled k_inv_cols_rx to scratch.)
+// spilled the top-k inverse kernel to scratch.)
 template <int ZC> struct AsxWinX {
     uint32_t a, w, seed, n;
     uint32_t zo[ZC];
@@ -213,8 +227,6 @@ template <int ZC> __host__ __device__ inline AsxWinX<ZC> asx_win_x(const AsxTopk
     }
     return z;
 }
-// the zone capacity of the inverse kernel of a pass with nz zones
-inline int asx_tk_zone_cap(int nz) { return nz <= 1 ? 1 : nz <= 3 ? 3 : ASX_TOPK_MAX - 1; }
 // per-lane top-k workspace: the records and pass j's results, which k_topk_step moves to entry j of the caller's arrays
 struct AsxTopkWs {
     AsxTopkPair *pairs;          // [pairs]
@@ -225,20 +237,21 @@ struct AsxTopkWs {
 };
 
 // Which lags compete for pair i of a group, and what seeds its running maximum: the host's one statement of that choice.  Host only,
-// never a kernel argument: the launcher of each kernel family switches on `kind` and hands its flavour what that flavour takes.
-//   ALL     every lag, seed 0 (k_inv_cols_r, k_finalize, ...).  The plan's full window is this: it launches exactly the kernels of
-//           a plan that never had one.
-//   WINDOW  the plan's window (asx_plan_set_lag_window), by value, the seed inside it (k_inv_cols_rw / k_inv_cols_w; k_finalize,
-//           k_refine_pick and k_pearson_prep take the seed)
-//   ROWS    per-pair windows, which replace the plan's: each pair's row and seed from device memory (the _p kernels)
-//   TOPK    a top-k pass >= 2, which replaces both: each pair's window, seed and zones from its record (the _x kernels)
+// never a kernel argument: asx_with_selection (below) turns it into the selection object a kernel template takes (k_inv_cols_r,
+// k_refine_pick); the launchers of the families that still have a kernel per flavour switch on `kind`.
+//   ALL     every lag, seed 0 (k_inv_cols_r<..., AsxSelAll>, k_inv_cols, k_finalize, ...).  The plan's full window is this: it
+//           launches exactly the kernels of a plan that never had one.
+//   WINDOW  the plan's window (asx_plan_set_lag_window), by value, the seed inside it (k_inv_cols_r<..., AsxWin> / k_inv_cols_w;
+//           k_finalize, k_refine_pick and k_pearson_prep take the seed)
+//   ROWS    per-pair windows, which replace the plan's: each pair's row and seed from device memory (<AsxWinRows>, the _p kernels)
+//   TOPK    a top-k pass >= 2, which replaces both: each pair's window, seed and zones from its record (<AsxSelTopk..>, the _x kernels)
 struct AsxSearch {
     enum Kind { ALL, WINDOW, ROWS, TOPK } kind;
     int64_t lo, hi;              // the plan's window in lags ...
     AsxWin win;                  // ... and as indices
     AsxWinRows rows;             // the call's per-pair windows (rows.rows null: none)
     const AsxTopkPair *tk;       // TOPK: the group's records,
-    int tk_zones;                //   the most zones one of them holds in this pass (asx_tk_zone_cap picks the inverse kernel by it)
+    int tk_zones;                //   the most zones one of them holds in this pass (asx_with_selection picks the zone capacity by it)
     unsigned long long *tk_sink; //   and AsxTopkWs::sink
     // the index an empty running maximum stands for, and the one whose exact value competes signed -- where a kernel takes it by
     // value (the ROWS and TOPK kernels read each pair's own)
@@ -257,8 +270,9 @@ struct AsxSearch {
 
 // Pool calls (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev): pair i of a call is source a_i of one pool against sample b_i of another.  Every track of both
 // pools has its forward column pass in the plan's bank (written once per call); k_pool_resolve (rlayout.hip) turns each pair of a launch
-// group into one of these records in the lane's workspace, and the listed kernels (k_rows_rl, k_refine_dots_l, k_pearson_partial_l,
-// k_pearson_prep_l, k_pearson_prep_pl, k_pearson_prep_xl) read pair i's slots and inputs from it instead of from i * pitch.  An index
+// group into one of these records in the lane's workspace, and the listed kernels (k_rows_rl, k_refine_dots<float, AsxAtList>,
+// k_pearson_partial_l, k_pearson_prep_l, k_pearson_prep_pl, k_pearson_prep_xl) read pair i's slots and inputs from it instead of from
+// i * pitch.  An index
 // outside its pool gives slot 0 and ASX_POOL_INVALID: k_rows_rl writes a NaN Q and a zero bound for it -- every inverse tile of every
 // pass leaves at once, whatever the pair's window, zones or seed, so its running maximum stays empty and it can never overflow -- and
 // k_invalid_pairs writes (0, NaN, -4) behind the Pearson kernels (top-k: k_invalid_pairs_k, all k entries, behind the last step).
@@ -281,12 +295,32 @@ struct AsxPoolArgs {
 
 // Where pair i's inputs are, for the exact passes over float or double inputs: src + i * src_pitch and smp + i * smp_pitch (elements;
 // 0 = one track for every pair), or, in a pool call (pl not null, float inputs only), src + pl[i].src_off and smp + pl[i].smp_off
-// (the listed kernels).  Host only: the launchers unpack it.
+// (the listed kernels).  Host only: asx_with_inputs turns it into the inputs object a launcher hands on -- to k_refine_dots<TIn, Where>
+// as it is, where the two pitches were; unpacked for the kernels that still take the pitches or the list.
 template <typename TIn> struct AsxInputs {
     const TIn *src, *smp;
     size_t src_pitch, smp_pitch;
     const AsxPoolPair *pl;
 };
+// Inputs: where pair i's tracks start, in elements from src / smp
+struct AsxAtPitch {
+    size_t src_pitch, smp_pitch; // 0 = one track for every pair
+    __device__ __forceinline__ size_t src_off(size_t pair) const { return pair * src_pitch; }
+    __device__ __forceinline__ size_t smp_off(size_t pair) const { return pair * smp_pitch; }
+};
+struct AsxAtList {
+    const AsxPoolPair *__restrict__ pl;
+    __device__ __forceinline__ size_t src_off(size_t pair) const { return pl[pair].src_off; }
+    __device__ __forceinline__ size_t smp_off(size_t pair) const { return pl[pair].smp_off; }
+};
+// go(the inputs object of `in`): listed in a pool call (float inputs only), else pitched
+template <typename TIn, class F> void asx_with_inputs(const AsxInputs<TIn> &in, F go)
+{
+    if constexpr (std::is_same<TIn, float>::value) {
+        if (in.pl) return go(AsxAtList{ in.pl });
+    }
+    go(AsxAtPitch{ in.src_pitch, in.smp_pitch });
+}
 
 // kernel launchers (defined in xcorr_kernels.hip, called from asx_api.hip)
 struct AsxCand {          // one near-maximum lag found by a column tile
@@ -319,7 +353,7 @@ struct AsxPeakWs {
     float *tile_peak;      // [pairs][M2 / T] SIGNED float32 r (times F) at the best lag of each k_inv_cols_r tile
 };
 
-// Per-lane workspace of the pruned inverse pass (rlayout.hip: k_rows_re, k_tile_bounds, k_prune_select, k_inv_cols_rq)
+// Per-lane workspace of the pruned inverse pass (rlayout.hip: k_rows_re, k_tile_bounds, k_prune_select, k_inv_cols_r<..., AsxSelPrune>)
 struct AsxPrune {
     float *eng;            // [pairs][M1 + 1][ntiles] sum of |Q[k1][j2]|^2 over the tile's columns (k_rows_re)
     float *ub;             // [pairs][ntiles] upper bound of |r^| over the tile
@@ -329,6 +363,73 @@ struct AsxPrune {
     unsigned char *skip;   // [pairs][ntiles] 1 = the second launch leaves the tile out
     unsigned long long *stats; // [2] tiles transformed, tiles in all: cumulative over the plan's life (asx_plan_prune_stats)
 };
+
+// Selections: the device-side partners of AsxSearch, the last argument of a kernel template <..., Sel>.  Every method is
+// __forceinline__: emitted as a function and called, window_of changed the inverse kernels by thousands of instructions.
+//   k_inv_cols_r masks: Sel::masks, and sel.window_of(pair, N) is what asx_win_has is asked and whose .seed competes signed --
+//   AsxSelAll, AsxWin, AsxWinRows, AsxSelTopk<ZC>, and the pruned pass's AsxSelPrune<FIRST>.
+//   k_refine_pick asks sel.seed_of(pair, N) alone: AsxSelSeed (ALL and WINDOW), AsxWinRows, AsxSelTopkSeed.
+struct AsxSelAll {
+    static constexpr bool masks = false;
+    __device__ __forceinline__ AsxWin window_of(size_t, uint32_t) const { return AsxWin{}; }
+};
+template <int ZC> struct AsxSelTopk { // ZC: the zones the kernel tests
+    const AsxTopkPair *__restrict__ X;
+    static constexpr bool masks = true;
+    __device__ __forceinline__ AsxWinX<ZC> window_of(size_t pair, uint32_t) const { return asx_win_x<ZC>(X, pair); }
+};
+struct AsxSelSeed {
+    uint32_t seed;
+    __device__ __forceinline__ uint32_t seed_of(size_t, uint32_t) const { return seed; }
+};
+struct AsxSelTopkSeed {
+    const AsxTopkPair *__restrict__ X;
+    __device__ __forceinline__ uint32_t seed_of(size_t pair, uint32_t) const { return X[pair].z.seed; }
+};
+// The pruned inverse pass (AsxPrune): every lag competes, nothing is dumped (the kernel has no r_out argument), and the block's tile
+// is not its place in the grid.  FIRST: grid (npairs, 2) -- y = 0 the pair's largest-bound tile, which holds the peak on all but
+// contrived inputs, y = 1 the seed's tile (tile 0: lag 0 competes signed), gone when that is the same tile.  !FIRST: the full grid;
+// a block whose flag is set leaves before it asks for anything else.
+template <bool FIRST> struct AsxSelPrune {
+    const int *__restrict__ best;
+    const unsigned char *__restrict__ skip;
+    static constexpr bool masks = false;
+    __device__ __forceinline__ AsxWin window_of(size_t, uint32_t) const { return AsxWin{}; }
+};
+// The block's tile, from the tile of its place in the grid (tile width T, rows of M2 columns): asx_sel_takes false = the block
+// leaves.  (The pruned pass's are written as they are -- one || and one && -- because that is the shape the kernels they replace
+// compiled from: the same tests stated the other way round gave other branches.)
+template <class Sel> __device__ __forceinline__ bool asx_sel_takes(const Sel &, int, int, int) { return true; }
+template <class Sel> __device__ __forceinline__ int asx_sel_tile(const Sel &, int grid_tile) { return grid_tile; }
+template <bool FIRST> __device__ __forceinline__ bool asx_sel_takes(const AsxSelPrune<FIRST> &q, int grid_tile, int M2, int T)
+{
+    if constexpr (FIRST) {
+        const int bt = q.best[blockIdx.x];
+        return blockIdx.y == 0 || bt != 0;
+    } else {
+        return grid_tile * T < M2 && !q.skip[(size_t)blockIdx.x * (size_t)(M2 / T) + grid_tile];
+    }
+}
+template <bool FIRST> __device__ __forceinline__ int asx_sel_tile(const AsxSelPrune<FIRST> &q, int grid_tile)
+{
+    if constexpr (FIRST) return blockIdx.y == 0 ? q.best[blockIdx.x] : 0;
+    else return grid_tile;
+}
+// go(the selection object of q).  ZC...: the zone capacities the kernel family's top-k instances are compiled for, ascending, the
+// last one ASX_TOPK_MAX - 1 -- a pass runs the first that holds its zones; none: the family asks for the seed alone.
+template <int... ZC, class F> void asx_with_selection(const AsxSearch &q, F go)
+{
+    if constexpr (sizeof...(ZC) == 0) {
+        if (q.kind == AsxSearch::TOPK) go(AsxSelTopkSeed{ q.tk });
+        else if (q.kind == AsxSearch::ROWS) go(q.rows);
+        else go(AsxSelSeed{ q.seed() });
+    } else {
+        if (q.kind == AsxSearch::TOPK) (void)((q.tk_zones <= ZC && (go(AsxSelTopk<ZC>{ q.tk }), true)) || ...);
+        else if (q.kind == AsxSearch::ROWS) go(q.rows);
+        else if (q.kind == AsxSearch::WINDOW) go(q.win);
+        else go(AsxSelAll{});
+    }
+}
 
 // Where forward column passes are (real-column plans), and how the pairs of a launch group find theirs: the host's one statement of
 // that.  Host only, never a kernel argument: the launchers of rlayout.hip unpack it.

@@ -1,6 +1,6 @@
 // csrc/pearson_partial_body.h -- the body of k_pearson_partial and of its listed form k_pearson_partial_l (xcorr_kernels.hip),
-// included INSIDE both kernels (k_pearson_partial has to stay the kernel it was).  ASX_SRC_OF(pair) / ASX_SMP_OF(pair): as in
-// refine_dots_body.h.
+// included INSIDE both kernels (k_pearson_partial has to stay the kernel it was).  ASX_SRC_OF(pair) / ASX_SMP_OF(pair): where pair's
+// inputs start, in elements from src / smp (by default pair * src_pitch / pair * smp_pitch; the listed form defines its own).
 #ifndef ASX_SRC_OF
 #define ASX_SRC_OF(pair) pair * src_pitch
 #define ASX_SMP_OF(pair) pair * smp_pitch

@@ -775,50 +775,98 @@ __device__ __forceinline__ dd_t dd_add(dd_t a, dd_t b)
     return r;
 }
 
-// src_pitch / smp_pitch: the pairs' input steps in elements (0 = one track for every pair)
-template <typename TIn>
+// at: where pair i's inputs start, in elements from src / smp -- AsxAtPitch, or AsxAtList (asx_xcorr_pool_f32_dev, float inputs)
+template <typename TIn, class Where>
 __global__ __launch_bounds__(ASX_THREADS) void k_refine_dots(const AsxDev *__restrict__ Pp, const TIn *__restrict__ src,
-                                                              const TIn *__restrict__ smp, size_t src_pitch, size_t smp_pitch, AsxPeakWs W)
+                                                              const TIn *__restrict__ smp, Where at, AsxPeakWs W)
 {
-#include "refine_dots_body.h"
-}
-
-// the listed form (asx_xcorr_pool_f32_dev): pair i's inputs at src + PL[i].src_off, smp + PL[i].smp_off
-__global__ __launch_bounds__(ASX_THREADS) void k_refine_dots_l(const AsxDev *__restrict__ Pp, const float *__restrict__ src,
-                                                                const float *__restrict__ smp, const AsxPoolPair *__restrict__ PL,
-                                                                AsxPeakWs W)
-{
-    typedef float TIn;
-#define ASX_SRC_OF(pair) PL[pair].src_off
-#define ASX_SMP_OF(pair) PL[pair].smp_off
-#include "refine_dots_body.h"
+    __shared__ double red[2][ASX_THREADS / 64];
+    const size_t pair = blockIdx.y;
+    const uint32_t ncand = W.refine_n[pair];
+    if (blockIdx.x >= ncand) return;
+    const uint32_t N = Pp->N, L = 2u * N;
+    const TIn *x = src + at.src_off(pair);
+    const TIn *y = smp + at.smp_off(pair);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t c = blockIdx.x; c < ncand; c += gridDim.x) {
+        const uint32_t k = W.refine_idx[pair * (size_t)W.cap + c];
+        double hi = 0.0, lo = 0.0;
+        for (uint32_t n = threadIdx.x; n < N; n += ASX_THREADS) {
+            uint32_t i = n + k;
+            if (i >= L) i -= L;
+            const double a = (double)x[i], b = (double)y[n];
+            const double p = a * b;
+            double pe = 0.0;
+            if (sizeof(TIn) == sizeof(double)) pe = fma(a, b, -p);
+            const double s = hi + p;
+            const double bb = s - hi;
+            lo += ((hi - (s - bb)) + (p - bb)) + pe;
+            hi = s;
+        }
+        dd_t acc;
+        acc.hi = hi; acc.lo = lo;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            dd_t o;
+            o.hi = __shfl_xor(acc.hi, off, 64);
+            o.lo = __shfl_xor(acc.lo, off, 64);
+            acc = dd_add(acc, o);
+        }
+        if (lane == 0) { red[0][wave] = acc.hi; red[1][wave] = acc.lo; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            dd_t t;
+            t.hi = red[0][0]; t.lo = red[1][0];
+            for (int w = 1; w < ASX_THREADS / 64; w++) {
+                dd_t o;
+                o.hi = red[0][w]; o.lo = red[1][w];
+                t = dd_add(t, o);
+            }
+            W.refine_val[pair * (size_t)W.cap + c] = t.hi + t.lo;
+        }
+        __syncthreads();
+    }
 }
 
 // grid (npairs): the reference's max_abs_index rule (src/cross_correlation.c:52-67) on the exact values:
 // key(seed) = r[seed] signed, key(i) = |r[i]|, largest key, smallest lag among equal keys; a NaN key never
 // wins unless it sits at the seed (index 0, or the first index of a lag window: AsxWin).
+// sel.seed_of(pair): the plan's (AsxSelSeed), the pair's own from its row (AsxWinRows) or the pass's from the pair's top-k record
+// (AsxSelTopkSeed).
+template <class Sel>
 __global__ __launch_bounds__(ASX_THREADS) void k_refine_pick(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
-                                                              uint32_t seed)
+                                                              Sel sel)
 {
-#include "refine_pick_body.h"
-}
-
-// the per-pair form (asx_xcorr_windowed_f32_dev): the seed is the pair's own, from its row
-__global__ __launch_bounds__(ASX_THREADS) void k_refine_pick_p(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
-                                                                AsxWinRows R)
-{
-    AsxWin Z;
-    (void)asx_win_row(R, blockIdx.x, Pp->N, Z);
-    const uint32_t seed = Z.seed;
-#include "refine_pick_body.h"
-}
-
-// the top-k form (passes 2..k): the seed is the pass's, from the pair's record
-__global__ __launch_bounds__(ASX_THREADS) void k_refine_pick_x(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
-                                                                const AsxTopkPair *__restrict__ X)
-{
-    const uint32_t seed = X[blockIdx.x].z.seed;
-#include "refine_pick_body.h"
+    const uint32_t seed = sel.seed_of(blockIdx.x, Pp->N);
+    __shared__ double rkey[ASX_THREADS / 64];
+    __shared__ uint32_t ridx[ASX_THREADS / 64];
+    const size_t pair = blockIdx.x;
+    const uint32_t n = W.refine_n[pair];
+    if (n < 2u) return;
+    double bk = -INFINITY;
+    uint32_t bi = 0xFFFFFFFFu;
+    for (uint32_t i = threadIdx.x; i < n; i += ASX_THREADS) {
+        const uint32_t idx = W.refine_idx[pair * (size_t)W.cap + i];
+        const double v = W.refine_val[pair * (size_t)W.cap + i];
+        double key;
+        if (idx == seed) key = (v != v) ? (double)INFINITY : v + 0.0;
+        else { key = fabs(v); if (key != key) key = -(double)INFINITY; }
+        if (key > bk || (key == bk && idx < bi)) { bk = key; bi = idx; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ok = __shfl_xor(bk, off, 64);
+        const uint32_t oi = (uint32_t)__shfl_xor((int)bi, off, 64);
+        if (ok > bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { rkey[wave] = bk; ridx[wave] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < ASX_THREADS / 64; w++)
+            if (rkey[w] > bk || (rkey[w] == bk && ridx[w] < bi)) { bk = rkey[w]; bi = ridx[w]; }
+        if (bi != 0xFFFFFFFFu) seg[pair] = make_seg(bi, Pp->N);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1293,28 +1341,19 @@ void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, d
                        coef, ret);
 }
 
-// The strided / listed choice of the exact passes: go(kernel, where pair i's inputs are...) with the strided kernel and the two
-// pitches, or (pool calls, float inputs only) the listed kernel and the pairs' records.
-template <typename TIn, class KS, class KL, class F> static void launch_by_inputs(const AsxInputs<TIn> &in, KS strided, KL listed, F go)
-{
-    if constexpr (std::is_same<TIn, float>::value) {
-        if (in.pl) return go(listed, in.pl);
-    }
-    go(strided, in.src_pitch, in.smp_pitch);
-}
-
 template <typename TIn>
 void asx_launch_refine(const AsxDev &P, const AsxInputs<TIn> &in, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s,
                        int dot_blocks, bool pick, const AsxSearch &q)
 {
-    launch_by_inputs(in, k_refine_dots<TIn>, k_refine_dots_l, [&](auto kernel, auto... where) {
-        hipLaunchKernelGGL(kernel, dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, in.src, in.smp, where..., W);
+    asx_with_inputs(in, [&](auto at) {
+        hipLaunchKernelGGL((k_refine_dots<TIn, decltype(at)>), dim3(dot_blocks, npairs), dim3(ASX_THREADS), 0, s, P.self_dev, in.src,
+                           in.smp, at, W);
     });
     if (!pick) return;
     const dim3 grid(npairs), block(ASX_THREADS);
-    if (q.kind == AsxSearch::TOPK) hipLaunchKernelGGL(k_refine_pick_x, grid, block, 0, s, P.self_dev, W, seg, q.tk);
-    else if (q.kind == AsxSearch::ROWS) hipLaunchKernelGGL(k_refine_pick_p, grid, block, 0, s, P.self_dev, W, seg, q.rows);
-    else hipLaunchKernelGGL(k_refine_pick, grid, block, 0, s, P.self_dev, W, seg, q.seed());
+    asx_with_selection(q, [&](auto sel) {
+        hipLaunchKernelGGL(k_refine_pick<decltype(sel)>, grid, block, 0, s, P.self_dev, W, seg, sel);
+    });
 }
 
 // Partial blocks per pair: a function of the segment's BASIS LENGTH ONLY -- one block per 16 sweeps of 256 threads x 4
@@ -1337,9 +1376,13 @@ template <typename TIn, bool SPEC>
 static void launch_pearson_partial(const AsxInputs<TIn> &in, uint32_t basis_len, const AsxSeg *seg, const AsxSpecWs &S, double *psums,
                                    int npairs, hipStream_t s)
 {
-    launch_by_inputs(in, k_pearson_partial<TIn, SPEC>, k_pearson_partial_l<SPEC>, [&](auto kernel, auto... where) {
-        hipLaunchKernelGGL(kernel, dim3(asx_pearson_blocks(basis_len), npairs), dim3(ASX_THREADS), 0, s, in.src, in.smp, where...,
-                           basis_len, seg, psums, S);
+    const dim3 grid(asx_pearson_blocks(basis_len), npairs), block(ASX_THREADS);
+    asx_with_inputs(in, [&](auto at) {
+        if constexpr (std::is_same<decltype(at), AsxAtList>::value)
+            hipLaunchKernelGGL(k_pearson_partial_l<SPEC>, grid, block, 0, s, in.src, in.smp, at.pl, basis_len, seg, psums, S);
+        else
+            hipLaunchKernelGGL((k_pearson_partial<TIn, SPEC>), grid, block, 0, s, in.src, in.smp, at.src_pitch, at.smp_pitch, basis_len,
+                               seg, psums, S);
     });
 }
 

@@ -1,5 +1,5 @@
 """The pruned inverse column pass (asx_plan_set_prune, include/audiosync/xcorr_hip.h; csrc/rlayout.hip: k_rows_re, k_tile_bounds,
-k_prune_select, k_inv_cols_rq) against the unpruned pass ON THE SAME PLAN: lag and ret equal, the coefficient bit for bit, and all
+k_prune_select, k_inv_cols_r<..., AsxSelPrune>) against the unpruned pass ON THE SAME PLAN: lag and ret equal, the coefficient bit for bit, and all
 three against the float64 oracle under the project's tolerance.  The coefficient of the spectral Pearson form is built from the
 float32 r[peak], so its bits also say that k_rows_re leaves the Q that k_rows_r leaves.
 

@@ -116,7 +116,7 @@ def test_one_wave_row_kernel_issues_every_look_up_in_front_of_its_rows(isa):
 
 def test_inverse_column_kernel_600_asks_for_its_twiddle_in_front_of_the_rows(isa):
     """k_inv_cols_r, 600-row tiles: between the first row load and the first barrier there is no 8-byte table load left"""
-    ins = one(isa, "void k_inv_cols_r<Sched<600, 10, 10, 6>, 16, 512>")
+    ins = one(isa, "void k_inv_cols_r<Sched<600, 10, 10, 6>, 16, 512, AsxSelAll,")
     rows = positions(ins, lambda s: s.startswith("global_load_dwordx4") and s.endswith(" nt"))
     first_barrier = positions(ins, lambda s: s.startswith("s_barrier"))[0]
     tables = positions(ins, lambda s: s.startswith("global_load_dwordx2"))

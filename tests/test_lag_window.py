@@ -11,7 +11,7 @@ import pytest
 import oracle
 from lag_window_model import model, window_indices, window_peak
 from test_kernel_resources import READELF, demangled, kernels_of
-from util import ROOT, asx, graft
+from util import ROOT, asx, graft, kernel_forms
 
 NEW_ABI = ("asx_plan_set_lag_window", "asx_plan_lag_window", "asx_stream_set_lag_window")
 
@@ -53,16 +53,17 @@ def kernels():
 
 
 def test_windowed_inverse_kernels_exist_and_keep_the_budgets_of_their_unwindowed_forms(kernels):
-    """k_inv_cols_rw beside every k_inv_cols_r, k_inv_cols_w beside every k_inv_cols: same LDS (so the same blocks per CU by
-    tile), <= 128 VGPRs, no scratch"""
+    """the window form beside every plain instance of k_inv_cols_r (<..., AsxWin> beside <..., AsxSelAll>) and of k_inv_cols
+    (k_inv_cols_w), same template arguments: same LDS (so the same blocks per CU by tile), <= 128 VGPRs, no scratch"""
     pairs = 0
-    for plain, win in (("void k_inv_cols_r<", "void k_inv_cols_rw<"), ("void k_inv_cols<", "void k_inv_cols_w<")):
-        base = {n[len(plain):].split(">(")[0]: r for n, r in kernels.items() if n.startswith(plain)}
-        wind = {n[len(win):].split(">(")[0]: r for n, r in kernels.items() if n.startswith(win)}
-        assert base and set(base) == set(wind), (plain, sorted(base), sorted(wind))
-        for k, r in wind.items():
-            assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (win, k, r)
-            assert r["group_segment_fixed_size"] == base[k]["group_segment_fixed_size"], (win, k, r, base[k])
+    for family in ("k_inv_cols_r", "k_inv_cols"):
+        base = kernel_forms(kernels, family, "all")
+        wind = kernel_forms(kernels, family, "window")
+        assert base and set(base) == set(wind), (family, sorted(base), sorted(wind))
+        for k, rs in wind.items():
+            ((_, r),), ((_, b),) = rs, base[k]
+            assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (family, k, r)
+            assert r["group_segment_fixed_size"] == b["group_segment_fixed_size"], (family, k, r, b)
             pairs += 1
     assert pairs == 3 + 8, pairs
 

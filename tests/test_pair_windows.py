@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from test_kernel_resources import READELF, demangled, kernels_of
-from util import ROOT, asx, graft
+from util import ROOT, asx, graft, kernel_forms
 
 NEW_ABI = ("asx_xcorr_windowed_f32_dev",)
 
@@ -39,27 +39,26 @@ def kernels():
 
 
 def test_per_pair_inverse_kernels_sit_beside_the_windowed_ones(kernels):
-    """k_inv_cols_rp beside every k_inv_cols_rw, k_inv_cols_wp beside every k_inv_cols_w, same template arguments: same LDS,
-    <= 128 VGPRs, no scratch"""
+    """the per-pair form beside every window form of k_inv_cols_r (<..., AsxWinRows> beside <..., AsxWin>) and of k_inv_cols
+    (k_inv_cols_wp beside k_inv_cols_w), same template arguments: same LDS, <= 128 VGPRs, no scratch"""
     pairs = 0
-    for win, per in (("void k_inv_cols_rw<", "void k_inv_cols_rp<"), ("void k_inv_cols_w<", "void k_inv_cols_wp<")):
-        base = {n[len(win):].split(">(")[0]: r for n, r in kernels.items() if n.startswith(win)}
-        mine = {n[len(per):].split(">(")[0]: r for n, r in kernels.items() if n.startswith(per)}
-        assert base and set(base) == set(mine), (win, sorted(base), sorted(mine))
-        for k, r in mine.items():
-            assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (per, k, r)
-            assert r["group_segment_fixed_size"] == base[k]["group_segment_fixed_size"], (per, k, r, base[k])
+    for family in ("k_inv_cols_r", "k_inv_cols"):
+        base = kernel_forms(kernels, family, "window")
+        mine = kernel_forms(kernels, family, "rows")
+        assert base and set(base) == set(mine), (family, sorted(base), sorted(mine))
+        for k, rs in mine.items():
+            ((_, r),), ((_, b),) = rs, base[k]
+            assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (family, k, r)
+            assert r["group_segment_fixed_size"] == b["group_segment_fixed_size"], (family, k, r, b)
             pairs += 1
     assert pairs == 3 + 8, pairs
 
 
 def test_per_pair_tail_kernels_meet_the_budgets(kernels):
-    found = {}
-    for n, r in kernels.items():
-        m = re.match(r"(?:void )?(k_finalize_p|k_refine_pick_p|k_pearson_prep_p|k_invalid_rows)\b", n)
-        if m:
-            found.setdefault(m.group(1), []).append((n, r))
-    assert {k: len(v) for k, v in found.items()} == {"k_finalize_p": 1, "k_refine_pick_p": 1, "k_pearson_prep_p": 2,
+    found = {f: [(f + " " + k, r) for k, rs in kernel_forms(kernels, f, "rows").items() for _, r in rs]
+             for f in ("k_finalize", "k_refine_pick", "k_pearson_prep")}
+    found["k_invalid_rows"] = [(n, r) for n, r in kernels.items() if n.startswith("k_invalid_rows(")]
+    assert {k: len(v) for k, v in found.items()} == {"k_finalize": 1, "k_refine_pick": 1, "k_pearson_prep": 2,
                                                      "k_invalid_rows": 1}, found
     for n, r in sum(found.values(), []):
         assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (n, r)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from test_kernel_resources import READELF, demangled, kernels_of
-from util import ROOT, asx, graft
+from util import ROOT, asx, graft, kernel_forms
 
 
 def test_new_symbol_is_declared_listed_and_exported():
@@ -105,9 +105,11 @@ def test_listed_tail_kernels_meet_the_budgets(kernels):
     """the listed forms of the tail kernels that read inputs, beside the forms they mirror, with the same LDS"""
     found = {}
     for k, r in kernels.items():
-        m = re.match(r"(?:void )?(k_pool_resolve|k_invalid_pairs|k_refine_dots_l|k_pearson_partial_l|k_pearson_prep_l|k_pearson_prep_pl)\b", k)
+        m = re.match(r"(?:void )?(k_pool_resolve|k_invalid_pairs|k_pearson_partial_l|k_pearson_prep_l|k_pearson_prep_pl)\b", k)
         if m:
             found.setdefault(m.group(1), []).append((k, r))
+    listed_dots = kernel_forms(kernels, "k_refine_dots", inputs="listed")
+    found["k_refine_dots_l"] = [("k_refine_dots " + k, r) for k, rs in listed_dots.items() for _, r in rs]
     assert {k: len(v) for k, v in found.items()} == {"k_pool_resolve": 1, "k_invalid_pairs": 1, "k_refine_dots_l": 1,
                                                      "k_pearson_partial_l": 2, "k_pearson_prep_l": 2, "k_pearson_prep_pl": 2}, found
     for name, ks in found.items():
@@ -118,5 +120,5 @@ def test_listed_tail_kernels_meet_the_budgets(kernels):
     for pfx in ("void k_pearson_prep_l<", "void k_pearson_prep_pl<"):
         got = {_args(k, pfx): v for k, v in lds.items() if k.startswith(pfx)}
         assert got == prep, (pfx, got, prep)
-    dots = [v for k, v in lds.items() if k.startswith("void k_refine_dots<float>")]
-    assert dots and [v for k, v in lds.items() if k.startswith("k_refine_dots_l")] == dots
+    dots = [r["group_segment_fixed_size"] for _, r in kernel_forms(kernels, "k_refine_dots", inputs="pitched")["float"]]
+    assert dots and [r["group_segment_fixed_size"] for _, r in listed_dots["float"]] == dots

@@ -8,7 +8,7 @@ import pytest
 
 import test_kernel_isa_order as order
 import test_kernel_resources as res
-from util import asx, graft
+from util import asx, graft, kernel_forms
 
 
 @pytest.fixture(scope="module")
@@ -33,8 +33,8 @@ def test_row_kernels_with_tile_energies_keep_the_row_budgets(kernels):
 
 
 def test_pruned_inverse_kernels_keep_the_column_budgets(kernels):
-    cols = [(n, r) for n, r in kernels.items() if n.startswith("void k_inv_cols_rq<")]
-    assert len(cols) == 6, sorted(n for n, _ in cols)  # three column schedules x {first two tiles, the rest}
+    cols = [(args + " " + first, r) for args, rs in kernel_forms(kernels, "k_inv_cols_r", "prune").items() for first, r in rs]
+    assert len(cols) == 6 and sorted(n.split()[-1] for n, _ in cols) == ["false"] * 3 + ["true"] * 3, sorted(n for n, _ in cols)  # three column schedules x {first two tiles, the rest}
     for n, r in cols:
         assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (n, r)
         m1 = int(re.search(r"Sched<(\d+)", n).group(1))
@@ -46,7 +46,7 @@ def test_pruned_inverse_kernels_keep_the_column_budgets(kernels):
 
 def test_the_existing_row_and_inverse_kernels_are_still_there(kernels):
     assert len([n for n in kernels if n.startswith("void k_rows_r<")]) == 12
-    assert len([n for n in kernels if n.startswith("void k_inv_cols_r<")]) == 3
+    assert len(kernel_forms(kernels, "k_inv_cols_r", "all")) == 3
 
 
 def test_two_half_row_kernel_with_energies_issues_no_load_behind_a_barrier():

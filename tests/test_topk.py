@@ -11,7 +11,7 @@ import pytest
 
 from test_kernel_resources import READELF, demangled, kernels_of
 from topk_model import allowed, brute_peaks, topk_peaks
-from util import ROOT, asx, graft
+from util import ROOT, asx, graft, kernel_forms
 
 
 def test_new_symbol_is_declared_listed_and_exported():
@@ -130,36 +130,28 @@ def kernels():
 
 
 def test_topk_inverse_kernels_sit_beside_the_per_pair_ones(kernels):
-    """k_inv_cols_rx (three zone capacities) beside every k_inv_cols_rp, k_inv_cols_wx beside every k_inv_cols_wp: same LDS,
-    <= 128 VGPRs, no scratch"""
+    """the top-k form beside every per-pair form, same template arguments: k_inv_cols_r<..., AsxSelTopk<ZC>> in three zone
+    capacities beside <..., AsxWinRows>, k_inv_cols_wx beside every k_inv_cols_wp: same LDS, <= 128 VGPRs, no scratch"""
     n = 0
-    for per, top in (("void k_inv_cols_rp<", "void k_inv_cols_rx<"), ("void k_inv_cols_wp<", "void k_inv_cols_wx<")):
-        base = {k[len(per):].split(">(")[0]: r for k, r in kernels.items() if k.startswith(per)}
-        mine = {}
-        for k, r in kernels.items():
-            if k.startswith(top):
-                args = k[len(top):].split(">(")[0]
-                if top.endswith("rx<"):
-                    args, zc = args.rsplit(", ", 1)
-                    assert zc in ("1", "3", "7"), k
-                mine.setdefault(args, []).append(r)
-        assert base and set(base) == set(mine), (top, sorted(base), sorted(mine))
+    for family, caps in (("k_inv_cols_r", ["1", "3", "7"]), ("k_inv_cols", [None])):
+        base = kernel_forms(kernels, family, "rows")
+        mine = kernel_forms(kernels, family, "topk")
+        assert base and set(base) == set(mine), (family, sorted(base), sorted(mine))
         for args, rs in mine.items():
-            assert len(rs) == (3 if top.endswith("rx<") else 1), (top, args)
-            for r in rs:
-                assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (top, args, r)
-                assert r["group_segment_fixed_size"] == base[args]["group_segment_fixed_size"], (top, args, r)
+            assert sorted(str(zc) for zc, _ in rs) == [str(c) for c in caps], (family, args)
+            ((_, b),) = base[args]
+            for _, r in rs:
+                assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (family, args, r)
+                assert r["group_segment_fixed_size"] == b["group_segment_fixed_size"], (family, args, r)
                 n += 1
     assert n == 3 * 3 + 8, n
 
 
 def test_topk_tail_kernels_meet_the_budgets(kernels):
-    found = {}
-    for k, r in kernels.items():
-        m = re.match(r"(?:void )?(k_finalize_x|k_refine_pick_x|k_pearson_prep_x|k_topk_step)\b", k)
-        if m:
-            found.setdefault(m.group(1), []).append((k, r))
-    assert {k: len(v) for k, v in found.items()} == {"k_finalize_x": 1, "k_refine_pick_x": 1, "k_pearson_prep_x": 2,
+    found = {f: [(f + " " + k, r) for k, rs in kernel_forms(kernels, f, "topk").items() for _, r in rs]
+             for f in ("k_finalize", "k_refine_pick", "k_pearson_prep")}
+    found["k_topk_step"] = [(k, r) for k, r in kernels.items() if k.startswith("k_topk_step(")]
+    assert {k: len(v) for k, v in found.items()} == {"k_finalize": 1, "k_refine_pick": 1, "k_pearson_prep": 2,
                                                      "k_topk_step": 1}, found
     for k, r in itertools.chain.from_iterable(found.values()):
         assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (k, r)

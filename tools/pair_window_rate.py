@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What per-pair lag windows (asx_xcorr_windowed_f32_dev) cost against the plain strided call: pairs per second of
 asx_xcorr_strided_f32_dev and of asx_xcorr_windowed_f32_dev with every row full ([-N, N-1]), so that both find the same peaks,
-and of asx_xcorr_strided_f32_dev with the plan window [-N+1, N-1] (the plan-window kernels k_inv_cols_rw: what the masking of the
+and of asx_xcorr_strided_f32_dev with the plan window [-N+1, N-1] (the plan-window kernels k_inv_cols_r<..., AsxWin>: what the masking of the
 windowed inverse body costs by itself).
 
     python3 tools/pair_window_rate.py [--runs 9] [--warmup 2] [--cases 1440000x124,480000x1024] [--out FILE]

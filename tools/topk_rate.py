@@ -13,7 +13,7 @@ profiling off, and --reps calls of one kind are timed back to back between two H
 the host.  The kinds ALTERNATE (strided, k = 1, k = 2, k = 4, strided, ...; --order, a permutation of 0,1,2,4) so that clock drift
 falls on all; reported are the median over --runs rounds of the time per call, the cost of one further pass ((t_k - t_1) / (k - 1)),
 whether k = 1 returned the strided call's bits, and how many entries came back marked inexact (ret = 1: the exact mode would have
-taken the second look at them).  The kernels of each pass (k_inv_cols_rx and the tail) show by name in a kernel trace of the same
+taken the second look at them).  The kernels of each pass (k_inv_cols_r<..., AsxSelTopk<ZC>> and the tail) show by name in a kernel trace of the same
 run (tools/README.md).  Prints one JSON line per length and kind of pair (and writes them to --out)."""
 import argparse
 import json
