@@ -122,7 +122,7 @@ size_t asx_plan_peak_capacity(const asx_plan *plan);
  * near-tie lists and the second look (which runs with the window of the call that listed the pair).  When the windowed peak
  * is the unwindowed one, every output is bit for bit the unwindowed call's.  The full window runs exactly the kernels of a
  * plan that never had one; any other window runs the inverse column pass in its windowed form (csrc/rlayout.hip
- * k_inv_cols_rw, csrc/xcorr_kernels.hip k_inv_cols_w).  The window does not prune work: the call costs what it costs.
+ * k_inv_cols_r<..., AsxWin>, csrc/xcorr_kernels.hip k_inv_cols<..., AsxWin>).  The window does not prune work: the call costs what it costs.
  * Every entry point on the plan honours it (asx_xcorr_debug_r_dev still returns the whole of r; asx_xcorr_batch_multi /
  * _multi_dev: set it on each plan).  Setting it neither allocates nor synchronises: it is safe between captured calls.
  * asx_plan_set_lag_window returns -1 and leaves the window unchanged when lag_min < -N, lag_max > N-1 or

@@ -123,8 +123,8 @@ struct AsxSeg {           // per pair, produced by k_finalize
 // (lag l >= 0 is index l, lag l < 0 index 2N + l: the inverse of the wrap at src/cross_correlation.c:256-263) -- one range, or two
 // when the window holds lag 0 and a negative lag.  seed = the smallest in-window index: the element that starts the reference's
 // running maximum with its SIGNED value (arr[0], :56), 0 for every window that holds lag 0.  The full window (a = N, w = 2N - 1,
-// seed = 0) runs the kernels without a window; the others run k_inv_cols_r<..., AsxWin> / k_inv_cols_w, which mask every key they
-// form with asx_win_has.  Travels by value as a kernel argument: it is its own selection (see "Selections" below).
+// seed = 0) runs the kernels without a window; the others run k_inv_cols_r<..., AsxWin> / k_inv_cols<..., AsxWin>, which mask every
+// key they form with asx_win_has.  Travels by value as a kernel argument: it is its own selection (see "Selections" below).
 struct AsxWin {
     uint32_t a, w, seed, n;
     static constexpr bool masks = true;
@@ -148,8 +148,8 @@ __host__ __device__ inline AsxWin asx_win_of(int64_t lo, int64_t hi, uint32_t N)
 
 // Per-pair lag windows (asx_xcorr_windowed_f32_dev): pair k of a group reads its row {lag_min, lag_max} at rows + 2 k step, in device
 // memory, when its kernels run (step 0: one row for every pair).  The group's pointer is already offset to its first pair
-// (Pairs::at, asx_api.hip).  The per-pair kernels (k_inv_cols_r<..., AsxWinRows>, k_refine_pick<AsxWinRows>, k_inv_cols_wp,
-// k_finalize_p, k_pearson_prep_p) form their AsxWin from it with asx_win_row instead of taking one by value: it is a selection too.
+// (Pairs::at, asx_api.hip).  The per-pair kernels (the <..., AsxWinRows> instances of k_inv_cols_r, k_inv_cols, k_finalize
+// and k_refine_pick; k_pearson_prep_p, _pl) form their AsxWin from it with asx_win_row instead of taking one by value: it is a selection too.
 struct AsxWinRows;
 __device__ inline bool asx_win_row(const AsxWinRows &R, size_t pair, uint32_t N, AsxWin &z);
 struct AsxWinRows {
@@ -180,8 +180,8 @@ __device__ inline bool asx_win_row(const AsxWinRows &R, size_t pair, uint32_t N,
 // Top-k peaks (asx_xcorr_topk_f32_dev): pass 1 is the strided / windowed call's peak search; pass j >= 2 searches the same Q again
 // with A_j = the call's window minus the zones |lag - lag_i| <= min_separation around the entries i < j (lags, not indices: -N and
 // N-1 are far apart).  k_topk_step (xcorr_kernels.hip) writes entry j and prepares pass j + 1 in the group's AsxTopkPair records; the
-// pass kernels (k_inv_cols_r<..., AsxSelTopk<ZC>>, k_refine_pick<AsxSelTopkSeed>, k_inv_cols_wx, k_finalize_x, k_pearson_prep_x;
-// k_pearson_prep_xl in a pool call) read them.
+// pass kernels (k_inv_cols_r / k_inv_cols<..., AsxSelTopk<ZC>>, k_finalize / k_refine_pick<AsxSelTopkSeed>, k_pearson_prep_x, _xl)
+// read them.
 #define ASX_TOPK_MAX 8
 #define ASX_TK_EMPTY 1u   // A_j is empty: this entry and every later one are (0, NaN, -3)
 #define ASX_TK_INVALID 2u // the pair's row is not a window: every entry is (0, NaN, -2)
@@ -233,18 +233,19 @@ struct AsxTopkWs {
     int64_t *lag;                // [pairs]
     double *coef;                // [pairs]
     int32_t *ret;                // [pairs]
-    unsigned long long *sink;    // [1] where k_finalize_x counts the later overflows of a pair already counted in this call
+    unsigned long long *sink;    // [1] where k_finalize's top-k form counts the later overflows of a pair already counted in this call
 };
 
 // Which lags compete for pair i of a group, and what seeds its running maximum: the host's one statement of that choice.  Host only,
-// never a kernel argument: asx_with_selection (below) turns it into the selection object a kernel template takes (k_inv_cols_r,
-// k_refine_pick); the launchers of the families that still have a kernel per flavour switch on `kind`.
-//   ALL     every lag, seed 0 (k_inv_cols_r<..., AsxSelAll>, k_inv_cols, k_finalize, ...).  The plan's full window is this: it
-//           launches exactly the kernels of a plan that never had one.
-//   WINDOW  the plan's window (asx_plan_set_lag_window), by value, the seed inside it (k_inv_cols_r<..., AsxWin> / k_inv_cols_w;
-//           k_finalize, k_refine_pick and k_pearson_prep take the seed)
-//   ROWS    per-pair windows, which replace the plan's: each pair's row and seed from device memory (<AsxWinRows>, the _p kernels)
-//   TOPK    a top-k pass >= 2, which replaces both: each pair's window, seed and zones from its record (<AsxSelTopk..>, the _x kernels)
+// never a kernel argument: asx_with_selection (below) turns it into the selection object a kernel template takes; launch_prep
+// (pearson_spectral.hip), whose family keeps a kernel per flavour, switches on `kind`.
+//   ALL     every lag, seed 0 (<..., AsxSelAll>; <AsxSelSeed> with seed 0).  The plan's full window is this: it launches exactly the
+//           kernels of a plan that never had one.
+//   WINDOW  the plan's window (asx_plan_set_lag_window), by value, the seed inside it (k_inv_cols_r / k_inv_cols<..., AsxWin>;
+//           k_finalize and k_refine_pick<AsxSelSeed> and k_pearson_prep take the seed)
+//   ROWS    per-pair windows, which replace the plan's: each pair's row and seed from device memory (<AsxWinRows>, k_pearson_prep_p)
+//   TOPK    a top-k pass >= 2, which replaces both: each pair's window, seed and zones from its record (<AsxSelTopk<ZC>>,
+//           <AsxSelTopkSeed>, k_pearson_prep_x)
 struct AsxSearch {
     enum Kind { ALL, WINDOW, ROWS, TOPK } kind;
     int64_t lo, hi;              // the plan's window in lags ...
@@ -270,9 +271,8 @@ struct AsxSearch {
 
 // Pool calls (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev): pair i of a call is source a_i of one pool against sample b_i of another.  Every track of both
 // pools has its forward column pass in the plan's bank (written once per call); k_pool_resolve (rlayout.hip) turns each pair of a launch
-// group into one of these records in the lane's workspace, and the listed kernels (k_rows_rl, k_refine_dots<float, AsxAtList>,
-// k_pearson_partial_l, k_pearson_prep_l, k_pearson_prep_pl, k_pearson_prep_xl) read pair i's slots and inputs from it instead of from
-// i * pitch.  An index
+// group into one of these records in the lane's workspace, and the listed kernels (k_rows_rl; the <..., AsxAtList> instances of
+// k_refine_dots and k_pearson_partial; k_pearson_prep_l, _pl, _xl) read pair i's slots and inputs from it instead of from i * pitch.  An index
 // outside its pool gives slot 0 and ASX_POOL_INVALID: k_rows_rl writes a NaN Q and a zero bound for it -- every inverse tile of every
 // pass leaves at once, whatever the pair's window, zones or seed, so its running maximum stays empty and it can never overflow -- and
 // k_invalid_pairs writes (0, NaN, -4) behind the Pearson kernels (top-k: k_invalid_pairs_k, all k entries, behind the last step).
@@ -295,8 +295,8 @@ struct AsxPoolArgs {
 
 // Where pair i's inputs are, for the exact passes over float or double inputs: src + i * src_pitch and smp + i * smp_pitch (elements;
 // 0 = one track for every pair), or, in a pool call (pl not null, float inputs only), src + pl[i].src_off and smp + pl[i].smp_off
-// (the listed kernels).  Host only: asx_with_inputs turns it into the inputs object a launcher hands on -- to k_refine_dots<TIn, Where>
-// as it is, where the two pitches were; unpacked for the kernels that still take the pitches or the list.
+// (the listed kernels).  Host only: asx_with_inputs turns it into the inputs object a launcher hands on to k_refine_dots and
+// k_pearson_partial<..., Where>; launch_prep unpacks the pitches or the list for k_pearson_prep's forms.
 template <typename TIn> struct AsxInputs {
     const TIn *src, *smp;
     size_t src_pitch, smp_pitch;
@@ -368,7 +368,9 @@ struct AsxPrune {
 // __forceinline__: emitted as a function and called, window_of changed the inverse kernels by thousands of instructions.
 //   k_inv_cols_r masks: Sel::masks, and sel.window_of(pair, N) is what asx_win_has is asked and whose .seed competes signed --
 //   AsxSelAll, AsxWin, AsxWinRows, AsxSelTopk<ZC>, and the pruned pass's AsxSelPrune<FIRST>.
-//   k_refine_pick asks sel.seed_of(pair, N) alone: AsxSelSeed (ALL and WINDOW), AsxWinRows, AsxSelTopkSeed.
+//   k_inv_cols (the packed-sample kernels) the same, with AsxSelTopk<ASX_TOPK_MAX - 1> alone and without the pruned pass.
+//   k_finalize and k_refine_pick ask sel.seed_of(pair, N) alone: AsxSelSeed (ALL and WINDOW), AsxWinRows,
+//   AsxSelTopkSeed (k_finalize reads the record's flags as well, and takes the sink as a trailing argument).
 struct AsxSelAll {
     static constexpr bool masks = false;
     __device__ __forceinline__ AsxWin window_of(size_t, uint32_t) const { return AsxWin{}; }

@@ -538,83 +538,414 @@ __device__ __forceinline__ double wave_sum(double v)
 // k_inv_cols: grid (ntiles, npairs).  Inverse column transforms; the time-domain
 // correlation r[2j] = Re g[j], r[2j+1] = Im g[j] only lives in LDS/registers.
 // ---------------------------------------------------------------------------
-template <int MAXR, class S1 = void, int TC = 0, int NT = 0>
+// Sel (asx_internal.h) says which lags compete.  Sel::masks: only the lags of Z = sel.window_of(pair) compete and Z.seed is the one
+// whose key is signed (the generalisation of the idx < nout test); the fast scans see out-of-window values as NaN (never a maximum
+// there, never a candidate), the general scans skip them; r_out still receives every lag.  One instance per selection, so that the
+// full window runs the <AsxSelAll> instance untouched: AsxWin the plan's window (asx_plan_set_lag_window); AsxWinRows the pair's row
+// in device memory (asx_xcorr_windowed_f32_dev), read once per block in front of the tile loads (an invalid row holds no lag,
+// asx_win_row); AsxSelTopk<ASX_TOPK_MAX - 1> the pass's window, seed and the zones around the pair's earlier entries from its record
+// (passes 2..k of asx_xcorr_topk_f32_dev; one zone capacity: the packed kernels are off the hot path).
+// The body is written here and nowhere else, and in the __global__ itself: a call boundary changes the instruction stream.
+template <int MAXR, class S1, int TC, int NT, class Sel>
 __global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols(const AsxDev *__restrict__ Pp, const float2 *__restrict__ ga,
-                                                                   AsxPeakWs W, float *__restrict__ r_out)
+                                                                   AsxPeakWs W, float *__restrict__ r_out, Sel sel)
 {
-    constexpr bool WIN = false;
-    const AsxWin Z{};
-#include "inv_cols_body.h"
-}
+    constexpr bool WIN = Sel::masks;
+    const auto Z = sel.window_of(blockIdx.y, Pp->N);
+    const AsxDev &PD = *Pp; // the plan lives in device memory: uniform scalar loads, taken once
+    const AsxKP P = asx_kp(PD);
+    __shared__ asx_peak_t red[ASX_FFT_THREADS_MAX / 64];
+    const size_t pair = blockIdx.y;
+    constexpr bool STATIC = !std::is_void<S1>::value;
+    int T = P.T, logT = P.logT, M1 = P.M1;
+    int nthreads = blockDim.x;
+    if constexpr (STATIC) { T = TC; logT = asx_ilog2(TC); M1 = S1::n; nthreads = NT; }
+    const int tile = col_tile_of_block(blockIdx.x, logT);
+    if (tile >= P.ntiles) return; // grid.x is rounded up (col_grid_x)
+    // A digitally silent track (a zero norm, e.g. the zero-filled tail of a short capture): r is exactly zero
+    // everywhere, the reference's scan returns index 0 (src/cross_correlation.c:52-67), which is what a running
+    // maximum left at zero means to k_finalize.  Without this every one of the 2N lags would be a near-tie of the
+    // maximum 0 inside a window of width 0, the lists would overflow and the synchronous entry points would
+    // re-evaluate all of them exactly (seconds at N = 1 440 000).  Block-uniform; r_out (tests) still wants zeros.
+    if (W.bound2[pair] == 0.f && r_out == nullptr) return;
+    const double shift = W.shift ? W.shift[pair] : 0.0; // block-uniform; non-zero only in the second look (second_look, asx_api.hip)
+    const int logH = logT - 1, H = T >> 1, M2 = P.M2;
+    const int c0 = tile * T;
+    const float2 *in = ga + pair * (size_t)P.M;
+    const bool even = (M2 & 1) == 0;
+    float4 *lds4 = reinterpret_cast<float4 *>(asx_lds);
 
-// the lag-window form (asx_plan_set_lag_window): a kernel of its own, so that the full window runs k_inv_cols untouched
-template <int MAXR, class S1 = void, int TC = 0, int NT = 0>
-__global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols_w(const AsxDev *__restrict__ Pp, const float2 *__restrict__ ga,
-                                                                     AsxPeakWs W, float *__restrict__ r_out, AsxWin Z)
-{
-    constexpr bool WIN = true;
-#include "inv_cols_body.h"
-}
+    const int nelem4 = M1 << logH;
+    const LdsLayout Lc = col_layout(T, logT, nthreads);
+    const size_t stamp_block = pair * P.ntiles + tile;
+    (void)stamp_block;
+    ASX_STAMP_AT(2, stamp_block, 0);
+    // The pair's running maximum so far (other tiles publish theirs with atomicMax below) and the width
+    // of the near-maximum window are consumed after the first pass of the scan, at the very end.  Loaded where
+    // they are used, the block waits 2 700 cycles for an L2 round trip there (phase stamps).  Thread 0 fetches
+    // them now and parks them in LDS: its wave waits for them together with its tile loads, and everybody reads
+    // them behind the barriers of the transform.
+    __shared__ asx_peak_t s_run0;
+    __shared__ float s_b2;
+    if (threadIdx.x == 0) {
+        s_run0 = W.pairmax[pair];
+        s_b2 = W.bound2[pair];
+    }
+    TwPre pre;
+    if constexpr (STATIC) pre = tw_prefetch_first<S1, true, true, true>(Lc, P.tw1);
+    else pre = tw_prefetch<true>(PD.st1, PD.st1.nstages - 1, Lc, P.tw1);
+#ifndef ASX_INV_FED
+#define ASX_INV_FED 1 // first inverse stage fed straight from HBM (compile-time schedules, full tiles)
+#endif
+    TwPre pre_last;
+    bool filled = false;
+    if constexpr (STATIC && ASX_INV_FED) {
+        if (even && (c0 + T <= M2)) { // block-uniform: full tile
+            // No fill phase: the first stage to run (innermost, 10 consecutive rows per butterfly) takes its
+            // inputs from HBM -- the thread's loads are all in flight together, as in the fill loop -- and writes
+            // its outputs to LDS: one LDS write + read pass and one barrier less per tile.
+            ASX_STAMP_AT(2, stamp_block, 1);
+            pre_last = lds_fft_static_head_fed<S1, true, true>(lds4, Lc, P.tw1, pre,
+                [&](auto RC, auto &v, int g, int pos0, int q) __attribute__((always_inline)) {
+                    const float2 *col = in + (size_t)pos0 * M2 + c0 + 2 * g;
+                    static_for<0, decltype(RC)::value>([&](auto TT) __attribute__((always_inline)) {
+                        constexpr int t = decltype(TT)::value;
+                        const float4 x = asx_ld16(col + (size_t)(t * q) * M2, ASX_NT & 16);
+                        v[t] = Cx2{ v2f{ x.x, x.z }, v2f{ x.y, x.w } };
+                    });
+                });
+            filled = true;
+        }
+    }
+    if (!filled) {
+    for (int e0 = threadIdx.x; e0 < nelem4; e0 += ASX_COL_LOADS * nthreads) {
+        float4 v[ASX_COL_LOADS];
+        static_for<0, ASX_COL_LOADS>([&](auto I) __attribute__((always_inline)) {
+            const int e = e0 + decltype(I)::value * nthreads;
+            const int cg = e & (H - 1), p1 = e >> logH;
+            const int j2 = c0 + 2 * cg;
+            v[I] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (even && (c0 + T <= M2)) { // block-uniform: full tile
+                if (e < nelem4) v[I] = *reinterpret_cast<const float4 *>(in + (size_t)p1 * M2 + j2);
+            } else if (e < nelem4 && j2 < M2) {
+                const float2 *g = in + (size_t)p1 * M2 + j2;
+                if (even) {
+                    v[I] = *reinterpret_cast<const float4 *>(g);
+                } else {
+                    const float2 a = g[0];
+                    const float2 b = (j2 + 1 < M2) ? g[1] : make_float2(0.f, 0.f);
+                    v[I] = make_float4(a.x, a.y, b.x, b.y);
+                }
+            }
+        });
+        static_for<0, ASX_COL_LOADS>([&](auto I) __attribute__((always_inline)) {
+            const int e = e0 + decltype(I)::value * nthreads;
+            if (e < nelem4) lds4[e] = v[I];
+        });
+    }
+    __syncthreads();
+    ASX_STAMP_AT(2, stamp_block, 1);
+    // every inverse stage but the last: the last one's outputs are consumed from registers below
+    // (r reaches neither HBM nor LDS; LDS keeps that stage's input, so the stage can be run again)
+    if constexpr (STATIC) pre_last = lds_fft_static_head<S1, true, true>(lds4, Lc, P.tw1, pre);
+    else lds_fft<MAXR, true, true>(lds4, PD.st1, Lc, P.tw1, pre); // run-time schedule: the whole transform, r into LDS
+    }
+    ASX_STAMP_AT(2, stamp_block, 2);
 
-// the per-pair form (asx_xcorr_windowed_f32_dev): the window is the pair's row in device memory, read once per block in front of
-// the tile loads; an invalid row holds no lag (asx_win_row)
-template <int MAXR, class S1 = void, int TC = 0, int NT = 0>
-__global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols_wp(const AsxDev *__restrict__ Pp, const float2 *__restrict__ ga,
-                                                                      AsxPeakWs W, float *__restrict__ r_out, AsxWinRows R)
-{
-    constexpr bool WIN = true;
-    AsxWin Z;
-    (void)asx_win_row(R, blockIdx.y, Pp->N, Z);
-#include "inv_cols_body.h"
-}
+    // ANY earlier value of the running maximum is a lower bound of the final one, so a stale read merely admits
+    // more candidates (k_finalize filters them against the final maximum).
+    const asx_peak_t run0 = s_run0;
+    const float b2 = s_b2;
+    const uint32_t seed = WIN ? Z.seed : 0u;
+    // the seed's tile (lag 0's without a window) takes the general form: idx >> 1 = j1 M2 + column
+    auto seed_tile = [&]() __attribute__((always_inline)) { return (int)(((seed >> 1) % (uint32_t)M2) / (uint32_t)T); };
+    auto inw = [&](uint32_t idx) __attribute__((always_inline)) { return !WIN || asx_win_has(Z, idx); };
+    // fast scans: out-of-window lags as NaN (a slot is four consecutive lags from i0)
+    auto mask4 = [&](float4 g, uint32_t i0) __attribute__((always_inline)) {
+        if constexpr (WIN) {
+            if (!inw(i0)) g.x = NAN;
+            if (!inw(i0 + 1)) g.y = NAN;
+            if (!inw(i0 + 2)) g.z = NAN;
+            if (!inw(i0 + 3)) g.w = NAN;
+        }
+        return g;
+    };
+    if constexpr (!STATIC) {
+        // Run-time schedules (lengths outside the reference's six): r lies in LDS and is scanned there.  The
+        // scan from the last stage's registers below, instantiated inside the switch over eleven radix bodies,
+        // pushed these kernels into scratch (k_inv_cols 0.77 ms against 0.43 ms for the compiled-in schedule).
+        const bool fastg = even && (c0 + T <= M2) && (P.nout == P.F) && (WIN ? tile != seed_tile() : tile != 0) && (r_out == nullptr) && shift == 0.0;
+        auto examine_slot = [&](int e, float4 g, float thr) {
+            const int cg = e & (H - 1), j1 = e >> logH;
+            const int j2 = c0 + 2 * cg;
+            if (j2 >= M2) return;
+            const uint32_t i0 = 2u * ((uint32_t)j1 * (uint32_t)M2 + (uint32_t)j2);
+            const float val[4] = { g.x, g.y, g.z, g.w }; // slot = {re0, im0, re1, im1}: four consecutive lags
+#pragma unroll
+            for (int h = 0; h < 4; h++) {
+                const uint32_t idx = i0 + h;
+                if ((WIN ? asx_win_has(Z, idx) : idx < P.nout) && j2 + (h >> 1) < M2) {
+                    const float key = shift == 0.0 ? peak_key_of(val[h], idx, seed) : peak_key_shifted(val[h], idx, shift, seed);
+                    if (key >= thr) cand_append(W, pair, idx, key);
+                }
+            }
+        };
+        if (fastg) {
+            // pass 1: per thread the largest and second largest slot maximum; a thread meets its slots in
+            // increasing lag order, so a strict '>' keeps the earliest of equal maxima
+            float best_m = -INFINITY, second_m = -INFINITY;
+            int best_e = threadIdx.x;
+            // (the slot's first lag, for the window's mask)
+            auto slot_i0 = [&](int e) { return 2u * ((uint32_t)(e >> logH) * (uint32_t)M2 + (uint32_t)(c0 + 2 * (e & (H - 1)))); };
+            for (int e = threadIdx.x; e < nelem4; e += nthreads) {
+                const float4 g = mask4(lds4[e], WIN ? slot_i0(e) : 0u);
+                const float m = fmaxf(fmaxf(fabsf(g.x), fabsf(g.y)), fmaxf(fabsf(g.z), fabsf(g.w))); // NaNs drop out
+                if (m > best_m) { second_m = best_m; best_m = m; best_e = e; }
+                else if (m > second_m) second_m = m;
+            }
+            const float4 gb = mask4(lds4[best_e], WIN ? slot_i0(best_e) : 0u);
+            uint32_t my_idx;
+            {
+                const int cg = best_e & (H - 1), j1 = best_e >> logH;
+                const uint32_t i0 = 2u * ((uint32_t)j1 * (uint32_t)M2 + (uint32_t)(c0 + 2 * cg));
+                const uint32_t h = fabsf(gb.x) == best_m ? 0u : fabsf(gb.y) == best_m ? 1u : fabsf(gb.z) == best_m ? 2u : 3u;
+                my_idx = i0 + h;
+            }
+            const float wmax = wave_max_nonneg(fmaxf(best_m, 0.f));
+            unsigned long long holders = __ballot(best_m == wmax);
+            uint32_t widx = 0xFFFFFFFFu;
+            while (holders) {
+                const int l = __ffsll((long long)holders) - 1;
+                const uint32_t li = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, l);
+                widx = li < widx ? li : widx;
+                holders &= holders - 1;
+            }
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = widx == 0xFFFFFFFFu ? 0 : peak_pack_key(wmax, widx);
+            __syncthreads();
+            asx_peak_t tb = red[0];
+            for (int w = 1; w < (int)((nthreads + 63) >> 6); w++) tb = peak_max(tb, red[w]);
+            if (threadIdx.x == 0) atomicMax(&W.pairmax[pair], tb);
+            const float thr = near_max_threshold(peak_key(peak_max(tb, run0)), b2);
+            if (best_m >= thr) {
+                if (second_m >= thr) {
+                    for (int e = threadIdx.x; e < nelem4; e += nthreads) {
+                        const float4 g = mask4(lds4[e], WIN ? slot_i0(e) : 0u);
+                        const float m = fmaxf(fmaxf(fabsf(g.x), fabsf(g.y)), fmaxf(fabsf(g.z), fabsf(g.w)));
+                        if (m >= thr) examine_slot(e, g, thr);
+                    }
+                } else {
+                    examine_slot(best_e, gb, thr);
+                }
+            }
+        } else {
+            float best_key = -INFINITY;
+            uint32_t best_idx = 0xFFFFFFFFu;
+            for (int e = threadIdx.x; e < nelem4; e += nthreads) {
+                const int cg = e & (H - 1), j1 = e >> logH;
+                const int j2 = c0 + 2 * cg;
+                if (j2 < M2) {
+                    const uint32_t i0 = 2u * ((uint32_t)j1 * (uint32_t)M2 + (uint32_t)j2);
+                    const float4 g = lds4[e];
+                    const float val[4] = { g.x, g.y, g.z, g.w };
+#pragma unroll
+                    for (int h = 0; h < 4; h++) {
+                        const uint32_t idx = i0 + h;
+                        if (idx < P.nout && j2 + (h >> 1) < M2) {
+                            const float key = shift == 0.0 ? peak_key_of(val[h], idx, seed) : peak_key_shifted(val[h], idx, shift, seed);
+                            if (inw(idx) && (key > best_key || (key == best_key && idx < best_idx) || best_idx == 0xFFFFFFFFu)) { best_key = key; best_idx = idx; }
+                            if (r_out) r_out[pair * (size_t)P.nout + idx] = val[h];
+                        }
+                    }
+                }
+            }
+            asx_peak_t best = best_idx == 0xFFFFFFFFu ? 0 : peak_pack_key(best_key, best_idx);
+            best = block_peak_max(best, red);
+            if (threadIdx.x == 0) { atomicMax(&W.pairmax[pair], best); red[0] = best; }
+            __syncthreads();
+            const float thr = near_max_threshold(peak_key(peak_max(red[0], run0)), b2);
+            for (int e = threadIdx.x; e < nelem4; e += nthreads) examine_slot(e, lds4[e], thr);
+        }
+        ASX_STAMP_AT(2, stamp_block, 3);
+    } else {
+    auto last_stage = [&](auto &&sink) __attribute__((always_inline)) {
+        lds_last_stage_static<S1, true, true>(lds4, Lc, P.tw1, pre_last, sink);
+    };
 
-// the top-k form (asx_xcorr_topk_f32_dev, passes 2..k): the pass's window, seed and the zones around the pair's earlier entries, from
-// its record (AsxTopkPair, written by k_topk_step); asx_win_has(AsxWinX) leaves the zones out
-template <int MAXR, class S1 = void, int TC = 0, int NT = 0>
-__global__ __launch_bounds__(ASX_FFT_THREADS_MAX, 4) void k_inv_cols_wx(const AsxDev *__restrict__ Pp, const float2 *__restrict__ ga,
-                                                                      AsxPeakWs W, float *__restrict__ r_out,
-                                                                      const AsxTopkPair *__restrict__ X)
-{
-    constexpr bool WIN = true;
-    const AsxWinX<ASX_TOPK_MAX - 1> Z = asx_win_x<ASX_TOPK_MAX - 1>(X, blockIdx.y); // (one zone capacity: the packed kernels are off the hot path)
-#include "inv_cols_body.h"
+    // Output T of a butterfly is row j1 = pos0 + T*q of column pair g: four consecutive lags
+    // {re0, im0, re1, im1} from i0 = 2*(j1*M2 + c0 + 2g).
+    // Peak search (src/cross_correlation.c:52-67): largest key, smallest lag among equal keys.
+    // Fast path (block-uniform): the tile is full, every lag counts, lag 0 (the signed one) is
+    // not in it and r is not being dumped -> one packed maximum per slot, indices resolved at the end.
+    const bool fast = even && (c0 + T <= M2) && (P.nout == P.F) && (WIN ? tile != seed_tile() : tile != 0) && (r_out == nullptr) && shift == 0.0;
+    // second look (rare, one instantiation for both paths): the thread runs its last stage again and
+    // appends every valid lag whose key is inside the window
+    auto examine_again = [&](float thr) __attribute__((always_inline)) {
+        last_stage([&](auto RC, auto &v, int g, int pos0, int q) __attribute__((always_inline)) {
+            const int j2 = c0 + 2 * g;
+            if (j2 >= M2) return;
+            static_for<0, decltype(RC)::value>([&](auto TT) __attribute__((always_inline)) {
+                constexpr int t = decltype(TT)::value;
+                const float val[4] = { v[t].re.x, v[t].im.x, v[t].re.y, v[t].im.y };
+                const uint32_t i0 = 2u * ((uint32_t)(pos0 + t * q) * (uint32_t)M2 + (uint32_t)j2);
+#pragma unroll
+                for (int h = 0; h < 4; h++) {
+                    const uint32_t idx = i0 + h;
+                    if ((WIN ? asx_win_has(Z, idx) : idx < P.nout) && j2 + (h >> 1) < M2) {
+                        const float key = shift == 0.0 ? peak_key_of(val[h], idx, seed) : peak_key_shifted(val[h], idx, shift, seed);
+                        if (key >= thr) cand_append(W, pair, idx, key);
+                    }
+                }
+            });
+        });
+    };
+    float thr_again = 0.f;
+    bool again = false;
+    if (fast) {
+        // pass 1: per thread the largest and second largest slot maximum
+        float best_m = -INFINITY, second_m = -INFINITY;
+        uint32_t best_i0 = 0xFFFFFFFFu;
+        float4 gb = make_float4(0.f, 0.f, 0.f, 0.f);
+        last_stage([&](auto RC, auto &v, int g, int pos0, int q) __attribute__((always_inline)) {
+            static_for<0, decltype(RC)::value>([&](auto TT) __attribute__((always_inline)) {
+                constexpr int t = decltype(TT)::value;
+                const float4 s4 = mask4(make_float4(v[t].re.x, v[t].im.x, v[t].re.y, v[t].im.y),
+                                        WIN ? 2u * ((uint32_t)(pos0 + t * q) * (uint32_t)M2 + (uint32_t)(c0 + 2 * g)) : 0u);
+                const float m = fmaxf(fmaxf(fabsf(s4.x), fabsf(s4.y)), fmaxf(fabsf(s4.z), fabsf(s4.w))); // NaNs drop out
+                const uint32_t i0 = 2u * ((uint32_t)(pos0 + t * q) * (uint32_t)M2 + (uint32_t)(c0 + 2 * g));
+                if (m > best_m || (m == best_m && i0 < best_i0)) { second_m = best_m; best_m = m; gb = s4; best_i0 = i0; }
+                else if (m > second_m) second_m = m;
+            });
+        });
+        // lag order inside a slot = its memory order {re0, im0, re1, im1}
+        const uint32_t hh = fabsf(gb.x) == best_m ? 0u : fabsf(gb.y) == best_m ? 1u : fabsf(gb.z) == best_m ? 2u : 3u;
+        const uint32_t my_idx = best_i0 + hh;
+        // wave maximum in registers, smallest lag among the lanes that hold it, one entry per wave
+        ASX_STAMP_AT(2, stamp_block, 4);
+        const float wmax = wave_max_nonneg(fmaxf(best_m, 0.f));
+        unsigned long long holders = __ballot(best_m == wmax);
+        uint32_t widx = 0xFFFFFFFFu;
+        while (holders) {
+            const int l = __ffsll((long long)holders) - 1;
+            const uint32_t li = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, l);
+            widx = li < widx ? li : widx;
+            holders &= holders - 1;
+        }
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = widx == 0xFFFFFFFFu ? 0 : peak_pack_key(wmax, widx);
+        __syncthreads();
+        // every thread folds the wave entries itself: no second barrier to broadcast the result
+        asx_peak_t tb = red[0];
+        for (int w = 1; w < (int)((nthreads + 63) >> 6); w++) tb = peak_max(tb, red[w]);
+        if (threadIdx.x == 0) atomicMax(&W.pairmax[pair], tb);
+        // Second look: lags within the float32 error window of the largest key known so far.  Almost every
+        // thread is below the threshold; the one that holds the maximum usually has no second slot near
+        // it and examines just that slot; a thread with more runs its last stage again.
+        ASX_STAMP_AT(2, stamp_block, 5);
+        const float thr = near_max_threshold(peak_key(peak_max(tb, run0)), b2);
+        thr_again = thr;
+        if (best_m >= thr) {
+            if (second_m >= thr) {
+                again = true;
+            } else {
+                const float val[4] = { gb.x, gb.y, gb.z, gb.w };
+#pragma unroll
+                for (int h = 0; h < 4; h++)
+                    if (fabsf(val[h]) >= thr) cand_append(W, pair, best_i0 + h, fabsf(val[h]));
+            }
+        }
+    } else {
+        // general form: first tile (lag 0 competes signed), ragged or embedded tiles, r dumped for tests
+        float best_key = -INFINITY;
+        uint32_t best_idx = 0xFFFFFFFFu;
+        last_stage([&](auto RC, auto &v, int g, int pos0, int q) __attribute__((always_inline)) {
+            const int j2 = c0 + 2 * g;
+            if (j2 >= M2) return;
+            static_for<0, decltype(RC)::value>([&](auto TT) __attribute__((always_inline)) {
+                constexpr int t = decltype(TT)::value;
+                const float val[4] = { v[t].re.x, v[t].im.x, v[t].re.y, v[t].im.y };
+                const uint32_t i0 = 2u * ((uint32_t)(pos0 + t * q) * (uint32_t)M2 + (uint32_t)j2);
+#pragma unroll
+                for (int h = 0; h < 4; h++) {
+                    const uint32_t idx = i0 + h;
+                    if (idx < P.nout && j2 + (h >> 1) < M2) {
+                        const float key = shift == 0.0 ? peak_key_of(val[h], idx, seed) : peak_key_shifted(val[h], idx, shift, seed);
+                        if (inw(idx) && (key > best_key || (key == best_key && idx < best_idx) || best_idx == 0xFFFFFFFFu)) { best_key = key; best_idx = idx; }
+                        if (r_out) r_out[pair * (size_t)P.nout + idx] = val[h];
+                    }
+                }
+            });
+        });
+        asx_peak_t best = best_idx == 0xFFFFFFFFu ? 0 : peak_pack_key(best_key, best_idx);
+        best = block_peak_max(best, red);
+        if (threadIdx.x == 0) { atomicMax(&W.pairmax[pair], best); red[0] = best; }
+        __syncthreads();
+        const float thr = near_max_threshold(peak_key(peak_max(red[0], run0)), b2);
+        again = best_key >= thr;
+        thr_again = thr;
+    }
+    if (again) examine_again(thr_again);
+    ASX_STAMP_AT(2, stamp_block, 3);
+    } // compiled-in schedules
 }
 
 #if ASX_HAS_PART(64)
 // ---------------------------------------------------------------------------
 // k_finalize: grid (npairs).  Reduce tile partials, wrap the lag, pick segments.
 // ---------------------------------------------------------------------------
-// seed: the lag window's first index (AsxWin; 0 without a window) -- what a running maximum that nothing reached stands for
-__global__ __launch_bounds__(ASX_THREADS) void k_finalize(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
-                                                           uint32_t pair_base, uint32_t seed)
+// sel.seed_of(pair): the index a running maximum that nothing reached stands for -- AsxSelSeed: the lag window's first index (0
+// without a window); AsxWinRows (asx_xcorr_windowed_f32_dev): the pair's own, from its row (0 for an invalid row, which lists nothing:
+// it never overflows, and k_invalid_rows overwrites its results); AsxSelTopkSeed (top-k passes 2..k): the pass's, from the pair's record.
+// Sink: nothing -- or, in the top-k form, unsigned long long: a pair that already overflowed in an earlier pass of the call was
+// counted and listed then, its later overflows go to `sink` (asx_plan_peak_overflows counts a pair once per call).
+template <class Sel, class... Sink>
+__global__ __launch_bounds__(ASX_THREADS) void k_finalize(const AsxDev *__restrict__ Pp, AsxPeakWs W0, AsxSeg *__restrict__ seg,
+                                                           uint32_t pair_base, Sel sel, Sink *__restrict__... sink)
 {
-#include "finalize_body.h"
-}
-
-// the per-pair form (asx_xcorr_windowed_f32_dev): the seed is the pair's own, from its row (0 for an invalid row, which lists nothing:
-// it never overflows, and k_invalid_rows overwrites its results)
-__global__ __launch_bounds__(ASX_THREADS) void k_finalize_p(const AsxDev *__restrict__ Pp, AsxPeakWs W, AsxSeg *__restrict__ seg,
-                                                             uint32_t pair_base, AsxWinRows R)
-{
-    AsxWin Z;
-    (void)asx_win_row(R, blockIdx.x, Pp->N, Z);
-    const uint32_t seed = Z.seed;
-#include "finalize_body.h"
-}
-
-// the top-k form (passes 2..k): the seed is the pass's, from the pair's record.  A pair that already overflowed in an earlier pass of
-// the call was counted and listed then: its later overflows go to a sink (asx_plan_peak_overflows counts a pair once per call)
-__global__ __launch_bounds__(ASX_THREADS) void k_finalize_x(const AsxDev *__restrict__ Pp, AsxPeakWs W0, AsxSeg *__restrict__ seg,
-                                                             uint32_t pair_base, const AsxTopkPair *__restrict__ X,
-                                                             unsigned long long *__restrict__ sink)
-{
-    const uint32_t seed = X[blockIdx.x].z.seed;
+    static_assert(sizeof...(Sink) <= 1, "the sink or nothing");
+    const uint32_t seed = sel.seed_of(blockIdx.x, Pp->N);
     AsxPeakWs W = W0;
-    if (X[blockIdx.x].flags & ASX_TK_INEXACT) {
-        W.overflows = sink;
-        W.over_list = nullptr;
+    if constexpr (sizeof...(Sink) == 1) {
+        if (sel.X[blockIdx.x].flags & ASX_TK_INEXACT) {
+            W.overflows = (sink, ...);
+            W.over_list = nullptr;
+        }
     }
-#include "finalize_body.h"
+    const uint32_t N = Pp->N;
+    __shared__ uint32_t nsel;
+    const size_t pair = blockIdx.x;
+    const asx_peak_t best = W.pairmax[pair];        // float32 maximum, smallest lag among equal keys
+    const uint32_t ntot = W.cand_n[pair];
+    const uint32_t n = ntot < W.cap ? ntot : W.cap;
+    // the tiles collected against the running maximum; keep what is near the FINAL maximum
+    const float thr = near_max_threshold(peak_key(best), W.bound2[pair]);
+    if (threadIdx.x == 0) nsel = 0;
+    __syncthreads();
+    const AsxCand *c = W.cand + pair * (size_t)W.cap;
+    uint32_t *out = W.refine_idx + pair * (size_t)W.cap;
+    for (uint32_t i = threadIdx.x; i < n; i += ASX_THREADS) {
+        const AsxCand e = c[i];
+        if (e.key >= thr) out[atomicAdd(&nsel, 1u)] = e.idx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        AsxSeg sg = make_seg(best ? peak_index(best) : seed, N);
+        // One candidate: the float32 argmax is unambiguous.  More than the list holds (a signal periodic in
+        // more than `cap` lags, an offset of hundreds of deviations in both tracks): the float32 argmax is only a
+        // placeholder.  The pair is MARKED (its ret becomes ASX_RET_INEXACT in k_pearson_final), counted
+        // (asx_plan_peak_overflows) and put on the list the entry points read to take the second look
+        // (asx_api.hip: resolve_overflows): the reference's scan has no candidate limit (src/cross_correlation.c:52-67).
+        const bool over = ntot > W.cap;
+        if (over) sg.flags = ASX_SEG_INEXACT;
+        seg[pair] = sg;
+        W.refine_n[pair] = (!over && nsel >= 2u) ? nsel : 0u;
+        if (over) {
+            atomicAdd(W.overflows, 1ull);
+            if (W.over_list) {
+                const uint32_t slot = atomicAdd(W.over_n, 1u);
+                if (slot < W.over_cap) W.over_list[slot] = pair_base + (uint32_t)pair;
+                if (W.over_host) (void)__hip_atomic_fetch_add(W.over_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
 }
 
 // grid (npairs / ASX_THREADS): behind the Pearson kernels of pass j of a top-k group (asx_xcorr_topk_f32_dev).  Pass j's result of
@@ -884,28 +1215,124 @@ __global__ __launch_bounds__(ASX_THREADS) void k_refine_pick(const AsxDev *__res
 #ifndef ASX_PEARSON_DEEP
 #define ASX_PEARSON_DEEP 4
 #endif
-template <typename TIn, bool SPEC>
-__global__ __launch_bounds__(ASX_THREADS) void k_pearson_partial(const TIn *__restrict__ src,
-                                                                  const TIn *__restrict__ smp,
-                                                                  size_t src_pitch, size_t smp_pitch,
-                                                                  uint32_t basis_len,
-                                                                  const AsxSeg *__restrict__ seg,
+// Where (asx_internal.h, Inputs): pair i's inputs at src + at.src_off(i), smp + at.smp_off(i) -- AsxAtPitch, or AsxAtList in a pool
+// call (asx_xcorr_pool_f32_dev, float inputs only)
+template <typename TIn, bool SPEC, class Where>
+__global__ __launch_bounds__(ASX_THREADS) void k_pearson_partial(const TIn *__restrict__ src, const TIn *__restrict__ smp, Where at,
+                                                                  uint32_t basis_len, const AsxSeg *__restrict__ seg,
                                                                   double *__restrict__ psums, AsxSpecWs V)
 {
-#include "pearson_partial_body.h"
-}
-
-// the listed form (asx_xcorr_pool_f32_dev): pair i's inputs at src + PL[i].src_off, smp + PL[i].smp_off
-template <bool SPEC>
-__global__ __launch_bounds__(ASX_THREADS) void k_pearson_partial_l(const float *__restrict__ src, const float *__restrict__ smp,
-                                                                    const AsxPoolPair *__restrict__ PL, uint32_t basis_len,
-                                                                    const AsxSeg *__restrict__ seg, double *__restrict__ psums,
-                                                                    AsxSpecWs V)
-{
-    typedef float TIn;
-#define ASX_SRC_OF(pair) PL[pair].src_off
-#define ASX_SMP_OF(pair) PL[pair].smp_off
-#include "pearson_partial_body.h"
+    __shared__ double red[6][ASX_THREADS / 64];
+    const size_t pair = blockIdx.y;
+    AsxSeg s = seg[pair];
+    // SPEC (the spectral Pearson form): what this pair still needs read -- nothing, its wrap-around part, or its segment -- follows from
+    // the sums k_pearson_prep left; every block works that out for itself (pair-uniform: scalar loads and arithmetic)
+    // Block 0 also RECORDS the mode (the spare header slot): k_pearson_final_spec, in another translation unit, reads it instead of
+    // deciding again -- with -ffp-contract=fast two inlining contexts may round `bound <= tol` differently at the threshold, and a final
+    // kernel that disagreed with the work list would read partial sums written for another mode.  One writer, a later
+    // kernel reads: no fence.
+    if constexpr (SPEC) {
+        const AsxSpecPick d = asx_spec_pick(s, V.part + pair * (size_t)(V.nb * 4), V.nb, V.hdr + pair * ASX_SPEC_HDR, V.tol, V.N);
+        s = d.work;
+        if (blockIdx.x == 0 && threadIdx.x == 0) V.hdr[pair * ASX_SPEC_HDR + 3] = (double)d.mode;
+    }
+    // gridDim.x partial blocks per pair (asx_pearson_blocks: by the basis length alone); the final kernel merges
+    // exactly gridDim.x entries
+    const uint32_t chunk = (basis_len + gridDim.x - 1) / gridDim.x;
+    const uint64_t lo = (uint64_t)blockIdx.x * chunk;
+    uint64_t hi = lo + chunk;
+    if (hi > s.len) hi = s.len;
+    if (lo >= s.len) {
+        // nothing of the segment falls to this block (block-uniform): an empty record (pstat_merge skips n == 0) -- the whole
+        // launch for a pair the spectral form has settled (pearson_spectral.hip), the tail of a short segment otherwise
+        if (threadIdx.x == 0) psums[(pair * gridDim.x + blockIdx.x) * 6] = 0.0;
+        return;
+    }
+    const TIn *x = src + at.src_off(pair) + s.src_off;
+    const TIn *y = smp + at.smp_off(pair) + s.smp_off;
+    uint64_t i = lo + 4u * threadIdx.x;
+    double px = 0, py = 0; // pivots: the first element this thread meets
+#if ASX_PEARSON_DEEP
+    // (taken from the first 16-byte load below when the thread has one: a scalar load and the wait for it in front of the loop otherwise)
+    if (i < hi && !(i + 3 < hi)) { px = (double)x[i]; py = (double)y[i]; }
+#else
+    if (i < hi) { px = (double)x[i]; py = (double)y[i]; }
+#endif
+    double sx = 0, sy = 0, sxy = 0, sxx = 0, syy = 0;
+    uint32_t cnt = 0;
+    auto add = [&](double a, double b) {
+        const double da = a - px, db = b - py;
+        sx += da;
+        sy += db;
+        sxy += da * db;
+        sxx += da * da;
+        syy += db * db;
+        cnt++;
+    };
+    // four consecutive elements per lane and step: 16-byte loads (the segments start at any element,
+    // so the vector type only promises element alignment), then the few elements that are left
+    typedef TIn vec4u __attribute__((ext_vector_type(4), aligned(sizeof(TIn))));
+    auto ld4 = [&](const TIn *p) __attribute__((always_inline)) {
+        return (ASX_NT & 4) ? __builtin_nontemporal_load(reinterpret_cast<const vec4u *>(p)) : *reinterpret_cast<const vec4u *>(p);
+    };
+#if ASX_PEARSON_DEEP
+    // ASX_PEARSON_DEEP steps at a time: their 2 * ASX_PEARSON_DEEP loads in flight together, then the same additions in the same order (the
+    // loop used to wait for each step's two loads before it issued the next step's: 16 memory round trips per block, one after the other)
+    {
+        bool first = i + 3 < hi;
+        constexpr uint32_t STEP = 4u * ASX_THREADS;
+        for (; i + 3 + (uint64_t)(ASX_PEARSON_DEEP - 1) * STEP < hi; i += (uint64_t)ASX_PEARSON_DEEP * STEP) {
+            vec4u a[ASX_PEARSON_DEEP], b[ASX_PEARSON_DEEP];
+#pragma unroll
+            for (int u = 0; u < ASX_PEARSON_DEEP; u++) { a[u] = ld4(x + i + (uint64_t)u * STEP); b[u] = ld4(y + i + (uint64_t)u * STEP); }
+            if (first) { px = (double)a[0].x; py = (double)b[0].x; first = false; }
+#pragma unroll
+            for (int u = 0; u < ASX_PEARSON_DEEP; u++) {
+                add((double)a[u].x, (double)b[u].x);
+                add((double)a[u].y, (double)b[u].y);
+                add((double)a[u].z, (double)b[u].z);
+                add((double)a[u].w, (double)b[u].w);
+            }
+        }
+        if (first) { px = (double)x[i]; py = (double)y[i]; } // fewer than ASX_PEARSON_DEEP whole steps: the step loop below meets it first
+    }
+#endif
+    for (; i + 3 < hi; i += 4u * ASX_THREADS) {
+        const vec4u a = (ASX_NT & 4) ? __builtin_nontemporal_load(reinterpret_cast<const vec4u *>(x + i)) : *reinterpret_cast<const vec4u *>(x + i);
+        const vec4u b = (ASX_NT & 4) ? __builtin_nontemporal_load(reinterpret_cast<const vec4u *>(y + i)) : *reinterpret_cast<const vec4u *>(y + i);
+        add((double)a.x, (double)b.x);
+        add((double)a.y, (double)b.y);
+        add((double)a.z, (double)b.z);
+        add((double)a.w, (double)b.w);
+    }
+    for (; i < hi; i++) add((double)x[i], (double)y[i]); // only the lane that holds the ragged end
+    PStat v;
+    v.n = (double)cnt;
+    v.mx = v.my = v.mxx = v.myy = v.cxy = 0.0;
+    if (cnt) {
+        v.mx = px + sx / v.n;
+        v.my = py + sy / v.n;
+        v.mxx = sxx - sx * sx / v.n;
+        v.myy = syy - sy * sy / v.n;
+        v.cxy = sxy - sx * sy / v.n;
+    }
+    v = pstat_wave_merge(v);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[0][wave] = v.n; red[1][wave] = v.mx; red[2][wave] = v.my;
+        red[3][wave] = v.mxx; red[4][wave] = v.myy; red[5][wave] = v.cxy;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < ASX_THREADS / 64; w++) {
+            PStat o;
+            o.n = red[0][w]; o.mx = red[1][w]; o.my = red[2][w];
+            o.mxx = red[3][w]; o.myy = red[4][w]; o.cxy = red[5][w];
+            v = pstat_merge(v, o);
+        }
+        double *out = psums + (pair * gridDim.x + blockIdx.x) * 6;
+        out[0] = v.n; out[1] = v.mx; out[2] = v.my; out[3] = v.mxx; out[4] = v.myy; out[5] = v.cxy;
+    }
 }
 
 // grid (npairs), one wave per pair: lane b owns the partial blocks b, b + 64, ... (merged in that order: a fixed tree for a
@@ -1210,19 +1637,16 @@ void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *z
 #endif
 #undef ASX_ROWS_LAUNCH
 
-// one flavour of the inverse column kernel, with the flavour's extra argument (none: every lag competes)
-template <class K, class... X>
-static void launch_inv(K kernel, const AsxDev &P, dim3 grid, hipStream_t s, const float2 *ga, const AsxPeakWs &W, float *r_out, X... extra)
+// one instance of the inverse column kernel with its selection
+template <class K, class Sel>
+static void launch_inv(K kernel, const AsxDev &P, dim3 grid, hipStream_t s, const float2 *ga, const AsxPeakWs &W, float *r_out, Sel sel)
 {
     allow_big_lds((const void *)kernel, lds_bytes_cols(P));
-    hipLaunchKernelGGL(kernel, grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, extra...);
+    hipLaunchKernelGGL(kernel, grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, sel);
 }
-// (one zone capacity in k_inv_cols_wx: q.tk_zones is not asked)
+// (one zone capacity in the packed kernels' top-k form, whatever q.tk_zones says)
 #define ASX_INV_LAUNCH(...) \
-    do { if (q.kind == AsxSearch::TOPK) launch_inv(k_inv_cols_wx<__VA_ARGS__>, P, grid, s, ga, W, r_out, q.tk); \
-         else if (q.kind == AsxSearch::ROWS) launch_inv(k_inv_cols_wp<__VA_ARGS__>, P, grid, s, ga, W, r_out, q.rows); \
-         else if (q.kind == AsxSearch::WINDOW) launch_inv(k_inv_cols_w<__VA_ARGS__>, P, grid, s, ga, W, r_out, q.win); \
-         else launch_inv(k_inv_cols<__VA_ARGS__>, P, grid, s, ga, W, r_out); } while (0)
+    asx_with_selection<ASX_TOPK_MAX - 1>(q, [&](auto sel) { launch_inv(k_inv_cols<__VA_ARGS__, decltype(sel)>, P, grid, s, ga, W, r_out, sel); })
 #if ASX_HAS_PART(16)
 bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
                                 hipStream_t s, const AsxSearch &q)
@@ -1241,7 +1665,7 @@ void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPea
 {
     dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
     const int mr = max_radix(P.st1);
-    if (mr <= 10) ASX_INV_LAUNCH(10); else if (mr <= 12) ASX_INV_LAUNCH(12); else ASX_INV_LAUNCH(16);
+    if (mr <= 10) ASX_INV_LAUNCH(10, void, 0, 0); else if (mr <= 12) ASX_INV_LAUNCH(12, void, 0, 0); else ASX_INV_LAUNCH(16, void, 0, 0);
 }
 #endif
 #undef ASX_INV_LAUNCH
@@ -1312,9 +1736,12 @@ void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int n
                          const AsxSearch &q)
 {
     const dim3 grid(npairs), block(ASX_THREADS);
-    if (q.kind == AsxSearch::TOPK) hipLaunchKernelGGL(k_finalize_x, grid, block, 0, s, P.self_dev, W, seg, pair_base, q.tk, q.tk_sink);
-    else if (q.kind == AsxSearch::ROWS) hipLaunchKernelGGL(k_finalize_p, grid, block, 0, s, P.self_dev, W, seg, pair_base, q.rows);
-    else hipLaunchKernelGGL(k_finalize, grid, block, 0, s, P.self_dev, W, seg, pair_base, q.seed());
+    asx_with_selection(q, [&](auto sel) {
+        if constexpr (std::is_same<decltype(sel), AsxSelTopkSeed>::value)
+            hipLaunchKernelGGL((k_finalize<AsxSelTopkSeed, unsigned long long>), grid, block, 0, s, P.self_dev, W, seg, pair_base, sel, q.tk_sink);
+        else
+            hipLaunchKernelGGL(k_finalize<decltype(sel)>, grid, block, 0, s, P.self_dev, W, seg, pair_base, sel);
+    });
 }
 
 void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, const AsxSearch &call, uint32_t N, int npairs, int j,
@@ -1371,18 +1798,14 @@ unsigned asx_pearson_blocks(uint32_t basis_len)
     return nb;
 }
 
-// k_pearson_partial / k_pearson_partial_l: SPEC = false with an empty S (the direct form), true with the spectral form's
+// k_pearson_partial: SPEC = false with an empty S (the direct form), true with the spectral form's
 template <typename TIn, bool SPEC>
 static void launch_pearson_partial(const AsxInputs<TIn> &in, uint32_t basis_len, const AsxSeg *seg, const AsxSpecWs &S, double *psums,
                                    int npairs, hipStream_t s)
 {
     const dim3 grid(asx_pearson_blocks(basis_len), npairs), block(ASX_THREADS);
     asx_with_inputs(in, [&](auto at) {
-        if constexpr (std::is_same<decltype(at), AsxAtList>::value)
-            hipLaunchKernelGGL(k_pearson_partial_l<SPEC>, grid, block, 0, s, in.src, in.smp, at.pl, basis_len, seg, psums, S);
-        else
-            hipLaunchKernelGGL((k_pearson_partial<TIn, SPEC>), grid, block, 0, s, in.src, in.smp, at.src_pitch, at.smp_pitch, basis_len,
-                               seg, psums, S);
+        hipLaunchKernelGGL((k_pearson_partial<TIn, SPEC, decltype(at)>), grid, block, 0, s, in.src, in.smp, at, basis_len, seg, psums, S);
     });
 }
 

@@ -74,8 +74,9 @@ def test_k_rows_headline_kernel_keeps_four_blocks_per_cu(kernels):
 
 def test_column_kernels_headline_keep_two_blocks_per_cu(kernels):
     names = {demangled(k): v for k, v in kernels.items()}
-    for prefix in ("void k_fwd_cols<12, Sched<1200, 12, 10, 10>, 8, 512>", "void k_inv_cols<12, Sched<1200, 12, 10, 10>, 8, 512>"):
-        (n, r), = [(n, r) for n, r in names.items() if n.startswith(prefix)]
+    (fwd, fr), = [(n, r) for n, r in names.items() if n.startswith("void k_fwd_cols<12, Sched<1200, 12, 10, 10>, 8, 512>")]
+    (_, ir), = kernel_forms(names, "k_inv_cols", "all")["12, Sched<1200, 12, 10, 10>, 8, 512"]
+    for n, r in ((fwd, fr), ("k_inv_cols<12, Sched<1200, 12, 10, 10>, 8, 512, AsxSelAll>", ir)):
         assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (n, r)
         assert 2 * (1200 * 8 * 8 + r["group_segment_fixed_size"]) <= 160 * 1024, (n, r)
 

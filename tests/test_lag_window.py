@@ -54,7 +54,7 @@ def kernels():
 
 def test_windowed_inverse_kernels_exist_and_keep_the_budgets_of_their_unwindowed_forms(kernels):
     """the window form beside every plain instance of k_inv_cols_r (<..., AsxWin> beside <..., AsxSelAll>) and of k_inv_cols
-    (k_inv_cols_w), same template arguments: same LDS (so the same blocks per CU by tile), <= 128 VGPRs, no scratch"""
+    (the same two selections), same template arguments: same LDS (so the same blocks per CU by tile), <= 128 VGPRs, no scratch"""
     pairs = 0
     for family in ("k_inv_cols_r", "k_inv_cols"):
         base = kernel_forms(kernels, family, "all")

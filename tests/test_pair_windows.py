@@ -40,7 +40,7 @@ def kernels():
 
 def test_per_pair_inverse_kernels_sit_beside_the_windowed_ones(kernels):
     """the per-pair form beside every window form of k_inv_cols_r (<..., AsxWinRows> beside <..., AsxWin>) and of k_inv_cols
-    (k_inv_cols_wp beside k_inv_cols_w), same template arguments: same LDS, <= 128 VGPRs, no scratch"""
+    (the same two selections), same template arguments: same LDS, <= 128 VGPRs, no scratch"""
     pairs = 0
     for family in ("k_inv_cols_r", "k_inv_cols"):
         base = kernel_forms(kernels, family, "window")

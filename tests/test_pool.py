@@ -105,20 +105,26 @@ def test_listed_tail_kernels_meet_the_budgets(kernels):
     """the listed forms of the tail kernels that read inputs, beside the forms they mirror, with the same LDS"""
     found = {}
     for k, r in kernels.items():
-        m = re.match(r"(?:void )?(k_pool_resolve|k_invalid_pairs|k_pearson_partial_l|k_pearson_prep_l|k_pearson_prep_pl)\b", k)
+        m = re.match(r"(?:void )?(k_pool_resolve|k_invalid_pairs)\b", k)
         if m:
             found.setdefault(m.group(1), []).append((k, r))
-    listed_dots = kernel_forms(kernels, "k_refine_dots", inputs="listed")
-    found["k_refine_dots_l"] = [("k_refine_dots " + k, r) for k, rs in listed_dots.items() for _, r in rs]
-    assert {k: len(v) for k, v in found.items()} == {"k_pool_resolve": 1, "k_invalid_pairs": 1, "k_refine_dots_l": 1,
-                                                     "k_pearson_partial_l": 2, "k_pearson_prep_l": 2, "k_pearson_prep_pl": 2}, found
+    listed = {name: kernel_forms(kernels, family, selection, "listed")
+              for name, family, selection in (("k_refine_dots listed", "k_refine_dots", None), ("k_pearson_partial listed", "k_pearson_partial", None),
+                                              ("k_pearson_prep seed listed", "k_pearson_prep", "seed"), ("k_pearson_prep rows listed", "k_pearson_prep", "rows"))}
+    listed_dots = listed["k_refine_dots listed"]
+    for name, forms in listed.items():
+        found[name] = [(name + " " + k, r) for k, rs in forms.items() for _, r in rs]
+    assert {k: len(v) for k, v in found.items()} == {"k_pool_resolve": 1, "k_invalid_pairs": 1, "k_refine_dots listed": 1,
+                                                     "k_pearson_partial listed": 2, "k_pearson_prep seed listed": 2, "k_pearson_prep rows listed": 2}, found
     for name, ks in found.items():
         for k, r in ks:
             assert r["vgpr_count"] <= 128 and r["private_segment_fixed_size"] == 0, (k, r)
-    lds = {k: r["group_segment_fixed_size"] for k, r in kernels.items()}
-    prep = {_args(k, "void k_pearson_prep<"): v for k, v in lds.items() if k.startswith("void k_pearson_prep<")}
-    for pfx in ("void k_pearson_prep_l<", "void k_pearson_prep_pl<"):
-        got = {_args(k, pfx): v for k, v in lds.items() if k.startswith(pfx)}
-        assert got == prep, (pfx, got, prep)
+
+    def lds_of(forms):
+        return {k: [r["group_segment_fixed_size"] for _, r in rs] for k, rs in forms.items()}
+
+    prep = lds_of(kernel_forms(kernels, "k_pearson_prep", "seed", "pitched"))
+    for name in ("k_pearson_prep seed listed", "k_pearson_prep rows listed"):
+        assert lds_of(listed[name]) == prep, (name, lds_of(listed[name]), prep)
     dots = [r["group_segment_fixed_size"] for _, r in kernel_forms(kernels, "k_refine_dots", inputs="pitched")["float"]]
     assert dots and [r["group_segment_fixed_size"] for _, r in listed_dots["float"]] == dots

@@ -131,9 +131,10 @@ def kernels():
 
 def test_topk_inverse_kernels_sit_beside_the_per_pair_ones(kernels):
     """the top-k form beside every per-pair form, same template arguments: k_inv_cols_r<..., AsxSelTopk<ZC>> in three zone
-    capacities beside <..., AsxWinRows>, k_inv_cols_wx beside every k_inv_cols_wp: same LDS, <= 128 VGPRs, no scratch"""
+    capacities beside <..., AsxWinRows>, k_inv_cols<..., AsxSelTopk<7>> (the packed kernels' one capacity) beside every
+    k_inv_cols<..., AsxWinRows>: same LDS, <= 128 VGPRs, no scratch"""
     n = 0
-    for family, caps in (("k_inv_cols_r", ["1", "3", "7"]), ("k_inv_cols", [None])):
+    for family, caps in (("k_inv_cols_r", ["1", "3", "7"]), ("k_inv_cols", ["7"])):
         base = kernel_forms(kernels, family, "rows")
         mine = kernel_forms(kernels, family, "topk")
         assert base and set(base) == set(mine), (family, sorted(base), sorted(mine))

@@ -24,16 +24,20 @@ def have_gpu():
 
 
 # How the kernel families spell "selection S, inputs I" in their demangled names.  A family that is one template names the policy
-# type among its template arguments (asx_internal.h: Selections, Inputs); a family with a kernel per form has a suffix for it.
+# types among its template arguments (asx_internal.h: Selections, Inputs); k_pearson_prep, which keeps a kernel per form, has a
+# suffix for it.
+INVERSE = {"all": "AsxSelAll", "window": "AsxWin", "rows": "AsxWinRows", "topk": "AsxSelTopk<"}
+SEED = {"seed": "AsxSelSeed", "rows": "AsxWinRows", "topk": "AsxSelTopkSeed"}
+INPUTS = {"pitched": "AsxAtPitch", "listed": "AsxAtList"}
 POLICY = {
-    "k_inv_cols_r": {"all": "AsxSelAll", "window": "AsxWin", "rows": "AsxWinRows", "topk": "AsxSelTopk<", "prune": "AsxSelPrune<"},
-    "k_refine_pick": {"seed": "AsxSelSeed", "rows": "AsxWinRows", "topk": "AsxSelTopkSeed"},
-    "k_refine_dots": {"pitched": "AsxAtPitch", "listed": "AsxAtList"},
+    "k_inv_cols_r": dict(INVERSE, prune="AsxSelPrune<"),
+    "k_inv_cols": INVERSE,
+    "k_refine_pick": SEED,
+    "k_finalize": SEED,
+    "k_refine_dots": INPUTS,
+    "k_pearson_partial": INPUTS,
 }
 SUFFIX = {
-    "k_inv_cols": {"all": "", "window": "_w", "rows": "_wp", "topk": "_wx"},
-    "k_finalize": {"seed": "", "rows": "_p", "topk": "_x"},
-    "k_pearson_partial": {"pitched": "", "listed": "_l"},
     "k_pearson_prep": {("seed", "pitched"): "", ("rows", "pitched"): "_p", ("topk", "pitched"): "_x",
                        ("seed", "listed"): "_l", ("rows", "listed"): "_pl", ("topk", "listed"): "_xl"},
 }
@@ -62,7 +66,8 @@ def template_args(name):
 def kernel_forms(kernels, family, selection=None, inputs=None):
     """The kernels "family F, selection S, inputs I" among {demangled name: record}: {the template arguments the family's forms
     share, as one string: [(the policy's own template argument or None, record), ...]}.  selection: all / window / rows / topk /
-    prune (the inverse kernels), seed / rows / topk (the kernels that take the seed); inputs: pitched / listed."""
+    prune (the inverse kernels), seed / rows / topk (the kernels that take the seed); inputs: pitched / listed (k_pearson_prep
+    asked for a selection alone: pitched)."""
     out = {}
     if family in POLICY:
         want = POLICY[family][selection or inputs]
@@ -73,8 +78,7 @@ def kernel_forms(kernels, family, selection=None, inputs=None):
                 own = args[hit[0]][len(want):].rstrip(" >") if want.endswith("<") else None
                 out.setdefault(", ".join(args[:hit[0]]), []).append((own, rec))
         return out
-    table = SUFFIX[family]
-    want = family + (table[(selection, inputs or "pitched")] if (selection, inputs or "pitched") in table else table[selection or inputs])
+    want = family + SUFFIX[family][(selection, inputs or "pitched")]
     for name, rec in kernels.items():
         base, args = template_args(name)
         if base == want:
