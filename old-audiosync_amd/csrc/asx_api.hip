@@ -157,7 +157,7 @@ struct asx_plan {
     int64_t win_lo = 0, win_hi = 0;    // asx_plan_set_lag_window: the lags whose peak is searched, [-N, N-1] (set at creation) = all
     bool spectral = false;             // float32 groups take the spectral Pearson form (asx_plan_set_pearson; real-column plans)
     unsigned long long *mode_count = nullptr; // [ASX_PM_NMODES], cumulative over the plan's life
-    bool prunable = false;             // asx_rlayout_prunable, asked once (plan_init): the lanes have their AsxPrune workspaces
+    bool prunable = false;             // AsxKernelChoice::prunable: the lanes have their AsxPrune workspaces
     bool prune = false;                // asx_plan_set_prune: in-scope groups skip the inverse column tiles a bound rules out
     unsigned long long *prune_stats = nullptr; // [2] tiles transformed, tiles in all, by the pruned groups; cumulative
     // "measure" plans only: at the first device-resident batch the forward column kernel is timed against the caller's buffers
@@ -230,34 +230,26 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
     // the device's r is the unnormalised inverse transform: F times the plain sum of products
     d.bound_scale = 2.0f * ASX_BOUND_C * 5.9604645e-8f * log2f((float)h.F) * (float)h.F;
     d.st1 = h.st1; d.st2 = h.st2;
-    d.threads_cols = asx_pick_threads(h.st1, h.T / 2, 64, asx_lds_bytes_cols(d));
-    d.threads_rows = asx_pick_threads(h.st2, 2, (h.M2 + ASX_ROW_STEPS - 1) / ASX_ROW_STEPS, asx_lds_bytes_rows(d));
-    if (const char *e = getenv("ASX_THREADS_COLS")) d.threads_cols = atoi(e);
-    if (const char *e = getenv("ASX_THREADS_ROWS")) d.threads_rows = atoi(e);
+    // Which kernels run was decided with the host plan (AsxKernelChoice, plan_math.cpp): the real-column kernels (rlayout.hip) when
+    // the plan allows them and they are compiled in for its schedules (the reference's six lengths), else the packed-sample kernels
+    const AsxKernelChoice &k = h.kernels;
+    // (the one check of it: a real-column plan without an entry has no kernel; the launchers look up and do not ask again)
+    if (k.rlayout && (k.cols < 0 || k.rows < 0 || !h.rlayout)) return fail("internal: a real-column plan without its kernels");
+    d.threads_cols = k.threads_cols; d.threads_rows = k.threads_rows;
+    d.rlayout = k.rlayout ? 1 : 0;
+    d.kcols = k.cols; d.krows = k.rows;
+    d.band_rows = k.band_rows;
+    d.nbands = k.band_rows ? 2 * h.M1 / k.band_rows : 0;
+    p->prunable = k.prunable;
     if (dev_upload(p, &d.tw1, h.tw1) || dev_upload(p, &d.tw2, h.tw2) || dev_upload(p, &d.tw2s, h.tw2s) || dev_upload(p, &d.tw_lo, h.tw_lo) ||
         dev_upload(p, &d.tw_hi, h.tw_hi) ||
         dev_upload(p, &d.k1_of_pos1, h.k1_of_pos1) || dev_upload(p, &d.pos1_of_k1, h.pos1_of_k1) ||
         dev_upload(p, &d.pos2_of_k2, h.pos2_of_k2) || dev_upload(p, &d.row_tasks, h.row_tasks))
         return -1;
 
-    // Which decomposition: the real-column kernels (rlayout.hip) when the plan allows them and they are compiled in for its
-    // schedules (the reference's six lengths); ASX_LAYOUT=packed forces the packed-sample kernels (A/B runs, the run-time-schedule
-    // kernels of ASX_GENERIC)
-    d.rlayout = 0;
-    d.band_rows = d.nbands = 0;
     d.col_pairs = nullptr;
     d.col_tw = nullptr;
-    {
-        const char *lay = getenv("ASX_LAYOUT");
-        const bool packed = (lay && !strcmp(lay, "packed")) || getenv("ASX_GENERIC");
-        if (h.rlayout && !packed) {
-            if (dev_upload(p, &d.col_pairs, h.col_pairs) || dev_upload(p, &d.col_tw, h.col_tw)) return -1;
-            d.rlayout = asx_rlayout_available(d) ? 1 : 0;
-            d.band_rows = d.rlayout ? asx_rlayout_band_rows(d) : 0;
-            d.nbands = d.band_rows ? 2 * h.M1 / d.band_rows : 0;
-            p->prunable = asx_rlayout_prunable(d);
-        }
-    }
+    if (k.rlayout && (dev_upload(p, &d.col_pairs, h.col_pairs) || dev_upload(p, &d.col_tw, h.col_tw))) return -1;
     // group size: keep the three inter-kernel intermediates (24*M bytes per pair) of one
     // group around the size of the 256 MiB Infinity Cache so the next kernel re-reads them on die
     size_t ws_mb = 4096;
@@ -855,7 +847,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // for, the lane's own lists (not the second look).  Everything else launches what it always did.
     // (GroupOpts::spectral is how an entry point says "float32 ABI": the double ABI clears it even when its frames were narrowed.
     // Whether the plan's Pearson form IS spectral -- p->spectral -- plays no part here.  p->prune is only ever set on a plan the
-    // pruned pass can run on: asx_rlayout_prunable.)
+    // pruned pass can run on: AsxKernelChoice::prunable.)
     const bool f32_entry = std::is_same<TIn, float>::value && o.spectral;
     const AsxSearch call = AsxSearch::of(p->win_lo, p->win_hi, P.N, x.win, x.win_step, W.tk, 0); // pass 1's search
     const bool prune = p->prune && f32_entry && !x.pool && x.bc == 0 && !o.r_out && !o.pk && o.topk.k == 1 && call.kind == AsxSearch::ALL;
@@ -873,8 +865,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
         asx_launch_pool_resolve(P, A, W.pool, C.nrm, C.band, (int)g, s);
     } else if (P.rlayout) {
         // the operands that are not the call's broadcast track, whose pass is in the slot: only its norm partials and band sums are copied
-        if (!asx_launch_fwd_cols_r(P, (x.bc & 1) ? nullptr : x.src, x.src_step, (x.bc & 2) ? nullptr : x.smp, x.smp_step, 0, (int)g, C, false, s))
-            return fail("internal: no forward column kernel for this plan");
+        asx_launch_fwd_cols_r(P, (x.bc & 1) ? nullptr : x.src, x.src_step, (x.bc & 2) ? nullptr : x.smp, x.smp_step, 0, (int)g, C, false, s);
         for (unsigned which = 0; which < 2; which++)
             if (x.bc & (1 << which)) asx_launch_bcast_aux(P, from.nrm, from.band, C.nrm, C.band, (int)g, which, s);
     } else if (x.src_step == 2 * (size_t)P.N && x.smp_step == P.N) {
@@ -891,7 +882,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     if (mark(1)) return -1;
     float2 *q = W.ga;
     if (!P.rlayout) asx_launch_rows(P, W.zxa, W.zya, q, tk, (int)g, s);
-    else if (!asx_launch_rows_r(P, C, q, tk, (int)g, s)) return fail("internal: no row kernel for this plan");
+    else asx_launch_rows_r(P, C, q, tk, (int)g, s);
     if (mark(2)) return -1;
     // Top-k (o.topk.k > 1): every pass's results go to the lane's temporaries, and k_topk_step moves them to entry j of y
     const int K = o.topk.k;
@@ -911,7 +902,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     auto pass = [&](const AsxSearch &find, bool first) -> int {
         float *const r_out = first ? o.r_out : nullptr;
         if (!P.rlayout) asx_launch_inv_cols(P, q, tk, r_out, (int)g, s, find);
-        else if (!asx_launch_inv_cols_r(P, q, tk, r_out, (int)g, s, find, C.prune)) return fail("internal: no inverse column kernel for this plan");
+        else asx_launch_inv_cols_r(P, q, tk, r_out, (int)g, s, find, C.prune);
         if (first && mark(3)) return -1;
         asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, find);
         // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
@@ -1100,7 +1091,8 @@ static int tune_placement(asx_plan *p, const float *d_src, const float *d_smp, s
         float best = 0.f;
         for (int r = 0; r < 4; r++) { // the first launch warms the set up; the fastest of the other three counts
             HIP_TRY(hipEventRecord(e0, s));
-            asx_launch_fwd_cols(P, d_src, d_smp, set[k][0], set[k][1], tk, (int)g, s);
+            if (P.rlayout) asx_launch_fwd_cols_r(P, d_src, 2 * (size_t)P.N, d_smp, P.N, 0, (int)g, { set[k][0], set[k][1], tk.nrm_part, tk.band }, false, s);
+            else asx_launch_fwd_cols(P, d_src, d_smp, set[k][0], set[k][1], tk, (int)g, s);
             HIP_TRY(hipEventRecord(e1, s));
             HIP_TRY(hipEventSynchronize(e1));
             float ms = 0.f;
@@ -1225,8 +1217,7 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
             B = T;
         }
         // the shared track's forward column pass: once per call, on the caller's stream, before any lane forks
-        if (!asx_launch_fwd_cols_r(P, (bc & 1) ? d_source : nullptr, 0, (bc & 2) ? d_sample : nullptr, 0, 0, 1, B, true, s))
-            return fail("internal: no forward column kernel for this plan");
+        asx_launch_fwd_cols_r(P, (bc & 1) ? d_source : nullptr, 0, (bc & 2) ? d_sample : nullptr, 0, 0, 1, B, true, s);
     }
     return run_batch(p, Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, bc, d_windows, window_stride), batch, y, s,
                      topk);
@@ -1328,9 +1319,8 @@ static int pool_batch(asx_plan *p, const char *fn, const float *d_sources, size_
     for (int op = 0; op < 2; op++) {
         const size_t n = op ? nsamples : nsources;
         for (size_t c0 = 0; c0 < n; c0 += 65535)
-            if (!asx_launch_fwd_cols_r(P, op ? nullptr : d_sources, source_stride, op ? d_samples : nullptr, sample_stride, c0,
-                                       (int)std::min<size_t>(65535, n - c0), p->bank.c, true, s))
-                return fail("internal: no forward column kernel for this plan");
+            asx_launch_fwd_cols_r(P, op ? nullptr : d_sources, source_stride, op ? d_samples : nullptr, sample_stride, c0,
+                                  (int)std::min<size_t>(65535, n - c0), p->bank.c, true, s);
     }
     p->bank.fills++;
     const PoolCall pool{ d_pairs, nsources, nsamples };
@@ -2088,6 +2078,39 @@ extern "C" int asx_stream_sync(asx_plan *p, void *stream)
 // ---------------------------------------------------------------------------
 // planning arithmetic exposed for the CPU test-suite (no HIP calls)
 // ---------------------------------------------------------------------------
+// the kernels the plan of (sample_len, split) would run under the current environment (AsxKernelChoice): out = {real-column,
+// entry of the column list, of the row list, block size of the packed column kernels, of the row kernels, band_rows, prunable};
+// cols / rows: the two entries spelled out (asx_kernel_table_spell), ASX_KERNEL_ENTRY_CAP ints each
+static void choice_out(const AsxKernelChoice &k, int *out, int *cols, int *rows)
+{
+    const int v[7] = { k.rlayout, k.cols, k.rows, k.threads_cols, k.threads_rows, k.band_rows, k.prunable };
+    memcpy(out, v, sizeof v);
+    asx_kernel_table_spell(k.rlayout ? 0 : 2, k.cols, cols);
+    asx_kernel_table_spell(k.rlayout ? 1 : 3, k.rows, rows);
+}
+// entry `index` of list 0 .. 3 of kernel_table.h (AsxRCols, AsxRRows, AsxPCols, AsxPRows) into out; 1: the list ends before it
+extern "C" int asx_planmath_kernel_table(int list, int index, int *out)
+{
+    if (!out) return fail("asx_planmath_kernel_table: null argument");
+    return asx_kernel_table_spell(list, index, out) ? 0 : 1;
+}
+extern "C" int asx_planmath_kernels(size_t sample_len, const char *split, int *out, int *cols, int *rows)
+{
+    if (!out || !cols || !rows) return fail("asx_planmath_kernels: null argument");
+    AsxHostPlan h;
+    std::string err = asx_host_plan_build(sample_len, split, &h);
+    if (!err.empty()) return fail("%s", err.c_str());
+    choice_out(h.kernels, out, cols, rows);
+    return 0;
+}
+// the same of a live plan: the record it holds
+extern "C" int asx_plan_debug_kernels(const asx_plan *p, int *out, int *cols, int *rows)
+{
+    if (!p || !out || !cols || !rows) return fail("asx_plan_debug_kernels: null argument");
+    choice_out(p->host.kernels, out, cols, rows);
+    return 0;
+}
+
 extern "C" int asx_planmath_describe(size_t sample_len, const char *split, uint32_t *F, uint32_t *src_valid,
                                      int *M1, int *M2, int *T, int *nst1, int *radix1, int *nst2,
                                      int *radix2)

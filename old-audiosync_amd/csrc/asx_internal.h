@@ -95,13 +95,15 @@ struct AsxDev {
     const int *pos2_of_k2; // k2 -> slot inside a row after the forward row transform
     const int4 *row_tasks; // [M1/2+1] {slot of row k1, slot of row M1-k1, k1, M1-k1}: one load starts a k_rows block
     int band_rows, nbands; // spectral Pearson form: rows of the [2 M1][M2] sample matrix per band (what one lane group of k_fwd_cols_r
-                           // loads: asx_rlayout_band_rows), bands of the source = 2 M1 / band_rows; 0 = not available
+                           // loads: AsxKernelChoice::band_rows), bands of the source = 2 M1 / band_rows; 0 = not available
     int rlayout;           // 1: this plan runs the real-column kernels (rlayout.hip); 0: the packed-sample kernels (xcorr_kernels.hip)
     const int4 *col_pairs; // real-column kernels (rlayout.hip): [M1/2 + 1] {u, slot of u, slot of M1 - u, 0}; null = not available
     const float2 *col_tw;  // w_{2 M1}^u, same order
     const AsxDev *self_dev; // device copy of this struct (what the kernels read)
     unsigned long long *stamps; // diagnostic builds (-DASX_STAMPS) only: per-block phase clocks, 8 slots per block
     int stamp_kernel;      // which kernel records them: 0 k_rows, 1 k_fwd_cols, 2 k_inv_cols ($ASX_STAMPS = 1 | fwd | inv)
+    int kcols, krows;      // host only (no kernel reads them): the plan's entries of its layout's lists in kernel_table.h, what the
+                           // launchers look up (AsxKernelChoice::cols / rows; -1, packed plans only: the run-time-schedule kernel)
 };
 
 // Peak-search partial: order-preserving key in the high word, ~index in the low word,
@@ -477,6 +479,7 @@ struct AsxSpecWs {
     uint32_t N;            // sample_len (set by the launcher)
 };
 
+// xcorr_kernels.hip: the packed-sample decomposition, each pass on the instance P.kcols / P.krows names
 void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, float2 *zxa,
                          float2 *zya, const AsxPeakWs &W, int npairs, hipStream_t s);
 void asx_launch_rows(const AsxDev &P, float2 *zxa, float2 *zya, float2 *ga,
@@ -484,14 +487,14 @@ void asx_launch_rows(const AsxDev &P, float2 *zxa, float2 *zya, float2 *ga,
 // q: which flavour of the inverse column kernel runs (AsxSearch)
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                          const AsxSearch &q);
-// rlayout.hip: the real-column decomposition (production lengths); false = no kernel compiled in for this plan.  Which flavour of a
-// kernel runs is the launcher's decision: the row launcher reads it from the group's AsxSpectra, the inverse launcher from the search
+// rlayout.hip: the real-column decomposition (production lengths), each pass on the instance P.kcols / P.krows names.  Which flavour
+// of it runs is the launcher's decision: the row launcher reads it from the group's AsxSpectra, the inverse launcher from the search
 // and from U (the AsxPrune of a group in scope for pruning, else null), the forward launcher from the operands it is given (null: not
 // that operand) -- tracks first .. first + count - 1 of each, into the same tracks of dst.
-bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, size_t first,
+void asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, size_t first,
                            int count, const AsxSpectra &dst, bool temporal, hipStream_t s);
-bool asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s);
-bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
+void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s);
+void asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                            const AsxSearch &search, const AsxPrune *U);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
@@ -502,9 +505,6 @@ void asx_launch_pool_resolve(const AsxDev &P, const AsxPoolArgs &A, AsxPoolPair 
 void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 // the same behind the last k_topk_step of a pool group with top-k: all k entries of such a pair (entry stride k)
 void asx_launch_invalid_pairs_k(const AsxPoolPair *pl, int k, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
-bool asx_rlayout_available(const AsxDev &P); // all three kernels compiled in for this plan's schedules
-bool asx_rlayout_prunable(const AsxDev &P);  // ... and the pruned inverse pass can run on it (asked once, by plan_init)
-int asx_rlayout_band_rows(const AsxDev &P);
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,
                          const AsxSearch &q);
 // behind the Pearson kernels of pass j of a top-k group: entry j of the caller's arrays (entry stride k) from the pass's results,
@@ -543,6 +543,3 @@ template <typename TIn>
 void asx_launch_dc_remove(const TIn *src, const TIn *smp, uint32_t N, double scale, double *stats, float *out, hipStream_t s);
 void asx_launch_synth(uint64_t seed, uint64_t first_pair, size_t count, uint32_t N,
                       int noise_shift, float *src, float *smp, int64_t *true_lag, hipStream_t s);
-int asx_pick_threads(const AsxStages &st, int groups, int min_threads, size_t lds_bytes);
-size_t asx_lds_bytes_cols(const AsxDev &P);
-size_t asx_lds_bytes_rows(const AsxDev &P);

@@ -4,6 +4,7 @@
 #include <functional>
 #include <algorithm>
 #include "plan_math.h"
+#include "kernel_table.h"
 
 #include <cmath>
 #include <cstdio>
@@ -175,6 +176,71 @@ std::vector<std::string> asx_host_plan_candidates(size_t N, size_t max_count)
     return out;
 }
 
+// Block size: a multiple of 64 (<= ASX_FFT_THREADS_MAX).  First enough waves per CU to hide
+// LDS/HBM latency given how many blocks the LDS footprint admits (target >= 12 waves per CU),
+// then the size that wastes the fewest thread slots over the stages (each stage has
+// `groups * n / radix` work items); ties go to the larger block.
+static int pick_threads(const AsxStages &st, int groups, int min_threads, size_t lds_bytes)
+{
+    long blocks_per_cu = lds_bytes ? (long)(160 * 1024 / lds_bytes) : 8;
+    if (blocks_per_cu < 1) blocks_per_cu = 1;
+    if (blocks_per_cu > 8) blocks_per_cu = 8;
+    int want = 64 * (int)((12 + blocks_per_cu - 1) / blocks_per_cu);
+    if (want > ASX_FFT_THREADS_MAX) want = ASX_FFT_THREADS_MAX;
+    if (min_threads < want) min_threads = want;
+    long best_cost = -1;
+    int best = ASX_FFT_THREADS_MAX;
+    for (int bd = 64; bd <= ASX_FFT_THREADS_MAX; bd += 64) {
+        if (bd < min_threads) continue;
+        long cost = 0;
+        for (int i = 0; i < st.nstages; i++) {
+            const long items = (long)groups * st.nbf[i];
+            cost += (items + bd - 1) / bd * bd;
+        }
+        if (st.nstages == 0) cost = bd;
+        if (best_cost < 0 || cost <= best_cost) { best_cost = cost; best = bd; }
+    }
+    return best;
+}
+
+// Which kernels the plan h runs.  The real-column kernels when the plan allows them (h.rlayout), nothing forces the packed ones and
+// BOTH a column and a row entry match; else the packed kernels, columns and rows each on a compiled-in schedule that matches the
+// split and the block size, or on the run-time schedule (generic: always that).
+static AsxKernelChoice choose_kernels(const AsxHostPlan &h, bool packed, bool generic)
+{
+    AsxKernelChoice k;
+    k.threads_cols = pick_threads(h.st1, h.T / 2, 64, (size_t)h.M1 * h.T * sizeof(float2));
+    k.threads_rows = pick_threads(h.st2, 2, (h.M2 + ASX_ROW_STEPS - 1) / ASX_ROW_STEPS, (size_t)4 * h.M2 * sizeof(float2));
+    if (const char *e = getenv("ASX_THREADS_COLS")) k.threads_cols = atoi(e);
+    if (const char *e = getenv("ASX_THREADS_ROWS")) k.threads_rows = atoi(e);
+    if (h.rlayout && !packed) {
+        const int c = asx_match_entry(AsxRCols{}, [&](auto e) { return h.T == e.t && schedule_is<typename decltype(e)::sched>(h.st1); });
+        const int r = asx_match_entry(AsxRRows{}, [&](auto e) { return h.M2 == e.m2; });
+        if (c >= 0 && r >= 0) {
+            k.rlayout = true;
+            k.cols = c; k.rows = r;
+            asx_with_entry(AsxRCols{}, c, [&](auto e) { k.band_rows = 2 * rcol_rows_per_group(decltype(e)::sched::n, e.nt, e.t); });
+            // the tile width k_rows_re sums energies for, whole tiles only (AsxSelPrune indexes its flags by M2 / T), and a tile
+            // per thread of a k_tile_bounds block
+            k.prunable = h.T == ASX_PRUNE_T && h.M2 % ASX_PRUNE_T == 0 && h.ntiles <= 1024;
+            return k;
+        }
+    }
+    if (generic) return k;
+    k.cols = asx_match_entry(AsxPCols{}, [&](auto e) { return h.T == e.t && k.threads_cols == e.nt && schedule_is<typename decltype(e)::sched>(h.st1); });
+    k.rows = asx_match_entry(AsxPRows{}, [&](auto e) { return k.threads_rows == e.nt && schedule_is<typename decltype(e)::sched>(h.st2); });
+    return k;
+}
+
+static_assert(ASX_ENTRY_INTS <= ASX_KERNEL_ENTRY_CAP, "an entry of kernel_table.h no longer fits the diagnostics' buffers");
+bool asx_kernel_table_spell(int list, int index, int *out)
+{
+    auto spell = [&](auto e) { asx_entry_spell(e, out); };
+    out[0] = -1;
+    return list == 0 ? asx_with_entry(AsxRCols{}, index, spell) : list == 1 ? asx_with_entry(AsxRRows{}, index, spell)
+         : list == 2 ? asx_with_entry(AsxPCols{}, index, spell) : list == 3 && asx_with_entry(AsxPRows{}, index, spell);
+}
+
 std::string asx_host_plan_build(size_t N, const char *split_override, AsxHostPlan *hp)
 {
     if (N == 0) return "sample_len must be > 0";
@@ -207,9 +273,10 @@ std::string asx_host_plan_build(size_t N, const char *split_override, AsxHostPla
         { 720000u, "600x1200x16", nullptr }, { 960000u, "400x2400x16", "800x1200x8" },
         { 1440000u, "600x2400x16", "1200x1200x8" },
     };
+    // ASX_LAYOUT=packed forces the packed-sample kernels (A/B runs); ASX_GENERIC their run-time-schedule forms (diagnostic)
+    const char *lay = getenv("ASX_LAYOUT");
+    const bool generic = getenv("ASX_GENERIC") != nullptr, packed = (lay && !strcmp(lay, "packed")) || generic;
     if (!(split_override && *split_override)) {
-        const char *lay = getenv("ASX_LAYOUT");
-        const bool packed = (lay && !strcmp(lay, "packed")) || getenv("ASX_GENERIC");
         for (const auto &t : kTuned)
             if (t.M == M && F == 2 * (uint64_t)N) split_override = (packed && t.split_packed) ? t.split_packed : t.split;
     }
@@ -300,5 +367,6 @@ std::string asx_host_plan_build(size_t N, const char *split_override, AsxHostPla
         }
         hp->rlayout = true;
     }
+    hp->kernels = choose_kernels(*hp, packed, generic);
     return "";
 }

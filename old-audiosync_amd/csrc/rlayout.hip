@@ -31,9 +31,9 @@
 #include "asx_internal.h"
 #include "lds_fft.h"
 #include "xcorr_dev.h"
+#include "kernel_table.h"
 
 #include <algorithm>
-#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -105,7 +105,7 @@ __device__ __forceinline__ void wave_lds_sync()
 //   -DASX_EXP_PAIRMOD=<m>   every pair of a launch uses the C / Q workspaces of pair (pair % m): wrong results, the traffic
 //                           of a launch whose intermediates never leave the 256 MiB Infinity Cache (upper bound of keeping
 //                           them on die, EXPERIMENTS.md)
-//   -DASX_ROWS2_SCHED=a,b,c the radix schedule of the 1200-point sub-rows of the two-half row kernel
+//   -DASX_ROWS2_SCHED=a,b,c the radix schedule of the 1200-point sub-rows of the two-half row kernel (kernel_table.h)
 // sum over the four lanes of a quad (every lane gets it): two DPP steps
 __device__ __forceinline__ float quad_sum(float v)
 {
@@ -132,8 +132,6 @@ template <int N> __device__ __forceinline__ float tree_sum(const float (&p)[N])
         return tree_sum<(N + 1) / 2>(q);
     }
 }
-// row pairs a lane group of k_fwd_cols_r<Sched<m1, ...>, t, nt> loads = half the rows of a band (asx_rlayout_band_rows)
-__host__ __device__ constexpr int rcol_rows_per_group(int m1, int nt, int t) { return (m1 + nt / (t / 4) - 1) / (nt / (t / 4)); }
 
 #ifdef ASX_EXP_PAIRMOD
 #define RWS_PAIR(pair) ((pair) % (ASX_EXP_PAIRMOD))
@@ -165,9 +163,6 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
     if (nt) { asx_f2v w; w.x = v.x; w.y = v.y; __builtin_nontemporal_store(w, reinterpret_cast<asx_f2v *>(p)); }
     else *p = v;
 }
-#ifndef ASX_ROWS2_SCHED
-#define ASX_ROWS2_SCHED 12, 10, 10
-#endif
 
 // k_rows_r, which table look-ups are issued ahead of the loads they would otherwise queue behind (vmcnt completes in order):
 // bit 0 = the block's tw_step / leg entries BEFORE the row loads (the barrier in front of the load phase's arithmetic then waits for an
@@ -1242,24 +1237,6 @@ __global__ __launch_bounds__(256) void k_prune_select(const float *__restrict__ 
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-static bool schedule_is_r(const AsxStages &st, int n, std::initializer_list<int> radices)
-{
-    if (st.n != n || st.nstages != (int)radices.size()) return false;
-    int i = 0;
-    for (int r : radices)
-        if (st.radix[i++] != r) return false;
-    return true;
-}
-
-// Row schedules of the real-column kernels: X(block size of a (sub-)row, two-half form, (sub-)row length, radices...); the plan's row
-// length M2 is the sub-row's, twice in the two-half form.  Chosen by the row length alone: these kernels carry their own schedule and
-// only read the plan's w_M2 table.
-// 480-point rows: ONE wave per block -- a block is 11.5 KB of traffic and a chain of five short phases, so what counts is
-// how many are in flight: sixteen single-wave blocks per CU against eight of two waves (rows 0.93 -> 0.83 ms per 1024
-// pairs of N = 144 000, same box)
-#define ASX_RROWS(X) \
-    X(128, false, 1200, 12, 10, 10) X(128, true, 1200, ASX_ROWS2_SCHED) X(64, false, 480, 10, 8, 6)
-
 // one flavour of k_rows_r, with the flavour's extra argument (none: k_rows_r itself)
 template <class K, class... X>
 static void launch_rows_r(K kernel, const AsxDev &P, int nt, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs,
@@ -1273,41 +1250,22 @@ static void launch_rows_r(K kernel, const AsxDev &P, int nt, const AsxSpectra &C
 // The row pass of a group whose spectra are C, which decides the flavour: k_rows_re (plus the tile energies C.prune->eng) when the
 // group is in scope for pruning, k_rows_rl (C_x / C_y at the pairs' bank slots) in a pool group, else k_rows_r in the broadcast form
 // C.bc.  The operands that are not broadcast and q have the group workspace's pair pitch.
-bool asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s)
+void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s)
 {
-#define ASX_BC(b, nt, two, n, ...) launch_rows_r(k_rows_r<Sched<n, __VA_ARGS__>, nt, two, b>, P, (two) ? 2 * nt : nt, C, q, W, npairs, s)
-#define ASX_TRY(nt, two, n, ...)                                                                                                \
-    if (P.M2 == ((two) ? 2 * n : n)) {                                                                                          \
-        if (C.prune)                                                                                                            \
-            launch_rows_r(k_rows_re<Sched<n, __VA_ARGS__>, nt, two>, P, (two) ? 2 * nt : nt, C, q, W, npairs, s, C.prune->eng); \
-        else if (C.pl)                                                                                                          \
-            launch_rows_r(k_rows_rl<Sched<n, __VA_ARGS__>, nt, two>, P, (two) ? 2 * nt : nt, C, q, W, npairs, s, C.pl);         \
-        else                                                                                                                    \
-            switch (C.bc) {                                                                                                     \
-            case 0: ASX_BC(0, nt, two, n, __VA_ARGS__); break;                                                                  \
-            case 1: ASX_BC(1, nt, two, n, __VA_ARGS__); break;                                                                  \
-            case 2: ASX_BC(2, nt, two, n, __VA_ARGS__); break;                                                                  \
-            default: ASX_BC(3, nt, two, n, __VA_ARGS__); break;                                                                 \
-            }                                                                                                                   \
-        return true;                                                                                                            \
-    }
-    ASX_RROWS(ASX_TRY)
-#undef ASX_TRY
-#undef ASX_BC
-    return false;
-}
-
-// Column schedules of the production sample lengths (plan_math.cpp's tuned table):  X(M1, tile width in real columns,
-// block size, radices...).  (1200- and 800-row tiles hold only eight real columns: 32-byte input pieces, measured 25 % slower
-// in k_fwd_cols_r, and a fed first stage of radix 10 needs 20 rows in flight per thread: the two longest lengths use 600 / 400
-// rows with 2400-point rows instead.)  Block sizes are measured (profiles/r4_experiments/10_*, 11_*): 400-row tiles 512
-// threads (320, the packed kernels' choice: 12 % slower at N = 480 000), 300-row tiles 256 (320 / 384 / 512: 20-35 % slower).
-#define ASX_RCOLS(X) \
-    X(600, 16, 512, 10, 10, 6) X(400, 16, 512, 10, 8, 5) X(300, 16, 256, 10, 6, 5)
-
-static void allow_big_lds_r(const void *fn, size_t bytes)
-{
-    if (bytes > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    asx_with_entry(AsxRRows{}, P.krows, [&](auto e) {
+        using S = typename decltype(e)::sched;
+        constexpr int NT = e.nt, nt = e.two ? 2 * NT : NT;
+        constexpr bool TWO = e.two;
+        if (C.prune) launch_rows_r(k_rows_re<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.prune->eng);
+        else if (C.pl) launch_rows_r(k_rows_rl<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl);
+        else
+            switch (C.bc) {
+            case 0: launch_rows_r(k_rows_r<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s); break;
+            case 1: launch_rows_r(k_rows_r<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s); break;
+            case 2: launch_rows_r(k_rows_r<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s); break;
+            default: launch_rows_r(k_rows_r<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s); break;
+            }
+    });
 }
 
 // Blocks of `fn` the current device holds at once (k_inv_cols_r's first generation, the one its stagger delays half of): occupancy
@@ -1334,12 +1292,11 @@ static unsigned resident_blocks(const void *fn, int nthreads, size_t lds)
 // apart (0 = one track), into the same tracks of dst: C at pitch (M1 + 1) M2, norm partials and band sums in the AsxPeakWs layouts.
 // temporal: C stored with ordinary stores (the broadcast slot, the bank).  The kernel reads and writes only the operands it is
 // launched for (op0 + blockIdx.y), so an absent operand's pointers are never used.
-bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, size_t first,
+void asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, size_t first,
                            int count, const AsxSpectra &dst, bool temporal, hipStream_t s)
 {
-    if (!P.col_pairs) return false;
     const unsigned op0 = src ? 0 : 1, nops = (src ? 1 : 0) + (smp ? 1 : 0);
-    if (nops == 0) return true;
+    if (nops == 0) return;
     const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, lds = (size_t)P.M1 * P.T * sizeof(float2);
     const size_t per = 2 * (size_t)P.ntiles; // norm partials per track slot; band sums: nbands times as many
     if (src) src += first * src_stride;
@@ -1348,21 +1305,15 @@ bool asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride,
     float2 *band = dst.band ? dst.band + first * per * (size_t)P.nbands : nullptr;
     float *nrm = dst.nrm + first * per;
     const dim3 grid(rcol_grid_x(P.ntiles, P.logT), nops, count);
-#define ASX_TRY1(nts, m1, t, nt, ...)                                                                                        \
-    {                                                                                                                       \
-        allow_big_lds_r((const void *)k_fwd_cols_r<Sched<m1, __VA_ARGS__>, t, nt, nts>, lds);                               \
-        hipLaunchKernelGGL((k_fwd_cols_r<Sched<m1, __VA_ARGS__>, t, nt, nts>), grid, dim3(nt), lds, s, rargs_of(P), src, smp,  \
-                           src_stride, smp_stride, cx, cy, nrm, pitch, band, op0);                                          \
-    }
-#define ASX_TRY(m1, t, nt, ...)                                                                                             \
-    if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                                                          \
-        if (temporal) ASX_TRY1(false, m1, t, nt, __VA_ARGS__) else ASX_TRY1(true, m1, t, nt, __VA_ARGS__)                   \
-        return true;                                                                                                        \
-    }
-    ASX_RCOLS(ASX_TRY)
-#undef ASX_TRY
-#undef ASX_TRY1
-    return false;
+    auto launch = [&](auto kernel, int nt) {
+        allow_big_lds((const void *)kernel, lds);
+        hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, s, rargs_of(P), src, smp, src_stride, smp_stride, cx, cy, nrm, pitch, band, op0);
+    };
+    asx_with_entry(AsxRCols{}, P.kcols, [&](auto e) {
+        using S = typename decltype(e)::sched;
+        if (temporal) launch(k_fwd_cols_r<S, e.t, e.nt, false>, e.nt);
+        else launch(k_fwd_cols_r<S, e.t, e.nt, true>, e.nt);
+    });
 }
 
 void asx_launch_pool_resolve(const AsxDev &P, const AsxPoolArgs &A, AsxPoolPair *out, float *nrm, float2 *band, int npairs,
@@ -1387,7 +1338,7 @@ static void launch_inv_r(K kernel, const AsxDev &P, dim3 grid, int nt, size_t ld
                          float *r_out, Sel sel)
 {
     const void *fn = (const void *)kernel;
-    allow_big_lds_r(fn, lds);
+    allow_big_lds(fn, lds);
     hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, s, rargs_of(P), q, ((size_t)P.M1 + 1) * (size_t)P.M2, W, r_out,
                        resident_blocks(fn, nt, lds), sel);
 }
@@ -1399,9 +1350,9 @@ static void launch_inv_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, 
     const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, lds = (size_t)S1::n * TC * sizeof(float2);
     auto k1 = k_inv_cols_r<S1, TC, NT, AsxSelPrune<true>>;
     auto k2 = k_inv_cols_r<S1, TC, NT, AsxSelPrune<false>>;
-    allow_big_lds_r((const void *)k1, lds);
-    allow_big_lds_r((const void *)k2, lds);
-    const int tp = (P.ntiles + 31) & ~31; // asx_rlayout_prunable: at most 1024
+    allow_big_lds((const void *)k1, lds);
+    allow_big_lds((const void *)k2, lds);
+    const int tp = (P.ntiles + 31) & ~31; // AsxKernelChoice::prunable: at most 1024
     hipLaunchKernelGGL(k_tile_bounds, dim3(npairs, 1024 / tp), dim3((tp + 63) & ~63), 0, s, U.eng, U.ub, U.best, U.part, U.ticket, P.M1 + 1, P.ntiles,
                        4.0 * (double)P.M1, ASX_PRUNE_FLOOR_PER_TERM * (double)ASX_PRUNE_T * (double)(P.M1 + 1));
     hipLaunchKernelGGL(k1, dim3(npairs, 2), dim3(NT), lds, s, rargs_of(P), q, pitch, W, resident_blocks((const void *)k1, NT, lds),
@@ -1413,54 +1364,19 @@ static void launch_inv_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, 
 
 // The inverse column pass of a group: U null, the flavour the search asks for; U the lane's prune workspace (a group in scope for
 // pruning: every lag competes, no r_out, and k_rows_re has left U->eng), the pruned pass.
-bool asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
+void asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                            const AsxSearch &search, const AsxPrune *U)
 {
-    if (!P.col_pairs) return false;
-#define ASX_TRY(m1, t, nt, ...)                                                                                             \
-    if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) {                                                          \
-        const size_t lds = (size_t)(m1) * (t) * sizeof(float2);                                                             \
-        const dim3 grid(npairs, rcol_grid_x(P.M2 / (t), asx_ilog2(t)));                                                     \
-        if (U)                                                                                                              \
-            launch_inv_rq<Sched<m1, __VA_ARGS__>, t, nt>(P, q, W, *U, npairs, s);                                           \
-        else                                                                                                                \
-            asx_with_selection<1, 3, ASX_TOPK_MAX - 1>(search, [&](auto sel) {                                              \
-                launch_inv_r(k_inv_cols_r<Sched<m1, __VA_ARGS__>, t, nt, decltype(sel), float>, P, grid, nt, lds, s, q, W,  \
-                             r_out, sel);                                                                                   \
-            });                                                                                                             \
-        return true;                                                                                                        \
-    }
-    ASX_RCOLS(ASX_TRY)
-#undef ASX_TRY
-    return false;
-}
-
-// rows of the sample matrix per band of the spectral Pearson form = what one lane group of this plan's k_fwd_cols_r loads; 0 = no kernel
-int asx_rlayout_band_rows(const AsxDev &P)
-{
-#define ASX_TRY(m1, t, nt, ...) if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) return 2 * rcol_rows_per_group(m1, nt, t);
-    ASX_RCOLS(ASX_TRY)
-#undef ASX_TRY
-    return 0;
-}
-
-bool asx_rlayout_available(const AsxDev &P)
-{
-    if (!P.col_pairs || P.nout != P.F) return false;
-    bool cols = false, rows = false;
-#define ASX_TRY(m1, t, nt, ...) if (P.T == (t) && schedule_is_r(P.st1, m1, { __VA_ARGS__ })) cols = true;
-    ASX_RCOLS(ASX_TRY)
-#undef ASX_TRY
-#define ASX_TRY(nt, two, n, ...) if (P.M2 == ((two) ? 2 * n : n)) rows = true;
-    ASX_RROWS(ASX_TRY)
-#undef ASX_TRY
-    return cols && rows;
-}
-
-// Whether the pruned inverse pass can run on this plan, the one statement of it (plan_init asks once; the launchers do not ask
-// again): the real-column kernels, the tile width k_rows_re sums energies for, whole tiles only (AsxSelPrune indexes its flags by
-// M2 / T), and a tile per thread of a k_tile_bounds block.
-bool asx_rlayout_prunable(const AsxDev &P)
-{
-    return asx_rlayout_available(P) && P.T == ASX_PRUNE_T && P.M2 % ASX_PRUNE_T == 0 && P.ntiles <= 1024;
+    asx_with_entry(AsxRCols{}, P.kcols, [&](auto e) {
+        using S = typename decltype(e)::sched;
+        constexpr int T = e.t, NT = e.nt;
+        const size_t lds = (size_t)S::n * T * sizeof(float2);
+        const dim3 grid(npairs, rcol_grid_x(P.M2 / T, asx_ilog2(T)));
+        if (U)
+            launch_inv_rq<S, T, NT>(P, q, W, *U, npairs, s);
+        else
+            asx_with_selection<1, 3, ASX_TOPK_MAX - 1>(search, [&](auto sel) {
+                launch_inv_r(k_inv_cols_r<S, T, NT, decltype(sel), float>, P, grid, NT, lds, s, q, W, r_out, sel);
+            });
+    });
 }

@@ -99,6 +99,11 @@ __device__ __forceinline__ LdsLayout col_layout(int T, int logT, int nthreads)
     return L;
 }
 constexpr int asx_ilog2(int v) { return v <= 1 ? 0 : 1 + asx_ilog2(v >> 1); }
+// a column kernel's tile may take more dynamic LDS than a kernel gets unasked (a per-function, per-device attribute: set at the launch)
+static inline void allow_big_lds(const void *fn, size_t bytes)
+{
+    if (bytes > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
 
 
 // ---------------------------------------------------------------------------

@@ -17,9 +17,9 @@
 #include "asx_internal.h"
 #include "lds_fft.h"
 #include "xcorr_dev.h"
+#include "kernel_table.h"
 
 #include <algorithm>
-#include <initializer_list>
 #include <math.h>
 #include <type_traits>
 #include <stdlib.h>
@@ -1543,195 +1543,113 @@ static int max_radix(const AsxStages &st)
     return m;
 }
 
-static void allow_big_lds(const void *fn, size_t bytes)
-{
-    if (bytes > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-static bool schedule_is(const AsxStages &st, int n, std::initializer_list<int> radices)
-{
-    if (st.n != n || st.nstages != (int)radices.size()) return false;
-    int i = 0;
-    for (int r : radices)
-        if (st.radix[i++] != r) return false;
-    return true;
-}
-// Column schedules of the production sample lengths (plan_math.cpp's tuned table), compiled in:
-//   X(M1, tile width, block size, MAXR for the launch bounds, radices...)
-#define ASX_STATIC_COLS(X) \
-    X(1200, 8, 512, 12, 12, 10, 10) X(800, 8, 320, 10, 10, 10, 8) X(600, 16, 512, 10, 10, 10, 6) \
-    X(400, 16, 320, 10, 10, 8, 5) X(300, 16, 256, 10, 10, 6, 5)
-
-// Every transform kernel has two launchers, each in its own part of the build: *_static returns false
-// when no compiled-in schedule matches the plan, *_generic takes any plan.
-bool asx_launch_fwd_cols_static(const AsxDev &P, const float *src, const float *smp, float2 *zxa, float2 *zya,
-                                const AsxPeakWs &W, int npairs, hipStream_t s);
-void asx_launch_fwd_cols_generic(const AsxDev &P, const float *src, const float *smp, float2 *zxa, float2 *zya,
-                                 const AsxPeakWs &W, int npairs, hipStream_t s);
-bool asx_launch_rows_static(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga, const AsxPeakWs &W,
-                            int npairs, hipStream_t s);
-void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga, const AsxPeakWs &W,
+// Every packed transform pass has its launcher in the part of the build that holds the compiled-in schedules (AsxPCols / AsxPRows,
+// kernel_table.h): it looks the plan's entry up there, and hands a plan without one (-1) to the run-time-schedule kernels, which
+// are a part of their own (*_any: they take any plan).
+void asx_launch_fwd_cols_any(const AsxDev &P, const float *src, const float *smp, float2 *zxa, float2 *zya, const AsxPeakWs &W,
                              int npairs, hipStream_t s);
-bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                hipStream_t s, const AsxSearch &q);
-void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                 hipStream_t s, const AsxSearch &q);
+void asx_launch_rows_any(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga, const AsxPeakWs &W, int npairs,
+                         hipStream_t s);
+void asx_launch_inv_cols_any(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
+                             const AsxSearch &q);
 
-#define ASX_FWD_LAUNCH(...) \
-    do { allow_big_lds((const void *)k_fwd_cols<__VA_ARGS__>, lds_bytes_cols(P)); \
-         hipLaunchKernelGGL((k_fwd_cols<__VA_ARGS__>), grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, src, smp, zxa, zya, W.nrm_part); } while (0)
-#if ASX_HAS_PART(1)
-bool asx_launch_fwd_cols_static(const AsxDev &P, const float *src, const float *smp, float2 *zxa, float2 *zya,
-                                const AsxPeakWs &W, int npairs, hipStream_t s)
+template <class K>
+static void launch_fwd(K kernel, const AsxDev &P, int npairs, hipStream_t s, const float *src, const float *smp, float2 *zxa,
+                       float2 *zya, const AsxPeakWs &W)
 {
-    dim3 grid(col_grid_x(P.ntiles, P.logT), 2, npairs);
-#define ASX_TRY_STATIC(m1, t, nt, maxr, ...) \
-    if (P.T == (t) && P.threads_cols == (nt) && schedule_is(P.st1, m1, { __VA_ARGS__ })) { ASX_FWD_LAUNCH(maxr, Sched<m1, __VA_ARGS__>, t, nt); return true; }
-    ASX_STATIC_COLS(ASX_TRY_STATIC)
-#undef ASX_TRY_STATIC
-    return false;
+    allow_big_lds((const void *)kernel, lds_bytes_cols(P));
+    hipLaunchKernelGGL(kernel, dim3(col_grid_x(P.ntiles, P.logT), 2, npairs), dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev,
+                       src, smp, zxa, zya, W.nrm_part);
+}
+#if ASX_HAS_PART(1)
+void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, float2 *zxa, float2 *zya, const AsxPeakWs &W,
+                         int npairs, hipStream_t s)
+{
+    if (!asx_with_entry(AsxPCols{}, P.kcols, [&](auto e) {
+            launch_fwd(k_fwd_cols<e.maxr, typename decltype(e)::sched, e.t, e.nt>, P, npairs, s, src, smp, zxa, zya, W);
+        }))
+        asx_launch_fwd_cols_any(P, src, smp, zxa, zya, W, npairs, s);
 }
 #endif
 #if ASX_HAS_PART(2)
-void asx_launch_fwd_cols_generic(const AsxDev &P, const float *src, const float *smp, float2 *zxa, float2 *zya,
-                                 const AsxPeakWs &W, int npairs, hipStream_t s)
+void asx_launch_fwd_cols_any(const AsxDev &P, const float *src, const float *smp, float2 *zxa, float2 *zya, const AsxPeakWs &W,
+                             int npairs, hipStream_t s)
 {
-    dim3 grid(col_grid_x(P.ntiles, P.logT), 2, npairs);
     const int mr = max_radix(P.st1);
-    if (mr <= 10) ASX_FWD_LAUNCH(10); else if (mr <= 12) ASX_FWD_LAUNCH(12); else ASX_FWD_LAUNCH(16);
+    if (mr <= 10) launch_fwd(k_fwd_cols<10>, P, npairs, s, src, smp, zxa, zya, W);
+    else if (mr <= 12) launch_fwd(k_fwd_cols<12>, P, npairs, s, src, smp, zxa, zya, W);
+    else launch_fwd(k_fwd_cols<16>, P, npairs, s, src, smp, zxa, zya, W);
 }
 #endif
-#undef ASX_FWD_LAUNCH
 
-#define ASX_ROWS_LAUNCH(...) \
-    do { allow_big_lds((const void *)k_rows<__VA_ARGS__>, lds); \
-         hipLaunchKernelGGL((k_rows<__VA_ARGS__>), dim3(ntasks), dim3(P.threads_rows), lds, s, P.self_dev, zxa, zya, ga, P.row_tasks, P.M1, P.M2, P.M, W); } while (0)
-static size_t rows_lds_request(const AsxDev &P)
+// one task (pair, k1) per block
+template <class K>
+static void launch_rows(K kernel, const AsxDev &P, int npairs, hipStream_t s, const float2 *zxa, const float2 *zya, float2 *ga,
+                        const AsxPeakWs &W)
 {
     size_t lds = lds_bytes_rows(P);
     // diagnostic: a larger request caps the blocks per CU (occupancy sweep, tools/README.md)
     if (const char *e = getenv("ASX_DBG_ROWS_LDS")) lds = std::max(lds, (size_t)atol(e));
-    return lds;
+    allow_big_lds((const void *)kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3((P.M1 / 2 + 1) * npairs), dim3(P.threads_rows), lds, s, P.self_dev, zxa, zya, ga, P.row_tasks, P.M1,
+                       P.M2, P.M, W);
 }
 #if ASX_HAS_PART(4)
-// row lengths of the production sample lengths (plan_math.cpp's tuned table): schedule compiled in
-bool asx_launch_rows_static(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga, const AsxPeakWs &W,
-                            int npairs, hipStream_t s)
+void asx_launch_rows(const AsxDev &P, float2 *zxa, float2 *zya, float2 *ga, const AsxPeakWs &W, int npairs, hipStream_t s)
 {
-    const int ntasks = (P.M1 / 2 + 1) * npairs; // one task (pair, k1) per block
-    const size_t lds = rows_lds_request(P);
-    if (P.threads_rows == 256 && schedule_is(P.st2, 1200, { 12, 10, 10 })) { ASX_ROWS_LAUNCH(12, Sched<1200, 12, 10, 10>, 256); return true; }
-    if (P.threads_rows == 128 && schedule_is(P.st2, 480, { 10, 8, 6 })) { ASX_ROWS_LAUNCH(10, Sched<480, 10, 8, 6>, 128); return true; }
-    return false;
+    if (!asx_with_entry(AsxPRows{}, P.krows, [&](auto e) {
+            launch_rows(k_rows<e.maxr, typename decltype(e)::sched, e.nt>, P, npairs, s, zxa, zya, ga, W);
+        }))
+        asx_launch_rows_any(P, zxa, zya, ga, W, npairs, s);
 }
 #endif
 #if ASX_HAS_PART(8)
-void asx_launch_rows_generic(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga, const AsxPeakWs &W,
-                             int npairs, hipStream_t s)
+void asx_launch_rows_any(const AsxDev &P, const float2 *zxa, const float2 *zya, float2 *ga, const AsxPeakWs &W, int npairs,
+                         hipStream_t s)
 {
-    const int ntasks = (P.M1 / 2 + 1) * npairs;
-    const size_t lds = rows_lds_request(P);
     const int mr = max_radix(P.st2);
-    if (mr <= 10) ASX_ROWS_LAUNCH(10); else if (mr <= 12) ASX_ROWS_LAUNCH(12); else ASX_ROWS_LAUNCH(16);
+    if (mr <= 10) launch_rows(k_rows<10>, P, npairs, s, zxa, zya, ga, W);
+    else if (mr <= 12) launch_rows(k_rows<12>, P, npairs, s, zxa, zya, ga, W);
+    else launch_rows(k_rows<16>, P, npairs, s, zxa, zya, ga, W);
 }
 #endif
-#undef ASX_ROWS_LAUNCH
 
 // one instance of the inverse column kernel with its selection
 template <class K, class Sel>
-static void launch_inv(K kernel, const AsxDev &P, dim3 grid, hipStream_t s, const float2 *ga, const AsxPeakWs &W, float *r_out, Sel sel)
+static void launch_inv(K kernel, const AsxDev &P, int npairs, hipStream_t s, const float2 *ga, const AsxPeakWs &W, float *r_out, Sel sel)
 {
     allow_big_lds((const void *)kernel, lds_bytes_cols(P));
-    hipLaunchKernelGGL(kernel, grid, dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga, W, r_out, sel);
+    hipLaunchKernelGGL(kernel, dim3(col_grid_x(P.ntiles, P.logT), npairs), dim3(P.threads_cols), lds_bytes_cols(P), s, P.self_dev, ga,
+                       W, r_out, sel);
 }
-// (one zone capacity in the packed kernels' top-k form, whatever q.tk_zones says)
-#define ASX_INV_LAUNCH(...) \
-    asx_with_selection<ASX_TOPK_MAX - 1>(q, [&](auto sel) { launch_inv(k_inv_cols<__VA_ARGS__, decltype(sel)>, P, grid, s, ga, W, r_out, sel); })
+// q: which flavour runs (one zone capacity in the packed kernels' top-k form, whatever q.tk_zones says)
 #if ASX_HAS_PART(16)
-bool asx_launch_inv_cols_static(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                hipStream_t s, const AsxSearch &q)
-{
-    dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
-#define ASX_TRY_STATIC(m1, t, nt, maxr, ...) \
-    if (P.T == (t) && P.threads_cols == (nt) && schedule_is(P.st1, m1, { __VA_ARGS__ })) { ASX_INV_LAUNCH(maxr, Sched<m1, __VA_ARGS__>, t, nt); return true; }
-    ASX_STATIC_COLS(ASX_TRY_STATIC)
-#undef ASX_TRY_STATIC
-    return false;
-}
-#endif
-#if ASX_HAS_PART(32)
-void asx_launch_inv_cols_generic(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs,
-                                 hipStream_t s, const AsxSearch &q)
-{
-    dim3 grid(col_grid_x(P.ntiles, P.logT), npairs);
-    const int mr = max_radix(P.st1);
-    if (mr <= 10) ASX_INV_LAUNCH(10, void, 0, 0); else if (mr <= 12) ASX_INV_LAUNCH(12, void, 0, 0); else ASX_INV_LAUNCH(16, void, 0, 0);
-}
-#endif
-#undef ASX_INV_LAUNCH
-
-#if ASX_HAS_PART(64)
-size_t asx_lds_bytes_cols(const AsxDev &P) { return lds_bytes_cols(P); }
-size_t asx_lds_bytes_rows(const AsxDev &P) { return lds_bytes_rows(P); }
-
-// Block size: a multiple of 64 (<= ASX_FFT_THREADS_MAX).  First enough waves per CU to hide
-// LDS/HBM latency given how many blocks the LDS footprint admits (target >= 12 waves per CU),
-// then the size that wastes the fewest thread slots over the stages (each stage has
-// `groups * n / radix` work items); ties go to the larger block.
-int asx_pick_threads(const AsxStages &st, int groups, int min_threads, size_t lds_bytes)
-{
-    long blocks_per_cu = lds_bytes ? (long)(160 * 1024 / lds_bytes) : 8;
-    if (blocks_per_cu < 1) blocks_per_cu = 1;
-    if (blocks_per_cu > 8) blocks_per_cu = 8;
-    int want = 64 * (int)((12 + blocks_per_cu - 1) / blocks_per_cu);
-    if (want > ASX_FFT_THREADS_MAX) want = ASX_FFT_THREADS_MAX;
-    if (min_threads < want) min_threads = want;
-    long best_cost = -1;
-    int best = ASX_FFT_THREADS_MAX;
-    for (int bd = 64; bd <= ASX_FFT_THREADS_MAX; bd += 64) {
-        if (bd < min_threads) continue;
-        long cost = 0;
-        for (int i = 0; i < st.nstages; i++) {
-            const long items = (long)groups * st.nbf[i];
-            cost += (items + bd - 1) / bd * bd;
-        }
-        if (st.nstages == 0) cost = bd;
-        if (best_cost < 0 || cost <= best_cost) { best_cost = cost; best = bd; }
-    }
-    return best;
-}
-
-static bool generic_only()
-{
-    static const bool g = getenv("ASX_GENERIC") != nullptr; // diagnostic: never use the compiled-in schedules
-    return g;
-}
-
-void asx_launch_fwd_cols(const AsxDev &P, const float *src, const float *smp, float2 *zxa,
-                         float2 *zya, const AsxPeakWs &W, int npairs, hipStream_t s)
-{
-    if (P.rlayout && asx_launch_fwd_cols_r(P, src, 2 * (size_t)P.N, smp, P.N, 0, npairs, { zxa, zya, W.nrm_part, W.band }, false, s))
-        return;
-    if (generic_only() || !asx_launch_fwd_cols_static(P, src, smp, zxa, zya, W, npairs, s))
-        asx_launch_fwd_cols_generic(P, src, smp, zxa, zya, W, npairs, s);
-}
-
-void asx_launch_rows(const AsxDev &P, float2 *zxa, float2 *zya, float2 *ga,
-                     const AsxPeakWs &W, int npairs, hipStream_t s)
-{
-    if (P.rlayout && asx_launch_rows_r(P, { zxa, zya, W.nrm_part, W.band }, ga, W, npairs, s)) return;
-    if (generic_only() || !asx_launch_rows_static(P, zxa, zya, ga, W, npairs, s))
-        asx_launch_rows_generic(P, zxa, zya, ga, W, npairs, s);
-}
-
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                          const AsxSearch &q)
 {
-    if (P.rlayout && asx_launch_inv_cols_r(P, ga, W, r_out, npairs, s, q, nullptr)) return;
-    if (generic_only() || !asx_launch_inv_cols_static(P, ga, W, r_out, npairs, s, q))
-        asx_launch_inv_cols_generic(P, ga, W, r_out, npairs, s, q);
+    if (!asx_with_entry(AsxPCols{}, P.kcols, [&](auto e) {
+            asx_with_selection<ASX_TOPK_MAX - 1>(q, [&](auto sel) {
+                launch_inv(k_inv_cols<e.maxr, typename decltype(e)::sched, e.t, e.nt, decltype(sel)>, P, npairs, s, ga, W, r_out, sel);
+            });
+        }))
+        asx_launch_inv_cols_any(P, ga, W, r_out, npairs, s, q);
 }
+#endif
+#if ASX_HAS_PART(32)
+void asx_launch_inv_cols_any(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
+                             const AsxSearch &q)
+{
+    const int mr = max_radix(P.st1);
+    asx_with_selection<ASX_TOPK_MAX - 1>(q, [&](auto sel) {
+        using Sel = decltype(sel);
+        if (mr <= 10) launch_inv(k_inv_cols<10, void, 0, 0, Sel>, P, npairs, s, ga, W, r_out, sel);
+        else if (mr <= 12) launch_inv(k_inv_cols<12, void, 0, 0, Sel>, P, npairs, s, ga, W, r_out, sel);
+        else launch_inv(k_inv_cols<16, void, 0, 0, Sel>, P, npairs, s, ga, W, r_out, sel);
+    });
+}
+#endif
 
+#if ASX_HAS_PART(64)
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,
                          const AsxSearch &q)
 {

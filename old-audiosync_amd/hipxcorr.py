@@ -228,6 +228,53 @@ def planmath_describe(sample_len, split=None):
             "radix1": list(r1[: n1.value]), "radix2": list(r2[: n2.value])}
 
 
+KERNEL_ENTRY_CAP = 32   # ints per spelled entry the asx_*_kernels exports may write (asx_api.hip: ASX_KERNEL_ENTRY_CAP)
+
+
+def _kernel_entry(v, nhead, flag=None):
+    """(constants..., (radices...)) of a spelled entry, None for none; flag: the constant that is a bool"""
+    if v[0] < 0:
+        return None
+    v = list(v)
+    head = [bool(x) if i == flag else x for i, x in enumerate(v[:nhead])]
+    return (*head, tuple(v[nhead:v.index(0, nhead)]))
+
+
+def planmath_kernel_table():
+    """host-only: the four lists of csrc/kernel_table.h, each entry as planmath_kernels spells it"""
+    f = lib().asx_planmath_kernel_table
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_int, ctypes.c_int, c_intp]
+    table = {}
+    for which, (name, nhead, flag) in enumerate((("real-column cols", 3, None), ("real-column rows", 3, 1),
+                                                 ("packed cols", 4, None), ("packed rows", 3, None))):
+        table[name], buf = [], (ctypes.c_int * KERNEL_ENTRY_CAP)()
+        while f(which, len(table[name]), buf) == 0:
+            table[name].append(_kernel_entry(buf, nhead, flag))
+    return table
+
+
+def _kernel_choice(call):
+    """the dict of an AsxKernelChoice (asx_planmath_kernels / asx_plan_debug_kernels): an entry of csrc/kernel_table.h as the
+    constants its list states and the tuple of its radices, None for a run-time schedule"""
+    out, cols, rows = (ctypes.c_int * 7)(), (ctypes.c_int * KERNEL_ENTRY_CAP)(), (ctypes.c_int * KERNEL_ENTRY_CAP)()
+    if call(out, cols, rows) != 0:
+        raise AsxError(_err())
+    real, entry = bool(out[0]), _kernel_entry
+    # real-column: (M1, T, NT, radices) and (NT, two-half, n, radices); packed: (M1, T, NT, MAXR, radices) and (NT, MAXR, n, radices)
+    return {"layout": "real-column" if real else "packed", "cols": entry(cols, 3 if real else 4),
+            "rows": entry(rows, 3, 1 if real else None), "threads": (out[3], out[4]), "band_rows": out[5],
+            "prunable": bool(out[6])}
+
+
+def planmath_kernels(sample_len, split=None):
+    """host-only: the kernels the plan of sample_len would run under the current environment (no GPU needed)."""
+    f = lib().asx_planmath_kernels
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_size_t, ctypes.c_char_p, c_intp, c_intp, c_intp]
+    return _kernel_choice(lambda *a: f(sample_len, _split_arg(split), *a))
+
+
 def planmath_candidates(sample_len, max_count=16):
     """host-only: the splits the measured mode (split="measure") would time, cheapest first."""
     buf = ctypes.create_string_buffer(64 * max_count + 1)
@@ -748,6 +795,13 @@ class Plan:
         if f(self._h, int(pair), ub, ctypes.byref(best), n) != 0:
             raise AsxError("asx_plan_debug_prune failed")
         return np.frombuffer(ub, dtype=np.float32).copy(), int(best.value)
+
+    def debug_kernels(self):
+        """the kernels this plan runs, as planmath_kernels spells them: the record made when the plan was built"""
+        f = lib().asx_plan_debug_kernels
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.c_void_p, c_intp, c_intp, c_intp]
+        return _kernel_choice(lambda *a: f(self._h, *a))
 
     def debug_bank(self):
         """(source tracks, sample tracks) the plan's pool bank holds, and how many pool calls have filled it"""

@@ -712,7 +712,7 @@ print("RESULT " + json.dumps(out))
 
 def test_generic_kernels_agree_with_compiled_in_schedules(mod):
     """The launchers pick kernels with a compile-time schedule for the production lengths
-    (xcorr_kernels.hip, ASX_STATIC_COLS / asx_launch_rows); ASX_GENERIC=1 (read once per process)
+    (the lists of kernel_table.h, resolved when a plan is built); ASX_GENERIC=1 (read then)
     forces the run-time-schedule kernels every other length uses.  Same inputs, same answers,
     and both equal to the oracle."""
     import json
@@ -791,3 +791,24 @@ def test_measure_plans_pick_the_faster_placement_of_their_workspaces(mod, torch)
 def plain_split(mod, n):
     with mod.Plan(n, 1, 0) as p:
         return p.split
+
+
+@pytest.mark.parametrize("n,split,env", [(144000, None, {}), (288000, None, {}), (480000, None, {}), (960000, None, {}),
+                                         (144000, None, {"ASX_LAYOUT": "packed"}), (1000, "25x40x8", {})])
+def test_a_plan_runs_the_kernels_the_planner_names(mod, monkeypatch, n, split, env):
+    """The kernels of a plan are chosen once, when it is built, from csrc/kernel_table.h: the live plan holds the record the
+    host-only planner states for the same length and environment (tests/test_plan_math.py pins which that is), its layout and
+    block sizes are the record's, and it correlates with them.  The four real-column lengths reach every entry of both
+    real-column lists."""
+    for k in ("ASX_LAYOUT", "ASX_GENERIC", "ASX_THREADS_COLS", "ASX_THREADS_ROWS", "ASX_STAGE_ORDER"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    want = mod.planmath_kernels(n, split)
+    assert want["layout"] == ("packed" if env or split else "real-column")
+    src, smp, true_lag = oracle.synth_pair(41, 0, n, 0)
+    with mod.Plan(n, max_batch=1, split=split) as plan:
+        assert plan.debug_kernels() == want
+        assert plan.layout == want["layout"] and plan.threads == want["threads"]
+        lag, coef, ret = plan.xcorr_batch_f32(src[None], smp[None])
+    assert int(ret[0]) == 0 and int(lag[0]) == true_lag

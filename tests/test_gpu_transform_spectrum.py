@@ -123,7 +123,7 @@ def test_forced_splits_spectrum_bin_by_bin(mod, torch, monkeypatch):
     assert set(layouts.values()) == {"real-column", "packed"}, layouts
 
 
-# ---- the run-time-schedule kernels ($ASX_GENERIC=1, read once per process: one child process) ------------------------------
+# ---- the run-time-schedule kernels ($ASX_GENERIC=1, read when a plan is created; here in a child process) ------------------------------
 
 _GENERIC_SPECTRUM = r"""
 import json, sys

@@ -150,3 +150,103 @@ def test_spectral_pearson_algebra_matches_the_reference_reduction():
             continue
         want = oracle.pearson_coefficient(a.copy(), b.copy())
         assert abs(coef - want) < 1e-10, (peak, mode, coef, want)
+
+
+# ---- which compiled-in kernels a plan runs (csrc/kernel_table.h, AsxKernelChoice) ----------------
+# The environment is read when a plan is built, so each case sets it for itself.
+
+KERNEL_ENV = ("ASX_LAYOUT", "ASX_GENERIC", "ASX_THREADS_COLS", "ASX_THREADS_ROWS", "ASX_STAGE_ORDER")
+
+
+def kernels(monkeypatch, n, split=None, **env):
+    for k in KERNEL_ENV:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    return asx().planmath_kernels(n, split)
+
+
+def rcol_rows_per_group(m1, nt, t):
+    """row pairs one lane group of k_fwd_cols_r loads: the block's nt / (t / 4) groups share the m1 rows"""
+    groups = nt // (t // 4)
+    return (m1 + groups - 1) // groups
+
+
+RCOL = {300: (300, 16, 256, (10, 6, 5)), 400: (400, 16, 512, (10, 8, 5)), 600: (600, 16, 512, (10, 10, 6))}
+RROW = {480: (64, False, 480, (10, 8, 6)), 1200: (128, False, 1200, (12, 10, 10)), 2400: (128, True, 1200, (12, 10, 10))}
+REAL_COLUMN = {144000: (300, 480), 288000: (600, 480), 480000: (400, 1200), 720000: (600, 1200), 960000: (400, 2400),
+               1440000: (600, 2400)}
+# ASX_LAYOUT=packed: what the parent of the commit that introduced the table matched at run time (its ASX_STATIC_COLS chain and the
+# two hand-written row schedules, with asx_pick_threads' block sizes), evaluated by a host program on that commit's sources
+PCOL = {300: (300, 16, 256, 10, (10, 6, 5)), 400: (400, 16, 320, 10, (10, 8, 5)), 600: (600, 16, 512, 10, (10, 10, 6)),
+        800: (800, 8, 320, 10, (10, 10, 8)), 1200: (1200, 8, 512, 12, (12, 10, 10))}
+PROW = {480: (128, 10, 480, (10, 8, 6)), 1200: (256, 12, 1200, (12, 10, 10))}
+PACKED = {144000: (300, 480, (256, 128)), 288000: (600, 480, (512, 128)), 480000: (400, 1200, (320, 256)),
+          720000: (600, 1200, (512, 256)), 960000: (800, 1200, (320, 256)), 1440000: (1200, 1200, (512, 256))}
+
+
+@pytest.mark.parametrize("n", PRODUCTION)
+def test_production_lengths_run_the_real_column_kernels(monkeypatch, n):
+    k = kernels(monkeypatch, n)
+    m1, m2 = REAL_COLUMN[n]
+    assert k["layout"] == "real-column"
+    assert k["cols"] == RCOL[m1] and k["rows"] == RROW[m2]
+    assert k["prunable"] is True
+    _, t, nt, _ = RCOL[m1]
+    assert k["band_rows"] == 2 * rcol_rows_per_group(m1, nt, t)
+
+
+@pytest.mark.parametrize("n", PRODUCTION)
+def test_packed_layout_runs_the_compiled_in_packed_schedules(monkeypatch, n):
+    k = kernels(monkeypatch, n, ASX_LAYOUT="packed")
+    m1, m2, threads = PACKED[n]
+    assert k == {"layout": "packed", "cols": PCOL[m1], "rows": PROW[m2], "threads": threads, "band_rows": 0, "prunable": False}
+    assert k["cols"][2] == threads[0] and k["rows"][0] == threads[1]     # a compiled-in block size is the plan's block size
+
+
+@pytest.mark.parametrize("n", PRODUCTION)
+def test_generic_runs_no_compiled_in_schedule(monkeypatch, n):
+    k = kernels(monkeypatch, n, ASX_GENERIC="1")
+    assert (k["layout"], k["cols"], k["rows"], k["prunable"]) == ("packed", None, None, False)
+    assert k["threads"] == PACKED[n][2]
+
+
+def test_a_length_outside_the_table_runs_the_run_time_schedules(monkeypatch):
+    k = kernels(monkeypatch, 1000, "25x40x8")
+    assert (k["layout"], k["cols"], k["rows"], k["band_rows"], k["prunable"]) == ("packed", None, None, 0, False)
+
+
+def test_a_split_without_a_column_pair_is_refused_as_before(monkeypatch):
+    with pytest.raises(asx().AsxError, match="bad ASX_SPLIT override"):
+        kernels(monkeypatch, 144000, "1x144000x1")
+    # one the planner accepts but no table holds: the packed kernels on run-time schedules
+    k = kernels(monkeypatch, 144000, "150x960x16")
+    assert (k["layout"], k["cols"], k["rows"]) == ("packed", None, None)
+
+
+def test_a_block_size_override_leaves_the_compiled_in_packed_schedule(monkeypatch):
+    """the packed instances are compiled for one block size: another one runs the run-time-schedule kernel of that pass alone"""
+    k = kernels(monkeypatch, 144000, ASX_LAYOUT="packed", ASX_THREADS_COLS="512")
+    assert k["cols"] is None and k["rows"] == PROW[480] and k["threads"] == (512, 128)
+    k = kernels(monkeypatch, 144000, ASX_LAYOUT="packed", ASX_THREADS_ROWS="256")
+    assert k["cols"] == PCOL[300] and k["rows"] is None and k["threads"] == (256, 256)
+
+
+def test_every_entry_of_the_kernel_table_is_reached(monkeypatch):
+    """an entry no plan resolves to is a set of kernels built for nothing: the lengths and environments above reach all of them.
+    The lists are read from the library (csrc/kernel_table.h), so an entry added there is held to this too."""
+    table = asx().planmath_kernel_table()
+    assert table == {"real-column cols": [RCOL[600], RCOL[400], RCOL[300]], "real-column rows": [RROW[1200], RROW[2400], RROW[480]],
+                     "packed cols": [PCOL[1200], PCOL[800], PCOL[600], PCOL[400], PCOL[300]], "packed rows": [PROW[1200], PROW[480]]}
+    seen = {"real-column": (set(), set()), "packed": (set(), set())}
+    for env in ({}, {"ASX_LAYOUT": "packed"}, {"ASX_GENERIC": "1"}):
+        for n in PRODUCTION:
+            k = kernels(monkeypatch, n, **env)
+            seen[k["layout"]][0].add(k["cols"])
+            seen[k["layout"]][1].add(k["rows"])
+    for layout in seen:
+        for which, reached in zip(("cols", "rows"), seen[layout]):
+            unreached = set(table["%s %s" % (layout, which)]) - reached
+            assert not unreached, "no plan runs %s %s %s" % (layout, which, sorted(unreached))
+    assert seen["real-column"] == (set(RCOL.values()), set(RROW.values()))
+    assert seen["packed"] == (set(PCOL.values()) | {None}, set(PROW.values()) | {None})

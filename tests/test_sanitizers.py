@@ -76,3 +76,10 @@ def test_float32_exactness_check_of_the_double_abi(san, binary):
     forked child, where the pool's threads do not exist and the caller converts every chunk itself"""
     out = run([os.path.join(san, binary)] + (["nofork"] if binary.endswith("tsan") else []))
     assert ", 0 failures" in out and (binary.endswith("tsan") or out.startswith("50 cases"))
+
+
+def test_kernel_choice_of_the_host_plans_under_asan(san):
+    """csrc/plan_math.cpp -- the host plans of the production lengths and of lengths outside the table, and the kernels they
+    resolve to from csrc/kernel_table.h, under the default environment, ASX_LAYOUT=packed and ASX_GENERIC=1"""
+    out = run([os.path.join(san, "choice_asan")])
+    assert ", 0 failures" in out and not out.startswith("0 cases")
