@@ -4,6 +4,7 @@
 #include "audiosync/xcorr_hip.h"
 
 #include "asx_internal.h"
+#include "dev_mem.h"
 #include "plan_math.h"
 #include "shard_driver.h"
 #include "host_narrow.h"
@@ -65,6 +66,11 @@ extern "C" int asx_device_count(void)
     return n;
 }
 
+struct EventPair { // two events that go with their scope
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~EventPair() { for (hipEvent_t e : { e0, e1 }) if (e) (void)hipEventDestroy(e); }
+};
+
 struct DevGuard {
     int prev = -1;
     bool ok = false;
@@ -90,6 +96,14 @@ extern "C" int asx_current_device(void)
     return d;
 }
 
+// csrc/dev_mem.h bound to HIP: every set of device buffers below is an AsxMemSet over this pair.  A failed take leaves its error
+// in g_take_err for the caller's message and no sticky error behind.
+static thread_local hipError_t g_take_err = hipSuccess;
+static const AsxMemOps hip_mem = {
+    [](void **out, size_t bytes) { return (g_take_err = hipMalloc(out, bytes)) == hipSuccess ? 0 : ((void)hipGetLastError(), -1); },
+    [](void *ptr) { (void)hipFree(ptr); }
+};
+
 // ---------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------
@@ -99,12 +113,12 @@ struct asx_plan {
     AsxDev dev{};
     size_t group = 1;          // pairs per launch group
     size_t stamp_blocks = 0;   // diagnostic stamp buffer: blocks x 8 slots
-    size_t ws_bytes = 0;
     hipStream_t stream = nullptr;
     std::mutex lock;
 
-    // device tables
-    std::vector<void *> allocs; // everything to hipFree on destroy
+    // Who owns the plan's device memory (asx_plan_workspace_bytes: all but the bank's).  mem: what plan_init takes and, once created,
+    // the lazy sets (big, bslot, st, st64: whole or absent); cxy0: lane 0's C_x / C_y, which tune_placement may replace; bank.mem.
+    AsxMemSet mem{ hip_mem }, cxy0{ hip_mem };
     // "Lanes": each owns the workspaces of one launch group and a stream.  With two lanes
     // (ASX_LANES=2) consecutive groups of a batch alternate lanes so that kernels of different
     // groups may overlap; measured gain 0..4 %, less than simply doubling the group, so one
@@ -141,9 +155,10 @@ struct asx_plan {
     // Bank of asx_xcorr_pool_f32_dev (real-column plans; allocated at the first pool call, grown when a call names more tracks): the
     // forward column pass of every track of a call's two pools -- source a at row a of cx, sample b at row b of cy, their norm partials
     // and band sums in the AsxPeakWs layout of "pair" a, operand 0, and "pair" b, operand 1 -- written once per call before the launch
-    // groups, read by slot (k_pool_resolve, k_rows_rl).  Its own allocations: not part of asx_plan_workspace_bytes.
+    // groups, read by slot (k_pool_resolve, k_rows_rl).  Its own set, replaced wholesale on growth: not part of asx_plan_workspace_bytes.
     struct Bank {
         AsxSpectra c{};
+        AsxMemSet mem{ hip_mem };
         size_t nsrc = 0, nsmp = 0;      // capacity in tracks
         unsigned long long fills = 0;   // pool calls that filled it (diagnostic: asx_plan_debug_bank)
     } bank;
@@ -165,12 +180,12 @@ struct asx_plan {
     bool tune_placement = false, placement_done = false;
     double placement_ms[2] = { 0.0, 0.0 };
     int placement_kept = -1;
-    // staging for the host-pointer entry points (lazy)
-    float *st_src = nullptr, *st_smp = nullptr;
-    int64_t *st_lag = nullptr;
-    double *st_coef = nullptr;
-    int32_t *st_ret = nullptr;
-    double *st_src64 = nullptr, *st_smp64 = nullptr;
+    // staging for the host-pointer entry points (lazy): a group's float32 inputs and results, one pair's float64 inputs
+    struct Staging {
+        float *src = nullptr, *smp = nullptr;
+        int64_t *lag = nullptr; double *coef = nullptr; int32_t *ret = nullptr;
+    } st;
+    struct Staging64 { double *src = nullptr, *smp = nullptr; } st64;
     float *pin32 = nullptr;            // page-locked staging of the double ABI's narrowed frames (3N floats, lazy)
     unsigned long long narrowed = 0;   // asx_xcorr_f64 calls whose frames crossed PCIe as float32
 
@@ -195,25 +210,26 @@ struct PlanCall {
           s(stream ? (hipStream_t)stream : p->stream) {}
 };
 
-template <typename T> static int dev_alloc(asx_plan *p, T **out, size_t count)
+template <typename T> static int dev_alloc(AsxMemSet &m, T **out, size_t count)
 {
-    void *ptr = nullptr;
-    size_t bytes = count * sizeof(T);
-    if (bytes == 0) bytes = sizeof(T);
-    HIP_TRY(hipMalloc(&ptr, bytes));
-    p->allocs.push_back(ptr);
-    p->ws_bytes += bytes;
-    *out = static_cast<T *>(ptr);
-    return 0;
+    return m.take(out, count) ? fail("hipMalloc(&ptr, bytes) failed: %s (%s:%d)", hipGetErrorString(g_take_err), __FILE__, __LINE__) : 0;
 }
 
-template <typename T> static int dev_upload(asx_plan *p, const T **out, const std::vector<T> &v)
+template <typename T> static int dev_upload(AsxMemSet &m, const T **out, const std::vector<T> &v)
 {
     T *d = nullptr;
-    if (dev_alloc(p, &d, v.size()) != 0) return -1;
+    if (dev_alloc(m, &d, v.size()) != 0) return -1;
     HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     *out = d;
     return 0;
+}
+
+// An AsxSpectra as a set of passes for nsrc source and nsmp sample tracks, its pieces taken from m: the plan's broadcast slot
+// (1, 1) and its bank.  -1 when a piece cannot be had; the message is the caller's.
+static int take_spectra(const AsxDev &P, AsxMemSet &m, AsxSpectra &c, size_t nsrc, size_t nsmp)
+{
+    const size_t pitch = asx_spectrum_len(P), na = std::max(nsrc, nsmp), nt = P.ntiles, nb = nt * (size_t)P.nbands;
+    return m.take(&c.cx, nsrc * pitch) || m.take(&c.cy, nsmp * pitch) || m.take(&c.nrm, na * 2 * nt) || (nb && m.take(&c.band, na * 2 * nb)) ? -1 : 0;
 }
 
 static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
@@ -222,6 +238,7 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
     if (!err.empty()) return fail("plan for sample_len=%zu: %s", N, err.c_str());
     const AsxHostPlan &h = p->host;
     AsxDev &d = p->dev;
+    AsxMemSet &m = p->mem;
     d.N = (uint32_t)N;
     d.F = h.F; d.M = h.M; d.M1 = h.M1; d.M2 = h.M2; d.T = h.T; d.logT = h.logT; d.ntiles = h.ntiles;
     d.src_valid = h.src_valid;
@@ -241,15 +258,15 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
     d.band_rows = k.band_rows;
     d.nbands = k.band_rows ? 2 * h.M1 / k.band_rows : 0;
     p->prunable = k.prunable;
-    if (dev_upload(p, &d.tw1, h.tw1) || dev_upload(p, &d.tw2, h.tw2) || dev_upload(p, &d.tw2s, h.tw2s) || dev_upload(p, &d.tw_lo, h.tw_lo) ||
-        dev_upload(p, &d.tw_hi, h.tw_hi) ||
-        dev_upload(p, &d.k1_of_pos1, h.k1_of_pos1) || dev_upload(p, &d.pos1_of_k1, h.pos1_of_k1) ||
-        dev_upload(p, &d.pos2_of_k2, h.pos2_of_k2) || dev_upload(p, &d.row_tasks, h.row_tasks))
+    if (dev_upload(m, &d.tw1, h.tw1) || dev_upload(m, &d.tw2, h.tw2) || dev_upload(m, &d.tw2s, h.tw2s) || dev_upload(m, &d.tw_lo, h.tw_lo) ||
+        dev_upload(m, &d.tw_hi, h.tw_hi) ||
+        dev_upload(m, &d.k1_of_pos1, h.k1_of_pos1) || dev_upload(m, &d.pos1_of_k1, h.pos1_of_k1) ||
+        dev_upload(m, &d.pos2_of_k2, h.pos2_of_k2) || dev_upload(m, &d.row_tasks, h.row_tasks))
         return -1;
 
     d.col_pairs = nullptr;
     d.col_tw = nullptr;
-    if (k.rlayout && (dev_upload(p, &d.col_pairs, h.col_pairs) || dev_upload(p, &d.col_tw, h.col_tw))) return -1;
+    if (k.rlayout && (dev_upload(m, &d.col_pairs, h.col_pairs) || dev_upload(m, &d.col_tw, h.col_tw))) return -1;
     // group size: keep the three inter-kernel intermediates (24*M bytes per pair) of one
     // group around the size of the 256 MiB Infinity Cache so the next kernel re-reads them on die
     size_t ws_mb = 4096;
@@ -269,17 +286,17 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
     for (int l = 0; l < p->nlanes; l++) {
         asx_plan::Lane &ln = p->lanes[l];
         ln.pk.cap = (uint32_t)cap;
-        // (M1 + 1) rows per pair and spectrum: the real-column kernels (rlayout.hip) keep rows k1 = 0 .. M1
-        const size_t mz = ((size_t)h.M1 + 1) * (size_t)h.M2;
-        if (dev_alloc(p, &ln.zxa, g * mz) || dev_alloc(p, &ln.zya, g * mz) || dev_alloc(p, &ln.ga, g * mz) ||
-            dev_alloc(p, &ln.pk.nrm_part, g * 2 * (size_t)h.ntiles) || dev_alloc(p, &ln.pk.bound2, g) ||
-            dev_alloc(p, &ln.pk.pairmax, g) || dev_alloc(p, &ln.pk.cand_n, g) ||
-            dev_alloc(p, &ln.pk.cand, g * cap) || dev_alloc(p, &ln.pk.refine_n, g) ||
-            dev_alloc(p, &ln.pk.refine_idx, g * cap) || dev_alloc(p, &ln.pk.refine_val, g * cap) ||
-            dev_alloc(p, &ln.pk.overflows, 1) ||
-            dev_alloc(p, &ln.seg, g) || dev_alloc(p, &ln.psums, g * (size_t)asx_pearson_blocks((uint32_t)N) * 6) ||
-            dev_alloc(p, &ln.tk.pairs, g) || dev_alloc(p, &ln.tk.lag, g) || dev_alloc(p, &ln.tk.coef, g) || dev_alloc(p, &ln.tk.ret, g) ||
-            dev_alloc(p, &ln.tk.sink, 1) || dev_alloc(p, &ln.pool, g))
+        const size_t mz = asx_spectrum_len(d);
+        AsxMemSet &cxy = l == 0 ? p->cxy0 : m;
+        if (dev_alloc(cxy, &ln.zxa, g * mz) || dev_alloc(cxy, &ln.zya, g * mz) || dev_alloc(m, &ln.ga, g * mz) ||
+            dev_alloc(m, &ln.pk.nrm_part, g * 2 * (size_t)h.ntiles) || dev_alloc(m, &ln.pk.bound2, g) ||
+            dev_alloc(m, &ln.pk.pairmax, g) || dev_alloc(m, &ln.pk.cand_n, g) ||
+            dev_alloc(m, &ln.pk.cand, g * cap) || dev_alloc(m, &ln.pk.refine_n, g) ||
+            dev_alloc(m, &ln.pk.refine_idx, g * cap) || dev_alloc(m, &ln.pk.refine_val, g * cap) ||
+            dev_alloc(m, &ln.pk.overflows, 1) ||
+            dev_alloc(m, &ln.seg, g) || dev_alloc(m, &ln.psums, g * (size_t)asx_pearson_blocks((uint32_t)N) * 6) ||
+            dev_alloc(m, &ln.tk.pairs, g) || dev_alloc(m, &ln.tk.lag, g) || dev_alloc(m, &ln.tk.coef, g) || dev_alloc(m, &ln.tk.ret, g) ||
+            dev_alloc(m, &ln.tk.sink, 1) || dev_alloc(m, &ln.pool, g))
             return -1;
         HIP_TRY(hipMemset(ln.pk.overflows, 0, sizeof(unsigned long long)));
         ln.pk.band = nullptr; ln.pk.tile_peak = nullptr;
@@ -288,11 +305,11 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
             // per inverse tile, the work list and the window sums of the group's pairs
             const size_t nbands = (size_t)d.nbands;
             if (!p->mode_count) {
-                if (dev_alloc(p, &p->mode_count, ASX_PM_NMODES)) return -1;
+                if (dev_alloc(m, &p->mode_count, ASX_PM_NMODES)) return -1;
                 HIP_TRY(hipMemset(p->mode_count, 0, ASX_PM_NMODES * sizeof(unsigned long long)));
             }
-            if (dev_alloc(p, &ln.pk.band, g * 2 * nbands * (size_t)h.ntiles) || dev_alloc(p, &ln.pk.tile_peak, g * (size_t)(h.M2 / h.T)) ||
-                dev_alloc(p, &ln.spec.part, g * ASX_PREP_BLOCKS_MAX * 4) || dev_alloc(p, &ln.spec.hdr, g * ASX_SPEC_HDR))
+            if (dev_alloc(m, &ln.pk.band, g * 2 * nbands * (size_t)h.ntiles) || dev_alloc(m, &ln.pk.tile_peak, g * (size_t)(h.M2 / h.T)) ||
+                dev_alloc(m, &ln.spec.part, g * ASX_PREP_BLOCKS_MAX * 4) || dev_alloc(m, &ln.spec.hdr, g * ASX_SPEC_HDR))
                 return -1;
             ln.spec.mode_count = p->mode_count;
             ln.spec.tol = 1e-5;
@@ -300,12 +317,12 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
         if (p->prunable) {
             // pruned inverse pass: 4 (M1 + 1) ntiles bytes per pair, about 1 % of Q; the group size does not depend on it
             if (!p->prune_stats) {
-                if (dev_alloc(p, &p->prune_stats, 2)) return -1;
+                if (dev_alloc(m, &p->prune_stats, 2)) return -1;
                 HIP_TRY(hipMemset(p->prune_stats, 0, 2 * sizeof(unsigned long long)));
             }
-            if (dev_alloc(p, &ln.prune.eng, g * ((size_t)h.M1 + 1) * (size_t)h.ntiles) || dev_alloc(p, &ln.prune.ub, g * (size_t)h.ntiles) ||
-                dev_alloc(p, &ln.prune.best, g) || dev_alloc(p, &ln.prune.skip, g * (size_t)h.ntiles) ||
-                dev_alloc(p, &ln.prune.part, g * 1024) || dev_alloc(p, &ln.prune.ticket, g))
+            if (dev_alloc(m, &ln.prune.eng, g * ((size_t)h.M1 + 1) * (size_t)h.ntiles) || dev_alloc(m, &ln.prune.ub, g * (size_t)h.ntiles) ||
+                dev_alloc(m, &ln.prune.best, g) || dev_alloc(m, &ln.prune.skip, g * (size_t)h.ntiles) ||
+                dev_alloc(m, &ln.prune.part, g * 1024) || dev_alloc(m, &ln.prune.ticket, g))
                 return -1;
             // part: [slices][tiles rounded up to 32] of 1024 doubles per pair whatever the length; every slot a launch reads it has
             // written itself, the zeroing is for a defined first state only.  The tickets must be zero: k_tile_bounds counts on it
@@ -320,7 +337,7 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
     // the list of overflowed pairs is one per plan (the lanes append with atomics); a "window" of a device-resident
     // batch between two looks at it never holds more pairs than this
     p->over_cap = std::max<size_t>(g * (size_t)p->nlanes, 1024);
-    if (dev_alloc(p, &p->over_list, p->over_cap) || dev_alloc(p, &p->over_n, 1)) return -1;
+    if (dev_alloc(m, &p->over_list, p->over_cap) || dev_alloc(m, &p->over_n, 1)) return -1;
     HIP_TRY(hipMemset(p->over_n, 0, sizeof(uint32_t)));
     uint32_t *d_over_host = nullptr;
     {
@@ -350,14 +367,14 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
     if (const char *e = getenv("ASX_STAMPS")) {
         unsigned long long *st = nullptr;
         p->stamp_blocks = g * (size_t)std::max(h.M1 + 1, 2 * h.ntiles);
-        if (dev_alloc(p, &st, p->stamp_blocks * 8)) return -1;
+        if (dev_alloc(m, &st, p->stamp_blocks * 8)) return -1;
         HIP_TRY(hipMemset(st, 0, p->stamp_blocks * 8 * sizeof(unsigned long long)));
         d.stamps = st;
         d.stamp_kernel = !strcmp(e, "fwd") ? 1 : !strcmp(e, "inv") ? 2 : 0;
     }
     {
         AsxDev *dcopy = nullptr;
-        if (dev_alloc(p, &dcopy, 1)) return -1;
+        if (dev_alloc(m, &dcopy, 1)) return -1;
         d.self_dev = dcopy;
         HIP_TRY(hipMemcpy(dcopy, &d, sizeof(AsxDev), hipMemcpyHostToDevice));
     }
@@ -387,36 +404,29 @@ static std::string measure_best_split(size_t N, size_t max_batch, int device)
     probe = std::max<size_t>(probe, 4);
     probe = std::min<size_t>(probe, 1024);
     probe = std::max<size_t>(1, std::min(probe, max_batch));
-    float *d_src = nullptr, *d_smp = nullptr;
-    int64_t *d_lag = nullptr;
-    double *d_coef = nullptr;
-    int32_t *d_ret = nullptr;
+    AsxMemSet m(hip_mem); // the probe's pairs and results
+    asx_plan::Staging d;
     std::string best;
     float best_ms = 0.f;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipMalloc(&d_src, probe * 2 * N * sizeof(float)) == hipSuccess && hipMalloc(&d_smp, probe * N * sizeof(float)) == hipSuccess &&
-        hipMalloc(&d_lag, probe * sizeof(int64_t)) == hipSuccess && hipMalloc(&d_coef, probe * sizeof(double)) == hipSuccess &&
-        hipMalloc(&d_ret, probe * sizeof(int32_t)) == hipSuccess && hipEventCreate(&e0) == hipSuccess &&
-        hipEventCreate(&e1) == hipSuccess &&
-        asx_synth_pairs_dev(12345, 0, probe, N, 1, d_src, d_smp, nullptr, nullptr) == 0 && hipDeviceSynchronize() == hipSuccess) {
+    EventPair ev;
+    if (!m.take(&d.src, probe * 2 * N) && !m.take(&d.smp, probe * N) && !m.take(&d.lag, probe) && !m.take(&d.coef, probe) &&
+        !m.take(&d.ret, probe) && hipEventCreate(&ev.e0) == hipSuccess && hipEventCreate(&ev.e1) == hipSuccess &&
+        asx_synth_pairs_dev(12345, 0, probe, N, 1, d.src, d.smp, nullptr, nullptr) == 0 && hipDeviceSynchronize() == hipSuccess) {
         for (const std::string &c : cands) {
             asx_plan *p = asx_plan_create_ex(N, probe, device, c.c_str());
             if (!p) continue;
-            bool ok = asx_xcorr_batch_f32_dev(p, d_src, d_smp, probe, d_lag, d_coef, d_ret, nullptr) == 0; // warm-up
+            bool ok = asx_xcorr_batch_f32_dev(p, d.src, d.smp, probe, d.lag, d.coef, d.ret, nullptr) == 0; // warm-up
             float ms = 0.f;
             if (ok) {
-                ok = hipEventRecord(e0, p->stream) == hipSuccess;
-                for (int r = 0; r < 2 && ok; r++) ok = asx_xcorr_batch_f32_dev(p, d_src, d_smp, probe, d_lag, d_coef, d_ret, nullptr) == 0;
-                ok = ok && hipEventRecord(e1, p->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-                     hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+                ok = hipEventRecord(ev.e0, p->stream) == hipSuccess;
+                for (int r = 0; r < 2 && ok; r++) ok = asx_xcorr_batch_f32_dev(p, d.src, d.smp, probe, d.lag, d.coef, d.ret, nullptr) == 0;
+                ok = ok && hipEventRecord(ev.e1, p->stream) == hipSuccess && hipEventSynchronize(ev.e1) == hipSuccess &&
+                     hipEventElapsedTime(&ms, ev.e0, ev.e1) == hipSuccess;
             }
             asx_plan_destroy(p);
             if (ok && (best.empty() || ms < best_ms)) { best = c; best_ms = ms; }
         }
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(d_src); (void)hipFree(d_smp); (void)hipFree(d_lag); (void)hipFree(d_coef); (void)hipFree(d_ret);
     (void)hipGetLastError();
     return best;
 }
@@ -476,9 +486,7 @@ extern "C" asx_plan *asx_plan_create(size_t sample_len, size_t max_batch, int de
 extern "C" void asx_plan_destroy(asx_plan *p)
 {
     if (!p) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(p->device);
+    DevGuard dg(p->device); // (until the plan's sets have given their device memory back)
     if (p->stream) { (void)hipStreamSynchronize(p->stream); (void)hipStreamDestroy(p->stream); }
     for (auto &ln : p->lanes) {
         if (ln.stream) { (void)hipStreamSynchronize(ln.stream); (void)hipStreamDestroy(ln.stream); }
@@ -487,19 +495,15 @@ extern "C" void asx_plan_destroy(asx_plan *p)
     if (p->fork) (void)hipEventDestroy(p->fork);
     for (auto &ring : p->evr)
         for (hipEvent_t ev : ring) (void)hipEventDestroy(ev);
-    for (void *a : p->allocs) (void)hipFree(a);
-    for (void *a : { (void *)p->bank.c.cx, (void *)p->bank.c.cy, (void *)p->bank.c.nrm, (void *)p->bank.c.band })
-        if (a) (void)hipFree(a);
     if (p->pin32) (void)hipHostFree(p->pin32);
     if (p->h_over_n) (void)hipHostFree((void *)p->h_over_n);
-    (void)hipSetDevice(prev);
     delete p;
 }
 
 extern "C" size_t asx_plan_sample_len(const asx_plan *p) { return p ? p->host.N : 0; }
 extern "C" size_t asx_plan_fft_len(const asx_plan *p) { return p ? p->host.F : 0; }
 extern "C" size_t asx_plan_group(const asx_plan *p) { return p ? p->group : 0; }
-extern "C" size_t asx_plan_workspace_bytes(const asx_plan *p) { return p ? p->ws_bytes : 0; }
+extern "C" size_t asx_plan_workspace_bytes(const asx_plan *p) { return p ? p->mem.bytes() + p->cxy0.bytes() : 0; }
 // diagnostic: copy back the k_rows phase clocks of the last group (needs ASX_STAMPS env + -DASX_STAMPS build)
 extern "C" long asx_plan_debug_stamps(asx_plan *p, unsigned long long *out, size_t cap)
 {
@@ -955,18 +959,16 @@ static int second_look(asx_plan *p, const Pairs<TIn> &xi, const Results &yi, hip
     const AsxDev &P = p->dev;
     const size_t N = p->host.N;
     asx_plan::BigPeak &B = p->big;
-    if (!B.cand) {
-        // into a local first: a failed allocation must not leave half a set behind for the next call
-        // (what was allocated stays on the plan's list and is freed with the plan)
-        asx_plan::BigPeak T;
-        T.cap = 2 * N;
-        if (dev_alloc(p, &T.cand, T.cap) || dev_alloc(p, &T.refine_idx, T.cap) || dev_alloc(p, &T.refine_val, T.cap) ||
-            dev_alloc(p, &T.cand_n, 1) || dev_alloc(p, &T.refine_n, 1) || dev_alloc(p, &T.overflows, 1) ||
-            dev_alloc(p, &T.src_dc, 2 * N) || dev_alloc(p, &T.stats, ASX_DC_STATS_DOUBLES))
-            return -1;
-        HIP_TRY(hipMemsetAsync(T.overflows, 0, sizeof(unsigned long long), s));
-        B = T;
-    }
+    if (!B.cand && asx_mem_whole(p->mem, B, [&](AsxMemSet &m, asx_plan::BigPeak &T) {
+            T.cap = 2 * N;
+            if (dev_alloc(m, &T.cand, T.cap) || dev_alloc(m, &T.refine_idx, T.cap) || dev_alloc(m, &T.refine_val, T.cap) ||
+                dev_alloc(m, &T.cand_n, 1) || dev_alloc(m, &T.refine_n, 1) || dev_alloc(m, &T.overflows, 1) ||
+                dev_alloc(m, &T.src_dc, 2 * N) || dev_alloc(m, &T.stats, ASX_DC_STATS_DOUBLES))
+                return -1;
+            HIP_TRY(hipMemsetAsync(T.overflows, 0, sizeof(unsigned long long), s));
+            return 0;
+        }))
+        return -1;
     AsxPeakWs K = p->lanes[0].pk;         // slot 0's norms, bound and running maximum (k_rows recomputes all three) ...
     K.cand_n = B.cand_n; K.cand = B.cand; // ... with lists for all 2N lags: this look cannot overflow
     K.refine_n = B.refine_n; K.refine_idx = B.refine_idx; K.refine_val = B.refine_val;
@@ -1063,54 +1065,33 @@ static int tune_placement(asx_plan *p, const float *d_src, const float *d_smp, s
     p->placement_done = true;
     const AsxDev &P = p->dev;
     asx_plan::Lane &W = p->lanes[0];
-    const size_t mz = ((size_t)p->host.M1 + 1) * (size_t)p->host.M2 * p->group;
-    // whatever leaves this function early gives back the second set and the events (a failing HIP call used to leak them)
-    struct Scratch {
-        float2 *alt[2] = { nullptr, nullptr };
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        bool keep_alt = false;
-        ~Scratch()
-        {
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-            if (!keep_alt) for (float2 *a : alt) if (a) (void)hipFree(a);
-        }
-    } sc;
-    float2 *(&alt)[2] = sc.alt;
-    if (hipMalloc((void **)&alt[0], mz * sizeof(float2)) != hipSuccess || hipMalloc((void **)&alt[1], mz * sizeof(float2)) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0; // no room for a second set: keep what there is
-    }
-    hipEvent_t &e0 = sc.e0, &e1 = sc.e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    const size_t mz = asx_spectrum_len(P) * p->group;
+    // whatever leaves this function gives back the set that lost and the events (a failing HIP call used to leak them)
+    AsxMemSet second(hip_mem);
+    float2 *set[2][2] = { { W.zxa, W.zya }, { nullptr, nullptr } };
+    if (second.take(&set[1][0], mz) || second.take(&set[1][1], mz)) return 0; // no room for a second set: keep what there is
+    EventPair ev;
+    HIP_TRY(hipEventCreate(&ev.e0));
+    HIP_TRY(hipEventCreate(&ev.e1));
     AsxPeakWs tk = W.pk;
     tk.band = nullptr; tk.tile_peak = nullptr;
-    float2 *set[2][2] = { { W.zxa, W.zya }, { alt[0], alt[1] } };
     for (int k = 0; k < 2; k++) {
         float best = 0.f;
         for (int r = 0; r < 4; r++) { // the first launch warms the set up; the fastest of the other three counts
-            HIP_TRY(hipEventRecord(e0, s));
+            HIP_TRY(hipEventRecord(ev.e0, s));
             if (P.rlayout) asx_launch_fwd_cols_r(P, d_src, 2 * (size_t)P.N, d_smp, P.N, 0, (int)g, { set[k][0], set[k][1], tk.nrm_part, tk.band }, false, s);
             else asx_launch_fwd_cols(P, d_src, d_smp, set[k][0], set[k][1], tk, (int)g, s);
-            HIP_TRY(hipEventRecord(e1, s));
-            HIP_TRY(hipEventSynchronize(e1));
+            HIP_TRY(hipEventRecord(ev.e1, s));
+            HIP_TRY(hipEventSynchronize(ev.e1));
             float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+            HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
             if (r >= 1 && (best == 0.f || ms < best)) best = ms;
         }
         p->placement_ms[k] = best;
     }
     const int keep = p->placement_ms[1] < 0.995 * p->placement_ms[0] ? 1 : 0;
     p->placement_kept = keep;
-    sc.keep_alt = true; // from here on the loop below owns both sets
-    for (int i = 0; i < 2; i++) {
-        float2 *drop = set[1 - keep][i];
-        auto it = std::find(p->allocs.begin(), p->allocs.end(), (void *)drop);
-        if (it != p->allocs.end()) p->allocs.erase(it);
-        (void)hipFree(drop);
-        if (keep == 1) p->allocs.push_back(set[1][i]);
-    }
+    if (keep == 1) p->cxy0.swap(second); // (two sets of one size: asx_plan_workspace_bytes does not change)
     W.zxa = set[keep][0];
     W.zya = set[keep][1];
     return 0;
@@ -1209,12 +1190,8 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
             if (stream_capturing(s))
                 return fail("%s: the plan's broadcast workspace does not exist yet and cannot be allocated "
                             "during a stream capture; make one call with a stride of 0 outside the capture first", fn);
-            AsxSpectra T{};
-            const size_t mz = ((size_t)p->host.M1 + 1) * (size_t)p->host.M2;
-            if (dev_alloc(p, &T.cx, mz) || dev_alloc(p, &T.cy, mz) || dev_alloc(p, &T.nrm, 2 * (size_t)P.ntiles) ||
-                (P.nbands && dev_alloc(p, &T.band, 2 * (size_t)P.ntiles * (size_t)P.nbands)))
-                return -1;
-            B = T;
+            if (asx_mem_whole(p->mem, B, [&](AsxMemSet &m, AsxSpectra &T) { return take_spectra(P, m, T, 1, 1); }))
+                return fail("hipMalloc(&ptr, bytes) failed: %s (%s:%d)", hipGetErrorString(g_take_err), __FILE__, __LINE__);
         }
         // the shared track's forward column pass: once per call, on the caller's stream, before any lane forks
         asx_launch_fwd_cols_r(P, (bc & 1) ? d_source : nullptr, 0, (bc & 2) ? d_sample : nullptr, 0, 0, 1, B, true, s);
@@ -1269,26 +1246,14 @@ static int ensure_bank(asx_plan *p, const char *fn, size_t nsrc, size_t nsmp, hi
         return fail("%s: the plan's bank holds %zu x %zu tracks and cannot grow to %zu x %zu during a stream capture; make a call "
                     "with pools at least this large outside the capture first", fn, B.nsrc, B.nsmp, nsrc, nsmp);
     const AsxDev &P = p->dev;
-    const size_t ns = std::max(nsrc, B.nsrc), nm = std::max(nsmp, B.nsmp), na = std::max(ns, nm);
-    const size_t pitch = ((size_t)p->host.M1 + 1) * (size_t)p->host.M2, nb = (size_t)P.ntiles * (size_t)P.nbands;
+    const size_t ns = std::max(nsrc, B.nsrc), nm = std::max(nsmp, B.nsmp);
+    // the old bank goes before the new one comes: both at once would double the peak
     HIP_TRY(hipDeviceSynchronize());
-    for (void *a : { (void *)B.c.cx, (void *)B.c.cy, (void *)B.c.nrm, (void *)B.c.band })
-        if (a) (void)hipFree(a);
-    B = asx_plan::Bank{ {}, 0, 0, B.fills };
-    asx_plan::Bank T = B;
-    if (hipMalloc((void **)&T.c.cx, ns * pitch * sizeof(float2)) != hipSuccess ||
-        hipMalloc((void **)&T.c.cy, nm * pitch * sizeof(float2)) != hipSuccess ||
-        hipMalloc((void **)&T.c.nrm, na * 2 * (size_t)P.ntiles * sizeof(float)) != hipSuccess ||
-        (nb && hipMalloc((void **)&T.c.band, na * 2 * nb * sizeof(float2)) != hipSuccess)) {
-        (void)hipGetLastError();
-        for (void *a : { (void *)T.c.cx, (void *)T.c.cy, (void *)T.c.nrm, (void *)T.c.band })
-            if (a) (void)hipFree(a);
+    B.mem.clear(); B.c = AsxSpectra{}; B.nsrc = B.nsmp = 0;
+    if (asx_mem_whole(B.mem, B.c, [&](AsxMemSet &m, AsxSpectra &T) { return take_spectra(P, m, T, ns, nm); }))
         return fail("%s: cannot allocate the plan's bank for %zu source and %zu sample tracks (%zu bytes per track)", fn, ns, nm,
-                    pitch * sizeof(float2));
-    }
-    T.nsrc = ns;
-    T.nsmp = nm;
-    B = T;
+                    asx_spectrum_len(P) * sizeof(float2));
+    B.nsrc = ns; B.nsmp = nm;
     return 0;
 }
 
@@ -1381,12 +1346,17 @@ extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const f
     return rc;
 }
 
-static int ensure_staging(asx_plan *p)
+static int ensure_staging(asx_plan *p, bool with64 = false) // with64: one pair's float64 inputs too (asx_xcorr_f64)
 {
-    if (p->st_src) return 0;
     const size_t N = p->host.N, g = p->group;
-    if (dev_alloc(p, &p->st_src, g * 2 * N) || dev_alloc(p, &p->st_smp, g * N) ||
-        dev_alloc(p, &p->st_lag, g) || dev_alloc(p, &p->st_coef, g) || dev_alloc(p, &p->st_ret, g))
+    if (!p->st.src && asx_mem_whole(p->mem, p->st, [&](AsxMemSet &m, asx_plan::Staging &T) {
+            return dev_alloc(m, &T.src, g * 2 * N) || dev_alloc(m, &T.smp, g * N) || dev_alloc(m, &T.lag, g) || dev_alloc(m, &T.coef, g) ||
+                   dev_alloc(m, &T.ret, g);
+        }))
+        return -1;
+    if (with64 && !p->st64.src && asx_mem_whole(p->mem, p->st64, [&](AsxMemSet &m, asx_plan::Staging64 &T) {
+            return dev_alloc(m, &T.src, 2 * N) || dev_alloc(m, &T.smp, N);
+        }))
         return -1;
     return 0;
 }
@@ -1400,13 +1370,13 @@ extern "C" int asx_xcorr_batch_f32(asx_plan *p, const float *source, const float
     if (ensure_staging(p)) return -1;
     const size_t N = p->host.N;
     hipStream_t s = c.s;
-    const Pairs<float> x = Pairs<float>::contiguous(p->st_src, p->st_smp, N);
-    const Results d{ p->st_lag, p->st_coef, p->st_ret };
+    const Pairs<float> x = Pairs<float>::contiguous(p->st.src, p->st.smp, N);
+    const Results d{ p->st.lag, p->st.coef, p->st.ret };
     prof_begin_call(p);
     for (size_t done = 0; done < batch; done += p->group) {
         const size_t g = std::min(p->group, batch - done);
-        HIP_TRY(hipMemcpyAsync(p->st_src, source + done * 2 * N, g * 2 * N * sizeof(float), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(p->st_smp, sample + done * N, g * N * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->st.src, source + done * 2 * N, g * 2 * N * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->st.smp, sample + done * N, g * N * sizeof(float), hipMemcpyHostToDevice, s));
         if (run_group(p, x, g, d, s) || fetch_results(p, x, g, d, { lag + done, coef + done, ret + done }, s)) return -1;
     }
     return 0;
@@ -1654,8 +1624,8 @@ template <typename TIn>
 static int staged_pair(asx_plan *p, const TIn *tsrc, const TIn *tsmp, const Results &h, hipStream_t s)
 {
     const size_t N = p->host.N;
-    const Pairs<TIn> x = Pairs<TIn>::staged(p->st_src, p->st_smp, tsrc, tsmp, N);
-    const Results d{ p->st_lag, p->st_coef, p->st_ret };
+    const Pairs<TIn> x = Pairs<TIn>::staged(p->st.src, p->st.smp, tsrc, tsmp, N);
+    const Results d{ p->st.lag, p->st.coef, p->st.ret };
     return run_group(p, x, 1, d, s, { .spectral = false }) || fetch_results(p, x, 1, d, h, s) ? -1 : 0;
 }
 
@@ -1665,11 +1635,8 @@ extern "C" int asx_xcorr_f64(asx_plan *p, const double *source, const double *sa
     if (!p || !source || !sample || !lag || !coefficient) return fail("asx_xcorr_f64: null argument");
     PlanCall c(p);
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
-    if (ensure_staging(p)) return -1;
+    if (ensure_staging(p, true)) return -1;
     const size_t N = p->host.N;
-    if (!p->st_src64) {
-        if (dev_alloc(p, &p->st_src64, 2 * N) || dev_alloc(p, &p->st_smp64, N)) return -1;
-    }
     hipStream_t s = c.s;
     prof_begin_call(p);
     // What ffmpeg decodes from 16-bit or float audio is exactly representable in float32 (src/capture/linux_capture.c:370
@@ -1683,8 +1650,8 @@ extern "C" int asx_xcorr_f64(asx_plan *p, const double *source, const double *sa
             else (void)hipGetLastError(); // no staging: the 8-byte path below
         }
         if (p->pin32) {
-            narrow = upload_narrowed(s, source, 2 * N, p->pin32, p->st_src);
-            if (narrow == 1) narrow = upload_narrowed(s, sample, N, p->pin32 + 2 * N, p->st_smp);
+            narrow = upload_narrowed(s, source, 2 * N, p->pin32, p->st.src);
+            if (narrow == 1) narrow = upload_narrowed(s, sample, N, p->pin32 + 2 * N, p->st.smp);
             if (narrow < 0) return -1;
         }
     }
@@ -1694,13 +1661,13 @@ extern "C" int asx_xcorr_f64(asx_plan *p, const double *source, const double *sa
     const Results h{ &h_lag, &h_coef, &h_ret };
     if (narrow == 1) {
         p->narrowed++;
-        if (staged_pair(p, p->st_src, p->st_smp, h, s)) return -1;
+        if (staged_pair(p, p->st.src, p->st.smp, h, s)) return -1;
     } else {
-        HIP_TRY(hipMemcpyAsync(p->st_src64, source, 2 * N * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(p->st_smp64, sample, N * sizeof(double), hipMemcpyHostToDevice, s));
-        asx_launch_cvt_f64_f32(p->st_src64, p->st_src, 2 * N, s);
-        asx_launch_cvt_f64_f32(p->st_smp64, p->st_smp, N, s);
-        if (staged_pair(p, p->st_src64, p->st_smp64, h, s)) return -1;
+        HIP_TRY(hipMemcpyAsync(p->st64.src, source, 2 * N * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(p->st64.smp, sample, N * sizeof(double), hipMemcpyHostToDevice, s));
+        asx_launch_cvt_f64_f32(p->st64.src, p->st.src, 2 * N, s);
+        asx_launch_cvt_f64_f32(p->st64.smp, p->st.smp, N, s);
+        if (staged_pair(p, p->st64.src, p->st64.smp, h, s)) return -1;
     }
     *lag = (long)h_lag;
     *coefficient = h_coef;
@@ -1712,8 +1679,9 @@ extern "C" int asx_xcorr_f64(asx_plan *p, const double *source, const double *sa
 struct PearsonScratch {
     std::mutex lock;
     size_t cap = 0;              // doubles per array
-    double *a = nullptr, *b = nullptr, *ps = nullptr, *c = nullptr;
-    AsxSeg *seg = nullptr;
+    double *a = nullptr, *b = nullptr;
+    struct Fixed { double *ps = nullptr, *c = nullptr; AsxSeg *seg = nullptr; } f;
+    AsxMemSet ab{ hip_mem }, fixed{ hip_mem }; // a / b: replaced on growth; the rest: whole or absent
     hipStream_t stream = nullptr;
 };
 static std::mutex g_pearson_lock;
@@ -1739,40 +1707,33 @@ extern "C" int asx_pearson_f64(const double *a, const double *b, size_t n, int d
     PearsonScratch &S = *Sp;
     std::lock_guard<std::mutex> guard(S.lock);
     if (!S.stream) {
-        // committed only when every piece exists: a failed allocation leaves nothing half-initialised behind
+        if (!S.f.ps && asx_mem_whole(S.fixed, S.f, [](AsxMemSet &m, PearsonScratch::Fixed &T) {
+                return m.take(&T.ps, ASX_PEARSON_BLOCKS_MAX * 6) || m.take(&T.c, 1) || m.take(&T.seg, 1);
+            }))
+            return fail("asx_pearson_f64: scratch allocation failed: %s", hipGetErrorString(g_take_err));
         hipStream_t st = nullptr;
-        double *ps = nullptr, *c = nullptr;
-        AsxSeg *seg = nullptr;
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
-            hipMalloc((void **)&ps, ASX_PEARSON_BLOCKS_MAX * 6 * sizeof(double)) != hipSuccess ||
-            hipMalloc((void **)&c, sizeof(double)) != hipSuccess || hipMalloc((void **)&seg, sizeof(AsxSeg)) != hipSuccess) {
-            const hipError_t e = hipGetLastError();
-            if (st) (void)hipStreamDestroy(st);
-            (void)hipFree(ps); (void)hipFree(c); (void)hipFree(seg);
-            return fail("asx_pearson_f64: scratch allocation failed: %s", hipGetErrorString(e));
-        }
-        S.ps = ps; S.c = c; S.seg = seg; S.stream = st;
+        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess)
+            return fail("asx_pearson_f64: scratch allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        S.stream = st;
     }
     if (n > S.cap) {
-        (void)hipFree(S.a); (void)hipFree(S.b);
+        S.ab.clear();
         S.a = S.b = nullptr; S.cap = 0;
         const size_t want = std::max<size_t>(n, 4096);
+        AsxMemSet grown(hip_mem);
         double *na = nullptr, *nb = nullptr;
-        if (hipMalloc((void **)&na, want * sizeof(double)) != hipSuccess || hipMalloc((void **)&nb, want * sizeof(double)) != hipSuccess) {
-            const hipError_t e = hipGetLastError();
-            (void)hipFree(na); (void)hipFree(nb);
-            return fail("asx_pearson_f64: hipMalloc failed: %s", hipGetErrorString(e));
-        }
+        if (grown.take(&na, want) || grown.take(&nb, want)) return fail("asx_pearson_f64: hipMalloc failed: %s", hipGetErrorString(g_take_err));
+        S.ab.swap(grown);
         S.a = na; S.b = nb; S.cap = want;
     }
     AsxSeg seg{};
     seg.lag = 0; seg.src_off = 0; seg.smp_off = 0; seg.len = (uint32_t)n; seg.peak = 0;
     HIP_TRY(hipMemcpyAsync(S.a, a, n * sizeof(double), hipMemcpyHostToDevice, S.stream));
     HIP_TRY(hipMemcpyAsync(S.b, b, n * sizeof(double), hipMemcpyHostToDevice, S.stream));
-    HIP_TRY(hipMemcpyAsync(S.seg, &seg, sizeof(seg), hipMemcpyHostToDevice, S.stream));
-    asx_launch_pearson(AsxInputs<double>{ S.a, S.b, 0, 0, nullptr }, (uint32_t)n, S.seg, S.ps, nullptr, S.c, nullptr, 1, S.stream);
+    HIP_TRY(hipMemcpyAsync(S.f.seg, &seg, sizeof(seg), hipMemcpyHostToDevice, S.stream));
+    asx_launch_pearson(AsxInputs<double>{ S.a, S.b, 0, 0, nullptr }, (uint32_t)n, S.f.seg, S.f.ps, nullptr, S.f.c, nullptr, 1, S.stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, S.c, sizeof(double), hipMemcpyDeviceToHost, S.stream));
+    HIP_TRY(hipMemcpyAsync(out, S.f.c, sizeof(double), hipMemcpyDeviceToHost, S.stream));
     HIP_TRY(hipStreamSynchronize(S.stream));
     return 0;
 }
@@ -1810,11 +1771,9 @@ struct asx_stream {
     int device = 0;
     size_t cap = 0;                 // max sample frames (source capacity = 2*cap)
     size_t n_src = 0, n_smp = 0;    // frames resident
-    double *src64 = nullptr, *smp64 = nullptr;
-    float *src32 = nullptr, *smp32 = nullptr;
-    int64_t *d_lag = nullptr;
-    double *d_coef = nullptr;
-    int32_t *d_ret = nullptr;
+    asx_plan::Staging f32;          // the tracks as float32, one result
+    asx_plan::Staging64 f64;        // the tracks as they came
+    AsxMemSet mem{ hip_mem };       // the seven buffers of the two
     std::vector<asx_plan *> plans;  // one per prefix length seen
     int64_t win_lo = INT64_MIN, win_hi = INT64_MAX; // asx_stream_set_lag_window, in frames: clamped to [-n, n-1] per prefix length n
     hipStream_t s = nullptr;        // uploads and conversions of new frames
@@ -1824,14 +1783,9 @@ struct asx_stream {
 extern "C" void asx_stream_destroy(asx_stream *st)
 {
     if (!st) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(st->device);
+    DevGuard dg(st->device); // (until the stream's set has given its buffers back)
     for (asx_plan *p : st->plans) asx_plan_destroy(p);
     if (st->s) { (void)hipStreamSynchronize(st->s); (void)hipStreamDestroy(st->s); }
-    (void)hipFree(st->src64); (void)hipFree(st->smp64); (void)hipFree(st->src32); (void)hipFree(st->smp32);
-    (void)hipFree(st->d_lag); (void)hipFree(st->d_coef); (void)hipFree(st->d_ret);
-    (void)hipSetDevice(prev);
     delete st;
 }
 
@@ -1846,15 +1800,11 @@ extern "C" asx_stream *asx_stream_create(size_t max_sample_len, int device)
     st->device = device;
     st->cap = max_sample_len;
     const size_t n = max_sample_len;
-    if (hipMalloc((void **)&st->src64, 2 * n * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&st->smp64, n * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&st->src32, 2 * n * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&st->smp32, n * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&st->d_lag, sizeof(int64_t)) != hipSuccess ||
-        hipMalloc((void **)&st->d_coef, sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&st->d_ret, sizeof(int32_t)) != hipSuccess ||
-        hipStreamCreateWithFlags(&st->s, hipStreamNonBlocking) != hipSuccess) {
-        fail("asx_stream_create: hipMalloc failed: %s", hipGetErrorString(hipGetLastError()));
+    AsxMemSet &m = st->mem;
+    const bool took = !(m.take(&st->f64.src, 2 * n) || m.take(&st->f64.smp, n) || m.take(&st->f32.src, 2 * n) || m.take(&st->f32.smp, n) ||
+                        m.take(&st->f32.lag, 1) || m.take(&st->f32.coef, 1) || m.take(&st->f32.ret, 1));
+    if (!took || hipStreamCreateWithFlags(&st->s, hipStreamNonBlocking) != hipSuccess) {
+        fail("asx_stream_create: hipMalloc failed: %s", hipGetErrorString(took ? hipGetLastError() : g_take_err));
         asx_stream_destroy(st);
         return nullptr;
     }
@@ -1893,12 +1843,12 @@ extern "C" int asx_stream_append_f64(asx_stream *st, const double *source_frames
     // (No float32 narrowing here, unlike asx_xcorr_f64: the frames come from page-locked memory and go by DMA as they are;
     //  a CPU pass over them to save PCIe bytes measured SLOWER, 1.98 against 1.76 ms for the six intervals.)
     if (n_source) {
-        HIP_TRY(hipMemcpyAsync(st->src64 + st->n_src, source_frames, n_source * sizeof(double), hipMemcpyHostToDevice, st->s));
-        asx_launch_cvt_f64_f32(st->src64 + st->n_src, st->src32 + st->n_src, n_source, st->s);
+        HIP_TRY(hipMemcpyAsync(st->f64.src + st->n_src, source_frames, n_source * sizeof(double), hipMemcpyHostToDevice, st->s));
+        asx_launch_cvt_f64_f32(st->f64.src + st->n_src, st->f32.src + st->n_src, n_source, st->s);
     }
     if (n_sample) {
-        HIP_TRY(hipMemcpyAsync(st->smp64 + st->n_smp, sample_frames, n_sample * sizeof(double), hipMemcpyHostToDevice, st->s));
-        asx_launch_cvt_f64_f32(st->smp64 + st->n_smp, st->smp32 + st->n_smp, n_sample, st->s);
+        HIP_TRY(hipMemcpyAsync(st->f64.smp + st->n_smp, sample_frames, n_sample * sizeof(double), hipMemcpyHostToDevice, st->s));
+        asx_launch_cvt_f64_f32(st->f64.smp + st->n_smp, st->f32.smp + st->n_smp, n_sample, st->s);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st->s));
@@ -1942,8 +1892,8 @@ extern "C" int asx_stream_xcorr(asx_stream *st, size_t sample_len, long *lag, do
     int64_t h_lag = 0;
     double h_coef = 0;
     int32_t h_ret = -1;
-    const Pairs<double> x = Pairs<double>::staged(st->src32, st->smp32, st->src64, st->smp64, sample_len);
-    const Results d{ st->d_lag, st->d_coef, st->d_ret };
+    const Pairs<double> x = Pairs<double>::staged(st->f32.src, st->f32.smp, st->f64.src, st->f64.smp, sample_len);
+    const Results d{ st->f32.lag, st->f32.coef, st->f32.ret };
     if (run_group(p, x, 1, d, c.s) || fetch_results(p, x, 1, d, { &h_lag, &h_coef, &h_ret }, c.s)) return -1;
     *lag = (long)h_lag;
     *coefficient = h_coef;

@@ -453,6 +453,8 @@ struct AsxSpectra {
     const AsxPoolPair *pl = nullptr;
     const AsxPrune *prune = nullptr;
 };
+// float2 elements of one track's column spectrum: rows k1 = 0 .. M1 of M2 columns, the pitch between the tracks of a set
+inline size_t asx_spectrum_len(const AsxDev &P) { return ((size_t)P.M1 + 1) * (size_t)P.M2; }
 
 // Spectral Pearson: the coefficient from r[peak] and window sums instead of a second pass over the inputs.
 // Modes a pair can take (k_pearson_prep decides, k_pearson_partial / k_pearson_final_spec act on it):

@@ -1297,7 +1297,7 @@ void asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride,
 {
     const unsigned op0 = src ? 0 : 1, nops = (src ? 1 : 0) + (smp ? 1 : 0);
     if (nops == 0) return;
-    const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, lds = (size_t)P.M1 * P.T * sizeof(float2);
+    const size_t pitch = asx_spectrum_len(P), lds = (size_t)P.M1 * P.T * sizeof(float2);
     const size_t per = 2 * (size_t)P.ntiles; // norm partials per track slot; band sums: nbands times as many
     if (src) src += first * src_stride;
     if (smp) smp += first * smp_stride;
@@ -1339,7 +1339,7 @@ static void launch_inv_r(K kernel, const AsxDev &P, dim3 grid, int nt, size_t ld
 {
     const void *fn = (const void *)kernel;
     allow_big_lds(fn, lds);
-    hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, s, rargs_of(P), q, ((size_t)P.M1 + 1) * (size_t)P.M2, W, r_out,
+    hipLaunchKernelGGL(kernel, grid, dim3(nt), lds, s, rargs_of(P), q, asx_spectrum_len(P), W, r_out,
                        resident_blocks(fn, nt, lds), sel);
 }
 
@@ -1347,7 +1347,7 @@ static void launch_inv_r(K kernel, const AsxDev &P, dim3 grid, int nt, size_t ld
 template <class S1, int TC, int NT>
 static void launch_inv_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, const AsxPrune &U, int npairs, hipStream_t s)
 {
-    const size_t pitch = ((size_t)P.M1 + 1) * (size_t)P.M2, lds = (size_t)S1::n * TC * sizeof(float2);
+    const size_t pitch = asx_spectrum_len(P), lds = (size_t)S1::n * TC * sizeof(float2);
     auto k1 = k_inv_cols_r<S1, TC, NT, AsxSelPrune<true>>;
     auto k2 = k_inv_cols_r<S1, TC, NT, AsxSelPrune<false>>;
     allow_big_lds((const void *)k1, lds);

@@ -793,6 +793,32 @@ def plain_split(mod, n):
         return p.split
 
 
+def test_workspace_bytes_count_each_lazy_set_once(mod):
+    """asx_plan_workspace_bytes is everything the plan holds but the pool bank: the staging of the host-pointer calls (per pair of a
+    group 2N + N floats and a result of 8 + 8 + 4 bytes), of the double ABI (2N + N doubles) and the broadcast slot count from the
+    call that creates them, and no later call adds to them"""
+    n = 144000
+    rng = np.random.default_rng(47)
+    src = rng.standard_normal((2, 2 * n)).astype(np.float32)
+    smp = rng.standard_normal((2, n)).astype(np.float32)
+    with mod.Plan(n, 2, 0) as plan:
+        g = plan.group
+        w0 = plan.workspace_bytes
+        seen = []
+        for _ in range(2):
+            plan.xcorr_batch_f32(src, smp)
+            seen.append(plan.workspace_bytes)
+            plan.xcorr_f64(src[0], smp[0])
+            seen.append(plan.workspace_bytes)
+            plan.xcorr_broadcast_f32(src[0], smp)   # a source stride of 0
+            seen.append(plan.workspace_bytes)
+        w3 = seen[2]
+        assert seen[0] == w0 + g * (12 * n + 20) and seen[1] == seen[0] + 24 * n and w3 > seen[1], (w0, g, seen)
+        assert seen[3:] == [w3, w3, w3], seen
+        plan.xcorr_pool_f32(src, smp)
+        assert plan.workspace_bytes == w3
+
+
 @pytest.mark.parametrize("n,split,env", [(144000, None, {}), (288000, None, {}), (480000, None, {}), (960000, None, {}),
                                          (144000, None, {"ASX_LAYOUT": "packed"}), (1000, "25x40x8", {})])
 def test_a_plan_runs_the_kernels_the_planner_names(mod, monkeypatch, n, split, env):

@@ -292,3 +292,24 @@ def test_other_calls_after_a_pool_call(mod, torch):
         assert bits(pool, 3 * 0 + i) == bits(w_bc, i), i
     for a, b in zip(pool, pool2):
         assert a.tobytes() == b.tobytes()
+
+
+def test_a_bank_no_device_can_hold(mod, torch):
+    """A pool call that names more tracks than any device holds (2^31 - 1 sources, the most the entry point accepts: a bank of about
+    3.7e15 bytes) fails before anything is launched, names the bank, and leaves the plan without one -- the old bank is released
+    before the new one is asked for -- and the next call builds it again and returns what it returned before"""
+    n = 144000
+    rng = np.random.default_rng(43)
+    d_src = torch.from_numpy(rng.standard_normal(2 * 2 * n).astype(np.float32)).cuda()
+    d_smp = torch.from_numpy(rng.standard_normal(2 * n).astype(np.float32)).cuda()
+    with mod.Plan(n, 4, 0) as plan:
+        assert plan.layout == "real-column"
+        first = pool_dev(plan, torch, d_src, 2 * n, 2, d_smp, n, 2, None, 4)
+        assert plan.debug_bank() == (2, 2, 1)
+        with pytest.raises(mod.AsxError, match="bank"):   # (the exception's text is asx_last_error's)
+            pool_dev(plan, torch, d_src, 2 * n, INT32_MAX, d_smp, n, 2, [[0, 0]], 1)
+        assert plan.debug_bank() == (0, 0, 1)
+        again = pool_dev(plan, torch, d_src, 2 * n, 2, d_smp, n, 2, None, 4)
+        assert plan.debug_bank() == (2, 2, 2)
+    for a, b in zip(first, again):
+        assert a.tobytes() == b.tobytes()

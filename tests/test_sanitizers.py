@@ -83,3 +83,12 @@ def test_kernel_choice_of_the_host_plans_under_asan(san):
     resolve to from csrc/kernel_table.h, under the default environment, ASX_LAYOUT=packed and ASX_GENERIC=1"""
     out = run([os.path.join(san, "choice_asan")])
     assert ", 0 failures" in out and not out.startswith("0 cases")
+
+
+def test_ownership_of_device_memory_without_hardware(san):
+    """csrc/dev_mem.h -- the sets that own the library's device buffers, and the rule that a lazily created set exists whole or
+    not at all -- on malloc / free with a failing k-th allocation, which no GPU can be made to produce: for every failing piece the
+    destination and the owner's byte count are untouched and nothing stays live, a retry ends with exactly one set, adopt / swap /
+    move hand ownership over once, a set replaced on growth releases before it takes; AddressSanitizer's leak check at exit"""
+    out = run([os.path.join(san, "mem_asan")])
+    assert ", 0 failures" in out and not out.startswith("0 cases")
