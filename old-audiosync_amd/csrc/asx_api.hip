@@ -622,6 +622,45 @@ extern "C" int asx_plan_debug_peak(asx_plan *p, size_t pair, float *bound2, uint
     return 0;
 }
 
+// diagnostic (not in the public header): what the spectral Pearson form (pearson_spectral.hip) built the coefficient of pair `pair`
+// of the last group on lane 0 from.  Real-column plans only.
+//   dims[4]   ntiles, nbands, band_rows, blocks of k_pearson_prep per pair
+//   band      null, or [2][ntiles][nbands] {sum, sum of squares} (float pairs; band_cap = the floats it holds, at least
+//             4 ntiles nbands): operand 0 the source, operand 1 the sample, whose bands past nbands / 2 were never written
+//   hdr[4]    r[peak], the bound on its error, the direct flag, the mode k_pearson_partial recorded
+//   seg[6]    lag, src_off, smp_off, len, peak, flags of the pair's AsxSeg
+//   pick[8]   mode, n, Sx, Sxx, Sy, Syy, r, bound: asx_spec_pick evaluated ON THE DEVICE from that state (k_debug_spec_pick)
+// Synchronises the device; what it allocates lives for the call alone.
+extern "C" int asx_plan_debug_spectral(asx_plan *p, size_t pair, int *dims, float *band, size_t band_cap, double *hdr,
+                                       long long *seg, double *pick)
+{
+    if (!p || pair >= p->group || !dims || !hdr || !seg || !pick) return -1;
+    const asx_plan::Lane &W = p->lanes[0];
+    if (!p->dev.rlayout || !W.pk.band || !W.spec.hdr) return -1;
+    PlanCall c(p, nullptr, false);
+    if (!c.dg.ok || hipDeviceSynchronize() != hipSuccess) return -1;
+    const AsxDev &P = p->dev;
+    const size_t cells = (size_t)P.ntiles * (size_t)P.nbands;
+    if (band) {
+        if (band_cap < 4 * cells) return -1;
+        if (hipMemcpy(band, W.pk.band + pair * 2 * cells, 2 * cells * sizeof(float2), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    }
+    AsxSeg sg;
+    if (hipMemcpy(hdr, W.spec.hdr + pair * ASX_SPEC_HDR, ASX_SPEC_HDR * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&sg, W.seg + pair, sizeof sg, hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+    seg[0] = sg.lag; seg[1] = sg.src_off; seg[2] = sg.smp_off; seg[3] = sg.len; seg[4] = sg.peak; seg[5] = sg.flags;
+    AsxMemSet tmp(hip_mem);
+    double *d_pick = nullptr;
+    if (tmp.take(&d_pick, 8)) return -1;
+    const int nb = asx_launch_debug_spec_pick(P, W.spec, W.seg, pair, d_pick, p->stream);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess ||
+        hipMemcpy(pick, d_pick, 8 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+    dims[0] = P.ntiles; dims[1] = P.nbands; dims[2] = P.band_rows; dims[3] = nb;
+    return 0;
+}
+
 // diagnostic (not in the public header): the pruned pass's bounds ub[0 .. n) and largest-bound tile of pair `pair` of the last pruned
 // group on lane 0 (n <= the plan's tile count)
 extern "C" int asx_plan_debug_prune(asx_plan *p, size_t pair, float *ub, int *best, size_t n)

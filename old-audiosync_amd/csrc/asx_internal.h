@@ -530,6 +530,9 @@ void asx_launch_pearson_partial_spec_f32(const AsxInputs<float> &in, uint32_t ba
 void asx_launch_pearson_spectral_f32(const AsxDev &P, const AsxInputs<float> &in, const AsxSearch &q, const AsxPeakWs &W,
                                      const AsxSpecWs &S, AsxSeg *seg, double *psums, int64_t *lag, double *coef, int32_t *ret,
                                      int npairs, hipStream_t s);
+// diagnostic: asx_spec_pick of `pair` on the device, out (device, 8 doubles) = {mode, n, Sx, Sxx, Sy, Syy, r, bound}; returns the
+// blocks of k_pearson_prep per pair (the shares AsxSpecWs::part holds for it)
+int asx_launch_debug_spec_pick(const AsxDev &P, const AsxSpecWs &S, const AsxSeg *seg, size_t pair, double *out, hipStream_t s);
 void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch,
                               double min_confidence, double sample_rate, int64_t *lag_ms, int32_t *accept,
                               hipStream_t s);

@@ -268,16 +268,38 @@ static void launch_prep(const AsxDev &P, const AsxInputs<float> &in, const AsxSe
                            seg, q.seed());
 }
 
+// the long-track form of k_pearson_prep: ASX_PREP_BLOCKS blocks of ASX_PREP_THREADS threads per pair (a function of the plan alone)
+static bool prep_long_tracks(const AsxDev &P) { return (size_t)P.band_rows * (size_t)P.M2 >= 16384; }
+
 void asx_launch_pearson_spectral_f32(const AsxDev &P, const AsxInputs<float> &in, const AsxSearch &q, const AsxPeakWs &W,
                                      const AsxSpecWs &S0, AsxSeg *seg, double *psums, int64_t *lag, double *coef, int32_t *ret,
                                      int npairs, hipStream_t s)
 {
     AsxSpecWs S = S0;
     S.N = P.N;
-    const bool long_tracks = (size_t)P.band_rows * (size_t)P.M2 >= 16384;
+    const bool long_tracks = prep_long_tracks(P);
     S.nb = long_tracks ? ASX_PREP_BLOCKS : 1;
     if (long_tracks) launch_prep<ASX_PREP_THREADS, ASX_PREP_BLOCKS>(P, in, q, W, S, seg, npairs, s);
     else launch_prep<256, 1>(P, in, q, W, S, seg, npairs, s);
     asx_launch_pearson_partial_spec_f32(in, P.N, seg, S, psums, npairs, s);
     hipLaunchKernelGGL(k_pearson_final_spec, dim3(npairs), dim3(64), 0, s, seg, psums, asx_pearson_blocks(P.N), S, lag, coef, ret);
+}
+
+// diagnostic (asx_plan_debug_spectral, asx_api.hip): asx_spec_pick of one pair, called on the device as k_pearson_partial and
+// k_pearson_final_spec call it, from what the last group left -- out = {mode, n, Sx, Sxx, Sy, Syy, r, bound}.  One thread; launched
+// by the diagnostic alone.
+__global__ __launch_bounds__(64) void k_debug_spec_pick(const AsxSeg *__restrict__ seg, AsxSpecWs S, size_t pair, double *__restrict__ out)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const AsxSpecPick d = asx_spec_pick(seg[pair], S.part + pair * (size_t)(S.nb * 4), S.nb, S.hdr + pair * ASX_SPEC_HDR, S.tol, S.N);
+    out[0] = (double)d.mode; out[1] = d.n; out[2] = d.Sx; out[3] = d.Sxx; out[4] = d.Sy; out[5] = d.Syy; out[6] = d.r; out[7] = d.bound;
+}
+
+int asx_launch_debug_spec_pick(const AsxDev &P, const AsxSpecWs &S0, const AsxSeg *seg, size_t pair, double *out, hipStream_t s)
+{
+    AsxSpecWs S = S0;
+    S.N = P.N;
+    S.nb = prep_long_tracks(P) ? ASX_PREP_BLOCKS : 1; // as asx_launch_pearson_spectral_f32 sets them
+    hipLaunchKernelGGL(k_debug_spec_pick, dim3(1), dim3(1), 0, s, seg, S, pair, out);
+    return S.nb;
 }

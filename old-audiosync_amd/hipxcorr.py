@@ -796,6 +796,54 @@ class Plan:
             raise AsxError("asx_plan_debug_prune failed")
         return np.frombuffer(ub, dtype=np.float32).copy(), int(best.value)
 
+    def debug_peak(self, pair=0):
+        """diagnostic: the peak-search state of `pair` of the last group on lane 0 (asx_plan_debug_peak) -- bound2 (2B in the
+        device's scale, F times the plain sum), cand_n, refine_n, the float32 maximum's (key, index) decoded from pairmax (None,
+        None when nothing competed), and the near-tie list refine_idx[:refine_n] with its exact values refine_val[:refine_n]"""
+        cap = self.peak_capacity
+        b2, cn, rn, pm = ctypes.c_float(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+        vals, idxs = np.zeros(cap, dtype=np.float64), np.zeros(cap, dtype=np.uint32)
+        f = lib().asx_plan_debug_peak
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32),
+                      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.c_void_p,
+                      ctypes.c_size_t]
+        if f(self._h, int(pair), ctypes.byref(b2), ctypes.byref(cn), ctypes.byref(rn), ctypes.byref(pm), vals.ctypes.data,
+             idxs.ctypes.data, cap) != 0:
+            raise AsxError("asx_plan_debug_peak failed")
+        key = index = None
+        if pm.value:   # peak_pack_key (csrc/xcorr_dev.h): an order-preserving key in the high word, ~index in the low word
+            hi = pm.value >> 32
+            hi = (hi & 0x7FFFFFFF) if hi & 0x80000000 else (~hi & 0xFFFFFFFF)
+            key = float(np.array([hi], dtype=np.uint32).view(np.float32)[0])
+            index = 0xFFFFFFFF - (pm.value & 0xFFFFFFFF)
+        n = min(int(rn.value), cap)
+        return {"bound2": float(b2.value), "cand_n": int(cn.value), "refine_n": int(rn.value), "key": key, "index": index,
+                "refine_idx": idxs[:n].astype(np.int64), "refine_val": vals[:n].copy()}
+
+    def debug_spectral(self, pair=0):
+        """diagnostic (real-column plans): what the spectral Pearson form built the coefficient of `pair` of the last group on lane 0
+        from (asx_plan_debug_spectral) -- band: float32 [2][ntiles][nbands][2], {sum, sum of squares} of every band x tile cell of
+        the source (0) and the sample (1: only bands < nbands / 2 exist); nbands, band_rows, prep_blocks; the header r, rb, direct,
+        mode; seg: the pair's segment; pick: asx_spec_pick as a one-thread kernel evaluates it from that state"""
+        ntiles = (self.split[1] + self.split[2] - 1) // self.split[2]
+        f = lib().asx_plan_debug_spectral
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.c_void_p, ctypes.c_size_t, c_intp, ctypes.c_void_p, ctypes.c_size_t, c_f64p,
+                      ctypes.POINTER(ctypes.c_longlong), c_f64p]
+        dims, hdr, seg, pick = (ctypes.c_int * 4)(), (ctypes.c_double * 4)(), (ctypes.c_longlong * 6)(), (ctypes.c_double * 8)()
+        if f(self._h, int(pair), dims, None, 0, hdr, seg, pick) != 0:
+            raise AsxError("asx_plan_debug_spectral failed (a real-column plan that has run a group?)")
+        assert dims[0] == ntiles, (dims[0], ntiles)
+        band = np.zeros((2, dims[0], dims[1], 2), dtype=np.float32)
+        if f(self._h, int(pair), dims, band.ctypes.data, band.size, hdr, seg, pick) != 0:
+            raise AsxError("asx_plan_debug_spectral failed")
+        return {"band": band, "nbands": dims[1], "band_rows": dims[2], "prep_blocks": dims[3],
+                "r": hdr[0], "rb": hdr[1], "direct": hdr[2] != 0.0, "mode": int(hdr[3]),
+                "seg": dict(zip(("lag", "src_off", "smp_off", "len", "peak", "flags"), (int(v) for v in seg))),
+                "pick": dict(zip(("mode", "n", "Sx", "Sxx", "Sy", "Syy", "r", "bound"),
+                                 (int(pick[0]),) + tuple(float(v) for v in pick[1:])))}
+
     def debug_kernels(self):
         """the kernels this plan runs, as planmath_kernels spells them: the record made when the plan was built"""
         f = lib().asx_plan_debug_kernels
