@@ -28,8 +28,8 @@
  * Per-pair result convention (the reference's, src/cross_correlation.c:140,276,298):
  *   ret[i] = 0 on success, -1 when the Pearson coefficient is NaN (lag[i] and
  *   coef[i] are still written, exactly as the reference leaves them).
- *   ret[i] = -2 (asx_xcorr_windowed_f32_dev only): pair i's lag window was not a window
- *   inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.
+ *   ret[i] = -2 (asx_xcorr_windowed_f32_dev, and asx_xcorr_phat_f32_dev with rows): pair i's lag
+ *   window was not a window inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.
  *   ret = -3 (asx_xcorr_topk_f32_dev and asx_xcorr_pool_topk_f32_dev only): no lag is left for
  *   this entry of the pair (its window minus the zones around the earlier entries is empty);
  *   lag = 0 and coef = NaN.
@@ -298,6 +298,44 @@ int asx_xcorr_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_
                            size_t batch, int k, int64_t min_separation,
                            int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream);
 
+/* GCC-PHAT: the strided batch with the phase transform.  Every other entry point ranks lags by the raw correlation r, whose peak
+ * belongs to whatever carries the most energy (a shared mains hum, a bass line, a room mode), not to the best alignment.  Here
+ * every bin of the cross spectrum Q = X conj(Y), at F = 2N, is divided by its magnitude before the inverse transform, so each
+ * frequency has one vote:  Q'[k] = Q[k] / |Q[k]| where |Q[k]| > 0, and Q'[k] = 0 where Q[k] is exactly zero.  Pure PHAT: no floor,
+ * no exponent.  The division gives a unit-magnitude bin for every finite non-zero float32 Q[k] whatever its exponent (the exponent
+ * is taken out before squaring: tracks scaled by 2^40 or 2^-40 weigh as the unscaled ones do); a NaN bin stays NaN.
+ *   Inputs.  Strides, broadcast (a stride of 0), the 16-byte layout rule and the stream rule are those of
+ * asx_xcorr_strided_f32_dev.  d_windows == NULL: the plan's lag window (asx_plan_set_lag_window) applies to every pair.  Otherwise
+ * d_windows holds per-pair rows exactly as in asx_xcorr_windowed_f32_dev, and the plan's window is ignored and left as it is.
+ * Real-column plans only (asx_plan_layout() == 1, where F = 2N): a packed plan returns -1, as the pool calls do.  A NULL d_source,
+ * d_sample, d_coef or d_ret, a base pointer that is not 16-byte aligned and a non-zero stride that is not a multiple of 4 also
+ * return -1 with nothing launched and the outputs untouched.  d_lag and d_peak may be NULL.  batch == 0 returns 0.
+ *   The peak.  max_abs_index() (src/cross_correlation.c:52-67) over the window in ascending index order -- the seed with its
+ * signed value, every other element with fabs and the strict '>' -- applied to the FLOAT32 values of r_phat that the device
+ * computes; among equal float32 values the smallest index wins.  This is the float32 argmax, NOT the float64 argmax by
+ * construction: the error bound, the near-tie lists, the exact re-evaluation and the second look of the other entry points rest
+ * on r being the plain time-domain sum, and none of that holds for a whitened spectrum.  The resolution is the float32 error of
+ * r_phat / F, measured against a float64 model over all 2N lags: at most 2.2e-8 of full scale at N = 144 000 and 3.2e-8 at N = 960 000
+ * (tests/test_gpu_phat.py).  Two lags whose peak heights differ by less than that may come back in either order.
+ *   Outputs per pair.  lag: the peak's lag after the reference's wrap (:256-263).  coef: the reference's Pearson coefficient of
+ * the ORIGINAL samples at that lag, always in the direct form: under asx_plan_set_pearson(plan, 0) bit for bit what
+ * asx_xcorr_windowed_f32_dev returns for the row [lag, lag] (the precedent of the top-k call's later entries), so
+ * asx_results_to_ms_dev and the acceptance rule keep working.  peak: |r_phat[lag]| / F, between 0 and 1 -- 1 for a pure circular
+ * delay, 0 for a silent pair.  ret: 0, -1 for a NaN coefficient, -2 for a row that is not a window (that pair gets lag 0 and NaN
+ * for coef and peak; the other pairs are untouched, bit for bit).  ret is never 1.
+ *   A pair with a digitally silent track returns the seed's lag (lag 0 without a window), as the plain rule does, with peak 0.
+ *   What the call never does.  It never lists a pair, never takes a second look and never synchronises the host: it is
+ * asynchronous whatever asx_plan_set_exact says.  It leaves asx_plan_peak_overflows, asx_plan_peak_repairs, asx_plan_pearson_modes
+ * and asx_plan_prune_stats unchanged (the pruned inverse pass is never used: |Q'| = 1 makes its energy bound useless).  It
+ * allocates nothing after plan creation, but for the broadcast slot's first allocation under asx_xcorr_strided_f32_dev's rule.
+ *   Weakness.  Bins that hold only rounding noise vote too: on band-limited material the empty part of the spectrum adds noise
+ * to r_phat and lowers the peak.  A magnitude floor is future work.  Not offered with PHAT: pools, top-k, the double ABI,
+ * streams, packed plans. */
+int asx_xcorr_phat_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                           const float *d_sample, size_t sample_stride,
+                           const int64_t *d_windows, size_t window_stride, size_t batch,
+                           int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
 /* Many tracks against many: listed pairs of two track pools, every track transformed once per call.
  * Source track a is d_sources + a*source_stride (2N floats), sample track b is d_samples + b*sample_stride
  * (N floats); strides in floats.  The pools may overlap or alias (one pool of clips as both, for all-pairs),
@@ -405,6 +443,11 @@ int asx_xcorr_batch_multi_dev(asx_comm *comm, const float *const *d_source, cons
 int asx_xcorr_debug_r_dev(asx_plan *plan, const float *d_source, const float *d_sample,
                           float *d_r, int64_t *d_lag, double *d_coef, int32_t *d_ret,
                           void *stream);
+
+/* The same aid for asx_xcorr_phat_f32_dev: ONE contiguous pair under the plan's window, and the whole of r_phat to d_r: 2N floats,
+ * unnormalised (F times the value that peak reports).  d_r, d_coef and d_ret must not be NULL; real-column plans only. */
+int asx_xcorr_phat_debug_r_dev(asx_plan *plan, const float *d_source, const float *d_sample, float *d_r,
+                               int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
 
 /* pearson_coefficient() on two equal-length host double ranges. Writes the
  * coefficient (NaN for a constant range, like the reference). */

@@ -833,15 +833,16 @@ template <typename TIn> struct Pairs {
 };
 
 // Where pair k's results go (lag and ret may be null): entries step apart (the top-k calls: step = k, entry j of pair i at
-// i * k + j; every other entry point: 1).
+// i * k + j; every other entry point: 1).  peak: the PHAT call's peak heights (step 1), null everywhere else.
 struct Results {
     int64_t *lag;
     double *coef;
     int32_t *ret;
     size_t step = 1;
+    double *peak = nullptr;
     Results at(size_t k) const
     {
-        return { lag ? lag + k * step : nullptr, coef + k * step, ret ? ret + k * step : nullptr, step };
+        return { lag ? lag + k * step : nullptr, coef + k * step, ret ? ret + k * step : nullptr, step, peak ? peak + k : nullptr };
     }
 };
 
@@ -869,6 +870,10 @@ struct GroupOpts {
     int dot_blocks = 0;          // blocks per pair of the exact re-evaluation; 0: by the group size
     const AsxPeakWs *pk = nullptr; // the peak workspace instead of the lane's (the second look's lists for every lag)
     Topk topk{};                 // k > 1: passes 2..k over the group's Q (y's entry stride is k)
+    // How the product spectrum is weighted (asx_internal.h).  ASX_W_PHAT (asx_xcorr_phat_f32_dev, real-column plans, k = 1, no pool):
+    // the row pass's PHAT flavour and the PHAT tail -- k_phat_finalize, the direct Pearson form, k_invalid_rows -- with no pruned
+    // pass, no list and no spectral form, whatever the plan's switches say: none of them means anything for a whitened spectrum.
+    AsxWeight weight = ASX_W_NONE;
 };
 
 // One group: g <= plan->group pairs, the first g of x, results to the first g of y.
@@ -880,8 +885,9 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     const AsxPeakWs &pk = o.pk ? *o.pk : W.pk;
     auto mark = [&](size_t k) { return o.prof_group != GroupOpts::no_marks && prof_mark(p, s, o.prof_group * 6 + k); };
     AsxPeakWs fin = pk;
-    if (!o.listed) { fin.over_list = nullptr; fin.over_n = nullptr; fin.over_host = nullptr; fin.over_cap = 0; }
-    const bool spectral = std::is_same<TIn, float>::value && p->spectral && o.spectral && pk.band;
+    const bool phat = o.weight == ASX_W_PHAT;
+    if (!o.listed || phat) { fin.over_list = nullptr; fin.over_n = nullptr; fin.over_host = nullptr; fin.over_cap = 0; }
+    const bool spectral = std::is_same<TIn, float>::value && p->spectral && o.spectral && pk.band && !phat;
     AsxPeakWs tk = pk; // what the transform kernels see
     if (!spectral) { tk.band = nullptr; tk.tile_peak = nullptr; }
     // The pruned pair of passes (rlayout.hip: k_rows_re, and k_tile_bounds and k_inv_cols_r<..., AsxSelPrune> around k_prune_select) in place of the row pass
@@ -893,13 +899,13 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // pruned pass can run on: AsxKernelChoice::prunable.)
     const bool f32_entry = std::is_same<TIn, float>::value && o.spectral;
     const AsxSearch call = AsxSearch::of(p->win_lo, p->win_hi, P.N, x.win, x.win_step, W.tk, 0); // pass 1's search
-    const bool prune = p->prune && f32_entry && !x.pool && x.bc == 0 && !o.r_out && !o.pk && o.topk.k == 1 && call.kind == AsxSearch::ALL;
+    const bool prune = p->prune && !phat && f32_entry && !x.pool && x.bc == 0 && !o.r_out && !o.pk && o.topk.k == 1 && call.kind == AsxSearch::ALL;
     // The group's spectra (AsxSpectra): the lane's own forward passes -- but a broadcast operand's rows are in the plan's slot, and a
     // pool group's in the bank, found through its resolved records -- with the norm partials and band sums always in the lane's places.
     const AsxPoolPair *pl = x.pool ? W.pool : nullptr;
     const AsxSpectra &from = pl ? p->bank.c : p->bslot;
     const AsxSpectra C{ (pl || (x.bc & 1)) ? from.cx : W.zxa, (pl || (x.bc & 2)) ? from.cy : W.zya, pk.nrm_part, tk.band, x.bc, pl,
-                        prune ? &W.prune : nullptr };
+                        prune ? &W.prune : nullptr, o.weight };
     if (mark(0)) return -1;
     if (pl) {
         // pool calls: the bank holds every track's forward column pass; this group only resolves its pairs into slots and offsets
@@ -947,6 +953,13 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
         if (!P.rlayout) asx_launch_inv_cols(P, q, tk, r_out, (int)g, s, find);
         else asx_launch_inv_cols_r(P, q, tk, r_out, (int)g, s, find, C.prune);
         if (first && mark(3)) return -1;
+        if (phat) {
+            // the PHAT tail: the float32 maximum stands (k_phat_finalize), then the reference's coefficient of the samples at that lag
+            asx_launch_phat_finalize(P, fin, W.seg, y.peak, (int)g, s, find);
+            if (first && mark(4)) return -1;
+            asx_launch_pearson(in, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
+            return 0;
+        }
         asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, find);
         // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
         asx_launch_refine(P, in, pk, W.seg, (int)g, s, dot_blocks, !spectral, find);
@@ -959,6 +972,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     };
     if (pass(call, true)) return -1;
     // a pair whose row is not a window: (0, NaN, -2), the others untouched (top-k: k_topk_step writes it for every entry)
+    // (a PHAT group: k_phat_finalize has given such a pair a NaN peak)
     if (call.kind == AsxSearch::ROWS && K == 1) asx_launch_invalid_rows(call.rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
     // a pool pair with an index outside its pool: (0, NaN, -4), which takes precedence over -2
     if (pl && K == 1) asx_launch_invalid_pairs(pl, y.lag, y.coef, y.ret, (int)g, s);
@@ -1145,10 +1159,13 @@ extern "C" int asx_plan_placement(asx_plan *p, double ms[2], int *kept)
     return 0;
 }
 
-// A device-resident batch of float32 pairs, after the entry point's own checks.
-static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Results &y, hipStream_t s, const Topk &topk = {})
+// A device-resident batch of float32 pairs, after the entry point's own checks.  A PHAT batch (weight) lists nothing, so it never reads
+// the overflow list: asynchronous whatever asx_plan_set_exact says.
+static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Results &y, hipStream_t s, const Topk &topk = {},
+                     AsxWeight weight = ASX_W_NONE)
 {
     prof_begin_call(p);
+    const bool exact = p->exact && weight == ASX_W_NONE;
     // chunking: groups of at most `group` pairs; with two lanes a batch is cut into at least two
     // chunks (when it is big enough to fill the chip twice) that alternate between the lanes
     const bool overlap = (p->nlanes == 2) && !p->profiling && batch >= 8;
@@ -1156,7 +1173,7 @@ static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Res
     if (overlap && batch < 2 * chunk) chunk = (batch + 1) / 2;
     // windows: the pairs between two looks at the list of overflowed pairs (asx_plan_set_exact, on by default); a
     // window is a whole number of chunks and at most `over_cap` pairs, i.e. the whole batch unless it is very long
-    const size_t window = p->exact ? std::max<size_t>(chunk, p->over_cap / chunk * chunk) : batch;
+    const size_t window = exact ? std::max<size_t>(chunk, p->over_cap / chunk * chunk) : batch;
     size_t gi = 0;
     for (size_t w0 = 0; w0 < batch; w0 += window) {
         const size_t wn = std::min(window, batch - w0);
@@ -1169,7 +1186,8 @@ static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Res
             const int lane = overlap ? (int)(gi & 1) : 0;
             hipStream_t ls = overlap ? p->lanes[lane].stream : s;
             if (run_group(p, x.at(done), g, y.at(done), ls,
-                          { .prof_group = gi, .lane = lane, .pair_base = (uint32_t)(done - w0), .listed = p->exact, .topk = topk }))
+                          { .prof_group = gi, .lane = lane, .pair_base = (uint32_t)(done - w0), .listed = exact, .topk = topk,
+                            .weight = weight }))
                 return -1;
         }
         if (overlap) {
@@ -1179,7 +1197,7 @@ static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Res
             }
         }
         // the second look, behind the window's last group (one host synchronisation per window)
-        if (p->exact && resolve_overflows(p, x.at(w0), y.at(w0), s, topk) < 0) return -1;
+        if (exact && resolve_overflows(p, x.at(w0), y.at(w0), s, topk) < 0) return -1;
     }
     prof_end_call(p, gi);
     return 0;
@@ -1206,12 +1224,13 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
 // d_windows: null, or the per-pair windows (Pairs::win), window_stride rows apart.
 static int strided_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
                          size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, const Results &y, void *stream,
-                         const Topk &topk = {})
+                         const Topk &topk = {}, AsxWeight weight = ASX_W_NONE)
 {
     PlanCall c(p, stream);
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
     hipStream_t s = c.s;
     const AsxDev &P = p->dev;
+    if (weight != ASX_W_NONE && P.rlayout != 1) return fail("%s: PHAT calls need a real-column plan (asx_plan_layout() == 1)", fn);
     if (P.rlayout) {
         // k_fwd_cols_r reads every row of a pair's inputs as 16-byte loads from the pair's first frame
         if (((uintptr_t)d_source & 15u) || ((uintptr_t)d_sample & 15u))
@@ -1236,7 +1255,7 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
         asx_launch_fwd_cols_r(P, (bc & 1) ? d_source : nullptr, 0, (bc & 2) ? d_sample : nullptr, 0, 0, 1, B, true, s);
     }
     return run_batch(p, Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, bc, d_windows, window_stride), batch, y, s,
-                     topk);
+                     topk, weight);
 }
 
 extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
@@ -1257,6 +1276,37 @@ extern "C" int asx_xcorr_windowed_f32_dev(asx_plan *p, const float *d_source, si
     if (!p || !d_source || !d_sample || !d_windows || !d_coef || !d_ret) return fail("asx_xcorr_windowed_f32_dev: null argument");
     return strided_batch(p, "asx_xcorr_windowed_f32_dev", d_source, source_stride, d_sample, sample_stride, d_windows, window_stride,
                          batch, { d_lag, d_coef, d_ret }, stream);
+}
+
+// GCC-PHAT: the strided / windowed batch with the whitened product spectrum (run_group: GroupOpts::weight).  The peak is the float32
+// argmax of r_phat under the library's rule, the coefficient the reference's at that lag in the direct form, peak its height.
+extern "C" int asx_xcorr_phat_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                      size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                      int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+{
+    if (!p || !d_source || !d_sample || !d_coef || !d_ret) return fail("asx_xcorr_phat_f32_dev: null argument");
+    return strided_batch(p, "asx_xcorr_phat_f32_dev", d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch,
+                         { d_lag, d_coef, d_ret, 1, d_peak }, stream, {}, ASX_W_PHAT);
+}
+
+// one contiguous pair through the PHAT group, r_phat of every lag (2N floats, F times the normalised value) to d_r; the plan's window
+extern "C" int asx_xcorr_phat_debug_r_dev(asx_plan *p, const float *d_source, const float *d_sample, float *d_r, int64_t *d_lag,
+                                          double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_phat_debug_r_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_ret || !d_r) return fail("%s: null argument", fn);
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    if (p->dev.rlayout != 1) return fail("%s: PHAT calls need a real-column plan (asx_plan_layout() == 1)", fn);
+    if (((uintptr_t)d_source & 15u) || ((uintptr_t)d_sample & 15u))
+        return fail("%s: real-column plans need 16-byte aligned inputs (source %p, sample %p)", fn, (const void *)d_source,
+                    (const void *)d_sample);
+    prof_begin_call(p);
+    const size_t N = p->host.N;
+    const int rc = run_group(p, Pairs<float>::contiguous(d_source, d_sample, N), 1, { d_lag, d_coef, d_ret, 1, d_peak }, c.s,
+                             { .listed = false, .spectral = false, .r_out = d_r, .weight = ASX_W_PHAT });
+    prof_end_call(p, 1);
+    return rc;
 }
 
 // The K strongest separated lags per pair: the strided / windowed batch with passes 2..k over each group's Q (run_group).  k = 1

@@ -445,6 +445,10 @@ template <int... ZC, class F> void asx_with_selection(const AsxSearch &q, F go)
 //   (a pool group: cx / cy are the bank's).  nrm and band are then the group's own places (the lane's), whatever cx / cy are: a
 //   broadcast or listed operand's are copied there (k_bcast_aux, k_pool_resolve).  asx_launch_rows_r picks its kernel by it.
 //   prune: the lane's workspace of the pruned inverse pass when the group is in scope for it (run_group decides), else null.
+//   weight: how the product spectrum is weighted before the inverse passes (AsxWeight; run_group's GroupOpts::weight).
+// ASX_W_PHAT (asx_xcorr_phat_f32_dev): every bin of X conj(Y) divided by its magnitude in the row pass (k_rows_rp), the tiny bound, and
+// k_phat_finalize in place of the exactness machinery.
+enum AsxWeight { ASX_W_NONE = 0, ASX_W_PHAT = 1 };
 struct AsxSpectra {
     float2 *cx, *cy;
     float *nrm;
@@ -452,6 +456,7 @@ struct AsxSpectra {
     int bc = 0;
     const AsxPoolPair *pl = nullptr;
     const AsxPrune *prune = nullptr;
+    AsxWeight weight = ASX_W_NONE;
 };
 // float2 elements of one track's column spectrum: rows k1 = 0 .. M1 of M2 columns, the pitch between the tracks of a set
 inline size_t asx_spectrum_len(const AsxDev &P) { return ((size_t)P.M1 + 1) * (size_t)P.M2; }
@@ -498,6 +503,10 @@ void asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride,
 void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s);
 void asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                            const AsxSearch &search, const AsxPrune *U);
+// the tail of a PHAT group (rlayout.hip: k_phat_finalize), behind the inverse column pass and in front of the direct Pearson launch:
+// seg from the float32 running maximum alone, refine_n = 0, peak[pair] = |r_phat[lag]| / F (peak may be null)
+void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, double *peak, int npairs, hipStream_t s,
+                              const AsxSearch &q);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 // pool calls: each pair's record (out) and its two slots' norm partials and band sums (band may be null) into the group's places

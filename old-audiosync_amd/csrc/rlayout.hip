@@ -208,11 +208,31 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 //   hold a tile and add it in four DPP steps inside their row, the balanced tree ((0+1)+(2+3))+... that tree_sum<16> is; one lane
 //   of the sixteen stores.  No atomics: the same Q gives the same bits.  Nothing is loaded for it.  (Lanes are four dwords apart:
 //   a four-way bank conflict on these stores and loads, a few hundred LDS cycles per block.)
+//   PHAT (k_rows_rp, asx_xcorr_phat_f32_dev): the phase transform.  Every bin of the product X conj(Y) is divided by its magnitude in
+//   the registers where it is formed, between the product and the first inverse butterfly (phat_unit below), so that the inverse
+//   passes deliver r_phat, whose every frequency has one vote.  Nothing of the float32 error bound holds for a whitened spectrum:
+//   row 0's block leaves the smallest positive normal float as the pair's bound (zero for a silent track, as ever), with which the
+//   unchanged k_inv_cols_r instances keep the float32 maximum and list exact float32 ties only.
 // ---------------------------------------------------------------------------
+// q / |q| for every finite non-zero float32 q, whatever its exponent: the exponent of max(|re|, |im|) is taken out first, so the
+// larger component lies in [1/2, 1) and the sum of squares in [1/4, 2) -- re * re + im * im of the bin itself overflows from 2^64
+// on and is flushed below 2^-63, inputs the plain path handles.  v_rsq_f32 is good to one ulp; one Newton step brings |q'| to
+// within two roundings of 1.  q = 0 exactly gives 0 (a bin nobody has a phase for casts no vote); a NaN component makes both NaN.
+__device__ __forceinline__ Cx1 phat_unit(Cx1 q)
+{
+    const float m = fmaxf(fabsf(q.re), fabsf(q.im));
+    const int e = __builtin_amdgcn_frexp_expf(m);
+    const float a = ldexpf(q.re, -e), b = ldexpf(q.im, -e);
+    const float n2 = fmaf(a, a, b * b);
+    float y = __builtin_amdgcn_rsqf(n2);
+    y = fmaf(y, fmaf(-0.5f * n2 * y, y, 0.5f), y); // y + y (1/2 - n2 y^2 / 2)
+    return m == 0.f ? Cx1{ 0.f, 0.f } : Cx1{ a * y, b * y };
+}
+
 // The body takes P and W by value: that call boundary loads their fields at the top of the kernel.  Written inside the __global__
 // itself the instruction stream changes, and with it the float32 rounding of r (11 of the headline's 124 coefficients moved by
 // about 1e-7).
-template <class S, int NT, bool TWO, int BC, bool ENG = false>
+template <class S, int NT, bool TWO, int BC, bool ENG = false, bool PHAT = false>
 __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restrict__ cx, const float2 *__restrict__ cy,
                                             float2 *__restrict__ qo, int nrows, size_t pitch_x, size_t pitch_y, size_t pitch_q,
                                             AsxPeakWs W, const AsxPoolPair *__restrict__ L = nullptr, float *__restrict__ eng = nullptr)
@@ -261,7 +281,8 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
         for (int t = tid; t < P.ntiles; t += 64) { sx += np[t]; sy += np[P.ntiles + t]; }
         sx = wave_sum_f32(sx); sy = wave_sum_f32(sy);
         if (tid == 0) {
-            W.bound2[pair] = P.bound_scale * sqrtf(sx) * sqrtf(sy);
+            if constexpr (PHAT) W.bound2[pair] = (sx != 0.f && sy != 0.f) ? 1.17549435e-38f : 0.f; // FLT_MIN: exact ties only
+            else W.bound2[pair] = P.bound_scale * sqrtf(sx) * sqrtf(sy);
             W.pairmax[pair] = 0;
             W.cand_n[pair] = 0;
         }
@@ -409,6 +430,7 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
                 // src/cross_correlation.c:232-233: X * conj(Y); member x = source, member y = sample
                 pr[T] = Cx1{ v[T].re.x * v[T].re.y + v[T].im.x * v[T].im.y, v[T].im.x * v[T].re.y - v[T].re.x * v[T].im.y };
             });
+            if constexpr (PHAT) static_for<0, R2>([&](auto T) __attribute__((always_inline)) { pr[T] = phat_unit(pr[T]); });
             Bfly<R2, true>::run(pr);
             static_for<0, R2>([&](auto T) __attribute__((always_inline)) { lds_put1(p + decltype(T)::value, pr[T]); });
         }
@@ -530,6 +552,16 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_re(
                                                                                  float *__restrict__ eng)
 {
     rows_r_body<S, NT, TWO, 0, true>(P, cx, cy, qo, nrows, pair_pitch, pair_pitch, pair_pitch, W, nullptr, eng);
+}
+
+// The row pass of a PHAT group (asx_launch_rows_r, AsxSpectra::weight == ASX_W_PHAT): k_rows_r<S, NT, TWO, BC> with the whitened product
+// (PHAT above).  A kernel name of its own, like k_rows_re: the twelve k_rows_r instances stay the kernels they were.
+template <class S, int NT, bool TWO, int BC>
+__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rp(const RArgs P, const float2 *__restrict__ cx,
+                                                                                 const float2 *__restrict__ cy, float2 *__restrict__ qo,
+                                                                                 int nrows, size_t pair_pitch, AsxPeakWs W)
+{
+    rows_r_body<S, NT, TWO, BC, false, true>(P, cx, cy, qo, nrows, (BC & 1) ? 0 : pair_pitch, (BC & 2) ? 0 : pair_pitch, pair_pitch, W);
 }
 
 // The listed form (asx_xcorr_pool_f32_dev): pair p's C_x / C_y are rows L[p].sx / L[p].sy of the bank (cx, cy: its source and sample
@@ -1235,6 +1267,34 @@ __global__ __launch_bounds__(256) void k_prune_select(const float *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// k_phat_finalize: grid (npairs / 256), a thread per pair.  The tail of a PHAT group behind k_inv_cols_r: the float32 running maximum IS
+// the answer -- the reference's rule (src/cross_correlation.c:52-67: the seed signed, then fabs and a strict '>') applied to the
+// float32 values of r_phat, the smallest index among equal ones, which is what pairmax encodes.  No candidate is read, no pair is
+// listed, counted or marked: seg (flags 0; the seed when nothing was seen -- a silent track -- found as k_finalize finds it),
+// refine_n = 0, and peak = |r_phat[lag]| / F.  A pair whose row is not a window gets a NaN peak (k_invalid_rows writes the rest).
+// ---------------------------------------------------------------------------
+template <class Sel>
+__global__ __launch_bounds__(256) void k_phat_finalize(AsxPeakWs W, AsxSeg *__restrict__ seg, double *__restrict__ peak, uint32_t N,
+                                                        double f, int npairs, Sel sel)
+{
+    const int pair = blockIdx.x * 256 + threadIdx.x;
+    if (pair >= npairs) return;
+    const asx_peak_t best = W.pairmax[pair];
+    seg[pair] = make_seg(best ? peak_index(best) : sel.seed_of((size_t)pair, N), N);
+    W.refine_n[pair] = 0u;
+    if (!peak) return;
+    // the key is |r| everywhere but at the seed, which competes signed; an empty maximum (a silent track) stands for r = 0; a NaN seed
+    // was packed as -infinity (peak_pack_key)
+    const float key = best ? peak_key(best) : 0.f;
+    double v = key == -INFINITY ? (double)NAN : fabs((double)key) / f;
+    if constexpr (std::is_same<Sel, AsxWinRows>::value) {
+        AsxWin z;
+        if (!asx_win_row(sel, (size_t)pair, N, z)) v = (double)NAN;
+    }
+    peak[pair] = v;
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 // one flavour of k_rows_r, with the flavour's extra argument (none: k_rows_r itself)
@@ -1249,14 +1309,22 @@ static void launch_rows_r(K kernel, const AsxDev &P, int nt, const AsxSpectra &C
 
 // The row pass of a group whose spectra are C, which decides the flavour: k_rows_re (plus the tile energies C.prune->eng) when the
 // group is in scope for pruning, k_rows_rl (C_x / C_y at the pairs' bank slots) in a pool group, else k_rows_r in the broadcast form
-// C.bc.  The operands that are not broadcast and q have the group workspace's pair pitch.
+// C.bc -- or, in a PHAT group (C.weight; never pruned, never a pool group), k_rows_rp in that form.  The operands that are not
+// broadcast and q have the group workspace's pair pitch.
 void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s)
 {
     asx_with_entry(AsxRRows{}, P.krows, [&](auto e) {
         using S = typename decltype(e)::sched;
         constexpr int NT = e.nt, nt = e.two ? 2 * NT : NT;
         constexpr bool TWO = e.two;
-        if (C.prune) launch_rows_r(k_rows_re<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.prune->eng);
+        if (C.weight == ASX_W_PHAT)
+            switch (C.bc) {
+            case 0: launch_rows_r(k_rows_rp<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s); break;
+            case 1: launch_rows_r(k_rows_rp<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s); break;
+            case 2: launch_rows_r(k_rows_rp<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s); break;
+            default: launch_rows_r(k_rows_rp<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s); break;
+            }
+        else if (C.prune) launch_rows_r(k_rows_re<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.prune->eng);
         else if (C.pl) launch_rows_r(k_rows_rl<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl);
         else
             switch (C.bc) {
@@ -1265,6 +1333,16 @@ void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const As
             case 2: launch_rows_r(k_rows_r<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s); break;
             default: launch_rows_r(k_rows_r<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s); break;
             }
+    });
+}
+
+void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, double *peak, int npairs, hipStream_t s,
+                              const AsxSearch &q)
+{
+    asx_with_selection(q, [&](auto sel) {
+        if constexpr (!std::is_same<decltype(sel), AsxSelTopkSeed>::value) // (top-k with PHAT does not exist)
+            hipLaunchKernelGGL(k_phat_finalize<decltype(sel)>, dim3((unsigned)(npairs + 255) / 256), dim3(256), 0, s, W, seg, peak, P.N,
+                               (double)P.F, npairs, sel);
     });
 }
 

@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "asx_plan_set_pearson", "asx_plan_pearson_modes", "asx_plan_placement", "asx_host_malloc", "asx_host_free", "asx_shard_range", "asx_result_bytes", "asx_comm_create", "asx_comm_destroy", "asx_xcorr_batch_multi_dev",
     "asx_xcorr_strided_f32_dev", "asx_plan_set_lag_window", "asx_plan_lag_window", "asx_stream_set_lag_window",
     "asx_xcorr_windowed_f32_dev", "asx_xcorr_topk_f32_dev", "asx_xcorr_pool_f32_dev", "asx_xcorr_pool_topk_f32_dev",
-    "asx_topk_best_dev", "asx_plan_set_prune", "asx_plan_prune_stats",
+    "asx_topk_best_dev", "asx_plan_set_prune", "asx_plan_prune_stats", "asx_xcorr_phat_f32_dev", "asx_xcorr_phat_debug_r_dev",
 ]
 
 TOPK_MAX = 8  # ASX_TOPK_MAX, include/audiosync/xcorr_hip.h
@@ -119,6 +119,11 @@ def lib():
     L.asx_xcorr_windowed_f32_dev.restype = ctypes.c_int
     L.asx_xcorr_windowed_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
                                              vp, vp, vp, vp]
+    L.asx_xcorr_phat_f32_dev.restype = ctypes.c_int
+    L.asx_xcorr_phat_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
+                                         vp, vp, vp, vp, vp]
+    L.asx_xcorr_phat_debug_r_dev.restype = ctypes.c_int
+    L.asx_xcorr_phat_debug_r_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.asx_xcorr_topk_f32_dev.restype = ctypes.c_int
     L.asx_xcorr_topk_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
                                          ctypes.c_int, ctypes.c_int64, vp, vp, vp, vp]
@@ -753,6 +758,24 @@ class Plan:
         if rc != 0:
             raise AsxError(_err())
 
+    def xcorr_phat_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, d_lag, d_coef, d_peak, d_ret,
+                       stream=0):
+        """raw device pointers (ints): asx_xcorr_phat_f32_dev -- the strided batch ranked by the GCC-PHAT curve; d_windows = 0: the
+        plan's window applies, else per-pair rows as in xcorr_windowed_dev; d_peak (float64, may be 0) receives |r_phat[lag]| / F;
+        always asynchronous on `stream`"""
+        rc = lib().asx_xcorr_phat_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride), d_windows or None,
+                                          int(window_stride), int(batch), d_lag or None, d_coef or None, d_peak or None,
+                                          d_ret or None, stream or None)
+        if rc != 0:
+            raise AsxError(_err())
+
+    def phat_debug_r_dev(self, d_src, d_smp, d_r, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_phat_debug_r_dev -- one contiguous pair, r_phat of all 2N lags (times F) to d_r"""
+        rc = lib().asx_xcorr_phat_debug_r_dev(self._h, d_src or None, d_smp or None, d_r or None, d_lag or None, d_coef or None,
+                                              d_peak or None, d_ret or None, stream or None)
+        if rc != 0:
+            raise AsxError(_err())
+
     def xcorr_topk_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, k, min_separation, d_lag, d_coef,
                        d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_topk_f32_dev -- the k strongest lags of pair i at least min_separation apart, entry j
@@ -928,6 +951,41 @@ class Plan:
         anything is uploaded.  Returns (lag int64 [B, k], coef float64 [B, k], ret int32 [B, k]); ret = -3 where no lag was left."""
         s, t, w, batch, ss, ts, ws, k, sep = topk_args(self.sample_len, source, sample, k, min_separation, windows)
         return self._strided_host(s, ss, t, ts, batch, w, ws, topk=(k, sep))
+
+    def xcorr_phat_f32(self, source, sample, windows=None):
+        """Pairs ranked by the GCC-PHAT curve (asx_xcorr_phat_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N]; a
+        1-D operand serves every pair.  windows: None (the plan's window), or integers [2] / [B, 2] as in xcorr_windowed_f32.
+        Returns (lag int64[B], coef float64[B], peak float64[B], ret int32[B]): the float32 argmax of r_phat, the reference's
+        Pearson coefficient of the samples at that lag, and the peak height |r_phat[lag]| / F in [0, 1]."""
+        n = self.sample_len
+        s, t, w, batch, ss, ts, ws = windowed_args(n, source, sample, np.zeros(2, dtype=np.int64) if windows is None else windows)
+        if windows is None:
+            w, ws = None, 0
+        L = lib()
+        bufs = []
+        try:
+            def dev(host=None, nbytes=0):
+                nbytes = host.nbytes if host is not None else nbytes
+                ptr = L.asx_device_malloc(max(int(nbytes), 16), self.device)
+                if not ptr:
+                    raise AsxError(_err())
+                bufs.append(ptr)
+                if host is not None and L.asx_memcpy_h2d(ptr, host.ctypes.data, nbytes) != 0:
+                    raise AsxError(_err())
+                return ptr
+            d_src, d_smp = dev(s), dev(t)
+            d_win = dev(w) if w is not None else 0
+            out = [np.zeros(batch, dtype=dt) for dt in (np.int64, np.float64, np.float64, np.int32)]
+            d_out = [dev(nbytes=h.nbytes) for h in out]
+            self.xcorr_phat_dev(d_src, ss, d_smp, ts, d_win, ws, batch, *d_out)
+            self.sync()
+            for h, d in zip(out, d_out):
+                if L.asx_memcpy_d2h(h.ctypes.data, d, h.nbytes) != 0:
+                    raise AsxError(_err())
+            return tuple(out)
+        finally:
+            for ptr in bufs:
+                L.asx_device_free(ptr)
 
     def _strided_host(self, src, src_stride, smp, smp_stride, batch, windows=None, window_stride=0, topk=None):
         """host float32 buffers (and int64 windows) -> device copies -> asx_xcorr_strided_f32_dev (asx_xcorr_windowed_f32_dev;
