@@ -329,12 +329,40 @@ int asx_xcorr_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_
  * and asx_plan_prune_stats unchanged (the pruned inverse pass is never used: |Q'| = 1 makes its energy bound useless).  It
  * allocates nothing after plan creation, but for the broadcast slot's first allocation under asx_xcorr_strided_f32_dev's rule.
  *   Weakness.  Bins that hold only rounding noise vote too: on band-limited material the empty part of the spectrum adds noise
- * to r_phat and lowers the peak.  A magnitude floor is future work.  Not offered with PHAT: pools, top-k, the double ABI,
- * streams, packed plans. */
+ * to r_phat and lowers the peak.  asx_xcorr_phat_band_f32_dev, below, lets only a chosen range of bins vote.  Not offered with
+ * PHAT: pools, top-k, the double ABI, streams, packed plans. */
 int asx_xcorr_phat_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
                            const float *d_sample, size_t sample_stride,
                            const int64_t *d_windows, size_t window_stride, size_t batch,
                            int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
+/* Band-limited GCC-PHAT: asx_xcorr_phat_f32_dev in which only the bins of a frequency band vote.  Most material is band-limited
+ * (speech, codecs that low-pass, hum and rumble at the bottom): outside its band the cross spectrum is rounding noise, and with
+ * every bin at unit weight that noise lowers the peak and can move it.  Everything asx_xcorr_phat_f32_dev says holds, but for this:
+ *   The band.  Bins are those of the length-F = 2N real transform: bin m, 0 <= m <= N, is the frequency m * rate / (2N)
+ * (asx_band_bins converts).  Q'[k] = Q[k] / |Q[k]| when bin_lo <= min(k, F - k) <= bin_hi and Q[k] != 0, and Q'[k] = 0 otherwise: a
+ * bin and its mirror are one frequency, so r_phat stays real.  The band must satisfy 0 <= bin_lo <= bin_hi <= N; any other returns
+ * -1 with nothing launched and the outputs untouched, as every refusal of asx_xcorr_phat_f32_dev does here too.  One band per
+ * call, for every pair.
+ *   The peak.  peak = |r_phat[lag]| / V with V = 2 (bin_hi - bin_lo + 1) - [bin_lo == 0] - [bin_hi == N], the number of k in
+ * [0, F) that vote: between 0 and 1, and 1 for a pure circular delay whatever the band.  A narrow band makes a wide peak: what
+ * the float32 argmax resolves is still the float32 error of r_phat / V over the lags (tests/test_gpu_phat_band.py).
+ *   The full band [0, N] IS asx_xcorr_phat_f32_dev: the same kernels, the same bits.
+ *   Measured on float64 models of three pairs low-passed at N/6 with noise of 1e-4 under them (N = 144 000, tests/test_phat_band.py):
+ * peak 0.041 / 0.027 / 0.096 with every bin voting, one lag wrong; 0.248 / 0.148 / 0.570 with bins [1, N/6], every lag right.
+ *   The call costs what asx_xcorr_phat_f32_dev costs, within two percent either way by the band (measured: DESIGN.md); rows
+ * that hold no bin of the band are not skipped.  Not offered: a band per pair, a magnitude floor, an exponent. */
+int asx_xcorr_phat_band_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                                const float *d_sample, size_t sample_stride,
+                                const int64_t *d_windows, size_t window_stride, size_t batch,
+                                int64_t bin_lo, int64_t bin_hi,
+                                int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
+/* The bins of the band [f_lo_hz, f_hi_hz] for a plan of sample_len = N at sample_rate: bin_lo = ceil(f_lo 2N / rate), bin_hi =
+ * min(N, floor(f_hi 2N / rate)) (a band that reaches past the Nyquist frequency ends there).  Host arithmetic, no device.  Returns
+ * 0, or -1 with the outputs untouched for a rate that is not positive, f_lo < 0, f_lo > f_hi, a NaN, or a band that holds no bin. */
+int asx_band_bins(size_t sample_len, double sample_rate, double f_lo_hz, double f_hi_hz,
+                  int64_t *bin_lo, int64_t *bin_hi);
 
 /* Many tracks against many: listed pairs of two track pools, every track transformed once per call.
  * Source track a is d_sources + a*source_stride (2N floats), sample track b is d_samples + b*sample_stride
@@ -448,6 +476,11 @@ int asx_xcorr_debug_r_dev(asx_plan *plan, const float *d_source, const float *d_
  * unnormalised (F times the value that peak reports).  d_r, d_coef and d_ret must not be NULL; real-column plans only. */
 int asx_xcorr_phat_debug_r_dev(asx_plan *plan, const float *d_source, const float *d_sample, float *d_r,
                                int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
+/* ... and for asx_xcorr_phat_band_f32_dev: d_r is V times the value that peak reports (V: the number of bins that vote). */
+int asx_xcorr_phat_band_debug_r_dev(asx_plan *plan, const float *d_source, const float *d_sample,
+                                    int64_t bin_lo, int64_t bin_hi, float *d_r,
+                                    int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
 
 /* pearson_coefficient() on two equal-length host double ranges. Writes the
  * coefficient (NaN for a constant range, like the reference). */

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cassert>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -873,7 +874,10 @@ struct GroupOpts {
     // How the product spectrum is weighted (asx_internal.h).  ASX_W_PHAT (asx_xcorr_phat_f32_dev, real-column plans, k = 1, no pool):
     // the row pass's PHAT flavour and the PHAT tail -- k_phat_finalize, the direct Pearson form, k_invalid_rows -- with no pruned
     // pass, no list and no spectral form, whatever the plan's switches say: none of them means anything for a whitened spectrum.
+    // ASX_W_PHAT_BAND (asx_xcorr_phat_band_f32_dev): the same group, but only the bins of `fband` vote (k_rows_rb) and the peak height is
+    // per voter (AsxBand::votes).  The entry points turn the full band into ASX_W_PHAT (band_weight).
     AsxWeight weight = ASX_W_NONE;
+    AsxBand fband{};
 };
 
 // One group: g <= plan->group pairs, the first g of x, results to the first g of y.
@@ -885,7 +889,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     const AsxPeakWs &pk = o.pk ? *o.pk : W.pk;
     auto mark = [&](size_t k) { return o.prof_group != GroupOpts::no_marks && prof_mark(p, s, o.prof_group * 6 + k); };
     AsxPeakWs fin = pk;
-    const bool phat = o.weight == ASX_W_PHAT;
+    const bool phat = o.weight != ASX_W_NONE;
     if (!o.listed || phat) { fin.over_list = nullptr; fin.over_n = nullptr; fin.over_host = nullptr; fin.over_cap = 0; }
     const bool spectral = std::is_same<TIn, float>::value && p->spectral && o.spectral && pk.band && !phat;
     AsxPeakWs tk = pk; // what the transform kernels see
@@ -905,7 +909,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     const AsxPoolPair *pl = x.pool ? W.pool : nullptr;
     const AsxSpectra &from = pl ? p->bank.c : p->bslot;
     const AsxSpectra C{ (pl || (x.bc & 1)) ? from.cx : W.zxa, (pl || (x.bc & 2)) ? from.cy : W.zya, pk.nrm_part, tk.band, x.bc, pl,
-                        prune ? &W.prune : nullptr, o.weight };
+                        prune ? &W.prune : nullptr, o.weight, o.fband };
     if (mark(0)) return -1;
     if (pl) {
         // pool calls: the bank holds every track's forward column pass; this group only resolves its pairs into slots and offsets
@@ -955,7 +959,8 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
         if (first && mark(3)) return -1;
         if (phat) {
             // the PHAT tail: the float32 maximum stands (k_phat_finalize), then the reference's coefficient of the samples at that lag
-            asx_launch_phat_finalize(P, fin, W.seg, y.peak, (int)g, s, find);
+            // (the peak height is per bin that voted)
+            asx_launch_phat_finalize(P, fin, W.seg, y.peak, o.weight == ASX_W_PHAT_BAND ? o.fband.votes(P.N) : (double)P.F, (int)g, s, find);
             if (first && mark(4)) return -1;
             asx_launch_pearson(in, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
             return 0;
@@ -1162,7 +1167,7 @@ extern "C" int asx_plan_placement(asx_plan *p, double ms[2], int *kept)
 // A device-resident batch of float32 pairs, after the entry point's own checks.  A PHAT batch (weight) lists nothing, so it never reads
 // the overflow list: asynchronous whatever asx_plan_set_exact says.
 static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Results &y, hipStream_t s, const Topk &topk = {},
-                     AsxWeight weight = ASX_W_NONE)
+                     AsxWeight weight = ASX_W_NONE, const AsxBand &band = {})
 {
     prof_begin_call(p);
     const bool exact = p->exact && weight == ASX_W_NONE;
@@ -1187,7 +1192,7 @@ static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Res
             hipStream_t ls = overlap ? p->lanes[lane].stream : s;
             if (run_group(p, x.at(done), g, y.at(done), ls,
                           { .prof_group = gi, .lane = lane, .pair_base = (uint32_t)(done - w0), .listed = exact, .topk = topk,
-                            .weight = weight }))
+                            .weight = weight, .fband = band }))
                 return -1;
         }
         if (overlap) {
@@ -1224,7 +1229,7 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
 // d_windows: null, or the per-pair windows (Pairs::win), window_stride rows apart.
 static int strided_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
                          size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, const Results &y, void *stream,
-                         const Topk &topk = {}, AsxWeight weight = ASX_W_NONE)
+                         const Topk &topk = {}, AsxWeight weight = ASX_W_NONE, const AsxBand &band = {})
 {
     PlanCall c(p, stream);
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
@@ -1255,7 +1260,7 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
         asx_launch_fwd_cols_r(P, (bc & 1) ? d_source : nullptr, 0, (bc & 2) ? d_sample : nullptr, 0, 0, 1, B, true, s);
     }
     return run_batch(p, Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, bc, d_windows, window_stride), batch, y, s,
-                     topk, weight);
+                     topk, weight, band);
 }
 
 extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
@@ -1289,12 +1294,38 @@ extern "C" int asx_xcorr_phat_f32_dev(asx_plan *p, const float *d_source, size_t
                          { d_lag, d_coef, d_ret, 1, d_peak }, stream, {}, ASX_W_PHAT);
 }
 
-// one contiguous pair through the PHAT group, r_phat of every lag (2N floats, F times the normalised value) to d_r; the plan's window
-extern "C" int asx_xcorr_phat_debug_r_dev(asx_plan *p, const float *d_source, const float *d_sample, float *d_r, int64_t *d_lag,
-                                          double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+// The weighting of a banded PHAT call: bins [bin_lo, bin_hi] of the F = 2N point transform, 0 <= bin_lo <= bin_hi <= N.  The full band
+// is plain PHAT -- the kernels and the bits of asx_xcorr_phat_f32_dev, as the full lag window is no window.  false: not a band.
+static bool band_weight(const asx_plan *p, int64_t bin_lo, int64_t bin_hi, AsxWeight &weight, AsxBand &band)
 {
-    static const char *fn = "asx_xcorr_phat_debug_r_dev";
-    if (!p || !d_source || !d_sample || !d_coef || !d_ret || !d_r) return fail("%s: null argument", fn);
+    const int64_t N = (int64_t)p->host.N;
+    if (bin_lo < 0 || bin_lo > bin_hi || bin_hi > N) return false;
+    const bool full = bin_lo == 0 && bin_hi == N;
+    weight = full ? ASX_W_PHAT : ASX_W_PHAT_BAND;
+    band = full ? AsxBand{} : AsxBand{ (uint32_t)bin_lo, (uint32_t)(bin_hi - bin_lo) };
+    return true;
+}
+
+// GCC-PHAT in which only the bins of a band vote: asx_xcorr_phat_f32_dev with the banded row pass and the peak height per voter.
+extern "C" int asx_xcorr_phat_band_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                           size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                           int64_t bin_lo, int64_t bin_hi, int64_t *d_lag, double *d_coef, double *d_peak,
+                                           int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_phat_band_f32_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_ret) return fail("%s: null argument", fn);
+    AsxWeight weight;
+    AsxBand band;
+    if (!band_weight(p, bin_lo, bin_hi, weight, band))
+        return fail("%s: bins [%lld, %lld] are not a band inside [0, %zu]", fn, (long long)bin_lo, (long long)bin_hi, (size_t)p->host.N);
+    return strided_batch(p, fn, d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch,
+                         { d_lag, d_coef, d_ret, 1, d_peak }, stream, {}, weight, band);
+}
+
+// one contiguous pair through a PHAT group (weight, band), r_phat of every lag (2N floats, unnormalised) to d_r; the plan's window
+static int phat_debug_r(asx_plan *p, const char *fn, const float *d_source, const float *d_sample, float *d_r, const Results &y,
+                        void *stream, AsxWeight weight, const AsxBand &band)
+{
     PlanCall c(p, stream);
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
     if (p->dev.rlayout != 1) return fail("%s: PHAT calls need a real-column plan (asx_plan_layout() == 1)", fn);
@@ -1303,10 +1334,45 @@ extern "C" int asx_xcorr_phat_debug_r_dev(asx_plan *p, const float *d_source, co
                     (const void *)d_sample);
     prof_begin_call(p);
     const size_t N = p->host.N;
-    const int rc = run_group(p, Pairs<float>::contiguous(d_source, d_sample, N), 1, { d_lag, d_coef, d_ret, 1, d_peak }, c.s,
-                             { .listed = false, .spectral = false, .r_out = d_r, .weight = ASX_W_PHAT });
+    const int rc = run_group(p, Pairs<float>::contiguous(d_source, d_sample, N), 1, y, c.s,
+                             { .listed = false, .spectral = false, .r_out = d_r, .weight = weight, .fband = band });
     prof_end_call(p, 1);
     return rc;
+}
+
+extern "C" int asx_xcorr_phat_debug_r_dev(asx_plan *p, const float *d_source, const float *d_sample, float *d_r, int64_t *d_lag,
+                                          double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_phat_debug_r_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_ret || !d_r) return fail("%s: null argument", fn);
+    return phat_debug_r(p, fn, d_source, d_sample, d_r, { d_lag, d_coef, d_ret, 1, d_peak }, stream, ASX_W_PHAT, {});
+}
+
+// the same for the banded call: d_r holds votes times what peak reports
+extern "C" int asx_xcorr_phat_band_debug_r_dev(asx_plan *p, const float *d_source, const float *d_sample, int64_t bin_lo,
+                                               int64_t bin_hi, float *d_r, int64_t *d_lag, double *d_coef, double *d_peak,
+                                               int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_phat_band_debug_r_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_ret || !d_r) return fail("%s: null argument", fn);
+    AsxWeight weight;
+    AsxBand band;
+    if (!band_weight(p, bin_lo, bin_hi, weight, band))
+        return fail("%s: bins [%lld, %lld] are not a band inside [0, %zu]", fn, (long long)bin_lo, (long long)bin_hi, (size_t)p->host.N);
+    return phat_debug_r(p, fn, d_source, d_sample, d_r, { d_lag, d_coef, d_ret, 1, d_peak }, stream, weight, band);
+}
+
+// The bins of a frequency band, for the banded call: bin m of the F = 2N point transform is m * rate / (2N) Hz.  Host arithmetic only.
+extern "C" int asx_band_bins(size_t sample_len, double sample_rate, double f_lo_hz, double f_hi_hz, int64_t *bin_lo, int64_t *bin_hi)
+{
+    // (every comparison with a NaN is false: written so that a NaN fails)
+    if (!bin_lo || !bin_hi || sample_len == 0 || !(sample_rate > 0.0) || !(f_lo_hz >= 0.0) || !(f_lo_hz <= f_hi_hz)) return -1;
+    const double n = (double)sample_len, per_hz = 2.0 * n / sample_rate;
+    const double lo = std::ceil(f_lo_hz * per_hz), hi = std::min(n, std::floor(f_hi_hz * per_hz));
+    if (!(lo <= hi)) return -1; // no bin inside (or an infinite rate or frequency made a NaN)
+    *bin_lo = (int64_t)lo;
+    *bin_hi = (int64_t)hi;
+    return 0;
 }
 
 // The K strongest separated lags per pair: the strided / windowed batch with passes 2..k over each group's Q (run_group).  k = 1

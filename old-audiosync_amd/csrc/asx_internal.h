@@ -448,7 +448,16 @@ template <int... ZC, class F> void asx_with_selection(const AsxSearch &q, F go)
 //   weight: how the product spectrum is weighted before the inverse passes (AsxWeight; run_group's GroupOpts::weight).
 // ASX_W_PHAT (asx_xcorr_phat_f32_dev): every bin of X conj(Y) divided by its magnitude in the row pass (k_rows_rp), the tiny bound, and
 // k_phat_finalize in place of the exactness machinery.
-enum AsxWeight { ASX_W_NONE = 0, ASX_W_PHAT = 1 };
+// ASX_W_PHAT_BAND (asx_xcorr_phat_band_f32_dev): the same, but only the bins whose frequency min(k, F - k) lies in the band vote
+// (k_rows_rb sets the others to zero), and k_phat_finalize divides by the number of voters.  The full band is ASX_W_PHAT.
+enum AsxWeight { ASX_W_NONE = 0, ASX_W_PHAT = 1, ASX_W_PHAT_BAND = 2 };
+// The band of an ASX_W_PHAT_BAND group, bins of the F = 2N point transform: lo <= min(k, F - k) <= lo + span, lo + span <= N.  Kept
+// as the two operands of the kernel's unsigned range compare; passed to k_rows_rb by value.
+struct AsxBand {
+    uint32_t lo = 0, span = 0;
+    // bins k of [0, F) inside: a bin and its mirror both vote, bins 0 and N are their own mirrors
+    double votes(uint32_t N) const { return 2.0 * ((double)span + 1.0) - (lo == 0) - (lo + span == N); }
+};
 struct AsxSpectra {
     float2 *cx, *cy;
     float *nrm;
@@ -457,6 +466,7 @@ struct AsxSpectra {
     const AsxPoolPair *pl = nullptr;
     const AsxPrune *prune = nullptr;
     AsxWeight weight = ASX_W_NONE;
+    AsxBand fband{}; // the frequency band that votes: weight == ASX_W_PHAT_BAND only
 };
 // float2 elements of one track's column spectrum: rows k1 = 0 .. M1 of M2 columns, the pitch between the tracks of a set
 inline size_t asx_spectrum_len(const AsxDev &P) { return ((size_t)P.M1 + 1) * (size_t)P.M2; }
@@ -504,8 +514,9 @@ void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const As
 void asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                            const AsxSearch &search, const AsxPrune *U);
 // the tail of a PHAT group (rlayout.hip: k_phat_finalize), behind the inverse column pass and in front of the direct Pearson launch:
-// seg from the float32 running maximum alone, refine_n = 0, peak[pair] = |r_phat[lag]| / F (peak may be null)
-void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, double *peak, int npairs, hipStream_t s,
+// seg from the float32 running maximum alone, refine_n = 0, peak[pair] = |r_phat[lag]| / f (peak may be null); f: the number of bins
+// that voted -- F, or AsxBand::votes in a banded group
+void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, double *peak, double f, int npairs, hipStream_t s,
                               const AsxSearch &q);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);

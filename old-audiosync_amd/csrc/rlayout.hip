@@ -213,6 +213,15 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 //   passes deliver r_phat, whose every frequency has one vote.  Nothing of the float32 error bound holds for a whitened spectrum:
 //   row 0's block leaves the smallest positive normal float as the pair's bound (zero for a silent track, as ever), with which the
 //   unchanged k_inv_cols_r instances keep the float32 maximum and list exact float32 ties only.
+//   BAND (k_rows_rb, asx_xcorr_phat_band_f32_dev; with PHAT): only a range of frequencies votes.  Behind phat_unit every bin of the
+//   thread is kept when min(k, F - k) lies in [lo, lo + span] and set to zero otherwise.  Where a bin is at that point: forward
+//   stage 0 is decimation in frequency, so unit u holds the bins k2 = u (mod R0); stage 1 leaves residue jl (mod R1) in the R2 slots
+//   from jl * R2; stage 2's output T is the last digit: k2 = u + R0 (jl + R1 T) inside a (sub-)row (tests/model_fourstep.py:
+//   position_table).  The two-half form's half 0 holds the even bins and half 1 the odd ones, k2 -> 2 k2 + half; and row k1 holds
+//   k = k1 + 2 M1 k2.  From T to T + 1 the bin moves by a step that is the same for every thread: one multiply for the first bin,
+//   then an addition, two subtractions, two unsigned compares and two selects per bin.  Rows hold bins above N too (rows 0 and
+//   M1 hold a bin and its mirror; the mirrors of the other rows' bins are in NO row, the inverse column pass makes them up), hence
+//   the test on both k and F - k.  The band arrives by value as a kernel argument: nothing is looked up, no load is added or moved.
 // ---------------------------------------------------------------------------
 // q / |q| for every finite non-zero float32 q, whatever its exponent: the exponent of max(|re|, |im|) is taken out first, so the
 // larger component lies in [1/2, 1) and the sum of squares in [1/4, 2) -- re * re + im * im of the bin itself overflows from 2^64
@@ -232,12 +241,14 @@ __device__ __forceinline__ Cx1 phat_unit(Cx1 q)
 // The body takes P and W by value: that call boundary loads their fields at the top of the kernel.  Written inside the __global__
 // itself the instruction stream changes, and with it the float32 rounding of r (11 of the headline's 124 coefficients moved by
 // about 1e-7).
-template <class S, int NT, bool TWO, int BC, bool ENG = false, bool PHAT = false>
+template <class S, int NT, bool TWO, int BC, bool ENG = false, bool PHAT = false, bool BAND = false>
 __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restrict__ cx, const float2 *__restrict__ cy,
                                             float2 *__restrict__ qo, int nrows, size_t pitch_x, size_t pitch_y, size_t pitch_q,
-                                            AsxPeakWs W, const AsxPoolPair *__restrict__ L = nullptr, float *__restrict__ eng = nullptr)
+                                            AsxPeakWs W, const AsxPoolPair *__restrict__ L = nullptr, float *__restrict__ eng = nullptr,
+                                            const AsxBand band = {})
 {
     static_assert(S::nstages == 3, "three-stage row schedules only");
+    static_assert(!BAND || PHAT, "a band is a band of the phase transform");
     constexpr int NS = S::n;                 // length of a (sub-)row transform
     constexpr int M2 = TWO ? 2 * NS : NS;    // row length
     constexpr int TWS = TWO ? 2 : 1;         // w_NS^q = tw2[TWS * q] (tw2 is the table of M2)
@@ -431,6 +442,17 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
                 pr[T] = Cx1{ v[T].re.x * v[T].re.y + v[T].im.x * v[T].im.y, v[T].im.x * v[T].re.y - v[T].re.x * v[T].im.y };
             });
             if constexpr (PHAT) static_for<0, R2>([&](auto T) __attribute__((always_inline)) { pr[T] = phat_unit(pr[T]); });
+            if constexpr (BAND) {
+                // pr[T] is bin k2 = unit + R0 (jl + R1 T) of the (sub-)row, i.e. k = k1 + 2 M1 k2 (two-half form: 2 k2 + half for k2)
+                constexpr uint32_t HS = TWO ? 2u : 1u;
+                const uint32_t F = 2u * P.N, m2 = 2u * (uint32_t)P.M1;
+                const uint32_t k0 = k1 + m2 * (HS * (uint32_t)(unit + R0 * jl) + (uint32_t)half), kstep = m2 * (HS * R0 * R1);
+                static_for<0, R2>([&](auto T) __attribute__((always_inline)) {
+                    const uint32_t k = k0 + (uint32_t) decltype(T)::value * kstep;
+                    const bool in = (k - band.lo <= band.span) || (F - k - band.lo <= band.span); // min(k, F - k) in [lo, lo + span]
+                    pr[T] = in ? pr[T] : Cx1{ 0.f, 0.f };
+                });
+            }
             Bfly<R2, true>::run(pr);
             static_for<0, R2>([&](auto T) __attribute__((always_inline)) { lds_put1(p + decltype(T)::value, pr[T]); });
         }
@@ -562,6 +584,18 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rp(
                                                                                  int nrows, size_t pair_pitch, AsxPeakWs W)
 {
     rows_r_body<S, NT, TWO, BC, false, true>(P, cx, cy, qo, nrows, (BC & 1) ? 0 : pair_pitch, (BC & 2) ? 0 : pair_pitch, pair_pitch, W);
+}
+
+// The row pass of a banded PHAT group (AsxSpectra::weight == ASX_W_PHAT_BAND): k_rows_rp<S, NT, TWO, BC> that lets only the bins of
+// `band` vote (BAND above).  Again a kernel name of its own: the k_rows_r and k_rows_rp instances stay the kernels they were.
+template <class S, int NT, bool TWO, int BC>
+__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rb(const RArgs P, const float2 *__restrict__ cx,
+                                                                                 const float2 *__restrict__ cy, float2 *__restrict__ qo,
+                                                                                 int nrows, size_t pair_pitch, AsxPeakWs W,
+                                                                                 const AsxBand band)
+{
+    rows_r_body<S, NT, TWO, BC, false, true, true>(P, cx, cy, qo, nrows, (BC & 1) ? 0 : pair_pitch, (BC & 2) ? 0 : pair_pitch, pair_pitch, W,
+                                                   nullptr, nullptr, band);
 }
 
 // The listed form (asx_xcorr_pool_f32_dev): pair p's C_x / C_y are rows L[p].sx / L[p].sy of the bank (cx, cy: its source and sample
@@ -1309,15 +1343,22 @@ static void launch_rows_r(K kernel, const AsxDev &P, int nt, const AsxSpectra &C
 
 // The row pass of a group whose spectra are C, which decides the flavour: k_rows_re (plus the tile energies C.prune->eng) when the
 // group is in scope for pruning, k_rows_rl (C_x / C_y at the pairs' bank slots) in a pool group, else k_rows_r in the broadcast form
-// C.bc -- or, in a PHAT group (C.weight; never pruned, never a pool group), k_rows_rp in that form.  The operands that are not
-// broadcast and q have the group workspace's pair pitch.
+// C.bc -- or, in a PHAT group (C.weight; never pruned, never a pool group), k_rows_rp in that form, or k_rows_rb with C.fband when only
+// a band votes.  The operands that are not broadcast and q have the group workspace's pair pitch.
 void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s)
 {
     asx_with_entry(AsxRRows{}, P.krows, [&](auto e) {
         using S = typename decltype(e)::sched;
         constexpr int NT = e.nt, nt = e.two ? 2 * NT : NT;
         constexpr bool TWO = e.two;
-        if (C.weight == ASX_W_PHAT)
+        if (C.weight == ASX_W_PHAT_BAND)
+            switch (C.bc) {
+            case 0: launch_rows_r(k_rows_rb<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s, C.fband); break;
+            case 1: launch_rows_r(k_rows_rb<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s, C.fband); break;
+            case 2: launch_rows_r(k_rows_rb<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s, C.fband); break;
+            default: launch_rows_r(k_rows_rb<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s, C.fband); break;
+            }
+        else if (C.weight == ASX_W_PHAT)
             switch (C.bc) {
             case 0: launch_rows_r(k_rows_rp<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s); break;
             case 1: launch_rows_r(k_rows_rp<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s); break;
@@ -1336,13 +1377,13 @@ void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const As
     });
 }
 
-void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, double *peak, int npairs, hipStream_t s,
+void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, double *peak, double f, int npairs, hipStream_t s,
                               const AsxSearch &q)
 {
     asx_with_selection(q, [&](auto sel) {
         if constexpr (!std::is_same<decltype(sel), AsxSelTopkSeed>::value) // (top-k with PHAT does not exist)
             hipLaunchKernelGGL(k_phat_finalize<decltype(sel)>, dim3((unsigned)(npairs + 255) / 256), dim3(256), 0, s, W, seg, peak, P.N,
-                               (double)P.F, npairs, sel);
+                               f, npairs, sel);
     });
 }
 

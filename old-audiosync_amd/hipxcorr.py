@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "asx_xcorr_strided_f32_dev", "asx_plan_set_lag_window", "asx_plan_lag_window", "asx_stream_set_lag_window",
     "asx_xcorr_windowed_f32_dev", "asx_xcorr_topk_f32_dev", "asx_xcorr_pool_f32_dev", "asx_xcorr_pool_topk_f32_dev",
     "asx_topk_best_dev", "asx_plan_set_prune", "asx_plan_prune_stats", "asx_xcorr_phat_f32_dev", "asx_xcorr_phat_debug_r_dev",
+    "asx_xcorr_phat_band_f32_dev", "asx_xcorr_phat_band_debug_r_dev", "asx_band_bins",
 ]
 
 TOPK_MAX = 8  # ASX_TOPK_MAX, include/audiosync/xcorr_hip.h
@@ -124,6 +125,14 @@ def lib():
                                          vp, vp, vp, vp, vp]
     L.asx_xcorr_phat_debug_r_dev.restype = ctypes.c_int
     L.asx_xcorr_phat_debug_r_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.asx_xcorr_phat_band_f32_dev.restype = ctypes.c_int
+    L.asx_xcorr_phat_band_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
+                                              ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, vp]
+    L.asx_xcorr_phat_band_debug_r_dev.restype = ctypes.c_int
+    L.asx_xcorr_phat_band_debug_r_dev.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, vp, vp]
+    L.asx_band_bins.restype = ctypes.c_int
+    L.asx_band_bins.argtypes = [ctypes.c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.asx_xcorr_topk_f32_dev.restype = ctypes.c_int
     L.asx_xcorr_topk_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
                                          ctypes.c_int, ctypes.c_int64, vp, vp, vp, vp]
@@ -364,6 +373,15 @@ def xcorr_batch_multi(plans, source, sample):
     if rc != 0:
         raise AsxError(_err())
     return lag, coef, ret
+
+
+def band_bins(sample_len, sample_rate, f_lo_hz, f_hi_hz):
+    """asx_band_bins: (bin_lo, bin_hi) of the band [f_lo_hz, f_hi_hz] for the banded PHAT calls -- bins of the 2N-point transform, bin m at
+    m * sample_rate / (2N) Hz, a band past the Nyquist frequency ending at bin N.  No device.  ValueError: no such band."""
+    lo, hi = ctypes.c_int64(-1), ctypes.c_int64(-1)
+    if lib().asx_band_bins(int(sample_len), float(sample_rate), float(f_lo_hz), float(f_hi_hz), ctypes.byref(lo), ctypes.byref(hi)) != 0:
+        raise ValueError("no bins for the band [%r, %r] Hz at %r Hz and %r samples" % (f_lo_hz, f_hi_hz, sample_rate, sample_len))
+    return int(lo.value), int(hi.value)
 
 
 def windowed_args(n, source, sample, windows):
@@ -776,6 +794,23 @@ class Plan:
         if rc != 0:
             raise AsxError(_err())
 
+    def xcorr_phat_band_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, bin_lo, bin_hi, d_lag, d_coef,
+                            d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_phat_band_f32_dev -- xcorr_phat_dev in which only bins bin_lo..bin_hi of the
+        2N-point transform vote (band_bins converts from Hz); d_peak receives |r_phat[lag]| / V, V the number of bins that vote"""
+        rc = lib().asx_xcorr_phat_band_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride), d_windows or None,
+                                               int(window_stride), int(batch), int(bin_lo), int(bin_hi), d_lag or None, d_coef or None,
+                                               d_peak or None, d_ret or None, stream or None)
+        if rc != 0:
+            raise AsxError(_err())
+
+    def phat_band_debug_r_dev(self, d_src, d_smp, bin_lo, bin_hi, d_r, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_phat_band_debug_r_dev -- one contiguous pair, r_phat of all 2N lags (times V) to d_r"""
+        rc = lib().asx_xcorr_phat_band_debug_r_dev(self._h, d_src or None, d_smp or None, int(bin_lo), int(bin_hi), d_r or None,
+                                                   d_lag or None, d_coef or None, d_peak or None, d_ret or None, stream or None)
+        if rc != 0:
+            raise AsxError(_err())
+
     def xcorr_topk_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, k, min_separation, d_lag, d_coef,
                        d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_topk_f32_dev -- the k strongest lags of pair i at least min_separation apart, entry j
@@ -952,11 +987,16 @@ class Plan:
         s, t, w, batch, ss, ts, ws, k, sep = topk_args(self.sample_len, source, sample, k, min_separation, windows)
         return self._strided_host(s, ss, t, ts, batch, w, ws, topk=(k, sep))
 
-    def xcorr_phat_f32(self, source, sample, windows=None):
+    def xcorr_phat_band_f32(self, source, sample, bin_lo, bin_hi, windows=None):
+        """xcorr_phat_f32 in which only bins bin_lo..bin_hi of the 2N-point transform vote (asx_xcorr_phat_band_f32_dev; band_bins
+        converts from Hz).  peak is |r_phat[lag]| / V, V the number of bins that vote.  The full band (0, N) is xcorr_phat_f32."""
+        return self.xcorr_phat_f32(source, sample, windows, band=(int(bin_lo), int(bin_hi)))
+
+    def xcorr_phat_f32(self, source, sample, windows=None, band=None):
         """Pairs ranked by the GCC-PHAT curve (asx_xcorr_phat_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N]; a
         1-D operand serves every pair.  windows: None (the plan's window), or integers [2] / [B, 2] as in xcorr_windowed_f32.
         Returns (lag int64[B], coef float64[B], peak float64[B], ret int32[B]): the float32 argmax of r_phat, the reference's
-        Pearson coefficient of the samples at that lag, and the peak height |r_phat[lag]| / F in [0, 1]."""
+        Pearson coefficient of the samples at that lag, and the peak height |r_phat[lag]| / F in [0, 1].  band: xcorr_phat_band_f32's."""
         n = self.sample_len
         s, t, w, batch, ss, ts, ws = windowed_args(n, source, sample, np.zeros(2, dtype=np.int64) if windows is None else windows)
         if windows is None:
@@ -977,7 +1017,10 @@ class Plan:
             d_win = dev(w) if w is not None else 0
             out = [np.zeros(batch, dtype=dt) for dt in (np.int64, np.float64, np.float64, np.int32)]
             d_out = [dev(nbytes=h.nbytes) for h in out]
-            self.xcorr_phat_dev(d_src, ss, d_smp, ts, d_win, ws, batch, *d_out)
+            if band is None:
+                self.xcorr_phat_dev(d_src, ss, d_smp, ts, d_win, ws, batch, *d_out)
+            else:
+                self.xcorr_phat_band_dev(d_src, ss, d_smp, ts, d_win, ws, batch, band[0], band[1], *d_out)
             self.sync()
             for h, d in zip(out, d_out):
                 if L.asx_memcpy_d2h(h.ctypes.data, d, h.nbytes) != 0:
