@@ -15,22 +15,105 @@ c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_intp = ctypes.POINTER(ctypes.c_int)
 
+_vp, _sz, _int, _i64, _u64, _dbl, _str = (ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64,
+                                          ctypes.c_double, ctypes.c_char_p)
+_vpp, _szp, _longp = ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_long)
+_u32p, _u64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+
+# name -> (restype, argtypes) of every function include/audiosync/xcorr_hip.h declares; lib() applies it, ABI_SYMBOLS lists it, and
+# tests/test_binding_signatures.py holds it against the header's prototypes
+_HEADER_SIGNATURES = {
+    "asx_device_count": (_int, []),
+    "asx_current_device": (_int, []),
+    "asx_last_error": (_str, []),
+    "asx_abi_version": (_int, []),
+    "asx_plan_create": (_vp, [_sz, _sz, _int]),
+    "asx_plan_create_ex": (_vp, [_sz, _sz, _int, _str]),
+    "asx_plan_destroy": (None, [_vp]),
+    "asx_plan_sample_len": (_sz, [_vp]),
+    "asx_plan_fft_len": (_sz, [_vp]),
+    "asx_plan_group": (_sz, [_vp]),
+    "asx_plan_workspace_bytes": (_sz, [_vp]),
+    "asx_plan_peak_capacity": (_sz, [_vp]),
+    "asx_plan_threads": (_int, [_vp, c_intp, c_intp]),
+    "asx_plan_split": (_int, [_vp, c_intp, c_intp, c_intp]),
+    "asx_plan_layout": (_int, [_vp]),
+    "asx_plan_peak_overflows": (_int, [_vp, _u64p]),
+    "asx_plan_peak_repairs": (_int, [_vp, _u64p]),
+    "asx_plan_narrowed_calls": (_int, [_vp, _u64p]),
+    "asx_plan_set_exact": (_int, [_vp, _int]),
+    "asx_plan_set_lag_window": (_int, [_vp, _i64, _i64]),
+    "asx_plan_lag_window": (_int, [_vp, c_i64p, c_i64p]),
+    "asx_stream_set_lag_window": (_int, [_vp, _i64, _i64]),
+    "asx_plan_placement": (_int, [_vp, c_f64p, c_intp]),
+    "asx_plan_set_pearson": (_int, [_vp, _int]),
+    "asx_plan_pearson_modes": (_int, [_vp, _u64p]),
+    "asx_plan_set_prune": (_int, [_vp, _int]),
+    "asx_plan_prune_stats": (_int, [_vp, _u64p, _u64p]),
+    "asx_plan_set_profiling": (_int, [_vp, _int]),
+    "asx_plan_last_timings_ms": (_int, [_vp, c_f32p]),
+    "asx_plan_timings_ms": (_int, [_vp, _int, c_f32p]),
+    "asx_xcorr_f64": (_int, [_vp, c_f64p, c_f64p, _longp, c_f64p]),
+    "asx_xcorr_batch_f32": (_int, [_vp, c_f32p, c_f32p, _sz, c_i64p, c_f64p, c_i32p]),
+    "asx_xcorr_batch_multi": (_int, [_vpp, _int, c_f32p, c_f32p, _sz, c_i64p, c_f64p, c_i32p]),
+    "asx_xcorr_batch_f32_dev": (_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_strided_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_windowed_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _int, _i64, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_phat_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_phat_band_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_pool_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_pool_topk_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _i64, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_phat_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_phat_band_debug_r_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asx_band_bins": (_int, [_sz, _dbl, _dbl, _dbl, c_i64p, c_i64p]),
+    "asx_pearson_f64": (_int, [c_f64p, c_f64p, _sz, _int, c_f64p]),
+    "asx_results_to_ms_dev": (_int, [_vp, _vp, _vp, _sz, _dbl, _dbl, _vp, _vp, _vp]),
+    "asx_topk_best_dev": (_int, [_vp, _vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp]),
+    "asx_synth_pairs_dev": (_int, [_u64, _u64, _sz, _sz, _int, _vp, _vp, _vp, _vp]),
+    "asx_shard_range": (_int, [_sz, _int, _int, _szp, _szp]),
+    "asx_result_bytes": (_sz, [_sz]),
+    "asx_comm_create": (_vp, [_vpp, _int]),
+    "asx_comm_destroy": (None, [_vp]),
+    "asx_xcorr_batch_multi_dev": (_int, [_vp, _vpp, _vpp, _szp, _sz, _vpp]),
+    "asx_stream_create": (_vp, [_sz, _int]),
+    "asx_stream_destroy": (None, [_vp]),
+    "asx_stream_append_f64": (_int, [_vp, c_f64p, _sz, c_f64p, _sz]),
+    "asx_stream_lengths": (_int, [_vp, _szp, _szp]),
+    "asx_stream_reset": (_int, [_vp]),
+    "asx_stream_xcorr": (_int, [_vp, _sz, _longp, c_f64p]),
+    "asx_device_malloc": (_vp, [_sz, _int]),
+    "asx_device_free": (_int, [_vp]),
+    "asx_host_malloc": (_vp, [_sz]),
+    "asx_host_free": (_int, [_vp]),
+    "asx_memcpy_h2d": (_int, [_vp, _vp, _sz]),
+    "asx_memcpy_d2h": (_int, [_vp, _vp, _sz]),
+    "asx_stream_sync": (_int, [_vp, _vp]),
+}
+
+# exported by csrc/asx_api.hip for the tests and tools, NOT part of the public header: planning arithmetic (host only) and
+# read-outs of a plan's state
+_DIAGNOSTIC_SIGNATURES = {
+    "asx_planmath_describe": (_int, [_sz, _str, _u32p, _u32p, c_intp, c_intp, c_intp, c_intp, c_intp, c_intp, c_intp]),
+    "asx_planmath_table": (_int, [_sz, _str, _int, c_intp, _sz]),
+    "asx_planmath_twiddles": (_int, [_sz, _str, _int, c_f32p, _sz]),
+    "asx_planmath_candidates": (_int, [_sz, _sz, _str, _sz]),
+    "asx_planmath_kernels": (_int, [_sz, _str, c_intp, c_intp, c_intp]),
+    "asx_planmath_kernel_table": (_int, [_int, _int, c_intp]),
+    "asx_plan_debug_kernels": (_int, [_vp, c_intp, c_intp, c_intp]),
+    "asx_plan_debug_bank": (_int, [_vp, _u64p, _u64p, _u64p]),
+    "asx_plan_debug_prune": (_int, [_vp, _sz, c_f32p, c_intp, _sz]),
+    "asx_plan_debug_peak": (_int, [_vp, _sz, c_f32p, _u32p, _u32p, _u64p, _vp, _vp, _sz]),
+    "asx_plan_debug_spectral": (_int, [_vp, _sz, c_intp, _vp, _sz, c_f64p, ctypes.POINTER(ctypes.c_longlong), c_f64p]),
+    "asx_plan_debug_over_list": (_int, [_vp, _u32p, _u32p]),
+    "asx_plan_debug_stamps": (ctypes.c_long, [_vp, _vp, _sz]),
+}
+
+SIGNATURES = {**_HEADER_SIGNATURES, **_DIAGNOSTIC_SIGNATURES}
+
 # every symbol include/audiosync/xcorr_hip.h declares (checked by tests/test_abi.py)
-ABI_SYMBOLS = [
-    "asx_device_count", "asx_last_error", "asx_abi_version", "asx_plan_create", "asx_plan_create_ex", "asx_plan_destroy",
-    "asx_plan_sample_len", "asx_plan_fft_len", "asx_plan_split", "asx_plan_threads", "asx_plan_group",
-    "asx_plan_workspace_bytes", "asx_xcorr_f64", "asx_xcorr_batch_f32", "asx_xcorr_batch_f32_dev",
-    "asx_xcorr_debug_r_dev", "asx_pearson_f64", "asx_results_to_ms_dev", "asx_stream_create", "asx_stream_destroy",
-    "asx_stream_append_f64", "asx_stream_lengths", "asx_stream_reset", "asx_stream_xcorr", "asx_synth_pairs_dev", "asx_plan_set_profiling",
-    "asx_plan_last_timings_ms", "asx_device_malloc", "asx_device_free", "asx_memcpy_h2d",
-    "asx_memcpy_d2h", "asx_stream_sync", "asx_plan_peak_overflows", "asx_plan_peak_repairs", "asx_plan_set_exact", "asx_plan_peak_capacity",
-    "asx_current_device", "asx_plan_timings_ms", "asx_xcorr_batch_multi", "asx_plan_layout", "asx_plan_narrowed_calls",
-    "asx_plan_set_pearson", "asx_plan_pearson_modes", "asx_plan_placement", "asx_host_malloc", "asx_host_free", "asx_shard_range", "asx_result_bytes", "asx_comm_create", "asx_comm_destroy", "asx_xcorr_batch_multi_dev",
-    "asx_xcorr_strided_f32_dev", "asx_plan_set_lag_window", "asx_plan_lag_window", "asx_stream_set_lag_window",
-    "asx_xcorr_windowed_f32_dev", "asx_xcorr_topk_f32_dev", "asx_xcorr_pool_f32_dev", "asx_xcorr_pool_topk_f32_dev",
-    "asx_topk_best_dev", "asx_plan_set_prune", "asx_plan_prune_stats", "asx_xcorr_phat_f32_dev", "asx_xcorr_phat_debug_r_dev",
-    "asx_xcorr_phat_band_f32_dev", "asx_xcorr_phat_band_debug_r_dev", "asx_band_bins",
-]
+ABI_SYMBOLS = list(_HEADER_SIGNATURES)
 
 TOPK_MAX = 8  # ASX_TOPK_MAX, include/audiosync/xcorr_hip.h
 
@@ -63,158 +146,35 @@ def lib():
                        "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     _one_hip_runtime()
     L = ctypes.CDLL(LIB_PATH)
-    vp = ctypes.c_void_p
-    L.asx_device_count.restype = ctypes.c_int
-    L.asx_last_error.restype = ctypes.c_char_p
-    L.asx_abi_version.restype = ctypes.c_int
-    L.asx_plan_create.restype = vp
-    L.asx_plan_create.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]
-    L.asx_plan_create_ex.restype = vp
-    L.asx_plan_create_ex.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p]
-    L.asx_plan_destroy.restype = None
-    L.asx_plan_destroy.argtypes = [vp]
-    L.asx_plan_peak_overflows.restype = ctypes.c_int
-    L.asx_plan_peak_overflows.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.asx_plan_set_exact.restype = ctypes.c_int
-    L.asx_plan_set_exact.argtypes = [vp, ctypes.c_int]
-    L.asx_plan_set_lag_window.restype = ctypes.c_int
-    L.asx_plan_set_lag_window.argtypes = [vp, ctypes.c_int64, ctypes.c_int64]
-    L.asx_plan_lag_window.restype = ctypes.c_int
-    L.asx_plan_lag_window.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
-    L.asx_stream_set_lag_window.restype = ctypes.c_int
-    L.asx_stream_set_lag_window.argtypes = [vp, ctypes.c_int64, ctypes.c_int64]
-    L.asx_plan_placement.restype = ctypes.c_int
-    L.asx_plan_placement.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
-    L.asx_plan_set_pearson.restype = ctypes.c_int
-    L.asx_plan_set_pearson.argtypes = [vp, ctypes.c_int]
-    L.asx_plan_pearson_modes.restype = ctypes.c_int
-    L.asx_plan_pearson_modes.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.asx_plan_set_prune.restype = ctypes.c_int
-    L.asx_plan_set_prune.argtypes = [vp, ctypes.c_int]
-    L.asx_plan_prune_stats.restype = ctypes.c_int
-    L.asx_plan_prune_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-    L.asx_plan_peak_repairs.restype = ctypes.c_int
-    L.asx_plan_peak_repairs.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.asx_plan_narrowed_calls.restype = ctypes.c_int
-    L.asx_plan_narrowed_calls.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    for name in ("asx_plan_sample_len", "asx_plan_fft_len", "asx_plan_group", "asx_plan_workspace_bytes",
-                 "asx_plan_peak_capacity"):
-        getattr(L, name).restype = ctypes.c_size_t
-        getattr(L, name).argtypes = [vp]
-    L.asx_plan_threads.restype = ctypes.c_int
-    L.asx_plan_threads.argtypes = [vp, c_intp, c_intp]
-    L.asx_plan_split.restype = ctypes.c_int
-    L.asx_plan_split.argtypes = [vp, c_intp, c_intp, c_intp]
-    L.asx_plan_layout.restype = ctypes.c_int
-    L.asx_plan_layout.argtypes = [vp]
-    L.asx_xcorr_f64.restype = ctypes.c_int
-    L.asx_xcorr_f64.argtypes = [vp, c_f64p, c_f64p, ctypes.POINTER(ctypes.c_long), c_f64p]
-    L.asx_xcorr_batch_f32.restype = ctypes.c_int
-    L.asx_xcorr_batch_f32.argtypes = [vp, c_f32p, c_f32p, ctypes.c_size_t, c_i64p, c_f64p, c_i32p]
-    L.asx_xcorr_batch_multi.restype = ctypes.c_int
-    L.asx_xcorr_batch_multi.argtypes = [ctypes.POINTER(vp), ctypes.c_int, c_f32p, c_f32p, ctypes.c_size_t, c_i64p, c_f64p, c_i32p]
-    L.asx_xcorr_batch_f32_dev.restype = ctypes.c_int
-    L.asx_xcorr_batch_f32_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, vp, vp, vp]
-    L.asx_xcorr_strided_f32_dev.restype = ctypes.c_int
-    L.asx_xcorr_strided_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, vp]
-    L.asx_xcorr_windowed_f32_dev.restype = ctypes.c_int
-    L.asx_xcorr_windowed_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
-                                             vp, vp, vp, vp]
-    L.asx_xcorr_phat_f32_dev.restype = ctypes.c_int
-    L.asx_xcorr_phat_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
-                                         vp, vp, vp, vp, vp]
-    L.asx_xcorr_phat_debug_r_dev.restype = ctypes.c_int
-    L.asx_xcorr_phat_debug_r_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.asx_xcorr_phat_band_f32_dev.restype = ctypes.c_int
-    L.asx_xcorr_phat_band_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
-                                              ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, vp]
-    L.asx_xcorr_phat_band_debug_r_dev.restype = ctypes.c_int
-    L.asx_xcorr_phat_band_debug_r_dev.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, vp, vp]
-    L.asx_band_bins.restype = ctypes.c_int
-    L.asx_band_bins.argtypes = [ctypes.c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
-    L.asx_xcorr_topk_f32_dev.restype = ctypes.c_int
-    L.asx_xcorr_topk_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t,
-                                         ctypes.c_int, ctypes.c_int64, vp, vp, vp, vp]
-    L.asx_xcorr_pool_f32_dev.restype = ctypes.c_int
-    L.asx_xcorr_pool_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp,
-                                         ctypes.c_size_t, ctypes.c_size_t, vp, vp, vp, vp]
-    L.asx_xcorr_pool_topk_f32_dev.restype = ctypes.c_int
-    L.asx_xcorr_pool_topk_f32_dev.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, vp, vp,
-                                              ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, vp, vp, vp, vp]
-    L.asx_plan_debug_bank.restype = ctypes.c_int
-    L.asx_plan_debug_bank.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
-                                      ctypes.POINTER(ctypes.c_uint64)]
-    L.asx_shard_range.restype = ctypes.c_int
-    L.asx_shard_range.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t),
-                                  ctypes.POINTER(ctypes.c_size_t)]
-    L.asx_result_bytes.restype = ctypes.c_size_t
-    L.asx_result_bytes.argtypes = [ctypes.c_size_t]
-    L.asx_comm_create.restype = vp
-    L.asx_comm_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
-    L.asx_comm_destroy.restype = None
-    L.asx_comm_destroy.argtypes = [vp]
-    L.asx_xcorr_batch_multi_dev.restype = ctypes.c_int
-    L.asx_xcorr_batch_multi_dev.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t),
-                                            ctypes.c_size_t, ctypes.POINTER(vp)]
-    L.asx_xcorr_debug_r_dev.restype = ctypes.c_int
-    L.asx_xcorr_debug_r_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.asx_pearson_f64.restype = ctypes.c_int
-    L.asx_pearson_f64.argtypes = [c_f64p, c_f64p, ctypes.c_size_t, ctypes.c_int, c_f64p]
-    L.asx_results_to_ms_dev.restype = ctypes.c_int
-    L.asx_results_to_ms_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, vp, vp, vp]
-    L.asx_topk_best_dev.restype = ctypes.c_int
-    L.asx_topk_best_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.c_int, vp, vp, vp, vp, vp]
-    L.asx_stream_create.restype = vp
-    L.asx_stream_create.argtypes = [ctypes.c_size_t, ctypes.c_int]
-    L.asx_stream_destroy.restype = None
-    L.asx_stream_destroy.argtypes = [vp]
-    L.asx_stream_append_f64.restype = ctypes.c_int
-    L.asx_stream_append_f64.argtypes = [vp, c_f64p, ctypes.c_size_t, c_f64p, ctypes.c_size_t]
-    L.asx_stream_lengths.restype = ctypes.c_int
-    L.asx_stream_lengths.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
-    L.asx_stream_reset.restype = ctypes.c_int
-    L.asx_stream_reset.argtypes = [vp]
-    L.asx_stream_xcorr.restype = ctypes.c_int
-    L.asx_stream_xcorr.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_long), c_f64p]
-    L.asx_synth_pairs_dev.restype = ctypes.c_int
-    L.asx_synth_pairs_dev.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_size_t,
-                                      ctypes.c_int, vp, vp, vp, vp]
-    L.asx_plan_set_profiling.restype = ctypes.c_int
-    L.asx_plan_set_profiling.argtypes = [vp, ctypes.c_int]
-    L.asx_plan_last_timings_ms.restype = ctypes.c_int
-    L.asx_plan_last_timings_ms.argtypes = [vp, c_f32p]
-    L.asx_plan_timings_ms.restype = ctypes.c_int
-    L.asx_plan_timings_ms.argtypes = [vp, ctypes.c_int, c_f32p]
-    L.asx_device_malloc.restype = vp
-    L.asx_device_malloc.argtypes = [ctypes.c_size_t, ctypes.c_int]
-    L.asx_device_free.restype = ctypes.c_int
-    L.asx_device_free.argtypes = [vp]
-    L.asx_host_malloc.restype = vp
-    L.asx_host_malloc.argtypes = [ctypes.c_size_t]
-    L.asx_host_free.restype = ctypes.c_int
-    L.asx_host_free.argtypes = [vp]
-    L.asx_memcpy_h2d.restype = ctypes.c_int
-    L.asx_memcpy_h2d.argtypes = [vp, vp, ctypes.c_size_t]
-    L.asx_memcpy_d2h.restype = ctypes.c_int
-    L.asx_memcpy_d2h.argtypes = [vp, vp, ctypes.c_size_t]
-    L.asx_stream_sync.restype = ctypes.c_int
-    L.asx_stream_sync.argtypes = [vp, vp]
-    # planning arithmetic (host only)
-    L.asx_planmath_describe.restype = ctypes.c_int
-    L.asx_planmath_describe.argtypes = [ctypes.c_size_t, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32),
-                                        ctypes.POINTER(ctypes.c_uint32), c_intp, c_intp, c_intp, c_intp,
-                                        c_intp, c_intp, c_intp]
-    L.asx_planmath_table.restype = ctypes.c_int
-    L.asx_planmath_table.argtypes = [ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, c_intp, ctypes.c_size_t]
-    L.asx_planmath_twiddles.restype = ctypes.c_int
-    L.asx_planmath_twiddles.argtypes = [ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, c_f32p, ctypes.c_size_t]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
 
 def _err():
     return lib().asx_last_error().decode("utf-8", "replace")
+
+
+def _check(rc, message=None):
+    """a C-ABI status: non-zero raises AsxError with asx_last_error(), or with `message` for the calls that set none"""
+    if rc != 0:
+        raise AsxError(message or _err())
+
+
+def _handle(ptr):
+    """a handle or allocation the C-ABI returned: null raises AsxError with asx_last_error()"""
+    if not ptr:
+        raise AsxError(_err())
+    return ptr
+
+
+def _counters(fn, handle, count, message=None):
+    """the `count` uint64 out-parameters of fn(handle, ...) as a tuple of ints"""
+    c = [ctypes.c_uint64(0) for _ in range(count)]
+    _check(fn(handle, *c), message)
+    return tuple(v.value for v in c)
 
 
 def abi_version():
@@ -235,9 +195,7 @@ def planmath_describe(sample_len, split=None):
     m1, m2, t, n1, n2 = (ctypes.c_int() for _ in range(5))
     r1 = (ctypes.c_int * 16)()
     r2 = (ctypes.c_int * 16)()
-    rc = lib().asx_planmath_describe(sample_len, _split_arg(split), F, valid, m1, m2, t, n1, r1, n2, r2)
-    if rc != 0:
-        raise AsxError(_err())
+    _check(lib().asx_planmath_describe(sample_len, _split_arg(split), F, valid, m1, m2, t, n1, r1, n2, r2))
     return {"F": F.value, "src_valid": valid.value, "M1": m1.value, "M2": m2.value, "T": t.value,
             "radix1": list(r1[: n1.value]), "radix2": list(r2[: n2.value])}
 
@@ -257,8 +215,6 @@ def _kernel_entry(v, nhead, flag=None):
 def planmath_kernel_table():
     """host-only: the four lists of csrc/kernel_table.h, each entry as planmath_kernels spells it"""
     f = lib().asx_planmath_kernel_table
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.c_int, ctypes.c_int, c_intp]
     table = {}
     for which, (name, nhead, flag) in enumerate((("real-column cols", 3, None), ("real-column rows", 3, 1),
                                                  ("packed cols", 4, None), ("packed rows", 3, None))):
@@ -272,8 +228,7 @@ def _kernel_choice(call):
     """the dict of an AsxKernelChoice (asx_planmath_kernels / asx_plan_debug_kernels): an entry of csrc/kernel_table.h as the
     constants its list states and the tuple of its radices, None for a run-time schedule"""
     out, cols, rows = (ctypes.c_int * 7)(), (ctypes.c_int * KERNEL_ENTRY_CAP)(), (ctypes.c_int * KERNEL_ENTRY_CAP)()
-    if call(out, cols, rows) != 0:
-        raise AsxError(_err())
+    _check(call(out, cols, rows))
     real, entry = bool(out[0]), _kernel_entry
     # real-column: (M1, T, NT, radices) and (NT, two-half, n, radices); packed: (M1, T, NT, MAXR, radices) and (NT, MAXR, n, radices)
     return {"layout": "real-column" if real else "packed", "cols": entry(cols, 3 if real else 4),
@@ -284,18 +239,13 @@ def _kernel_choice(call):
 def planmath_kernels(sample_len, split=None):
     """host-only: the kernels the plan of sample_len would run under the current environment (no GPU needed)."""
     f = lib().asx_planmath_kernels
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.c_size_t, ctypes.c_char_p, c_intp, c_intp, c_intp]
     return _kernel_choice(lambda *a: f(sample_len, _split_arg(split), *a))
 
 
 def planmath_candidates(sample_len, max_count=16):
     """host-only: the splits the measured mode (split="measure") would time, cheapest first."""
     buf = ctypes.create_string_buffer(64 * max_count + 1)
-    L = lib()
-    L.asx_planmath_candidates.restype = ctypes.c_int
-    L.asx_planmath_candidates.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t]
-    n = L.asx_planmath_candidates(sample_len, max_count, buf, len(buf))
+    n = lib().asx_planmath_candidates(sample_len, max_count, buf, len(buf))
     if n < 0:
         raise AsxError(_err())
     return [x for x in buf.value.decode().split("\n") if x]
@@ -327,34 +277,25 @@ def pearson_f64(source_seg, sample_seg, device=-1):
     b = np.ascontiguousarray(sample_seg, dtype=np.float64)
     assert a.size == b.size
     out = ctypes.c_double(0.0)
-    rc = lib().asx_pearson_f64(a.ctypes.data_as(c_f64p), b.ctypes.data_as(c_f64p), a.size, device,
-                               ctypes.byref(out))
-    if rc != 0:
-        raise AsxError(_err())
+    _check(lib().asx_pearson_f64(a.ctypes.data_as(c_f64p), b.ctypes.data_as(c_f64p), a.size, device, ctypes.byref(out)))
     return out.value
 
 
 def results_to_ms_dev(d_lag, d_coef, d_ret, batch, d_lag_ms, d_accept=0, min_confidence=0.95, sample_rate=48000.0, stream=0):
-    rc = lib().asx_results_to_ms_dev(d_lag, d_coef, d_ret, batch, min_confidence, sample_rate, d_lag_ms,
-                                     d_accept or None, stream or None)
-    if rc != 0:
-        raise AsxError(_err())
+    _check(lib().asx_results_to_ms_dev(d_lag, d_coef, d_ret, batch, min_confidence, sample_rate, d_lag_ms,
+                                       d_accept or None, stream or None))
 
 
 def topk_best_dev(d_lag, d_coef, d_ret, batch, k, d_best_coef, d_best_ret, d_best_lag=0, d_best_entry=0, stream=0):
     """raw device pointers (ints): asx_topk_best_dev -- per pair, of its k entries at i*k + j, the one with ret == 0 and the largest
     signed coefficient (none: entry 0) to index i of the best arrays, which results_to_ms_dev takes; asynchronous on `stream`"""
-    rc = lib().asx_topk_best_dev(d_lag, d_coef, d_ret, int(batch), int(k), d_best_lag or None, d_best_coef, d_best_ret,
-                                 d_best_entry or None, stream or None)
-    if rc != 0:
-        raise AsxError(_err())
+    _check(lib().asx_topk_best_dev(d_lag, d_coef, d_ret, int(batch), int(k), d_best_lag or None, d_best_coef, d_best_ret,
+                                   d_best_entry or None, stream or None))
 
 
 def synth_pairs_dev(seed, first_pair, count, sample_len, noise_shift, d_src, d_smp, d_lag=0, stream=0):
-    rc = lib().asx_synth_pairs_dev(seed, first_pair, count, sample_len, noise_shift, d_src, d_smp,
-                                   d_lag or None, stream or None)
-    if rc != 0:
-        raise AsxError(_err())
+    _check(lib().asx_synth_pairs_dev(seed, first_pair, count, sample_len, noise_shift, d_src, d_smp,
+                                     d_lag or None, stream or None))
 
 
 def xcorr_batch_multi(plans, source, sample):
@@ -368,10 +309,8 @@ def xcorr_batch_multi(plans, source, sample):
     coef = np.zeros(batch, dtype=np.float64)
     ret = np.zeros(batch, dtype=np.int32)
     handles = (ctypes.c_void_p * len(plans))(*[p._h for p in plans])
-    rc = lib().asx_xcorr_batch_multi(handles, len(plans), s.ctypes.data_as(c_f32p), t.ctypes.data_as(c_f32p), batch,
-                                     lag.ctypes.data_as(c_i64p), coef.ctypes.data_as(c_f64p), ret.ctypes.data_as(c_i32p))
-    if rc != 0:
-        raise AsxError(_err())
+    _check(lib().asx_xcorr_batch_multi(handles, len(plans), s.ctypes.data_as(c_f32p), t.ctypes.data_as(c_f32p), batch,
+                                       lag.ctypes.data_as(c_i64p), coef.ctypes.data_as(c_f64p), ret.ctypes.data_as(c_i32p)))
     return lag, coef, ret
 
 
@@ -384,43 +323,67 @@ def band_bins(sample_len, sample_rate, f_lo_hz, f_hi_hz):
     return int(lo.value), int(hi.value)
 
 
+def _operands(n, source, sample):
+    """the two operands of a strided call for sample length n -> (source [2N] or [B, 2N], sample [N] or [B, N]) as contiguous
+    float32 arrays, (source_stride, sample_stride) in floats: 0 for a 1-D operand, which serves every pair"""
+    s = np.ascontiguousarray(source, dtype=np.float32)
+    t = np.ascontiguousarray(sample, dtype=np.float32)
+    if s.ndim not in (1, 2) or t.ndim not in (1, 2) or s.shape[-1] != 2 * n or t.shape[-1] != n:
+        raise ValueError("source must be [2N] or [B, 2N] and sample [N] or [B, N] with N = %d" % n)
+    return s, t, 2 * n if s.ndim == 2 else 0, n if t.ndim == 2 else 0
+
+
+def _window_rows(windows, batch=None):
+    """lag windows -> contiguous int64 [2] or [B, 2] rows (lag_min, lag_max); batch: the B that a 2-D array must have"""
+    w = np.asarray(windows)
+    if w.dtype.kind not in "iu":
+        raise ValueError("windows must hold integers (lag_min, lag_max), not %s" % w.dtype)
+    w = np.ascontiguousarray(w, dtype=np.int64)
+    if w.ndim not in (1, 2) or w.shape[-1] != 2 or (batch is not None and w.ndim == 2 and w.shape[0] != batch):
+        raise ValueError("windows must be [2] or [B, 2]" + ("" if batch is None else " with B = %d pairs" % batch))
+    return w
+
+
+def _shared_batch(*arrays):
+    """the batch size the 2-D arrays among `arrays` (None: absent) agree on; 1 when all are 1-D"""
+    sizes = {a.shape[0] for a in arrays if a is not None and a.ndim == 2}
+    if len(sizes) > 1:
+        raise ValueError("source, sample and windows have different batch sizes %s" % sorted(sizes))
+    return sizes.pop() if sizes else 1
+
+
+def _strided_args(n, source, sample, w):
+    """windowed_args' tuple for checked window rows w; w None (no rows): None and a window stride of 0 in their places"""
+    s, t, ss, ts = _operands(n, source, sample)
+    batch = _shared_batch(s, t, w)
+    if batch < 1:
+        raise ValueError("empty batch")
+    return s, t, w, batch, ss, ts, 1 if w is not None and w.ndim == 2 else 0
+
+
+def _topk_option(k, min_separation):
+    """-> (k, min_separation) as ints; ValueError unless they are integers (no bools), 1 <= k <= TOPK_MAX, min_separation >= 0"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= TOPK_MAX:
+        raise ValueError("k must be an integer in [1, %d], not %r" % (TOPK_MAX, k))
+    if isinstance(min_separation, bool) or not isinstance(min_separation, (int, np.integer)) or int(min_separation) < 0:
+        raise ValueError("min_separation must be an integer >= 0, not %r" % (min_separation,))
+    return int(k), int(min_separation)
+
+
 def windowed_args(n, source, sample, windows):
     """Host checks of Plan.xcorr_windowed_f32 for a plan of sample length n: source [2N] or [B, 2N], sample [N] or [B, N], windows
     [2] or [B, 2] integers (a 1-D operand serves every pair).  -> (source, sample, windows, batch, source_stride, sample_stride,
     window_stride) as contiguous float32 / int64 arrays and strides in elements / rows.  ValueError on anything else.  The rows'
     values are not checked: a row that is not a window comes back as (0, NaN, -2)."""
-    s = np.ascontiguousarray(source, dtype=np.float32)
-    t = np.ascontiguousarray(sample, dtype=np.float32)
-    w = np.asarray(windows)
-    if w.dtype.kind not in "iu":
-        raise ValueError("windows must hold integers (lag_min, lag_max), not %s" % w.dtype)
-    w = np.ascontiguousarray(w, dtype=np.int64)
-    if s.ndim not in (1, 2) or t.ndim not in (1, 2) or s.shape[-1] != 2 * n or t.shape[-1] != n:
-        raise ValueError("source must be [2N] or [B, 2N] and sample [N] or [B, N] with N = %d" % n)
-    if w.ndim not in (1, 2) or w.shape[-1] != 2:
-        raise ValueError("windows must be [2] or [B, 2]")
-    sizes = {a.shape[0] for a in (s, t, w) if a.ndim == 2}
-    if len(sizes) > 1:
-        raise ValueError("source, sample and windows have different batch sizes %s" % sorted(sizes))
-    batch = sizes.pop() if sizes else 1
-    if batch < 1:
-        raise ValueError("empty batch")
-    return s, t, w, batch, 2 * n if s.ndim == 2 else 0, n if t.ndim == 2 else 0, 1 if w.ndim == 2 else 0
+    return _strided_args(n, source, sample, _window_rows(windows))
 
 
 def topk_args(n, source, sample, k, min_separation, windows=None):
     """Host checks of Plan.xcorr_topk_f32: the shapes of windowed_args (windows=None: the plan's window, no rows), 1 <= k <= TOPK_MAX
     and min_separation >= 0, integers.  -> (source, sample, windows or None, batch, source_stride, sample_stride, window_stride, k,
     min_separation).  ValueError on anything else."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= TOPK_MAX:
-        raise ValueError("k must be an integer in [1, %d], not %r" % (TOPK_MAX, k))
-    if isinstance(min_separation, bool) or not isinstance(min_separation, (int, np.integer)) or int(min_separation) < 0:
-        raise ValueError("min_separation must be an integer >= 0, not %r" % (min_separation,))
-    if windows is None:
-        s, t, _, batch, ss, ts, _ = windowed_args(n, source, sample, np.zeros(2, dtype=np.int64))
-        return s, t, None, batch, ss, ts, 0, int(k), int(min_separation)
-    s, t, w, batch, ss, ts, ws = windowed_args(n, source, sample, windows)
-    return s, t, w, batch, ss, ts, ws, int(k), int(min_separation)
+    option = _topk_option(k, min_separation)
+    return _strided_args(n, source, sample, None if windows is None else _window_rows(windows)) + option
 
 
 def pool_args(n, sources, samples, pairs=None, windows=None):
@@ -450,23 +413,15 @@ def pool_args(n, sources, samples, pairs=None, windows=None):
             raise ValueError("pair indices must fit int32")
         pr = np.ascontiguousarray(pr, dtype=np.int32)
         batch = pr.shape[0]
-    w, ws = None, 0
-    if windows is not None:
-        w = np.asarray(windows)
-        if w.dtype.kind not in "iu":
-            raise ValueError("windows must hold integers (lag_min, lag_max), not %s" % w.dtype)
-        w = np.ascontiguousarray(w, dtype=np.int64)
-        if w.ndim not in (1, 2) or w.shape[-1] != 2 or (w.ndim == 2 and w.shape[0] != batch):
-            raise ValueError("windows must be [2] or [B, 2] with B = %d pairs" % batch)
-        ws = 1 if w.ndim == 2 else 0
-    return s, t, pr, w, batch, ws
+    w = None if windows is None else _window_rows(windows, batch)
+    return s, t, pr, w, batch, 1 if w is not None and w.ndim == 2 else 0
 
 
 def pool_topk_args(n, sources, samples, k, min_separation, pairs=None, windows=None):
     """Host checks of Plan.xcorr_pool_topk_f32: k and min_separation as topk_args checks them, the rest as pool_args.  -> pool_args'
     tuple + (k, min_separation).  ValueError on anything else."""
-    k, sep = topk_args(1, np.zeros(2, np.float32), np.zeros(1, np.float32), k, min_separation)[-2:]
-    return pool_args(n, sources, samples, pairs, windows) + (k, sep)
+    option = _topk_option(k, min_separation)
+    return pool_args(n, sources, samples, pairs, windows) + option
 
 
 def position_rows(n, hop, batch, p_lo, p_hi):
@@ -492,9 +447,7 @@ class PinnedArray:
 
     def __init__(self, count, dtype=np.float64):
         self.nbytes = int(count) * np.dtype(dtype).itemsize
-        self._p = lib().asx_host_malloc(self.nbytes)
-        if not self._p:
-            raise AsxError(_err())
+        self._p = _handle(lib().asx_host_malloc(self.nbytes))
         buf = (ctypes.c_char * self.nbytes).from_address(self._p)
         self.array = np.frombuffer(buf, dtype=dtype, count=int(count))
 
@@ -508,8 +461,7 @@ class PinnedArray:
 def shard_range(total, nshards, shard):
     """block partition of a batch over shards (asx_shard_range): -> (start, count)"""
     start, count = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    if lib().asx_shard_range(total, nshards, shard, ctypes.byref(start), ctypes.byref(count)) != 0:
-        raise AsxError(_err())
+    _check(lib().asx_shard_range(total, nshards, shard, ctypes.byref(start), ctypes.byref(count)))
     return start.value, count.value
 
 
@@ -524,9 +476,7 @@ class Comm:
     def __init__(self, plans):
         self.plans = list(plans)
         handles = (ctypes.c_void_p * len(self.plans))(*[p._h for p in self.plans])
-        self._h = lib().asx_comm_create(handles, len(self.plans))
-        if not self._h:
-            raise AsxError(_err())
+        self._h = _handle(lib().asx_comm_create(handles, len(self.plans)))
 
     def run(self, d_sources, d_samples, counts, width, d_gathered):
         n = len(self.plans)
@@ -535,8 +485,7 @@ class Comm:
         smp = (ctypes.c_void_p * n)(*d_samples)
         out = (ctypes.c_void_p * n)(*d_gathered)
         cnt = (ctypes.c_size_t * n)(*counts)
-        if lib().asx_xcorr_batch_multi_dev(self._h, src, smp, cnt, width, out) != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_batch_multi_dev(self._h, src, smp, cnt, width, out))
 
     def close(self):
         if self._h:
@@ -554,9 +503,7 @@ class Stream:
     """asx_stream: both tracks resident in HBM, new frames appended, one plan per prefix length."""
 
     def __init__(self, max_sample_len, device=-1):
-        self._h = lib().asx_stream_create(int(max_sample_len), int(device))
-        if not self._h:
-            raise AsxError(_err())
+        self._h = _handle(lib().asx_stream_create(int(max_sample_len), int(device)))
         self._destroy = lib().asx_stream_destroy  # bound now: module globals may be gone at interpreter exit
 
     def close(self):
@@ -569,9 +516,7 @@ class Stream:
     def append(self, source_frames, sample_frames):
         s = np.ascontiguousarray(source_frames, dtype=np.float64)
         t = np.ascontiguousarray(sample_frames, dtype=np.float64)
-        rc = lib().asx_stream_append_f64(self._h, s.ctypes.data_as(c_f64p), s.size, t.ctypes.data_as(c_f64p), t.size)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_stream_append_f64(self._h, s.ctypes.data_as(c_f64p), s.size, t.ctypes.data_as(c_f64p), t.size))
 
     def lengths(self):
         a, b = ctypes.c_size_t(), ctypes.c_size_t()
@@ -583,8 +528,7 @@ class Stream:
 
     def set_lag_window(self, lo, hi):
         """search the peak only at lags lo..hi (frames), clamped to [-n, n-1] for each prefix length n that xcorr correlates"""
-        if lib().asx_stream_set_lag_window(self._h, int(lo), int(hi)) != 0:
-            raise AsxError(_err())
+        _check(lib().asx_stream_set_lag_window(self._h, int(lo), int(hi)))
 
     def xcorr(self, sample_len):
         lag = ctypes.c_long(0)
@@ -593,14 +537,57 @@ class Stream:
         return ret, lag.value, coef.value
 
 
+class _Staging:
+    """Device copies of one call's host arrays on a plan's device.  Inside the `with` block: upload() the inputs, output() the
+    results' buffers, make the asynchronous _dev call with the pointers those returned, fetch() the results.  Every pointer handed
+    out is freed once when the block ends, also when something raised in between."""
+
+    def __init__(self, plan):
+        self._plan, self._lib, self._ptrs, self._outs = plan, lib(), [], []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        while self._ptrs:
+            self._lib.asx_device_free(self._ptrs.pop())
+
+    def alloc(self, nbytes):
+        """a device pointer to nbytes (at least 16) of the plan's device"""
+        self._ptrs.append(_handle(self._lib.asx_device_malloc(max(int(nbytes), 16), self._plan.device)))
+        return self._ptrs[-1]
+
+    def upload(self, host):
+        """a device pointer to a copy of the host array; None (an optional argument left out): 0"""
+        if host is None:
+            return 0
+        ptr = self.alloc(host.nbytes)
+        _check(self._lib.asx_memcpy_h2d(ptr, host.ctypes.data, host.nbytes))
+        return ptr
+
+    def output(self, shape, dtype):
+        """a device pointer to room for an array that fetch() will return"""
+        host = np.zeros(shape, dtype=dtype)
+        self._outs.append((host, self.alloc(host.nbytes)))
+        return self._outs[-1][1]
+
+    def fetch(self):
+        """wait for the plan's stream, then the outputs as host arrays, in the order they were reserved"""
+        self._plan.sync()
+        for host, ptr in self._outs:
+            _check(self._lib.asx_memcpy_d2h(host.ctypes.data, ptr, host.nbytes))
+        return tuple(host for host, _ in self._outs)
+
+
+_RESULTS = (np.int64, np.float64, np.int32)                    # lag, coef, ret
+_PHAT_RESULTS = (np.int64, np.float64, np.float64, np.int32)   # lag, coef, peak, ret
+
+
 class Plan:
     """asx_plan: fixed sample_len, owns tables + HBM workspaces on one device."""
 
     def __init__(self, sample_len, max_batch=1, device=-1, split=None):
-        self._h = lib().asx_plan_create_ex(int(sample_len), int(max_batch), int(device),
-                                           _split_arg(split))
-        if not self._h:
-            raise AsxError(_err())
+        self._h = _handle(lib().asx_plan_create_ex(int(sample_len), int(max_batch), int(device), _split_arg(split)))
         self._destroy = lib().asx_plan_destroy  # bound now: module globals may be gone at interpreter exit
         self.sample_len = int(sample_len)
         self.device = int(device)
@@ -632,76 +619,57 @@ class Plan:
 
     def peak_overflows(self):
         """pairs (since plan creation) with more near-tied lags than the plan re-evaluates exactly"""
-        c = ctypes.c_uint64(0)
-        if lib().asx_plan_peak_overflows(self._h, ctypes.byref(c)) != 0:
-            raise AsxError(_err())
-        return c.value
+        return _counters(lib().asx_plan_peak_overflows, self._h, 1)[0]
 
     def set_lag_window(self, lo, hi):
         """search the peak only at lags lo..hi, -N <= lo <= hi <= N-1 (asx_plan_set_lag_window); (-N, N-1) = every lag, the default"""
-        if lib().asx_plan_set_lag_window(self._h, int(lo), int(hi)) != 0:
-            raise AsxError(_err())
+        _check(lib().asx_plan_set_lag_window(self._h, int(lo), int(hi)))
 
     @property
     def lag_window(self):
         lo, hi = ctypes.c_int64(0), ctypes.c_int64(0)
-        if lib().asx_plan_lag_window(self._h, ctypes.byref(lo), ctypes.byref(hi)) != 0:
-            raise AsxError(_err())
+        _check(lib().asx_plan_lag_window(self._h, ctypes.byref(lo), ctypes.byref(hi)))
         return lo.value, hi.value
 
     def set_exact(self, on=True):
         """on (the default): every entry point takes the second look at overflowing pairs (the device-resident batch waits
         once per call for its kernels); off: that entry point stays asynchronous and marks such pairs with ret = 1"""
-        if lib().asx_plan_set_exact(self._h, 1 if on else 0) != 0:
-            raise AsxError(_err())
+        _check(lib().asx_plan_set_exact(self._h, 1 if on else 0))
 
     def placement(self):
         """("measure" plans) -> ((ms of the forward column kernel on the first / second allocation of its workspaces), kept)"""
         ms = (ctypes.c_double * 2)()
         kept = ctypes.c_int(-1)
-        if lib().asx_plan_placement(self._h, ms, ctypes.byref(kept)) != 0:
-            raise AsxError(_err())
+        _check(lib().asx_plan_placement(self._h, ms, ctypes.byref(kept)))
         return (float(ms[0]), float(ms[1])), int(kept.value)
 
     def set_pearson(self, spectral=True):
         """spectral (the default on real-column plans): the coefficient from r[peak] and the forward pass's band sums, no second
         pass over the inputs; False: the reference's reduction over both segments (include/audiosync/xcorr_hip.h)"""
-        if lib().asx_plan_set_pearson(self._h, 1 if spectral else 0) != 0:
-            raise AsxError(_err())
+        _check(lib().asx_plan_set_pearson(self._h, 1 if spectral else 0))
 
     def pearson_modes(self):
         """pairs so far that took (spectral, spectral + wrap-around correction, direct) under the spectral setting"""
         c = (ctypes.c_uint64 * 3)()
-        if lib().asx_plan_pearson_modes(self._h, c) != 0:
-            raise AsxError(_err())
+        _check(lib().asx_plan_pearson_modes(self._h, c))
         return tuple(int(v) for v in c)
 
     def set_prune(self, on=True):
         """on (the default on real-column plans): in-scope groups skip the inverse column tiles whose energy bound rules out the
         peak and its near-ties; same lag, ret and coefficient bits either way (include/audiosync/xcorr_hip.h)"""
-        if lib().asx_plan_set_prune(self._h, 1 if on else 0) != 0:
-            raise AsxError(_err())
+        _check(lib().asx_plan_set_prune(self._h, 1 if on else 0))
 
     def prune_stats(self):
         """(column tiles the pruned groups transformed, tiles those groups had in all) over the plan's life"""
-        a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        if lib().asx_plan_prune_stats(self._h, ctypes.byref(a), ctypes.byref(b)) != 0:
-            raise AsxError(_err())
-        return int(a.value), int(b.value)
+        return _counters(lib().asx_plan_prune_stats, self._h, 2)
 
     def narrowed_calls(self):
         """xcorr_f64 calls whose frames were all exactly float32 and crossed PCIe as 4 bytes each"""
-        c = ctypes.c_uint64(0)
-        if lib().asx_plan_narrowed_calls(self._h, ctypes.byref(c)) != 0:
-            raise AsxError(_err())
-        return c.value
+        return _counters(lib().asx_plan_narrowed_calls, self._h, 1)[0]
 
     def peak_repairs(self):
         """overflowing pairs that were looked at again with lists for all 2N lags"""
-        c = ctypes.c_uint64(0)
-        if lib().asx_plan_peak_repairs(self._h, ctypes.byref(c)) != 0:
-            raise AsxError(_err())
-        return c.value
+        return _counters(lib().asx_plan_peak_repairs, self._h, 1)[0]
 
     @property
     def workspace_bytes(self):
@@ -745,113 +713,85 @@ class Plan:
         lag = np.zeros(batch, dtype=np.int64)
         coef = np.zeros(batch, dtype=np.float64)
         ret = np.zeros(batch, dtype=np.int32)
-        rc = lib().asx_xcorr_batch_f32(self._h, s.ctypes.data_as(c_f32p), t.ctypes.data_as(c_f32p), batch,
-                                       lag.ctypes.data_as(c_i64p), coef.ctypes.data_as(c_f64p),
-                                       ret.ctypes.data_as(c_i32p))
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_batch_f32(self._h, s.ctypes.data_as(c_f32p), t.ctypes.data_as(c_f32p), batch,
+                                         lag.ctypes.data_as(c_i64p), coef.ctypes.data_as(c_f64p), ret.ctypes.data_as(c_i32p)))
         return lag, coef, ret
 
     def xcorr_batch_dev(self, d_src, d_smp, batch, d_lag, d_coef, d_ret, stream=0):
         """raw device pointers (ints); asynchronous on `stream` (0 = the plan's own)"""
-        rc = lib().asx_xcorr_batch_f32_dev(self._h, d_src, d_smp, batch, d_lag or None, d_coef,
-                                           d_ret or None, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_batch_f32_dev(self._h, d_src, d_smp, batch, d_lag or None, d_coef, d_ret or None, stream or None))
 
     def xcorr_strided_dev(self, d_src, src_stride, d_smp, smp_stride, batch, d_lag, d_coef, d_ret, stream=0):
         """raw device pointers (ints), strides in floats (0 = one track for every pair; see asx_xcorr_strided_f32_dev);
         asynchronous on `stream` (0 = the plan's own)"""
-        rc = lib().asx_xcorr_strided_f32_dev(self._h, d_src, int(src_stride), d_smp, int(smp_stride), int(batch), d_lag or None,
-                                             d_coef, d_ret or None, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_strided_f32_dev(self._h, d_src, int(src_stride), d_smp, int(smp_stride), int(batch), d_lag or None,
+                                               d_coef, d_ret or None, stream or None))
 
     def xcorr_windowed_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, d_lag, d_coef, d_ret,
                            stream=0):
         """raw device pointers (ints): asx_xcorr_windowed_f32_dev -- the strided batch with pair i's lag window at
         d_windows[2 i window_stride], d_windows[2 i window_stride + 1] (int64, device memory); asynchronous on `stream`"""
-        rc = lib().asx_xcorr_windowed_f32_dev(self._h, d_src, int(src_stride), d_smp, int(smp_stride), d_windows, int(window_stride),
-                                              int(batch), d_lag or None, d_coef, d_ret, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_windowed_f32_dev(self._h, d_src, int(src_stride), d_smp, int(smp_stride), d_windows, int(window_stride),
+                                                int(batch), d_lag or None, d_coef, d_ret, stream or None))
 
     def xcorr_phat_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, d_lag, d_coef, d_peak, d_ret,
                        stream=0):
         """raw device pointers (ints): asx_xcorr_phat_f32_dev -- the strided batch ranked by the GCC-PHAT curve; d_windows = 0: the
         plan's window applies, else per-pair rows as in xcorr_windowed_dev; d_peak (float64, may be 0) receives |r_phat[lag]| / F;
         always asynchronous on `stream`"""
-        rc = lib().asx_xcorr_phat_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride), d_windows or None,
-                                          int(window_stride), int(batch), d_lag or None, d_coef or None, d_peak or None,
-                                          d_ret or None, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_phat_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride), d_windows or None,
+                                            int(window_stride), int(batch), d_lag or None, d_coef or None, d_peak or None,
+                                            d_ret or None, stream or None))
 
     def phat_debug_r_dev(self, d_src, d_smp, d_r, d_lag, d_coef, d_peak, d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_phat_debug_r_dev -- one contiguous pair, r_phat of all 2N lags (times F) to d_r"""
-        rc = lib().asx_xcorr_phat_debug_r_dev(self._h, d_src or None, d_smp or None, d_r or None, d_lag or None, d_coef or None,
-                                              d_peak or None, d_ret or None, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_phat_debug_r_dev(self._h, d_src or None, d_smp or None, d_r or None, d_lag or None, d_coef or None,
+                                                d_peak or None, d_ret or None, stream or None))
 
     def xcorr_phat_band_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, bin_lo, bin_hi, d_lag, d_coef,
                             d_peak, d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_phat_band_f32_dev -- xcorr_phat_dev in which only bins bin_lo..bin_hi of the
         2N-point transform vote (band_bins converts from Hz); d_peak receives |r_phat[lag]| / V, V the number of bins that vote"""
-        rc = lib().asx_xcorr_phat_band_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride), d_windows or None,
-                                               int(window_stride), int(batch), int(bin_lo), int(bin_hi), d_lag or None, d_coef or None,
-                                               d_peak or None, d_ret or None, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_phat_band_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride),
+                                                 d_windows or None, int(window_stride), int(batch), int(bin_lo), int(bin_hi),
+                                                 d_lag or None, d_coef or None, d_peak or None, d_ret or None, stream or None))
 
     def phat_band_debug_r_dev(self, d_src, d_smp, bin_lo, bin_hi, d_r, d_lag, d_coef, d_peak, d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_phat_band_debug_r_dev -- one contiguous pair, r_phat of all 2N lags (times V) to d_r"""
-        rc = lib().asx_xcorr_phat_band_debug_r_dev(self._h, d_src or None, d_smp or None, int(bin_lo), int(bin_hi), d_r or None,
-                                                   d_lag or None, d_coef or None, d_peak or None, d_ret or None, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_phat_band_debug_r_dev(self._h, d_src or None, d_smp or None, int(bin_lo), int(bin_hi), d_r or None,
+                                                     d_lag or None, d_coef or None, d_peak or None, d_ret or None, stream or None))
 
     def xcorr_topk_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, k, min_separation, d_lag, d_coef,
                        d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_topk_f32_dev -- the k strongest lags of pair i at least min_separation apart, entry j
         at index i*k + j of d_lag / d_coef / d_ret; d_windows = 0: the plan's window applies; asynchronous on `stream`"""
-        rc = lib().asx_xcorr_topk_f32_dev(self._h, d_src, int(src_stride), d_smp, int(smp_stride), d_windows or None,
-                                          int(window_stride), int(batch), int(k), int(min_separation), d_lag or None, d_coef,
-                                          d_ret or None, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_topk_f32_dev(self._h, d_src, int(src_stride), d_smp, int(smp_stride), d_windows or None,
+                                            int(window_stride), int(batch), int(k), int(min_separation), d_lag or None, d_coef,
+                                            d_ret or None, stream or None))
 
     def xcorr_pool_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows, window_stride,
                        batch, d_lag, d_coef, d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_pool_f32_dev -- pair i is source d_pairs[2 i] of the source pool against sample
         d_pairs[2 i + 1] of the sample pool (int32, device memory); d_pairs = 0: every combination, source-major, batch =
         nsources * nsamples; d_windows = 0: the plan's window; asynchronous on `stream`"""
-        rc = lib().asx_xcorr_pool_f32_dev(self._h, d_sources, int(source_stride), int(nsources), d_samples, int(sample_stride),
-                                          int(nsamples), d_pairs or None, d_windows or None, int(window_stride), int(batch),
-                                          d_lag or None, d_coef, d_ret, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_pool_f32_dev(self._h, d_sources, int(source_stride), int(nsources), d_samples, int(sample_stride),
+                                            int(nsamples), d_pairs or None, d_windows or None, int(window_stride), int(batch),
+                                            d_lag or None, d_coef, d_ret, stream or None))
 
     def xcorr_pool_topk_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows,
                             window_stride, batch, k, min_separation, d_lag, d_coef, d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_pool_topk_f32_dev -- xcorr_pool_dev's pairs with the k strongest lags of pair i at
         least min_separation apart, entry j at index i*k + j of d_lag / d_coef / d_ret; asynchronous on `stream`"""
-        rc = lib().asx_xcorr_pool_topk_f32_dev(self._h, d_sources, int(source_stride), int(nsources), d_samples, int(sample_stride),
-                                               int(nsamples), d_pairs or None, d_windows or None, int(window_stride), int(batch),
-                                               int(k), int(min_separation), d_lag or None, d_coef, d_ret, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_pool_topk_f32_dev(self._h, d_sources, int(source_stride), int(nsources), d_samples, int(sample_stride),
+                                                 int(nsamples), d_pairs or None, d_windows or None, int(window_stride), int(batch),
+                                                 int(k), int(min_separation), d_lag or None, d_coef, d_ret, stream or None))
 
     def debug_prune(self, pair=0):
         """diagnostic: (upper bounds of |r| per column tile, the largest-bound tile) of `pair` of the last pruned group"""
         n = (self.split[1] + self.split[2] - 1) // self.split[2]
         ub = (ctypes.c_float * n)()
         best = ctypes.c_int(-1)
-        f = lib().asx_plan_debug_prune
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int), ctypes.c_size_t]
-        if f(self._h, int(pair), ub, ctypes.byref(best), n) != 0:
-            raise AsxError("asx_plan_debug_prune failed")
+        _check(lib().asx_plan_debug_prune(self._h, int(pair), ub, ctypes.byref(best), n), "asx_plan_debug_prune failed")
         return np.frombuffer(ub, dtype=np.float32).copy(), int(best.value)
 
     def debug_peak(self, pair=0):
@@ -861,14 +801,8 @@ class Plan:
         cap = self.peak_capacity
         b2, cn, rn, pm = ctypes.c_float(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
         vals, idxs = np.zeros(cap, dtype=np.float64), np.zeros(cap, dtype=np.uint32)
-        f = lib().asx_plan_debug_peak
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32),
-                      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.c_void_p,
-                      ctypes.c_size_t]
-        if f(self._h, int(pair), ctypes.byref(b2), ctypes.byref(cn), ctypes.byref(rn), ctypes.byref(pm), vals.ctypes.data,
-             idxs.ctypes.data, cap) != 0:
-            raise AsxError("asx_plan_debug_peak failed")
+        _check(lib().asx_plan_debug_peak(self._h, int(pair), ctypes.byref(b2), ctypes.byref(cn), ctypes.byref(rn), ctypes.byref(pm),
+                                         vals.ctypes.data, idxs.ctypes.data, cap), "asx_plan_debug_peak failed")
         key = index = None
         if pm.value:   # peak_pack_key (csrc/xcorr_dev.h): an order-preserving key in the high word, ~index in the low word
             hi = pm.value >> 32
@@ -886,16 +820,12 @@ class Plan:
         mode; seg: the pair's segment; pick: asx_spec_pick as a one-thread kernel evaluates it from that state"""
         ntiles = (self.split[1] + self.split[2] - 1) // self.split[2]
         f = lib().asx_plan_debug_spectral
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.c_void_p, ctypes.c_size_t, c_intp, ctypes.c_void_p, ctypes.c_size_t, c_f64p,
-                      ctypes.POINTER(ctypes.c_longlong), c_f64p]
         dims, hdr, seg, pick = (ctypes.c_int * 4)(), (ctypes.c_double * 4)(), (ctypes.c_longlong * 6)(), (ctypes.c_double * 8)()
-        if f(self._h, int(pair), dims, None, 0, hdr, seg, pick) != 0:
-            raise AsxError("asx_plan_debug_spectral failed (a real-column plan that has run a group?)")
+        _check(f(self._h, int(pair), dims, None, 0, hdr, seg, pick),
+               "asx_plan_debug_spectral failed (a real-column plan that has run a group?)")
         assert dims[0] == ntiles, (dims[0], ntiles)
         band = np.zeros((2, dims[0], dims[1], 2), dtype=np.float32)
-        if f(self._h, int(pair), dims, band.ctypes.data, band.size, hdr, seg, pick) != 0:
-            raise AsxError("asx_plan_debug_spectral failed")
+        _check(f(self._h, int(pair), dims, band.ctypes.data, band.size, hdr, seg, pick), "asx_plan_debug_spectral failed")
         return {"band": band, "nbands": dims[1], "band_rows": dims[2], "prep_blocks": dims[3],
                 "r": hdr[0], "rb": hdr[1], "direct": hdr[2] != 0.0, "mode": int(hdr[3]),
                 "seg": dict(zip(("lag", "src_off", "smp_off", "len", "peak", "flags"), (int(v) for v in seg))),
@@ -905,16 +835,36 @@ class Plan:
     def debug_kernels(self):
         """the kernels this plan runs, as planmath_kernels spells them: the record made when the plan was built"""
         f = lib().asx_plan_debug_kernels
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.c_void_p, c_intp, c_intp, c_intp]
         return _kernel_choice(lambda *a: f(self._h, *a))
 
     def debug_bank(self):
         """(source tracks, sample tracks) the plan's pool bank holds, and how many pool calls have filled it"""
-        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-        if lib().asx_plan_debug_bank(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)) != 0:
-            raise AsxError("asx_plan_debug_bank failed")
-        return a.value, b.value, c.value
+        return _counters(lib().asx_plan_debug_bank, self._h, 3, "asx_plan_debug_bank failed")
+
+    def debug_over_list(self):
+        """diagnostic: the plan's list of overflowed pairs as it stands, (count on the device, count of the host's mirror), read
+        without emptying it"""
+        d, h = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib().asx_plan_debug_over_list(self._h, ctypes.byref(d), ctypes.byref(h)), "asx_plan_debug_over_list failed")
+        return d.value, h.value
+
+    def debug_stamps(self, cap):
+        """diagnostic (a -DASX_STAMPS build run under ASX_STAMPS): the cycle stamps the last stamped kernel's blocks wrote, at most
+        `cap` of them, as a uint64 array of 8 per block"""
+        buf = np.zeros(int(cap), dtype=np.uint64)
+        got = lib().asx_plan_debug_stamps(self._h, buf.ctypes.data, buf.size)
+        if got < 0:
+            raise AsxError("asx_plan_debug_stamps failed (a plan created under ASX_STAMPS?)")
+        return buf[:got]
+
+    def _staged(self, inputs, shape, dtypes, launch):
+        """host arrays `inputs` (None: a null pointer) -> device copies; launch(*input pointers, *output pointers) makes the _dev
+        call; -> the outputs, one host array of `shape` per dtype of `dtypes`"""
+        with _Staging(self) as st:
+            d_in = [st.upload(a) for a in inputs]
+            d_out = [st.output(shape, dt) for dt in dtypes]
+            launch(*d_in, *d_out)
+            return st.fetch()
 
     def xcorr_pool_f32(self, sources, samples, pairs=None, windows=None):
         """Many tracks against many (asx_xcorr_pool_f32_dev): sources float32 [S, 2N], samples [R, N]; pairs None (every combination)
@@ -922,7 +872,11 @@ class Plan:
         xcorr_windowed_f32.  Every track is transformed once per call.  Shapes are checked on the host (ValueError) before anything is
         uploaded; an index outside its pool gives that pair (0, NaN, -4).  Returns (lag int64, coef float64, ret int32) of shape [B],
         or [S, R] when pairs is None."""
-        return Plan._pool_host(self, *pool_args(self.sample_len, sources, samples, pairs, windows))
+        n = self.sample_len
+        s, t, pr, w, batch, ws = pool_args(n, sources, samples, pairs, windows)
+        shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
+        return self._staged((s, t, pr, w), shape, _RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, *d_out))
 
     def xcorr_pool_topk_f32(self, sources, samples, k, min_separation, pairs=None, windows=None):
         """The k strongest separated lags per pair of two pools (asx_xcorr_pool_topk_f32_dev): the pools, pairs and windows of
@@ -930,54 +884,11 @@ class Plan:
         are checked on the host (ValueError) before anything is uploaded.  Returns (lag int64, coef float64, ret int32) of shape
         [B, k], or [S, R, k] when pairs is None; ret = -3 where no lag was left, -4 in all k entries of a pair with an index outside
         its pool."""
-        a = pool_topk_args(self.sample_len, sources, samples, k, min_separation, pairs, windows)
-        return Plan._pool_host(self, *a[:6], topk=a[6:])
-
-    def _pool_host(self, s, t, pr, w, batch, ws, topk=None):
-        """checked host arrays (pool_args) -> device copies -> asx_xcorr_pool_f32_dev (topk = (k, min_separation):
-        asx_xcorr_pool_topk_f32_dev, a last axis of k entries) -> (lag, coef, ret)"""
-        L = lib()
-        bufs = []
-        try:
-            def dev(nbytes):
-                ptr = L.asx_device_malloc(max(int(nbytes), 16), self.device)
-                if not ptr:
-                    raise AsxError(_err())
-                bufs.append(ptr)
-                return ptr
-            ups = [(dev(s.nbytes), s), (dev(t.nbytes), t)]
-            d_pairs = dev(pr.nbytes) if pr is not None else 0
-            d_win = dev(w.nbytes) if w is not None else 0
-            if pr is not None:
-                ups.append((d_pairs, pr))
-            if w is not None:
-                ups.append((d_win, w))
-            entries = batch if topk is None else batch * topk[0]
-            d_lag, d_coef, d_ret = dev(8 * entries), dev(8 * entries), dev(4 * entries)
-            for d, h in ups:
-                if L.asx_memcpy_h2d(d, h.ctypes.data, h.nbytes) != 0:
-                    raise AsxError(_err())
-            n = self.sample_len
-            if topk is None:
-                self.xcorr_pool_dev(ups[0][0], 2 * n, s.shape[0], ups[1][0], n, t.shape[0], d_pairs, d_win, ws, batch, d_lag, d_coef,
-                                    d_ret)
-            else:
-                self.xcorr_pool_topk_dev(ups[0][0], 2 * n, s.shape[0], ups[1][0], n, t.shape[0], d_pairs, d_win, ws, batch, topk[0],
-                                         topk[1], d_lag, d_coef, d_ret)
-            self.sync()
-            shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
-            if topk is not None:
-                shape += (topk[0],)
-            lag = np.zeros(shape, dtype=np.int64)
-            coef = np.zeros(shape, dtype=np.float64)
-            ret = np.zeros(shape, dtype=np.int32)
-            for h, d in ((lag, d_lag), (coef, d_coef), (ret, d_ret)):
-                if L.asx_memcpy_d2h(h.ctypes.data, d, h.nbytes) != 0:
-                    raise AsxError(_err())
-            return lag, coef, ret
-        finally:
-            for ptr in bufs:
-                L.asx_device_free(ptr)
+        n = self.sample_len
+        s, t, pr, w, batch, ws, k, sep = pool_topk_args(n, sources, samples, k, min_separation, pairs, windows)
+        shape = ((batch,) if pr is not None else (s.shape[0], t.shape[0])) + (k,)
+        return self._staged((s, t, pr, w), shape, _RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_topk_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, k, sep, *d_out))
 
     def xcorr_topk_f32(self, source, sample, k, min_separation, windows=None):
         """The k strongest separated lags per pair (asx_xcorr_topk_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N];
@@ -985,7 +896,8 @@ class Plan:
         window's lags farther than min_separation from entries 0..j-1.  Arguments are checked on the host (ValueError) before
         anything is uploaded.  Returns (lag int64 [B, k], coef float64 [B, k], ret int32 [B, k]); ret = -3 where no lag was left."""
         s, t, w, batch, ss, ts, ws, k, sep = topk_args(self.sample_len, source, sample, k, min_separation, windows)
-        return self._strided_host(s, ss, t, ts, batch, w, ws, topk=(k, sep))
+        return self._staged((s, t, w), (batch, k), _RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_topk_dev(
+            d_s, ss, d_t, ts, d_w, ws, batch, k, sep, *d_out))
 
     def xcorr_phat_band_f32(self, source, sample, bin_lo, bin_hi, windows=None):
         """xcorr_phat_f32 in which only bins bin_lo..bin_hi of the 2N-point transform vote (asx_xcorr_phat_band_f32_dev; band_bins
@@ -997,95 +909,28 @@ class Plan:
         1-D operand serves every pair.  windows: None (the plan's window), or integers [2] / [B, 2] as in xcorr_windowed_f32.
         Returns (lag int64[B], coef float64[B], peak float64[B], ret int32[B]): the float32 argmax of r_phat, the reference's
         Pearson coefficient of the samples at that lag, and the peak height |r_phat[lag]| / F in [0, 1].  band: xcorr_phat_band_f32's."""
-        n = self.sample_len
-        s, t, w, batch, ss, ts, ws = windowed_args(n, source, sample, np.zeros(2, dtype=np.int64) if windows is None else windows)
-        if windows is None:
-            w, ws = None, 0
-        L = lib()
-        bufs = []
-        try:
-            def dev(host=None, nbytes=0):
-                nbytes = host.nbytes if host is not None else nbytes
-                ptr = L.asx_device_malloc(max(int(nbytes), 16), self.device)
-                if not ptr:
-                    raise AsxError(_err())
-                bufs.append(ptr)
-                if host is not None and L.asx_memcpy_h2d(ptr, host.ctypes.data, nbytes) != 0:
-                    raise AsxError(_err())
-                return ptr
-            d_src, d_smp = dev(s), dev(t)
-            d_win = dev(w) if w is not None else 0
-            out = [np.zeros(batch, dtype=dt) for dt in (np.int64, np.float64, np.float64, np.int32)]
-            d_out = [dev(nbytes=h.nbytes) for h in out]
-            if band is None:
-                self.xcorr_phat_dev(d_src, ss, d_smp, ts, d_win, ws, batch, *d_out)
-            else:
-                self.xcorr_phat_band_dev(d_src, ss, d_smp, ts, d_win, ws, batch, band[0], band[1], *d_out)
-            self.sync()
-            for h, d in zip(out, d_out):
-                if L.asx_memcpy_d2h(h.ctypes.data, d, h.nbytes) != 0:
-                    raise AsxError(_err())
-            return tuple(out)
-        finally:
-            for ptr in bufs:
-                L.asx_device_free(ptr)
+        s, t, w, batch, ss, ts, ws = _strided_args(self.sample_len, source, sample, None if windows is None else _window_rows(windows))
+        if band is None:
+            return self._staged((s, t, w), (batch,), _PHAT_RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_phat_dev(
+                d_s, ss, d_t, ts, d_w, ws, batch, *d_out))
+        return self._staged((s, t, w), (batch,), _PHAT_RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_phat_band_dev(
+            d_s, ss, d_t, ts, d_w, ws, batch, band[0], band[1], *d_out))
 
-    def _strided_host(self, src, src_stride, smp, smp_stride, batch, windows=None, window_stride=0, topk=None):
-        """host float32 buffers (and int64 windows) -> device copies -> asx_xcorr_strided_f32_dev (asx_xcorr_windowed_f32_dev;
-        topk = (k, min_separation): asx_xcorr_topk_f32_dev, results [batch, k]) -> (lag, coef, ret)"""
-        L = lib()
-        bufs = []
-        try:
-            def dev(nbytes):
-                ptr = L.asx_device_malloc(max(int(nbytes), 16), self.device)
-                if not ptr:
-                    raise AsxError(_err())
-                bufs.append(ptr)
-                return ptr
-            d_src, d_smp = dev(src.nbytes), dev(smp.nbytes)
-            shape = (batch,) if topk is None else (batch, topk[0])
-            entries = batch if topk is None else batch * topk[0]
-            d_lag, d_coef, d_ret = dev(8 * entries), dev(8 * entries), dev(4 * entries)
-            ups = [(d_src, src), (d_smp, smp)]
-            if windows is not None:
-                ups.append((dev(windows.nbytes), windows))
-            for d, h in ups:
-                if L.asx_memcpy_h2d(d, h.ctypes.data, h.nbytes) != 0:
-                    raise AsxError(_err())
-            if topk is not None:
-                self.xcorr_topk_dev(d_src, src_stride, d_smp, smp_stride, ups[2][0] if windows is not None else 0, window_stride, batch,
-                                    topk[0], topk[1], d_lag, d_coef, d_ret)
-            elif windows is None:
-                self.xcorr_strided_dev(d_src, src_stride, d_smp, smp_stride, batch, d_lag, d_coef, d_ret)
-            else:
-                self.xcorr_windowed_dev(d_src, src_stride, d_smp, smp_stride, ups[2][0], window_stride, batch, d_lag, d_coef, d_ret)
-            self.sync()
-            lag = np.zeros(shape, dtype=np.int64)
-            coef = np.zeros(shape, dtype=np.float64)
-            ret = np.zeros(shape, dtype=np.int32)
-            for h, d in ((lag, d_lag), (coef, d_coef), (ret, d_ret)):
-                if L.asx_memcpy_d2h(h.ctypes.data, d, h.nbytes) != 0:
-                    raise AsxError(_err())
-            return lag, coef, ret
-        finally:
-            for ptr in bufs:
-                L.asx_device_free(ptr)
+    def _strided_f32(self, src, src_stride, smp, smp_stride, batch, windows=None, window_stride=0):
+        """checked host float32 buffers -> asx_xcorr_strided_f32_dev (with int64 window rows: asx_xcorr_windowed_f32_dev) ->
+        (lag, coef, ret) of [batch]"""
+        if windows is None:
+            return self._staged((src, smp), (batch,), _RESULTS, lambda d_s, d_t, *d_out: self.xcorr_strided_dev(
+                d_s, src_stride, d_t, smp_stride, batch, *d_out))
+        return self._staged((src, smp, windows), (batch,), _RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_windowed_dev(
+            d_s, src_stride, d_t, smp_stride, d_w, window_stride, batch, *d_out))
 
     def xcorr_broadcast_f32(self, source, sample):
         """One track against many.  source: float32 [2N] (one source for every pair) or [B, 2N]; sample: [N] (one sample for every
         pair) or [B, N].  At least one may be 1-D; with both 1-D there is one pair.  The 1-D track is transformed once per call
         (real-column plans).  Returns (lag int64[B], coef float64[B], ret int32[B]) like xcorr_batch_f32."""
-        n = self.sample_len
-        s = np.ascontiguousarray(source, dtype=np.float32)
-        t = np.ascontiguousarray(sample, dtype=np.float32)
-        if s.ndim not in (1, 2) or t.ndim not in (1, 2) or s.shape[-1] != 2 * n or t.shape[-1] != n:
-            raise ValueError("source must be [2N] or [B, 2N] and sample [N] or [B, N] with N = %d" % n)
-        bs = s.shape[0] if s.ndim == 2 else None
-        bt = t.shape[0] if t.ndim == 2 else None
-        if bs is not None and bt is not None and bs != bt:
-            raise ValueError("source and sample have different batch sizes (%d, %d)" % (bs, bt))
-        batch = bs if bs is not None else bt if bt is not None else 1
-        return self._strided_host(s, 2 * n if s.ndim == 2 else 0, t, n if t.ndim == 2 else 0, batch)
+        s, t, ss, ts = _operands(self.sample_len, source, sample)
+        return self._strided_f32(s, ss, t, ts, _shared_batch(s, t))
 
     def xcorr_windowed_f32(self, source, sample, windows):
         """Pairs with a lag window each (asx_xcorr_windowed_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N];
@@ -1094,7 +939,7 @@ class Plan:
         inside [-N, N-1] gives that pair (0, NaN, -2).  The plan's own window is not used.  Returns (lag, coef, ret) like
         xcorr_batch_f32."""
         s, t, w, batch, ss, ts, ws = windowed_args(self.sample_len, source, sample, windows)
-        return self._strided_host(s, ss, t, ts, batch, w, ws)
+        return self._strided_f32(s, ss, t, ts, batch, w, ws)
 
     def xcorr_windows_f32(self, recording, sample, hop, positions=None):
         """Windows recording[k*hop : k*hop + 2N] (k = 0 .. (len - 2N) // hop) of one long float32 recording, each correlated with
@@ -1118,22 +963,20 @@ class Plan:
             raise ValueError("recording shorter than one window of 2N = %d frames" % (2 * n))
         batch = (r.size - 2 * n) // hop + 1
         if positions is None:
-            return self._strided_host(r, hop, t, 0, batch)
+            return self._strided_f32(r, hop, t, 0, batch)
         p_lo, p_hi = (int(v) for v in positions)
         k0, k1, rows = position_rows(n, hop, batch, p_lo, p_hi)
         lag = np.zeros(batch, dtype=np.int64)
         coef = np.full(batch, np.nan, dtype=np.float64)
         ret = np.full(batch, -2, dtype=np.int32)
         if k1 > k0:
-            part = self._strided_host(np.ascontiguousarray(r[k0 * hop:(k1 - 1) * hop + 2 * n]), hop, t, 0, k1 - k0, rows, 1)
+            part = self._strided_f32(np.ascontiguousarray(r[k0 * hop:(k1 - 1) * hop + 2 * n]), hop, t, 0, k1 - k0, rows, 1)
             for whole, got in zip((lag, coef, ret), part):
                 whole[k0:k1] = got
         return lag, coef, ret
 
     def debug_r_dev(self, d_src, d_smp, d_r, d_lag, d_coef, d_ret, stream=0):
-        rc = lib().asx_xcorr_debug_r_dev(self._h, d_src, d_smp, d_r, d_lag, d_coef, d_ret, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_xcorr_debug_r_dev(self._h, d_src, d_smp, d_r, d_lag, d_coef, d_ret, stream or None))
 
     def set_profiling(self, depth):
         """depth > 0: keep the kernel events of the last `depth` batch calls; 0 / False: off"""
@@ -1141,12 +984,8 @@ class Plan:
 
     def last_timings_ms(self, calls_back=0):
         out = (ctypes.c_float * 6)()
-        rc = lib().asx_plan_timings_ms(self._h, int(calls_back), out)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_plan_timings_ms(self._h, int(calls_back), out))
         return dict(zip(("fwd_cols", "rows", "inv_cols", "finalize", "pearson", "total"), list(out)))
 
     def sync(self, stream=0):
-        rc = lib().asx_stream_sync(self._h, stream or None)
-        if rc != 0:
-            raise AsxError(_err())
+        _check(lib().asx_stream_sync(self._h, stream or None))

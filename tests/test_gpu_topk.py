@@ -194,13 +194,7 @@ def period8(n):
 
 def over_list(mod, plan):
     """the plan's list of overflowed pairs as it stands (device count, host mirror), read without emptying it"""
-    import ctypes
-    L = mod.lib()
-    L.asx_plan_debug_over_list.restype = ctypes.c_int
-    L.asx_plan_debug_over_list.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
-    d, h = ctypes.c_uint32(99), ctypes.c_uint32(99)
-    assert L.asx_plan_debug_over_list(plan._h, ctypes.byref(d), ctypes.byref(h)) == 0
-    return d.value, h.value
+    return plan.debug_over_list()
 
 
 def check_exact_and_async(mod, n, src, smp, k, sep, first_overflow, exact_r=None):

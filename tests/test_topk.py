@@ -112,7 +112,7 @@ def test_plan_method_checks_before_it_uploads():
     class NoDevice:
         sample_len = 16
 
-        def _strided_host(self, *a, **kw):
+        def _staged(self, *a, **kw):
             raise AssertionError("uploaded")
 
     for k, sep in ((0, 0), (9, 0), (2, -1)):

@@ -1,6 +1,6 @@
 """tools/dbg/cu_mates.py [fwd|invhw] -- which blocks of a column kernel's launch share a CU, and when they start (needs tools/experiments/column_kernels_hw_stamps.patch applied and a -DASX_STAMPS build:
 tools/mkfull.sh r_stamps "-DASX_STAMPS").  Prints, for the first generation of blocks, how the launch-order index of CU mates relates."""
-import ctypes, os, sys, collections
+import os, sys, collections
 import numpy as np
 which = sys.argv[1] if len(sys.argv) > 1 else "invhw"
 os.environ["ASX_STAMPS"] = which
@@ -17,13 +17,7 @@ plan = asx.Plan(n, batch, 0)
 for _ in range(3):
     plan.xcorr_batch_dev(d_src.data_ptr(), d_smp.data_ptr(), batch, d_lag.data_ptr(), d_coef.data_ptr(), d_ret.data_ptr(), st)
 torch.cuda.synchronize()
-L = asx.lib()
-L.asx_plan_debug_stamps.restype = ctypes.c_long
-L.asx_plan_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-cap = 8 * 80000
-buf = np.zeros(cap, dtype=np.uint64)
-got = L.asx_plan_debug_stamps(plan._h, buf.ctypes.data, cap)
-s = buf[:got].reshape(-1, 8).astype(np.int64)
+s = plan.debug_stamps(8 * 80000).reshape(-1, 8).astype(np.int64)
 hw, t0 = s[:, 6], s[:, 7]
 ok = t0 > 0
 idx = np.nonzero(ok)[0]

@@ -1,4 +1,4 @@
-import ctypes, os, sys
+import os, sys
 import numpy as np
 os.environ["ASX_STAMPS"] = "inv"
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
@@ -14,13 +14,7 @@ plan = asx.Plan(n, batch, 0)
 for _ in range(3):
     plan.xcorr_batch_dev(d_src.data_ptr(), d_smp.data_ptr(), batch, d_lag.data_ptr(), d_coef.data_ptr(), d_ret.data_ptr(), st)
 torch.cuda.synchronize()
-L = asx.lib()
-L.asx_plan_debug_stamps.restype = ctypes.c_long
-L.asx_plan_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-cap = 8 * 64 * 8192
-buf = np.zeros(cap, dtype=np.uint64)
-got = L.asx_plan_debug_stamps(plan._h, buf.ctypes.data, cap)
-s = buf[:got].reshape(-1, 8).astype(np.int64)
+s = plan.debug_stamps(8 * 64 * 8192).reshape(-1, 8).astype(np.int64)
 s = s[(s[:, 3] > 0) & (s[:, 4] > 0) & (s[:, 5] > 0)]
 print("blocks", len(s))
 # order of stamps in time: 0 start, 1 (fed begin), 2 head done, 4 after last stage + per-thread scan, 5 after reduce/fold, 3 end

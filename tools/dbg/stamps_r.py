@@ -1,6 +1,6 @@
 """tools/dbg/stamps_r.py [rows|inv] [N] -- per-phase cycle shares of the real-column kernels (needs a -DASX_STAMPS build of
 csrc/rlayout.hip: tools/mkr.sh r_stamps "-DASX_STAMPS", copied over libaudiosync_hip.so)"""
-import ctypes, os, sys
+import os, sys
 import numpy as np
 which = sys.argv[1] if len(sys.argv) > 1 else "rows"
 os.environ["ASX_STAMPS"] = {"rows": "1", "inv": "inv"}[which]
@@ -17,13 +17,7 @@ plan = asx.Plan(n, batch, 0)
 for _ in range(3):
     plan.xcorr_batch_dev(d_src.data_ptr(), d_smp.data_ptr(), batch, d_lag.data_ptr(), d_coef.data_ptr(), d_ret.data_ptr(), st)
 torch.cuda.synchronize()
-L = asx.lib()
-L.asx_plan_debug_stamps.restype = ctypes.c_long
-L.asx_plan_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-cap = 8 * 64 * 8192
-buf = np.zeros(cap, dtype=np.uint64)
-got = L.asx_plan_debug_stamps(plan._h, buf.ctypes.data, cap)
-s = buf[:got].reshape(-1, 8).astype(np.int64)
+s = plan.debug_stamps(8 * 64 * 8192).reshape(-1, 8).astype(np.int64)
 if which == "rows":
     seq = [0, 1, 2, 3, 4]
     names = ["loads + twiddles + fill", "forward stage 0", "wave-local chain (fwd 1, 2, product, inv 2, 1)", "inverse stage 0 (+ last radix-2) + stores"]

@@ -37,7 +37,7 @@ def main():
         d_src = torch.empty(batch * 2 * n, dtype=torch.float32, device="cuda")
         d_smp = torch.empty(batch * n, dtype=torch.float32, device="cuda")
         d_true = torch.empty(batch, dtype=torch.int64, device="cuda")
-        asx.lib().asx_synth_pairs_dev(2024, 0, batch, n, 1, d_src.data_ptr(), d_smp.data_ptr(), d_true.data_ptr(), None)
+        asx.synth_pairs_dev(2024, 0, batch, n, 1, d_src.data_ptr(), d_smp.data_ptr(), d_true.data_ptr())
         rows = torch.tensor([[-n, n - 1]] * batch, dtype=torch.int64, device="cuda")
         out = {k: (torch.empty(batch, dtype=torch.int64, device="cuda"), torch.empty(batch, dtype=torch.float64, device="cuda"),
                    torch.empty(batch, dtype=torch.int32, device="cuda")) for k in ("strided", "windowed", "plan_window")}

@@ -71,7 +71,7 @@ def main():
                     d_src.normal_(generator=g)
                     d_smp.normal_(generator=g)
                 else:
-                    asx.lib().asx_synth_pairs_dev(20260101, 0, batch, n, 1, d_src.data_ptr(), d_smp.data_ptr(), d_lag.data_ptr(), None)
+                    asx.synth_pairs_dev(20260101, 0, batch, n, 1, d_src.data_ptr(), d_smp.data_ptr(), d_lag.data_ptr())
                 torch.cuda.synchronize()
                 times = {True: [], False: []}
                 fam = {(on, k): [] for on in (True, False) for k in ("rows", "inv_cols")}

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """diagnostic: per-phase cycle shares of one transform kernel (needs a -DASX_STAMPS build).
 usage: stamps.py [N] [split|-] [rows|fwd|inv]"""
-import ctypes, os, sys
+import os, sys
 import numpy as np
 which = sys.argv[3] if len(sys.argv) > 3 else "rows"
 os.environ["ASX_STAMPS"] = {"rows": "1", "fwd": "fwd", "inv": "inv"}[which]
@@ -23,13 +23,7 @@ plan = asx.Plan(n, batch, 0, split=split)
 for _ in range(3):
     plan.xcorr_batch_dev(d_src.data_ptr(), d_smp.data_ptr(), batch, d_lag.data_ptr(), d_coef.data_ptr(), d_ret.data_ptr(), st)
 torch.cuda.synchronize()
-L = asx.lib()
-L.asx_plan_debug_stamps.restype = ctypes.c_long
-L.asx_plan_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-cap = 8 * 16 * 8192
-buf = np.zeros(cap, dtype=np.uint64)
-got = L.asx_plan_debug_stamps(plan._h, buf.ctypes.data, cap)
-s = buf[:got].reshape(-1, 8).astype(np.int64)
+s = plan.debug_stamps(8 * 16 * 8192).reshape(-1, 8).astype(np.int64)
 if which == "rows":
     names, last = ["setup+load", "fwd fft", "combine", "inv fft", "store"], 5
 elif which == "fwd":

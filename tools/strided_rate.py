@@ -35,7 +35,7 @@ def main():
         d_src = torch.empty(batch * 2 * n, dtype=torch.float32, device="cuda")
         d_smp = torch.empty(batch * n, dtype=torch.float32, device="cuda")
         d_lag = torch.empty(batch, dtype=torch.int64, device="cuda")
-        asx.lib().asx_synth_pairs_dev(2024, 0, batch, n, 1, d_src.data_ptr(), d_smp.data_ptr(), d_lag.data_ptr(), None)
+        asx.synth_pairs_dev(2024, 0, batch, n, 1, d_src.data_ptr(), d_smp.data_ptr(), d_lag.data_ptr())
         torch.cuda.synchronize()
         one_src = d_src[:2 * n].clone()
         one_smp = d_smp[:n].clone()

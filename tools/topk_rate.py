@@ -47,7 +47,7 @@ def main():
         n, batch = (int(v) for v in case.split("x"))
         d_src = torch.empty(batch * 2 * n, dtype=torch.float32, device="cuda")
         d_smp = torch.empty(batch * n, dtype=torch.float32, device="cuda")
-        asx.lib().asx_synth_pairs_dev(2024, 0, batch, n, 1, d_src.data_ptr(), d_smp.data_ptr(), None, None)
+        asx.synth_pairs_dev(2024, 0, batch, n, 1, d_src.data_ptr(), d_smp.data_ptr())
         torch.cuda.synchronize()
         for kind in a.kinds.split(","):
             smp = d_smp
