@@ -30,8 +30,12 @@ import numpy as np
 U = 2.0 ** -24
 # Largest z a correct device transform may show at any bin.  Measured on an MI355X: at most 0.52 on white noise, impulse
 # pairs and chirps (both layouts, every length and split in test_gpu_transform_spectrum.py), 2.24 on tracks with large DC
-# offsets (row M1 of the real-column split: the columns' Nyquist bin, a difference of two sums of the offset).  torch's
-# float32 CPU FFT reaches 0.6 on white noise.  One bin off by 1e-3 relative reaches 19 and more (test_spectrum_check.py).
+# offsets (row M1 of the real-column split: the columns' Nyquist bin, a difference of two sums of the offset).  The
+# run-time-schedule kernels (test_gpu_schedule_cover.py): at most 0.44 on white noise (split 125x75x2) and 0.25 on impulse
+# pairs (12x400x2) over the 59 forced splits of schedule_cover.CASES, 0.42 over the four longest lengths (N = 4 000 000,
+# split 3200x1250x2; 0.40 at 1 953 125, 0.41 at 2 097 152; the embedded 3 999 971 is held in the time domain, 3.1e-7 of
+# max |r|).  torch's float32 CPU FFT reaches 0.6 on white noise.  One bin off by 1e-3 relative reaches 19 and more
+# (test_spectrum_check.py).
 Z_MAX = 8.0
 
 

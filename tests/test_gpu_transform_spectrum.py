@@ -14,6 +14,7 @@ import pytest
 
 import oracle
 import spectrum_check as sc
+from device_spectrum import run_case
 from util import asx
 
 pytestmark = pytest.mark.gpu
@@ -34,43 +35,6 @@ def torch():
     import torch
     assert torch.cuda.is_available()
     return torch
-
-
-def device_r(mod, torch, x, y, split=None):
-    """the plain sum of products r[p] = sum_j x[(j + p) mod F] y[j] as the device computes it (debug_r_dev, as
-    test_raw_correlation_matches_oracle) -> (r float64[F], plan.layout, plan.split)"""
-    n = y.size
-    d_src = torch.from_numpy(x).cuda()
-    d_smp = torch.from_numpy(y).cuda()
-    d_r = torch.zeros(2 * n, dtype=torch.float32, device="cuda")
-    d_lag = torch.zeros(1, dtype=torch.int64, device="cuda")
-    d_coef = torch.zeros(1, dtype=torch.float64, device="cuda")
-    d_ret = torch.zeros(1, dtype=torch.int32, device="cuda")
-    with mod.Plan(n, 1, 0, split=split) as plan:
-        assert plan.fft_len == 2 * n
-        layout, spl = plan.layout, plan.split
-        plan.debug_r_dev(d_src.data_ptr(), d_smp.data_ptr(), d_r.data_ptr(), d_lag.data_ptr(), d_coef.data_ptr(),
-                         d_ret.data_ptr())
-        plan.sync()
-    return d_r.cpu().numpy().astype(np.float64) / (2 * n), layout, spl
-
-
-def impulse_edges(d):
-    """a = 2N - 1 and b = M2 - 1: the last sample of the last matrix row against the last column of row 0"""
-    return 2 * (d["M1"] * d["M2"]) - 1, d["M2"] - 1
-
-
-def run_case(mod, torch, n, kind, split=None, want_layout=None):
-    d = mod.planmath_describe(n, split)
-    a, b = impulse_edges(d)
-    x, y = sc.inputs(kind, n, a=a, b=b)
-    r, layout, spl = device_r(mod, torch, x, y, split)
-    if want_layout:
-        assert layout == want_layout
-    res = sc.check(sc.Reference(x, y), r, spl[0], spl[1], layout, kind)
-    print(res.summary())
-    assert res.zmax < sc.Z_MAX, res.message()
-    return layout
 
 
 # ---- per-bin parity: the real-column kernels (csrc/rlayout.hip) at the six production lengths ----------------------------
@@ -97,8 +61,7 @@ def test_packed_spectrum_bin_by_bin(mod, torch, monkeypatch, n, kind):
 def test_smooth_lengths_spectrum_bin_by_bin(mod, torch, monkeypatch, n):
     monkeypatch.delenv("ASX_LAYOUT", raising=False)
     d = mod.planmath_describe(n)
-    if d["F"] != 2 * n:
-        pytest.skip("F = %d != 2N = %d: an embedded plan's r is not X conj(Y)" % (d["F"], 2 * n))
+    assert d["F"] == 2 * n, "N = %d is smooth by construction, the planner embeds it in F = %d" % (n, d["F"])
     run_case(mod, torch, n, "W")
 
 
@@ -118,7 +81,7 @@ def test_forced_splits_spectrum_bin_by_bin(mod, torch, monkeypatch):
         except mod.AsxError:
             rejected.append(split)
             continue
-        layouts[split] = run_case(mod, torch, 144000, "W", split=split)
+        layouts[split] = run_case(mod, torch, 144000, "W", split=split).layout
     print("forced splits of 144000: %s; rejected by the planner: %s" % (layouts, rejected))
     assert set(layouts.values()) == {"real-column", "packed"}, layouts
 
