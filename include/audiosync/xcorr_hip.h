@@ -167,6 +167,22 @@ int asx_plan_pearson_modes(asx_plan *plan, uint64_t counts[3]);
 int asx_plan_set_prune(asx_plan *plan, int on);
 int asx_plan_prune_stats(asx_plan *plan, uint64_t *tiles_transformed, uint64_t *tiles_total);
 
+/* Partial storing of Q in the pruned inverse pass (the two longest lengths, N = 960 000 and 1 440 000; $ASX_QSTORE = the initial
+ * mode).  The pruned pass reads about two of a pair's column tiles of Q, so the row pass of a group need not store the others: it
+ * runs a few rows first, which store everything; from their tile energies each pair's tile 0 and up to three outstanding tiles are
+ * predicted -- or none, for unrelated tracks, and the pair stores everything -- and the other rows store only those.  The exact
+ * bounds then decide, as ever, which tiles the result needs; a pair that needs a tile that was not stored is run again through the
+ * full-store kernels when the call reads its overflow list.  Lag, ret, coefficient and every counter are what mode 0 returns, bit
+ * for bit.  Exact mode only (asx_plan_set_exact): the asynchronous mode never reads the list and keeps the full-store row pass.
+ *   mode 0  off
+ *   mode 1  auto, the default: groups of at least eight generations of row blocks (14 pairs at N = 1 440 000 on 256 compute units);
+ *           smaller groups and single pairs launch exactly what mode 0 launches
+ *   mode 2  always (any group size, eight predictor rows): for tests
+ * asx_plan_qstore_stats: pairs given a list, pairs that stored everything, pairs run again, tiles stored, over the plan's life
+ * (synchronises the DEVICE, as asx_plan_pearson_modes does). */
+int asx_plan_set_qstore(asx_plan *plan, int mode);
+int asx_plan_qstore_stats(asx_plan *plan, uint64_t out[4]);
+
 /* Introspection (used by tests, bench and DESIGN.md's numbers). */
 size_t asx_plan_sample_len(const asx_plan *plan);
 size_t asx_plan_fft_len(const asx_plan *plan);        /* F, real transform length */

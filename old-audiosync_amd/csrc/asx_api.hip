@@ -176,6 +176,11 @@ struct asx_plan {
     bool prunable = false;             // AsxKernelChoice::prunable: the lanes have their AsxPrune workspaces
     bool prune = false;                // asx_plan_set_prune: in-scope groups skip the inverse column tiles a bound rules out
     unsigned long long *prune_stats = nullptr; // [2] tiles transformed, tiles in all, by the pruned groups; cumulative
+    // asx_plan_set_qstore: 0 off, 1 auto, 2 always -- which pruned groups of an exact call store only the predicted tiles of Q
+    // (rlayout.hip: asx_qstore_rows, k_rows_rm, k_q_predict; the exact check in k_prune_select, the redo in resolve_overflows)
+    int qstore = 1;
+    unsigned long long *qstore_stats = nullptr; // [4] pairs given a list, pairs given all, -, tiles stored; cumulative
+    uint64_t qstore_redone = 0;                 // pairs whose stored set fell short and that ran again
     // "measure" plans only: at the first device-resident batch the forward column kernel is timed against the caller's buffers
     // on TWO allocations of its output workspaces and the faster set is kept (tune_placement)
     bool tune_placement = false, placement_done = false;
@@ -323,8 +328,15 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
             }
             if (dev_alloc(m, &ln.prune.eng, g * ((size_t)h.M1 + 1) * (size_t)h.ntiles) || dev_alloc(m, &ln.prune.ub, g * (size_t)h.ntiles) ||
                 dev_alloc(m, &ln.prune.best, g) || dev_alloc(m, &ln.prune.skip, g * (size_t)h.ntiles) ||
-                dev_alloc(m, &ln.prune.part, g * 1024) || dev_alloc(m, &ln.prune.ticket, g))
+                dev_alloc(m, &ln.prune.part, g * 1024) || dev_alloc(m, &ln.prune.ticket, g) || dev_alloc(m, &ln.prune.list, g) ||
+                dev_alloc(m, &ln.prune.redo, g))
                 return -1;
+            if (!p->qstore_stats) {
+                if (dev_alloc(m, &p->qstore_stats, 4)) return -1;
+                HIP_TRY(hipMemset(p->qstore_stats, 0, 4 * sizeof(unsigned long long)));
+            }
+            HIP_TRY(hipMemset(ln.prune.redo, 0, g));
+            ln.prune.qstats = p->qstore_stats;
             // part: [slices][tiles rounded up to 32] of 1024 doubles per pair whatever the length; every slot a launch reads it has
             // written itself, the zeroing is for a defined first state only.  The tickets must be zero: k_tile_bounds counts on it
             // and leaves them zero behind every launch
@@ -359,6 +371,7 @@ static int plan_init(asx_plan *p, size_t N, size_t max_batch, const char *split)
     if (const char *e = getenv("ASX_PEARSON")) p->spectral = p->spectral && strcmp(e, "direct") != 0; // A/B of the two forms
     p->prune = p->prunable;
     if (const char *e = getenv("ASX_PRUNE")) p->prune = p->prune && atoi(e) != 0; // A/B of the pruned inverse pass
+    if (const char *e = getenv("ASX_QSTORE")) p->qstore = std::min(2, std::max(0, atoi(e))); // A/B of partial storing
     if (const char *e = getenv("ASX_EXACT")) p->exact = atoi(e) != 0; // initial value of asx_plan_set_exact (A/B of its cost)
     p->win_lo = -(int64_t)p->host.N; // the full lag window
     p->win_hi = (int64_t)p->host.N - 1;
@@ -594,6 +607,29 @@ extern "C" int asx_plan_prune_stats(asx_plan *p, uint64_t *tiles_transformed, ui
     HIP_TRY(hipMemcpy(v, p->prune_stats, sizeof v, hipMemcpyDeviceToHost));
     *tiles_transformed = v[0];
     *tiles_total = v[1];
+    return 0;
+}
+
+extern "C" int asx_plan_set_qstore(asx_plan *p, int mode)
+{
+    if (!p) return fail("asx_plan_set_qstore: null argument");
+    if (mode < 0 || mode > 2) return fail("asx_plan_set_qstore: mode %d (0 off, 1 auto, 2 always)", mode);
+    std::lock_guard<std::mutex> guard(p->lock);
+    p->qstore = mode;
+    return 0;
+}
+
+extern "C" int asx_plan_qstore_stats(asx_plan *p, uint64_t out[4])
+{
+    if (!p || !out) return fail("asx_plan_qstore_stats: null argument");
+    PlanCall c(p);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!p->qstore_stats) return 0;
+    HIP_TRY(hipDeviceSynchronize()); // the whole device, as asx_plan_pearson_modes does
+    unsigned long long v[4];
+    HIP_TRY(hipMemcpy(v, p->qstore_stats, sizeof v, hipMemcpyDeviceToHost));
+    out[0] = v[0]; out[1] = v[1]; out[2] = p->qstore_redone; out[3] = v[3];
     return 0;
 }
 
@@ -878,6 +914,7 @@ struct GroupOpts {
     // per voter (AsxBand::votes).  The entry points turn the full band into ASX_W_PHAT (band_weight).
     AsxWeight weight = ASX_W_NONE;
     AsxBand fband{};
+    bool qstore = true;          // partial storing of Q allowed (false: the second run of a pair whose stored set fell short)
 };
 
 // One group: g <= plan->group pairs, the first g of x, results to the first g of y.
@@ -908,8 +945,17 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // pool group's in the bank, found through its resolved records -- with the norm partials and band sums always in the lane's places.
     const AsxPoolPair *pl = x.pool ? W.pool : nullptr;
     const AsxSpectra &from = pl ? p->bank.c : p->bslot;
+    // Partial storing of Q (rlayout.hip: k_rows_rm): a pruned group of a call that reads the overflow list behind it (o.listed, the
+    // exact mode -- the list is how a pair whose stored set fell short gets its second run, so the asynchronous mode keeps k_rows_re),
+    // whose row schedule has the kernel and whose size the plan's switch lets in (asx_qstore_rows).  The kernels get a copy of the
+    // lane's AsxPrune that says so: list null = Q is whole.
+    AsxPrune U = W.prune;
+    U.q_rows = (prune && o.listed && o.qstore && fin.over_list) ? asx_qstore_rows(P, (int)g, p->qstore) : 0;
+    U.q_row_a = P.M1 / 3; // away from the real rows 0 and M1
+    U.pair_base = o.pair_base;
+    if (!U.q_rows) { U.list = nullptr; U.redo = nullptr; }
     const AsxSpectra C{ (pl || (x.bc & 1)) ? from.cx : W.zxa, (pl || (x.bc & 2)) ? from.cy : W.zya, pk.nrm_part, tk.band, x.bc, pl,
-                        prune ? &W.prune : nullptr, o.weight, o.fband };
+                        prune ? &U : nullptr, o.weight, o.fband };
     if (mark(0)) return -1;
     if (pl) {
         // pool calls: the bank holds every track's forward column pass; this group only resolves its pairs into slots and offsets
@@ -976,6 +1022,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
         return 0;
     };
     if (pass(call, true)) return -1;
+    if (U.q_rows && spectral) asx_launch_qstore_takeback(U, W.spec, (int)g, s);
     // a pair whose row is not a window: (0, NaN, -2), the others untouched (top-k: k_topk_step writes it for every entry)
     // (a PHAT group: k_phat_finalize has given such a pair a NaN peak)
     if (call.kind == AsxSearch::ROWS && K == 1) asx_launch_invalid_rows(call.rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
@@ -1051,45 +1098,63 @@ static int second_look(asx_plan *p, const Pairs<TIn> &xi, const Results &yi, hip
 template <typename TIn>
 static int resolve_overflows(asx_plan *p, const Pairs<TIn> &x, const Results &y, hipStream_t s, const Topk &topk = {})
 {
-    HIP_TRY(hipStreamSynchronize(s));
-    if (p->lanes[0].pk.cap >= 2 * p->host.N) return 0; // the ordinary list already holds every lag
-    const uint32_t n = *p->h_over_n;
-    if (n == 0) return 0;
-    if (n > p->over_cap) {
-        // cannot happen (a window is at most over_cap pairs); if it ever does, the list must not stay poisoned
-        (void)hipMemsetAsync(p->over_n, 0, sizeof(uint32_t), s);
-        (void)hipStreamSynchronize(s);
-        *p->h_over_n = 0;
-        return fail("internal: %u overflowed pairs in a window of %zu", n, p->over_cap);
-    }
-    p->h_over.resize(n);
-    HIP_TRY(hipMemcpyAsync(p->h_over.data(), p->over_list, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemsetAsync(p->over_n, 0, sizeof(uint32_t), s));
-    // pool calls: the listed pairs' rows {a, b} (a small copy of those rows only), so that each pair's second look runs on explicit
-    // pointers -- as the strided call's does
-    std::vector<int32_t> ab;
-    if (x.pool) {
-        ab.resize(2 * (size_t)n);
-        for (uint32_t k = 0; k < n; k++) {
-            const size_t pi = x.first + p->h_over[k];
-            if (x.pool->rows)
-                HIP_TRY(hipMemcpyAsync(&ab[2 * k], x.pool->rows + 2 * pi, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            else { ab[2 * k] = (int32_t)(pi / x.pool->nsmp); ab[2 * k + 1] = (int32_t)(pi % x.pool->nsmp); }
+    // An entry with ASX_QSTORE_REDO is a pair whose partially stored Q fell short (k_prune_select): it runs again as a group of
+    // one with partial storing off -- k_rows_re and the pruned pass over the whole of Q, in slot 0 of lane 0, into its own results,
+    // listed as usual.  Such a run may overflow its near-tie list like any other: when one ran, the list is looked at once more
+    // (that second round can hold no such entry).  Nothing here costs a call without entries anything new.
+    int total = 0;
+    for (int round = 0; round < 2; round++) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (p->lanes[0].pk.cap >= 2 * p->host.N) return total; // the ordinary list already holds every lag
+        const uint32_t n = *p->h_over_n;
+        if (n == 0) return total;
+        if (n > p->over_cap) {
+            // cannot happen (a window is at most over_cap pairs); if it ever does, the list must not stay poisoned
+            (void)hipMemsetAsync(p->over_n, 0, sizeof(uint32_t), s);
+            (void)hipStreamSynchronize(s);
+            *p->h_over_n = 0;
+            return fail("internal: %u overflowed pairs in a window of %zu", n, p->over_cap);
         }
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    *p->h_over_n = 0;
-    for (uint32_t k = 0; k < n; k++) {
-        const uint32_t i = p->h_over[k];
-        Pairs<TIn> xi = x.at(i);
+        p->h_over.resize(n);
+        HIP_TRY(hipMemcpyAsync(p->h_over.data(), p->over_list, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemsetAsync(p->over_n, 0, sizeof(uint32_t), s));
+        // pool calls: the listed pairs' rows {a, b} (a small copy of those rows only), so that each pair's second look runs on explicit
+        // pointers -- as the strided call's does
+        std::vector<int32_t> ab;
         if (x.pool) {
-            const int64_t a = ab[2 * k], b = ab[2 * k + 1];
-            if (a < 0 || (size_t)a >= x.pool->nsrc || b < 0 || (size_t)b >= x.pool->nsmp) continue; // (k_rows_rl never lets one overflow)
-            xi = xi.pool_pair((size_t)a, (size_t)b, p->host.N);
+            ab.resize(2 * (size_t)n);
+            for (uint32_t k = 0; k < n; k++) {
+                const size_t pi = x.first + (p->h_over[k] & ~ASX_QSTORE_REDO);
+                if (x.pool->rows)
+                    HIP_TRY(hipMemcpyAsync(&ab[2 * k], x.pool->rows + 2 * pi, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                else { ab[2 * k] = (int32_t)(pi / x.pool->nsmp); ab[2 * k + 1] = (int32_t)(pi % x.pool->nsmp); }
+            }
         }
-        if (second_look(p, xi, y.at(i), s, topk)) return -1;
+        HIP_TRY(hipStreamSynchronize(s));
+        *p->h_over_n = 0;
+        const std::vector<uint32_t> list = p->h_over; // (a second run appends to the plan's list: keep this round's)
+        uint32_t redone = 0;
+        for (uint32_t k = 0; k < n; k++) {
+            const uint32_t i = list[k] & ~ASX_QSTORE_REDO;
+            Pairs<TIn> xi = x.at(i);
+            if (list[k] & ASX_QSTORE_REDO) {
+                if (run_group(p, xi, 1, y.at(i), s, { .prof_group = GroupOpts::no_marks, .pair_base = i, .topk = topk, .qstore = false }))
+                    return -1;
+                p->qstore_redone++;
+                redone++;
+                continue;
+            }
+            if (x.pool) {
+                const int64_t a = ab[2 * k], b = ab[2 * k + 1];
+                if (a < 0 || (size_t)a >= x.pool->nsrc || b < 0 || (size_t)b >= x.pool->nsmp) continue; // (k_rows_rl never lets one overflow)
+                xi = xi.pool_pair((size_t)a, (size_t)b, p->host.N);
+            }
+            if (second_look(p, xi, y.at(i), s, topk)) return -1;
+        }
+        total += (int)n;
+        if (!redone) return total;
     }
-    return (int)n;
+    return total;
 }
 
 // Copies the results of the g pairs of one group of a host-side entry point (device d, host h) back to the host.  The copies go

@@ -52,6 +52,32 @@
 #define ASX_PRUNE_DELTA 6.103515625e-5f
 #define ASX_PRUNE_FLOOR_PER_TERM 3.944304526105059e-31
 #define ASX_PRUNE_T 16                      // the tile width the row pass sums energies for (every real-column schedule's)
+// Partial storing of Q (rlayout.hip: k_rows_rm, k_q_predict).  A pair's stored column tiles travel as one 64-bit
+// word: four 16-bit tile indices, tile 0 first, 0xFFFF = no tile; ASX_Q_ALL = every tile (the whole of Q, as k_rows_re stores it).
+// ASX_QSTORE_C: a tile is predicted when its energy over the predictor rows exceeds this many medians of the pair's tiles.  Derived on
+// the CPU with tests/model_fourstep.py (tests/test_qstore_model.py restates it): over eight predictor rows the LARGEST tile of
+// unrelated Gaussian tracks reaches 1.37 medians at most over 300 pairs of 30 tiles (99 %: 1.34; the sum of 8 x 16 values of |Q|^2 has
+// a relative deviation of about 0.09, and more rows or fewer tiles only narrow it: 1.17 over 32 rows), while the peak's tile of the
+// bench generator's pairs stands at 3.8 ... 9.3 medians at noise shift 1 and 2.2 ... 4.3 at noise shift 0 with 30 tiles, every other
+// tile under 1.3; with the 150 tiles of the two-half form a planted delay's tile stands at about 36 medians (the peak's energy is in
+// one tile of five times as many).  1.75 leaves a quarter above the noise and a quarter below the weakest generator pair.  A wrong
+// prediction costs time, never a result: k_prune_select checks the stored set against the exact bounds and sends the pair through
+// the full-store path again.
+#define ASX_Q_ALL 0xFFFFFFFFFFFFFFFFull
+#define ASX_QSTORE_C 1.75
+#define ASX_QSTORE_REDO 0x80000000u         // an entry of the overflow list with this bit: run the pair again with partial storing off
+__host__ __device__ inline bool asx_q_stored(unsigned long long w, int tile)
+{
+    const unsigned t = (unsigned)tile;
+    return w == ASX_Q_ALL || (unsigned)(w & 0xFFFFu) == t || (unsigned)((w >> 16) & 0xFFFFu) == t ||
+           (unsigned)((w >> 32) & 0xFFFFu) == t || (unsigned)((w >> 48) & 0xFFFFu) == t;
+}
+// The rows of one k_rows_rm launch: `count` rows of every pair, block r of a pair taking row r, or r + hop from r = row_a on -- one
+// compare and one add, so that one kernel serves the predictor rows (row_a = 0, hop = the first of them) and the rest (row_a = the
+// first predictor row, hop = their number).
+struct AsxRowRun {
+    int row_a = 0, count = 0, hop = 0;
+};
 #define ASX_CAND_MAX 16384                  // upper limit of a plan's per-pair candidate capacity
 #define ASX_CAND_MIN 2048
 #define ASX_DOT_BLOCKS 128                  // blocks per pair that walk the pair's candidate list
@@ -364,6 +390,12 @@ struct AsxPrune {
     unsigned *ticket;      // [pairs] slices of the pair that have left their sums; zero between launches
     unsigned char *skip;   // [pairs][ntiles] 1 = the second launch leaves the tile out
     unsigned long long *stats; // [2] tiles transformed, tiles in all: cumulative over the plan's life (asx_plan_prune_stats)
+    // Partial storing of Q.  list null (a group without it: run_group hands the kernels a copy that says so): Q is whole.
+    unsigned long long *list;  // [pairs] the tiles of Q launch B stored (k_q_predict), read by launch B and by the pruned pass of the SAME group
+    unsigned char *redo;       // [pairs] 1 = k_prune_select found the stored set short: the pair's results are discarded and it runs again
+    unsigned long long *qstats; // [4] pairs given a list, pairs given ASX_Q_ALL, pairs redone (kept by the host), tiles stored; cumulative
+    int q_rows, q_row_a;       // the predictor rows: q_rows rows from q_row_a (set per group)
+    uint32_t pair_base;        // the group's first pair in the caller's overflow window (set per group)
 };
 
 // Selections: the device-side partners of AsxSearch, the last argument of a kernel template <..., Sel>.  Every method is
@@ -397,6 +429,7 @@ struct AsxSelTopkSeed {
 template <bool FIRST> struct AsxSelPrune {
     const int *__restrict__ best;
     const unsigned char *__restrict__ skip;
+    const unsigned long long *__restrict__ list; // partial storing: the pair's stored tiles (null: Q is whole)
     static constexpr bool masks = false;
     __device__ __forceinline__ AsxWin window_of(size_t, uint32_t) const { return AsxWin{}; }
 };
@@ -408,8 +441,10 @@ template <class Sel> __device__ __forceinline__ int asx_sel_tile(const Sel &, in
 template <bool FIRST> __device__ __forceinline__ bool asx_sel_takes(const AsxSelPrune<FIRST> &q, int grid_tile, int M2, int T)
 {
     if constexpr (FIRST) {
+        // (the largest-bound tile may not be stored: its block leaves at once, k_prune_select then sends the pair round again)
         const int bt = q.best[blockIdx.x];
-        return blockIdx.y == 0 || bt != 0;
+        if (blockIdx.y == 0) return !q.list || asx_q_stored(q.list[blockIdx.x], bt);
+        return bt != 0;
     } else {
         return grid_tile * T < M2 && !q.skip[(size_t)blockIdx.x * (size_t)(M2 / T) + grid_tile];
     }
@@ -511,6 +546,10 @@ void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, 
 void asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, size_t first,
                            int count, const AsxSpectra &dst, bool temporal, hipStream_t s);
 void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s);
+// partial storing: the predictor rows a pruned group of npairs pairs gets under `mode` (asx_plan_set_qstore), 0 = the group keeps k_rows_re
+int asx_qstore_rows(const AsxDev &P, int npairs, int mode);
+// behind the Pearson kernels of a group with partial storing: the discarded pass of every pair U.redo marks leaves the counters
+void asx_launch_qstore_takeback(const AsxPrune &U, const AsxSpecWs &S, int npairs, hipStream_t s);
 void asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                            const AsxSearch &search, const AsxPrune *U);
 // the tail of a PHAT group (rlayout.hip: k_phat_finalize), behind the inverse column pass and in front of the direct Pearson launch:

@@ -208,6 +208,11 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 //   hold a tile and add it in four DPP steps inside their row, the balanced tree ((0+1)+(2+3))+... that tree_sum<16> is; one lane
 //   of the sixteen stores.  No atomics: the same Q gives the same bits.  Nothing is loaded for it.  (Lanes are four dwords apart:
 //   a four-way bank conflict on these stores and loads, a few hundred LDS cycles per block.)
+//   MSK (k_rows_rm, partial storing of Q; with ENG, the two-half form only): the launch holds some of a pair's rows (AsxRowRun), and a
+//   pair may come with a list of up to four column tiles (asx_internal.h: ASX_Q_ALL), the only ones the pruned pass will read.  A block
+//   of such a pair keeps its Q values in LDS -- {re, im} in front of the energy in slot c, written by the thread that alone has just
+//   read that slot -- and behind the fifth barrier one wave copies the listed tiles to Q, sixteen lanes a tile.  Without a list the
+//   store phase is ENG's.  The expressions that form Q and |Q|^2 are the same in both: the stored bits are k_rows_re's.
 //   PHAT (k_rows_rp, asx_xcorr_phat_f32_dev): the phase transform.  Every bin of the product X conj(Y) is divided by its magnitude in
 //   the registers where it is formed, between the product and the first inverse butterfly (phat_unit below), so that the inverse
 //   passes deliver r_phat, whose every frequency has one vote.  Nothing of the float32 error bound holds for a whitened spectrum:
@@ -241,12 +246,14 @@ __device__ __forceinline__ Cx1 phat_unit(Cx1 q)
 // The body takes P and W by value: that call boundary loads their fields at the top of the kernel.  Written inside the __global__
 // itself the instruction stream changes, and with it the float32 rounding of r (11 of the headline's 124 coefficients moved by
 // about 1e-7).
-template <class S, int NT, bool TWO, int BC, bool ENG = false, bool PHAT = false, bool BAND = false>
+template <class S, int NT, bool TWO, int BC, bool ENG = false, bool PHAT = false, bool BAND = false, bool MSK = false>
 __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restrict__ cx, const float2 *__restrict__ cy,
                                             float2 *__restrict__ qo, int nrows, size_t pitch_x, size_t pitch_y, size_t pitch_q,
                                             AsxPeakWs W, const AsxPoolPair *__restrict__ L = nullptr, float *__restrict__ eng = nullptr,
-                                            const AsxBand band = {})
+                                            const AsxBand band = {}, const AsxRowRun run = {},
+                                            const unsigned long long *__restrict__ list = nullptr)
 {
+    static_assert(!MSK || (ENG && TWO), "partial storing: the two-half form, with the tile energies");
     static_assert(S::nstages == 3, "three-stage row schedules only");
     static_assert(!BAND || PHAT, "a band is a band of the phase transform");
     constexpr int NS = S::n;                 // length of a (sub-)row transform
@@ -273,8 +280,14 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
     __shared__ float2 tw_step[WSTEPS]; // (1/2) w_F^(k1 * 2*NTB*i): the four-step twiddle from load step to load step
     __shared__ float2 leg[R0];         // w_F^(k1 * Q0*t): ... and from leg to leg of the last inverse stage
 
-    const int pair = task / nrows;
-    const uint32_t k1 = (uint32_t)(task - pair * nrows);
+    // MSK: the launch holds run.count rows of every pair, k1 = r, or r + run.hop from r = run.row_a on (AsxRowRun)
+    const int pair = MSK ? task / run.count : task / nrows;
+    uint32_t k1 = (uint32_t)(task - pair * (MSK ? run.count : nrows));
+    if constexpr (MSK) k1 += (int)k1 >= run.row_a ? (uint32_t)run.hop : 0u;
+    // ... and the pair's stored tiles (ASX_Q_ALL, or no list at all: the whole row), asked for with the other early look-ups; block-uniform
+    unsigned long long wl = ASX_Q_ALL;
+    if constexpr (MSK) { if (list) wl = list[pair]; }
+    [[maybe_unused]] const bool part = MSK && wl != ASX_Q_ALL;
     const size_t row = (size_t)RWS_PAIR(pair) * pitch_q + (size_t)k1 * M2;
     size_t rowx, rowy;
     if constexpr ((BC & 4) != 0) {
@@ -520,17 +533,33 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
             const float2 w2 = (ASX_ROWS_EARLY & 2) ? tail_w2 : P.tw2[j];                                  // w_M2^j
             const float2 fa = (ASX_ROWS_EARLY & 2) ? cmul(tail_lo, tail_hi) : tw_F(P, k1 * (uint32_t)j);  // w_F^(k1 j)
             const float2 fbh = cmul(fa, wh);                  // w_F^(k1 (j + n))
-            static_for<0, R0>([&](auto T) __attribute__((always_inline)) {
-                constexpr int t = decltype(T)::value;
-                const Cx1 A = Cx1{ v[t].re.x, v[t].im.x };
-                const Cx1 Bw = mul_root<2 * R0, t, true>(mulwc(Cx1{ v[t].re.y, v[t].im.y }, w2)); // conj(w_M2^(j + Q0 t)) B
-                const float2 lg = leg[t];
-                const Cx1 y = mulwc(A + Bw, t == 0 ? fa : cmul(fa, lg));
-                const Cx1 z = mulwc(A - Bw, t == 0 ? fbh : cmul(fbh, lg));
-                st_f2(go + j + t * Q0, make_float2(y.re, y.im), ASX_RNT & 8);
-                st_f2(go + NS + j + t * Q0, make_float2(z.re, z.im), ASX_RNT & 8);
-                if constexpr (ENG) { eng_put(ej, t * Q0, y); eng_put(ej, NS + t * Q0, z); }
-            });
+            // PART (MSK, a pair with a list): Q stays in LDS, {re, im} in front of the energy in slot c -- the slots j + Q0 t and
+            // NS + j + Q0 t are exactly the ones this thread alone has just read, so no barrier is needed -- and the listed tiles leave
+            // behind the fifth barrier (below).  Otherwise Q leaves from registers, as ever.
+            auto leave = [&](auto PART) __attribute__((always_inline)) {
+                static_for<0, R0>([&](auto T) __attribute__((always_inline)) {
+                    constexpr int t = decltype(T)::value;
+                    const Cx1 A = Cx1{ v[t].re.x, v[t].im.x };
+                    const Cx1 Bw = mul_root<2 * R0, t, true>(mulwc(Cx1{ v[t].re.y, v[t].im.y }, w2)); // conj(w_M2^(j + Q0 t)) B
+                    const float2 lg = leg[t];
+                    const Cx1 y = mulwc(A + Bw, t == 0 ? fa : cmul(fa, lg));
+                    const Cx1 z = mulwc(A - Bw, t == 0 ? fbh : cmul(fbh, lg));
+                    if constexpr (decltype(PART)::value) {
+                        ej[4 * (t * Q0) - 2] = y.re; ej[4 * (t * Q0) - 1] = y.im;
+                        ej[4 * (NS + t * Q0) - 2] = z.re; ej[4 * (NS + t * Q0) - 1] = z.im;
+                    } else {
+                        st_f2(go + j + t * Q0, make_float2(y.re, y.im), ASX_RNT & 8);
+                        st_f2(go + NS + j + t * Q0, make_float2(z.re, z.im), ASX_RNT & 8);
+                    }
+                    if constexpr (ENG) { eng_put(ej, t * Q0, y); eng_put(ej, NS + t * Q0, z); }
+                });
+            };
+            if constexpr (MSK) {
+                if (part) leave(std::true_type{});
+                else leave(std::false_type{});
+            } else {
+                leave(std::false_type{});
+            }
         }
     }
     if constexpr (ENG) {
@@ -550,6 +579,18 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
                 constexpr int i = decltype(I)::value;
                 if ((i + 1) * NTB <= M2 || tid + i * NTB < M2) eo[(NTB / 16) * i] = v[I];
             });
+        if constexpr (MSK) {
+            // the listed tiles from LDS to Q: one wave, sixteen lanes a tile, 8 bytes per lane, 128 bytes per tile row (an unused
+            // entry of the list names no tile)
+            if (part && tid < 64) {
+                const unsigned t = (unsigned)(wl >> (16 * (tid >> 4))) & 0xFFFFu;
+                if (t < (unsigned)NTILE) {
+                    const int c = (int)t * ASX_PRUNE_T + (tid & 15);
+                    const float *sl = reinterpret_cast<const float *>(asx_lds_r) + 4 * c;
+                    st_f2(go + c, make_float2(sl[0], sl[1]), ASX_RNT & 8);
+                }
+            }
+        }
     }
     RSTAMP(0, task, 4);
 #ifdef ASX_STAMPS
@@ -574,6 +615,20 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_re(
                                                                                  float *__restrict__ eng)
 {
     rows_r_body<S, NT, TWO, 0, true>(P, cx, cy, qo, nrows, pair_pitch, pair_pitch, pair_pitch, W, nullptr, eng);
+}
+
+// The row pass with partial storing (asx_launch_rows_r, a pruned group whose AsxPrune carries a list): k_rows_re on the rows of `run`,
+// which stores of a pair with a list only the listed column tiles of Q (MSK above) -- list null, or a pair's entry ASX_Q_ALL: every
+// column, from registers, as k_rows_re does.  The energies are k_rows_re's either way.  Two-half form only.
+template <class S, int NT, bool TWO>
+__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rm(const RArgs P, const float2 *__restrict__ cx,
+                                                                                 const float2 *__restrict__ cy, float2 *__restrict__ qo,
+                                                                                 int nrows, size_t pair_pitch, AsxPeakWs W,
+                                                                                 float *__restrict__ eng, const AsxRowRun run,
+                                                                                 const unsigned long long *__restrict__ list)
+{
+    rows_r_body<S, NT, TWO, 0, true, false, false, true>(P, cx, cy, qo, nrows, pair_pitch, pair_pitch, pair_pitch, W, nullptr, eng, {}, run,
+                                                          list);
 }
 
 // The row pass of a PHAT group (asx_launch_rows_r, AsxSpectra::weight == ASX_W_PHAT): k_rows_r<S, NT, TWO, BC> with the whitened product
@@ -1277,27 +1332,108 @@ __global__ __launch_bounds__(1024) void k_tile_bounds(const float *__restrict__ 
 // (a silent pair: the blocks left at the zero bound) and a NaN bound make the comparison false: nothing but the two is skipped.
 __global__ __launch_bounds__(256) void k_prune_select(const float *__restrict__ ub, const int *__restrict__ best,
                                                        unsigned char *__restrict__ skip, AsxPeakWs W, int ntiles,
-                                                       unsigned long long *__restrict__ stats)
+                                                       unsigned long long *__restrict__ stats, const unsigned long long *__restrict__ list,
+                                                       unsigned char *__restrict__ redo, uint32_t pair_base)
 {
-    __shared__ unsigned kept;
+    __shared__ unsigned kept, short_of;
     const size_t pair = blockIdx.x;
-    if (threadIdx.x == 0) kept = 0;
+    if (threadIdx.x == 0) { kept = 0; short_of = 0; }
     __syncthreads();
     const asx_peak_t pm = W.pairmax[pair];
     const float thr = near_max_threshold(peak_key(pm), W.bound2[pair]); // NaN when pm == 0
     const int bt = best[pair];
-    unsigned n = 0;
+    const unsigned long long w = list ? list[pair] : ASX_Q_ALL;
+    unsigned n = 0, miss = asx_q_stored(w, bt) ? 0u : 1u;
     for (int t = threadIdx.x; t < ntiles; t += 256) {
         const bool sk = t == bt || t == 0 || (pm != 0 && ub[pair * ntiles + t] < thr);
         skip[pair * ntiles + t] = sk ? 1 : 0;
         n += sk ? 0u : 1u;
+        miss |= (!sk && !asx_q_stored(w, t)) ? 1u : 0u;
     }
     if (n) atomicAdd(&kept, n);
+    if (miss) atomicOr(&short_of, 1u);
     __syncthreads();
+    // Partial storing: the exact check of the prediction.  The pair is complete when the largest-bound tile and every tile left to
+    // the second launch are stored (tile 0 always is).  Otherwise nothing of this pass may stand: every tile is skipped, and the
+    // running maximum and the candidate count are emptied, so that the tail treats the pair as a silent one -- it can neither list
+    // nor mark it -- and the pair goes on the overflow list with ASX_QSTORE_REDO, counted for the host as k_finalize counts an
+    // overflowed pair (but not in W.overflows: the pair has not overflowed).  redo is written for every pair of such a group.
+    const bool again = short_of != 0; // block-uniform
+    if (again)
+        for (int t = threadIdx.x; t < ntiles; t += 256) skip[pair * ntiles + t] = 1;
     if (threadIdx.x == 0) {
-        atomicAdd(&stats[0], (unsigned long long)(kept + (bt == 0 ? 1u : 2u)));
+        const unsigned first = 1u + ((bt != 0 && asx_q_stored(w, bt)) ? 1u : 0u);
+        atomicAdd(&stats[0], (unsigned long long)((again ? 0u : kept) + first));
         atomicAdd(&stats[1], (unsigned long long)ntiles);
+        if (list) redo[pair] = again ? 1 : 0;
+        if (again) {
+            W.pairmax[pair] = 0;
+            W.cand_n[pair] = 0;
+            if (W.over_list) {
+                const uint32_t slot = atomicAdd(W.over_n, 1u);
+                if (slot < W.over_cap) W.over_list[slot] = (pair_base + (uint32_t)pair) | ASX_QSTORE_REDO;
+                if (W.over_host) (void)__hip_atomic_fetch_add(W.over_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
     }
+}
+
+// Partial storing, the prediction.  grid (npairs), 256 threads, a tile per thread (ntiles <= 256), behind launch A of the row pass:
+// p[t] = the float64 sum of eng[k1][t] over the predictor rows in increasing k1; list[pair] = tile 0 plus the up-to-three tiles
+// t != 0 of largest p[t] that exceed c medians of p (ties: the smaller tile; the median: the element of rank ntiles / 2), or
+// ASX_Q_ALL when no tile, tile 0 included, does -- unrelated tracks, where every tile will be needed.  A NaN makes every comparison false: ASX_Q_ALL.
+// Only the time depends on what this writes (k_prune_select).
+__global__ __launch_bounds__(256) void k_q_predict(const float *__restrict__ eng, int nrows, int ntiles, int row_a, int r0, double c,
+                                                    unsigned long long *__restrict__ list, unsigned long long *__restrict__ qstats)
+{
+    __shared__ double p[256];
+    __shared__ double med;
+    __shared__ unsigned pick[3];
+    const size_t pair = blockIdx.x;
+    const int t = threadIdx.x;
+    double mine = 0.0;
+    if (t < ntiles) {
+        const float *e = eng + (pair * (size_t)nrows + (size_t)row_a) * ntiles + t;
+        for (int i = 0; i < r0; i++) mine += (double)e[(size_t)i * ntiles];
+        p[t] = mine;
+    }
+    if (t == 0) med = (double)NAN;
+    if (t < 3) pick[t] = 0xFFFFu;
+    __syncthreads();
+    int below = 0, above = 0; // tiles in front of this one in ascending order; tiles t' != 0 in front of it in descending order
+    if (t < ntiles)
+        for (int o = 0; o < ntiles; o++) {
+            const double v = p[o];
+            below += (v < mine || (v == mine && o < t)) ? 1 : 0;
+            above += (o != 0 && (v > mine || (v == mine && o < t))) ? 1 : 0;
+        }
+    if (t < ntiles && below == ntiles / 2) med = mine;
+    __syncthreads();
+    if (t > 0 && t < ntiles && above < 3 && mine > c * med) pick[above] = (unsigned)t;
+    __syncthreads();
+    if (t != 0) return;
+    // (the picks are the largest: a pick at place 1 or 2 implies the places in front of it)
+    // (tile 0 standing out alone -- a peak at a lag that is a small multiple of M2 away from 0 -- is a list of tile 0)
+    unsigned long long w = ASX_Q_ALL;
+    unsigned stored = (unsigned)ntiles;
+    if (pick[0] != 0xFFFFu || mine > c * med) {
+        w = 0ull | ((unsigned long long)pick[0] << 16) | ((unsigned long long)pick[1] << 32) | ((unsigned long long)pick[2] << 48);
+        stored = 1u + (pick[0] != 0xFFFFu ? 1u : 0u) + (pick[1] != 0xFFFFu ? 1u : 0u) + (pick[2] != 0xFFFFu ? 1u : 0u);
+    }
+    list[pair] = w;
+    atomicAdd(&qstats[w == ASX_Q_ALL ? 1 : 0], 1ull);
+    atomicAdd(&qstats[3], (unsigned long long)stored);
+}
+
+// Partial storing, behind the Pearson kernels of the group: the spectral form has counted the mode of every pair's pass
+// (k_pearson_final_spec: hdr[3]); a discarded pass (redo) is taken back, the pair's second run counts its own.
+__global__ __launch_bounds__(256) void k_qstore_takeback(const unsigned char *__restrict__ redo, const double *__restrict__ hdr,
+                                                          unsigned long long *__restrict__ mode_count, int npairs)
+{
+    const int pair = blockIdx.x * 256 + threadIdx.x;
+    if (pair >= npairs || !redo[pair]) return;
+    const int mode = (int)hdr[(size_t)pair * ASX_SPEC_HDR + 3];
+    if (mode >= 0 && mode < ASX_PM_NMODES) atomicAdd(&mode_count[mode], ~0ull); // minus one
 }
 
 // ---------------------------------------------------------------------------
@@ -1365,6 +1501,23 @@ void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const As
             case 2: launch_rows_r(k_rows_rp<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s); break;
             default: launch_rows_r(k_rows_rp<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s); break;
             }
+        else if (C.prune && C.prune->list) {
+            // partial storing (run_group asked asx_qstore_rows): launch A, the predictor rows, stores everything and leaves their
+            // energies; k_q_predict states each pair's list; launch B, the other rows, stores the listed tiles
+            if constexpr (TWO) {
+                const AsxPrune &U = *C.prune;
+                const int nrows = P.M1 + 1, r0 = U.q_rows, a = U.q_row_a;
+                auto rows = [&](AsxRowRun run, const unsigned long long *list) {
+                    hipLaunchKernelGGL((k_rows_rm<S, NT, TWO>), dim3((unsigned)run.count * (unsigned)npairs), dim3(nt),
+                                       (size_t)P.M2 * sizeof(float4), s, rargs_of(P), (const float2 *)C.cx, (const float2 *)C.cy, q, nrows,
+                                       (size_t)nrows * (size_t)P.M2, W, U.eng, run, list);
+                };
+                rows(AsxRowRun{ 0, r0, a }, nullptr);
+                hipLaunchKernelGGL(k_q_predict, dim3(npairs), dim3(256), 0, s, U.eng, nrows, P.ntiles, a, r0, (double)ASX_QSTORE_C, U.list,
+                                   U.qstats);
+                rows(AsxRowRun{ a, nrows - r0, r0 }, U.list);
+            }
+        }
         else if (C.prune) launch_rows_r(k_rows_re<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.prune->eng);
         else if (C.pl) launch_rows_r(k_rows_rl<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl);
         else
@@ -1405,6 +1558,36 @@ static unsigned resident_blocks(const void *fn, int nthreads, size_t lds)
         n = (unsigned)per_cu * (unsigned)cus;
     known[{ fn, dev }] = n;
     return n;
+}
+
+// Partial storing: the predictor rows R0 of a pruned group of npairs pairs, 0 = the group keeps k_rows_re.  The plan's row schedule
+// must have a k_rows_rm instance (the two-half form) and at most 256 tiles (k_q_predict).  R0 = the kernel's resident blocks / npairs,
+// clamped to [8, 32], so that launch A is about one generation of blocks: rows that had to be computed anyway, and enough of them that
+// the tile sums of unrelated tracks stay under ASX_QSTORE_C medians.  mode 1 (auto): only a group of at least ASX_QSTORE_MIN_GENS
+// generations of blocks -- the split costs the row pass about one generation's tail and two launches, which has to be small against
+// what a third less store traffic returns (about 8 % of the pass: measured, EXPERIMENTS.md); single pairs and small groups launch
+// exactly what they launched before.  mode 2: any group, R0 = 8 (tests).
+constexpr int ASX_QSTORE_MIN_GENS = 8;
+int asx_qstore_rows(const AsxDev &P, int npairs, int mode)
+{
+    int r0 = 0;
+    if (mode <= 0 || npairs <= 0 || P.ntiles > 256 || P.M1 + 1 < 64) return 0;
+    asx_with_entry(AsxRRows{}, P.krows, [&](auto e) {
+        using S = typename decltype(e)::sched;
+        constexpr int NT = e.nt;
+        if constexpr (e.two) {
+            if (mode >= 2) { r0 = 8; return; }
+            const unsigned res = resident_blocks((const void *)k_rows_rm<S, NT, true>, 2 * NT, (size_t)P.M2 * sizeof(float4));
+            if ((size_t)(P.M1 + 1) * (size_t)npairs < (size_t)ASX_QSTORE_MIN_GENS * res) return;
+            r0 = std::min(32, std::max(8, (int)(res / (unsigned)npairs)));
+        }
+    });
+    return r0;
+}
+
+void asx_launch_qstore_takeback(const AsxPrune &U, const AsxSpecWs &S, int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_qstore_takeback, dim3((unsigned)(npairs + 255) / 256), dim3(256), 0, s, U.redo, S.hdr, S.mode_count, npairs);
 }
 
 // Forward columns of tracks first .. first + count - 1 of src and / or smp (null: not that operand), src_stride / smp_stride floats
@@ -1475,10 +1658,10 @@ static void launch_inv_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, 
     hipLaunchKernelGGL(k_tile_bounds, dim3(npairs, 1024 / tp), dim3((tp + 63) & ~63), 0, s, U.eng, U.ub, U.best, U.part, U.ticket, P.M1 + 1, P.ntiles,
                        4.0 * (double)P.M1, ASX_PRUNE_FLOOR_PER_TERM * (double)ASX_PRUNE_T * (double)(P.M1 + 1));
     hipLaunchKernelGGL(k1, dim3(npairs, 2), dim3(NT), lds, s, rargs_of(P), q, pitch, W, resident_blocks((const void *)k1, NT, lds),
-                       AsxSelPrune<true>{ U.best, U.skip });
-    hipLaunchKernelGGL(k_prune_select, dim3(npairs), dim3(256), 0, s, U.ub, U.best, U.skip, W, P.ntiles, U.stats);
+                       AsxSelPrune<true>{ U.best, U.skip, U.list });
+    hipLaunchKernelGGL(k_prune_select, dim3(npairs), dim3(256), 0, s, U.ub, U.best, U.skip, W, P.ntiles, U.stats, U.list, U.redo, U.pair_base);
     hipLaunchKernelGGL(k2, dim3(npairs, rcol_grid_x(P.ntiles, asx_ilog2(TC))), dim3(NT), lds, s, rargs_of(P), q, pitch, W,
-                       resident_blocks((const void *)k2, NT, lds), AsxSelPrune<false>{ U.best, U.skip });
+                       resident_blocks((const void *)k2, NT, lds), AsxSelPrune<false>{ U.best, U.skip, U.list });
 }
 
 // The inverse column pass of a group: U null, the flavour the search asks for; U the lane's prune workspace (a group in scope for

@@ -50,6 +50,8 @@ _HEADER_SIGNATURES = {
     "asx_plan_pearson_modes": (_int, [_vp, _u64p]),
     "asx_plan_set_prune": (_int, [_vp, _int]),
     "asx_plan_prune_stats": (_int, [_vp, _u64p, _u64p]),
+    "asx_plan_set_qstore": (_int, [_vp, _int]),
+    "asx_plan_qstore_stats": (_int, [_vp, _u64p]),
     "asx_plan_set_profiling": (_int, [_vp, _int]),
     "asx_plan_last_timings_ms": (_int, [_vp, c_f32p]),
     "asx_plan_timings_ms": (_int, [_vp, _int, c_f32p]),
@@ -662,6 +664,17 @@ class Plan:
     def prune_stats(self):
         """(column tiles the pruned groups transformed, tiles those groups had in all) over the plan's life"""
         return _counters(lib().asx_plan_prune_stats, self._h, 2)
+
+    def set_qstore(self, mode=1):
+        """partial storing of Q in the pruned pass: 0 off, 1 auto (large groups of the two longest lengths), 2 always; same lag, ret and
+        coefficient bits in every mode (include/audiosync/xcorr_hip.h)"""
+        _check(lib().asx_plan_set_qstore(self._h, int(mode)))
+
+    def qstore_stats(self):
+        """(pairs given a list, pairs that stored everything, pairs run again, tiles stored) over the plan's life"""
+        c = (ctypes.c_uint64 * 4)()
+        _check(lib().asx_plan_qstore_stats(self._h, c))
+        return tuple(int(v) for v in c)
 
     def narrowed_calls(self):
         """xcorr_f64 calls whose frames were all exactly float32 and crossed PCIe as 4 bytes each"""
