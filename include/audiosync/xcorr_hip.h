@@ -33,9 +33,9 @@
  *   ret = -3 (asx_xcorr_topk_f32_dev and asx_xcorr_pool_topk_f32_dev only): no lag is left for
  *   this entry of the pair (its window minus the zones around the earlier entries is empty);
  *   lag = 0 and coef = NaN.
- *   ret = -4 (asx_xcorr_pool_f32_dev and asx_xcorr_pool_topk_f32_dev only): a pair's source or
- *   sample index is outside its pool; lag = 0 and coef = NaN (the top-k form: in all k entries
- *   of the pair).  It takes precedence over -2 and -3.
+ *   ret = -4 (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev and asx_xcorr_pool_phat_f32_dev
+ *   only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
+ *   form: in all k entries of the pair).  It takes precedence over -2 and -3.
  */
 #ifndef AUDIOSYNC_XCORR_HIP_H
 #define AUDIOSYNC_XCORR_HIP_H
@@ -345,8 +345,9 @@ int asx_xcorr_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_
  * and asx_plan_prune_stats unchanged (the pruned inverse pass is never used: |Q'| = 1 makes its energy bound useless).  It
  * allocates nothing after plan creation, but for the broadcast slot's first allocation under asx_xcorr_strided_f32_dev's rule.
  *   Weakness.  Bins that hold only rounding noise vote too: on band-limited material the empty part of the spectrum adds noise
- * to r_phat and lowers the peak.  asx_xcorr_phat_band_f32_dev, below, lets only a chosen range of bins vote.  Not offered with
- * PHAT: pools, top-k, the double ABI, streams, packed plans. */
+ * to r_phat and lowers the peak.  asx_xcorr_phat_band_f32_dev, below, lets only a chosen range of bins vote, and
+ * asx_xcorr_pool_phat_f32_dev takes listed pairs of two track pools.  Not offered with PHAT: top-k, the double ABI, streams, packed
+ * plans. */
 int asx_xcorr_phat_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
                            const float *d_sample, size_t sample_stride,
                            const int64_t *d_windows, size_t window_stride, size_t batch,
@@ -443,6 +444,40 @@ int asx_xcorr_pool_topk_f32_dev(asx_plan *plan,
                                 const int64_t *d_windows, size_t window_stride,
                                 size_t batch, int k, int64_t min_separation,
                                 int64_t *d_lag, double *d_coef, int32_t *d_ret, void *stream);
+
+/* GCC-PHAT over two track pools: asx_xcorr_pool_f32_dev's pairs ranked as asx_xcorr_phat_band_f32_dev ranks them.  All pairs over the
+ * clips of one event share a hum, a bass line or a room mode, which is where the raw correlation picks the loudest common component
+ * and where the bank pays most: c clips are c * c pairs and 2c forward column passes.
+ *   Everything before `batch` means what it means in asx_xcorr_pool_f32_dev: the pools, which may alias or overlap, strides that may
+ * be below the track length, d_pairs == NULL = every combination source-major (batch = nsources * nsamples), per-pair window rows or
+ * the plan's window (d_windows == NULL), the 16-byte layout rule, the stream rule and the bank with its growth rule -- filled once
+ * per call, never grown inside a stream capture.
+ *   bin_lo, bin_hi, d_peak, the vote count V and the peak rule mean what they mean in asx_xcorr_phat_band_f32_dev.  The band is always
+ * given: the full band [0, N] is plain PHAT, the kernels and the bits of a banded strided call over the full band.
+ *   Per pair it is the banded PHAT call: for a pair whose indices are inside their pools, (lag, coef, peak, ret) are bit for bit what
+ * asx_xcorr_phat_band_f32_dev returns for that pair alone on the same plan with the same band and window (the pair's row, or the
+ * plan's window): the bank holds the same column spectra and the row pass forms the same float32 Q'.  A row that is not a window
+ * gives that pair (0, NaN, NaN, -2).  A pair with a digitally silent track returns the seed's lag with peak 0, ret following its NaN
+ * coefficient.  ret is never 1.
+ *   A row of d_pairs with an index outside its pool gives that pair lag 0, coef NaN, peak NaN and ret -4 (over -2), reads nothing
+ * outside the pools and leaves the other pairs untouched, bit for bit.
+ *   What the call never does, as the PHAT call: it lists nothing, takes no second look and does not synchronise the host beyond what
+ * a bank that must grow costs; it leaves asx_plan_peak_overflows, asx_plan_peak_repairs, asx_plan_pearson_modes, asx_plan_prune_stats
+ * and asx_plan_qstore_stats unchanged and runs the same whatever asx_plan_set_exact says.  With a bank already large enough it
+ * allocates nothing.
+ *   Returns -1 with the outputs untouched and nothing launched on every refusal of asx_xcorr_pool_f32_dev (a NULL pool, d_coef or
+ * d_ret; an empty pool while batch > 0; not a real-column plan; alignment; strides that are not multiples of 4 floats; d_pairs ==
+ * NULL with batch != nsources * nsamples; a bank that cannot be allocated, or would have to grow during a stream capture) and for a
+ * band outside 0 <= bin_lo <= bin_hi <= N.  d_lag and d_peak may be NULL.  batch == 0 returns 0.
+ *   Cost: the bank fill once per call, then per group the row pass of the strided PHAT call on the bank's rows and its tail
+ * (measured: DESIGN.md).  Not offered: top-k with PHAT, a band per pair. */
+int asx_xcorr_pool_phat_f32_dev(asx_plan *plan,
+                                const float *d_sources, size_t source_stride, size_t nsources,
+                                const float *d_samples, size_t sample_stride, size_t nsamples,
+                                const int32_t *d_pairs,
+                                const int64_t *d_windows, size_t window_stride,
+                                size_t batch, int64_t bin_lo, int64_t bin_hi,
+                                int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
 
 /* The batched variant over several GPUs of one node from ONE process (BASELINE.json north_star; no
  * reference equivalent): plans[i] was created on device i (any devices; all the same sample_len); the

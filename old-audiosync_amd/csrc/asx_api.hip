@@ -907,9 +907,11 @@ struct GroupOpts {
     int dot_blocks = 0;          // blocks per pair of the exact re-evaluation; 0: by the group size
     const AsxPeakWs *pk = nullptr; // the peak workspace instead of the lane's (the second look's lists for every lag)
     Topk topk{};                 // k > 1: passes 2..k over the group's Q (y's entry stride is k)
-    // How the product spectrum is weighted (asx_internal.h).  ASX_W_PHAT (asx_xcorr_phat_f32_dev, real-column plans, k = 1, no pool):
+    // How the product spectrum is weighted (asx_internal.h).  ASX_W_PHAT (asx_xcorr_phat_f32_dev, real-column plans, k = 1):
     // the row pass's PHAT flavour and the PHAT tail -- k_phat_finalize, the direct Pearson form, k_invalid_rows -- with no pruned
     // pass, no list and no spectral form, whatever the plan's switches say: none of them means anything for a whitened spectrum.
+    // In a pool group (asx_xcorr_pool_phat_f32_dev) the row pass is the listed PHAT flavour, the Pearson form reads the pairs' inputs
+    // through the group's records, and k_invalid_pairs gives a pair outside its pool a NaN peak too.
     // ASX_W_PHAT_BAND (asx_xcorr_phat_band_f32_dev): the same group, but only the bins of `fband` vote (k_rows_rb) and the peak height is
     // per voter (AsxBand::votes).  The entry points turn the full band into ASX_W_PHAT (band_weight).
     AsxWeight weight = ASX_W_NONE;
@@ -1026,8 +1028,9 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // a pair whose row is not a window: (0, NaN, -2), the others untouched (top-k: k_topk_step writes it for every entry)
     // (a PHAT group: k_phat_finalize has given such a pair a NaN peak)
     if (call.kind == AsxSearch::ROWS && K == 1) asx_launch_invalid_rows(call.rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
-    // a pool pair with an index outside its pool: (0, NaN, -4), which takes precedence over -2
-    if (pl && K == 1) asx_launch_invalid_pairs(pl, y.lag, y.coef, y.ret, (int)g, s);
+    // a pool pair with an index outside its pool: (0, NaN, -4), which takes precedence over -2 (a PHAT group: and a NaN peak over the 0
+    // that k_phat_finalize wrote for its empty maximum)
+    if (pl && K == 1) asx_launch_invalid_pairs(pl, y.lag, y.coef, y.ret, y.peak, (int)g, s);
     // Passes 2..k over the same Q; the transforms are not run again.  In a pool group the passes read the pairs' inputs through the
     // group's records (the listed kernels), and an invalid pair -- whose Q is NaN and whose bound is zero, so that no pass finds or
     // lists anything for it -- gets (0, NaN, -4) in all k entries behind the last step, over the steps' -2 and -3.
@@ -1477,11 +1480,13 @@ static int ensure_bank(asx_plan *p, const char *fn, size_t nsrc, size_t nsmp, hi
     return 0;
 }
 
-// asx_xcorr_pool_f32_dev and asx_xcorr_pool_topk_f32_dev (fn: the entry point's name for the messages; y and topk: the latter's entry
-// stride and option, after its own checks of k and min_separation)
+// asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev and asx_xcorr_pool_phat_f32_dev (fn: the entry point's name for the messages; y
+// and topk: the top-k call's entry stride and option, after its own checks of k and min_separation; weight and band: the PHAT call's,
+// after band_weight)
 static int pool_batch(asx_plan *p, const char *fn, const float *d_sources, size_t source_stride, size_t nsources, const float *d_samples,
                       size_t sample_stride, size_t nsamples, const int32_t *d_pairs, const int64_t *d_windows, size_t window_stride,
-                      size_t batch, const Results &y, void *stream, const Topk &topk = {})
+                      size_t batch, const Results &y, void *stream, const Topk &topk = {}, AsxWeight weight = ASX_W_NONE,
+                      const AsxBand &band = {})
 {
     if (!p || !d_sources || !d_samples || !y.coef || !y.ret) return fail("%s: null argument", fn);
     PlanCall c(p, stream);
@@ -1510,7 +1515,7 @@ static int pool_batch(asx_plan *p, const char *fn, const float *d_sources, size_
     p->bank.fills++;
     const PoolCall pool{ d_pairs, nsources, nsamples };
     return run_batch(p, Pairs<float>::pooled(&pool, d_sources, source_stride, d_samples, sample_stride, d_windows, window_stride), batch, y,
-                     s, topk);
+                     s, topk, weight, band);
 }
 
 extern "C" int asx_xcorr_pool_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
@@ -1534,6 +1539,23 @@ extern "C" int asx_xcorr_pool_topk_f32_dev(asx_plan *p, const float *d_sources, 
     if (min_separation < 0) return fail("%s: min_separation = %lld is negative", fn, (long long)min_separation);
     return pool_batch(p, fn, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows, window_stride,
                       batch, { d_lag, d_coef, d_ret, (size_t)k }, stream, Topk{ k, min_separation });
+}
+
+// GCC-PHAT over two pools: the pool call's pairs through PHAT groups (run_group: GroupOpts::weight with a pool), the bank filled once per
+// call.  The band is always given; the full band is plain PHAT (band_weight).
+extern "C" int asx_xcorr_pool_phat_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                           const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                           const int64_t *d_windows, size_t window_stride, size_t batch, int64_t bin_lo, int64_t bin_hi,
+                                           int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_pool_phat_f32_dev";
+    if (!p) return fail("%s: null argument", fn);
+    AsxWeight weight;
+    AsxBand band;
+    if (!band_weight(p, bin_lo, bin_hi, weight, band))
+        return fail("%s: bins [%lld, %lld] are not a band inside [0, %zu]", fn, (long long)bin_lo, (long long)bin_hi, (size_t)p->host.N);
+    return pool_batch(p, fn, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows, window_stride,
+                      batch, { d_lag, d_coef, d_ret, 1, d_peak }, stream, {}, weight, band);
 }
 
 // diagnostic (not in the public header): the bank's capacity in tracks and how many pool calls have filled it

@@ -304,6 +304,7 @@ struct AsxSearch {
 // outside its pool gives slot 0 and ASX_POOL_INVALID: k_rows_rl writes a NaN Q and a zero bound for it -- every inverse tile of every
 // pass leaves at once, whatever the pair's window, zones or seed, so its running maximum stays empty and it can never overflow -- and
 // k_invalid_pairs writes (0, NaN, -4) behind the Pearson kernels (top-k: k_invalid_pairs_k, all k entries, behind the last step).
+// A PHAT pool group (asx_xcorr_pool_phat_f32_dev) is the same with k_rows_rlp / k_rows_rlb, and k_invalid_pairs also writes a NaN peak.
 #define ASX_POOL_INVALID 1u
 struct AsxPoolPair {
     uint32_t sx, sy;        // bank slots: source a, sample b (0 for an invalid pair)
@@ -482,7 +483,8 @@ template <int... ZC, class F> void asx_with_selection(const AsxSearch &q, F go)
 //   prune: the lane's workspace of the pruned inverse pass when the group is in scope for it (run_group decides), else null.
 //   weight: how the product spectrum is weighted before the inverse passes (AsxWeight; run_group's GroupOpts::weight).
 // ASX_W_PHAT (asx_xcorr_phat_f32_dev): every bin of X conj(Y) divided by its magnitude in the row pass (k_rows_rp), the tiny bound, and
-// k_phat_finalize in place of the exactness machinery.
+// k_phat_finalize in place of the exactness machinery.  Together with pl (asx_xcorr_pool_phat_f32_dev): the listed forms, k_rows_rlp
+// and k_rows_rlb.
 // ASX_W_PHAT_BAND (asx_xcorr_phat_band_f32_dev): the same, but only the bins whose frequency min(k, F - k) lies in the band vote
 // (k_rows_rb sets the others to zero), and k_phat_finalize divides by the number of voters.  The full band is ASX_W_PHAT.
 enum AsxWeight { ASX_W_NONE = 0, ASX_W_PHAT = 1, ASX_W_PHAT_BAND = 2 };
@@ -562,8 +564,9 @@ void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sban
 // pool calls: each pair's record (out) and its two slots' norm partials and band sums (band may be null) into the group's places
 void asx_launch_pool_resolve(const AsxDev &P, const AsxPoolArgs &A, AsxPoolPair *out, float *nrm, float2 *band, int npairs,
                              hipStream_t s);
-// behind the Pearson kernels of a pool group: (0, NaN, -4) for every pair flagged ASX_POOL_INVALID
-void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
+// behind the Pearson kernels of a pool group: (0, NaN, -4) for every pair flagged ASX_POOL_INVALID, and NaN in peak (null but in a
+// PHAT pool group)
+void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, double *peak, int npairs, hipStream_t s);
 // the same behind the last k_topk_step of a pool group with top-k: all k entries of such a pair (entry stride k)
 void asx_launch_invalid_pairs_k(const AsxPoolPair *pl, int k, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,

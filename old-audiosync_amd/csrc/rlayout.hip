@@ -196,7 +196,8 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 //                pieces, whole 128-byte lines of C and Q) instead of 1200 / 800 rows of eight.
 //   BC: broadcast forms (asx_xcorr_strided_f32_dev).  Bit 0 = C_x is the plan's broadcast slot, one C for every pair (pair step
 //   0, temporal loads: every pair reads it, it must stay in the caches), bit 1 = C_y is.  BC = 0: both have Q's pair step.
-//   Bit 2 (k_rows_rl, pool calls): C_x / C_y are rows sx / sy of the plan's bank (L[pair], AsxPoolPair), temporal like the slot.
+//   Bit 2 (k_rows_rl, pool calls; with PHAT k_rows_rlp, with PHAT and BAND k_rows_rlb): C_x / C_y are rows sx / sy of the plan's bank
+//   (L[pair], AsxPoolPair), temporal like the slot.
 //   ENG (k_rows_re, the pruned inverse pass): the block also leaves the energy of its row of Q per column tile of sixteen,
 //   eng[pair][k1][tile] = sum of |Q[k1][j2]|^2 over the tile's columns, in float32, one contiguous run per block.  The store phase
 //   holds every Q value in a register: its |Q|^2 goes to LDS, into the upper halves of the slots, which are free by then (the
@@ -653,6 +654,26 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rb(
                                                    nullptr, nullptr, band);
 }
 
+// What the listed row kernels do for a pair flagged ASX_POOL_INVALID (k_rows_rl below): the block's row of Q becomes NaN and row 0's
+// block leaves a zero bound and an empty running maximum.  true (block-uniform): the block is done.
+template <class S, int NT, bool TWO>
+__device__ __forceinline__ bool rows_rl_invalid(float2 *__restrict__ qo, int nrows, size_t pair_pitch, const AsxPeakWs &W,
+                                                const AsxPoolPair *__restrict__ L)
+{
+    const int pair = blockIdx.x / nrows;
+    if (!(L[pair].flags & ASX_POOL_INVALID)) return false;
+    constexpr int M2 = TWO ? 2 * S::n : S::n, NTB = TWO ? 2 * NT : NT;
+    const int k1 = blockIdx.x - pair * nrows;
+    float2 *go = qo + (size_t)pair * pair_pitch + (size_t)k1 * M2;
+    for (int j = threadIdx.x; j < M2; j += NTB) go[j] = make_float2(NAN, NAN);
+    if (k1 == 0 && threadIdx.x == 0) {
+        W.bound2[pair] = 0.f;
+        W.pairmax[pair] = 0;
+        W.cand_n[pair] = 0;
+    }
+    return true;
+}
+
 // The listed form (asx_xcorr_pool_f32_dev): pair p's C_x / C_y are rows L[p].sx / L[p].sy of the bank (cx, cy: its source and sample
 // spectra, pair_pitch apart), both loaded temporal -- consecutive pairs may share a slot.  The same body: the same float32 Q, bit for
 // bit, as k_rows_r on the same C rows.  A pair flagged ASX_POOL_INVALID (an index outside its pool) gets a NaN Q and a zero bound instead: every
@@ -665,20 +686,32 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rl(
                                                                                  int nrows, size_t pair_pitch, AsxPeakWs W,
                                                                                  const AsxPoolPair *__restrict__ L)
 {
-    const int pair = blockIdx.x / nrows;
-    if (L[pair].flags & ASX_POOL_INVALID) { // block-uniform
-        constexpr int M2 = TWO ? 2 * S::n : S::n, NTB = TWO ? 2 * NT : NT;
-        const int k1 = blockIdx.x - pair * nrows;
-        float2 *go = qo + (size_t)pair * pair_pitch + (size_t)k1 * M2;
-        for (int j = threadIdx.x; j < M2; j += NTB) go[j] = make_float2(NAN, NAN);
-        if (k1 == 0 && threadIdx.x == 0) {
-            W.bound2[pair] = 0.f;
-            W.pairmax[pair] = 0;
-            W.cand_n[pair] = 0;
-        }
-        return;
-    }
+    if (rows_rl_invalid<S, NT, TWO>(qo, nrows, pair_pitch, W, L)) return;
     rows_r_body<S, NT, TWO, 7>(P, cx, cy, qo, nrows, pair_pitch, pair_pitch, pair_pitch, W, L);
+}
+
+// The listed form of a PHAT group (asx_xcorr_pool_phat_f32_dev over the full band): k_rows_rl with the whitened product, the float32
+// Q' of k_rows_rp on the same C rows.  An invalid pair leaves what k_rows_rl leaves: k_phat_finalize then finds an empty maximum, and
+// k_invalid_pairs overwrites the pair's results, its peak included.  Names of their own: the k_rows_rl instances stay the kernels they were.
+template <class S, int NT, bool TWO>
+__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rlp(const RArgs P, const float2 *__restrict__ cx,
+                                                                                  const float2 *__restrict__ cy, float2 *__restrict__ qo,
+                                                                                  int nrows, size_t pair_pitch, AsxPeakWs W,
+                                                                                  const AsxPoolPair *__restrict__ L)
+{
+    if (rows_rl_invalid<S, NT, TWO>(qo, nrows, pair_pitch, W, L)) return;
+    rows_r_body<S, NT, TWO, 7, false, true>(P, cx, cy, qo, nrows, pair_pitch, pair_pitch, pair_pitch, W, L);
+}
+
+// ... and of a banded PHAT group: k_rows_rlp that lets only the bins of `band` vote, the float32 Q' of k_rows_rb.
+template <class S, int NT, bool TWO>
+__global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rlb(const RArgs P, const float2 *__restrict__ cx,
+                                                                                  const float2 *__restrict__ cy, float2 *__restrict__ qo,
+                                                                                  int nrows, size_t pair_pitch, AsxPeakWs W,
+                                                                                  const AsxPoolPair *__restrict__ L, const AsxBand band)
+{
+    if (rows_rl_invalid<S, NT, TWO>(qo, nrows, pair_pitch, W, L)) return;
+    rows_r_body<S, NT, TWO, 7, false, true, true>(P, cx, cy, qo, nrows, pair_pitch, pair_pitch, pair_pitch, W, L, nullptr, band);
 }
 
 // ---------------------------------------------------------------------------
@@ -1479,15 +1512,18 @@ static void launch_rows_r(K kernel, const AsxDev &P, int nt, const AsxSpectra &C
 
 // The row pass of a group whose spectra are C, which decides the flavour: k_rows_re (plus the tile energies C.prune->eng) when the
 // group is in scope for pruning, k_rows_rl (C_x / C_y at the pairs' bank slots) in a pool group, else k_rows_r in the broadcast form
-// C.bc -- or, in a PHAT group (C.weight; never pruned, never a pool group), k_rows_rp in that form, or k_rows_rb with C.fband when only
-// a band votes.  The operands that are not broadcast and q have the group workspace's pair pitch.
+// C.bc -- or, in a PHAT group (C.weight; never pruned), k_rows_rp in that form, or k_rows_rb with C.fband when only a band votes; in a
+// PHAT group that is a pool group their listed forms, k_rows_rlp and k_rows_rlb.  The operands that are not broadcast and q have the
+// group workspace's pair pitch.
 void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s)
 {
     asx_with_entry(AsxRRows{}, P.krows, [&](auto e) {
         using S = typename decltype(e)::sched;
         constexpr int NT = e.nt, nt = e.two ? 2 * NT : NT;
         constexpr bool TWO = e.two;
-        if (C.weight == ASX_W_PHAT_BAND)
+        if (C.weight == ASX_W_PHAT_BAND && C.pl) launch_rows_r(k_rows_rlb<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl, C.fband);
+        else if (C.weight == ASX_W_PHAT && C.pl) launch_rows_r(k_rows_rlp<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl);
+        else if (C.weight == ASX_W_PHAT_BAND)
             switch (C.bc) {
             case 0: launch_rows_r(k_rows_rb<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s, C.fband); break;
             case 1: launch_rows_r(k_rows_rb<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s, C.fband); break;

@@ -1057,15 +1057,18 @@ __global__ __launch_bounds__(ASX_THREADS) void k_invalid_rows(AsxWinRows R, uint
 }
 
 // grid (npairs / ASX_THREADS): behind the Pearson kernels (and k_invalid_rows) of a pool group, the pairs with an index outside its pool
-// (ASX_POOL_INVALID) get lag 0, a NaN coefficient and ret -4; the others are not touched
+// (ASX_POOL_INVALID) get lag 0, a NaN coefficient and ret -4; the others are not touched.  peak: null, or the peak heights of a PHAT
+// pool group (asx_xcorr_pool_phat_f32_dev), where such a pair gets NaN over the 0 that k_phat_finalize wrote for its empty maximum.
 __global__ __launch_bounds__(ASX_THREADS) void k_invalid_pairs(const AsxPoolPair *__restrict__ PL, int npairs, int64_t *__restrict__ lag,
-                                                                double *__restrict__ coef, int32_t *__restrict__ ret)
+                                                                double *__restrict__ coef, int32_t *__restrict__ ret,
+                                                                double *__restrict__ peak)
 {
     const int pair = blockIdx.x * ASX_THREADS + threadIdx.x;
     if (pair >= npairs || !(PL[pair].flags & ASX_POOL_INVALID)) return;
     if (lag) lag[pair] = 0;
     coef[pair] = (double)NAN;
     ret[pair] = -4;
+    if (peak) peak[pair] = (double)NAN;
 }
 
 // the k-entry form (asx_xcorr_pool_topk_f32_dev): behind the LAST k_topk_step of a pool group, all k entries (index pair * k + j) of
@@ -1669,9 +1672,10 @@ void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, co
                        call.rows, N, npairs, j, k, sep, lag, coef, ret);
 }
 
-void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
+void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, double *peak, int npairs, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_invalid_pairs, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, pl, npairs, lag, coef, ret);
+    hipLaunchKernelGGL(k_invalid_pairs, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, pl, npairs, lag, coef, ret,
+                       peak);
 }
 
 void asx_launch_invalid_pairs_k(const AsxPoolPair *pl, int k, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)

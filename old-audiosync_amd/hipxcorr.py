@@ -66,6 +66,7 @@ _HEADER_SIGNATURES = {
     "asx_xcorr_phat_band_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_topk_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _i64, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_pool_phat_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_band_debug_r_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -424,6 +425,15 @@ def pool_topk_args(n, sources, samples, k, min_separation, pairs=None, windows=N
     tuple + (k, min_separation).  ValueError on anything else."""
     option = _topk_option(k, min_separation)
     return pool_args(n, sources, samples, pairs, windows) + option
+
+
+def pool_phat_args(n, sources, samples, pairs=None, windows=None, band=None):
+    """Host checks of Plan.xcorr_pool_phat_f32: band None (every bin, (0, N)) or integers (bin_lo, bin_hi) with 0 <= bin_lo <= bin_hi
+    <= N, the rest as pool_args.  -> pool_args' tuple + (bin_lo, bin_hi).  ValueError on anything else."""
+    lo, hi = (0, n) if band is None else band
+    if any(isinstance(b, bool) or not isinstance(b, (int, np.integer)) for b in (lo, hi)) or not 0 <= int(lo) <= int(hi) <= n:
+        raise ValueError("band must be integers (bin_lo, bin_hi) with 0 <= bin_lo <= bin_hi <= %d, not %r" % (n, band))
+    return pool_args(n, sources, samples, pairs, windows) + (int(lo), int(hi))
 
 
 def position_rows(n, hop, batch, p_lo, p_hi):
@@ -799,6 +809,16 @@ class Plan:
                                                  int(nsamples), d_pairs or None, d_windows or None, int(window_stride), int(batch),
                                                  int(k), int(min_separation), d_lag or None, d_coef, d_ret, stream or None))
 
+    def xcorr_pool_phat_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows,
+                            window_stride, batch, bin_lo, bin_hi, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_phat_f32_dev -- xcorr_pool_dev's pairs ranked by the GCC-PHAT curve in which
+        bins bin_lo..bin_hi vote ((0, N): every bin); d_peak (float64, may be 0) receives |r_phat[lag]| / V; always asynchronous on
+        `stream`"""
+        _check(lib().asx_xcorr_pool_phat_f32_dev(self._h, d_sources or None, int(source_stride), int(nsources), d_samples or None,
+                                                 int(sample_stride), int(nsamples), d_pairs or None, d_windows or None,
+                                                 int(window_stride), int(batch), int(bin_lo), int(bin_hi), d_lag or None,
+                                                 d_coef or None, d_peak or None, d_ret or None, stream or None))
+
     def debug_prune(self, pair=0):
         """diagnostic: (upper bounds of |r| per column tile, the largest-bound tile) of `pair` of the last pruned group"""
         n = (self.split[1] + self.split[2] - 1) // self.split[2]
@@ -902,6 +922,18 @@ class Plan:
         shape = ((batch,) if pr is not None else (s.shape[0], t.shape[0])) + (k,)
         return self._staged((s, t, pr, w), shape, _RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_topk_dev(
             d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, k, sep, *d_out))
+
+    def xcorr_pool_phat_f32(self, sources, samples, pairs=None, windows=None, band=None):
+        """Pairs of two pools ranked by the GCC-PHAT curve (asx_xcorr_pool_phat_f32_dev): the pools, pairs and windows of
+        xcorr_pool_f32; band None (every bin votes) or (bin_lo, bin_hi) as in xcorr_phat_band_f32.  Every track is transformed once
+        per call.  Arguments are checked on the host (ValueError) before anything is uploaded.  Returns (lag int64, coef float64,
+        peak float64, ret int32) of shape [B], or [S, R] when pairs is None; a pair with an index outside its pool gets
+        (0, NaN, NaN, -4)."""
+        n = self.sample_len
+        s, t, pr, w, batch, ws, lo, hi = pool_phat_args(n, sources, samples, pairs, windows, band)
+        shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
+        return self._staged((s, t, pr, w), shape, _PHAT_RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_phat_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, lo, hi, *d_out))
 
     def xcorr_topk_f32(self, source, sample, k, min_separation, windows=None):
         """The k strongest separated lags per pair (asx_xcorr_topk_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N];
