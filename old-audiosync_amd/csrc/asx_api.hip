@@ -900,20 +900,20 @@ struct GroupOpts {
     // a second look at its own staging buffers with them.  Marked and counted (ASX_SEG_INEXACT -> ret = 1,
     // asx_plan_peak_overflows) they still are.
     bool listed = true;
-    // The spectral Pearson form (pearson_spectral.hip) may run: float32 inputs of a float32 ENTRY POINT on a real-column plan.
-    // The double ABI keeps the float64 reduction over the caller's values even when its frames crossed PCIe as float32.
-    bool spectral = true;
+    // The group belongs to a float32 entry point's ordinary path, which has two effects (asx_group_form): the spectral Pearson form may
+    // run, and the pruned inverse pass may.  Cleared, both are off -- the double ABI (it keeps the float64 reduction over the caller's
+    // values even when its frames crossed PCIe as float32), the second look and the r dumps (they exist to see every lag's r and end
+    // with the direct form).
+    bool f32_abi = true;
     float *r_out = nullptr;      // r of every lag (asx_xcorr_debug_r_dev)
     int dot_blocks = 0;          // blocks per pair of the exact re-evaluation; 0: by the group size
     const AsxPeakWs *pk = nullptr; // the peak workspace instead of the lane's (the second look's lists for every lag)
     Topk topk{};                 // k > 1: passes 2..k over the group's Q (y's entry stride is k)
-    // How the product spectrum is weighted (asx_internal.h).  ASX_W_PHAT (asx_xcorr_phat_f32_dev, real-column plans, k = 1):
-    // the row pass's PHAT flavour and the PHAT tail -- k_phat_finalize, the direct Pearson form, k_invalid_rows -- with no pruned
-    // pass, no list and no spectral form, whatever the plan's switches say: none of them means anything for a whitened spectrum.
-    // In a pool group (asx_xcorr_pool_phat_f32_dev) the row pass is the listed PHAT flavour, the Pearson form reads the pairs' inputs
-    // through the group's records, and k_invalid_pairs gives a pair outside its pool a NaN peak too.
-    // ASX_W_PHAT_BAND (asx_xcorr_phat_band_f32_dev): the same group, but only the bins of `fband` vote (k_rows_rb) and the peak height is
-    // per voter (AsxBand::votes).  The entry points turn the full band into ASX_W_PHAT (band_weight).
+    // How the product spectrum is weighted (AsxWeight, asx_internal.h; real-column plans, k = 1): a weighted group runs the row pass's
+    // PHAT flavour and the PHAT tail -- k_phat_finalize, the direct Pearson form, k_invalid_rows.  In a pool group the Pearson form
+    // reads the pairs' inputs through the group's records, and k_invalid_pairs gives a pair outside its pool a NaN peak too.
+    // ASX_W_PHAT_BAND: only the bins of `fband` vote and the peak height is per voter (AsxBand::votes).  The entry points turn the
+    // full band into ASX_W_PHAT (band_weight).
     AsxWeight weight = ASX_W_NONE;
     AsxBand fband{};
     bool qstore = true;          // partial storing of Q allowed (false: the second run of a pair whose stored set fell short)
@@ -927,44 +927,34 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     asx_plan::Lane &W = p->lanes[o.lane];
     const AsxPeakWs &pk = o.pk ? *o.pk : W.pk;
     auto mark = [&](size_t k) { return o.prof_group != GroupOpts::no_marks && prof_mark(p, s, o.prof_group * 6 + k); };
-    AsxPeakWs fin = pk;
-    const bool phat = o.weight != ASX_W_NONE;
-    if (!o.listed || phat) { fin.over_list = nullptr; fin.over_n = nullptr; fin.over_host = nullptr; fin.over_cap = 0; }
-    const bool spectral = std::is_same<TIn, float>::value && p->spectral && o.spectral && pk.band && !phat;
-    AsxPeakWs tk = pk; // what the transform kernels see
-    if (!spectral) { tk.band = nullptr; tk.tile_peak = nullptr; }
-    // The pruned pair of passes (rlayout.hip: k_rows_re, and k_tile_bounds and k_inv_cols_r<..., AsxSelPrune> around k_prune_select) in place of the row pass
-    // and the inverse column pass:
-    // a float32 entry point's group on a real-column plan, every lag competing, no broadcast operand and no pool, one pass, r not asked
-    // for, the lane's own lists (not the second look).  Everything else launches what it always did.
-    // (GroupOpts::spectral is how an entry point says "float32 ABI": the double ABI clears it even when its frames were narrowed.
-    // Whether the plan's Pearson form IS spectral -- p->spectral -- plays no part here.  p->prune is only ever set on a plan the
-    // pruned pass can run on: AsxKernelChoice::prunable.)
-    const bool f32_entry = std::is_same<TIn, float>::value && o.spectral;
     const AsxSearch call = AsxSearch::of(p->win_lo, p->win_hi, P.N, x.win, x.win_step, W.tk, 0); // pass 1's search
-    const bool prune = p->prune && !phat && f32_entry && !x.pool && x.bc == 0 && !o.r_out && !o.pk && o.topk.k == 1 && call.kind == AsxSearch::ALL;
+    // what the group launches (plan_math.h): decided here, once, and only branched on below
+    const AsxGroupForm form = asx_group_form(
+        { .rlayout = P.rlayout != 0, .plan_prune = p->prune, .plan_spectral = p->spectral, .band_sums = pk.band != nullptr,
+          .over_list = pk.over_list != nullptr, .f32_inputs = std::is_same<TIn, float>::value, .f32_abi = o.f32_abi, .listed = o.listed,
+          .r_out = o.r_out != nullptr, .own_lists = o.pk != nullptr, .k = o.topk.k, .search = call.kind, .weight = o.weight,
+          .pool = x.pool != nullptr, .bc = x.bc, .qstore = o.qstore });
+    const AsxPeakWs fin = form.appends ? pk : asx_peak_unlisted(pk);                      // what k_finalize sees
+    const AsxPeakWs tk = form.tail == ASX_TAIL_SPECTRAL ? pk : asx_peak_unbanded(pk);     // what the transform kernels see
     // The group's spectra (AsxSpectra): the lane's own forward passes -- but a broadcast operand's rows are in the plan's slot, and a
     // pool group's in the bank, found through its resolved records -- with the norm partials and band sums always in the lane's places.
     const AsxPoolPair *pl = x.pool ? W.pool : nullptr;
     const AsxSpectra &from = pl ? p->bank.c : p->bslot;
-    // Partial storing of Q (rlayout.hip: k_rows_rm): a pruned group of a call that reads the overflow list behind it (o.listed, the
-    // exact mode -- the list is how a pair whose stored set fell short gets its second run, so the asynchronous mode keeps k_rows_re),
-    // whose row schedule has the kernel and whose size the plan's switch lets in (asx_qstore_rows).  The kernels get a copy of the
-    // lane's AsxPrune that says so: list null = Q is whole.
+    const AsxSpectra C{ (pl || (x.bc & 1)) ? from.cx : W.zxa, (pl || (x.bc & 2)) ? from.cy : W.zya, pk.nrm_part, tk.band, form.bc, pl };
+    // The pruned pass's kernels get a copy of the lane's AsxPrune that says whether Q is stored in part: q_rows predictor rows
+    // (asx_qstore_rows: the row schedule has the kernel and the plan's switch lets a group of this size in), or 0 and list null = Q is whole.
     AsxPrune U = W.prune;
-    U.q_rows = (prune && o.listed && o.qstore && fin.over_list) ? asx_qstore_rows(P, (int)g, p->qstore) : 0;
+    U.q_rows = form.qstore ? asx_qstore_rows(P, (int)g, p->qstore) : 0;
     U.q_row_a = P.M1 / 3; // away from the real rows 0 and M1
     U.pair_base = o.pair_base;
     if (!U.q_rows) { U.list = nullptr; U.redo = nullptr; }
-    const AsxSpectra C{ (pl || (x.bc & 1)) ? from.cx : W.zxa, (pl || (x.bc & 2)) ? from.cy : W.zya, pk.nrm_part, tk.band, x.bc, pl,
-                        prune ? &U : nullptr, o.weight, o.fband };
     if (mark(0)) return -1;
-    if (pl) {
+    if (form.fwd == ASX_FWD_POOL) {
         // pool calls: the bank holds every track's forward column pass; this group only resolves its pairs into slots and offsets
         const AsxPoolArgs A{ x.pool->rows, (uint64_t)x.first, (uint64_t)x.pool->nsrc, (uint64_t)x.pool->nsmp, (uint64_t)x.src_step,
                              (uint64_t)x.smp_step, from.nrm, from.band };
         asx_launch_pool_resolve(P, A, W.pool, C.nrm, C.band, (int)g, s);
-    } else if (P.rlayout) {
+    } else if (form.fwd == ASX_FWD_REAL) {
         // the operands that are not the call's broadcast track, whose pass is in the slot: only its norm partials and band sums are copied
         asx_launch_fwd_cols_r(P, (x.bc & 1) ? nullptr : x.src, x.src_step, (x.bc & 2) ? nullptr : x.smp, x.smp_step, 0, (int)g, C, false, s);
         for (unsigned which = 0; which < 2; which++)
@@ -982,8 +972,8 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     }
     if (mark(1)) return -1;
     float2 *q = W.ga;
-    if (!P.rlayout) asx_launch_rows(P, W.zxa, W.zya, q, tk, (int)g, s);
-    else asx_launch_rows_r(P, C, q, tk, (int)g, s);
+    if (form.rows == ASX_ROWS_PACKED) asx_launch_rows(P, W.zxa, W.zya, q, tk, (int)g, s);
+    else asx_launch_rows_r(P, C, form.rows, form.weight, o.fband, form.pruned ? &U : nullptr, q, tk, (int)g, s);
     if (mark(2)) return -1;
     // Top-k (o.topk.k > 1): every pass's results go to the lane's temporaries, and k_topk_step moves them to entry j of y
     const int K = o.topk.k;
@@ -1002,29 +992,29 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // first: pass 1, which the profiling marks time and whose r goes to o.r_out.
     auto pass = [&](const AsxSearch &find, bool first) -> int {
         float *const r_out = first ? o.r_out : nullptr;
-        if (!P.rlayout) asx_launch_inv_cols(P, q, tk, r_out, (int)g, s, find);
-        else asx_launch_inv_cols_r(P, q, tk, r_out, (int)g, s, find, C.prune);
+        if (form.rows == ASX_ROWS_PACKED) asx_launch_inv_cols(P, q, tk, r_out, (int)g, s, find);
+        else asx_launch_inv_cols_r(P, q, tk, r_out, (int)g, s, find, form.pruned ? &U : nullptr);
         if (first && mark(3)) return -1;
-        if (phat) {
+        if (form.tail == ASX_TAIL_PHAT) {
             // the PHAT tail: the float32 maximum stands (k_phat_finalize), then the reference's coefficient of the samples at that lag
             // (the peak height is per bin that voted)
-            asx_launch_phat_finalize(P, fin, W.seg, y.peak, o.weight == ASX_W_PHAT_BAND ? o.fband.votes(P.N) : (double)P.F, (int)g, s, find);
+            asx_launch_phat_finalize(P, fin, W.seg, y.peak, form.weight == ASX_W_PHAT_BAND ? o.fband.votes(P.N) : (double)P.F, (int)g, s, find);
             if (first && mark(4)) return -1;
             asx_launch_pearson(in, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
             return 0;
         }
         asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, find);
         // (the spectral form's first kernel applies the rule to the exact values itself: one launch less)
-        asx_launch_refine(P, in, pk, W.seg, (int)g, s, dot_blocks, !spectral, find);
+        asx_launch_refine(P, in, pk, W.seg, (int)g, s, dot_blocks, form.tail == ASX_TAIL_DIRECT, find);
         if (first && mark(4)) return -1;
-        if (!spectral)
+        if (form.tail == ASX_TAIL_DIRECT)
             asx_launch_pearson(in, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
         else if constexpr (std::is_same<TIn, float>::value)
             asx_launch_pearson_spectral_f32(P, in, find, tk, W.spec, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
         return 0;
     };
     if (pass(call, true)) return -1;
-    if (U.q_rows && spectral) asx_launch_qstore_takeback(U, W.spec, (int)g, s);
+    if (U.q_rows && form.takeback) asx_launch_qstore_takeback(U, W.spec, (int)g, s);
     // a pair whose row is not a window: (0, NaN, -2), the others untouched (top-k: k_topk_step writes it for every entry)
     // (a PHAT group: k_phat_finalize has given such a pair a NaN peak)
     if (call.kind == AsxSearch::ROWS && K == 1) asx_launch_invalid_rows(call.rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
@@ -1077,19 +1067,19 @@ static int second_look(asx_plan *p, const Pairs<TIn> &xi, const Results &yi, hip
             return 0;
         }))
         return -1;
-    AsxPeakWs K = p->lanes[0].pk;         // slot 0's norms, bound and running maximum (k_rows recomputes all three) ...
+    // slot 0's norms, bound and running maximum (k_rows recomputes all three); no overflow list and no band sums (the second look
+    // ends with the direct Pearson reduction) ...
+    AsxPeakWs K = asx_peak_unbanded(asx_peak_unlisted(p->lanes[0].pk));
     K.cand_n = B.cand_n; K.cand = B.cand; // ... with lists for all 2N lags: this look cannot overflow
     K.refine_n = B.refine_n; K.refine_idx = B.refine_idx; K.refine_val = B.refine_val;
     K.overflows = B.overflows;
-    K.over_list = nullptr; K.over_n = nullptr; K.over_host = nullptr; K.over_cap = 0;
-    K.band = nullptr; K.tile_peak = nullptr; // the second look ends with the direct Pearson reduction
     K.cap = (uint32_t)B.cap;
     HIP_TRY(hipMemsetAsync(B.cand_n, 0, sizeof(uint32_t), s));
     // r = r' + stats[2]
     asx_launch_dc_remove(xi.tsrc, xi.tsmp, P.N, (double)P.F, B.stats, B.src_dc, s);
     K.shift = B.stats + 2;
     if (run_group(p, Pairs<TIn>::staged(B.src_dc, xi.smp, xi.tsrc, xi.tsmp, N, xi.win, xi.win_step), 1, yi, s,
-                  { .prof_group = GroupOpts::no_marks, .listed = false, .spectral = false, .dot_blocks = 2048, .pk = &K, .topk = topk }))
+                  { .prof_group = GroupOpts::no_marks, .listed = false, .f32_abi = false, .dot_blocks = 2048, .pk = &K, .topk = topk }))
         return -1;
     p->repaired++;
     return 0;
@@ -1199,8 +1189,7 @@ static int tune_placement(asx_plan *p, const float *d_src, const float *d_smp, s
     EventPair ev;
     HIP_TRY(hipEventCreate(&ev.e0));
     HIP_TRY(hipEventCreate(&ev.e1));
-    AsxPeakWs tk = W.pk;
-    tk.band = nullptr; tk.tile_peak = nullptr;
+    const AsxPeakWs tk = asx_peak_unbanded(W.pk);
     for (int k = 0; k < 2; k++) {
         float best = 0.f;
         for (int r = 0; r < 4; r++) { // the first launch warms the set up; the fastest of the other three counts
@@ -1403,7 +1392,7 @@ static int phat_debug_r(asx_plan *p, const char *fn, const float *d_source, cons
     prof_begin_call(p);
     const size_t N = p->host.N;
     const int rc = run_group(p, Pairs<float>::contiguous(d_source, d_sample, N), 1, y, c.s,
-                             { .listed = false, .spectral = false, .r_out = d_r, .weight = weight, .fband = band });
+                             { .listed = false, .f32_abi = false, .r_out = d_r, .weight = weight, .fband = band });
     prof_end_call(p, 1);
     return rc;
 }
@@ -1582,7 +1571,7 @@ extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const f
     const size_t N = p->host.N;
     const Pairs<float> x = Pairs<float>::contiguous(d_source, d_sample, N);
     const Results y{ d_lag, d_coef, d_ret };
-    int rc = run_group(p, x, 1, y, c.s, { .listed = p->exact, .spectral = false, .r_out = d_r });
+    int rc = run_group(p, x, 1, y, c.s, { .listed = p->exact, .f32_abi = false, .r_out = d_r });
     prof_end_call(p, 1);
     if (rc == 0 && p->exact && resolve_overflows(p, x, y, c.s) < 0) rc = -1;
     return rc;
@@ -1861,14 +1850,14 @@ int upload_narrowed(hipStream_t s, const double *host, size_t n, float *pin, flo
 } // namespace
 
 // One pair of asx_xcorr_f64 in the plan's staging buffers: the transforms read the float32 copy, the exact passes tsrc / tsmp
-// (the float32 copy itself when the frames were narrowed); the direct Pearson form, see GroupOpts::spectral.
+// (the float32 copy itself when the frames were narrowed); the direct Pearson form, see GroupOpts::f32_abi.
 template <typename TIn>
 static int staged_pair(asx_plan *p, const TIn *tsrc, const TIn *tsmp, const Results &h, hipStream_t s)
 {
     const size_t N = p->host.N;
     const Pairs<TIn> x = Pairs<TIn>::staged(p->st.src, p->st.smp, tsrc, tsmp, N);
     const Results d{ p->st.lag, p->st.coef, p->st.ret };
-    return run_group(p, x, 1, d, s, { .spectral = false }) || fetch_results(p, x, 1, d, h, s) ? -1 : 0;
+    return run_group(p, x, 1, d, s, { .f32_abi = false }) || fetch_results(p, x, 1, d, h, s) ? -1 : 0;
 }
 
 extern "C" int asx_xcorr_f64(asx_plan *p, const double *source, const double *sample, long *lag,
@@ -2300,6 +2289,21 @@ extern "C" int asx_plan_debug_kernels(const asx_plan *p, int *out, int *cols, in
 {
     if (!p || !out || !cols || !rows) return fail("asx_plan_debug_kernels: null argument");
     choice_out(p->host.kernels, out, cols, rows);
+    return 0;
+}
+
+// asx_group_form of an ask given as ASX_GROUP_ASK_INTS ints (plan_math.h states both orders), into ASX_GROUP_FORM_INTS ints
+extern "C" int asx_planmath_group_form(const int *ask, int nask, int *out, int nout)
+{
+    if (!ask || !out || nask != ASX_GROUP_ASK_INTS || nout != ASX_GROUP_FORM_INTS)
+        return fail("asx_planmath_group_form: %d and %d ints, not %d and %d", nask, nout, ASX_GROUP_ASK_INTS, ASX_GROUP_FORM_INTS);
+    AsxGroupAsk a;
+    a.rlayout = ask[0]; a.plan_prune = ask[1]; a.plan_spectral = ask[2]; a.band_sums = ask[3]; a.over_list = ask[4];
+    a.f32_inputs = ask[5]; a.f32_abi = ask[6]; a.listed = ask[7]; a.r_out = ask[8]; a.own_lists = ask[9]; a.k = ask[10];
+    a.search = ask[11]; a.weight = (AsxWeight)ask[12]; a.pool = ask[13]; a.bc = ask[14]; a.qstore = ask[15];
+    const AsxGroupForm f = asx_group_form(a);
+    const int v[ASX_GROUP_FORM_INTS] = { f.fwd, f.rows, f.weight, f.bc, f.pruned, f.tail, f.appends, f.qstore, f.takeback };
+    memcpy(out, v, sizeof v);
     return 0;
 }
 

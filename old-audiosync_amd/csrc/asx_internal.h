@@ -381,6 +381,19 @@ struct AsxPeakWs {
                            // (band = AsxDev::band_rows consecutive rows of the [2 M1][M2] sample matrix; the sample fills the first half)
     float *tile_peak;      // [pairs][M2 / T] SIGNED float32 r (times F) at the best lag of each k_inv_cols_r tile
 };
+// The views of a peak workspace a group's kernels are handed (run_group and second_look, asx_api.hip): the fields a kernel finds
+// null are how it is told.  Without the overflow list: k_finalize marks and counts an overflowing pair but lists nothing.
+inline AsxPeakWs asx_peak_unlisted(AsxPeakWs W)
+{
+    W.over_list = nullptr; W.over_n = nullptr; W.over_host = nullptr; W.over_cap = 0;
+    return W;
+}
+// Without the band sums and tile peaks: the transform kernels leave nothing for the spectral Pearson form.
+inline AsxPeakWs asx_peak_unbanded(AsxPeakWs W)
+{
+    W.band = nullptr; W.tile_peak = nullptr;
+    return W;
+}
 
 // Per-lane workspace of the pruned inverse pass (rlayout.hip: k_rows_re, k_tile_bounds, k_prune_select, k_inv_cols_r<..., AsxSelPrune>)
 struct AsxPrune {
@@ -479,11 +492,17 @@ template <int... ZC, class F> void asx_with_selection(const AsxSearch &q, F go)
 //   As a group's spectra it adds where pair i's rows are: cx + i pitch and cy + i pitch (the lane's workspace); one track for every
 //   pair for the operands of `bc` (bit 0: cx, bit 1: cy -- the broadcast slot's, pitch 0); or rows pl[i].sx of cx and pl[i].sy of cy
 //   (a pool group: cx / cy are the bank's).  nrm and band are then the group's own places (the lane's), whatever cx / cy are: a
-//   broadcast or listed operand's are copied there (k_bcast_aux, k_pool_resolve).  asx_launch_rows_r picks its kernel by it.
-//   prune: the lane's workspace of the pruned inverse pass when the group is in scope for it (run_group decides), else null.
-//   weight: how the product spectrum is weighted before the inverse passes (AsxWeight; run_group's GroupOpts::weight).
+//   broadcast or listed operand's are copied there (k_bcast_aux, k_pool_resolve).
+struct AsxSpectra {
+    float2 *cx, *cy;
+    float *nrm;
+    float2 *band;                 // may be null: no band sums
+    int bc = 0;
+    const AsxPoolPair *pl = nullptr;
+};
+// How the product spectrum is weighted before the inverse passes (run_group's GroupOpts::weight; the scope rules: asx_group_form).
 // ASX_W_PHAT (asx_xcorr_phat_f32_dev): every bin of X conj(Y) divided by its magnitude in the row pass (k_rows_rp), the tiny bound, and
-// k_phat_finalize in place of the exactness machinery.  Together with pl (asx_xcorr_pool_phat_f32_dev): the listed forms, k_rows_rlp
+// k_phat_finalize in place of the exactness machinery.  In a pool group (asx_xcorr_pool_phat_f32_dev): the listed forms, k_rows_rlp
 // and k_rows_rlb.
 // ASX_W_PHAT_BAND (asx_xcorr_phat_band_f32_dev): the same, but only the bins whose frequency min(k, F - k) lies in the band vote
 // (k_rows_rb sets the others to zero), and k_phat_finalize divides by the number of voters.  The full band is ASX_W_PHAT.
@@ -495,16 +514,10 @@ struct AsxBand {
     // bins k of [0, F) inside: a bin and its mirror both vote, bins 0 and N are their own mirrors
     double votes(uint32_t N) const { return 2.0 * ((double)span + 1.0) - (lo == 0) - (lo + span == N); }
 };
-struct AsxSpectra {
-    float2 *cx, *cy;
-    float *nrm;
-    float2 *band;                 // may be null: no band sums
-    int bc = 0;
-    const AsxPoolPair *pl = nullptr;
-    const AsxPrune *prune = nullptr;
-    AsxWeight weight = ASX_W_NONE;
-    AsxBand fband{}; // the frequency band that votes: weight == ASX_W_PHAT_BAND only
-};
+// Which row pass a group runs (asx_group_form, plan_math.h), the weight beside it: the packed-sample k_rows; k_rows_r in the broadcast
+// form bc (weighted: k_rows_rp / k_rows_rb); k_rows_re, which leaves the tile energies of the pruned pass (or k_rows_rm under partial
+// storing); k_rows_rl, C_x / C_y at the pairs' bank slots (weighted: k_rows_rlp / k_rows_rlb).
+enum AsxRowFlavour { ASX_ROWS_PACKED, ASX_ROWS_PLAIN, ASX_ROWS_ENERGY, ASX_ROWS_LISTED };
 // float2 elements of one track's column spectrum: rows k1 = 0 .. M1 of M2 columns, the pitch between the tracks of a set
 inline size_t asx_spectrum_len(const AsxDev &P) { return ((size_t)P.M1 + 1) * (size_t)P.M2; }
 
@@ -542,12 +555,15 @@ void asx_launch_rows(const AsxDev &P, float2 *zxa, float2 *zya, float2 *ga,
 void asx_launch_inv_cols(const AsxDev &P, const float2 *ga, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                          const AsxSearch &q);
 // rlayout.hip: the real-column decomposition (production lengths), each pass on the instance P.kcols / P.krows names.  Which flavour
-// of it runs is the launcher's decision: the row launcher reads it from the group's AsxSpectra, the inverse launcher from the search
-// and from U (the AsxPrune of a group in scope for pruning, else null), the forward launcher from the operands it is given (null: not
-// that operand) -- tracks first .. first + count - 1 of each, into the same tracks of dst.
+// of it runs is the group's form (asx_group_form): the row launcher is told, the inverse launcher takes it from the search and from
+// U (the AsxPrune of a pruned group, else null), the forward launcher from the operands it is given (null: not that operand) --
+// tracks first .. first + count - 1 of each, into the same tracks of dst.
 void asx_launch_fwd_cols_r(const AsxDev &P, const float *src, size_t src_stride, const float *smp, size_t smp_stride, size_t first,
                            int count, const AsxSpectra &dst, bool temporal, hipStream_t s);
-void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s);
+// rows: ASX_ROWS_PLAIN (C.bc), _LISTED (C.pl) or _ENERGY (U: the group's AsxPrune, whose q_rows > 0 asks for partial storing; null
+// otherwise); fband: the band that votes when weight is ASX_W_PHAT_BAND
+void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, AsxRowFlavour rows, AsxWeight weight, const AsxBand &fband, const AsxPrune *U,
+                       float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s);
 // partial storing: the predictor rows a pruned group of npairs pairs gets under `mode` (asx_plan_set_qstore), 0 = the group keeps k_rows_re
 int asx_qstore_rows(const AsxDev &P, int npairs, int mode);
 // behind the Pearson kernels of a group with partial storing: the discarded pass of every pair U.redo marks leaves the counters

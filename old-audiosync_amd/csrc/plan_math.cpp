@@ -370,3 +370,33 @@ std::string asx_host_plan_build(size_t N, const char *split_override, AsxHostPla
     hp->kernels = choose_kernels(*hp, packed, generic);
     return "";
 }
+
+// The form of a launch group.  Every rule is stated here and nowhere else.
+AsxGroupForm asx_group_form(const AsxGroupAsk &a)
+{
+    AsxGroupForm f{};
+    f.weight = a.weight;
+    f.bc = a.bc;
+    // A weighted (PHAT) group: the PHAT row flavours and k_phat_finalize, which lists nothing; no pruned pass and no spectral form
+    // whatever the plan's switches say -- none of them means anything for a whitened spectrum.
+    const bool phat = a.weight != ASX_W_NONE;
+    // A caller that does not read the overflow list behind the group (the asynchronous mode) must not leave entries on it.
+    f.appends = a.listed && !phat;
+    // The spectral Pearson form (pearson_spectral.hip) reads the band sums and tile peaks this group's transform kernels leave: float32
+    // inputs of a float32 entry point, on a workspace that has them.
+    const bool spectral = a.f32_inputs && a.plan_spectral && a.f32_abi && a.band_sums && !phat;
+    f.tail = phat ? ASX_TAIL_PHAT : spectral ? ASX_TAIL_SPECTRAL : ASX_TAIL_DIRECT;
+    // The pruned pair of passes (rlayout.hip: k_rows_re, and k_tile_bounds and k_inv_cols_r<..., AsxSelPrune> around k_prune_select):
+    // a float32 entry point's group, every lag competing, no broadcast operand and no pool, one pass, r not asked for, the lane's own
+    // lists.  Whether the plan's Pearson form is spectral plays no part.  (The plan's switch is only ever on where the pass can run:
+    // AsxKernelChoice::prunable, real-column plans.)
+    f.pruned = a.plan_prune && !phat && a.f32_inputs && a.f32_abi && !a.pool && a.bc == 0 && !a.r_out && !a.own_lists && a.k == 1 &&
+               a.search == AsxSearch::ALL;
+    // Partial storing of Q (k_rows_rm): a pruned group of a call that reads the overflow list behind it -- the list is how a pair
+    // whose stored set fell short gets its second run, so the asynchronous mode keeps k_rows_re -- and not that second run itself.
+    f.qstore = f.pruned && a.listed && a.qstore && a.over_list;
+    f.takeback = f.qstore && spectral; // (k_qstore_takeback corrects the spectral form's mode counters)
+    f.fwd = a.pool ? ASX_FWD_POOL : a.rlayout ? ASX_FWD_REAL : ASX_FWD_PACKED;
+    f.rows = !a.rlayout ? ASX_ROWS_PACKED : f.pruned ? ASX_ROWS_ENERGY : a.pool ? ASX_ROWS_LISTED : ASX_ROWS_PLAIN;
+    return f;
+}

@@ -55,3 +55,46 @@ std::vector<int> asx_position_table(const AsxStages &st); // pos[k] = slot of X[
 // AsxRCols, 1 AsxRRows, 2 AsxPCols, 3 AsxPRows; false, and a first int of -1: the list has no such entry
 bool asx_kernel_table_spell(int list, int index, int *out);
 constexpr int ASX_KERNEL_ENTRY_CAP = 32; // ints per entry a caller of the diagnostic exports provides (hipxcorr.py: KERNEL_ENTRY_CAP)
+
+// The form of a launch group: what run_group (asx_api.hip) launches for it, decided once from values alone ("The form
+// of a launch group"; tabled without a device by tests/test_group_form.py through asx_planmath_group_form).
+// The ask: what run_group knows before it launches anything.
+struct AsxGroupAsk {
+    // the plan
+    bool rlayout = false;        // a real-column plan (else packed)
+    bool plan_prune = false;     // asx_plan_set_prune
+    bool plan_spectral = false;  // asx_plan_set_pearson
+    bool band_sums = false;      // the peak workspace in use has band sums (AsxPeakWs::band)
+    bool over_list = false;      // ... and an overflow list (AsxPeakWs::over_list)
+    // the call
+    bool f32_inputs = false;     // the exact passes read float32 (TIn)
+    bool f32_abi = false;        // GroupOpts::f32_abi
+    bool listed = false;         // GroupOpts::listed
+    bool r_out = false;          // r of every lag is asked for
+    bool own_lists = false;      // the group runs on lists of its own (GroupOpts::pk: the second look)
+    int k = 1;                   // top-k passes
+    int search = AsxSearch::ALL; // pass 1's AsxSearch::Kind
+    AsxWeight weight = ASX_W_NONE;
+    bool pool = false;           // a pool group
+    int bc = 0;                  // broadcast operands (bit 0: source, bit 1: sample)
+    bool qstore = false;         // GroupOpts::qstore
+};
+enum AsxFwdForm { ASX_FWD_POOL, ASX_FWD_REAL, ASX_FWD_PACKED }; // pool resolve; k_fwd_cols_r (+ k_bcast_aux per bit of bc); k_fwd_cols
+enum AsxTail { ASX_TAIL_PHAT, ASX_TAIL_DIRECT, ASX_TAIL_SPECTRAL };
+struct AsxGroupForm {
+    AsxFwdForm fwd;
+    AsxRowFlavour rows;
+    AsxWeight weight;            // beside the row flavour: PHAT and pruning exclude each other
+    int bc;                      // the form of the plain row flavour
+    bool pruned;                 // the pruned pair of passes in place of the inverse column pass (rows == ASX_ROWS_ENERGY on a real-column plan)
+    AsxTail tail;
+    bool appends;                // k_finalize may append to the overflow list
+    // Partial storing of Q may be asked for: asx_qstore_rows, which asks the device, then says how many predictor rows -- more than
+    // none: k_rows_rm in place of k_rows_re, and k_qstore_takeback behind the Pearson kernels when `takeback`
+    bool qstore;
+    bool takeback;
+};
+AsxGroupForm asx_group_form(const AsxGroupAsk &a);
+// the diagnostic export's arrays: the ask's fields in the order above as ints, and {fwd, rows, weight, bc, pruned, tail, appends,
+// qstore, takeback}
+constexpr int ASX_GROUP_ASK_INTS = 16, ASX_GROUP_FORM_INTS = 9;

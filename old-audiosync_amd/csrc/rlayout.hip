@@ -632,7 +632,7 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rm(
                                                           list);
 }
 
-// The row pass of a PHAT group (asx_launch_rows_r, AsxSpectra::weight == ASX_W_PHAT): k_rows_r<S, NT, TWO, BC> with the whitened product
+// The row pass of a PHAT group (asx_launch_rows_r, weight ASX_W_PHAT): k_rows_r<S, NT, TWO, BC> with the whitened product
 // (PHAT above).  A kernel name of its own, like k_rows_re: the twelve k_rows_r instances stay the kernels they were.
 template <class S, int NT, bool TWO, int BC>
 __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rp(const RArgs P, const float2 *__restrict__ cx,
@@ -642,7 +642,7 @@ __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rp(
     rows_r_body<S, NT, TWO, BC, false, true>(P, cx, cy, qo, nrows, (BC & 1) ? 0 : pair_pitch, (BC & 2) ? 0 : pair_pitch, pair_pitch, W);
 }
 
-// The row pass of a banded PHAT group (AsxSpectra::weight == ASX_W_PHAT_BAND): k_rows_rp<S, NT, TWO, BC> that lets only the bins of
+// The row pass of a banded PHAT group (weight ASX_W_PHAT_BAND): k_rows_rp<S, NT, TWO, BC> that lets only the bins of
 // `band` vote (BAND above).  Again a kernel name of its own: the k_rows_r and k_rows_rp instances stay the kernels they were.
 template <class S, int NT, bool TWO, int BC>
 __global__ __launch_bounds__(TWO ? 2 * NT : NT, ASX_ROWSR_WAVES) void k_rows_rb(const RArgs P, const float2 *__restrict__ cx,
@@ -1510,59 +1510,63 @@ static void launch_rows_r(K kernel, const AsxDev &P, int nt, const AsxSpectra &C
                        (const float2 *)C.cx, (const float2 *)C.cy, q, nrows, (size_t)nrows * (size_t)P.M2, W, extra...);
 }
 
-// The row pass of a group whose spectra are C, which decides the flavour: k_rows_re (plus the tile energies C.prune->eng) when the
-// group is in scope for pruning, k_rows_rl (C_x / C_y at the pairs' bank slots) in a pool group, else k_rows_r in the broadcast form
-// C.bc -- or, in a PHAT group (C.weight; never pruned), k_rows_rp in that form, or k_rows_rb with C.fband when only a band votes; in a
-// PHAT group that is a pool group their listed forms, k_rows_rlp and k_rows_rlb.  The operands that are not broadcast and q have the
-// group workspace's pair pitch.
-void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s)
+// The row pass of a group whose spectra are C, in the flavour its form names (asx_group_form; never ASX_ROWS_PACKED here): k_rows_re
+// (plus the tile energies U->eng) for the pruned pass, k_rows_rl (C_x / C_y at the pairs' bank slots) in a pool group, else k_rows_r in
+// the broadcast form C.bc -- or, weighted, k_rows_rp in that form, or k_rows_rb with fband when only a band votes, and in a pool group
+// their listed forms, k_rows_rlp and k_rows_rlb.  The operands that are not broadcast and q have the group workspace's pair pitch.
+void asx_launch_rows_r(const AsxDev &P, const AsxSpectra &C, AsxRowFlavour rows, AsxWeight weight, const AsxBand &fband, const AsxPrune *U,
+                       float2 *q, const AsxPeakWs &W, int npairs, hipStream_t s)
 {
     asx_with_entry(AsxRRows{}, P.krows, [&](auto e) {
         using S = typename decltype(e)::sched;
         constexpr int NT = e.nt, nt = e.two ? 2 * NT : NT;
         constexpr bool TWO = e.two;
-        if (C.weight == ASX_W_PHAT_BAND && C.pl) launch_rows_r(k_rows_rlb<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl, C.fband);
-        else if (C.weight == ASX_W_PHAT && C.pl) launch_rows_r(k_rows_rlp<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl);
-        else if (C.weight == ASX_W_PHAT_BAND)
-            switch (C.bc) {
-            case 0: launch_rows_r(k_rows_rb<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s, C.fband); break;
-            case 1: launch_rows_r(k_rows_rb<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s, C.fband); break;
-            case 2: launch_rows_r(k_rows_rb<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s, C.fband); break;
-            default: launch_rows_r(k_rows_rb<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s, C.fband); break;
-            }
-        else if (C.weight == ASX_W_PHAT)
-            switch (C.bc) {
-            case 0: launch_rows_r(k_rows_rp<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s); break;
-            case 1: launch_rows_r(k_rows_rp<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s); break;
-            case 2: launch_rows_r(k_rows_rp<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s); break;
-            default: launch_rows_r(k_rows_rp<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s); break;
-            }
-        else if (C.prune && C.prune->list) {
+        switch (rows) {
+        case ASX_ROWS_ENERGY:
+            if (!U->q_rows) launch_rows_r(k_rows_re<S, NT, TWO>, P, nt, C, q, W, npairs, s, U->eng);
             // partial storing (run_group asked asx_qstore_rows): launch A, the predictor rows, stores everything and leaves their
             // energies; k_q_predict states each pair's list; launch B, the other rows, stores the listed tiles
-            if constexpr (TWO) {
-                const AsxPrune &U = *C.prune;
-                const int nrows = P.M1 + 1, r0 = U.q_rows, a = U.q_row_a;
-                auto rows = [&](AsxRowRun run, const unsigned long long *list) {
+            else if constexpr (TWO) {
+                const int nrows = P.M1 + 1, r0 = U->q_rows, a = U->q_row_a;
+                auto part = [&](AsxRowRun run, const unsigned long long *list) {
                     hipLaunchKernelGGL((k_rows_rm<S, NT, TWO>), dim3((unsigned)run.count * (unsigned)npairs), dim3(nt),
                                        (size_t)P.M2 * sizeof(float4), s, rargs_of(P), (const float2 *)C.cx, (const float2 *)C.cy, q, nrows,
-                                       (size_t)nrows * (size_t)P.M2, W, U.eng, run, list);
+                                       (size_t)nrows * (size_t)P.M2, W, U->eng, run, list);
                 };
-                rows(AsxRowRun{ 0, r0, a }, nullptr);
-                hipLaunchKernelGGL(k_q_predict, dim3(npairs), dim3(256), 0, s, U.eng, nrows, P.ntiles, a, r0, (double)ASX_QSTORE_C, U.list,
-                                   U.qstats);
-                rows(AsxRowRun{ a, nrows - r0, r0 }, U.list);
+                part(AsxRowRun{ 0, r0, a }, nullptr);
+                hipLaunchKernelGGL(k_q_predict, dim3(npairs), dim3(256), 0, s, U->eng, nrows, P.ntiles, a, r0, (double)ASX_QSTORE_C, U->list,
+                                   U->qstats);
+                part(AsxRowRun{ a, nrows - r0, r0 }, U->list);
             }
+            break;
+        case ASX_ROWS_LISTED:
+            if (weight == ASX_W_PHAT_BAND) launch_rows_r(k_rows_rlb<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl, fband);
+            else if (weight == ASX_W_PHAT) launch_rows_r(k_rows_rlp<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl);
+            else launch_rows_r(k_rows_rl<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl);
+            break;
+        default:
+            if (weight == ASX_W_PHAT_BAND)
+                switch (C.bc) {
+                case 0: launch_rows_r(k_rows_rb<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s, fband); break;
+                case 1: launch_rows_r(k_rows_rb<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s, fband); break;
+                case 2: launch_rows_r(k_rows_rb<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s, fband); break;
+                default: launch_rows_r(k_rows_rb<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s, fband); break;
+                }
+            else if (weight == ASX_W_PHAT)
+                switch (C.bc) {
+                case 0: launch_rows_r(k_rows_rp<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s); break;
+                case 1: launch_rows_r(k_rows_rp<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s); break;
+                case 2: launch_rows_r(k_rows_rp<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s); break;
+                default: launch_rows_r(k_rows_rp<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s); break;
+                }
+            else
+                switch (C.bc) {
+                case 0: launch_rows_r(k_rows_r<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s); break;
+                case 1: launch_rows_r(k_rows_r<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s); break;
+                case 2: launch_rows_r(k_rows_r<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s); break;
+                default: launch_rows_r(k_rows_r<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s); break;
+                }
         }
-        else if (C.prune) launch_rows_r(k_rows_re<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.prune->eng);
-        else if (C.pl) launch_rows_r(k_rows_rl<S, NT, TWO>, P, nt, C, q, W, npairs, s, C.pl);
-        else
-            switch (C.bc) {
-            case 0: launch_rows_r(k_rows_r<S, NT, TWO, 0>, P, nt, C, q, W, npairs, s); break;
-            case 1: launch_rows_r(k_rows_r<S, NT, TWO, 1>, P, nt, C, q, W, npairs, s); break;
-            case 2: launch_rows_r(k_rows_r<S, NT, TWO, 2>, P, nt, C, q, W, npairs, s); break;
-            default: launch_rows_r(k_rows_r<S, NT, TWO, 3>, P, nt, C, q, W, npairs, s); break;
-            }
     });
 }
 
@@ -1700,8 +1704,8 @@ static void launch_inv_rq(const AsxDev &P, const float2 *q, const AsxPeakWs &W, 
                        resident_blocks((const void *)k2, NT, lds), AsxSelPrune<false>{ U.best, U.skip, U.list });
 }
 
-// The inverse column pass of a group: U null, the flavour the search asks for; U the lane's prune workspace (a group in scope for
-// pruning: every lag competes, no r_out, and k_rows_re has left U->eng), the pruned pass.
+// The inverse column pass of a group: U null, the flavour the search asks for; U the AsxPrune of a pruned group (every lag competes,
+// no r_out, and the row pass has left U->eng), the pruned pass.
 void asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W, float *r_out, int npairs, hipStream_t s,
                            const AsxSearch &search, const AsxPrune *U)
 {

@@ -104,6 +104,7 @@ _DIAGNOSTIC_SIGNATURES = {
     "asx_planmath_candidates": (_int, [_sz, _sz, _str, _sz]),
     "asx_planmath_kernels": (_int, [_sz, _str, c_intp, c_intp, c_intp]),
     "asx_planmath_kernel_table": (_int, [_int, _int, c_intp]),
+    "asx_planmath_group_form": (_int, [c_intp, _int, c_intp, _int]),
     "asx_plan_debug_kernels": (_int, [_vp, c_intp, c_intp, c_intp]),
     "asx_plan_debug_bank": (_int, [_vp, _u64p, _u64p, _u64p]),
     "asx_plan_debug_prune": (_int, [_vp, _sz, c_f32p, c_intp, _sz]),
@@ -243,6 +244,26 @@ def planmath_kernels(sample_len, split=None):
     """host-only: the kernels the plan of sample_len would run under the current environment (no GPU needed)."""
     f = lib().asx_planmath_kernels
     return _kernel_choice(lambda *a: f(sample_len, _split_arg(split), *a))
+
+
+# a launch group's ask and form as csrc/plan_math.h orders them (AsxGroupAsk, AsxGroupForm)
+GROUP_ASK = ("rlayout", "plan_prune", "plan_spectral", "band_sums", "over_list", "f32_inputs", "f32_abi", "listed", "r_out",
+             "own_lists", "k", "search", "weight", "pool", "bc", "qstore")
+GROUP_FORM = ("fwd", "rows", "weight", "bc", "pruned", "tail", "appends", "qstore", "takeback")
+GROUP_ENUMS = {"search": ("all", "window", "rows", "topk"), "weight": ("none", "phat", "phat-band"),
+               "fwd": ("pool", "real-column", "packed"), "rows": ("packed", "plain", "energy", "listed"),
+               "tail": ("phat", "direct", "spectral")}
+
+
+def planmath_group_form(**ask):
+    """host-only: what run_group launches for a group (csrc/plan_math.cpp: asx_group_form).  ask: every name of GROUP_ASK -- bools,
+    k and bc ints, search and weight by the names of GROUP_ENUMS; returns the dict of GROUP_FORM, its enums by name too."""
+    if set(ask) != set(GROUP_ASK):
+        raise ValueError("planmath_group_form: the ask is %s" % (GROUP_ASK,))
+    a = (ctypes.c_int * len(GROUP_ASK))(*(GROUP_ENUMS[n].index(ask[n]) if n in GROUP_ENUMS else int(ask[n]) for n in GROUP_ASK))
+    out = (ctypes.c_int * len(GROUP_FORM))()
+    _check(lib().asx_planmath_group_form(a, len(a), out, len(out)))
+    return {n: GROUP_ENUMS[n][v] if n in GROUP_ENUMS else v if n == "bc" else bool(v) for n, v in zip(GROUP_FORM, out)}
 
 
 def planmath_candidates(sample_len, max_count=16):
