@@ -41,8 +41,15 @@
 //     c2r transform of length 2 M1 <= 1200 delivers a column whose 2-norm is off by at most C eps log2(2 M1) of it -- the worst-case
 //     constant of one transform is ~1 (a third of the three transforms' ~3 in ASX_BOUND_C's note), taken as ASX_BOUND_C = 4 here as
 //     there: 4 * 10.3 = 41 eps, the tangling's few roundings included.
-// 43 eps = 5.1e-6 = 2^-17.6.  The bound has a factor 1.8 to spare on the generator's pairs (the second-largest bound is <= 0.56 of the
-// peak), so the factor is rounded up generously: 2^-14, twelve times what the derivation asks for.
+//   a block of k_rows_rm whose pair has a list (rlayout.hip: ASX_QTW_LATE) squares S, the output of the last radix-2 combine, and not
+//     the Q = S conj(g) that is stored, g the four-step twiddle as the kernel forms it: up to three table pairs (w_F^(k1 j), w_F^(k1 n),
+//     leg[t]), six entries each rounded once per component, whose modulus is 1 to within u = 2^-24 each, joined by up to five complex
+//     products, plus the product S conj(g) itself -- six products at sqrt(5) u each at the most (2 u each as fused here).  |Q| and |S|
+//     therefore differ by at most (6 + 6 sqrt(5)) u = 19.4 u relatively, |Q|^2 and |S|^2 by 39 u: 20 eps on E, 10 eps on its root,
+//     in either direction.  (Typical: a few u; the roundings do not line up.)
+// 43 + 10 = 53 eps = 6.3e-6 = 2^-17.3 (43 eps = 2^-17.6 for the blocks that square Q itself).  The bound has a factor 1.8 to spare on
+// the generator's pairs (the second-largest bound is <= 0.56 of the peak), so the factor is rounded up generously: 2^-14 = 512 eps,
+// nearly ten times what the derivation asks for; the late twiddle fits inside it and does not change it.
 // All of the above are RELATIVE roundings.  |Q|^2 = re * re + im * im can also underflow: each of the two products loses up to
 // FLT_MIN absolutely when it is flushed or denormal (r itself, a sum of 2 M1 such Q, is then still an ordinary float32: tracks of
 // amplitude 1e-16 give |r| ~ 5e-23 and every |Q|^2 = 0).  A tile's energy is a sum of n = 16 (M1 + 1) terms, so its absolute error

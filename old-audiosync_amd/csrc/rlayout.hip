@@ -176,6 +176,13 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 #ifndef ASX_ROWS_EARLY
 #define ASX_ROWS_EARLY 14
 #endif
+// k_rows_rm, a block of a pair with a list: 1 = the conjugate four-step twiddle is applied by the copy wave, to the <= 64 values that
+// leave the block, and the tile energies are those of the untwiddled values (MSK below); 0 = by the store phase, to all 2400 (the
+// form partial storing came with: for same-box A/B builds).  Measured (profiles/qtw_late/, alternating traces, three runs each):
+// launch B 875 -> 848 us on one box, 895 -> 853 on another.
+#ifndef ASX_QTW_LATE
+#define ASX_QTW_LATE 1
+#endif
 #ifndef ASX_ROWSR_WAVES
 #define ASX_ROWSR_WAVES 4 // waves per SIMD the register allocation must allow: 8 blocks of 2 waves per CU
 #endif
@@ -211,9 +218,17 @@ __device__ __forceinline__ void st_f2(float2 *p, float2 v, bool nt)
 //   a four-way bank conflict on these stores and loads, a few hundred LDS cycles per block.)
 //   MSK (k_rows_rm, partial storing of Q; with ENG, the two-half form only): the launch holds some of a pair's rows (AsxRowRun), and a
 //   pair may come with a list of up to four column tiles (asx_internal.h: ASX_Q_ALL), the only ones the pruned pass will read.  A block
-//   of such a pair keeps its Q values in LDS -- {re, im} in front of the energy in slot c, written by the thread that alone has just
+//   of such a pair keeps its values in LDS -- {re, im} in front of the energy in slot c, written by the thread that alone has just
 //   read that slot -- and behind the fifth barrier one wave copies the listed tiles to Q, sixteen lanes a tile.  Without a list the
-//   store phase is ENG's.  The expressions that form Q and |Q|^2 are the same in both: the stored bits are k_rows_re's.
+//   store phase is ENG's.  What such a block keeps in LDS is the output of the last radix-2 combine, S = A +- conj(w_M2^i) B, WITHOUT
+//   the conjugate four-step twiddle (ASX_QTW_LATE): of the row's 2400 values at most 64 leave the block, the others are only squared
+//   for the tile energies, and the factor has modulus 1 -- |S|^2 stands for |Q|^2 (asx_internal.h, ASX_PRUNE_DELTA, says what that
+//   costs the bound).  The store phase of a listed block therefore needs neither w_F^(k1 j) nor leg[]: its threads skip those
+//   look-ups, and a lane of the copy wave, which holds column c = i + NS * upper, i = j + Q0 t, asks for w_F^(k1 j) of ITS column
+//   instead -- behind the row loads, because which of the two a thread asks for hangs on list[pair], and a wait for that word must
+//   not stand in front of the rows; the values are not needed before the block's end.  The lane then forms Q with the functions
+//   of the register path on the same operand values, cmul(lo, hi), times wh for the upper half, times leg[t] for t > 0, mulwc: the
+//   stored bits are k_rows_re's.
 //   PHAT (k_rows_rp, asx_xcorr_phat_f32_dev): the phase transform.  Every bin of the product X conj(Y) is divided by its magnitude in
 //   the registers where it is formed, between the product and the first inverse butterfly (phat_unit below), so that the inverse
 //   passes deliver r_phat, whose every frequency has one vote.  Nothing of the float32 error bound holds for a whitened spectrum:
@@ -289,6 +304,13 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
     unsigned long long wl = ASX_Q_ALL;
     if constexpr (MSK) { if (list) wl = list[pair]; }
     [[maybe_unused]] const bool part = MSK && wl != ASX_Q_ALL;
+    constexpr bool LATE = MSK && ASX_QTW_LATE != 0; // a listed block twiddles only what it stores (see MSK above)
+    static_assert(!LATE || (ASX_ROWS_EARLY & 2) != 0, "ASX_QTW_LATE: the store phase's look-ups are the early ones");
+    // the column of a listed tile that lane tid of the copy wave (tid < 64) holds; -1: an unused entry of the list names no tile
+    [[maybe_unused]] auto copy_col = [&]() __attribute__((always_inline)) {
+        const unsigned t = (unsigned)(wl >> (16 * (tid >> 4))) & 0xFFFFu;
+        return t < (unsigned)(M2 / ASX_PRUNE_T) ? (int)t * ASX_PRUNE_T + (tid & 15) : -1;
+    };
     const size_t row = (size_t)RWS_PAIR(pair) * pitch_q + (size_t)k1 * M2;
     size_t rowx, rowy;
     if constexpr ((BC & 4) != 0) {
@@ -326,10 +348,12 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
     // the look-ups of the two-half form's store phase (threads [0, Q0): butterfly j = tid)
     float2 tail_w2 = make_float2(1.f, 0.f), tail_lo = tail_w2, tail_hi = tail_w2;
     if (TWO && (ASX_ROWS_EARLY & 2) && tid < Q0) {
-        const uint32_t p = k1 * (uint32_t)tid;
+        [[maybe_unused]] const uint32_t p = k1 * (uint32_t)tid;
         tail_w2 = P.tw2[tid];
-        tail_lo = P.tw_lo[p & (ASX_TW_LO - 1u)];
-        tail_hi = P.tw_hi[p >> ASX_TW_LOG];
+        if constexpr (!LATE) { // (LATE: behind the row loads, see there)
+            tail_lo = P.tw_lo[p & (ASX_TW_LO - 1u)];
+            tail_hi = P.tw_hi[p >> ASX_TW_LOG];
+        }
     }
     // (bit 2 of ASX_ROWS_EARLY: the two-half form's w_M2^(2q), w_M2^(2q+1) of every load step asked for HERE, in front of the rows, instead
     // of inside the step behind the barrier -- a table load and the wait for it between the arrival of the rows and their first use)
@@ -381,7 +405,22 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
     const int ul = lane / LPU, jl = lane - ul * LPU;
     const int j1c = jl < R2 ? jl : 0;
     const float2 s1w1 = P.tw2[TWS * K1.twmul * j1c], s1w4 = P.tw2[TWS * (R1 > 4 ? 4 : 1) * K1.twmul * j1c];
-    if constexpr (LOOKUPS_FIRST) { issue_row_loads(); publish_step_and_leg(); }
+    if constexpr (LOOKUPS_FIRST) issue_row_loads();
+    if constexpr (LATE) {
+        // w_F^(k1 j): of the thread's own butterfly j = tid, or in a listed block of the column the lane will copy.  list[pair] decides,
+        // so these two look-ups stand behind the row loads; they are used behind the block's last barrier.
+        int jq = tid < Q0 ? tid : -1;
+        if (part) {
+            const int c = tid < 64 ? copy_col() : -1;
+            jq = c < 0 ? -1 : (c % NS) % Q0;
+        }
+        if (jq >= 0) {
+            const uint32_t p = k1 * (uint32_t)jq;
+            tail_lo = P.tw_lo[p & (ASX_TW_LO - 1u)];
+            tail_hi = P.tw_hi[p >> ASX_TW_LOG];
+        }
+    }
+    if constexpr (LOOKUPS_FIRST) publish_step_and_leg();
     RSTAMP(0, task, 0);
 #ifdef ASX_STAMPS
     if (P.stamps && P.stamp_kernel == 0 && threadIdx.x == 0) { P.stamps[(size_t)task * 8 + 6] = t_entry; P.stamps[(size_t)task * 8 + 7] = w_entry; }
@@ -536,12 +575,20 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
             const float2 fbh = cmul(fa, wh);                  // w_F^(k1 (j + n))
             // PART (MSK, a pair with a list): Q stays in LDS, {re, im} in front of the energy in slot c -- the slots j + Q0 t and
             // NS + j + Q0 t are exactly the ones this thread alone has just read, so no barrier is needed -- and the listed tiles leave
-            // behind the fifth barrier (below).  Otherwise Q leaves from registers, as ever.
+            // behind the fifth barrier (below).  Otherwise Q leaves from registers, as ever.  LATE: what stays is A +- Bw, the
+            // twiddle is the copy wave's; fa and fbh are then not this butterfly's and not used.
             auto leave = [&](auto PART) __attribute__((always_inline)) {
                 static_for<0, R0>([&](auto T) __attribute__((always_inline)) {
                     constexpr int t = decltype(T)::value;
                     const Cx1 A = Cx1{ v[t].re.x, v[t].im.x };
                     const Cx1 Bw = mul_root<2 * R0, t, true>(mulwc(Cx1{ v[t].re.y, v[t].im.y }, w2)); // conj(w_M2^(j + Q0 t)) B
+                    if constexpr (decltype(PART)::value && LATE) {
+                        const Cx1 sp = A + Bw, sm = A - Bw;
+                        ej[4 * (t * Q0) - 2] = sp.re; ej[4 * (t * Q0) - 1] = sp.im;
+                        ej[4 * (NS + t * Q0) - 2] = sm.re; ej[4 * (NS + t * Q0) - 1] = sm.im;
+                        eng_put(ej, t * Q0, sp); eng_put(ej, NS + t * Q0, sm);
+                        return;
+                    }
                     const float2 lg = leg[t];
                     const Cx1 y = mulwc(A + Bw, t == 0 ? fa : cmul(fa, lg));
                     const Cx1 z = mulwc(A - Bw, t == 0 ? fbh : cmul(fbh, lg));
@@ -584,11 +631,20 @@ __device__ __forceinline__ void rows_r_body(const RArgs P, const float2 *__restr
             // the listed tiles from LDS to Q: one wave, sixteen lanes a tile, 8 bytes per lane, 128 bytes per tile row (an unused
             // entry of the list names no tile)
             if (part && tid < 64) {
-                const unsigned t = (unsigned)(wl >> (16 * (tid >> 4))) & 0xFFFFu;
-                if (t < (unsigned)NTILE) {
-                    const int c = (int)t * ASX_PRUNE_T + (tid & 15);
+                const int c = copy_col();
+                if (c >= 0) {
                     const float *sl = reinterpret_cast<const float *>(asx_lds_r) + 4 * c;
-                    st_f2(go + c, make_float2(sl[0], sl[1]), ASX_RNT & 8);
+                    if constexpr (LATE) {
+                        // the register path's expressions for column c = j + Q0 t (+ NS): y = mulwc(A + Bw, t == 0 ? fa : cmul(fa, leg[t])),
+                        // z the same with fbh = cmul(fa, wh) for fa
+                        const int i = c >= NS ? c - NS : c, t = i / Q0;
+                        const float2 fa = cmul(tail_lo, tail_hi); // w_F^(k1 j), j = i mod Q0: asked for at the top
+                        const float2 f = c >= NS ? cmul(fa, wh) : fa;
+                        const Cx1 y = mulwc(Cx1{ sl[0], sl[1] }, t == 0 ? f : cmul(f, leg[t]));
+                        st_f2(go + c, make_float2(y.re, y.im), ASX_RNT & 8);
+                    } else {
+                        st_f2(go + c, make_float2(sl[0], sl[1]), ASX_RNT & 8);
+                    }
                 }
             }
         }
