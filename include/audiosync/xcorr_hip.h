@@ -33,8 +33,8 @@
  *   ret = -3 (asx_xcorr_topk_f32_dev and asx_xcorr_pool_topk_f32_dev only): no lag is left for
  *   this entry of the pair (its window minus the zones around the earlier entries is empty);
  *   lag = 0 and coef = NaN.
- *   ret = -4 (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev and asx_xcorr_pool_phat_f32_dev
- *   only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
+ *   ret = -4 (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_pool_phat_f32_dev and
+ *   asx_xcorr_pool_phat_sub_f32_dev only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
  *   form: in all k entries of the pair).  It takes precedence over -2 and -3.
  */
 #ifndef AUDIOSYNC_XCORR_HIP_H
@@ -375,6 +375,40 @@ int asx_xcorr_phat_band_f32_dev(asx_plan *plan, const float *d_source, size_t so
                                 int64_t bin_lo, int64_t bin_hi,
                                 int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
 
+/* Sub-sample GCC-PHAT: asx_xcorr_phat_band_f32_dev, plus the curve around each pair's peak and a fractional lag.  A delay is
+ * rarely a whole number of frames, and the shape of the peak -- its width, its side lobes -- says how far to trust it.
+ *   Everything asx_xcorr_phat_band_f32_dev says holds: inputs, strides, broadcast, the layout rule, windows (rows or the plan's), the
+ * band and its vote count V (the full band [0, N] runs the plain PHAT kernels, V = F), every refusal, asynchronous whatever
+ * asx_plan_set_exact says, no counter touched, nothing allocated.  (lag, coef, peak, ret) are bit for bit that call's results for
+ * every pair: what is added runs behind it and only reads.
+ *   New arguments.  1 <= half_width <= ASX_NEAR_MAX; d_frac must not be NULL; d_near may be.  Anything else returns -1 with nothing
+ * launched and the outputs untouched.
+ *   d_near.  With h = half_width and p_i the index of pair i's peak in r_phat (lag l >= 0 is index l, lag l < 0 index 2N + l),
+ * d_near[i * (2h + 1) + (d + h)] = r_phat[(p_i + d) mod 2N] / V for d = -h .. h: signed, 2h + 1 doubles per pair.  Neighbours are
+ * taken in index space, circularly: index 2N - 1 (lag -1) sits beside index 0, and index N (lag -N) beside index N - 1.  The
+ * neighbourhood does not depend on the window: lags outside the pair's window are reported like any other, and one of them may
+ * exceed the peak.  Each value is a float64 sum over one column of the group's float32 whitened spectrum Q' (DESIGN.md), so the
+ * centre entry is the float64 sum over the same float32 Q' from which peak's float32 inverse transform came: |centre| may differ
+ * from peak by the float32 rounding of that transform (at most 2e-7 of full scale, tests/test_gpu_phat_sub.py).
+ *   d_frac.  d_frac[i] is the vertex of the parabola through the three centre values y-, y0, y+ (d = -1, 0, 1), all in float64 and
+ * in this order: s = -1 when y0 < 0, else +1; a = s y-, b = s y0, c = s y+; den = (a - 2 b) + c.  frac = NaN when any of the three
+ * is NaN; frac = 0 when den >= 0 (a flat top, a silent pair); otherwise frac = 0.5 (a - c) / den, clamped to [-0.5, 0.5].  The
+ * delay estimate is lag + frac frames.
+ *   The parabola is biased on a sinc-shaped peak: a full-band pure delay of a quarter frame past a whole lag gives frac of about
+ * 0.14, and 0.4 gives about 0.29 (the table: DESIGN.md).  That is why d_near is offered: a caller fits the interpolator of their
+ * choice over 2h + 1 points.
+ *   Special pairs.  A silent pair: peak 0, every near entry 0, frac 0.  A pair with ret -2 gets NaN in frac and in all of its near
+ * entries; the other pairs are untouched.
+ *   Cost: one small kernel per launch group, (M1 + 1)(2h + 1) reads of 8 bytes per pair.  Measured on full groups: 1 % (h = 1) to
+ * 4 % (h = 8) of the banded call at N = 144 000, 0.5 % to 1.3 % at N = 1 440 000. */
+#define ASX_NEAR_MAX 8
+int asx_xcorr_phat_sub_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                               const float *d_sample, size_t sample_stride,
+                               const int64_t *d_windows, size_t window_stride, size_t batch,
+                               int64_t bin_lo, int64_t bin_hi, int half_width,
+                               int64_t *d_lag, double *d_coef, double *d_peak,
+                               double *d_frac, double *d_near, int32_t *d_ret, void *stream);
+
 /* The bins of the band [f_lo_hz, f_hi_hz] for a plan of sample_len = N at sample_rate: bin_lo = ceil(f_lo 2N / rate), bin_hi =
  * min(N, floor(f_hi 2N / rate)) (a band that reaches past the Nyquist frequency ends there).  Host arithmetic, no device.  Returns
  * 0, or -1 with the outputs untouched for a rate that is not positive, f_lo < 0, f_lo > f_hi, a NaN, or a band that holds no bin. */
@@ -478,6 +512,19 @@ int asx_xcorr_pool_phat_f32_dev(asx_plan *plan,
                                 const int64_t *d_windows, size_t window_stride,
                                 size_t batch, int64_t bin_lo, int64_t bin_hi,
                                 int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
+/* ... with the curve around each pair's peak and a fractional lag: asx_xcorr_pool_phat_f32_dev's arguments up to bin_hi and
+ * everything that call says (the pools, d_pairs, windows, the band, the bank, every refusal; (lag, coef, peak, ret) bit for bit its
+ * results), then half_width, d_frac and d_near as asx_xcorr_phat_sub_f32_dev defines them, with the same two refusals.  A pair
+ * with ret -2 or -4 gets NaN in frac and in all of its near entries; the other pairs are untouched. */
+int asx_xcorr_pool_phat_sub_f32_dev(asx_plan *plan,
+                                    const float *d_sources, size_t source_stride, size_t nsources,
+                                    const float *d_samples, size_t sample_stride, size_t nsamples,
+                                    const int32_t *d_pairs,
+                                    const int64_t *d_windows, size_t window_stride,
+                                    size_t batch, int64_t bin_lo, int64_t bin_hi, int half_width,
+                                    int64_t *d_lag, double *d_coef, double *d_peak,
+                                    double *d_frac, double *d_near, int32_t *d_ret, void *stream);
 
 /* The batched variant over several GPUs of one node from ONE process (BASELINE.json north_star; no
  * reference equivalent): plans[i] was created on device i (any devices; all the same sample_len); the

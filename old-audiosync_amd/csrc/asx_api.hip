@@ -890,6 +890,15 @@ struct Topk {
     int64_t sep = 0;
 };
 
+// The peak's neighbourhood, which the sub-sample PHAT calls ask for (asx_xcorr_phat_sub_f32_dev): near, 2h + 1 values of r_phat / V
+// per pair around its peak (may be null), and frac, the parabolic vertex of the three centre values.  frac null: not asked for.
+struct Near {
+    double *frac = nullptr;
+    double *near = nullptr;
+    int h = 0;
+    Near at(size_t k) const { return { frac ? frac + k : nullptr, near ? near + k * (size_t)(2 * h + 1) : nullptr, h }; }
+};
+
 struct GroupOpts {
     static constexpr size_t no_marks = SIZE_MAX;
     size_t prof_group = 0;       // which group of the call the profiling events time (no_marks: none)
@@ -917,6 +926,7 @@ struct GroupOpts {
     AsxWeight weight = ASX_W_NONE;
     AsxBand fband{};
     bool qstore = true;          // partial storing of Q allowed (false: the second run of a pair whose stored set fell short)
+    Near near{};                 // a PHAT group: the group's places for the peak's neighbourhood (k_phat_near behind the tail), or none
 };
 
 // One group: g <= plan->group pairs, the first g of x, results to the first g of y.
@@ -1001,6 +1011,10 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
             asx_launch_phat_finalize(P, fin, W.seg, y.peak, form.weight == ASX_W_PHAT_BAND ? o.fband.votes(P.N) : (double)P.F, (int)g, s, find);
             if (first && mark(4)) return -1;
             asx_launch_pearson(in, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
+            // the peak's neighbourhood from the Q' this pass searched, around the index k_phat_finalize settled: it only reads
+            if (o.near.frac)
+                asx_launch_phat_near(P, q, W.seg, form.weight == ASX_W_PHAT_BAND ? o.fband.votes(P.N) : (double)P.F, o.near.h, find, pl,
+                                     o.near.frac, o.near.near, (int)g, s);
             return 0;
         }
         asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, find);
@@ -1224,7 +1238,7 @@ extern "C" int asx_plan_placement(asx_plan *p, double ms[2], int *kept)
 // A device-resident batch of float32 pairs, after the entry point's own checks.  A PHAT batch (weight) lists nothing, so it never reads
 // the overflow list: asynchronous whatever asx_plan_set_exact says.
 static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Results &y, hipStream_t s, const Topk &topk = {},
-                     AsxWeight weight = ASX_W_NONE, const AsxBand &band = {})
+                     AsxWeight weight = ASX_W_NONE, const AsxBand &band = {}, const Near &near = {})
 {
     prof_begin_call(p);
     const bool exact = p->exact && weight == ASX_W_NONE;
@@ -1249,7 +1263,7 @@ static int run_batch(asx_plan *p, const Pairs<float> &x, size_t batch, const Res
             hipStream_t ls = overlap ? p->lanes[lane].stream : s;
             if (run_group(p, x.at(done), g, y.at(done), ls,
                           { .prof_group = gi, .lane = lane, .pair_base = (uint32_t)(done - w0), .listed = exact, .topk = topk,
-                            .weight = weight, .fband = band }))
+                            .weight = weight, .fband = band, .near = near.at(done) }))
                 return -1;
         }
         if (overlap) {
@@ -1286,7 +1300,7 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
 // d_windows: null, or the per-pair windows (Pairs::win), window_stride rows apart.
 static int strided_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
                          size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, const Results &y, void *stream,
-                         const Topk &topk = {}, AsxWeight weight = ASX_W_NONE, const AsxBand &band = {})
+                         const Topk &topk = {}, AsxWeight weight = ASX_W_NONE, const AsxBand &band = {}, const Near &near = {})
 {
     PlanCall c(p, stream);
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
@@ -1317,7 +1331,7 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
         asx_launch_fwd_cols_r(P, (bc & 1) ? d_source : nullptr, 0, (bc & 2) ? d_sample : nullptr, 0, 0, 1, B, true, s);
     }
     return run_batch(p, Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, bc, d_windows, window_stride), batch, y, s,
-                     topk, weight, band);
+                     topk, weight, band, near);
 }
 
 extern "C" int asx_xcorr_strided_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
@@ -1377,6 +1391,39 @@ extern "C" int asx_xcorr_phat_band_f32_dev(asx_plan *p, const float *d_source, s
         return fail("%s: bins [%lld, %lld] are not a band inside [0, %zu]", fn, (long long)bin_lo, (long long)bin_hi, (size_t)p->host.N);
     return strided_batch(p, fn, d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch,
                          { d_lag, d_coef, d_ret, 1, d_peak }, stream, {}, weight, band);
+}
+
+// What the sub-sample PHAT calls add to their arguments: 1 <= half_width <= ASX_NEAR_MAX, d_frac not null (d_near may be), and a row
+// long enough to hold the neighbourhood (every real-column plan's is; a packed plan is refused by the PHAT rule behind this).
+static bool near_option(const asx_plan *p, const char *fn, int half_width, double *d_frac, double *d_near, Near &near)
+{
+    if (half_width < 1 || half_width > ASX_NEAR_MAX) { fail("%s: half_width = %d is not in [1, %d]", fn, half_width, ASX_NEAR_MAX); return false; }
+    if (!d_frac) { fail("%s: null argument (d_frac)", fn); return false; }
+    if (p->dev.rlayout == 1 && 2 * half_width + 1 > p->dev.M2) {
+        fail("%s: half_width = %d needs rows of at least %d columns, the plan's have %d", fn, half_width, 2 * half_width + 1, p->dev.M2);
+        return false;
+    }
+    near = Near{ d_frac, d_near, half_width };
+    return true;
+}
+
+// Sub-sample GCC-PHAT: asx_xcorr_phat_band_f32_dev, and behind each group's tail k_phat_near, which reads r_phat around the peak from
+// the group's Q' and writes d_near and d_frac.  The four other results are the banded call's: the same launches in front of it.
+extern "C" int asx_xcorr_phat_sub_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                          size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                          int64_t bin_lo, int64_t bin_hi, int half_width, int64_t *d_lag, double *d_coef, double *d_peak,
+                                          double *d_frac, double *d_near, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_phat_sub_f32_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_ret) return fail("%s: null argument", fn);
+    AsxWeight weight;
+    AsxBand band;
+    Near near;
+    if (!band_weight(p, bin_lo, bin_hi, weight, band))
+        return fail("%s: bins [%lld, %lld] are not a band inside [0, %zu]", fn, (long long)bin_lo, (long long)bin_hi, (size_t)p->host.N);
+    if (!near_option(p, fn, half_width, d_frac, d_near, near)) return -1;
+    return strided_batch(p, fn, d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch,
+                         { d_lag, d_coef, d_ret, 1, d_peak }, stream, {}, weight, band, near);
 }
 
 // one contiguous pair through a PHAT group (weight, band), r_phat of every lag (2N floats, unnormalised) to d_r; the plan's window
@@ -1475,7 +1522,7 @@ static int ensure_bank(asx_plan *p, const char *fn, size_t nsrc, size_t nsmp, hi
 static int pool_batch(asx_plan *p, const char *fn, const float *d_sources, size_t source_stride, size_t nsources, const float *d_samples,
                       size_t sample_stride, size_t nsamples, const int32_t *d_pairs, const int64_t *d_windows, size_t window_stride,
                       size_t batch, const Results &y, void *stream, const Topk &topk = {}, AsxWeight weight = ASX_W_NONE,
-                      const AsxBand &band = {})
+                      const AsxBand &band = {}, const Near &near = {})
 {
     if (!p || !d_sources || !d_samples || !y.coef || !y.ret) return fail("%s: null argument", fn);
     PlanCall c(p, stream);
@@ -1504,7 +1551,7 @@ static int pool_batch(asx_plan *p, const char *fn, const float *d_sources, size_
     p->bank.fills++;
     const PoolCall pool{ d_pairs, nsources, nsamples };
     return run_batch(p, Pairs<float>::pooled(&pool, d_sources, source_stride, d_samples, sample_stride, d_windows, window_stride), batch, y,
-                     s, topk, weight, band);
+                     s, topk, weight, band, near);
 }
 
 extern "C" int asx_xcorr_pool_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
@@ -1545,6 +1592,25 @@ extern "C" int asx_xcorr_pool_phat_f32_dev(asx_plan *p, const float *d_sources, 
         return fail("%s: bins [%lld, %lld] are not a band inside [0, %zu]", fn, (long long)bin_lo, (long long)bin_hi, (size_t)p->host.N);
     return pool_batch(p, fn, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows, window_stride,
                       batch, { d_lag, d_coef, d_ret, 1, d_peak }, stream, {}, weight, band);
+}
+
+// ... with the peak's neighbourhood: asx_xcorr_phat_sub_f32_dev's two outputs for the pool call's pairs
+extern "C" int asx_xcorr_pool_phat_sub_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                               const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                               const int64_t *d_windows, size_t window_stride, size_t batch, int64_t bin_lo,
+                                               int64_t bin_hi, int half_width, int64_t *d_lag, double *d_coef, double *d_peak,
+                                               double *d_frac, double *d_near, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_pool_phat_sub_f32_dev";
+    if (!p) return fail("%s: null argument", fn);
+    AsxWeight weight;
+    AsxBand band;
+    Near near;
+    if (!band_weight(p, bin_lo, bin_hi, weight, band))
+        return fail("%s: bins [%lld, %lld] are not a band inside [0, %zu]", fn, (long long)bin_lo, (long long)bin_hi, (size_t)p->host.N);
+    if (!near_option(p, fn, half_width, d_frac, d_near, near)) return -1;
+    return pool_batch(p, fn, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows, window_stride,
+                      batch, { d_lag, d_coef, d_ret, 1, d_peak }, stream, {}, weight, band, near);
 }
 
 // diagnostic (not in the public header): the bank's capacity in tracks and how many pool calls have filled it

@@ -582,6 +582,13 @@ void asx_launch_inv_cols_r(const AsxDev &P, const float2 *q, const AsxPeakWs &W,
 // that voted -- F, or AsxBand::votes in a banded group
 void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, double *peak, double f, int npairs, hipStream_t s,
                               const AsxSearch &q);
+// behind it, when the call asked for the peak's neighbourhood (asx_xcorr_phat_sub_f32_dev; rlayout.hip: k_phat_near): r_phat / f at
+// the 2h + 1 indices around seg[pair].peak from the group's whole Q' (q), to near[pair * (2h + 1) ..] (may be null), and the parabolic
+// vertex of the three centre values to frac[pair]; 1 <= h <= ASX_NEAR_MAX and 2h + 1 <= P.M2.  find: the pass's search, whose invalid
+// rows get NaN; pl: the pool group's records (null: no pool), whose invalid pairs get NaN.  It only reads what the group left.
+#define ASX_NEAR_MAX 8
+void asx_launch_phat_near(const AsxDev &P, const float2 *q, const AsxSeg *seg, double f, int h, const AsxSearch &find,
+                          const AsxPoolPair *pl, double *frac, double *near, int npairs, hipStream_t s);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 // pool calls: each pair's record (out) and its two slots' norm partials and band sums (band may be null) into the group's places

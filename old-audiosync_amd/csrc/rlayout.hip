@@ -1554,6 +1554,111 @@ __global__ __launch_bounds__(256) void k_phat_finalize(AsxPeakWs W, AsxSeg *__re
 }
 
 // ---------------------------------------------------------------------------
+// k_phat_near: grid (npairs), a block per pair.  Behind k_phat_finalize in the tail of a PHAT group whose call asked for it
+// (asx_xcorr_phat_sub_f32_dev): r_phat at the 2h + 1 indices around the pair's settled peak p = seg[pair].peak, straight from the
+// group's float32 Q', which is whole (a PHAT group is never pruned) -- rows u = 0 .. M1 at q + pair * pair_pitch + u * M2, columns in
+// natural order, as k_rows_rp wrote and k_inv_cols_r read them.  One lag idx = j1 * M2 + j2 is a sum down ONE column:
+//     r[idx] = Re Q[0][j2] + (-1)^j1 Re Q[M1][j2] + 2 sum_{0 < u < M1} Re( Q[u][j2] exp(+i pi u j1 / M1) )
+// (the c2r column step of k_inv_cols_r written out), and the neighbours in INDEX space, circularly over F = 2N, are the neighbouring
+// columns of the same rows; a step across a row end moves j1 by one (2 M1 - 1 -> 0 at index F - 1 -> 0).  2h + 1 <= M2 (the launcher's
+// callers check it), so the indices hold at most two values of j1 and a thread needs at most two twiddles per row, each from the
+// reduced integer (u * j1) mod 2 M1: sincospi of that over M1 is good to the last bits whatever M1 is.  Threads stride over the rows
+// and accumulate in float64; the block's sum is a fixed tree (lanes, then waves), so a pair's values do not depend on the batch.
+//   near[pair * (2h + 1) + e] = r[(p - h + e) mod F] / v, signed (near may be null); frac[pair] = the vertex of the parabola through
+// the three centre values, in float64 in the order the header states.  The window plays no part.  A pair whose row is not a window
+// (rows) or whose indices lie outside their pools (pl) gets NaN in all of them.  The kernel only reads what the group left.
+// ---------------------------------------------------------------------------
+#define ASX_NEAR_N (2 * ASX_NEAR_MAX + 1)
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__global__ __launch_bounds__(256) void k_phat_near(const float2 *__restrict__ q, size_t pair_pitch, const AsxSeg *__restrict__ seg,
+                                                    uint32_t N, int M1, int M2, double v, int h, const int64_t *__restrict__ rows,
+                                                    size_t rows_step, const AsxPoolPair *__restrict__ pl, double *__restrict__ frac,
+                                                    double *__restrict__ near)
+{
+    const size_t pair = blockIdx.x;
+    const int tid = threadIdx.x, n = 2 * h + 1;
+    __shared__ double red[4][ASX_NEAR_N];
+    __shared__ double y[ASX_NEAR_N];
+    bool valid = true;
+    if (rows) {
+        AsxWin z;
+        valid = asx_win_row(AsxWinRows{ rows, rows_step }, pair, N, z);
+    }
+    if (pl && (pl[pair].flags & ASX_POOL_INVALID)) valid = false;
+    if (!valid) { // (block-uniform: nobody is left at a barrier)
+        if (near && tid < n) near[pair * (size_t)n + tid] = (double)NAN;
+        if (tid == 0) frac[pair] = (double)NAN;
+        return;
+    }
+    const uint32_t F = 2u * N;
+    const uint32_t first = (seg[pair].peak % F + F - (uint32_t)h) % F; // index of entry 0
+    const uint32_t j1a = first / (uint32_t)M2, j2a = first - j1a * (uint32_t)M2;
+    const uint32_t j1b = j1a + 1u == 2u * (uint32_t)M1 ? 0u : j1a + 1u;  // behind the row end
+    const bool two = j2a + (uint32_t)n > (uint32_t)M2;
+    const float2 *in = q + RWS_PAIR(pair) * pair_pitch;
+    double acc[ASX_NEAR_N];
+#pragma unroll
+    for (int e = 0; e < ASX_NEAR_N; e++) acc[e] = 0.0;
+    for (int u = tid; u <= M1; u += 256) {
+        // the weights of Re Q and Im Q of row u at j1a and at j1b
+        double ca = 1.0, sa = 0.0, cb = 1.0, sb = 0.0;
+        if (u == M1) {
+            ca = (j1a & 1u) ? -1.0 : 1.0;
+            cb = (j1b & 1u) ? -1.0 : 1.0;
+        } else if (u != 0) {
+            sincospi((double)(((uint32_t)u * j1a) % (2u * (uint32_t)M1)) / (double)M1, &sa, &ca);
+            ca *= 2.0; sa *= 2.0;
+            if (two) {
+                sincospi((double)(((uint32_t)u * j1b) % (2u * (uint32_t)M1)) / (double)M1, &sb, &cb);
+                cb *= 2.0; sb *= 2.0;
+            }
+        }
+        const float2 *row = in + (size_t)u * (size_t)M2;
+#pragma unroll
+        for (int e = 0; e < ASX_NEAR_N; e++) {
+            if (e < n) {
+                const uint32_t c = j2a + (uint32_t)e;
+                const bool wrapped = c >= (uint32_t)M2;
+                const float2 x = row[wrapped ? c - (uint32_t)M2 : c];
+                acc[e] += (wrapped ? cb : ca) * (double)x.x - (wrapped ? sb : sa) * (double)x.y;
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < ASX_NEAR_N; e++) {
+        if (e < n) {
+            const double s = wave_sum_f64(acc[e]);
+            if ((tid & 63) == 0) red[tid >> 6][e] = s;
+        }
+    }
+    __syncthreads();
+    if (tid < n) {
+        const double r = ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) / v;
+        y[tid] = r;
+        if (near) near[pair * (size_t)n + tid] = r;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double ym = y[h - 1], y0 = y[h], yp = y[h + 1];
+        double f;
+        if (ym != ym || y0 != y0 || yp != yp) f = (double)NAN;
+        else {
+            const double sg = y0 < 0.0 ? -1.0 : 1.0;
+            const double a = sg * ym, b = sg * y0, c = sg * yp;
+            const double den = (a - 2.0 * b) + c;
+            if (den >= 0.0) f = 0.0; // a flat top, a silent pair
+            else f = fmin(0.5, fmax(-0.5, 0.5 * (a - c) / den));
+        }
+        frac[pair] = f;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
 // one flavour of k_rows_r, with the flavour's extra argument (none: k_rows_r itself)
@@ -1634,6 +1739,14 @@ void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, 
             hipLaunchKernelGGL(k_phat_finalize<decltype(sel)>, dim3((unsigned)(npairs + 255) / 256), dim3(256), 0, s, W, seg, peak, P.N,
                                f, npairs, sel);
     });
+}
+
+void asx_launch_phat_near(const AsxDev &P, const float2 *q, const AsxSeg *seg, double f, int h, const AsxSearch &find,
+                          const AsxPoolPair *pl, double *frac, double *near, int npairs, hipStream_t s)
+{
+    const bool rows = find.kind == AsxSearch::ROWS;
+    hipLaunchKernelGGL(k_phat_near, dim3((unsigned)npairs), dim3(256), 0, s, q, asx_spectrum_len(P), seg, P.N, P.M1, P.M2, f, h,
+                       rows ? find.rows.rows : nullptr, rows ? find.rows.step : (size_t)0, pl, frac, near);
 }
 
 // Blocks of `fn` the current device holds at once (k_inv_cols_r's first generation, the one its stagger delays half of): occupancy

@@ -64,9 +64,12 @@ _HEADER_SIGNATURES = {
     "asx_xcorr_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _int, _i64, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_band_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_phat_sub_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_topk_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _i64, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_phat_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_pool_phat_sub_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i64, _i64, _int, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _vp]),
     "asx_xcorr_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_band_debug_r_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -120,6 +123,7 @@ SIGNATURES = {**_HEADER_SIGNATURES, **_DIAGNOSTIC_SIGNATURES}
 ABI_SYMBOLS = list(_HEADER_SIGNATURES)
 
 TOPK_MAX = 8  # ASX_TOPK_MAX, include/audiosync/xcorr_hip.h
+NEAR_MAX = 8  # ASX_NEAR_MAX, include/audiosync/xcorr_hip.h
 
 
 class AsxError(RuntimeError):
@@ -455,6 +459,37 @@ def pool_phat_args(n, sources, samples, pairs=None, windows=None, band=None):
     if any(isinstance(b, bool) or not isinstance(b, (int, np.integer)) for b in (lo, hi)) or not 0 <= int(lo) <= int(hi) <= n:
         raise ValueError("band must be integers (bin_lo, bin_hi) with 0 <= bin_lo <= bin_hi <= %d, not %r" % (n, band))
     return pool_args(n, sources, samples, pairs, windows) + (int(lo), int(hi))
+
+
+def _band_option(n, band):
+    """band None (every bin, (0, N)) or integers (bin_lo, bin_hi) with 0 <= bin_lo <= bin_hi <= N -> (bin_lo, bin_hi) as ints"""
+    lo, hi = (0, n) if band is None else band
+    if any(isinstance(b, bool) or not isinstance(b, (int, np.integer)) for b in (lo, hi)) or not 0 <= int(lo) <= int(hi) <= n:
+        raise ValueError("band must be integers (bin_lo, bin_hi) with 0 <= bin_lo <= bin_hi <= %d, not %r" % (n, band))
+    return int(lo), int(hi)
+
+
+def _near_option(half_width):
+    """-> half_width as an int; ValueError unless it is an integer (no bool) in [1, NEAR_MAX]"""
+    if isinstance(half_width, bool) or not isinstance(half_width, (int, np.integer)) or not 1 <= int(half_width) <= NEAR_MAX:
+        raise ValueError("half_width must be an integer in [1, %d], not %r" % (NEAR_MAX, half_width))
+    return int(half_width)
+
+
+def phat_sub_args(n, source, sample, windows=None, band=None, half_width=1):
+    """Host checks of Plan.xcorr_phat_sub_f32: the shapes of windowed_args (windows=None: the plan's window, no rows), band None
+    (every bin) or integers (bin_lo, bin_hi) with 0 <= bin_lo <= bin_hi <= N, half_width an integer in [1, NEAR_MAX].  ->
+    (source, sample, windows or None, batch, source_stride, sample_stride, window_stride, bin_lo, bin_hi, half_width).  ValueError on
+    anything else."""
+    option = _band_option(n, band) + (_near_option(half_width),)
+    return _strided_args(n, source, sample, None if windows is None else _window_rows(windows)) + option
+
+
+def pool_phat_sub_args(n, sources, samples, pairs=None, windows=None, band=None, half_width=1):
+    """Host checks of Plan.xcorr_pool_phat_sub_f32: half_width an integer in [1, NEAR_MAX], the rest as pool_phat_args.  ->
+    pool_phat_args' tuple + (half_width,).  ValueError on anything else."""
+    h = _near_option(half_width)
+    return pool_phat_args(n, sources, samples, pairs, windows, band) + (h,)
 
 
 def position_rows(n, hop, batch, p_lo, p_hi):
@@ -840,6 +875,27 @@ class Plan:
                                                  int(window_stride), int(batch), int(bin_lo), int(bin_hi), d_lag or None,
                                                  d_coef or None, d_peak or None, d_ret or None, stream or None))
 
+    def xcorr_phat_sub_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, bin_lo, bin_hi, half_width,
+                           d_lag, d_coef, d_peak, d_frac, d_near, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_phat_sub_f32_dev -- xcorr_phat_band_dev, plus d_near (float64 [batch][2 half_width
+        + 1], may be 0): r_phat / V at the indices around each pair's peak, and d_frac (float64 [batch]): the parabolic vertex of
+        the three centre values, so that the delay is lag + frac frames"""
+        _check(lib().asx_xcorr_phat_sub_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride),
+                                                d_windows or None, int(window_stride), int(batch), int(bin_lo), int(bin_hi),
+                                                int(half_width), d_lag or None, d_coef or None, d_peak or None, d_frac or None,
+                                                d_near or None, d_ret or None, stream or None))
+
+    def xcorr_pool_phat_sub_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows,
+                                window_stride, batch, bin_lo, bin_hi, half_width, d_lag, d_coef, d_peak, d_frac, d_near, d_ret,
+                                stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_phat_sub_f32_dev -- xcorr_pool_phat_dev with d_frac and d_near as in
+        xcorr_phat_sub_dev"""
+        _check(lib().asx_xcorr_pool_phat_sub_f32_dev(self._h, d_sources or None, int(source_stride), int(nsources), d_samples or None,
+                                                     int(sample_stride), int(nsamples), d_pairs or None, d_windows or None,
+                                                     int(window_stride), int(batch), int(bin_lo), int(bin_hi), int(half_width),
+                                                     d_lag or None, d_coef or None, d_peak or None, d_frac or None, d_near or None,
+                                                     d_ret or None, stream or None))
+
     def debug_prune(self, pair=0):
         """diagnostic: (upper bounds of |r| per column tile, the largest-bound tile) of `pair` of the last pruned group"""
         n = (self.split[1] + self.split[2] - 1) // self.split[2]
@@ -955,6 +1011,35 @@ class Plan:
         shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
         return self._staged((s, t, pr, w), shape, _PHAT_RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_phat_dev(
             d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, lo, hi, *d_out))
+
+    def _staged_sub(self, inputs, shape, h, launch):
+        """_staged for the sub-sample PHAT calls: outputs (lag, coef, peak, frac, near, ret), near of shape + (2h + 1,)"""
+        with _Staging(self) as st:
+            d_in = [st.upload(a) for a in inputs]
+            d_out = [st.output(shape, np.int64), st.output(shape, np.float64), st.output(shape, np.float64),
+                     st.output(shape, np.float64), st.output(tuple(shape) + (2 * h + 1,), np.float64), st.output(shape, np.int32)]
+            launch(*d_in, *d_out)
+            return st.fetch()
+
+    def xcorr_phat_sub_f32(self, source, sample, windows=None, band=None, half_width=1):
+        """xcorr_phat_f32 with the curve around each peak and a fractional lag (asx_xcorr_phat_sub_f32_dev).  source, sample,
+        windows and band as in xcorr_phat_f32; half_width h in [1, NEAR_MAX].  Arguments are checked on the host (ValueError) before
+        anything is uploaded.  Returns (lag, coef, peak, frac float64[B], near float64[B, 2h + 1], ret): near[i, d + h] is r_phat /
+        V at index (peak index + d) mod 2N, signed; frac the vertex of the parabola through near[i, h - 1 : h + 2], so that the delay
+        estimate is lag + frac frames."""
+        s, t, w, batch, ss, ts, ws, lo, hi, h = phat_sub_args(self.sample_len, source, sample, windows, band, half_width)
+        return self._staged_sub((s, t, w), (batch,), h, lambda d_s, d_t, d_w, *d_out: self.xcorr_phat_sub_dev(
+            d_s, ss, d_t, ts, d_w, ws, batch, lo, hi, h, *d_out))
+
+    def xcorr_pool_phat_sub_f32(self, sources, samples, pairs=None, windows=None, band=None, half_width=1):
+        """xcorr_pool_phat_f32 with the curve around each peak and a fractional lag (asx_xcorr_pool_phat_sub_f32_dev): half_width,
+        frac and near as in xcorr_phat_sub_f32.  Returns (lag, coef, peak, frac, near, ret) of shape [B] (near: [B, 2h + 1]), or
+        [S, R] (near: [S, R, 2h + 1]) when pairs is None; a pair with ret -2 or -4 has NaN in frac and near."""
+        n = self.sample_len
+        s, t, pr, w, batch, ws, lo, hi, h = pool_phat_sub_args(n, sources, samples, pairs, windows, band, half_width)
+        shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
+        return self._staged_sub((s, t, pr, w), shape, h, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_phat_sub_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, lo, hi, h, *d_out))
 
     def xcorr_topk_f32(self, source, sample, k, min_separation, windows=None):
         """The k strongest separated lags per pair (asx_xcorr_topk_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N];
