@@ -29,13 +29,15 @@
  *   ret[i] = 0 on success, -1 when the Pearson coefficient is NaN (lag[i] and
  *   coef[i] are still written, exactly as the reference leaves them).
  *   ret[i] = -2 (asx_xcorr_windowed_f32_dev, and asx_xcorr_phat_f32_dev with rows): pair i's lag
- *   window was not a window inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.
+ *   window was not a window inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.  (asx_xcorr_curve_f32_dev and
+ *   asx_xcorr_pool_curve_f32_dev: an entry's centre was not a lag inside [-N, N-1]; NaN in all its values.)
  *   ret = -3 (asx_xcorr_topk_f32_dev and asx_xcorr_pool_topk_f32_dev only): no lag is left for
  *   this entry of the pair (its window minus the zones around the earlier entries is empty);
  *   lag = 0 and coef = NaN.
  *   ret = -4 (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_pool_phat_f32_dev and
  *   asx_xcorr_pool_phat_sub_f32_dev only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
- *   form: in all k entries of the pair).  It takes precedence over -2 and -3.
+ *   form: in all k entries of the pair).  It takes precedence over -2 and -3.  (asx_xcorr_pool_curve_f32_dev: NaN in all
+ *   the values of the pair's entries.)
  */
 #ifndef AUDIOSYNC_XCORR_HIP_H
 #define AUDIOSYNC_XCORR_HIP_H
@@ -608,6 +610,63 @@ int asx_topk_best_dev(const int64_t *d_lag, const double *d_coef, const int32_t 
                       size_t batch, int k,
                       int64_t *d_best_lag, double *d_best_coef, int32_t *d_best_ret, int32_t *d_best_entry,
                       void *stream);
+
+/* The exact correlation curve and a fractional lag around given lags: a consumer that runs behind the batch, strided, windowed, top-k
+ * and pool calls on the lags they returned.  Those calls rank lags by the raw correlation r and hand back one coefficient per lag;
+ * this one says how sharp a candidate is: r and the Pearson coefficient at the 2h + 1 indices around it, and the parabola's vertex.
+ * It needs no transform -- r at an index is the time-domain sum r[idx] = sum_{n<N} source[(n + idx) mod 2N] * sample[n], the quantity
+ * the exact re-evaluation computes -- so it runs on every plan, packed ones included.
+ *   Inputs.  Pair i's inputs are exactly those of asx_xcorr_strided_f32_dev: strides in floats, a stride of 0 broadcasts, strides
+ * below the track length are allowed.  Real-column plans keep the 16-byte layout rule (16-byte aligned base pointers, every stride a
+ * multiple of 4 floats); packed plans take any float-aligned pointer and any stride.  1 <= entries <= ASX_TOPK_MAX.  Entry
+ * e = i * entries + j belongs to pair i = e / entries; its centre is the lag d_center[e] (int64, device memory, read when the kernels
+ * run), in the convention of every d_lag output: the d_lag of a top-k call with k = entries can be passed straight in, and
+ * entries = 1 serves the other calls.  1 <= half_width <= ASX_NEAR_MAX.
+ *   Outputs, with h = half_width, n = 2h + 1 and p the centre's index (lag l >= 0 is index l, lag l < 0 index 2N + l):
+ *   d_r[e * n + (d + h)] = r[(p + d) mod 2N] for d = -h .. h: the plain sum above in float64 (products of two float32 values are exact
+ * in float64), unnormalised and signed.  Neighbours are taken in index space, circularly: index 2N - 1 (lag -1) sits beside index 0,
+ * and index N (lag -N) beside index N - 1.  Every value is within N * 2^-53 * sum_n |source * sample| (over the terms of its index)
+ * of the exact sum.
+ *   d_coef[e * n + (d + h)] = the reference's Pearson coefficient at that index's lag, after the wrap and with the segments of
+ * src/cross_correlation.c:256-272, always in the direct form: bit for bit what asx_xcorr_windowed_f32_dev returns on the same plan for
+ * that pair with the row [l, l] under asx_plan_set_pearson(plan, 0) (the precedent of the top-k call's later entries), and NaN where
+ * that call's coefficient is NaN (the empty segment at lag -N, a constant segment).  d_coef may be NULL: no Pearson pass runs then.
+ *   d_frac[e] = the vertex of the parabola through the three centre values of d_r, by the rule and in the operation order stated for
+ * asx_xcorr_phat_sub_f32_dev: s by the sign of y0, den = (a - 2 b) + c, 0 when den >= 0, clamped to [-0.5, 0.5], NaN when any of the
+ * three is NaN.
+ *   d_ret[e] = 0 for a computed entry, -2 for a centre outside [-N, N-1].  A -2 entry gets NaN in frac and in all n values of r and
+ * coef, and reads nothing; the other entries are untouched, bit for bit.
+ *   Every value of an entry is independent of the batch size and of the entry's position in the batch (a fixed reduction tree).
+ *   Refusals: a NULL plan, track, d_center, d_r, d_frac or d_ret, entries or half_width out of range, and the layout rule on a
+ * real-column plan return -1 with nothing launched and the outputs untouched.  batch == 0 returns 0.
+ *   What the call never does.  It allocates nothing after plan creation (asx_plan_workspace_bytes stays the same), never
+ * synchronises the host and touches no counter: overflows, repairs, Pearson modes, prune and qstore stats stay unchanged.  It behaves
+ * the same whatever asx_plan_set_exact, asx_plan_set_pearson, asx_plan_set_prune or the plan's lag window say.  It uses the plan's
+ * lane workspaces, so the one-stream-at-a-time rule of asx_xcorr_batch_f32_dev applies.
+ *   Cost.  r and frac: one pass over each entry's tracks, 8N bytes, for all n sums (a block's stretch of the source goes through LDS
+ * once, with a halo of 2h).  The coefficient curve: one direct Pearson pass per neighbour, n passes per entry; d_coef == NULL skips
+ * them.  Measured: DESIGN.md. */
+int asx_xcorr_curve_f32_dev(asx_plan *plan,
+                            const float *d_source, size_t source_stride,
+                            const float *d_sample, size_t sample_stride,
+                            size_t batch, int entries, const int64_t *d_center, int half_width,
+                            double *d_r, double *d_coef, double *d_frac, int32_t *d_ret, void *stream);
+
+/* ... for pairs of two track pools: the inputs of asx_xcorr_pool_f32_dev -- the pools, which may alias or overlap, strides that may be
+ * below the track length, d_pairs == NULL = every combination source-major, batch then nsources * nsamples -- with entries,
+ * d_center, half_width and the outputs of asx_xcorr_curve_f32_dev: each entry is what that call returns for the pair's two tracks.
+ * Real-column plans only, as every pool call.  It never touches, fills or grows the bank: it reads the tracks themselves.
+ *   d_ret[e] = -4 for an entry whose pair's row names a track outside its pool (over -2): NaN in frac and in all its values of r and
+ * coef, nothing read outside the pools, the other entries untouched, bit for bit.
+ *   Returns -1 with the outputs untouched and nothing launched on the refusals of asx_xcorr_curve_f32_dev and on every refusal of
+ * asx_xcorr_pool_f32_dev that does not concern the bank (a NULL pool; an empty pool while batch > 0; not a real-column plan;
+ * alignment; strides that are not multiples of 4 floats; d_pairs == NULL with batch != nsources * nsamples).  batch == 0 returns 0. */
+int asx_xcorr_pool_curve_f32_dev(asx_plan *plan,
+                                 const float *d_sources, size_t source_stride, size_t nsources,
+                                 const float *d_samples, size_t sample_stride, size_t nsamples,
+                                 const int32_t *d_pairs,
+                                 size_t batch, int entries, const int64_t *d_center, int half_width,
+                                 double *d_r, double *d_coef, double *d_frac, int32_t *d_ret, void *stream);
 
 /* ---- growing-window (streaming) mode ------------------------------------ */
 

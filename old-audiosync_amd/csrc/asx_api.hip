@@ -1613,6 +1613,75 @@ extern "C" int asx_xcorr_pool_phat_sub_f32_dev(asx_plan *p, const float *d_sourc
                       batch, { d_lag, d_coef, d_ret, 1, d_peak }, stream, {}, weight, band, near);
 }
 
+// ---------------------------------------------------------------------------
+// the curve around given lags (asx_xcorr_curve_f32_dev, asx_xcorr_pool_curve_f32_dev): a consumer behind any call, on the lags it
+// returned.  No transform, no group: r and frac from k_curve_dots over the tracks themselves, the coefficient curve from the direct
+// Pearson kernels over one virtual pair per neighbour; both in slices of a launch group, in lane 0's records and psums.
+// ---------------------------------------------------------------------------
+// both entry points (fn: the entry point's name for the messages; pooled: nsrc, nsmp and d_pairs mean something)
+static int curve_call(asx_plan *p, const char *fn, bool pooled, const float *d_src, size_t src_stride, size_t nsrc, const float *d_smp,
+                      size_t smp_stride, size_t nsmp, const int32_t *d_pairs, size_t batch, int entries, const int64_t *d_center,
+                      int half_width, double *d_r, double *d_coef, double *d_frac, int32_t *d_ret, void *stream)
+{
+    if (!p || !d_src || !d_smp || !d_center || !d_r || !d_frac || !d_ret) return fail("%s: null argument", fn);
+    if (entries < 1 || entries > ASX_TOPK_MAX) return fail("%s: entries = %d is not in [1, %d]", fn, entries, ASX_TOPK_MAX);
+    if (half_width < 1 || half_width > ASX_NEAR_MAX) return fail("%s: half_width = %d is not in [1, %d]", fn, half_width, ASX_NEAR_MAX);
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
+    const AsxDev &P = p->dev;
+    if (pooled && P.rlayout != 1) return fail("%s: pool calls need a real-column plan (asx_plan_layout() == 1)", fn);
+    if (P.rlayout) {
+        if (((uintptr_t)d_src & 15u) || ((uintptr_t)d_smp & 15u))
+            return fail("%s: real-column plans need 16-byte aligned inputs (source %p, sample %p)", fn, (const void *)d_src,
+                        (const void *)d_smp);
+        if ((src_stride & 3u) || (smp_stride & 3u))
+            return fail("%s: real-column plans need strides that are multiples of 4 floats (source_stride %zu, sample_stride %zu)", fn,
+                        src_stride, smp_stride);
+    }
+    if (pooled) {
+        if (nsrc > INT32_MAX || nsmp > INT32_MAX) return fail("%s: a pool of more than 2^31 - 1 tracks", fn);
+        if (!d_pairs && batch != nsrc * nsmp)
+            return fail("%s: without pairs the batch is every combination, %zu x %zu, not %zu", fn, nsrc, nsmp, batch);
+    }
+    if (batch == 0) return 0;
+    if (pooled && (nsrc == 0 || nsmp == 0)) return fail("%s: an empty pool (%zu sources, %zu samples) for %zu pairs", fn, nsrc, nsmp, batch);
+    asx_plan::Lane &W = p->lanes[0];
+    const AsxCurve A{ d_center, d_r, d_frac, d_ret, P.N, entries, half_width, pooled ? d_pairs : nullptr,
+                      pooled ? (uint64_t)nsrc : 0u, pooled ? (uint64_t)nsmp : 0u, (uint64_t)src_stride, (uint64_t)smp_stride };
+    const size_t total = batch * (size_t)entries, n = 2 * (size_t)half_width + 1;
+    for (size_t e0 = 0; e0 < total; e0 += p->group)
+        asx_launch_curve_r(d_src, d_smp, A, e0, (int)std::min(p->group, total - e0), W.pool, W.psums, s);
+    if (d_coef) {
+        // one direct Pearson pass per neighbour: the kernels, the chunks and the merge tree of a windowed call with the row [l, l]
+        const AsxInputs<float> in{ d_src, d_smp, 0, 0, W.pool };
+        for (size_t v0 = 0; v0 < total * n; v0 += p->group) {
+            const int g = (int)std::min(p->group, total * n - v0);
+            asx_launch_curve_segs(A, v0, g, W.seg, W.pool, s);
+            asx_launch_pearson(in, P.N, W.seg, W.psums, (int64_t *)nullptr, d_coef + v0, (int32_t *)nullptr, g, s);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int asx_xcorr_curve_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                       size_t sample_stride, size_t batch, int entries, const int64_t *d_center, int half_width,
+                                       double *d_r, double *d_coef, double *d_frac, int32_t *d_ret, void *stream)
+{
+    return curve_call(p, "asx_xcorr_curve_f32_dev", false, d_source, source_stride, 0, d_sample, sample_stride, 0, nullptr, batch,
+                      entries, d_center, half_width, d_r, d_coef, d_frac, d_ret, stream);
+}
+
+extern "C" int asx_xcorr_pool_curve_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                            const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                            size_t batch, int entries, const int64_t *d_center, int half_width, double *d_r,
+                                            double *d_coef, double *d_frac, int32_t *d_ret, void *stream)
+{
+    return curve_call(p, "asx_xcorr_pool_curve_f32_dev", true, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples,
+                      d_pairs, batch, entries, d_center, half_width, d_r, d_coef, d_frac, d_ret, stream);
+}
+
 // diagnostic (not in the public header): the bank's capacity in tracks and how many pool calls have filled it
 extern "C" int asx_plan_debug_bank(asx_plan *p, uint64_t *nsrc, uint64_t *nsmp, uint64_t *fills)
 {

@@ -589,6 +589,32 @@ void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, 
 #define ASX_NEAR_MAX 8
 void asx_launch_phat_near(const AsxDev &P, const float2 *q, const AsxSeg *seg, double f, int h, const AsxSearch &find,
                           const AsxPoolPair *pl, double *frac, double *near, int npairs, hipStream_t s);
+// The curve around given lags (asx_xcorr_curve_f32_dev, asx_xcorr_pool_curve_f32_dev; xcorr_kernels.hip: k_curve_dots): one call's
+// arguments as its kernels take them, by value.  Entry e = pair * entries + j is centred on the lag center[e]; pair i is tracks
+// (i, i) at the strides of the strided form (nsrc == 0), or the tracks of row i of `rows` (null: every combination, source-major) in
+// the pool form (nsrc > 0: a pool call with pairs never has an empty pool).
+#define ASX_CURVE_N (2 * ASX_NEAR_MAX + 1)
+struct AsxCurve {
+    const int64_t *center;  // [batch * entries] lags, the convention of every d_lag
+    double *r;              // [batch * entries][2 h + 1]
+    double *frac;           // [batch * entries]
+    int32_t *ret;           // [batch * entries]
+    uint32_t N;
+    int entries, h;
+    const int32_t *rows;
+    uint64_t nsrc, nsmp, src_stride, smp_stride;
+};
+// blocks of k_curve_dots per entry: by the length alone, as asx_pearson_blocks, and as many as leave their ASX_CURVE_N partial sums
+// in a pair's share of the lane's psums (6 doubles per Pearson block); one block writes its entry's results itself
+unsigned asx_curve_blocks(uint32_t N);
+// r and frac (and ret) of entries first .. first + count - 1, count at most a launch group: the pool form's records go to pl (the
+// lane's, [count]), the blocks' partial sums to part (the lane's psums)
+void asx_launch_curve_r(const float *src, const float *smp, const AsxCurve &A, size_t first, int count, AsxPoolPair *pl, double *part,
+                        hipStream_t s);
+// the coefficient curve's virtual pairs first .. first + count - 1 (virtual pair e (2 h + 1) + d + h: entry e at its neighbour d),
+// count at most a launch group: each one's segment to seg and its tracks' offsets to pl, what asx_launch_pearson's listed form reads.
+// An invalid entry's get an empty segment at offset 0: nothing is read and the coefficient is NaN.
+void asx_launch_curve_segs(const AsxCurve &A, size_t first, int count, AsxSeg *seg, AsxPoolPair *pl, hipStream_t s);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 // pool calls: each pair's record (out) and its two slots' norm partials and band sums (band may be null) into the group's places

@@ -1643,19 +1643,7 @@ __global__ __launch_bounds__(256) void k_phat_near(const float2 *__restrict__ q,
         if (near) near[pair * (size_t)n + tid] = r;
     }
     __syncthreads();
-    if (tid == 0) {
-        const double ym = y[h - 1], y0 = y[h], yp = y[h + 1];
-        double f;
-        if (ym != ym || y0 != y0 || yp != yp) f = (double)NAN;
-        else {
-            const double sg = y0 < 0.0 ? -1.0 : 1.0;
-            const double a = sg * ym, b = sg * y0, c = sg * yp;
-            const double den = (a - 2.0 * b) + c;
-            if (den >= 0.0) f = 0.0; // a flat top, a silent pair
-            else f = fmin(0.5, fmax(-0.5, 0.5 * (a - c) / den));
-        }
-        frac[pair] = f;
-    }
+    if (tid == 0) frac[pair] = asx_parabola_frac(y[h - 1], y[h], y[h + 1]);
 }
 
 // ---------------------------------------------------------------------------

@@ -235,6 +235,25 @@ __device__ __forceinline__ AsxSeg make_seg(uint32_t peak, uint32_t N)
 }
 
 // ---------------------------------------------------------------------------
+// The vertex of the parabola through three neighbouring values of a curve, y- y0 y+ at d = -1, 0, 1, in float64 and in the order
+// include/audiosync/xcorr_hip.h states for asx_xcorr_phat_sub_f32_dev: the one statement of that rule (k_phat_near, rlayout.hip; the
+// curve kernels, xcorr_kernels.hip).  NaN when any of the three is NaN; 0 for a flat top or a silent pair; clamped to [-0.5, 0.5].
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ double asx_parabola_frac(double ym, double y0, double yp)
+{
+    double f;
+    if (ym != ym || y0 != y0 || yp != yp) f = (double)NAN;
+    else {
+        const double sg = y0 < 0.0 ? -1.0 : 1.0;
+        const double a = sg * ym, b = sg * y0, c = sg * yp;
+        const double den = (a - 2.0 * b) + c;
+        if (den >= 0.0) f = 0.0; // a flat top, a silent pair
+        else f = fmin(0.5, fmax(-0.5, 0.5 * (a - c) / den));
+    }
+    return f;
+}
+
+// ---------------------------------------------------------------------------
 // The spectral Pearson form's decision for one pair (pearson_spectral.hip), from what k_pearson_prep left: the blocks' shares of the window
 // sums (added here in block order: the same bits whoever adds them), r[peak] and the bound on its error.  Pure: every block of
 // k_pearson_partial and k_pearson_final_spec work it out for themselves and agree.

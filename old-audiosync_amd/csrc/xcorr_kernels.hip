@@ -1415,6 +1415,212 @@ __global__ __launch_bounds__(ASX_THREADS) void k_topk_best(const int64_t *__rest
 }
 
 // ---------------------------------------------------------------------------
+// The curve around given lags (asx_xcorr_curve_f32_dev, asx_xcorr_pool_curve_f32_dev): behind any call, on the lags it returned,
+//     r[idx] = sum_{n<N} source[(n + idx) mod 2N] * sample[n]     at idx = (p + d) mod 2N, d = -h .. h,
+// the sum of k_refine_dots, for all 2h + 1 indices in ONE pass over the entry's tracks: with i0 = (p - h) mod 2N, sample n meets
+// source (n + i0 + j) mod 2N for j = 0 .. 2h, a window that slides with n.
+// ---------------------------------------------------------------------------
+// where entry e's tracks are and what its ret is: -4 for a row outside its pool (over -2), -2 for a centre outside [-N, N-1]
+__device__ __forceinline__ int32_t curve_locate(const AsxCurve &A, size_t e, uint64_t &src_off, uint64_t &smp_off)
+{
+    const size_t pair = e / (size_t)A.entries;
+    int64_t a = (int64_t)pair, b = (int64_t)pair;
+    bool in = true;
+    if (A.nsrc) {
+        if (A.rows) { a = A.rows[2 * pair]; b = A.rows[2 * pair + 1]; }
+        else { a = (int64_t)(pair / A.nsmp); b = (int64_t)(pair % A.nsmp); }
+        in = a >= 0 && (uint64_t)a < A.nsrc && b >= 0 && (uint64_t)b < A.nsmp;
+    }
+    src_off = in ? (uint64_t)a * A.src_stride : 0u;
+    smp_off = in ? (uint64_t)b * A.smp_stride : 0u;
+    if (!in) return -4;
+    const int64_t c = A.center[e], n = (int64_t)A.N;
+    return (c < -n || c > n - 1) ? -2 : 0;
+}
+// index of the entry's first value, (p - h) mod 2N, p the index of the lag c in [-N, N-1]
+__device__ __forceinline__ uint32_t curve_first(int64_t c, uint32_t N, int h)
+{
+    const uint32_t L = 2u * N;
+    const uint32_t p = c >= 0 ? (uint32_t)c : (uint32_t)((int64_t)L + c);
+    return (p + L - (uint32_t)h % L) % L;
+}
+// an entry's results from its 2h + 1 final values y (shared memory; not read when rv != 0): r, then frac, then ret
+__device__ __forceinline__ void curve_write(const AsxCurve &A, size_t e, int32_t rv, const double *y, int tid)
+{
+    const int n = 2 * A.h + 1;
+    if (tid < n) A.r[e * (size_t)n + tid] = rv ? (double)NAN : y[tid];
+    if (tid == 0) {
+        A.frac[e] = rv ? (double)NAN : asx_parabola_frac(y[A.h - 1], y[A.h], y[A.h + 1]);
+        A.ret[e] = rv;
+    }
+}
+
+// pool form: entries first .. first + count - 1 as listed input records (what k_pool_resolve makes of a pair, without the bank)
+__global__ __launch_bounds__(ASX_THREADS) void k_curve_resolve(AsxCurve A, size_t first, int count, AsxPoolPair *__restrict__ out)
+{
+    const int le = (int)(blockIdx.x * ASX_THREADS + threadIdx.x);
+    if (le >= count) return;
+    AsxPoolPair rec;
+    const int32_t rv = curve_locate(A, first + (size_t)le, rec.src_off, rec.smp_off);
+    rec.sx = rec.sy = 0u;
+    rec.flags = rv == -4 ? ASX_POOL_INVALID : 0u;
+    rec.pad = 0u;
+    out[le] = rec;
+}
+
+// grid (blocks per entry, entries of the slice), entry e = first + blockIdx.y.  Block x takes samples [x chunk, (x + 1) chunk) in
+// sweeps of ASX_CURVE_SWEEP: the sweep's stretch of the source, 2h values longer and taken modulo 2N, goes through LDS once, and a
+// thread forms the 2h + 1 products of each of its four consecutive samples from a window of 4 + 2h values it reads from there --
+// one pass over both tracks for all the sums.  float64 throughout (the products of float32 values are exact); the order is fixed:
+// a thread's samples ascending, the lanes of a wave (wave_sum), the waves, and, when the entry has more than one block, the blocks in
+// order (k_curve_sum, from `part`): an entry's bits depend on neither the batch nor its place in it.  With one block per entry the
+// block writes the results itself.  Where: AsxAtPitch, indexed by the entry's pair, or AsxAtList, indexed by the entry's place in
+// the slice (k_curve_resolve's records).  An entry that is not valid reads nothing.
+#define ASX_CURVE_SWEEP (4 * ASX_THREADS)
+typedef float asx_f4u __attribute__((ext_vector_type(4), aligned(4))); // four floats at any float-aligned address
+template <class Where>
+__global__ __launch_bounds__(ASX_THREADS) void k_curve_dots(const float *__restrict__ src, const float *__restrict__ smp, Where at,
+                                                             AsxCurve A, size_t first, double *__restrict__ part)
+{
+    constexpr bool listed = std::is_same<Where, AsxAtList>::value;
+    __shared__ __attribute__((aligned(16))) float xs[ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX];
+    __shared__ double red[ASX_THREADS / 64][ASX_CURVE_N];
+    __shared__ double yv[ASX_CURVE_N];
+    const int tid = threadIdx.x, h = A.h, n = 2 * h + 1;
+    const size_t le = blockIdx.y, e = first + le;
+    const size_t rec = listed ? le : e / (size_t)A.entries;
+    const uint32_t N = A.N, L = 2u * N;
+    const int64_t c = A.center[e];
+    int32_t rv = (c < -(int64_t)N || c > (int64_t)N - 1) ? -2 : 0;
+    if constexpr (listed) {
+        if (at.pl[rec].flags & ASX_POOL_INVALID) rv = -4;
+    }
+    if (rv) { // (block-uniform: nobody is left at a barrier)
+        if (gridDim.x == 1) curve_write(A, e, rv, yv, tid);
+        return;
+    }
+    const uint32_t i0 = curve_first(c, N, h);
+    const float *x = src + at.src_off(rec);
+    const float *y = smp + at.smp_off(rec);
+    const uint32_t chunk = ((N + gridDim.x - 1) / gridDim.x + 3u) & ~3u;
+    const uint64_t lo = (uint64_t)blockIdx.x * chunk;
+    const uint64_t hi = lo + chunk < (uint64_t)N ? lo + chunk : (uint64_t)N;
+    double acc[ASX_CURVE_N];
+#pragma unroll
+    for (int j = 0; j < ASX_CURVE_N; j++) acc[j] = 0.0;
+    for (uint64_t n0 = lo; n0 < hi; n0 += ASX_CURVE_SWEEP) {
+        const uint32_t cnt = hi - n0 < (uint64_t)ASX_CURVE_SWEEP ? (uint32_t)(hi - n0) : (uint32_t)ASX_CURVE_SWEEP;
+        // the thread's four samples; past the block's end: zeros, which meet zeros below
+        const uint32_t t4 = 4u * (uint32_t)tid;
+        asx_f4v yq = { 0.0f, 0.0f, 0.0f, 0.0f };
+        if (t4 + 3u < cnt) yq = *reinterpret_cast<const asx_f4u *>(y + n0 + t4);
+        else {
+            if (t4 < cnt) yq.x = y[n0 + t4];
+            if (t4 + 1u < cnt) yq.y = y[n0 + t4 + 1u];
+            if (t4 + 2u < cnt) yq.z = y[n0 + t4 + 2u];
+        }
+        // xs[t] = source[(n0 + i0 + t) mod 2N] for t < cnt + 2h, zero behind: 16-byte loads where the four neither leave the sweep
+        // nor straddle the wrap
+        const uint32_t g0 = (uint32_t)((n0 + i0) % L), need = cnt + 2u * (uint32_t)h;
+        auto wrapped = [&](uint32_t i) { if (i >= L) { i -= L; if (i >= L) i %= L; } return i; };
+        for (uint32_t t = t4; t < (uint32_t)(ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX); t += (uint32_t)ASX_CURVE_SWEEP) {
+            asx_f4v v = { 0.0f, 0.0f, 0.0f, 0.0f };
+            if (t < need) {
+                const uint32_t g = wrapped(g0 + t);
+                if (t + 3u < need && g + 3u < L) v = *reinterpret_cast<const asx_f4u *>(x + g);
+                else {
+                    v.x = x[g];
+                    if (t + 1u < need) v.y = x[wrapped(g0 + t + 1u)];
+                    if (t + 2u < need) v.z = x[wrapped(g0 + t + 2u)];
+                    if (t + 3u < need) v.w = x[wrapped(g0 + t + 3u)];
+                }
+            }
+            *reinterpret_cast<asx_f4v *>(xs + t) = v;
+        }
+        __syncthreads();
+        double w[4 + 2 * ASX_NEAR_MAX];
+#pragma unroll
+        for (int q = 0; q < (4 + 2 * ASX_NEAR_MAX) / 4; q++) {
+            asx_f4v v = { 0.0f, 0.0f, 0.0f, 0.0f };
+            if (4 * q < 4 + 2 * h) v = *reinterpret_cast<const asx_f4v *>(xs + t4 + 4u * (uint32_t)q);
+            w[4 * q] = (double)v.x; w[4 * q + 1] = (double)v.y; w[4 * q + 2] = (double)v.z; w[4 * q + 3] = (double)v.w;
+        }
+        const double y0 = (double)yq.x, y1 = (double)yq.y, y2 = (double)yq.z, y3 = (double)yq.w;
+#pragma unroll
+        for (int j = 0; j < ASX_CURVE_N; j++) {
+            if (j < n) {
+                double a = acc[j];
+                a = fma(w[j], y0, a);
+                a = fma(w[j + 1], y1, a);
+                a = fma(w[j + 2], y2, a);
+                a = fma(w[j + 3], y3, a);
+                acc[j] = a;
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < ASX_CURVE_N; j++) {
+        if (j < n) {
+            const double s = wave_sum(acc[j]);
+            if ((tid & 63) == 0) red[tid >> 6][j] = s;
+        }
+    }
+    __syncthreads();
+    if (tid < n) {
+        const double v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+        if (gridDim.x == 1) yv[tid] = v;
+        else part[(le * gridDim.x + blockIdx.x) * ASX_CURVE_N + tid] = v;
+    }
+    if (gridDim.x == 1) {
+        __syncthreads();
+        curve_write(A, e, 0, yv, tid);
+    }
+}
+
+// grid (entries of the slice), one wave: an entry's nb partial sums in block order, then its results; pl: the pool form's records
+__global__ __launch_bounds__(64) void k_curve_sum(AsxCurve A, size_t first, unsigned nb, const double *__restrict__ part,
+                                                   const AsxPoolPair *__restrict__ pl)
+{
+    __shared__ double yv[ASX_CURVE_N];
+    const int tid = threadIdx.x, n = 2 * A.h + 1;
+    const size_t le = blockIdx.x, e = first + le;
+    const int64_t c = A.center[e];
+    int32_t rv = (c < -(int64_t)A.N || c > (int64_t)A.N - 1) ? -2 : 0;
+    if (pl && (pl[le].flags & ASX_POOL_INVALID)) rv = -4;
+    if (!rv && tid < n) {
+        const double *p = part + le * nb * ASX_CURVE_N + tid;
+        double s = p[0];
+        for (unsigned b = 1; b < nb; b++) s += p[(size_t)b * ASX_CURVE_N];
+        yv[tid] = s;
+    }
+    __syncthreads();
+    curve_write(A, e, rv, yv, tid);
+}
+
+// the coefficient curve: virtual pair v = e (2h + 1) + j is entry e at index (i0 + j) mod 2N -- the segment the peak search would have
+// left for that lag (make_seg) and the entry's tracks as a listed input record, so that the direct Pearson kernels run on them as
+// they run on a pool group
+__global__ __launch_bounds__(ASX_THREADS) void k_curve_segs(AsxCurve A, size_t first, int count, AsxSeg *__restrict__ seg,
+                                                             AsxPoolPair *__restrict__ out)
+{
+    const int lv = (int)(blockIdx.x * ASX_THREADS + threadIdx.x);
+    if (lv >= count) return;
+    const size_t v = first + (size_t)lv, n = (size_t)(2 * A.h + 1), e = v / n;
+    AsxPoolPair rec;
+    AsxSeg s;
+    if (curve_locate(A, e, rec.src_off, rec.smp_off) == 0)
+        s = make_seg((curve_first(A.center[e], A.N, A.h) + (uint32_t)(v % n)) % (2u * A.N), A.N);
+    else {
+        s.lag = 0; s.src_off = s.smp_off = s.len = s.peak = s.flags = 0u;
+        rec.src_off = rec.smp_off = 0u;
+    }
+    rec.sx = rec.sy = rec.flags = rec.pad = 0u;
+    seg[lv] = s;
+    out[lv] = rec;
+}
+
+// ---------------------------------------------------------------------------
 // second look, DC removal (second_look, asx_api.hip): one pair, one block each.  An offset of hundreds of standard deviations
 // in BOTH tracks makes the float32 error bound (proportional to |source|_2 |sample|_2) wider than the whole range of
 // r, every lag a near-tie.  r'[k] = sum (source[n+k] - m) sample[n] = r[k] - m * sum(sample) for ANY constant m: the
@@ -1762,6 +1968,35 @@ void asx_launch_topk_best(const int64_t *lag, const double *coef, const int32_t 
     const unsigned blocks = (unsigned)((batch + ASX_THREADS - 1) / ASX_THREADS);
     hipLaunchKernelGGL(k_topk_best, dim3(blocks), dim3(ASX_THREADS), 0, s, lag, coef, ret, batch, k, best_lag, best_coef, best_ret,
                        best_entry);
+}
+
+unsigned asx_curve_blocks(uint32_t N)
+{
+    const unsigned nb = asx_pearson_blocks(N) * 6u / (unsigned)ASX_CURVE_N;
+    return nb < 1u ? 1u : nb;
+}
+
+void asx_launch_curve_r(const float *src, const float *smp, const AsxCurve &A, size_t first, int count, AsxPoolPair *pl, double *part,
+                        hipStream_t s)
+{
+    const unsigned nb = asx_curve_blocks(A.N);
+    const dim3 grid(nb, (unsigned)count), block(ASX_THREADS);
+    if (A.nsrc) {
+        hipLaunchKernelGGL(k_curve_resolve, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), block, 0, s, A, first, count, pl);
+        hipLaunchKernelGGL(k_curve_dots<AsxAtList>, grid, block, 0, s, src, smp, AsxAtList{ pl }, A, first, part);
+    } else {
+        hipLaunchKernelGGL(k_curve_dots<AsxAtPitch>, grid, block, 0, s, src, smp, AsxAtPitch{ (size_t)A.src_stride, (size_t)A.smp_stride },
+                           A, first, part);
+    }
+    if (nb > 1u)
+        hipLaunchKernelGGL(k_curve_sum, dim3((unsigned)count), dim3(64), 0, s, A, first, nb, (const double *)part,
+                           (const AsxPoolPair *)(A.nsrc ? pl : nullptr));
+}
+
+void asx_launch_curve_segs(const AsxCurve &A, size_t first, int count, AsxSeg *seg, AsxPoolPair *pl, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_curve_segs, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, A, first, count,
+                       seg, pl);
 }
 
 void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t s)

@@ -70,6 +70,8 @@ _HEADER_SIGNATURES = {
     "asx_xcorr_pool_phat_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_phat_sub_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i64, _i64, _int, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp]),
+    "asx_xcorr_curve_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_pool_curve_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_band_debug_r_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -492,6 +494,55 @@ def pool_phat_sub_args(n, sources, samples, pairs=None, windows=None, band=None,
     return pool_phat_args(n, sources, samples, pairs, windows, band) + (h,)
 
 
+def _curve_option(half_width, entries):
+    """-> (half_width, entries) as ints; ValueError unless they are integers (no bools), half_width in [1, NEAR_MAX] and entries in
+    [1, TOPK_MAX]"""
+    if isinstance(entries, bool) or not isinstance(entries, (int, np.integer)) or not 1 <= int(entries) <= TOPK_MAX:
+        raise ValueError("entries must be an integer in [1, %d], not %r" % (TOPK_MAX, entries))
+    return _near_option(half_width), int(entries)
+
+
+def _centers(centers, lead, entries):
+    """the centre lags of a curve call -> a contiguous int64 array of shape lead + (entries,), or lead alone when entries == 1
+    (lead: the shape of the pairs; a None in it: any size).  -> (centers, their leading shape)"""
+    c = np.asarray(centers)
+    if c.dtype.kind not in "iu":
+        raise ValueError("centers must hold integers (lags), not %s" % c.dtype)
+    c = np.ascontiguousarray(c, dtype=np.int64)
+    shapes = [tuple(lead) + (entries,)] + ([tuple(lead)] if entries == 1 else [])
+    for want in shapes:
+        if c.ndim == len(want) and all(w is None or w == g for w, g in zip(want, c.shape)):
+            return c, c.shape[:len(lead)]
+    raise ValueError("centers must be of shape %s, not %s" % (" or ".join(str(list(w)).replace("None", "B") for w in shapes), list(c.shape)))
+
+
+def curve_args(n, source, sample, centers, half_width=1, entries=1):
+    """Host checks of Plan.xcorr_curve_f32 for a plan of sample length n: source [2N] or [B, 2N], sample [N] or [B, N] (a 1-D operand
+    serves every pair), centers integers [B, entries] (or [B] when entries == 1) -- B the batch of the 2-D operands, any B >= 1 when
+    both are 1-D -- half_width an integer in [1, NEAR_MAX], entries in [1, TOPK_MAX].  -> (source, sample, centers, batch,
+    source_stride, sample_stride, half_width, entries) as contiguous float32 / int64 arrays and strides in floats.  ValueError on
+    anything else.  The centres' values are not checked: one outside [-N, N-1] comes back with ret -2."""
+    h, entries = _curve_option(half_width, entries)
+    s, t, ss, ts = _operands(n, source, sample)
+    sizes = {a.shape[0] for a in (s, t) if a.ndim == 2}
+    if len(sizes) > 1:
+        raise ValueError("source and sample have different batch sizes %s" % sorted(sizes))
+    c, lead = _centers(centers, (sizes.pop() if sizes else None,), entries)
+    if lead[0] < 1:
+        raise ValueError("empty batch")
+    return s, t, c, lead[0], ss, ts, h, entries
+
+
+def pool_curve_args(n, sources, samples, centers, pairs=None, half_width=1, entries=1):
+    """Host checks of Plan.xcorr_pool_curve_f32: the pools and pairs of pool_args, centers integers [B, entries] (or [B] when entries
+    == 1) with pairs, [S, R, entries] (or [S, R]) without, half_width and entries as curve_args checks them.  -> (sources, samples,
+    pairs or None, centers, batch, half_width, entries).  ValueError on anything else."""
+    h, entries = _curve_option(half_width, entries)
+    s, t, pr, _, batch, _ = pool_args(n, sources, samples, pairs)
+    c, _ = _centers(centers, (batch,) if pr is not None else (s.shape[0], t.shape[0]), entries)
+    return s, t, pr, c, batch, h, entries
+
+
 def position_rows(n, hop, batch, p_lo, p_hi):
     """Lag windows of Plan.xcorr_windows_f32(..., positions=(p_lo, p_hi)): window k (source frames k*hop .. k*hop + 2N - 1 of the
     recording, 0 <= k < batch) holds a sample that starts at recording frame k*hop + lag, so its rows are
@@ -896,6 +947,23 @@ class Plan:
                                                      d_lag or None, d_coef or None, d_peak or None, d_frac or None, d_near or None,
                                                      d_ret or None, stream or None))
 
+    def xcorr_curve_dev(self, d_src, src_stride, d_smp, smp_stride, batch, entries, d_center, half_width, d_r, d_coef, d_frac, d_ret,
+                        stream=0):
+        """raw device pointers (ints): asx_xcorr_curve_f32_dev -- around each of the batch * entries lags of d_center (int64), the
+        exact r (d_r) and the Pearson coefficient (d_coef, may be 0: not computed) at the 2 half_width + 1 neighbouring indices,
+        float64 [batch * entries][2 half_width + 1], the parabolic vertex d_frac and d_ret, [batch * entries]"""
+        _check(lib().asx_xcorr_curve_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride), int(batch),
+                                             int(entries), d_center or None, int(half_width), d_r or None, d_coef or None,
+                                             d_frac or None, d_ret or None, stream or None))
+
+    def xcorr_pool_curve_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, batch, entries,
+                             d_center, half_width, d_r, d_coef, d_frac, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_curve_f32_dev -- xcorr_curve_dev for the pairs of xcorr_pool_dev"""
+        _check(lib().asx_xcorr_pool_curve_f32_dev(self._h, d_sources or None, int(source_stride), int(nsources), d_samples or None,
+                                                  int(sample_stride), int(nsamples), d_pairs or None, int(batch), int(entries),
+                                                  d_center or None, int(half_width), d_r or None, d_coef or None, d_frac or None,
+                                                  d_ret or None, stream or None))
+
     def debug_prune(self, pair=0):
         """diagnostic: (upper bounds of |r| per column tile, the largest-bound tile) of `pair` of the last pruned group"""
         n = (self.split[1] + self.split[2] - 1) // self.split[2]
@@ -1040,6 +1108,39 @@ class Plan:
         shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
         return self._staged_sub((s, t, pr, w), shape, h, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_phat_sub_dev(
             d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, lo, hi, h, *d_out))
+
+    def _staged_curve(self, inputs, shape, h, coef, launch):
+        """_staged for the curve calls: outputs (r, coef, frac, ret), r and coef of shape + (2h + 1,); coef False: a null d_coef, and
+        None in its place"""
+        with _Staging(self) as st:
+            d_in = [st.upload(a) for a in inputs]
+            wide = tuple(shape) + (2 * h + 1,)
+            d_r = st.output(wide, np.float64)
+            d_coef = st.output(wide, np.float64) if coef else 0
+            launch(*d_in, d_r, d_coef, st.output(shape, np.float64), st.output(shape, np.int32))
+            out = st.fetch()
+            return out if coef else (out[0], None) + out[1:]
+
+    def xcorr_curve_f32(self, source, sample, centers, half_width=1, entries=1, coef=True):
+        """The exact correlation curve around given lags (asx_xcorr_curve_f32_dev), behind any call on the lags it returned.  source:
+        float32 [2N] or [B, 2N]; sample: [N] or [B, N]; centers: integers [B, entries] (or [B] when entries == 1), the lag output of
+        xcorr_topk_f32 with k = entries as it is.  Arguments are checked on the host (ValueError) before anything is uploaded.
+        Returns (r, coef, frac, ret): r[..., d + h] the time-domain sum at index (centre's index + d) mod 2N in float64, coef the
+        reference's Pearson coefficient at that lag in the direct form (None with coef=False: no Pearson pass), both of the shape of
+        centers + (2h + 1,); frac the vertex of the parabola through r[..., h - 1 : h + 2] and ret (0, or -2 for a centre outside
+        [-N, N-1], whose values are NaN) of the shape of centers."""
+        s, t, c, batch, ss, ts, h, entries = curve_args(self.sample_len, source, sample, centers, half_width, entries)
+        return self._staged_curve((s, t, c), c.shape, h, coef, lambda d_s, d_t, d_c, *d_out: self.xcorr_curve_dev(
+            d_s, ss, d_t, ts, batch, entries, d_c, h, *d_out))
+
+    def xcorr_pool_curve_f32(self, sources, samples, centers, pairs=None, half_width=1, entries=1, coef=True):
+        """xcorr_curve_f32 for pairs of two pools (asx_xcorr_pool_curve_f32_dev): the pools and pairs of xcorr_pool_f32, centers
+        integers [B, entries] (or [B] when entries == 1) with pairs, [S, R, entries] (or [S, R]) without.  Returns (r, coef, frac,
+        ret) as xcorr_curve_f32; every entry of a pair with an index outside its pool has ret -4 and NaN values."""
+        n = self.sample_len
+        s, t, pr, c, batch, h, entries = pool_curve_args(n, sources, samples, centers, pairs, half_width, entries)
+        return self._staged_curve((s, t, pr, c), c.shape, h, coef, lambda d_s, d_t, d_pr, d_c, *d_out: self.xcorr_pool_curve_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, batch, entries, d_c, h, *d_out))
 
     def xcorr_topk_f32(self, source, sample, k, min_separation, windows=None):
         """The k strongest separated lags per pair (asx_xcorr_topk_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N];
