@@ -30,14 +30,15 @@
  *   coef[i] are still written, exactly as the reference leaves them).
  *   ret[i] = -2 (asx_xcorr_windowed_f32_dev, and asx_xcorr_phat_f32_dev with rows): pair i's lag
  *   window was not a window inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.  (asx_xcorr_curve_f32_dev and
- *   asx_xcorr_pool_curve_f32_dev: an entry's centre was not a lag inside [-N, N-1]; NaN in all its values.)
+ *   asx_xcorr_pool_curve_f32_dev: an entry's centre was not a lag inside [-N, N-1]; NaN in all its values.  The same in
+ *   asx_xcorr_track_f32_dev and asx_xcorr_pool_track_f32_dev, with used = 0.)
  *   ret = -3 (asx_xcorr_topk_f32_dev and asx_xcorr_pool_topk_f32_dev only): no lag is left for
  *   this entry of the pair (its window minus the zones around the earlier entries is empty);
  *   lag = 0 and coef = NaN.
  *   ret = -4 (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_pool_phat_f32_dev and
  *   asx_xcorr_pool_phat_sub_f32_dev only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
  *   form: in all k entries of the pair).  It takes precedence over -2 and -3.  (asx_xcorr_pool_curve_f32_dev: NaN in all
- *   the values of the pair's entries.)
+ *   the values of the pair's entries.  asx_xcorr_pool_track_f32_dev: the same, with used = 0.)
  */
 #ifndef AUDIOSYNC_XCORR_HIP_H
 #define AUDIOSYNC_XCORR_HIP_H
@@ -667,6 +668,68 @@ int asx_xcorr_pool_curve_f32_dev(asx_plan *plan,
                                  const int32_t *d_pairs,
                                  size_t batch, int entries, const int64_t *d_center, int half_width,
                                  double *d_r, double *d_coef, double *d_frac, int32_t *d_ret, void *stream);
+
+/* A lag track: the exact r per time segment around given lags, and a drift fit.  Every other call returns one lag for a whole window
+ * of N frames, which assumes that the lag is constant over the window.  Two recorders never share a clock: at 20 - 100 ppm of
+ * relative drift the lag moves by dozens of frames across a 30 s window and a whitened peak smears away.  This call is the curve
+ * call's sibling, a consumer behind any call on the lags it returned: it keeps the curve's sum apart per stretch of time, over a lag
+ * range wide enough to hold a drifting peak -- r as a function of (time segment, lag) -- and fits a line through its ridge.  It runs
+ * no transform and no launch group, so it works on every plan, packed ones included.
+ *   Inputs: exactly those of asx_xcorr_curve_f32_dev -- strides in floats, a stride of 0 broadcasts, strides below the track length
+ * are allowed; the 16-byte layout rule on real-column plans only; 1 <= entries <= ASX_TOPK_MAX; entry e = i * entries + j belongs
+ * to pair i; d_center[e] is a lag in the d_lag convention, read when the kernels run.  1 <= half_width <= ASX_TRACK_HALF_MAX.
+ * 1 <= segments <= min(ASX_TRACK_SEG_MAX, N).
+ *   Definitions, with h = half_width, n = 2h + 1, S = segments and p the centre's index (lag l >= 0 is index l, lag l < 0 index
+ * 2N + l): segment s covers the sample's frames [b_s, b_{s+1}) with b_s = floor(s * N / S) in 64-bit integers; its time is
+ * t_s = (b_s + b_{s+1} - 1) / 2, the mean frame index, exact in float64.
+ *   d_r[(e * S + s) * n + (d + h)] = r_s[d] = sum_{n in segment s} source[(n + p + d) mod 2N] * sample[n] for d = -h .. h: in float64
+ * (products of two float32 values are exact), signed and unnormalised; neighbours are circular in index space, as in the curve
+ * call.  Each value is within len_s * 2^-53 * sum |products of its terms| of the exact sum, and over s the sums add up to the curve
+ * call's r[(p + d) mod 2N].
+ *   d_seg[(e * S + s) * 2 + {0, 1}] = {off_s, w_s}.  m_s is the d with the largest |r_s[d]|, scanned from d = -h upwards with fabs
+ * and a strict >: the smallest d wins ties and an all-zero segment gives -h.  w_s = |r_s[m_s]|.  An interior peak, -h < m_s < h:
+ * off_s = (double)m_s + frac, one add, with frac the parabola rule of asx_xcorr_phat_sub_f32_dev on r_s[m_s - 1], r_s[m_s],
+ * r_s[m_s + 1].  At an edge off_s = -h or +h exactly.  A segment is used when its peak is interior and all of its n values are
+ * finite.  d_seg may be NULL.  It is offered so that a caller can fit robustly themselves (a median slope, an outlier cut) where
+ * the weighted line below is not what they want.
+ *   d_used[e] = the number of used segments.
+ *   d_fit[e * 3 + {0, 1, 2}] = {drift, lag0, rms}: the weighted least-squares line through (t_s, off_s) over the used segments with
+ * weights w_s, in float64, the used segments taken in ascending s: W = sum w, tbar = sum w t / W, ybar = sum w off / W,
+ * Stt = sum w (t - tbar)^2, Sty = sum w (t - tbar)(off - ybar), drift = Sty / Stt, lag0 = ybar - drift * tbar,
+ * rms = sqrt(sum w (off - (lag0 + drift * t))^2 / W).  With fewer than two used segments all three are NaN: segments = 1 is a wide
+ * curve with no fit.  Meaning: sample frame n lines up with source frame n + center + lag0 + drift * n, so 1e6 * drift is the clock
+ * offset in ppm.  Within a segment the lag still moves: a segment smears by drift * N / S frames, so pick S large enough that this
+ * stays near or below one frame for the drift you expect, and half_width large enough to hold drift * N / 2 on either side.
+ *   d_ret[e] = 0, or -2 for a centre outside [-N, N-1]: such an entry gets NaN in all of its r, seg and fit values and used = 0, and
+ * reads nothing; the other entries are untouched, bit for bit.
+ *   Refusals: a NULL plan, track, d_center, d_r, d_fit, d_used or d_ret, entries, half_width or segments out of range, and the curve
+ * call's layout refusals return -1 with nothing launched and the outputs untouched.  batch == 0 returns 0.
+ *   What the call never does.  It allocates nothing after plan creation (asx_plan_workspace_bytes stays the same), never
+ * synchronises the host, and touches no counter and no bank.  It behaves the same whatever asx_plan_set_exact,
+ * asx_plan_set_pearson, asx_plan_set_prune, asx_plan_set_qstore or the plan's lag window say.  It uses the plan's lane workspaces,
+ * so the one-stream-at-a-time rule of asx_xcorr_batch_f32_dev applies.  Every value of an entry is independent of the batch size,
+ * of the entry's position in the batch and of the plan's max_batch: the reduction tree is fixed by N, S and h alone.
+ *   Cost: one pass over the entry's tracks, 8N bytes, per tile of 17 lags (h = 8: one pass, h = 64: eight).  Measured: DESIGN.md. */
+#define ASX_TRACK_HALF_MAX 64
+#define ASX_TRACK_SEG_MAX  64
+int asx_xcorr_track_f32_dev(asx_plan *plan,
+                            const float *d_source, size_t source_stride,
+                            const float *d_sample, size_t sample_stride,
+                            size_t batch, int entries, const int64_t *d_center, int half_width, int segments,
+                            double *d_r, double *d_seg, double *d_fit, int32_t *d_used, int32_t *d_ret, void *stream);
+
+/* ... for pairs of two track pools: the pools, d_pairs and batch of asx_xcorr_pool_curve_f32_dev with the remaining arguments and
+ * the outputs of asx_xcorr_track_f32_dev.  Real-column plans only, as every pool call.  It never touches, fills or grows the bank.
+ *   d_ret[e] = -4 for an entry whose pair's row names a track outside its pool (over -2): NaN in all of its r, seg and fit values,
+ * used = 0, nothing read outside the pools, the other entries untouched, bit for bit.
+ *   Returns -1 with the outputs untouched and nothing launched on the refusals of asx_xcorr_track_f32_dev and on the pool refusals of
+ * asx_xcorr_pool_curve_f32_dev.  batch == 0 returns 0. */
+int asx_xcorr_pool_track_f32_dev(asx_plan *plan,
+                                 const float *d_sources, size_t source_stride, size_t nsources,
+                                 const float *d_samples, size_t sample_stride, size_t nsamples,
+                                 const int32_t *d_pairs,
+                                 size_t batch, int entries, const int64_t *d_center, int half_width, int segments,
+                                 double *d_r, double *d_seg, double *d_fit, int32_t *d_used, int32_t *d_ret, void *stream);
 
 /* ---- growing-window (streaming) mode ------------------------------------ */
 

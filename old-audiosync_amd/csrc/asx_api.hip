@@ -1682,6 +1682,70 @@ extern "C" int asx_xcorr_pool_curve_f32_dev(asx_plan *p, const float *d_sources,
                       d_pairs, batch, entries, d_center, half_width, d_r, d_coef, d_frac, d_ret, stream);
 }
 
+// ---------------------------------------------------------------------------
+// the lag track (asx_xcorr_track_f32_dev, asx_xcorr_pool_track_f32_dev): the curve's sibling -- r per time segment over a wide lag
+// range, each segment's peak and the drift line through the peaks.  No transform, no group: k_track_dots over the tracks themselves
+// and k_track_fit behind it, in slices of a launch group, in lane 0's records and psums.
+// ---------------------------------------------------------------------------
+static int track_call(asx_plan *p, const char *fn, bool pooled, const float *d_src, size_t src_stride, size_t nsrc, const float *d_smp,
+                      size_t smp_stride, size_t nsmp, const int32_t *d_pairs, size_t batch, int entries, const int64_t *d_center,
+                      int half_width, int segments, double *d_r, double *d_seg, double *d_fit, int32_t *d_used, int32_t *d_ret,
+                      void *stream)
+{
+    if (!p || !d_src || !d_smp || !d_center || !d_r || !d_fit || !d_used || !d_ret) return fail("%s: null argument", fn);
+    if (entries < 1 || entries > ASX_TOPK_MAX) return fail("%s: entries = %d is not in [1, %d]", fn, entries, ASX_TOPK_MAX);
+    if (half_width < 1 || half_width > ASX_TRACK_HALF_MAX)
+        return fail("%s: half_width = %d is not in [1, %d]", fn, half_width, ASX_TRACK_HALF_MAX);
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
+    const AsxDev &P = p->dev;
+    if (segments < 1 || segments > ASX_TRACK_SEG_MAX || (uint64_t)segments > (uint64_t)P.N)
+        return fail("%s: segments = %d is not in [1, min(%d, N = %u)]", fn, segments, ASX_TRACK_SEG_MAX, (unsigned)P.N);
+    if (pooled && P.rlayout != 1) return fail("%s: pool calls need a real-column plan (asx_plan_layout() == 1)", fn);
+    if (P.rlayout) {
+        if (((uintptr_t)d_src & 15u) || ((uintptr_t)d_smp & 15u))
+            return fail("%s: real-column plans need 16-byte aligned inputs (source %p, sample %p)", fn, (const void *)d_src,
+                        (const void *)d_smp);
+        if ((src_stride & 3u) || (smp_stride & 3u))
+            return fail("%s: real-column plans need strides that are multiples of 4 floats (source_stride %zu, sample_stride %zu)", fn,
+                        src_stride, smp_stride);
+    }
+    if (pooled) {
+        if (nsrc > INT32_MAX || nsmp > INT32_MAX) return fail("%s: a pool of more than 2^31 - 1 tracks", fn);
+        if (!d_pairs && batch != nsrc * nsmp)
+            return fail("%s: without pairs the batch is every combination, %zu x %zu, not %zu", fn, nsrc, nsmp, batch);
+    }
+    if (batch == 0) return 0;
+    if (pooled && (nsrc == 0 || nsmp == 0)) return fail("%s: an empty pool (%zu sources, %zu samples) for %zu pairs", fn, nsrc, nsmp, batch);
+    asx_plan::Lane &W = p->lanes[0];
+    const AsxTrack A{ d_center, d_r, d_seg, d_fit, d_used, d_ret, P.N, entries, half_width, segments, pooled ? d_pairs : nullptr,
+                      pooled ? (uint64_t)nsrc : 0u, pooled ? (uint64_t)nsmp : 0u, (uint64_t)src_stride, (uint64_t)smp_stride };
+    const size_t total = batch * (size_t)entries;
+    for (size_t e0 = 0; e0 < total; e0 += p->group)
+        asx_launch_track(d_src, d_smp, A, e0, (int)std::min(p->group, total - e0), W.pool, W.psums, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int asx_xcorr_track_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                       size_t sample_stride, size_t batch, int entries, const int64_t *d_center, int half_width,
+                                       int segments, double *d_r, double *d_seg, double *d_fit, int32_t *d_used, int32_t *d_ret,
+                                       void *stream)
+{
+    return track_call(p, "asx_xcorr_track_f32_dev", false, d_source, source_stride, 0, d_sample, sample_stride, 0, nullptr, batch,
+                      entries, d_center, half_width, segments, d_r, d_seg, d_fit, d_used, d_ret, stream);
+}
+
+extern "C" int asx_xcorr_pool_track_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                            const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                            size_t batch, int entries, const int64_t *d_center, int half_width, int segments,
+                                            double *d_r, double *d_seg, double *d_fit, int32_t *d_used, int32_t *d_ret, void *stream)
+{
+    return track_call(p, "asx_xcorr_pool_track_f32_dev", true, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples,
+                      d_pairs, batch, entries, d_center, half_width, segments, d_r, d_seg, d_fit, d_used, d_ret, stream);
+}
+
 // diagnostic (not in the public header): the bank's capacity in tracks and how many pool calls have filled it
 extern "C" int asx_plan_debug_bank(asx_plan *p, uint64_t *nsrc, uint64_t *nsmp, uint64_t *fills)
 {

@@ -615,6 +615,31 @@ void asx_launch_curve_r(const float *src, const float *smp, const AsxCurve &A, s
 // count at most a launch group: each one's segment to seg and its tracks' offsets to pl, what asx_launch_pearson's listed form reads.
 // An invalid entry's get an empty segment at offset 0: nothing is read and the coefficient is NaN.
 void asx_launch_curve_segs(const AsxCurve &A, size_t first, int count, AsxSeg *seg, AsxPoolPair *pl, hipStream_t s);
+// The lag track (asx_xcorr_track_f32_dev, asx_xcorr_pool_track_f32_dev; xcorr_kernels.hip: k_track_dots, k_track_fit): one call's
+// arguments as its kernels take them, by value.  Entries, centres, pairs and pools as in AsxCurve; S time segments, segment s the
+// sample's frames [floor(s N / S), floor((s + 1) N / S)).
+#define ASX_TRACK_HALF_MAX 64
+#define ASX_TRACK_SEG_MAX 64
+struct AsxTrack {
+    const int64_t *center;  // [batch * entries]
+    double *r;              // [batch * entries][S][2 h + 1]
+    double *seg;            // [batch * entries][S][2] {off, w}, or null
+    double *fit;            // [batch * entries][3] {drift, lag0, rms}
+    int32_t *used;          // [batch * entries]
+    int32_t *ret;           // [batch * entries]
+    uint32_t N;
+    int entries, h, S;
+    const int32_t *rows;
+    uint64_t nsrc, nsmp, src_stride, smp_stride;
+};
+// blocks of k_track_dots per (segment, lag tile): floor(asx_curve_blocks(N) / (S * tiles)), tiles = ceil((2h + 1) / ASX_CURVE_N), so
+// that an entry's partial sums fit its share of the lane's psums as the curve's do; at least one, which writes its values itself.
+// By N, S and h alone: the reduction tree of an entry does not depend on the batch or the plan's max_batch.
+unsigned asx_track_blocks(uint32_t N, int segments, int half_width);
+// every output of entries first .. first + count - 1, count at most a launch group: the pool form's records go to pl (the lane's,
+// [count]), the blocks' partial sums to part (the lane's psums); k_track_fit runs last and owns an invalid entry's outputs
+void asx_launch_track(const float *src, const float *smp, const AsxTrack &A, size_t first, int count, AsxPoolPair *pl, double *part,
+                      hipStream_t s);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 // pool calls: each pair's record (out) and its two slots' norm partials and band sums (band may be null) into the group's places

@@ -1621,6 +1621,216 @@ __global__ __launch_bounds__(ASX_THREADS) void k_curve_segs(AsxCurve A, size_t f
 }
 
 // ---------------------------------------------------------------------------
+// The lag track (asx_xcorr_track_f32_dev, asx_xcorr_pool_track_f32_dev): the curve's sum kept apart per time segment,
+//     r_s[d] = sum_{b_s <= n < b_{s+1}} source[(n + p + d) mod 2N] * sample[n],   b_s = floor(s N / S),   d = -h .. h,
+// over a lag range wide enough to hold a drifting peak, and behind it each segment's peak and the weighted line through the peaks.
+// ---------------------------------------------------------------------------
+// the first frame of segment s
+__device__ __forceinline__ uint64_t track_bound(uint32_t N, int S, int s) { return (uint64_t)s * (uint64_t)N / (uint64_t)S; }
+// the ret of entry e: k_curve_dots' rule (pl: the pool form's records, indexed by the entry's place in the slice, or null)
+__device__ __forceinline__ int32_t track_ret(const AsxTrack &A, size_t e, size_t le, const AsxPoolPair *pl)
+{
+    const int64_t c = A.center[e];
+    if (pl && (pl[le].flags & ASX_POOL_INVALID)) return -4;
+    return (c < -(int64_t)A.N || c > (int64_t)A.N - 1) ? -2 : 0;
+}
+
+// grid (blocks per segment and tile, segments * tiles, entries of the slice): k_curve_dots' sweep restricted to segment s =
+// blockIdx.y / tiles and to the lags d = -h + ASX_CURVE_N tile .. of tile = blockIdx.y % tiles, at most ASX_CURVE_N of them (the last
+// tile may be short).  Block x takes the segment's frames [b_s + x chunk, b_s + (x + 1) chunk); a segment starts at any frame, so the
+// sample is read with 4-byte aligned loads of four.  The same order as k_curve_dots: a thread's samples ascending, the lanes of a
+// wave, the waves, and, with more than one block, the blocks in order (k_track_sum, from `part`); one block writes its values to
+// A.r itself.  An entry that is not valid reads and writes nothing: k_track_fit fills in all of its outputs.
+template <class Where>
+__global__ __launch_bounds__(ASX_THREADS) void k_track_dots(const float *__restrict__ src, const float *__restrict__ smp, Where at,
+                                                             AsxTrack A, size_t first, int tiles, double *__restrict__ part)
+{
+    constexpr bool listed = std::is_same<Where, AsxAtList>::value;
+    __shared__ __attribute__((aligned(16))) float xs[ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX];
+    __shared__ double red[ASX_THREADS / 64][ASX_CURVE_N];
+    const int tid = threadIdx.x, h = A.h, n = 2 * h + 1;
+    const size_t le = blockIdx.z, e = first + le;
+    const size_t rec = listed ? le : e / (size_t)A.entries;
+    const uint32_t N = A.N, L = 2u * N;
+    const int64_t c = A.center[e];
+    bool valid = !(c < -(int64_t)N || c > (int64_t)N - 1);
+    if constexpr (listed) {
+        if (at.pl[rec].flags & ASX_POOL_INVALID) valid = false;
+    }
+    if (!valid) return; // (block-uniform: nobody is left at a barrier)
+    const int sg = (int)blockIdx.y / tiles, tile = (int)blockIdx.y - sg * tiles;
+    const int d0 = tile * ASX_CURVE_N, nt = n - d0 < ASX_CURVE_N ? n - d0 : ASX_CURVE_N; // the tile's first value and how many
+    const uint32_t i0 = (curve_first(c, N, h) + (uint32_t)d0 % L) % L;
+    const float *x = src + at.src_off(rec);
+    const float *y = smp + at.smp_off(rec);
+    const uint64_t b0 = track_bound(N, A.S, sg), b1 = track_bound(N, A.S, sg + 1);
+    const uint32_t chunk = (((uint32_t)(b1 - b0) + gridDim.x - 1) / gridDim.x + 3u) & ~3u;
+    const uint64_t lo = b0 + (uint64_t)blockIdx.x * chunk;
+    const uint64_t hi = lo + chunk < b1 ? lo + chunk : b1;
+    double acc[ASX_CURVE_N];
+#pragma unroll
+    for (int j = 0; j < ASX_CURVE_N; j++) acc[j] = 0.0;
+    for (uint64_t n0 = lo; n0 < hi; n0 += ASX_CURVE_SWEEP) {
+        const uint32_t cnt = hi - n0 < (uint64_t)ASX_CURVE_SWEEP ? (uint32_t)(hi - n0) : (uint32_t)ASX_CURVE_SWEEP;
+        // the thread's four samples; past the block's end: zeros, which meet zeros below
+        const uint32_t t4 = 4u * (uint32_t)tid;
+        asx_f4v yq = { 0.0f, 0.0f, 0.0f, 0.0f };
+        if (t4 + 3u < cnt) yq = *reinterpret_cast<const asx_f4u *>(y + n0 + t4);
+        else {
+            if (t4 < cnt) yq.x = y[n0 + t4];
+            if (t4 + 1u < cnt) yq.y = y[n0 + t4 + 1u];
+            if (t4 + 2u < cnt) yq.z = y[n0 + t4 + 2u];
+        }
+        // xs[t] = source[(n0 + i0 + t) mod 2N] for t < cnt + nt - 1, zero behind
+        const uint32_t g0 = (uint32_t)((n0 + i0) % L), need = cnt + (uint32_t)nt - 1u;
+        auto wrapped = [&](uint32_t i) { if (i >= L) { i -= L; if (i >= L) i %= L; } return i; };
+        for (uint32_t t = t4; t < (uint32_t)(ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX); t += (uint32_t)ASX_CURVE_SWEEP) {
+            asx_f4v v = { 0.0f, 0.0f, 0.0f, 0.0f };
+            if (t < need) {
+                const uint32_t g = wrapped(g0 + t);
+                if (t + 3u < need && g + 3u < L) v = *reinterpret_cast<const asx_f4u *>(x + g);
+                else {
+                    v.x = x[g];
+                    if (t + 1u < need) v.y = x[wrapped(g0 + t + 1u)];
+                    if (t + 2u < need) v.z = x[wrapped(g0 + t + 2u)];
+                    if (t + 3u < need) v.w = x[wrapped(g0 + t + 3u)];
+                }
+            }
+            *reinterpret_cast<asx_f4v *>(xs + t) = v;
+        }
+        __syncthreads();
+        double w[4 + 2 * ASX_NEAR_MAX];
+#pragma unroll
+        for (int q = 0; q < (4 + 2 * ASX_NEAR_MAX) / 4; q++) {
+            asx_f4v v = { 0.0f, 0.0f, 0.0f, 0.0f };
+            if (4 * q < 3 + nt) v = *reinterpret_cast<const asx_f4v *>(xs + t4 + 4u * (uint32_t)q);
+            w[4 * q] = (double)v.x; w[4 * q + 1] = (double)v.y; w[4 * q + 2] = (double)v.z; w[4 * q + 3] = (double)v.w;
+        }
+        const double y0 = (double)yq.x, y1 = (double)yq.y, y2 = (double)yq.z, y3 = (double)yq.w;
+#pragma unroll
+        for (int j = 0; j < ASX_CURVE_N; j++) {
+            if (j < nt) {
+                double a = acc[j];
+                a = fma(w[j], y0, a);
+                a = fma(w[j + 1], y1, a);
+                a = fma(w[j + 2], y2, a);
+                a = fma(w[j + 3], y3, a);
+                acc[j] = a;
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < ASX_CURVE_N; j++) {
+        if (j < nt) {
+            const double s = wave_sum(acc[j]);
+            if ((tid & 63) == 0) red[tid >> 6][j] = s;
+        }
+    }
+    __syncthreads();
+    if (tid < nt) {
+        const double v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+        if (gridDim.x == 1) A.r[(e * (size_t)A.S + (size_t)sg) * (size_t)n + (size_t)(d0 + tid)] = v;
+        else part[((le * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * ASX_CURVE_N + tid] = v;
+    }
+}
+
+// grid (segments * tiles, entries of the slice), one wave: a segment's tile from its nb partial sums in block order
+__global__ __launch_bounds__(64) void k_track_sum(AsxTrack A, size_t first, int tiles, unsigned nb, const double *__restrict__ part,
+                                                   const AsxPoolPair *__restrict__ pl)
+{
+    const int tid = threadIdx.x, n = 2 * A.h + 1;
+    const size_t le = blockIdx.y, e = first + le;
+    if (track_ret(A, e, le, pl)) return;
+    const int sg = (int)blockIdx.x / tiles, d0 = ((int)blockIdx.x - sg * tiles) * ASX_CURVE_N;
+    if (tid >= ASX_CURVE_N || d0 + tid >= n) return;
+    const double *p = part + (le * gridDim.x + blockIdx.x) * nb * ASX_CURVE_N + tid;
+    double s = p[0];
+    for (unsigned b = 1; b < nb; b++) s += p[(size_t)b * ASX_CURVE_N];
+    A.r[(e * (size_t)A.S + (size_t)sg) * (size_t)n + (size_t)(d0 + tid)] = s;
+}
+
+// grid (entries of the slice), one wave, behind the entry's finished r: lane s takes segment s -- its peak m_s (the largest |r_s[d]|
+// scanned from d = -h upwards, strict >), off_s = m_s + frac (one add; m_s alone at an edge) and w_s = |r_s[m_s]| -- then lane 0 the
+// weighted line through (t_s, off_s) of the used segments in ascending s.  An entry that is not valid gets NaN everywhere, used 0.
+__global__ __launch_bounds__(64) void k_track_fit(AsxTrack A, size_t first, const AsxPoolPair *__restrict__ pl)
+{
+    __shared__ double ts[ASX_TRACK_SEG_MAX], offs[ASX_TRACK_SEG_MAX], ws[ASX_TRACK_SEG_MAX];
+    __shared__ int use[ASX_TRACK_SEG_MAX];
+    const int tid = threadIdx.x, h = A.h, n = 2 * h + 1, S = A.S;
+    const size_t le = blockIdx.x, e = first + le;
+    const int32_t rv = track_ret(A, e, le, pl);
+    if (rv) { // (block-uniform)
+        double *r = A.r + e * (size_t)S * (size_t)n;
+        for (int i = tid; i < S * n; i += 64) r[i] = (double)NAN;
+        if (A.seg)
+            for (int i = tid; i < 2 * S; i += 64) A.seg[e * (size_t)S * 2 + i] = (double)NAN;
+        if (tid < 3) A.fit[e * 3 + tid] = (double)NAN;
+        if (tid == 0) { A.used[e] = 0; A.ret[e] = rv; }
+        return;
+    }
+    if (tid < S) {
+        const double *r = A.r + (e * (size_t)S + (size_t)tid) * (size_t)n;
+        int m = 0;
+        double best = fabs(r[0]);
+        bool finite = r[0] - r[0] == 0.0;
+        for (int j = 1; j < n; j++) {
+            const double v = r[j], a = fabs(v);
+            if (!(v - v == 0.0)) finite = false;
+            if (a > best) { best = a; m = j; }
+        }
+        const bool interior = m > 0 && m < n - 1;
+        double off = (double)(m - h);
+        if (interior) off = (double)(m - h) + asx_parabola_frac(r[m - 1], r[m], r[m + 1]);
+        const double w = fabs(r[m]);
+        if (A.seg) {
+            A.seg[(e * (size_t)S + (size_t)tid) * 2] = off;
+            A.seg[(e * (size_t)S + (size_t)tid) * 2 + 1] = w;
+        }
+        const uint64_t b0 = track_bound(A.N, S, tid), b1 = track_bound(A.N, S, tid + 1);
+        ts[tid] = (double)(b0 + b1 - 1u) * 0.5;
+        offs[tid] = off;
+        ws[tid] = w;
+        use[tid] = interior && finite;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    int used = 0;
+    double W = 0.0, swt = 0.0, swy = 0.0;
+    for (int s = 0; s < S; s++) {
+        if (!use[s]) continue;
+        used++;
+        W += ws[s];
+        swt += ws[s] * ts[s];
+        swy += ws[s] * offs[s];
+    }
+    double drift = (double)NAN, lag0 = (double)NAN, rms = (double)NAN;
+    if (used >= 2) {
+        const double tbar = swt / W, ybar = swy / W;
+        double Stt = 0.0, Sty = 0.0, res = 0.0;
+        for (int s = 0; s < S; s++) {
+            if (!use[s]) continue;
+            const double dt = ts[s] - tbar;
+            Stt += ws[s] * dt * dt;
+            Sty += ws[s] * dt * (offs[s] - ybar);
+        }
+        drift = Sty / Stt;
+        lag0 = ybar - drift * tbar;
+        for (int s = 0; s < S; s++) {
+            if (!use[s]) continue;
+            const double d = offs[s] - (lag0 + drift * ts[s]);
+            res += ws[s] * d * d;
+        }
+        rms = sqrt(res / W);
+    }
+    A.fit[e * 3] = drift;
+    A.fit[e * 3 + 1] = lag0;
+    A.fit[e * 3 + 2] = rms;
+    A.used[e] = used;
+    A.ret[e] = 0;
+}
+
+// ---------------------------------------------------------------------------
 // second look, DC removal (second_look, asx_api.hip): one pair, one block each.  An offset of hundreds of standard deviations
 // in BOTH tracks makes the float32 error bound (proportional to |source|_2 |sample|_2) wider than the whole range of
 // r, every lag a near-tie.  r'[k] = sum (source[n+k] - m) sample[n] = r[k] - m * sum(sample) for ANY constant m: the
@@ -1997,6 +2207,34 @@ void asx_launch_curve_segs(const AsxCurve &A, size_t first, int count, AsxSeg *s
 {
     hipLaunchKernelGGL(k_curve_segs, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, A, first, count,
                        seg, pl);
+}
+
+unsigned asx_track_blocks(uint32_t N, int segments, int half_width)
+{
+    const unsigned tiles = (2u * (unsigned)half_width + ASX_CURVE_N) / (unsigned)ASX_CURVE_N;
+    const unsigned nb = asx_curve_blocks(N) / ((unsigned)segments * tiles);
+    return nb < 1u ? 1u : nb;
+}
+
+void asx_launch_track(const float *src, const float *smp, const AsxTrack &A, size_t first, int count, AsxPoolPair *pl, double *part,
+                      hipStream_t s)
+{
+    const int tiles = (2 * A.h + ASX_CURVE_N) / ASX_CURVE_N; // ceil((2h + 1) / ASX_CURVE_N)
+    const unsigned nb = asx_track_blocks(A.N, A.S, A.h);
+    const dim3 grid(nb, (unsigned)(A.S * tiles), (unsigned)count), block(ASX_THREADS);
+    const AsxPoolPair *list = A.nsrc ? pl : nullptr;
+    if (A.nsrc) {
+        const AsxCurve C{ A.center, nullptr, nullptr, nullptr, A.N, A.entries, A.h, A.rows, A.nsrc, A.nsmp, A.src_stride, A.smp_stride };
+        hipLaunchKernelGGL(k_curve_resolve, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), block, 0, s, C, first, count, pl);
+        hipLaunchKernelGGL(k_track_dots<AsxAtList>, grid, block, 0, s, src, smp, AsxAtList{ pl }, A, first, tiles, part);
+    } else {
+        hipLaunchKernelGGL(k_track_dots<AsxAtPitch>, grid, block, 0, s, src, smp, AsxAtPitch{ (size_t)A.src_stride, (size_t)A.smp_stride },
+                           A, first, tiles, part);
+    }
+    if (nb > 1u)
+        hipLaunchKernelGGL(k_track_sum, dim3((unsigned)(A.S * tiles), (unsigned)count), dim3(64), 0, s, A, first, tiles, nb,
+                           (const double *)part, list);
+    hipLaunchKernelGGL(k_track_fit, dim3((unsigned)count), dim3(64), 0, s, A, first, list);
 }
 
 void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t s)

@@ -72,6 +72,9 @@ _HEADER_SIGNATURES = {
                                                _vp, _vp, _vp]),
     "asx_xcorr_curve_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_curve_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_track_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_pool_track_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp,
+                                            _vp]),
     "asx_xcorr_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_band_debug_r_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -126,6 +129,8 @@ ABI_SYMBOLS = list(_HEADER_SIGNATURES)
 
 TOPK_MAX = 8  # ASX_TOPK_MAX, include/audiosync/xcorr_hip.h
 NEAR_MAX = 8  # ASX_NEAR_MAX, include/audiosync/xcorr_hip.h
+TRACK_HALF_MAX = 64  # ASX_TRACK_HALF_MAX, include/audiosync/xcorr_hip.h
+TRACK_SEG_MAX = 64   # ASX_TRACK_SEG_MAX, include/audiosync/xcorr_hip.h
 
 
 class AsxError(RuntimeError):
@@ -541,6 +546,37 @@ def pool_curve_args(n, sources, samples, centers, pairs=None, half_width=1, entr
     s, t, pr, _, batch, _ = pool_args(n, sources, samples, pairs)
     c, _ = _centers(centers, (batch,) if pr is not None else (s.shape[0], t.shape[0]), entries)
     return s, t, pr, c, batch, h, entries
+
+
+def _track_option(n, half_width, segments, entries):
+    """-> (half_width, segments, entries) as ints; ValueError unless they are integers (no bools), half_width in [1, TRACK_HALF_MAX],
+    segments in [1, min(TRACK_SEG_MAX, n)] and entries in [1, TOPK_MAX]"""
+    def integer(v):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    if not integer(entries) or not 1 <= int(entries) <= TOPK_MAX:
+        raise ValueError("entries must be an integer in [1, %d], not %r" % (TOPK_MAX, entries))
+    if not integer(half_width) or not 1 <= int(half_width) <= TRACK_HALF_MAX:
+        raise ValueError("half_width must be an integer in [1, %d], not %r" % (TRACK_HALF_MAX, half_width))
+    if not integer(segments) or not 1 <= int(segments) <= min(TRACK_SEG_MAX, int(n)):
+        raise ValueError("segments must be an integer in [1, %d], not %r" % (min(TRACK_SEG_MAX, int(n)), segments))
+    return int(half_width), int(segments), int(entries)
+
+
+def track_args(n, source, sample, centers, half_width, segments, entries=1):
+    """Host checks of Plan.xcorr_track_f32 for a plan of sample length n: source, sample and centers as curve_args checks them,
+    half_width an integer in [1, TRACK_HALF_MAX], segments in [1, min(TRACK_SEG_MAX, n)], entries in [1, TOPK_MAX].  -> (source,
+    sample, centers, batch, source_stride, sample_stride, half_width, segments, entries).  ValueError on anything else."""
+    h, segs, entries = _track_option(n, half_width, segments, entries)
+    s, t, c, batch, ss, ts, _, _ = curve_args(n, source, sample, centers, 1, entries)
+    return s, t, c, batch, ss, ts, h, segs, entries
+
+
+def pool_track_args(n, sources, samples, centers, half_width, segments, pairs=None, entries=1):
+    """Host checks of Plan.xcorr_pool_track_f32: the pools, pairs and centers of pool_curve_args, the options of track_args.  ->
+    (sources, samples, pairs or None, centers, batch, half_width, segments, entries).  ValueError on anything else."""
+    h, segs, entries = _track_option(n, half_width, segments, entries)
+    s, t, pr, c, batch, _, _ = pool_curve_args(n, sources, samples, centers, pairs, 1, entries)
+    return s, t, pr, c, batch, h, segs, entries
 
 
 def position_rows(n, hop, batch, p_lo, p_hi):
@@ -964,6 +1000,23 @@ class Plan:
                                                   d_center or None, int(half_width), d_r or None, d_coef or None, d_frac or None,
                                                   d_ret or None, stream or None))
 
+    def xcorr_track_dev(self, d_src, src_stride, d_smp, smp_stride, batch, entries, d_center, half_width, segments, d_r, d_seg, d_fit,
+                        d_used, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_track_f32_dev -- around each of the batch * entries lags of d_center (int64), r per
+        time segment (d_r, float64 [batch * entries][segments][2 half_width + 1]), each segment's {offset, weight} (d_seg, [..][segments]
+        [2], may be 0), the drift line {drift, lag0, rms} (d_fit, [..][3]), the used segments (d_used, int32) and d_ret"""
+        _check(lib().asx_xcorr_track_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride), int(batch),
+                                             int(entries), d_center or None, int(half_width), int(segments), d_r or None,
+                                             d_seg or None, d_fit or None, d_used or None, d_ret or None, stream or None))
+
+    def xcorr_pool_track_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, batch, entries,
+                             d_center, half_width, segments, d_r, d_seg, d_fit, d_used, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_track_f32_dev -- xcorr_track_dev for the pairs of xcorr_pool_dev"""
+        _check(lib().asx_xcorr_pool_track_f32_dev(self._h, d_sources or None, int(source_stride), int(nsources), d_samples or None,
+                                                  int(sample_stride), int(nsamples), d_pairs or None, int(batch), int(entries),
+                                                  d_center or None, int(half_width), int(segments), d_r or None, d_seg or None,
+                                                  d_fit or None, d_used or None, d_ret or None, stream or None))
+
     def debug_prune(self, pair=0):
         """diagnostic: (upper bounds of |r| per column tile, the largest-bound tile) of `pair` of the last pruned group"""
         n = (self.split[1] + self.split[2] - 1) // self.split[2]
@@ -1141,6 +1194,37 @@ class Plan:
         s, t, pr, c, batch, h, entries = pool_curve_args(n, sources, samples, centers, pairs, half_width, entries)
         return self._staged_curve((s, t, pr, c), c.shape, h, coef, lambda d_s, d_t, d_pr, d_c, *d_out: self.xcorr_pool_curve_dev(
             d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, batch, entries, d_c, h, *d_out))
+
+    def _staged_track(self, inputs, shape, h, segs, launch):
+        """_staged for the track calls: outputs (r, seg, fit, used, ret) of shape + (S, 2h + 1), (S, 2), (3,), () and ()"""
+        with _Staging(self) as st:
+            d_in = [st.upload(a) for a in inputs]
+            shape = tuple(shape)
+            launch(*d_in, st.output(shape + (segs, 2 * h + 1), np.float64), st.output(shape + (segs, 2), np.float64),
+                   st.output(shape + (3,), np.float64), st.output(shape, np.int32), st.output(shape, np.int32))
+            return st.fetch()
+
+    def xcorr_track_f32(self, source, sample, centers, half_width, segments, entries=1):
+        """A lag track around given lags (asx_xcorr_track_f32_dev), behind any call on the lags it returned: the curve's sum kept
+        apart per time segment, and the drift line through the segments' peaks.  source, sample, centers and entries as in
+        xcorr_curve_f32; half_width h in [1, TRACK_HALF_MAX]; segments S in [1, min(TRACK_SEG_MAX, N)].  Arguments are checked on the
+        host (ValueError) before anything is uploaded.  Returns (r, seg, fit, used, ret): r[..., s, d + h] the sum over segment s
+        (the sample's frames floor(s N / S) .. floor((s + 1) N / S) - 1) at index (centre's index + d) mod 2N, seg[..., s, :] =
+        (offset of the segment's peak from the centre, its weight |r|), fit[..., :] = (drift in frames per frame, lag0, rms) of the
+        weighted line through the used segments (NaN with fewer than two), used their number, ret 0 or -2 (a centre outside
+        [-N, N-1]: NaN values, used 0) -- of the shape of centers plus the trailing axes named."""
+        s, t, c, batch, ss, ts, h, segs, entries = track_args(self.sample_len, source, sample, centers, half_width, segments, entries)
+        return self._staged_track((s, t, c), c.shape, h, segs, lambda d_s, d_t, d_c, *d_out: self.xcorr_track_dev(
+            d_s, ss, d_t, ts, batch, entries, d_c, h, segs, *d_out))
+
+    def xcorr_pool_track_f32(self, sources, samples, centers, half_width, segments, pairs=None, entries=1):
+        """xcorr_track_f32 for pairs of two pools (asx_xcorr_pool_track_f32_dev): the pools, pairs and centers of
+        xcorr_pool_curve_f32.  Returns (r, seg, fit, used, ret) as xcorr_track_f32; every entry of a pair with an index outside its
+        pool has ret -4, NaN values and used 0."""
+        n = self.sample_len
+        s, t, pr, c, batch, h, segs, entries = pool_track_args(n, sources, samples, centers, half_width, segments, pairs, entries)
+        return self._staged_track((s, t, pr, c), c.shape, h, segs, lambda d_s, d_t, d_pr, d_c, *d_out: self.xcorr_pool_track_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, batch, entries, d_c, h, segs, *d_out))
 
     def xcorr_topk_f32(self, source, sample, k, min_separation, windows=None):
         """The k strongest separated lags per pair (asx_xcorr_topk_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N];
