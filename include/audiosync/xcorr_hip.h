@@ -39,6 +39,9 @@
  *   asx_xcorr_pool_phat_sub_f32_dev only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
  *   form: in all k entries of the pair).  It takes precedence over -2 and -3.  (asx_xcorr_pool_curve_f32_dev: NaN in all
  *   the values of the pair's entries.  asx_xcorr_pool_track_f32_dev: the same, with used = 0.)
+ *   ret = -5 (asx_xcorr_warp_f32_dev and asx_xcorr_pool_warp_f32_dev only): an entry's drift line is not valid; NaN in all its
+ *   values and len = 0.  In these two calls -4 and -2 mean what they mean in the calls around given lags and take precedence, in
+ *   that order.
  */
 #ifndef AUDIOSYNC_XCORR_HIP_H
 #define AUDIOSYNC_XCORR_HIP_H
@@ -730,6 +733,75 @@ int asx_xcorr_pool_track_f32_dev(asx_plan *plan,
                                  const int32_t *d_pairs,
                                  size_t batch, int entries, const int64_t *d_center, int half_width, int segments,
                                  double *d_r, double *d_seg, double *d_fit, int32_t *d_used, int32_t *d_ret, void *stream);
+
+/* A warped correlation: the exact r and the Pearson coefficient along a drift line.  The track call reports how fast the lag moves;
+ * every coefficient of the other calls is the reference's Pearson coefficient at one constant lag, and on a drifting pair it
+ * collapses although the tracks match (white noise, 12 frames of drift over the window: 0.11 - 0.16 at the best constant lag, 1.0
+ * along the line).  This call takes the line and computes along it: the exact correlation around the line, the parabola vertex
+ * across it, and the reference's Pearson coefficient of the frames that line up -- a confidence that asx_results_to_ms_dev can
+ * test.  It is a consumer behind the track call, in one pass over the two tracks; it runs no transform and no launch group, so it
+ * works on every plan, packed ones included.
+ *   Inputs: exactly those of asx_xcorr_curve_f32_dev -- strides in floats, a stride of 0 broadcasts, strides below the track length
+ * are allowed; the 16-byte layout rule on real-column plans only; 1 <= entries <= ASX_TOPK_MAX; entry e = i * entries + j belongs
+ * to pair i; d_center[e] is a lag in the d_lag convention; 1 <= half_width <= ASX_NEAR_MAX.  Entry e's line is
+ * a = d_line[e * line_stride] (the drift, in frames per frame) and b = d_line[e * line_stride + 1] (lag0, in frames): sample frame
+ * n meets source frame n + center + lag0 + drift * n, rounded to the nearest frame.  line_stride counts doubles: 3 passes the track
+ * call's d_fit straight in, 2 is a packed array of lines, 0 is one line for every entry, 1 is refused.  Centres and lines are read
+ * when the kernels run.
+ *   Definitions, with N the plan's sample_len, h = half_width, c = d_center[e] and p the centre's index (lag l >= 0 is index l, lag
+ * l < 0 index 2N + l).
+ *   The shift: k_n = floor((b + a * (double)n) + 0.5) as an int64, all in float64, the multiply, the two adds and the floor each
+ * rounded on their own, no fused multiply-add: numpy's np.floor((b + a * n) + 0.5) is the same integer for every n.
+ *   A valid line: a and b finite, |a| <= ASX_WARP_DRIFT_MAX and |b| <= N.  Then n + k_n is non-decreasing, four consecutive frames
+ * hold at most one step and a sweep of 1024 frames spans at most 17 steps.
+ *   d_r[e * (2h + 1) + (d + h)] = sum_{n<N} source[(n + p + d + k_n) mod 2N] * sample[n] for d = -h .. h, the mod mathematical
+ * (never negative): in float64 (products of two float32 values are exact), signed and unnormalised; circular in index space, as
+ * in the curve call.  Each value is within N * 2^-53 * sum |products of its terms| of the exact sum.  The line (0, 0) gives the
+ * curve call's r.
+ *   d_frac[e] = the parabola rule of asx_xcorr_phat_sub_f32_dev on the three centre values of d_r: the vertex across the line.
+ *   The lined-up frames: u_n = n + c + k_n, linear with no wrap, for d = 0; V = {n in [0, N) : 0 <= u_n < 2N}, one contiguous
+ * range; d_len[e] = |V|.  d_len may be NULL.  For the line (0, 0) V is the reference's segment for the lag c
+ * (src/cross_correlation.c:256-271).
+ *   d_coef[e] = pearson_coefficient() (src/cross_correlation.c:74-116) over the pairs (source[u_n], sample[n]), n in V: in float64
+ * from the float32 samples in the direct form, partial statistics with the exact pairwise merge of the direct Pearson kernels.  NaN
+ * when V is empty or a side is constant.
+ *   d_ret[e] = 0 for a computed entry; -1 when the coefficient is NaN (r, frac and len are still written), so that (d_center,
+ * d_coef, d_ret) feed asx_results_to_ms_dev as they stand; -2 for a centre outside [-N, N-1]; -5 for a line that is not valid,
+ * the NaN line that the track call returns with fewer than two used segments included.  -2 takes precedence over -5.  Such an
+ * entry gets NaN in r, frac and coef and len = 0, and reads nothing; the other entries are untouched, bit for bit.
+ *   Refusals: a NULL plan, track, d_center, d_line, d_r, d_frac, d_coef or d_ret, entries or half_width out of range,
+ * line_stride == 1, and the curve call's layout refusals return -1 with nothing launched and the outputs untouched.  batch == 0
+ * returns 0.
+ *   What the call never does.  It allocates nothing after plan creation (asx_plan_workspace_bytes stays the same), never
+ * synchronises the host, and touches no counter and no bank.  It behaves the same whatever asx_plan_set_exact,
+ * asx_plan_set_pearson, asx_plan_set_prune, asx_plan_set_qstore or the plan's lag window say.  It uses lane 0's records and psums,
+ * so the one-stream-at-a-time rule of asx_xcorr_batch_f32_dev applies.  Every value of an entry is independent of the batch size,
+ * of the entry's position in the batch and of the plan's max_batch: the reduction tree is fixed by N alone.
+ *   What is not offered: interpolation between frames (nearest frame only: the sums stay exact products of stored samples, and at
+ * the drifts of real clocks a frame is repeated or dropped once in 10^4 or more), a coefficient for d != 0, a piecewise path
+ * through the track call's d_seg.
+ *   Cost: one pass over the entry's tracks, 8N bytes.  Measured: DESIGN.md. */
+#define ASX_WARP_DRIFT_MAX 0.015625   /* 2^-6 */
+int asx_xcorr_warp_f32_dev(asx_plan *plan,
+                           const float *d_source, size_t source_stride,
+                           const float *d_sample, size_t sample_stride,
+                           size_t batch, int entries, const int64_t *d_center,
+                           const double *d_line, size_t line_stride, int half_width,
+                           double *d_r, double *d_frac, double *d_coef, int64_t *d_len, int32_t *d_ret, void *stream);
+
+/* ... for pairs of two track pools: the pools, d_pairs and batch of asx_xcorr_pool_curve_f32_dev with the remaining arguments and
+ * the outputs of asx_xcorr_warp_f32_dev.  Real-column plans only, as every pool call.  It never touches, fills or grows the bank.
+ *   d_ret[e] = -4 for an entry whose pair's row names a track outside its pool (over -2, which is over -5): NaN in r, frac and
+ * coef, len = 0, nothing read outside the pools, the other entries untouched, bit for bit.
+ *   Returns -1 with the outputs untouched and nothing launched on the refusals of asx_xcorr_warp_f32_dev and on the pool refusals of
+ * asx_xcorr_pool_curve_f32_dev.  batch == 0 returns 0. */
+int asx_xcorr_pool_warp_f32_dev(asx_plan *plan,
+                                const float *d_sources, size_t source_stride, size_t nsources,
+                                const float *d_samples, size_t sample_stride, size_t nsamples,
+                                const int32_t *d_pairs,
+                                size_t batch, int entries, const int64_t *d_center,
+                                const double *d_line, size_t line_stride, int half_width,
+                                double *d_r, double *d_frac, double *d_coef, int64_t *d_len, int32_t *d_ret, void *stream);
 
 /* ---- growing-window (streaming) mode ------------------------------------ */
 

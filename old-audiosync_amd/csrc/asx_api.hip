@@ -1746,6 +1746,70 @@ extern "C" int asx_xcorr_pool_track_f32_dev(asx_plan *p, const float *d_sources,
                       d_pairs, batch, entries, d_center, half_width, segments, d_r, d_seg, d_fit, d_used, d_ret, stream);
 }
 
+// ---------------------------------------------------------------------------
+// the warped correlation (asx_xcorr_warp_f32_dev, asx_xcorr_pool_warp_f32_dev): the curve's r, its frac and one Pearson coefficient
+// along a drift line per entry, what the track call's fit feeds.  No transform, no group: k_warp_dots over the tracks themselves and
+// k_warp_final behind it, in slices of a launch group, in lane 0's records and psums.
+// ---------------------------------------------------------------------------
+static int warp_call(asx_plan *p, const char *fn, bool pooled, const float *d_src, size_t src_stride, size_t nsrc, const float *d_smp,
+                     size_t smp_stride, size_t nsmp, const int32_t *d_pairs, size_t batch, int entries, const int64_t *d_center,
+                     const double *d_line, size_t line_stride, int half_width, double *d_r, double *d_frac, double *d_coef,
+                     int64_t *d_len, int32_t *d_ret, void *stream)
+{
+    if (!p || !d_src || !d_smp || !d_center || !d_line || !d_r || !d_frac || !d_coef || !d_ret) return fail("%s: null argument", fn);
+    if (entries < 1 || entries > ASX_TOPK_MAX) return fail("%s: entries = %d is not in [1, %d]", fn, entries, ASX_TOPK_MAX);
+    if (half_width < 1 || half_width > ASX_NEAR_MAX) return fail("%s: half_width = %d is not in [1, %d]", fn, half_width, ASX_NEAR_MAX);
+    if (line_stride == 1) return fail("%s: line_stride = 1: a line is two doubles (0: one line for every entry)", fn);
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
+    const AsxDev &P = p->dev;
+    if (pooled && P.rlayout != 1) return fail("%s: pool calls need a real-column plan (asx_plan_layout() == 1)", fn);
+    if (P.rlayout) {
+        if (((uintptr_t)d_src & 15u) || ((uintptr_t)d_smp & 15u))
+            return fail("%s: real-column plans need 16-byte aligned inputs (source %p, sample %p)", fn, (const void *)d_src,
+                        (const void *)d_smp);
+        if ((src_stride & 3u) || (smp_stride & 3u))
+            return fail("%s: real-column plans need strides that are multiples of 4 floats (source_stride %zu, sample_stride %zu)", fn,
+                        src_stride, smp_stride);
+    }
+    if (pooled) {
+        if (nsrc > INT32_MAX || nsmp > INT32_MAX) return fail("%s: a pool of more than 2^31 - 1 tracks", fn);
+        if (!d_pairs && batch != nsrc * nsmp)
+            return fail("%s: without pairs the batch is every combination, %zu x %zu, not %zu", fn, nsrc, nsmp, batch);
+    }
+    if (batch == 0) return 0;
+    if (pooled && (nsrc == 0 || nsmp == 0)) return fail("%s: an empty pool (%zu sources, %zu samples) for %zu pairs", fn, nsrc, nsmp, batch);
+    asx_plan::Lane &W = p->lanes[0];
+    const AsxWarp A{ d_center, d_line, (uint64_t)line_stride, d_r, d_frac, d_coef, d_len, d_ret, P.N, entries, half_width,
+                     pooled ? d_pairs : nullptr, pooled ? (uint64_t)nsrc : 0u, pooled ? (uint64_t)nsmp : 0u, (uint64_t)src_stride,
+                     (uint64_t)smp_stride };
+    const size_t total = batch * (size_t)entries;
+    for (size_t e0 = 0; e0 < total; e0 += p->group)
+        asx_launch_warp(d_src, d_smp, A, e0, (int)std::min(p->group, total - e0), W.pool, W.psums, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int asx_xcorr_warp_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                      size_t sample_stride, size_t batch, int entries, const int64_t *d_center, const double *d_line,
+                                      size_t line_stride, int half_width, double *d_r, double *d_frac, double *d_coef, int64_t *d_len,
+                                      int32_t *d_ret, void *stream)
+{
+    return warp_call(p, "asx_xcorr_warp_f32_dev", false, d_source, source_stride, 0, d_sample, sample_stride, 0, nullptr, batch, entries,
+                     d_center, d_line, line_stride, half_width, d_r, d_frac, d_coef, d_len, d_ret, stream);
+}
+
+extern "C" int asx_xcorr_pool_warp_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                           const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                           size_t batch, int entries, const int64_t *d_center, const double *d_line, size_t line_stride,
+                                           int half_width, double *d_r, double *d_frac, double *d_coef, int64_t *d_len, int32_t *d_ret,
+                                           void *stream)
+{
+    return warp_call(p, "asx_xcorr_pool_warp_f32_dev", true, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples,
+                     d_pairs, batch, entries, d_center, d_line, line_stride, half_width, d_r, d_frac, d_coef, d_len, d_ret, stream);
+}
+
 // diagnostic (not in the public header): the bank's capacity in tracks and how many pool calls have filled it
 extern "C" int asx_plan_debug_bank(asx_plan *p, uint64_t *nsrc, uint64_t *nsmp, uint64_t *fills)
 {

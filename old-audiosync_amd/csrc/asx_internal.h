@@ -640,6 +640,32 @@ unsigned asx_track_blocks(uint32_t N, int segments, int half_width);
 // [count]), the blocks' partial sums to part (the lane's psums); k_track_fit runs last and owns an invalid entry's outputs
 void asx_launch_track(const float *src, const float *smp, const AsxTrack &A, size_t first, int count, AsxPoolPair *pl, double *part,
                       hipStream_t s);
+// The warped correlation (asx_xcorr_warp_f32_dev, asx_xcorr_pool_warp_f32_dev; xcorr_kernels.hip: k_warp_dots, k_warp_final): one
+// call's arguments as its kernels take them, by value.  Entries, centres, pairs and pools as in AsxCurve; entry e's line is
+// {line[e * line_stride], line[e * line_stride + 1]} = {drift a, lag0 b}: sample frame n meets source frame n + centre + k_n,
+// k_n = floor((b + a n) + 0.5).
+#define ASX_WARP_DRIFT_MAX 0.015625
+struct AsxWarp {
+    const int64_t *center;  // [batch * entries]
+    const double *line;     // entry e's {a, b} at e * line_stride
+    uint64_t line_stride;   // in doubles: 0, 2, 3, ...
+    double *r;              // [batch * entries][2 h + 1]
+    double *frac;           // [batch * entries]
+    double *coef;           // [batch * entries]
+    int64_t *len;           // [batch * entries], or null
+    int32_t *ret;           // [batch * entries]
+    uint32_t N;
+    int entries, h;
+    const int32_t *rows;
+    uint64_t nsrc, nsmp, src_stride, smp_stride;
+};
+// blocks of k_warp_dots per entry: by the length alone, as asx_curve_blocks, and as many as leave their ASX_CURVE_N partial sums and
+// their Pearson record (6 doubles) in a pair's share of the lane's psums; one block leaves its sums in r and its record in part[le * 6]
+unsigned asx_warp_blocks(uint32_t N);
+// every output of entries first .. first + count - 1, count at most a launch group: the pool form's records go to pl (the lane's,
+// [count]), the blocks' partial sums and records to part (the lane's psums); k_warp_final runs last and owns an invalid entry's outputs
+void asx_launch_warp(const float *src, const float *smp, const AsxWarp &A, size_t first, int count, AsxPoolPair *pl, double *part,
+                     hipStream_t s);
 void asx_launch_bcast_aux(const AsxDev &P, const float *snrm, const float2 *sband, float *nrm, float2 *band, int npairs,
                           unsigned which, hipStream_t s);
 // pool calls: each pair's record (out) and its two slots' norm partials and band sums (band may be null) into the group's places

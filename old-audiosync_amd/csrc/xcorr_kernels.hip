@@ -1831,6 +1831,264 @@ __global__ __launch_bounds__(64) void k_track_fit(AsxTrack A, size_t first, cons
 }
 
 // ---------------------------------------------------------------------------
+// The warped correlation (asx_xcorr_warp_f32_dev, asx_xcorr_pool_warp_f32_dev): the curve's sum along a drift line (a, b),
+//     r[d] = sum_{n<N} source[(n + p + d + k_n) mod 2N] * sample[n],   k_n = floor((b + a n) + 0.5),   d = -h .. h,
+// and the reference's Pearson coefficient of the frames that line up at d = 0: the pairs (source[u_n], sample[n]) with
+// u_n = n + c + k_n inside [0, 2N).  One pass over the entry's tracks gives both.
+// ---------------------------------------------------------------------------
+// the most k moves across a sweep of a valid line: ASX_CURVE_SWEEP * ASX_WARP_DRIFT_MAX = 16, and one for the rounding
+#define ASX_WARP_STEPS 17
+#define ASX_WARP_XS ((ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX + ASX_WARP_STEPS + 3) & ~3)
+// what a block of k_warp_dots leaves: its ASX_CURVE_N partial sums, then its Pearson record {n, mx, my, mxx, myy, cxy}
+#define ASX_WARP_REC (ASX_CURVE_N + 6)
+// k_n: the multiply, the two adds and the floor each rounded on their own (no fused multiply-add), as numpy rounds
+// np.floor((b + a * n) + 0.5).  It stays a double: an integer of at most N + N / 64 + 1, so differences of shifts and frame indices
+// are exact there and the sweeps need no 64-bit integer conversions.
+__device__ __forceinline__ double warp_shift(double a, double b, uint32_t n)
+{
+    return floor(__dadd_rn(__dadd_rn(b, __dmul_rn(a, (double)n)), 0.5));
+}
+// the ret of entry e when it is not computed: -4 for a row outside its pool (pl: the pool form's records, indexed by the entry's
+// place in the slice, or null), over -2 for a centre outside [-N, N-1], over -5 for a line that is not valid -- a or b not finite
+// (the comparisons fail on NaN), |a| > ASX_WARP_DRIFT_MAX or |b| > N; 0 for an entry to compute
+__device__ __forceinline__ int32_t warp_ret(const AsxWarp &A, size_t e, size_t le, const AsxPoolPair *pl)
+{
+    if (pl && (pl[le].flags & ASX_POOL_INVALID)) return -4;
+    const int64_t c = A.center[e];
+    if (c < -(int64_t)A.N || c > (int64_t)A.N - 1) return -2;
+    const double a = A.line[e * A.line_stride], b = A.line[e * A.line_stride + 1];
+    return (fabs(a) <= ASX_WARP_DRIFT_MAX && fabs(b) <= (double)A.N) ? 0 : -5;
+}
+
+// grid (blocks per entry, entries of the slice), entry e = first + blockIdx.y: k_curve_dots' sweep along the line.  k is monotone in
+// n, so a sweep's shifts lie between those of its two ends; the sweep's stretch of the source starts at (n0 + p - h + k_min) mod 2N,
+// is up to 2h + ASX_WARP_STEPS longer than the sweep and goes through LDS once.  A thread reads the window of its four frames at the
+// offset k_n - k_min: one window of 4 + 2h values when the four share k, and a second one for the frames behind the step otherwise
+// (four consecutive frames of a valid line hold at most one step); a frame meets the window of its own k, the others a zero.  In
+// the same pass the thread keeps the Pearson statistics of its frames n with 0 <= n + c + k_n < 2N, relative to the first such pair
+// it meets, as k_pearson_partial does; their source values are the window's d = 0 column.  float64 throughout; the order is fixed:
+// a thread's frames ascending, the lanes of a wave, the waves, and the blocks in order (k_warp_final, from `part`): an entry's bits
+// depend on neither the batch nor its place in it.  With one block per entry the sums go to A.r and the record to part[le * 6].
+// An entry that is not valid reads and writes nothing: k_warp_final fills in all of its outputs.
+template <class Where>
+__global__ __launch_bounds__(ASX_THREADS, 4) void k_warp_dots(const float *__restrict__ src, const float *__restrict__ smp, Where at,
+                                                            AsxWarp A, size_t first, double *__restrict__ part)
+{
+    constexpr bool listed = std::is_same<Where, AsxAtList>::value;
+    __shared__ __attribute__((aligned(16))) float xs[ASX_WARP_XS];
+    __shared__ double red[ASX_THREADS / 64][ASX_WARP_REC];
+    const int tid = threadIdx.x, h = A.h, n = 2 * h + 1;
+    const size_t le = blockIdx.y, e = first + le;
+    const size_t rec = listed ? le : e / (size_t)A.entries;
+    const uint32_t N = A.N, L = 2u * N;
+    const AsxPoolPair *pl = nullptr;
+    if constexpr (listed) pl = at.pl;
+    if (warp_ret(A, e, le, pl)) return; // (block-uniform: nobody is left at a barrier)
+    const int64_t c = A.center[e];
+    const double la = A.line[e * A.line_stride], lb = A.line[e * A.line_stride + 1];
+    const uint32_t i0 = curve_first(c, N, h);
+    const float *x = src + at.src_off(rec);
+    const float *y = smp + at.smp_off(rec);
+    const uint32_t chunk = ((N + gridDim.x - 1) / gridDim.x + 3u) & ~3u;
+    const uint64_t lo64 = (uint64_t)blockIdx.x * chunk;
+    const uint32_t lo = lo64 < (uint64_t)N ? (uint32_t)lo64 : N, hi = N - lo < chunk ? N : lo + chunk; // (2N fits 32 bits)
+    double acc[ASX_CURVE_N];
+#pragma unroll
+    for (int j = 0; j < ASX_CURVE_N; j++) acc[j] = 0.0;
+    double px = 0, py = 0, sx = 0, sy = 0, sxy = 0, sxx = 0, syy = 0; // pivots: the first lined-up pair this thread meets
+    uint32_t seen = 0;
+    auto add = [&](double u, double v) {
+        if (!seen) { px = u; py = v; }
+        const double da = u - px, db = v - py;
+        sx += da;
+        sy += db;
+        sxy += da * db;
+        sxx += da * da;
+        syy += db * db;
+        seen++;
+    };
+    for (uint32_t n0 = lo; n0 < hi; n0 += ASX_CURVE_SWEEP) {
+        const uint32_t cnt = hi - n0 < (uint32_t)ASX_CURVE_SWEEP ? hi - n0 : (uint32_t)ASX_CURVE_SWEEP;
+        // the thread's four samples; past the block's end: zeros, which meet zeros below
+        const uint32_t t4 = 4u * (uint32_t)tid;
+        asx_f4v yq = { 0.0f, 0.0f, 0.0f, 0.0f };
+        if (t4 + 3u < cnt) yq = *reinterpret_cast<const asx_f4u *>(y + (size_t)n0 + t4);
+        else {
+            if (t4 < cnt) yq.x = y[(size_t)n0 + t4];
+            if (t4 + 1u < cnt) yq.y = y[(size_t)n0 + t4 + 1u];
+            if (t4 + 2u < cnt) yq.z = y[(size_t)n0 + t4 + 2u];
+        }
+        // the shifts of the sweep's ends and of the thread's frames (a frame past the sweep's end takes the last one's: its offset
+        // stays inside the stretch)
+        const uint32_t last = n0 + cnt - 1u;
+        const double ka = warp_shift(la, lb, n0), kb = warp_shift(la, lb, last), kmin = ka < kb ? ka : kb;
+        const int64_t km = (int64_t)kmin, u0 = (int64_t)n0 + c + km; // u_n = u0 + (n - n0) + (k_n - kmin)
+        // per frame: its offset into the stretch, whether it shares the first frame's shift, and whether it lines up at d = 0 -- inside
+        // the block's frames and 0 <= u_n < 2N
+        uint32_t o0 = 0u, o3 = 0u;
+        unsigned same = 0u, in = 0u;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t nq = n0 + t4 + (uint32_t)q < last ? n0 + t4 + (uint32_t)q : last;
+            const double k = warp_shift(la, lb, nq);
+            const uint32_t o = (uint32_t)(int)(k - kmin);
+            if (q == 0) o0 = o;
+            o3 = o;
+            if (o == o0) same |= 1u << q;
+            if (t4 + (uint32_t)q < cnt && (uint64_t)(u0 + (int64_t)(t4 + (uint32_t)q + o)) < (uint64_t)L) in |= 1u << q;
+        }
+        // xs[t] = source[(n0 + i0 + kmin + t) mod 2N] for t < cnt + 2h + (kmax - kmin), zero behind.  n0 + i0 < 3N and |kmin| < 2N:
+        // two subtractions bring the index home
+        uint64_t gi = (uint64_t)n0 + i0;
+        if (gi >= L) gi -= L;
+        gi = (uint64_t)((int64_t)gi + km + (int64_t)L);
+        if (gi >= L) gi -= L;
+        if (gi >= L) gi -= L;
+        const uint32_t g0 = (uint32_t)gi;
+        const uint32_t need = cnt + 2u * (uint32_t)h + (uint32_t)(int)((ka < kb ? kb : ka) - kmin);
+        auto wrapped = [&](uint32_t i) { if (i >= L) { i -= L; if (i >= L) i %= L; } return i; };
+        for (uint32_t t = t4; t < (uint32_t)ASX_WARP_XS; t += (uint32_t)ASX_CURVE_SWEEP) {
+            asx_f4v v = { 0.0f, 0.0f, 0.0f, 0.0f };
+            if (t < need) {
+                const uint32_t g = wrapped(g0 + t);
+                if (t + 3u < need && g + 3u < L) v = *reinterpret_cast<const asx_f4u *>(x + g);
+                else {
+                    v.x = x[g];
+                    if (t + 1u < need) v.y = x[wrapped(g0 + t + 1u)];
+                    if (t + 2u < need) v.z = x[wrapped(g0 + t + 2u)];
+                    if (t + 3u < need) v.w = x[wrapped(g0 + t + 3u)];
+                }
+            }
+            *reinterpret_cast<asx_f4v *>(xs + t) = v;
+        }
+        __syncthreads();
+        // the frames of `take` against the window at offset o (any float: 4-byte aligned reads), one window value at a time: value i
+        // meets frame q at the sum j = i - q, so every sum takes its frames in ascending order
+        auto window = [&](uint32_t o, unsigned take) __attribute__((always_inline)) {
+            const float *wp = xs + t4 + o;
+            const double y0 = (take & 1u) ? (double)yq.x : 0.0, y1 = (take & 2u) ? (double)yq.y : 0.0;
+            const double y2 = (take & 4u) ? (double)yq.z : 0.0, y3 = (take & 8u) ? (double)yq.w : 0.0;
+            { // the statistics first: their four values are gone before the sums take the registers
+                const asx_f4v xc = *reinterpret_cast<const asx_f4u *>(wp + h); // the d = 0 column: source[u_n] of the four frames
+                const unsigned st = take & in;
+                if (st & 1u) add((double)xc.x, y0);
+                if (st & 2u) add((double)xc.y, y1);
+                if (st & 4u) add((double)xc.z, y2);
+                if (st & 8u) add((double)xc.w, y3);
+            }
+#pragma unroll
+            for (int q = 0; q < (4 + 2 * ASX_NEAR_MAX) / 4; q++) {
+                if (4 * q >= 4 + 2 * h) break; // (block-uniform) the window ends: the sums past 2h + 1 hold what nobody reads
+                const asx_f4v v = *reinterpret_cast<const asx_f4u *>(wp + 4 * q);
+                const float f[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int i = 4 * q + u;
+                    const double w = (double)f[u];
+                    if (i < ASX_CURVE_N) acc[i] = fma(w, y0, acc[i]);
+                    if (i >= 1 && i - 1 < ASX_CURVE_N) acc[i - 1] = fma(w, y1, acc[i - 1]);
+                    if (i >= 2 && i - 2 < ASX_CURVE_N) acc[i - 2] = fma(w, y2, acc[i - 2]);
+                    if (i >= 3 && i - 3 < ASX_CURVE_N) acc[i - 3] = fma(w, y3, acc[i - 3]);
+                }
+            }
+        };
+        window(o0, same);
+        if (same != 15u) window(o3, 15u & ~same);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < ASX_CURVE_N; j++) {
+        if (j < n) {
+            const double s = wave_sum(acc[j]);
+            if ((tid & 63) == 0) red[tid >> 6][j] = s;
+        }
+    }
+    PStat v;
+    v.n = (double)seen;
+    v.mx = v.my = v.mxx = v.myy = v.cxy = 0.0;
+    if (seen) {
+        v.mx = px + sx / v.n;
+        v.my = py + sy / v.n;
+        v.mxx = sxx - sx * sx / v.n;
+        v.myy = syy - sy * sy / v.n;
+        v.cxy = sxy - sx * sy / v.n;
+    }
+    v = pstat_wave_merge(v);
+    if ((tid & 63) == 0) {
+        double *o = &red[tid >> 6][ASX_CURVE_N];
+        o[0] = v.n; o[1] = v.mx; o[2] = v.my; o[3] = v.mxx; o[4] = v.myy; o[5] = v.cxy;
+    }
+    __syncthreads();
+    double *out = part + (le * gridDim.x + blockIdx.x) * ASX_WARP_REC;
+    if (tid < n) {
+        const double s = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+        if (gridDim.x == 1) A.r[e * (size_t)n + (size_t)tid] = s;
+        else out[tid] = s;
+    }
+    if (tid == 64) { // (a lane of the second wave: the first one's hold the sums) the waves' records in order
+        for (int w = 0; w < ASX_THREADS / 64; w++) {
+            const double *p = &red[w][ASX_CURVE_N];
+            PStat o;
+            o.n = p[0]; o.mx = p[1]; o.my = p[2]; o.mxx = p[3]; o.myy = p[4]; o.cxy = p[5];
+            v = w ? pstat_merge(v, o) : o;
+        }
+        double *st = gridDim.x == 1 ? part + le * 6 : out + ASX_CURVE_N;
+        st[0] = v.n; st[1] = v.mx; st[2] = v.my; st[3] = v.mxx; st[4] = v.myy; st[5] = v.cxy;
+    }
+}
+
+// grid (entries of the slice), one wave per entry, behind k_warp_dots: the entry's nb partial sums in block order (nb == 1: they are
+// in A.r already), then frac; its nb Pearson records merged as k_pearson_final merges them -- lane b owns the blocks b, b + 64, ... --
+// then coef, len = the records' count and ret (-1 for a NaN coefficient).  An entry that is not valid gets NaN everywhere, len 0.
+__global__ __launch_bounds__(64) void k_warp_final(AsxWarp A, size_t first, unsigned nb, const double *__restrict__ part,
+                                                    const AsxPoolPair *__restrict__ pl)
+{
+    __shared__ double yv[ASX_CURVE_N];
+    const int tid = threadIdx.x, n = 2 * A.h + 1;
+    const size_t le = blockIdx.x, e = first + le;
+    const int32_t rv = warp_ret(A, e, le, pl);
+    if (rv) { // (block-uniform)
+        if (tid < n) A.r[e * (size_t)n + (size_t)tid] = (double)NAN;
+        if (tid == 0) {
+            A.frac[e] = (double)NAN;
+            A.coef[e] = (double)NAN;
+            if (A.len) A.len[e] = 0;
+            A.ret[e] = rv;
+        }
+        return;
+    }
+    if (tid < n) {
+        double s;
+        if (nb == 1u) s = A.r[e * (size_t)n + (size_t)tid];
+        else {
+            const double *p = part + le * nb * ASX_WARP_REC + tid;
+            s = p[0];
+            for (unsigned b = 1; b < nb; b++) s += p[(size_t)b * ASX_WARP_REC];
+            A.r[e * (size_t)n + (size_t)tid] = s;
+        }
+        yv[tid] = s;
+    }
+    PStat v;
+    v.n = v.mx = v.my = v.mxx = v.myy = v.cxy = 0.0;
+    for (unsigned b = (unsigned)tid; b < nb; b += 64u) {
+        const double *p = nb == 1u ? part + le * 6 : part + (le * nb + b) * ASX_WARP_REC + ASX_CURVE_N;
+        PStat o;
+        o.n = p[0]; o.mx = p[1]; o.my = p[2]; o.mxx = p[3]; o.myy = p[4]; o.cxy = p[5];
+        v = pstat_merge(v, o);
+    }
+    v = pstat_wave_merge(v);
+    __syncthreads();
+    if (tid == 0) {
+        // src/cross_correlation.c:115; no lined-up frame or a constant side gives 0/0 = NaN like the reference
+        const double cf = v.cxy / sqrt(v.mxx * v.myy);
+        A.frac[e] = asx_parabola_frac(yv[A.h - 1], yv[A.h], yv[A.h + 1]);
+        A.coef[e] = cf;
+        if (A.len) A.len[e] = (int64_t)v.n;
+        A.ret[e] = (cf != cf) ? -1 : 0;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // second look, DC removal (second_look, asx_api.hip): one pair, one block each.  An offset of hundreds of standard deviations
 // in BOTH tracks makes the float32 error bound (proportional to |source|_2 |sample|_2) wider than the whole range of
 // r, every lag a near-tie.  r'[k] = sum (source[n+k] - m) sample[n] = r[k] - m * sum(sample) for ANY constant m: the
@@ -2235,6 +2493,29 @@ void asx_launch_track(const float *src, const float *smp, const AsxTrack &A, siz
         hipLaunchKernelGGL(k_track_sum, dim3((unsigned)(A.S * tiles), (unsigned)count), dim3(64), 0, s, A, first, tiles, nb,
                            (const double *)part, list);
     hipLaunchKernelGGL(k_track_fit, dim3((unsigned)count), dim3(64), 0, s, A, first, list);
+}
+
+unsigned asx_warp_blocks(uint32_t N)
+{
+    const unsigned nb = asx_pearson_blocks(N) * 6u / (unsigned)ASX_WARP_REC;
+    return nb < 1u ? 1u : nb;
+}
+
+void asx_launch_warp(const float *src, const float *smp, const AsxWarp &A, size_t first, int count, AsxPoolPair *pl, double *part,
+                     hipStream_t s)
+{
+    const unsigned nb = asx_warp_blocks(A.N);
+    const dim3 grid(nb, (unsigned)count), block(ASX_THREADS);
+    const AsxPoolPair *list = A.nsrc ? pl : nullptr;
+    if (A.nsrc) {
+        const AsxCurve C{ A.center, nullptr, nullptr, nullptr, A.N, A.entries, A.h, A.rows, A.nsrc, A.nsmp, A.src_stride, A.smp_stride };
+        hipLaunchKernelGGL(k_curve_resolve, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), block, 0, s, C, first, count, pl);
+        hipLaunchKernelGGL(k_warp_dots<AsxAtList>, grid, block, 0, s, src, smp, AsxAtList{ pl }, A, first, part);
+    } else {
+        hipLaunchKernelGGL(k_warp_dots<AsxAtPitch>, grid, block, 0, s, src, smp, AsxAtPitch{ (size_t)A.src_stride, (size_t)A.smp_stride },
+                           A, first, part);
+    }
+    hipLaunchKernelGGL(k_warp_final, dim3((unsigned)count), dim3(64), 0, s, A, first, nb, (const double *)part, list);
 }
 
 void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t s)

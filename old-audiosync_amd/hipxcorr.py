@@ -75,6 +75,9 @@ _HEADER_SIGNATURES = {
     "asx_xcorr_track_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_track_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp,
                                             _vp]),
+    "asx_xcorr_warp_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_pool_warp_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _int, _vp, _vp, _sz, _int, _vp, _vp, _vp, _vp,
+                                           _vp, _vp]),
     "asx_xcorr_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_debug_r_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_band_debug_r_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -131,6 +134,7 @@ TOPK_MAX = 8  # ASX_TOPK_MAX, include/audiosync/xcorr_hip.h
 NEAR_MAX = 8  # ASX_NEAR_MAX, include/audiosync/xcorr_hip.h
 TRACK_HALF_MAX = 64  # ASX_TRACK_HALF_MAX, include/audiosync/xcorr_hip.h
 TRACK_SEG_MAX = 64   # ASX_TRACK_SEG_MAX, include/audiosync/xcorr_hip.h
+WARP_DRIFT_MAX = 2.0 ** -6  # ASX_WARP_DRIFT_MAX, include/audiosync/xcorr_hip.h
 
 
 class AsxError(RuntimeError):
@@ -579,6 +583,38 @@ def pool_track_args(n, sources, samples, centers, half_width, segments, pairs=No
     return s, t, pr, c, batch, h, segs, entries
 
 
+def _lines(lines, shape):
+    """the drift lines of a warp call for centres of `shape` -> (a contiguous float64 array, line_stride in doubles): [2] or [3], one
+    line {drift, lag0} for every entry (stride 0), or shape + [2] (packed lines) or shape + [3] (the track call's fit, whose rms is
+    not read).  The values are not checked: a line that is not valid comes back with ret -5."""
+    ln = np.asarray(lines)
+    if ln.dtype.kind not in "fiu":
+        raise ValueError("lines must hold numbers {drift, lag0}, not %s" % ln.dtype)
+    ln = np.ascontiguousarray(ln, dtype=np.float64)
+    if ln.ndim == 1 and ln.shape[0] in (2, 3):
+        return ln, 0
+    if ln.ndim == len(shape) + 1 and ln.shape[:-1] == tuple(shape) and ln.shape[-1] in (2, 3):
+        return ln, ln.shape[-1]
+    raise ValueError("lines must be of shape [2], [3] or %s + [2] or [3], not %s" % (list(shape), list(ln.shape)))
+
+
+def warp_args(n, source, sample, centers, lines, half_width=1, entries=1):
+    """Host checks of Plan.xcorr_warp_f32 for a plan of sample length n: source, sample, centers, half_width and entries as curve_args
+    checks them, lines as _lines does.  -> (source, sample, centers, lines, batch, source_stride, sample_stride, line_stride,
+    half_width, entries).  ValueError on anything else."""
+    s, t, c, batch, ss, ts, h, entries = curve_args(n, source, sample, centers, half_width, entries)
+    ln, ls = _lines(lines, c.shape)
+    return s, t, c, ln, batch, ss, ts, ls, h, entries
+
+
+def pool_warp_args(n, sources, samples, centers, lines, pairs=None, half_width=1, entries=1):
+    """Host checks of Plan.xcorr_pool_warp_f32: the pools, pairs and centers of pool_curve_args, lines as warp_args.  -> (sources,
+    samples, pairs or None, centers, lines, batch, line_stride, half_width, entries).  ValueError on anything else."""
+    s, t, pr, c, batch, h, entries = pool_curve_args(n, sources, samples, centers, pairs, half_width, entries)
+    ln, ls = _lines(lines, c.shape)
+    return s, t, pr, c, ln, batch, ls, h, entries
+
+
 def position_rows(n, hop, batch, p_lo, p_hi):
     """Lag windows of Plan.xcorr_windows_f32(..., positions=(p_lo, p_hi)): window k (source frames k*hop .. k*hop + 2N - 1 of the
     recording, 0 <= k < batch) holds a sample that starts at recording frame k*hop + lag, so its rows are
@@ -1017,6 +1053,24 @@ class Plan:
                                                   d_center or None, int(half_width), int(segments), d_r or None, d_seg or None,
                                                   d_fit or None, d_used or None, d_ret or None, stream or None))
 
+    def xcorr_warp_dev(self, d_src, src_stride, d_smp, smp_stride, batch, entries, d_center, d_line, line_stride, half_width, d_r,
+                       d_frac, d_coef, d_len, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_warp_f32_dev -- along each entry's line {drift, lag0} (d_line, float64, entry e's at
+        e * line_stride; 0: one line for all) through its lag of d_center (int64): r at the 2 half_width + 1 offsets across the line
+        (d_r, float64), the vertex across it (d_frac), the Pearson coefficient of the frames that line up (d_coef), their number
+        (d_len, int64, may be 0) and d_ret"""
+        _check(lib().asx_xcorr_warp_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride), int(batch),
+                                            int(entries), d_center or None, d_line or None, int(line_stride), int(half_width),
+                                            d_r or None, d_frac or None, d_coef or None, d_len or None, d_ret or None, stream or None))
+
+    def xcorr_pool_warp_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, batch, entries,
+                            d_center, d_line, line_stride, half_width, d_r, d_frac, d_coef, d_len, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_warp_f32_dev -- xcorr_warp_dev for the pairs of xcorr_pool_dev"""
+        _check(lib().asx_xcorr_pool_warp_f32_dev(self._h, d_sources or None, int(source_stride), int(nsources), d_samples or None,
+                                                 int(sample_stride), int(nsamples), d_pairs or None, int(batch), int(entries),
+                                                 d_center or None, d_line or None, int(line_stride), int(half_width), d_r or None,
+                                                 d_frac or None, d_coef or None, d_len or None, d_ret or None, stream or None))
+
     def debug_prune(self, pair=0):
         """diagnostic: (upper bounds of |r| per column tile, the largest-bound tile) of `pair` of the last pruned group"""
         n = (self.split[1] + self.split[2] - 1) // self.split[2]
@@ -1225,6 +1279,37 @@ class Plan:
         s, t, pr, c, batch, h, segs, entries = pool_track_args(n, sources, samples, centers, half_width, segments, pairs, entries)
         return self._staged_track((s, t, pr, c), c.shape, h, segs, lambda d_s, d_t, d_pr, d_c, *d_out: self.xcorr_pool_track_dev(
             d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, batch, entries, d_c, h, segs, *d_out))
+
+    def _staged_warp(self, inputs, shape, h, launch):
+        """_staged for the warp calls: outputs (r, frac, coef, length, ret), r of shape + (2h + 1,)"""
+        with _Staging(self) as st:
+            d_in = [st.upload(a) for a in inputs]
+            shape = tuple(shape)
+            launch(*d_in, st.output(shape + (2 * h + 1,), np.float64), st.output(shape, np.float64), st.output(shape, np.float64),
+                   st.output(shape, np.int64), st.output(shape, np.int32))
+            return st.fetch()
+
+    def xcorr_warp_f32(self, source, sample, centers, lines, half_width=1, entries=1):
+        """The correlation along a drift line (asx_xcorr_warp_f32_dev), behind the track call on the line it fitted: sample frame n
+        meets source frame n + centre + k_n, k_n = floor((lag0 + drift * n) + 0.5).  source, sample, centers, half_width and entries as
+        in xcorr_curve_f32; lines: float64 {drift, lag0} -- [2] or [3] (one line for every entry), or of the shape of centers + (2,)
+        or + (3,) (xcorr_track_f32's fit as it is).  Arguments are checked on the host (ValueError) before anything is uploaded.
+        Returns (r, frac, coef, length, ret): r[..., d + h] the sum at the offset d across the line, frac the vertex of the parabola
+        through r[..., h - 1 : h + 2], coef the reference's Pearson coefficient of the frames that line up at d = 0 and length their
+        number, ret 0, -1 (a NaN coefficient), -2 (a centre outside [-N, N-1]) or -5 (a line that is not valid: not finite, |drift| >
+        WARP_DRIFT_MAX or |lag0| > N), the last two with NaN values and length 0 -- of the shape of centers, r + (2h + 1,)."""
+        s, t, c, ln, batch, ss, ts, ls, h, entries = warp_args(self.sample_len, source, sample, centers, lines, half_width, entries)
+        return self._staged_warp((s, t, c, ln), c.shape, h, lambda d_s, d_t, d_c, d_ln, *d_out: self.xcorr_warp_dev(
+            d_s, ss, d_t, ts, batch, entries, d_c, d_ln, ls, h, *d_out))
+
+    def xcorr_pool_warp_f32(self, sources, samples, centers, lines, pairs=None, half_width=1, entries=1):
+        """xcorr_warp_f32 for pairs of two pools (asx_xcorr_pool_warp_f32_dev): the pools, pairs and centers of xcorr_pool_curve_f32.
+        Returns (r, frac, coef, length, ret) as xcorr_warp_f32; every entry of a pair with an index outside its pool has ret -4, NaN
+        values and length 0."""
+        n = self.sample_len
+        s, t, pr, c, ln, batch, ls, h, entries = pool_warp_args(n, sources, samples, centers, lines, pairs, half_width, entries)
+        return self._staged_warp((s, t, pr, c, ln), c.shape, h, lambda d_s, d_t, d_pr, d_c, d_ln, *d_out: self.xcorr_pool_warp_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, batch, entries, d_c, d_ln, ls, h, *d_out))
 
     def xcorr_topk_f32(self, source, sample, k, min_separation, windows=None):
         """The k strongest separated lags per pair (asx_xcorr_topk_f32_dev).  source: float32 [2N] or [B, 2N]; sample: [N] or [B, N];
