@@ -615,6 +615,61 @@ int asx_topk_best_dev(const int64_t *d_lag, const double *d_coef, const int32_t 
                       int64_t *d_best_lag, double *d_best_coef, int32_t *d_best_ret, int32_t *d_best_entry,
                       void *stream);
 
+/* Each pair's lag by triangle closure over a clip pool, and the clips placed: the consumer of an all-pairs top-k call that uses
+ * more than one pair at a time.  asx_topk_best_dev picks by coefficient alone, which takes the wrong entry exactly where runner-ups
+ * were asked for (a chorus, an echo, a loud private event); this call picks the entry that the other clips agree with.
+ *   Input.  The outputs of asx_xcorr_pool_topk_f32_dev (or of asx_xcorr_pool_f32_dev, with k = 1) over ONE pool used as both sides,
+ * with d_pairs == NULL and nsources = nsamples = C = nclips: pair (a, b) is index a * C + b, entry j of that pair is at
+ * (a * C + b) * k + j.  With clip start times T (in frames of the common event), frame i of clip b is frame
+ * i + T_b - T_a of clip a, and a lag l says sample[i] = source[i + l]: with clip a as the source and clip b as the sample, the lag
+ * of pair (a, b) estimates T_b - T_a.  Hence lag_ac + lag_cb = (T_c - T_a) + (T_b - T_c) = lag_ab, and lag_ab = -lag_ba.  A caller
+ * who computed only some pairs fills the others with ret != 0.
+ *   The rule.  Everything is integer arithmetic, apart from coefficient comparisons; no result depends on the launch geometry.
+ *   Valid entries.  An entry is valid when ret == 0 and |lag| <= ASX_CLOSURE_LAG_MAX; every sum below then fits an int64.
+ *   Votes, of a valid entry (a, b, j) with a != b: one vote if some valid (b, a, q) has |lag_abj + lag_baq| <= tolerance; one vote
+ * for each third clip c outside {a, b} for which valid (a, c, p) and (c, b, q) exist with |lag_acp + lag_cbq - lag_abj| <= tolerance.
+ * Votes count clips, not combinations: the range is 0 .. C - 1.  Invalid entries and the diagonal get 0.  d_votes, if given,
+ * receives all C * C * k values.
+ *   Pick.  For each pair (a, b), scan j upwards over the valid entries: entry j replaces the current best when its votes are larger,
+ * or when its votes are equal and coef[j] > coef[best] -- strictly, so a NaN never wins and the smallest j wins ties.  If the pair
+ * has no valid entry, entry 0 is copied as it is and best_entry = 0.  (lag, coef, ret) of the pick go to index a * C + b of
+ * d_best_lag / d_best_coef / d_best_ret and j to d_best_entry: the layout asx_results_to_ms_dev takes; the coefficient is copied
+ * bit for bit.  On the diagonal this is asx_topk_best_dev's rule (votes are all 0); with k = 1 the pick is the identity.
+ *   Confirm.  Let L be the picked lags.  Pair (a, b) is good when a != b and it has a valid entry.  d_confirm[a * C + b] is 0 for a
+ * pair that is not good; for a good pair it is [(b, a) good and |L_ab + L_ba| <= tolerance] plus the number of c outside {a, b} with
+ * (a, c) and (c, b) good and |L_ac + L_cb - L_ab| <= tolerance.  Here only the PICKED entries vote, so a pool in which every pair
+ * picked the same periodic decoy confirms nothing.  A pair is usable when it is good and confirm >= min_confirm.
+ *   Root.  If root is in [0, C), that clip is the root.  If root == -1, score[a] = #usable (a, .) + #usable (., a); the largest
+ * score wins, and the smallest index wins among equals.  d_root[0] receives the root.
+ *   Offsets.  The root r gets offset 0, support 0, placed 1.  Every other clip b has a multiset E_b of estimates of T_b - T_r:
+ * L_rb if (r, b) is usable; -L_br if (b, r) is usable; and for every c outside {r, b}: L_rc + L_cb if both are usable, and
+ * -(L_bc + L_cr) if both are usable.  d_offset[b] is the lower median of E_b, the element at index (|E_b| - 1) / 2 of E_b sorted
+ * ascending; d_support[b] is the number of elements of E_b within tolerance of the median; d_placed[b] = 1 when E_b is not empty.
+ * An empty E_b gives offset 0, support 0, placed 0.
+ *   Ambiguity.  If every pair carries decoys at +-P, shifting one clip by P closes every triangle as well as the truth does, so lags
+ * alone cannot decide: the votes of the true entries and of the decoys tie, and the pick falls back to the coefficient, which is
+ * what asx_topk_best_dev does.  A wrong pick that no other pick agrees with has confirm 0: test d_confirm before trusting a pair.  The
+ * converse does not hold: with periodic decoys in many pairs, two wrong picks one period off can confirm one another, so
+ * confirm >= 1 is not proof that a pick is right; a larger min_confirm, and d_support against the number of clips, say more.
+ *   Refusals: -1 with nothing launched and the outputs untouched for a NULL pointer other than d_votes; nclips == 0;
+ * nclips * nclips * k > INT32_MAX; k outside 1..ASX_TOPK_MAX; tolerance < 0 or > ASX_CLOSURE_LAG_MAX; min_confirm < 0; root outside
+ * [-1, nclips).  nclips == 1 is legal: it has the diagonal only and root 0.
+ *   All pointers are device pointers: d_votes [C * C * k]; d_best_lag, d_best_coef, d_best_ret, d_best_entry, d_confirm [C * C] each;
+ * d_root [1]; d_offset, d_support, d_placed [C] each.  The call takes no plan, allocates nothing, never synchronises the host, and is
+ * asynchronous and capturable on `stream`: four kernel launches in order, each reading required outputs of those before it (there
+ * is no workspace), so the outputs must not alias the inputs or one another.
+ *   Not offered: clips reachable only over three or more hops are not placed (E_b holds one- and two-hop estimates); a least-squares
+ * solve over all pairs; an explicit pair list (unlisted pairs are stated by ret != 0); weighting by coefficient. */
+#define ASX_CLOSURE_LAG_MAX ((int64_t)1 << 40)
+int asx_pool_closure_dev(const int64_t *d_lag, const double *d_coef, const int32_t *d_ret,
+                         size_t nclips, int k, int64_t tolerance, int min_confirm, int root,
+                         int32_t *d_votes,
+                         int64_t *d_best_lag, double *d_best_coef, int32_t *d_best_ret,
+                         int32_t *d_best_entry, int32_t *d_confirm,
+                         int32_t *d_root,
+                         int64_t *d_offset, int32_t *d_support, int32_t *d_placed,
+                         void *stream);
+
 /* The exact correlation curve and a fractional lag around given lags: a consumer that runs behind the batch, strided, windowed, top-k
  * and pool calls on the lags they returned.  Those calls rank lags by the raw correlation r and hand back one coefficient per lag;
  * this one says how sharp a candidate is: r and the Pearson coefficient at the 2h + 1 indices around it, and the parabola's vertex.

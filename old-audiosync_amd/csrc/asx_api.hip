@@ -2258,6 +2258,34 @@ extern "C" int asx_topk_best_dev(const int64_t *d_lag, const double *d_coef, con
     return 0;
 }
 
+// Each pair's entry by triangle closure over one pool's all-pairs tables, and the clips' offsets from the picks (k_closure_votes,
+// k_closure_confirm, k_closure_root, k_closure_offsets): four launches on `stream`, nothing allocated, no workspace -- every kernel
+// reads required outputs of those before it.
+static_assert(ASX_CLOSURE_LAG_MAX == ASX_CLOSURE_LAG_LIMIT, "the header's limit of a valid lag and the kernels' copy of it differ");
+extern "C" int asx_pool_closure_dev(const int64_t *d_lag, const double *d_coef, const int32_t *d_ret, size_t nclips, int k,
+                                    int64_t tolerance, int min_confirm, int root, int32_t *d_votes, int64_t *d_best_lag,
+                                    double *d_best_coef, int32_t *d_best_ret, int32_t *d_best_entry, int32_t *d_confirm,
+                                    int32_t *d_root, int64_t *d_offset, int32_t *d_support, int32_t *d_placed, void *stream)
+{
+    if (!d_lag || !d_coef || !d_ret || !d_best_lag || !d_best_coef || !d_best_ret || !d_best_entry || !d_confirm || !d_root ||
+        !d_offset || !d_support || !d_placed)
+        return fail("asx_pool_closure_dev: null argument");
+    if (k < 1 || k > ASX_TOPK_MAX) return fail("asx_pool_closure_dev: k = %d is not in [1, %d]", k, ASX_TOPK_MAX);
+    if (nclips == 0) return fail("asx_pool_closure_dev: no clips");
+    // (nclips > 65535 first: it is what keeps the 64-bit product below from wrapping, at nclips = 2^33 for instance)
+    if (nclips > 65535 || (uint64_t)nclips * nclips * (uint64_t)k > (uint64_t)INT32_MAX)
+        return fail("asx_pool_closure_dev: %zu clips with k = %d are more than INT32_MAX entries", nclips, k);
+    if (tolerance < 0 || tolerance > ASX_CLOSURE_LAG_MAX)
+        return fail("asx_pool_closure_dev: tolerance = %lld is not in [0, 2^40]", (long long)tolerance);
+    if (min_confirm < 0) return fail("asx_pool_closure_dev: min_confirm = %d is negative", min_confirm);
+    if (root < -1 || (root >= 0 && (size_t)root >= nclips))
+        return fail("asx_pool_closure_dev: root = %d is neither -1 nor one of the %zu clips", root, nclips);
+    asx_launch_pool_closure(d_lag, d_coef, d_ret, (uint32_t)nclips, k, tolerance, min_confirm, root, d_votes, d_best_lag, d_best_coef,
+                            d_best_ret, d_best_entry, d_confirm, d_root, d_offset, d_support, d_placed, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---------------------------------------------------------------------------
 // growing-window streams (BASELINE config 5)
 // ---------------------------------------------------------------------------

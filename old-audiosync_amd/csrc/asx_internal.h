@@ -708,6 +708,16 @@ void asx_launch_results_to_ms(const int64_t *lag, const double *coef, const int3
 // asx_topk_best_dev: per pair the entry with ret == 0 and the largest signed coefficient (none: entry 0), to index pair
 void asx_launch_topk_best(const int64_t *lag, const double *coef, const int32_t *ret, size_t batch, int k, int64_t *best_lag,
                           double *best_coef, int32_t *best_ret, int32_t *best_entry, hipStream_t s);
+// asx_pool_closure_dev over the [C][C][k] tables of one pool (C * C * k <= INT32_MAX, 1 <= k <= ASX_TOPK_MAX, 0 <= tol <=
+// ASX_CLOSURE_LAG_MAX): k_closure_votes (votes, may be NULL, and the pick to best_*), k_closure_confirm, k_closure_root (root in
+// [0, C) or -1: chosen), k_closure_offsets -- four launches in this order on s, each reading the outputs of those before it
+// ASX_CLOSURE_LAG_LIMIT: the kernels' copy of ASX_CLOSURE_LAG_MAX of include/audiosync/xcorr_hip.h, which this header does not
+// include; asx_api.hip includes both and holds them together with a static_assert (tests/test_closure.py reads both too)
+#define ASX_CLOSURE_LAG_LIMIT ((int64_t)1 << 40)
+void asx_launch_pool_closure(const int64_t *lag, const double *coef, const int32_t *ret, uint32_t C, int k, int64_t tol,
+                             int min_confirm, int root, int32_t *votes, int64_t *best_lag, double *best_coef, int32_t *best_ret,
+                             int32_t *best_entry, int32_t *confirm, int32_t *d_root, int64_t *offset, int32_t *support,
+                             int32_t *placed, hipStream_t s);
 void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t s);
 unsigned asx_pearson_blocks(uint32_t basis_len); // partial blocks per pair: psums holds 6 doubles per block and pair
 // second look, DC removal: stats[0] = mean of source[0..2N), stats[1] = sum of sample[0..N), stats[2] = scale * stats[0] * stats[1]

@@ -1415,6 +1415,308 @@ __global__ __launch_bounds__(ASX_THREADS) void k_topk_best(const int64_t *__rest
 }
 
 // ---------------------------------------------------------------------------
+// Triangle closure over one clip pool (asx_pool_closure_dev): the tables are [C][C][k], pair (a, b) at a * C + b, and the lag of
+// (a, b) estimates T_b - T_a, so lag_ac + lag_cb = lag_ab and lag_ab = -lag_ba.  Everything below is integer arithmetic (counts
+// and int64 sums of lags within +-ASX_CLOSURE_LAG_LIMIT); only the pick compares coefficients.  C * C * k <= INT32_MAX: 32-bit indices.
+// ---------------------------------------------------------------------------
+#define ASX_CLOSURE_CH 256                          // clips of row (a, ., .) staged in LDS at a time
+#define ASX_CLOSURE_BT 16                           // the b of one block: four per wave
+#define ASX_CLOSURE_INV ((int64_t)1 << 60)          // a lag that is not valid: no sum that holds it is near a valid lag
+#define ASX_CLOSURE_TINV (-((int64_t)1 << 62))      // ... and the target of an entry that is not valid: near no sum
+
+__device__ __forceinline__ bool closure_valid(int64_t lag, int32_t ret)
+{
+    return ret == 0 && lag >= -ASX_CLOSURE_LAG_LIMIT && lag <= ASX_CLOSURE_LAG_LIMIT;
+}
+
+// Vote and pick.  Block (x, y): clip a = y and the clips b = x * BT .. x * BT + BT - 1.  The row (a, c, p) goes through LDS once per
+// block in chunks of CH clips c, as [p][c] so that the 64 lanes of a wave read 64 consecutive int64; a lag that is not valid is
+// stored as INV.  Wave w takes b = w, w + 4, ...; its lanes run over c and read the column entry (c, b, .) -- k * 8 contiguous bytes
+// per lane at a stride of C * k * 8 -- straight from global memory: the b of a block are neighbours, so the 16 * k * 8 contiguous
+// bytes of (c, b0 .. b0 + 15, .) are the whole of the lines a lane touches, and the table (C * C * k * 12 bytes) is read by every
+// a from L2.  The lane with c == b takes the reverse pair instead: P = {0}, Q = -lag(b, a, .).  |s - lag_j| <= tol is
+// (uint64)(s - (lag_j - tol)) <= 2 tol; each lane forms its k x k sums and a mask of the j it supports, a ballot and a popcount per
+// j count the clips, and the wave that owns b adds them to the block's counters.
+__global__ __launch_bounds__(ASX_THREADS) void k_closure_votes(const int64_t *__restrict__ lag, const double *__restrict__ coef,
+                                                                const int32_t *__restrict__ ret, uint32_t C, int k, int64_t tol,
+                                                                int32_t *__restrict__ votes, int64_t *__restrict__ best_lag,
+                                                                double *__restrict__ best_coef, int32_t *__restrict__ best_ret,
+                                                                int32_t *__restrict__ best_entry)
+{
+    __shared__ int64_t rowP[ASX_TOPK_MAX * ASX_CLOSURE_CH];
+    __shared__ int32_t cnt[ASX_CLOSURE_BT][ASX_TOPK_MAX];
+    const uint32_t a = blockIdx.y, b0 = blockIdx.x * ASX_CLOSURE_BT;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t tol2 = 2u * (uint64_t)tol;
+    if (threadIdx.x < ASX_CLOSURE_BT * ASX_TOPK_MAX) (&cnt[0][0])[threadIdx.x] = 0;
+    for (uint32_t c0 = 0; c0 < C; c0 += ASX_CLOSURE_CH) {
+        __syncthreads();                                        // the chunk before this one has been read
+        const uint32_t nch = min((uint32_t)ASX_CLOSURE_CH, C - c0), row0 = (a * C + c0) * (uint32_t)k;
+        for (uint32_t i = threadIdx.x; i < nch * (uint32_t)k; i += ASX_THREADS) {
+            const uint32_t cl = i / (uint32_t)k, p = i - cl * (uint32_t)k;
+            const int64_t v = lag[row0 + i];
+            rowP[p * ASX_CLOSURE_CH + cl] = closure_valid(v, ret[row0 + i]) ? v : ASX_CLOSURE_INV;
+        }
+        __syncthreads();
+        for (uint32_t bt = w; bt < ASX_CLOSURE_BT; bt += ASX_THREADS / 64) {
+            const uint32_t b = b0 + bt;
+            if (b >= C || b == a) continue;                     // (the same in every lane of the wave)
+            int64_t T[ASX_TOPK_MAX];
+#pragma unroll
+            for (int j = 0; j < ASX_TOPK_MAX; j++) {
+                T[j] = ASX_CLOSURE_TINV;
+                if (j < k) {
+                    const uint32_t e = (a * C + b) * (uint32_t)k + (uint32_t)j;
+                    const int64_t v = lag[e];
+                    if (closure_valid(v, ret[e])) T[j] = v - tol;
+                }
+            }
+            int32_t wc[ASX_TOPK_MAX];
+#pragma unroll
+            for (int j = 0; j < ASX_TOPK_MAX; j++) wc[j] = 0;
+            for (uint32_t ci = 0; ci < nch; ci += 64) {
+                const uint32_t cl = ci + lane, c = c0 + cl;
+                uint32_t mask = 0;                              // (a predicate per j instead, held as lane masks, measured 1.4 x slower)
+                if (cl < nch && c != a) {
+                    const bool rev = c == b;
+                    const uint32_t q0 = (rev ? b * C + a : c * C + b) * (uint32_t)k;
+                    int64_t Q[ASX_TOPK_MAX];
+#pragma unroll
+                    for (int q = 0; q < ASX_TOPK_MAX; q++) {
+                        Q[q] = ASX_CLOSURE_INV;
+                        if (q < k) {
+                            const int64_t v = lag[q0 + (uint32_t)q];
+                            if (closure_valid(v, ret[q0 + (uint32_t)q])) Q[q] = rev ? -v : v;
+                        }
+                    }
+                    for (int p = 0; p < k; p++) {
+                        int64_t P = rowP[p * ASX_CLOSURE_CH + cl];
+                        if (rev) P = p == 0 ? 0 : ASX_CLOSURE_INV;
+#pragma unroll
+                        for (int q = 0; q < ASX_TOPK_MAX; q++) {
+                            if (q < k) {
+                                const int64_t s = P + Q[q];
+#pragma unroll
+                                for (int j = 0; j < ASX_TOPK_MAX; j++) mask |= ((uint64_t)(s - T[j]) <= tol2 ? 1u : 0u) << j;
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < ASX_TOPK_MAX; j++) wc[j] += (int32_t)__popcll(__ballot((mask >> j) & 1u));
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int j = 0; j < ASX_TOPK_MAX; j++) cnt[bt][j] += wc[j];
+            }
+        }
+    }
+    __syncthreads();
+    // the pick, one thread per b: more votes, then the larger coefficient (strictly: a NaN never wins), then the smaller j
+    const uint32_t b = b0 + threadIdx.x;
+    if (threadIdx.x >= ASX_CLOSURE_BT || b >= C) return;
+    const uint32_t pair = a * C + b, e0 = pair * (uint32_t)k;
+    int bj = -1;
+    int32_t bv = 0;
+    double bc = 0.0;
+    for (int j = 0; j < k; j++) {
+        const int32_t v = cnt[threadIdx.x][j];                  // 0 on the diagonal and for an entry that is not valid
+        if (votes) votes[e0 + (uint32_t)j] = v;
+        if (!closure_valid(lag[e0 + (uint32_t)j], ret[e0 + (uint32_t)j])) continue;
+        const double c = coef[e0 + (uint32_t)j];
+        if (bj < 0 || v > bv || (v == bv && c > bc)) { bj = j; bv = v; bc = c; }
+    }
+    const uint32_t e = e0 + (uint32_t)(bj < 0 ? 0 : bj);
+    best_lag[pair] = lag[e];
+    reinterpret_cast<int64_t *>(best_coef)[pair] = reinterpret_cast<const int64_t *>(coef)[e];   // the bits, a NaN's payload too
+    best_ret[pair] = ret[e];
+    best_entry[pair] = bj < 0 ? 0 : bj;
+}
+
+// a pair with a valid picked entry off the diagonal
+__device__ __forceinline__ bool closure_good(const int64_t *L, const int32_t *R, uint32_t C, uint32_t x, uint32_t y)
+{
+    return x != y && closure_valid(L[x * C + y], R[x * C + y]);
+}
+
+// Confirm, one wave per pair (a, b), lanes over the third clip c: only the PICKED lags L vote.  The lane with c == b takes (b, a).
+__global__ __launch_bounds__(ASX_THREADS) void k_closure_confirm(const int64_t *__restrict__ L, const int32_t *__restrict__ R,
+                                                                  uint32_t C, int64_t tol, int32_t *__restrict__ confirm)
+{
+    const uint32_t pair = blockIdx.x * (ASX_THREADS / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (pair >= C * C) return;
+    const uint32_t a = pair / C, b = pair - a * C, lane = threadIdx.x & 63u;
+    int32_t n = 0;
+    if (closure_good(L, R, C, a, b)) {
+        const int64_t lab = L[pair];
+        for (uint32_t c0 = 0; c0 < C; c0 += 64) {
+            const uint32_t c = c0 + lane;
+            bool hit = false;
+            if (c < C && c != a) {
+                int64_t d = INT64_MAX;
+                if (c == b) { if (closure_good(L, R, C, b, a)) d = lab + L[b * C + a]; }
+                else if (closure_good(L, R, C, a, c) && closure_good(L, R, C, c, b)) d = L[a * C + c] + L[c * C + b] - lab;
+                hit = d >= -tol && d <= tol;
+            }
+            n += (int32_t)__popcll(__ballot(hit));
+        }
+    }
+    if (lane == 0) confirm[pair] = n;
+}
+
+// a pair the offsets may use: good, and confirmed by at least min_confirm clips
+__device__ __forceinline__ bool closure_usable(const int64_t *L, const int32_t *R, const int32_t *F, uint32_t C, int min_confirm,
+                                               uint32_t x, uint32_t y)
+{
+    return closure_good(L, R, C, x, y) && F[x * C + y] >= min_confirm;
+}
+
+// the sum of v over a block of ASX_THREADS threads, in every thread, with one barrier; red: ASX_THREADS / 64 ints of LDS that the sum
+// before this one did not use (two buffers in turn: the barrier of a sum lies between the reads of the one before it and the
+// writes of the one after it)
+__device__ __forceinline__ int32_t closure_block_sum(int32_t v, int32_t *red)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int32_t s = 0;
+#pragma unroll
+    for (int i = 0; i < ASX_THREADS / 64; i++) s += red[i];
+    return s;
+}
+
+// The root, one block: the given clip, or the one with the most usable pairs (a, .) and (., a), the smallest index among equals.
+// Scores are counted a tile of ASX_THREADS clips at a time in LDS, in two passes that both read consecutive pairs: the rows (a, .)
+// of the tile's clips, then per clip b the run (b, a0 .. a0 + tile - 1) of their columns.  Integer atomics: no order shows.
+__global__ __launch_bounds__(ASX_THREADS) void k_closure_root(const int64_t *__restrict__ L, const int32_t *__restrict__ R,
+                                                               const int32_t *__restrict__ F, uint32_t C, int min_confirm, int root,
+                                                               int32_t *__restrict__ out)
+{
+    __shared__ int32_t score[ASX_THREADS];
+    __shared__ int32_t red_s[ASX_THREADS / 64];
+    __shared__ uint32_t red_a[ASX_THREADS / 64];
+    if (root >= 0) {
+        if (threadIdx.x == 0) out[0] = root;
+        return;
+    }
+    int32_t best = -1;
+    uint32_t best_a = 0;
+    for (uint32_t a0 = 0; a0 < C; a0 += ASX_THREADS) {
+        const uint32_t nt = min((uint32_t)ASX_THREADS, C - a0);
+        __syncthreads();                                        // the tile before this one has been read
+        score[threadIdx.x] = 0;
+        __syncthreads();
+        // (all three loads of a pair whatever they hold, so that the loads of several pairs are in flight at a time)
+        auto usable = [&](uint32_t x, uint32_t y) {
+            const uint32_t i = x * C + y;
+            const int64_t l = L[i];
+            const int32_t r = R[i], f = F[i];
+            return x != y && closure_valid(l, r) && f >= min_confirm;
+        };
+#pragma unroll 4
+        for (uint32_t i = threadIdx.x; i < nt * C; i += ASX_THREADS) {
+            const uint32_t al = i / C, b = i - al * C;
+            if (usable(a0 + al, b)) atomicAdd(&score[al], 1);
+        }
+#pragma unroll 4
+        for (uint32_t i = threadIdx.x; i < nt * C; i += ASX_THREADS) {
+            const uint32_t b = i / nt, al = i - b * nt;
+            if (usable(b, a0 + al)) atomicAdd(&score[al], 1);
+        }
+        __syncthreads();
+        int32_t s = threadIdx.x < nt ? score[threadIdx.x] : -1;
+        uint32_t a = a0 + threadIdx.x;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int32_t s2 = __shfl_xor(s, o);
+            const uint32_t a2 = __shfl_xor(a, o);
+            if (s2 > s || (s2 == s && a2 < a)) { s = s2; a = a2; }
+        }
+        if ((threadIdx.x & 63u) == 0) { red_s[threadIdx.x >> 6] = s; red_a[threadIdx.x >> 6] = a; }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < ASX_THREADS / 64; i++)              // waves and tiles in ascending order of a: strictly more wins
+            if (red_s[i] > best) { best = red_s[i]; best_a = red_a[i]; }
+    }
+    if (threadIdx.x == 0) out[0] = (int32_t)best_a;
+}
+
+// Clip b's estimates of T_b - T_root that hold clip c (the multiset E_b of the header), each handed to fn
+template <typename Fn>
+__device__ __forceinline__ void closure_estimates(const int64_t *L, const int32_t *R, const int32_t *F, uint32_t C, int min_confirm,
+                                                  uint32_t r, uint32_t b, uint32_t c, Fn &&fn)
+{
+    if (c == b) {
+        if (closure_usable(L, R, F, C, min_confirm, r, b)) fn(L[r * C + b]);
+    } else if (c == r) {
+        if (closure_usable(L, R, F, C, min_confirm, b, r)) fn(-L[b * C + r]);
+    } else {
+        if (closure_usable(L, R, F, C, min_confirm, r, c) && closure_usable(L, R, F, C, min_confirm, c, b)) fn(L[r * C + c] + L[c * C + b]);
+        if (closure_usable(L, R, F, C, min_confirm, b, c) && closure_usable(L, R, F, C, min_confirm, c, r)) fn(-(L[b * C + c] + L[c * C + r]));
+    }
+}
+
+// Offsets, one block per clip b: the lower median of E_b by rank counting -- the smallest v with #(x <= v) > (|E_b| - 1) / 2, found by
+// bisection between the smallest and the largest estimate, each step one count over the block -- and the number of estimates within
+// tol of it.  E_b is never stored: an estimate is two lags and their flags, read again (from L2) at every step, so any C fits; a
+// pool whose usable pairs agree has its estimates a few frames apart and needs a few steps.
+__global__ __launch_bounds__(ASX_THREADS) void k_closure_offsets(const int64_t *__restrict__ L, const int32_t *__restrict__ R,
+                                                                  const int32_t *__restrict__ F, uint32_t C, int64_t tol,
+                                                                  int min_confirm, const int32_t *__restrict__ root,
+                                                                  int64_t *__restrict__ offset, int32_t *__restrict__ support,
+                                                                  int32_t *__restrict__ placed)
+{
+    __shared__ int32_t red[2][ASX_THREADS / 64];
+    __shared__ int64_t red_lo[ASX_THREADS / 64], red_hi[ASX_THREADS / 64];
+    const uint32_t b = blockIdx.x, r = (uint32_t)root[0];
+    if (b == r) {
+        if (threadIdx.x == 0) { offset[b] = 0; support[b] = 0; placed[b] = 1; }
+        return;
+    }
+    // how many estimates there are, the smallest and the largest
+    int32_t n = 0;
+    int64_t lo = INT64_MAX, hi = INT64_MIN;
+    for (uint32_t c = threadIdx.x; c < C; c += ASX_THREADS)
+        closure_estimates(L, R, F, C, min_confirm, r, b, c, [&](int64_t x) { n++; lo = x < lo ? x : lo; hi = x > hi ? x : hi; });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int64_t l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+    }
+    if ((threadIdx.x & 63u) == 0) { red_lo[threadIdx.x >> 6] = lo; red_hi[threadIdx.x >> 6] = hi; }
+    const int32_t total = closure_block_sum(n, red[0]);         // (its barrier also covers red_lo and red_hi)
+#pragma unroll
+    for (int i = 0; i < ASX_THREADS / 64; i++) {
+        lo = red_lo[i] < lo ? red_lo[i] : lo;
+        hi = red_hi[i] > hi ? red_hi[i] : hi;
+    }
+    int turn = 0;
+    auto count_le = [&](int64_t v) {
+        int32_t m = 0;
+        for (uint32_t c = threadIdx.x; c < C; c += ASX_THREADS)
+            closure_estimates(L, R, F, C, min_confirm, r, b, c, [&](int64_t x) { m += x <= v ? 1 : 0; });
+        turn ^= 1;
+        return closure_block_sum(m, red[turn]);
+    };
+    int64_t med = 0;
+    int32_t sup = 0;
+    if (total > 0) {
+        const int32_t want = (total - 1) / 2 + 1;               // the median is the smallest v with at least this many at or below it
+        lo -= 1;                                                // count_le(lo) = 0 < want <= total = count_le(hi)
+        while (hi - lo > 1) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (count_le(mid) >= want) hi = mid; else lo = mid;
+        }
+        med = hi;
+        sup = count_le(med + tol) - count_le(med - tol - 1);
+    }
+    if (threadIdx.x == 0) { offset[b] = med; support[b] = sup; placed[b] = total > 0 ? 1 : 0; }
+}
+
+// ---------------------------------------------------------------------------
 // The curve around given lags (asx_xcorr_curve_f32_dev, asx_xcorr_pool_curve_f32_dev): behind any call, on the lags it returned,
 //     r[idx] = sum_{n<N} source[(n + idx) mod 2N] * sample[n]     at idx = (p + d) mod 2N, d = -h .. h,
 // the sum of k_refine_dots, for all 2h + 1 indices in ONE pass over the entry's tracks: with i0 = (p - h) mod 2N, sample n meets
@@ -2436,6 +2738,23 @@ void asx_launch_topk_best(const int64_t *lag, const double *coef, const int32_t 
     const unsigned blocks = (unsigned)((batch + ASX_THREADS - 1) / ASX_THREADS);
     hipLaunchKernelGGL(k_topk_best, dim3(blocks), dim3(ASX_THREADS), 0, s, lag, coef, ret, batch, k, best_lag, best_coef, best_ret,
                        best_entry);
+}
+
+void asx_launch_pool_closure(const int64_t *lag, const double *coef, const int32_t *ret, uint32_t C, int k, int64_t tol,
+                             int min_confirm, int root, int32_t *votes, int64_t *best_lag, double *best_coef, int32_t *best_ret,
+                             int32_t *best_entry, int32_t *confirm, int32_t *d_root, int64_t *offset, int32_t *support,
+                             int32_t *placed, hipStream_t s)
+{
+    const dim3 block(ASX_THREADS);
+    hipLaunchKernelGGL(k_closure_votes, dim3((C + ASX_CLOSURE_BT - 1) / ASX_CLOSURE_BT, C), block, 0, s, lag, coef, ret, C, k, tol,
+                       votes, best_lag, best_coef, best_ret, best_entry);
+    const uint32_t per = ASX_THREADS / 64;
+    hipLaunchKernelGGL(k_closure_confirm, dim3((C * C + per - 1) / per), block, 0, s, (const int64_t *)best_lag,
+                       (const int32_t *)best_ret, C, tol, confirm);
+    hipLaunchKernelGGL(k_closure_root, dim3(1), block, 0, s, (const int64_t *)best_lag, (const int32_t *)best_ret,
+                       (const int32_t *)confirm, C, min_confirm, root, d_root);
+    hipLaunchKernelGGL(k_closure_offsets, dim3(C), block, 0, s, (const int64_t *)best_lag, (const int32_t *)best_ret,
+                       (const int32_t *)confirm, C, tol, min_confirm, (const int32_t *)d_root, offset, support, placed);
 }
 
 unsigned asx_curve_blocks(uint32_t N)

@@ -85,6 +85,7 @@ _HEADER_SIGNATURES = {
     "asx_pearson_f64": (_int, [c_f64p, c_f64p, _sz, _int, c_f64p]),
     "asx_results_to_ms_dev": (_int, [_vp, _vp, _vp, _sz, _dbl, _dbl, _vp, _vp, _vp]),
     "asx_topk_best_dev": (_int, [_vp, _vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp]),
+    "asx_pool_closure_dev": (_int, [_vp, _vp, _vp, _sz, _int, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_synth_pairs_dev": (_int, [_u64, _u64, _sz, _sz, _int, _vp, _vp, _vp, _vp]),
     "asx_shard_range": (_int, [_sz, _int, _int, _szp, _szp]),
     "asx_result_bytes": (_sz, [_sz]),
@@ -135,6 +136,7 @@ NEAR_MAX = 8  # ASX_NEAR_MAX, include/audiosync/xcorr_hip.h
 TRACK_HALF_MAX = 64  # ASX_TRACK_HALF_MAX, include/audiosync/xcorr_hip.h
 TRACK_SEG_MAX = 64   # ASX_TRACK_SEG_MAX, include/audiosync/xcorr_hip.h
 WARP_DRIFT_MAX = 2.0 ** -6  # ASX_WARP_DRIFT_MAX, include/audiosync/xcorr_hip.h
+CLOSURE_LAG_MAX = 1 << 40   # ASX_CLOSURE_LAG_MAX, include/audiosync/xcorr_hip.h
 
 
 class AsxError(RuntimeError):
@@ -330,6 +332,82 @@ def topk_best_dev(d_lag, d_coef, d_ret, batch, k, d_best_coef, d_best_ret, d_bes
     signed coefficient (none: entry 0) to index i of the best arrays, which results_to_ms_dev takes; asynchronous on `stream`"""
     _check(lib().asx_topk_best_dev(d_lag, d_coef, d_ret, int(batch), int(k), d_best_lag or None, d_best_coef, d_best_ret,
                                    d_best_entry or None, stream or None))
+
+
+def pool_closure_dev(d_lag, d_coef, d_ret, nclips, k, tolerance, min_confirm, root, d_best_lag, d_best_coef, d_best_ret, d_best_entry,
+                     d_confirm, d_root, d_offset, d_support, d_placed, d_votes=0, stream=0):
+    """raw device pointers (ints): asx_pool_closure_dev -- over the [C, C, k] tables of an all-pairs top-k call on one pool, per pair
+    the entry the other clips agree with (triangle closure) to index a * C + b of the best arrays, which results_to_ms_dev takes,
+    the clips that confirm each pick, the root and every clip's offset from it; d_votes [C * C * k] is optional; asynchronous on
+    `stream`, on the current device"""
+    _check(lib().asx_pool_closure_dev(d_lag, d_coef, d_ret, int(nclips), int(k), int(tolerance), int(min_confirm), int(root),
+                                      d_votes or None, d_best_lag, d_best_coef, d_best_ret, d_best_entry, d_confirm, d_root, d_offset,
+                                      d_support, d_placed, stream or None))
+
+
+def closure_args(lag, coef, ret, tolerance, min_confirm=1, root=-1):
+    """Host checks of pool_closure: lag and ret integer arrays and coef a real one, all of one shape [C, C, k] with C >= 1 and
+    1 <= k <= TOPK_MAX (C * C * k <= 2^31 - 1, lags within int64, rets within int32); tolerance an integer in [0, CLOSURE_LAG_MAX],
+    min_confirm an integer >= 0, root an integer in [-1, C) -- no bools, no floats.  -> (lag int64, coef float64, ret int32, C, k,
+    tolerance, min_confirm, root) as contiguous arrays and ints.  ValueError on anything else.  The values of the tables are not
+    checked: an entry with ret != 0 or |lag| > CLOSURE_LAG_MAX is not valid, which is part of the rule."""
+    lg, cf, rt = np.asarray(lag), np.asarray(coef), np.asarray(ret)
+    if lg.dtype.kind not in "iu" or rt.dtype.kind not in "iu":
+        raise ValueError("lag and ret must hold integers, not %s and %s" % (lg.dtype, rt.dtype))
+    if cf.dtype.kind not in "fiu":
+        raise ValueError("coef must hold real numbers, not %s" % cf.dtype)
+    if lg.ndim != 3 or lg.shape[0] != lg.shape[1] or cf.shape != lg.shape or rt.shape != lg.shape:
+        raise ValueError("lag, coef and ret must share one shape [C, C, k], not %s, %s and %s"
+                         % (list(lg.shape), list(cf.shape), list(rt.shape)))
+    c, k = lg.shape[0], lg.shape[2]
+    if c < 1 or not 1 <= k <= TOPK_MAX or c * c * k > 2 ** 31 - 1:
+        raise ValueError("[C, C, k] needs C >= 1, 1 <= k <= %d and C * C * k <= 2^31 - 1, not C = %d, k = %d" % (TOPK_MAX, c, k))
+    if lg.dtype == np.uint64 and lg.max() > 2 ** 63 - 1:
+        raise ValueError("lags must fit int64")
+    if rt.min() < -2 ** 31 or rt.max() > 2 ** 31 - 1:
+        raise ValueError("rets must fit int32")
+    for name, v, lo, hi in (("tolerance", tolerance, 0, CLOSURE_LAG_MAX), ("min_confirm", min_confirm, 0, 2 ** 31 - 1),
+                            ("root", root, -1, c - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError("%s must be an integer in [%d, %d], not %r" % (name, lo, hi, v))
+    return (np.ascontiguousarray(lg, dtype=np.int64), np.ascontiguousarray(cf, dtype=np.float64),
+            np.ascontiguousarray(rt, dtype=np.int32), c, k, int(tolerance), int(min_confirm), int(root))
+
+
+class _CurrentDevice:
+    """what _Staging needs of a plan, for the calls that take none: they run on the current device, on the null stream"""
+
+    def __init__(self, device):
+        current = lib().asx_current_device()
+        if device not in (-1, current):
+            raise AsxError("this call takes no plan and runs on the current device (%d), not on device %d" % (current, device))
+        self.device = -1
+
+    def sync(self):
+        _check(lib().asx_stream_sync(None, None))
+
+
+def pool_closure(lag, coef, ret, tolerance, min_confirm=1, root=-1, device=-1, votes=False):
+    """Triangle closure over one clip pool (asx_pool_closure_dev) on host arrays: lag, coef, ret of shape [C, C, k] as
+    Plan.xcorr_pool_topk_f32 returns them for one array as both pools (pairs=None).  Arguments are checked on the host (closure_args,
+    ValueError) before anything is uploaded.  Returns a dict of numpy arrays: best_lag int64, best_coef float64, best_ret, best_entry
+    and confirm int32 of shape [C, C]; root, an int; offset int64, support and placed int32 of shape [C]; votes int32 [C, C, k] when
+    votes=True.  device: -1 or the current device (the call takes no plan)."""
+    lg, cf, rt, c, k, tolerance, min_confirm, root = closure_args(lag, coef, ret, tolerance, min_confirm, root)
+    with _Staging(_CurrentDevice(int(device))) as st:
+        d_in = [st.upload(a) for a in (lg, cf, rt)]
+        d_votes = st.output((c, c, k), np.int32) if votes else 0
+        names = (("best_lag", (c, c), np.int64), ("best_coef", (c, c), np.float64), ("best_ret", (c, c), np.int32),
+                 ("best_entry", (c, c), np.int32), ("confirm", (c, c), np.int32), ("root", (1,), np.int32), ("offset", (c,), np.int64),
+                 ("support", (c,), np.int32), ("placed", (c,), np.int32))
+        d_out = [st.output(shape, dt) for _, shape, dt in names]
+        pool_closure_dev(*d_in, c, k, tolerance, min_confirm, root, *d_out, d_votes=d_votes)
+        got = st.fetch()
+    out = dict(zip([n for n, _, _ in names], got[1:] if votes else got))
+    out["root"] = int(out["root"][0])
+    if votes:
+        out["votes"] = got[0]
+    return out
 
 
 def synth_pairs_dev(seed, first_pair, count, sample_len, noise_shift, d_src, d_smp, d_lag=0, stream=0):
