@@ -1618,17 +1618,20 @@ extern "C" int asx_xcorr_pool_phat_sub_f32_dev(asx_plan *p, const float *d_sourc
 // returned.  No transform, no group: r and frac from k_curve_dots over the tracks themselves, the coefficient curve from the direct
 // Pearson kernels over one virtual pair per neighbour; both in slices of a launch group, in lane 0's records and psums.
 // ---------------------------------------------------------------------------
-// both entry points (fn: the entry point's name for the messages; pooled: nsrc, nsmp and d_pairs mean something)
-static int curve_call(asx_plan *p, const char *fn, bool pooled, const float *d_src, size_t src_stride, size_t nsrc, const float *d_smp,
-                      size_t smp_stride, size_t nsmp, const int32_t *d_pairs, size_t batch, int entries, const int64_t *d_center,
-                      int half_width, double *d_r, double *d_coef, double *d_frac, int32_t *d_ret, void *stream)
+// What the curve, track and warp calls share.  Before PlanCall, behind the caller's null check: the ranges of entries and of
+// half_width, at most hmax (fn: the entry point's name for the messages).  0, or -1 with the message set.
+static int entries_ranges(const char *fn, int entries, int half_width, int hmax)
 {
-    if (!p || !d_src || !d_smp || !d_center || !d_r || !d_frac || !d_ret) return fail("%s: null argument", fn);
     if (entries < 1 || entries > ASX_TOPK_MAX) return fail("%s: entries = %d is not in [1, %d]", fn, entries, ASX_TOPK_MAX);
-    if (half_width < 1 || half_width > ASX_NEAR_MAX) return fail("%s: half_width = %d is not in [1, %d]", fn, half_width, ASX_NEAR_MAX);
-    PlanCall c(p, stream);
-    if (!c.dg.ok) return fail("cannot select device %d", p->device);
-    hipStream_t s = c.s;
+    if (half_width < 1 || half_width > hmax) return fail("%s: half_width = %d is not in [1, %d]", fn, half_width, hmax);
+    return 0;
+}
+// Behind PlanCall: the plan's layout against the inputs and the pools (pooled: nsrc, nsmp and d_pairs mean something), then E, the
+// call's entries as the kernels take them.  1: go on; 0: nothing to do; -1 with the message set.
+static int entries_of_call(const asx_plan *p, const char *fn, bool pooled, const float *d_src, size_t src_stride, size_t nsrc,
+                           const float *d_smp, size_t smp_stride, size_t nsmp, const int32_t *d_pairs, size_t batch, int entries,
+                           const int64_t *d_center, int half_width, AsxLagEntries &E)
+{
     const AsxDev &P = p->dev;
     if (pooled && P.rlayout != 1) return fail("%s: pool calls need a real-column plan (asx_plan_layout() == 1)", fn);
     if (P.rlayout) {
@@ -1646,20 +1649,40 @@ static int curve_call(asx_plan *p, const char *fn, bool pooled, const float *d_s
     }
     if (batch == 0) return 0;
     if (pooled && (nsrc == 0 || nsmp == 0)) return fail("%s: an empty pool (%zu sources, %zu samples) for %zu pairs", fn, nsrc, nsmp, batch);
+    E = AsxLagEntries{ d_center, P.N, entries, half_width, pooled ? d_pairs : nullptr, pooled ? (uint64_t)nsrc : 0u,
+                       pooled ? (uint64_t)nsmp : 0u, (uint64_t)src_stride, (uint64_t)smp_stride };
+    return 1;
+}
+// go(first, count) over [0, total) in slices of a launch group
+template <class F> static void group_slices(const asx_plan *p, size_t total, F go)
+{
+    for (size_t e0 = 0; e0 < total; e0 += p->group) go(e0, (int)std::min(p->group, total - e0));
+}
+
+// both entry points
+static int curve_call(asx_plan *p, const char *fn, bool pooled, const float *d_src, size_t src_stride, size_t nsrc, const float *d_smp,
+                      size_t smp_stride, size_t nsmp, const int32_t *d_pairs, size_t batch, int entries, const int64_t *d_center,
+                      int half_width, double *d_r, double *d_coef, double *d_frac, int32_t *d_ret, void *stream)
+{
+    if (!p || !d_src || !d_smp || !d_center || !d_r || !d_frac || !d_ret) return fail("%s: null argument", fn);
+    if (entries_ranges(fn, entries, half_width, ASX_NEAR_MAX)) return -1;
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
+    AsxCurve A{ {}, d_r, d_frac, d_ret };
+    const int go = entries_of_call(p, fn, pooled, d_src, src_stride, nsrc, d_smp, smp_stride, nsmp, d_pairs, batch, entries, d_center,
+                                   half_width, A.E);
+    if (go <= 0) return go;
     asx_plan::Lane &W = p->lanes[0];
-    const AsxCurve A{ d_center, d_r, d_frac, d_ret, P.N, entries, half_width, pooled ? d_pairs : nullptr,
-                      pooled ? (uint64_t)nsrc : 0u, pooled ? (uint64_t)nsmp : 0u, (uint64_t)src_stride, (uint64_t)smp_stride };
     const size_t total = batch * (size_t)entries, n = 2 * (size_t)half_width + 1;
-    for (size_t e0 = 0; e0 < total; e0 += p->group)
-        asx_launch_curve_r(d_src, d_smp, A, e0, (int)std::min(p->group, total - e0), W.pool, W.psums, s);
+    group_slices(p, total, [&](size_t e0, int g) { asx_launch_curve_r(d_src, d_smp, A, e0, g, W.pool, W.psums, s); });
     if (d_coef) {
         // one direct Pearson pass per neighbour: the kernels, the chunks and the merge tree of a windowed call with the row [l, l]
         const AsxInputs<float> in{ d_src, d_smp, 0, 0, W.pool };
-        for (size_t v0 = 0; v0 < total * n; v0 += p->group) {
-            const int g = (int)std::min(p->group, total * n - v0);
-            asx_launch_curve_segs(A, v0, g, W.seg, W.pool, s);
-            asx_launch_pearson(in, P.N, W.seg, W.psums, (int64_t *)nullptr, d_coef + v0, (int32_t *)nullptr, g, s);
-        }
+        group_slices(p, total * n, [&](size_t v0, int g) {
+            asx_launch_curve_segs(A.E, v0, g, W.seg, W.pool, s);
+            asx_launch_pearson(in, p->dev.N, W.seg, W.psums, (int64_t *)nullptr, d_coef + v0, (int32_t *)nullptr, g, s);
+        });
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1693,37 +1716,18 @@ static int track_call(asx_plan *p, const char *fn, bool pooled, const float *d_s
                       void *stream)
 {
     if (!p || !d_src || !d_smp || !d_center || !d_r || !d_fit || !d_used || !d_ret) return fail("%s: null argument", fn);
-    if (entries < 1 || entries > ASX_TOPK_MAX) return fail("%s: entries = %d is not in [1, %d]", fn, entries, ASX_TOPK_MAX);
-    if (half_width < 1 || half_width > ASX_TRACK_HALF_MAX)
-        return fail("%s: half_width = %d is not in [1, %d]", fn, half_width, ASX_TRACK_HALF_MAX);
+    if (entries_ranges(fn, entries, half_width, ASX_TRACK_HALF_MAX)) return -1;
     PlanCall c(p, stream);
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
     hipStream_t s = c.s;
-    const AsxDev &P = p->dev;
-    if (segments < 1 || segments > ASX_TRACK_SEG_MAX || (uint64_t)segments > (uint64_t)P.N)
-        return fail("%s: segments = %d is not in [1, min(%d, N = %u)]", fn, segments, ASX_TRACK_SEG_MAX, (unsigned)P.N);
-    if (pooled && P.rlayout != 1) return fail("%s: pool calls need a real-column plan (asx_plan_layout() == 1)", fn);
-    if (P.rlayout) {
-        if (((uintptr_t)d_src & 15u) || ((uintptr_t)d_smp & 15u))
-            return fail("%s: real-column plans need 16-byte aligned inputs (source %p, sample %p)", fn, (const void *)d_src,
-                        (const void *)d_smp);
-        if ((src_stride & 3u) || (smp_stride & 3u))
-            return fail("%s: real-column plans need strides that are multiples of 4 floats (source_stride %zu, sample_stride %zu)", fn,
-                        src_stride, smp_stride);
-    }
-    if (pooled) {
-        if (nsrc > INT32_MAX || nsmp > INT32_MAX) return fail("%s: a pool of more than 2^31 - 1 tracks", fn);
-        if (!d_pairs && batch != nsrc * nsmp)
-            return fail("%s: without pairs the batch is every combination, %zu x %zu, not %zu", fn, nsrc, nsmp, batch);
-    }
-    if (batch == 0) return 0;
-    if (pooled && (nsrc == 0 || nsmp == 0)) return fail("%s: an empty pool (%zu sources, %zu samples) for %zu pairs", fn, nsrc, nsmp, batch);
+    if (segments < 1 || segments > ASX_TRACK_SEG_MAX || (uint64_t)segments > (uint64_t)p->dev.N)
+        return fail("%s: segments = %d is not in [1, min(%d, N = %u)]", fn, segments, ASX_TRACK_SEG_MAX, (unsigned)p->dev.N);
+    AsxTrack A{ {}, segments, d_r, d_seg, d_fit, d_used, d_ret };
+    const int go = entries_of_call(p, fn, pooled, d_src, src_stride, nsrc, d_smp, smp_stride, nsmp, d_pairs, batch, entries, d_center,
+                                   half_width, A.E);
+    if (go <= 0) return go;
     asx_plan::Lane &W = p->lanes[0];
-    const AsxTrack A{ d_center, d_r, d_seg, d_fit, d_used, d_ret, P.N, entries, half_width, segments, pooled ? d_pairs : nullptr,
-                      pooled ? (uint64_t)nsrc : 0u, pooled ? (uint64_t)nsmp : 0u, (uint64_t)src_stride, (uint64_t)smp_stride };
-    const size_t total = batch * (size_t)entries;
-    for (size_t e0 = 0; e0 < total; e0 += p->group)
-        asx_launch_track(d_src, d_smp, A, e0, (int)std::min(p->group, total - e0), W.pool, W.psums, s);
+    group_slices(p, batch * (size_t)entries, [&](size_t e0, int g) { asx_launch_track(d_src, d_smp, A, e0, g, W.pool, W.psums, s); });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1757,36 +1761,17 @@ static int warp_call(asx_plan *p, const char *fn, bool pooled, const float *d_sr
                      int64_t *d_len, int32_t *d_ret, void *stream)
 {
     if (!p || !d_src || !d_smp || !d_center || !d_line || !d_r || !d_frac || !d_coef || !d_ret) return fail("%s: null argument", fn);
-    if (entries < 1 || entries > ASX_TOPK_MAX) return fail("%s: entries = %d is not in [1, %d]", fn, entries, ASX_TOPK_MAX);
-    if (half_width < 1 || half_width > ASX_NEAR_MAX) return fail("%s: half_width = %d is not in [1, %d]", fn, half_width, ASX_NEAR_MAX);
+    if (entries_ranges(fn, entries, half_width, ASX_NEAR_MAX)) return -1;
     if (line_stride == 1) return fail("%s: line_stride = 1: a line is two doubles (0: one line for every entry)", fn);
     PlanCall c(p, stream);
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
     hipStream_t s = c.s;
-    const AsxDev &P = p->dev;
-    if (pooled && P.rlayout != 1) return fail("%s: pool calls need a real-column plan (asx_plan_layout() == 1)", fn);
-    if (P.rlayout) {
-        if (((uintptr_t)d_src & 15u) || ((uintptr_t)d_smp & 15u))
-            return fail("%s: real-column plans need 16-byte aligned inputs (source %p, sample %p)", fn, (const void *)d_src,
-                        (const void *)d_smp);
-        if ((src_stride & 3u) || (smp_stride & 3u))
-            return fail("%s: real-column plans need strides that are multiples of 4 floats (source_stride %zu, sample_stride %zu)", fn,
-                        src_stride, smp_stride);
-    }
-    if (pooled) {
-        if (nsrc > INT32_MAX || nsmp > INT32_MAX) return fail("%s: a pool of more than 2^31 - 1 tracks", fn);
-        if (!d_pairs && batch != nsrc * nsmp)
-            return fail("%s: without pairs the batch is every combination, %zu x %zu, not %zu", fn, nsrc, nsmp, batch);
-    }
-    if (batch == 0) return 0;
-    if (pooled && (nsrc == 0 || nsmp == 0)) return fail("%s: an empty pool (%zu sources, %zu samples) for %zu pairs", fn, nsrc, nsmp, batch);
+    AsxWarp A{ {}, d_line, (uint64_t)line_stride, d_r, d_frac, d_coef, d_len, d_ret };
+    const int go = entries_of_call(p, fn, pooled, d_src, src_stride, nsrc, d_smp, smp_stride, nsmp, d_pairs, batch, entries, d_center,
+                                   half_width, A.E);
+    if (go <= 0) return go;
     asx_plan::Lane &W = p->lanes[0];
-    const AsxWarp A{ d_center, d_line, (uint64_t)line_stride, d_r, d_frac, d_coef, d_len, d_ret, P.N, entries, half_width,
-                     pooled ? d_pairs : nullptr, pooled ? (uint64_t)nsrc : 0u, pooled ? (uint64_t)nsmp : 0u, (uint64_t)src_stride,
-                     (uint64_t)smp_stride };
-    const size_t total = batch * (size_t)entries;
-    for (size_t e0 = 0; e0 < total; e0 += p->group)
-        asx_launch_warp(d_src, d_smp, A, e0, (int)std::min(p->group, total - e0), W.pool, W.psums, s);
+    group_slices(p, batch * (size_t)entries, [&](size_t e0, int g) { asx_launch_warp(d_src, d_smp, A, e0, g, W.pool, W.psums, s); });
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -341,11 +341,13 @@ template <typename TIn> struct AsxInputs {
 // Inputs: where pair i's tracks start, in elements from src / smp
 struct AsxAtPitch {
     size_t src_pitch, smp_pitch; // 0 = one track for every pair
+    __device__ __forceinline__ const AsxPoolPair *list() const { return nullptr; }
     __device__ __forceinline__ size_t src_off(size_t pair) const { return pair * src_pitch; }
     __device__ __forceinline__ size_t smp_off(size_t pair) const { return pair * smp_pitch; }
 };
 struct AsxAtList {
     const AsxPoolPair *__restrict__ pl;
+    __device__ __forceinline__ const AsxPoolPair *list() const { return pl; }
     __device__ __forceinline__ size_t src_off(size_t pair) const { return pl[pair].src_off; }
     __device__ __forceinline__ size_t smp_off(size_t pair) const { return pl[pair].smp_off; }
 };
@@ -589,20 +591,25 @@ void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, 
 #define ASX_NEAR_MAX 8
 void asx_launch_phat_near(const AsxDev &P, const float2 *q, const AsxSeg *seg, double f, int h, const AsxSearch &find,
                           const AsxPoolPair *pl, double *frac, double *near, int npairs, hipStream_t s);
+// The entries of a call of the curve, the lag track or the warped correlation, as their kernels take them, by value.  Entry e = pair *
+// entries + j is centred on the lag center[e]; pair i is tracks (i, i) at the strides of the strided form (nsrc == 0), or the tracks
+// of row i of `rows` (null: every combination, source-major) in the pool form (nsrc > 0: a pool call with pairs never has an empty
+// pool).
+struct AsxLagEntries {
+    const int64_t *center;  // [batch * entries] lags, the convention of every d_lag
+    uint32_t N;
+    int entries, h;         // h: the half width, 2 h + 1 values around each centre
+    const int32_t *rows;
+    uint64_t nsrc, nsmp, src_stride, smp_stride;
+};
 // The curve around given lags (asx_xcorr_curve_f32_dev, asx_xcorr_pool_curve_f32_dev; xcorr_kernels.hip: k_curve_dots): one call's
-// arguments as its kernels take them, by value.  Entry e = pair * entries + j is centred on the lag center[e]; pair i is tracks
-// (i, i) at the strides of the strided form (nsrc == 0), or the tracks of row i of `rows` (null: every combination, source-major) in
-// the pool form (nsrc > 0: a pool call with pairs never has an empty pool).
+// arguments as its kernels take them, by value.
 #define ASX_CURVE_N (2 * ASX_NEAR_MAX + 1)
 struct AsxCurve {
-    const int64_t *center;  // [batch * entries] lags, the convention of every d_lag
+    AsxLagEntries E;
     double *r;              // [batch * entries][2 h + 1]
     double *frac;           // [batch * entries]
     int32_t *ret;           // [batch * entries]
-    uint32_t N;
-    int entries, h;
-    const int32_t *rows;
-    uint64_t nsrc, nsmp, src_stride, smp_stride;
 };
 // blocks of k_curve_dots per entry: by the length alone, as asx_pearson_blocks, and as many as leave their ASX_CURVE_N partial sums
 // in a pair's share of the lane's psums (6 doubles per Pearson block); one block writes its entry's results itself
@@ -614,23 +621,19 @@ void asx_launch_curve_r(const float *src, const float *smp, const AsxCurve &A, s
 // the coefficient curve's virtual pairs first .. first + count - 1 (virtual pair e (2 h + 1) + d + h: entry e at its neighbour d),
 // count at most a launch group: each one's segment to seg and its tracks' offsets to pl, what asx_launch_pearson's listed form reads.
 // An invalid entry's get an empty segment at offset 0: nothing is read and the coefficient is NaN.
-void asx_launch_curve_segs(const AsxCurve &A, size_t first, int count, AsxSeg *seg, AsxPoolPair *pl, hipStream_t s);
+void asx_launch_curve_segs(const AsxLagEntries &E, size_t first, int count, AsxSeg *seg, AsxPoolPair *pl, hipStream_t s);
 // The lag track (asx_xcorr_track_f32_dev, asx_xcorr_pool_track_f32_dev; xcorr_kernels.hip: k_track_dots, k_track_fit): one call's
-// arguments as its kernels take them, by value.  Entries, centres, pairs and pools as in AsxCurve; S time segments, segment s the
-// sample's frames [floor(s N / S), floor((s + 1) N / S)).
+// arguments as its kernels take them, by value.  S time segments, segment s the sample's frames [floor(s N / S), floor((s + 1) N / S)).
 #define ASX_TRACK_HALF_MAX 64
 #define ASX_TRACK_SEG_MAX 64
 struct AsxTrack {
-    const int64_t *center;  // [batch * entries]
+    AsxLagEntries E;
+    int S;
     double *r;              // [batch * entries][S][2 h + 1]
     double *seg;            // [batch * entries][S][2] {off, w}, or null
     double *fit;            // [batch * entries][3] {drift, lag0, rms}
     int32_t *used;          // [batch * entries]
     int32_t *ret;           // [batch * entries]
-    uint32_t N;
-    int entries, h, S;
-    const int32_t *rows;
-    uint64_t nsrc, nsmp, src_stride, smp_stride;
 };
 // blocks of k_track_dots per (segment, lag tile): floor(asx_curve_blocks(N) / (S * tiles)), tiles = ceil((2h + 1) / ASX_CURVE_N), so
 // that an entry's partial sums fit its share of the lane's psums as the curve's do; at least one, which writes its values itself.
@@ -641,12 +644,11 @@ unsigned asx_track_blocks(uint32_t N, int segments, int half_width);
 void asx_launch_track(const float *src, const float *smp, const AsxTrack &A, size_t first, int count, AsxPoolPair *pl, double *part,
                       hipStream_t s);
 // The warped correlation (asx_xcorr_warp_f32_dev, asx_xcorr_pool_warp_f32_dev; xcorr_kernels.hip: k_warp_dots, k_warp_final): one
-// call's arguments as its kernels take them, by value.  Entries, centres, pairs and pools as in AsxCurve; entry e's line is
-// {line[e * line_stride], line[e * line_stride + 1]} = {drift a, lag0 b}: sample frame n meets source frame n + centre + k_n,
-// k_n = floor((b + a n) + 0.5).
+// call's arguments as its kernels take them, by value.  Entry e's line is {line[e * line_stride], line[e * line_stride + 1]} =
+// {drift a, lag0 b}: sample frame n meets source frame n + centre + k_n, k_n = floor((b + a n) + 0.5).
 #define ASX_WARP_DRIFT_MAX 0.015625
 struct AsxWarp {
-    const int64_t *center;  // [batch * entries]
+    AsxLagEntries E;
     const double *line;     // entry e's {a, b} at e * line_stride
     uint64_t line_stride;   // in doubles: 0, 2, 3, ...
     double *r;              // [batch * entries][2 h + 1]
@@ -654,10 +656,6 @@ struct AsxWarp {
     double *coef;           // [batch * entries]
     int64_t *len;           // [batch * entries], or null
     int32_t *ret;           // [batch * entries]
-    uint32_t N;
-    int entries, h;
-    const int32_t *rows;
-    uint64_t nsrc, nsmp, src_stride, smp_stride;
 };
 // blocks of k_warp_dots per entry: by the length alone, as asx_curve_blocks, and as many as leave their ASX_CURVE_N partial sums and
 // their Pearson record (6 doubles) in a pair's share of the lane's psums; one block leaves its sums in r and its record in part[le * 6]

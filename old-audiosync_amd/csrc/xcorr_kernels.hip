@@ -1722,22 +1722,33 @@ __global__ __launch_bounds__(ASX_THREADS) void k_closure_offsets(const int64_t *
 // the sum of k_refine_dots, for all 2h + 1 indices in ONE pass over the entry's tracks: with i0 = (p - h) mod 2N, sample n meets
 // source (n + i0 + j) mod 2N for j = 0 .. 2h, a window that slides with n.
 // ---------------------------------------------------------------------------
-// where entry e's tracks are and what its ret is: -4 for a row outside its pool (over -2), -2 for a centre outside [-N, N-1]
-__device__ __forceinline__ int32_t curve_locate(const AsxCurve &A, size_t e, uint64_t &src_off, uint64_t &smp_off)
+// the ret of entry e as far as curve, track and warp share it: -4 for a row outside its pool (`outside`), over -2 for a centre
+// outside [-N, N-1]; 0 for an entry to compute
+__device__ __forceinline__ int32_t entry_ret(const AsxLagEntries &E, size_t e, bool outside)
 {
-    const size_t pair = e / (size_t)A.entries;
+    if (outside) return -4;
+    const int64_t c = E.center[e], n = (int64_t)E.N;
+    return (c < -n || c > n - 1) ? -2 : 0;
+}
+// ... behind k_curve_resolve (pl: the pool form's records, indexed by the entry's place in the slice le, or null)
+__device__ __forceinline__ int32_t entry_ret(const AsxLagEntries &E, size_t e, size_t le, const AsxPoolPair *pl)
+{
+    return entry_ret(E, e, pl && (pl[le].flags & ASX_POOL_INVALID));
+}
+// where entry e's tracks are and what its ret is
+__device__ __forceinline__ int32_t curve_locate(const AsxLagEntries &E, size_t e, uint64_t &src_off, uint64_t &smp_off)
+{
+    const size_t pair = e / (size_t)E.entries;
     int64_t a = (int64_t)pair, b = (int64_t)pair;
     bool in = true;
-    if (A.nsrc) {
-        if (A.rows) { a = A.rows[2 * pair]; b = A.rows[2 * pair + 1]; }
-        else { a = (int64_t)(pair / A.nsmp); b = (int64_t)(pair % A.nsmp); }
-        in = a >= 0 && (uint64_t)a < A.nsrc && b >= 0 && (uint64_t)b < A.nsmp;
+    if (E.nsrc) {
+        if (E.rows) { a = E.rows[2 * pair]; b = E.rows[2 * pair + 1]; }
+        else { a = (int64_t)(pair / E.nsmp); b = (int64_t)(pair % E.nsmp); }
+        in = a >= 0 && (uint64_t)a < E.nsrc && b >= 0 && (uint64_t)b < E.nsmp;
     }
-    src_off = in ? (uint64_t)a * A.src_stride : 0u;
-    smp_off = in ? (uint64_t)b * A.smp_stride : 0u;
-    if (!in) return -4;
-    const int64_t c = A.center[e], n = (int64_t)A.N;
-    return (c < -n || c > n - 1) ? -2 : 0;
+    src_off = in ? (uint64_t)a * E.src_stride : 0u;
+    smp_off = in ? (uint64_t)b * E.smp_stride : 0u;
+    return entry_ret(E, e, !in);
 }
 // index of the entry's first value, (p - h) mod 2N, p the index of the lag c in [-N, N-1]
 __device__ __forceinline__ uint32_t curve_first(int64_t c, uint32_t N, int h)
@@ -1749,257 +1760,84 @@ __device__ __forceinline__ uint32_t curve_first(int64_t c, uint32_t N, int h)
 // an entry's results from its 2h + 1 final values y (shared memory; not read when rv != 0): r, then frac, then ret
 __device__ __forceinline__ void curve_write(const AsxCurve &A, size_t e, int32_t rv, const double *y, int tid)
 {
-    const int n = 2 * A.h + 1;
+    const int h = A.E.h, n = 2 * h + 1;
     if (tid < n) A.r[e * (size_t)n + tid] = rv ? (double)NAN : y[tid];
     if (tid == 0) {
-        A.frac[e] = rv ? (double)NAN : asx_parabola_frac(y[A.h - 1], y[A.h], y[A.h + 1]);
+        A.frac[e] = rv ? (double)NAN : asx_parabola_frac(y[h - 1], y[h], y[h + 1]);
         A.ret[e] = rv;
     }
 }
 
 // pool form: entries first .. first + count - 1 as listed input records (what k_pool_resolve makes of a pair, without the bank)
-__global__ __launch_bounds__(ASX_THREADS) void k_curve_resolve(AsxCurve A, size_t first, int count, AsxPoolPair *__restrict__ out)
+__global__ __launch_bounds__(ASX_THREADS) void k_curve_resolve(AsxLagEntries E, size_t first, int count, AsxPoolPair *__restrict__ out)
 {
     const int le = (int)(blockIdx.x * ASX_THREADS + threadIdx.x);
     if (le >= count) return;
     AsxPoolPair rec;
-    const int32_t rv = curve_locate(A, first + (size_t)le, rec.src_off, rec.smp_off);
+    const int32_t rv = curve_locate(E, first + (size_t)le, rec.src_off, rec.smp_off);
     rec.sx = rec.sy = 0u;
     rec.flags = rv == -4 ? ASX_POOL_INVALID : 0u;
     rec.pad = 0u;
     out[le] = rec;
 }
 
-// grid (blocks per entry, entries of the slice), entry e = first + blockIdx.y.  Block x takes samples [x chunk, (x + 1) chunk) in
-// sweeps of ASX_CURVE_SWEEP: the sweep's stretch of the source, 2h values longer and taken modulo 2N, goes through LDS once, and a
-// thread forms the 2h + 1 products of each of its four consecutive samples from a window of 4 + 2h values it reads from there --
-// one pass over both tracks for all the sums.  float64 throughout (the products of float32 values are exact); the order is fixed:
-// a thread's samples ascending, the lanes of a wave (wave_sum), the waves, and, when the entry has more than one block, the blocks in
-// order (k_curve_sum, from `part`): an entry's bits depend on neither the batch nor its place in it.  With one block per entry the
-// block writes the results itself.  Where: AsxAtPitch, indexed by the entry's pair, or AsxAtList, indexed by the entry's place in
-// the slice (k_curve_resolve's records).  An entry that is not valid reads nothing.
+// The sweep that k_curve_dots, k_track_dots and k_warp_dots share.  A block takes a range of the sample's frames in sweeps of
+// ASX_CURVE_SWEEP: the sweep's stretch of the source, a few values longer and taken modulo 2N, goes through LDS once, and a thread
+// forms the products of each of its four consecutive samples from a window of values it reads from there -- one pass over both
+// tracks for all the sums.  float64 throughout (the products of float32 values are exact); the order is fixed: a thread's samples
+// ascending, the lanes of a wave (wave_sum), the waves, and, with more than one block, the blocks in order (from `part`): an entry's
+// bits depend on neither the batch nor its place in it.
 #define ASX_CURVE_SWEEP (4 * ASX_THREADS)
 typedef float asx_f4u __attribute__((ext_vector_type(4), aligned(4))); // four floats at any float-aligned address
-template <class Where>
-__global__ __launch_bounds__(ASX_THREADS) void k_curve_dots(const float *__restrict__ src, const float *__restrict__ smp, Where at,
-                                                             AsxCurve A, size_t first, double *__restrict__ part)
+// the thread's four samples y[n0 + t4 ..+ 3] of the sweep of cnt frames from n0; past the sweep's end: zeros, which meet zeros of
+// the stretch
+__device__ __forceinline__ asx_f4v sweep_samples(const float *y, uint64_t n0, uint32_t t4, uint32_t cnt)
 {
-    constexpr bool listed = std::is_same<Where, AsxAtList>::value;
-    __shared__ __attribute__((aligned(16))) float xs[ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX];
-    __shared__ double red[ASX_THREADS / 64][ASX_CURVE_N];
-    __shared__ double yv[ASX_CURVE_N];
-    const int tid = threadIdx.x, h = A.h, n = 2 * h + 1;
-    const size_t le = blockIdx.y, e = first + le;
-    const size_t rec = listed ? le : e / (size_t)A.entries;
-    const uint32_t N = A.N, L = 2u * N;
-    const int64_t c = A.center[e];
-    int32_t rv = (c < -(int64_t)N || c > (int64_t)N - 1) ? -2 : 0;
-    if constexpr (listed) {
-        if (at.pl[rec].flags & ASX_POOL_INVALID) rv = -4;
-    }
-    if (rv) { // (block-uniform: nobody is left at a barrier)
-        if (gridDim.x == 1) curve_write(A, e, rv, yv, tid);
-        return;
-    }
-    const uint32_t i0 = curve_first(c, N, h);
-    const float *x = src + at.src_off(rec);
-    const float *y = smp + at.smp_off(rec);
-    const uint32_t chunk = ((N + gridDim.x - 1) / gridDim.x + 3u) & ~3u;
-    const uint64_t lo = (uint64_t)blockIdx.x * chunk;
-    const uint64_t hi = lo + chunk < (uint64_t)N ? lo + chunk : (uint64_t)N;
-    double acc[ASX_CURVE_N];
-#pragma unroll
-    for (int j = 0; j < ASX_CURVE_N; j++) acc[j] = 0.0;
-    for (uint64_t n0 = lo; n0 < hi; n0 += ASX_CURVE_SWEEP) {
-        const uint32_t cnt = hi - n0 < (uint64_t)ASX_CURVE_SWEEP ? (uint32_t)(hi - n0) : (uint32_t)ASX_CURVE_SWEEP;
-        // the thread's four samples; past the block's end: zeros, which meet zeros below
-        const uint32_t t4 = 4u * (uint32_t)tid;
-        asx_f4v yq = { 0.0f, 0.0f, 0.0f, 0.0f };
-        if (t4 + 3u < cnt) yq = *reinterpret_cast<const asx_f4u *>(y + n0 + t4);
-        else {
-            if (t4 < cnt) yq.x = y[n0 + t4];
-            if (t4 + 1u < cnt) yq.y = y[n0 + t4 + 1u];
-            if (t4 + 2u < cnt) yq.z = y[n0 + t4 + 2u];
-        }
-        // xs[t] = source[(n0 + i0 + t) mod 2N] for t < cnt + 2h, zero behind: 16-byte loads where the four neither leave the sweep
-        // nor straddle the wrap
-        const uint32_t g0 = (uint32_t)((n0 + i0) % L), need = cnt + 2u * (uint32_t)h;
-        auto wrapped = [&](uint32_t i) { if (i >= L) { i -= L; if (i >= L) i %= L; } return i; };
-        for (uint32_t t = t4; t < (uint32_t)(ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX); t += (uint32_t)ASX_CURVE_SWEEP) {
-            asx_f4v v = { 0.0f, 0.0f, 0.0f, 0.0f };
-            if (t < need) {
-                const uint32_t g = wrapped(g0 + t);
-                if (t + 3u < need && g + 3u < L) v = *reinterpret_cast<const asx_f4u *>(x + g);
-                else {
-                    v.x = x[g];
-                    if (t + 1u < need) v.y = x[wrapped(g0 + t + 1u)];
-                    if (t + 2u < need) v.z = x[wrapped(g0 + t + 2u)];
-                    if (t + 3u < need) v.w = x[wrapped(g0 + t + 3u)];
-                }
-            }
-            *reinterpret_cast<asx_f4v *>(xs + t) = v;
-        }
-        __syncthreads();
-        double w[4 + 2 * ASX_NEAR_MAX];
-#pragma unroll
-        for (int q = 0; q < (4 + 2 * ASX_NEAR_MAX) / 4; q++) {
-            asx_f4v v = { 0.0f, 0.0f, 0.0f, 0.0f };
-            if (4 * q < 4 + 2 * h) v = *reinterpret_cast<const asx_f4v *>(xs + t4 + 4u * (uint32_t)q);
-            w[4 * q] = (double)v.x; w[4 * q + 1] = (double)v.y; w[4 * q + 2] = (double)v.z; w[4 * q + 3] = (double)v.w;
-        }
-        const double y0 = (double)yq.x, y1 = (double)yq.y, y2 = (double)yq.z, y3 = (double)yq.w;
-#pragma unroll
-        for (int j = 0; j < ASX_CURVE_N; j++) {
-            if (j < n) {
-                double a = acc[j];
-                a = fma(w[j], y0, a);
-                a = fma(w[j + 1], y1, a);
-                a = fma(w[j + 2], y2, a);
-                a = fma(w[j + 3], y3, a);
-                acc[j] = a;
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int j = 0; j < ASX_CURVE_N; j++) {
-        if (j < n) {
-            const double s = wave_sum(acc[j]);
-            if ((tid & 63) == 0) red[tid >> 6][j] = s;
-        }
-    }
-    __syncthreads();
-    if (tid < n) {
-        const double v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-        if (gridDim.x == 1) yv[tid] = v;
-        else part[(le * gridDim.x + blockIdx.x) * ASX_CURVE_N + tid] = v;
-    }
-    if (gridDim.x == 1) {
-        __syncthreads();
-        curve_write(A, e, 0, yv, tid);
-    }
-}
-
-// grid (entries of the slice), one wave: an entry's nb partial sums in block order, then its results; pl: the pool form's records
-__global__ __launch_bounds__(64) void k_curve_sum(AsxCurve A, size_t first, unsigned nb, const double *__restrict__ part,
-                                                   const AsxPoolPair *__restrict__ pl)
-{
-    __shared__ double yv[ASX_CURVE_N];
-    const int tid = threadIdx.x, n = 2 * A.h + 1;
-    const size_t le = blockIdx.x, e = first + le;
-    const int64_t c = A.center[e];
-    int32_t rv = (c < -(int64_t)A.N || c > (int64_t)A.N - 1) ? -2 : 0;
-    if (pl && (pl[le].flags & ASX_POOL_INVALID)) rv = -4;
-    if (!rv && tid < n) {
-        const double *p = part + le * nb * ASX_CURVE_N + tid;
-        double s = p[0];
-        for (unsigned b = 1; b < nb; b++) s += p[(size_t)b * ASX_CURVE_N];
-        yv[tid] = s;
-    }
-    __syncthreads();
-    curve_write(A, e, rv, yv, tid);
-}
-
-// the coefficient curve: virtual pair v = e (2h + 1) + j is entry e at index (i0 + j) mod 2N -- the segment the peak search would have
-// left for that lag (make_seg) and the entry's tracks as a listed input record, so that the direct Pearson kernels run on them as
-// they run on a pool group
-__global__ __launch_bounds__(ASX_THREADS) void k_curve_segs(AsxCurve A, size_t first, int count, AsxSeg *__restrict__ seg,
-                                                             AsxPoolPair *__restrict__ out)
-{
-    const int lv = (int)(blockIdx.x * ASX_THREADS + threadIdx.x);
-    if (lv >= count) return;
-    const size_t v = first + (size_t)lv, n = (size_t)(2 * A.h + 1), e = v / n;
-    AsxPoolPair rec;
-    AsxSeg s;
-    if (curve_locate(A, e, rec.src_off, rec.smp_off) == 0)
-        s = make_seg((curve_first(A.center[e], A.N, A.h) + (uint32_t)(v % n)) % (2u * A.N), A.N);
+    asx_f4v yq = { 0.0f, 0.0f, 0.0f, 0.0f };
+    if (t4 + 3u < cnt) yq = *reinterpret_cast<const asx_f4u *>(y + n0 + t4);
     else {
-        s.lag = 0; s.src_off = s.smp_off = s.len = s.peak = s.flags = 0u;
-        rec.src_off = rec.smp_off = 0u;
+        if (t4 < cnt) yq.x = y[n0 + t4];
+        if (t4 + 1u < cnt) yq.y = y[n0 + t4 + 1u];
+        if (t4 + 2u < cnt) yq.z = y[n0 + t4 + 2u];
     }
-    rec.sx = rec.sy = rec.flags = rec.pad = 0u;
-    seg[lv] = s;
-    out[lv] = rec;
+    return yq;
 }
-
-// ---------------------------------------------------------------------------
-// The lag track (asx_xcorr_track_f32_dev, asx_xcorr_pool_track_f32_dev): the curve's sum kept apart per time segment,
-//     r_s[d] = sum_{b_s <= n < b_{s+1}} source[(n + p + d) mod 2N] * sample[n],   b_s = floor(s N / S),   d = -h .. h,
-// over a lag range wide enough to hold a drifting peak, and behind it each segment's peak and the weighted line through the peaks.
-// ---------------------------------------------------------------------------
-// the first frame of segment s
-__device__ __forceinline__ uint64_t track_bound(uint32_t N, int S, int s) { return (uint64_t)s * (uint64_t)N / (uint64_t)S; }
-// the ret of entry e: k_curve_dots' rule (pl: the pool form's records, indexed by the entry's place in the slice, or null)
-__device__ __forceinline__ int32_t track_ret(const AsxTrack &A, size_t e, size_t le, const AsxPoolPair *pl)
+// the stretch: xs[t] = x[(g0 + t) mod L] for t < need, zero behind, up to the LDS length LEN; 16-byte loads where the four neither
+// leave `need` nor straddle the wrap.  The thread stores xs[t4 + k ASX_CURVE_SWEEP ..+ 3]; the caller's barrier follows.
+template <int LEN>
+__device__ __forceinline__ void sweep_fill(float *xs, const float *x, uint32_t L, uint32_t g0, uint32_t need, uint32_t t4)
 {
-    const int64_t c = A.center[e];
-    if (pl && (pl[le].flags & ASX_POOL_INVALID)) return -4;
-    return (c < -(int64_t)A.N || c > (int64_t)A.N - 1) ? -2 : 0;
-}
-
-// grid (blocks per segment and tile, segments * tiles, entries of the slice): k_curve_dots' sweep restricted to segment s =
-// blockIdx.y / tiles and to the lags d = -h + ASX_CURVE_N tile .. of tile = blockIdx.y % tiles, at most ASX_CURVE_N of them (the last
-// tile may be short).  Block x takes the segment's frames [b_s + x chunk, b_s + (x + 1) chunk); a segment starts at any frame, so the
-// sample is read with 4-byte aligned loads of four.  The same order as k_curve_dots: a thread's samples ascending, the lanes of a
-// wave, the waves, and, with more than one block, the blocks in order (k_track_sum, from `part`); one block writes its values to
-// A.r itself.  An entry that is not valid reads and writes nothing: k_track_fit fills in all of its outputs.
-template <class Where>
-__global__ __launch_bounds__(ASX_THREADS) void k_track_dots(const float *__restrict__ src, const float *__restrict__ smp, Where at,
-                                                             AsxTrack A, size_t first, int tiles, double *__restrict__ part)
-{
-    constexpr bool listed = std::is_same<Where, AsxAtList>::value;
-    __shared__ __attribute__((aligned(16))) float xs[ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX];
-    __shared__ double red[ASX_THREADS / 64][ASX_CURVE_N];
-    const int tid = threadIdx.x, h = A.h, n = 2 * h + 1;
-    const size_t le = blockIdx.z, e = first + le;
-    const size_t rec = listed ? le : e / (size_t)A.entries;
-    const uint32_t N = A.N, L = 2u * N;
-    const int64_t c = A.center[e];
-    bool valid = !(c < -(int64_t)N || c > (int64_t)N - 1);
-    if constexpr (listed) {
-        if (at.pl[rec].flags & ASX_POOL_INVALID) valid = false;
+    static_assert(LEN % 4 == 0, "the stretch is stored in fours");
+    auto wrapped = [&](uint32_t i) { if (i >= L) { i -= L; if (i >= L) i %= L; } return i; };
+    for (uint32_t t = t4; t < (uint32_t)LEN; t += (uint32_t)ASX_CURVE_SWEEP) {
+        asx_f4v v = { 0.0f, 0.0f, 0.0f, 0.0f };
+        if (t < need) {
+            const uint32_t g = wrapped(g0 + t);
+            if (t + 3u < need && g + 3u < L) v = *reinterpret_cast<const asx_f4u *>(x + g);
+            else {
+                v.x = x[g];
+                if (t + 1u < need) v.y = x[wrapped(g0 + t + 1u)];
+                if (t + 2u < need) v.z = x[wrapped(g0 + t + 2u)];
+                if (t + 3u < need) v.w = x[wrapped(g0 + t + 3u)];
+            }
+        }
+        *reinterpret_cast<asx_f4v *>(xs + t) = v;
     }
-    if (!valid) return; // (block-uniform: nobody is left at a barrier)
-    const int sg = (int)blockIdx.y / tiles, tile = (int)blockIdx.y - sg * tiles;
-    const int d0 = tile * ASX_CURVE_N, nt = n - d0 < ASX_CURVE_N ? n - d0 : ASX_CURVE_N; // the tile's first value and how many
-    const uint32_t i0 = (curve_first(c, N, h) + (uint32_t)d0 % L) % L;
-    const float *x = src + at.src_off(rec);
-    const float *y = smp + at.smp_off(rec);
-    const uint64_t b0 = track_bound(N, A.S, sg), b1 = track_bound(N, A.S, sg + 1);
-    const uint32_t chunk = (((uint32_t)(b1 - b0) + gridDim.x - 1) / gridDim.x + 3u) & ~3u;
-    const uint64_t lo = b0 + (uint64_t)blockIdx.x * chunk;
-    const uint64_t hi = lo + chunk < b1 ? lo + chunk : b1;
-    double acc[ASX_CURVE_N];
+}
+// the sweeps of a block at a constant lag: acc[j] = sum over the frames n of [lo, hi) of x[(n + i0 + j) mod L] y[n] for j < nt, nt <=
+// ASX_CURVE_N (the sums past nt hold what nobody reads).  A thread forms the nt products of each of its four samples from a window
+// of 3 + nt values.  xs: ASX_CURVE_SWEEP + 2 ASX_NEAR_MAX floats of LDS; every argument but tid is block-uniform (two barriers a sweep).
+__device__ __forceinline__ void sweep_dots(float *xs, const float *x, const float *y, uint32_t L, uint32_t i0, uint64_t lo, uint64_t hi,
+                                           int nt, int tid, double (&acc)[ASX_CURVE_N])
+{
 #pragma unroll
     for (int j = 0; j < ASX_CURVE_N; j++) acc[j] = 0.0;
     for (uint64_t n0 = lo; n0 < hi; n0 += ASX_CURVE_SWEEP) {
         const uint32_t cnt = hi - n0 < (uint64_t)ASX_CURVE_SWEEP ? (uint32_t)(hi - n0) : (uint32_t)ASX_CURVE_SWEEP;
-        // the thread's four samples; past the block's end: zeros, which meet zeros below
         const uint32_t t4 = 4u * (uint32_t)tid;
-        asx_f4v yq = { 0.0f, 0.0f, 0.0f, 0.0f };
-        if (t4 + 3u < cnt) yq = *reinterpret_cast<const asx_f4u *>(y + n0 + t4);
-        else {
-            if (t4 < cnt) yq.x = y[n0 + t4];
-            if (t4 + 1u < cnt) yq.y = y[n0 + t4 + 1u];
-            if (t4 + 2u < cnt) yq.z = y[n0 + t4 + 2u];
-        }
+        const asx_f4v yq = sweep_samples(y, n0, t4, cnt);
         // xs[t] = source[(n0 + i0 + t) mod 2N] for t < cnt + nt - 1, zero behind
-        const uint32_t g0 = (uint32_t)((n0 + i0) % L), need = cnt + (uint32_t)nt - 1u;
-        auto wrapped = [&](uint32_t i) { if (i >= L) { i -= L; if (i >= L) i %= L; } return i; };
-        for (uint32_t t = t4; t < (uint32_t)(ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX); t += (uint32_t)ASX_CURVE_SWEEP) {
-            asx_f4v v = { 0.0f, 0.0f, 0.0f, 0.0f };
-            if (t < need) {
-                const uint32_t g = wrapped(g0 + t);
-                if (t + 3u < need && g + 3u < L) v = *reinterpret_cast<const asx_f4u *>(x + g);
-                else {
-                    v.x = x[g];
-                    if (t + 1u < need) v.y = x[wrapped(g0 + t + 1u)];
-                    if (t + 2u < need) v.z = x[wrapped(g0 + t + 2u)];
-                    if (t + 3u < need) v.w = x[wrapped(g0 + t + 3u)];
-                }
-            }
-            *reinterpret_cast<asx_f4v *>(xs + t) = v;
-        }
+        sweep_fill<ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX>(xs, x, L, (uint32_t)((n0 + i0) % L), cnt + (uint32_t)nt - 1u, t4);
         __syncthreads();
         double w[4 + 2 * ASX_NEAR_MAX];
 #pragma unroll
@@ -2022,6 +1860,11 @@ __global__ __launch_bounds__(ASX_THREADS) void k_track_dots(const float *__restr
         }
         __syncthreads();
     }
+}
+// the block's sums from its threads': the lanes of each wave into red[wave][j] (the caller's barrier follows), then the four waves
+template <int REC>
+__device__ __forceinline__ void sweep_wave_sums(const double (&acc)[ASX_CURVE_N], int nt, int tid, double (&red)[ASX_THREADS / 64][REC])
+{
 #pragma unroll
     for (int j = 0; j < ASX_CURVE_N; j++) {
         if (j < nt) {
@@ -2029,9 +1872,136 @@ __global__ __launch_bounds__(ASX_THREADS) void k_track_dots(const float *__restr
             if ((tid & 63) == 0) red[tid >> 6][j] = s;
         }
     }
+}
+template <int REC> __device__ __forceinline__ double sweep_block_sum(const double (&red)[ASX_THREADS / 64][REC], int j)
+{
+    static_assert(ASX_THREADS / 64 == 4, "the tree below adds four waves");
+    return (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+}
+// an entry's nb partial sums p[0], p[stride], ... in block order
+__device__ __forceinline__ double sweep_blocks_sum(const double *p, unsigned nb, int stride)
+{
+    double s = p[0];
+    for (unsigned b = 1; b < nb; b++) s += p[(size_t)b * stride];
+    return s;
+}
+
+// grid (blocks per entry, entries of the slice), entry e = first + blockIdx.y: the sweep over all 2h + 1 lags.  Block x takes samples
+// [x chunk, (x + 1) chunk); with more than one block per entry k_curve_sum adds the partial sums, with one the block writes the
+// results itself.  Where: AsxAtPitch, indexed by the entry's pair, or AsxAtList, indexed by the entry's place in the slice
+// (k_curve_resolve's records).  An entry that is not valid reads nothing.
+template <class Where>
+__global__ __launch_bounds__(ASX_THREADS) void k_curve_dots(const float *__restrict__ src, const float *__restrict__ smp, Where at,
+                                                             AsxCurve A, size_t first, double *__restrict__ part)
+{
+    constexpr bool listed = std::is_same<Where, AsxAtList>::value;
+    __shared__ __attribute__((aligned(16))) float xs[ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX];
+    __shared__ double red[ASX_THREADS / 64][ASX_CURVE_N];
+    __shared__ double yv[ASX_CURVE_N];
+    const int tid = threadIdx.x, h = A.E.h, n = 2 * h + 1;
+    const size_t le = blockIdx.y, e = first + le;
+    const size_t rec = listed ? le : e / (size_t)A.E.entries;
+    const uint32_t N = A.E.N;
+    if (const int32_t rv = entry_ret(A.E, e, le, at.list())) { // (block-uniform: nobody is left at a barrier)
+        if (gridDim.x == 1) curve_write(A, e, rv, yv, tid);
+        return;
+    }
+    const float *x = src + at.src_off(rec);
+    const float *y = smp + at.smp_off(rec);
+    const uint32_t chunk = ((N + gridDim.x - 1) / gridDim.x + 3u) & ~3u;
+    const uint64_t lo = (uint64_t)blockIdx.x * chunk;
+    const uint64_t hi = lo + chunk < (uint64_t)N ? lo + chunk : (uint64_t)N;
+    double acc[ASX_CURVE_N];
+    sweep_dots(xs, x, y, 2u * N, curve_first(A.E.center[e], N, h), lo, hi, n, tid, acc);
+    sweep_wave_sums(acc, n, tid, red);
+    __syncthreads();
+    if (tid < n) {
+        const double v = sweep_block_sum(red, tid);
+        if (gridDim.x == 1) yv[tid] = v;
+        else part[(le * gridDim.x + blockIdx.x) * ASX_CURVE_N + tid] = v;
+    }
+    if (gridDim.x == 1) {
+        __syncthreads();
+        curve_write(A, e, 0, yv, tid);
+    }
+}
+
+// grid (entries of the slice), one wave: an entry's nb partial sums in block order, then its results; pl: the pool form's records
+__global__ __launch_bounds__(64) void k_curve_sum(AsxCurve A, size_t first, unsigned nb, const double *__restrict__ part,
+                                                   const AsxPoolPair *__restrict__ pl)
+{
+    __shared__ double yv[ASX_CURVE_N];
+    const int tid = threadIdx.x, n = 2 * A.E.h + 1;
+    const size_t le = blockIdx.x, e = first + le;
+    const int32_t rv = entry_ret(A.E, e, le, pl);
+    if (!rv && tid < n) yv[tid] = sweep_blocks_sum(part + le * nb * ASX_CURVE_N + tid, nb, ASX_CURVE_N);
+    __syncthreads();
+    curve_write(A, e, rv, yv, tid);
+}
+
+// the coefficient curve: virtual pair v = e (2h + 1) + j is entry e at index (i0 + j) mod 2N -- the segment the peak search would have
+// left for that lag (make_seg) and the entry's tracks as a listed input record, so that the direct Pearson kernels run on them as
+// they run on a pool group
+__global__ __launch_bounds__(ASX_THREADS) void k_curve_segs(AsxLagEntries E, size_t first, int count, AsxSeg *__restrict__ seg,
+                                                             AsxPoolPair *__restrict__ out)
+{
+    const int lv = (int)(blockIdx.x * ASX_THREADS + threadIdx.x);
+    if (lv >= count) return;
+    const size_t v = first + (size_t)lv, n = (size_t)(2 * E.h + 1), e = v / n;
+    AsxPoolPair rec;
+    AsxSeg s;
+    if (curve_locate(E, e, rec.src_off, rec.smp_off) == 0)
+        s = make_seg((curve_first(E.center[e], E.N, E.h) + (uint32_t)(v % n)) % (2u * E.N), E.N);
+    else {
+        s.lag = 0; s.src_off = s.smp_off = s.len = s.peak = s.flags = 0u;
+        rec.src_off = rec.smp_off = 0u;
+    }
+    rec.sx = rec.sy = rec.flags = rec.pad = 0u;
+    seg[lv] = s;
+    out[lv] = rec;
+}
+
+// ---------------------------------------------------------------------------
+// The lag track (asx_xcorr_track_f32_dev, asx_xcorr_pool_track_f32_dev): the curve's sum kept apart per time segment,
+//     r_s[d] = sum_{b_s <= n < b_{s+1}} source[(n + p + d) mod 2N] * sample[n],   b_s = floor(s N / S),   d = -h .. h,
+// over a lag range wide enough to hold a drifting peak, and behind it each segment's peak and the weighted line through the peaks.
+// ---------------------------------------------------------------------------
+// the first frame of segment s
+__device__ __forceinline__ uint64_t track_bound(uint32_t N, int S, int s) { return (uint64_t)s * (uint64_t)N / (uint64_t)S; }
+
+// grid (blocks per segment and tile, segments * tiles, entries of the slice): the sweep restricted to segment s = blockIdx.y / tiles
+// and to the lags d = -h + ASX_CURVE_N tile .. of tile = blockIdx.y % tiles, at most ASX_CURVE_N of them (the last tile may be
+// short).  Block x takes the segment's frames [b_s + x chunk, b_s + (x + 1) chunk); a segment starts at any frame, which is why the
+// sweep reads the sample with 4-byte aligned loads of four.  With more than one block k_track_sum adds the partial sums; one block
+// writes its values to A.r itself.  An entry that is not valid reads and writes nothing: k_track_fit fills in all of its outputs.
+template <class Where>
+__global__ __launch_bounds__(ASX_THREADS) void k_track_dots(const float *__restrict__ src, const float *__restrict__ smp, Where at,
+                                                             AsxTrack A, size_t first, int tiles, double *__restrict__ part)
+{
+    constexpr bool listed = std::is_same<Where, AsxAtList>::value;
+    __shared__ __attribute__((aligned(16))) float xs[ASX_CURVE_SWEEP + 2 * ASX_NEAR_MAX];
+    __shared__ double red[ASX_THREADS / 64][ASX_CURVE_N];
+    const int tid = threadIdx.x, h = A.E.h, n = 2 * h + 1;
+    const size_t le = blockIdx.z, e = first + le;
+    const size_t rec = listed ? le : e / (size_t)A.E.entries;
+    const uint32_t N = A.E.N, L = 2u * N;
+    if (entry_ret(A.E, e, le, at.list())) return; // (block-uniform: nobody is left at a barrier)
+    const int64_t c = A.E.center[e];
+    const int sg = (int)blockIdx.y / tiles, tile = (int)blockIdx.y - sg * tiles;
+    const int d0 = tile * ASX_CURVE_N, nt = n - d0 < ASX_CURVE_N ? n - d0 : ASX_CURVE_N; // the tile's first value and how many
+    const uint32_t i0 = (curve_first(c, N, h) + (uint32_t)d0 % L) % L;
+    const float *x = src + at.src_off(rec);
+    const float *y = smp + at.smp_off(rec);
+    const uint64_t b0 = track_bound(N, A.S, sg), b1 = track_bound(N, A.S, sg + 1);
+    const uint32_t chunk = (((uint32_t)(b1 - b0) + gridDim.x - 1) / gridDim.x + 3u) & ~3u;
+    const uint64_t lo = b0 + (uint64_t)blockIdx.x * chunk;
+    const uint64_t hi = lo + chunk < b1 ? lo + chunk : b1;
+    double acc[ASX_CURVE_N];
+    sweep_dots(xs, x, y, L, i0, lo, hi, nt, tid, acc);
+    sweep_wave_sums(acc, nt, tid, red);
     __syncthreads();
     if (tid < nt) {
-        const double v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+        const double v = sweep_block_sum(red, tid);
         if (gridDim.x == 1) A.r[(e * (size_t)A.S + (size_t)sg) * (size_t)n + (size_t)(d0 + tid)] = v;
         else part[((le * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * ASX_CURVE_N + tid] = v;
     }
@@ -2041,15 +2011,13 @@ __global__ __launch_bounds__(ASX_THREADS) void k_track_dots(const float *__restr
 __global__ __launch_bounds__(64) void k_track_sum(AsxTrack A, size_t first, int tiles, unsigned nb, const double *__restrict__ part,
                                                    const AsxPoolPair *__restrict__ pl)
 {
-    const int tid = threadIdx.x, n = 2 * A.h + 1;
+    const int tid = threadIdx.x, n = 2 * A.E.h + 1;
     const size_t le = blockIdx.y, e = first + le;
-    if (track_ret(A, e, le, pl)) return;
+    if (entry_ret(A.E, e, le, pl)) return;
     const int sg = (int)blockIdx.x / tiles, d0 = ((int)blockIdx.x - sg * tiles) * ASX_CURVE_N;
     if (tid >= ASX_CURVE_N || d0 + tid >= n) return;
-    const double *p = part + (le * gridDim.x + blockIdx.x) * nb * ASX_CURVE_N + tid;
-    double s = p[0];
-    for (unsigned b = 1; b < nb; b++) s += p[(size_t)b * ASX_CURVE_N];
-    A.r[(e * (size_t)A.S + (size_t)sg) * (size_t)n + (size_t)(d0 + tid)] = s;
+    A.r[(e * (size_t)A.S + (size_t)sg) * (size_t)n + (size_t)(d0 + tid)] =
+        sweep_blocks_sum(part + (le * gridDim.x + blockIdx.x) * nb * ASX_CURVE_N + tid, nb, ASX_CURVE_N);
 }
 
 // grid (entries of the slice), one wave, behind the entry's finished r: lane s takes segment s -- its peak m_s (the largest |r_s[d]|
@@ -2059,9 +2027,9 @@ __global__ __launch_bounds__(64) void k_track_fit(AsxTrack A, size_t first, cons
 {
     __shared__ double ts[ASX_TRACK_SEG_MAX], offs[ASX_TRACK_SEG_MAX], ws[ASX_TRACK_SEG_MAX];
     __shared__ int use[ASX_TRACK_SEG_MAX];
-    const int tid = threadIdx.x, h = A.h, n = 2 * h + 1, S = A.S;
+    const int tid = threadIdx.x, h = A.E.h, n = 2 * h + 1, S = A.S;
     const size_t le = blockIdx.x, e = first + le;
-    const int32_t rv = track_ret(A, e, le, pl);
+    const int32_t rv = entry_ret(A.E, e, le, pl);
     if (rv) { // (block-uniform)
         double *r = A.r + e * (size_t)S * (size_t)n;
         for (int i = tid; i < S * n; i += 64) r[i] = (double)NAN;
@@ -2089,7 +2057,7 @@ __global__ __launch_bounds__(64) void k_track_fit(AsxTrack A, size_t first, cons
             A.seg[(e * (size_t)S + (size_t)tid) * 2] = off;
             A.seg[(e * (size_t)S + (size_t)tid) * 2 + 1] = w;
         }
-        const uint64_t b0 = track_bound(A.N, S, tid), b1 = track_bound(A.N, S, tid + 1);
+        const uint64_t b0 = track_bound(A.E.N, S, tid), b1 = track_bound(A.E.N, S, tid + 1);
         ts[tid] = (double)(b0 + b1 - 1u) * 0.5;
         offs[tid] = off;
         ws[tid] = w;
@@ -2150,28 +2118,24 @@ __device__ __forceinline__ double warp_shift(double a, double b, uint32_t n)
 {
     return floor(__dadd_rn(__dadd_rn(b, __dmul_rn(a, (double)n)), 0.5));
 }
-// the ret of entry e when it is not computed: -4 for a row outside its pool (pl: the pool form's records, indexed by the entry's
-// place in the slice, or null), over -2 for a centre outside [-N, N-1], over -5 for a line that is not valid -- a or b not finite
-// (the comparisons fail on NaN), |a| > ASX_WARP_DRIFT_MAX or |b| > N; 0 for an entry to compute
+// the ret of entry e when it is not computed: entry_ret's, over -5 for a line that is not valid -- a or b not finite (the comparisons
+// fail on NaN), |a| > ASX_WARP_DRIFT_MAX or |b| > N; 0 for an entry to compute
 __device__ __forceinline__ int32_t warp_ret(const AsxWarp &A, size_t e, size_t le, const AsxPoolPair *pl)
 {
-    if (pl && (pl[le].flags & ASX_POOL_INVALID)) return -4;
-    const int64_t c = A.center[e];
-    if (c < -(int64_t)A.N || c > (int64_t)A.N - 1) return -2;
+    if (const int32_t rv = entry_ret(A.E, e, le, pl)) return rv;
     const double a = A.line[e * A.line_stride], b = A.line[e * A.line_stride + 1];
-    return (fabs(a) <= ASX_WARP_DRIFT_MAX && fabs(b) <= (double)A.N) ? 0 : -5;
+    return (fabs(a) <= ASX_WARP_DRIFT_MAX && fabs(b) <= (double)A.E.N) ? 0 : -5;
 }
 
-// grid (blocks per entry, entries of the slice), entry e = first + blockIdx.y: k_curve_dots' sweep along the line.  k is monotone in
+// grid (blocks per entry, entries of the slice), entry e = first + blockIdx.y: the sweep along the line.  k is monotone in
 // n, so a sweep's shifts lie between those of its two ends; the sweep's stretch of the source starts at (n0 + p - h + k_min) mod 2N,
 // is up to 2h + ASX_WARP_STEPS longer than the sweep and goes through LDS once.  A thread reads the window of its four frames at the
 // offset k_n - k_min: one window of 4 + 2h values when the four share k, and a second one for the frames behind the step otherwise
 // (four consecutive frames of a valid line hold at most one step); a frame meets the window of its own k, the others a zero.  In
 // the same pass the thread keeps the Pearson statistics of its frames n with 0 <= n + c + k_n < 2N, relative to the first such pair
-// it meets, as k_pearson_partial does; their source values are the window's d = 0 column.  float64 throughout; the order is fixed:
-// a thread's frames ascending, the lanes of a wave, the waves, and the blocks in order (k_warp_final, from `part`): an entry's bits
-// depend on neither the batch nor its place in it.  With one block per entry the sums go to A.r and the record to part[le * 6].
-// An entry that is not valid reads and writes nothing: k_warp_final fills in all of its outputs.
+// it meets, as k_pearson_partial does; their source values are the window's d = 0 column.  The sweep's order, with the blocks added
+// by k_warp_final; with one block per entry the sums go to A.r and the record to part[le * 6].  An entry that is not valid reads and
+// writes nothing: k_warp_final fills in all of its outputs.
 template <class Where>
 __global__ __launch_bounds__(ASX_THREADS, 4) void k_warp_dots(const float *__restrict__ src, const float *__restrict__ smp, Where at,
                                                             AsxWarp A, size_t first, double *__restrict__ part)
@@ -2179,14 +2143,12 @@ __global__ __launch_bounds__(ASX_THREADS, 4) void k_warp_dots(const float *__res
     constexpr bool listed = std::is_same<Where, AsxAtList>::value;
     __shared__ __attribute__((aligned(16))) float xs[ASX_WARP_XS];
     __shared__ double red[ASX_THREADS / 64][ASX_WARP_REC];
-    const int tid = threadIdx.x, h = A.h, n = 2 * h + 1;
+    const int tid = threadIdx.x, h = A.E.h, n = 2 * h + 1;
     const size_t le = blockIdx.y, e = first + le;
-    const size_t rec = listed ? le : e / (size_t)A.entries;
-    const uint32_t N = A.N, L = 2u * N;
-    const AsxPoolPair *pl = nullptr;
-    if constexpr (listed) pl = at.pl;
-    if (warp_ret(A, e, le, pl)) return; // (block-uniform: nobody is left at a barrier)
-    const int64_t c = A.center[e];
+    const size_t rec = listed ? le : e / (size_t)A.E.entries;
+    const uint32_t N = A.E.N, L = 2u * N;
+    if (warp_ret(A, e, le, at.list())) return; // (block-uniform: nobody is left at a barrier)
+    const int64_t c = A.E.center[e];
     const double la = A.line[e * A.line_stride], lb = A.line[e * A.line_stride + 1];
     const uint32_t i0 = curve_first(c, N, h);
     const float *x = src + at.src_off(rec);
@@ -2211,15 +2173,8 @@ __global__ __launch_bounds__(ASX_THREADS, 4) void k_warp_dots(const float *__res
     };
     for (uint32_t n0 = lo; n0 < hi; n0 += ASX_CURVE_SWEEP) {
         const uint32_t cnt = hi - n0 < (uint32_t)ASX_CURVE_SWEEP ? hi - n0 : (uint32_t)ASX_CURVE_SWEEP;
-        // the thread's four samples; past the block's end: zeros, which meet zeros below
         const uint32_t t4 = 4u * (uint32_t)tid;
-        asx_f4v yq = { 0.0f, 0.0f, 0.0f, 0.0f };
-        if (t4 + 3u < cnt) yq = *reinterpret_cast<const asx_f4u *>(y + (size_t)n0 + t4);
-        else {
-            if (t4 < cnt) yq.x = y[(size_t)n0 + t4];
-            if (t4 + 1u < cnt) yq.y = y[(size_t)n0 + t4 + 1u];
-            if (t4 + 2u < cnt) yq.z = y[(size_t)n0 + t4 + 2u];
-        }
+        const asx_f4v yq = sweep_samples(y, n0, t4, cnt);
         // the shifts of the sweep's ends and of the thread's frames (a frame past the sweep's end takes the last one's: its offset
         // stays inside the stretch)
         const uint32_t last = n0 + cnt - 1u;
@@ -2248,21 +2203,7 @@ __global__ __launch_bounds__(ASX_THREADS, 4) void k_warp_dots(const float *__res
         if (gi >= L) gi -= L;
         const uint32_t g0 = (uint32_t)gi;
         const uint32_t need = cnt + 2u * (uint32_t)h + (uint32_t)(int)((ka < kb ? kb : ka) - kmin);
-        auto wrapped = [&](uint32_t i) { if (i >= L) { i -= L; if (i >= L) i %= L; } return i; };
-        for (uint32_t t = t4; t < (uint32_t)ASX_WARP_XS; t += (uint32_t)ASX_CURVE_SWEEP) {
-            asx_f4v v = { 0.0f, 0.0f, 0.0f, 0.0f };
-            if (t < need) {
-                const uint32_t g = wrapped(g0 + t);
-                if (t + 3u < need && g + 3u < L) v = *reinterpret_cast<const asx_f4u *>(x + g);
-                else {
-                    v.x = x[g];
-                    if (t + 1u < need) v.y = x[wrapped(g0 + t + 1u)];
-                    if (t + 2u < need) v.z = x[wrapped(g0 + t + 2u)];
-                    if (t + 3u < need) v.w = x[wrapped(g0 + t + 3u)];
-                }
-            }
-            *reinterpret_cast<asx_f4v *>(xs + t) = v;
-        }
+        sweep_fill<ASX_WARP_XS>(xs, x, L, g0, need, t4);
         __syncthreads();
         // the frames of `take` against the window at offset o (any float: 4-byte aligned reads), one window value at a time: value i
         // meets frame q at the sum j = i - q, so every sum takes its frames in ascending order
@@ -2298,13 +2239,7 @@ __global__ __launch_bounds__(ASX_THREADS, 4) void k_warp_dots(const float *__res
         if (same != 15u) window(o3, 15u & ~same);
         __syncthreads();
     }
-#pragma unroll
-    for (int j = 0; j < ASX_CURVE_N; j++) {
-        if (j < n) {
-            const double s = wave_sum(acc[j]);
-            if ((tid & 63) == 0) red[tid >> 6][j] = s;
-        }
-    }
+    sweep_wave_sums(acc, n, tid, red);
     PStat v;
     v.n = (double)seen;
     v.mx = v.my = v.mxx = v.myy = v.cxy = 0.0;
@@ -2323,7 +2258,7 @@ __global__ __launch_bounds__(ASX_THREADS, 4) void k_warp_dots(const float *__res
     __syncthreads();
     double *out = part + (le * gridDim.x + blockIdx.x) * ASX_WARP_REC;
     if (tid < n) {
-        const double s = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+        const double s = sweep_block_sum(red, tid);
         if (gridDim.x == 1) A.r[e * (size_t)n + (size_t)tid] = s;
         else out[tid] = s;
     }
@@ -2346,7 +2281,7 @@ __global__ __launch_bounds__(64) void k_warp_final(AsxWarp A, size_t first, unsi
                                                     const AsxPoolPair *__restrict__ pl)
 {
     __shared__ double yv[ASX_CURVE_N];
-    const int tid = threadIdx.x, n = 2 * A.h + 1;
+    const int tid = threadIdx.x, h = A.E.h, n = 2 * h + 1;
     const size_t le = blockIdx.x, e = first + le;
     const int32_t rv = warp_ret(A, e, le, pl);
     if (rv) { // (block-uniform)
@@ -2363,9 +2298,7 @@ __global__ __launch_bounds__(64) void k_warp_final(AsxWarp A, size_t first, unsi
         double s;
         if (nb == 1u) s = A.r[e * (size_t)n + (size_t)tid];
         else {
-            const double *p = part + le * nb * ASX_WARP_REC + tid;
-            s = p[0];
-            for (unsigned b = 1; b < nb; b++) s += p[(size_t)b * ASX_WARP_REC];
+            s = sweep_blocks_sum(part + le * nb * ASX_WARP_REC + tid, nb, ASX_WARP_REC);
             A.r[e * (size_t)n + (size_t)tid] = s;
         }
         yv[tid] = s;
@@ -2383,7 +2316,7 @@ __global__ __launch_bounds__(64) void k_warp_final(AsxWarp A, size_t first, unsi
     if (tid == 0) {
         // src/cross_correlation.c:115; no lined-up frame or a constant side gives 0/0 = NaN like the reference
         const double cf = v.cxy / sqrt(v.mxx * v.myy);
-        A.frac[e] = asx_parabola_frac(yv[A.h - 1], yv[A.h], yv[A.h + 1]);
+        A.frac[e] = asx_parabola_frac(yv[h - 1], yv[h], yv[h + 1]);
         A.coef[e] = cf;
         if (A.len) A.len[e] = (int64_t)v.n;
         A.ret[e] = (cf != cf) ? -1 : 0;
@@ -2766,23 +2699,23 @@ unsigned asx_curve_blocks(uint32_t N)
 void asx_launch_curve_r(const float *src, const float *smp, const AsxCurve &A, size_t first, int count, AsxPoolPair *pl, double *part,
                         hipStream_t s)
 {
-    const unsigned nb = asx_curve_blocks(A.N);
+    const unsigned nb = asx_curve_blocks(A.E.N);
     const dim3 grid(nb, (unsigned)count), block(ASX_THREADS);
-    if (A.nsrc) {
-        hipLaunchKernelGGL(k_curve_resolve, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), block, 0, s, A, first, count, pl);
+    if (A.E.nsrc) {
+        hipLaunchKernelGGL(k_curve_resolve, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), block, 0, s, A.E, first, count, pl);
         hipLaunchKernelGGL(k_curve_dots<AsxAtList>, grid, block, 0, s, src, smp, AsxAtList{ pl }, A, first, part);
     } else {
-        hipLaunchKernelGGL(k_curve_dots<AsxAtPitch>, grid, block, 0, s, src, smp, AsxAtPitch{ (size_t)A.src_stride, (size_t)A.smp_stride },
+        hipLaunchKernelGGL(k_curve_dots<AsxAtPitch>, grid, block, 0, s, src, smp, AsxAtPitch{ (size_t)A.E.src_stride, (size_t)A.E.smp_stride },
                            A, first, part);
     }
     if (nb > 1u)
         hipLaunchKernelGGL(k_curve_sum, dim3((unsigned)count), dim3(64), 0, s, A, first, nb, (const double *)part,
-                           (const AsxPoolPair *)(A.nsrc ? pl : nullptr));
+                           (const AsxPoolPair *)(A.E.nsrc ? pl : nullptr));
 }
 
-void asx_launch_curve_segs(const AsxCurve &A, size_t first, int count, AsxSeg *seg, AsxPoolPair *pl, hipStream_t s)
+void asx_launch_curve_segs(const AsxLagEntries &E, size_t first, int count, AsxSeg *seg, AsxPoolPair *pl, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_curve_segs, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, A, first, count,
+    hipLaunchKernelGGL(k_curve_segs, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, E, first, count,
                        seg, pl);
 }
 
@@ -2796,16 +2729,15 @@ unsigned asx_track_blocks(uint32_t N, int segments, int half_width)
 void asx_launch_track(const float *src, const float *smp, const AsxTrack &A, size_t first, int count, AsxPoolPair *pl, double *part,
                       hipStream_t s)
 {
-    const int tiles = (2 * A.h + ASX_CURVE_N) / ASX_CURVE_N; // ceil((2h + 1) / ASX_CURVE_N)
-    const unsigned nb = asx_track_blocks(A.N, A.S, A.h);
+    const int tiles = (2 * A.E.h + ASX_CURVE_N) / ASX_CURVE_N; // ceil((2h + 1) / ASX_CURVE_N)
+    const unsigned nb = asx_track_blocks(A.E.N, A.S, A.E.h);
     const dim3 grid(nb, (unsigned)(A.S * tiles), (unsigned)count), block(ASX_THREADS);
-    const AsxPoolPair *list = A.nsrc ? pl : nullptr;
-    if (A.nsrc) {
-        const AsxCurve C{ A.center, nullptr, nullptr, nullptr, A.N, A.entries, A.h, A.rows, A.nsrc, A.nsmp, A.src_stride, A.smp_stride };
-        hipLaunchKernelGGL(k_curve_resolve, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), block, 0, s, C, first, count, pl);
+    const AsxPoolPair *list = A.E.nsrc ? pl : nullptr;
+    if (A.E.nsrc) {
+        hipLaunchKernelGGL(k_curve_resolve, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), block, 0, s, A.E, first, count, pl);
         hipLaunchKernelGGL(k_track_dots<AsxAtList>, grid, block, 0, s, src, smp, AsxAtList{ pl }, A, first, tiles, part);
     } else {
-        hipLaunchKernelGGL(k_track_dots<AsxAtPitch>, grid, block, 0, s, src, smp, AsxAtPitch{ (size_t)A.src_stride, (size_t)A.smp_stride },
+        hipLaunchKernelGGL(k_track_dots<AsxAtPitch>, grid, block, 0, s, src, smp, AsxAtPitch{ (size_t)A.E.src_stride, (size_t)A.E.smp_stride },
                            A, first, tiles, part);
     }
     if (nb > 1u)
@@ -2823,15 +2755,14 @@ unsigned asx_warp_blocks(uint32_t N)
 void asx_launch_warp(const float *src, const float *smp, const AsxWarp &A, size_t first, int count, AsxPoolPair *pl, double *part,
                      hipStream_t s)
 {
-    const unsigned nb = asx_warp_blocks(A.N);
+    const unsigned nb = asx_warp_blocks(A.E.N);
     const dim3 grid(nb, (unsigned)count), block(ASX_THREADS);
-    const AsxPoolPair *list = A.nsrc ? pl : nullptr;
-    if (A.nsrc) {
-        const AsxCurve C{ A.center, nullptr, nullptr, nullptr, A.N, A.entries, A.h, A.rows, A.nsrc, A.nsmp, A.src_stride, A.smp_stride };
-        hipLaunchKernelGGL(k_curve_resolve, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), block, 0, s, C, first, count, pl);
+    const AsxPoolPair *list = A.E.nsrc ? pl : nullptr;
+    if (A.E.nsrc) {
+        hipLaunchKernelGGL(k_curve_resolve, dim3(((unsigned)count + ASX_THREADS - 1) / ASX_THREADS), block, 0, s, A.E, first, count, pl);
         hipLaunchKernelGGL(k_warp_dots<AsxAtList>, grid, block, 0, s, src, smp, AsxAtList{ pl }, A, first, part);
     } else {
-        hipLaunchKernelGGL(k_warp_dots<AsxAtPitch>, grid, block, 0, s, src, smp, AsxAtPitch{ (size_t)A.src_stride, (size_t)A.smp_stride },
+        hipLaunchKernelGGL(k_warp_dots<AsxAtPitch>, grid, block, 0, s, src, smp, AsxAtPitch{ (size_t)A.E.src_stride, (size_t)A.E.smp_stride },
                            A, first, part);
     }
     hipLaunchKernelGGL(k_warp_final, dim3((unsigned)count), dim3(64), 0, s, A, first, nb, (const double *)part, list);

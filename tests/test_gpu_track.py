@@ -3,7 +3,8 @@
 r must be the float64 model's sum (tests/track_model.py: math.fsum over the exact products of a segment) at every lag of every segment
 within len_s * 2^-53 * sum |products| -- the first-order worst case of any float64 summation order; seg must be the header's rule
 applied to the call's own r, bit for bit; fit must be the model's line through the call's own seg within the model's first-order
-tolerances (track_model.fit_tolerances); a planted drift must come back within half a frame over the window.  Shapes: N = 1000 on a
+tolerances (track_model.fit_tolerances); a planted drift must come back within half a frame over the window; with S = 1 and h = 8
+r must be the curve call's r byte for byte (one sweep, the same blocks, the same order).  Shapes: N = 1000 on a
 packed plan (25 x 40), N = 999, which no block size divides, and N = 144 000, the smallest real-column length, where S = 1 with h = 8
 runs three blocks per segment and the sum kernel and everything else one block per (segment, tile).
 
@@ -161,6 +162,8 @@ def test_r_seg_and_fit_at_the_small_lengths(mod, n, segs):
                 assert np.isnan(fit).all() and set(used.tolist()) <= {0, 1}
             if h == 8:                                           # over s the sums add up to the curve call's r
                 cr = plan.xcorr_curve_f32(src, smp, cs, half_width=h, coef=False)[0]
+                if segs == 1:                                    # one segment, one tile: the curve call's sweep, block for block
+                    assert r[:, 0, :].tobytes() == cr.tobytes(), (n, np.argwhere(r[:, 0, :] != cr).tolist())
                 for k, c in enumerate(cs):
                     for j, idx in enumerate(track_model.indices(c, n, h)):
                         tol = model_rows(n, idx)[1][1][0]                 # S = 1: the curve call's own tolerance
@@ -185,6 +188,8 @@ def test_r_seg_and_fit_at_144000(mod, segs):
             assert counts[4] == counts[5] == segs, counts
             if h == 8:
                 cr = plan.xcorr_curve_f32(src, smp, cs, half_width=h, coef=False)[0]
+                if segs == 1:                                    # three blocks per entry in both calls, added in the same order
+                    assert r[:, 0, :].tobytes() == cr.tobytes(), np.argwhere(r[:, 0, :] != cr).tolist()
                 for k in (3, 5):
                     for j, idx in enumerate(track_model.indices(cs[k], n, h)):
                         tol = model_rows(n, idx)[1][1][0]
