@@ -32,11 +32,12 @@
  *   window was not a window inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.  (asx_xcorr_curve_f32_dev and
  *   asx_xcorr_pool_curve_f32_dev: an entry's centre was not a lag inside [-N, N-1]; NaN in all its values.  The same in
  *   asx_xcorr_track_f32_dev and asx_xcorr_pool_track_f32_dev, with used = 0.)
- *   ret = -3 (asx_xcorr_topk_f32_dev and asx_xcorr_pool_topk_f32_dev only): no lag is left for
+ *   ret = -3 (asx_xcorr_topk_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_phat_topk_f32_dev and
+ *   asx_xcorr_pool_phat_topk_f32_dev only): no lag is left for
  *   this entry of the pair (its window minus the zones around the earlier entries is empty);
  *   lag = 0 and coef = NaN.
- *   ret = -4 (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_pool_phat_f32_dev and
- *   asx_xcorr_pool_phat_sub_f32_dev only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
+ *   ret = -4 (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_pool_phat_f32_dev,
+ *   asx_xcorr_pool_phat_sub_f32_dev and asx_xcorr_pool_phat_topk_f32_dev only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
  *   form: in all k entries of the pair).  It takes precedence over -2 and -3.  (asx_xcorr_pool_curve_f32_dev: NaN in all
  *   the values of the pair's entries.  asx_xcorr_pool_track_f32_dev: the same, with used = 0.)
  *   ret = -5 (asx_xcorr_warp_f32_dev and asx_xcorr_pool_warp_f32_dev only): an entry's drift line is not valid; NaN in all its
@@ -352,8 +353,9 @@ int asx_xcorr_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_
  * allocates nothing after plan creation, but for the broadcast slot's first allocation under asx_xcorr_strided_f32_dev's rule.
  *   Weakness.  Bins that hold only rounding noise vote too: on band-limited material the empty part of the spectrum adds noise
  * to r_phat and lowers the peak.  asx_xcorr_phat_band_f32_dev, below, lets only a chosen range of bins vote, and
- * asx_xcorr_pool_phat_f32_dev takes listed pairs of two track pools.  Not offered with PHAT: top-k, the double ABI, streams, packed
- * plans. */
+ * asx_xcorr_pool_phat_f32_dev takes listed pairs of two track pools, and asx_xcorr_phat_topk_f32_dev returns the K strongest
+ * separated lags of r_phat.  Not offered with PHAT: the double ABI, streams, packed plans, and the neighbourhood of each entry of the
+ * top-k call. */
 int asx_xcorr_phat_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
                            const float *d_sample, size_t sample_stride,
                            const int64_t *d_windows, size_t window_stride, size_t batch,
@@ -414,6 +416,46 @@ int asx_xcorr_phat_sub_f32_dev(asx_plan *plan, const float *d_source, size_t sou
                                int64_t bin_lo, int64_t bin_hi, int half_width,
                                int64_t *d_lag, double *d_coef, double *d_peak,
                                double *d_frac, double *d_near, int32_t *d_ret, void *stream);
+
+/* Top-k GCC-PHAT: the K strongest separated lags per pair by the whitened curve, each with its coefficient and its peak height.  An
+ * echo, a chorus and a second loudspeaker are separate peaks of r_phat; on material whose raw correlation follows a shared hum, these
+ * runner-ups by phase alignment are the candidates a closure over several clips (asx_pool_closure_dev) needs.
+ *   Inputs.  Strides, broadcast (a stride of 0), the 16-byte layout rule, real-column plans only, per-pair window rows or the plan's
+ * window (d_windows == NULL), the band and its vote count V and the stream rule are those of asx_xcorr_phat_band_f32_dev.  The band
+ * is always given; the full band [0, N] is plain PHAT and runs the plain PHAT row kernels.  k and min_separation are those of
+ * asx_xcorr_topk_f32_dev.  Entry j (0-based) of pair i is at index i*k + j of d_lag, d_coef, d_peak and d_ret.  d_lag and d_peak
+ * may be NULL.
+ *   The rule.  A_1 is the pair's window.  A_j is A_1 minus every lag l with |l - lag_i| <= min_separation for an earlier entry
+ * i < j -- linear lag distance, so lags -N and N-1 are far apart.  Entry j is asx_xcorr_phat_f32_dev's peak rule over A_j in
+ * ascending index order, applied to the float32 values of r_phat that the device computes: the smallest index of A_j is the seed and
+ * competes with its SIGNED value, every other element with fabs and the strict '>'; among equal float32 values the smallest index
+ * wins.  This is the float32 argmax of each pass, exactly as that call states for its one pass: two candidates whose heights differ
+ * by less than its resolution may come back in either order.
+ *   Outputs per entry.  lag: the peak's lag after the reference's wrap.  coef: the reference's Pearson coefficient of the ORIGINAL
+ * samples at that lag, always in the direct form: under asx_plan_set_pearson(plan, 0) bit for bit what asx_xcorr_windowed_f32_dev
+ * returns for the row [lag, lag].  peak: |r_phat[lag]| / V.  ret: 0, or -1 for a NaN coefficient.  ret is never 1.
+ *   Special entries.  If A_j is empty, entry j and every later entry of the pair are (0, NaN, peak NaN, -3).  A row that is not a
+ * window gives (0, NaN, NaN, -2) in all k entries of its pair.  Every other pair is untouched, bit for bit.  A pair with a digitally
+ * silent track follows the rule as it stands: every pass finds an empty maximum and returns the seed of A_j with peak 0.
+ *   Relation to the other calls.  Entry 0 of every pair is bit for bit the (lag, coef, peak, ret) of asx_xcorr_phat_band_f32_dev on
+ * the same plan with the same band and window; k = 1 launches exactly that call.
+ *   What the call never does.  It lists nothing, takes no second look and never synchronises the host.  It runs the same whatever
+ * asx_plan_set_exact, _pearson, _prune and _qstore say, and leaves asx_plan_peak_overflows, asx_plan_peak_repairs,
+ * asx_plan_pearson_modes, asx_plan_prune_stats and asx_plan_qstore_stats unchanged.  It allocates nothing after plan creation (but
+ * for the broadcast slot's first allocation under asx_xcorr_strided_f32_dev's rule), asx_plan_workspace_bytes does not change, and
+ * it is asynchronous and capturable, as the PHAT call is.
+ *   Returns -1 with nothing launched and the outputs untouched on every refusal of asx_xcorr_phat_band_f32_dev, for k outside
+ * 1..ASX_TOPK_MAX and for min_separation < 0.  batch == 0 returns 0.
+ *   Cost.  The transforms and the row pass run once per call.  Every further entry is one inverse column pass over the resident Q',
+ * plus the PHAT tail, the direct Pearson launch and the step; no pass does any exact re-evaluation, so unlike the raw top-k call a
+ * runner-up at the noise floor costs what any other pass costs (measured: DESIGN.md).
+ *   Not offered: the neighbourhood and fractional lag per entry (asx_xcorr_curve_f32_dev serves raw entries; a PHAT caller re-runs
+ * asx_xcorr_phat_sub_f32_dev with a row [lag, lag]), a band per pair, packed plans, the double ABI, streams. */
+int asx_xcorr_phat_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                                const float *d_sample, size_t sample_stride,
+                                const int64_t *d_windows, size_t window_stride, size_t batch,
+                                int64_t bin_lo, int64_t bin_hi, int k, int64_t min_separation,
+                                int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
 
 /* The bins of the band [f_lo_hz, f_hi_hz] for a plan of sample_len = N at sample_rate: bin_lo = ceil(f_lo 2N / rate), bin_hi =
  * min(N, floor(f_hi 2N / rate)) (a band that reaches past the Nyquist frequency ends there).  Host arithmetic, no device.  Returns
@@ -510,7 +552,8 @@ int asx_xcorr_pool_topk_f32_dev(asx_plan *plan,
  * NULL with batch != nsources * nsamples; a bank that cannot be allocated, or would have to grow during a stream capture) and for a
  * band outside 0 <= bin_lo <= bin_hi <= N.  d_lag and d_peak may be NULL.  batch == 0 returns 0.
  *   Cost: the bank fill once per call, then per group the row pass of the strided PHAT call on the bank's rows and its tail
- * (measured: DESIGN.md).  Not offered: top-k with PHAT, a band per pair. */
+ * (measured: DESIGN.md).  asx_xcorr_pool_phat_topk_f32_dev returns the K strongest lags of every pair.  Not offered: a band per
+ * pair. */
 int asx_xcorr_pool_phat_f32_dev(asx_plan *plan,
                                 const float *d_sources, size_t source_stride, size_t nsources,
                                 const float *d_samples, size_t sample_stride, size_t nsamples,
@@ -531,6 +574,31 @@ int asx_xcorr_pool_phat_sub_f32_dev(asx_plan *plan,
                                     size_t batch, int64_t bin_lo, int64_t bin_hi, int half_width,
                                     int64_t *d_lag, double *d_coef, double *d_peak,
                                     double *d_frac, double *d_near, int32_t *d_ret, void *stream);
+
+/* Top-k GCC-PHAT over two track pools: asx_xcorr_pool_phat_f32_dev's pairs with asx_xcorr_phat_topk_f32_dev's entries.  An all-pairs
+ * call over the clips of one event gives the [C, C, k] tables that asx_pool_closure_dev places the clips from, ranked by phase
+ * alignment where a shared hum makes the raw ranking least trustworthy.
+ *   Everything before `batch` means what it means in asx_xcorr_pool_phat_f32_dev (the pools, d_pairs, windows, the layout and stream
+ * rules, the bank, filled ONCE per call whatever k is); the band, k, min_separation, the entry layout (index i*k + j of d_lag,
+ * d_coef, d_peak and d_ret; d_lag and d_peak may be NULL), the rule and the outputs are those of asx_xcorr_phat_topk_f32_dev.
+ *   Per pair it is that call: for a pair whose indices are inside their pools, all k entries are bit for bit what
+ * asx_xcorr_phat_topk_f32_dev returns for that pair alone on the same plan with the same band, k, min_separation and window; entry 0
+ * is bit for bit asx_xcorr_pool_phat_f32_dev's result, and k = 1 launches exactly that call.
+ *   A row of d_pairs with an index outside its pool gives (0, NaN, NaN, -4) in all k entries of that pair (over -2 and -3), reads
+ * nothing outside the pools and leaves the other pairs untouched, bit for bit.
+ *   What the call never does is what asx_xcorr_phat_topk_f32_dev never does; the one host synchronisation it can make is a bank that
+ * must grow, under asx_xcorr_pool_f32_dev's rule.
+ *   Returns -1 with the outputs untouched and nothing launched on every refusal of asx_xcorr_pool_phat_f32_dev, for k outside
+ * 1..ASX_TOPK_MAX and for min_separation < 0.  batch == 0 returns 0.
+ *   Cost: the bank fill and each group's row pass once per call; every further entry is one inverse column pass over the resident
+ * Q' plus the tail, as in asx_xcorr_phat_topk_f32_dev.  Not offered: what that call does not offer. */
+int asx_xcorr_pool_phat_topk_f32_dev(asx_plan *plan,
+                                     const float *d_sources, size_t source_stride, size_t nsources,
+                                     const float *d_samples, size_t sample_stride, size_t nsamples,
+                                     const int32_t *d_pairs,
+                                     const int64_t *d_windows, size_t window_stride, size_t batch,
+                                     int64_t bin_lo, int64_t bin_hi, int k, int64_t min_separation,
+                                     int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
 
 /* The batched variant over several GPUs of one node from ONE process (BASELINE.json north_star; no
  * reference equivalent): plans[i] was created on device i (any devices; all the same sample_len); the

@@ -870,7 +870,7 @@ template <typename TIn> struct Pairs {
 };
 
 // Where pair k's results go (lag and ret may be null): entries step apart (the top-k calls: step = k, entry j of pair i at
-// i * k + j; every other entry point: 1).  peak: the PHAT call's peak heights (step 1), null everywhere else.
+// i * k + j; every other entry point: 1).  peak: the PHAT calls' peak heights, an entry each, null everywhere else.
 struct Results {
     int64_t *lag;
     double *coef;
@@ -879,7 +879,7 @@ struct Results {
     double *peak = nullptr;
     Results at(size_t k) const
     {
-        return { lag ? lag + k * step : nullptr, coef + k * step, ret ? ret + k * step : nullptr, step, peak ? peak + k : nullptr };
+        return { lag ? lag + k * step : nullptr, coef + k * step, ret ? ret + k * step : nullptr, step, peak ? peak + k * step : nullptr };
     }
 };
 
@@ -918,9 +918,11 @@ struct GroupOpts {
     int dot_blocks = 0;          // blocks per pair of the exact re-evaluation; 0: by the group size
     const AsxPeakWs *pk = nullptr; // the peak workspace instead of the lane's (the second look's lists for every lag)
     Topk topk{};                 // k > 1: passes 2..k over the group's Q (y's entry stride is k)
-    // How the product spectrum is weighted (AsxWeight, asx_internal.h; real-column plans, k = 1): a weighted group runs the row pass's
+    // How the product spectrum is weighted (AsxWeight, asx_internal.h; real-column plans): a weighted group runs the row pass's
     // PHAT flavour and the PHAT tail -- k_phat_finalize, the direct Pearson form, k_invalid_rows.  In a pool group the Pearson form
     // reads the pairs' inputs through the group's records, and k_invalid_pairs gives a pair outside its pool a NaN peak too.
+    // With topk.k > 1 (the PHAT top-k calls) passes 2..k search the resident Q', each ending in the same tail, and k_topk_peak
+    // writes each entry's peak height in front of the step.
     // ASX_W_PHAT_BAND: only the bins of `fband` vote and the peak height is per voter (AsxBand::votes).  The entry points turn the
     // full band into ASX_W_PHAT (band_weight).
     AsxWeight weight = ASX_W_NONE;
@@ -1000,6 +1002,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     auto search = [&](int j) { return AsxSearch::of(p->win_lo, p->win_hi, P.N, x.win, x.win_step, W.tk, j); };
     // One pass over the group's Q: the inverse columns, finalize, the exact re-evaluation and Pearson, the lags of `find` competing.
     // first: pass 1, which the profiling marks time and whose r goes to o.r_out.
+    const double votes = form.weight == ASX_W_PHAT_BAND ? o.fband.votes(P.N) : (double)P.F; // a PHAT group: the bins that voted
     auto pass = [&](const AsxSearch &find, bool first) -> int {
         float *const r_out = first ? o.r_out : nullptr;
         if (form.rows == ASX_ROWS_PACKED) asx_launch_inv_cols(P, q, tk, r_out, (int)g, s, find);
@@ -1007,14 +1010,13 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
         if (first && mark(3)) return -1;
         if (form.tail == ASX_TAIL_PHAT) {
             // the PHAT tail: the float32 maximum stands (k_phat_finalize), then the reference's coefficient of the samples at that lag
-            // (the peak height is per bin that voted)
-            asx_launch_phat_finalize(P, fin, W.seg, y.peak, form.weight == ASX_W_PHAT_BAND ? o.fband.votes(P.N) : (double)P.F, (int)g, s, find);
+            // (the peak height is per bin that voted; top-k: the step forms each entry's from the running maximum this leaves alone)
+            asx_launch_phat_finalize(P, fin, W.seg, K > 1 ? nullptr : y.peak, votes, (int)g, s, find);
             if (first && mark(4)) return -1;
             asx_launch_pearson(in, P.N, W.seg, W.psums, out.lag, out.coef, out.ret, (int)g, s);
             // the peak's neighbourhood from the Q' this pass searched, around the index k_phat_finalize settled: it only reads
             if (o.near.frac)
-                asx_launch_phat_near(P, q, W.seg, form.weight == ASX_W_PHAT_BAND ? o.fband.votes(P.N) : (double)P.F, o.near.h, find, pl,
-                                     o.near.frac, o.near.near, (int)g, s);
+                asx_launch_phat_near(P, q, W.seg, votes, o.near.h, find, pl, o.near.frac, o.near.near, (int)g, s);
             return 0;
         }
         asx_launch_finalize(P, fin, W.seg, (int)g, s, o.pair_base, find);
@@ -1038,11 +1040,14 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // Passes 2..k over the same Q; the transforms are not run again.  In a pool group the passes read the pairs' inputs through the
     // group's records (the listed kernels), and an invalid pair -- whose Q is NaN and whose bound is zero, so that no pass finds or
     // lists anything for it -- gets (0, NaN, -4) in all k entries behind the last step, over the steps' -2 and -3.
+    // A PHAT group's passes search the resident Q' and end in the PHAT tail; k_topk_peak takes the entry's peak height from the
+    // pass's running maximum before the step zeroes it.
     for (int j = 0; K > 1 && j < K; j++) {
         if (j > 0 && pass(search(j), false)) return -1;
+        if (form.tail == ASX_TAIL_PHAT && y.peak) asx_launch_topk_peak(W.tk, pk, call, P.N, (int)g, j, K, votes, y.peak, s);
         asx_launch_topk_step(W.tk, W.seg, pk, call, P.N, (int)g, j, K, o.topk.sep, y.lag, y.coef, y.ret, s);
     }
-    if (pl && K > 1) asx_launch_invalid_pairs_k(pl, K, y.lag, y.coef, y.ret, (int)g, s);
+    if (pl && K > 1) asx_launch_invalid_pairs_k(pl, K, y.lag, y.coef, y.ret, y.peak, (int)g, s);
     if (mark(5)) return -1;
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1492,6 +1497,25 @@ extern "C" int asx_xcorr_topk_f32_dev(asx_plan *p, const float *d_source, size_t
                          { d_lag, d_coef, d_ret, (size_t)k }, stream, Topk{ k, min_separation });
 }
 
+// The K strongest separated lags per pair by the GCC-PHAT curve: the banded PHAT call with passes 2..k over each group's resident Q'
+// (run_group).  k = 1 launches exactly asx_xcorr_phat_band_f32_dev.
+extern "C" int asx_xcorr_phat_topk_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                           size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                           int64_t bin_lo, int64_t bin_hi, int k, int64_t min_separation, int64_t *d_lag, double *d_coef,
+                                           double *d_peak, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_phat_topk_f32_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_ret) return fail("%s: null argument", fn);
+    if (k < 1 || k > ASX_TOPK_MAX) return fail("%s: k = %d is not in [1, %d]", fn, k, ASX_TOPK_MAX);
+    if (min_separation < 0) return fail("%s: min_separation = %lld is negative", fn, (long long)min_separation);
+    AsxWeight weight;
+    AsxBand band;
+    if (!band_weight(p, bin_lo, bin_hi, weight, band))
+        return fail("%s: bins [%lld, %lld] are not a band inside [0, %zu]", fn, (long long)bin_lo, (long long)bin_hi, (size_t)p->host.N);
+    return strided_batch(p, fn, d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch,
+                         { d_lag, d_coef, d_ret, (size_t)k, d_peak }, stream, Topk{ k, min_separation }, weight, band);
+}
+
 // ---------------------------------------------------------------------------
 // pool calls: listed pairs of two track pools (asx_xcorr_pool_f32_dev)
 // ---------------------------------------------------------------------------
@@ -1592,6 +1616,26 @@ extern "C" int asx_xcorr_pool_phat_f32_dev(asx_plan *p, const float *d_sources, 
         return fail("%s: bins [%lld, %lld] are not a band inside [0, %zu]", fn, (long long)bin_lo, (long long)bin_hi, (size_t)p->host.N);
     return pool_batch(p, fn, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows, window_stride,
                       batch, { d_lag, d_coef, d_ret, 1, d_peak }, stream, {}, weight, band);
+}
+
+// The K strongest separated lags per pair of two pools by the GCC-PHAT curve: the pool PHAT call with passes 2..k over each group's
+// resident Q' (run_group); the bank is filled once per call whatever k is.  k = 1 launches exactly asx_xcorr_pool_phat_f32_dev.
+extern "C" int asx_xcorr_pool_phat_topk_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                                const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                                const int64_t *d_windows, size_t window_stride, size_t batch, int64_t bin_lo,
+                                                int64_t bin_hi, int k, int64_t min_separation, int64_t *d_lag, double *d_coef,
+                                                double *d_peak, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_pool_phat_topk_f32_dev";
+    if (!p) return fail("%s: null argument", fn);
+    if (k < 1 || k > ASX_TOPK_MAX) return fail("%s: k = %d is not in [1, %d]", fn, k, ASX_TOPK_MAX);
+    if (min_separation < 0) return fail("%s: min_separation = %lld is negative", fn, (long long)min_separation);
+    AsxWeight weight;
+    AsxBand band;
+    if (!band_weight(p, bin_lo, bin_hi, weight, band))
+        return fail("%s: bins [%lld, %lld] are not a band inside [0, %zu]", fn, (long long)bin_lo, (long long)bin_hi, (size_t)p->host.N);
+    return pool_batch(p, fn, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows, window_stride,
+                      batch, { d_lag, d_coef, d_ret, (size_t)k, d_peak }, stream, Topk{ k, min_separation }, weight, band);
 }
 
 // ... with the peak's neighbourhood: asx_xcorr_phat_sub_f32_dev's two outputs for the pool call's pairs

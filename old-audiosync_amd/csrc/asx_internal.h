@@ -672,14 +672,20 @@ void asx_launch_pool_resolve(const AsxDev &P, const AsxPoolArgs &A, AsxPoolPair 
 // behind the Pearson kernels of a pool group: (0, NaN, -4) for every pair flagged ASX_POOL_INVALID, and NaN in peak (null but in a
 // PHAT pool group)
 void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, double *peak, int npairs, hipStream_t s);
-// the same behind the last k_topk_step of a pool group with top-k: all k entries of such a pair (entry stride k)
-void asx_launch_invalid_pairs_k(const AsxPoolPair *pl, int k, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
+// the same behind the last k_topk_step of a pool group with top-k: all k entries of such a pair (entry stride k; peak: null but in a
+// PHAT pool group that was asked for the heights)
+void asx_launch_invalid_pairs_k(const AsxPoolPair *pl, int k, int64_t *lag, double *coef, int32_t *ret, double *peak, int npairs,
+                                hipStream_t s);
 void asx_launch_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, int npairs, hipStream_t s, uint32_t pair_base,
                          const AsxSearch &q);
 // behind the Pearson kernels of pass j of a top-k group: entry j of the caller's arrays (entry stride k) from the pass's results,
 // then pass j + 1's records (call: the call's own search, pass 0's -- the plan's window, used when it has no rows)
 void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, const AsxSearch &call, uint32_t N, int npairs, int j,
                           int k, int64_t sep, int64_t *lag, double *coef, int32_t *ret, hipStream_t s);
+// in FRONT of that step in a PHAT top-k group (k_topk_peak): entry j's peak height (entry stride k) from the pass's running maximum,
+// which the step zeroes -- per voter (f: what asx_launch_phat_finalize takes), NaN where the step writes -2 or -3; peak is not null
+void asx_launch_topk_peak(const AsxTopkWs &T, const AsxPeakWs &W, const AsxSearch &call, uint32_t N, int npairs, int j, int k, double f,
+                          double *peak, hipStream_t s);
 // behind the Pearson kernels of a group with per-pair windows: (lag, coef, ret) = (0, NaN, -2) for every pair whose row is invalid
 void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s);
 // The exact passes over float or double inputs (instances for both next to the kernels, xcorr_kernels.hip).

@@ -1553,6 +1553,18 @@ __global__ __launch_bounds__(256) void k_phat_finalize(AsxPeakWs W, AsxSeg *__re
     peak[pair] = v;
 }
 
+// Its AsxSelTopkSeed form, under a name of its own as k_pearson_prep_x has one (the two k_phat_finalize instances stay the kernels they
+// were): the tail of passes 2..k of a PHAT top-k group (asx_xcorr_phat_topk_f32_dev), whose seed is the pair's record's.  It writes no
+// peak: k_topk_peak forms each entry's height from pairmax, which this kernel leaves as it found it.
+__global__ __launch_bounds__(256) void k_phat_finalize_x(AsxPeakWs W, AsxSeg *__restrict__ seg, uint32_t N, int npairs, AsxSelTopkSeed sel)
+{
+    const int pair = blockIdx.x * 256 + threadIdx.x;
+    if (pair >= npairs) return;
+    const asx_peak_t best = W.pairmax[pair];
+    seg[pair] = make_seg(best ? peak_index(best) : sel.seed_of((size_t)pair, N), N);
+    W.refine_n[pair] = 0u;
+}
+
 // ---------------------------------------------------------------------------
 // k_phat_near: grid (npairs), a block per pair.  Behind k_phat_finalize in the tail of a PHAT group whose call asked for it
 // (asx_xcorr_phat_sub_f32_dev): r_phat at the 2h + 1 indices around the pair's settled peak p = seg[pair].peak, straight from the
@@ -1723,9 +1735,11 @@ void asx_launch_phat_finalize(const AsxDev &P, const AsxPeakWs &W, AsxSeg *seg, 
                               const AsxSearch &q)
 {
     asx_with_selection(q, [&](auto sel) {
-        if constexpr (!std::is_same<decltype(sel), AsxSelTopkSeed>::value) // (top-k with PHAT does not exist)
-            hipLaunchKernelGGL(k_phat_finalize<decltype(sel)>, dim3((unsigned)(npairs + 255) / 256), dim3(256), 0, s, W, seg, peak, P.N,
-                               f, npairs, sel);
+        const dim3 grid((unsigned)(npairs + 255) / 256), block(256);
+        if constexpr (std::is_same<decltype(sel), AsxSelTopkSeed>::value) // (a top-k pass: the step's k_topk_peak writes the peak)
+            hipLaunchKernelGGL(k_phat_finalize_x, grid, block, 0, s, W, seg, P.N, npairs, sel);
+        else
+            hipLaunchKernelGGL(k_phat_finalize<decltype(sel)>, grid, block, 0, s, W, seg, peak, P.N, f, npairs, sel);
     });
 }
 

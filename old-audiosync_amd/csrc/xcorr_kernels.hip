@@ -1042,6 +1042,30 @@ __global__ __launch_bounds__(ASX_THREADS) void k_topk_step(AsxTopkWs T, const As
     W.cand_n[pair] = 0;
 }
 
+// grid (npairs / ASX_THREADS): what the step of a PHAT top-k group (asx_xcorr_phat_topk_f32_dev) adds, launched IN FRONT of pass j's
+// k_topk_step: entry j's peak height.  The pass's running maximum is still in pairmax (k_phat_finalize only read it; the step zeroes
+// it), so peak[pair * k + j] is formed as k_phat_finalize forms the one-entry call's -- |key| / f, 0 for an empty maximum, NaN for a
+// NaN seed -- and is NaN where the step is about to write -2 or -3: the record's flags say so from pass 1 on (an earlier step set
+// them), the pair's row in pass 0.  k_topk_step needs no PHAT form of its own: no pass of a PHAT group marks its segment, so ret is
+// never 1, and bound2 stays what row 0 of the PHAT row kernel set (FLT_MIN, or 0 for a silent track).
+__global__ __launch_bounds__(ASX_THREADS) void k_topk_peak(const AsxTopkPair *__restrict__ X, const asx_peak_t *__restrict__ pairmax,
+                                                            AsxWinRows R, uint32_t N, int npairs, int j, int k, double f,
+                                                            double *__restrict__ peak)
+{
+    const int pair = blockIdx.x * ASX_THREADS + threadIdx.x;
+    if (pair >= npairs) return;
+    bool entry;
+    if (j == 0) {
+        AsxWin z;
+        entry = !R.rows || asx_win_row(R, (size_t)pair, N, z);
+    } else {
+        entry = !(X[pair].flags & (ASX_TK_INVALID | ASX_TK_EMPTY));
+    }
+    const asx_peak_t best = pairmax[pair];
+    const float key = best ? peak_key(best) : 0.f;
+    peak[(size_t)pair * (size_t)k + (size_t)j] = (!entry || key == -INFINITY) ? (double)NAN : fabs((double)key) / f;
+}
+
 // grid (npairs / ASX_THREADS): behind k_pearson_final / k_pearson_final_spec of a group with per-pair windows, the pairs whose row is
 // invalid (asx_win_row) get lag 0, a NaN coefficient and ret -2; the others are not touched
 __global__ __launch_bounds__(ASX_THREADS) void k_invalid_rows(AsxWinRows R, uint32_t N, int npairs, int64_t *__restrict__ lag,
@@ -1084,6 +1108,22 @@ __global__ __launch_bounds__(ASX_THREADS) void k_invalid_pairs_k(const AsxPoolPa
         if (lag) lag[e] = 0;
         coef[e] = (double)NAN;
         ret[e] = -4;
+    }
+}
+
+// ... of a PHAT pool group whose call asked for the peak heights (asx_xcorr_pool_phat_topk_f32_dev): a NaN peak in all k entries as well
+__global__ __launch_bounds__(ASX_THREADS) void k_invalid_pairs_kp(const AsxPoolPair *__restrict__ PL, int npairs, int k,
+                                                                   int64_t *__restrict__ lag, double *__restrict__ coef,
+                                                                   int32_t *__restrict__ ret, double *__restrict__ peak)
+{
+    const int pair = blockIdx.x * ASX_THREADS + threadIdx.x;
+    if (pair >= npairs || !(PL[pair].flags & ASX_POOL_INVALID)) return;
+    for (int j = 0; j < k; j++) {
+        const size_t e = (size_t)pair * (size_t)k + (size_t)j;
+        if (lag) lag[e] = 0;
+        coef[e] = (double)NAN;
+        ret[e] = -4;
+        peak[e] = (double)NAN;
     }
 }
 
@@ -2581,16 +2621,25 @@ void asx_launch_topk_step(AsxTopkWs T, const AsxSeg *seg, const AsxPeakWs &W, co
                        call.rows, N, npairs, j, k, sep, lag, coef, ret);
 }
 
+void asx_launch_topk_peak(const AsxTopkWs &T, const AsxPeakWs &W, const AsxSearch &call, uint32_t N, int npairs, int j, int k, double f,
+                          double *peak, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_topk_peak, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, T.pairs, W.pairmax, call.rows,
+                       N, npairs, j, k, f, peak);
+}
+
 void asx_launch_invalid_pairs(const AsxPoolPair *pl, int64_t *lag, double *coef, int32_t *ret, double *peak, int npairs, hipStream_t s)
 {
     hipLaunchKernelGGL(k_invalid_pairs, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, pl, npairs, lag, coef, ret,
                        peak);
 }
 
-void asx_launch_invalid_pairs_k(const AsxPoolPair *pl, int k, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)
+void asx_launch_invalid_pairs_k(const AsxPoolPair *pl, int k, int64_t *lag, double *coef, int32_t *ret, double *peak, int npairs,
+                                hipStream_t s)
 {
-    hipLaunchKernelGGL(k_invalid_pairs_k, dim3((npairs + ASX_THREADS - 1) / ASX_THREADS), dim3(ASX_THREADS), 0, s, pl, npairs, k, lag, coef,
-                       ret);
+    const dim3 grid((npairs + ASX_THREADS - 1) / ASX_THREADS), block(ASX_THREADS);
+    if (peak) hipLaunchKernelGGL(k_invalid_pairs_kp, grid, block, 0, s, pl, npairs, k, lag, coef, ret, peak);
+    else hipLaunchKernelGGL(k_invalid_pairs_k, grid, block, 0, s, pl, npairs, k, lag, coef, ret);
 }
 
 void asx_launch_invalid_rows(const AsxWinRows &rows, uint32_t N, int64_t *lag, double *coef, int32_t *ret, int npairs, hipStream_t s)

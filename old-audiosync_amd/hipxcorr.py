@@ -65,11 +65,14 @@ _HEADER_SIGNATURES = {
     "asx_xcorr_phat_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_band_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_sub_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_phat_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_topk_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _int, _i64, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_phat_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_phat_sub_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i64, _i64, _int, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp]),
+    "asx_xcorr_pool_phat_topk_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i64, _i64, _int, _i64, _vp, _vp,
+                                                _vp, _vp, _vp]),
     "asx_xcorr_curve_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_curve_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_track_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -579,6 +582,22 @@ def pool_phat_sub_args(n, sources, samples, pairs=None, windows=None, band=None,
     pool_phat_args' tuple + (half_width,).  ValueError on anything else."""
     h = _near_option(half_width)
     return pool_phat_args(n, sources, samples, pairs, windows, band) + (h,)
+
+
+def phat_topk_args(n, source, sample, k, min_separation, windows=None, band=None):
+    """Host checks of Plan.xcorr_phat_topk_f32: the shapes of windowed_args (windows=None: the plan's window, no rows), band None
+    (every bin) or integers (bin_lo, bin_hi) with 0 <= bin_lo <= bin_hi <= N, k and min_separation as topk_args checks them.  ->
+    (source, sample, windows or None, batch, source_stride, sample_stride, window_stride, bin_lo, bin_hi, k, min_separation).
+    ValueError on anything else."""
+    option = _band_option(n, band) + _topk_option(k, min_separation)
+    return _strided_args(n, source, sample, None if windows is None else _window_rows(windows)) + option
+
+
+def pool_phat_topk_args(n, sources, samples, k, min_separation, pairs=None, windows=None, band=None):
+    """Host checks of Plan.xcorr_pool_phat_topk_f32: k and min_separation as topk_args checks them, the rest as pool_phat_args.  ->
+    pool_phat_args' tuple + (k, min_separation).  ValueError on anything else."""
+    option = _topk_option(k, min_separation)
+    return pool_phat_args(n, sources, samples, pairs, windows, band) + option
 
 
 def _curve_option(half_width, entries):
@@ -1097,6 +1116,26 @@ class Plan:
                                                      d_lag or None, d_coef or None, d_peak or None, d_frac or None, d_near or None,
                                                      d_ret or None, stream or None))
 
+    def xcorr_phat_topk_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, bin_lo, bin_hi, k,
+                            min_separation, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_phat_topk_f32_dev -- xcorr_phat_band_dev's pairs with the k strongest lags of r_phat
+        at least min_separation apart, entry j of pair i at index i*k + j of d_lag / d_coef / d_peak / d_ret (d_lag and d_peak may be
+        0); always asynchronous on `stream`"""
+        _check(lib().asx_xcorr_phat_topk_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride),
+                                                 d_windows or None, int(window_stride), int(batch), int(bin_lo), int(bin_hi), int(k),
+                                                 int(min_separation), d_lag or None, d_coef or None, d_peak or None, d_ret or None,
+                                                 stream or None))
+
+    def xcorr_pool_phat_topk_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows,
+                                 window_stride, batch, bin_lo, bin_hi, k, min_separation, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_phat_topk_f32_dev -- xcorr_pool_phat_dev's pairs with the entries of
+        xcorr_phat_topk_dev"""
+        _check(lib().asx_xcorr_pool_phat_topk_f32_dev(self._h, d_sources or None, int(source_stride), int(nsources), d_samples or None,
+                                                      int(sample_stride), int(nsamples), d_pairs or None, d_windows or None,
+                                                      int(window_stride), int(batch), int(bin_lo), int(bin_hi), int(k),
+                                                      int(min_separation), d_lag or None, d_coef or None, d_peak or None,
+                                                      d_ret or None, stream or None))
+
     def xcorr_curve_dev(self, d_src, src_stride, d_smp, smp_stride, batch, entries, d_center, half_width, d_r, d_coef, d_frac, d_ret,
                         stream=0):
         """raw device pointers (ints): asx_xcorr_curve_f32_dev -- around each of the batch * entries lags of d_center (int64), the
@@ -1264,6 +1303,26 @@ class Plan:
         shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
         return self._staged((s, t, pr, w), shape, _PHAT_RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_phat_dev(
             d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, lo, hi, *d_out))
+
+    def xcorr_phat_topk_f32(self, source, sample, k, min_separation, windows=None, band=None):
+        """The k strongest separated lags per pair by the GCC-PHAT curve (asx_xcorr_phat_topk_f32_dev).  source, sample, windows and
+        band as in xcorr_phat_f32; k and min_separation as in xcorr_topk_f32.  Arguments are checked on the host (ValueError) before
+        anything is uploaded.  Returns (lag int64[B, k], coef float64[B, k], peak float64[B, k], ret int32[B, k]); ret = -3 (and a NaN
+        peak) where no lag was left.  Entry 0 is xcorr_phat_f32's result."""
+        s, t, w, batch, ss, ts, ws, lo, hi, k, sep = phat_topk_args(self.sample_len, source, sample, k, min_separation, windows, band)
+        return self._staged((s, t, w), (batch, k), _PHAT_RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_phat_topk_dev(
+            d_s, ss, d_t, ts, d_w, ws, batch, lo, hi, k, sep, *d_out))
+
+    def xcorr_pool_phat_topk_f32(self, sources, samples, k, min_separation, pairs=None, windows=None, band=None):
+        """The k strongest separated lags per pair of two pools by the GCC-PHAT curve (asx_xcorr_pool_phat_topk_f32_dev): the pools,
+        pairs, windows and band of xcorr_pool_phat_f32, k and min_separation of xcorr_topk_f32.  Every track is transformed once per
+        call, whatever k is.  Returns (lag, coef, peak, ret) of shape [B, k], or [S, R, k] when pairs is None -- the tables
+        pool_closure takes; ret = -3 where no lag was left, -4 in all k entries of a pair with an index outside its pool."""
+        n = self.sample_len
+        s, t, pr, w, batch, ws, lo, hi, k, sep = pool_phat_topk_args(n, sources, samples, k, min_separation, pairs, windows, band)
+        shape = ((batch,) if pr is not None else (s.shape[0], t.shape[0])) + (k,)
+        return self._staged((s, t, pr, w), shape, _PHAT_RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_phat_topk_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, lo, hi, k, sep, *d_out))
 
     def _staged_sub(self, inputs, shape, h, launch):
         """_staged for the sub-sample PHAT calls: outputs (lag, coef, peak, frac, near, ret), near of shape + (2h + 1,)"""
