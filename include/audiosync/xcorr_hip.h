@@ -31,7 +31,8 @@
  *   ret[i] = -2 (asx_xcorr_windowed_f32_dev, and asx_xcorr_phat_f32_dev with rows): pair i's lag
  *   window was not a window inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.  (asx_xcorr_curve_f32_dev and
  *   asx_xcorr_pool_curve_f32_dev: an entry's centre was not a lag inside [-N, N-1]; NaN in all its values.  The same in
- *   asx_xcorr_track_f32_dev and asx_xcorr_pool_track_f32_dev, with used = 0.)
+ *   asx_xcorr_track_f32_dev and asx_xcorr_pool_track_f32_dev, with used = 0.  asx_xcorr_ncc_f32_dev with rows: the row was not a
+ *   window inside [0, N-1]; peak[i] = NaN too.)
  *   ret = -3 (asx_xcorr_topk_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_phat_topk_f32_dev and
  *   asx_xcorr_pool_phat_topk_f32_dev only): no lag is left for
  *   this entry of the pair (its window minus the zones around the earlier entries is empty);
@@ -360,6 +361,71 @@ int asx_xcorr_phat_f32_dev(asx_plan *plan, const float *d_source, size_t source_
                            const float *d_sample, size_t sample_stride,
                            const int64_t *d_windows, size_t window_stride, size_t batch,
                            int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
+/* Normalised cross-correlation: the strided batch with the lags ranked by the Pearson coefficient itself.  Every other search ranks
+ * lags by the raw r or the whitened r_phat and reports the coefficient only at the one lag that won, so a louder, merely similar
+ * stretch of the source, a level step or slow rumble can win r with a coefficient near 0.  This call searches the curve of
+ * coefficients (what other toolkits call normxcorr or the `coeff` option of xcorr).
+ *   The definition.  N = sample_len, x = the source (2N float32), y = the sample (N float32).  Only the lags 0 <= l <= N-1 exist for
+ * this call: there the sample lies wholly inside the source, the reference's segment for l >= 0 being source[l, l+N) against the whole
+ * sample (src/cross_correlation.c:264-271).  Negative lags are out of scope: there the circular r[2N + l] also holds the |l| products
+ * that wrapped around, and taking them out for every lag is a second correlation, against the source's upper half alone, which prefix
+ * sums cannot supply.  In float64:
+ *     mu     = mean of all 2N source frames
+ *     Sx[l]  = sum_{n<N} x[l+n]             (accumulated as sums of x - mu, then N*mu added back: an offset costs no digits)
+ *     Vx[l]  = sum_{n<N} (x[l+n] - mean_l)^2 = Sxx'[l] - Sx'[l]^2 / N    on the mu-shifted values
+ *     Sy, Vy = the same over the sample, about its own mean
+ *     c[l]   = (r32[l] / s  -  Sx[l] * Sy / N) / sqrt(Vx[l] * Vy)
+ *     c32[l] = (float) c[l]
+ * r32[l] is the float32 value the plan's transforms produce for index l (what asx_xcorr_debug_r_dev returns) and s the factor it
+ * carries against the plain sum (asx_plan_fft_len()).  Everything behind r32 is float64: in exact arithmetic c[l] is
+ * pearson_coefficient() of the reference's segments at lag l, and the only float32 error in it is that of r32.
+ *   Which lags compete.  Vmax = max of Vx[l] over ALL lags 0..N-1, whatever the window.  Lag l competes iff Vy > 0,
+ * Vx[l] >= min_energy * Vmax, and c[l] is not NaN (nor infinite: a window of exactly constant frames under an inexact r32).
+ * ASX_NCC_MIN_ENERGY (1e-6) <= min_energy <= 1; anything else, a NaN included, is refused.  The floor keeps windows of digital silence
+ * out (their coefficient is 0/0) and windows so quiet that the error of r32 divided by their energy is noise of order 1.  A lag whose
+ * Vx lies within a relative 1e-6 of the threshold may fall on either side.
+ *   The peak.  Among the competing lags of the pair's window the largest |c32[l]| wins, the smallest lag among equal float32 values.
+ * There is no signed seed: the reference's arr[0] quirk belongs to max_abs_index() over r, and this curve is not r.  If no lag
+ * competes the pair returns lag = the window's lag_min and peak = 0 (a constant or silent sample, a silent source, N = 1).  It is the
+ * float32 argmax, NOT the float64 argmax by construction, as for PHAT and for the same reason: two lags closer than the curve's
+ * resolution (measured: DESIGN.md, tests/test_gpu_ncc.py) may come back in either order.
+ *   Outputs per pair.  lag: the winner.  coef: the reference's coefficient of the ORIGINAL samples at that lag, in the direct form:
+ * under asx_plan_set_pearson(plan, 0) bit for bit what asx_xcorr_windowed_f32_dev returns for the row [lag, lag].  peak:
+ * (double)|c32[lag]|.  ret: 0 for a computed pair; -1 for a NaN coefficient (lag, coef and peak are still written); -2 for a row that
+ * does not satisfy 0 <= lag_min <= lag_max <= N-1 (lag 0, coef NaN, peak NaN, the other pairs untouched bit for bit).  ret is never 1.
+ *   Inputs.  Strides, broadcast (a stride of 0), strides below the track length, the 16-byte layout rule on real-column plans and
+ * the stream rule are those of asx_xcorr_strided_f32_dev.  The call runs on every plan, packed ones included.  d_windows == NULL
+ * means every lag 0..N-1: the plan's own window is ignored and left as it is, because its default [-N, N-1] is not a window of this
+ * call.  Otherwise d_windows holds per-pair rows, read on the device as in asx_xcorr_windowed_f32_dev, under the stricter rule above.
+ *   Refusals: -1 with nothing launched and the outputs untouched for a NULL plan, track, d_coef, d_peak or d_ret, min_energy out of
+ * range, the layout rule failing, and the first allocation (below) failing or falling inside a stream capture.  d_lag may be NULL.
+ * batch == 0 returns 0.
+ *   What the call never does.  It lists nothing and takes no second look.  It behaves the same whatever asx_plan_set_exact,
+ * asx_plan_set_pearson, asx_plan_set_prune, asx_plan_set_qstore and the plan's window say.  It leaves asx_plan_peak_overflows,
+ * asx_plan_peak_repairs, asx_plan_pearson_modes, asx_plan_prune_stats, asx_plan_qstore_stats and asx_plan_workspace_bytes unchanged.
+ * After its first call on a plan it allocates nothing (but for the broadcast slot's first allocation under
+ * asx_xcorr_strided_f32_dev's rule, which that call counts in asx_plan_workspace_bytes), and it never synchronises the host.  Every value of a pair is independent of the
+ * batch size and of the pair's position in the batch: the reduction trees are fixed by N alone.  A broadcast track's moments are
+ * computed once per call.
+ *   Memory.  r of every lag (8N bytes per pair) and a per-lag table of the source's sliding sums (16N bytes per source track) for one
+ * group of pairs form one set, allocated at the plan's first NCC call and kept with the plan; it is not counted in
+ * asx_plan_workspace_bytes.  The call works in groups of min(asx_plan_group(), 2^30 / 24N) pairs, at least one, so the set holds at
+ * most 1 GiB (or one pair's 24N bytes).
+ *   Cost: the transforms of the strided call with every inverse tile in its general form (r is written out), three passes over the
+ * tracks for the moments and one over r and the table (measured: DESIGN.md).
+ *   Not offered: negative lags, pools, top-k, a neighbourhood or fractional lag (asx_xcorr_curve_f32_dev serves the returned lag),
+ * the double ABI, streams, and a fused inverse pass. */
+#define ASX_NCC_MIN_ENERGY 1e-6
+int asx_xcorr_ncc_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                          const float *d_sample, size_t sample_stride,
+                          const int64_t *d_windows, size_t window_stride, size_t batch,
+                          double min_energy,
+                          int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+/* ONE contiguous pair, every lag competing under min_energy: c32 of lags 0..N-1 to d_c (N floats, NaN where the lag does not
+ * compete); the results are those of asx_xcorr_ncc_f32_dev for that pair without rows */
+int asx_xcorr_ncc_debug_c_dev(asx_plan *plan, const float *d_source, const float *d_sample, double min_energy,
+                              float *d_c, int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
 
 /* Band-limited GCC-PHAT: asx_xcorr_phat_f32_dev in which only the bins of a frequency band vote.  Most material is band-limited
  * (speech, codecs that low-pass, hum and rumble at the bottom): outside its band the cross spectrum is rounding noise, and with

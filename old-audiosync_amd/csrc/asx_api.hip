@@ -117,8 +117,8 @@ struct asx_plan {
     hipStream_t stream = nullptr;
     std::mutex lock;
 
-    // Who owns the plan's device memory (asx_plan_workspace_bytes: all but the bank's).  mem: what plan_init takes and, once created,
-    // the lazy sets (big, bslot, st, st64: whole or absent); cxy0: lane 0's C_x / C_y, which tune_placement may replace; bank.mem.
+    // Who owns the plan's device memory (asx_plan_workspace_bytes: all but the bank's and the NCC set's).  mem: what plan_init takes and, once created,
+    // the lazy sets (big, bslot, st, st64: whole or absent); cxy0: lane 0's C_x / C_y, which tune_placement may replace; bank.mem; ncc.mem.
     AsxMemSet mem{ hip_mem }, cxy0{ hip_mem };
     // "Lanes": each owns the workspaces of one launch group and a stream.  With two lanes
     // (ASX_LANES=2) consecutive groups of a batch alternate lanes so that kernels of different
@@ -163,6 +163,14 @@ struct asx_plan {
         size_t nsrc = 0, nsmp = 0;      // capacity in tracks
         unsigned long long fills = 0;   // pool calls that filled it (diagnostic: asx_plan_debug_bank)
     } bank;
+    // Normalised cross-correlation (asx_xcorr_ncc_f32_dev; lazy, whole or absent, allocated at the plan's first such call): r of every
+    // lag of one NCC group, the per-lag tables of its source tracks and the small sums (AsxNccWs).  group <= the plan's: the set is
+    // bounded by ASX_NCC_WS_BYTES (or one pair's share where that is larger).  Its own set: not part of asx_plan_workspace_bytes.
+    struct Ncc {
+        AsxNccWs w{};
+        AsxMemSet mem{ hip_mem };
+        size_t group = 0;
+    } ncc;
     // pairs whose near-tie list overflowed since the list was last emptied (k_finalize appends, resolve_overflows reads)
     uint32_t *over_list = nullptr, *over_n = nullptr;
     volatile uint32_t *h_over_n = nullptr; // page-locked host mirror of *over_n (device-visible: AsxPeakWs::over_host)
@@ -929,6 +937,10 @@ struct GroupOpts {
     AsxBand fband{};
     bool qstore = true;          // partial storing of Q allowed (false: the second run of a pair whose stored set fell short)
     Near near{};                 // a PHAT group: the group's places for the peak's neighbourhood (k_phat_near behind the tail), or none
+    // Not part of the ask: the group ends behind its inverse pass (asx_xcorr_ncc_f32_dev, with r_out) -- no finalize, no exact
+    // re-evaluation, no Pearson pass, so no counter moves and y is not written -- and every lag's r is wanted whatever the plan's
+    // window says: the search is the full one.
+    bool transforms_only = false;
 };
 
 // One group: g <= plan->group pairs, the first g of x, results to the first g of y.
@@ -939,7 +951,8 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     asx_plan::Lane &W = p->lanes[o.lane];
     const AsxPeakWs &pk = o.pk ? *o.pk : W.pk;
     auto mark = [&](size_t k) { return o.prof_group != GroupOpts::no_marks && prof_mark(p, s, o.prof_group * 6 + k); };
-    const AsxSearch call = AsxSearch::of(p->win_lo, p->win_hi, P.N, x.win, x.win_step, W.tk, 0); // pass 1's search
+    const AsxSearch call = o.transforms_only ? AsxSearch::of(-(int64_t)P.N, (int64_t)P.N - 1, P.N, nullptr, 0, W.tk, 0)
+                                             : AsxSearch::of(p->win_lo, p->win_hi, P.N, x.win, x.win_step, W.tk, 0); // pass 1's search
     // what the group launches (plan_math.h): decided here, once, and only branched on below
     const AsxGroupForm form = asx_group_form(
         { .rlayout = P.rlayout != 0, .plan_prune = p->prune, .plan_spectral = p->spectral, .band_sums = pk.band != nullptr,
@@ -1008,6 +1021,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
         if (form.rows == ASX_ROWS_PACKED) asx_launch_inv_cols(P, q, tk, r_out, (int)g, s, find);
         else asx_launch_inv_cols_r(P, q, tk, r_out, (int)g, s, find, form.pruned ? &U : nullptr);
         if (first && mark(3)) return -1;
+        if (o.transforms_only) return 0;
         if (form.tail == ASX_TAIL_PHAT) {
             // the PHAT tail: the float32 maximum stands (k_phat_finalize), then the reference's coefficient of the samples at that lag
             // (the peak height is per bin that voted; top-k: the step forms each entry's from the running maximum this leaves alone)
@@ -1303,15 +1317,11 @@ extern "C" int asx_xcorr_batch_f32_dev(asx_plan *p, const float *d_source, const
 // ---------------------------------------------------------------------------
 // asx_xcorr_strided_f32_dev and asx_xcorr_windowed_f32_dev (fn: the entry point's name for the messages), after their own null checks.
 // d_windows: null, or the per-pair windows (Pairs::win), window_stride rows apart.
-static int strided_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
-                         size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, const Results &y, void *stream,
-                         const Topk &topk = {}, AsxWeight weight = ASX_W_NONE, const AsxBand &band = {}, const Near &near = {})
+// The layout rule of a strided call's inputs: 0, or -1 with the message.
+static int strided_layout(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
+                          size_t sample_stride)
 {
-    PlanCall c(p, stream);
-    if (!c.dg.ok) return fail("cannot select device %d", p->device);
-    hipStream_t s = c.s;
     const AsxDev &P = p->dev;
-    if (weight != ASX_W_NONE && P.rlayout != 1) return fail("%s: PHAT calls need a real-column plan (asx_plan_layout() == 1)", fn);
     if (P.rlayout) {
         // k_fwd_cols_r reads every row of a pair's inputs as 16-byte loads from the pair's first frame
         if (((uintptr_t)d_source & 15u) || ((uintptr_t)d_sample & 15u))
@@ -1321,7 +1331,15 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
             return fail("%s: real-column plans need strides that are multiples of 4 floats "
                         "(source_stride %zu, sample_stride %zu)", fn, source_stride, sample_stride);
     }
-    if (batch == 0) return 0;
+    return 0;
+}
+
+// The call's broadcast operands (bit 0: the source, bit 1: the sample; real-column plans): the slot, allocated at the first such call,
+// and the shared track's forward column pass into it.  -> bc through *out; -1 with the message.
+static int strided_broadcast(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
+                             size_t sample_stride, hipStream_t s, int *out)
+{
+    const AsxDev &P = p->dev;
     const int bc = P.rlayout ? (source_stride == 0 ? 1 : 0) | (sample_stride == 0 ? 2 : 0) : 0;
     if (bc) {
         AsxSpectra &B = p->bslot;
@@ -1335,6 +1353,22 @@ static int strided_batch(asx_plan *p, const char *fn, const float *d_source, siz
         // the shared track's forward column pass: once per call, on the caller's stream, before any lane forks
         asx_launch_fwd_cols_r(P, (bc & 1) ? d_source : nullptr, 0, (bc & 2) ? d_sample : nullptr, 0, 0, 1, B, true, s);
     }
+    *out = bc;
+    return 0;
+}
+
+static int strided_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
+                         size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, const Results &y, void *stream,
+                         const Topk &topk = {}, AsxWeight weight = ASX_W_NONE, const AsxBand &band = {}, const Near &near = {})
+{
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
+    if (weight != ASX_W_NONE && p->dev.rlayout != 1) return fail("%s: PHAT calls need a real-column plan (asx_plan_layout() == 1)", fn);
+    if (strided_layout(p, fn, d_source, source_stride, d_sample, sample_stride)) return -1;
+    if (batch == 0) return 0;
+    int bc = 0;
+    if (strided_broadcast(p, fn, d_source, source_stride, d_sample, sample_stride, s, &bc)) return -1;
     return run_batch(p, Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, bc, d_windows, window_stride), batch, y, s,
                      topk, weight, band, near);
 }
@@ -1867,6 +1901,96 @@ extern "C" int asx_xcorr_debug_r_dev(asx_plan *p, const float *d_source, const f
     prof_end_call(p, 1);
     if (rc == 0 && p->exact && resolve_overflows(p, x, y, c.s) < 0) rc = -1;
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// normalised cross-correlation (asx_xcorr_ncc_f32_dev): a consumer behind ordinary launch groups
+// ---------------------------------------------------------------------------
+#define ASX_NCC_WS_BYTES ((size_t)1 << 30)
+static_assert(ASX_NCC_MIN_ENERGY == 1e-6, "the header's floor");
+
+// The plan's NCC set: r (8N bytes per pair) and the per-lag table (16N bytes per source track) of one NCC group, plus the chunk sums.
+static int ensure_ncc(asx_plan *p, const char *fn, hipStream_t s)
+{
+    if (p->ncc.w.r) return 0;
+    if (stream_capturing(s))
+        return fail("%s: the plan's NCC workspace does not exist yet and cannot be allocated during a stream capture; make one call "
+                    "outside the capture first", fn);
+    const size_t N = p->host.N;
+    const size_t g = std::max<size_t>(1, std::min(p->group, ASX_NCC_WS_BYTES / (24 * N)));
+    const size_t chunks = g * ((size_t)asx_ncc_chunks((uint32_t)(2 * N)) + asx_ncc_chunks((uint32_t)N));
+    if (asx_mem_whole(p->ncc.mem, p->ncc.w, [&](AsxMemSet &m, AsxNccWs &T) {
+            return m.take(&T.r, g * 2 * N) || m.take(&T.table, g * N) || m.take(&T.raw, chunks) || m.take(&T.m1, chunks) ||
+                           m.take(&T.m2, chunks) || m.take(&T.sstat, g * ASX_NCC_STAT) || m.take(&T.ystat, g * ASX_NCC_STAT) ||
+                           m.take(&T.best, g)
+                       ? -1 : 0;
+        }))
+        return fail("%s: hipMalloc of the NCC workspace failed: %s", fn, hipGetErrorString(g_take_err));
+    p->ncc.group = g;
+    return 0;
+}
+
+// After the entry point's null checks.  c_out: the debug call's curve (one contiguous pair), else null.
+static int ncc_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample, size_t sample_stride,
+                     const int64_t *d_windows, size_t window_stride, size_t batch, double min_energy, float *c_out, const Results &y,
+                     void *stream)
+{
+    if (!(min_energy >= ASX_NCC_MIN_ENERGY && min_energy <= 1.0)) // (a NaN fails both)
+        return fail("%s: min_energy %g is not in [%g, 1]", fn, min_energy, (double)ASX_NCC_MIN_ENERGY);
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
+    const AsxDev &P = p->dev;
+    if (strided_layout(p, fn, d_source, source_stride, d_sample, sample_stride)) return -1;
+    if (batch == 0) return 0;
+    if (ensure_ncc(p, fn, s)) return -1;
+    int bc = 0;
+    if (strided_broadcast(p, fn, d_source, source_stride, d_sample, sample_stride, s, &bc)) return -1;
+    // the transforms see no rows: every lag's r is wanted, and the rows are this call's own (0 <= lag_min <= lag_max <= N-1)
+    const Pairs<float> x = Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, bc, nullptr, 0);
+    asx_plan::Lane &L = p->lanes[0];
+    prof_begin_call(p);
+    size_t gi = 0;
+    for (size_t done = 0; done < batch; done += p->ncc.group, gi++) {
+        const size_t g = std::min(p->ncc.group, batch - done);
+        const Pairs<float> xg = x.at(done);
+        const Results yg = y.at(done);
+        const int64_t *rows = d_windows ? d_windows + 2 * done * window_stride : nullptr;
+        AsxNccWs W = p->ncc.w;
+        // a track every pair shares (a stride of 0, whatever the layout): its moments once per call, by the first group
+        W.nsrc = source_stride == 0 ? 1u : (uint32_t)g;
+        W.nsmp = sample_stride == 0 ? 1u : (uint32_t)g;
+        W.do_src = source_stride != 0 || done == 0;
+        W.do_smp = sample_stride != 0 || done == 0;
+        if (run_group(p, xg, g, yg, s, { .prof_group = gi, .listed = false, .f32_abi = false, .r_out = W.r, .transforms_only = true }))
+            return -1;
+        asx_launch_ncc_moments(W, xg.src, source_stride, xg.smp, sample_stride, P.N, s);
+        asx_launch_ncc_peak(W, W.r, P.nout, P.N, (double)P.F, min_energy, rows, window_stride, c_out, L.seg, yg.peak, (int)g, s);
+        // the reference's coefficient of the samples at the winner, in the direct form
+        asx_launch_pearson(xg.inputs(nullptr), P.N, L.seg, L.psums, yg.lag, yg.coef, yg.ret, (int)g, s);
+        if (rows) asx_launch_ncc_invalid(P.N, rows, window_stride, yg.lag, yg.coef, yg.peak, yg.ret, (int)g, s);
+        HIP_TRY(hipGetLastError());
+    }
+    prof_end_call(p, gi);
+    return 0;
+}
+
+extern "C" int asx_xcorr_ncc_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                     size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                     double min_energy, int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+{
+    if (!p || !d_source || !d_sample || !d_coef || !d_peak || !d_ret) return fail("asx_xcorr_ncc_f32_dev: null argument");
+    return ncc_batch(p, "asx_xcorr_ncc_f32_dev", d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch,
+                     min_energy, nullptr, { d_lag, d_coef, d_ret, 1, d_peak }, stream);
+}
+
+extern "C" int asx_xcorr_ncc_debug_c_dev(asx_plan *p, const float *d_source, const float *d_sample, double min_energy, float *d_c,
+                                         int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+{
+    if (!p || !d_source || !d_sample || !d_c || !d_coef || !d_peak || !d_ret) return fail("asx_xcorr_ncc_debug_c_dev: null argument");
+    const size_t N = p->host.N;
+    return ncc_batch(p, "asx_xcorr_ncc_debug_c_dev", d_source, 2 * N, d_sample, N, nullptr, 0, 1, min_energy, d_c,
+                     { d_lag, d_coef, d_ret, 1, d_peak }, stream);
 }
 
 static int ensure_staging(asx_plan *p, bool with64 = false) // with64: one pair's float64 inputs too (asx_xcorr_f64)

@@ -722,6 +722,34 @@ void asx_launch_pool_closure(const int64_t *lag, const double *coef, const int32
                              int min_confirm, int root, int32_t *votes, int64_t *best_lag, double *best_coef, int32_t *best_ret,
                              int32_t *best_entry, int32_t *confirm, int32_t *d_root, int64_t *offset, int32_t *support,
                              int32_t *placed, hipStream_t s);
+// Normalised cross-correlation (asx_xcorr_ncc_f32_dev; the k_ncc_* kernels, ncc.hip).  A track is cut into chunks of ASX_NCC_CHUNK
+// frames and the lags 0..N-1 into chunks of as many lags: the reduction trees follow from N alone.  The workspace of one NCC group
+// (plan-owned, lazy, whole or absent: asx_plan::Ncc): nsrc source and nsmp sample tracks -- the group's pairs, or 1 for the call's
+// broadcast track, whose moments the call's first group computes (do_src / do_smp) and the later ones read.
+#define ASX_NCC_CHUNK 2048
+#define ASX_NCC_STAT 4 // doubles per track: {mu, Vmax (source), Sy, Vy (sample)}
+__host__ __device__ inline uint32_t asx_ncc_chunks(uint32_t frames) { return (frames + ASX_NCC_CHUNK - 1) / ASX_NCC_CHUNK; }
+// a row of this call: 0 <= lag_min <= lag_max <= N-1
+__host__ __device__ inline bool asx_ncc_row_ok(int64_t lo, int64_t hi, uint32_t N) { return 0 <= lo && lo <= hi && hi <= (int64_t)N - 1; }
+struct AsxNccWs {
+    float *r;              // [pairs][2N] what the group's inverse pass left (run_group's r_out)
+    double2 *table;        // [nsrc][N] per lag {Sx' = sum of the window's frames minus mu, Vx}
+    double *raw, *m1, *m2; // chunk sums: source track t's at t * chunks(2N), sample track t's behind all of them at t * chunks(N)
+    double *sstat, *ystat; // [nsrc][ASX_NCC_STAT], [nsmp][ASX_NCC_STAT]
+    asx_peak_t *best;      // [pairs] the packed (|c32|, smallest lag) maximum; 0: no lag competes
+    uint32_t nsrc, nsmp;
+    bool do_src, do_smp;
+};
+// the moments of the group's tracks (those of do_src / do_smp): k_ncc_sums, k_ncc_moments, k_ncc_table
+void asx_launch_ncc_moments(const AsxNccWs &W, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch, uint32_t N,
+                            hipStream_t s);
+// k_ncc_peak and k_ncc_finalize: each pair's winner among the lags of its row (rows null: 0..N-1) to seg and peak; c_out: null, or
+// c32 of every lag ([pairs][N], NaN where the lag does not compete); scale: what r carries against the plain sum (F)
+void asx_launch_ncc_peak(const AsxNccWs &W, const float *r, size_t r_pitch, uint32_t N, double scale, double min_energy,
+                         const int64_t *rows, size_t rows_step, float *c_out, AsxSeg *seg, double *peak, int npairs, hipStream_t s);
+// behind the Pearson kernels: (0, NaN, NaN, -2) for every pair whose row is not a row of this call
+void asx_launch_ncc_invalid(uint32_t N, const int64_t *rows, size_t rows_step, int64_t *lag, double *coef, double *peak, int32_t *ret,
+                            int npairs, hipStream_t s);
 void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t s);
 unsigned asx_pearson_blocks(uint32_t basis_len); // partial blocks per pair: psums holds 6 doubles per block and pair
 // second look, DC removal: stats[0] = mean of source[0..2N), stats[1] = sum of sample[0..N), stats[2] = scale * stats[0] * stats[1]

@@ -1,0 +1,292 @@
+// csrc/ncc.hip — normalised cross-correlation (asx_xcorr_ncc_f32_dev): the k_ncc_* kernels, which turn the float32 r of lags 0..N-1
+// that an ordinary launch group left (run_group with r_out, asx_api.hip) into the Pearson coefficient of every lag and search its peak.
+// They know nothing of the transform layout: they read the caller's tracks, r and a plan-owned workspace (AsxNccWs).
+//
+// Everything behind r32 is float64, and every sum is a fixed tree that the track length alone decides: a track is cut into chunks of
+// ASX_NCC_CHUNK frames, a chunk is summed by one block (thread t takes the frames t, t + 256, ..., then lanes, then waves), the chunk
+// sums by thread-strided partial sums and the same block tree.  No value of a pair depends on the batch or on its place in it.
+//   k_ncc_sums     grid (source chunks + sample chunks, tracks): the plain sum of every chunk, for the means
+//   k_ncc_moments  same grid: mu (every block forms it from the chunk sums, in the same order), then sum (x - mu) and sum (x - mu)^2
+//                  of the chunk: an offset costs no digits
+//   k_ncc_table    grid (lag chunks + 1, tracks): block b < lag chunks owns the lags [b CHUNK, (b + 1) CHUNK): the window sums of its
+//                  first lag from whole chunk sums and the frames of the remainder, then a block scan of the sliding differences
+//                  (x[l + N] - mu)^k - (x[l] - mu)^k, k = 1, 2 -> the per-lag table {Sx' (mu-shifted), Vx} and the track's Vmax
+//                  (atomic maximum: order-free).  The extra block: Sy and Vy of the sample track.
+//   k_ncc_peak     grid (lag chunks, pairs): c32 of the block's lags, the window and the competing rule, the packed (|c32|, smallest
+//                  lag) maximum of the pair (asx_peak_t, atomic maximum); optionally c32 itself for the debug call
+//   k_ncc_finalize a thread per pair: AsxSeg through make_seg and the peak height
+//   k_ncc_invalid  a thread per pair, behind the Pearson kernels: (0, NaN, NaN, -2) for a row that is not a window of this call
+#include "asx_internal.h"
+#include "xcorr_dev.h"
+
+#define NCC_NT 256
+#define NCC_PER (ASX_NCC_CHUNK / NCC_NT)
+static_assert(ASX_NCC_CHUNK % NCC_NT == 0 && NCC_PER == 8, "eight frames per thread");
+
+// ---- block-wide float64 sums and scans: lanes (shuffles), then the four waves in index order ---------------------------------------
+__device__ __forceinline__ double ncc_wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// the sums of a and b over the block, in every thread; lds: 2 * (NCC_NT / 64) doubles
+__device__ __forceinline__ void ncc_block_sum2(double &a, double &b, double *lds)
+{
+    a = ncc_wave_sum(a);
+    b = ncc_wave_sum(b);
+    __syncthreads(); // (lds may still be read from the call before)
+    if ((threadIdx.x & 63) == 0) { lds[threadIdx.x >> 6] = a; lds[NCC_NT / 64 + (threadIdx.x >> 6)] = b; }
+    __syncthreads();
+    a = lds[0]; b = lds[NCC_NT / 64];
+#pragma unroll
+    for (int w = 1; w < NCC_NT / 64; w++) { a += lds[w]; b += lds[NCC_NT / 64 + w]; }
+}
+// the sums of a[0 .. n) and b[0 .. n) (b may be null: zero), in every thread
+__device__ __forceinline__ void ncc_sum_arrays(const double *__restrict__ a, const double *__restrict__ b, uint32_t n, double &sa,
+                                               double &sb, double *lds)
+{
+    sa = 0.0; sb = 0.0;
+    for (uint32_t i = threadIdx.x; i < n; i += NCC_NT) { sa += a[i]; if (b) sb += b[i]; }
+    ncc_block_sum2(sa, sb, lds);
+}
+
+// which track and chunk a block of the grid (source chunks + sample chunks, tracks) owns; false: none
+struct NccChunk {
+    const float *x;      // the track
+    uint32_t len, c, nc; // its length, the block's chunk, its chunks
+    size_t slot;         // where the chunk's sums go in raw / m1 / m2
+    double *stat;        // the track's statistics
+};
+__device__ __forceinline__ bool ncc_chunk_of(const AsxNccWs &W, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch,
+                                             uint32_t N, NccChunk &k)
+{
+    const uint32_t nsc = asx_ncc_chunks(2u * N), nyc = asx_ncc_chunks(N), t = blockIdx.y;
+    if (blockIdx.x < nsc) {
+        if (t >= W.nsrc || !W.do_src) return false;
+        k = { src + (size_t)t * src_pitch, 2u * N, blockIdx.x, nsc, (size_t)t * nsc + blockIdx.x, W.sstat + (size_t)t * ASX_NCC_STAT };
+    } else {
+        if (t >= W.nsmp || !W.do_smp) return false;
+        k = { smp + (size_t)t * smp_pitch, N, blockIdx.x - nsc, nyc, (size_t)W.nsrc * nsc + (size_t)t * nyc + (blockIdx.x - nsc),
+              W.ystat + (size_t)t * ASX_NCC_STAT };
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_ncc_sums(AsxNccWs W, const float *__restrict__ src, size_t src_pitch,
+                                                      const float *__restrict__ smp, size_t smp_pitch, uint32_t N)
+{
+    __shared__ double lds[2 * (NCC_NT / 64)];
+    NccChunk k;
+    if (!ncc_chunk_of(W, src, src_pitch, smp, smp_pitch, N, k)) return;
+    const uint32_t f0 = k.c * ASX_NCC_CHUNK;
+    double s = 0.0, z = 0.0;
+#pragma unroll
+    for (int j = 0; j < NCC_PER; j++) {
+        const uint32_t f = f0 + j * NCC_NT + threadIdx.x;
+        if (f < k.len) s += (double)k.x[f];
+    }
+    ncc_block_sum2(s, z, lds);
+    if (threadIdx.x == 0) {
+        W.raw[k.slot] = s;
+        if (k.c == 0 && blockIdx.x < asx_ncc_chunks(2u * N)) k.stat[1] = 0.0; // the source track's Vmax, which k_ncc_table raises
+    }
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_ncc_moments(AsxNccWs W, const float *__restrict__ src, size_t src_pitch,
+                                                         const float *__restrict__ smp, size_t smp_pitch, uint32_t N)
+{
+    __shared__ double lds[2 * (NCC_NT / 64)];
+    NccChunk k;
+    if (!ncc_chunk_of(W, src, src_pitch, smp, smp_pitch, N, k)) return;
+    double tot, z;
+    ncc_sum_arrays(W.raw + (k.slot - k.c), nullptr, k.nc, tot, z, lds);
+    const double mu = tot / (double)k.len;
+    const uint32_t f0 = k.c * ASX_NCC_CHUNK;
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < NCC_PER; j++) {
+        const uint32_t f = f0 + j * NCC_NT + threadIdx.x;
+        if (f < k.len) { const double a = (double)k.x[f] - mu; s1 += a; s2 += a * a; }
+    }
+    ncc_block_sum2(s1, s2, lds);
+    if (threadIdx.x == 0) {
+        W.m1[k.slot] = s1;
+        W.m2[k.slot] = s2;
+        if (k.c == 0) k.stat[0] = mu;
+    }
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_ncc_table(AsxNccWs W, const float *__restrict__ src, size_t src_pitch, uint32_t N)
+{
+    __shared__ double lds[2 * (NCC_NT / 64)];
+    __shared__ float head[ASX_NCC_CHUNK], tail[ASX_NCC_CHUNK];
+    const uint32_t nsc = asx_ncc_chunks(2u * N), nyc = asx_ncc_chunks(N), t = blockIdx.y;
+    const double dN = (double)N;
+    if (blockIdx.x == nyc) {
+        // the sample track: Sy and Vy about its own mean
+        if (t >= W.nsmp || !W.do_smp) return;
+        const size_t at = (size_t)W.nsrc * nsc + (size_t)t * nyc;
+        double s1, s2;
+        ncc_sum_arrays(W.m1 + at, W.m2 + at, nyc, s1, s2, lds);
+        if (threadIdx.x == 0) {
+            double *st = W.ystat + (size_t)t * ASX_NCC_STAT;
+            st[2] = s1 + dN * st[0];
+            st[3] = s2 - s1 * s1 / dN;
+        }
+        return;
+    }
+    if (t >= W.nsrc || !W.do_src) return;
+    const float *x = src + (size_t)t * src_pitch;
+    double *st = W.sstat + (size_t)t * ASX_NCC_STAT;
+    const double mu = st[0];
+    const uint32_t b = blockIdx.x, l0 = b * ASX_NCC_CHUNK;
+    // the block's frames: [l0, l0 + CHUNK) leave the window one by one, [l0 + N, l0 + N + CHUNK) enter it (zero past the track's end:
+    // only lags >= N would read them)
+#pragma unroll
+    for (int j = 0; j < NCC_PER; j++) {
+        const uint32_t i = j * NCC_NT + threadIdx.x, f = l0 + i, e = l0 + N + i;
+        head[i] = f < 2u * N ? x[f] : 0.f;
+        tail[i] = e < 2u * N ? x[e] : 0.f;
+    }
+    // the window [l0, l0 + N) of the block's first lag: K whole chunks from chunk b on, then R frames
+    const uint32_t K = N / ASX_NCC_CHUNK, R = N % ASX_NCC_CHUNK;
+    double w1, w2;
+    ncc_sum_arrays(W.m1 + (size_t)t * nsc + b, W.m2 + (size_t)t * nsc + b, K, w1, w2, lds);
+    {
+        double r1 = 0.0, r2 = 0.0;
+        const uint32_t f0 = l0 + K * ASX_NCC_CHUNK;
+        for (uint32_t i = threadIdx.x; i < R; i += NCC_NT) { const double a = (double)x[f0 + i] - mu; r1 += a; r2 += a * a; }
+        ncc_block_sum2(r1, r2, lds); // (its first barrier also puts head and tail in place)
+        w1 += r1; w2 += r2;
+    }
+    // the thread's eight consecutive lags l0 + 8 tid + k: exclusive prefix of the sliding differences inside the thread, ...
+    double p1[NCC_PER], p2[NCC_PER], t1 = 0.0, t2 = 0.0;
+    const uint32_t j0 = threadIdx.x * NCC_PER;
+#pragma unroll
+    for (int k = 0; k < NCC_PER; k++) {
+        p1[k] = t1; p2[k] = t2;
+        const double in = (double)tail[j0 + k] - mu, out = (double)head[j0 + k] - mu;
+        t1 += in - out;
+        t2 += in * in - out * out;
+    }
+    // ... across the lanes (an inclusive scan of the threads' totals), across the waves
+    double i1 = t1, i2 = t2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double u1 = __shfl_up(i1, off, 64), u2 = __shfl_up(i2, off, 64);
+        if (lane >= off) { i1 += u1; i2 += u2; }
+    }
+    __syncthreads();
+    if (lane == 63) { lds[wave] = i1; lds[NCC_NT / 64 + wave] = i2; }
+    __syncthreads();
+    double o1 = __shfl_up(i1, 1, 64), o2 = __shfl_up(i2, 1, 64); // exclusive in the wave
+    if (lane == 0) { o1 = 0.0; o2 = 0.0; }
+    for (int w = 0; w < wave; w++) { o1 += lds[w]; o2 += lds[NCC_NT / 64 + w]; }
+    double vmax = 0.0;
+    double2 *tab = W.table + (size_t)t * N;
+#pragma unroll
+    for (int k = 0; k < NCC_PER; k++) {
+        const uint32_t l = l0 + j0 + k;
+        if (l < N) {
+            const double s1 = w1 + (o1 + p1[k]), s2 = w2 + (o2 + p2[k]);
+            const double vx = s2 - s1 * s1 / dN;
+            tab[l] = make_double2(s1, vx);
+            vmax = fmax(vmax, vx); // (a NaN drops out)
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, off, 64));
+    // non-negative doubles order as their bits do
+    if (lane == 0 && vmax > 0.0) atomicMax(reinterpret_cast<unsigned long long *>(st + 1), (unsigned long long)__double_as_longlong(vmax));
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_ncc_peak(AsxNccWs W, const float *__restrict__ r, size_t r_pitch, uint32_t N, double scale,
+                                                      double min_energy, const int64_t *__restrict__ rows, size_t rows_step,
+                                                      float *__restrict__ c_out)
+{
+    __shared__ asx_peak_t red[NCC_NT / 64];
+    const size_t pair = blockIdx.y;
+    const size_t ts = W.nsrc > 1 ? pair : 0, ty = W.nsmp > 1 ? pair : 0;
+    const double *sx = W.sstat + ts * ASX_NCC_STAT, *sy = W.ystat + ty * ASX_NCC_STAT;
+    const double mu = sx[0], floor_v = min_energy * sx[1], Sy = sy[2], Vy = sy[3], dN = (double)N;
+    int64_t lo = 0, hi = (int64_t)N - 1;
+    if (rows) {
+        lo = rows[2 * pair * rows_step]; hi = rows[2 * pair * rows_step + 1];
+        if (!asx_ncc_row_ok(lo, hi, N)) hi = -1; // holds no lag
+    }
+    const double2 *tab = W.table + ts * N;
+    const float *rp = r + pair * r_pitch;
+    const uint32_t l0 = blockIdx.x * ASX_NCC_CHUNK;
+    asx_peak_t best = 0;
+#pragma unroll 2
+    for (int j = 0; j < NCC_PER; j++) {
+        const uint32_t l = l0 + j * NCC_NT + threadIdx.x;
+        if (l >= N) break;
+        const double2 e = tab[l];
+        const double Sx = e.x + dN * mu;
+        const double c = ((double)rp[l] / scale - Sx * Sy / dN) / sqrt(e.y * Vy);
+        const float c32 = (float)c;
+        const bool competes = Vy > 0.0 && e.y >= floor_v && fabs(c) <= 1.7976931348623157e308; // (false for a NaN and for +-infinity)
+        if (c_out) c_out[pair * (size_t)N + l] = competes ? c32 : NAN;
+        if (competes && (int64_t)l >= lo && (int64_t)l <= hi) best = peak_max(best, peak_pack_key(fabsf(c32), l));
+    }
+    best = block_peak_max(best, red);
+    if (threadIdx.x == 0 && best) atomicMax(&W.best[pair], best);
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_ncc_finalize(AsxNccWs W, uint32_t N, const int64_t *__restrict__ rows, size_t rows_step,
+                                                          AsxSeg *__restrict__ seg, double *__restrict__ peak, int npairs)
+{
+    const int pair = blockIdx.x * NCC_NT + threadIdx.x;
+    if (pair >= npairs) return;
+    const asx_peak_t best = W.best[pair];
+    uint32_t first = 0; // no lag competes: the window's lag_min (an invalid row: 0, and k_ncc_invalid writes its results)
+    if (rows) {
+        const int64_t lo = rows[2 * (size_t)pair * rows_step], hi = rows[2 * (size_t)pair * rows_step + 1];
+        if (asx_ncc_row_ok(lo, hi, N)) first = (uint32_t)lo;
+    }
+    seg[pair] = make_seg(best ? peak_index(best) : first, N);
+    peak[pair] = best ? (double)peak_key(best) : 0.0;
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_ncc_invalid(uint32_t N, const int64_t *__restrict__ rows, size_t rows_step,
+                                                         int64_t *__restrict__ lag, double *__restrict__ coef, double *__restrict__ peak,
+                                                         int32_t *__restrict__ ret, int npairs)
+{
+    const int pair = blockIdx.x * NCC_NT + threadIdx.x;
+    if (pair >= npairs) return;
+    if (asx_ncc_row_ok(rows[2 * (size_t)pair * rows_step], rows[2 * (size_t)pair * rows_step + 1], N)) return;
+    if (lag) lag[pair] = 0;
+    coef[pair] = (double)NAN;
+    peak[pair] = (double)NAN;
+    ret[pair] = -2;
+}
+
+// ---- launchers ----------------------------------------------------------------------------------------------------------------------
+void asx_launch_ncc_moments(const AsxNccWs &W, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch, uint32_t N,
+                            hipStream_t s)
+{
+    if (!W.do_src && !W.do_smp) return;
+    const unsigned nsc = asx_ncc_chunks(2u * N), nyc = asx_ncc_chunks(N), nt = W.nsrc > W.nsmp ? W.nsrc : W.nsmp;
+    hipLaunchKernelGGL(k_ncc_sums, dim3(nsc + nyc, nt), dim3(NCC_NT), 0, s, W, src, src_pitch, smp, smp_pitch, N);
+    hipLaunchKernelGGL(k_ncc_moments, dim3(nsc + nyc, nt), dim3(NCC_NT), 0, s, W, src, src_pitch, smp, smp_pitch, N);
+    hipLaunchKernelGGL(k_ncc_table, dim3(nyc + 1, nt), dim3(NCC_NT), 0, s, W, src, src_pitch, N);
+}
+
+void asx_launch_ncc_peak(const AsxNccWs &W, const float *r, size_t r_pitch, uint32_t N, double scale, double min_energy,
+                         const int64_t *rows, size_t rows_step, float *c_out, AsxSeg *seg, double *peak, int npairs, hipStream_t s)
+{
+    (void)hipMemsetAsync(W.best, 0, (size_t)npairs * sizeof(asx_peak_t), s);
+    hipLaunchKernelGGL(k_ncc_peak, dim3(asx_ncc_chunks(N), npairs), dim3(NCC_NT), 0, s, W, r, r_pitch, N, scale, min_energy, rows, rows_step,
+                       c_out);
+    hipLaunchKernelGGL(k_ncc_finalize, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, W, N, rows, rows_step, seg, peak, npairs);
+}
+
+void asx_launch_ncc_invalid(uint32_t N, const int64_t *rows, size_t rows_step, int64_t *lag, double *coef, double *peak, int32_t *ret,
+                            int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_ncc_invalid, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, N, rows, rows_step, lag, coef, peak, ret,
+                       npairs);
+}

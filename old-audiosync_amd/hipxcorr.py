@@ -63,6 +63,8 @@ _HEADER_SIGNATURES = {
     "asx_xcorr_windowed_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "asx_xcorr_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _int, _i64, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_ncc_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_ncc_debug_c_dev": (_int, [_vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_band_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_sub_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -140,6 +142,7 @@ TRACK_HALF_MAX = 64  # ASX_TRACK_HALF_MAX, include/audiosync/xcorr_hip.h
 TRACK_SEG_MAX = 64   # ASX_TRACK_SEG_MAX, include/audiosync/xcorr_hip.h
 WARP_DRIFT_MAX = 2.0 ** -6  # ASX_WARP_DRIFT_MAX, include/audiosync/xcorr_hip.h
 CLOSURE_LAG_MAX = 1 << 40   # ASX_CLOSURE_LAG_MAX, include/audiosync/xcorr_hip.h
+NCC_MIN_ENERGY = 1e-6       # ASX_NCC_MIN_ENERGY, include/audiosync/xcorr_hip.h
 
 
 class AsxError(RuntimeError):
@@ -496,6 +499,22 @@ def windowed_args(n, source, sample, windows):
     window_stride) as contiguous float32 / int64 arrays and strides in elements / rows.  ValueError on anything else.  The rows'
     values are not checked: a row that is not a window comes back as (0, NaN, -2)."""
     return _strided_args(n, source, sample, _window_rows(windows))
+
+
+def _energy_option(min_energy):
+    """-> min_energy as a float; ValueError unless it is a real number (no bool) with NCC_MIN_ENERGY <= min_energy <= 1"""
+    if isinstance(min_energy, bool) or not isinstance(min_energy, (int, float, np.integer, np.floating)) or \
+            not NCC_MIN_ENERGY <= float(min_energy) <= 1.0:
+        raise ValueError("min_energy must be a number in [%g, 1], not %r" % (NCC_MIN_ENERGY, min_energy))
+    return float(min_energy)
+
+
+def ncc_args(n, source, sample, windows=None, min_energy=1e-3):
+    """Host checks of Plan.xcorr_ncc_f32: the shapes of windowed_args (windows=None: every lag 0..N-1, no rows) and
+    NCC_MIN_ENERGY <= min_energy <= 1.  -> (source, sample, windows or None, batch, source_stride, sample_stride, window_stride,
+    min_energy).  ValueError on anything else.  The rows' values are not checked: a row outside [0, N-1] comes back as ret = -2."""
+    option = _energy_option(min_energy)
+    return _strided_args(n, source, sample, None if windows is None else _window_rows(windows)) + (option,)
 
 
 def topk_args(n, source, sample, k, min_separation, windows=None):
@@ -1042,6 +1061,19 @@ class Plan:
                                             int(window_stride), int(batch), d_lag or None, d_coef or None, d_peak or None,
                                             d_ret or None, stream or None))
 
+    def xcorr_ncc_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, min_energy, d_lag, d_coef, d_peak,
+                      d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_ncc_f32_dev -- the strided batch with the lags 0..N-1 ranked by the Pearson
+        coefficient itself; d_windows = 0: every lag 0..N-1, else per-pair rows inside [0, N-1]; peak: |c32[lag]|"""
+        _check(lib().asx_xcorr_ncc_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride), d_windows or None,
+                                           int(window_stride), int(batch), float(min_energy), d_lag or None, d_coef or None,
+                                           d_peak or None, d_ret or None, stream or None))
+
+    def ncc_debug_c_dev(self, d_src, d_smp, min_energy, d_c, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """asx_xcorr_ncc_debug_c_dev: one contiguous pair, c32 of lags 0..N-1 to d_c (NaN where the lag does not compete)"""
+        _check(lib().asx_xcorr_ncc_debug_c_dev(self._h, d_src or None, d_smp or None, float(min_energy), d_c or None, d_lag or None,
+                                               d_coef or None, d_peak or None, d_ret or None, stream or None))
+
     def phat_debug_r_dev(self, d_src, d_smp, d_r, d_lag, d_coef, d_peak, d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_phat_debug_r_dev -- one contiguous pair, r_phat of all 2N lags (times F) to d_r"""
         _check(lib().asx_xcorr_phat_debug_r_dev(self._h, d_src or None, d_smp or None, d_r or None, d_lag or None, d_coef or None,
@@ -1456,6 +1488,16 @@ class Plan:
         s, t, w, batch, ss, ts, ws, k, sep = topk_args(self.sample_len, source, sample, k, min_separation, windows)
         return self._staged((s, t, w), (batch, k), _RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_topk_dev(
             d_s, ss, d_t, ts, d_w, ws, batch, k, sep, *d_out))
+
+    def xcorr_ncc_f32(self, source, sample, windows=None, min_energy=1e-3):
+        """Pairs ranked by the normalised cross-correlation (asx_xcorr_ncc_f32_dev): the Pearson coefficient of every lag 0..N-1.
+        source: float32 [2N] or [B, 2N]; sample: [N] or [B, N]; a 1-D operand serves every pair.  windows: None (every lag 0..N-1),
+        or integers [2] / [B, 2] rows inside [0, N-1].  min_energy: the share of the loudest window's energy below which a lag does
+        not compete.  Arguments are checked on the host (ValueError) before anything is uploaded.  Returns (lag int64[B], coef
+        float64[B], peak float64[B], ret int32[B]): peak is |c32[lag]|, coef the reference's coefficient of the samples there."""
+        s, t, w, batch, ss, ts, ws, me = ncc_args(self.sample_len, source, sample, windows, min_energy)
+        return self._staged((s, t, w), (batch,), _PHAT_RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_ncc_dev(
+            d_s, ss, d_t, ts, d_w, ws, batch, me, *d_out))
 
     def xcorr_phat_band_f32(self, source, sample, bin_lo, bin_hi, windows=None):
         """xcorr_phat_f32 in which only bins bin_lo..bin_hi of the 2N-point transform vote (asx_xcorr_phat_band_f32_dev; band_bins
