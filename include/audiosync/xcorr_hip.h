@@ -32,15 +32,17 @@
  *   window was not a window inside [-N, N-1]; lag[i] = 0 and coef[i] = NaN.  (asx_xcorr_curve_f32_dev and
  *   asx_xcorr_pool_curve_f32_dev: an entry's centre was not a lag inside [-N, N-1]; NaN in all its values.  The same in
  *   asx_xcorr_track_f32_dev and asx_xcorr_pool_track_f32_dev, with used = 0.  asx_xcorr_ncc_f32_dev with rows: the row was not a
- *   window inside [0, N-1]; peak[i] = NaN too.)
+ *   window inside [0, N-1]; peak[i] = NaN too.  The same in asx_xcorr_ncc_topk_f32_dev, asx_xcorr_pool_ncc_f32_dev and
+ *   asx_xcorr_pool_ncc_topk_f32_dev, in all k entries.)
  *   ret = -3 (asx_xcorr_topk_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_phat_topk_f32_dev and
  *   asx_xcorr_pool_phat_topk_f32_dev only): no lag is left for
  *   this entry of the pair (its window minus the zones around the earlier entries is empty);
- *   lag = 0 and coef = NaN.
+ *   lag = 0 and coef = NaN.  (asx_xcorr_ncc_topk_f32_dev and asx_xcorr_pool_ncc_topk_f32_dev too: peak = NaN as well.)
  *   ret = -4 (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_pool_phat_f32_dev,
  *   asx_xcorr_pool_phat_sub_f32_dev and asx_xcorr_pool_phat_topk_f32_dev only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
  *   form: in all k entries of the pair).  It takes precedence over -2 and -3.  (asx_xcorr_pool_curve_f32_dev: NaN in all
- *   the values of the pair's entries.  asx_xcorr_pool_track_f32_dev: the same, with used = 0.)
+ *   the values of the pair's entries.  asx_xcorr_pool_track_f32_dev: the same, with used = 0.  asx_xcorr_pool_ncc_f32_dev and
+ *   asx_xcorr_pool_ncc_topk_f32_dev: lag = 0, coef = NaN and peak = NaN, in all k entries.)
  *   ret = -5 (asx_xcorr_warp_f32_dev and asx_xcorr_pool_warp_f32_dev only): an entry's drift line is not valid; NaN in all its
  *   values and len = 0.  In these two calls -4 and -2 mean what they mean in the calls around given lags and take precedence, in
  *   that order.
@@ -414,8 +416,9 @@ int asx_xcorr_phat_f32_dev(asx_plan *plan, const float *d_source, size_t source_
  * most 1 GiB (or one pair's 24N bytes).
  *   Cost: the transforms of the strided call with every inverse tile in its general form (r is written out), three passes over the
  * tracks for the moments and one over r and the table (measured: DESIGN.md).
- *   Not offered: negative lags, pools, top-k, a neighbourhood or fractional lag (asx_xcorr_curve_f32_dev serves the returned lag),
- * the double ABI, streams, and a fused inverse pass. */
+ *   Not offered: negative lags, a neighbourhood or fractional lag (asx_xcorr_curve_f32_dev serves the returned lag), the double
+ * ABI, streams, and a fused inverse pass.  Offered as calls of their own, below: top-k (asx_xcorr_ncc_topk_f32_dev) and pools
+ * (asx_xcorr_pool_ncc_f32_dev, asx_xcorr_pool_ncc_topk_f32_dev). */
 #define ASX_NCC_MIN_ENERGY 1e-6
 int asx_xcorr_ncc_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
                           const float *d_sample, size_t sample_stride,
@@ -426,6 +429,81 @@ int asx_xcorr_ncc_f32_dev(asx_plan *plan, const float *d_source, size_t source_s
  * compete); the results are those of asx_xcorr_ncc_f32_dev for that pair without rows */
 int asx_xcorr_ncc_debug_c_dev(asx_plan *plan, const float *d_source, const float *d_sample, double min_energy,
                               float *d_c, int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
+/* The K strongest separated lags of the coefficient curve per pair.  The true offset can be the third-best normalised peak (a
+ * quiet copy of the sample next to louder ones, with a level step that the raw top-k call ranks first): this call returns it.
+ *   c[l], c32[l], Vmax, min_energy, which lags compete and the row rule 0 <= lag_min <= lag_max <= N-1 are those of
+ * asx_xcorr_ncc_f32_dev, word for word; Vmax is over all lags 0..N-1, whatever the window and the zones.  Inputs, strides,
+ * broadcast, the layout rule, the stream rule and d_windows are that call's too; the call runs on every plan.
+ *   Outputs.  Entry j (0-based) of pair i is at index i*k + j of d_lag, d_coef, d_peak and d_ret.  1 <= k <= ASX_TOPK_MAX (8) and
+ * min_separation >= 0.
+ *   The rule.  A_0 is the set of lags of the pair's row: 0..N-1 when there are no rows (the plan's window is ignored, as in the NCC
+ * call).  A_j is A_0 minus every lag l with |l - lag_i| <= min_separation for an earlier entry i < j.
+ *   Entry j, when A_j holds a competing lag: the largest |c32| among the competing lags of A_j wins, the smallest lag among equal
+ * float32 values; there is no signed seed.  peak = (double)|c32[lag]|.  coef is the direct Pearson form at that lag: under
+ * asx_plan_set_pearson(plan, 0) bit for bit what asx_xcorr_windowed_f32_dev returns for the row [lag, lag].  ret is 0, or -1 for a
+ * NaN coefficient.
+ *   Entry j, when A_j is not empty but no lag of it competes: lag = the smallest lag of A_j, peak = 0, coef and ret as above.  The
+ * zone around that lag is taken like any other.  (What the NCC call does for entry 0, and the PHAT top-k call for a silent pair.)
+ *   Entry j, when A_j is empty: entry j and every later entry are (0, NaN, peak NaN, -3).
+ *   A row that is not a row of this call gives (0, NaN, NaN, -2) in all k entries.  The other pairs are untouched, bit for bit.
+ * ret is never 1.
+ *   k = 1 launches exactly asx_xcorr_ncc_f32_dev.  Entry 0 is always bit for bit the k = 1 result.  It is the float32 argmax of each
+ * pass, NOT the float64 argmax by construction, as the NCC call states for its one pass.
+ *   Refusals: those of asx_xcorr_ncc_f32_dev (a NULL plan, track, d_coef, d_peak or d_ret, min_energy out of range, the layout rule,
+ * the first allocation inside a stream capture), and k or min_separation out of range: -1 with nothing launched and the outputs
+ * untouched.  d_lag may be NULL.  batch == 0 returns 0.
+ *   What the call never does is what the NCC call never does: no listing, no second look, no counters, no host synchronisation.  It
+ * behaves the same whatever asx_plan_set_exact, asx_plan_set_pearson, asx_plan_set_prune and asx_plan_set_qstore say, and leaves
+ * asx_plan_workspace_bytes unchanged.  Once the plan's NCC set exists the call is asynchronous and capturable.
+ *   Memory and cost.  The first pass forms c32 of every lag anyway; it is kept in the upper half of the group's r (the negative lags,
+ * which no NCC kernel reads), so the set's size rule is that of asx_xcorr_ncc_f32_dev, plus 80 bytes per pair.  Every further entry
+ * rescans those 4N bytes per pair with the row and at most 7 zones masked, and runs one direct Pearson pass: no further inverse
+ * transform, and no dependence on the height of the runner-up (measured: DESIGN.md). */
+int asx_xcorr_ncc_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                               const float *d_sample, size_t sample_stride,
+                               const int64_t *d_windows, size_t window_stride, size_t batch,
+                               double min_energy, int k, int64_t min_separation,
+                               int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
+/* Normalised cross-correlation over listed pairs of two track pools.  All-pairs over C clips is C^2 pairs but only C sources and C
+ * samples: here every track's transform (the bank) AND its moments -- the per-lag table {Sx, Vx} and Vmax of a source track, {mu, Sy,
+ * Vy} of a sample track -- are formed once per call, not once per pair.
+ *   Everything before `batch` means what it means in asx_xcorr_pool_f32_dev: aliasing pools, strides below the track length,
+ * d_pairs == NULL = every combination, source-major; the layout and stream rules are the same, and the bank is filled once per call
+ * with the same growth rule.  Real-column plans only.  d_windows == NULL means every lag 0..N-1; otherwise per-pair rows under the NCC
+ * call's rule 0 <= lag_min <= lag_max <= N-1.  min_energy, the curve, which lags compete, the peak and the outputs per pair are those
+ * of asx_xcorr_ncc_f32_dev.
+ *   Per pair inside its pools, the results are bit for bit those of asx_xcorr_ncc_f32_dev for that pair alone on the same plan: the
+ * bank gives the same float32 Q, so the same r32, and the moment trees are fixed by N.
+ *   A pool index outside its pool gives (0, NaN, NaN, -4).  It takes precedence over -2, and nothing outside the pools is read.  The
+ * other pairs are untouched, bit for bit.  ret is never 1.
+ *   Refusals: every refusal of asx_xcorr_pool_f32_dev, plus the NCC call's (min_energy out of range, a NULL d_peak): -1, nothing
+ * launched, outputs untouched.  batch == 0 returns 0.
+ *   Memory.  Beside the bank and the NCC set, the plan keeps a track set sized by the pools: 16N bytes per source track, plus the
+ * chunk sums (three doubles per 2048 frames of every track) and four doubles per track.  It is allocated at the first pool NCC call
+ * and grows like the bank: everything is reallocated behind a device synchronisation when a call names more tracks, never inside a
+ * stream capture (such a call returns -1; make one call with pools at least this large outside the capture first).  It is not
+ * counted in asx_plan_workspace_bytes.  Once its sets exist the call is asynchronous and capturable.
+ *   What the call never does is what the NCC call never does. */
+int asx_xcorr_pool_ncc_f32_dev(asx_plan *plan, const float *d_sources, size_t source_stride, size_t nsources,
+                               const float *d_samples, size_t sample_stride, size_t nsamples,
+                               const int32_t *d_pairs, const int64_t *d_windows, size_t window_stride, size_t batch,
+                               double min_energy,
+                               int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
+/* ... with the K strongest separated lags per pair: the rule and the outputs of asx_xcorr_ncc_topk_f32_dev over the pairs of
+ * asx_xcorr_pool_ncc_f32_dev.  k = 1 launches exactly asx_xcorr_pool_ncc_f32_dev, and entry 0 is always bit for bit the k = 1 result.
+ * For a pair inside its pools, all k entries are bit for bit those of asx_xcorr_ncc_topk_f32_dev for that pair alone on the same plan.
+ * A pool index outside its pool gives (0, NaN, NaN, -4) in all k entries; it takes precedence over -2 and -3.  Refusals: those of the
+ * pool call above plus k and min_separation out of range.  The bank and the track set are filled once per call whatever k is.
+ *   The [C][C][k] tables of an all-pairs call have the layout asx_pool_closure_dev takes, but feeding them to it is not offered: this
+ * curve holds the lags 0..N-1 only, so a pair whose true lag is negative has no entry to offer. */
+int asx_xcorr_pool_ncc_topk_f32_dev(asx_plan *plan, const float *d_sources, size_t source_stride, size_t nsources,
+                                    const float *d_samples, size_t sample_stride, size_t nsamples,
+                                    const int32_t *d_pairs, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                    double min_energy, int k, int64_t min_separation,
+                                    int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
 
 /* Band-limited GCC-PHAT: asx_xcorr_phat_f32_dev in which only the bins of a frequency band vote.  Most material is band-limited
  * (speech, codecs that low-pass, hum and rumble at the bottom): outside its band the cross spectrum is rounding noise, and with

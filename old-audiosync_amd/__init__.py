@@ -15,5 +15,5 @@ from .hipxcorr import (  # noqa: F401
     LIB_PATH, AsxError, Plan, Stream, abi_version, device_count, lib, pearson_f64, planmath_candidates, planmath_describe, planmath_group_form, planmath_kernel_table, planmath_kernels,
     planmath_table, planmath_twiddles, band_bins, results_to_ms_dev, synth_pairs_dev, topk_best_dev, xcorr_batch_multi,
     Comm, PinnedArray, result_bytes, shard_range, closure_args, pool_closure, pool_closure_dev, phat_topk_args, pool_phat_topk_args,
-    NCC_MIN_ENERGY, ncc_args,
+    NCC_MIN_ENERGY, ncc_args, ncc_topk_args, pool_ncc_args, pool_ncc_topk_args,
 )

@@ -117,8 +117,9 @@ struct asx_plan {
     hipStream_t stream = nullptr;
     std::mutex lock;
 
-    // Who owns the plan's device memory (asx_plan_workspace_bytes: all but the bank's and the NCC set's).  mem: what plan_init takes and, once created,
-    // the lazy sets (big, bslot, st, st64: whole or absent); cxy0: lane 0's C_x / C_y, which tune_placement may replace; bank.mem; ncc.mem.
+    // Who owns the plan's device memory (asx_plan_workspace_bytes: all but the bank's and the NCC sets').  mem: what plan_init takes and, once created,
+    // the lazy sets (big, bslot, st, st64: whole or absent); cxy0: lane 0's C_x / C_y, which tune_placement may replace; bank.mem; ncc.mem;
+    // ncc.tmem.
     AsxMemSet mem{ hip_mem }, cxy0{ hip_mem };
     // "Lanes": each owns the workspaces of one launch group and a stream.  With two lanes
     // (ASX_LANES=2) consecutive groups of a batch alternate lanes so that kernels of different
@@ -166,10 +167,18 @@ struct asx_plan {
     // Normalised cross-correlation (asx_xcorr_ncc_f32_dev; lazy, whole or absent, allocated at the plan's first such call): r of every
     // lag of one NCC group, the per-lag tables of its source tracks and the small sums (AsxNccWs).  group <= the plan's: the set is
     // bounded by ASX_NCC_WS_BYTES (or one pair's share where that is larger).  Its own set: not part of asx_plan_workspace_bytes.
+    // The pool calls' track set (asx_xcorr_pool_ncc_f32_dev; lazy, whole or absent, grown like the bank and like it replaced wholesale):
+    // the per-lag table, the chunk sums and the statistics of nsrc source and nsmp sample tracks, in the AsxNccWs pointers of those
+    // names (`tracks`: its r, best and tk stay null).  Its own set too.  built_*: source tables and sample moment sets formed over
+    // the plan's life, by every NCC call (host-side counts: asx_plan_debug_ncc).
     struct Ncc {
         AsxNccWs w{};
         AsxMemSet mem{ hip_mem };
         size_t group = 0;
+        AsxNccWs tracks{};
+        AsxMemSet tmem{ hip_mem };
+        size_t nsrc = 0, nsmp = 0;
+        unsigned long long built_src = 0, built_smp = 0;
     } ncc;
     // pairs whose near-tie list overflowed since the list was last emptied (k_finalize appends, resolve_overflows reads)
     uint32_t *over_list = nullptr, *over_n = nullptr;
@@ -1050,7 +1059,8 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     if (call.kind == AsxSearch::ROWS && K == 1) asx_launch_invalid_rows(call.rows, P.N, y.lag, y.coef, y.ret, (int)g, s);
     // a pool pair with an index outside its pool: (0, NaN, -4), which takes precedence over -2 (a PHAT group: and a NaN peak over the 0
     // that k_phat_finalize wrote for its empty maximum)
-    if (pl && K == 1) asx_launch_invalid_pairs(pl, y.lag, y.coef, y.ret, y.peak, (int)g, s);
+    // (a pool group of an NCC call ends behind its inverse pass: ncc_batch writes that pair's entries behind its own last pass)
+    if (pl && K == 1 && !o.transforms_only) asx_launch_invalid_pairs(pl, y.lag, y.coef, y.ret, y.peak, (int)g, s);
     // Passes 2..k over the same Q; the transforms are not run again.  In a pool group the passes read the pairs' inputs through the
     // group's records (the listed kernels), and an invalid pair -- whose Q is NaN and whose bound is zero, so that no pass finds or
     // lists anything for it -- gets (0, NaN, -4) in all k entries behind the last step, over the steps' -2 and -3.
@@ -1574,6 +1584,39 @@ static int ensure_bank(asx_plan *p, const char *fn, size_t nsrc, size_t nsmp, hi
     return 0;
 }
 
+// What every pool call checks of its pools and pairs behind its null checks; 0, or -1 with the message
+static int pool_layout(asx_plan *p, const char *fn, const float *d_sources, size_t source_stride, size_t nsources, const float *d_samples,
+                       size_t sample_stride, size_t nsamples, const int32_t *d_pairs, size_t batch)
+{
+    const AsxDev &P = p->dev;
+    if (P.rlayout != 1) return fail("%s: pool calls need a real-column plan (asx_plan_layout() == 1)", fn);
+    if (((uintptr_t)d_sources & 15u) || ((uintptr_t)d_samples & 15u))
+        return fail("%s: the pools must be 16-byte aligned (sources %p, samples %p)", fn, (const void *)d_sources, (const void *)d_samples);
+    if ((source_stride & 3u) || (sample_stride & 3u))
+        return fail("%s: strides must be multiples of 4 floats (source_stride %zu, sample_stride %zu)", fn, source_stride, sample_stride);
+    if (nsources > INT32_MAX || nsamples > INT32_MAX) return fail("%s: a pool of more than 2^31 - 1 tracks", fn);
+    if (!d_pairs && batch != nsources * nsamples)
+        return fail("%s: without pairs the batch is every combination, %zu x %zu, not %zu", fn, nsources, nsamples, batch);
+    if (batch != 0 && (nsources == 0 || nsamples == 0))
+        return fail("%s: an empty pool (%zu sources, %zu samples) for %zu pairs", fn, nsources, nsamples, batch);
+    return 0;
+}
+
+// the bank fill: every track's forward column pass, once per call, on the caller's stream before any lane forks (grid.z: at most
+// 65535 tracks per launch)
+static void pool_fill(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources, const float *d_samples,
+                      size_t sample_stride, size_t nsamples, hipStream_t s)
+{
+    const AsxDev &P = p->dev;
+    for (int op = 0; op < 2; op++) {
+        const size_t n = op ? nsamples : nsources;
+        for (size_t c0 = 0; c0 < n; c0 += 65535)
+            asx_launch_fwd_cols_r(P, op ? nullptr : d_sources, source_stride, op ? d_samples : nullptr, sample_stride, c0,
+                                  (int)std::min<size_t>(65535, n - c0), p->bank.c, true, s);
+    }
+    p->bank.fills++;
+}
+
 // asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev and asx_xcorr_pool_phat_f32_dev (fn: the entry point's name for the messages; y
 // and topk: the top-k call's entry stride and option, after its own checks of k and min_separation; weight and band: the PHAT call's,
 // after band_weight)
@@ -1586,27 +1629,10 @@ static int pool_batch(asx_plan *p, const char *fn, const float *d_sources, size_
     PlanCall c(p, stream);
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
     hipStream_t s = c.s;
-    const AsxDev &P = p->dev;
-    if (P.rlayout != 1) return fail("%s: pool calls need a real-column plan (asx_plan_layout() == 1)", fn);
-    if (((uintptr_t)d_sources & 15u) || ((uintptr_t)d_samples & 15u))
-        return fail("%s: the pools must be 16-byte aligned (sources %p, samples %p)", fn, (const void *)d_sources, (const void *)d_samples);
-    if ((source_stride & 3u) || (sample_stride & 3u))
-        return fail("%s: strides must be multiples of 4 floats (source_stride %zu, sample_stride %zu)", fn, source_stride, sample_stride);
-    if (nsources > INT32_MAX || nsamples > INT32_MAX) return fail("%s: a pool of more than 2^31 - 1 tracks", fn);
-    if (!d_pairs && batch != nsources * nsamples)
-        return fail("%s: without pairs the batch is every combination, %zu x %zu, not %zu", fn, nsources, nsamples, batch);
+    if (pool_layout(p, fn, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, batch)) return -1;
     if (batch == 0) return 0;
-    if (nsources == 0 || nsamples == 0) return fail("%s: an empty pool (%zu sources, %zu samples) for %zu pairs", fn, nsources, nsamples, batch);
     if (ensure_bank(p, fn, nsources, nsamples, s)) return -1;
-    // the bank fill: every track's forward column pass, once per call, on the caller's stream before any lane forks (grid.z: at most
-    // 65535 tracks per launch)
-    for (int op = 0; op < 2; op++) {
-        const size_t n = op ? nsamples : nsources;
-        for (size_t c0 = 0; c0 < n; c0 += 65535)
-            asx_launch_fwd_cols_r(P, op ? nullptr : d_sources, source_stride, op ? d_samples : nullptr, sample_stride, c0,
-                                  (int)std::min<size_t>(65535, n - c0), p->bank.c, true, s);
-    }
-    p->bank.fills++;
+    pool_fill(p, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, s);
     const PoolCall pool{ d_pairs, nsources, nsamples };
     return run_batch(p, Pairs<float>::pooled(&pool, d_sources, source_stride, d_samples, sample_stride, d_windows, window_stride), batch, y,
                      s, topk, weight, band, near);
@@ -1922,7 +1948,7 @@ static int ensure_ncc(asx_plan *p, const char *fn, hipStream_t s)
     if (asx_mem_whole(p->ncc.mem, p->ncc.w, [&](AsxMemSet &m, AsxNccWs &T) {
             return m.take(&T.r, g * 2 * N) || m.take(&T.table, g * N) || m.take(&T.raw, chunks) || m.take(&T.m1, chunks) ||
                            m.take(&T.m2, chunks) || m.take(&T.sstat, g * ASX_NCC_STAT) || m.take(&T.ystat, g * ASX_NCC_STAT) ||
-                           m.take(&T.best, g)
+                           m.take(&T.best, g) || m.take(&T.tk, g)
                        ? -1 : 0;
         }))
         return fail("%s: hipMalloc of the NCC workspace failed: %s", fn, hipGetErrorString(g_take_err));
@@ -1930,10 +1956,37 @@ static int ensure_ncc(asx_plan *p, const char *fn, hipStream_t s)
     return 0;
 }
 
-// After the entry point's null checks.  c_out: the debug call's curve (one contiguous pair), else null.
+// The plan's NCC track set holds at least nsrc source and nsmp sample tracks: 16N bytes of table per source track, three doubles per
+// chunk of 2048 frames and four per track.  Grown as the bank is (ensure_bank): everything reallocated behind a device synchronisation,
+// never inside a stream capture.
+static int ensure_ncc_tracks(asx_plan *p, const char *fn, size_t nsrc, size_t nsmp, hipStream_t s)
+{
+    asx_plan::Ncc &C = p->ncc;
+    if (nsrc <= C.nsrc && nsmp <= C.nsmp) return 0;
+    if (stream_capturing(s))
+        return fail("%s: the plan's NCC track set holds %zu x %zu tracks and cannot grow to %zu x %zu during a stream capture; make a "
+                    "call with pools at least this large outside the capture first", fn, C.nsrc, C.nsmp, nsrc, nsmp);
+    const size_t N = p->host.N, ns = std::max(nsrc, C.nsrc), nm = std::max(nsmp, C.nsmp);
+    const size_t chunks = ns * asx_ncc_chunks((uint32_t)(2 * N)) + nm * asx_ncc_chunks((uint32_t)N);
+    HIP_TRY(hipDeviceSynchronize());
+    C.tmem.clear(); C.tracks = AsxNccWs{}; C.nsrc = C.nsmp = 0;
+    if (asx_mem_whole(C.tmem, C.tracks, [&](AsxMemSet &m, AsxNccWs &T) {
+            return m.take(&T.table, ns * N) || m.take(&T.raw, chunks) || m.take(&T.m1, chunks) || m.take(&T.m2, chunks) ||
+                           m.take(&T.sstat, ns * ASX_NCC_STAT) || m.take(&T.ystat, nm * ASX_NCC_STAT)
+                       ? -1 : 0;
+        }))
+        return fail("%s: cannot allocate the plan's NCC track set for %zu source and %zu sample tracks (%zu bytes per source track)", fn,
+                    ns, nm, 16 * N);
+    C.nsrc = ns; C.nsmp = nm;
+    return 0;
+}
+
+// After the entry point's null checks and the top-k option's.  c_out: the debug call's curve (one contiguous pair), else null.
+// pool: null (the strided forms: d_source and d_sample are pair 0's tracks), or the pool call's pairs (they are the two pools).
+// topk.k > 1: y's entry stride is k.
 static int ncc_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample, size_t sample_stride,
                      const int64_t *d_windows, size_t window_stride, size_t batch, double min_energy, float *c_out, const Results &y,
-                     void *stream)
+                     void *stream, const PoolCall *pool = nullptr, const Topk &topk = {})
 {
     if (!(min_energy >= ASX_NCC_MIN_ENERGY && min_energy <= 1.0)) // (a NaN fails both)
         return fail("%s: min_energy %g is not in [%g, 1]", fn, min_energy, (double)ASX_NCC_MIN_ENERGY);
@@ -1941,14 +1994,27 @@ static int ncc_batch(asx_plan *p, const char *fn, const float *d_source, size_t 
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
     hipStream_t s = c.s;
     const AsxDev &P = p->dev;
-    if (strided_layout(p, fn, d_source, source_stride, d_sample, sample_stride)) return -1;
+    if (pool ? pool_layout(p, fn, d_source, source_stride, pool->nsrc, d_sample, sample_stride, pool->nsmp, pool->rows, batch)
+             : strided_layout(p, fn, d_source, source_stride, d_sample, sample_stride))
+        return -1;
     if (batch == 0) return 0;
+    if (pool && (ensure_bank(p, fn, pool->nsrc, pool->nsmp, s) || ensure_ncc_tracks(p, fn, pool->nsrc, pool->nsmp, s))) return -1;
     if (ensure_ncc(p, fn, s)) return -1;
     int bc = 0;
-    if (strided_broadcast(p, fn, d_source, source_stride, d_sample, sample_stride, s, &bc)) return -1;
+    if (!pool && strided_broadcast(p, fn, d_source, source_stride, d_sample, sample_stride, s, &bc)) return -1;
+    if (pool) {
+        // once per call, before the groups: every track's forward column pass into the bank and its moments into the track set
+        pool_fill(p, d_source, source_stride, pool->nsrc, d_sample, sample_stride, pool->nsmp, s);
+        asx_launch_ncc_pool_moments(p->ncc.tracks, d_source, source_stride, pool->nsrc, d_sample, sample_stride, pool->nsmp, P.N, s);
+        p->ncc.built_src += pool->nsrc;
+        p->ncc.built_smp += pool->nsmp;
+    }
     // the transforms see no rows: every lag's r is wanted, and the rows are this call's own (0 <= lag_min <= lag_max <= N-1)
-    const Pairs<float> x = Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, bc, nullptr, 0);
+    const Pairs<float> x = pool ? Pairs<float>::pooled(pool, d_source, source_stride, d_sample, sample_stride, nullptr, 0)
+                                : Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, bc, nullptr, 0);
     asx_plan::Lane &L = p->lanes[0];
+    const AsxPoolPair *pl = pool ? L.pool : nullptr; // the group's records, which run_group resolves
+    const int K = topk.k;
     prof_begin_call(p);
     size_t gi = 0;
     for (size_t done = 0; done < batch; done += p->ncc.group, gi++) {
@@ -1957,21 +2023,101 @@ static int ncc_batch(asx_plan *p, const char *fn, const float *d_source, size_t 
         const Results yg = y.at(done);
         const int64_t *rows = d_windows ? d_windows + 2 * done * window_stride : nullptr;
         AsxNccWs W = p->ncc.w;
-        // a track every pair shares (a stride of 0, whatever the layout): its moments once per call, by the first group
-        W.nsrc = source_stride == 0 ? 1u : (uint32_t)g;
-        W.nsmp = sample_stride == 0 ? 1u : (uint32_t)g;
-        W.do_src = source_stride != 0 || done == 0;
-        W.do_smp = sample_stride != 0 || done == 0;
+        if (pool) {
+            // a pair's table and statistics: those of its slots in the track set
+            W.table = p->ncc.tracks.table; W.sstat = p->ncc.tracks.sstat; W.ystat = p->ncc.tracks.ystat;
+            W.nsrc = W.nsmp = 0;
+            W.do_src = W.do_smp = false;
+        } else {
+            // a track every pair shares (a stride of 0, whatever the layout): its moments once per call, by the first group
+            W.nsrc = source_stride == 0 ? 1u : (uint32_t)g;
+            W.nsmp = sample_stride == 0 ? 1u : (uint32_t)g;
+            W.do_src = source_stride != 0 || done == 0;
+            W.do_smp = sample_stride != 0 || done == 0;
+            if (W.do_src) p->ncc.built_src += W.nsrc;
+            if (W.do_smp) p->ncc.built_smp += W.nsmp;
+        }
         if (run_group(p, xg, g, yg, s, { .prof_group = gi, .listed = false, .f32_abi = false, .r_out = W.r, .transforms_only = true }))
             return -1;
-        asx_launch_ncc_moments(W, xg.src, source_stride, xg.smp, sample_stride, P.N, s);
-        asx_launch_ncc_peak(W, W.r, P.nout, P.N, (double)P.F, min_energy, rows, window_stride, c_out, L.seg, yg.peak, (int)g, s);
-        // the reference's coefficient of the samples at the winner, in the direct form
-        asx_launch_pearson(xg.inputs(nullptr), P.N, L.seg, L.psums, yg.lag, yg.coef, yg.ret, (int)g, s);
-        if (rows) asx_launch_ncc_invalid(P.N, rows, window_stride, yg.lag, yg.coef, yg.peak, yg.ret, (int)g, s);
+        if (!pool) asx_launch_ncc_moments(W, xg.src, source_stride, xg.smp, sample_stride, P.N, s);
+        asx_launch_ncc_peak(W, W.r, P.nout, P.N, (double)P.F, min_energy, rows, window_stride, c_out, L.seg, yg.peak, (int)g, s, pl, K);
+        const AsxInputs<float> in = xg.inputs(pl);
+        if (K == 1) {
+            // the reference's coefficient of the samples at the winner, in the direct form
+            asx_launch_pearson(in, P.N, L.seg, L.psums, yg.lag, yg.coef, yg.ret, (int)g, s);
+            if (rows) asx_launch_ncc_invalid(P.N, rows, window_stride, yg.lag, yg.coef, yg.peak, yg.ret, (int)g, s);
+            if (pl) asx_launch_invalid_pairs(pl, yg.lag, yg.coef, yg.ret, yg.peak, (int)g, s);
+        } else {
+            // Entry j: its lag from the pass's maximum (k_ncctop_step), the direct form at that lag into the lane's temporaries, which the
+            // next step moves to the caller's arrays; pass j + 1 rescans the curve that k_ncc_peak left (k_ncctop_scan).
+            for (int j = 0; j <= K; j++) {
+                if (j > 0 && j < K) asx_launch_ncctop_scan(W, P.nout, P.N, rows, window_stride, topk.sep, j, (int)g, s);
+                asx_launch_ncctop_step(W, P.N, rows, window_stride, topk.sep, j, K, L.seg, L.tk.lag, L.tk.coef, L.tk.ret, yg.lag, yg.coef,
+                                       yg.peak, yg.ret, (int)g, s);
+                if (j < K) asx_launch_pearson(in, P.N, L.seg, L.psums, L.tk.lag, L.tk.coef, L.tk.ret, (int)g, s);
+            }
+            if (pl) asx_launch_invalid_pairs_k(pl, K, yg.lag, yg.coef, yg.ret, yg.peak, (int)g, s);
+        }
         HIP_TRY(hipGetLastError());
     }
     prof_end_call(p, gi);
+    return 0;
+}
+
+static bool ncc_topk_option(const char *fn, int k, int64_t min_separation)
+{
+    if (k < 1 || k > ASX_TOPK_MAX) return fail("%s: k = %d is not in [1, %d]", fn, k, ASX_TOPK_MAX), false;
+    if (min_separation < 0) return fail("%s: min_separation = %lld is negative", fn, (long long)min_separation), false;
+    return true;
+}
+
+// The K strongest separated lags of the coefficient curve: k = 1 launches exactly asx_xcorr_ncc_f32_dev.
+extern "C" int asx_xcorr_ncc_topk_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                          size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                          double min_energy, int k, int64_t min_separation, int64_t *d_lag, double *d_coef, double *d_peak,
+                                          int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_ncc_topk_f32_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    if (!ncc_topk_option(fn, k, min_separation)) return -1;
+    return ncc_batch(p, fn, d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch, min_energy, nullptr,
+                     { d_lag, d_coef, d_ret, (size_t)k, d_peak }, stream, nullptr, Topk{ k, min_separation });
+}
+
+// The NCC call over listed pairs of two pools: the bank filled and every track's moments formed once per call.
+extern "C" int asx_xcorr_pool_ncc_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                          const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                          const int64_t *d_windows, size_t window_stride, size_t batch, double min_energy, int64_t *d_lag,
+                                          double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_pool_ncc_f32_dev";
+    if (!p || !d_sources || !d_samples || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    const PoolCall pool{ d_pairs, nsources, nsamples };
+    return ncc_batch(p, fn, d_sources, source_stride, d_samples, sample_stride, d_windows, window_stride, batch, min_energy, nullptr,
+                     { d_lag, d_coef, d_ret, 1, d_peak }, stream, &pool);
+}
+
+// ... with the K strongest separated lags per pair: k = 1 launches exactly asx_xcorr_pool_ncc_f32_dev.
+extern "C" int asx_xcorr_pool_ncc_topk_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                               const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                               const int64_t *d_windows, size_t window_stride, size_t batch, double min_energy, int k,
+                                               int64_t min_separation, int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret,
+                                               void *stream)
+{
+    static const char *fn = "asx_xcorr_pool_ncc_topk_f32_dev";
+    if (!p || !d_sources || !d_samples || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    if (!ncc_topk_option(fn, k, min_separation)) return -1;
+    const PoolCall pool{ d_pairs, nsources, nsamples };
+    return ncc_batch(p, fn, d_sources, source_stride, d_samples, sample_stride, d_windows, window_stride, batch, min_energy, nullptr,
+                     { d_lag, d_coef, d_ret, (size_t)k, d_peak }, stream, &pool, Topk{ k, min_separation });
+}
+
+// diagnostic: the NCC track set's capacity (sources, samples), and the source tables and sample moment sets built over the plan's life
+extern "C" int asx_plan_debug_ncc(asx_plan *p, uint64_t out[4])
+{
+    if (!p || !out) return -1;
+    out[0] = p->ncc.nsrc; out[1] = p->ncc.nsmp;
+    out[2] = p->ncc.built_src; out[3] = p->ncc.built_smp;
     return 0;
 }
 

@@ -731,22 +731,52 @@ void asx_launch_pool_closure(const int64_t *lag, const double *coef, const int32
 __host__ __device__ inline uint32_t asx_ncc_chunks(uint32_t frames) { return (frames + ASX_NCC_CHUNK - 1) / ASX_NCC_CHUNK; }
 // a row of this call: 0 <= lag_min <= lag_max <= N-1
 __host__ __device__ inline bool asx_ncc_row_ok(int64_t lo, int64_t hi, uint32_t N) { return 0 <= lo && lo <= hi && hi <= (int64_t)N - 1; }
+// A pair's record in the top-k NCC calls (asx_xcorr_ncc_topk_f32_dev): the lags of the entries decided so far, whose zones the next
+// pass leaves out, and the entry whose coefficient the direct Pearson pass is forming (k_ncctop_step writes and reads it, k_ncctop_scan
+// reads the lags).
+#define ASX_NCC_TK_EMPTY 1u   // A_j is empty from entry `n` on: (0, NaN, NaN, -3)
+#define ASX_NCC_TK_INVALID 2u // the pair's row is not a row of the call: every entry is (0, NaN, NaN, -2)
+struct AsxNccTopk {
+    int64_t lag[ASX_TOPK_MAX]; // entries 0 .. n - 1
+    double peak;               // of entry n - 1
+    uint32_t n, flags;
+};
 struct AsxNccWs {
-    float *r;              // [pairs][2N] what the group's inverse pass left (run_group's r_out)
+    float *r;              // [pairs][2N] what the group's inverse pass left (run_group's r_out); a top-k group keeps c32 of the lags
+                           // 0..N-1 in the upper half (the negative lags, which no NCC kernel reads) behind k_ncc_peak
     double2 *table;        // [nsrc][N] per lag {Sx' = sum of the window's frames minus mu, Vx}
     double *raw, *m1, *m2; // chunk sums: source track t's at t * chunks(2N), sample track t's behind all of them at t * chunks(N)
     double *sstat, *ystat; // [nsrc][ASX_NCC_STAT], [nsmp][ASX_NCC_STAT]
     asx_peak_t *best;      // [pairs] the packed (|c32|, smallest lag) maximum; 0: no lag competes
+    AsxNccTopk *tk;        // [pairs] the top-k calls' records
     uint32_t nsrc, nsmp;
     bool do_src, do_smp;
 };
 // the moments of the group's tracks (those of do_src / do_smp): k_ncc_sums, k_ncc_moments, k_ncc_table
 void asx_launch_ncc_moments(const AsxNccWs &W, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch, uint32_t N,
                             hipStream_t s);
+// the same over the tracks of two pools (asx_xcorr_pool_ncc_f32_dev), once per call: T holds the plan's track set (table, chunk sums
+// and statistics of nsrc source and nsmp sample tracks); at most 65 535 tracks per launch (grid.y), each launch on its own share
+void asx_launch_ncc_pool_moments(const AsxNccWs &T, const float *srcs, size_t src_pitch, size_t nsrc, const float *smps, size_t smp_pitch,
+                                 size_t nsmp, uint32_t N, hipStream_t s);
 // k_ncc_peak and k_ncc_finalize: each pair's winner among the lags of its row (rows null: 0..N-1) to seg and peak; c_out: null, or
-// c32 of every lag ([pairs][N], NaN where the lag does not compete); scale: what r carries against the plain sum (F)
+// c32 of every lag ([pairs][N], NaN where the lag does not compete); scale: what r carries against the plain sum (F).  pl: null, or
+// a pool group's records, whose slots name each pair's table and statistics (W.table, W.sstat, W.ystat: the plan's track set).
+// k > 1 (a top-k group): c32 goes to the upper half of each pair's r instead, k_ncc_finalize does not run and seg and peak are left
+// alone: asx_launch_ncctop_step(j = 0) takes the pass's winner from W.best.
 void asx_launch_ncc_peak(const AsxNccWs &W, const float *r, size_t r_pitch, uint32_t N, double scale, double min_energy,
-                         const int64_t *rows, size_t rows_step, float *c_out, AsxSeg *seg, double *peak, int npairs, hipStream_t s);
+                         const int64_t *rows, size_t rows_step, float *c_out, AsxSeg *seg, double *peak, int npairs, hipStream_t s,
+                         const AsxPoolPair *pl = nullptr, int k = 1);
+// pass j >= 1 of a top-k group (k_ncctop_scan): the packed maximum over c32 as pass 0 left it in the upper half of r, among the lags
+// of the row that lie outside the zones +- sep around the record's j earlier entries, to W.best
+void asx_launch_ncctop_scan(const AsxNccWs &W, size_t r_pitch, uint32_t N, const int64_t *rows, size_t rows_step, int64_t sep, int j,
+                            int npairs, hipStream_t s);
+// between the passes of a top-k group (k_ncctop_step), a thread per pair, 0 <= j <= k.  j > 0: entry j - 1 (entry stride k) from the
+// direct Pearson pass's results in tmp_* and the record's peak, or (0, NaN, NaN, -3 / -2).  j < k: entry j from W.best -- the winner,
+// or the smallest lag of A_j with peak 0, or A_j is empty -- to the record and seg, and W.best back to 0.
+void asx_launch_ncctop_step(const AsxNccWs &W, uint32_t N, const int64_t *rows, size_t rows_step, int64_t sep, int j, int k, AsxSeg *seg,
+                            const int64_t *tmp_lag, const double *tmp_coef, const int32_t *tmp_ret, int64_t *lag, double *coef,
+                            double *peak, int32_t *ret, int npairs, hipStream_t s);
 // behind the Pearson kernels: (0, NaN, NaN, -2) for every pair whose row is not a row of this call
 void asx_launch_ncc_invalid(uint32_t N, const int64_t *rows, size_t rows_step, int64_t *lag, double *coef, double *peak, int32_t *ret,
                             int npairs, hipStream_t s);

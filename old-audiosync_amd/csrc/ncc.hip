@@ -16,6 +16,9 @@
 //                  lag) maximum of the pair (asx_peak_t, atomic maximum); optionally c32 itself for the debug call
 //   k_ncc_finalize a thread per pair: AsxSeg through make_seg and the peak height
 //   k_ncc_invalid  a thread per pair, behind the Pearson kernels: (0, NaN, NaN, -2) for a row that is not a window of this call
+// The pool calls (asx_xcorr_pool_ncc_f32_dev) run the three moment kernels over the tracks of the two pools, once per call, into the
+// plan's track set (asx_launch_ncc_pool_moments: the same kernels on the same chunks, so the same trees), and k_ncc_peak finds a
+// pair's table and statistics through its pool record.  The top-k calls add k_ncctop_scan and k_ncctop_step (below).
 #include "asx_internal.h"
 #include "xcorr_dev.h"
 
@@ -202,13 +205,15 @@ __global__ __launch_bounds__(NCC_NT) void k_ncc_table(AsxNccWs W, const float *_
     if (lane == 0 && vmax > 0.0) atomicMax(reinterpret_cast<unsigned long long *>(st + 1), (unsigned long long)__double_as_longlong(vmax));
 }
 
+// c_out: c32 of pair i's lag l to c_out[i * c_pitch + l] (the debug call: [pairs][N]; a top-k group: the upper half of r, which this
+// kernel does not read).  pl: a pool group's records -- pair i's table and statistics are those of its slots in the plan's track set.
 __global__ __launch_bounds__(NCC_NT) void k_ncc_peak(AsxNccWs W, const float *__restrict__ r, size_t r_pitch, uint32_t N, double scale,
                                                       double min_energy, const int64_t *__restrict__ rows, size_t rows_step,
-                                                      float *__restrict__ c_out)
+                                                      float *__restrict__ c_out, size_t c_pitch, const AsxPoolPair *__restrict__ pl)
 {
     __shared__ asx_peak_t red[NCC_NT / 64];
     const size_t pair = blockIdx.y;
-    const size_t ts = W.nsrc > 1 ? pair : 0, ty = W.nsmp > 1 ? pair : 0;
+    const size_t ts = pl ? pl[pair].sx : W.nsrc > 1 ? pair : 0, ty = pl ? pl[pair].sy : W.nsmp > 1 ? pair : 0;
     const double *sx = W.sstat + ts * ASX_NCC_STAT, *sy = W.ystat + ty * ASX_NCC_STAT;
     const double mu = sx[0], floor_v = min_energy * sx[1], Sy = sy[2], Vy = sy[3], dN = (double)N;
     int64_t lo = 0, hi = (int64_t)N - 1;
@@ -229,7 +234,7 @@ __global__ __launch_bounds__(NCC_NT) void k_ncc_peak(AsxNccWs W, const float *__
         const double c = ((double)rp[l] / scale - Sx * Sy / dN) / sqrt(e.y * Vy);
         const float c32 = (float)c;
         const bool competes = Vy > 0.0 && e.y >= floor_v && fabs(c) <= 1.7976931348623157e308; // (false for a NaN and for +-infinity)
-        if (c_out) c_out[pair * (size_t)N + l] = competes ? c32 : NAN;
+        if (c_out) c_out[pair * c_pitch + l] = competes ? c32 : NAN;
         if (competes && (int64_t)l >= lo && (int64_t)l <= hi) best = peak_max(best, peak_pack_key(fabsf(c32), l));
     }
     best = block_peak_max(best, red);
@@ -264,6 +269,110 @@ __global__ __launch_bounds__(NCC_NT) void k_ncc_invalid(uint32_t N, const int64_
     ret[pair] = -2;
 }
 
+// ---- top-k (asx_xcorr_ncc_topk_f32_dev, asx_xcorr_pool_ncc_topk_f32_dev) ---------------------------------------------------------
+// Pass 0 is k_ncc_peak, which leaves c32 of every lag in the upper half of the pair's r (NaN: the lag does not compete).  A pass j >= 1
+// rescans those 4N bytes with the row and the zones around the record's j earlier entries masked out; between the passes a thread per
+// pair turns the pass's maximum into entry j and the segment of the direct Pearson pass, and moves entry j - 1 to the caller's arrays.
+// (These kernels are k_ncctop_*, not k_ncc_*: tests/test_ncc.py holds the k_ncc_ family to the six kernels of the one-lag call.)
+
+// the zone of an earlier entry at `lag`: the lags zlo .. zlo + zwd = [lag - sep, lag + sep] clipped to [0, N-1]
+__device__ __forceinline__ void ncctop_zone(int64_t lag, int64_t sep, uint32_t N, uint32_t &zlo, uint32_t &zwd)
+{
+    const int64_t n1 = (int64_t)N - 1;
+    const int64_t lo = sep > lag ? 0 : lag - sep, hi = sep >= n1 - lag ? n1 : lag + sep; // (0 <= lag <= N-1: neither can overflow)
+    zlo = (uint32_t)lo;
+    zwd = (uint32_t)(hi - lo);
+}
+
+// grid (lag chunks, pairs): pass j, 1 <= j < ASX_TOPK_MAX.  The zones are tested as (l - zlo) > zwd in unsigned arithmetic, all
+// ASX_TOPK_MAX - 1 of them whatever j is: an unused one is (~0, 0), which holds no lag (AsxWinX's form, asx_internal.h).
+__global__ __launch_bounds__(NCC_NT) void k_ncctop_scan(AsxNccWs W, size_t r_pitch, uint32_t N, const int64_t *__restrict__ rows,
+                                                         size_t rows_step, int64_t sep, int j)
+{
+    __shared__ asx_peak_t red[NCC_NT / 64];
+    const size_t pair = blockIdx.y;
+    const AsxNccTopk *T = W.tk + pair;
+    if (T->flags) return; // (the whole block: an invalid row, or no lag was left for an earlier entry)
+    int64_t lo = 0, hi = (int64_t)N - 1;
+    if (rows) { lo = rows[2 * pair * rows_step]; hi = rows[2 * pair * rows_step + 1]; }
+    uint32_t zlo[ASX_TOPK_MAX - 1], zwd[ASX_TOPK_MAX - 1];
+#pragma unroll
+    for (int i = 0; i < ASX_TOPK_MAX - 1; i++) {
+        zlo[i] = ~0u; zwd[i] = 0u;
+        if (i < j) ncctop_zone(T->lag[i], sep, N, zlo[i], zwd[i]);
+    }
+    const float *c = W.r + pair * r_pitch + N;
+    const uint32_t l0 = blockIdx.x * ASX_NCC_CHUNK;
+    asx_peak_t best = 0;
+#pragma unroll 2
+    for (int q = 0; q < NCC_PER; q++) {
+        const uint32_t l = l0 + q * NCC_NT + threadIdx.x;
+        if (l >= N) break;
+        const float v = c[l];
+        bool in = v == v && (int64_t)l >= lo && (int64_t)l <= hi;
+#pragma unroll
+        for (int i = 0; i < ASX_TOPK_MAX - 1; i++) in = in && l - zlo[i] > zwd[i];
+        if (in) best = peak_max(best, peak_pack_key(fabsf(v), l));
+    }
+    best = block_peak_max(best, red);
+    if (threadIdx.x == 0 && best) atomicMax(&W.best[pair], best);
+}
+
+// a thread per pair, 0 <= j <= k (see asx_launch_ncctop_step).  The record stays in global memory: its lags are indexed by j.
+__global__ __launch_bounds__(NCC_NT) void k_ncctop_step(AsxNccWs W, uint32_t N, const int64_t *__restrict__ rows, size_t rows_step,
+                                                         int64_t sep, int j, int k, AsxSeg *__restrict__ seg,
+                                                         const int64_t *__restrict__ tmp_lag, const double *__restrict__ tmp_coef,
+                                                         const int32_t *__restrict__ tmp_ret, int64_t *__restrict__ lag,
+                                                         double *__restrict__ coef, double *__restrict__ peak, int32_t *__restrict__ ret,
+                                                         int npairs)
+{
+    const int pair = blockIdx.x * NCC_NT + threadIdx.x;
+    if (pair >= npairs) return;
+    AsxNccTopk *T = W.tk + pair;
+    int64_t lo = 0, hi = (int64_t)N - 1;
+    if (rows) { lo = rows[2 * (size_t)pair * rows_step]; hi = rows[2 * (size_t)pair * rows_step + 1]; }
+    uint32_t n = 0, flags = 0;
+    if (j == 0) { if (!asx_ncc_row_ok(lo, hi, N)) flags = ASX_NCC_TK_INVALID; }
+    else { n = T->n; flags = T->flags; }
+    if (j > 0) {
+        const size_t e = (size_t)pair * (size_t)k + (size_t)(j - 1);
+        const bool none = flags & ASX_NCC_TK_INVALID || n < (uint32_t)j; // n < j: no lag was left for this entry
+        if (lag) lag[e] = none ? 0 : tmp_lag[pair];
+        coef[e] = none ? (double)NAN : tmp_coef[pair];
+        peak[e] = none ? (double)NAN : T->peak;
+        ret[e] = flags & ASX_NCC_TK_INVALID ? -2 : none ? -3 : tmp_ret[pair];
+    }
+    if (j >= k) return;
+    const asx_peak_t best = W.best[pair];
+    W.best[pair] = 0;
+    uint32_t at = 0;
+    if (!flags) {
+        double height = 0.0;
+        bool have = true;
+        if (best) { at = peak_index(best); height = (double)peak_key(best); }
+        else {
+            // no lag of A_j competes: its smallest lag, the row's lag_min pushed past every zone that holds it
+            int64_t cand = lo;
+            for (int round = 0; round <= j; round++) {
+                bool moved = false;
+                for (int i = 0; i < j; i++) {
+                    uint32_t zlo, zwd;
+                    ncctop_zone(T->lag[i], sep, N, zlo, zwd);
+                    if (cand >= (int64_t)zlo && cand <= (int64_t)zlo + (int64_t)zwd) { cand = (int64_t)zlo + (int64_t)zwd + 1; moved = true; }
+                }
+                if (!moved) break;
+            }
+            have = cand <= hi;
+            at = have ? (uint32_t)cand : 0u;
+        }
+        if (have) { T->lag[j] = (int64_t)at; T->peak = height; n = (uint32_t)j + 1u; }
+        else flags = ASX_NCC_TK_EMPTY;
+    }
+    T->n = n;
+    T->flags = flags;
+    seg[pair] = make_seg(at, N); // (an entry that is not to be: lag 0's segment, whose coefficient the next step drops)
+}
+
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------
 void asx_launch_ncc_moments(const AsxNccWs &W, const float *src, size_t src_pitch, const float *smp, size_t smp_pitch, uint32_t N,
                             hipStream_t s)
@@ -275,13 +384,51 @@ void asx_launch_ncc_moments(const AsxNccWs &W, const float *src, size_t src_pitc
     hipLaunchKernelGGL(k_ncc_table, dim3(nyc + 1, nt), dim3(NCC_NT), 0, s, W, src, src_pitch, N);
 }
 
+void asx_launch_ncc_pool_moments(const AsxNccWs &T, const float *srcs, size_t src_pitch, size_t nsrc, const float *smps, size_t smp_pitch,
+                                 size_t nsmp, uint32_t N, hipStream_t s)
+{
+    const size_t nsc = asx_ncc_chunks(2u * N), nyc = asx_ncc_chunks(N), most = 65535;
+    for (size_t c0 = 0; c0 < std::max(nsrc, nsmp); c0 += most) {
+        // tracks c0 .. of either pool, as one "group" of the strided call's kernels: its chunk sums lie behind those of the launches before
+        const size_t s0 = std::min(c0, nsrc), y0 = std::min(c0, nsmp), at = s0 * nsc + y0 * nyc;
+        AsxNccWs W = T;
+        W.nsrc = (uint32_t)std::min(most, nsrc - s0);
+        W.nsmp = (uint32_t)std::min(most, nsmp - y0);
+        W.do_src = W.nsrc > 0;
+        W.do_smp = W.nsmp > 0;
+        W.table += s0 * (size_t)N;
+        W.raw += at; W.m1 += at; W.m2 += at;
+        W.sstat += s0 * ASX_NCC_STAT;
+        W.ystat += y0 * ASX_NCC_STAT;
+        asx_launch_ncc_moments(W, srcs + s0 * src_pitch, src_pitch, smps + y0 * smp_pitch, smp_pitch, N, s);
+    }
+}
+
 void asx_launch_ncc_peak(const AsxNccWs &W, const float *r, size_t r_pitch, uint32_t N, double scale, double min_energy,
-                         const int64_t *rows, size_t rows_step, float *c_out, AsxSeg *seg, double *peak, int npairs, hipStream_t s)
+                         const int64_t *rows, size_t rows_step, float *c_out, AsxSeg *seg, double *peak, int npairs, hipStream_t s,
+                         const AsxPoolPair *pl, int k)
 {
     (void)hipMemsetAsync(W.best, 0, (size_t)npairs * sizeof(asx_peak_t), s);
+    // a top-k group keeps the curve for its later passes: r_pitch >= 2N, and lags N..2N-1 of r are not read by any NCC kernel
+    float *const c = k > 1 ? W.r + N : c_out;
     hipLaunchKernelGGL(k_ncc_peak, dim3(asx_ncc_chunks(N), npairs), dim3(NCC_NT), 0, s, W, r, r_pitch, N, scale, min_energy, rows, rows_step,
-                       c_out);
+                       c, k > 1 ? r_pitch : (size_t)N, pl);
+    if (k > 1) return;
     hipLaunchKernelGGL(k_ncc_finalize, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, W, N, rows, rows_step, seg, peak, npairs);
+}
+
+void asx_launch_ncctop_scan(const AsxNccWs &W, size_t r_pitch, uint32_t N, const int64_t *rows, size_t rows_step, int64_t sep, int j,
+                            int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_ncctop_scan, dim3(asx_ncc_chunks(N), npairs), dim3(NCC_NT), 0, s, W, r_pitch, N, rows, rows_step, sep, j);
+}
+
+void asx_launch_ncctop_step(const AsxNccWs &W, uint32_t N, const int64_t *rows, size_t rows_step, int64_t sep, int j, int k, AsxSeg *seg,
+                            const int64_t *tmp_lag, const double *tmp_coef, const int32_t *tmp_ret, int64_t *lag, double *coef,
+                            double *peak, int32_t *ret, int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_ncctop_step, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, W, N, rows, rows_step, sep, j, k, seg, tmp_lag,
+                       tmp_coef, tmp_ret, lag, coef, peak, ret, npairs);
 }
 
 void asx_launch_ncc_invalid(uint32_t N, const int64_t *rows, size_t rows_step, int64_t *lag, double *coef, double *peak, int32_t *ret,

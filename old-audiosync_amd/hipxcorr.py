@@ -65,6 +65,10 @@ _HEADER_SIGNATURES = {
     "asx_xcorr_phat_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_ncc_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_ncc_debug_c_dev": (_int, [_vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_ncc_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_pool_ncc_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_pool_ncc_topk_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _dbl, _int, _i64, _vp, _vp, _vp, _vp,
+                                               _vp]),
     "asx_xcorr_phat_band_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_sub_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -124,6 +128,7 @@ _DIAGNOSTIC_SIGNATURES = {
     "asx_planmath_group_form": (_int, [c_intp, _int, c_intp, _int]),
     "asx_plan_debug_kernels": (_int, [_vp, c_intp, c_intp, c_intp]),
     "asx_plan_debug_bank": (_int, [_vp, _u64p, _u64p, _u64p]),
+    "asx_plan_debug_ncc": (_int, [_vp, _u64p]),
     "asx_plan_debug_prune": (_int, [_vp, _sz, c_f32p, c_intp, _sz]),
     "asx_plan_debug_peak": (_int, [_vp, _sz, c_f32p, _u32p, _u32p, _u64p, _vp, _vp, _sz]),
     "asx_plan_debug_spectral": (_int, [_vp, _sz, c_intp, _vp, _sz, c_f64p, ctypes.POINTER(ctypes.c_longlong), c_f64p]),
@@ -517,6 +522,13 @@ def ncc_args(n, source, sample, windows=None, min_energy=1e-3):
     return _strided_args(n, source, sample, None if windows is None else _window_rows(windows)) + (option,)
 
 
+def ncc_topk_args(n, source, sample, k, min_separation, windows=None, min_energy=1e-3):
+    """Host checks of Plan.xcorr_ncc_topk_f32: ncc_args' checks, and k and min_separation as topk_args checks them.  -> ncc_args' tuple
+    + (k, min_separation).  ValueError on anything else."""
+    option = _topk_option(k, min_separation)
+    return ncc_args(n, source, sample, windows, min_energy) + option
+
+
 def topk_args(n, source, sample, k, min_separation, windows=None):
     """Host checks of Plan.xcorr_topk_f32: the shapes of windowed_args (windows=None: the plan's window, no rows), 1 <= k <= TOPK_MAX
     and min_separation >= 0, integers.  -> (source, sample, windows or None, batch, source_stride, sample_stride, window_stride, k,
@@ -561,6 +573,20 @@ def pool_topk_args(n, sources, samples, k, min_separation, pairs=None, windows=N
     tuple + (k, min_separation).  ValueError on anything else."""
     option = _topk_option(k, min_separation)
     return pool_args(n, sources, samples, pairs, windows) + option
+
+
+def pool_ncc_args(n, sources, samples, pairs=None, windows=None, min_energy=1e-3):
+    """Host checks of Plan.xcorr_pool_ncc_f32: min_energy as ncc_args checks it, the rest as pool_args (windows None: every lag
+    0..N-1).  -> pool_args' tuple + (min_energy,).  ValueError on anything else."""
+    option = _energy_option(min_energy)
+    return pool_args(n, sources, samples, pairs, windows) + (option,)
+
+
+def pool_ncc_topk_args(n, sources, samples, k, min_separation, pairs=None, windows=None, min_energy=1e-3):
+    """Host checks of Plan.xcorr_pool_ncc_topk_f32: k and min_separation as topk_args checks them, the rest as pool_ncc_args.  ->
+    pool_ncc_args' tuple + (k, min_separation).  ValueError on anything else."""
+    option = _topk_option(k, min_separation)
+    return pool_ncc_args(n, sources, samples, pairs, windows, min_energy) + option
 
 
 def pool_phat_args(n, sources, samples, pairs=None, windows=None, band=None):
@@ -1069,6 +1095,33 @@ class Plan:
                                            int(window_stride), int(batch), float(min_energy), d_lag or None, d_coef or None,
                                            d_peak or None, d_ret or None, stream or None))
 
+    def xcorr_ncc_topk_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, min_energy, k, min_separation,
+                           d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_ncc_topk_f32_dev -- xcorr_ncc_dev with the k strongest lags of the coefficient curve
+        at least min_separation apart, entry j of pair i at index i*k + j of d_lag / d_coef / d_peak / d_ret"""
+        _check(lib().asx_xcorr_ncc_topk_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride),
+                                                d_windows or None, int(window_stride), int(batch), float(min_energy), int(k),
+                                                int(min_separation), d_lag or None, d_coef or None, d_peak or None, d_ret or None,
+                                                stream or None))
+
+    def xcorr_pool_ncc_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows,
+                           window_stride, batch, min_energy, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_ncc_f32_dev -- xcorr_pool_dev's pairs ranked by the Pearson coefficient of the
+        lags 0..N-1; every track's transform and moments once per call; d_windows = 0: every lag 0..N-1"""
+        _check(lib().asx_xcorr_pool_ncc_f32_dev(self._h, d_sources or None, int(source_stride), int(nsources), d_samples or None,
+                                                int(sample_stride), int(nsamples), d_pairs or None, d_windows or None,
+                                                int(window_stride), int(batch), float(min_energy), d_lag or None, d_coef or None,
+                                                d_peak or None, d_ret or None, stream or None))
+
+    def xcorr_pool_ncc_topk_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows,
+                                window_stride, batch, min_energy, k, min_separation, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_ncc_topk_f32_dev -- xcorr_pool_ncc_dev with the k strongest separated lags of
+        pair i, entry j at index i*k + j"""
+        _check(lib().asx_xcorr_pool_ncc_topk_f32_dev(self._h, d_sources or None, int(source_stride), int(nsources), d_samples or None,
+                                                     int(sample_stride), int(nsamples), d_pairs or None, d_windows or None,
+                                                     int(window_stride), int(batch), float(min_energy), int(k), int(min_separation),
+                                                     d_lag or None, d_coef or None, d_peak or None, d_ret or None, stream or None))
+
     def ncc_debug_c_dev(self, d_src, d_smp, min_energy, d_c, d_lag, d_coef, d_peak, d_ret, stream=0):
         """asx_xcorr_ncc_debug_c_dev: one contiguous pair, c32 of lags 0..N-1 to d_c (NaN where the lag does not compete)"""
         _check(lib().asx_xcorr_ncc_debug_c_dev(self._h, d_src or None, d_smp or None, float(min_energy), d_c or None, d_lag or None,
@@ -1274,6 +1327,13 @@ class Plan:
     def debug_bank(self):
         """(source tracks, sample tracks) the plan's pool bank holds, and how many pool calls have filled it"""
         return _counters(lib().asx_plan_debug_bank, self._h, 3, "asx_plan_debug_bank failed")
+
+    def debug_ncc(self):
+        """(source tracks, sample tracks) the plan's NCC track set holds, and the source tables and sample moment sets every NCC call
+        on this plan has built so far"""
+        c = (ctypes.c_uint64 * 4)()
+        _check(lib().asx_plan_debug_ncc(self._h, c), "asx_plan_debug_ncc failed")
+        return tuple(int(v) for v in c)
 
     def debug_over_list(self):
         """diagnostic: the plan's list of overflowed pairs as it stands, (count on the device, count of the host's mirror), read
@@ -1498,6 +1558,36 @@ class Plan:
         s, t, w, batch, ss, ts, ws, me = ncc_args(self.sample_len, source, sample, windows, min_energy)
         return self._staged((s, t, w), (batch,), _PHAT_RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_ncc_dev(
             d_s, ss, d_t, ts, d_w, ws, batch, me, *d_out))
+
+    def xcorr_ncc_topk_f32(self, source, sample, k, min_separation, windows=None, min_energy=1e-3):
+        """The k strongest separated lags per pair of the coefficient curve (asx_xcorr_ncc_topk_f32_dev): source, sample, windows and
+        min_energy as in xcorr_ncc_f32, k and min_separation as in xcorr_topk_f32.  Arguments are checked on the host (ValueError)
+        before anything is uploaded.  Returns (lag int64[B, k], coef float64[B, k], peak float64[B, k], ret int32[B, k]); ret = -3 (and
+        NaN for coef and peak) where no lag was left.  Entry 0 is xcorr_ncc_f32's result."""
+        s, t, w, batch, ss, ts, ws, me, k, sep = ncc_topk_args(self.sample_len, source, sample, k, min_separation, windows, min_energy)
+        return self._staged((s, t, w), (batch, k), _PHAT_RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_ncc_topk_dev(
+            d_s, ss, d_t, ts, d_w, ws, batch, me, k, sep, *d_out))
+
+    def xcorr_pool_ncc_f32(self, sources, samples, pairs=None, windows=None, min_energy=1e-3):
+        """Pairs of two pools ranked by the normalised cross-correlation (asx_xcorr_pool_ncc_f32_dev): the pools and pairs of
+        xcorr_pool_f32, windows and min_energy of xcorr_ncc_f32.  Every track is transformed, and its moments are formed, once per
+        call.  Arguments are checked on the host (ValueError) before anything is uploaded.  Returns (lag int64, coef float64, peak
+        float64, ret int32) of shape [B], or [S, R] when pairs is None; a pair with an index outside its pool gets (0, NaN, NaN, -4)."""
+        n = self.sample_len
+        s, t, pr, w, batch, ws, me = pool_ncc_args(n, sources, samples, pairs, windows, min_energy)
+        shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
+        return self._staged((s, t, pr, w), shape, _PHAT_RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_ncc_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, me, *d_out))
+
+    def xcorr_pool_ncc_topk_f32(self, sources, samples, k, min_separation, pairs=None, windows=None, min_energy=1e-3):
+        """The k strongest separated lags of the coefficient curve per pair of two pools (asx_xcorr_pool_ncc_topk_f32_dev): the
+        arguments of xcorr_pool_ncc_f32, k and min_separation of xcorr_topk_f32.  Returns (lag, coef, peak, ret) of shape [B, k], or
+        [S, R, k] when pairs is None; ret = -3 where no lag was left, -4 in all k entries of a pair with an index outside its pool."""
+        n = self.sample_len
+        s, t, pr, w, batch, ws, me, k, sep = pool_ncc_topk_args(n, sources, samples, k, min_separation, pairs, windows, min_energy)
+        shape = ((batch,) if pr is not None else (s.shape[0], t.shape[0])) + (k,)
+        return self._staged((s, t, pr, w), shape, _PHAT_RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_ncc_topk_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, me, k, sep, *d_out))
 
     def xcorr_phat_band_f32(self, source, sample, bin_lo, bin_hi, windows=None):
         """xcorr_phat_f32 in which only bins bin_lo..bin_hi of the 2N-point transform vote (asx_xcorr_phat_band_f32_dev; band_bins
