@@ -33,11 +33,13 @@
  *   asx_xcorr_pool_curve_f32_dev: an entry's centre was not a lag inside [-N, N-1]; NaN in all its values.  The same in
  *   asx_xcorr_track_f32_dev and asx_xcorr_pool_track_f32_dev, with used = 0.  asx_xcorr_ncc_f32_dev with rows: the row was not a
  *   window inside [0, N-1]; peak[i] = NaN too.  The same in asx_xcorr_ncc_topk_f32_dev, asx_xcorr_pool_ncc_f32_dev and
- *   asx_xcorr_pool_ncc_topk_f32_dev, in all k entries.)
+ *   asx_xcorr_pool_ncc_topk_f32_dev, in all k entries.  asx_xcorr_ncc_full_f32_dev and asx_xcorr_ncc_full_topk_f32_dev: the row was
+ *   not a window inside [-(N-1), N-1].)
  *   ret = -3 (asx_xcorr_topk_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_phat_topk_f32_dev and
  *   asx_xcorr_pool_phat_topk_f32_dev only): no lag is left for
  *   this entry of the pair (its window minus the zones around the earlier entries is empty);
- *   lag = 0 and coef = NaN.  (asx_xcorr_ncc_topk_f32_dev and asx_xcorr_pool_ncc_topk_f32_dev too: peak = NaN as well.)
+ *   lag = 0 and coef = NaN.  (asx_xcorr_ncc_topk_f32_dev, asx_xcorr_pool_ncc_topk_f32_dev and
+ *   asx_xcorr_ncc_full_topk_f32_dev too: peak = NaN as well.)
  *   ret = -4 (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_pool_phat_f32_dev,
  *   asx_xcorr_pool_phat_sub_f32_dev and asx_xcorr_pool_phat_topk_f32_dev only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
  *   form: in all k entries of the pair).  It takes precedence over -2 and -3.  (asx_xcorr_pool_curve_f32_dev: NaN in all
@@ -370,9 +372,9 @@ int asx_xcorr_phat_f32_dev(asx_plan *plan, const float *d_source, size_t source_
  * coefficients (what other toolkits call normxcorr or the `coeff` option of xcorr).
  *   The definition.  N = sample_len, x = the source (2N float32), y = the sample (N float32).  Only the lags 0 <= l <= N-1 exist for
  * this call: there the sample lies wholly inside the source, the reference's segment for l >= 0 being source[l, l+N) against the whole
- * sample (src/cross_correlation.c:264-271).  Negative lags are out of scope: there the circular r[2N + l] also holds the |l| products
- * that wrapped around, and taking them out for every lag is a second correlation, against the source's upper half alone, which prefix
- * sums cannot supply.  In float64:
+ * sample (src/cross_correlation.c:264-271).  Negative lags are out of scope here: there the circular r[2N + l] also holds the |l|
+ * products that wrapped around, and keeping them out for every lag is a second correlation, which prefix sums cannot supply.
+ * asx_xcorr_ncc_full_f32_dev, below, runs that second correlation and ranks the lags -(N-1)..N-1.  In float64:
  *     mu     = mean of all 2N source frames
  *     Sx[l]  = sum_{n<N} x[l+n]             (accumulated as sums of x - mu, then N*mu added back: an offset costs no digits)
  *     Vx[l]  = sum_{n<N} (x[l+n] - mean_l)^2 = Sxx'[l] - Sx'[l]^2 / N    on the mu-shifted values
@@ -416,9 +418,10 @@ int asx_xcorr_phat_f32_dev(asx_plan *plan, const float *d_source, size_t source_
  * most 1 GiB (or one pair's 24N bytes).
  *   Cost: the transforms of the strided call with every inverse tile in its general form (r is written out), three passes over the
  * tracks for the moments and one over r and the table (measured: DESIGN.md).
- *   Not offered: negative lags, a neighbourhood or fractional lag (asx_xcorr_curve_f32_dev serves the returned lag), the double
- * ABI, streams, and a fused inverse pass.  Offered as calls of their own, below: top-k (asx_xcorr_ncc_topk_f32_dev) and pools
- * (asx_xcorr_pool_ncc_f32_dev, asx_xcorr_pool_ncc_topk_f32_dev). */
+ *   Not offered: negative lags in this call (asx_xcorr_ncc_full_f32_dev has them), a neighbourhood or fractional lag
+ * (asx_xcorr_curve_f32_dev serves the returned lag), the double ABI, streams, and a fused inverse pass.  Offered as calls of their
+ * own, below: top-k (asx_xcorr_ncc_topk_f32_dev), pools (asx_xcorr_pool_ncc_f32_dev, asx_xcorr_pool_ncc_topk_f32_dev) and the full
+ * range of lags (asx_xcorr_ncc_full_f32_dev, asx_xcorr_ncc_full_topk_f32_dev). */
 #define ASX_NCC_MIN_ENERGY 1e-6
 int asx_xcorr_ncc_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
                           const float *d_sample, size_t sample_stride,
@@ -498,12 +501,79 @@ int asx_xcorr_pool_ncc_f32_dev(asx_plan *plan, const float *d_sources, size_t so
  * A pool index outside its pool gives (0, NaN, NaN, -4) in all k entries; it takes precedence over -2 and -3.  Refusals: those of the
  * pool call above plus k and min_separation out of range.  The bank and the track set are filled once per call whatever k is.
  *   The [C][C][k] tables of an all-pairs call have the layout asx_pool_closure_dev takes, but feeding them to it is not offered: this
- * curve holds the lags 0..N-1 only, so a pair whose true lag is negative has no entry to offer. */
+ * curve holds the lags 0..N-1 only, so a pair whose true lag is negative has no entry to offer.  (The full-range curve of
+ * asx_xcorr_ncc_full_topk_f32_dev has such entries, but no pool form yet.) */
 int asx_xcorr_pool_ncc_topk_f32_dev(asx_plan *plan, const float *d_sources, size_t source_stride, size_t nsources,
                                     const float *d_samples, size_t sample_stride, size_t nsamples,
                                     const int32_t *d_pairs, const int64_t *d_windows, size_t window_stride, size_t batch,
                                     double min_energy, int k, int64_t min_separation,
                                     int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
+/* Full-range normalised cross-correlation: asx_xcorr_ncc_f32_dev over the lags -(N-1) <= l <= N-1, so that a pair whose sample starts
+ * before the source has an entry too.  Lag -N has no overlap and does not exist for these calls.  N = sample_len, x = the source (2N
+ * float32), y = the sample (N float32).
+ *   Lags l >= 0.  Everything is that of asx_xcorr_ncc_f32_dev, word for word: mu, Sx[l], Vx[l], Sy, Vy, Vmax (the maximum of Vx[l] over
+ * the lags 0..N-1), c[l], c32[l] and the competing rule Vx[l] >= min_energy * Vmax.  c32[l] is bit for bit what
+ * asx_xcorr_ncc_debug_c_dev writes: the same transforms and the same moment kernels on the same chunks.
+ *   Lags l < 0.  The overlap is m = N + l frames and the segments are the reference's own (src/cross_correlation.c:256-262): x[0, m)
+ * against y[-l, N).  In float64, with a[n] = x[n] - mu (the same mu) and b[n] = y[n] - mean(y):
+ *     P1[m] = sum_{n<m} a[n],      P2[m] = sum_{n<m} a[n]^2
+ *     T1[m] = sum_{n>=N-m} b[n],   T2[m] = sum_{n>=N-m} b[n]^2
+ *     Sx[l] = P1[m] + m*mu         Vx[l] = P2[m] - P1[m]^2 / m
+ *     Sy[l] = T1[m] + m*mean(y)    Vy[l] = T2[m] - T1[m]^2 / m
+ *     c[l]  = (rlo32[2N + l] / s  -  Sx[l] * Sy[l] / m) / sqrt(Vx[l] * Vy[l]),   c32[l] = (float) c[l]
+ * rlo32 is the float32 r that the plan's transforms produce for the pair (x_lo, y), x_lo being x with the frames N..2N-1 set to zero,
+ * and s = asx_plan_fft_len().  With the upper half zero nothing wraps around: index 2N + l holds exactly the m wanted products.  (The
+ * difference r[2N + l] - corr(x_hi, y) is not formed: it would subtract two float32 numbers of the size of whatever fooled the raw
+ * search.)
+ *   Which negative lags compete.  Lag l < 0 competes iff m >= min_overlap, Vy > 0 (the whole sample's), Vx[l] * Vy[l] >= min_energy *
+ * Vmax * Vy, and c[l] is finite.  For l >= 0 the product rule would reduce to the NCC call's, which stays as it is.  The floor means
+ * the same on both sides: the error of r32 over the segment energies.  A lag within a relative 1e-6 of the threshold may fall on
+ * either side.  1 <= min_overlap <= N, anything else is refused; min_energy as in the NCC call.
+ *   Rows.  -(N-1) <= lag_min <= lag_max <= N-1; any other row gives (0, NaN, NaN, -2), the other pairs untouched bit for bit.
+ * d_windows == NULL means every lag -(N-1)..N-1; the plan's own window is ignored and left as it is.
+ *   The peak.  The largest |c32| among the competing lags of the row wins, the smallest (most negative) lag among equal float32
+ * values.  There is no signed seed.  If no lag competes: lag = the row's lag_min (-(N-1) without rows) and peak = 0.  It is the float32
+ * argmax, NOT the float64 argmax by construction, as in the NCC call.
+ *   Outputs per pair.  lag; coef: the direct Pearson form at the returned lag, under asx_plan_set_pearson(plan, 0) bit for bit what
+ * asx_xcorr_windowed_f32_dev returns for the row [lag, lag]; peak: (double)|c32[lag]|; ret: 0, -1 (a NaN coefficient) or -2.  Never 1.
+ *   Consequences.  (a) A pair with a row inside [0, N-1] returns, bit for bit, asx_xcorr_ncc_f32_dev's result for that row.  (b) With
+ * min_overlap == N no negative lag competes: the competing set and the peak value are the NCC call's, and a pair whose NCC result has
+ * a competing lag returns that result bit for bit.
+ *   Strides, broadcast (a stride of 0), strides below the track length, the layout rule, the stream rule, the refusals (plus
+ * min_overlap out of range) and what the call never does are the NCC call's.  The calls run on every plan, packed ones included.
+ * Every value of a pair is independent of the batch size and of the pair's position in the batch.  A broadcast track's moments, staged
+ * copy and tables are formed once per call.
+ *   Memory.  A set of its own, allocated at the plan's first full-range call and kept with the plan; not counted in
+ * asx_plan_workspace_bytes; refused inside a stream capture until it exists.  Per pair of one group: two r buffers (16N bytes; the
+ * top-k call keeps the curve in the halves of them that nothing reads), the staged x_lo (8N), the per-lag tables of the source for
+ * the lags >= 0 and < 0 (16N each) and of the sample (16N): 72N bytes, plus three doubles per 2048 frames of every track.  The call
+ * works in groups of min(asx_plan_group(), 2^30 / 72N) pairs, at least one, so the set holds at most 1 GiB (or one pair's 72N bytes).
+ *   Cost: two transform passes per group instead of one, the NCC call's moment passes, one pass over the first halves of the tracks
+ * for the tables of the negative lags and a peak pass over twice the lags: about twice the NCC call (measured: DESIGN.md).
+ *   Not offered: pools, and so asx_pool_closure_dev over full-range tables (the next step); the double ABI, streams, and a fused
+ * inverse pass. */
+int asx_xcorr_ncc_full_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                               const float *d_sample, size_t sample_stride,
+                               const int64_t *d_windows, size_t window_stride, size_t batch,
+                               double min_energy, int64_t min_overlap,
+                               int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+/* ... with the K strongest separated lags per pair, under asx_xcorr_ncc_topk_f32_dev's rule over the signed lags: A_0 is the row, or
+ * [-(N-1), N-1]; the zones are |l - lag_i| <= min_separation in signed lags, with no wrap between N-1 and -(N-1); an entry whose A_j
+ * holds no competing lag takes A_j's smallest lag with peak = 0; entries behind an empty A_j are (0, NaN, NaN, -3); a row that is not
+ * a row of this call gives (0, NaN, NaN, -2) in all k entries.  k = 1 launches exactly asx_xcorr_ncc_full_f32_dev, and entry 0 is
+ * always bit for bit the k = 1 result.  Refusals: those of that call, plus k and min_separation out of range. */
+int asx_xcorr_ncc_full_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                                    const float *d_sample, size_t sample_stride,
+                                    const int64_t *d_windows, size_t window_stride, size_t batch,
+                                    double min_energy, int64_t min_overlap, int k, int64_t min_separation,
+                                    int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+/* ONE contiguous pair, every lag competing under min_energy and min_overlap: c32 of the lags -(N-1)..N-1 to d_c (2N - 1 floats, lag l
+ * at index l + N - 1, NaN where the lag does not compete); the results are those of asx_xcorr_ncc_full_f32_dev for that pair without
+ * rows */
+int asx_xcorr_ncc_full_debug_c_dev(asx_plan *plan, const float *d_source, const float *d_sample, double min_energy,
+                                   int64_t min_overlap, float *d_c, int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret,
+                                   void *stream);
 
 /* Band-limited GCC-PHAT: asx_xcorr_phat_f32_dev in which only the bins of a frequency band vote.  Most material is band-limited
  * (speech, codecs that low-pass, hum and rumble at the bottom): outside its band the cross spectrum is rounding noise, and with

@@ -119,7 +119,7 @@ struct asx_plan {
 
     // Who owns the plan's device memory (asx_plan_workspace_bytes: all but the bank's and the NCC sets').  mem: what plan_init takes and, once created,
     // the lazy sets (big, bslot, st, st64: whole or absent); cxy0: lane 0's C_x / C_y, which tune_placement may replace; bank.mem; ncc.mem;
-    // ncc.tmem.
+    // ncc.tmem; nccfull.mem.
     AsxMemSet mem{ hip_mem }, cxy0{ hip_mem };
     // "Lanes": each owns the workspaces of one launch group and a stream.  With two lanes
     // (ASX_LANES=2) consecutive groups of a batch alternate lanes so that kernels of different
@@ -180,6 +180,15 @@ struct asx_plan {
         size_t nsrc = 0, nsmp = 0;
         unsigned long long built_src = 0, built_smp = 0;
     } ncc;
+    // The full-range NCC calls (asx_xcorr_ncc_full_f32_dev; lazy, whole or absent, allocated at the plan's first such call): what an
+    // NCC group holds (w: pass A's r, the tables of the lags >= 0, the small sums) and what the negative lags add (f: pass B's r, the
+    // staged sources, the prefix and suffix tables), for one group of `group` pairs.  Its own set, with its own bound
+    // (ensure_ncc_full): not part of asx_plan_workspace_bytes.
+    struct NccFull {
+        struct Set { AsxNccWs w{}; AsxNccFullWs f{}; } set;
+        AsxMemSet mem{ hip_mem };
+        size_t group = 0;
+    } nccfull;
     // pairs whose near-tie list overflowed since the list was last emptied (k_finalize appends, resolve_overflows reads)
     uint32_t *over_list = nullptr, *over_n = nullptr;
     volatile uint32_t *h_over_n = nullptr; // page-locked host mirror of *over_n (device-visible: AsxPeakWs::over_host)
@@ -2137,6 +2146,145 @@ extern "C" int asx_xcorr_ncc_debug_c_dev(asx_plan *p, const float *d_source, con
     const size_t N = p->host.N;
     return ncc_batch(p, "asx_xcorr_ncc_debug_c_dev", d_source, 2 * N, d_sample, N, nullptr, 0, 1, min_energy, d_c,
                      { d_lag, d_coef, d_ret, 1, d_peak }, stream);
+}
+
+// ---------------------------------------------------------------------------
+// full-range normalised cross-correlation (asx_xcorr_ncc_full_f32_dev): the lags -(N-1)..N-1, two transform passes per group
+// ---------------------------------------------------------------------------
+// The plan's full-range set, per pair of one group: two r buffers (16N bytes; a top-k group keeps the curve in the halves that nothing
+// reads), per source track the staged x_lo (8N) and the tables of the lags >= 0 and < 0 (16N each), per sample track the suffix table
+// (16N): ASX_NCCFULL_PAIR_BYTES * N bytes where every pair has tracks of its own, plus the chunk sums.
+#define ASX_NCCFULL_PAIR_BYTES 72
+static int ensure_ncc_full(asx_plan *p, const char *fn, hipStream_t s)
+{
+    if (p->nccfull.set.w.r) return 0;
+    if (stream_capturing(s))
+        return fail("%s: the plan's full-range NCC workspace does not exist yet and cannot be allocated during a stream capture; make "
+                    "one call outside the capture first", fn);
+    const size_t N = p->host.N, pitch = (2 * N + 3) & ~(size_t)3;
+    const size_t g = std::max<size_t>(1, std::min(p->group, ASX_NCC_WS_BYTES / (ASX_NCCFULL_PAIR_BYTES * N)));
+    const size_t chunks = g * ((size_t)asx_ncc_chunks((uint32_t)(2 * N)) + asx_ncc_chunks((uint32_t)N));
+    if (asx_mem_whole(p->nccfull.mem, p->nccfull.set, [&](AsxMemSet &m, asx_plan::NccFull::Set &T) {
+            T.f.pitch = pitch;
+            return m.take(&T.w.r, g * 2 * N) || m.take(&T.w.table, g * N) || m.take(&T.w.raw, chunks) || m.take(&T.w.m1, chunks) ||
+                           m.take(&T.w.m2, chunks) || m.take(&T.w.sstat, g * ASX_NCC_STAT) || m.take(&T.w.ystat, g * ASX_NCC_STAT) ||
+                           m.take(&T.w.best, g) || m.take(&T.w.tk, g) || m.take(&T.f.rlo, g * 2 * N) || m.take(&T.f.stage, g * pitch) ||
+                           m.take(&T.f.ptab, g * N) || m.take(&T.f.ttab, g * N)
+                       ? -1 : 0;
+        }))
+        return fail("%s: hipMalloc of the full-range NCC workspace failed: %s", fn, hipGetErrorString(g_take_err));
+    p->nccfull.group = g;
+    return 0;
+}
+
+// ncc_batch's sibling for the strided full-range calls, after the entry point's null checks and the top-k option's.  c_out: the debug
+// call's curve (one contiguous pair, 2N - 1 floats), else null.  topk.k > 1: y's entry stride is k.
+static int ncc_full_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
+                          size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, double min_energy,
+                          int64_t min_overlap, float *c_out, const Results &y, void *stream, const Topk &topk = {})
+{
+    if (!(min_energy >= ASX_NCC_MIN_ENERGY && min_energy <= 1.0)) // (a NaN fails both)
+        return fail("%s: min_energy %g is not in [%g, 1]", fn, min_energy, (double)ASX_NCC_MIN_ENERGY);
+    if (min_overlap < 1 || min_overlap > (int64_t)p->host.N)
+        return fail("%s: min_overlap %lld is not in [1, %zu]", fn, (long long)min_overlap, p->host.N);
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
+    const AsxDev &P = p->dev;
+    if (strided_layout(p, fn, d_source, source_stride, d_sample, sample_stride)) return -1;
+    if (batch == 0) return 0;
+    if (ensure_ncc_full(p, fn, s)) return -1;
+    int bc = 0;
+    if (strided_broadcast(p, fn, d_source, source_stride, d_sample, sample_stride, s, &bc)) return -1;
+    const Pairs<float> x = Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, bc, nullptr, 0);
+    asx_plan::Lane &L = p->lanes[0];
+    const AsxNccFullWs &F = p->nccfull.set.f;
+    const int K = topk.k;
+    // the slot holds one source spectrum: the shared source's for pass A, its x_lo's for pass B
+    auto slot_source = [&](const float *track) { asx_launch_fwd_cols_r(P, track, 0, nullptr, 0, 0, 1, p->bslot, true, s); };
+    prof_begin_call(p);
+    size_t gi = 0;
+    for (size_t done = 0; done < batch; done += p->nccfull.group, gi++) {
+        const size_t g = std::min(p->nccfull.group, batch - done);
+        const Pairs<float> xg = x.at(done);
+        const Results yg = y.at(done);
+        const int64_t *rows = d_windows ? d_windows + 2 * done * window_stride : nullptr;
+        AsxNccWs W = p->nccfull.set.w;
+        // a track every pair shares (a stride of 0, whatever the layout): its moments, x_lo and tables once per call, by the first group
+        W.nsrc = source_stride == 0 ? 1u : (uint32_t)g;
+        W.nsmp = sample_stride == 0 ? 1u : (uint32_t)g;
+        W.do_src = source_stride != 0 || done == 0;
+        W.do_smp = sample_stride != 0 || done == 0;
+        if (W.do_src) p->ncc.built_src += W.nsrc;
+        if (W.do_smp) p->ncc.built_smp += W.nsmp;
+        // pass A: the NCC call's own group on the caller's tracks -> r of the lags >= 0, then that call's moment kernels
+        if ((bc & 1) && done > 0) slot_source(d_source);
+        if (run_group(p, xg, g, yg, s, { .prof_group = gi, .listed = false, .f32_abi = false, .r_out = W.r, .transforms_only = true }))
+            return -1;
+        asx_launch_ncc_moments(W, xg.src, source_stride, xg.smp, sample_stride, P.N, s);
+        // pass B: the same samples against x_lo -> r of the lags < 0 without the products that wrap around
+        if (W.do_src) asx_launch_nccfull_stage(F, xg.src, source_stride, W.nsrc, P.N, s);
+        if (bc & 1) slot_source(F.stage);
+        const Pairs<float> xlo = Pairs<float>::strided(F.stage, source_stride == 0 ? 0 : F.pitch, xg.smp, sample_stride, bc, nullptr, 0);
+        if (run_group(p, xlo, g, yg, s, { .prof_group = GroupOpts::no_marks, .listed = false, .f32_abi = false, .r_out = F.rlo,
+                                          .transforms_only = true }))
+            return -1;
+        asx_launch_nccfull_prefix(W, F, xg.src, source_stride, xg.smp, sample_stride, P.N, s);
+        asx_launch_nccfull_peak(W, F, P.nout, P.N, (double)P.F, min_energy, min_overlap, rows, window_stride, c_out, L.seg, yg.peak, (int)g,
+                                s, K);
+        const AsxInputs<float> in = xg.inputs(nullptr);
+        if (K == 1) {
+            // the reference's coefficient of the samples at the winner, in the direct form
+            asx_launch_pearson(in, P.N, L.seg, L.psums, yg.lag, yg.coef, yg.ret, (int)g, s);
+            if (rows) asx_launch_nccfull_invalid(P.N, rows, window_stride, yg.lag, yg.coef, yg.peak, yg.ret, (int)g, s);
+        } else {
+            // ncc_batch's passes over the signed curve
+            for (int j = 0; j <= K; j++) {
+                if (j > 0 && j < K) asx_launch_nccfull_scan(W, F, P.nout, P.N, rows, window_stride, topk.sep, j, (int)g, s);
+                asx_launch_nccfull_step(W, P.N, rows, window_stride, topk.sep, j, K, L.seg, L.tk.lag, L.tk.coef, L.tk.ret, yg.lag, yg.coef,
+                                        yg.peak, yg.ret, (int)g, s);
+                if (j < K) asx_launch_pearson(in, P.N, L.seg, L.psums, L.tk.lag, L.tk.coef, L.tk.ret, (int)g, s);
+            }
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    prof_end_call(p, gi);
+    return 0;
+}
+
+extern "C" int asx_xcorr_ncc_full_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                          size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                          double min_energy, int64_t min_overlap, int64_t *d_lag, double *d_coef, double *d_peak,
+                                          int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_ncc_full_f32_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    return ncc_full_batch(p, fn, d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch, min_energy,
+                          min_overlap, nullptr, { d_lag, d_coef, d_ret, 1, d_peak }, stream);
+}
+
+// The K strongest separated lags of the full-range curve: k = 1 launches exactly asx_xcorr_ncc_full_f32_dev.
+extern "C" int asx_xcorr_ncc_full_topk_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                               size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                               double min_energy, int64_t min_overlap, int k, int64_t min_separation, int64_t *d_lag,
+                                               double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_ncc_full_topk_f32_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    if (!ncc_topk_option(fn, k, min_separation)) return -1;
+    return ncc_full_batch(p, fn, d_source, source_stride, d_sample, sample_stride, d_windows, window_stride, batch, min_energy,
+                          min_overlap, nullptr, { d_lag, d_coef, d_ret, (size_t)k, d_peak }, stream, Topk{ k, min_separation });
+}
+
+extern "C" int asx_xcorr_ncc_full_debug_c_dev(asx_plan *p, const float *d_source, const float *d_sample, double min_energy,
+                                              int64_t min_overlap, float *d_c, int64_t *d_lag, double *d_coef, double *d_peak,
+                                              int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_ncc_full_debug_c_dev";
+    if (!p || !d_source || !d_sample || !d_c || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    const size_t N = p->host.N;
+    return ncc_full_batch(p, fn, d_source, 2 * N, d_sample, N, nullptr, 0, 1, min_energy, min_overlap, d_c,
+                          { d_lag, d_coef, d_ret, 1, d_peak }, stream);
 }
 
 static int ensure_staging(asx_plan *p, bool with64 = false) // with64: one pair's float64 inputs too (asx_xcorr_f64)

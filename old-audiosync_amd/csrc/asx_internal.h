@@ -780,6 +780,44 @@ void asx_launch_ncctop_step(const AsxNccWs &W, uint32_t N, const int64_t *rows, 
 // behind the Pearson kernels: (0, NaN, NaN, -2) for every pair whose row is not a row of this call
 void asx_launch_ncc_invalid(uint32_t N, const int64_t *rows, size_t rows_step, int64_t *lag, double *coef, double *peak, int32_t *ret,
                             int npairs, hipStream_t s);
+// Full-range normalised cross-correlation (asx_xcorr_ncc_full_f32_dev; the k_nccfull_* kernels, ncc.hip): the lags -(N-1)..N-1, as
+// the indices i = l + N - 1 of one curve of 2N - 1 values (the smallest index is the smallest lag).  The lags >= 0 are the NCC call's
+// in every bit: W holds what that call's group holds, filled by the same kernels (pass A).  A lag l < 0 overlaps in m = N + l frames,
+// source[0, m) against sample[N - m, N): its r comes from a second correlation (pass B) of the sample against the staged source x_lo
+// (the first N frames, then zeros: nothing wraps around), its sums from prefix tables over the source and suffix tables over the sample.
+struct AsxNccFullWs {
+    float *rlo;    // [pairs][2N] r of (x_lo, y): index 2N + l = N + m holds the m products of lag l; the indices 0..N are read by nobody
+    float *stage;  // [nsrc][pitch] x_lo of the group's source tracks (the call's one broadcast track: staged by its first group)
+    size_t pitch;  // 2N rounded up to whole 16-byte vectors
+    double2 *ptab; // [nsrc][N] at index m = 1..N-1: {P1[m] = sum_{n<m} (x[n] - mu), Vx of x[0, m)}
+    double2 *ttab; // [nsmp][N] at index m = 1..N-1: {T1[m] = sum_{n>=N-m} (y[n] - mean y), Vy of y[N - m, N)}
+};
+// a row of the full-range calls: -(N-1) <= lag_min <= lag_max <= N-1
+__host__ __device__ inline bool asx_nccfull_row_ok(int64_t lo, int64_t hi, uint32_t N)
+{
+    return -((int64_t)N - 1) <= lo && lo <= hi && hi <= (int64_t)N - 1;
+}
+// k_nccfull_stage: x_lo of W.nsrc source tracks (src_pitch apart) into F.stage
+void asx_launch_nccfull_stage(const AsxNccFullWs &F, const float *src, size_t src_pitch, uint32_t nsrc, uint32_t N, hipStream_t s);
+// k_nccfull_prefix, behind asx_launch_ncc_moments on the same W and tracks (it starts from the chunk sums m1 / m2 and the means that
+// those kernels left): F.ptab of the source tracks (W.do_src) and F.ttab of the sample tracks (W.do_smp)
+void asx_launch_nccfull_prefix(const AsxNccWs &W, const AsxNccFullWs &F, const float *src, size_t src_pitch, const float *smp,
+                               size_t smp_pitch, uint32_t N, hipStream_t s);
+// k_nccfull_peak and k_nccfull_finalize: asx_launch_ncc_peak over the signed curve.  rows under asx_nccfull_row_ok (null: every lag);
+// a lag l < 0 competes only with an overlap of at least min_overlap frames.  c_out: null, or c32 of one pair's 2N - 1 lags.  k > 1: the
+// curve stays in the halves of the two r buffers that nothing reads (index i < N - 1 at F.rlo[i], the others at W.r[i + 1]),
+// k_nccfull_finalize does not run and asx_launch_nccfull_step(j = 0) takes the winner from W.best.
+void asx_launch_nccfull_peak(const AsxNccWs &W, const AsxNccFullWs &F, size_t r_pitch, uint32_t N, double scale, double min_energy,
+                             int64_t min_overlap, const int64_t *rows, size_t rows_step, float *c_out, AsxSeg *seg, double *peak,
+                             int npairs, hipStream_t s, int k = 1);
+// asx_launch_ncctop_scan / asx_launch_ncctop_step over the signed curve: the records hold indices, the zones do not wrap
+void asx_launch_nccfull_scan(const AsxNccWs &W, const AsxNccFullWs &F, size_t r_pitch, uint32_t N, const int64_t *rows, size_t rows_step,
+                             int64_t sep, int j, int npairs, hipStream_t s);
+void asx_launch_nccfull_step(const AsxNccWs &W, uint32_t N, const int64_t *rows, size_t rows_step, int64_t sep, int j, int k, AsxSeg *seg,
+                             const int64_t *tmp_lag, const double *tmp_coef, const int32_t *tmp_ret, int64_t *lag, double *coef,
+                             double *peak, int32_t *ret, int npairs, hipStream_t s);
+void asx_launch_nccfull_invalid(uint32_t N, const int64_t *rows, size_t rows_step, int64_t *lag, double *coef, double *peak,
+                                int32_t *ret, int npairs, hipStream_t s);
 void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t s);
 unsigned asx_pearson_blocks(uint32_t basis_len); // partial blocks per pair: psums holds 6 doubles per block and pair
 // second look, DC removal: stats[0] = mean of source[0..2N), stats[1] = sum of sample[0..N), stats[2] = scale * stats[0] * stats[1]

@@ -437,3 +437,316 @@ void asx_launch_ncc_invalid(uint32_t N, const int64_t *rows, size_t rows_step, i
     hipLaunchKernelGGL(k_ncc_invalid, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, N, rows, rows_step, lag, coef, peak, ret,
                        npairs);
 }
+
+// ---- the full range (asx_xcorr_ncc_full_f32_dev and its top-k form): the lags -(N-1)..N-1 ----------------------------------------
+// The curve has 2N - 1 values, index i = l + N - 1.  Its upper half (l >= 0) is k_ncc_peak's in every bit: the same moment kernels on
+// the same chunks, the same r32 (pass A) and the same expression.  A lag l < 0 overlaps in m = N + l = i + 1 frames, source[0, m)
+// against sample[N - m, N), the reference's own segments; its r is rlo32[2N + l] of pass B, which ran on x_lo (AsxNccFullWs).
+//   k_nccfull_stage    grid (vectors of a staged track, source tracks): x_lo = the first N frames, then zeros
+//   k_nccfull_prefix   grid (2 chunks(N), tracks): block c of a source track starts from the chunk sums m1 / m2 of the chunks before c
+//                      and scans its 2048 frames forwards -> {P1[m], Vx}; block c of a sample track starts from the chunks behind c and
+//                      scans its frames backwards -> {T1[m], Vy}; thread, lanes, waves, as k_ncc_table scans
+//   k_nccfull_peak     grid (chunks of the 2N - 1 indices, pairs): c32 of both halves, the row and the two competing rules, the packed
+//                      (|c32|, smallest index) maximum; optionally the curve
+//   k_nccfull_finalize / k_nccfull_invalid, k_nccfull_scan / k_nccfull_step: the tails of the one-lag and the top-k call in indices
+// (k_nccfull_*, not k_ncc_*: see the note at k_ncctop_scan.)
+__global__ __launch_bounds__(NCC_NT) void k_nccfull_stage(AsxNccFullWs F, const float *__restrict__ src, size_t src_pitch, uint32_t N)
+{
+    const size_t v = (size_t)blockIdx.x * NCC_NT + threadIdx.x;
+    if (4 * v >= F.pitch) return;
+    const float *x = src + (size_t)blockIdx.y * src_pitch;
+    const uint32_t f = (uint32_t)(4 * v);
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (f + 3 < N && ((uintptr_t)x & 15u) == 0) o = *reinterpret_cast<const float4 *>(x + f);
+    else {
+        if (f < N) o.x = x[f];
+        if (f + 1 < N) o.y = x[f + 1];
+        if (f + 2 < N) o.z = x[f + 2];
+        if (f + 3 < N) o.w = x[f + 3];
+    }
+    *reinterpret_cast<float4 *>(F.stage + (size_t)blockIdx.y * F.pitch + f) = o;
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_nccfull_prefix(AsxNccWs W, AsxNccFullWs F, const float *__restrict__ src, size_t src_pitch,
+                                                            const float *__restrict__ smp, size_t smp_pitch, uint32_t N)
+{
+    __shared__ double lds[2 * (NCC_NT / 64)];
+    __shared__ float fr[ASX_NCC_CHUNK];
+    const uint32_t nsc = asx_ncc_chunks(2u * N), nyc = asx_ncc_chunks(N), t = blockIdx.y;
+    const bool back = blockIdx.x >= nyc; // a sample track: the suffix sums
+    const uint32_t c = back ? blockIdx.x - nyc : blockIdx.x, f0 = c * ASX_NCC_CHUNK;
+    if (back ? (t >= W.nsmp || !W.do_smp) : (t >= W.nsrc || !W.do_src)) return;
+    const float *x = back ? smp + (size_t)t * smp_pitch : src + (size_t)t * src_pitch;
+    const double mu = (back ? W.ystat : W.sstat)[(size_t)t * ASX_NCC_STAT];
+    // the chunk's frames of the first N (zero past them), in scan order: a sample's chunk from its last frame down
+#pragma unroll
+    for (int j = 0; j < NCC_PER; j++) {
+        const uint32_t i = j * NCC_NT + threadIdx.x, f = f0 + i;
+        fr[back ? ASX_NCC_CHUNK - 1 - i : i] = f < N ? x[f] : 0.f;
+    }
+    // where the scan starts: the whole chunks in front of c (behind c), which lie inside the first N frames (a sample's last chunk
+    // holds the sums of its own frames only)
+    const size_t at = back ? (size_t)W.nsrc * nsc + (size_t)t * nyc + c + 1 : (size_t)t * nsc;
+    double w1, w2;
+    ncc_sum_arrays(W.m1 + at, W.m2 + at, back ? nyc - 1 - c : c, w1, w2, lds); // (its first barrier also puts fr in place)
+    // the thread's eight consecutive places 8 tid + k: the inclusive prefix inside the thread, ...
+    double p1[NCC_PER], p2[NCC_PER], t1 = 0.0, t2 = 0.0;
+    const uint32_t j0 = threadIdx.x * NCC_PER;
+#pragma unroll
+    for (int k = 0; k < NCC_PER; k++) {
+        const uint32_t f = back ? f0 + ASX_NCC_CHUNK - 1 - (j0 + k) : f0 + j0 + k;
+        const double a = f < N ? (double)fr[j0 + k] - mu : 0.0;
+        t1 += a;
+        t2 += a * a;
+        p1[k] = t1; p2[k] = t2;
+    }
+    // ... across the lanes (an inclusive scan of the threads' totals), across the waves
+    double i1 = t1, i2 = t2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double u1 = __shfl_up(i1, off, 64), u2 = __shfl_up(i2, off, 64);
+        if (lane >= off) { i1 += u1; i2 += u2; }
+    }
+    __syncthreads();
+    if (lane == 63) { lds[wave] = i1; lds[NCC_NT / 64 + wave] = i2; }
+    __syncthreads();
+    double o1 = __shfl_up(i1, 1, 64), o2 = __shfl_up(i2, 1, 64); // exclusive in the wave
+    if (lane == 0) { o1 = 0.0; o2 = 0.0; }
+    for (int w = 0; w < wave; w++) { o1 += lds[w]; o2 += lds[NCC_NT / 64 + w]; }
+    double2 *tab = (back ? F.ttab : F.ptab) + (size_t)t * N;
+#pragma unroll
+    for (int k = 0; k < NCC_PER; k++) {
+        // the overlap whose sums end at this place: frames [0, f] of a source, [f, N) of a sample
+        const uint32_t f = back ? f0 + ASX_NCC_CHUNK - 1 - (j0 + k) : f0 + j0 + k;
+        const uint32_t m = back ? N - f : f + 1;
+        if (f < N && m >= 1 && m < N) {
+            const double s1 = w1 + (o1 + p1[k]), s2 = w2 + (o2 + p2[k]);
+            tab[m] = make_double2(s1, s2 - s1 * s1 / (double)m);
+        }
+    }
+}
+
+// c_out: c32 of pair i's index j to c_out[i * c_pitch + j] (the debug call), or null.  keep: a top-k group -- c32 also goes to the
+// halves of the pair's two r buffers that this kernel does not read (index j < N - 1 to rlo[j], the others to r[j + 1]).
+__global__ __launch_bounds__(NCC_NT) void k_nccfull_peak(AsxNccWs W, AsxNccFullWs F, size_t r_pitch, uint32_t N, double scale,
+                                                          double min_energy, int64_t min_overlap, const int64_t *__restrict__ rows,
+                                                          size_t rows_step, float *__restrict__ c_out, size_t c_pitch, bool keep)
+{
+    __shared__ asx_peak_t red[NCC_NT / 64];
+    const size_t pair = blockIdx.y;
+    const size_t ts = W.nsrc > 1 ? pair : 0, ty = W.nsmp > 1 ? pair : 0;
+    const double *sx = W.sstat + ts * ASX_NCC_STAT, *sy = W.ystat + ty * ASX_NCC_STAT;
+    const double mu = sx[0], floor_v = min_energy * sx[1], my = sy[0], Sy = sy[2], Vy = sy[3], dN = (double)N;
+    const int64_t n1 = (int64_t)N - 1;
+    int64_t lo = -n1, hi = n1;
+    if (rows) {
+        lo = rows[2 * pair * rows_step]; hi = rows[2 * pair * rows_step + 1];
+        if (!asx_nccfull_row_ok(lo, hi, N)) { lo = 1; hi = 0; } // holds no lag
+    }
+    const double2 *tab = W.table + ts * N, *pt = F.ptab + ts * N, *tt = F.ttab + ty * N;
+    float *ra = W.r + pair * r_pitch, *rl = F.rlo + pair * r_pitch;
+    const uint32_t i0 = blockIdx.x * ASX_NCC_CHUNK, span = 2u * N - 1u;
+    asx_peak_t best = 0;
+#pragma unroll 2
+    for (int j = 0; j < NCC_PER; j++) {
+        const uint32_t i = i0 + j * NCC_NT + threadIdx.x;
+        if (i >= span) break;
+        double c;
+        bool competes;
+        if (i >= N - 1u) {
+            // (k_ncc_peak's lines: the same bits)
+            const uint32_t l = i - (N - 1u);
+            const double2 e = tab[l];
+            const double Sx = e.x + dN * mu;
+            c = ((double)ra[l] / scale - Sx * Sy / dN) / sqrt(e.y * Vy);
+            competes = Vy > 0.0 && e.y >= floor_v && fabs(c) <= 1.7976931348623157e308;
+        } else {
+            const uint32_t m = i + 1u; // the overlap; l = m - N, and r of its m products is at index 2N + l = N + m
+            const double2 p = pt[m], q = tt[m];
+            const double dm = (double)m, Sxl = p.x + dm * mu, Syl = q.x + dm * my, vv = p.y * q.y;
+            c = ((double)rl[N + m] / scale - Sxl * Syl / dm) / sqrt(vv);
+            competes = (int64_t)m >= min_overlap && Vy > 0.0 && vv >= floor_v * Vy && fabs(c) <= 1.7976931348623157e308;
+        }
+        const float c32 = (float)c;
+        const float v = competes ? c32 : NAN;
+        if (c_out) c_out[pair * c_pitch + i] = v;
+        if (keep) { if (i < N - 1u) rl[i] = v; else ra[i + 1u] = v; }
+        const int64_t l = (int64_t)i - n1;
+        if (competes && l >= lo && l <= hi) best = peak_max(best, peak_pack_key(fabsf(c32), i));
+    }
+    best = block_peak_max(best, red);
+    if (threadIdx.x == 0 && best) atomicMax(&W.best[pair], best);
+}
+
+// the segment of the curve's index i: the lag l = i - (N - 1) as the circular index the windowed call would have found it at
+__device__ __forceinline__ AsxSeg nccfull_seg(uint32_t i, uint32_t N) { return make_seg(i >= N - 1u ? i - (N - 1u) : N + 1u + i, N); }
+
+__global__ __launch_bounds__(NCC_NT) void k_nccfull_finalize(AsxNccWs W, uint32_t N, const int64_t *__restrict__ rows, size_t rows_step,
+                                                              AsxSeg *__restrict__ seg, double *__restrict__ peak, int npairs)
+{
+    const int pair = blockIdx.x * NCC_NT + threadIdx.x;
+    if (pair >= npairs) return;
+    const asx_peak_t best = W.best[pair];
+    uint32_t first = 0; // no lag competes: the row's lag_min (an invalid row: the first lag, and k_nccfull_invalid writes its results)
+    if (rows) {
+        const int64_t lo = rows[2 * (size_t)pair * rows_step], hi = rows[2 * (size_t)pair * rows_step + 1];
+        if (asx_nccfull_row_ok(lo, hi, N)) first = (uint32_t)(lo + (int64_t)N - 1);
+    }
+    seg[pair] = nccfull_seg(best ? peak_index(best) : first, N);
+    peak[pair] = best ? (double)peak_key(best) : 0.0;
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_nccfull_invalid(uint32_t N, const int64_t *__restrict__ rows, size_t rows_step,
+                                                             int64_t *__restrict__ lag, double *__restrict__ coef,
+                                                             double *__restrict__ peak, int32_t *__restrict__ ret, int npairs)
+{
+    const int pair = blockIdx.x * NCC_NT + threadIdx.x;
+    if (pair >= npairs) return;
+    if (asx_nccfull_row_ok(rows[2 * (size_t)pair * rows_step], rows[2 * (size_t)pair * rows_step + 1], N)) return;
+    if (lag) lag[pair] = 0;
+    coef[pair] = (double)NAN;
+    peak[pair] = (double)NAN;
+    ret[pair] = -2;
+}
+
+// k_ncctop_scan over the 2N - 1 indices: the record's lags are indices, and a zone is clipped at the curve's two ends (no wrap)
+__global__ __launch_bounds__(NCC_NT) void k_nccfull_scan(AsxNccWs W, AsxNccFullWs F, size_t r_pitch, uint32_t N,
+                                                          const int64_t *__restrict__ rows, size_t rows_step, int64_t sep, int j)
+{
+    __shared__ asx_peak_t red[NCC_NT / 64];
+    const size_t pair = blockIdx.y;
+    const AsxNccTopk *T = W.tk + pair;
+    if (T->flags) return; // (the whole block: an invalid row, or no lag was left for an earlier entry)
+    const uint32_t span = 2u * N - 1u;
+    int64_t lo = 0, hi = (int64_t)span - 1;
+    if (rows) { lo = rows[2 * pair * rows_step] + (int64_t)N - 1; hi = rows[2 * pair * rows_step + 1] + (int64_t)N - 1; }
+    uint32_t zlo[ASX_TOPK_MAX - 1], zwd[ASX_TOPK_MAX - 1];
+#pragma unroll
+    for (int i = 0; i < ASX_TOPK_MAX - 1; i++) {
+        zlo[i] = ~0u; zwd[i] = 0u;
+        if (i < j) ncctop_zone(T->lag[i], sep, span, zlo[i], zwd[i]);
+    }
+    const float *ca = W.r + pair * r_pitch + 1, *cl = F.rlo + pair * r_pitch;
+    const uint32_t i0 = blockIdx.x * ASX_NCC_CHUNK;
+    asx_peak_t best = 0;
+#pragma unroll 2
+    for (int q = 0; q < NCC_PER; q++) {
+        const uint32_t l = i0 + q * NCC_NT + threadIdx.x;
+        if (l >= span) break;
+        const float v = l < N - 1u ? cl[l] : ca[l];
+        bool in = v == v && (int64_t)l >= lo && (int64_t)l <= hi;
+#pragma unroll
+        for (int i = 0; i < ASX_TOPK_MAX - 1; i++) in = in && l - zlo[i] > zwd[i];
+        if (in) best = peak_max(best, peak_pack_key(fabsf(v), l));
+    }
+    best = block_peak_max(best, red);
+    if (threadIdx.x == 0 && best) atomicMax(&W.best[pair], best);
+}
+
+// k_ncctop_step in indices
+__global__ __launch_bounds__(NCC_NT) void k_nccfull_step(AsxNccWs W, uint32_t N, const int64_t *__restrict__ rows, size_t rows_step,
+                                                          int64_t sep, int j, int k, AsxSeg *__restrict__ seg,
+                                                          const int64_t *__restrict__ tmp_lag, const double *__restrict__ tmp_coef,
+                                                          const int32_t *__restrict__ tmp_ret, int64_t *__restrict__ lag,
+                                                          double *__restrict__ coef, double *__restrict__ peak, int32_t *__restrict__ ret,
+                                                          int npairs)
+{
+    const int pair = blockIdx.x * NCC_NT + threadIdx.x;
+    if (pair >= npairs) return;
+    AsxNccTopk *T = W.tk + pair;
+    const uint32_t span = 2u * N - 1u;
+    int64_t lo = 0, hi = (int64_t)span - 1;
+    bool row_ok = true;
+    if (rows) {
+        const int64_t a = rows[2 * (size_t)pair * rows_step], b = rows[2 * (size_t)pair * rows_step + 1];
+        row_ok = asx_nccfull_row_ok(a, b, N);
+        if (row_ok) { lo = a + (int64_t)N - 1; hi = b + (int64_t)N - 1; }
+    }
+    uint32_t n = 0, flags = 0;
+    if (j == 0) { if (!row_ok) flags = ASX_NCC_TK_INVALID; }
+    else { n = T->n; flags = T->flags; }
+    if (j > 0) {
+        const size_t e = (size_t)pair * (size_t)k + (size_t)(j - 1);
+        const bool none = flags & ASX_NCC_TK_INVALID || n < (uint32_t)j; // n < j: no lag was left for this entry
+        if (lag) lag[e] = none ? 0 : tmp_lag[pair];
+        coef[e] = none ? (double)NAN : tmp_coef[pair];
+        peak[e] = none ? (double)NAN : T->peak;
+        ret[e] = flags & ASX_NCC_TK_INVALID ? -2 : none ? -3 : tmp_ret[pair];
+    }
+    if (j >= k) return;
+    const asx_peak_t best = W.best[pair];
+    W.best[pair] = 0;
+    uint32_t at = N - 1u; // (an entry that is not to be: lag 0's segment, whose coefficient the next step drops)
+    if (!flags) {
+        double height = 0.0;
+        bool have = true;
+        if (best) { at = peak_index(best); height = (double)peak_key(best); }
+        else {
+            // no lag of A_j competes: its smallest lag, the row's lag_min pushed past every zone that holds it
+            int64_t cand = lo;
+            for (int round = 0; round <= j; round++) {
+                bool moved = false;
+                for (int i = 0; i < j; i++) {
+                    uint32_t zlo, zwd;
+                    ncctop_zone(T->lag[i], sep, span, zlo, zwd);
+                    if (cand >= (int64_t)zlo && cand <= (int64_t)zlo + (int64_t)zwd) { cand = (int64_t)zlo + (int64_t)zwd + 1; moved = true; }
+                }
+                if (!moved) break;
+            }
+            have = cand <= hi;
+            if (have) at = (uint32_t)cand;
+        }
+        if (have) { T->lag[j] = (int64_t)at; T->peak = height; n = (uint32_t)j + 1u; }
+        else flags = ASX_NCC_TK_EMPTY;
+    }
+    T->n = n;
+    T->flags = flags;
+    seg[pair] = nccfull_seg(at, N);
+}
+
+void asx_launch_nccfull_stage(const AsxNccFullWs &F, const float *src, size_t src_pitch, uint32_t nsrc, uint32_t N, hipStream_t s)
+{
+    const unsigned nv = (unsigned)(F.pitch / 4);
+    hipLaunchKernelGGL(k_nccfull_stage, dim3((nv + NCC_NT - 1) / NCC_NT, nsrc), dim3(NCC_NT), 0, s, F, src, src_pitch, N);
+}
+
+void asx_launch_nccfull_prefix(const AsxNccWs &W, const AsxNccFullWs &F, const float *src, size_t src_pitch, const float *smp,
+                               size_t smp_pitch, uint32_t N, hipStream_t s)
+{
+    if (!W.do_src && !W.do_smp) return;
+    const unsigned nyc = asx_ncc_chunks(N), nt = W.nsrc > W.nsmp ? W.nsrc : W.nsmp;
+    hipLaunchKernelGGL(k_nccfull_prefix, dim3(2 * nyc, nt), dim3(NCC_NT), 0, s, W, F, src, src_pitch, smp, smp_pitch, N);
+}
+
+void asx_launch_nccfull_peak(const AsxNccWs &W, const AsxNccFullWs &F, size_t r_pitch, uint32_t N, double scale, double min_energy,
+                             int64_t min_overlap, const int64_t *rows, size_t rows_step, float *c_out, AsxSeg *seg, double *peak,
+                             int npairs, hipStream_t s, int k)
+{
+    (void)hipMemsetAsync(W.best, 0, (size_t)npairs * sizeof(asx_peak_t), s);
+    hipLaunchKernelGGL(k_nccfull_peak, dim3(asx_ncc_chunks(2u * N - 1u), npairs), dim3(NCC_NT), 0, s, W, F, r_pitch, N, scale, min_energy,
+                       min_overlap, rows, rows_step, c_out, (size_t)(2u * N - 1u), k > 1);
+    if (k > 1) return;
+    hipLaunchKernelGGL(k_nccfull_finalize, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, W, N, rows, rows_step, seg, peak, npairs);
+}
+
+void asx_launch_nccfull_scan(const AsxNccWs &W, const AsxNccFullWs &F, size_t r_pitch, uint32_t N, const int64_t *rows, size_t rows_step,
+                             int64_t sep, int j, int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_nccfull_scan, dim3(asx_ncc_chunks(2u * N - 1u), npairs), dim3(NCC_NT), 0, s, W, F, r_pitch, N, rows, rows_step, sep, j);
+}
+
+void asx_launch_nccfull_step(const AsxNccWs &W, uint32_t N, const int64_t *rows, size_t rows_step, int64_t sep, int j, int k, AsxSeg *seg,
+                             const int64_t *tmp_lag, const double *tmp_coef, const int32_t *tmp_ret, int64_t *lag, double *coef,
+                             double *peak, int32_t *ret, int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_nccfull_step, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, W, N, rows, rows_step, sep, j, k, seg, tmp_lag,
+                       tmp_coef, tmp_ret, lag, coef, peak, ret, npairs);
+}
+
+void asx_launch_nccfull_invalid(uint32_t N, const int64_t *rows, size_t rows_step, int64_t *lag, double *coef, double *peak,
+                                int32_t *ret, int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_nccfull_invalid, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, N, rows, rows_step, lag, coef, peak, ret,
+                       npairs);
+}

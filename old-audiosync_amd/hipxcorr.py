@@ -69,6 +69,9 @@ _HEADER_SIGNATURES = {
     "asx_xcorr_pool_ncc_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _dbl, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_ncc_topk_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _dbl, _int, _i64, _vp, _vp, _vp, _vp,
                                                _vp]),
+    "asx_xcorr_ncc_full_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_ncc_full_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_ncc_full_debug_c_dev": (_int, [_vp, _vp, _vp, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_band_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_sub_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -527,6 +530,30 @@ def ncc_topk_args(n, source, sample, k, min_separation, windows=None, min_energy
     + (k, min_separation).  ValueError on anything else."""
     option = _topk_option(k, min_separation)
     return ncc_args(n, source, sample, windows, min_energy) + option
+
+
+def _overlap_option(n, min_overlap):
+    """-> min_overlap as an int; None: (N + 1) // 2.  ValueError unless it is an integer (no bool) with 1 <= min_overlap <= N"""
+    if min_overlap is None:
+        return (n + 1) // 2
+    if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, np.integer)) or not 1 <= int(min_overlap) <= n:
+        raise ValueError("min_overlap must be an integer in [1, %d], not %r" % (n, min_overlap))
+    return int(min_overlap)
+
+
+def ncc_full_args(n, source, sample, windows=None, min_energy=1e-3, min_overlap=None):
+    """Host checks of Plan.xcorr_ncc_full_f32: ncc_args' checks (windows=None: every lag -(N-1)..N-1, no rows), and min_overlap as an
+    integer in [1, N] (None: (N + 1) // 2).  -> ncc_args' tuple + (min_overlap,).  ValueError on anything else.  The rows' values are
+    not checked: a row outside [-(N-1), N-1] comes back as ret = -2."""
+    option = _overlap_option(n, min_overlap)
+    return ncc_args(n, source, sample, windows, min_energy) + (option,)
+
+
+def ncc_full_topk_args(n, source, sample, k, min_separation, windows=None, min_energy=1e-3, min_overlap=None):
+    """Host checks of Plan.xcorr_ncc_full_topk_f32: ncc_full_args' checks, and k and min_separation as topk_args checks them.  ->
+    ncc_full_args' tuple + (k, min_separation).  ValueError on anything else."""
+    option = _topk_option(k, min_separation)
+    return ncc_full_args(n, source, sample, windows, min_energy, min_overlap) + option
 
 
 def topk_args(n, source, sample, k, min_separation, windows=None):
@@ -1127,6 +1154,30 @@ class Plan:
         _check(lib().asx_xcorr_ncc_debug_c_dev(self._h, d_src or None, d_smp or None, float(min_energy), d_c or None, d_lag or None,
                                                d_coef or None, d_peak or None, d_ret or None, stream or None))
 
+    def xcorr_ncc_full_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, min_energy, min_overlap,
+                           d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_ncc_full_f32_dev -- xcorr_ncc_dev over the lags -(N-1)..N-1; a negative lag competes
+        with an overlap of at least min_overlap frames; d_windows = 0: every lag, else per-pair rows inside [-(N-1), N-1]"""
+        _check(lib().asx_xcorr_ncc_full_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride),
+                                                d_windows or None, int(window_stride), int(batch), float(min_energy), int(min_overlap),
+                                                d_lag or None, d_coef or None, d_peak or None, d_ret or None, stream or None))
+
+    def xcorr_ncc_full_topk_dev(self, d_src, src_stride, d_smp, smp_stride, d_windows, window_stride, batch, min_energy, min_overlap, k,
+                                min_separation, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_ncc_full_topk_f32_dev -- xcorr_ncc_full_dev with the k strongest lags of the signed
+        curve at least min_separation apart, entry j of pair i at index i*k + j of d_lag / d_coef / d_peak / d_ret"""
+        _check(lib().asx_xcorr_ncc_full_topk_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride),
+                                                     d_windows or None, int(window_stride), int(batch), float(min_energy),
+                                                     int(min_overlap), int(k), int(min_separation), d_lag or None, d_coef or None,
+                                                     d_peak or None, d_ret or None, stream or None))
+
+    def ncc_full_debug_c_dev(self, d_src, d_smp, min_energy, min_overlap, d_c, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """asx_xcorr_ncc_full_debug_c_dev: one contiguous pair, c32 of the lags -(N-1)..N-1 to d_c (2N - 1 floats, lag l at index
+        l + N - 1, NaN where the lag does not compete)"""
+        _check(lib().asx_xcorr_ncc_full_debug_c_dev(self._h, d_src or None, d_smp or None, float(min_energy), int(min_overlap),
+                                                    d_c or None, d_lag or None, d_coef or None, d_peak or None, d_ret or None,
+                                                    stream or None))
+
     def phat_debug_r_dev(self, d_src, d_smp, d_r, d_lag, d_coef, d_peak, d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_phat_debug_r_dev -- one contiguous pair, r_phat of all 2N lags (times F) to d_r"""
         _check(lib().asx_xcorr_phat_debug_r_dev(self._h, d_src or None, d_smp or None, d_r or None, d_lag or None, d_coef or None,
@@ -1567,6 +1618,25 @@ class Plan:
         s, t, w, batch, ss, ts, ws, me, k, sep = ncc_topk_args(self.sample_len, source, sample, k, min_separation, windows, min_energy)
         return self._staged((s, t, w), (batch, k), _PHAT_RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_ncc_topk_dev(
             d_s, ss, d_t, ts, d_w, ws, batch, me, k, sep, *d_out))
+
+    def xcorr_ncc_full_f32(self, source, sample, windows=None, min_energy=1e-3, min_overlap=None):
+        """Pairs ranked by the full-range normalised cross-correlation (asx_xcorr_ncc_full_f32_dev): the Pearson coefficient of every
+        lag -(N-1)..N-1.  source, sample and min_energy as in xcorr_ncc_f32; windows: None (every lag), or integers [2] / [B, 2] rows
+        inside [-(N-1), N-1]; min_overlap: the fewest frames a negative lag must overlap in to compete, 1..N (None: (N + 1) // 2).
+        Arguments are checked on the host (ValueError) before anything is uploaded.  Returns (lag, coef, peak, ret) as xcorr_ncc_f32."""
+        s, t, w, batch, ss, ts, ws, me, mo = ncc_full_args(self.sample_len, source, sample, windows, min_energy, min_overlap)
+        return self._staged((s, t, w), (batch,), _PHAT_RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_ncc_full_dev(
+            d_s, ss, d_t, ts, d_w, ws, batch, me, mo, *d_out))
+
+    def xcorr_ncc_full_topk_f32(self, source, sample, k, min_separation, windows=None, min_energy=1e-3, min_overlap=None):
+        """The k strongest separated lags per pair of the full-range curve (asx_xcorr_ncc_full_topk_f32_dev): the arguments of
+        xcorr_ncc_full_f32, k and min_separation as in xcorr_topk_f32.  Arguments are checked on the host (ValueError) before
+        anything is uploaded.  Returns (lag, coef, peak, ret) of shape [B, k]; ret = -3 (and NaN for coef and peak) where no lag was
+        left.  Entry 0 is xcorr_ncc_full_f32's result."""
+        s, t, w, batch, ss, ts, ws, me, mo, k, sep = ncc_full_topk_args(self.sample_len, source, sample, k, min_separation, windows,
+                                                                        min_energy, min_overlap)
+        return self._staged((s, t, w), (batch, k), _PHAT_RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_ncc_full_topk_dev(
+            d_s, ss, d_t, ts, d_w, ws, batch, me, mo, k, sep, *d_out))
 
     def xcorr_pool_ncc_f32(self, sources, samples, pairs=None, windows=None, min_energy=1e-3):
         """Pairs of two pools ranked by the normalised cross-correlation (asx_xcorr_pool_ncc_f32_dev): the pools and pairs of
