@@ -2130,6 +2130,45 @@ extern "C" int asx_plan_debug_ncc(asx_plan *p, uint64_t out[4])
     return 0;
 }
 
+// diagnostic (not in the public header): the float64 tables behind the coefficient, as the last call left them in one of the plan's
+// sets.  which: 0 the NCC set (the tracks of the last NCC group; one track where the stride was 0), 1 the pool calls' track set,
+// 2 the full-range set (as 0, plus the two tables of the negative lags).
+//   sstat[2]  the source track's mu and Vmax          ystat[3]  the sample track's mean, Sy, Vy
+//   table     [N] {Sx' (mu-shifted), Vx} of the lags 0..N-1, as 2N doubles
+//   ptab, ttab  which = 2 only, else ignored: [N] {P1[m], Vx of x[0, m)} and {T1[m], Vy of y[N - m, N)} as 2N doubles each; the
+//             entries m = 1..N-1 are copied, entry 0 (which no kernel writes) is left as the caller had it
+// An output may be null: it is not copied.  Synchronises the device; launches nothing and changes nothing.
+extern "C" int asx_plan_debug_ncc_tables(asx_plan *p, int which, size_t source_track, size_t sample_track, double *sstat, double *ystat,
+                                         double *table, double *ptab, double *ttab)
+{
+    static const char *fn = "asx_plan_debug_ncc_tables";
+    if (!p) return fail("%s: null plan", fn);
+    if (which < 0 || which > 2) return fail("%s: which = %d is not 0 (strided), 1 (pool) or 2 (full)", fn, which);
+    PlanCall c(p);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    const AsxNccWs &W = which == 0 ? p->ncc.w : which == 1 ? p->ncc.tracks : p->nccfull.set.w;
+    const size_t ns = which == 0 ? p->ncc.group : which == 1 ? p->ncc.nsrc : p->nccfull.group;
+    const size_t nm = which == 1 ? p->ncc.nsmp : ns;
+    if (!W.table) return fail("%s: the plan has no such set yet (which = %d): make a call that fills it first", fn, which);
+    if (source_track >= ns || sample_track >= nm)
+        return fail("%s: track (%zu, %zu) is outside the set's %zu source and %zu sample tracks", fn, source_track, sample_track, ns, nm);
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t N = p->host.N;
+    if (sstat) HIP_TRY(hipMemcpy(sstat, W.sstat + source_track * ASX_NCC_STAT, 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (ystat) {
+        double st[ASX_NCC_STAT];
+        HIP_TRY(hipMemcpy(st, W.ystat + sample_track * ASX_NCC_STAT, sizeof st, hipMemcpyDeviceToHost));
+        ystat[0] = st[0]; ystat[1] = st[2]; ystat[2] = st[3];
+    }
+    if (table) HIP_TRY(hipMemcpy(table, W.table + source_track * N, N * sizeof(double2), hipMemcpyDeviceToHost));
+    if (which == 2 && N > 1) {
+        const AsxNccFullWs &F = p->nccfull.set.f;
+        if (ptab) HIP_TRY(hipMemcpy(ptab + 2, F.ptab + source_track * N + 1, (N - 1) * sizeof(double2), hipMemcpyDeviceToHost));
+        if (ttab) HIP_TRY(hipMemcpy(ttab + 2, F.ttab + sample_track * N + 1, (N - 1) * sizeof(double2), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
 extern "C" int asx_xcorr_ncc_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
                                      size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch,
                                      double min_energy, int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream)

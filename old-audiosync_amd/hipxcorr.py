@@ -132,6 +132,7 @@ _DIAGNOSTIC_SIGNATURES = {
     "asx_plan_debug_kernels": (_int, [_vp, c_intp, c_intp, c_intp]),
     "asx_plan_debug_bank": (_int, [_vp, _u64p, _u64p, _u64p]),
     "asx_plan_debug_ncc": (_int, [_vp, _u64p]),
+    "asx_plan_debug_ncc_tables": (_int, [_vp, _int, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "asx_plan_debug_prune": (_int, [_vp, _sz, c_f32p, c_intp, _sz]),
     "asx_plan_debug_peak": (_int, [_vp, _sz, c_f32p, _u32p, _u32p, _u64p, _vp, _vp, _sz]),
     "asx_plan_debug_spectral": (_int, [_vp, _sz, c_intp, _vp, _sz, c_f64p, ctypes.POINTER(ctypes.c_longlong), c_f64p]),
@@ -1385,6 +1386,28 @@ class Plan:
         c = (ctypes.c_uint64 * 4)()
         _check(lib().asx_plan_debug_ncc(self._h, c), "asx_plan_debug_ncc failed")
         return tuple(int(v) for v in c)
+
+    NCC_TABLE_SETS = {"strided": 0, "pool": 1, "full": 2}
+
+    def debug_ncc_tables(self, which, source_track=0, sample_track=0):
+        """diagnostic: the float64 tables behind the coefficient as the last call left them (asx_plan_debug_ncc_tables).  which:
+        "strided" (the tracks of the last NCC group; one track where the stride was 0), "pool" (the plan's track set) or "full" (the
+        full-range set).  -> {"mu", "vmax" of the source track; "mean_y", "sy", "vy" of the sample track; "table": float64 [N, 2],
+        {Sx' (mu-shifted), Vx} per lag; and for "full" "ptab", "ttab": [N, 2] at the overlaps m = 1..N-1, row 0 NaN (never
+        written)}.  AsxError where the set does not exist or a track is outside it."""
+        n = self.sample_len
+        sstat, ystat = np.zeros(2, dtype=np.float64), np.zeros(3, dtype=np.float64)
+        table = np.zeros((n, 2), dtype=np.float64)
+        full = which == "full"
+        ptab, ttab = (np.full((n, 2), np.nan, dtype=np.float64) for _ in range(2)) if full else (None, None)
+        _check(lib().asx_plan_debug_ncc_tables(self._h, self.NCC_TABLE_SETS[which], int(source_track), int(sample_track),
+                                               sstat.ctypes.data, ystat.ctypes.data, table.ctypes.data,
+                                               ptab.ctypes.data if full else None, ttab.ctypes.data if full else None))
+        out = {"mu": float(sstat[0]), "vmax": float(sstat[1]), "mean_y": float(ystat[0]), "sy": float(ystat[1]), "vy": float(ystat[2]),
+               "table": table}
+        if full:
+            out["ptab"], out["ttab"] = ptab, ttab
+        return out
 
     def debug_over_list(self):
         """diagnostic: the plan's list of overflowed pairs as it stands, (count on the device, count of the host's mirror), read
