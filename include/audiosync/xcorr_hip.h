@@ -33,18 +33,19 @@
  *   asx_xcorr_pool_curve_f32_dev: an entry's centre was not a lag inside [-N, N-1]; NaN in all its values.  The same in
  *   asx_xcorr_track_f32_dev and asx_xcorr_pool_track_f32_dev, with used = 0.  asx_xcorr_ncc_f32_dev with rows: the row was not a
  *   window inside [0, N-1]; peak[i] = NaN too.  The same in asx_xcorr_ncc_topk_f32_dev, asx_xcorr_pool_ncc_f32_dev and
- *   asx_xcorr_pool_ncc_topk_f32_dev, in all k entries.  asx_xcorr_ncc_full_f32_dev and asx_xcorr_ncc_full_topk_f32_dev: the row was
- *   not a window inside [-(N-1), N-1].)
+ *   asx_xcorr_pool_ncc_topk_f32_dev, in all k entries.  asx_xcorr_ncc_full_f32_dev, asx_xcorr_ncc_full_topk_f32_dev and their pool
+ *   forms asx_xcorr_pool_ncc_full_f32_dev and asx_xcorr_pool_ncc_full_topk_f32_dev: the row was not a window inside [-(N-1), N-1].)
  *   ret = -3 (asx_xcorr_topk_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_phat_topk_f32_dev and
  *   asx_xcorr_pool_phat_topk_f32_dev only): no lag is left for
  *   this entry of the pair (its window minus the zones around the earlier entries is empty);
- *   lag = 0 and coef = NaN.  (asx_xcorr_ncc_topk_f32_dev, asx_xcorr_pool_ncc_topk_f32_dev and
- *   asx_xcorr_ncc_full_topk_f32_dev too: peak = NaN as well.)
+ *   lag = 0 and coef = NaN.  (asx_xcorr_ncc_topk_f32_dev, asx_xcorr_pool_ncc_topk_f32_dev, asx_xcorr_ncc_full_topk_f32_dev and
+ *   asx_xcorr_pool_ncc_full_topk_f32_dev too: peak = NaN as well.)
  *   ret = -4 (asx_xcorr_pool_f32_dev, asx_xcorr_pool_topk_f32_dev, asx_xcorr_pool_phat_f32_dev,
  *   asx_xcorr_pool_phat_sub_f32_dev and asx_xcorr_pool_phat_topk_f32_dev only): a pair's source or sample index is outside its pool; lag = 0 and coef = NaN (the top-k
  *   form: in all k entries of the pair).  It takes precedence over -2 and -3.  (asx_xcorr_pool_curve_f32_dev: NaN in all
- *   the values of the pair's entries.  asx_xcorr_pool_track_f32_dev: the same, with used = 0.  asx_xcorr_pool_ncc_f32_dev and
- *   asx_xcorr_pool_ncc_topk_f32_dev: lag = 0, coef = NaN and peak = NaN, in all k entries.)
+ *   the values of the pair's entries.  asx_xcorr_pool_track_f32_dev: the same, with used = 0.  asx_xcorr_pool_ncc_f32_dev,
+ *   asx_xcorr_pool_ncc_topk_f32_dev, asx_xcorr_pool_ncc_full_f32_dev and asx_xcorr_pool_ncc_full_topk_f32_dev: lag = 0, coef = NaN
+ *   and peak = NaN, in all k entries.)
  *   ret = -5 (asx_xcorr_warp_f32_dev and asx_xcorr_pool_warp_f32_dev only): an entry's drift line is not valid; NaN in all its
  *   values and len = 0.  In these two calls -4 and -2 mean what they mean in the calls around given lags and take precedence, in
  *   that order.
@@ -501,8 +502,8 @@ int asx_xcorr_pool_ncc_f32_dev(asx_plan *plan, const float *d_sources, size_t so
  * A pool index outside its pool gives (0, NaN, NaN, -4) in all k entries; it takes precedence over -2 and -3.  Refusals: those of the
  * pool call above plus k and min_separation out of range.  The bank and the track set are filled once per call whatever k is.
  *   The [C][C][k] tables of an all-pairs call have the layout asx_pool_closure_dev takes, but feeding them to it is not offered: this
- * curve holds the lags 0..N-1 only, so a pair whose true lag is negative has no entry to offer.  (The full-range curve of
- * asx_xcorr_ncc_full_topk_f32_dev has such entries, but no pool form yet.) */
+ * curve holds the lags 0..N-1 only, so a pair whose true lag is negative has no entry to offer.  The tables for closure come from
+ * asx_xcorr_pool_ncc_full_topk_f32_dev, below, whose curve holds the lags -(N-1)..N-1. */
 int asx_xcorr_pool_ncc_topk_f32_dev(asx_plan *plan, const float *d_sources, size_t source_stride, size_t nsources,
                                     const float *d_samples, size_t sample_stride, size_t nsamples,
                                     const int32_t *d_pairs, const int64_t *d_windows, size_t window_stride, size_t batch,
@@ -551,8 +552,8 @@ int asx_xcorr_pool_ncc_topk_f32_dev(asx_plan *plan, const float *d_sources, size
  * works in groups of min(asx_plan_group(), 2^30 / 72N) pairs, at least one, so the set holds at most 1 GiB (or one pair's 72N bytes).
  *   Cost: two transform passes per group instead of one, the NCC call's moment passes, one pass over the first halves of the tracks
  * for the tables of the negative lags and a peak pass over twice the lags: about twice the NCC call (measured: DESIGN.md).
- *   Not offered: pools, and so asx_pool_closure_dev over full-range tables (the next step); the double ABI, streams, and a fused
- * inverse pass. */
+ *   Not offered: pools in this call (asx_xcorr_pool_ncc_full_f32_dev, below, has them, and with them the tables
+ * asx_pool_closure_dev takes); the double ABI, streams, and a fused inverse pass. */
 int asx_xcorr_ncc_full_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
                                const float *d_sample, size_t sample_stride,
                                const int64_t *d_windows, size_t window_stride, size_t batch,
@@ -574,6 +575,55 @@ int asx_xcorr_ncc_full_topk_f32_dev(asx_plan *plan, const float *d_source, size_
 int asx_xcorr_ncc_full_debug_c_dev(asx_plan *plan, const float *d_source, const float *d_sample, double min_energy,
                                    int64_t min_overlap, float *d_c, int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret,
                                    void *stream);
+
+/* Full-range normalised cross-correlation over listed pairs of two track pools: the pairs of asx_xcorr_pool_ncc_f32_dev under the
+ * curve of asx_xcorr_ncc_full_f32_dev.  An all-pairs table over the clips of one event needs both: every track transformed once, and
+ * the negative lags, since lag_ba = -lag_ab puts a negative true lag in half the table.
+ *   From asx_xcorr_pool_ncc_f32_dev: everything before `batch` (aliasing pools, strides below the track length, d_pairs == NULL =
+ * every combination, source-major), the 16-byte alignment rule, the stride rule and the stream rule, real-column plans only, and its
+ * refusals.  A pool index outside its pool gives (0, NaN, NaN, -4); it takes precedence over -2, nothing outside the pools is read,
+ * and the other pairs are untouched bit for bit.  batch == 0 returns 0.
+ *   From asx_xcorr_ncc_full_f32_dev: the curve over -(N-1) <= l <= N-1, min_energy, min_overlap and the two competing rules, the row
+ * rule -(N-1) <= lag_min <= lag_max <= N-1 (d_windows == NULL: every lag), the peak rule, the outputs per pair, and the additional
+ * refusal for min_overlap outside [1, N].
+ *   Per pair inside its pools, the results are bit for bit those of asx_xcorr_ncc_full_f32_dev for that pair alone on the same plan.
+ * Every value of a pair is independent of the batch, of the pair's position in it and of the group boundaries.  ret is never 1; no
+ * listing, no second look, no counters, no host synchronisation.
+ *   Once per call, before the groups, for every TRACK (the strided call does this once per pair): the forward column pass (the bank),
+ * the moments and the per-lag table, x_lo of every source track and its forward column pass into a second bank of source spectra
+ * (the sample side of pass B is the first bank's: the samples are the same in both passes), the prefix table of every source and the
+ * suffix table of every sample track.  Each group then runs only the row and inverse passes of pass A and pass B, the peak pass and
+ * the tails.
+ *   Memory.  Beside the bank and the pool NCC call's track set (16N bytes per source track), the plan keeps a full-range track set
+ * sized by the pools: per source track x_lo (8N bytes), its column spectrum (one bank row: about 8N bytes) and the prefix table
+ * (16N), per sample track the suffix table (16N), plus the norm partials and band sums of a bank.  It is allocated at the first such
+ * call and grows like the bank: everything is reallocated behind a device synchronisation when a call names more tracks, never
+ * inside a stream capture (such a call returns -1; make one call with pools at least this large outside the capture first).  It is
+ * not counted in asx_plan_workspace_bytes.  The per-group buffers -- two r buffers per pair (16N bytes), the packed maxima and the
+ * top-k records -- are those of the strided full-range set, which this call allocates whole if the plan has none (72N bytes per pair
+ * of a group; its per-pair track buffers lie idle in this call) and whose bound of 1 GiB stays: the call works in groups of
+ * min(asx_plan_group(), 2^30 / 72N) pairs, at least one, which is smaller than the plan's group wherever 72N * asx_plan_group()
+ * exceeds 1 GiB.
+ *   Cost (measured: DESIGN.md): per pair the two row and inverse passes, the peak pass and the tails; per track everything else. */
+int asx_xcorr_pool_ncc_full_f32_dev(asx_plan *plan, const float *d_sources, size_t source_stride, size_t nsources,
+                                    const float *d_samples, size_t sample_stride, size_t nsamples,
+                                    const int32_t *d_pairs, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                    double min_energy, int64_t min_overlap,
+                                    int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+
+/* ... with the K strongest separated lags per pair: the rule and the outputs of asx_xcorr_ncc_full_topk_f32_dev (signed lags, no wrap
+ * between N-1 and -(N-1)) over the pairs of asx_xcorr_pool_ncc_full_f32_dev.  k = 1 launches exactly that call, and entry 0 is always
+ * bit for bit the k = 1 result.  For a pair inside its pools, all k entries are bit for bit those of asx_xcorr_ncc_full_topk_f32_dev
+ * for that pair alone on the same plan.  A pool index outside its pool gives (0, NaN, NaN, -4) in all k entries; it takes precedence
+ * over -2 and -3.  Refusals: those of the call above plus k and min_separation out of range.  The banks and the track sets are filled
+ * once per call whatever k is.
+ *   With ONE pool as both sides, d_pairs == NULL and nsources = nsamples = C, the [C][C][k] tables are the input of
+ * asx_pool_closure_dev: every pair has an entry for its true lag, whatever its sign. */
+int asx_xcorr_pool_ncc_full_topk_f32_dev(asx_plan *plan, const float *d_sources, size_t source_stride, size_t nsources,
+                                         const float *d_samples, size_t sample_stride, size_t nsamples,
+                                         const int32_t *d_pairs, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                         double min_energy, int64_t min_overlap, int k, int64_t min_separation,
+                                         int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
 
 /* Band-limited GCC-PHAT: asx_xcorr_phat_f32_dev in which only the bins of a frequency band vote.  Most material is band-limited
  * (speech, codecs that low-pass, hum and rumble at the bottom): outside its band the cross spectrum is rounding noise, and with
@@ -900,7 +950,8 @@ int asx_topk_best_dev(const int64_t *d_lag, const double *d_coef, const int32_t 
 /* Each pair's lag by triangle closure over a clip pool, and the clips placed: the consumer of an all-pairs top-k call that uses
  * more than one pair at a time.  asx_topk_best_dev picks by coefficient alone, which takes the wrong entry exactly where runner-ups
  * were asked for (a chorus, an echo, a loud private event); this call picks the entry that the other clips agree with.
- *   Input.  The outputs of asx_xcorr_pool_topk_f32_dev (or of asx_xcorr_pool_f32_dev, with k = 1) over ONE pool used as both sides,
+ *   Input.  The outputs of asx_xcorr_pool_topk_f32_dev (or of asx_xcorr_pool_f32_dev, with k = 1) over ONE pool used as both sides
+ * -- or those of asx_xcorr_pool_ncc_full_topk_f32_dev, the coefficient curve over signed lags, which a loud private event does not fool --,
  * with d_pairs == NULL and nsources = nsamples = C = nclips: pair (a, b) is index a * C + b, entry j of that pair is at
  * (a * C + b) * k + j.  With clip start times T (in frames of the common event), frame i of clip b is frame
  * i + T_b - T_a of clip a, and a lag l says sample[i] = source[i + l]: with clip a as the source and clip b as the sample, the lag

@@ -16,5 +16,5 @@ from .hipxcorr import (  # noqa: F401
     planmath_table, planmath_twiddles, band_bins, results_to_ms_dev, synth_pairs_dev, topk_best_dev, xcorr_batch_multi,
     Comm, PinnedArray, result_bytes, shard_range, closure_args, pool_closure, pool_closure_dev, phat_topk_args, pool_phat_topk_args,
     NCC_MIN_ENERGY, ncc_args, ncc_topk_args, pool_ncc_args, pool_ncc_topk_args,
-    ncc_full_args, ncc_full_topk_args,
+    ncc_full_args, ncc_full_topk_args, pool_ncc_full_args, pool_ncc_full_topk_args,
 )

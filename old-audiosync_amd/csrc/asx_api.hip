@@ -119,7 +119,7 @@ struct asx_plan {
 
     // Who owns the plan's device memory (asx_plan_workspace_bytes: all but the bank's and the NCC sets').  mem: what plan_init takes and, once created,
     // the lazy sets (big, bslot, st, st64: whole or absent); cxy0: lane 0's C_x / C_y, which tune_placement may replace; bank.mem; ncc.mem;
-    // ncc.tmem; nccfull.mem.
+    // ncc.tmem; nccfull.mem; nccfull.pmem.
     AsxMemSet mem{ hip_mem }, cxy0{ hip_mem };
     // "Lanes": each owns the workspaces of one launch group and a stream.  With two lanes
     // (ASX_LANES=2) consecutive groups of a batch alternate lanes so that kernels of different
@@ -188,6 +188,16 @@ struct asx_plan {
         struct Set { AsxNccWs w{}; AsxNccFullWs f{}; } set;
         AsxMemSet mem{ hip_mem };
         size_t group = 0;
+        // The pool calls' track set (asx_xcorr_pool_ncc_full_f32_dev; lazy, whole or absent, grown like the bank and like it replaced
+        // wholesale): per source track x_lo (tracks.stage), its forward column pass (bank.cx: pass B's source rows; its norm partials
+        // and band sums in bank.nrm / bank.band, next to a copy of the samples' from the plan's bank) and the prefix table
+        // (tracks.ptab), per sample track the suffix table (tracks.ttab).  tracks.rlo and bank.cy stay null in the set: a group's
+        // rlo is `set`'s, and pass B's sample rows are the plan's bank's.  Its own set too.  staged / suffixed: sources staged and
+        // suffix tables built over the plan's life (host-side counts: asx_plan_debug_ncc_full).
+        struct Tracks { AsxNccFullWs tracks{}; AsxSpectra bank{}; } pool;
+        AsxMemSet pmem{ hip_mem };
+        size_t nsrc = 0, nsmp = 0;
+        unsigned long long staged = 0, suffixed = 0;
     } nccfull;
     // pairs whose near-tie list overflowed since the list was last emptied (k_finalize appends, resolve_overflows reads)
     uint32_t *over_list = nullptr, *over_n = nullptr;
@@ -959,6 +969,9 @@ struct GroupOpts {
     // re-evaluation, no Pearson pass, so no counter moves and y is not written -- and every lag's r is wanted whatever the plan's
     // window says: the search is the full one.
     bool transforms_only = false;
+    // A pool group's spectra instead of the plan's bank (null: the bank): pass B of asx_xcorr_pool_ncc_full_f32_dev, whose source rows
+    // are those of the staged x_lo tracks and whose sample rows are the bank's own.
+    const AsxSpectra *bank = nullptr;
 };
 
 // One group: g <= plan->group pairs, the first g of x, results to the first g of y.
@@ -982,7 +995,7 @@ static int run_group(asx_plan *p, const Pairs<TIn> &x, size_t g, const Results &
     // The group's spectra (AsxSpectra): the lane's own forward passes -- but a broadcast operand's rows are in the plan's slot, and a
     // pool group's in the bank, found through its resolved records -- with the norm partials and band sums always in the lane's places.
     const AsxPoolPair *pl = x.pool ? W.pool : nullptr;
-    const AsxSpectra &from = pl ? p->bank.c : p->bslot;
+    const AsxSpectra &from = pl ? (o.bank ? *o.bank : p->bank.c) : p->bslot;
     const AsxSpectra C{ (pl || (x.bc & 1)) ? from.cx : W.zxa, (pl || (x.bc & 2)) ? from.cy : W.zya, pk.nrm_part, tk.band, form.bc, pl };
     // The pruned pass's kernels get a copy of the lane's AsxPrune that says whether Q is stored in part: q_rows predictor rows
     // (asx_qstore_rows: the row schedule has the kernel and the plan's switch lets a group of this size in), or 0 and list null = Q is whole.
@@ -2132,10 +2145,11 @@ extern "C" int asx_plan_debug_ncc(asx_plan *p, uint64_t out[4])
 
 // diagnostic (not in the public header): the float64 tables behind the coefficient, as the last call left them in one of the plan's
 // sets.  which: 0 the NCC set (the tracks of the last NCC group; one track where the stride was 0), 1 the pool calls' track set,
-// 2 the full-range set (as 0, plus the two tables of the negative lags).
+// 2 the full-range set (as 0, plus the two tables of the negative lags), 3 the pool full-range calls' track set (the tracks of the
+// last such call by pool index: table and statistics from the pool calls' track set, which that call filled, plus the two tables).
 //   sstat[2]  the source track's mu and Vmax          ystat[3]  the sample track's mean, Sy, Vy
 //   table     [N] {Sx' (mu-shifted), Vx} of the lags 0..N-1, as 2N doubles
-//   ptab, ttab  which = 2 only, else ignored: [N] {P1[m], Vx of x[0, m)} and {T1[m], Vy of y[N - m, N)} as 2N doubles each; the
+//   ptab, ttab  which = 2 and 3 only, else ignored: [N] {P1[m], Vx of x[0, m)} and {T1[m], Vy of y[N - m, N)} as 2N doubles each; the
 //             entries m = 1..N-1 are copied, entry 0 (which no kernel writes) is left as the caller had it
 // An output may be null: it is not copied.  Synchronises the device; launches nothing and changes nothing.
 extern "C" int asx_plan_debug_ncc_tables(asx_plan *p, int which, size_t source_track, size_t sample_track, double *sstat, double *ystat,
@@ -2143,13 +2157,15 @@ extern "C" int asx_plan_debug_ncc_tables(asx_plan *p, int which, size_t source_t
 {
     static const char *fn = "asx_plan_debug_ncc_tables";
     if (!p) return fail("%s: null plan", fn);
-    if (which < 0 || which > 2) return fail("%s: which = %d is not 0 (strided), 1 (pool) or 2 (full)", fn, which);
+    if (which < 0 || which > 3) return fail("%s: which = %d is not 0 (strided), 1 (pool), 2 (full) or 3 (pool full)", fn, which);
     PlanCall c(p);
     if (!c.dg.ok) return fail("cannot select device %d", p->device);
-    const AsxNccWs &W = which == 0 ? p->ncc.w : which == 1 ? p->ncc.tracks : p->nccfull.set.w;
-    const size_t ns = which == 0 ? p->ncc.group : which == 1 ? p->ncc.nsrc : p->nccfull.group;
-    const size_t nm = which == 1 ? p->ncc.nsmp : ns;
-    if (!W.table) return fail("%s: the plan has no such set yet (which = %d): make a call that fills it first", fn, which);
+    const bool pooled = which == 1 || which == 3;
+    const AsxNccWs &W = which == 0 ? p->ncc.w : pooled ? p->ncc.tracks : p->nccfull.set.w;
+    const size_t ns = which == 0 ? p->ncc.group : which == 1 ? p->ncc.nsrc : which == 2 ? p->nccfull.group : p->nccfull.nsrc;
+    const size_t nm = which == 1 ? p->ncc.nsmp : which == 3 ? p->nccfull.nsmp : ns;
+    if (!W.table || (which == 3 && !p->nccfull.pool.tracks.ptab))
+        return fail("%s: the plan has no such set yet (which = %d): make a call that fills it first", fn, which);
     if (source_track >= ns || sample_track >= nm)
         return fail("%s: track (%zu, %zu) is outside the set's %zu source and %zu sample tracks", fn, source_track, sample_track, ns, nm);
     HIP_TRY(hipDeviceSynchronize());
@@ -2161,8 +2177,8 @@ extern "C" int asx_plan_debug_ncc_tables(asx_plan *p, int which, size_t source_t
         ystat[0] = st[0]; ystat[1] = st[2]; ystat[2] = st[3];
     }
     if (table) HIP_TRY(hipMemcpy(table, W.table + source_track * N, N * sizeof(double2), hipMemcpyDeviceToHost));
-    if (which == 2 && N > 1) {
-        const AsxNccFullWs &F = p->nccfull.set.f;
+    if (which >= 2 && N > 1) {
+        const AsxNccFullWs &F = which == 2 ? p->nccfull.set.f : p->nccfull.pool.tracks;
         if (ptab) HIP_TRY(hipMemcpy(ptab + 2, F.ptab + source_track * N + 1, (N - 1) * sizeof(double2), hipMemcpyDeviceToHost));
         if (ttab) HIP_TRY(hipMemcpy(ttab + 2, F.ttab + sample_track * N + 1, (N - 1) * sizeof(double2), hipMemcpyDeviceToHost));
     }
@@ -2324,6 +2340,164 @@ extern "C" int asx_xcorr_ncc_full_debug_c_dev(asx_plan *p, const float *d_source
     const size_t N = p->host.N;
     return ncc_full_batch(p, fn, d_source, 2 * N, d_sample, N, nullptr, 0, 1, min_energy, min_overlap, d_c,
                           { d_lag, d_coef, d_ret, 1, d_peak }, stream);
+}
+
+// ---------------------------------------------------------------------------
+// full-range NCC over track pools (asx_xcorr_pool_ncc_full_f32_dev): the per-track work once per call, two transform passes per group
+// ---------------------------------------------------------------------------
+// The plan's full-range track set holds at least nsrc source and nsmp sample tracks: per source track x_lo (8N bytes), its spectrum
+// (a bank row) and the prefix table (16N), per sample track the suffix table (16N), and the norm partials and band sums of a bank.
+// Grown as the bank is (ensure_bank): everything reallocated behind a device synchronisation, never inside a stream capture.
+static int ensure_ncc_full_tracks(asx_plan *p, const char *fn, size_t nsrc, size_t nsmp, hipStream_t s)
+{
+    asx_plan::NccFull &C = p->nccfull;
+    if (nsrc <= C.nsrc && nsmp <= C.nsmp) return 0;
+    if (stream_capturing(s))
+        return fail("%s: the plan's full-range NCC track set holds %zu x %zu tracks and cannot grow to %zu x %zu during a stream "
+                    "capture; make a call with pools at least this large outside the capture first", fn, C.nsrc, C.nsmp, nsrc, nsmp);
+    const AsxDev &P = p->dev;
+    const size_t N = p->host.N, ns = std::max(nsrc, C.nsrc), nm = std::max(nsmp, C.nsmp), pitch = (2 * N + 3) & ~(size_t)3;
+    const size_t na = std::max(ns, nm), nt = P.ntiles, nb = nt * (size_t)P.nbands;
+    HIP_TRY(hipDeviceSynchronize());
+    C.pmem.clear(); C.pool = asx_plan::NccFull::Tracks{}; C.nsrc = C.nsmp = 0;
+    if (asx_mem_whole(C.pmem, C.pool, [&](AsxMemSet &m, asx_plan::NccFull::Tracks &T) {
+            T.tracks.pitch = pitch;
+            return m.take(&T.tracks.stage, ns * pitch) || m.take(&T.tracks.ptab, ns * N) || m.take(&T.tracks.ttab, nm * N) ||
+                           m.take(&T.bank.cx, ns * asx_spectrum_len(P)) || m.take(&T.bank.nrm, na * 2 * nt) ||
+                           (nb && m.take(&T.bank.band, na * 2 * nb))
+                       ? -1 : 0;
+        }))
+        return fail("%s: cannot allocate the plan's full-range NCC track set for %zu source and %zu sample tracks (%zu bytes per "
+                    "source track, %zu per sample track)", fn, ns, nm, 24 * N + asx_spectrum_len(P) * sizeof(float2), 16 * N);
+    C.nsrc = ns; C.nsmp = nm;
+    return 0;
+}
+
+// ncc_full_batch's sibling for the pool calls, after the entry point's null checks and the top-k option's: ncc_batch's pools and
+// ncc_full_batch's curve.  topk.k > 1: y's entry stride is k.  The per-group buffers (two r buffers per pair, best, tk) are the
+// strided full-range set's, so a group of this call is that set's: min(the plan's group, one gibibyte / 72N) pairs.
+static int ncc_full_pool_batch(asx_plan *p, const char *fn, const float *d_sources, size_t source_stride, const float *d_samples,
+                               size_t sample_stride, const int64_t *d_windows, size_t window_stride, size_t batch, double min_energy,
+                               int64_t min_overlap, const Results &y, void *stream, const PoolCall &pool, const Topk &topk = {})
+{
+    if (!(min_energy >= ASX_NCC_MIN_ENERGY && min_energy <= 1.0)) // (a NaN fails both)
+        return fail("%s: min_energy %g is not in [%g, 1]", fn, min_energy, (double)ASX_NCC_MIN_ENERGY);
+    if (min_overlap < 1 || min_overlap > (int64_t)p->host.N)
+        return fail("%s: min_overlap %lld is not in [1, %zu]", fn, (long long)min_overlap, p->host.N);
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
+    const AsxDev &P = p->dev;
+    if (pool_layout(p, fn, d_sources, source_stride, pool.nsrc, d_samples, sample_stride, pool.nsmp, pool.rows, batch)) return -1;
+    if (batch == 0) return 0;
+    if (ensure_bank(p, fn, pool.nsrc, pool.nsmp, s) || ensure_ncc_tracks(p, fn, pool.nsrc, pool.nsmp, s) ||
+        ensure_ncc_full_tracks(p, fn, pool.nsrc, pool.nsmp, s) || ensure_ncc_full(p, fn, s))
+        return -1;
+    // Once per call, before the groups.  What ncc_batch does for its pools: every track's forward column pass into the bank and its
+    // moments into the NCC track set ...
+    pool_fill(p, d_sources, source_stride, pool.nsrc, d_samples, sample_stride, pool.nsmp, s);
+    asx_launch_ncc_pool_moments(p->ncc.tracks, d_sources, source_stride, pool.nsrc, d_samples, sample_stride, pool.nsmp, P.N, s);
+    p->ncc.built_src += pool.nsrc;
+    p->ncc.built_smp += pool.nsmp;
+    // ... and what the negative lags add: x_lo of every source track and the prefix and suffix tables, then the forward column pass
+    // of every x_lo into the second bank, whose sample side is the first bank's (the samples are the same in both passes: their norm
+    // partials and band sums are copied, their spectra shared)
+    AsxNccFullWs F = p->nccfull.pool.tracks;
+    AsxSpectra B = p->nccfull.pool.bank;
+    asx_launch_nccfull_pool_tracks(p->ncc.tracks, F, d_sources, source_stride, pool.nsrc, d_samples, sample_stride, pool.nsmp, P.N, s);
+    p->nccfull.staged += pool.nsrc;
+    p->nccfull.suffixed += pool.nsmp;
+    {
+        const size_t na = std::max(pool.nsrc, pool.nsmp), nt = P.ntiles, nb = nt * (size_t)P.nbands;
+        HIP_TRY(hipMemcpyAsync(B.nrm, p->bank.c.nrm, na * 2 * nt * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (nb) HIP_TRY(hipMemcpyAsync(B.band, p->bank.c.band, na * 2 * nb * sizeof(float2), hipMemcpyDeviceToDevice, s));
+        B.cy = p->bank.c.cy;
+        for (size_t c0 = 0; c0 < pool.nsrc; c0 += 65535)
+            asx_launch_fwd_cols_r(P, F.stage, F.pitch, nullptr, 0, c0, (int)std::min<size_t>(65535, pool.nsrc - c0), B, true, s);
+    }
+    // the transforms see no rows: every lag's r is wanted, and the rows are this call's own (-(N-1) <= lag_min <= lag_max <= N-1)
+    const Pairs<float> x = Pairs<float>::pooled(&pool, d_sources, source_stride, d_samples, sample_stride, nullptr, 0);
+    asx_plan::Lane &L = p->lanes[0];
+    const AsxPoolPair *pl = L.pool; // the group's records, which run_group resolves
+    F.rlo = p->nccfull.set.f.rlo;
+    const int K = topk.k;
+    prof_begin_call(p);
+    size_t gi = 0;
+    for (size_t done = 0; done < batch; done += p->nccfull.group, gi++) {
+        const size_t g = std::min(p->nccfull.group, batch - done);
+        const Pairs<float> xg = x.at(done);
+        const Results yg = y.at(done);
+        const int64_t *rows = d_windows ? d_windows + 2 * done * window_stride : nullptr;
+        // the group's r buffers, best and tk; a pair's tables and statistics: those of its slots in the two track sets
+        AsxNccWs W = p->nccfull.set.w;
+        W.table = p->ncc.tracks.table; W.sstat = p->ncc.tracks.sstat; W.ystat = p->ncc.tracks.ystat;
+        W.nsrc = W.nsmp = 0;
+        W.do_src = W.do_smp = false;
+        // pass A: the bank's rows -> r of the lags >= 0; pass B: the same samples against the rows of x_lo -> r of the lags < 0
+        if (run_group(p, xg, g, yg, s, { .prof_group = gi, .listed = false, .f32_abi = false, .r_out = W.r, .transforms_only = true }))
+            return -1;
+        if (run_group(p, xg, g, yg, s, { .prof_group = GroupOpts::no_marks, .listed = false, .f32_abi = false, .r_out = F.rlo,
+                                         .transforms_only = true, .bank = &B }))
+            return -1;
+        asx_launch_nccfp_peak(W, F, P.nout, P.N, (double)P.F, min_energy, min_overlap, rows, window_stride, L.seg, yg.peak, (int)g, s, pl, K);
+        const AsxInputs<float> in = xg.inputs(pl);
+        if (K == 1) {
+            // the reference's coefficient of the samples at the winner, in the direct form
+            asx_launch_pearson(in, P.N, L.seg, L.psums, yg.lag, yg.coef, yg.ret, (int)g, s);
+            if (rows) asx_launch_nccfull_invalid(P.N, rows, window_stride, yg.lag, yg.coef, yg.peak, yg.ret, (int)g, s);
+            asx_launch_invalid_pairs(pl, yg.lag, yg.coef, yg.ret, yg.peak, (int)g, s);
+        } else {
+            // ncc_full_batch's passes over the signed curve
+            for (int j = 0; j <= K; j++) {
+                if (j > 0 && j < K) asx_launch_nccfull_scan(W, F, P.nout, P.N, rows, window_stride, topk.sep, j, (int)g, s);
+                asx_launch_nccfull_step(W, P.N, rows, window_stride, topk.sep, j, K, L.seg, L.tk.lag, L.tk.coef, L.tk.ret, yg.lag, yg.coef,
+                                        yg.peak, yg.ret, (int)g, s);
+                if (j < K) asx_launch_pearson(in, P.N, L.seg, L.psums, L.tk.lag, L.tk.coef, L.tk.ret, (int)g, s);
+            }
+            asx_launch_invalid_pairs_k(pl, K, yg.lag, yg.coef, yg.ret, yg.peak, (int)g, s);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    prof_end_call(p, gi);
+    return 0;
+}
+
+// The full-range NCC call over listed pairs of two pools.
+extern "C" int asx_xcorr_pool_ncc_full_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                               const float *d_samples, size_t sample_stride, size_t nsamples, const int32_t *d_pairs,
+                                               const int64_t *d_windows, size_t window_stride, size_t batch, double min_energy,
+                                               int64_t min_overlap, int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret,
+                                               void *stream)
+{
+    static const char *fn = "asx_xcorr_pool_ncc_full_f32_dev";
+    if (!p || !d_sources || !d_samples || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    return ncc_full_pool_batch(p, fn, d_sources, source_stride, d_samples, sample_stride, d_windows, window_stride, batch, min_energy,
+                               min_overlap, { d_lag, d_coef, d_ret, 1, d_peak }, stream, PoolCall{ d_pairs, nsources, nsamples });
+}
+
+// ... with the K strongest separated lags per pair: k = 1 launches exactly asx_xcorr_pool_ncc_full_f32_dev.
+extern "C" int asx_xcorr_pool_ncc_full_topk_f32_dev(asx_plan *p, const float *d_sources, size_t source_stride, size_t nsources,
+                                                    const float *d_samples, size_t sample_stride, size_t nsamples,
+                                                    const int32_t *d_pairs, const int64_t *d_windows, size_t window_stride, size_t batch,
+                                                    double min_energy, int64_t min_overlap, int k, int64_t min_separation,
+                                                    int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_pool_ncc_full_topk_f32_dev";
+    if (!p || !d_sources || !d_samples || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    if (!ncc_topk_option(fn, k, min_separation)) return -1;
+    return ncc_full_pool_batch(p, fn, d_sources, source_stride, d_samples, sample_stride, d_windows, window_stride, batch, min_energy,
+                               min_overlap, { d_lag, d_coef, d_ret, (size_t)k, d_peak }, stream, PoolCall{ d_pairs, nsources, nsamples },
+                               Topk{ k, min_separation });
+}
+
+// diagnostic: the full-range track set's capacity (sources, samples), and the sources staged and the suffix tables built by the pool
+// full-range calls over the plan's life
+extern "C" int asx_plan_debug_ncc_full(asx_plan *p, uint64_t out[4])
+{
+    if (!p || !out) return -1;
+    out[0] = p->nccfull.nsrc; out[1] = p->nccfull.nsmp;
+    out[2] = p->nccfull.staged; out[3] = p->nccfull.suffixed;
+    return 0;
 }
 
 static int ensure_staging(asx_plan *p, bool with64 = false) // with64: one pair's float64 inputs too (asx_xcorr_f64)

@@ -818,6 +818,18 @@ void asx_launch_nccfull_step(const AsxNccWs &W, uint32_t N, const int64_t *rows,
                              double *peak, int32_t *ret, int npairs, hipStream_t s);
 void asx_launch_nccfull_invalid(uint32_t N, const int64_t *rows, size_t rows_step, int64_t *lag, double *coef, double *peak,
                                 int32_t *ret, int npairs, hipStream_t s);
+// The pool form (asx_xcorr_pool_ncc_full_f32_dev).  Behind asx_launch_ncc_pool_moments on the same pools and the same track set T:
+// x_lo of every source track into F.stage (k_nccfull_stage), F.ptab of every source and F.ttab of every sample track
+// (k_nccfull_prefix), F being the plan's full-range track set (its rlo is not touched); at most 65 535 tracks per launch, in
+// asx_launch_ncc_pool_moments' shares.
+void asx_launch_nccfull_pool_tracks(const AsxNccWs &T, const AsxNccFullWs &F, const float *srcs, size_t src_pitch, size_t nsrc,
+                                    const float *smps, size_t smp_pitch, size_t nsmp, uint32_t N, hipStream_t s);
+// k_nccfp_peak and k_nccfull_finalize: asx_launch_nccfull_peak for a pool group -- W.table, W.sstat, W.ystat, F.ptab and F.ttab are
+// the track sets', indexed by the slots of pl, the group's records; W.r, F.rlo, W.best and W.tk are the group's.  The scan, step and
+// invalid launches behind it are the strided call's.
+void asx_launch_nccfp_peak(const AsxNccWs &W, const AsxNccFullWs &F, size_t r_pitch, uint32_t N, double scale, double min_energy,
+                           int64_t min_overlap, const int64_t *rows, size_t rows_step, AsxSeg *seg, double *peak, int npairs,
+                           hipStream_t s, const AsxPoolPair *pl, int k = 1);
 void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t s);
 unsigned asx_pearson_blocks(uint32_t basis_len); // partial blocks per pair: psums holds 6 doubles per block and pair
 // second look, DC removal: stats[0] = mean of source[0..2N), stats[1] = sum of sample[0..N), stats[2] = scale * stats[0] * stats[1]

@@ -450,6 +450,10 @@ void asx_launch_ncc_invalid(uint32_t N, const int64_t *rows, size_t rows_step, i
 //                      (|c32|, smallest index) maximum; optionally the curve
 //   k_nccfull_finalize / k_nccfull_invalid, k_nccfull_scan / k_nccfull_step: the tails of the one-lag and the top-k call in indices
 // (k_nccfull_*, not k_ncc_*: see the note at k_ncctop_scan.)
+// The pool calls (asx_xcorr_pool_ncc_full_f32_dev) run k_nccfull_stage and k_nccfull_prefix over the tracks of the two pools, once per
+// call, into the plan's full-range track set (asx_launch_nccfull_pool_tracks: the same kernels against the same chunk sums, so the
+// same tables), k_nccfp_peak finds a pair's tables and statistics through its pool record, and the tails, which read nothing of a
+// track, are the strided call's kernels.
 __global__ __launch_bounds__(NCC_NT) void k_nccfull_stage(AsxNccFullWs F, const float *__restrict__ src, size_t src_pitch, uint32_t N)
 {
     const size_t v = (size_t)blockIdx.x * NCC_NT + threadIdx.x;
@@ -529,13 +533,12 @@ __global__ __launch_bounds__(NCC_NT) void k_nccfull_prefix(AsxNccWs W, AsxNccFul
 
 // c_out: c32 of pair i's index j to c_out[i * c_pitch + j] (the debug call), or null.  keep: a top-k group -- c32 also goes to the
 // halves of the pair's two r buffers that this kernel does not read (index j < N - 1 to rlo[j], the others to r[j + 1]).
-__global__ __launch_bounds__(NCC_NT) void k_nccfull_peak(AsxNccWs W, AsxNccFullWs F, size_t r_pitch, uint32_t N, double scale,
-                                                          double min_energy, int64_t min_overlap, const int64_t *__restrict__ rows,
-                                                          size_t rows_step, float *__restrict__ c_out, size_t c_pitch, bool keep)
+// (the body of k_nccfull_peak and k_nccfp_peak: pair's tables and statistics are those of source track ts and sample track ty)
+__device__ __forceinline__ void nccfull_peak_pair(const AsxNccWs &W, const AsxNccFullWs &F, size_t pair, size_t ts, size_t ty,
+                                                  size_t r_pitch, uint32_t N, double scale, double min_energy, int64_t min_overlap,
+                                                  const int64_t *__restrict__ rows, size_t rows_step, float *__restrict__ c_out,
+                                                  size_t c_pitch, bool keep, asx_peak_t *red)
 {
-    __shared__ asx_peak_t red[NCC_NT / 64];
-    const size_t pair = blockIdx.y;
-    const size_t ts = W.nsrc > 1 ? pair : 0, ty = W.nsmp > 1 ? pair : 0;
     const double *sx = W.sstat + ts * ASX_NCC_STAT, *sy = W.ystat + ty * ASX_NCC_STAT;
     const double mu = sx[0], floor_v = min_energy * sx[1], my = sy[0], Sy = sy[2], Vy = sy[3], dN = (double)N;
     const int64_t n1 = (int64_t)N - 1;
@@ -577,6 +580,30 @@ __global__ __launch_bounds__(NCC_NT) void k_nccfull_peak(AsxNccWs W, AsxNccFullW
     }
     best = block_peak_max(best, red);
     if (threadIdx.x == 0 && best) atomicMax(&W.best[pair], best);
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_nccfull_peak(AsxNccWs W, AsxNccFullWs F, size_t r_pitch, uint32_t N, double scale,
+                                                          double min_energy, int64_t min_overlap, const int64_t *__restrict__ rows,
+                                                          size_t rows_step, float *__restrict__ c_out, size_t c_pitch, bool keep)
+{
+    __shared__ asx_peak_t red[NCC_NT / 64];
+    const size_t pair = blockIdx.y;
+    nccfull_peak_pair(W, F, pair, W.nsrc > 1 ? pair : 0, W.nsmp > 1 ? pair : 0, r_pitch, N, scale, min_energy, min_overlap, rows,
+                      rows_step, c_out, c_pitch, keep, red);
+}
+
+// The pool form (asx_xcorr_pool_ncc_full_f32_dev): W.table, W.sstat and W.ystat are the plan's NCC track set, F.ptab and F.ttab the
+// full-range track set, and pair i's are those of its pool record's slots, as in k_ncc_peak; W.r, F.rlo and W.best are the group's.
+// An invalid pair's record names slot 0 and its r is NaN: no lag competes.  (k_nccfp_*, not k_nccfull_*: tests/test_ncc_full.py holds
+// that family to the seven kernels of the strided call.)
+__global__ __launch_bounds__(NCC_NT) void k_nccfp_peak(AsxNccWs W, AsxNccFullWs F, size_t r_pitch, uint32_t N, double scale,
+                                                        double min_energy, int64_t min_overlap, const int64_t *__restrict__ rows,
+                                                        size_t rows_step, bool keep, const AsxPoolPair *__restrict__ pl)
+{
+    __shared__ asx_peak_t red[NCC_NT / 64];
+    const size_t pair = blockIdx.y;
+    nccfull_peak_pair(W, F, pair, pl[pair].sx, pl[pair].sy, r_pitch, N, scale, min_energy, min_overlap, rows, rows_step, nullptr, 0, keep,
+                      red);
 }
 
 // the segment of the curve's index i: the lag l = i - (N - 1) as the circular index the windowed call would have found it at
@@ -726,6 +753,41 @@ void asx_launch_nccfull_peak(const AsxNccWs &W, const AsxNccFullWs &F, size_t r_
     (void)hipMemsetAsync(W.best, 0, (size_t)npairs * sizeof(asx_peak_t), s);
     hipLaunchKernelGGL(k_nccfull_peak, dim3(asx_ncc_chunks(2u * N - 1u), npairs), dim3(NCC_NT), 0, s, W, F, r_pitch, N, scale, min_energy,
                        min_overlap, rows, rows_step, c_out, (size_t)(2u * N - 1u), k > 1);
+    if (k > 1) return;
+    hipLaunchKernelGGL(k_nccfull_finalize, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, W, N, rows, rows_step, seg, peak, npairs);
+}
+
+void asx_launch_nccfull_pool_tracks(const AsxNccWs &T, const AsxNccFullWs &F, const float *srcs, size_t src_pitch, size_t nsrc,
+                                    const float *smps, size_t smp_pitch, size_t nsmp, uint32_t N, hipStream_t s)
+{
+    const size_t nsc = asx_ncc_chunks(2u * N), nyc = asx_ncc_chunks(N), most = 65535;
+    for (size_t c0 = 0; c0 < std::max(nsrc, nsmp); c0 += most) {
+        // asx_launch_ncc_pool_moments' shares: the chunk sums of tracks c0 .. lie where that launch left them
+        const size_t s0 = std::min(c0, nsrc), y0 = std::min(c0, nsmp), at = s0 * nsc + y0 * nyc;
+        AsxNccWs W = T;
+        W.nsrc = (uint32_t)std::min(most, nsrc - s0);
+        W.nsmp = (uint32_t)std::min(most, nsmp - y0);
+        W.do_src = W.nsrc > 0;
+        W.do_smp = W.nsmp > 0;
+        W.m1 += at; W.m2 += at;
+        W.sstat += s0 * ASX_NCC_STAT;
+        W.ystat += y0 * ASX_NCC_STAT;
+        AsxNccFullWs G = F;
+        G.stage += s0 * F.pitch;
+        G.ptab += s0 * (size_t)N;
+        G.ttab += y0 * (size_t)N;
+        if (W.do_src) asx_launch_nccfull_stage(G, srcs + s0 * src_pitch, src_pitch, W.nsrc, N, s);
+        asx_launch_nccfull_prefix(W, G, srcs + s0 * src_pitch, src_pitch, smps + y0 * smp_pitch, smp_pitch, N, s);
+    }
+}
+
+void asx_launch_nccfp_peak(const AsxNccWs &W, const AsxNccFullWs &F, size_t r_pitch, uint32_t N, double scale, double min_energy,
+                           int64_t min_overlap, const int64_t *rows, size_t rows_step, AsxSeg *seg, double *peak, int npairs,
+                           hipStream_t s, const AsxPoolPair *pl, int k)
+{
+    (void)hipMemsetAsync(W.best, 0, (size_t)npairs * sizeof(asx_peak_t), s);
+    hipLaunchKernelGGL(k_nccfp_peak, dim3(asx_ncc_chunks(2u * N - 1u), npairs), dim3(NCC_NT), 0, s, W, F, r_pitch, N, scale, min_energy,
+                       min_overlap, rows, rows_step, k > 1, pl);
     if (k > 1) return;
     hipLaunchKernelGGL(k_nccfull_finalize, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, W, N, rows, rows_step, seg, peak, npairs);
 }

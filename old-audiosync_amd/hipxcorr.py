@@ -72,6 +72,10 @@ _HEADER_SIGNATURES = {
     "asx_xcorr_ncc_full_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_ncc_full_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_ncc_full_debug_c_dev": (_int, [_vp, _vp, _vp, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_pool_ncc_full_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _dbl, _i64, _vp, _vp, _vp, _vp,
+                                               _vp]),
+    "asx_xcorr_pool_ncc_full_topk_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _dbl, _i64, _int, _i64, _vp,
+                                                    _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_band_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_sub_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_phat_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _i64, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -132,6 +136,7 @@ _DIAGNOSTIC_SIGNATURES = {
     "asx_plan_debug_kernels": (_int, [_vp, c_intp, c_intp, c_intp]),
     "asx_plan_debug_bank": (_int, [_vp, _u64p, _u64p, _u64p]),
     "asx_plan_debug_ncc": (_int, [_vp, _u64p]),
+    "asx_plan_debug_ncc_full": (_int, [_vp, _u64p]),
     "asx_plan_debug_ncc_tables": (_int, [_vp, _int, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "asx_plan_debug_prune": (_int, [_vp, _sz, c_f32p, c_intp, _sz]),
     "asx_plan_debug_peak": (_int, [_vp, _sz, c_f32p, _u32p, _u32p, _u64p, _vp, _vp, _sz]),
@@ -615,6 +620,21 @@ def pool_ncc_topk_args(n, sources, samples, k, min_separation, pairs=None, windo
     pool_ncc_args' tuple + (k, min_separation).  ValueError on anything else."""
     option = _topk_option(k, min_separation)
     return pool_ncc_args(n, sources, samples, pairs, windows, min_energy) + option
+
+
+def pool_ncc_full_args(n, sources, samples, pairs=None, windows=None, min_energy=1e-3, min_overlap=None):
+    """Host checks of Plan.xcorr_pool_ncc_full_f32: min_overlap as ncc_full_args checks it (None: (N + 1) // 2), the rest as
+    pool_ncc_args (windows None: every lag -(N-1)..N-1).  -> pool_ncc_args' tuple + (min_overlap,).  ValueError on anything else.  The
+    rows' values are not checked: a row outside [-(N-1), N-1] comes back as ret = -2."""
+    option = _overlap_option(n, min_overlap)
+    return pool_ncc_args(n, sources, samples, pairs, windows, min_energy) + (option,)
+
+
+def pool_ncc_full_topk_args(n, sources, samples, k, min_separation, pairs=None, windows=None, min_energy=1e-3, min_overlap=None):
+    """Host checks of Plan.xcorr_pool_ncc_full_topk_f32: k and min_separation as topk_args checks them, the rest as
+    pool_ncc_full_args.  -> pool_ncc_full_args' tuple + (k, min_separation).  ValueError on anything else."""
+    option = _topk_option(k, min_separation)
+    return pool_ncc_full_args(n, sources, samples, pairs, windows, min_energy, min_overlap) + option
 
 
 def pool_phat_args(n, sources, samples, pairs=None, windows=None, band=None):
@@ -1179,6 +1199,26 @@ class Plan:
                                                     d_c or None, d_lag or None, d_coef or None, d_peak or None, d_ret or None,
                                                     stream or None))
 
+    def xcorr_pool_ncc_full_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows,
+                                window_stride, batch, min_energy, min_overlap, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_ncc_full_f32_dev -- xcorr_pool_ncc_dev over the lags -(N-1)..N-1; every track's
+        transforms, moments and tables once per call; d_windows = 0: every lag, else per-pair rows inside [-(N-1), N-1]"""
+        _check(lib().asx_xcorr_pool_ncc_full_f32_dev(self._h, d_sources or None, int(source_stride), int(nsources), d_samples or None,
+                                                     int(sample_stride), int(nsamples), d_pairs or None, d_windows or None,
+                                                     int(window_stride), int(batch), float(min_energy), int(min_overlap),
+                                                     d_lag or None, d_coef or None, d_peak or None, d_ret or None, stream or None))
+
+    def xcorr_pool_ncc_full_topk_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows,
+                                     window_stride, batch, min_energy, min_overlap, k, min_separation, d_lag, d_coef, d_peak, d_ret,
+                                     stream=0):
+        """raw device pointers (ints): asx_xcorr_pool_ncc_full_topk_f32_dev -- xcorr_pool_ncc_full_dev with the k strongest lags of
+        the signed curve at least min_separation apart, entry j of pair i at index i*k + j"""
+        _check(lib().asx_xcorr_pool_ncc_full_topk_f32_dev(self._h, d_sources or None, int(source_stride), int(nsources),
+                                                          d_samples or None, int(sample_stride), int(nsamples), d_pairs or None,
+                                                          d_windows or None, int(window_stride), int(batch), float(min_energy),
+                                                          int(min_overlap), int(k), int(min_separation), d_lag or None,
+                                                          d_coef or None, d_peak or None, d_ret or None, stream or None))
+
     def phat_debug_r_dev(self, d_src, d_smp, d_r, d_lag, d_coef, d_peak, d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_phat_debug_r_dev -- one contiguous pair, r_phat of all 2N lags (times F) to d_r"""
         _check(lib().asx_xcorr_phat_debug_r_dev(self._h, d_src or None, d_smp or None, d_r or None, d_lag or None, d_coef or None,
@@ -1387,20 +1427,31 @@ class Plan:
         _check(lib().asx_plan_debug_ncc(self._h, c), "asx_plan_debug_ncc failed")
         return tuple(int(v) for v in c)
 
+    def debug_ncc_full(self):
+        """(source tracks, sample tracks) the plan's full-range pool track set holds, and the sources staged (x_lo and its prefix
+        table) and the sample suffix tables built by the pool full-range calls on this plan so far"""
+        c = (ctypes.c_uint64 * 4)()
+        _check(lib().asx_plan_debug_ncc_full(self._h, c), "asx_plan_debug_ncc_full failed")
+        return tuple(int(v) for v in c)
+
     NCC_TABLE_SETS = {"strided": 0, "pool": 1, "full": 2}
+    # the track sets that hold the full-range tables of a pool's tracks (tests/test_ncc_exact.py holds NCC_TABLE_SETS to its three)
+    NCC_POOL_TABLE_SETS = {"pool_full": 3}
 
     def debug_ncc_tables(self, which, source_track=0, sample_track=0):
         """diagnostic: the float64 tables behind the coefficient as the last call left them (asx_plan_debug_ncc_tables).  which:
-        "strided" (the tracks of the last NCC group; one track where the stride was 0), "pool" (the plan's track set) or "full" (the
-        full-range set).  -> {"mu", "vmax" of the source track; "mean_y", "sy", "vy" of the sample track; "table": float64 [N, 2],
-        {Sx' (mu-shifted), Vx} per lag; and for "full" "ptab", "ttab": [N, 2] at the overlaps m = 1..N-1, row 0 NaN (never
-        written)}.  AsxError where the set does not exist or a track is outside it."""
+        "strided" (the tracks of the last NCC group; one track where the stride was 0), "pool" (the plan's track set), "full" (the
+        full-range set) or "pool_full" (the pool full-range calls' track set, indexed by pool track).  -> {"mu", "vmax" of the source
+        track; "mean_y", "sy", "vy" of the sample track; "table": float64 [N, 2], {Sx' (mu-shifted), Vx} per lag; and for "full" and
+        "pool_full" "ptab", "ttab": [N, 2] at the overlaps m = 1..N-1, row 0 NaN (never written)}.  AsxError where the set does not
+        exist or a track is outside it."""
         n = self.sample_len
         sstat, ystat = np.zeros(2, dtype=np.float64), np.zeros(3, dtype=np.float64)
         table = np.zeros((n, 2), dtype=np.float64)
-        full = which == "full"
+        full = which in ("full", "pool_full")
         ptab, ttab = (np.full((n, 2), np.nan, dtype=np.float64) for _ in range(2)) if full else (None, None)
-        _check(lib().asx_plan_debug_ncc_tables(self._h, self.NCC_TABLE_SETS[which], int(source_track), int(sample_track),
+        sets = dict(self.NCC_TABLE_SETS, **self.NCC_POOL_TABLE_SETS)
+        _check(lib().asx_plan_debug_ncc_tables(self._h, sets[which], int(source_track), int(sample_track),
                                                sstat.ctypes.data, ystat.ctypes.data, table.ctypes.data,
                                                ptab.ctypes.data if full else None, ttab.ctypes.data if full else None))
         out = {"mu": float(sstat[0]), "vmax": float(sstat[1]), "mean_y": float(ystat[0]), "sy": float(ystat[1]), "vy": float(ystat[2]),
@@ -1681,6 +1732,31 @@ class Plan:
         shape = ((batch,) if pr is not None else (s.shape[0], t.shape[0])) + (k,)
         return self._staged((s, t, pr, w), shape, _PHAT_RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_ncc_topk_dev(
             d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, me, k, sep, *d_out))
+
+    def xcorr_pool_ncc_full_f32(self, sources, samples, pairs=None, windows=None, min_energy=1e-3, min_overlap=None):
+        """Pairs of two pools ranked by the full-range normalised cross-correlation (asx_xcorr_pool_ncc_full_f32_dev): the pools and
+        pairs of xcorr_pool_f32, windows (rows inside [-(N-1), N-1]), min_energy and min_overlap of xcorr_ncc_full_f32.  Every
+        track's transforms, moments and tables are formed once per call.  Arguments are checked on the host (ValueError) before
+        anything is uploaded.  Returns (lag, coef, peak, ret) of shape [B], or [S, R] when pairs is None; a pair with an index
+        outside its pool gets (0, NaN, NaN, -4)."""
+        n = self.sample_len
+        s, t, pr, w, batch, ws, me, mo = pool_ncc_full_args(n, sources, samples, pairs, windows, min_energy, min_overlap)
+        shape = (batch,) if pr is not None else (s.shape[0], t.shape[0])
+        return self._staged((s, t, pr, w), shape, _PHAT_RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_ncc_full_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, me, mo, *d_out))
+
+    def xcorr_pool_ncc_full_topk_f32(self, sources, samples, k, min_separation, pairs=None, windows=None, min_energy=1e-3,
+                                     min_overlap=None):
+        """The k strongest separated lags of the full-range curve per pair of two pools (asx_xcorr_pool_ncc_full_topk_f32_dev): the
+        arguments of xcorr_pool_ncc_full_f32, k and min_separation of xcorr_topk_f32.  Returns (lag, coef, peak, ret) of shape
+        [B, k], or [S, R, k] when pairs is None -- with one recording as both pools, the tables pool_closure takes; ret = -3 where no
+        lag was left, -4 in all k entries of a pair with an index outside its pool."""
+        n = self.sample_len
+        s, t, pr, w, batch, ws, me, mo, k, sep = pool_ncc_full_topk_args(n, sources, samples, k, min_separation, pairs, windows,
+                                                                         min_energy, min_overlap)
+        shape = ((batch,) if pr is not None else (s.shape[0], t.shape[0])) + (k,)
+        return self._staged((s, t, pr, w), shape, _PHAT_RESULTS, lambda d_s, d_t, d_pr, d_w, *d_out: self.xcorr_pool_ncc_full_topk_dev(
+            d_s, 2 * n, s.shape[0], d_t, n, t.shape[0], d_pr, d_w, ws, batch, me, mo, k, sep, *d_out))
 
     def xcorr_phat_band_f32(self, source, sample, bin_lo, bin_hi, windows=None):
         """xcorr_phat_f32 in which only bins bin_lo..bin_hi of the 2N-point transform vote (asx_xcorr_phat_band_f32_dev; band_bins
