@@ -991,7 +991,7 @@ int asx_topk_best_dev(const int64_t *d_lag, const double *d_coef, const int32_t 
  * d_root [1]; d_offset, d_support, d_placed [C] each.  The call takes no plan, allocates nothing, never synchronises the host, and is
  * asynchronous and capturable on `stream`: four kernel launches in order, each reading required outputs of those before it (there
  * is no workspace), so the outputs must not alias the inputs or one another.
- *   Not offered: clips reachable only over three or more hops are not placed (E_b holds one- and two-hop estimates); a least-squares
+ *   Not offered: clips reachable only over three or more hops are not placed (E_b holds one- and two-hop estimates; asx_pool_place_dev, below, walks longer chains from this call's outputs); a least-squares
  * solve over all pairs; an explicit pair list (unlisted pairs are stated by ret != 0); weighting by coefficient. */
 #define ASX_CLOSURE_LAG_MAX ((int64_t)1 << 40)
 int asx_pool_closure_dev(const int64_t *d_lag, const double *d_coef, const int32_t *d_ret,
@@ -1002,6 +1002,62 @@ int asx_pool_closure_dev(const int64_t *d_lag, const double *d_coef, const int32
                          int32_t *d_root,
                          int64_t *d_offset, int32_t *d_support, int32_t *d_placed,
                          void *stream);
+
+/* Every clip that a chain of usable pairs reaches, placed, and a verdict per pair: the consumer behind asx_pool_closure_dev for events
+ * longer than a clip.  A pool pair is clip a's 2N frames against clip b's first N, so a true lag exists only for |T_b - T_a| < N: in
+ * an event of more than about three clip lengths most pairs hold garbage, the truth lives in a band around the diagonal, and most
+ * clips are three or more hops from any root, where closure's one- and two-hop estimates end.  This call walks the chains.
+ *   Input.  d_lag, d_ret, d_confirm are closure's d_best_lag, d_best_ret, d_confirm ([C * C], pair (a, b) at index a * C + b, L_ab its
+ * lag, an estimate of T_b - T_a) with the tolerance and min_confirm that call was given, or any tables of that layout.  d_root [1] is
+ * closure's d_root or the caller's, in DEVICE memory: it is read when the kernels run, so closure followed by this call needs no
+ * host step in between, and a replayed graph follows a root that changed.
+ *   The rule.  Everything is int64 sums and integer counts; no output depends on the launch geometry.
+ *   Usable, exactly as in asx_pool_closure_dev: usable(x, y) holds when x != y, ret == 0, |lag| <= ASX_CLOSURE_LAG_MAX and
+ * confirm[x * C + y] >= min_confirm.
+ *   Root.  r = d_root[0].  If r is outside [0, C), no clip is reached: every hops is -1, every state is 0 and everything else is 0.
+ * Otherwise hops[r] = 0 and offset[r] = 0.
+ *   Layers.  For h = 1 .. max_hops and every clip b not yet reached, E_b is the multiset of o[c] + L_cb over the clips c with
+ * 0 <= hops[c] < h and usable(c, b), and of o[c] - L_bc over the clips c with 0 <= hops[c] < h and usable(b, c).  If E_b is not
+ * empty, hops[b] = h and offset[b] is the lower median of E_b, the element at index (|E_b| - 1) / 2 of E_b sorted ascending
+ * (closure's definition).  By the breadth-first property the neighbours that count at layer h all lie in layer h - 1.  A median over
+ * them, not a spanning tree: one wrong pick cannot carry a clip away while it is outvoted.  A clip never reached has hops -1,
+ * offset 0, support 0, degree 0 and step 0.
+ *   Sweeps, a Jacobi median relaxation over all usable pairs.  For s = 1 .. sweeps, every clip b with hops > 0 takes the lower
+ * median of o_{s-1}[c] + L_cb and o_{s-1}[c] - L_bc over ALL reached c with the pair usable; all clips read the offsets of the sweep
+ * before; the root stays 0.  d_step[b] = o_s[b] - o_{s-1}[b] of the last sweep, and 0 for the root, for a clip that was not reached
+ * and when sweeps == 0: all of d_step zero says the offsets are a fixed point.  |offset| <= (max_hops + sweeps) * 2^40 < 2^52.
+ *   What sweeps do not do.  Along a chain without redundancy, +-1 frame of jitter per pair adds up to about one frame per hop, and
+ * no sweep shrinks that: sweeps only bring in the pairs to clips of the same and of later layers.  Without sweeps a clip's error is
+ * bounded by its own hops times the jitter, with sweeps by the largest hops of the pool.
+ *   Per clip, with the final offsets o, for every reached clip, the root included: d_degree[b] = |E_b| over ALL reached neighbours,
+ * d_support[b] = the number of those elements within tolerance of o[b].
+ *   Per pair (a, b): when usable(a, b) and both ends are reached, d_resid = L_ab - (o[b] - o[a]) and d_state = 1 if |resid| <=
+ * tolerance, 2 if not; anything else, the diagonal included: state 0, resid 0.  The pairs of state 2 are the ones to run again under a
+ * lag window around o[b] - o[a].
+ *   The input decides.  In a large pool random garbage lags close triangles by accident and come out usable (hundreds of pairs at
+ * C = 300, k = 2, min_confirm = 1), and a clip reached over such a pair alone lands anywhere.  Mask the pairs you do not believe --
+ * ret != 0, a coefficient or peak threshold, a larger min_confirm -- and read d_state and d_support against d_degree.
+ *   Refusals: -1 with nothing launched and the outputs untouched for a NULL pointer other than d_scratch when sweeps == 0;
+ * nclips == 0; nclips * nclips > INT32_MAX; tolerance < 0 or > ASX_CLOSURE_LAG_MAX; min_confirm < 0; max_hops outside
+ * [1, ASX_PLACE_HOPS_MAX]; sweeps outside [0, ASX_PLACE_SWEEPS_MAX].  nclips == 1 is legal.
+ *   All pointers are device pointers: d_scratch, d_offset, d_hops, d_support, d_degree, d_step [C] each; d_resid, d_state [C * C] each.
+ * The call takes no plan, allocates nothing, needs no workspace beyond d_scratch (which may be NULL iff sweeps == 0), never
+ * synchronises the host, and is asynchronous and capturable on `stream`: 2 + max_hops + sweeps kernel launches whatever the tables
+ * hold, none of which waits for another block; a layer behind the last one that placed a clip costs a launch whose blocks leave at
+ * once.  It keeps its state between launches in the outputs and resets it: they may be dirty, and a second call or a replay gives the
+ * same bytes.  The outputs must not alias the inputs or one another.
+ *   Not offered: components other than the root's (call again with a clip of hops -1 as the root); weighting by coefficient; a
+ * floating-point least-squares solve. */
+#define ASX_PLACE_HOPS_MAX   1024
+#define ASX_PLACE_SWEEPS_MAX 64
+int asx_pool_place_dev(const int64_t *d_lag, const int32_t *d_ret, const int32_t *d_confirm,
+                       size_t nclips, int64_t tolerance, int min_confirm,
+                       const int32_t *d_root,
+                       int max_hops, int sweeps,
+                       int64_t *d_scratch,
+                       int64_t *d_offset, int32_t *d_hops, int32_t *d_support, int32_t *d_degree, int64_t *d_step,
+                       int64_t *d_resid, int32_t *d_state,
+                       void *stream);
 
 /* The exact correlation curve and a fractional lag around given lags: a consumer that runs behind the batch, strided, windowed, top-k
  * and pool calls on the lags they returned.  Those calls rank lags by the raw correlation r and hand back one coefficient per lag;

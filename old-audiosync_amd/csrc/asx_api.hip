@@ -2946,6 +2946,33 @@ extern "C" int asx_pool_closure_dev(const int64_t *d_lag, const double *d_coef, 
     return 0;
 }
 
+// Every clip that a chain of usable pairs reaches from the root, and a verdict per pair, from closure's picked tables (k_place_init,
+// k_place_layer, k_place_sweep, k_place_verdict: place.hip): 2 + max_hops + sweeps launches on `stream`, nothing allocated; the root
+// is read on the device.
+extern "C" int asx_pool_place_dev(const int64_t *d_lag, const int32_t *d_ret, const int32_t *d_confirm, size_t nclips,
+                                  int64_t tolerance, int min_confirm, const int32_t *d_root, int max_hops, int sweeps,
+                                  int64_t *d_scratch, int64_t *d_offset, int32_t *d_hops, int32_t *d_support, int32_t *d_degree,
+                                  int64_t *d_step, int64_t *d_resid, int32_t *d_state, void *stream)
+{
+    if (!d_lag || !d_ret || !d_confirm || !d_root || !d_offset || !d_hops || !d_support || !d_degree || !d_step || !d_resid || !d_state)
+        return fail("asx_pool_place_dev: null argument");
+    if (nclips == 0) return fail("asx_pool_place_dev: no clips");
+    if (nclips > 65535 || (uint64_t)nclips * nclips > (uint64_t)INT32_MAX)
+        return fail("asx_pool_place_dev: %zu clips are more than INT32_MAX pairs", nclips);
+    if (tolerance < 0 || tolerance > ASX_CLOSURE_LAG_MAX)
+        return fail("asx_pool_place_dev: tolerance = %lld is not in [0, 2^40]", (long long)tolerance);
+    if (min_confirm < 0) return fail("asx_pool_place_dev: min_confirm = %d is negative", min_confirm);
+    if (max_hops < 1 || max_hops > ASX_PLACE_HOPS_MAX)
+        return fail("asx_pool_place_dev: max_hops = %d is not in [1, %d]", max_hops, ASX_PLACE_HOPS_MAX);
+    if (sweeps < 0 || sweeps > ASX_PLACE_SWEEPS_MAX)
+        return fail("asx_pool_place_dev: sweeps = %d is not in [0, %d]", sweeps, ASX_PLACE_SWEEPS_MAX);
+    if (sweeps > 0 && !d_scratch) return fail("asx_pool_place_dev: sweeps = %d need d_scratch", sweeps);
+    asx_launch_pool_place(d_lag, d_ret, d_confirm, (uint32_t)nclips, tolerance, min_confirm, d_root, max_hops, sweeps, d_scratch,
+                          d_offset, d_hops, d_support, d_degree, d_step, d_resid, d_state, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---------------------------------------------------------------------------
 // growing-window streams (BASELINE config 5)
 // ---------------------------------------------------------------------------

@@ -722,6 +722,12 @@ void asx_launch_pool_closure(const int64_t *lag, const double *coef, const int32
                              int min_confirm, int root, int32_t *votes, int64_t *best_lag, double *best_coef, int32_t *best_ret,
                              int32_t *best_entry, int32_t *confirm, int32_t *d_root, int64_t *offset, int32_t *support,
                              int32_t *placed, hipStream_t s);
+// asx_pool_place_dev over the picked [C][C] tables of that call (C * C <= INT32_MAX, 0 <= tol <= ASX_CLOSURE_LAG_MAX, 1 <= max_hops,
+// 0 <= sweeps; scratch may be NULL when sweeps == 0), place.hip: k_place_init, max_hops times k_place_layer, sweeps times
+// k_place_sweep, k_place_verdict -- 2 + max_hops + sweeps launches on s whatever the tables hold; the root is read on the device
+void asx_launch_pool_place(const int64_t *lag, const int32_t *ret, const int32_t *confirm, uint32_t C, int64_t tol, int min_confirm,
+                           const int32_t *d_root, int max_hops, int sweeps, int64_t *scratch, int64_t *offset, int32_t *hops,
+                           int32_t *support, int32_t *degree, int64_t *step, int64_t *resid, int32_t *state, hipStream_t s);
 // Normalised cross-correlation (asx_xcorr_ncc_f32_dev; the k_ncc_* kernels, ncc.hip).  A track is cut into chunks of ASX_NCC_CHUNK
 // frames and the lags 0..N-1 into chunks of as many lags: the reduction trees follow from N alone.  The workspace of one NCC group
 // (plan-owned, lazy, whole or absent: asx_plan::Ncc): nsrc source and nsmp sample tracks -- the group's pairs, or 1 for the call's

@@ -18,6 +18,7 @@
 #include "lds_fft.h"
 #include "xcorr_dev.h"
 #include "kernel_table.h"
+#include "closure_dev.h"
 
 #include <algorithm>
 #include <math.h>
@@ -1464,10 +1465,7 @@ __global__ __launch_bounds__(ASX_THREADS) void k_topk_best(const int64_t *__rest
 #define ASX_CLOSURE_INV ((int64_t)1 << 60)          // a lag that is not valid: no sum that holds it is near a valid lag
 #define ASX_CLOSURE_TINV (-((int64_t)1 << 62))      // ... and the target of an entry that is not valid: near no sum
 
-__device__ __forceinline__ bool closure_valid(int64_t lag, int32_t ret)
-{
-    return ret == 0 && lag >= -ASX_CLOSURE_LAG_LIMIT && lag <= ASX_CLOSURE_LAG_LIMIT;
-}
+// (closure_valid, closure_good, closure_usable, closure_block_sum and the rank-counting lower median: closure_dev.h, shared with place.hip)
 
 // Vote and pick.  Block (x, y): clip a = y and the clips b = x * BT .. x * BT + BT - 1.  The row (a, c, p) goes through LDS once per
 // block in chunks of CH clips c, as [p][c] so that the 64 lanes of a wave read 64 consecutive int64; a lag that is not valid is
@@ -1574,12 +1572,6 @@ __global__ __launch_bounds__(ASX_THREADS) void k_closure_votes(const int64_t *__
     best_entry[pair] = bj < 0 ? 0 : bj;
 }
 
-// a pair with a valid picked entry off the diagonal
-__device__ __forceinline__ bool closure_good(const int64_t *L, const int32_t *R, uint32_t C, uint32_t x, uint32_t y)
-{
-    return x != y && closure_valid(L[x * C + y], R[x * C + y]);
-}
-
 // Confirm, one wave per pair (a, b), lanes over the third clip c: only the PICKED lags L vote.  The lane with c == b takes (b, a).
 __global__ __launch_bounds__(ASX_THREADS) void k_closure_confirm(const int64_t *__restrict__ L, const int32_t *__restrict__ R,
                                                                   uint32_t C, int64_t tol, int32_t *__restrict__ confirm)
@@ -1603,28 +1595,6 @@ __global__ __launch_bounds__(ASX_THREADS) void k_closure_confirm(const int64_t *
         }
     }
     if (lane == 0) confirm[pair] = n;
-}
-
-// a pair the offsets may use: good, and confirmed by at least min_confirm clips
-__device__ __forceinline__ bool closure_usable(const int64_t *L, const int32_t *R, const int32_t *F, uint32_t C, int min_confirm,
-                                               uint32_t x, uint32_t y)
-{
-    return closure_good(L, R, C, x, y) && F[x * C + y] >= min_confirm;
-}
-
-// the sum of v over a block of ASX_THREADS threads, in every thread, with one barrier; red: ASX_THREADS / 64 ints of LDS that the sum
-// before this one did not use (two buffers in turn: the barrier of a sum lies between the reads of the one before it and the
-// writes of the one after it)
-__device__ __forceinline__ int32_t closure_block_sum(int32_t v, int32_t *red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int32_t s = 0;
-#pragma unroll
-    for (int i = 0; i < ASX_THREADS / 64; i++) s += red[i];
-    return s;
 }
 
 // The root, one block: the given clip, or the one with the most usable pairs (a, .) and (., a), the smallest index among equals.
@@ -1698,8 +1668,7 @@ __device__ __forceinline__ void closure_estimates(const int64_t *L, const int32_
     }
 }
 
-// Offsets, one block per clip b: the lower median of E_b by rank counting -- the smallest v with #(x <= v) > (|E_b| - 1) / 2, found by
-// bisection between the smallest and the largest estimate, each step one count over the block -- and the number of estimates within
+// Offsets, one block per clip b: the lower median of E_b by rank counting (closure_lower_median) and the number of estimates within
 // tol of it.  E_b is never stored: an estimate is two lags and their flags, read again (from L2) at every step, so any C fits; a
 // pool whose usable pairs agree has its estimates a few frames apart and needs a few steps.
 __global__ __launch_bounds__(ASX_THREADS) void k_closure_offsets(const int64_t *__restrict__ L, const int32_t *__restrict__ R,
@@ -1708,51 +1677,19 @@ __global__ __launch_bounds__(ASX_THREADS) void k_closure_offsets(const int64_t *
                                                                   int64_t *__restrict__ offset, int32_t *__restrict__ support,
                                                                   int32_t *__restrict__ placed)
 {
-    __shared__ int32_t red[2][ASX_THREADS / 64];
-    __shared__ int64_t red_lo[ASX_THREADS / 64], red_hi[ASX_THREADS / 64];
+    __shared__ ClosureLds sh;
     const uint32_t b = blockIdx.x, r = (uint32_t)root[0];
     if (b == r) {
         if (threadIdx.x == 0) { offset[b] = 0; support[b] = 0; placed[b] = 1; }
         return;
     }
-    // how many estimates there are, the smallest and the largest
-    int32_t n = 0;
-    int64_t lo = INT64_MAX, hi = INT64_MIN;
-    for (uint32_t c = threadIdx.x; c < C; c += ASX_THREADS)
-        closure_estimates(L, R, F, C, min_confirm, r, b, c, [&](int64_t x) { n++; lo = x < lo ? x : lo; hi = x > hi ? x : hi; });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int64_t l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
-        lo = l2 < lo ? l2 : lo;
-        hi = h2 > hi ? h2 : hi;
-    }
-    if ((threadIdx.x & 63u) == 0) { red_lo[threadIdx.x >> 6] = lo; red_hi[threadIdx.x >> 6] = hi; }
-    const int32_t total = closure_block_sum(n, red[0]);         // (its barrier also covers red_lo and red_hi)
-#pragma unroll
-    for (int i = 0; i < ASX_THREADS / 64; i++) {
-        lo = red_lo[i] < lo ? red_lo[i] : lo;
-        hi = red_hi[i] > hi ? red_hi[i] : hi;
-    }
-    int turn = 0;
-    auto count_le = [&](int64_t v) {
-        int32_t m = 0;
-        for (uint32_t c = threadIdx.x; c < C; c += ASX_THREADS)
-            closure_estimates(L, R, F, C, min_confirm, r, b, c, [&](int64_t x) { m += x <= v ? 1 : 0; });
-        turn ^= 1;
-        return closure_block_sum(m, red[turn]);
+    auto each = [&](auto &&fn) {
+        for (uint32_t c = threadIdx.x; c < C; c += ASX_THREADS) closure_estimates(L, R, F, C, min_confirm, r, b, c, fn);
     };
+    int turn = 1;
     int64_t med = 0;
-    int32_t sup = 0;
-    if (total > 0) {
-        const int32_t want = (total - 1) / 2 + 1;               // the median is the smallest v with at least this many at or below it
-        lo -= 1;                                                // count_le(lo) = 0 < want <= total = count_le(hi)
-        while (hi - lo > 1) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (count_le(mid) >= want) hi = mid; else lo = mid;
-        }
-        med = hi;
-        sup = count_le(med + tol) - count_le(med - tol - 1);
-    }
+    const int32_t total = closure_lower_median(each, sh, turn, med);
+    const int32_t sup = total > 0 ? closure_count_near(each, med, tol, sh, turn) : 0;
     if (threadIdx.x == 0) { offset[b] = med; support[b] = sup; placed[b] = total > 0 ? 1 : 0; }
 }
 

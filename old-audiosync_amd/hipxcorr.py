@@ -102,6 +102,7 @@ _HEADER_SIGNATURES = {
     "asx_results_to_ms_dev": (_int, [_vp, _vp, _vp, _sz, _dbl, _dbl, _vp, _vp, _vp]),
     "asx_topk_best_dev": (_int, [_vp, _vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _vp]),
     "asx_pool_closure_dev": (_int, [_vp, _vp, _vp, _sz, _int, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asx_pool_place_dev": (_int, [_vp, _vp, _vp, _sz, _i64, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_synth_pairs_dev": (_int, [_u64, _u64, _sz, _sz, _int, _vp, _vp, _vp, _vp]),
     "asx_shard_range": (_int, [_sz, _int, _int, _szp, _szp]),
     "asx_result_bytes": (_sz, [_sz]),
@@ -156,6 +157,8 @@ TRACK_HALF_MAX = 64  # ASX_TRACK_HALF_MAX, include/audiosync/xcorr_hip.h
 TRACK_SEG_MAX = 64   # ASX_TRACK_SEG_MAX, include/audiosync/xcorr_hip.h
 WARP_DRIFT_MAX = 2.0 ** -6  # ASX_WARP_DRIFT_MAX, include/audiosync/xcorr_hip.h
 CLOSURE_LAG_MAX = 1 << 40   # ASX_CLOSURE_LAG_MAX, include/audiosync/xcorr_hip.h
+PLACE_HOPS_MAX = 1024       # ASX_PLACE_HOPS_MAX, include/audiosync/xcorr_hip.h
+PLACE_SWEEPS_MAX = 64       # ASX_PLACE_SWEEPS_MAX, include/audiosync/xcorr_hip.h
 NCC_MIN_ENERGY = 1e-6       # ASX_NCC_MIN_ENERGY, include/audiosync/xcorr_hip.h
 
 
@@ -428,6 +431,67 @@ def pool_closure(lag, coef, ret, tolerance, min_confirm=1, root=-1, device=-1, v
     if votes:
         out["votes"] = got[0]
     return out
+
+
+def pool_place_dev(d_lag, d_ret, d_confirm, nclips, tolerance, min_confirm, d_root, max_hops, sweeps, d_offset, d_hops, d_support,
+                   d_degree, d_step, d_resid, d_state, d_scratch=0, stream=0):
+    """raw device pointers (ints): asx_pool_place_dev -- from closure's picked tables (d_best_lag, d_best_ret, d_confirm, [C * C]) and
+    the root in device memory (d_root [1]), every clip that a chain of usable pairs reaches: hops from the root and offset per clip,
+    support, degree and the last sweep's step [C each], and per pair the residual against the offsets and a state (1 agrees, 2
+    disagrees, 0 not usable or an end not reached) [C * C each]; d_scratch [C] is needed when sweeps > 0; asynchronous on `stream`, on
+    the current device"""
+    _check(lib().asx_pool_place_dev(d_lag, d_ret, d_confirm, int(nclips), int(tolerance), int(min_confirm), d_root, int(max_hops),
+                                    int(sweeps), d_scratch or None, d_offset, d_hops, d_support, d_degree, d_step, d_resid, d_state,
+                                    stream or None))
+
+
+def place_args(best_lag, best_ret, confirm, root, tolerance, min_confirm=1, max_hops=64, sweeps=0):
+    """Host checks of pool_place: best_lag, best_ret and confirm integer arrays of one shape [C, C] with C >= 1 and C * C <= 2^31 - 1
+    (lags within int64, rets and confirms within int32); root an integer within int32 (outside [0, C) is legal: no clip is reached);
+    tolerance an integer in [0, CLOSURE_LAG_MAX], min_confirm an integer >= 0, max_hops one in [1, PLACE_HOPS_MAX], sweeps one in
+    [0, PLACE_SWEEPS_MAX] -- no bools, no floats.  -> (lag int64, ret int32, confirm int32, C, root, tolerance, min_confirm, max_hops,
+    sweeps) as contiguous arrays and ints.  ValueError on anything else."""
+    lg, rt, cf = np.asarray(best_lag), np.asarray(best_ret), np.asarray(confirm)
+    for name, a in (("best_lag", lg), ("best_ret", rt), ("confirm", cf)):
+        if a.dtype.kind not in "iu":
+            raise ValueError("%s must hold integers, not %s" % (name, a.dtype))
+    if lg.ndim != 2 or lg.shape[0] != lg.shape[1] or rt.shape != lg.shape or cf.shape != lg.shape:
+        raise ValueError("best_lag, best_ret and confirm must share one shape [C, C], not %s, %s and %s"
+                         % (list(lg.shape), list(rt.shape), list(cf.shape)))
+    c = lg.shape[0]
+    if c < 1 or c * c > 2 ** 31 - 1:
+        raise ValueError("[C, C] needs C >= 1 and C * C <= 2^31 - 1, not C = %d" % c)
+    if lg.dtype == np.uint64 and lg.max() > 2 ** 63 - 1:
+        raise ValueError("lags must fit int64")
+    for name, a in (("rets", rt), ("confirms", cf)):
+        if a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1:
+            raise ValueError("%s must fit int32" % name)
+    for name, v, lo, hi in (("root", root, -2 ** 31, 2 ** 31 - 1), ("tolerance", tolerance, 0, CLOSURE_LAG_MAX),
+                            ("min_confirm", min_confirm, 0, 2 ** 31 - 1), ("max_hops", max_hops, 1, PLACE_HOPS_MAX),
+                            ("sweeps", sweeps, 0, PLACE_SWEEPS_MAX)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError("%s must be an integer in [%d, %d], not %r" % (name, lo, hi, v))
+    return (np.ascontiguousarray(lg, dtype=np.int64), np.ascontiguousarray(rt, dtype=np.int32), np.ascontiguousarray(cf, dtype=np.int32),
+            c, int(root), int(tolerance), int(min_confirm), int(max_hops), int(sweeps))
+
+
+def pool_place(best_lag, best_ret, confirm, root, tolerance, min_confirm=1, max_hops=64, sweeps=0, device=-1):
+    """Placement over chains of usable pairs (asx_pool_place_dev) on host arrays: best_lag, best_ret, confirm of shape [C, C] and root
+    as pool_closure returns them, with the tolerance and min_confirm it was given.  Arguments are checked on the host (place_args,
+    ValueError) before anything is uploaded.  Returns a dict of numpy arrays: offset and step int64, hops, support and degree int32 of
+    shape [C]; resid int64 and state int32 of shape [C, C].  device: -1 or the current device (the call takes no plan)."""
+    lg, rt, cf, c, root, tolerance, min_confirm, max_hops, sweeps = place_args(best_lag, best_ret, confirm, root, tolerance, min_confirm,
+                                                                               max_hops, sweeps)
+    with _Staging(_CurrentDevice(int(device))) as st:
+        d_in = [st.upload(a) for a in (lg, rt, cf)]
+        d_root = st.upload(np.array([root], dtype=np.int32))
+        d_scratch = st.alloc(8 * c) if sweeps else 0
+        names = (("offset", (c,), np.int64), ("hops", (c,), np.int32), ("support", (c,), np.int32), ("degree", (c,), np.int32),
+                 ("step", (c,), np.int64), ("resid", (c, c), np.int64), ("state", (c, c), np.int32))
+        d_out = [st.output(shape, dt) for _, shape, dt in names]
+        pool_place_dev(*d_in, c, tolerance, min_confirm, d_root, max_hops, sweeps, *d_out, d_scratch=d_scratch)
+        got = st.fetch()
+    return dict(zip([n for n, _, _ in names], got))
 
 
 def synth_pairs_dev(seed, first_pair, count, sample_len, noise_shift, d_src, d_smp, d_lag=0, stream=0):
