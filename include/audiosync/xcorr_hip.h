@@ -48,7 +48,9 @@
  *   and peak = NaN, in all k entries.)
  *   ret = -5 (asx_xcorr_warp_f32_dev and asx_xcorr_pool_warp_f32_dev only): an entry's drift line is not valid; NaN in all its
  *   values and len = 0.  In these two calls -4 and -2 mean what they mean in the calls around given lags and take precedence, in
- *   that order.
+ *   that order.  (asx_xcorr_ncc_ragged_f32_dev and asx_xcorr_ncc_ragged_topk_f32_dev: a pair's row of lengths is not valid; lag = 0,
+ *   coef = NaN and peak = NaN in all k entries.  There it takes precedence over -2 and -3, which mean what they mean in
+ *   asx_xcorr_ncc_full_f32_dev.)
  */
 #ifndef AUDIOSYNC_XCORR_HIP_H
 #define AUDIOSYNC_XCORR_HIP_H
@@ -575,6 +577,74 @@ int asx_xcorr_ncc_full_topk_f32_dev(asx_plan *plan, const float *d_source, size_
 int asx_xcorr_ncc_full_debug_c_dev(asx_plan *plan, const float *d_source, const float *d_sample, double min_energy,
                                    int64_t min_overlap, float *d_c, int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret,
                                    void *stream);
+
+/* Ragged normalised cross-correlation: the curve of asx_xcorr_ncc_full_f32_dev for pairs whose tracks are shorter than the plan's
+ * shape.  Pair i's source holds Ls <= 2N frames and its sample Lm <= N, and every moment of a lag is taken over the frames that the
+ * two really share there.  (Cutting every track to the shortest throws the overlap away; zero-padding them lets the padding into Sy,
+ * Vy and the window sums, and a sample that rides on an offset becomes a rectangular pulse that is ranked against other pulses.)
+ *   Lengths.  Pair i's row {Ls, Lm} is read on the device, at d_lengths + 2 * i * length_stride, the way the rows of d_windows are
+ * read; a length_stride of 0 means one row for all pairs, and d_lengths == NULL means (2N, N) for every pair.  A row is valid iff
+ * 1 <= Ls <= 2N and 1 <= Lm <= N; any other row gives (0, NaN, NaN, -5) in all entries, which takes precedence over -2 and -3, the
+ * other pairs untouched bit for bit.  The tracks still occupy 2N and N floats at the caller's strides.  Frames at and beyond a track's
+ * length are ignored whatever they hold, NaN included: the call stages, per pair, x' = x[0, Ls) then zeros up to 2N, x_lo' =
+ * x[0, min(Ls, N)) then zeros, and y' = y[0, Lm) then zeros, and reads nothing else of them.  A broadcast track (a stride of 0) is
+ * staged and summed per pair as well, since each pair may cut it differently.
+ *   The curve.  Lags -(N-1) <= l <= N-1 at index l + N - 1, 2N - 1 values, as in the full-range call.  In float64, behind r32:
+ *     mu = mean x[0, Ls),  my = mean y[0, Lm),  a = x - mu,  b = y - my
+ *     PA1[j] = sum_{n<j} a[n],  PA2[j] = sum_{n<j} a[n]^2  (j = 0..Ls);   PB1, PB2 likewise over b (j = 0..Lm)
+ *     n0 = max(0, -l),  n1 = min(Lm, Ls - l),  m = n1 - n0            (m <= 0: the lag does not exist)
+ *     S1x = PA1[n1+l] - PA1[n0+l],  S2x likewise,  Vx[l] = S2x - S1x^2 / m,  Sx = S1x + m*mu   (y: over [n0, n1))
+ *     c[l] = (r32 / s - Sx * Sy / m) / sqrt(Vx[l] * Vy[l]),   c32 = (float) c
+ *     r32 = rA32[l] for l >= 0,  rlo32[2N + l] for l < 0;   s = asx_plan_fft_len()
+ * rA32 is the float32 r of the plan's transforms for (x', y'), rlo32 for (x_lo', y').  With the zeros in place nothing wraps: for
+ * l >= 0 the source index n + l is at most 2N - 2, and for l < 0 the wrapped indices fall in the zero half of x_lo'.
+ *   Which lags compete.  Lag l competes iff m >= min(min_overlap, Ls, Lm), Vy > 0, Vx[l] * Vy[l] >= min_energy * Vmax * Vy, and c[l]
+ * is finite.  Vy = PB2[Lm] - PB1[Lm]^2 / Lm is the sample's energy about my over [0, Lm); Vmax is the largest window energy
+ * (PA2[j+w] - PA2[j]) - (PA1[j+w] - PA1[j])^2 / w of the source over the windows x[j, j+w), w = min(Ls, Lm), 0 <= j <= min(Ls - w,
+ * N - 1).  1 <= min_overlap <= N, min_energy as in the NCC call.  With (2N, N) this is the full-range call's rule on both sides of
+ * zero (the sums are formed in another order, so a lag at the threshold may fall on the other side and the last bits of c32 may
+ * differ).  A short sample under the default min_overlap competes only at the lags of full overlap: template matching.  A lag within
+ * a relative 1e-6 of the threshold may fall on either side.
+ *   Rows, the peak, the outputs: the full-range call's, word for word -- rows -(N-1) <= lag_min <= lag_max <= N-1 or (0, NaN, NaN,
+ * -2); the largest |c32| wins, the smallest lag among equals; no lag competes: lag = the row's lag_min and peak = 0.  coef is the
+ * direct Pearson form over source[n0+l, n1+l) against sample[n0, n1), from the caller's tracks; a returned lag with m <= 0 has an
+ * empty segment: coef = NaN and ret = -1, the reference's empty-segment case.  ret is never 1.
+ *   Strides, the layout rule, the stream rule and the refusals are the full-range call's, plus d_lengths == NULL together with a
+ * length_stride other than 0.  Every value of a pair is independent of the batch size and of the pair's position in the batch: the
+ * sums are fixed trees that N and the pair's lengths decide, Vmax an order-free maximum.  The call takes no listing and no second
+ * look, touches no counters, never synchronises the host, behaves the same whatever the plan's setters say and runs on every plan,
+ * packed ones included.
+ *   Memory.  A set of its own, allocated at the plan's first ragged call and kept with the plan; not counted in
+ * asx_plan_workspace_bytes; refused inside a stream capture until it exists.  Per pair of one group: the staged x' and x_lo' (8N
+ * bytes each) and y' (4N), two r buffers (16N; the top-k call keeps the curve in the halves that nothing reads), the prefix tables
+ * of 2N + 1 and N + 1 double2 (32N + 16N): 84N bytes, plus three doubles per 2048 frames of every track.  The call works in groups
+ * of min(asx_plan_group(), 2^30 / 84N) pairs, at least one, so the set holds at most 1 GiB (or one pair's 84N bytes).
+ *   Cost: the full-range call's two transform passes, and in place of its moment passes one pass that stages the tracks and three
+ * over the staged copies and tables (measured: DESIGN.md).
+ *   Not offered: pools (the next step, as the full-range call went); lags >= N, which a short sample would leave unwrapped in pass
+ * A; the double ABI; streams. */
+int asx_xcorr_ncc_ragged_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                                 const float *d_sample, size_t sample_stride,
+                                 const int64_t *d_lengths, size_t length_stride,
+                                 const int64_t *d_windows, size_t window_stride, size_t batch,
+                                 double min_energy, int64_t min_overlap,
+                                 int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+/* ... with the K strongest separated lags per pair: the rule and the outputs of asx_xcorr_ncc_full_topk_f32_dev (signed lags, no wrap
+ * between N-1 and -(N-1), -3 behind an empty A_j, -2 and -5 in all k entries) over the ragged curve.  k = 1 launches exactly
+ * asx_xcorr_ncc_ragged_f32_dev, and entry 0 is always bit for bit the k = 1 result.  Refusals: those of that call, plus k and
+ * min_separation out of range. */
+int asx_xcorr_ncc_ragged_topk_f32_dev(asx_plan *plan, const float *d_source, size_t source_stride,
+                                      const float *d_sample, size_t sample_stride,
+                                      const int64_t *d_lengths, size_t length_stride,
+                                      const int64_t *d_windows, size_t window_stride, size_t batch,
+                                      double min_energy, int64_t min_overlap, int k, int64_t min_separation,
+                                      int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
+/* ONE contiguous pair of the lengths (source_len, sample_len), host values under the rule of a row of d_lengths: c32 of the lags
+ * -(N-1)..N-1 to d_c (2N - 1 floats, lag l at index l + N - 1, NaN where the lag does not exist or does not compete); the results
+ * are those of asx_xcorr_ncc_ragged_f32_dev for that pair without rows */
+int asx_xcorr_ncc_ragged_debug_c_dev(asx_plan *plan, const float *d_source, const float *d_sample, int64_t source_len,
+                                     int64_t sample_len, double min_energy, int64_t min_overlap, float *d_c, int64_t *d_lag,
+                                     double *d_coef, double *d_peak, int32_t *d_ret, void *stream);
 
 /* Full-range normalised cross-correlation over listed pairs of two track pools: the pairs of asx_xcorr_pool_ncc_f32_dev under the
  * curve of asx_xcorr_ncc_full_f32_dev.  An all-pairs table over the clips of one event needs both: every track transformed once, and

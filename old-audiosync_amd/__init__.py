@@ -17,5 +17,6 @@ from .hipxcorr import (  # noqa: F401
     Comm, PinnedArray, result_bytes, shard_range, closure_args, pool_closure, pool_closure_dev, phat_topk_args, pool_phat_topk_args,
     NCC_MIN_ENERGY, ncc_args, ncc_topk_args, pool_ncc_args, pool_ncc_topk_args,
     ncc_full_args, ncc_full_topk_args, pool_ncc_full_args, pool_ncc_full_topk_args,
+    ncc_ragged_args, ncc_ragged_topk_args, ragged_pack,
     PLACE_HOPS_MAX, PLACE_SWEEPS_MAX, place_args, pool_place, pool_place_dev,
 )

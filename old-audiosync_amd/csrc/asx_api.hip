@@ -119,7 +119,7 @@ struct asx_plan {
 
     // Who owns the plan's device memory (asx_plan_workspace_bytes: all but the bank's and the NCC sets').  mem: what plan_init takes and, once created,
     // the lazy sets (big, bslot, st, st64: whole or absent); cxy0: lane 0's C_x / C_y, which tune_placement may replace; bank.mem; ncc.mem;
-    // ncc.tmem; nccfull.mem; nccfull.pmem.
+    // ncc.tmem; nccfull.mem; nccfull.pmem; nccrag.mem.
     AsxMemSet mem{ hip_mem }, cxy0{ hip_mem };
     // "Lanes": each owns the workspaces of one launch group and a stream.  With two lanes
     // (ASX_LANES=2) consecutive groups of a batch alternate lanes so that kernels of different
@@ -199,6 +199,14 @@ struct asx_plan {
         size_t nsrc = 0, nsmp = 0;
         unsigned long long staged = 0, suffixed = 0;
     } nccfull;
+    // The ragged NCC calls (asx_xcorr_ncc_ragged_f32_dev; lazy, whole or absent, allocated at the plan's first such call): per pair of
+    // one group the staged tracks, the two r buffers, the prefix tables and the small sums (AsxNccRagWs).  Its own set, with its own
+    // bound (ensure_ncc_ragged): not part of asx_plan_workspace_bytes.
+    struct NccRag {
+        AsxNccRagWs w{};
+        AsxMemSet mem{ hip_mem };
+        size_t group = 0;
+    } nccrag;
     // pairs whose near-tie list overflowed since the list was last emptied (k_finalize appends, resolve_overflows reads)
     uint32_t *over_list = nullptr, *over_n = nullptr;
     volatile uint32_t *h_over_n = nullptr; // page-locked host mirror of *over_n (device-visible: AsxPeakWs::over_host)
@@ -2340,6 +2348,158 @@ extern "C" int asx_xcorr_ncc_full_debug_c_dev(asx_plan *p, const float *d_source
     const size_t N = p->host.N;
     return ncc_full_batch(p, fn, d_source, 2 * N, d_sample, N, nullptr, 0, 1, min_energy, min_overlap, d_c,
                           { d_lag, d_coef, d_ret, 1, d_peak }, stream);
+}
+
+// ---------------------------------------------------------------------------
+// ragged NCC (asx_xcorr_ncc_ragged_f32_dev): the full-range curve for pairs whose tracks hold Ls <= 2N and Lm <= N frames
+// ---------------------------------------------------------------------------
+// The plan's ragged set, per pair of one group: the staged x', x_lo' (8N bytes each) and y' (4N), two r buffers (16N), the prefix
+// tables of 2N + 1 and N + 1 double2 (32N + 16N): ASX_NCCRAG_PAIR_BYTES * N bytes, plus the chunk sums.  Every pair has all of it,
+// a broadcast track's too.
+#define ASX_NCCRAG_PAIR_BYTES 84
+static int ensure_ncc_ragged(asx_plan *p, const char *fn, hipStream_t s)
+{
+    if (p->nccrag.w.r) return 0;
+    if (stream_capturing(s))
+        return fail("%s: the plan's ragged NCC workspace does not exist yet and cannot be allocated during a stream capture; make "
+                    "one call outside the capture first", fn);
+    const size_t N = p->host.N, xpitch = (2 * N + 3) & ~(size_t)3, ypitch = (N + 3) & ~(size_t)3;
+    const size_t g = std::max<size_t>(1, std::min(p->group, ASX_NCC_WS_BYTES / (ASX_NCCRAG_PAIR_BYTES * N)));
+    const size_t chunks = g * ((size_t)asx_ncc_chunks((uint32_t)(2 * N)) + asx_ncc_chunks((uint32_t)N));
+    if (asx_mem_whole(p->nccrag.mem, p->nccrag.w, [&](AsxMemSet &m, AsxNccRagWs &T) {
+            T.xpitch = xpitch; T.ypitch = ypitch;
+            return m.take(&T.xs, g * xpitch) || m.take(&T.xlo, g * xpitch) || m.take(&T.ys, g * ypitch) || m.take(&T.r, g * 2 * N) ||
+                           m.take(&T.rlo, g * 2 * N) || m.take(&T.pa, g * (2 * N + 1)) || m.take(&T.pb, g * (N + 1)) ||
+                           m.take(&T.raw, chunks) || m.take(&T.m1, chunks) || m.take(&T.m2, chunks) ||
+                           m.take(&T.stat, g * ASX_NCC_STAT) || m.take(&T.best, g) || m.take(&T.tk, g)
+                       ? -1 : 0;
+        }))
+        return fail("%s: hipMalloc of the ragged NCC workspace failed: %s", fn, hipGetErrorString(g_take_err));
+    p->nccrag.group = g;
+    return 0;
+}
+
+// ncc_full_batch's sibling for the ragged calls, after the entry point's null checks and the top-k option's.  lens: where a pair's
+// {Ls, Lm} is read (AsxRagLens: device rows, or one pair of values).  c_out: the debug call's curve (one contiguous pair, 2N - 1
+// floats), else null.  topk.k > 1: y's entry stride is k.  The transforms read the staged copies only, with no broadcast slot: a
+// shared track is cut per pair.
+static int ncc_ragged_batch(asx_plan *p, const char *fn, const float *d_source, size_t source_stride, const float *d_sample,
+                            size_t sample_stride, const AsxRagLens &lens, const int64_t *d_windows, size_t window_stride, size_t batch,
+                            double min_energy, int64_t min_overlap, float *c_out, const Results &y, void *stream, const Topk &topk = {})
+{
+    if (!(min_energy >= ASX_NCC_MIN_ENERGY && min_energy <= 1.0)) // (a NaN fails both)
+        return fail("%s: min_energy %g is not in [%g, 1]", fn, min_energy, (double)ASX_NCC_MIN_ENERGY);
+    if (min_overlap < 1 || min_overlap > (int64_t)p->host.N)
+        return fail("%s: min_overlap %lld is not in [1, %zu]", fn, (long long)min_overlap, p->host.N);
+    if (!lens.rows && lens.step != 0)
+        return fail("%s: length_stride %zu without lengths (d_lengths is null)", fn, lens.step);
+    PlanCall c(p, stream);
+    if (!c.dg.ok) return fail("cannot select device %d", p->device);
+    hipStream_t s = c.s;
+    const AsxDev &P = p->dev;
+    if (strided_layout(p, fn, d_source, source_stride, d_sample, sample_stride)) return -1;
+    if (batch == 0) return 0;
+    if (ensure_ncc_ragged(p, fn, s)) return -1;
+    asx_plan::Lane &L = p->lanes[0];
+    const AsxNccRagWs &R = p->nccrag.w;
+    // what k_nccfull_scan and k_nccfull_step take of a group: the two r buffers that keep the curve, the maxima and the records
+    AsxNccWs W{};
+    W.r = R.r; W.best = R.best; W.tk = R.tk;
+    AsxNccFullWs F{};
+    F.rlo = R.rlo;
+    const int K = topk.k;
+    const Pairs<float> x = Pairs<float>::strided(d_source, source_stride, d_sample, sample_stride, 0, nullptr, 0);
+    const Pairs<float> xa = Pairs<float>::strided(R.xs, R.xpitch, R.ys, R.ypitch, 0, nullptr, 0);
+    const Pairs<float> xb = Pairs<float>::strided(R.xlo, R.xpitch, R.ys, R.ypitch, 0, nullptr, 0);
+    prof_begin_call(p);
+    size_t gi = 0;
+    for (size_t done = 0; done < batch; done += p->nccrag.group, gi++) {
+        const size_t g = std::min(p->nccrag.group, batch - done);
+        const Pairs<float> xg = x.at(done);
+        const Results yg = y.at(done);
+        const int64_t *rows = d_windows ? d_windows + 2 * done * window_stride : nullptr;
+        AsxRagLens lg = lens;
+        if (lg.rows) lg.rows += 2 * done * lg.step;
+        asx_launch_nccrag_tracks(R, lg, xg.src, source_stride, xg.smp, sample_stride, P.N, (int)g, s);
+        // pass A: (x', y') -> r of the lags >= 0; pass B: (x_lo', y') -> r of the lags < 0
+        if (run_group(p, xa, g, yg, s, { .prof_group = gi, .listed = false, .f32_abi = false, .r_out = R.r, .transforms_only = true }))
+            return -1;
+        if (run_group(p, xb, g, yg, s, { .prof_group = GroupOpts::no_marks, .listed = false, .f32_abi = false, .r_out = R.rlo,
+                                         .transforms_only = true }))
+            return -1;
+        asx_launch_nccrag_peak(R, lg, P.N, (double)P.F, min_energy, min_overlap, rows, window_stride, c_out, L.seg, yg.peak, (int)g, s, K);
+        // the reference's coefficient over the overlap, in the direct form, from the caller's tracks
+        const AsxInputs<float> in = xg.inputs(nullptr);
+        if (K == 1) {
+            asx_launch_pearson(in, P.N, L.seg, L.psums, yg.lag, yg.coef, yg.ret, (int)g, s);
+            if (rows) asx_launch_nccfull_invalid(P.N, rows, window_stride, yg.lag, yg.coef, yg.peak, yg.ret, (int)g, s);
+        } else {
+            // ncc_full_batch's passes; behind each step the entry's segment by the pair's lengths
+            for (int j = 0; j <= K; j++) {
+                if (j > 0 && j < K) asx_launch_nccfull_scan(W, F, P.nout, P.N, rows, window_stride, topk.sep, j, (int)g, s);
+                asx_launch_nccfull_step(W, P.N, rows, window_stride, topk.sep, j, K, L.seg, L.tk.lag, L.tk.coef, L.tk.ret, yg.lag, yg.coef,
+                                        yg.peak, yg.ret, (int)g, s);
+                if (j < K) {
+                    asx_launch_nccrag_seg(R, lg, P.N, j, L.seg, (int)g, s);
+                    asx_launch_pearson(in, P.N, L.seg, L.psums, L.tk.lag, L.tk.coef, L.tk.ret, (int)g, s);
+                }
+            }
+        }
+        if (lg.rows || !(1 <= lg.ls && lg.ls <= 2 * (int64_t)P.N && 1 <= lg.lm && lg.lm <= (int64_t)P.N))
+            asx_launch_nccrag_invalid(lg, P.N, K, yg.lag, yg.coef, yg.peak, yg.ret, (int)g, s); // -5 takes precedence over -2 and -3
+        HIP_TRY(hipGetLastError());
+    }
+    prof_end_call(p, gi);
+    return 0;
+}
+
+extern "C" int asx_xcorr_ncc_ragged_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                            size_t sample_stride, const int64_t *d_lengths, size_t length_stride,
+                                            const int64_t *d_windows, size_t window_stride, size_t batch, double min_energy,
+                                            int64_t min_overlap, int64_t *d_lag, double *d_coef, double *d_peak, int32_t *d_ret,
+                                            void *stream)
+{
+    static const char *fn = "asx_xcorr_ncc_ragged_f32_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    const int64_t N = (int64_t)p->host.N;
+    return ncc_ragged_batch(p, fn, d_source, source_stride, d_sample, sample_stride, { d_lengths, length_stride, 2 * N, N }, d_windows,
+                            window_stride, batch, min_energy, min_overlap, nullptr, { d_lag, d_coef, d_ret, 1, d_peak }, stream);
+}
+
+// The K strongest separated lags of the ragged curve: k = 1 launches exactly asx_xcorr_ncc_ragged_f32_dev.
+extern "C" int asx_xcorr_ncc_ragged_topk_f32_dev(asx_plan *p, const float *d_source, size_t source_stride, const float *d_sample,
+                                                 size_t sample_stride, const int64_t *d_lengths, size_t length_stride,
+                                                 const int64_t *d_windows, size_t window_stride, size_t batch, double min_energy,
+                                                 int64_t min_overlap, int k, int64_t min_separation, int64_t *d_lag, double *d_coef,
+                                                 double *d_peak, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_ncc_ragged_topk_f32_dev";
+    if (!p || !d_source || !d_sample || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    if (!ncc_topk_option(fn, k, min_separation)) return -1;
+    const int64_t N = (int64_t)p->host.N;
+    return ncc_ragged_batch(p, fn, d_source, source_stride, d_sample, sample_stride, { d_lengths, length_stride, 2 * N, N }, d_windows,
+                            window_stride, batch, min_energy, min_overlap, nullptr, { d_lag, d_coef, d_ret, (size_t)k, d_peak }, stream,
+                            Topk{ k, min_separation });
+}
+
+extern "C" int asx_xcorr_ncc_ragged_debug_c_dev(asx_plan *p, const float *d_source, const float *d_sample, int64_t source_len,
+                                                int64_t sample_len, double min_energy, int64_t min_overlap, float *d_c, int64_t *d_lag,
+                                                double *d_coef, double *d_peak, int32_t *d_ret, void *stream)
+{
+    static const char *fn = "asx_xcorr_ncc_ragged_debug_c_dev";
+    if (!p || !d_source || !d_sample || !d_c || !d_coef || !d_peak || !d_ret) return fail("%s: null argument", fn);
+    const size_t N = p->host.N;
+    return ncc_ragged_batch(p, fn, d_source, 2 * N, d_sample, N, { nullptr, 0, source_len, sample_len }, nullptr, 0, 1, min_energy,
+                            min_overlap, d_c, { d_lag, d_coef, d_ret, 1, d_peak }, stream);
+}
+
+// diagnostic: the ragged set's pairs per group and its bytes (0, 0 until the plan's first ragged call)
+extern "C" int asx_plan_debug_ncc_ragged(asx_plan *p, uint64_t out[2])
+{
+    if (!p || !out) return -1;
+    out[0] = p->nccrag.group;
+    out[1] = p->nccrag.mem.bytes();
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -836,6 +836,50 @@ void asx_launch_nccfull_pool_tracks(const AsxNccWs &T, const AsxNccFullWs &F, co
 void asx_launch_nccfp_peak(const AsxNccWs &W, const AsxNccFullWs &F, size_t r_pitch, uint32_t N, double scale, double min_energy,
                            int64_t min_overlap, const int64_t *rows, size_t rows_step, AsxSeg *seg, double *peak, int npairs,
                            hipStream_t s, const AsxPoolPair *pl, int k = 1);
+// Ragged NCC (asx_xcorr_ncc_ragged_f32_dev; the k_nccrag_* kernels, ncc.hip): the full-range curve of 2N - 1 indices for a pair whose
+// tracks hold Ls <= 2N and Lm <= N frames.  Every pair has staged copies of its own (x' = x[0, Ls) then zeros, x_lo' = x[0, min(Ls, N))
+// then zeros, y' = y[0, Lm) then zeros), which the two transform passes read, and prefix tables over the frames that count.
+// A pair's lengths: row {Ls, Lm} at rows + 2 * pair * step in device memory (step 0: one row for every pair), or, rows null, (ls, lm).
+struct AsxRagLens {
+    const int64_t *rows;
+    size_t step;
+    int64_t ls, lm;
+};
+// a row that is no pair of lengths (false) counts as (0, 0): nothing of its tracks is read and no lag exists
+__host__ __device__ inline bool asx_nccrag_lens(const AsxRagLens &L, size_t pair, uint32_t N, uint32_t &Ls, uint32_t &Lm)
+{
+    const int64_t a = L.rows ? L.rows[2 * pair * L.step] : L.ls, b = L.rows ? L.rows[2 * pair * L.step + 1] : L.lm;
+    const bool ok = 1 <= a && a <= 2 * (int64_t)N && 1 <= b && b <= (int64_t)N;
+    Ls = ok ? (uint32_t)a : 0u;
+    Lm = ok ? (uint32_t)b : 0u;
+    return ok;
+}
+struct AsxNccRagWs {
+    float *xs, *xlo;       // [pairs][xpitch] x' and x_lo'
+    float *ys;             // [pairs][ypitch] y'
+    size_t xpitch, ypitch; // 2N and N rounded up to whole 16-byte vectors
+    float *r, *rlo;        // [pairs][2N] r of (x', y') and of (x_lo', y'); a top-k group keeps the curve where the full-range call does
+    double2 *pa;           // [pairs][2N + 1] {PA1[j], PA2[j]} = sums of (x[n] - mu) and its square over n < j, j = 0..Ls
+    double2 *pb;           // [pairs][N + 1] the same over y - my, j = 0..Lm
+    double *raw, *m1, *m2; // chunk sums: pair i's source chunks at i * (chunks(2N) + chunks(N)), its sample chunks behind them
+    double *stat;          // [pairs][ASX_NCC_STAT] {mu, Vmax, my, -}
+    asx_peak_t *best;      // [pairs]
+    AsxNccTopk *tk;        // [pairs]
+};
+// k_nccrag_stage, k_nccrag_moments, k_nccrag_prefix, k_nccrag_vmax: the staged copies, means, prefix tables and Vmax of npairs pairs
+void asx_launch_nccrag_tracks(const AsxNccRagWs &R, const AsxRagLens &L, const float *src, size_t src_pitch, const float *smp,
+                              size_t smp_pitch, uint32_t N, int npairs, hipStream_t s);
+// k_nccrag_peak and k_nccrag_finalize: asx_launch_nccfull_peak for ragged pairs (seg: the overlap of the winner's lag in the caller's
+// tracks).  k > 1: the curve stays where k_nccfull_scan reads it and k_nccrag_finalize does not run.
+void asx_launch_nccrag_peak(const AsxNccRagWs &R, const AsxRagLens &L, uint32_t N, double scale, double min_energy, int64_t min_overlap,
+                            const int64_t *rows, size_t rows_step, float *c_out, AsxSeg *seg, double *peak, int npairs, hipStream_t s,
+                            int k = 1);
+// behind asx_launch_nccfull_step(j) of a ragged top-k group (k_nccrag_seg): entry j's segment by the pair's lengths, an empty one where
+// the entry is not to be
+void asx_launch_nccrag_seg(const AsxNccRagWs &R, const AsxRagLens &L, uint32_t N, int j, AsxSeg *seg, int npairs, hipStream_t s);
+// last of a group (k_nccrag_invalid): (0, NaN, NaN, -5) in all k entries of every pair whose row is no pair of lengths
+void asx_launch_nccrag_invalid(const AsxRagLens &L, uint32_t N, int k, int64_t *lag, double *coef, double *peak, int32_t *ret, int npairs,
+                               hipStream_t s);
 void asx_launch_cvt_f64_f32(const double *in, float *out, size_t n, hipStream_t s);
 unsigned asx_pearson_blocks(uint32_t basis_len); // partial blocks per pair: psums holds 6 doubles per block and pair
 // second look, DC removal: stats[0] = mean of source[0..2N), stats[1] = sum of sample[0..N), stats[2] = scale * stats[0] * stats[1]

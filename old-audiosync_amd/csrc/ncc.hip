@@ -812,3 +812,325 @@ void asx_launch_nccfull_invalid(uint32_t N, const int64_t *rows, size_t rows_ste
     hipLaunchKernelGGL(k_nccfull_invalid, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, N, rows, rows_step, lag, coef, peak, ret,
                        npairs);
 }
+
+// ---- ragged tracks (asx_xcorr_ncc_ragged_f32_dev and its top-k form): pair i holds Ls <= 2N source and Lm <= N sample frames ---------
+// The curve is the full-range call's in shape: 2N - 1 values, index i = l + N - 1, so the row rule, the zones, k_nccfull_scan and
+// k_nccfull_step and the places where a top-k group keeps the curve are that call's.  What differs is what a lag's moments are taken
+// over: sample frames [n0, n1) = [max(0, -l), min(Lm, Ls - l)) against source frames [n0 + l, n1 + l), m = n1 - n0 of them (m <= 0:
+// the lag does not exist), from prefix tables over the frames that count, about the means of those frames.  Frames at and beyond a
+// length are never read: the kernels below read the caller's tracks once (k_nccrag_stage) and then the staged copies, whose tails
+// are zero, and the two transform passes read only those (pass A: x', pass B: x_lo').  Every pair is staged and summed by itself, a
+// broadcast track too: each pair may cut it differently.  The trees are fixed by N and the pair's lengths.
+//   k_nccrag_stage     grid (source chunks + sample chunks, pairs): x', x_lo' and y' of the chunk, its plain sum
+//   k_nccrag_moments   same grid: the mean over [0, len) from the chunk sums, then sum (x - mu) and sum (x - mu)^2 of the chunk
+//   k_nccrag_prefix    same grid: block c starts from the chunk sums in front of c and scans its frames -> {PA1, PA2}[j], j <= len
+//   k_nccrag_vmax      grid (chunks(N), pairs): the largest energy of a window x[j, j + w), w = min(Ls, Lm) (atomic maximum)
+//   k_nccrag_peak      grid (chunks of the 2N - 1 indices, pairs): c32, the row and the competing rule, the packed maximum
+//   k_nccrag_finalize / k_nccrag_seg / k_nccrag_invalid: a thread per pair -- the winner's (a top-k entry's) segment, the -5 rows
+// (k_nccrag_*, not k_nccfull_*: see the note at k_nccfp_peak.)
+#define NCCRAG_VEC (ASX_NCC_CHUNK / 4 / NCC_NT)
+static_assert(NCCRAG_VEC == 2, "two 16-byte vectors of a chunk per thread");
+
+// which track and chunk a block of the grid (source chunks + sample chunks, pairs) owns
+struct NccRagChunk {
+    bool src;
+    uint32_t len, c, nc, f0; // the track's length, the block's chunk, the track's chunks, the chunk's first frame
+    size_t slot;             // where the chunk's sums go in raw / m1 / m2
+};
+__device__ __forceinline__ NccRagChunk nccrag_chunk_of(const AsxRagLens &L, uint32_t N)
+{
+    const uint32_t nsc = asx_ncc_chunks(2u * N), nyc = asx_ncc_chunks(N);
+    uint32_t Ls, Lm;
+    asx_nccrag_lens(L, blockIdx.y, N, Ls, Lm);
+    NccRagChunk k;
+    k.src = blockIdx.x < nsc;
+    k.c = k.src ? blockIdx.x : blockIdx.x - nsc;
+    k.nc = k.src ? nsc : nyc;
+    k.len = k.src ? Ls : Lm;
+    k.f0 = k.c * ASX_NCC_CHUNK;
+    k.slot = (size_t)blockIdx.y * (nsc + nyc) + blockIdx.x;
+    return k;
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_nccrag_stage(AsxNccRagWs R, AsxRagLens L, const float *__restrict__ src, size_t src_pitch,
+                                                          const float *__restrict__ smp, size_t smp_pitch, uint32_t N)
+{
+    __shared__ double lds[2 * (NCC_NT / 64)];
+    const NccRagChunk k = nccrag_chunk_of(L, N);
+    const size_t pair = blockIdx.y, pitch = k.src ? R.xpitch : R.ypitch;
+    const float *x = k.src ? src + pair * src_pitch : smp + pair * smp_pitch;
+    float *out = (k.src ? R.xs : R.ys) + pair * pitch;
+    const bool vec = ((uintptr_t)x & 15u) == 0;
+    double s = 0.0, z = 0.0;
+#pragma unroll
+    for (int j = 0; j < NCCRAG_VEC; j++) {
+        const uint32_t f = k.f0 + 4u * (j * NCC_NT + threadIdx.x);
+        if (f >= pitch) continue; // (the pitch is a whole number of vectors)
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (vec && f + 3 < k.len) v = *reinterpret_cast<const float4 *>(x + f);
+        else {
+            if (f < k.len) v.x = x[f];
+            if (f + 1 < k.len) v.y = x[f + 1];
+            if (f + 2 < k.len) v.z = x[f + 2];
+            if (f + 3 < k.len) v.w = x[f + 3];
+        }
+        s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
+        *reinterpret_cast<float4 *>(out + f) = v;
+        if (k.src) {
+            if (f >= N) v.x = 0.f;
+            if (f + 1 >= N) v.y = 0.f;
+            if (f + 2 >= N) v.z = 0.f;
+            if (f + 3 >= N) v.w = 0.f;
+            *reinterpret_cast<float4 *>(R.xlo + pair * pitch + f) = v;
+        }
+    }
+    ncc_block_sum2(s, z, lds);
+    if (threadIdx.x == 0) {
+        R.raw[k.slot] = s;
+        if (blockIdx.x == 0) R.stat[pair * ASX_NCC_STAT + 1] = 0.0; // Vmax, which k_nccrag_vmax raises
+    }
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_nccrag_moments(AsxNccRagWs R, AsxRagLens L, uint32_t N)
+{
+    __shared__ double lds[2 * (NCC_NT / 64)];
+    const NccRagChunk k = nccrag_chunk_of(L, N);
+    const size_t pair = blockIdx.y, pitch = k.src ? R.xpitch : R.ypitch;
+    const float *x = (k.src ? R.xs : R.ys) + pair * pitch;
+    double tot, z;
+    ncc_sum_arrays(R.raw + (k.slot - k.c), nullptr, k.nc, tot, z, lds);
+    const double mu = k.len ? tot / (double)k.len : 0.0;
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < NCCRAG_VEC; j++) {
+        const uint32_t f = k.f0 + 4u * (j * NCC_NT + threadIdx.x);
+        if (f >= k.len) continue; // (f < len <= pitch: the vector lies inside the staged track)
+        const float4 v = *reinterpret_cast<const float4 *>(x + f);
+        const float e[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            if (f + q < k.len) { const double a = (double)e[q] - mu; s1 += a; s2 += a * a; }
+    }
+    ncc_block_sum2(s1, s2, lds);
+    if (threadIdx.x == 0) {
+        R.m1[k.slot] = s1;
+        R.m2[k.slot] = s2;
+        if (k.c == 0) R.stat[pair * ASX_NCC_STAT + (k.src ? 0 : 2)] = mu;
+    }
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_nccrag_prefix(AsxNccRagWs R, AsxRagLens L, uint32_t N)
+{
+    __shared__ double lds[2 * (NCC_NT / 64)];
+    const NccRagChunk k = nccrag_chunk_of(L, N);
+    const size_t pair = blockIdx.y, pitch = k.src ? R.xpitch : R.ypitch;
+    const float *x = (k.src ? R.xs : R.ys) + pair * pitch;
+    const double mu = R.stat[pair * ASX_NCC_STAT + (k.src ? 0 : 2)];
+    // where the scan starts: the whole chunks in front of c
+    double w1, w2;
+    ncc_sum_arrays(R.m1 + (k.slot - k.c), R.m2 + (k.slot - k.c), k.c, w1, w2, lds);
+    // the thread's eight consecutive frames f .. f + 7: the inclusive prefix inside the thread, ...
+    const uint32_t f = k.f0 + threadIdx.x * NCC_PER;
+    float4 u = make_float4(0.f, 0.f, 0.f, 0.f), v = u;
+    if (f < k.len) u = *reinterpret_cast<const float4 *>(x + f);
+    if (f + 4 < k.len) v = *reinterpret_cast<const float4 *>(x + f + 4);
+    const float e[NCC_PER] = { u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w };
+    double p1[NCC_PER], p2[NCC_PER], t1 = 0.0, t2 = 0.0;
+#pragma unroll
+    for (int q = 0; q < NCC_PER; q++) {
+        const double a = f + q < k.len ? (double)e[q] - mu : 0.0;
+        t1 += a;
+        t2 += a * a;
+        p1[q] = t1; p2[q] = t2;
+    }
+    // ... across the lanes (an inclusive scan of the threads' totals), across the waves: k_nccfull_prefix's order
+    double i1 = t1, i2 = t2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double u1 = __shfl_up(i1, off, 64), u2 = __shfl_up(i2, off, 64);
+        if (lane >= off) { i1 += u1; i2 += u2; }
+    }
+    __syncthreads();
+    if (lane == 63) { lds[wave] = i1; lds[NCC_NT / 64 + wave] = i2; }
+    __syncthreads();
+    double o1 = __shfl_up(i1, 1, 64), o2 = __shfl_up(i2, 1, 64); // exclusive in the wave
+    if (lane == 0) { o1 = 0.0; o2 = 0.0; }
+    for (int w = 0; w < wave; w++) { o1 += lds[w]; o2 += lds[NCC_NT / 64 + w]; }
+    double2 *tab = k.src ? R.pa + pair * (2 * (size_t)N + 1) : R.pb + pair * ((size_t)N + 1);
+#pragma unroll
+    for (int q = 0; q < NCC_PER; q++)
+        if (f + q < k.len) tab[f + q + 1] = make_double2(w1 + (o1 + p1[q]), w2 + (o2 + p2[q])); // (f + q + 1 <= len: inside the table)
+    if (k.c == 0 && threadIdx.x == 0) tab[0] = make_double2(0.0, 0.0);
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_nccrag_vmax(AsxNccRagWs R, AsxRagLens L, uint32_t N)
+{
+    const size_t pair = blockIdx.y;
+    uint32_t Ls, Lm;
+    if (!asx_nccrag_lens(L, pair, N, Ls, Lm)) return;
+    // the windows x[j, j + w), 0 <= j <= min(Ls - w, N - 1): j + w <= Ls, inside the table
+    const uint32_t w = Ls < Lm ? Ls : Lm, jmax = Ls - w < N - 1u ? Ls - w : N - 1u;
+    const double2 *pa = R.pa + pair * (2 * (size_t)N + 1);
+    const double dw = (double)w;
+    double vmax = 0.0;
+#pragma unroll 2
+    for (int q = 0; q < NCC_PER; q++) {
+        const uint32_t j = blockIdx.x * ASX_NCC_CHUNK + q * NCC_NT + threadIdx.x;
+        if (j > jmax) break;
+        const double2 a0 = pa[j], a1 = pa[j + w];
+        const double s1 = a1.x - a0.x;
+        vmax = fmax(vmax, (a1.y - a0.y) - s1 * s1 / dw); // (a NaN drops out)
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, off, 64));
+    // non-negative doubles order as their bits do
+    if ((threadIdx.x & 63) == 0 && vmax > 0.0)
+        atomicMax(reinterpret_cast<unsigned long long *>(R.stat + pair * ASX_NCC_STAT + 1), (unsigned long long)__double_as_longlong(vmax));
+}
+
+// the overlap of the curve's index i in the caller's tracks (no frames: an empty segment, whose coefficient is NaN)
+__device__ __forceinline__ AsxSeg nccrag_seg(uint32_t i, uint32_t N, uint32_t Ls, uint32_t Lm)
+{
+    const int64_t l = (int64_t)i - ((int64_t)N - 1), n0 = l < 0 ? -l : 0, n1 = min((int64_t)Lm, (int64_t)Ls - l);
+    AsxSeg s;
+    s.lag = l;
+    s.peak = i >= N - 1u ? i - (N - 1u) : N + 1u + i;
+    s.flags = 0;
+    s.src_off = s.smp_off = s.len = 0;
+    if (n1 > n0) { s.src_off = (uint32_t)(n0 + l); s.smp_off = (uint32_t)n0; s.len = (uint32_t)(n1 - n0); }
+    return s;
+}
+
+// c_out and keep: as in k_nccfull_peak
+__global__ __launch_bounds__(NCC_NT) void k_nccrag_peak(AsxNccRagWs R, AsxRagLens L, size_t r_pitch, uint32_t N, double scale,
+                                                         double min_energy, int64_t min_overlap, const int64_t *__restrict__ rows,
+                                                         size_t rows_step, float *__restrict__ c_out, size_t c_pitch, bool keep)
+{
+    __shared__ asx_peak_t red[NCC_NT / 64];
+    const size_t pair = blockIdx.y;
+    uint32_t Ls, Lm;
+    asx_nccrag_lens(L, pair, N, Ls, Lm); // (not a pair of lengths: (0, 0), no lag exists)
+    const double *st = R.stat + pair * ASX_NCC_STAT;
+    const double mu = st[0], my = st[2];
+    const double2 *pa = R.pa + pair * (2 * (size_t)N + 1), *pb = R.pb + pair * ((size_t)N + 1);
+    double Vy = 0.0;
+    if (Lm) { const double2 e = pb[Lm]; Vy = e.y - e.x * e.x / (double)Lm; }
+    const double floor_v = min_energy * st[1] * Vy;
+    const int64_t need = min(min_overlap, (int64_t)min(Ls, Lm));
+    const int64_t n1 = (int64_t)N - 1;
+    int64_t lo = -n1, hi = n1;
+    if (rows) {
+        lo = rows[2 * pair * rows_step]; hi = rows[2 * pair * rows_step + 1];
+        if (!asx_nccfull_row_ok(lo, hi, N)) { lo = 1; hi = 0; } // holds no lag
+    }
+    float *ra = R.r + pair * r_pitch, *rl = R.rlo + pair * r_pitch;
+    const uint32_t i0 = blockIdx.x * ASX_NCC_CHUNK, span = 2u * N - 1u;
+    asx_peak_t best = 0;
+#pragma unroll 2
+    for (int j = 0; j < NCC_PER; j++) {
+        const uint32_t i = i0 + j * NCC_NT + threadIdx.x;
+        if (i >= span) break;
+        const int64_t l = (int64_t)i - n1, f0 = l < 0 ? -l : 0, f1 = min((int64_t)Lm, (int64_t)Ls - l), m = f1 - f0;
+        float c32 = NAN;
+        bool competes = false;
+        if (m > 0) {
+            // 0 <= f0 + l < f1 + l <= Ls and 0 <= f0 < f1 <= Lm: inside the tables; r of lag l >= 0 at ra[l], of l < 0 at rl[2N + l]
+            const double2 a0 = pa[f0 + l], a1 = pa[f1 + l], b0 = pb[f0], b1 = pb[f1];
+            const double dm = (double)m, s1x = a1.x - a0.x, s1y = b1.x - b0.x;
+            const double vx = (a1.y - a0.y) - s1x * s1x / dm, vy = (b1.y - b0.y) - s1y * s1y / dm, vv = vx * vy;
+            const double Sx = s1x + dm * mu, Sy = s1y + dm * my;
+            const double r32 = (double)(l >= 0 ? ra[l] : rl[2 * (int64_t)N + l]);
+            const double c = (r32 / scale - Sx * Sy / dm) / sqrt(vv);
+            c32 = (float)c;
+            competes = m >= need && Vy > 0.0 && vv >= floor_v && fabs(c) <= 1.7976931348623157e308;
+        }
+        const float v = competes ? c32 : NAN;
+        if (c_out) c_out[pair * c_pitch + i] = v;
+        if (keep) { if (i < N - 1u) rl[i] = v; else ra[i + 1u] = v; }
+        if (competes && l >= lo && l <= hi) best = peak_max(best, peak_pack_key(fabsf(c32), i));
+    }
+    best = block_peak_max(best, red);
+    if (threadIdx.x == 0 && best) atomicMax(&R.best[pair], best);
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_nccrag_finalize(AsxNccRagWs R, AsxRagLens L, uint32_t N, const int64_t *__restrict__ rows,
+                                                             size_t rows_step, AsxSeg *__restrict__ seg, double *__restrict__ peak,
+                                                             int npairs)
+{
+    const int pair = blockIdx.x * NCC_NT + threadIdx.x;
+    if (pair >= npairs) return;
+    uint32_t Ls, Lm;
+    asx_nccrag_lens(L, (size_t)pair, N, Ls, Lm);
+    const asx_peak_t best = R.best[pair];
+    uint32_t first = 0; // no lag competes: the row's lag_min (a row that is none: the first lag, and the invalid kernels write its results)
+    if (rows) {
+        const int64_t lo = rows[2 * (size_t)pair * rows_step], hi = rows[2 * (size_t)pair * rows_step + 1];
+        if (asx_nccfull_row_ok(lo, hi, N)) first = (uint32_t)(lo + (int64_t)N - 1);
+    }
+    seg[pair] = nccrag_seg(best ? peak_index(best) : first, N, Ls, Lm);
+    peak[pair] = best ? (double)peak_key(best) : 0.0;
+}
+
+// behind k_nccfull_step(j), which left the full-range call's segment of entry j: the ragged one, or an empty one where the record
+// holds no entry j (its coefficient is dropped by the next step)
+__global__ __launch_bounds__(NCC_NT) void k_nccrag_seg(AsxNccRagWs R, AsxRagLens L, uint32_t N, int j, AsxSeg *__restrict__ seg, int npairs)
+{
+    const int pair = blockIdx.x * NCC_NT + threadIdx.x;
+    if (pair >= npairs) return;
+    uint32_t Ls, Lm;
+    asx_nccrag_lens(L, (size_t)pair, N, Ls, Lm);
+    const AsxNccTopk *T = R.tk + pair;
+    const bool have = !T->flags && T->n == (uint32_t)j + 1u;
+    seg[pair] = have ? nccrag_seg((uint32_t)T->lag[j], N, Ls, Lm) : nccrag_seg(N - 1u, N, 0u, 0u);
+}
+
+__global__ __launch_bounds__(NCC_NT) void k_nccrag_invalid(AsxRagLens L, uint32_t N, int k, int64_t *__restrict__ lag,
+                                                            double *__restrict__ coef, double *__restrict__ peak,
+                                                            int32_t *__restrict__ ret, int npairs)
+{
+    const int pair = blockIdx.x * NCC_NT + threadIdx.x;
+    if (pair >= npairs) return;
+    uint32_t Ls, Lm;
+    if (asx_nccrag_lens(L, (size_t)pair, N, Ls, Lm)) return;
+    for (int j = 0; j < k; j++) {
+        const size_t e = (size_t)pair * (size_t)k + (size_t)j;
+        if (lag) lag[e] = 0;
+        coef[e] = (double)NAN;
+        peak[e] = (double)NAN;
+        ret[e] = -5;
+    }
+}
+
+void asx_launch_nccrag_tracks(const AsxNccRagWs &R, const AsxRagLens &L, const float *src, size_t src_pitch, const float *smp,
+                              size_t smp_pitch, uint32_t N, int npairs, hipStream_t s)
+{
+    const unsigned nsc = asx_ncc_chunks(2u * N), nyc = asx_ncc_chunks(N);
+    hipLaunchKernelGGL(k_nccrag_stage, dim3(nsc + nyc, npairs), dim3(NCC_NT), 0, s, R, L, src, src_pitch, smp, smp_pitch, N);
+    hipLaunchKernelGGL(k_nccrag_moments, dim3(nsc + nyc, npairs), dim3(NCC_NT), 0, s, R, L, N);
+    hipLaunchKernelGGL(k_nccrag_prefix, dim3(nsc + nyc, npairs), dim3(NCC_NT), 0, s, R, L, N);
+    hipLaunchKernelGGL(k_nccrag_vmax, dim3(nyc, npairs), dim3(NCC_NT), 0, s, R, L, N);
+}
+
+void asx_launch_nccrag_peak(const AsxNccRagWs &R, const AsxRagLens &L, uint32_t N, double scale, double min_energy, int64_t min_overlap,
+                            const int64_t *rows, size_t rows_step, float *c_out, AsxSeg *seg, double *peak, int npairs, hipStream_t s,
+                            int k)
+{
+    (void)hipMemsetAsync(R.best, 0, (size_t)npairs * sizeof(asx_peak_t), s);
+    hipLaunchKernelGGL(k_nccrag_peak, dim3(asx_ncc_chunks(2u * N - 1u), npairs), dim3(NCC_NT), 0, s, R, L, (size_t)(2u * N), N, scale,
+                       min_energy, min_overlap, rows, rows_step, c_out, (size_t)(2u * N - 1u), k > 1);
+    if (k > 1) return;
+    hipLaunchKernelGGL(k_nccrag_finalize, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, R, L, N, rows, rows_step, seg, peak,
+                       npairs);
+}
+
+void asx_launch_nccrag_seg(const AsxNccRagWs &R, const AsxRagLens &L, uint32_t N, int j, AsxSeg *seg, int npairs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_nccrag_seg, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, R, L, N, j, seg, npairs);
+}
+
+void asx_launch_nccrag_invalid(const AsxRagLens &L, uint32_t N, int k, int64_t *lag, double *coef, double *peak, int32_t *ret, int npairs,
+                               hipStream_t s)
+{
+    hipLaunchKernelGGL(k_nccrag_invalid, dim3((npairs + NCC_NT - 1) / NCC_NT), dim3(NCC_NT), 0, s, L, N, k, lag, coef, peak, ret, npairs);
+}

@@ -72,6 +72,10 @@ _HEADER_SIGNATURES = {
     "asx_xcorr_ncc_full_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_ncc_full_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_ncc_full_debug_c_dev": (_int, [_vp, _vp, _vp, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_ncc_ragged_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "asx_xcorr_ncc_ragged_topk_f32_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _dbl, _i64, _int, _i64, _vp, _vp, _vp,
+                                                 _vp, _vp]),
+    "asx_xcorr_ncc_ragged_debug_c_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "asx_xcorr_pool_ncc_full_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _dbl, _i64, _vp, _vp, _vp, _vp,
                                                _vp]),
     "asx_xcorr_pool_ncc_full_topk_f32_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _dbl, _i64, _int, _i64, _vp,
@@ -138,6 +142,7 @@ _DIAGNOSTIC_SIGNATURES = {
     "asx_plan_debug_bank": (_int, [_vp, _u64p, _u64p, _u64p]),
     "asx_plan_debug_ncc": (_int, [_vp, _u64p]),
     "asx_plan_debug_ncc_full": (_int, [_vp, _u64p]),
+    "asx_plan_debug_ncc_ragged": (_int, [_vp, _u64p]),
     "asx_plan_debug_ncc_tables": (_int, [_vp, _int, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "asx_plan_debug_prune": (_int, [_vp, _sz, c_f32p, c_intp, _sz]),
     "asx_plan_debug_peak": (_int, [_vp, _sz, c_f32p, _u32p, _u32p, _u64p, _vp, _vp, _sz]),
@@ -624,6 +629,52 @@ def ncc_full_topk_args(n, source, sample, k, min_separation, windows=None, min_e
     ncc_full_args' tuple + (k, min_separation).  ValueError on anything else."""
     option = _topk_option(k, min_separation)
     return ncc_full_args(n, source, sample, windows, min_energy, min_overlap) + option
+
+
+def ragged_pack(tracks, width):
+    """1-D arrays of differing sizes -> (float32 [n, width], zero-padded behind each track, and their sizes as int64 [n]): an
+    operand of Plan.xcorr_ncc_ragged_f32 and its column of lengths.  ValueError for a track that is not 1-D, is empty or is longer
+    than width."""
+    rows = [np.asarray(t, dtype=np.float32) for t in tracks]
+    if not rows or any(r.ndim != 1 or not 1 <= r.size <= width for r in rows):
+        raise ValueError("tracks must be 1-D arrays of 1..%d frames each, at least one of them" % width)
+    out = np.zeros((len(rows), int(width)), dtype=np.float32)
+    for i, r in enumerate(rows):
+        out[i, :r.size] = r
+    return out, np.array([r.size for r in rows], dtype=np.int64)
+
+
+def _length_rows(lengths, batch=None):
+    """track lengths -> contiguous int64 [2] or [B, 2] rows (Ls, Lm); batch: the B that a 2-D array must have"""
+    v = np.asarray(lengths)
+    if v.dtype.kind not in "iu":
+        raise ValueError("lengths must hold integers (source frames, sample frames), not %s" % v.dtype)
+    v = np.ascontiguousarray(v, dtype=np.int64)
+    if v.ndim not in (1, 2) or v.shape[-1] != 2 or (batch is not None and v.ndim == 2 and v.shape[0] != batch):
+        raise ValueError("lengths must be [2] or [B, 2]" + ("" if batch is None else " with B = %d pairs" % batch))
+    return v
+
+
+def ncc_ragged_args(n, source, sample, lengths=None, windows=None, min_energy=1e-3, min_overlap=None):
+    """Host checks of Plan.xcorr_ncc_ragged_f32: ncc_full_args' checks, and lengths as None (every pair (2N, N)) or integers [2] /
+    [B, 2] rows (Ls, Lm); a 2-D lengths array counts towards the batch size like the other operands.  -> (source, sample, lengths or
+    None, windows or None, batch, source_stride, sample_stride, length_stride, window_stride, min_energy, min_overlap).  ValueError on
+    anything else.  The rows' values are not checked: a row outside 1 <= Ls <= 2N, 1 <= Lm <= N comes back as ret = -5."""
+    me, mo = _energy_option(min_energy), _overlap_option(n, min_overlap)
+    s, t, ss, ts = _operands(n, source, sample)
+    v = None if lengths is None else _length_rows(lengths)
+    w = None if windows is None else _window_rows(windows)
+    batch = _shared_batch(s, t, v, w)
+    if batch < 1:
+        raise ValueError("empty batch")
+    return (s, t, v, w, batch, ss, ts, 1 if v is not None and v.ndim == 2 else 0, 1 if w is not None and w.ndim == 2 else 0, me, mo)
+
+
+def ncc_ragged_topk_args(n, source, sample, k, min_separation, lengths=None, windows=None, min_energy=1e-3, min_overlap=None):
+    """Host checks of Plan.xcorr_ncc_ragged_topk_f32: ncc_ragged_args' checks, and k and min_separation as topk_args checks them.  ->
+    ncc_ragged_args' tuple + (k, min_separation).  ValueError on anything else."""
+    option = _topk_option(k, min_separation)
+    return ncc_ragged_args(n, source, sample, lengths, windows, min_energy, min_overlap) + option
 
 
 def topk_args(n, source, sample, k, min_separation, windows=None):
@@ -1263,6 +1314,32 @@ class Plan:
                                                     d_c or None, d_lag or None, d_coef or None, d_peak or None, d_ret or None,
                                                     stream or None))
 
+    def xcorr_ncc_ragged_dev(self, d_src, src_stride, d_smp, smp_stride, d_lengths, length_stride, d_windows, window_stride, batch,
+                             min_energy, min_overlap, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_ncc_ragged_f32_dev -- xcorr_ncc_full_dev for pairs whose row (Ls, Lm) of d_lengths says
+        how many frames of their tracks count; d_lengths = 0: (2N, N) for every pair; a row that is no pair of lengths: ret = -5"""
+        _check(lib().asx_xcorr_ncc_ragged_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride),
+                                                  d_lengths or None, int(length_stride), d_windows or None, int(window_stride),
+                                                  int(batch), float(min_energy), int(min_overlap), d_lag or None, d_coef or None,
+                                                  d_peak or None, d_ret or None, stream or None))
+
+    def xcorr_ncc_ragged_topk_dev(self, d_src, src_stride, d_smp, smp_stride, d_lengths, length_stride, d_windows, window_stride, batch,
+                                  min_energy, min_overlap, k, min_separation, d_lag, d_coef, d_peak, d_ret, stream=0):
+        """raw device pointers (ints): asx_xcorr_ncc_ragged_topk_f32_dev -- xcorr_ncc_ragged_dev with the k strongest lags of the signed
+        curve at least min_separation apart, entry j of pair i at index i*k + j of d_lag / d_coef / d_peak / d_ret"""
+        _check(lib().asx_xcorr_ncc_ragged_topk_f32_dev(self._h, d_src or None, int(src_stride), d_smp or None, int(smp_stride),
+                                                       d_lengths or None, int(length_stride), d_windows or None, int(window_stride),
+                                                       int(batch), float(min_energy), int(min_overlap), int(k), int(min_separation),
+                                                       d_lag or None, d_coef or None, d_peak or None, d_ret or None, stream or None))
+
+    def ncc_ragged_debug_c_dev(self, d_src, d_smp, source_len, sample_len, min_energy, min_overlap, d_c, d_lag, d_coef, d_peak, d_ret,
+                               stream=0):
+        """asx_xcorr_ncc_ragged_debug_c_dev: one contiguous pair of the lengths (source_len, sample_len), c32 of the lags -(N-1)..N-1
+        to d_c (2N - 1 floats, lag l at index l + N - 1, NaN where the lag does not exist or does not compete)"""
+        _check(lib().asx_xcorr_ncc_ragged_debug_c_dev(self._h, d_src or None, d_smp or None, int(source_len), int(sample_len),
+                                                      float(min_energy), int(min_overlap), d_c or None, d_lag or None, d_coef or None,
+                                                      d_peak or None, d_ret or None, stream or None))
+
     def xcorr_pool_ncc_full_dev(self, d_sources, source_stride, nsources, d_samples, sample_stride, nsamples, d_pairs, d_windows,
                                 window_stride, batch, min_energy, min_overlap, d_lag, d_coef, d_peak, d_ret, stream=0):
         """raw device pointers (ints): asx_xcorr_pool_ncc_full_f32_dev -- xcorr_pool_ncc_dev over the lags -(N-1)..N-1; every track's
@@ -1496,6 +1573,12 @@ class Plan:
         table) and the sample suffix tables built by the pool full-range calls on this plan so far"""
         c = (ctypes.c_uint64 * 4)()
         _check(lib().asx_plan_debug_ncc_full(self._h, c), "asx_plan_debug_ncc_full failed")
+        return tuple(int(v) for v in c)
+
+    def debug_ncc_ragged(self):
+        """(pairs per group, bytes) of the plan's ragged NCC set; (0, 0) until the plan's first ragged call"""
+        c = (ctypes.c_uint64 * 2)()
+        _check(lib().asx_plan_debug_ncc_ragged(self._h, c), "asx_plan_debug_ncc_ragged failed")
         return tuple(int(v) for v in c)
 
     NCC_TABLE_SETS = {"strided": 0, "pool": 1, "full": 2}
@@ -1775,6 +1858,28 @@ class Plan:
                                                                         min_energy, min_overlap)
         return self._staged((s, t, w), (batch, k), _PHAT_RESULTS, lambda d_s, d_t, d_w, *d_out: self.xcorr_ncc_full_topk_dev(
             d_s, ss, d_t, ts, d_w, ws, batch, me, mo, k, sep, *d_out))
+
+    def xcorr_ncc_ragged_f32(self, source, sample, lengths=None, windows=None, min_energy=1e-3, min_overlap=None):
+        """Pairs of tracks of differing lengths ranked by the normalised cross-correlation over what they really share
+        (asx_xcorr_ncc_ragged_f32_dev).  source, sample, windows, min_energy and min_overlap as in xcorr_ncc_full_f32 (ragged_pack
+        pads tracks to the plan's shape); lengths: None (every pair (2N, N)), or integers [2] / [B, 2] rows (Ls, Lm) -- frames at and
+        beyond them are ignored whatever they hold.  Arguments are checked on the host (ValueError) before anything is uploaded.
+        Returns (lag, coef, peak, ret) as xcorr_ncc_f32; ret = -5 for a row outside 1 <= Ls <= 2N, 1 <= Lm <= N."""
+        s, t, v, w, batch, ss, ts, vs, ws, me, mo = ncc_ragged_args(self.sample_len, source, sample, lengths, windows, min_energy,
+                                                                    min_overlap)
+        return self._staged((s, t, v, w), (batch,), _PHAT_RESULTS, lambda d_s, d_t, d_v, d_w, *d_out: self.xcorr_ncc_ragged_dev(
+            d_s, ss, d_t, ts, d_v, vs, d_w, ws, batch, me, mo, *d_out))
+
+    def xcorr_ncc_ragged_topk_f32(self, source, sample, k, min_separation, lengths=None, windows=None, min_energy=1e-3,
+                                  min_overlap=None):
+        """The k strongest separated lags per pair of the ragged curve (asx_xcorr_ncc_ragged_topk_f32_dev): the arguments of
+        xcorr_ncc_ragged_f32, k and min_separation as in xcorr_topk_f32.  Arguments are checked on the host (ValueError) before
+        anything is uploaded.  Returns (lag, coef, peak, ret) of shape [B, k]; ret = -3 (and NaN for coef and peak) where no lag was
+        left, -5 in all k entries for a row that is no pair of lengths.  Entry 0 is xcorr_ncc_ragged_f32's result."""
+        s, t, v, w, batch, ss, ts, vs, ws, me, mo, k, sep = ncc_ragged_topk_args(self.sample_len, source, sample, k, min_separation,
+                                                                                 lengths, windows, min_energy, min_overlap)
+        return self._staged((s, t, v, w), (batch, k), _PHAT_RESULTS, lambda d_s, d_t, d_v, d_w, *d_out: self.xcorr_ncc_ragged_topk_dev(
+            d_s, ss, d_t, ts, d_v, vs, d_w, ws, batch, me, mo, k, sep, *d_out))
 
     def xcorr_pool_ncc_f32(self, sources, samples, pairs=None, windows=None, min_energy=1e-3):
         """Pairs of two pools ranked by the normalised cross-correlation (asx_xcorr_pool_ncc_f32_dev): the pools and pairs of
